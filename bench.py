@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: book-page images/s, end-to-end detect+recognise @1280x960 (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the whole hot path (CRAFT detect -> boxes -> crops -> CRNN -> CTC) over one batch of
@@ -12,7 +12,7 @@ that is BASELINE.json configs[3] (512 pages sharded across 8 MI355X).  `--config
 instead: 16 dense A4@300dpi scans (2480x3504) per GPU on the fp16 MFMA path.  `--precision` selects bbocr_config::precision; the
 default is "fp16" -- the LIBRARY's default, the one mode whose boxes and strings equalled the fp32 CPU path's on every input class
 measured (synthetic pages, dense A4 scans, the reference's real images).  "mixed" (bf16 detector, 2 % faster, loses
-boxes on continuous-tone inputs) runs as `legs.mixed`.  Every run re-checks identity with the CPU oracle (`parity_in_run`).
+boxes on continuous-tone inputs) runs as `legs.mixed`.  A `--full` run also re-checks identity with the CPU oracle (`parity_in_run`).
 
 Calls in flight: the reference shares ONE Reader between two ThreadPoolExecutor workers (batch_processor_enhanced.py:215); the timed
 region does the same -- `--in-flight 2` (default) worker threads call `readtext_device` on one Reader, libbbocr gives each call its own
@@ -23,13 +23,21 @@ Weights: the designed detector (bb_ocr_amd.weights.designed_craft_state) and the
 synthetic pages (tests/golden/crnn_synth_fp16.npz, tests/golden/train_crnn.py) -- a recogniser that reads the pages has the
 top-2 logit margins of a trained model, so "same text as the fp32 CPU path" is measurable (`parity_in_run`).
 
+A plain run sets up, warms up, times the K steps, writes the last timed step's result if asked and prints the line; everything else
+it can measure or check runs only with `--full` (`--legs` / `--cpu-pages` pick single extras without it).
+
+  --dump-outputs DIR -- after the timed steps, rank 0 writes what the last timed step returned for its pages as DIR/<name>.npy
+                   (boxes, confidences, boxes_per_page, text_codepoints; see dump_outputs): same arguments, same seeded inputs, so
+                   two builds can be compared array for array.
+
 Rank 0 prints ONE JSON line.  Extra objects:
   roofline      -- the dominant kernel (conv_mfma, detector launches): algorithmic FLOPs / sum of launch durations
                    measured with HIP events on the library's stream inside the timed region; peak = 2.5 PFLOP/s dense bf16.
-  cpu_baseline  -- the CPU oracle (restatement of the easyocr algorithm, kind "port") timed on this host, N=1 only.
+  --full only (N=1):
+  cpu_baseline  -- the CPU oracle (restatement of the easyocr algorithm, kind "port") timed on this host.
   parity_in_run -- the SAME pages the CPU oracle just read, compared with what the timed GPU step returned for them:
                    boxes identical n/m, texts identical n/m.
-  legs          -- N=1 only, after the timed region, own readers: `serial` (one call in flight), `mixed`, `exact`, `a4_fp16` (configs[4] share),
+  legs          -- after the timed region, own readers: `serial` (one call in flight), `mixed`, `exact`, `a4_fp16` (configs[4] share),
                    `det_only_b32_bf16` (configs[1], own roofline), `single_page` (the reference's real call: readtext(<jpeg path>), p50 / p95
                    incl. decode + H2D), `host_pages` (64-page batches starting in pinned host memory, H2D overlapped), `lowconf` (faint-ink
                    pages on which upstream's contrast retry is live, compared with the CPU oracle box by box).
@@ -57,6 +65,9 @@ CONFIGS = {   # BASELINE.json configs -> (page W, H, batch per GPU, text lines, 
 TRAINED_CRNN = os.path.join(ROOT, "tests", "golden", "crnn_synth_fp16.npz")
 METRIC = {"p1": "book-page images/sec end-to-end (detect+recognize) @1280x960",
           "a4": "A4@300dpi page images/sec end-to-end (detect+recognize) @2480x3504, fp16 MFMA conv path (BASELINE.json configs[4], per-GPU share)"}
+FULL_LEGS = "serial,mixed,exact,exact_rec,a4,det_only,single_page,host_pages,lowconf,preprocess,extractor"     # --full's --legs
+FULL_CPU_PAGES = 16                                                                                            # --full's --cpu-pages
+DUMP_LIMIT_BYTES = 64 << 20
 DTYPE = {"bf16": "bf16", "fp16": "fp16", "exact": "fp16 (split hi+lo operands, three MFMA product terms per layer, in both networks)", "mixed": "bf16 (detector) + fp16 (recogniser)",
          "exact_rec": "fp16 (detector) + split fp16 hi+lo operands (recogniser)"}
 
@@ -408,7 +419,7 @@ def leg_lowconf(reader, states, n_gpu_pages=16, n_cpu_pages=2, steps=3):
 
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=6)
@@ -421,9 +432,14 @@ def main():
     ap.add_argument("--lines", type=int, default=0, help="text lines per page (0 = the config's: 24 / 110, SURVEY.md section 8d)")
     ap.add_argument("--precision", choices=("bf16", "fp16", "exact", "mixed", "exact_rec"), default=None, help="bbocr_config::precision (default: the config's)")
     ap.add_argument("--rec-weights", choices=("trained", "random"), default="trained", help="recogniser: tests/golden/crnn_synth_fp16.npz or seeded random")
-    ap.add_argument("--cpu-pages", type=int, default=16, help="pages for the CPU-oracle baseline + parity_in_run after one warm-up page (0 = skip)")
-    ap.add_argument("--legs", default="serial,mixed,exact,exact_rec,a4,det_only,single_page,host_pages,lowconf,preprocess,extractor",
-                    help="N=1: extra legs run after the timed region (comma list of serial, fp16, mixed, bf16, exact, exact_rec, a4, det_only, single_page, host_pages, lowconf, preprocess, extractor; '' = none)")
+    ap.add_argument("--full", action="store_true", help="N=1: after the timed region also run every leg, the CPU-oracle baseline and parity_in_run "
+                                                        "(the defaults of --legs / --cpu-pages; a plain run does neither)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's result (rank 0's pages) as DIR/<name>.npy")
+    ap.add_argument("--cpu-pages", type=int, default=None, help="pages for the CPU-oracle baseline + parity_in_run after one warm-up page "
+                                                                f"(0 = skip; default {FULL_CPU_PAGES} with --full, else 0)")
+    ap.add_argument("--legs", default=None,
+                    help="N=1: extra legs run after the timed region (comma list of serial, fp16, mixed, bf16, exact, exact_rec, a4, det_only, single_page, host_pages, "
+                         "lowconf, preprocess, extractor; '' = none; default: every leg with --full, else none)")
     ap.add_argument("--leg-steps", type=int, default=6)
     ap.add_argument("--in-flight", type=int, default=2, help="calls in flight on the one Reader during the timed region (worker threads; bbocr_config::call_slots = 2)")
     ap.add_argument("--det-sub-batch", type=int, default=0)
@@ -432,12 +448,22 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL; gloo only for single-GPU rehearsals)")
     ap.add_argument("--allow-local-weights", action="store_true", help="N > 1: if the packed weight broadcast fails, build the seeded weights on every rank "
                                                                        "and continue (reported as weights_broadcast_ok false) instead of exiting non-zero")
-    args = ap.parse_args()
-    cw, ch, cb, cl, cpitch, cprec, workload = CONFIGS[args.config]
+    args = ap.parse_args(argv)
+    if args.legs is None:
+        args.legs = FULL_LEGS if args.full else ""
+    if args.cpu_pages is None:
+        args.cpu_pages = FULL_CPU_PAGES if args.full else 0
+    cw, ch, cb, cl, _, cprec, _ = CONFIGS[args.config]
     args.width, args.height = args.width or cw, args.height or ch
     args.batch, args.lines = args.batch or cb, args.lines or cl
     args.precision = args.precision or cprec
     args.unique = args.unique or args.batch
+    return args
+
+
+def main():
+    args = parse_args()
+    workload = CONFIGS[args.config][6]
 
     import numpy as np
     import torch
@@ -549,6 +575,9 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        kept = dump_outputs(args.dump_outputs, out)
+        log(f"last timed step's result for {kept} of {len(out)} pages written to {args.dump_outputs}")
 
     pages = B * world * args.steps
     result = {
@@ -577,7 +606,7 @@ def main():
         "stage_ms_per_step_rank0": {k: v / args.steps for k, v in stage.items()},
         "stage_ms_note": ("per CALL, from device events and host clocks inside that call; with more than one call in flight the stages of different calls overlap "
                           "(their sum exceeds ms_per_step) and a stage queued behind the other call's detector includes that wait -- "
-                          "legs.serial holds the one-call-at-a-time breakdown") if args.in_flight > 1 else "one call at a time",
+                          "legs.serial of a --full run holds the one-call-at-a-time breakdown") if args.in_flight > 1 else "one call at a time",
         "roofline": rf,
     }
     if world > 1:
@@ -653,6 +682,34 @@ def parity(ref_pages, gpu_pages, mode):
             "pages_identical": f"{pages_same}/{len(ref_pages)}", "all_identical": bool(same_boxes == boxes and same_text == boxes),
             "first_text_difference": worst,
             "what": "oracle.pipeline.OracleReader.readtext (fp32 CPU) vs the last timed GPU step's result for the same pages: box coordinates equal as numbers, decoded strings equal"}
+
+
+def dump_outputs(directory, pages, limit=DUMP_LIMIT_BYTES):
+    """What a caller of the timed path receives -- per page a list of (box, text, confidence) -- as float arrays, written to
+    directory/<name>.npy:
+      boxes           (n, 4, 2) float64  corner coordinates, pages in order, boxes in the order returned
+      confidences     (n,)      float64
+      boxes_per_page  (pages,)  float64  how the n boxes split over the pages
+      text_codepoints (n, L)    float32  Unicode code points of each box's text, 0-padded to the longest text L
+    If the arrays would exceed `limit` bytes, the trailing half of the pages is dropped until they fit.  -> pages written."""
+    import numpy as np
+
+    while True:
+        flat = [item for pg in pages for item in pg]
+        width = max((len(t) for _, t, _ in flat), default=0)
+        arrays = {
+            "boxes": np.array([b for b, _, _ in flat], dtype=np.float64).reshape(len(flat), 4, 2),
+            "confidences": np.array([c for _, _, c in flat], dtype=np.float64),
+            "boxes_per_page": np.array([len(pg) for pg in pages], dtype=np.float64),
+            "text_codepoints": np.array([[ord(ch) for ch in t] + [0] * (width - len(t)) for _, t, _ in flat], dtype=np.float32).reshape(len(flat), width),
+        }
+        if sum(a.nbytes for a in arrays.values()) <= limit or len(pages) <= 1:
+            break
+        pages = pages[: len(pages) // 2]
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+    return len(pages)
 
 
 def host_cores():

@@ -28,8 +28,8 @@ sys.path.insert(0, ROOT)
 
 REF_JSON = "/root/reference/pipeline_components/img_to_json/ocr_testing/results/json"
 PAIRS = {  # json name -> (input image relative to the reference root, committed copy or None)
-    "ocr_comparison_IMG_9684.json": ("pipeline_demo/books/2a/IMG_9684.JPG", None),
-    "ocr_comparison_IMG_9685.json": ("pipeline_demo/books/2a/IMG_9685.JPG", None),
+    "ocr_comparison_IMG_9684.json": ("pipeline_demo/books/2a/IMG_9684.JPG", "photos/IMG_9684.JPG"),
+    "ocr_comparison_IMG_9685.json": ("pipeline_demo/books/2a/IMG_9685.JPG", "photos/IMG_9685.JPG"),
     "ocr_comparison_book1.json": ("pipeline_components/img_to_json/ocr_testing/results/images/book1_preprocessed.png", "ref_images/book1_preprocessed.png"),
     "ocr_comparison_book2.json": ("pipeline_components/img_to_json/ocr_testing/results/images/book2_preprocessed.png", "ref_images/book2_preprocessed.png"),
     "ocr_comparison_book4.json": ("pipeline_components/img_to_json/ocr_testing/results/images/book4_preprocessed.png", "ref_images/book4_preprocessed.png"),

@@ -14,18 +14,14 @@ needs_weights = pytest.mark.skipif(not (WDIR and os.path.exists(os.path.join(WDI
 
 
 def _image_path(pair):
-    if pair["committed_copy"]:
-        return os.path.join(HERE, "golden", pair["committed_copy"])
-    p = os.path.join("/root/reference", pair["image"])
-    return p if os.path.exists(p) else None
+    return os.path.join(HERE, "golden", pair["committed_copy"])
 
 
 def test_pairs_file_is_consistent():
     assert len(PAIRS) == 7
     for p in PAIRS:
         assert len(p["easyocr_text"]) == p["text_length"]
-        if p["committed_copy"]:
-            assert os.path.exists(os.path.join(HERE, "golden", p["committed_copy"]))
+        assert os.path.exists(_image_path(p))                 # every input image is committed under tests/golden
 
 
 @needs_weights
@@ -37,8 +33,6 @@ def test_oracle_reproduces_reference_text(pair):
     from oracle import pipeline
 
     path = _image_path(pair)
-    if path is None:
-        pytest.skip("input image not present on this machine")
     cs, rs = weights.load_checkpoint_dir(WDIR)
     ref = pipeline.OracleReader({k: torch.from_numpy(v) for k, v in cs.items()}, {k: torch.from_numpy(v) for k, v in rs.items()})
     text = " ".join(r[1] for r in ref.readtext(path))
@@ -52,8 +46,6 @@ def test_hip_backend_reproduces_reference_text(pair):
     import bb_ocr_amd
 
     path = _image_path(pair)
-    if path is None:
-        pytest.skip("input image not present on this machine")
     reader = bb_ocr_amd.Reader(["en"], model_storage_directory=WDIR)
     text = " ".join(r[1] for r in reader.readtext(path, paragraph=False, batch_size=1, workers=0))
     assert text == pair["easyocr_text"]
