@@ -107,6 +107,9 @@ PROTOTYPES = {
     "bbocr_preproc_defaults": (None, [C.POINTER(bbocr_preproc_params), C.c_int]),
     "bbocr_preprocess_chain": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(bbocr_preproc_params), _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bbocr_op_preprocess_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double]),
+    "bbocr_auto_crop": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "bbocr_op_autocrop_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, _vp]),
 }
 
 _lib = None

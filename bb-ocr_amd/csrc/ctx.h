@@ -157,6 +157,7 @@ struct bbocr_ctx : WeightView {
     bool slot_busy = false;                   // this slot is running a call
     hipStream_t stream = nullptr;             // the compute stream (root's; slots share it: kernels of concurrent calls run in issue order)
     DevBuf pp_gray, pp_a, pp_b, pp_c, pp_tab;  // pre-processing chain (f2): planes and small tables
+    DevBuf ac_work;                            // text-region auto-crop (autocrop.cpp): planes, packed masks, labels, boxes
     DevBuf pp_cubic;                           // cubic-resize weight tables, kept on the device while (W, dw, H, dh) repeats
     int pp_cubic_key[4] = {0, 0, 0, 0};
     unsigned long long pp_cubic_K[2] = {0, 0};
@@ -336,6 +337,7 @@ const uint8_t* pp_fold_lut(bbocr_ctx* c, size_t n, double contrast, double brigh
 void pp_clahe(bbocr_ctx* c, const uint8_t* src, int H, int W, const uint8_t* d_lut, uint8_t* dst, double clip_limit);
 void pp_unsharp(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, uint8_t* tmp1, uint8_t* tmp2, float radius, int percent, int threshold);
 void preprocess_chain_impl(bbocr_ctx* c, const uint8_t* bgr, int H, int W, const bbocr_preproc_params& q, uint8_t* out, int dh, int dw);
+void gaussian_taps_fixed(int n, double sigma, int* k);   // autocrop.cpp
 
 // worker threads of this slot: bbocr_config::host_threads, or min(16, the process's CPU share); the pool is made once and kept
 inline HostPool& host_pool(bbocr_ctx* c) {

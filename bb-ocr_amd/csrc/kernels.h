@@ -181,3 +181,16 @@ bool pp_unsharp_fused_ok(int H, int W, int r, const uint8_t* a, const uint8_t* b
 hipError_t launch_pp_unsharp_fused(const uint8_t* in, uint8_t* tmp, uint8_t* dst, int H, int W, unsigned int ww, unsigned int fw, int percent,
                                    int threshold, hipStream_t s);
 hipError_t launch_pp_unsharp(const uint8_t* in, const uint8_t* blur, uint8_t* dst, size_t total, int percent, int threshold, hipStream_t s);
+
+// ------------------------------------------------------------------ text-region auto-crop (autocrop.hip), enhanced_extractor.py::_auto_crop_text_region
+constexpr int AC_BOX = 35, AC_BOX_R = 17, AC_MEAN_C = 10;     // adaptiveThreshold MEAN: block 35, C 10
+constexpr int AC_GAU = 31, AC_GAU_R = 15, AC_GAU_C = 5;       // adaptiveThreshold GAUSSIAN: block 31, C 5
+struct AcTaps { int k[AC_GAU]; };                             // 8.8 fixed-point Gaussian taps (sum 256)
+hipError_t launch_ac_gray_blur(const uint8_t* src, int H, int W, size_t pitch, int channels, uint8_t* dst, hipStream_t s);
+hipError_t launch_ac_cues(const uint8_t* e, int H, int W, const AcTaps& taps, uint16_t* rbox, uint16_t* rgau, uint8_t* part, uint8_t* grad,
+                          unsigned int* hist, int* thr, hipStream_t s);
+hipError_t launch_ac_pack(const uint8_t* e, const uint8_t* part, const uint8_t* grad, const int* thr, int H, int W, int WW, uint32_t* bits, hipStream_t s);
+hipError_t launch_ac_rect(const uint32_t* src, uint32_t* tmp, uint32_t* dst, int H, int W, int WW, int rx, int ry, int erode, const uint32_t* or_with,
+                          hipStream_t s);
+hipError_t launch_ac_components(const uint32_t* bits, int H, int W, int WW, int* label, uint8_t* flag, int* count, int cap, int* boxes, hipStream_t s);
+hipError_t launch_ac_unpack(const uint32_t* bits, const int* label, int H, int W, int WW, uint8_t* dst, hipStream_t s);

@@ -6,8 +6,10 @@
 exception to the empty string (:529-531).  ``extract_texts`` does the same for ALL pages of a book (or of many books) with ONE
 ``readtext_batched`` call per page shape, so the backend sees 64-page batches instead of single pages.
 
-Only the OCR step is batched; cropping / LLM steps of the extractor stay where they are.  The down-scaling rule is restated
-exactly, including its JPEG round trip (the reference writes the thumbnail as JPEG quality 90/95 and lets easyocr decode it).
+The LLM steps of the extractor stay where they are.  The optional OCR-input steps in front of the down-scaling (:425-485) run on
+the card when asked for: ``use_preprocessing`` (f2, csrc/preproc.hip), ``edge_crop_percent`` (a strided view, no copy) and
+``crop_for_ocr`` (the text-region auto-crop, csrc/autocrop.hip); only the final crop is downloaded.  The down-scaling rule is
+restated exactly, including its JPEG round trip (the reference writes the thumbnail as JPEG quality 90/95 and lets easyocr decode it).
 """
 from __future__ import annotations
 
@@ -43,6 +45,51 @@ def _ocr_input(image_path, image_index=None, decode_once=True):
     return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(reformat_input(os.fspath(image_path)))
 
 
+def _ocr_input_array(page, image_index=None, decode_once=True):
+    """``_ocr_input`` for a page the reference would have written as a PNG (its pre-processed / cropped file): gray [H,W] or BGR
+    [H,W,3] uint8.  Gray pages are read back as three equal channels, so the RGB thumbnail is the gray one replicated."""
+    from PIL import Image
+
+    from .reader import decode_file, decode_file_ycc
+
+    cover = image_index is None or image_index == 0
+    max_dim = 1600 if cover else 2400
+    rgb = np.ascontiguousarray(np.repeat(page[:, :, None], 3, axis=2) if page.ndim == 2 else page[:, :, ::-1])
+    if max(page.shape[0], page.shape[1]) > max_dim:
+        img = Image.fromarray(rgb)
+        img.thumbnail((max_dim, max_dim))
+        buf = io.BytesIO()
+        img.save(buf, format="JPEG", quality=(90 if cover else 95))
+        data = buf.getvalue()
+        ycc = decode_file_ycc(data, padded=True) if decode_once else None
+        return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(data))
+    if page.ndim == 2:
+        return ("rgb", rgb, np.ascontiguousarray(page))
+    buf = io.BytesIO()                                            # a colour page: through the PNG file the reference writes
+    Image.fromarray(rgb).save(buf, format="PNG")
+    return ("rgb",) + tuple(decode_file(buf.getvalue()))
+
+
+def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128):
+    """The page ``extract_text_with_ocr`` would hand to the down-scaling step (:425-485), as a host array: decoded like ``cv2.imread``
+    (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
+    final crop comes back.  A step that returns None in the reference leaves the page as it was."""
+    from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, preprocess_bgr_device
+
+    page = reader._to_dev(_imread_bgr(image_path))
+    if use_preprocessing:
+        page = preprocess_bgr_device(reader, page)
+    if edge_crop_percent > 0.0:
+        b = central_edge_crop_box(page.shape[0], page.shape[1], edge_crop_percent)
+        if b is not None:
+            page = page[b[1]:b[3], b[0]:b[2]]
+    if crop_for_ocr:
+        b = auto_crop_box_device(reader, page, crop_margin)
+        if b is not None:
+            page = page[b[1]:b[3], b[0]:b[2]]
+    return page.contiguous().cpu().numpy()
+
+
 def ocr_input_image(image_path, image_index=None):
     """The pixels ``extract_text_with_ocr`` hands to easyocr for ``image_path`` (enhanced_extractor.py:486-512): pages whose
     longer side exceeds 1600 px (cover, ``image_index`` None or 0) / 2400 px (other pages) are ``Image.thumbnail``-ed to that
@@ -67,12 +114,23 @@ def ocr_input_image(image_path, image_index=None):
     return reformat_input(os.fspath(image_path))
 
 
-def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, **readtext_kw):
+def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
+                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
-    batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step)."""
-    res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers,
-                     decode=lambda path, i: _ocr_input(path, i, decode_once), **readtext_kw)
+    batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
+    ``use_preprocessing`` / ``edge_crop_percent`` / ``crop_for_ocr`` / ``crop_margin``: the extractor's settings of the same names
+    (``ocr_page_crop``); with all of them off the pages are read as before."""
+    if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
+        if crop_margin < 0:
+            raise ValueError("crop_margin must be >= 0")
+
+        def decode(path, i):
+            page = ocr_page_crop(reader, path, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin)
+            return _ocr_input_array(page, i, decode_once)
+    else:
+        decode = lambda path, i: _ocr_input(path, i, decode_once)
+    res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, **readtext_kw)
     return {i: " ".join(t[1] for t in r) for i, r in res.items()}
 
 

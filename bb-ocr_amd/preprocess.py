@@ -79,3 +79,88 @@ def preprocess_for_book_cover(image_path, output_path=None, reader=None, legacy=
         os.makedirs(os.path.dirname(output_path) or ".", exist_ok=True)
         Image.fromarray(out).save(output_path)
     return out, output_path, list(LEGACY_STEPS if legacy else STEPS)
+
+
+# ------------------------------------------------------------------------------------------------ crops of the extractor's OCR input
+def central_edge_crop_box(h, w, percent):
+    """``_central_edge_crop`` (enhanced_extractor.py:374-397) as a box: ``(x0, y0, x1, y1)`` with ``percent`` removed from every edge,
+    or None where the reference returns None (``percent <= 0``, or what is left is narrower than max(16, 20 %) on either axis)."""
+    if percent <= 0.0:
+        return None
+    mx = int(round(w * (percent / 100.0)))
+    my = int(round(h * (percent / 100.0)))
+    x0, y0 = max(0, mx), max(0, my)
+    x1, y1 = min(w, w - mx), min(h, h - my)
+    if x1 - x0 < max(16, w * 0.2) or y1 - y0 < max(16, h * 0.2):
+        return None
+    return (x0, y0, x1, y1)
+
+
+def _page_layout(reader, page_dev):
+    """(H, W, row pitch in bytes, channels) of a uint8 gray [H,W] or BGR [H,W,3] device tensor, strided views included."""
+    import torch
+
+    if not isinstance(page_dev, torch.Tensor) or page_dev.dtype != torch.uint8 or page_dev.ndim not in (2, 3):
+        raise ValueError("expected a uint8 gray [H,W] or BGR [H,W,3] device tensor")
+    if not page_dev.is_cuda or page_dev.device.index != reader.device_index:
+        raise ValueError(f"expected a tensor on {reader.device}")
+    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
+    ch = 1 if page_dev.ndim == 2 else int(page_dev.shape[2])
+    st = page_dev.stride()
+    if ch not in (1, 3) or st[1] != ch or (ch == 3 and st[2] != 1) or H < 1 or W < 1 or st[0] < W * ch:
+        raise ValueError("expected rows of packed pixels (gray, or interleaved BGR) with a row stride of at least one row")
+    return H, W, int(st[0]), ch
+
+
+def auto_crop_box_device(reader, page_dev, margin=128, with_components=False):
+    """``_auto_crop_text_region`` (enhanced_extractor.py:239-372) on the device: the crop box ``(x0, y0, x1, y1)`` of a uint8 gray
+    [H,W] or BGR [H,W,3] tensor on the reader's device (a strided view such as an edge crop of a larger page is read in place), or None
+    where the reference returns None.  ``with_components=True`` also returns the kept component boxes ``(x, y, w, h)`` sorted by (y, x)."""
+    if int(margin) < 0:
+        raise ValueError("margin must be >= 0")
+    H, W, pitch, ch = _page_layout(reader, page_dev)
+    box = (C.c_int * 4)()
+    found, n = C.c_int(), C.c_int()
+    cap = 4096
+    while True:
+        comps = (C.c_int * (4 * cap))()
+        reader._check(reader._lib.bbocr_auto_crop(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, pitch, ch, int(margin), box, C.byref(found),
+                                                  comps, cap, C.byref(n)))
+        if n.value <= cap or not with_components:
+            break
+        cap = n.value
+    out = tuple(box) if found.value else None
+    if with_components:
+        return out, [tuple(comps[4 * k:4 * k + 4]) for k in range(n.value)]
+    return out
+
+
+def _read_page(image_path_or_array):
+    if isinstance(image_path_or_array, np.ndarray):
+        return np.ascontiguousarray(image_path_or_array)
+    if not os.path.exists(image_path_or_array):
+        return None                                                   # cv2.imread -> None -> the reference returns None
+    return _imread_bgr(image_path_or_array)
+
+
+def auto_crop_text_region(image_path_or_array, margin=128, reader=None):
+    """Drop-in for ``_auto_crop_text_region(image_path, margin)``: the cropped page (an array, where the reference writes it to a PNG
+    and returns the path) or None.  A path is decoded like ``cv2.imread`` (BGR, EXIF-transposed); an array may be gray or BGR."""
+    if reader is None:
+        raise ValueError("auto_crop_text_region needs a bb_ocr_amd.Reader (device context)")
+    img = _read_page(image_path_or_array)
+    if img is None:
+        return None
+    b = auto_crop_box_device(reader, reader._to_dev(img), margin)
+    return None if b is None else img[b[1]:b[3], b[0]:b[2]].copy()
+
+
+def central_edge_crop(image_path_or_array, percent):
+    """Drop-in for ``_central_edge_crop(image_path, percent)``: the cropped page (an array) or None."""
+    if percent <= 0.0:
+        return None
+    img = _read_page(image_path_or_array)
+    if img is None:
+        return None
+    b = central_edge_crop_box(img.shape[0], img.shape[1], percent)
+    return None if b is None else img[b[1]:b[3], b[0]:b[2]].copy()

@@ -298,6 +298,19 @@ int bbocr_preprocess_chain(bbocr_ctx* ctx, const uint8_t* dev_bgr, int H, int W,
  * arrays), 7 = PIL UnsharpMask (radius 1, `param` %, threshold 3).  Stages 1-7 keep the size (dh = H, dw = W). */
 int bbocr_op_preprocess_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, uint8_t* dev_dst, int dh, int dw, double param);
 
+/* ---- text-region auto-crop (enhanced_extractor.py::_auto_crop_text_region, the extractor's `crop_for_ocr`) of one u8 page on the
+ * device: gray [H,W] (channels 1) or BGR [H,W,3] (channels 3), rows `pitch` bytes apart (a crop of a larger plane is passed as a
+ * pointer + pitch).  box = (x0, y0, x1, y1) of the crop with `margin` applied, *found = 0 when the reference returns None (then box is
+ * zeros).  comp_boxes receives min(*n_comps, max_comps) kept component boxes (x, y, w, h), sorted by (y, x); comp_boxes may be null
+ * when max_comps is 0.  A pipeline call: runs in a call slot next to readtext calls, returns with its work finished.  BBOCR_ERR_ARG,
+ * before anything is queued: null pointers, H or W < 1, pitch < W * channels, channels not 1 or 3, margin < 0, a page smaller than
+ * the 8x8 CLAHE grid allows. */
+int bbocr_auto_crop(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int channels, int margin, int box[4], int* found,
+                    int* comp_boxes, int max_comps, int* n_comps);
+/* its intermediates as u8 [H,W] in dev_dst (parity tests): stage 0 = CLAHE output, 1 = composite threshold mask (0/255), 2 = merged
+ * morphology mask, 3 = pixels of the external (RETR_EXTERNAL) components of the merged mask */
+int bbocr_op_autocrop_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int channels, uint8_t* dev_dst);
+
 #ifdef __cplusplus
 }
 #endif
