@@ -110,6 +110,16 @@ PROTOTYPES = {
     "bbocr_auto_crop": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "bbocr_op_autocrop_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, _vp]),
+    "bbocr_ocr_thumbnail": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int)]),
+    "bbocr_op_thumbnail_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_thumbnail_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_host_thumbnail_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "bbocr_host_resample_coeffs": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                             C.POINTER(C.c_int)]),
+    "bbocr_host_jpeg_qtables": (C.c_int, [C.c_int, C.POINTER(C.c_uint16)]),
 }
 
 _lib = None

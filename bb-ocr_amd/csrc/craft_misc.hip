@@ -139,19 +139,11 @@ __global__ void __launch_bounds__(256) ycc_to_rgb_gray_kernel(const uint8_t* __r
         int y, cb, cr;
         if (stride == 4) {
             const unsigned int p = ((const unsigned int*)ycc)[i];
-            y = (int)(p & 255u); cb = (int)((p >> 8) & 255u) - 128; cr = (int)((p >> 16) & 255u) - 128;
+            y = (int)(p & 255u); cb = (int)((p >> 8) & 255u); cr = (int)((p >> 16) & 255u);
         } else {
-            y = ycc[i * 3]; cb = (int)ycc[i * 3 + 1] - 128; cr = (int)ycc[i * 3 + 2] - 128;
+            y = ycc[i * 3]; cb = ycc[i * 3 + 1]; cr = ycc[i * 3 + 2];
         }
-        int r = y + ((91881 * cr + 32768) >> 16);
-        int g = y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-        int b = y + ((116130 * cb + 32768) >> 16);
-        r = r < 0 ? 0 : (r > 255 ? 255 : r);
-        g = g < 0 ? 0 : (g > 255 ? 255 : g);
-        b = b < 0 ? 0 : (b > 255 ? 255 : b);
-        rgb[i * 3] = (uint8_t)r;
-        rgb[i * 3 + 1] = (uint8_t)g;
-        rgb[i * 3 + 2] = (uint8_t)b;
+        jpeg_ycc_to_rgb(y, cb, cr, rgb + i * 3);
         if (gray) gray[i] = (uint8_t)y;
     }
 }

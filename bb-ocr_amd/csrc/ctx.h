@@ -158,6 +158,10 @@ struct bbocr_ctx : WeightView {
     hipStream_t stream = nullptr;             // the compute stream (root's; slots share it: kernels of concurrent calls run in issue order)
     DevBuf pp_gray, pp_a, pp_b, pp_c, pp_tab;  // pre-processing chain (f2): planes and small tables
     DevBuf ac_work;                            // text-region auto-crop (autocrop.cpp): planes, packed masks, labels, boxes
+    DevBuf th_coef;                            // OCR-input thumbnail (thumb.cpp): resample tables, kept while the geometry repeats
+    int th_coef_key[6] = {0, 0, 0, 0, 0, 0};
+    int th_coef_ks[2] = {0, 0};
+    int th_coef_rows[2] = {0, 0};
     DevBuf pp_cubic;                           // cubic-resize weight tables, kept on the device while (W, dw, H, dh) repeats
     int pp_cubic_key[4] = {0, 0, 0, 0};
     unsigned long long pp_cubic_K[2] = {0, 0};

@@ -84,6 +84,17 @@ hipError_t launch_maxpool(const uint16_t* in, uint16_t* out, int N, int H, int W
                           int relu_in, hipStream_t s);
 hipError_t launch_gray(const uint8_t* rgb, uint8_t* gray, size_t npix, hipStream_t s);
 hipError_t launch_ycc_to_rgb_gray(const uint8_t* ycc, int stride, uint8_t* rgb, uint8_t* gray, size_t npix, hipStream_t s);
+// jdcolor.c::ycc_rgb_convert of one pixel (the formulas are stated at ycc_to_rgb_gray_kernel, craft_misc.hip); also thumb.hip's last pass
+__device__ __forceinline__ void jpeg_ycc_to_rgb(int y, int cb, int cr, uint8_t* rgb) {
+    cb -= 128;
+    cr -= 128;
+    int r = y + ((91881 * cr + 32768) >> 16);
+    int g = y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    int b = y + ((116130 * cb + 32768) >> 16);
+    rgb[0] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
+    rgb[1] = (uint8_t)(g < 0 ? 0 : (g > 255 ? 255 : g));
+    rgb[2] = (uint8_t)(b < 0 ? 0 : (b > 255 ? 255 : b));
+}
 hipError_t launch_resize_u8(const uint8_t* src, int N, int sh, int sw, int C, uint8_t* dst, int dh, int dw, hipStream_t s);
 
 // ------------------------------------------------------------------ exact detector, element-wise helpers on pair tensors (craft_pair.hip)
@@ -194,3 +205,19 @@ hipError_t launch_ac_rect(const uint32_t* src, uint32_t* tmp, uint32_t* dst, int
                           hipStream_t s);
 hipError_t launch_ac_components(const uint32_t* bits, int H, int W, int WW, int* label, uint8_t* flag, int* count, int cap, int* boxes, hipStream_t s);
 hipError_t launch_ac_unpack(const uint32_t* bits, const int* label, int H, int W, int WW, uint8_t* dst, hipStream_t s);
+
+// ------------------------------------------------------------------ OCR-input thumbnail + JPEG round trip (thumb.hip), enhanced_extractor.py:486-512
+enum : int { TH_GRAY = 0, TH_BGR = 1, TH_RGB = 2, TH_YCC4 = 3, TH_YCC3 = 4 };   // bbocr.h BBOCR_PAGE_*
+constexpr int TH_PRECISION_BITS = 22;                                             // Pillow Resample.c, 8 bpc
+struct ThQuant { unsigned short q[2][64]; };                                       // luminance, chrominance (natural order)
+hipError_t launch_th_reduce(const uint8_t* src, size_t pitch, int layout, int H, int W, int fx, int fy, uint8_t* dst, int rh, int rw, int C,
+                            hipStream_t s);
+hipError_t launch_th_resample_h(const uint8_t* src, size_t pitch, int layout, int y0, int rows, int ow, int C, const int* bounds, const int* kk,
+                                int ksize, uint8_t* dst, hipStream_t s);
+hipError_t launch_th_resample_v(const uint8_t* src, size_t spitch, int y0, int width, int oh, const int* bounds, const int* kk, int ksize,
+                                uint8_t* dst, size_t dpitch, hipStream_t s);
+hipError_t launch_th_jpeg(const uint8_t* src, size_t pitch, int C, int H, int W, const ThQuant& q, uint8_t* yp, int wp, uint8_t* cbp, uint8_t* crp,
+                          hipStream_t s);
+hipError_t launch_th_upsample(const uint8_t* yp, int wp, const uint8_t* cbp, const uint8_t* crp, int H, int W, int gray_only, uint8_t* rgb,
+                              uint8_t* gray, uint8_t* ycc, hipStream_t s);
+hipError_t launch_th_direct(const uint8_t* src, size_t pitch, int layout, int H, int W, uint8_t* rgb, uint8_t* gray, hipStream_t s);

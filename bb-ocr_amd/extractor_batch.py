@@ -70,10 +70,26 @@ def _ocr_input_array(page, image_index=None, decode_once=True):
     return ("rgb",) + tuple(decode_file(buf.getvalue()))
 
 
-def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128):
+def _ocr_input_device(reader, image_path, image_index=None, decode_once=True):
+    """``_ocr_input`` with the down-scaling on the card: a YCbCr-coded JPEG above the page's limit is decoded once on the host, uploaded
+    and thumbnailed + JPEG round-tripped on the device (``("dev", rgb_dev, gray_dev)``); every other file takes ``_ocr_input``."""
+    from .preprocess import ocr_input_ycc_device, ocr_thumbnail_rule
+    from .reader import decode_file_ycc
+
+    m, _ = ocr_thumbnail_rule(image_index)
+    ycc = decode_file_ycc(os.fspath(image_path), padded=True)
+    if ycc is None:
+        return _ocr_input(image_path, image_index, decode_once)        # PNG, gray or CMYK JPEG, ...: the host path
+    if max(ycc.shape[0], ycc.shape[1]) <= m:
+        return "ycc", ycc, None                                       # no thumbnail: what _ocr_input returns for it
+    return ("dev",) + tuple(ocr_input_ycc_device(reader, reader._to_dev(ycc), image_index))
+
+
+def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, on_device=False):
     """The page ``extract_text_with_ocr`` would hand to the down-scaling step (:425-485), as a host array: decoded like ``cv2.imread``
     (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
-    final crop comes back.  A step that returns None in the reference leaves the page as it was."""
+    final crop comes back.  A step that returns None in the reference leaves the page as it was.  ``on_device=True``: the crop stays on
+    the card, as a (possibly strided) view of the device page."""
     from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, preprocess_bgr_device
 
     page = reader._to_dev(_imread_bgr(image_path))
@@ -87,6 +103,8 @@ def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent
         b = auto_crop_box_device(reader, page, crop_margin)
         if b is not None:
             page = page[b[1]:b[3], b[0]:b[2]]
+    if on_device:
+        return page
     return page.contiguous().cpu().numpy()
 
 
@@ -115,19 +133,27 @@ def ocr_input_image(image_path, image_index=None):
 
 
 def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
-                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, **readtext_kw):
+                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
     batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
     ``use_preprocessing`` / ``edge_crop_percent`` / ``crop_for_ocr`` / ``crop_margin``: the extractor's settings of the same names
-    (``ocr_page_crop``); with all of them off the pages are read as before."""
+    (``ocr_page_crop``); with all of them off the pages are read as before.  ``device_thumbnail=True``: the down-scaling + JPEG round trip
+    of :486-512 runs on the card (csrc/thumb.hip, identical pixels): a cropped page stays on the card from upload to OCR, and a
+    YCbCr-coded JPEG above the limit is uploaded as decoded and shrunk there."""
+    from .preprocess import ocr_input_device
+
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
         if crop_margin < 0:
             raise ValueError("crop_margin must be >= 0")
 
         def decode(path, i):
-            page = ocr_page_crop(reader, path, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin)
+            page = ocr_page_crop(reader, path, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=device_thumbnail)
+            if device_thumbnail:
+                return ("dev",) + tuple(ocr_input_device(reader, page, i))
             return _ocr_input_array(page, i, decode_once)
+    elif device_thumbnail:
+        decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once)
     else:
         decode = lambda path, i: _ocr_input(path, i, decode_once)
     res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, **readtext_kw)
@@ -191,6 +217,16 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
             by_shape = {}
 
             def flush(group):
+                if not isinstance(group[0][1], np.ndarray):
+                    # "dev" pages (already in HBM): one concatenation on the card, nothing to upload
+                    import torch
+
+                    rgb, gray = torch.stack([p[1] for p in group]), torch.stack([p[2] for p in group])
+                    torch.cuda.current_stream(rgb.device).synchronize()                       # the library runs on its own stream
+                    batches.put(("dev", [p[0] for p in group], rgb, gray))
+                    for _ in group:
+                        slots.release()
+                    return
                 # pages travel as LISTS: the Reader uploads them one by one into the device batch (no 236-MB np.stack on this thread)
                 gray = None if group[0][2] is None else [p[2] for p in group]                 # None: a group of once-decoded YCbCr pages
                 batches.put(([p[0] for p in group], [p[1] for p in group], gray))
@@ -218,7 +254,7 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
                         slots.release()
                         continue
                     kind, rgb, gray = page                          # kind "ycc": rgb holds the YCbCr triples, gray is None
-                    key = (kind, rgb.shape)
+                    key = (kind, tuple(rgb.shape))                  # kind "dev": device tensors (rgb, gray)
                     group = by_shape.setdefault(key, [])
                     group.append((i, rgb, gray))
                     if len(group) >= max_batch:
@@ -243,6 +279,8 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
         """Stage between the assembler and the device calls: the batch's pages reach the card (one GIL-free C call on the context's upload
         stream, outside the call slots) while both device workers are still inside their calls -- a worker that uploaded its own batch left
         the card idle for that long, and the two workers fell into step.  Readers without the upload entry (test doubles) pass through."""
+        if item[0] == "dev":
+            return item
         ids, rgb, gray = item
         to_dev = getattr(reader, "_to_dev", None)
         if to_dev is None:
@@ -253,6 +291,20 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
             return item                                  # the device worker retries from the host pages and reports per page
 
     def ocr(item):
+        if item[0] == "dev":                             # device pages: the page-by-page retry reads slices of the same tensors
+            _, ids, rgb_dev, gray_dev = item
+            try:
+                res = reader.readtext_device(rgb_dev, gray_dev, **readtext_kw)
+            except Exception:
+                res = []
+                for k in range(len(ids)):
+                    try:
+                        res.append(reader.readtext_device(rgb_dev[k:k + 1], gray_dev[k:k + 1], **readtext_kw)[0])
+                    except Exception:
+                        res.append([])
+            for i, r in zip(ids, res):
+                texts[i] = r
+            return
         if len(item) == 5:                               # uploaded: device tensors + the host pages for the page-by-page retry
             ids, rgb_dev, gray_dev, rgb, gray = item
             try:

@@ -135,6 +135,58 @@ def auto_crop_box_device(reader, page_dev, margin=128, with_components=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the OCR input itself (:486-512)
+PAGE_GRAY, PAGE_BGR, PAGE_RGB, PAGE_YCBCR4, PAGE_YCBCR3 = 0, 1, 2, 3, 4          # bbocr.h BBOCR_PAGE_*
+
+
+def ocr_thumbnail_rule(image_index=None):
+    """(max_dim, JPEG quality) of the extractor's down-scaling step: 1600 / 90 for the cover (``image_index`` None or 0), else 2400 / 95."""
+    return (1600, 90) if image_index is None or image_index == 0 else (2400, 95)
+
+
+def ocr_thumbnail_device(reader, page_dev, layout, max_dim, quality):
+    """``bbocr_ocr_thumbnail`` of a uint8 device page of the given ``PAGE_*`` layout (rows of packed pixels; a strided row pitch is read
+    in place) -> ``(rgb_dev [h,w,3], gray_dev [h,w])``."""
+    import torch
+
+    if not isinstance(page_dev, torch.Tensor) or page_dev.dtype != torch.uint8 or page_dev.ndim not in (2, 3):
+        raise ValueError("expected a uint8 [H,W] or [H,W,C] device tensor")
+    if not page_dev.is_cuda or page_dev.device.index != reader.device_index:
+        raise ValueError(f"expected a tensor on {reader.device}")
+    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
+    ch = 1 if page_dev.ndim == 2 else int(page_dev.shape[2])
+    want = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}.get(layout)
+    st = page_dev.stride()
+    if want is None or ch != want or st[1] != ch or (ch > 1 and st[2] != 1) or st[0] < W * ch:
+        raise ValueError(f"page of shape {tuple(page_dev.shape)} / strides {st} does not hold layout {layout}")
+    oh, ow = C.c_int(), C.c_int()
+    reader._check(reader._lib.bbocr_thumbnail_dims(H, W, int(max_dim), C.byref(oh), C.byref(ow)))
+    rgb = torch.empty((oh.value, ow.value, 3), dtype=torch.uint8, device=page_dev.device)
+    gray = torch.empty((oh.value, ow.value), dtype=torch.uint8, device=page_dev.device)
+    reader._check(reader._lib.bbocr_ocr_thumbnail(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, int(st[0]), int(layout), int(max_dim),
+                                                  int(quality), C.c_void_p(rgb.data_ptr()), C.c_void_p(gray.data_ptr()), C.byref(oh),
+                                                  C.byref(ow)))
+    return rgb, gray
+
+
+def ocr_input_device(reader, page_dev, image_index=None):
+    """``extractor_batch._ocr_input_array`` on the device: a uint8 gray [H,W] or BGR [H,W,3] tensor on the reader's device (a strided view
+    such as an edge or auto crop is read in place) -> ``(rgb_dev [h,w,3], gray_dev [h,w])``, the pages ``readtext`` sees.  Above 1600 px
+    (cover) / 2400 px the page is thumbnailed and goes through the JPEG round trip of the file the reference writes, to the bit."""
+    H, W, _, ch = _page_layout(reader, page_dev)
+    m, q = ocr_thumbnail_rule(image_index)
+    return ocr_thumbnail_device(reader, page_dev, PAGE_GRAY if ch == 1 else PAGE_BGR, m, q)
+
+
+def ocr_input_ycc_device(reader, ycc_dev, image_index=None):
+    """``extractor_batch._ocr_input`` on the device for a YCbCr-coded JPEG file: ``ycc_dev`` is its ``decode_file_ycc`` decode (uint8
+    [H,W,4] Pillow's padded pixels, or [H,W,3]) on the reader's device.  ``Image.open(path)`` without EXIF transpose, as the reference
+    reads it -> ``(rgb_dev, gray_dev)``."""
+    m, q = ocr_thumbnail_rule(image_index)
+    layout = PAGE_YCBCR4 if ycc_dev.ndim == 3 and ycc_dev.shape[2] == 4 else PAGE_YCBCR3
+    return ocr_thumbnail_device(reader, ycc_dev, layout, m, q)
+
+
 def _read_page(image_path_or_array):
     if isinstance(image_path_or_array, np.ndarray):
         return np.ascontiguousarray(image_path_or_array)

@@ -311,6 +311,37 @@ int bbocr_auto_crop(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long l
  * morphology mask, 3 = pixels of the external (RETR_EXTERNAL) components of the merged mask */
 int bbocr_op_autocrop_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int channels, uint8_t* dev_dst);
 
+/* ---- OCR-input thumbnail (enhanced_extractor.py:486-512, the step between the crops and readtext) of one u8 page on the device: a page
+ * whose longer side exceeds max_dim becomes Image.thumbnail((max_dim, max_dim)) in RGB (Pillow 12: reduce by int(size / out / 2) when that
+ * is > 1, then bicubic with 22-bit fixed-point weights) and goes through the lossy half of a baseline 4:2:0 ISLOW JPEG file of the given
+ * quality (libjpeg-turbo: colour conversion, edge replication, downsampling, DCT, quantisation, IDCT, fancy upsampling).  dev_rgb
+ * [out_h,out_w,3] and dev_gray [out_h,out_w] receive what easyocr reads from that file: the RGB decode and libjpeg's Y plane, to the bit.
+ * A page at or below max_dim is passed on as the reference reads it: gray -> replicated RGB + itself, RGB / BGR -> RGB + libpng's gray
+ * (9797 R + 19234 G + 3737 B) >> 15, YCbCr -> libjpeg's RGB + Y.  quality <= 0: no JPEG (the resized page, gray by the same rules).
+ * Pages: rows `pitch` bytes apart (a crop of a larger plane is a pointer + pitch), layout BBOCR_PAGE_*; YCBCR4 is Pillow's padded
+ * decode (decode_file_ycc(padded=True)).  A pipeline call: runs in a call slot next to readtext calls, scratch from the slot, returns
+ * with its work finished.  BBOCR_ERR_ARG before anything is queued: null pointers, H or W < 1, an unknown layout, pitch shorter than
+ * a row, max_dim < 1, quality > 100. */
+enum { BBOCR_PAGE_GRAY = 0, BBOCR_PAGE_BGR = 1, BBOCR_PAGE_RGB = 2, BBOCR_PAGE_YCBCR4 = 3, BBOCR_PAGE_YCBCR3 = 4 };
+int bbocr_ocr_thumbnail(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int max_dim, int quality, uint8_t* dev_rgb,
+                        uint8_t* dev_gray, int* out_h, int* out_w);
+/* its parts (parity tests): stage 0 = the thumbnail alone (reduce + resize) as RGB [out_h,out_w,3] in dev_dst (a page at or below
+ * max_dim: the page as RGB); stage 1 = the JPEG round trip alone of a gray or RGB page, RGB -> dev_dst [H,W,3], Y -> dev_gray [H,W];
+ * stage 2 = the upsampled YCbCr triple of that round trip, before the colour conversion, in dev_dst [H,W,3].  Stages 1 and 2 need
+ * 1 <= quality <= 100; dev_gray is only read by stage 1. */
+int bbocr_op_thumbnail_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int max_dim, int quality,
+                             uint8_t* dev_dst, uint8_t* dev_gray, int* out_h, int* out_w);
+/* host only: Image.thumbnail's output size ((H, W) when no thumbnail is taken) */
+int bbocr_thumbnail_dims(int H, int W, int max_dim, int* out_h, int* out_w);
+/* host only: the plan of that thumbnail -- output size, reduce factors (x, y), the reduced region (x0, y0, x1, y1) and the float box
+ * (x0, y0, x1, y1) handed to the bicubic resample in the reduced image */
+int bbocr_host_thumbnail_plan(int H, int W, int max_dim, int* out_h, int* out_w, int factors[2], int reduce_box[4], float resize_box[4]);
+/* host only: Pillow's bicubic coefficients of one axis (precompute_coeffs + normalize_coeffs_8bpc): bounds [out][2] = (first, count),
+ * coeffs [out][max_ksize] (22-bit fixed point).  *ksize is always set; bounds = coeffs = NULL is a size query. */
+int bbocr_host_resample_coeffs(int in_size, float in0, float in1, int out_size, int* bounds, int* coeffs, int max_ksize, int* ksize);
+/* host only: jpeg_set_quality(quality, TRUE)'s luminance (0..63) and chrominance (64..127) tables, natural order */
+int bbocr_host_jpeg_qtables(int quality, uint16_t* out);
+
 #ifdef __cplusplus
 }
 #endif
