@@ -5,10 +5,6 @@
 // other call's thousands of conv workgroups -- was measured: the mere existence of a priority stream made every other stream of the
 // process slower, CCL 1.2 -> 2.3 ms, detector 53 -> 57 ms per step, 922 -> 873 images/s; profiles/r04_inflight_ab.txt.  Plain stream.)
 static hipError_t create_seq_stream(hipStream_t* s) {
-    static const bool prio = (diag_knob("BBOCR_SEQ_PRIO", 0) != 0);      // A/B knob (diagnostic builds)
-    int lo = 0, hi = 0;
-    if (prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
-        return hipStreamCreateWithPriority(s, hipStreamNonBlocking, hi);
     return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
 
@@ -63,15 +59,11 @@ bbocr_ctx* slot_create(bbocr_ctx* root) {
     bbocr_ctx* s = new bbocr_ctx();
     s->root = root;
     s->cfg = root->cfg;
-    static const bool own_stream = (diag_knob("BBOCR_SLOT_OWN_STREAM", 0) != 0);   // A/B knob: concurrent calls on separate compute streams
-    hipError_t e = hipSuccess;
-    if (own_stream) e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    else s->stream = root->stream;
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
+    s->stream = root->stream;
+    hipError_t e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
     if (e == hipSuccess) e = create_seq_stream(&s->seq_stream);
     if (e != hipSuccess) {
         if (s->stream2) (void)hipStreamDestroy(s->stream2);
-        if (own_stream && s->stream) (void)hipStreamDestroy(s->stream);
         delete s;
         fail(BBOCR_ERR_HIP, std::string("call slot: ") + hipGetErrorString(e));
     }
@@ -98,10 +90,7 @@ void slot_destroy(bbocr_ctx* c) {
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->seq_stream) (void)hipStreamDestroy(c->seq_stream);
-    if (c->root != c) {
-        if (c->stream && c->stream != c->root->stream) (void)hipStreamDestroy(c->stream);
-        delete c;
-    }
+    if (c->root != c) delete c;
 }
 
 // stage times of the call a thread has just finished (bbocr_stage_times): per calling thread, because one context serves several
@@ -278,7 +267,6 @@ int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* 
         HostBoxes hb;
         hb.polys.resize(B); hb.hori.resize(B); hb.freeb.resize(B);
         RecEarly early;
-        static const bool early_on = (diag_knob("BBOCR_REC_EARLY", 1) != 0);   // A/B knob
         for (size_t k = 0; k < subs.size(); ++k) {
             const int b0 = subs[k].first, nb = subs[k].second;
             HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->sub_events[k], 0));
@@ -291,7 +279,7 @@ int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* 
             }
             // every page but the last pass's has its boxes: their crops go through the recogniser's conv stack (queued behind the
             // detector on `stream`) while the last pass's CCL + host geometry run -- that stretch would otherwise leave the card idle
-            if (early_on && subs.size() >= 2 && k + 2 == subs.size() && pp.rotation_info[0] == 0 && ctx->crnn_loaded)
+            if (subs.size() >= 2 && k + 2 == subs.size() && pp.rotation_info[0] == 0 && ctx->crnn_loaded)
                 rec_early_begin(ctx, dev_gray, b0 + nb, B, H, W, hb, pp, early);
         }
         HIPCHK(hipEventSynchronize(ctx->det_t1));   // the detector's end, not the stream's: the early recogniser part may be running behind it

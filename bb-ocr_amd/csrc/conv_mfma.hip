@@ -15,19 +15,8 @@
 // (MF*16 pixels) x 64 couts.  Launch grid is XCD-remapped so the cout tiles of one pixel tile share an L2.
 #include "common.h"
 #include "kernels.h"
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 #include <utility>
-
-// Timing-only ablations (BBOCR_CONV_DBG) and the per-tile s_memtime timeline (BBOCR_CONV_STAMPS) produce garbage results / extra
-// syncs: they exist in diagnostic builds only (make DIAG=1 -> -DBBOCR_DIAG), the shipped library has neither the branches nor the knobs.
-#ifdef BBOCR_DIAG
-#define CONV_DBG(a, bit) ((a).dbg & (bit))
-#else
-#define CONV_DBG(a, bit) false
-#endif
 
 // LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4: lane l's 16 bytes land at lds + 16 l), issued as inline assembly.  The builtin
 // (__builtin_amdgcn_global_load_lds) is modelled by hipcc's waitcnt pass as a FLAT access that touches LDS: while one is outstanding -- in
@@ -372,11 +361,11 @@ __device__ __forceinline__ void conv_epilogue_pool2x2_lean(const ConvArgs& a, f3
 // The plain trunk layer's epilogue -- bias (+ ReLU) -> 16-bit NHWC, all 64 couts of the wave stored -- and nothing else.  The shared
 // epilogue above executes ~1,000 vector instructions per wave behind a k-loop whose co-resident workgroup keeps the SIMD's issue port half
 // busy with MFMAs: 9-15 k cycles during which the workgroup's LDS and registers are held and its slot computes nothing (timing-only
-// ablation, BBOCR_CONV_DBG=8: the pass is 20 % shorter without epilogues, conv2_1 33 %).  Here a value costs one add, half a convert and
+// ablation: the pass is 20 % shorter without epilogues, conv2_1 33 %).  Here a value costs one add, half a convert and
 // half an integer max: ReLU is applied to the PACKED pair (both element types are sign-magnitude, so max(int16, 0) == ReLU, and
 // round-then-ReLU == ReLU-then-round bit for bit), bias is a plain add (acc_scale is 1 on this path), interior tiles skip the per-lane
-// bounds tests.  WHOLE: regroup the two 32-byte runs of a pixel across lanes so that every store writes whole 128-byte lines (as above).
-template <int EL, int MF, bool WHOLE>
+// bounds tests.  The two 32-byte runs of a pixel are regrouped across lanes so that every store writes whole 128-byte lines (as above).
+template <int EL, int MF>
 __device__ __forceinline__ void conv_epilogue_plain_lean(const ConvArgs& a, f32x4 (&acc)[MF][4], int n, int nt, int oy0, int ox0, int wm, int wn,
                                                          int fpr, int lane, int BN) {
     typedef short s16x2_t __attribute__((ext_vector_type(2)));
@@ -393,8 +382,8 @@ __device__ __forceinline__ void conv_epilogue_plain_lean(const ConvArgs& a, f32x
     const bool relu = a.relu_out != 0;                                               // wave-uniform
     const bool inside = oy0 + a.TH <= a.OH && ox0 + a.TW <= a.OW;                     // wave-uniform: a tile inside the image needs no per-lane tests
     const s16x2_t z2 = {0, 0};
-    // element offset of this lane inside a fragment row: WHOLE -> pixel (pl & 7), run (pl >> 3); else pixel pl, run 0 (run 1 = + 32)
-    const size_t lane_off = WHOLE ? (size_t)(pl & 7) * a.out_cs + cout0 + (pl >> 3) * 32 : (size_t)pl * a.out_cs + cout0;
+    // element offset of this lane inside a fragment row: pixel (pl & 7), run (pl >> 3)
+    const size_t lane_off = (size_t)(pl & 7) * a.out_cs + cout0 + (pl >> 3) * 32;
 #pragma unroll
     for (int f = 0; f < MF; ++f) {
         const int F = wm * MF + f;
@@ -409,27 +398,19 @@ __device__ __forceinline__ void conv_epilogue_plain_lean(const ConvArgs& a, f32x
             p[i] = q;
         }
         uint16_t* op = (uint16_t*)a.out + ((size_t)(n * a.OH + oy) * a.OW + xb) * a.out_cs + lane_off;
-        if constexpr (WHOLE) {
-            u32x4 dA, dB;
+        u32x4 dA, dB;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                dA[i] = (unsigned)__builtin_amdgcn_update_dpp((int)p[i], (int)p[4 + i], 0x118 /*row_shr:8*/, 0xF, 0xC, false);
-                dB[i] = (unsigned)__builtin_amdgcn_update_dpp((int)p[4 + i], (int)p[i], 0x108 /*row_shl:8*/, 0xF, 0x3, false);
-            }
-            if (inside) {
-                *(u32x4*)op = dA;
-                *(u32x4*)(op + (size_t)8 * a.out_cs) = dB;
-            } else {
-                const int xA = xb + (pl & 7);
-                if (oy < a.OH && xA < a.OW) *(u32x4*)op = dA;
-                if (oy < a.OH && xA + 8 < a.OW) *(u32x4*)(op + (size_t)8 * a.out_cs) = dB;
-            }
+        for (int i = 0; i < 4; ++i) {
+            dA[i] = (unsigned)__builtin_amdgcn_update_dpp((int)p[i], (int)p[4 + i], 0x118 /*row_shr:8*/, 0xF, 0xC, false);
+            dB[i] = (unsigned)__builtin_amdgcn_update_dpp((int)p[4 + i], (int)p[i], 0x108 /*row_shl:8*/, 0xF, 0x3, false);
+        }
+        if (inside) {
+            *(u32x4*)op = dA;
+            *(u32x4*)(op + (size_t)8 * a.out_cs) = dB;
         } else {
-            const u32x4 lo = {p[0], p[1], p[2], p[3]}, hi = {p[4], p[5], p[6], p[7]};
-            if (inside || (oy < a.OH && xb + pl < a.OW)) {
-                *(u32x4*)op = lo;
-                *(u32x4*)(op + 32) = hi;
-            }
+            const int xA = xb + (pl & 7);
+            if (oy < a.OH && xA < a.OW) *(u32x4*)op = dA;
+            if (oy < a.OH && xA + 8 < a.OW) *(u32x4*)(op + (size_t)8 * a.out_cs) = dB;
         }
     }
 }
@@ -568,7 +549,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv_mfma_kernel(const ConvAr
         for (int i = 0; i < PH; ++i) {
             const int sp = src_pix[part * PH + i];
             u32x4 v = {0u, 0u, 0u, 0u};
-            if (sp >= 0 && !CONV_DBG(a, 2)) v = *(const u32x4*)(src + (size_t)sp * cs + cb);   // dbg bit 2: timing-only ablation
+            if (sp >= 0) v = *(const u32x4*)(src + (size_t)sp * cs + cb);
             pre[i] = v;
         }
     };
@@ -616,7 +597,6 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv_mfma_kernel(const ConvAr
     // ---- weight slice: LDS-DMA, LDS image == global image (fragment order), lane-linear
     const unsigned char* wsrc = (const unsigned char*)a.wpk + (size_t)nt * nk * WBUF;
     auto issue_w = [&](int ks, int buf) {
-        if (CONV_DBG(a, 1)) return;   // timing-only ablation (diagnostic build, BBOCR_CONV_DBG): no weight DMA, results are garbage
 #pragma unroll
         for (int p0 = 0; p0 < WPIECES; p0 += NT) {
             if (p0 + wave * 64 < WPIECES) {
@@ -784,12 +764,6 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
             spix[pb] = (py < a.PH && rowok && iy < a.H && lx >= 0 && ix < a.W) ? (g.n * a.H + iy) * a.W + ix : -1;
         }
     };
-    auto stamp = [&](int i) {   // tile timeline: compiled in by -DBBOCR_DIAG only
-#ifdef BBOCR_DIAG
-        if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 4 + i] = __builtin_amdgcn_s_memtime();
-#endif
-    };
-    stamp(0);
     Geo cur;
     geom(tile, cur);
     if constexpr (!FUSE1) geom_pix(cur);
@@ -959,7 +933,6 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
         }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    stamp(1);
 
     int wslot = 0, par = 0;
     const unsigned char* wp = cur.wsrc + (size_t)(RING - 1) * WBUF;   // next weight slice to issue
@@ -993,19 +966,17 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
 #pragma unroll
             for (int f = 0; f < 4; ++f) bq[f] = pre[f];
         }
-        // (dbg bits 16 / 32: timing-only ablations of a diagnostic build -- the k-loop without its weight / patch DMA, results are garbage)
         if constexpr (Sched::wcnt(MORE, tap) > 0) {
             int slot = wslot + RING - 1;
             if (slot >= RING) slot -= RING;
-            if (!CONV_DBG(a, 16)) issue_w(wp, slot);
+            issue_w(wp, slot);
             wp += WBUF;
         }
         if constexpr (MORE && Sched::pcnt(tap) > 0) {
             constexpr int p0 = Sched::pfirst(tap);
             const int nc = c + 1;
-            if (!CONV_DBG(a, 32))
-                [&]<int... I>(std::integer_sequence<int, I...>) { (issue_p(spix[p0 + I], nc, par ^ 1, std::integral_constant<int, p0 + I>{}), ...); }(
-                    std::make_integer_sequence<int, Sched::pcnt(tap)>{});
+            [&]<int... I>(std::integer_sequence<int, I...>) { (issue_p(spix[p0 + I], nc, par ^ 1, std::integral_constant<int, p0 + I>{}), ...); }(
+                std::make_integer_sequence<int, Sched::pcnt(tap)>{});
         }
         __builtin_amdgcn_sched_barrier(0);
         constexpr int kyn = (tap + 1) / KS, kxn = (tap + 1) % KS;
@@ -1051,26 +1022,15 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
     };
     for (int c = 0; c + 1 < a.nchunks; ++c) chunk(std::true_type{}, c);
     chunk(std::false_type{}, a.nchunks - 1);
-    stamp(2);
-#ifdef BBOCR_DIAG
-    if (CONV_DBG(a, 8)) {   // timing-only ablation, no epilogue
-        if (acc[0][0][0] == 123.456f) *(float*)a.out = acc[MF - 1][3][3];
-        return;
-    }
-#endif
     if constexpr (FUSE1) conv_epilogue_pool2x2_lean<EL, MF>(a, acc, cur.n, cur.oy0, cur.ox0, wm, lane);       // (launch_dma checks its preconditions)
     else if constexpr (EPI == 1) conv_epilogue_post1x1<EL, MF>(a, acc, cur.n, cur.oy0, cur.ox0, wm, fpr, lane);                  // (launch_dma checks its preconditions)
     else if constexpr (KS == 3 && NF == 4) {
-        // a.lean (set by launch_dma_one when the layer is a plain one, wave-uniform): 1 / 2 = bias (+ ReLU) -> 16-bit stores, whole lines / half lines;
+        // a.lean (set by launch_dma_one when the layer is a plain one, wave-uniform): 1 = bias (+ ReLU) -> 16-bit stores of whole lines;
         // 3 = the pooled-only epilogue of the fused conv1_2 launch on this layer's couts; 0 = the shared epilogue with all its variants
-        if (a.lean == 1) conv_epilogue_plain_lean<EL, MF, true>(a, acc, cur.n, cur.nt, cur.oy0, cur.ox0, wm, wn, fpr, lane, BN);
-        else if (a.lean == 2) conv_epilogue_plain_lean<EL, MF, false>(a, acc, cur.n, cur.nt, cur.oy0, cur.ox0, wm, wn, fpr, lane, BN);
+        if (a.lean == 1) conv_epilogue_plain_lean<EL, MF>(a, acc, cur.n, cur.nt, cur.oy0, cur.ox0, wm, wn, fpr, lane, BN);
         else if (a.lean == 3) conv_epilogue_pool2x2_lean<EL, MF>(a, acc, cur.n, cur.oy0, cur.ox0, wm, lane, cur.nt * BN + wn * 64);
         else conv_epilogue<EL, MF>(a, acc, cur.n, cur.nt, cur.oy0, cur.ox0, wm, wn, fpr, lane, BN, sub, cur.sph, cur.spw);
     } else conv_epilogue<EL, MF>(a, acc, cur.n, cur.nt, cur.oy0, cur.ox0, wm, wn, fpr, lane, BN, sub, cur.sph, cur.spw);
-#ifdef BBOCR_DIAG
-    if (a.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(3); }
-#endif
 }
 
 // ================================================================================================ 3x3, resident weights
@@ -1212,7 +1172,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_resw_kernel(const ConvArgs a) 
 template <int EL>
 static hipError_t launch_resw(const ConvArgs& a, hipStream_t s) {
     const int ntiles = a.N * a.tiles_x * a.tiles_y;
-    static const int db_knob = diag_knob("BBOCR_RESW_DB", 1);
     const int ncu = device_cus();
     auto go = [&](auto kern, size_t smem, int per_cu, LdsOptIn& attr) -> hipError_t {
         if (hipError_t e = lds_opt_in(attr, (const void*)kern, smem); e != hipSuccess) return e;
@@ -1221,14 +1180,10 @@ static hipError_t launch_resw(const ConvArgs& a, hipStream_t s) {
         return hipGetLastError();
     };
     constexpr size_t P = 324 * 64, W1 = 9 * 2048, W2 = 18 * 2048;
-    static LdsOptIn at[5];
-    if (a.cout_store == 64) return go(conv3x3_resw_kernel<EL, 1, true, 4, true>, 9 * 4096 + 2 * P, 2, at[4]);       // 78.3 KB: two workgroups per CU
-    if (a.nchunks == 1) {
-        if (db_knob) return go(conv3x3_resw_kernel<EL, 1, true>, W1 + 2 * P, 2, at[0]);          // 59.9 KB: two workgroups per CU
-        return go(conv3x3_resw_kernel<EL, 1, false>, W1 + P, 4, at[1]);                           // 39.2 KB: four
-    }
-    if (db_knob >= 2) return go(conv3x3_resw_kernel<EL, 2, true>, W2 + 4 * P, 1, at[2]);           // 119.8 KB: one
-    return go(conv3x3_resw_kernel<EL, 2, false>, W2 + 2 * P, 2, at[3]);                            // 78.3 KB: two
+    static LdsOptIn at[3];
+    if (a.cout_store == 64) return go(conv3x3_resw_kernel<EL, 1, true, 4, true>, 9 * 4096 + 2 * P, 2, at[2]);       // 78.3 KB: two workgroups per CU
+    if (a.nchunks == 1) return go(conv3x3_resw_kernel<EL, 1, true>, W1 + 2 * P, 2, at[0]);         // 59.9 KB: two workgroups per CU
+    return go(conv3x3_resw_kernel<EL, 2, false>, W2 + 2 * P, 2, at[1]);                            // 78.3 KB: two
 }
 
 // ================================================================================================ CRAFT upconv4 in one launch
@@ -1426,8 +1381,7 @@ static hipError_t launch_up4_el(const ConvArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_up4_fused(const ConvPlan& p1, const ConvPlan& p3, ConvArgs a, hipStream_t s) {
-    static const bool on = (diag_knob("BBOCR_UP4_FUSED", 1) != 0);      // A/B knob (diagnostic builds)
-    if (!on || p1.KH != 1 || p1.Cin != 128 || p1.Cout != 64 || p1.BN != 64 || p3.KH != 3 || p3.Cin != 64 || p3.Cout_pad != 64 || p3.BN != 64 ||
+    if (p1.KH != 1 || p1.Cin != 128 || p1.Cout != 64 || p1.BN != 64 || p3.KH != 3 || p3.Cin != 64 || p3.Cout_pad != 64 || p3.BN != 64 ||
         p1.el != p3.el || p1.split || p3.split || a.in0_cs != 128 || a.up_cs != 64 || !a.addup || !a.zero || a.cout_store > 32 || (a.up_H & 1) || (a.up_W & 1) ||
         a.up_H != a.H || a.up_W != a.W)
         return hipErrorNotSupported;
@@ -1436,7 +1390,7 @@ hipError_t launch_up4_fused(const ConvPlan& p1, const ConvPlan& p3, ConvArgs a, 
     a.tiles_x = (a.OW + 15) / 16; a.tiles_y = (a.OH + 15) / 16; a.ntiles_n = 1; a.nchunks = 2; a.ntaps = 9;
     a.aux_w = p1.d_w; a.aux_b = p1.d_b;
     a.wpk = p3.d_w; a.bias = p3.d_b;
-    a.acc_scale = 1.f; a.dbg = 0;
+    a.acc_scale = 1.f;
     if ((long long)a.N * a.tiles_x * a.tiles_y > 0x7fffffffLL) return hipErrorNotSupported;
     return p3.el ? launch_up4_el<1>(a, s) : launch_up4_el<0>(a, s);
 }
@@ -1601,60 +1555,21 @@ static hipError_t launch_cfg(const ConvArgs& a, int grid, hipStream_t s) {
     return launch_one<EL, WM, WN, MF, PITER>(a, smem, grid, s);
 }
 
-static bool conv_dma() {   // BBOCR_CONV_DMA=0 disables the LDS-DMA staged 3x3 variant (A/B runs)
-    static const bool v = (diag_knob("BBOCR_CONV_DMA", 1) != 0);
-    return v;
-}
-
-// BBOCR_CONV_STAMPS=<dir>: diagnostic tile timeline — every 3x3 DMA launch is followed by a sync and dumps its per-workgroup
-// s_memtime stamps to <dir>/stamps_<seq>_<Cin>x<Cout>_<H>x<W>_g<grid>.bin (tools/tile_timeline.py reads them)
-static const char* conv_stamps_dir() {
-#ifdef BBOCR_DIAG
-    static const char* d = getenv("BBOCR_CONV_STAMPS");
-    return d;
-#else
-    return nullptr;
-#endif
-}
-
 template <int EL, int WM, int WN, int MF, int NPB, int RING, int NPS = NPB * 64, bool FUSE1 = false, int NF = 4, int EPI = 0, int KS = 3>
 static hipError_t launch_dma_one(ConvArgs a, int grid, hipStream_t s) {
     auto k = conv3x3_dma_kernel<EL, WM, WN, MF, NPB, RING, NPS, FUSE1, NF, EPI, KS>;
     const size_t smem_max = (size_t)RING * WN * 64 * 64 + (size_t)2 * NPS * 64;
     // a single 32-channel chunk (conv_cls: Cin = 32) never touches the second patch buffer: without it a workgroup needs 33 KB and
     // FOUR share a CU -- these launches are bound by per-tile latency, not by MFMA or HBM
-    static const bool one_buf = (diag_knob("BBOCR_CONV_1BUF", 1) != 0);   // A/B knob
-    const size_t smem = (one_buf && a.nchunks == 1 && !FUSE1) ? smem_max - (size_t)NPS * 64 : smem_max;
+    const size_t smem = (a.nchunks == 1 && !FUSE1) ? smem_max - (size_t)NPS * 64 : smem_max;
     static LdsOptIn attr;
     if (hipError_t e = lds_opt_in(attr, (const void*)k, smem_max); e != hipSuccess) return e;
     {   // which epilogue (conv_epilogue_plain_lean / conv_epilogue_pool2x2_lean / the shared one): plain layers whose waves store all their 64 couts
-        static const int lean_knob = diag_knob("BBOCR_CONV_LEAN", 1);      // A/B knob: 0 off, 1 whole-line stores, 2 half-line stores (no DPP regroup)
         a.lean = 0;
-        const bool plain = lean_knob && !FUSE1 && EPI == 0 && KS == 3 && NF == 4 && a.sub == 1 && !a.out_f32 && !a.tail && !a.split_off && !a.addup && !a.post_w &&
+        const bool plain = !FUSE1 && EPI == 0 && KS == 3 && NF == 4 && a.sub == 1 && !a.out_f32 && !a.tail && !a.split_off && !a.addup && !a.post_w &&
                            a.acc_scale == 1.f && a.cout_store == a.ntiles_n * WN * 64 && a.out_cs % 8 == 0;
-        if (plain && a.pool_mode == 0 && a.out) a.lean = lean_knob == 2 ? 2 : 1;
+        if (plain && a.pool_mode == 0 && a.out) a.lean = 1;
         else if (plain && a.pool_mode == 1 && !a.store_full && a.TH == 16 && a.TW == 16 && a.pool_out) a.lean = 3;
-    }
-    if (const char* dir = conv_stamps_dir()) {
-        static int seq = 0;
-        unsigned long long* dev = nullptr;
-        const size_t bytes = (size_t)grid * 4 * sizeof(unsigned long long);
-        if (hipMalloc((void**)&dev, bytes) != hipSuccess) return hipErrorOutOfMemory;
-        (void)hipMemsetAsync(dev, 0, bytes, s);
-        a.stamps = dev;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(WM * WN * 64), smem, s, a);
-        hipError_t e = hipStreamSynchronize(s);
-        if (e == hipSuccess) {
-            unsigned long long* h = (unsigned long long*)malloc(bytes);
-            e = hipMemcpy(h, dev, bytes, hipMemcpyDeviceToHost);
-            char path[512];
-            snprintf(path, sizeof(path), "%s/stamps_%03d_%dx%d_%dx%d_g%d_bn%d_r%d.bin", dir, seq++, a.C0 + a.C1, a.ntiles_n * WN * 64, a.H, a.W, grid,
-                     WN * 64, RING);
-            if (FILE* f = fopen(path, "wb")) { fwrite(h, 1, bytes, f); fclose(f); }
-            free(h);
-        }
-        (void)hipFree(dev);
-        return e;
     }
     hipLaunchKernelGGL(k, dim3(grid), dim3(WM * WN * 64), smem, s, a);
     return hipGetLastError();
@@ -1662,13 +1577,7 @@ static hipError_t launch_dma_one(ConvArgs a, int grid, hipStream_t s) {
 
 template <int EL, int WM, int WN, int MF>
 static hipError_t launch_dma(const ConvArgs& a, int npb, int grid, hipStream_t s) {
-    const size_t wb = (size_t)WN * 64 * 64, pb = (size_t)2 * npb * 64 * 64;
-    static const int ring_cap = diag_knob("BBOCR_DMA_RING", 4);
-    const bool r4 = ring_cap >= 4 && 4 * wb + pb <= 80 * 1024;      // deepest ring that still lets two workgroups share a CU
     if constexpr (WN == 1) {
-        // BN = 64: k-steps are short (16 MFMAs per wave), what pays is a THIRD co-resident workgroup: 16x16 tiles with the patch
-        // trimmed to its 18 x 18 = 324 pixels and a 3-deep weight ring are 53,760 B of LDS (3 x 53,760 <= 160 KB)
-        static const bool three = (diag_knob("BBOCR_CONV_3WG", 1) != 0);
         if (a.c11_w) {   // conv1_2 with the conv1_1 producer fused in
             if (!(npb == 6 && a.PH == 18 && a.PW == 18 && a.TH == 16 && a.TW == 16 && a.nchunks == 2 && a.sub == 1)) return hipErrorInvalidValue;
             // the kernel's only epilogue: 64 stored couts, MaxPool2d(2,2) fused, nothing but the pooled 16-bit tensor kept
@@ -1676,37 +1585,39 @@ static hipError_t launch_dma(const ConvArgs& a, int npb, int grid, hipStream_t s
                 return hipErrorInvalidValue;
             return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, true>(a, grid, s);
         }
-        if (a.post_w) {   // 1x1 64 -> 64 behind the layer: 16 x 16 tiles of a plain 64-cout layer only, anything else is declined
-            if (!(WN == 1 && three && npb == 6 && a.PH == 18 && a.PW == 18 && a.cout_store == 64 && a.ntiles_n == 1 && a.sub == 1 && !a.pool_mode &&
-                  !a.split_off && !a.out_f32 && !a.tail && !a.addup))
-                return hipErrorNotSupported;
-            if constexpr (WN == 1) return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 4, 1>(a, grid, s);
-        }
-        if (three && npb == 6 && a.PH * a.PW == 324) {
-            static const bool half = (diag_knob("BBOCR_CONV_NF2", 1) != 0);   // A/B knob
-            static const bool resw = (diag_knob("BBOCR_CONV_RESW", 1) != 0);    // A/B knob
-            if (resw && half && a.cout_store <= 32 && a.nchunks <= 2 && a.sub == 1 && !a.C1 && !a.pool_mode && a.TH == 16 && a.TW == 16 && a.ntiles_n == 1)
+    }
+    if (a.post_w) {   // 1x1 64 -> 64 behind the layer: 16 x 16 tiles of a plain 64-cout layer only, anything else is declined
+        if constexpr (WN == 1)
+            if (npb == 6 && a.PH == 18 && a.PW == 18 && a.cout_store == 64 && a.ntiles_n == 1 && a.sub == 1 && !a.pool_mode && !a.split_off &&
+                !a.out_f32 && !a.tail && !a.addup)
+                return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 4, 1>(a, grid, s);
+        return hipErrorNotSupported;
+    }
+    if constexpr (WN == 1) {
+        // BN = 64: k-steps are short (16 MFMAs per wave), what pays is a THIRD co-resident workgroup: 16x16 tiles with the patch
+        // trimmed to its 18 x 18 = 324 pixels and a 3-deep weight ring are 53,760 B of LDS (3 x 53,760 <= 160 KB)
+        if (npb == 6 && a.PH * a.PW == 324) {
+            if (a.cout_store <= 32 && a.nchunks <= 2 && a.sub == 1 && !a.C1 && !a.pool_mode && a.TH == 16 && a.TW == 16 && a.ntiles_n == 1)
                 return launch_resw<EL>(a, s);
             // one input chunk, 64 couts, MaxPool2d(2,2) fused and only the pooled tensor kept (the CRNN's 32 -> 64 layer): nine 4 KB slices resident
-            static const bool resw64 = (diag_knob("BBOCR_CONV_RESW64", 1) != 0);    // A/B knob
-            if (resw && resw64 && a.cout_store == 64 && a.nchunks == 1 && a.sub == 1 && !a.C1 && a.pool_mode == 1 && !a.store_full && !a.split_off && !a.out_f32 &&
+            if (a.cout_store == 64 && a.nchunks == 1 && a.sub == 1 && !a.C1 && a.pool_mode == 1 && !a.store_full && !a.split_off && !a.out_f32 &&
                 !a.tail && !a.relu_in0 && a.TH == 16 && a.TW == 16 && a.ntiles_n == 1 && a.acc_scale > 0.f)
                 return launch_resw<EL>(a, s);
-            if (half && a.cout_store <= 32) return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 2>(a, grid, s);
+            if (a.cout_store <= 32) return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 2>(a, grid, s);
             return launch_dma_one<EL, WM, WN, MF, 6, 3, 324>(a, grid, s);
         }
-        if (a.post_w) return hipErrorNotSupported;
         if (npb == 6) return launch_dma_one<EL, WM, WN, MF, 6, 3>(a, grid, s);      // measured faster than the 4-deep ring at this tile
+    } else if (npb == 6) {
+        const size_t wb = (size_t)WN * 64 * 64, pb = (size_t)2 * npb * 64 * 64;
+        // the deepest ring that still lets two workgroups share a CU
+        return 4 * wb + pb <= 80 * 1024 ? launch_dma_one<EL, WM, WN, MF, 6, 4>(a, grid, s) : launch_dma_one<EL, WM, WN, MF, 6, 3>(a, grid, s);
     }
-    if (a.post_w) return hipErrorNotSupported;
-    if (npb == 6) return r4 ? launch_dma_one<EL, WM, WN, MF, 6, 4>(a, grid, s) : launch_dma_one<EL, WM, WN, MF, 6, 3>(a, grid, s);
     if (npb == 7) return launch_dma_one<EL, WM, WN, MF, 7, 3>(a, grid, s);
     return hipErrorInvalidValue;
 }
 
-int conv_plan_bn(int Cout) {   // couts per workgroup tile (BBOCR_BN64_UPTO: A/B knob, measured no gain for the 128-cout layers)
-    static const int bn64_upto = diag_knob("BBOCR_BN64_UPTO", 64);
-    return Cout > bn64_upto ? 128 : 64;
+int conv_plan_bn(int Cout) {   // couts per workgroup tile (64-cout tiles measured no gain for the 128-cout layers)
+    return Cout > 64 ? 128 : 64;
 }
 
 template <int EL>
@@ -1721,9 +1632,9 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
     a.ntaps = p.KH * p.KW;
     a.sub = 1;
     // a 1x1 behind the layer (a.post_w) exists for plain 3x3 layers with one 64-cout tile on the LDS-DMA kernel; the caller falls back to two launches
-    if (a.post_w && !(conv_dma() && a.zero && p.KH == 3 && p.KW == 3 && p.dil == 1 && p.pad_h == 1 && p.pad_w == 1 && BN == 64 && p.Cout_pad == 64))
+    if (a.post_w && !(a.zero && p.KH == 3 && p.KW == 3 && p.dil == 1 && p.pad_h == 1 && p.pad_w == 1 && BN == 64 && p.Cout_pad == 64))
         return hipErrorNotSupported;
-    if (conv_dma() && a.zero && !a.pool_mode && p.KH == 3 && p.KW == 3 && p.dil > 1 && p.pad_h == p.dil && p.pad_w == p.dil) {
+    if (a.zero && !a.pool_mode && p.KH == 3 && p.KW == 3 && p.dil > 1 && p.pad_h == p.dil && p.pad_w == p.dil) {
         const int d = p.dil, LH = cdiv(a.OH, d), LW = cdiv(a.OW, d);   // phase sub-lattice size
         long long best = -1;
         for (int th = 16; th >= 4; th >>= 1) {
@@ -1747,7 +1658,6 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
             a.nchunks = p.Cin_pad / 32;
             a.wpk = p.d_w;
             a.bias = p.d_b;
-            a.dbg = 0;
             const long long g = (long long)a.N * a.tiles_x * a.tiles_y * a.ntiles_n;
             if (g > 0 && g <= 0x7fffffffLL)
                 return BN == 128 ? launch_dma<EL, 2, 2, 8>(a, a.NP / 64, (int)g, s) : launch_dma<EL, 4, 1, 4>(a, a.NP / 64, (int)g, s);
@@ -1758,7 +1668,7 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
     const int ring = 2;
     const int max_piter = 16;
     // 2x2 / padding 0 (the CRNN's last conv, 4 input rows -> 3) on the LDS-DMA kernel: 4 x 64 tiles, whose 5 x 65 patch is six 64-pixel blocks
-    const bool dma2x2 = conv_dma() && a.zero && p.KH == 2 && p.KW == 2 && p.dil == 1 && p.pad_h == 0 && p.pad_w == 0 && !a.pool_mode && !a.tail &&
+    const bool dma2x2 = a.zero && p.KH == 2 && p.KW == 2 && p.dil == 1 && p.pad_h == 0 && p.pad_w == 0 && !a.pool_mode && !a.tail &&
                         !a.addup && !a.post_w && (BN == 128 || BN == 64);
     // tile shape: the TH x (BM/TH) rectangle with the least (MFMA work on partial tiles + patch staging) per layer
     if (dma2x2) {
@@ -1787,33 +1697,26 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
     if ((a.in0_cs & 7) || (a.C1 && (a.in1_cs & 7)) || (a.out_cs & (a.out_f32 ? 3 : 7)) || (a.cout_store & 15)) return hipErrorInvalidValue;
     a.wpk = p.d_w;
     a.bias = p.d_b;
-#ifdef BBOCR_DIAG
-    static const int dbg = diag_knob("BBOCR_CONV_DBG", 0);
-    a.dbg = dbg;
-#else
-    a.dbg = 0;
-#endif
     const long long grid_ll = (long long)a.N * a.tiles_x * a.tiles_y * a.ntiles_n;
     if (grid_ll <= 0 || grid_ll > 0x7fffffffLL) return hipErrorInvalidValue;
     const int grid = (int)grid_ll;
-    if (a.addup && !(conv_dma() && p.KH == 1 && p.KW == 1 && a.zero && !a.pool_mode && !a.out_f32 && !a.tail && a.cout_store % 64 == 0 &&
+    if (a.addup && !(p.KH == 1 && p.KW == 1 && a.zero && !a.pool_mode && !a.out_f32 && !a.tail && a.cout_store % 64 == 0 &&
                      a.cout_store == p.Cout_pad))
         return hipErrorInvalidValue;
-    if (conv_dma() && p.KH == 1 && p.KW == 1 && p.pad_h == 0 && p.pad_w == 0 && a.zero && !a.pool_mode)
+    if (p.KH == 1 && p.KW == 1 && p.pad_h == 0 && p.pad_w == 0 && a.zero && !a.pool_mode)
         return BN == 256 ? launch_dma1x1<EL, 2, 4, 8>(a, s) : (BN == 128 ? launch_dma1x1<EL, 2, 2, 8>(a, s) : launch_dma1x1<EL, 4, 1, 4>(a, s));
     if (dma2x2)
         return BN == 128 ? launch_dma_one<EL, 2, 2, 8, 6, 4, 384, false, 4, 0, 2>(a, grid, s) : launch_dma_one<EL, 4, 1, 4, 6, 3, 384, false, 4, 0, 2>(a, grid, s);
-    if (conv_dma() && p.KH == 3 && p.KW == 3 && p.dil == 1 && p.pad_h == 1 && p.pad_w == 1 && a.zero) {
+    if (p.KH == 3 && p.KW == 3 && p.dil == 1 && p.pad_h == 1 && p.pad_w == 1 && a.zero) {
         const int npb = cdiv(a.PH * a.PW, 64);
         if (npb == 6 || npb == 7) {
             a.NP = npb * 64;
             return BN == 128 ? launch_dma<EL, 2, 2, 8>(a, npb, grid, s) : launch_dma<EL, 4, 1, 4>(a, npb, grid, s);
         }
     }
-    if (a.post_w) return hipErrorNotSupported;
     // the generic kernel below knows neither the fused conv1_1 producer (in0 would be read as a 64-channel tensor: an out-of-bounds access on
-    // the uint8 page -- what BBOCR_CONV_DMA=0 did in a diagnostic build in round 4) nor the up-sampling epilogue: refuse, never run garbage
-    if (a.c11_w || a.addup) return hipErrorNotSupported;
+    // the uint8 page, a GPU fault in round 4) nor the up-sampling epilogue nor the 1x1 behind the layer: refuse, never run garbage
+    if (a.c11_w || a.addup || a.post_w) return hipErrorNotSupported;
     const int piter = cdiv(a.NP / 16, NWV);
     if (BN == 128) return piter <= 4 ? launch_cfg<EL, 2, 2, 8, 4>(a, grid, s) : (piter <= 8 ? launch_cfg<EL, 2, 2, 8, 8>(a, grid, s) : launch_cfg<EL, 2, 2, 8, 16>(a, grid, s));
     if (BN == 64) return piter <= 4 ? launch_cfg<EL, 4, 1, 4, 4>(a, grid, s) : (piter <= 8 ? launch_cfg<EL, 4, 1, 4, 8>(a, grid, s) : launch_cfg<EL, 4, 1, 4, 16>(a, grid, s));

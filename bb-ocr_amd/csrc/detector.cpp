@@ -182,9 +182,8 @@ static void craft_forward(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, in
     Act u3b{c->arena.alloc<uint16_t>((size_t)u3a.N * u3a.H * u3a.W * 64), u3a.N, u3a.H, u3a.W, 64};
     Act z{c->arena.alloc<uint16_t>((size_t)u3a.N * u3a.H * u3a.W * 64), u3a.N, u3a.H, u3a.W, 64};
     if (!ar.dry) {
-        static const bool post_on = (diag_knob("BBOCR_UP3_POST", 1) != 0);     // A/B knob
         hipError_t e = hipErrorNotSupported;
-        if (post_on && c->up4y_post && !c->up3b.split) {
+        if (c->up4y_post && !c->up3b.split) {
             ConvArgs a{};
             a.in0 = u3a.p; a.C0 = u3a.C; a.in0_cs = u3a.C;
             a.N = u3a.N; a.H = u3a.H; a.W = u3a.W;
@@ -316,15 +315,15 @@ void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bb
         craft_forward_any(c, nullptr, 1, d.th, d.tw, d.H32, d.W32, nullptr);
         const size_t per_page = std::max<size_t>(c->arena.off, 1);
         const int cap = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)96 << 30) / per_page));
-        static const int tail_knob = diag_knob("BBOCR_DET_TAIL", 8);   // A/B knob: tail length in 1280x960-page equivalents
+        constexpr int kTailEquiv = 8;         // tail length in 1280x960-page equivalents
         // pages larger than 1280x960 (an A4@300dpi canvas is 3.8 of them) count by their pixels: 16 A4 scans run as [14, 2]
         const double equiv = std::max(1.0, (double)d.th * d.tw / (960.0 * 1280.0));
-        const int tail_pages = tail_knob > 0 ? std::max(1, (int)std::lround(tail_knob / equiv)) : 0;
+        const int tail_pages = std::max(1, (int)std::lround(kTailEquiv / equiv));
         // ... unless another call is in flight on this context (bbocr_config::call_slots): its kernels fill the card while this call's
         // last pass is turned into boxes, so the short pass has nothing left to hide and only costs its own inefficiency (round 4, two calls
         // in flight: [56, 8] 942, one pass of 64 959, [32, 32] 947 images/s)
         const bool alone = !other_call_in_flight(c);
-        const int tail = (alone && after_sub && B * equiv >= 24.0 && cap > tail_pages && B > tail_pages && tail_pages > 0) ? tail_pages : 0;
+        const int tail = (alone && after_sub && B * equiv >= 24.0 && cap > tail_pages && B > tail_pages) ? tail_pages : 0;
         const int body = B - tail, nbig = cdiv(body, cap);
         for (int i = 0; i < nbig; ++i) passes.push_back(body / nbig + (i < body % nbig ? 1 : 0));
         if (tail) passes.push_back(tail);

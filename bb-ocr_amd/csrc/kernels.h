@@ -23,7 +23,9 @@ struct ConvArgs {
     // fused max-pool in the epilogue: 0 none, 1 = MaxPool2d(2,2), 2 = MaxPool2d((2,1),(2,1)); bf16 output [N,OH/2,OW(/2),pool_cs]
     int pool_mode, pool_relu, store_full, pool_cs;
     void* pool_out;
-    int dbg;               // timing-only ablation switches (BBOCR_CONV_DBG); 0 in production
+    // aux_w (see aux_b) sits apart from aux_b on purpose: argument offsets decide how hipcc merges the kernels' argument loads, and this
+    // order compiles every conv kernel with the register and spill counts they were measured with
+    const uint16_t* aux_w;
     const float* tail;     // non-null: fuse the CRAFT classifier tail (two 1x1 convs on 16 channels) into the epilogue (BN=64 config,
                            // cout_store 16): {b1[16], w2[32], b2[2]}; tail_frag: W1 as a bf16 MFMA A fragment [64 lanes][8]
     const uint16_t* tail_frag;
@@ -43,14 +45,12 @@ struct ConvArgs {
     const uint16_t* c11_w;
     const float* c11_b;
     int rgb_H, rgb_W;
-    unsigned long long* stamps;   // diagnostic (BBOCR_CONV_STAMPS): per workgroup {t_start, t_prologue, t_mainloop, t_end} s_memtime; null in production
     // conv3x3_up4_kernel (CRAFT upconv4 as ONE launch): in0 = the skip tensor s1 [N,H,W,128], addup/up_* = z = W_y y at half resolution,
     // aux_w / aux_b = the packed 1x1 weights (64 couts x 128 cin, BN = 64 plan) and bias of upconv4.conv.0; wpk / bias = upconv4.conv.3
-    const uint16_t* aux_w;
     const float* aux_b;
     float acc_scale;       // accumulators are multiplied by this before the bias (set from ConvPlan::acc_scale by launch_conv; 1 unless
                            // the packed weights carry a power-of-two scale, see the split-fp16 plans)
-    int lean;              // conv3x3_dma_kernel: which epilogue (set by its launcher: 0 shared, 1 / 2 plain lean with whole / half-line stores, 3 pooled lean)
+    int lean;              // conv3x3_dma_kernel: which epilogue (set by its launcher: 0 shared, 1 plain lean, 3 pooled lean)
     int split_off;         // > 0 (fp16 element type only): every stored value v goes out as the pair hi = fp16(v) at its channel and
                            // lo = fp16(v - hi) at channel + split_off -- the [hi | lo] activation layout of the exact recogniser mode
 };

@@ -407,10 +407,10 @@ hipError_t launch_lstm(const void* xproj, const uint16_t* whh_pk, uint16_t* out,
         return hipGetLastError();
     }
     const size_t smem8 = 2 * 32 * 16 * 16 + (size_t)8 * LSTM8_NL * 1024;
-    static const int pf_dist = diag_knob("BBOCR_LSTM_PF", 2);   // x prefetch distance in steps (0 = off)
+    constexpr int kPfDist = 2;      // x prefetch distance in steps (0 = off)
     auto go = [&](auto kern, LdsOptIn& attr) -> hipError_t {
         if (hipError_t e = lds_opt_in(attr, (const void*)kern, smem8); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(ntiles, 2), dim3(512), smem8, s, (const uint16_t*)xproj, whh_pk, out, (const int4*)tiles_dev, pf_dist);
+        hipLaunchKernelGGL(kern, dim3(ntiles, 2), dim3(512), smem8, s, (const uint16_t*)xproj, whh_pk, out, (const int4*)tiles_dev, kPfDist);
         return hipGetLastError();
     };
     static LdsOptIn attr_bf, attr_f16;

@@ -256,8 +256,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
         // event of this slot's feature parts: its launches are latency chains of 100-300 workgroups (BiLSTM: 4.9 us per time step against
         // 1 us of MFMA work) that leave most of the card idle -- with a second call in flight that call's detector fills it, instead of
         // waiting in (or making this stage wait in) the compute stream's FIFO.
-        static const bool own = (diag_knob("BBOCR_SEQ_STREAM", 1) != 0);      // A/B knob
-        hipStream_t ss = (own && c->seq_stream && c->feat_ev) ? c->seq_stream : c->stream;
+        hipStream_t ss = (c->seq_stream && c->feat_ev) ? c->seq_stream : c->stream;
         std::unique_lock<std::mutex> enq;
         if (ss == c->stream) enq = std::unique_lock<std::mutex>(c->root->enq_mu);
         else HIPCHK(hipStreamWaitEvent(ss, c->feat_ev, 0));

@@ -263,9 +263,8 @@ void load_craft(bbocr_ctx* c, const TensorMap& tm) {
     load_layer(c, tm, c->fc6, "basenet.slice5.1", "", 512, 1024, 3, 6, 6, det_el(c));
     // the long-K 1x1 GEMMs run 256-cout tiles (8 waves): their 128-cout tiles moved 24 KB of LDS-DMA per 2.1 MFLOP k-step and sat at the
     // DMA fill rate (~8 TB/s, 0.71 PFLOP/s); 32 KB per 4.2 MFLOP now
-    static const int bn1x1 = diag_knob("BBOCR_BN256_1X1", 1) ? 256 : 0;
-    load_layer(c, tm, c->fc7, "basenet.slice5.2", "", 1024, 1024, 1, 0, 1, det_el(c), false, bn1x1);
-    load_layer(c, tm, c->up1a, "upconv1.conv.0", "upconv1.conv.1", 1536, 512, 1, 0, 1, det_el(c), false, bn1x1);
+    load_layer(c, tm, c->fc7, "basenet.slice5.2", "", 1024, 1024, 1, 0, 1, det_el(c), false, 256);
+    load_layer(c, tm, c->up1a, "upconv1.conv.0", "upconv1.conv.1", 1536, 512, 1, 0, 1, det_el(c), false, 256);
     load_layer(c, tm, c->up1b, "upconv1.conv.3", "upconv1.conv.4", 512, 256, 3, 1, 1, det_el(c));
     load_split_1x1(c, tm, c->up2y, c->up2s, "upconv2.conv.0", "upconv2.conv.1", 256, 512, 256);
     load_layer(c, tm, c->up2b, "upconv2.conv.3", "upconv2.conv.4", 256, 128, 3, 1, 1, det_el(c));
@@ -349,7 +348,7 @@ void load_crnn(bbocr_ctx* c, const TensorMap& tm) {
             c->whh_scale[l] = pack_lstm_whh_split(hf, hb, pk.data());
             c->whh[l] = upload(c, pk);
         } else {
-            c->xproj[l] = make_plan(256, 2048, 1, 1, 0, 1, rec_el(c), diag_knob("BBOCR_BN256_XPROJ", 1) ? 256 : 0);
+            c->xproj[l] = make_plan(256, 2048, 1, 1, 0, 1, rec_el(c), 256);
             upload_plan(c, c->xproj[l], w, b);
             std::vector<uint16_t> pk(lstm_whh_packed_elems());
             pack_lstm_whh8(hf, hb, pk.data(), rec_el(c));
@@ -360,7 +359,7 @@ void load_crnn(bbocr_ctx* c, const TensorMap& tm) {
         if (rec_split(c)) {
             upload_split_plan(c, c->lin[l], 512, 256, 1, 1, 0, lw, lb, 1.f);     // reads lstm_exact_kernel's pair: lo = fp16(h - hi), unscaled
         } else {
-            c->lin[l] = make_plan(512, 256, 1, 1, 0, 1, rec_el(c), diag_knob("BBOCR_BN256_LIN", 1) ? 256 : 0);
+            c->lin[l] = make_plan(512, 256, 1, 1, 0, 1, rec_el(c), 256);
             upload_plan(c, c->lin[l], lw, lb);
         }
     }

@@ -1,9 +1,9 @@
 """A/B helper on a detector where every layer matters: run the NOISE-SENSITIVE CRAFT (tests/conftest.py) on 3 pages of 1280x960 (many
-tiles per persistent workgroup) + 4 pages of 640x480 under a list of environments (diagnostic build: BBOCR_* knobs) and compare every
+tiles per persistent workgroup) + 4 pages of 640x480 under a list of environments (one build each: BBOCR_LIB_PATH) and compare every
 heat-map with the first environment's, bit for bit.  The designed detector's lattice-valued maps (tools/ab_heat.py) can hide a
 low-order difference; this one cannot.
 
-  BBOCR_LIB_PATH=$PWD/bb-ocr_amd/libbbocr_diag.so python tools/ab_heat_noise.py [fp16|bf16] X=1 BBOCR_UP4_FUSED=0 BBOCR_UP3_POST=0 ...
+  python tools/ab_heat_noise.py [fp16|bf16] BBOCR_LIB_PATH=a/libbbocr.so BBOCR_LIB_PATH=b/libbbocr.so ...
 """
 import os, subprocess, sys, tempfile
 import numpy as np

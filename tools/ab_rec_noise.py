@@ -1,7 +1,7 @@
-"""A/B helper for the RECOGNISER half (diagnostic build): the whole readtext result -- boxes, texts, confidences as doubles -- of 8 bench
-pages + 2 faint-ink pages (contrast retry live) under a list of BBOCR_* environments, compared with the first one's exactly.
+"""A/B helper for the RECOGNISER half: the whole readtext result -- boxes, texts, confidences as doubles -- of 8 bench
+pages + 2 faint-ink pages (contrast retry live) under a list of environments (one build each: BBOCR_LIB_PATH), compared with the first one's exactly.
 
-  BBOCR_LIB_PATH=$PWD/bb-ocr_amd/libbbocr_diag.so python tools/ab_rec_noise.py fp16 X=1 BBOCR_CONV_RESW64=0 BBOCR_BN256_XPROJ=0 ...
+  python tools/ab_rec_noise.py fp16 BBOCR_LIB_PATH=a/libbbocr.so BBOCR_LIB_PATH=b/libbbocr.so ...
 """
 import os, pickle, subprocess, sys, tempfile
 
