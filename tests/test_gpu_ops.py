@@ -364,7 +364,7 @@ def test_fused_upconv4_kernel_equals_the_two_launch_path_bit_for_bit(tmp_path):
     (1,200 tiles on 512 persistent workgroups: second and third tiles per workgroup), eight runs: 0 differing values, every run.  The
     harness (tools/micro/up4_check.hip) is what found the two defects of the round-2 kernel: a bare s_barrier passed with an LDS read still
     queued, and packed-fp32 VALU writes into registers that MFMAs still in flight read as srcC.  Compiled here with the box's hipcc against
-    the in-tree library."""
+    the in-tree library.  Both paths against fp64, per element: tests/test_gpu_stages.py::test_up4_fused and ::test_addup."""
     import os
     import shutil
     import subprocess

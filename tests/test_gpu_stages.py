@@ -1,0 +1,293 @@
+"""-m gpu: every fused launch of the fast-mode detector, pool5 and the BiLSTM recurrence, ONE stage at a time with the production plans and
+packed side tables of a live context (tools/micro/stage_shim.hip), against the fp64 reference of its own operation (tests/stage_ref.py) under
+the tolerance rule stated there.  An L2 norm over a heat-map cannot see an error confined to a page border, a tile seam, the first pixel of the
+second page of a batch or one time step of 79; these checks are per element, and a failure names the element and the region it lies in.
+
+hipErrorNotSupported (801) from a stage is a failure: production would silently take its fallback path on that shape.
+Set BBOCR_STAGE_STATS=<file> to collect one JSON line per case (the table of DESIGN.md section 5)."""
+import ctypes as C
+import json
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import stage_ref as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEED = 3
+
+
+@pytest.fixture(scope="module")
+def shim_path(tmp_path_factory):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc on this box")
+    lib = os.path.join(ROOT, "bb-ocr_amd")
+    so = str(tmp_path_factory.mktemp("stage_shim") / "stage_shim.so")
+    cc = subprocess.run([hipcc, "-O2", "-std=c++20", "-shared", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(lib, "csrc"), "-I" + os.path.join(ROOT, "include"),
+                         os.path.join(ROOT, "tools", "micro", "stage_shim.hip"), "-L" + lib, "-lbbocr", "-Wl,-rpath," + lib, "-o", so],
+                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    assert cc.returncode == 0, cc.stdout.decode()[-2000:]
+    return so
+
+
+@pytest.fixture(scope="module")
+def stage_states():
+    from bb_ocr_amd import weights
+
+    return R.craft_state(SEED), weights.synthetic_crnn_state(SEED)
+
+
+class Stage:
+    """a Reader of one precision + the shim bound to its context"""
+
+    def __init__(self, so, states, el):
+        import bb_ocr_amd
+
+        self.el, self.dtype = el, R.DTYPES[el]
+        self.reader = bb_ocr_amd.Reader(["en"], gpu=True, weights=states, precision=el)      # loads libbbocr.so (after torch's HIP runtime)
+        self.lib = C.CDLL(so)
+        self.lib.stage_shim_error.restype = C.c_char_p
+        self.W = R.Weights(states[0], el)
+        self.crnn = states[1]
+        self.h = self.reader._h
+        assert self.lib.stage_shim_det_el(self.h) == self.lib.stage_shim_rec_el(self.h) == (1 if el == "fp16" else 0)
+
+    def call(self, fn, *args):
+        """tensors go as (pointer, element count); synchronises torch's stream first (the library runs on its own non-blocking one)"""
+        a = []
+        for x in args:
+            if torch.is_tensor(x):
+                assert x.is_cuda and x.is_contiguous()
+                a += [C.c_void_p(x.data_ptr()), C.c_size_t(x.numel())]
+            else:
+                a.append(x)
+        torch.cuda.synchronize()
+        rc = getattr(self.lib, fn)(self.h, *a)
+        assert rc == 0, f"{fn}: status {rc}" + (" (hipErrorNotSupported: production would take the fallback path)" if rc == 801 else "") + \
+            f" {self.lib.stage_shim_error().decode()}"
+
+    def twice(self, run):
+        """run() -> output tensor (NaN-filled before the launch); the two runs must agree bit for bit"""
+        a, b = run(), run()
+        v = lambda t: t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+        assert torch.equal(v(a), v(b)), f"two runs on the same input differ in {int((v(a) != v(b)).sum())} of {a.numel()} values"
+        return a.cpu()
+
+    def out(self, shape, dtype=None):
+        return torch.full(shape, float("nan"), dtype=dtype or self.dtype, device="cuda")
+
+
+@pytest.fixture(scope="module", params=["bf16", "fp16"])
+def st(request, shim_path, stage_states):
+    s = Stage(shim_path, stage_states, request.param)
+    yield s
+    s.reader.close()
+
+
+def _act(shape, el, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=g) * scale).to(R.DTYPES[el])
+
+
+def _record(stage, el, case, stats):
+    path = os.environ.get("BBOCR_STAGE_STATS")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps({"stage": stage, "el": el, "case": case, **stats}) + "\n")
+
+
+def _check(st, stage, case, got, refs, el_out, **kw):
+    _record(stage, st.el, case, R.check(got, *refs, el_out, f"{stage} {st.el} {case}", **kw))
+
+
+# ------------------------------------------------------------------------------------------------ conv1_1 in conv1_2's prologue + 2x2 pool
+@pytest.mark.parametrize("content", ["random", "zeros", "white"])
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("geom", [(17, 33, 32, 64), (32, 32, 32, 32), (50, 70, 64, 96), (96, 128, 96, 128), (1, 1, 32, 32)])
+def test_c11_conv1_2_pool(st, geom, N, content):
+    Hi, Wi, H32, W32 = geom
+    g = torch.Generator().manual_seed(100 + Hi)
+    rgb = {"random": lambda: torch.randint(0, 256, (N, Hi, Wi, 3), generator=g, dtype=torch.uint8),
+           "zeros": lambda: torch.zeros((N, Hi, Wi, 3), dtype=torch.uint8),
+           "white": lambda: torch.full((N, Hi, Wi, 3), 255, dtype=torch.uint8)}[content]()
+    d = rgb.cuda()
+
+    def run():
+        o = st.out((N, H32 // 2, W32 // 2, 64))
+        st.call("stage_c11_conv1_2_pool", d, N, Hi, Wi, H32, W32, o)
+        return o
+
+    got = st.twice(run)
+    beyond = torch.ones((H32 // 2, W32 // 2), dtype=torch.bool)
+    beyond[:Hi // 2, :Wi // 2] = False                  # pooled pixels whose 2x2 window touches the canvas beyond the page
+    _check(st, "c11+conv1_2+pool", f"{N}x{Hi}x{Wi} on {H32}x{W32} {content}", got, R.refs_c11(st.W, rgb, Hi, Wi, H32, W32, st.el), st.el, beyond=beyond)
+
+
+# ------------------------------------------------------------------------------------------------ two-source 1x1 (upconv1.conv.0)
+@pytest.mark.parametrize("shape", [(1, 2, 2), (3, 7, 5), (2, 16, 24)])
+def test_up1a_two_sources(st, shape):
+    N, H, W = shape
+    f7, s4 = _act((N, H, W, 1024), st.el, 200), _act((N, H, W, 512), st.el, 201)
+    df, ds = f7.cuda(), s4.cuda()
+
+    def run():
+        o = st.out((N, H, W, 512))
+        st.call("stage_up1a", df, ds, N, H, W, o)
+        return o
+
+    rq = R.up1a(st.W, f7, s4, st.el)
+    _check(st, "up1a", f"{N}x{H}x{W}", st.twice(run), (rq, rq, 0.0), st.el)
+
+
+# ------------------------------------------------------------------------------------------------ 1x1 + up-sampling added in the epilogue
+@pytest.mark.parametrize("shape", [(1, 4, 4), (3, 12, 20), (2, 40, 56), (1, 64, 96)])
+@pytest.mark.parametrize("level", [2, 3, 4])
+def test_addup(st, level, shape):
+    N, H, W = shape
+    cs, co = {2: (512, 256), 3: (256, 128), 4: (128, 64)}[level]
+    skip, z = _act((N, H, W, cs), st.el, 300 + level), _act((N, H // 2, W // 2, co), st.el, 310 + level)
+    dk, dz = skip.cuda(), z.cuda()
+
+    def run():
+        o = st.out((N, H, W, co))
+        st.call("stage_addup", level, dk, dz, N, H, W, o)
+        return o
+
+    rq = R.addup(st.W, level, skip, z, st.el)
+    _check(st, f"addup up{level}s", f"{N}x{H}x{W}", st.twice(run), (rq, rq, 0.0), st.el)
+
+
+# ------------------------------------------------------------------------------------------------ upconv3 3x3 with upconv4's y-half 1x1 behind it
+@pytest.mark.parametrize("shape", [(1, 16, 16), (2, 24, 40), (1, 56, 72)])
+def test_up3b_post_w(st, shape):
+    N, H, W = shape
+    u3a = _act((N, H, W, 128), st.el, 400)
+    d = u3a.cuda()
+
+    def run():
+        o = st.out((N, H, W, 64))
+        st.call("stage_up3b_post", d, N, H, W, o)
+        return o
+
+    _check(st, "up3b+post_w", f"{N}x{H}x{W}", st.twice(run), R.refs_up3b_post(st.W, u3a, st.el), st.el)
+
+
+# ------------------------------------------------------------------------------------------------ upconv4 as one launch
+@pytest.mark.parametrize("shape", [(1, 16, 16), (3, 48, 64), (4, 240, 320)])
+def test_up4_fused(st, shape):
+    N, H, W = shape
+    s1, z = _act((N, H, W, 128), st.el, 500), _act((N, H // 2, W // 2, 64), st.el, 501)
+    ds, dz = s1.cuda(), z.cuda()
+
+    def run():
+        o = st.out((N, H, W, 32))
+        st.call("stage_up4_fused", ds, dz, N, H, W, o)
+        return o
+
+    _check(st, "up4 fused", f"{N}x{H}x{W}", st.twice(run), R.refs_up4(st.W, s1, z, st.el), st.el)
+
+
+# ------------------------------------------------------------------------------------------------ conv_cls.4 + classifier tail
+@pytest.mark.parametrize("shape,scale", [((1, 16, 16), 1.0), ((2, 40, 56), 1.0), ((1, 112, 176), 1.0), ((2, 40, 56), 6.0)])
+def test_cls_tail(st, shape, scale):
+    N, H, W = shape
+    c2 = _act((N, H, W, 32), st.el, 600, scale)
+    d = c2.cuda()
+
+    def run():
+        o = st.out((N, H, W, 2), torch.float32)
+        st.call("stage_cls_tail", d, N, H, W, o)
+        return o
+
+    refs = R.refs_cls_tail(st.W, c2, st.el)
+    if scale > 1.0:             # the pushed case: both ReLUs clip on a sizeable share of the values
+        w4, b4 = st.W.cls4()
+        w1, b1, _, _ = st.W.tail()
+        y = R.conv(R.nchw(c2.double()), w4, b4, pad=1)
+        hpre = R.conv(torch.relu(y), w1, b1)
+        assert 0.2 < float((y < 0).double().mean()) < 0.8 and 0.2 < float((hpre < 0).double().mean()) < 0.8
+    _check(st, "cls4+tail", f"{N}x{H}x{W} x{scale:g}", st.twice(run), refs, None)
+
+
+# ------------------------------------------------------------------------------------------------ pool5
+@pytest.mark.parametrize("shape", [(1, 2, 2), (2, 6, 10), (1, 30, 40)])
+def test_pool5_bit_exact(st, shape):
+    N, H, W = shape
+    x = (torch.rand((N, H, W, 512), generator=torch.Generator().manual_seed(700)) * 8 - 4).to(st.dtype)
+    d = x.cuda()
+
+    def run():
+        o = st.out((N, H, W, 512))
+        st.call("stage_pool5", d, N, H, W, o)
+        return o
+
+    got, want = st.twice(run), R.pool5(x)
+    assert (want < 0).any()
+    diff = got.view(torch.int16) != want.view(torch.int16)
+    assert not diff.any(), f"pool5 {st.el} {shape}: {int(diff.sum())} values differ; by region {R.localise(diff)}"
+
+
+# ------------------------------------------------------------------------------------------------ BiLSTM recurrence, mixed tile table
+TILES = [(16, 15), (3, 79), (1, 15), (16, 255), (5, 639)]     # (sequences, T): T = imgW / 4 - 1 of the buckets 64, 320, 1024, 2560
+
+
+@pytest.mark.parametrize("sigma", [1.5, 0.3])
+@pytest.mark.parametrize("layer", [0, 1])
+def test_bilstm_mixed_tiles(st, layer, sigma):
+    assert st.lib.stage_shim_tile_seqs(st.h) == 16
+    perm = torch.tensor([st.lib.stage_shim_xproj_channel(d, g, u) for d in range(2) for g in range(4) for u in range(256)], dtype=torch.long)
+    assert sorted(perm.tolist()) == list(range(2048))
+    gen = torch.Generator().manual_seed(800 + layer)
+    xs = [R.rnd(torch.randn((n, T, 2, 1024), generator=gen, dtype=torch.float64) * sigma, st.el) for n, T in TILES]
+    rows = sum(n * T for n, T in TILES)
+    rows_pad = (rows + 255) // 256 * 256                 # bbocr_crnn_logits' rows_pad: the kernel prefetches x two steps ahead
+    xproj = torch.zeros((rows_pad, 2048), dtype=torch.float64)
+    table, row0 = [], 0
+    for (n, T), x in zip(TILES, xs):
+        xproj[row0:row0 + n * T, perm] = x.reshape(n * T, 2048)
+        table.append((row0, n, T, 0))
+        row0 += n * T
+    dx = xproj.to(st.dtype).cuda()
+
+    def launch(entries):
+        o = st.out((rows_pad, 512))
+        t = np.ascontiguousarray(np.array(entries, dtype=np.int32))
+        torch.cuda.synchronize()
+        rc = st.lib.stage_lstm(st.h, layer, C.c_void_p(dx.data_ptr()), C.c_void_p(o.data_ptr()), C.c_size_t(rows_pad), t.ctypes.data_as(C.POINTER(C.c_int)), len(entries))
+        assert rc == 0, f"stage_lstm: status {rc} {st.lib.stage_shim_error().decode()}"
+        return o
+
+    got = st.twice(lambda: launch(table))
+    assert torch.isnan(got[rows:].float()).all()         # nothing is written behind the last sequence
+    # tiles are independent: the same sequences, one tile per launch, give the same rows bit for bit
+    for k, (r0, n, T, _) in enumerate(table):
+        alone = launch([table[k]]).cpu()
+        assert torch.equal(alone[r0:r0 + n * T].view(torch.int16), got[r0:r0 + n * T].view(torch.int16)), f"tile {k} differs when launched alone"
+    wf, wb = R.lstm_weights(st.crnn, layer, st.el)
+    rq, rn = [], []
+    for x in xs:
+        q, nq, _ = R.refs_bilstm(wf, wb, x, st.el)
+        rq.append(q.reshape(-1, 512))
+        rn.append(nq.reshape(-1, 512))
+    rq, rn = torch.cat(rq), torch.cat(rn)
+    E = 2.0 * (rq - rn).abs().max().item()
+    g64 = got[:rows].double()
+    try:
+        _check(st, f"bilstm layer {layer}", f"sigma {sigma:g}", g64, (rq, rn, E), st.el, index_names=("row", "channel (fwd 0-255 | bwd 256-511)"))
+    except AssertionError as e:
+        tight, _ = R.bounds(rq, rn, E, st.el)
+        miss = ~((g64 - rq).abs() <= tight)
+        where = []
+        for k, (r0, n, T, _) in enumerate(table):
+            m = miss[r0:r0 + n * T].reshape(n, T, 2, 256)
+            if m.any():
+                s, t, d, _u = [int(v[0]) for v in torch.nonzero(m, as_tuple=True)]
+                where.append(f"tile {k} ({n} x T={T}, first row {r0}): {int(m.sum())} beyond tight, first at sequence {s}, t {t}, {'bwd' if d else 'fwd'}")
+        raise AssertionError(str(e) + "; " + "; ".join(where)) from None

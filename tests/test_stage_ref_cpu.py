@@ -1,0 +1,219 @@
+"""The stage references of tests/stage_ref.py ARE the oracle, and the checks built on them have teeth (no GPU).
+
+* composition: the un-rounded stage functions chained in craft_forward's order equal oracle.nets.CRAFT in double; the recurrence equals
+  torch.nn.LSTM in double -- which also proves the identities the fast path relies on (up-sampling commuted behind the 1x1, the concat split);
+* sensitivity: every named mistake moves at least one element beyond the allowance bound, so a kernel making it fails its GPU test;
+* cap: torch-fp32 arithmetic standing in for the kernel passes the whole rule (allowance, 1-in-1,000 cap, rms ratio) on every two-rounding stage;
+* the shim the GPU tests load compiles for gfx950.
+"""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import stage_ref as R
+
+ELS = ["bf16", "fp16"]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def craft_sd():
+    return R.craft_state(3)
+
+
+@pytest.fixture(scope="module")
+def crnn_sd():
+    from bb_ocr_amd import weights
+
+    return weights.synthetic_crnn_state(0)
+
+
+def _act(shape, el, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=g) * scale).to(R.DTYPES[el])
+
+
+def _rgb(N, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 256, (N, H, W, 3), generator=g, dtype=torch.uint8)
+
+
+def _standin(fn, el_out):
+    """torch-fp32 arithmetic with the kernel's rounding points, output stored in the element type"""
+    return R.round_out(fn(torch.float32).double(), el_out)
+
+
+# ------------------------------------------------------------------------------------------------ composition
+def test_stage_chain_is_the_oracle_craft(craft_sd):
+    from oracle import nets
+
+    W = R.Weights(craft_sd, None)
+    rgb = _rgb(1, 96, 128, 1)
+    L = lambda conv, bn=None: W.layer(conv, bn)
+    c = lambda x, wb, pad=1, dil=1: R.conv(x, wb[0], wb[1], pad=pad, dil=dil)
+    nq = dict(q=False)
+    p1 = R.nchw(R.c11_conv1_2_pool(W, rgb, 96, 128, 96, 128, None, **nq))
+    a3 = F.relu(c(p1, L("basenet.slice1.7", "basenet.slice1.8")))
+    s1 = c(a3, L("basenet.slice1.10", "basenet.slice1.11"))
+    p2 = F.max_pool2d(F.relu(s1), 2)
+    a5 = F.relu(c(p2, L("basenet.slice2.14", "basenet.slice2.15")))
+    s2 = c(a5, L("basenet.slice2.17", "basenet.slice2.18"))
+    p3 = F.max_pool2d(F.relu(c(F.relu(s2), L("basenet.slice3.20", "basenet.slice3.21"))), 2)
+    a8 = F.relu(c(p3, L("basenet.slice3.24", "basenet.slice3.25")))
+    s3 = c(a8, L("basenet.slice3.27", "basenet.slice3.28"))
+    p4 = F.max_pool2d(F.relu(c(F.relu(s3), L("basenet.slice4.30", "basenet.slice4.31"))), 2)
+    a11 = F.relu(c(p4, L("basenet.slice4.34", "basenet.slice4.35")))
+    s4 = c(a11, L("basenet.slice4.37", "basenet.slice4.38"))
+    p5 = R.nchw(R.pool5(R.nhwc(s4)))
+    f6 = c(p5, L("basenet.slice5.1"), pad=6, dil=6)
+    f7 = c(f6, L("basenet.slice5.2"), pad=0)
+    u1a = R.nchw(R.up1a(W, R.nhwc(f7), R.nhwc(s4), None, **nq))
+    u1b = F.relu(c(u1a, L("upconv1.conv.3", "upconv1.conv.4")))
+    u2a = R.nchw(R.addup(W, 2, R.nhwc(s3), R.nhwc(R.conv(u1b, W.upN(2)[0])), None, **nq))
+    u2b = F.relu(c(u2a, L("upconv2.conv.3", "upconv2.conv.4")))
+    u3a = R.addup(W, 3, R.nhwc(s2), R.nhwc(R.conv(u2b, W.upN(3)[0])), None, **nq)
+    z4 = R.up3b_post(W, u3a, None, **nq)
+    u4b = R.nchw(R.up4(W, R.nhwc(s1), z4, None, **nq))
+    c1 = F.relu(c(u4b, L("conv_cls.0")))
+    c2 = F.relu(c(c1, L("conv_cls.2")))
+    heat = R.cls_tail(W, R.nhwc(c2), None, **nq)
+
+    net = nets.load_state_dict_any(nets.CRAFT(), {k: torch.from_numpy(np.asarray(v)) for k, v in craft_sd.items()}).double().eval()
+    with torch.no_grad():
+        want, feat = net(R.normalise(rgb, 96, 128, 96, 128, None, False, torch.float64))
+    assert heat.shape == want.shape == (1, 48, 64, 2)
+    assert (u4b - feat).abs().max().item() <= 1e-9 * max(1.0, feat.abs().max().item())
+    assert (heat - want).abs().max().item() <= 1e-9
+
+
+def test_recurrence_is_torch_lstm():
+    torch.manual_seed(5)
+    rnn = torch.nn.LSTM(256, 256, bidirectional=True, batch_first=True).double()
+    x = torch.randn(3, 21, 256, dtype=torch.float64)
+    with torch.no_grad():
+        want, _ = rnn(x)
+        xp = torch.stack([x @ rnn.weight_ih_l0.t() + rnn.bias_ih_l0 + rnn.bias_hh_l0,
+                          x @ rnn.weight_ih_l0_reverse.t() + rnn.bias_ih_l0_reverse + rnn.bias_hh_l0_reverse], dim=2)
+        got = R.bilstm(rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, xp, None, q=False)
+    assert (got - want).abs().max().item() <= 1e-12
+
+
+def test_weight_folding_is_the_packers_fp32_arithmetic(craft_sd):
+    """the rounded weights come from fold_conv's fp32 product, not from an fp64 fold: the two differ on a few weights per layer"""
+    w32, b32 = R.Weights(craft_sd, "bf16").layer("upconv1.conv.0", "upconv1.conv.1")
+    w64, _ = R.Weights(craft_sd, None).layer("upconv1.conv.0", "upconv1.conv.1")
+    assert torch.equal(w32, R.rnd(w32, "bf16")) and torch.equal(b32, b32.float().double())
+    assert (w32 - w64).abs().max().item() <= 2.0 ** -8 * w64.abs().max().item()
+
+
+# ------------------------------------------------------------------------------------------------ sensitivity
+def _assert_sensitive(name, refs, mutated, el_out):
+    rq, rn, E = refs
+    assert not R.fails_allowance(rq, rq, rn, E, el_out), f"{name}: ref_q itself misses the allowance"
+    assert R.fails_allowance(mutated, rq, rn, E, el_out), f"{name}: the mistake stays inside the allowance -- the GPU check could not see it"
+    with pytest.raises(AssertionError):            # and the rule as the GPU tests apply it rejects a kernel that stores exactly this
+        R.check(R.round_out(mutated, el_out), rq, rn, E, el_out, name)
+
+
+@pytest.mark.parametrize("el", ELS)
+def test_sensitivity_c11(craft_sd, el):
+    W = R.Weights(craft_sd, el)
+    rgb = _rgb(2, 17, 33, 2)
+    refs = R.refs_c11(W, rgb, 17, 33, 32, 64, el)
+    for mut in ("canvas_norm0", "pad_relu_bias"):
+        _assert_sensitive(mut, refs, R.c11_conv1_2_pool(W, rgb, 17, 33, 32, 64, el, mut=mut), el)
+
+
+@pytest.mark.parametrize("el", ELS)
+def test_sensitivity_up1a(craft_sd, el):
+    W = R.Weights(craft_sd, el)
+    f7, s4 = _act((2, 4, 6, 1024), el, 3), _act((2, 4, 6, 512), el, 4)
+    rq = R.up1a(W, f7, s4, el)
+    swapped = R.up1a(W, f7, s4, el, mut="concat_swapped")       # the skip tensor's 512 columns applied to fc7's first channels and vice versa
+    _assert_sensitive("concat_swapped", (rq, rq, 0.0), swapped, el)
+
+
+@pytest.mark.parametrize("level", [2, 3, 4])
+@pytest.mark.parametrize("el", ELS)
+def test_sensitivity_addup(craft_sd, el, level):
+    W = R.Weights(craft_sd, el)
+    cs, co = {2: (512, 256), 3: (256, 128), 4: (128, 64)}[level]
+    skip, z = _act((3, 12, 20, cs), el, 5), _act((3, 6, 10, co), el, 6)
+    rq = R.addup(W, level, skip, z, el)
+    for mut in ("align_corners", "nearest", "edge_unclamped", "page_off_by_one"):
+        _assert_sensitive(mut, (rq, rq, 0.0), R.addup(W, level, skip, z, el, mut=mut), el)
+
+
+@pytest.mark.parametrize("el", ELS)
+def test_sensitivity_post_w_up4_tail_pool5(craft_sd, el):
+    W = R.Weights(craft_sd, el)
+    u3a = _act((1, 16, 16, 128), el, 7)
+    _assert_sensitive("relu_after_post", R.refs_up3b_post(W, u3a, el), R.up3b_post(W, u3a, el, mut="relu_after_post"), el)
+    s1, z = _act((2, 16, 16, 128), el, 8), _act((2, 8, 8, 64), el, 9)
+    refs = R.refs_up4(W, s1, z, el)
+    for mut in ("align_corners", "nearest", "edge_unclamped", "page_off_by_one"):
+        _assert_sensitive("up4 " + mut, refs, R.up4(W, s1, z, el, mut=mut), el)
+    c2 = _act((1, 16, 16, 32), el, 10, 2.0)
+    _assert_sensitive("w1_transposed", R.refs_cls_tail(W, c2, el), R.cls_tail(W, c2, el, mut="w1_transposed"), None)
+    x = (torch.rand((1, 6, 10, 512), generator=torch.Generator().manual_seed(11)) * 8 - 4).to(R.DTYPES[el])
+    assert not torch.equal(R.pool5(x, mut="zero_pad").view(torch.int16), R.pool5(x).view(torch.int16))
+    assert (R.pool5(x)[0, 0, 0] < 0).any()           # a corner window of negative values: 0-padding would win there
+
+
+@pytest.mark.parametrize("el", ELS)
+def test_sensitivity_bilstm(crnn_sd, el):
+    wf, wb = R.lstm_weights(crnn_sd, 0, el)
+    g = torch.Generator().manual_seed(12)
+    x = R.rnd(torch.randn((3, 15, 2, 1024), generator=g, dtype=torch.float64) * 1.5, el)
+    pad = R.rnd(torch.randn((3, 2, 2, 1024), generator=g, dtype=torch.float64) * 1.5, el)
+    refs = R.refs_bilstm(wf, wb, x, el)
+    for mut in ("gate_order", "bwd_padded_start", "carry_c"):
+        _assert_sensitive(mut, refs, R.bilstm(wf, wb, x, el, mut=mut, pad_x=pad), el)
+
+
+# ------------------------------------------------------------------------------------------------ cap: fp32 arithmetic passes the whole rule
+@pytest.mark.parametrize("el", ELS)
+def test_fp32_standin_passes_the_rule_on_every_two_rounding_stage(craft_sd, crnn_sd, el):
+    W = R.Weights(craft_sd, el)
+    rgb = _rgb(2, 50, 70, 20)
+    got = _standin(lambda dt: R.c11_conv1_2_pool(W, rgb, 50, 70, 64, 96, el, True, dt), el)
+    R.check(got, *R.refs_c11(W, rgb, 50, 70, 64, 96, el), el, f"c11 stand-in {el}")
+    u3a = _act((2, 24, 40, 128), el, 21)
+    R.check(_standin(lambda dt: R.up3b_post(W, u3a, el, True, dt), el), *R.refs_up3b_post(W, u3a, el), el, f"post_w stand-in {el}")
+    s1, z = _act((2, 48, 64, 128), el, 22), _act((2, 24, 32, 64), el, 23)
+    R.check(_standin(lambda dt: R.up4(W, s1, z, el, True, dt), el), *R.refs_up4(W, s1, z, el), el, f"up4 stand-in {el}")
+    c2 = _act((2, 40, 56, 32), el, 24, 2.0)
+    R.check(_standin(lambda dt: R.cls_tail(W, c2, el, True, dt), None), *R.refs_cls_tail(W, c2, el), None, f"tail stand-in {el}")
+    wf, wb = R.lstm_weights(crnn_sd, 0, el)
+    for sigma in (1.5, 0.3):
+        x = R.rnd(torch.randn((16, 79, 2, 1024), generator=torch.Generator().manual_seed(25), dtype=torch.float64) * sigma, el)
+        R.check(_standin(lambda dt: R.bilstm(wf, wb, x, el, True, dt), el), *R.refs_bilstm(wf, wb, x, el), el, f"bilstm stand-in {el} sigma {sigma}",
+                index_names=("seq", "t", "c"))
+
+
+def test_the_rule_rejects_truncation(craft_sd):
+    """rounding toward zero instead of to nearest doubles the noise: the rms condition (and the tight bound) see it"""
+    el = "bf16"
+    W = R.Weights(craft_sd, el)
+    skip, z = _act((1, 12, 20, 256), el, 30), _act((1, 6, 10, 128), el, 31)
+    rq = R.addup(W, 3, skip, z, el)
+    trunc = (rq.float().view(torch.int32) & ~0xFFFF).view(torch.float32).double()
+    with pytest.raises(AssertionError):
+        R.check(trunc, rq, rq, 0.0, el, "truncating stand-in")
+    R.check(R.rnd(rq, el), rq, rq, 0.0, el, "rounding stand-in")
+
+
+# ------------------------------------------------------------------------------------------------ the shim compiles
+def test_stage_shim_compiles(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc on this box")
+    cc = subprocess.run([hipcc, "-O2", "-std=c++20", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "bb-ocr_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
+                         "-c", os.path.join(ROOT, "tools", "micro", "stage_shim.hip"), "-o", str(tmp_path / "stage_shim.o")],
+                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    assert cc.returncode == 0, cc.stdout.decode()[-2000:]

@@ -1,0 +1,185 @@
+// Test-only shim (tests/test_gpu_stages.py): runs ONE stage of the fast-mode detector / recogniser with the production plans and packed side
+// tables of a live context, so that each fused launch can be compared with an fp64 reference of its own operation (tests/stage_ref.py).
+// No kernels of its own.  Built by the test as a shared object against the in-tree library:
+//   hipcc -O2 -std=c++20 -shared -fPIC --offload-arch=gfx950 -Ibb-ocr_amd/csrc -Iinclude tools/micro/stage_shim.hip -Lbb-ocr_amd -lbbocr -o stage_shim.so
+// Every function takes the bbocr_ctx* of a Reader, device pointers of caller-owned tensors with their element counts (checked against the
+// shapes before anything is launched), runs on c->stream, waits for it and returns the hipError_t as an int (0 = success); a StatusError of the
+// library comes back as SHIM_STATUS + |code|, anything else as SHIM_UNKNOWN, with the text in stage_shim_error().
+#include "ctx.h"
+
+namespace {
+constexpr int SHIM_STATUS = 10000, SHIM_UNKNOWN = 19999, SHIM_BAD_ARGS = 20000;
+std::string g_err;
+
+template <typename F> int run_stage(bbocr_ctx* c, F&& f) {
+    g_err.clear();
+    if (!c) { g_err = "null context"; return SHIM_BAD_ARGS; }
+    try {
+        hipError_t e = hipSetDevice(c->cfg.device);
+        if (e != hipSuccess) return (int)e;
+        c->cur = c->stream;                       // the layer helpers launch on c->cur; outside a guarded() call nothing has set it
+        e = f();
+        const hipError_t s = hipStreamSynchronize(c->stream);
+        return (int)(e != hipSuccess ? e : s);
+    } catch (const StatusError& se) {
+        g_err = se.msg;
+        (void)hipStreamSynchronize(c->stream);
+        return SHIM_STATUS + std::abs(se.code);
+    } catch (const std::exception& ex) {
+        g_err = ex.what();
+        (void)hipStreamSynchronize(c->stream);
+        return SHIM_UNKNOWN;
+    } catch (...) {
+        g_err = "unknown failure";
+        (void)hipStreamSynchronize(c->stream);
+        return SHIM_UNKNOWN;
+    }
+}
+
+bool fast_detector(const bbocr_ctx* c) { return c->craft_loaded && !det_split(c); }
+size_t px(int N, int H, int W) { return (size_t)N * H * W; }
+bool dims_ok(int N, int H, int W) { return N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 26); }
+#define NEED(cond)                                                         \
+    do {                                                                   \
+        if (!(cond)) { g_err = "bad arguments: " #cond; return SHIM_BAD_ARGS; } \
+    } while (0)
+
+// helper-allocated outputs live in the context's arena: dry pass, arena.buf.ensure, real pass (as bbocr_crnn_logits does), then a copy out
+template <typename F> hipError_t with_arena(bbocr_ctx* c, uint16_t* out, size_t out_elems, F&& stage) {
+    c->arena.begin(true);
+    (void)stage();
+    c->arena.buf.ensure(c->arena.off);
+    c->arena.begin(false);
+    const Act o = stage();
+    if ((size_t)o.N * o.H * o.W * o.C != out_elems) fail(BBOCR_ERR_INTERNAL, "stage shim: output size differs from the caller's tensor");
+    return hipMemcpyAsync(out, o.p, out_elems * 2, hipMemcpyDeviceToDevice, c->stream);
+}
+}  // namespace
+
+extern "C" {
+
+const char* stage_shim_error() { return g_err.c_str(); }
+int stage_shim_det_el(bbocr_ctx* c) { return c ? det_el(c) : -1; }
+int stage_shim_rec_el(bbocr_ctx* c) { return c ? rec_el(c) : -1; }
+int stage_shim_xproj_channel(int dir, int gate, int unit) { return lstm8_xproj_channel(dir, gate, unit); }
+int stage_shim_tile_seqs(bbocr_ctx* c) { return c ? lstm_tile_seqs(rec_mode(c)) : -1; }
+
+// normalise + conv1_1 + ReLU produced in conv1_2's prologue, conv1_2 + BN + ReLU, 2x2 max-pool: rgb uint8 [N, Himg, Wimg, 3] on the zero
+// canvas H32 x W32 -> out [N, H32/2, W32/2, 64]
+int stage_c11_conv1_2_pool(bbocr_ctx* c, const uint8_t* rgb, size_t rgb_elems, int N, int Himg, int Wimg, int H32, int W32, uint16_t* out, size_t out_elems) {
+    NEED(c && fast_detector(c) && rgb && out && dims_ok(N, H32, W32) && Himg > 0 && Wimg > 0 && Himg <= H32 && Wimg <= W32 && H32 % 32 == 0 && W32 % 32 == 0);
+    NEED(rgb_elems == px(N, Himg, Wimg) * 3 && out_elems == px(N, H32 / 2, W32 / 2) * 64);
+    return run_stage(c, [&] {
+        return with_arena(c, out, out_elems, [&] {
+            const Act canvas{nullptr, N, H32, W32, 64};
+            const RgbSource src{rgb, Himg, Wimg};
+            return conv_pool_act(c, c->conv1_2, canvas, false, true, 64, 1, false, nullptr, &src);
+        });
+    });
+}
+
+// upconv1's 1x1 over the virtual concat [fc7 (1024) | relu5_3 (512)] + BN + ReLU -> out [N, H, W, 512]
+int stage_up1a(bbocr_ctx* c, const uint16_t* f7, size_t f7_elems, const uint16_t* s4, size_t s4_elems, int N, int H, int W, uint16_t* out, size_t out_elems) {
+    NEED(c && fast_detector(c) && f7 && s4 && out && dims_ok(N, H, W));
+    NEED(f7_elems == px(N, H, W) * 1024 && s4_elems == px(N, H, W) * 512 && out_elems == px(N, H, W) * 512);
+    return run_stage(c, [&] {
+        return with_arena(c, out, out_elems, [&] {
+            const Act a0{(uint16_t*)f7, N, H, W, 1024}, a1{(uint16_t*)s4, N, H, W, 512};
+            return conv_act(c, c->up1a, a0, false, &a1, false, true, 512);
+        });
+    });
+}
+
+// the skip half of a U-net 1x1 with up(z) added in its epilogue (craft_forward::up_stage's second launch; level 4: the first launch of
+// upconv4's two-launch path): skip [N, H, W, Cs], z [N, H/2, W/2, cout] -> out [N, H, W, cout] = ReLU(up(z) + W_s skip + b)
+int stage_addup(bbocr_ctx* c, int level, const uint16_t* skip, size_t skip_elems, const uint16_t* z, size_t z_elems, int N, int H, int W, uint16_t* out,
+                size_t out_elems) {
+    NEED(c && fast_detector(c) && skip && z && out && dims_ok(N, H, W) && H % 2 == 0 && W % 2 == 0 && level >= 2 && level <= 4);
+    const ConvPlan& ps = level == 2 ? c->up2s : (level == 3 ? c->up3s : c->up4s);
+    const int Cs = ps.Cin, cout = ps.Cout;
+    NEED(skip_elems == px(N, H, W) * Cs && z_elems == px(N, H / 2, W / 2) * cout && out_elems == px(N, H, W) * cout);
+    return run_stage(c, [&] {
+        c->arena.begin(false);                    // run_conv is a no-op in a dry pass; nothing is carved from the arena here
+        const Act sk{(uint16_t*)skip, N, H, W, Cs}, zz{(uint16_t*)z, N, H / 2, W / 2, cout};
+        run_conv(c, ps, sk, false, nullptr, false, true, out, cout, cout, false, &zz);
+        return hipSuccess;
+    });
+}
+
+// upconv3's 3x3 + BN + ReLU with z = W_y u3b (upconv4's y-half 1x1) applied in the epilogue: u3a [N, H, W, 128] -> z [N, H, W, 64]
+int stage_up3b_post(bbocr_ctx* c, const uint16_t* u3a, size_t u3a_elems, int N, int H, int W, uint16_t* z, size_t z_elems) {
+    NEED(c && fast_detector(c) && c->up4y_post && u3a && z && dims_ok(N, H, W));
+    NEED(u3a_elems == px(N, H, W) * 128 && z_elems == px(N, H, W) * 64);
+    return run_stage(c, [&] {
+        // detector.cpp::craft_forward, "if (c->up4y_post && !c->up3b.split)": hipErrorNotSupported is returned, production would fall back
+        ConvArgs a{};
+        a.in0 = u3a; a.C0 = 128; a.in0_cs = 128;
+        a.N = N; a.H = H; a.W = W;
+        a.relu_out = 1; a.out = z; a.out_cs = 64; a.cout_store = 64; a.post_w = c->up4y_post;
+        return launch_conv_profiled(c, c->up3b, a, true);
+    });
+}
+
+// upconv4 as one launch: s1 [N, H, W, 128], z [N, H/2, W/2, 64] -> u4b [N, H, W, 32]
+int stage_up4_fused(bbocr_ctx* c, const uint16_t* s1, size_t s1_elems, const uint16_t* z, size_t z_elems, int N, int H, int W, uint16_t* u4b, size_t u4b_elems) {
+    NEED(c && fast_detector(c) && s1 && z && u4b && dims_ok(N, H, W) && H % 2 == 0 && W % 2 == 0);
+    NEED(s1_elems == px(N, H, W) * 128 && z_elems == px(N, H / 2, W / 2) * 64 && u4b_elems == px(N, H, W) * 32);
+    return run_stage(c, [&] {
+        // detector.cpp::craft_forward, the block behind "upconv4 as ONE launch" (launch_up4_profiled with profiling off)
+        ConvArgs a{};
+        a.in0 = s1; a.C0 = 128; a.in0_cs = 128;
+        a.N = N; a.H = H; a.W = W;
+        a.addup = z; a.up_H = H; a.up_W = W; a.up_cs = 64;
+        a.relu_out = 1; a.out = u4b; a.out_cs = 32; a.cout_store = 32;
+        a.zero = c->zero_page;
+        return launch_up4_fused(c->up4s, c->up4b, a, c->cur);
+    });
+}
+
+// conv_cls.4 (3x3 32 -> 16 + ReLU) with conv_cls.6 / .8 in its epilogue: c2 [N, H, W, 32] -> heat fp32 [N, H, W, 2]
+int stage_cls_tail(bbocr_ctx* c, const uint16_t* c2, size_t c2_elems, int N, int H, int W, float* heat, size_t heat_elems) {
+    NEED(c && fast_detector(c) && c->cls_tail && c->cls_tail_frag && c2 && heat && dims_ok(N, H, W));
+    NEED(c2_elems == px(N, H, W) * 32 && heat_elems == px(N, H, W) * 2);
+    return run_stage(c, [&] {
+        // detector.cpp::craft_forward, the block behind "conv_cls.4 ... with conv_cls.6/.8 fused into its epilogue"
+        ConvArgs a{};
+        a.in0 = c2; a.C0 = 32; a.in0_cs = 32;
+        a.N = N; a.H = H; a.W = W;
+        a.relu_out = 1; a.out = heat; a.out_cs = 16; a.cout_store = 16; a.tail = c->cls_tail; a.tail_frag = c->cls_tail_frag;
+        return launch_conv_profiled(c, c->cls4, a);
+    });
+}
+
+// pool5 = MaxPool2d(3, 1, 1) without ReLU: in [N, H, W, 512] -> out [N, H, W, 512]
+int stage_pool5(bbocr_ctx* c, const uint16_t* in, size_t in_elems, int N, int H, int W, uint16_t* out, size_t out_elems) {
+    NEED(c && in && out && dims_ok(N, H, W) && in_elems == px(N, H, W) * 512 && out_elems == in_elems);
+    return run_stage(c, [&] {
+        return with_arena(c, out, out_elems, [&] {
+            const Act a{(uint16_t*)in, N, H, W, 512};
+            return pool_act(c, a, 3, 3, 1, 1, 1, 1, false);
+        });
+    });
+}
+
+// BiLSTM recurrence of layer l over a tile table given on the HOST (int4 {first row, sequences, T, 0} per workgroup): xproj [rows_pad, 2048]
+// in the permuted channel order, out [rows_pad, 512] (fwd | bwd).  rows_pad: a multiple of 256, as bbocr_crnn_logits allocates.
+int stage_lstm(bbocr_ctx* c, int layer, const uint16_t* xproj, uint16_t* out, size_t rows_pad, const int* tiles_host, int ntiles) {
+    NEED(c && c->crnn_loaded && !rec_split(c) && (layer == 0 || layer == 1) && c->whh[layer] && xproj && out && tiles_host && ntiles > 0 && ntiles <= 65535);
+    NEED(rows_pad > 0 && rows_pad % 256 == 0 && rows_pad < ((size_t)1 << 24));
+    const int cap = lstm_tile_seqs(rec_mode(c));
+    for (int i = 0; i < ntiles; ++i) {
+        const int row0 = tiles_host[4 * i], n = tiles_host[4 * i + 1], T = tiles_host[4 * i + 2];
+        NEED(row0 >= 0 && n >= 1 && n <= cap && T >= 1 && (size_t)row0 + (size_t)n * T <= rows_pad);
+    }
+    return run_stage(c, [&] {
+        int* tiles_dev = nullptr;
+        HIPCHK(hipMalloc((void**)&tiles_dev, (size_t)ntiles * 16));
+        hipError_t e = hipMemcpy(tiles_dev, tiles_host, (size_t)ntiles * 16, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_lstm(xproj, c->whh[layer], out, tiles_dev, ntiles, rec_mode(c), c->whh_scale[layer], c->stream);
+        const hipError_t s = hipStreamSynchronize(c->stream);
+        (void)hipFree(tiles_dev);
+        return e != hipSuccess ? e : s;
+    });
+}
+
+}  // extern "C"
