@@ -248,7 +248,6 @@ int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* 
             HIPCHK(launch_gray(dev_rgb, (uint8_t*)ctx->gray.p, (size_t)B * H * W, ctx->stream));
             dev_gray = (const uint8_t*)ctx->gray.p;
         }
-        auto t0 = clk::now();
         // The whole detector is enqueued first (one event per sub-batch, no host wait); box extraction of sub-batch k then
         // runs on the second stream + host threads while sub-batch k+1 is still in the detector.
         std::vector<std::pair<int, int>> subs;
@@ -286,7 +285,6 @@ int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* 
         float det_ms = 0.f;
         HIPCHK(hipEventElapsedTime(&det_ms, ctx->det_t0, ctx->det_t1));
         ctx->times[0] = det_ms;          // GPU span of the detector; box extraction (times[1], times[2]) overlaps it except for the last sub-batch
-        (void)t0;
         std::vector<BoxJob> jobs;
         std::vector<int> off;
         recognize_impl(ctx, dev_gray, B, H, W, hb, pp, jobs, off, &early);

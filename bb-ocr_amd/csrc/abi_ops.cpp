@@ -114,9 +114,7 @@ int bbocr_op_conv2d(bbocr_ctx* ctx, const uint16_t* dev_in, int N, int H, int W,
         const size_t owned0 = ctx->owned.size();
         upload_plan(ctx, p, wv, bv);
         const int store = cdiv(Cout, 16) * 16;
-        ConvArgs a{};
-        a.in0 = dev_in; a.C0 = Cin; a.in0_cs = Cin;
-        a.N = N; a.H = H; a.W = W;
+        ConvArgs a = conv_args(p, Act{(uint16_t*)dev_in, N, H, W, Cin});
         a.relu_in0 = relu_in != 0; a.relu_out = relu_out != 0; a.out_f32 = out_f32 != 0;
         a.out = dev_out; a.out_cs = store; a.cout_store = store;
         a.pool_mode = pool_mode; a.pool_relu = pool_relu != 0; a.store_full = (pool_mode && dev_out) ? 1 : 0; a.pool_cs = store; a.pool_out = dev_pool_out;
@@ -133,23 +131,29 @@ int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW
     return guarded(ctx, [&](bbocr_ctx* ctx) {
         if (!ctx->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
         if (!dev_crops || !dev_logits || n <= 0 || imgW < 64 || (imgW & 63)) fail(BBOCR_ERR_ARG, "bad crop batch");
-        const int T = imgW / 4 - 1;
-        const size_t rows = (size_t)n * T, rows_pad = align_up(rows, 256);
+        // what a recognition pass runs: the n crops planned as one part, side by side in its wide image with REC_GAP zero columns between
+        // them (a cleared buffer: 0 is the padding value, and the padding code of the exact mode), conv stack over the wide image with the
+        // gaps cleared after every layer, gathered 3-row mean, the part's LSTM tile table, sequence stage
+        std::vector<BoxJob> jobs(n);
+        std::vector<int> all(n);
+        for (int i = 0; i < n; ++i) { jobs[i].d = CropDesc{}; jobs[i].d.imgW = imgW; all[i] = i; }
+        RecPart part;
+        rec_plan_part(jobs, all, 0, 0, part);
+        const size_t rows = part.rows, rows_pad = align_up(rows, 256);
         ctx->seq_v.ensure(rows_pad * 256 * 2 * (rec_split(ctx) ? 2 : 1));
         ctx->seq_logits.ensure(rows_pad * 112 * 4);
-        ctx->arena.begin(true);
-        crnn_features(ctx, dev_crops, n, imgW, nullptr);
-        ctx->arena.buf.ensure(ctx->arena.off);
-        ctx->arena.begin(false);
-        crnn_features(ctx, dev_crops, n, imgW, (uint16_t*)ctx->seq_v.p);
-        std::vector<int> tiles;
-        const int ts = lstm_tile_seqs(rec_mode(ctx));
-        for (int s0 = 0; s0 < n; s0 += ts) {
-            tiles.push_back(s0 * T); tiles.push_back(std::min(ts, n - s0)); tiles.push_back(T); tiles.push_back(0);
-        }
-        ctx->seq_tables.ensure(tiles.size() * 4);
-        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        crnn_sequence(ctx, rows_pad, (const int*)ctx->seq_tables.p, (int)(tiles.size() / 4), (float*)ctx->seq_logits.p);
+        const CropDesc* dd = rec_upload_descs(ctx, part, ctx->crop_desc);
+        uint16_t* wide = rec_wide_image(ctx, part);
+        HIPCHK(hipMemsetAsync(wide, 0, 64 * part.cols * 2, ctx->stream));
+        for (int i = 0; i < n; ++i)
+            HIPCHK(hipMemcpy2DAsync(wide + part.descs[i].slot, part.cols * 2, dev_crops + (size_t)i * 64 * imgW, (size_t)imgW * 2, (size_t)imgW * 2, 64,
+                                    hipMemcpyDeviceToDevice, ctx->stream));
+        crnn_features_wide(ctx, part, dd, wide);
+        RecRun run;
+        rec_add_tables(run, part, lstm_tile_seqs(rec_mode(ctx)));
+        ctx->seq_tables.ensure(run.tiles.size() * 4);
+        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, run.tiles.data(), run.tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        crnn_sequence(ctx, rows_pad, (const int*)ctx->seq_tables.p, (int)(run.tiles.size() / 4), (float*)ctx->seq_logits.p);
         HIPCHK(hipMemcpyAsync(dev_logits, ctx->seq_logits.p, rows * 112 * 4, hipMemcpyDeviceToDevice, ctx->stream));
         slot_sync(ctx, ctx->stream);
     });
@@ -161,15 +165,11 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
         if (!dev_logits || !text_off || !text_idx || !conf || n <= 0 || T <= 0 || C <= 0 || C > cs) fail(BBOCR_ERR_ARG, "bad ctc arguments");
         const bool beam = beam_width > 0;
         const size_t rows = (size_t)n * T;
-        ctx->ctc_idx.ensure(rows * 4);
-        ctx->ctc_pmax.ensure(rows * 4);
-        ctx->ctc_out_idx.ensure(rows * 4);
-        ctx->ctc_out.ensure((size_t)n * sizeof(CtcOut));
+        ctc_size(ctx, rows, n, cs, beam);
         std::vector<int> seqs;
         for (int i = 0; i < n; ++i) { seqs.push_back(i * T); seqs.push_back(T); }
         ctx->seq_tables.ensure(seqs.size() * 4);
         HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (beam) ctx->ctc_probs.ensure(rows * cs * sizeof(float));
         HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, n, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
                           (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask, beam ? (float*)ctx->ctc_probs.p : nullptr));
         std::vector<int> oidx(rows);
@@ -181,12 +181,12 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
         if (beam) HIPCHK(hipMemcpyAsync(probs.data(), ctx->ctc_probs.p, probs.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         slot_sync(ctx, ctx->stream);
         if (beam) ctc_beam_search_batch(probs.data(), seqs.data(), n, C, cs, beam_width, beam_texts, &host_pool(ctx));
+        std::vector<int> text;
         int o = 0;
         for (int i = 0; i < n; ++i) {
             text_off[i] = o;
-            if (beam) for (int v : beam_texts[i]) text_idx[o++] = v;
-            else for (int k = 0; k < oo[i].len; ++k) text_idx[o++] = oidx[(size_t)i * T + k];
-            conf[i] = oo[i].cnt > 0 ? std::pow((double)oo[i].prod, 2.0 / std::sqrt((double)oo[i].cnt)) : 0.0;
+            conf[i] = ctc_decode(oo[i], oidx.data() + (size_t)i * T, beam ? &beam_texts[i] : nullptr, text);
+            for (int v : text) text_idx[o++] = v;
         }
         text_off[n] = o;
     });
@@ -249,8 +249,7 @@ int bbocr_op_crops(bbocr_ctx* ctx, const uint8_t* dev_gray, int H, int W, const 
             j.d.imgW = imgW;                       // batched branch (rotation_info): forced width, np.rot90(crop, mode - 1)
             j.d.rot = mode - 1;
             if (j.d.rot & 1) std::swap(j.d.rw, j.d.rh);
-            const int cw = (int)std::ceil(64 * ((double)j.d.rw / (double)j.d.rh));
-            j.d.fw = cw > imgW ? imgW : cw;
+            crop_refit_fw(j.d);
             jobs.push_back(j);
         };
         for (int i = 0; i < n_hori; ++i) {
@@ -268,21 +267,19 @@ int bbocr_op_crops(bbocr_ctx* ctx, const uint8_t* dev_gray, int H, int W, const 
         *n_out = (int)jobs.size();
         if (jobs.empty()) return;
         size_t a_total = 0, w_total = 0;
+        rec_layout_scratch(jobs, 0, a_total, w_total);
         bool any_warp = false, any_tall = false;
         std::vector<CropDesc> descs;
         for (size_t i = 0; i < jobs.size(); ++i) {
             CropDesc& d = jobs[i].d;
-            d.a_off = (int)a_total;
-            a_total += align_up((size_t)d.rw * d.rh, 16);
-            if (d.warp) { d.warp_off = (int)w_total; w_total += align_up((size_t)d.sw * d.sh, 16); }
-            d.slot = (int)i;
+            d.slot = (int)i;                       // row of the bucket tensor [n, 64, imgW]
             any_warp |= d.warp != 0;
             any_tall |= !(d.fw == d.rw && d.rh == 64);
+            descs.push_back(d);
         }
         ctx->crop_scratch.ensure(std::max<size_t>(a_total, 16));
         ctx->crop_hscratch.ensure(std::max<size_t>(a_total, 16));
         ctx->crop_wscratch.ensure(std::max<size_t>(w_total, 16));
-        for (auto& j : jobs) descs.push_back(j.d);
         ctx->crop_desc.ensure(descs.size() * sizeof(CropDesc));
         ctx->crop_luts.ensure(descs.size() * 256);
         HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
@@ -297,21 +294,8 @@ int bbocr_op_crops(bbocr_ctx* ctx, const uint8_t* dev_gray, int H, int W, const 
             HIPCHK(hipMemcpyAsync(hist.data(), ctx->crop_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
             slot_sync(ctx, ctx->stream);
             std::vector<uint8_t> luts(descs.size() * 256);
-            for (size_t k = 0; k < descs.size(); ++k) {
-                const size_t npx = (size_t)descs[k].rw * descs[k].rh;
-                const double high = percentile_u8(&hist[k * 256], npx, 90.0), lowp = percentile_u8(&hist[k * 256], npx, 10.0);
-                const double con = (high - lowp) / std::max(10.0, high + lowp);
-                for (int v = 0; v < 256; ++v) {
-                    if (con < (double)contrast) {
-                        double x = ((double)v - lowp + 25) * (200.0 / std::max(10.0, high - lowp));
-                        x = std::max(0.0, std::min(255.0, x));
-                        luts[k * 256 + v] = (uint8_t)x;
-                    } else {
-                        luts[k * 256 + v] = (uint8_t)v;
-                    }
-                }
-                descs[k].lut_off = (int)(k * 256);
-            }
+            for (size_t k = 0; k < descs.size(); ++k)       // a crop whose contrast is high enough stays as it is (lut_off -1), as in recognize_impl's retry
+                if (contrast_lut(&hist[k * 256], (size_t)descs[k].rw * descs[k].rh, (double)contrast, &luts[k * 256])) descs[k].lut_off = (int)(k * 256);
             HIPCHK(hipMemcpyAsync(ctx->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, ctx->stream));
             HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
         }

@@ -463,30 +463,6 @@ __device__ __forceinline__ void rowmean3_8(const uint16_t* p0, const uint16_t* p
     }
 }
 
-template <int MODE>
-__global__ void __launch_bounds__(256) rowmean3_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int n, int T, int C8) {
-    constexpr int M = MODE == REC_SPLIT ? 2 : 1;             // stored channels per logical channel
-    const size_t total = (size_t)n * T * C8;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t per = (size_t)T * C8;
-        const size_t img = i / per, rem = i - img * per;
-        const size_t t = rem / C8, c8 = rem - t * C8;
-        const size_t row = (size_t)T * C8 * 8 * M;           // elements of one feature row
-        const uint16_t* p = in + img * 3 * row + (t * C8 * M + c8) * 8;
-        rowmean3_8<MODE>(p, p + row, p + 2 * row, out + ((img * T + t) * C8 * M + c8) * 8, C8 * 8);
-    }
-}
-
-hipError_t launch_rowmean3(const uint16_t* in, uint16_t* out, int n, int T, int C, int mode, hipStream_t s) {
-    const size_t total = (size_t)n * T * (C / 8);
-    if (total == 0) return hipSuccess;
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (mode == REC_SPLIT) hipLaunchKernelGGL(rowmean3_kernel<REC_SPLIT>, dim3(grid), dim3(256), 0, s, in, out, n, T, C / 8);
-    else if (mode == REC_F16) hipLaunchKernelGGL(rowmean3_kernel<REC_F16>, dim3(grid), dim3(256), 0, s, in, out, n, T, C / 8);
-    else hipLaunchKernelGGL(rowmean3_kernel<REC_BF16>, dim3(grid), dim3(256), 0, s, in, out, n, T, C / 8);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------------ wide recogniser image helpers
 // All crops of a recognition pass sit side by side in ONE image (crop_final's wide layout), so every CRNN layer is one launch
 // over [H, Wt] instead of one per width bucket.  The columns between two crops are that layer's zero padding: a conv writes

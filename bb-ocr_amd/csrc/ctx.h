@@ -315,12 +315,17 @@ void weights_export(bbocr_ctx* c, void* dev_dst, size_t bytes);
 void weights_import(bbocr_ctx* c, const void* dev_src, size_t bytes);
 void load_craft(bbocr_ctx* c, const TensorMap& tm);
 void load_crnn(bbocr_ctx* c, const TensorMap& tm);
+ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1 = nullptr, const Act* addup = nullptr);
 hipError_t launch_conv_profiled(bbocr_ctx* c, const ConvPlan& p, ConvArgs a, bool may_decline = false);   // may_decline: hipErrorNotSupported is returned, not thrown
 void run_conv(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, void* out, int out_cs, int cout_store, bool out_f32, const Act* addup = nullptr);
 void prof_collect(bbocr_ctx* c);
 Act conv_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, int store);
 Act conv_pool_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, bool relu_out, int store, int mode, bool pool_relu, Act* full, const RgbSource* rgb = nullptr);
 Act pool_act(bbocr_ctx* c, const Act& a, int kh, int kw, int sh, int sw, int ph, int pw, bool relu_in);
+void craft_up_stage(bbocr_ctx* c, const ConvPlan& py, const ConvPlan& ps, const Act& y, const Act& skip, uint16_t* z, uint16_t* out);
+bool craft_up3b_post(bbocr_ctx* c, const Act& u3a, uint16_t* u3b, uint16_t* z);      // true: the one fused launch ran; false: the two launches
+bool craft_up4(bbocr_ctx* c, const Act& s1, const uint16_t* z, uint16_t* u4b);       // likewise
+void craft_cls_tail(bbocr_ctx* c, const Act& c2, float* heat);
 DetDims det_dims(int H, int W, int canvas, double mag);
 void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bbocr_params& p, float* heat, const std::function<void(int, int)>& after_sub = nullptr);
 void boxes_impl(bbocr_ctx* c, const float* heat, int B, int h, int w, double ratio, const bbocr_params& p, HostBoxes& hb, hipStream_t st);
@@ -329,9 +334,17 @@ void import_boxes(const bbocr_boxlist* bl, HostBoxes& hb);
 bool plan_horizontal(const std::array<int, 4>& box, int img, int H, int W, BoxJob& j);
 bool plan_free(const std::array<double, 8>& fq, int img, BoxJob& j);
 int rec_mode(const bbocr_ctx* c);
-void crnn_features(bbocr_ctx* c, const uint16_t* crops, int n, int imgW, uint16_t* v_out);
+void crop_refit_fw(CropDesc& d);
+void rec_layout_scratch(std::vector<BoxJob>& jobs, size_t first, size_t& a_total, size_t& w_total);
+bool contrast_lut(const unsigned int* hist, size_t npx, double target, uint8_t* lut);
+void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int>& sel, int res0, size_t row_base, RecPart& part);
+const CropDesc* rec_upload_descs(bbocr_ctx* c, const RecPart& part, DevBuf& desc_buf);
+uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part);
+void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide);
+void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
 void crnn_sequence(bbocr_ctx* c, size_t rows_pad, const int* tiles_dev, int ntiles, float* logits);
-double percentile_u8(const unsigned int* hist, size_t n, double q);
+void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, bool beam);
+double ctc_decode(const CtcOut& o, const int* idx, const std::vector<int>* beam_text, std::vector<int>& text);
 void rec_early_begin(bbocr_ctx* c, const uint8_t* gray, int pages, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p, RecEarly& e);
 void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p, std::vector<BoxJob>& jobs, std::vector<int>& box_off, RecEarly* early = nullptr);
 bbocr_result* export_result(int B, const std::vector<BoxJob>& jobs, const std::vector<int>& box_off);
@@ -370,8 +383,8 @@ struct EnqLock {       // see bbocr_ctx::enq_mu; never held across a host wait f
 constexpr int kMaxSlots = 2;       // calls in flight per context (the reference runs 2 ThreadPoolExecutor workers on one Reader)
 bbocr_ctx* slot_create(bbocr_ctx* root);                 // abi.cpp
 void slot_destroy(bbocr_ctx* s);                         // abi.cpp (everything but the shared compute stream and the weights)
-void publish_times(const bbocr_ctx* s);
-void dist_release(bbocr_ctx* root);                      // dist.cpp                  // abi.cpp: the finished call's stage times -> the calling thread's record
+void publish_times(const bbocr_ctx* s);                  // abi.cpp: the finished call's stage times -> the calling thread's record
+void dist_release(bbocr_ctx* root);                      // dist.cpp
 
 // wait for what THIS slot has queued on `st` so far (the compute stream is shared between slots: hipStreamSynchronize would also wait for
 // the other call's kernels queued behind ours -- and the card would then run dry while both hosts wait)
@@ -381,6 +394,8 @@ inline void slot_sync(bbocr_ctx* c, hipStream_t st) {
     HIPCHK(hipEventSynchronize(c->sync_ev));
 }
 
+inline void prof_release(bbocr_ctx* c, const bbocr_ctx::ProfRec& r) { c->prof_pool.push_back(r.e0); c->prof_pool.push_back(r.e1); }   // events back to the pool
+
 // bbocr.h promises that a call returns with its own work finished -- also when it fails half-way: kernels already queued may still
 // read caller-owned inputs / write caller-owned outputs, and host vectors that were async-copy targets die during unwinding
 inline void guarded_drain(bbocr_ctx* ctx) {
@@ -389,7 +404,7 @@ inline void guarded_drain(bbocr_ctx* ctx) {
     if (ctx->seq_stream) (void)hipStreamSynchronize(ctx->seq_stream);
     ctx->cur = ctx->stream;
     (void)hipGetLastError();
-    for (auto& r : ctx->prof_recs) { ctx->prof_pool.push_back(r.e0); ctx->prof_pool.push_back(r.e1); }
+    for (auto& r : ctx->prof_recs) prof_release(ctx, r);
     ctx->prof_recs.clear();
 }
 

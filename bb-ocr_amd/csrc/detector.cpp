@@ -2,83 +2,62 @@
 #include "ctx.h"
 
 // ------------------------------------------------------------------------------------------------ conv helper
+static hipEvent_t prof_event(bbocr_ctx* c) {
+    hipEvent_t e;
+    if (!c->prof_pool.empty()) { e = c->prof_pool.back(); c->prof_pool.pop_back(); }
+    else HIPCHK(hipEventCreate(&e));
+    return e;
+}
+
+// launch() between two pooled events on c->cur, `flops` booked under the current group; a launch that did not succeed (declined:
+// hipErrorNotSupported) books nothing and gives its events back.  Without profiling (or outside the profiled group): just launch().
+template <typename F> static hipError_t profiled(bbocr_ctx* c, double flops, F&& launch) {
+    if (c->profiling == 0 || (c->profiling == 1 && c->prof_group != 0)) return launch();
+    bbocr_ctx::ProfRec r{prof_event(c), prof_event(c), flops, c->prof_group};
+    HIPCHK(hipEventRecord(r.e0, c->cur));
+    const hipError_t e = launch();
+    HIPCHK(hipEventRecord(r.e1, c->cur));
+    if (e == hipSuccess) c->prof_recs.push_back(r);
+    else prof_release(c, r);
+    return e;
+}
+
 hipError_t launch_conv_profiled(bbocr_ctx* c, const ConvPlan& p, ConvArgs a, bool may_decline) {
     a.zero = c->zero_page;
-    if (c->profiling == 0 || (c->profiling == 1 && c->prof_group != 0)) {
-        const hipError_t e = launch_conv(p, a, c->cur);
-        if (may_decline && e == hipErrorNotSupported) return e;
-        HIPCHK(e);
-        return hipSuccess;
-    }
-    auto get_event = [&]() {
-        hipEvent_t e;
-        if (!c->prof_pool.empty()) { e = c->prof_pool.back(); c->prof_pool.pop_back(); }
-        else HIPCHK(hipEventCreate(&e));
-        return e;
-    };
-    bbocr_ctx::ProfRec r;
-    r.e0 = get_event();
-    r.e1 = get_event();
     const int OH = a.H + 2 * p.pad_h - (p.KH - 1) * p.dil, OW = a.W + 2 * p.pad_w - (p.KW - 1) * p.dil;
-    r.flops = 2.0 * a.N * OH * OW * (double)p.Cout * (p.split ? p.Cin / 3 : p.Cin) * p.KH * p.KW;   // algorithmic (unpadded) work; a split-fp16 plan
-                                                                                                     // executes three product terms per MAC: counted once
-    if (a.c11_w) r.flops += 2.0 * a.N * a.H * a.W * 64.0 * 27.0;            // conv1_1 produced inside this launch
-    if (a.tail) r.flops += 2.0 * a.N * OH * OW * (16.0 * 16.0 + 16.0 * 2.0);   // fused classifier tail
-    if (a.post_w) r.flops += 2.0 * a.N * OH * OW * 64.0 * 64.0;                 // 1x1 applied in the epilogue
-    r.group = c->prof_group;
-    HIPCHK(hipEventRecord(r.e0, c->cur));
-    const hipError_t e = launch_conv(p, a, c->cur);
-    HIPCHK(hipEventRecord(r.e1, c->cur));
-    if (may_decline && e == hipErrorNotSupported) {
-        c->prof_pool.push_back(r.e0);
-        c->prof_pool.push_back(r.e1);
-        return e;
-    }
+    double flops = 2.0 * a.N * OH * OW * (double)p.Cout * (p.split ? p.Cin / 3 : p.Cin) * p.KH * p.KW;   // algorithmic (unpadded) work; a split-fp16 plan
+                                                                                                          // executes three product terms per MAC: counted once
+    if (a.c11_w) flops += 2.0 * a.N * a.H * a.W * 64.0 * 27.0;            // conv1_1 produced inside this launch
+    if (a.tail) flops += 2.0 * a.N * OH * OW * (16.0 * 16.0 + 16.0 * 2.0);   // fused classifier tail
+    if (a.post_w) flops += 2.0 * a.N * OH * OW * 64.0 * 64.0;                 // 1x1 applied in the epilogue
+    const hipError_t e = profiled(c, flops, [&] { return launch_conv(p, a, c->cur); });
+    if (may_decline && e == hipErrorNotSupported) return e;
     HIPCHK(e);
-    c->prof_recs.push_back(r);
     return hipSuccess;
 }
 
-// the fused upconv4 launch, timed like two conv launches (algorithmic FLOPs of the 1x1 over s1 and of the 3x3)
-static hipError_t launch_up4_profiled(bbocr_ctx* c, const ConvArgs& a) {
-    if (c->profiling == 0 || (c->profiling == 1 && c->prof_group != 0)) return launch_up4_fused(c->up4s, c->up4b, a, c->cur);
-    hipEvent_t e0, e1;
-    auto get_event = [&](hipEvent_t& e) {
-        if (!c->prof_pool.empty()) { e = c->prof_pool.back(); c->prof_pool.pop_back(); }
-        else HIPCHK(hipEventCreate(&e));
-    };
-    get_event(e0);
-    get_event(e1);
-    HIPCHK(hipEventRecord(e0, c->cur));
-    const hipError_t r = launch_up4_fused(c->up4s, c->up4b, a, c->cur);
-    HIPCHK(hipEventRecord(e1, c->cur));
-    if (r != hipSuccess) { c->prof_pool.push_back(e0); c->prof_pool.push_back(e1); return r; }
-    bbocr_ctx::ProfRec rec;
-    rec.e0 = e0; rec.e1 = e1; rec.group = c->prof_group;
-    rec.flops = 2.0 * a.N * a.H * a.W * (128.0 * 64.0 + 64.0 * 32.0 * 9.0);
-    c->prof_recs.push_back(rec);
-    return hipSuccess;
-}
-
+// ConvArgs of a launch over a0 (a1: a second source behind it, virtual channel concat; addup: the half-resolution tensor whose 2x
+// up-sampling the epilogue adds): sources and image shape.  The caller adds the output and the epilogue switches.
 // Split-fp16 plans (ConvPlan::split, exact recogniser mode): the activation `a0` is a pair tensor [hi | lo] whose Act::C counts BOTH
 // halves; the launch reads [hi | lo | hi] (in1 = the hi half again) and, unless it writes fp32, stores its output as a pair too.
-static void conv_sources(const ConvPlan& p, ConvArgs& a, const Act& a0, const Act* a1) {
+ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1, const Act* addup) {
+    ConvArgs a{};
     a.in0 = a0.p; a.C0 = a0.C; a.in0_cs = a0.C;
+    a.N = a0.N; a.H = a0.H; a.W = a0.W;
     if (p.split) {
         if (a1 || (a0.C & 63)) fail(BBOCR_ERR_INTERNAL, "split-fp16 conv: one pair tensor with a multiple of 32 logical channels expected");
         a.in1 = a0.p; a.C1 = a0.C / 2; a.in1_cs = a0.C;
     } else if (a1) {
         a.in1 = a1->p; a.C1 = a1->C; a.in1_cs = a1->C;
     }
+    if (addup) { a.addup = addup->p; a.up_H = a0.H; a.up_W = a0.W; a.up_cs = addup->C; }
+    return a;
 }
 
 void run_conv(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, void* out,
                      int out_cs, int cout_store, bool out_f32, const Act* addup) {
     if (c->arena.dry) return;
-    ConvArgs a{};
-    if (addup) { a.addup = addup->p; a.up_H = a0.H; a.up_W = a0.W; a.up_cs = addup->C; }
-    conv_sources(p, a, a0, a1);
-    a.N = a0.N; a.H = a0.H; a.W = a0.W;
+    ConvArgs a = conv_args(p, a0, a1, addup);
     a.relu_in0 = relu0; a.relu_in1 = p.split ? relu0 : relu1; a.relu_out = relu_out; a.out_f32 = out_f32;
     a.out = out; a.out_cs = out_cs; a.cout_store = cout_store;
     if (p.split && !out_f32) a.split_off = cout_store;          // out_cs is 2 * cout_store then
@@ -96,17 +75,18 @@ void prof_collect(bbocr_ctx* c) {
             root->prof_flops[r.group] += r.flops;
             root->prof_launches[r.group] += 1;
         }
-        c->prof_pool.push_back(r.e0);
-        c->prof_pool.push_back(r.e1);
+        prof_release(c, r);
     }
     c->prof_recs.clear();
 }
+
+static Act arena_act(bbocr_ctx* c, int N, int H, int W, int C) { return Act{c->arena.alloc<uint16_t>((size_t)N * H * W * C), N, H, W, C}; }
 
 // conv producing a fresh bf16 activation with `store` channels (multiple of 16)
 Act conv_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, int store) {
     const int OH = a0.H + 2 * p.pad_h - (p.KH - 1) * p.dil, OW = a0.W + 2 * p.pad_w - (p.KW - 1) * p.dil;
     const int cs = p.split ? 2 * store : store;                  // pair tensors carry [hi | lo]
-    Act o{c->arena.alloc<uint16_t>((size_t)a0.N * OH * OW * cs), a0.N, OH, OW, cs};
+    Act o = arena_act(c, a0.N, OH, OW, cs);
     run_conv(c, p, a0, relu0, a1, relu1, relu_out, o.p, cs, store, false);
     return o;
 }
@@ -118,13 +98,10 @@ Act conv_pool_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, bo
     const int OH = a0.H + 2 * p.pad_h - (p.KH - 1) * p.dil, OW = a0.W + 2 * p.pad_w - (p.KW - 1) * p.dil;
     const int PH = OH / 2, PW = mode == 1 ? OW / 2 : OW;
     const int cs = p.split ? 2 * store : store;
-    if (full) *full = Act{c->arena.alloc<uint16_t>((size_t)a0.N * OH * OW * cs), a0.N, OH, OW, cs};
-    Act o{c->arena.alloc<uint16_t>((size_t)a0.N * PH * PW * cs), a0.N, PH, PW, cs};
+    if (full) *full = arena_act(c, a0.N, OH, OW, cs);
+    Act o = arena_act(c, a0.N, PH, PW, cs);
     if (c->arena.dry) return o;
-    ConvArgs a{};
-    if (!rgb) conv_sources(p, a, a0, nullptr);
-    else { a.C0 = a0.C; a.in0_cs = a0.C; }
-    a.N = a0.N; a.H = a0.H; a.W = a0.W;
+    ConvArgs a = conv_args(p, a0);
     a.relu_in0 = relu0; a.relu_in1 = relu0; a.relu_out = relu_out; a.out_f32 = 0;
     a.out = full ? (void*)full->p : nullptr; a.out_cs = cs; a.cout_store = store;
     if (p.split) a.split_off = store;
@@ -136,15 +113,68 @@ Act conv_pool_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, bo
 
 Act pool_act(bbocr_ctx* c, const Act& a, int kh, int kw, int sh, int sw, int ph, int pw, bool relu_in) {
     const int OH = (a.H + 2 * ph - kh) / sh + 1, OW = (a.W + 2 * pw - kw) / sw + 1;
-    Act o{c->arena.alloc<uint16_t>((size_t)a.N * OH * OW * a.C), a.N, OH, OW, a.C};
+    Act o = arena_act(c, a.N, OH, OW, a.C);
     if (!c->arena.dry) HIPCHK(launch_maxpool(a.p, o.p, a.N, a.H, a.W, a.C, kh, kw, sh, sw, ph, pw, relu_in, c->cur));
     return o;
 }
 
 // ------------------------------------------------------------------------------------------------ detector
+// The fused stages of the fast-mode detector.  Each takes its input activations and the caller's output pointers and holds its own fallback;
+// the ones that can fall back return whether the fused launch ran.  craft_forward and the per-stage tests (tools/micro/stage_shim.hip) call these.
+
+// cat([up(y), skip]) -> 1x1 + BN + ReLU, with the up-sampling commuted behind the (linear) 1x1: z = W_y y at y's
+// resolution, then out = ReLU(up(z) + W_s skip + b) in the epilogue of the skip half -- up(y) is never written
+void craft_up_stage(bbocr_ctx* c, const ConvPlan& py, const ConvPlan& ps, const Act& y, const Act& skip, uint16_t* z, uint16_t* out) {
+    const int cout = ps.Cout;
+    const Act zz{z, y.N, y.H, y.W, cout};
+    run_conv(c, py, y, false, nullptr, false, false, z, cout, cout, false);
+    run_conv(c, ps, skip, false, nullptr, false, true, out, cout, cout, false, &zz);
+}
+
+// upconv3's 3x3 with z = W_y u3b (the y half of upconv4's 1x1, linear) applied in its epilogue: u3b itself has no other reader and is
+// not stored, one launch and 2 x 9.8 MB per page less; shapes the kernel declines take the two launches through `u3b`
+bool craft_up3b_post(bbocr_ctx* c, const Act& u3a, uint16_t* u3b, uint16_t* z) {
+    if (c->arena.dry) return false;
+    if (c->up4y_post && !c->up3b.split) {
+        ConvArgs a = conv_args(c->up3b, u3a);
+        a.relu_out = 1; a.out = z; a.out_cs = 64; a.cout_store = 64; a.post_w = c->up4y_post;
+        if (launch_conv_profiled(c, c->up3b, a, true) == hipSuccess) return true;
+    }
+    const Act b{u3b, u3a.N, u3a.H, u3a.W, 64};
+    run_conv(c, c->up3b, u3a, false, nullptr, false, true, u3b, 64, 64, false);
+    run_conv(c, c->up4y, b, false, nullptr, false, false, z, 64, 64, false);
+    return false;
+}
+
+// upconv4 as ONE launch behind z = W_y u3b (half resolution): the 3x3 produces its own input patch (1x1 over s1 + up(z) + ReLU) in LDS, so the
+// 64-channel u4a never reaches HBM (conv_mfma.hip::conv3x3_up4_kernel); any other shape takes the two launches, with u4a in the arena
+bool craft_up4(bbocr_ctx* c, const Act& s1, const uint16_t* z, uint16_t* u4b) {
+    const Act zz{(uint16_t*)z, s1.N, s1.H / 2, s1.W / 2, 64};
+    if (!c->arena.dry) {
+        ConvArgs a = conv_args(c->up4s, s1, nullptr, &zz);
+        a.relu_out = 1; a.out = u4b; a.out_cs = 32; a.cout_store = 32;
+        a.zero = c->zero_page;
+        // timed like two conv launches: algorithmic FLOPs of the 1x1 over s1 and of the 3x3
+        const hipError_t e = profiled(c, 2.0 * a.N * a.H * a.W * (128.0 * 64.0 + 64.0 * 32.0 * 9.0), [&] { return launch_up4_fused(c->up4s, c->up4b, a, c->cur); });
+        if (e == hipSuccess) return true;
+        if (e != hipErrorNotSupported) HIPCHK(e);
+    }
+    Act u4a = arena_act(c, s1.N, s1.H, s1.W, 64);        // carved by the sizing pass and by the fallback only
+    run_conv(c, c->up4s, s1, false, nullptr, false, true, u4a.p, 64, 64, false, &zz);
+    run_conv(c, c->up4b, u4a, false, nullptr, false, true, u4b, 32, 32, false);
+    return false;
+}
+
+// conv_cls.4 (3x3 32->16 + ReLU) with conv_cls.6/.8 fused into its epilogue: writes the fp32 heat-map directly
+void craft_cls_tail(bbocr_ctx* c, const Act& c2, float* heat) {
+    if (c->arena.dry) return;
+    ConvArgs a = conv_args(c->cls4, c2);
+    a.relu_out = 1; a.out = heat; a.out_cs = 16; a.cout_store = 16; a.tail = c->cls_tail; a.tail_frag = c->cls_tail_frag;
+    (void)launch_conv_profiled(c, c->cls4, a);
+}
+
 // rgb: [nb, Himg, Wimg, 3] on a zero canvas H32 x W32 -> heat fp32 [nb, H32/2, W32/2, 2]
 static void craft_forward(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, int Wimg, int H32, int W32, float* heat) {
-    Arena& ar = c->arena;
     c->prof_group = 0;
     // normalise + conv1_1 + ReLU are produced inside conv1_2's prologue (its 64-channel input never reaches HBM)
     const Act canvas{nullptr, nb, H32, W32, 64};
@@ -166,68 +196,18 @@ static void craft_forward(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, in
     Act f7 = conv_act(c, c->fc7, f6, false, nullptr, false, false, 1024);
     Act u1a = conv_act(c, c->up1a, f7, false, &s4, false, true, 512);              // cat([fc7, relu5_3]) -> 1x1
     Act u1b = conv_act(c, c->up1b, u1a, false, nullptr, false, true, 256);
-    // cat([up(y), skip]) -> 1x1 + BN + ReLU, with the up-sampling commuted behind the (linear) 1x1: z = W_y y at y's
-    // resolution, then ReLU(up(z) + W_s skip + b) in the epilogue of the skip half -- up(y) is never written
-    auto up_stage = [&](const ConvPlan& py, const ConvPlan& ps, const Act& y, const Act& skip, bool relu_skip, int cout) {
-        Act z = conv_act(c, py, y, false, nullptr, false, false, cout);
-        Act o{c->arena.alloc<uint16_t>((size_t)skip.N * skip.H * skip.W * cout), skip.N, skip.H, skip.W, cout};
-        run_conv(c, ps, skip, relu_skip, nullptr, false, true, o.p, cout, cout, false, &z);
-        return o;
-    };
-    Act u2a = up_stage(c->up2y, c->up2s, u1b, s3, false, 256);
+    Act z2 = arena_act(c, u1b.N, u1b.H, u1b.W, 256), u2a = arena_act(c, s3.N, s3.H, s3.W, 256);
+    craft_up_stage(c, c->up2y, c->up2s, u1b, s3, z2.p, u2a.p);
     Act u2b = conv_act(c, c->up2b, u2a, false, nullptr, false, true, 128);
-    Act u3a = up_stage(c->up3y, c->up3s, u2b, s2, false, 128);
-    // upconv3's 3x3 with z = W_y u3b (the y half of upconv4's 1x1, linear) applied in its epilogue: u3b itself has no other reader and is
-    // not stored, one launch and 2 x 9.8 MB per page less; shapes the kernel declines take the two launches
-    Act u3b{c->arena.alloc<uint16_t>((size_t)u3a.N * u3a.H * u3a.W * 64), u3a.N, u3a.H, u3a.W, 64};
-    Act z{c->arena.alloc<uint16_t>((size_t)u3a.N * u3a.H * u3a.W * 64), u3a.N, u3a.H, u3a.W, 64};
-    if (!ar.dry) {
-        hipError_t e = hipErrorNotSupported;
-        if (c->up4y_post && !c->up3b.split) {
-            ConvArgs a{};
-            a.in0 = u3a.p; a.C0 = u3a.C; a.in0_cs = u3a.C;
-            a.N = u3a.N; a.H = u3a.H; a.W = u3a.W;
-            a.relu_out = 1; a.out = z.p; a.out_cs = 64; a.cout_store = 64; a.post_w = c->up4y_post;
-            e = launch_conv_profiled(c, c->up3b, a, true);
-        }
-        if (e != hipSuccess) {
-            run_conv(c, c->up3b, u3a, false, nullptr, false, true, u3b.p, 64, 64, false);
-            run_conv(c, c->up4y, u3b, false, nullptr, false, false, z.p, 64, 64, false);
-        }
-    }
-    // upconv4 as ONE launch behind z = W_y u3b: the 3x3 produces its own input patch (1x1 over s1 + up(z) + ReLU) in LDS, so the
-    // 64-channel u4a never reaches HBM (conv_mfma.hip::conv3x3_up4_kernel); any other shape takes the two launches
-    Act u4b{nullptr, s1.N, s1.H, s1.W, 32};
-    {
-        u4b.p = c->arena.alloc<uint16_t>((size_t)s1.N * s1.H * s1.W * 32);
-        bool fused = false;
-        if (!ar.dry) {
-            ConvArgs a{};
-            a.in0 = s1.p; a.C0 = s1.C; a.in0_cs = s1.C;
-            a.N = s1.N; a.H = s1.H; a.W = s1.W;
-            a.addup = z.p; a.up_H = s1.H; a.up_W = s1.W; a.up_cs = z.C;
-            a.relu_out = 1; a.out = u4b.p; a.out_cs = 32; a.cout_store = 32;
-            a.zero = c->zero_page;
-            const hipError_t e = launch_up4_profiled(c, a);
-            if (e == hipSuccess) fused = true;
-            else if (e != hipErrorNotSupported) HIPCHK(e);
-        }
-        if (!fused) {
-            Act u4a{c->arena.alloc<uint16_t>((size_t)s1.N * s1.H * s1.W * 64), s1.N, s1.H, s1.W, 64};
-            run_conv(c, c->up4s, s1, false, nullptr, false, true, u4a.p, 64, 64, false, &z);
-            run_conv(c, c->up4b, u4a, false, nullptr, false, true, u4b.p, 32, 32, false);
-        }
-    }
+    Act z3 = arena_act(c, u2b.N, u2b.H, u2b.W, 128), u3a = arena_act(c, s2.N, s2.H, s2.W, 128);
+    craft_up_stage(c, c->up3y, c->up3s, u2b, s2, z3.p, u3a.p);
+    Act u3b = arena_act(c, u3a.N, u3a.H, u3a.W, 64), z4 = arena_act(c, u3a.N, u3a.H, u3a.W, 64);     // u3b: written by the two-launch path only
+    (void)craft_up3b_post(c, u3a, u3b.p, z4.p);
+    Act u4b = arena_act(c, s1.N, s1.H, s1.W, 32);
+    (void)craft_up4(c, s1, z4.p, u4b.p);
     Act c1 = conv_act(c, c->cls0, u4b, false, nullptr, false, true, 32);
     Act c2 = conv_act(c, c->cls2, c1, false, nullptr, false, true, 32);
-    // conv_cls.4 (3x3 32->16 + ReLU) with conv_cls.6/.8 fused into its epilogue: writes the fp32 heat-map directly
-    if (!ar.dry) {
-        ConvArgs a{};
-        a.in0 = c2.p; a.C0 = c2.C; a.in0_cs = c2.C;
-        a.N = c2.N; a.H = c2.H; a.W = c2.W;
-        a.relu_out = 1; a.out = heat; a.out_cs = 16; a.cout_store = 16; a.tail = c->cls_tail; a.tail_frag = c->cls_tail_frag;
-        (void)launch_conv_profiled(c, c->cls4, a);
-    }
+    craft_cls_tail(c, c2, heat);
 }
 
 // EXACT mode: the same network on pair tensors [hi | lo] (22 significand bits) with split-fp16 plans in every layer, in the reference's own

@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (api.cpp) and the HIP kernels.  Not public.
+// Internal launch interface between the host side of libbbocr (ctx.h and the .cpp translation units) and the HIP kernels.  Not public.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -146,12 +146,11 @@ hipError_t launch_crop_hist(const uint8_t* scratch, const CropDesc* descs_dev, i
 hipError_t launch_crnn_conv0(const uint16_t* in, const float* w /*[9][32] tap-major*/, const float* b, uint16_t* out, int n, int W, int mode, hipStream_t s,
                              const uint16_t* afrag = nullptr /*pack_crnn_conv0_mfma: the MFMA form (bf16 / fp16 modes, W % 4 == 0)*/);
 void pack_crnn_conv0_mfma(const float* w_tap_major /*[9][32]*/, uint16_t* out /*[2][64][8]*/, int el);
-hipError_t launch_rowmean3(const uint16_t* in, uint16_t* out, int n, int T, int C, int mode, hipStream_t s);   // C: logical channels
 // wide recogniser image (all crops side by side, CropDesc::slot = first column, ::pad_ = first pooled row): clear the separator
 // columns of a layer output [H][Wl][C] (shift = log2 horizontal down-scale), and the 3-row mean gathered into the pooled rows
 hipError_t launch_crnn_zero_gaps(uint16_t* t, const CropDesc* descs_dev, int first, int count, int H, int Wl, int C, int shift, hipStream_t s);
 hipError_t launch_rowmean3_gather(const uint16_t* in, int Wc, int C, const CropDesc* descs_dev, int first, int count, uint16_t* out, int mode,
-                                  hipStream_t s);
+                                  hipStream_t s);   // C: logical channels
 // BiLSTM recurrence: xproj bf16 [n,T,2048] (permuted channels, see lstm8_xproj_channel), out bf16 [n,T,512] (fwd | bwd)
 // tiles_dev: int4 per workgroup {first row, sequences (<=16), T, 0}; tensors are pooled over all buckets: [rows, C]
 // mode REC_SPLIT: xproj is FP32 [rows, 2048], out is the pair [rows, 512 hi | 512 lo] with the lo half UNSCALED (fp16(h - hi): the linear

@@ -1,6 +1,27 @@
 // Recogniser orchestration: crops (utils.py::get_image_list), AlignCollate, CRNN forward, CTC, contrast retry, rotation variants (easyocr recognition.py::get_text).
 #include "ctx.h"
 
+// AlignCollate's content width of the stage-A image rw x rh (after a rotation, if any) inside the padded width imgW
+void crop_refit_fw(CropDesc& d) {
+    const int cw = (int)std::ceil(64 * ((double)d.rw / (double)d.rh));
+    d.fw = cw > d.imgW ? d.imgW : cw;
+}
+
+// get_image_list's resize target and own padded width of a width x height crop; false = degenerate
+static bool plan_sizes(CropDesc& d, int width, int height) {
+    double ratio = (double)width / (double)height;
+    if (ratio < 1.0) {
+        ratio = 1.0 / ratio;
+        d.rw = 64; d.rh = (int)(64 * ratio);
+    } else {
+        d.rw = (int)(64 * ratio); d.rh = 64;
+    }
+    if ((int)(64 * ratio) == 0) return false;
+    d.imgW = (int)std::ceil(std::max(ratio, 1.0)) * 64;
+    crop_refit_fw(d);
+    return d.rw > 0 && d.rh > 0 && d.fw > 0;
+}
+
 // AlignCollate / get_image_list geometry of one horizontal box; false = skipped (degenerate)
 bool plan_horizontal(const std::array<int, 4>& box, int img, int H, int W, BoxJob& j) {
     const int x_min = std::max(0, box[0]), x_max = std::min(box[1], W), y_min = std::max(0, box[2]), y_max = std::min(box[3], H);
@@ -13,19 +34,7 @@ bool plan_horizontal(const std::array<int, 4>& box, int img, int H, int W, BoxJo
     CropDesc& d = j.d;
     memset(&d, 0, sizeof(d));
     d.img = img; d.sx0 = x_min; d.sy0 = y_min; d.sw = width; d.sh = height; d.warp = 0; d.lut_off = -1;
-    double ratio = (double)width / (double)height;
-    if (ratio < 1.0) {
-        ratio = 1.0 / ratio;
-        d.rw = 64; d.rh = (int)(64 * ratio);
-    } else {
-        d.rw = (int)(64 * ratio); d.rh = 64;
-    }
-    if ((int)(64 * ratio) == 0) return false;
-    d.imgW = (int)std::ceil(std::max(ratio, 1.0)) * 64;
-    const double r2 = (double)d.rw / (double)d.rh;
-    const int cw = (int)std::ceil(64 * r2);
-    d.fw = cw > d.imgW ? d.imgW : cw;
-    return d.rw > 0 && d.rh > 0 && d.fw > 0;
+    return plan_sizes(d, width, height);
 }
 
 bool plan_free(const std::array<double, 8>& fq, int img, BoxJob& j) {
@@ -46,54 +55,26 @@ bool plan_free(const std::array<double, 8>& fq, int img, BoxJob& j) {
     memset(&d, 0, sizeof(d));
     d.img = img; d.sx0 = 0; d.sy0 = 0; d.sw = maxW; d.sh = maxH; d.warp = 1; d.lut_off = -1;
     bbocr::perspective_inverse(rect, maxW, maxH, d.Minv);
-    double ratio = (double)maxW / (double)maxH;
-    if (ratio < 1.0) {
-        ratio = 1.0 / ratio;
-        d.rw = 64; d.rh = (int)(64 * ratio);
-    } else {
-        d.rw = (int)(64 * ratio); d.rh = 64;
-    }
-    if ((int)(64 * ratio) == 0) return false;
-    d.imgW = (int)std::ceil(std::max(ratio, 1.0)) * 64;
-    const double r2 = (double)d.rw / (double)d.rh;
-    const int cw = (int)std::ceil(64 * r2);
-    d.fw = cw > d.imgW ? d.imgW : cw;
-    return d.rw > 0 && d.rh > 0 && d.fw > 0;
+    return plan_sizes(d, maxW, maxH);
 }
 
 // tensor mode of the recogniser (kernels.h REC_*) and stored 16-bit elements per logical channel
 int rec_mode(const bbocr_ctx* c) { return rec_split(c) ? REC_SPLIT : (rec_el(c) ? REC_F16 : REC_BF16); }
 static inline int rec_mul(const bbocr_ctx* c) { return rec_split(c) ? 2 : 1; }
 
-// conv stack of the recogniser for n normalised crops of one padded width: 16-bit [n,64,imgW] -> v [n*T, 256] (x rec_mul)
-void crnn_features(bbocr_ctx* c, const uint16_t* crops, int n, int imgW, uint16_t* v_out) {
+// The conv stack of the recogniser over the WIDE image [64][part.cols] of a part (16-bit; exact mode: codes): every crop side by side with
+// 4 zero columns between neighbours (CropDesc::slot = first column), so each layer is ONE launch over [H, Wt] whatever the mix of width
+// buckets.  The separator columns are each layer's zero padding; convolutions write into them, so they are cleared on every layer output
+// (4 >> shift columns per crop).  The 3-row mean is gathered straight into every crop's pooled rows of c->seq_v (CropDesc::pad_).
+// descs: the part's descriptors on the device.  In a dry arena pass nothing is launched.
+void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide) {
     Arena& ar = c->arena;
     c->prof_group = 1;
-    const int T = imgW / 4 - 1;
-    const int m = rec_mul(c);
-    Act c0{ar.alloc<uint16_t>((size_t)n * 32 * (imgW / 2) * 32 * m), n, 32, imgW / 2, 32 * m};
-    if (!ar.dry) HIPCHK(launch_crnn_conv0(crops, c->r0_wb, c->r0_wb + 288, c0.p, n, imgW, rec_mode(c), c->cur, c->r0_afrag));
-    Act q1 = conv_pool_act(c, c->r1, c0, false, true, 64, 1, false, nullptr);
-    Act c2 = conv_act(c, c->r2, q1, false, nullptr, false, true, 128);
-    Act q2 = conv_pool_act(c, c->r3, c2, false, true, 128, 2, false, nullptr);
-    Act c4 = conv_act(c, c->r4, q2, false, nullptr, false, true, 256);
-    Act q3 = conv_pool_act(c, c->r5, c4, false, true, 256, 2, false, nullptr);
-    Act c6 = conv_act(c, c->r6, q3, false, nullptr, false, true, 256);   // [n,3,T,256]
-    if (!ar.dry) HIPCHK(launch_rowmean3(c6.p, v_out, n, T, 256, rec_mode(c), c->cur));
-}
-
-// The same conv stack over the WIDE image of a recognition pass: every crop side by side with 4 zero columns between
-// neighbours (CropDesc::slot = first column), so each layer is ONE launch over [H, Wt] whatever the mix of width buckets.  The
-// separator columns are each layer's zero padding; convolutions write into them, so they are cleared on every layer output
-// (4 >> shift columns per crop).  The 3-row mean is gathered straight into every crop's pooled rows (CropDesc::pad_).
-static void crnn_features_wide(bbocr_ctx* c, const uint16_t* wide, int Wt, const CropDesc* descs, int first, int count, uint16_t* seq_v) {
-    Arena& ar = c->arena;
-    c->prof_group = 1;
-    const int m = rec_mul(c);
+    const int m = rec_mul(c), Wt = (int)part.cols, count = (int)part.descs.size();
     Act c0{ar.alloc<uint16_t>((size_t)32 * (Wt / 2) * 32 * m), 1, 32, Wt / 2, 32 * m};
     if (!ar.dry) HIPCHK(launch_crnn_conv0(wide, c->r0_wb, c->r0_wb + 288, c0.p, 1, Wt, rec_mode(c), c->cur, c->r0_afrag));
     auto gaps = [&](const Act& a, int shift) {
-        if (!ar.dry) HIPCHK(launch_crnn_zero_gaps(a.p, descs, first, count, a.H, a.W, a.C, shift, c->cur));
+        if (!ar.dry) HIPCHK(launch_crnn_zero_gaps(a.p, descs, 0, count, a.H, a.W, a.C, shift, c->cur));
     };
     gaps(c0, 1);
     Act q1 = conv_pool_act(c, c->r1, c0, false, true, 64, 1, false, nullptr);
@@ -107,7 +88,7 @@ static void crnn_features_wide(bbocr_ctx* c, const uint16_t* wide, int Wt, const
     Act q3 = conv_pool_act(c, c->r5, c4, false, true, 256, 2, false, nullptr);
     gaps(q3, 2);
     Act c6 = conv_act(c, c->r6, q3, false, nullptr, false, true, 256);   // [1, 3, Wt/4 - 1, 256]
-    if (!ar.dry) HIPCHK(launch_rowmean3_gather(c6.p, c6.W, 256, descs, first, count, seq_v, rec_mode(c), c->cur));
+    if (!ar.dry) HIPCHK(launch_rowmean3_gather(c6.p, c6.W, 256, descs, 0, count, (uint16_t*)c->seq_v.p, rec_mode(c), c->cur));
 }
 
 // Sequence half of the recogniser over the POOLED time steps of every bucket (rows = sum n_i*T_i, padded to x256):
@@ -144,7 +125,7 @@ void crnn_sequence(bbocr_ctx* c, size_t rows_pad, const int* tiles_dev, int ntil
 static size_t rec_max_rows(const bbocr_ctx* c) { return c->cfg.rec_max_cols > 0 ? (size_t)std::max(64, c->cfg.rec_max_cols / 4) : (size_t)1500000; }
 
 // lay the crops `sel` (indices into jobs; result position = res0 + position in sel) out as one part whose rows start at row_base
-static void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int>& sel, int res0, size_t row_base, RecPart& part) {
+void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int>& sel, int res0, size_t row_base, RecPart& part) {
     std::map<int, std::vector<int>> buckets;          // by padded width, box order kept inside a bucket
     for (size_t k = 0; k < sel.size(); ++k) buckets[jobs[sel[k]].d.imgW].push_back((int)k);
     size_t rows = row_base, cols = 0;
@@ -170,36 +151,50 @@ static void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int
     part.cols = cols;
 }
 
-// enqueue a part: descriptor upload, crops (stage A = gather / warp + cv2 resize when asked, stage B = AlignCollate into the wide image),
-// conv stack, pooled rows into seq_v.  Nothing here waits for the device (the buffers it needs are sized by the caller).
-static void rec_launch_part(bbocr_ctx* c, const uint8_t* gray, int H, int W, const RecPart& part, DevBuf& desc_buf, bool stage_a) {
-    if (part.descs.empty()) return;
-    EnqLock enq(c);                           // one feature part = one contiguous block on the compute stream
+// The three steps of enqueueing a part; nothing here waits for the device (the buffers it needs are sized by the caller).
+// 1. the part's descriptors -> desc_buf, through the pinned staging buffer that goes with it
+const CropDesc* rec_upload_descs(bbocr_ctx* c, const RecPart& part, DevBuf& desc_buf) {
     const size_t bytes = part.descs.size() * sizeof(CropDesc);
     desc_buf.ensure(bytes);
     PinBuf& pin = (&desc_buf == &c->crop_desc2) ? c->desc_pin2 : c->desc_pin;
     pin.ensure(bytes);
     memcpy(pin.p, part.descs.data(), bytes);
-    const CropDesc* dd = (const CropDesc*)desc_buf.p;
-    const int n = (int)part.descs.size(), Wt = (int)part.cols;
     HIPCHK(hipMemcpyAsync(desc_buf.p, pin.p, bytes, hipMemcpyHostToDevice, c->stream));
-    if (stage_a)
+    return (const CropDesc*)desc_buf.p;
+}
+
+// 2. the arena sized for the part's conv stack (dry pass) and begun again; returns the part's wide image [64][part.cols], carved first.
+// The caller fills it, then 3. crnn_features_wide.
+uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part) {
+    c->arena.begin(true);
+    (void)c->arena.alloc<uint16_t>((size_t)64 * part.cols);
+    crnn_features_wide(c, part, nullptr, nullptr);
+    c->arena.buf.ensure(c->arena.off);
+    c->arena.begin(false);
+    return c->arena.alloc<uint16_t>((size_t)64 * part.cols);
+}
+
+// enqueue a part: descriptor upload, crops (stage A = gather / warp + cv2 resize when asked, stage B = AlignCollate into the wide image),
+// conv stack, pooled rows into seq_v
+static void rec_launch_part(bbocr_ctx* c, const uint8_t* gray, int H, int W, const RecPart& part, DevBuf& desc_buf, bool stage_a) {
+    if (part.descs.empty()) return;
+    EnqLock enq(c);                           // one feature part = one contiguous block on the compute stream
+    const CropDesc* dd = rec_upload_descs(c, part, desc_buf);
+    const int n = (int)part.descs.size(), Wt = (int)part.cols;
+    auto crops = [&](uint16_t* wide, int stage) {
         HIPCHK(launch_crops(gray, H, W, dd, 0, n, 0, part.any_warp, part.any_tall, (uint8_t*)c->crop_wscratch.p, (uint8_t*)c->crop_scratch.p,
-                            (uint8_t*)c->crop_hscratch.p, (const uint8_t*)c->crop_luts.p, nullptr, 1, c->stream));
-    for (int pass = 0; pass < 2; ++pass) {
-        c->arena.begin(pass == 0);
-        uint16_t* wide = c->arena.alloc<uint16_t>((size_t)64 * Wt);
-        if (pass == 1)
-            HIPCHK(launch_crops(gray, H, W, dd, 0, n, 0, part.any_warp, part.any_tall, (uint8_t*)c->crop_wscratch.p, (uint8_t*)c->crop_scratch.p,
-                                (uint8_t*)c->crop_hscratch.p, (const uint8_t*)c->crop_luts.p, wide, 2, c->stream, Wt, REC_GAP, rec_mode(c)));
-        crnn_features_wide(c, wide, Wt, dd, 0, n, (uint16_t*)c->seq_v.p);
-        if (pass == 0) c->arena.buf.ensure(c->arena.off);
-    }
+                            (uint8_t*)c->crop_hscratch.p, (const uint8_t*)c->crop_luts.p, wide, stage, c->stream, wide ? Wt : 0, wide ? REC_GAP : 0,
+                            wide ? rec_mode(c) : 0));
+    };
+    if (stage_a) crops(nullptr, 1);
+    uint16_t* wide = rec_wide_image(c, part);
+    crops(wide, 2);
+    crnn_features_wide(c, part, dd, wide);
     if (!c->feat_ev) HIPCHK(hipEventCreateWithFlags(&c->feat_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->feat_ev, c->stream));      // what the sequence stage (on seq_stream) waits for
 }
 
-static void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs) {
+void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs) {
     for (const RecChunk& ch : part.chunks) {
         for (int s0 = 0; s0 < ch.n; s0 += tile_seqs) {
             run.tiles.push_back((int)(ch.row0 + (size_t)s0 * ch.T));
@@ -214,6 +209,24 @@ static void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs) {
         }
     }
     run.rows += part.rows;
+}
+
+// device buffers of one launch_ctc over `rows` time steps of `nseq` sequences (cs: row stride of the logits; beam: the probabilities are kept)
+void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, bool beam) {
+    c->ctc_idx.ensure(rows * 4);
+    c->ctc_pmax.ensure(rows * 4);
+    c->ctc_out_idx.ensure(rows * 4);
+    c->ctc_out.ensure((size_t)nseq * sizeof(CtcOut));
+    if (beam) c->ctc_probs.ensure(rows * cs * sizeof(float));
+}
+
+// CtcOut -> (text, confidence) of one sequence: the greedy path's classes (idx: the sequence's rows of launch_ctc's out_idx) unless the beam
+// search's text is given; the confidence is the greedy path's either way
+double ctc_decode(const CtcOut& o, const int* idx, const std::vector<int>* beam_text, std::vector<int>& text) {
+    if (beam_text) text = *beam_text;
+    else text.assign(idx, idx + o.len);
+    // custom_mean: prod ** (2 / sqrt(len)); an all-blank sequence scores np.array([0])
+    return o.cnt > 0 ? std::pow((double)o.prod, 2.0 / std::sqrt((double)o.cnt)) : 0.0;
 }
 
 // sequence stage + CTC over every row the parts of `run` produced; texts / confs are indexed by result position
@@ -238,12 +251,8 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     c->seq_tables.ensure((tiles.size() + seqs.size()) * 4);
     int* tiles_dev = (int*)c->seq_tables.p;
     int* seqs_dev = tiles_dev + tiles.size();
-    c->ctc_idx.ensure(rows * 4);
-    c->ctc_pmax.ensure(rows * 4);
-    c->ctc_out_idx.ensure(rows * 4);
-    c->ctc_out.ensure((size_t)nseq * sizeof(CtcOut));
     const bool beam = c->beam_width > 0;
-    if (beam) c->ctc_probs.ensure(rows * 112 * sizeof(float));
+    ctc_size(c, rows, nseq, 112, beam);
     const size_t oo_off = align_up(rows * 4, 16);
     c->ctc_pin.ensure(oo_off + (size_t)nseq * sizeof(CtcOut));
     const int* oidx = (const int*)c->ctc_pin.p;
@@ -282,11 +291,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     if (beam) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, 97, 112, c->beam_width, beam_texts, &host_pool(c));   // the confidence stays the greedy path's
     for (int i = 0; i < nseq; ++i) {
         const int k = run.seq_k[i];
-        const size_t r0 = (size_t)seqs[2 * i];
-        if (beam) texts[k] = beam_texts[i];
-        else texts[k].assign(oidx + r0, oidx + r0 + oo[i].len);
-        // custom_mean: prod ** (2 / sqrt(len)); an all-blank sequence scores np.array([0])
-        confs[k] = oo[i].cnt > 0 ? std::pow((double)oo[i].prod, 2.0 / std::sqrt((double)oo[i].cnt)) : 0.0;
+        confs[k] = ctc_decode(oo[i], oidx + seqs[2 * i], beam ? &beam_texts[i] : nullptr, texts[k]);
     }
     c->times[5] += (float)ms_since(t0);
 }
@@ -331,7 +336,7 @@ static void recognise_pass(bbocr_ctx* c, const uint8_t* gray, int H, int W, std:
 }
 
 // np.percentile(img, q) (method 'linear') from a 256-bin histogram of n uint8 samples
-double percentile_u8(const unsigned int* hist, size_t n, double q) {
+static double percentile_u8(const unsigned int* hist, size_t n, double q) {
     const double virt = (double)(n - 1) * (q / 100.0);
     const double prev = std::floor(virt);
     const double gamma = virt - prev;
@@ -351,8 +356,20 @@ double percentile_u8(const unsigned int* hist, size_t n, double q) {
     return r;
 }
 
-// State of a recognition whose FIRST feature part (the crops of pages [0, pages)) was enqueued before the boxes of the remaining pages
-// existed (readtext_batch: while the last detector pass's CCL + host geometry run).  recognize_impl picks it up and adds the rest.
+// adjust_contrast_grey of one crop of npx pixels from its histogram: false = its contrast is already >= target and the crop stays as it is,
+// true = lut[256] maps it
+bool contrast_lut(const unsigned int* hist, size_t npx, double target, uint8_t* lut) {
+    const double high = percentile_u8(hist, npx, 90.0), lowp = percentile_u8(hist, npx, 10.0);
+    const double contrast = (high - lowp) / std::max(10.0, high + lowp);
+    if (!(contrast < target)) return false;
+    const double ratio = 200.0 / std::max(10.0, high - lowp);
+    for (int v = 0; v < 256; ++v) {
+        double x = ((double)v - lowp + 25) * ratio;
+        x = std::max(0.0, std::min(255.0, x));
+        lut[v] = (uint8_t)x;
+    }
+    return true;
+}
 
 static void rec_check_params(bbocr_ctx* c, const bbocr_params& p) {
     if (!c->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
@@ -379,7 +396,7 @@ static void rec_plan_pages(const HostBoxes& hb, int b0, int b1, int H, int W, st
 }
 
 // crop scratch offsets of jobs [first, end), continuing at a_total / w_total
-static void rec_layout_scratch(std::vector<BoxJob>& jobs, size_t first, size_t& a_total, size_t& w_total) {
+void rec_layout_scratch(std::vector<BoxJob>& jobs, size_t first, size_t& a_total, size_t& w_total) {
     for (size_t i = first; i < jobs.size(); ++i) {
         BoxJob& j = jobs[i];
         j.d.a_off = (int)a_total;
@@ -392,7 +409,9 @@ static void rec_layout_scratch(std::vector<BoxJob>& jobs, size_t first, size_t& 
     }
 }
 
-// enqueue the feature part of pages [0, pages) of a B-page batch; the buffers that must survive until the rest arrives (stage-A
+// RecEarly: state of a recognition whose FIRST feature part (the crops of pages [0, pages)) was enqueued before the boxes of the remaining
+// pages existed (readtext_batch: while the last detector pass's CCL + host geometry run).  recognize_impl picks it up and adds the rest.
+// rec_early_begin enqueues the feature part of pages [0, pages) of a B-page batch; the buffers that must survive until the rest arrives (stage-A
 // crops for the contrast retry, pooled rows) are sized for the whole batch by extrapolation
 void rec_early_begin(bbocr_ctx* c, const uint8_t* gray, int pages, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p,
                             RecEarly& e) {
@@ -459,8 +478,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
             for (const BoxJob& j : page) page_w = std::max(page_w, j.d.imgW);
             for (BoxJob& j : page) {
                 j.d.imgW = page_w;
-                const int cw = (int)std::ceil(64 * ((double)j.d.rw / (double)j.d.rh));
-                j.d.fw = cw > page_w ? page_w : cw;
+                crop_refit_fw(j.d);
                 jobs.push_back(j);
             }
         }
@@ -472,8 +490,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
             BoxJob j = jobs[i];
             j.d.rot = angles[r] / 90;
             if (j.d.rot & 1) std::swap(j.d.rw, j.d.rh);
-            const int cw = (int)std::ceil(64 * ((double)j.d.rw / (double)j.d.rh));       // AlignCollate on the rotated image
-            j.d.fw = cw > j.d.imgW ? j.d.imgW : cw;
+            crop_refit_fw(j.d);                       // AlignCollate on the rotated image
             jobs.push_back(j);
         }
     // the variants only live inside this function: whatever path returns, the caller sees one job per box
@@ -556,17 +573,10 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
     std::vector<int> redo;
     std::vector<uint8_t> luts;
     for (size_t k = 0; k < low.size(); ++k) {
-        const size_t npx = (size_t)ld[k].rw * ld[k].rh;
-        const double high = percentile_u8(&hist[k * 256], npx, 90.0), lowp = percentile_u8(&hist[k * 256], npx, 10.0);
-        const double contrast = (high - lowp) / std::max(10.0, high + lowp);
-        if (!(contrast < p.adjust_contrast)) continue;
-        const double ratio = 200.0 / std::max(10.0, high - lowp);
+        uint8_t lut[256];
+        if (!contrast_lut(&hist[k * 256], (size_t)ld[k].rw * ld[k].rh, p.adjust_contrast, lut)) continue;
         jobs[low[k]].d.lut_off = (int)luts.size();
-        for (int v = 0; v < 256; ++v) {
-            double x = ((double)v - lowp + 25) * ratio;
-            x = std::max(0.0, std::min(255.0, x));
-            luts.push_back((uint8_t)x);
-        }
+        luts.insert(luts.end(), lut, lut + 256);
         redo.push_back(low[k]);
     }
     if (!redo.empty()) {

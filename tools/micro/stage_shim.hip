@@ -44,13 +44,17 @@ bool dims_ok(int N, int H, int W) { return N > 0 && H > 0 && W > 0 && (long long
         if (!(cond)) { g_err = "bad arguments: " #cond; return SHIM_BAD_ARGS; } \
     } while (0)
 
-// helper-allocated outputs live in the context's arena: dry pass, arena.buf.ensure, real pass (as bbocr_crnn_logits does), then a copy out
-template <typename F> hipError_t with_arena(bbocr_ctx* c, uint16_t* out, size_t out_elems, F&& stage) {
+// what a stage carves from the context's arena: dry pass, arena.buf.ensure, real pass (as a detector pass does)
+template <typename F> auto in_arena(bbocr_ctx* c, F&& stage) {
     c->arena.begin(true);
     (void)stage();
     c->arena.buf.ensure(c->arena.off);
     c->arena.begin(false);
-    const Act o = stage();
+    return stage();
+}
+// helper-allocated outputs live in the arena: a copy out
+template <typename F> hipError_t with_arena(bbocr_ctx* c, uint16_t* out, size_t out_elems, F&& stage) {
+    const Act o = in_arena(c, stage);
     if ((size_t)o.N * o.H * o.W * o.C != out_elems) fail(BBOCR_ERR_INTERNAL, "stage shim: output size differs from the caller's tensor");
     return hipMemcpyAsync(out, o.p, out_elems * 2, hipMemcpyDeviceToDevice, c->stream);
 }
@@ -90,8 +94,8 @@ int stage_up1a(bbocr_ctx* c, const uint16_t* f7, size_t f7_elems, const uint16_t
     });
 }
 
-// the skip half of a U-net 1x1 with up(z) added in its epilogue (craft_forward::up_stage's second launch; level 4: the first launch of
-// upconv4's two-launch path): skip [N, H, W, Cs], z [N, H/2, W/2, cout] -> out [N, H, W, cout] = ReLU(up(z) + W_s skip + b)
+// the skip half of a U-net 1x1 with up(z) added in its epilogue (craft_up_stage's second launch; level 4: the first launch of
+// craft_up4's two-launch path): skip [N, H, W, Cs], z [N, H/2, W/2, cout] -> out [N, H, W, cout] = ReLU(up(z) + W_s skip + b)
 int stage_addup(bbocr_ctx* c, int level, const uint16_t* skip, size_t skip_elems, const uint16_t* z, size_t z_elems, int N, int H, int W, uint16_t* out,
                 size_t out_elems) {
     NEED(c && fast_detector(c) && skip && z && out && dims_ok(N, H, W) && H % 2 == 0 && W % 2 == 0 && level >= 2 && level <= 4);
@@ -111,12 +115,9 @@ int stage_up3b_post(bbocr_ctx* c, const uint16_t* u3a, size_t u3a_elems, int N, 
     NEED(c && fast_detector(c) && c->up4y_post && u3a && z && dims_ok(N, H, W));
     NEED(u3a_elems == px(N, H, W) * 128 && z_elems == px(N, H, W) * 64);
     return run_stage(c, [&] {
-        // detector.cpp::craft_forward, "if (c->up4y_post && !c->up3b.split)": hipErrorNotSupported is returned, production would fall back
-        ConvArgs a{};
-        a.in0 = u3a; a.C0 = 128; a.in0_cs = 128;
-        a.N = N; a.H = H; a.W = W;
-        a.relu_out = 1; a.out = z; a.out_cs = 64; a.cout_store = 64; a.post_w = c->up4y_post;
-        return launch_conv_profiled(c, c->up3b, a, true);
+        // hipErrorNotSupported: the fused launch was declined and the two launches ran (through u3b in the arena), as in a detector pass
+        const Act a{(uint16_t*)u3a, N, H, W, 128};
+        return in_arena(c, [&] { return craft_up3b_post(c, a, c->arena.alloc<uint16_t>(px(N, H, W) * 64), z); }) ? hipSuccess : hipErrorNotSupported;
     });
 }
 
@@ -125,14 +126,8 @@ int stage_up4_fused(bbocr_ctx* c, const uint16_t* s1, size_t s1_elems, const uin
     NEED(c && fast_detector(c) && s1 && z && u4b && dims_ok(N, H, W) && H % 2 == 0 && W % 2 == 0);
     NEED(s1_elems == px(N, H, W) * 128 && z_elems == px(N, H / 2, W / 2) * 64 && u4b_elems == px(N, H, W) * 32);
     return run_stage(c, [&] {
-        // detector.cpp::craft_forward, the block behind "upconv4 as ONE launch" (launch_up4_profiled with profiling off)
-        ConvArgs a{};
-        a.in0 = s1; a.C0 = 128; a.in0_cs = 128;
-        a.N = N; a.H = H; a.W = W;
-        a.addup = z; a.up_H = H; a.up_W = W; a.up_cs = 64;
-        a.relu_out = 1; a.out = u4b; a.out_cs = 32; a.cout_store = 32;
-        a.zero = c->zero_page;
-        return launch_up4_fused(c->up4s, c->up4b, a, c->cur);
+        const Act a{(uint16_t*)s1, N, H, W, 128};
+        return in_arena(c, [&] { return craft_up4(c, a, z, u4b); }) ? hipSuccess : hipErrorNotSupported;      // as above
     });
 }
 
@@ -141,12 +136,9 @@ int stage_cls_tail(bbocr_ctx* c, const uint16_t* c2, size_t c2_elems, int N, int
     NEED(c && fast_detector(c) && c->cls_tail && c->cls_tail_frag && c2 && heat && dims_ok(N, H, W));
     NEED(c2_elems == px(N, H, W) * 32 && heat_elems == px(N, H, W) * 2);
     return run_stage(c, [&] {
-        // detector.cpp::craft_forward, the block behind "conv_cls.4 ... with conv_cls.6/.8 fused into its epilogue"
-        ConvArgs a{};
-        a.in0 = c2; a.C0 = 32; a.in0_cs = 32;
-        a.N = N; a.H = H; a.W = W;
-        a.relu_out = 1; a.out = heat; a.out_cs = 16; a.cout_store = 16; a.tail = c->cls_tail; a.tail_frag = c->cls_tail_frag;
-        return launch_conv_profiled(c, c->cls4, a);
+        c->arena.begin(false);                    // nothing is carved from the arena here
+        craft_cls_tail(c, Act{(uint16_t*)c2, N, H, W, 32}, heat);
+        return hipSuccess;
     });
 }
 
@@ -162,7 +154,7 @@ int stage_pool5(bbocr_ctx* c, const uint16_t* in, size_t in_elems, int N, int H,
 }
 
 // BiLSTM recurrence of layer l over a tile table given on the HOST (int4 {first row, sequences, T, 0} per workgroup): xproj [rows_pad, 2048]
-// in the permuted channel order, out [rows_pad, 512] (fwd | bwd).  rows_pad: a multiple of 256, as bbocr_crnn_logits allocates.
+// in the permuted channel order, out [rows_pad, 512] (fwd | bwd).  rows_pad: a multiple of 256, as the sequence stage allocates.
 int stage_lstm(bbocr_ctx* c, int layer, const uint16_t* xproj, uint16_t* out, size_t rows_pad, const int* tiles_host, int ntiles) {
     NEED(c && c->crnn_loaded && !rec_split(c) && (layer == 0 || layer == 1) && c->whh[layer] && xproj && out && tiles_host && ntiles > 0 && ntiles <= 65535);
     NEED(rows_pad > 0 && rows_pad % 256 == 0 && rows_pad < ((size_t)1 << 24));
