@@ -1,0 +1,462 @@
+// Baseline JPEG decoding, host side: the marker parser (bbocr_host_jpeg_plan: one linear pass, no entropy bit decoded), the per-batch
+// tables of jpegdec.hip (unstuffed segment bytes, subsequence lists, derived Huffman tables) and its launch sequence.  A batch runs on
+// its own stream of the root context, outside the call slots (the contract of bbocr_upload_pages): files decode while two OCR calls run.
+#include "ctx.h"
+
+namespace {
+
+constexpr unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct HuffSpec { bool have = false; unsigned char counts[16] = {0}; unsigned char vals[256] = {0}; int total = 0; };
+struct JpegParsed {
+    bbocr_jpeg_plan plan{};
+    unsigned short quant[3][64];              // per component, natural order
+    HuffSpec huff[2][2];                      // [class][id]
+    int tab_dc[3], tab_ac[3];
+    std::vector<std::pair<size_t, size_t>> segs;   // byte ranges of the restart segments in the file (stuffing included)
+};
+
+// jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.  Returns the reason.
+int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
+    bbocr_jpeg_plan& pl = out.plan;
+    pl = bbocr_jpeg_plan{};
+    if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
+    size_t p = 2;
+    unsigned short qt[4][64];
+    bool have_qt[4] = {false, false, false, false};
+    bool have_sof = false, jfif = false;
+    int adobe = -1, comp_id[4] = {0}, comp_tq[4] = {0}, dri = 0;
+    size_t scan_off = 0;
+    for (;;) {
+        for (;;) {
+            if (p + 2 > n || f[p] != 0xFF) return BBOCR_JPEG_TRUNCATED;
+            if (f[p + 1] == 0xFF) { ++p; continue; }
+            break;
+        }
+        const int m = f[p + 1];
+        p += 2;
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (m == 0xD9) return BBOCR_JPEG_TRUNCATED;
+        if (p + 2 > n) return BBOCR_JPEG_TRUNCATED;
+        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
+        if (L < 2 || p + L > n) return BBOCR_JPEG_TRUNCATED;
+        const uint8_t* s = f + p + 2;
+        const size_t sl = L - 2;
+        if (m == 0xC0) {
+            if (have_sof || sl < 6) return BBOCR_JPEG_SOF;
+            if (s[0] != 8) return BBOCR_JPEG_PRECISION;
+            pl.height = (s[1] << 8) | s[2];
+            pl.width = (s[3] << 8) | s[4];
+            pl.components = s[5];
+            if (pl.height == 0 || pl.width == 0 || sl < 6 + 3 * (size_t)pl.components) return BBOCR_JPEG_SOF;
+            for (int i = 0; i < pl.components && i < 4; ++i) {
+                comp_id[i] = s[6 + 3 * i];
+                if (i < 3) { pl.sampling[i][0] = s[7 + 3 * i] >> 4; pl.sampling[i][1] = s[7 + 3 * i] & 15; }
+                comp_tq[i] = s[8 + 3 * i];
+            }
+            have_sof = true;
+        } else if (m >= 0xC1 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
+            return BBOCR_JPEG_SOF;                           // extended, progressive, lossless, arithmetic conditioning
+        } else if (m == 0xC4) {
+            size_t q = 0;
+            while (q < sl) {
+                if (q + 17 > sl) return BBOCR_JPEG_TABLES;
+                const int tc = s[q] >> 4, th = s[q] & 15;
+                int tot = 0;
+                for (int i = 0; i < 16; ++i) tot += s[q + 1 + i];
+                if (tc > 1 || th > 1 || tot > 256 || q + 17 + tot > sl) return BBOCR_JPEG_TABLES;
+                HuffSpec& h = out.huff[tc][th];
+                h.have = true;
+                h.total = tot;
+                std::memcpy(h.counts, s + q + 1, 16);
+                std::memset(h.vals, 0, 256);
+                std::memcpy(h.vals, s + q + 17, (size_t)tot);
+                q += 17 + (size_t)tot;
+            }
+        } else if (m == 0xDB) {
+            size_t q = 0;
+            while (q < sl) {
+                if (s[q] >> 4) return BBOCR_JPEG_PRECISION;
+                const int id = s[q] & 15;
+                if (id > 3 || q + 65 > sl) return BBOCR_JPEG_TABLES;
+                for (int k = 0; k < 64; ++k) qt[id][kZigzag[k]] = s[q + 1 + k];
+                have_qt[id] = true;
+                q += 65;
+            }
+        } else if (m == 0xDD) {
+            if (sl < 2) return BBOCR_JPEG_TRUNCATED;
+            dri = (s[0] << 8) | s[1];
+        } else if (m == 0xE0 && sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) {
+            jfif = true;
+        } else if (m == 0xEE && sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
+            adobe = s[11];
+        } else if (m == 0xDA) {
+            if (!have_sof) return BBOCR_JPEG_SOF;
+            const int nc = pl.components;
+            if (nc != 1 && nc != 3) return BBOCR_JPEG_COMPONENTS;
+            if (nc == 3) {
+                if (!jfif && adobe != 1) return BBOCR_JPEG_COLORSPACE;
+                if (pl.sampling[0][0] != 2 || pl.sampling[0][1] != 2 || pl.sampling[1][0] != 1 || pl.sampling[1][1] != 1 || pl.sampling[2][0] != 1 ||
+                    pl.sampling[2][1] != 1)
+                    return BBOCR_JPEG_SAMPLING;
+            }
+            if (sl < 1 || s[0] != nc || sl < 1 + 2 * (size_t)nc + 3) return BBOCR_JPEG_MULTISCAN;
+            for (int i = 0; i < nc; ++i) {
+                if (s[1 + 2 * i] != comp_id[i]) return BBOCR_JPEG_MULTISCAN;
+                const int td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
+                if (td > 1 || ta > 1 || !out.huff[0][td].have || !out.huff[1][ta].have || comp_tq[i] > 3 || !have_qt[comp_tq[i]]) return BBOCR_JPEG_TABLES;
+                out.tab_dc[i] = td;
+                out.tab_ac[i] = 2 + ta;
+                std::memcpy(out.quant[i], qt[comp_tq[i]], sizeof qt[0]);
+            }
+            scan_off = p + L;
+            break;
+        }
+        p += L;
+    }
+    const int mcu = pl.components == 3 ? 16 : 8;
+    pl.mcu_cols = (pl.width + mcu - 1) / mcu;
+    pl.mcu_rows = (pl.height + mcu - 1) / mcu;
+    pl.restart_interval = dri;
+    pl.scan_offset = (long long)scan_off;
+    const long long nmcu = (long long)pl.mcu_cols * pl.mcu_rows;
+    size_t q = scan_off, start = scan_off, end = 0;
+    bool found = false;
+    int nseg = 0;
+    while (q < n) {
+        const void* hit = std::memchr(f + q, 0xFF, n - q);
+        if (!hit) break;
+        q = (size_t)((const uint8_t*)hit - f);
+        if (q + 1 >= n) break;
+        const int b = f[q + 1];
+        if (b == 0x00) {
+            q += 2;
+        } else if (b == 0xFF) {
+            q += 1;
+        } else if (b >= 0xD0 && b <= 0xD7) {
+            if (b - 0xD0 != nseg % 8) return BBOCR_JPEG_RESTART;
+            if (want_segs) out.segs.emplace_back(start, q);
+            ++nseg;
+            q += 2;
+            start = q;
+        } else {
+            if (want_segs) out.segs.emplace_back(start, q);
+            ++nseg;
+            end = q;
+            found = true;
+            break;
+        }
+    }
+    if (!found) return BBOCR_JPEG_NO_EOI;
+    if (f[end + 1] != 0xD9) return BBOCR_JPEG_MULTISCAN;
+    const long long ri = dri ? dri : nmcu;
+    if ((long long)nseg != (nmcu + ri - 1) / ri) return BBOCR_JPEG_RESTART;
+    pl.segments = nseg;
+    pl.scan_bytes = (long long)(end - scan_off);
+    pl.supported = 1;
+    return BBOCR_JPEG_OK;
+}
+
+// jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
+bool derive_table(const HuffSpec& h, JpegHuff& t) {
+    std::memset(&t, 0, sizeof t);
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int cnt = h.counts[l - 1];
+        t.valoff[l] = k - code;
+        if (cnt) {
+            if (code + cnt > (1 << l)) return false;
+            for (int i = 0; i < cnt; ++i, ++k, ++code)
+                if (l <= 9)
+                    for (int e = 0; e < (1 << (9 - l)); ++e) t.look[(code << (9 - l)) + e] = (unsigned short)((l << 8) | h.vals[k]);
+            t.maxcode[l] = code - 1;
+        } else {
+            t.maxcode[l] = -1;
+        }
+        code <<= 1;
+    }
+    t.maxcode[0] = t.maxcode[17] = -1;
+    std::memcpy(t.val, h.vals, 256);
+    return true;
+}
+
+struct FileJob {
+    JpegParsed ps;
+    int nsub = 0, groups = 0, nblocks = 0;
+    size_t o_huff, o_quant, o_segbyte, o_segsub, o_subseg, o_data, data_bytes;   // offsets in the input blob
+    size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[3], o_coef; // offsets in the work / coefficient buffers
+};
+
+void jpeg_stream_ready(bbocr_ctx* root) {
+    if (!root->jpeg_stream) HIPCHK(hipStreamCreateWithFlags(&root->jpeg_stream, hipStreamNonBlocking));
+}
+
+// The whole decode of `n` planned files; out[k] / pitch[k] / px: where the pixels go.  Fills dev_status[k] (JD_ERR_* bits) and leaves the
+// jobs for the stage entry point.  Everything is queued on the root's JPEG stream and finished on return.
+void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>& jobs, int S, uint8_t* const* outs, const long long* pitches,
+              int px, std::vector<int>& dev_status, std::vector<JpegDesc>* descs_out = nullptr) {
+    const int n = (int)jobs.size();
+    hipStream_t st = root->jpeg_stream;
+    size_t in_off = align_up(sizeof(JpegDesc) * (size_t)n, 256), work_off = align_up(4 * (size_t)n, 256), coef_off = 0;
+    auto carve = [](size_t& off, size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+    int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;
+    for (FileJob& j : jobs) {
+        const bbocr_jpeg_plan& pl = j.ps.plan;
+        j.o_huff = carve(in_off, 4 * sizeof(JpegHuff));
+        j.o_quant = carve(in_off, 3 * 64 * 2);
+        j.o_segbyte = carve(in_off, 4 * ((size_t)pl.segments + 1));
+        j.o_segsub = carve(in_off, 4 * ((size_t)pl.segments + 1));
+        j.o_data = carve(in_off, (size_t)pl.scan_bytes + 8);
+        // subsequences: every segment is cut on its own, so at most one per segment more than scan bits / S
+        j.o_subseg = carve(in_off, 4 * ((size_t)pl.segments + (size_t)pl.scan_bytes * 8 / S + 1));
+        j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? 6 : 1);
+        max_seg = std::max(max_seg, pl.segments);
+        max_blocks = std::max(max_blocks, j.nblocks);
+        max_h = std::max(max_h, pl.height);
+        max_w = std::max(max_w, pl.width);
+    }
+    root->jd_pin.ensure(in_off);
+    root->jd_in.ensure(in_off);
+    char* hb = (char*)root->jd_pin.p;
+    char* db = (char*)root->jd_in.p;
+    for (FileJob& j : jobs) {                                             // fill the blob: unstuff, cut, derive
+        const bbocr_jpeg_plan& pl = j.ps.plan;
+        JpegHuff* ht = (JpegHuff*)(hb + j.o_huff);
+        for (int cls = 0; cls < 2; ++cls)
+            for (int id = 0; id < 2; ++id)
+                if (!derive_table(j.ps.huff[cls][id], ht[cls * 2 + id])) std::memset(&ht[cls * 2 + id], 0, sizeof(JpegHuff));   // no code: the file fails
+        std::memcpy(hb + j.o_quant, j.ps.quant, sizeof j.ps.quant);
+        int* seg_byte = (int*)(hb + j.o_segbyte);
+        int* seg_sub = (int*)(hb + j.o_segsub);
+        int* sub_seg = (int*)(hb + j.o_subseg);
+        uint8_t* data = (uint8_t*)(hb + j.o_data);
+        size_t w = 0;
+        int nsub = 0;
+        for (int s = 0; s < pl.segments; ++s) {
+            const uint8_t* a = files[&j - jobs.data()] + j.ps.segs[s].first;
+            const uint8_t* e = files[&j - jobs.data()] + j.ps.segs[s].second;
+            seg_byte[s] = (int)w;
+            seg_sub[s] = nsub;
+            while (a < e) {                                               // copy up to and including the next FF, drop the 00 behind it
+                const uint8_t* ff = (const uint8_t*)std::memchr(a, 0xFF, (size_t)(e - a));
+                const size_t len = ff ? (size_t)(ff - a) + 1 : (size_t)(e - a);
+                std::memcpy(data + w, a, len);
+                w += len;
+                a += len;
+                if (ff && a < e && *a == 0x00) ++a;
+            }
+            const size_t bits = (w - (size_t)seg_byte[s]) * 8;
+            const int cnt = (int)std::max<size_t>((bits + S - 1) / S, 1);
+            for (int k = 0; k < cnt; ++k) sub_seg[nsub + k] = s;
+            nsub += cnt;
+        }
+        seg_byte[pl.segments] = (int)w;
+        seg_sub[pl.segments] = nsub;
+        j.data_bytes = w;
+        j.nsub = nsub;
+        j.groups = (nsub + JD_LANES - 1) / JD_LANES;
+        max_groups = std::max(max_groups, j.groups);
+        j.w_entry = carve(work_off, 8 * (size_t)nsub);
+        j.w_exits = carve(work_off, 8 * (size_t)nsub);
+        j.w_count = carve(work_off, 4 * (size_t)nsub);
+        j.w_scan = carve(work_off, 4 * (size_t)nsub);
+        j.w_first = carve(work_off, 4 * (size_t)nsub);
+        const size_t mcu = pl.components == 3 ? 16 : 8, ysz = (size_t)pl.mcu_cols * mcu * pl.mcu_rows * mcu;
+        j.w_plane[0] = carve(work_off, ysz);
+        j.w_plane[1] = carve(work_off, pl.components == 3 ? ysz / 4 : 0);
+        j.w_plane[2] = carve(work_off, pl.components == 3 ? ysz / 4 : 0);
+        j.o_coef = carve(coef_off, (size_t)j.nblocks * 128);
+    }
+    const int passes = max_groups + 1;
+    size_t flags_off = work_off;
+    for (FileJob& j : jobs) j.w_flags = carve(work_off, 4 * (size_t)passes);
+    root->jd_work.ensure(work_off);
+    root->jd_coef.ensure(std::max<size_t>(coef_off, 256));
+    char* wb = (char*)root->jd_work.p;
+    JpegDesc* descs = (JpegDesc*)hb;
+    for (int k = 0; k < n; ++k) {
+        const FileJob& j = jobs[k];
+        const bbocr_jpeg_plan& pl = j.ps.plan;
+        JpegDesc d{};
+        d.data = (const uint8_t*)(db + j.o_data);
+        d.seg_byte = (const int*)(db + j.o_segbyte);
+        d.seg_sub = (const int*)(db + j.o_segsub);
+        d.sub_seg = (const int*)(db + j.o_subseg);
+        d.entry = (unsigned long long*)(wb + j.w_entry);
+        d.exits = (unsigned long long*)(wb + j.w_exits);
+        d.count = (int*)(wb + j.w_count);
+        d.scan = (int*)(wb + j.w_scan);
+        d.first = (int*)(wb + j.w_first);
+        d.flags = (int*)(wb + j.w_flags);
+        d.status = (int*)wb + k;
+        d.coef = (short*)((char*)root->jd_coef.p + j.o_coef);
+        for (int c = 0; c < 3; ++c) d.plane[c] = (uint8_t*)(wb + j.w_plane[c]);
+        d.out = outs[k];
+        d.pitch = pitches[k];
+        d.huff = (const JpegHuff*)(db + j.o_huff);
+        d.quant = (const unsigned short*)(db + j.o_quant);
+        d.W = pl.width;
+        d.H = pl.height;
+        d.ncomp = pl.components;
+        d.bpm = pl.components == 3 ? 6 : 1;
+        d.mcux = pl.mcu_cols;
+        d.mcuy = pl.mcu_rows;
+        d.nmcu = pl.mcu_cols * pl.mcu_rows;
+        d.ri = pl.restart_interval ? pl.restart_interval : d.nmcu;
+        d.nseg = pl.segments;
+        d.nsub = j.nsub;
+        d.S = S;
+        d.nblocks = j.nblocks;
+        d.px = pl.components == 3 ? px : 1;
+        d.passes = passes;
+        for (int c = 0; c < 3; ++c) { d.tab_dc[c] = j.ps.tab_dc[c]; d.tab_ac[c] = j.ps.tab_ac[c]; }
+        descs[k] = d;
+    }
+    if (descs_out) descs_out->assign(descs, descs + n);
+    HIPCHK(hipMemcpyAsync(db, hb, in_off, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(wb, 0, align_up(4 * (size_t)n, 256), st));                    // status words
+    HIPCHK(hipMemsetAsync(wb + flags_off, 0, work_off - flags_off, st));                // pass flags
+    HIPCHK(hipMemsetAsync(root->jd_coef.p, 0, std::max<size_t>(coef_off, 256), st));
+    const JpegDesc* dd = (const JpegDesc*)db;
+    for (int pass = 0; pass < passes; ++pass) HIPCHK(launch_jd_sync(dd, n, max_groups, pass, st));
+    HIPCHK(launch_jd_scan(dd, n, st));
+    HIPCHK(launch_jd_write(dd, n, max_groups, st));
+    HIPCHK(launch_jd_dc(dd, n, max_seg, st));
+    HIPCHK(launch_jd_idct(dd, n, max_blocks, st));
+    HIPCHK(launch_jd_output(dd, n, max_h, max_w, st));
+    dev_status.assign((size_t)n, 0);
+    HIPCHK(hipMemcpyAsync(dev_status.data(), wb, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+}
+
+// entry points outside the call slots: errors reported like every other entry point's, the stream drained when a call fails
+template <typename F> int jpeg_guarded(bbocr_ctx* root, F&& f) {
+    if (!root) return BBOCR_ERR_ARG;
+    auto set_err = [&](const std::string& m) {
+        std::lock_guard<std::mutex> lk(root->pool_mu);
+        root->err = m;
+    };
+    try {
+        HIPCHK(hipSetDevice(root->cfg.device));
+        std::lock_guard<std::mutex> lk(root->jpeg_mu);
+        try {
+            jpeg_stream_ready(root);
+            HIPCHK(hipStreamSynchronize(nullptr));             // what the caller queued on the default stream (torch's allocations and fills)
+            f();
+            return BBOCR_OK;
+        } catch (...) {
+            if (root->jpeg_stream) (void)hipStreamSynchronize(root->jpeg_stream);
+            (void)hipGetLastError();
+            throw;
+        }
+    } catch (const StatusError& se) {
+        set_err(se.msg);
+        return se.code;
+    } catch (const std::exception& ex) {
+        set_err(ex.what());
+        return BBOCR_ERR_INTERNAL;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* plan) {
+    if (!file || !plan) return BBOCR_ERR_ARG;
+    JpegParsed ps;
+    const int reason = jpeg_parse(file, bytes, ps, false);
+    *plan = ps.plan;
+    plan->supported = reason == BBOCR_JPEG_OK;
+    plan->reason = reason;
+    return BBOCR_OK;
+}
+
+int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, uint8_t* const* dev_out,
+                      const long long* pitches, int* status) {
+    return jpeg_guarded(ctx, [&] {
+        if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
+        if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
+        const int px = layout == BBOCR_PAGE_YCBCR4 ? 4 : 3;
+        std::vector<FileJob> jobs;
+        std::vector<int> which;
+        std::vector<const uint8_t*> fs;
+        std::vector<uint8_t*> outs;
+        std::vector<long long> ps;
+        jobs.reserve((size_t)n);
+        for (int k = 0; k < n; ++k) {
+            status[k] = BBOCR_ERR_ARG;
+            if (!files[k] || !dev_out[k] || bytes[k] >= ((size_t)1 << 28)) continue;
+            FileJob j;
+            if (jpeg_parse(files[k], bytes[k], j.ps, true) != BBOCR_JPEG_OK) continue;      // the caller plans first: a refused file is its error
+            if (pitches[k] < (long long)j.ps.plan.width * (j.ps.plan.components == 3 ? px : 1)) continue;
+            jobs.push_back(std::move(j));
+            which.push_back(k);
+            fs.push_back(files[k]);
+            outs.push_back(dev_out[k]);
+            ps.push_back(pitches[k]);
+        }
+        if (jobs.empty()) return;
+        std::vector<int> st;
+        jpeg_run(ctx, fs.data(), jobs, JD_SUBSEQ_BITS, outs.data(), ps.data(), px, st);
+        for (size_t i = 0; i < which.size(); ++i) status[which[i]] = st[i] ? BBOCR_ERR_DATA : BBOCR_OK;
+    });
+}
+
+int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
+                        int* file_status) {
+    return jpeg_guarded(ctx, [&] {
+        if (!file || !dev_dst || stage < 0 || stage > 3 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
+        const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
+        if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
+        std::vector<FileJob> jobs(1);
+        if (jpeg_parse(file, bytes, jobs[0].ps, true) != BBOCR_JPEG_OK) fail(BBOCR_ERR_ARG, "the plan refuses this file");
+        const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
+        const int C = pl.components;
+        const size_t mcu = C == 3 ? 16 : 8, ysz = (size_t)pl.mcu_cols * mcu * pl.mcu_rows * mcu;
+        const size_t pix = (size_t)pl.width * pl.height * C;
+        // the pixels go to a scratch image unless they are the stage's output
+        ctx->jd_stage.ensure(pix);
+        uint8_t* out = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+        if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
+        const long long pitch = (long long)pl.width * C;
+        std::vector<int> st;
+        std::vector<JpegDesc> descs;
+        jpeg_run(ctx, &file, jobs, S, &out, &pitch, 3, st, &descs);
+        if (file_status) *file_status = st[0] ? BBOCR_ERR_DATA : BBOCR_OK;
+        const JpegDesc& d = descs[0];
+        hipStream_t s = ctx->jpeg_stream;
+        if (stage == 0) {
+            const size_t ns = (size_t)d.nsub;
+            if (dst_bytes < ns * 16) fail(BBOCR_ERR_ARG, "destination too small");
+            std::vector<unsigned long long> entry(ns);
+            std::vector<int> first(ns), rows(ns * 4);
+            HIPCHK(hipMemcpyAsync(entry.data(), d.entry, ns * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(first.data(), d.first, ns * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (size_t i = 0; i < ns; ++i) {
+                rows[4 * i] = (int)(unsigned)entry[i];
+                rows[4 * i + 1] = (int)((entry[i] >> 32) & 7);
+                rows[4 * i + 2] = (int)((entry[i] >> 40) & 63);
+                rows[4 * i + 3] = first[i];
+            }
+            HIPCHK(hipMemcpyAsync(dev_dst, rows.data(), ns * 16, hipMemcpyHostToDevice, s));
+        } else if (stage == 1) {
+            if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
+            HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
+        } else if (stage == 2) {
+            const size_t csz = C == 3 ? ysz / 4 : 0;
+            if (dst_bytes < ysz + 2 * csz) fail(BBOCR_ERR_ARG, "destination too small");
+            HIPCHK(hipMemcpyAsync(dev_dst, d.plane[0], ysz, hipMemcpyDeviceToDevice, s));
+            if (csz) {
+                HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz, d.plane[1], csz, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz + csz, d.plane[2], csz, hipMemcpyDeviceToDevice, s));
+            }
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    });
+}
+
+}  // extern "C"

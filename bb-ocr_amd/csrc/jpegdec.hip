@@ -1,0 +1,346 @@
+// Baseline JPEG decoding on the device (SOF0, Huffman, one interleaved scan, YCbCr 4:2:0 or grey), to the bit of libjpeg-turbo: the
+// entropy stage by speculative decoding with self-synchronisation (Weissenberger & Schmidt), then thumb.hip's decoder half (jpeg_dev.h).
+//   jd_sync     one lane per S-bit subsequence: decode from the assumed state (block 0 of the MCU, coefficient 0), then take the left
+//               neighbour's exit state and decode again until no state of the workgroup changes; launched once more per workgroup
+//               a segment spans, a launch returning at once when the launch before it changed nothing
+//   jd_scan     exclusive scan of the block counts: first output block of every subsequence
+//   jd_write    decode from the exact entry states into the zeroed coefficient buffer (natural order); checks what the file promised
+//   jd_dc       per component and restart segment: running sum of the DC differences
+//   jd_idct     dequantise + jidctint.c per block into the component planes
+//   jd_output   h2v2 fancy upsampling -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane, into the caller's tensor
+// The bytes are untrusted: every stream read is clamped to its segment (past the end: 1-bits), every store is index-checked, every loop
+// has a trip count fixed by the host's plan (S, lanes per workgroup, items per segment).
+#include "common.h"
+#include "kernels.h"
+#include "jpeg_dev.h"
+
+namespace {
+
+__device__ const unsigned char JD_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct JdState { unsigned p; int b, z; };                     // bit in `data`, block in the MCU, zig-zag position
+__device__ __forceinline__ unsigned long long jd_pack(const JdState& s) {
+    return (unsigned long long)s.p | ((unsigned long long)(unsigned)s.b << 32) | ((unsigned long long)(unsigned)s.z << 40);
+}
+__device__ __forceinline__ JdState jd_unpack(unsigned long long v) {
+    return JdState{(unsigned)v, (int)((v >> 32) & 7), (int)((v >> 40) & 63)};
+}
+
+// 16 bits at bit p of the segment whose bytes are [b0, b1); past the end: ones
+__device__ __forceinline__ unsigned jd_peek16(const uint8_t* __restrict__ data, unsigned b0, unsigned b1, unsigned p) {
+    const unsigned k = p >> 3;
+    unsigned w = 0;
+    for (int i = 0; i < 3; ++i) {
+        const unsigned a = k + i;
+        w = (w << 8) | ((a >= b0 && a < b1) ? (unsigned)data[a] : 0xFFu);
+    }
+    return (w >> (8 - (p & 7))) & 0xFFFFu;
+}
+
+__device__ __forceinline__ void jd_load_tables(const JpegHuff* __restrict__ g, JpegHuff* lds, int t, int nt) {
+    const int* src = (const int*)g;
+    int* dst = (int*)lds;
+    for (int i = t; i < (int)(4 * sizeof(JpegHuff) / 4); i += nt) dst[i] = src[i];
+    __syncthreads();
+}
+
+// Decode from st while its bit is before `end` and fewer than max_blocks blocks are complete.  Returns the blocks completed; *invalid: a
+// look-ahead without a code was met (the state's bit is then `end`).  coef != null: coefficients of block first_block + n are stored
+// (DC terms as differences).  At most S + 32 symbols: each takes at least one bit.
+__device__ int jd_run(const JpegDesc& d, const JpegHuff* T, unsigned b0, unsigned b1, JdState& st, unsigned end, int max_blocks, short* coef,
+                      int first_block, bool* invalid) {
+    unsigned p = st.p;
+    int b = st.b, z = st.z, n = 0;
+    *invalid = false;
+    const uint8_t* __restrict__ data = d.data;
+    for (int it = 0; it < d.S + 32 && p < end && n < max_blocks; ++it) {
+        const int c = d.bpm == 1 ? 0 : (b < 4 ? 0 : b - 3);
+        const int ti = z == 0 ? (c == 0 ? d.tab_dc[0] : (c == 1 ? d.tab_dc[1] : d.tab_dc[2])) : (c == 0 ? d.tab_ac[0] : (c == 1 ? d.tab_ac[1] : d.tab_ac[2]));
+        const JpegHuff& H = T[ti & 3];
+        const unsigned v = jd_peek16(data, b0, b1, p);
+        int len = 0, sym = 0;
+        const unsigned e = H.look[v >> 7];
+        if (e) {
+            len = (int)(e >> 8);
+            sym = (int)(e & 255);
+        } else {
+            for (int l = 10; l <= 16; ++l) {
+                const int code = (int)(v >> (16 - l));
+                if (code <= H.maxcode[l]) {
+                    len = l;
+                    sym = H.val[(code + H.valoff[l]) & 255];
+                    break;
+                }
+            }
+            if (!len) {
+                *invalid = true;
+                p = end;
+                break;
+            }
+        }
+        p += len;
+        int sz = sym & 15;
+        bool done = false;
+        if (z != 0) {
+            const int r = sym >> 4;
+            if (sz == 0) {                                     // ZRL skips 16 zeros, every other run length ends the block
+                z = r == 15 ? z + 16 : 64;
+                done = true;
+            } else {
+                z += r;
+            }
+        }
+        if (!done) {
+            int val = 0;
+            if (sz) {
+                const int bits = (int)(jd_peek16(data, b0, b1, p) >> (16 - sz));
+                p += sz;
+                val = bits >= (1 << (sz - 1)) ? bits : bits - (1 << sz) + 1;
+            }
+            const int blk = first_block + n;
+            if (coef && z <= 63 && (unsigned)blk < (unsigned)d.nblocks) coef[(size_t)blk * 64 + JD_ZZ[z]] = (short)val;
+            z += 1;
+        }
+        if (z > 63) {
+            z = 0;
+            b = b + 1 == d.bpm ? 0 : b + 1;
+            n += 1;
+        }
+    }
+    st.p = p;
+    st.b = b;
+    st.z = z;
+    return n;
+}
+
+struct JdSub { int seg, j; unsigned b0, b1, start, end; };
+__device__ __forceinline__ JdSub jd_sub(const JpegDesc& d, int i) {
+    JdSub s;
+    s.seg = min(max(d.sub_seg[i], 0), d.nseg - 1);
+    s.j = i - d.seg_sub[s.seg];
+    s.b0 = (unsigned)d.seg_byte[s.seg];
+    s.b1 = (unsigned)d.seg_byte[s.seg + 1];
+    s.start = s.b0 * 8u + (unsigned)s.j * (unsigned)d.S;
+    s.end = min(s.start + (unsigned)d.S, s.b1 * 8u);
+    return s;
+}
+
+__global__ void __launch_bounds__(JD_LANES) jd_sync_kernel(const JpegDesc* __restrict__ descs, int pass) {
+    __shared__ JpegHuff T[4];
+    __shared__ unsigned long long ex[JD_LANES];
+    const JpegDesc d = descs[blockIdx.y];
+    const int t = threadIdx.x, i = blockIdx.x * JD_LANES + t;
+    if ((int)blockIdx.x * JD_LANES >= d.nsub || pass >= d.passes) return;
+    if (pass > 0 && d.flags[pass - 1] == 0) return;           // the pass before changed nothing: every state is final
+    jd_load_tables(d.huff, T, t, JD_LANES);
+    const bool valid = i < d.nsub;
+    JdSub s{};
+    unsigned long long entry = 0, exit_ = 0;
+    int count = 0;
+    bool inv;
+    if (valid) {
+        s = jd_sub(d, i);
+        if (pass == 0) {
+            JdState st{s.start, 0, 0};
+            entry = jd_pack(st);
+            count = jd_run(d, T, s.b0, s.b1, st, s.end, 0x7fffffff, nullptr, 0, &inv);
+            exit_ = jd_pack(st);
+        } else {
+            entry = d.entry[i];
+            exit_ = d.exits[i];
+            count = d.count[i];
+        }
+    }
+    bool any = false;
+    for (int iter = 0; iter <= JD_LANES; ++iter) {
+        ex[t] = exit_;
+        __syncthreads();
+        bool ch = false;
+        if (valid && s.j > 0) {                               // subsequence 0 of a segment is exact by construction
+            unsigned long long prev = entry;
+            if (t > 0) prev = ex[t - 1];
+            else if (pass > 0) prev = __hip_atomic_load(&d.exits[i - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (prev != entry) {
+                entry = prev;
+                JdState st = jd_unpack(entry);
+                count = jd_run(d, T, s.b0, s.b1, st, s.end, 0x7fffffff, nullptr, 0, &inv);
+                exit_ = jd_pack(st);
+                ch = true;
+            }
+        }
+        if (!__syncthreads_or(ch)) break;
+        any = true;
+    }
+    if (valid) {
+        d.entry[i] = entry;
+        __hip_atomic_store(&d.exits[i], exit_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        d.count[i] = count;
+    }
+    if (t == 0 && (pass == 0 ? blockIdx.x == 0 : any)) d.flags[pass] = 1;
+}
+
+// one workgroup per file
+__global__ void __launch_bounds__(256) jd_scan_kernel(const JpegDesc* __restrict__ descs) {
+    __shared__ int sh[256];
+    const JpegDesc d = descs[blockIdx.x];
+    const int t = threadIdx.x;
+    int carry = 0;
+    for (int base = 0; base < d.nsub; base += 256) {
+        const int i = base + t;
+        const int v = i < d.nsub ? d.count[i] : 0;
+        sh[t] = v;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int a = t >= o ? sh[t - o] : 0;
+            __syncthreads();
+            sh[t] += a;
+            __syncthreads();
+        }
+        if (i < d.nsub) d.scan[i] = carry + sh[t] - v;
+        carry += sh[255];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(JD_LANES) jd_write_kernel(const JpegDesc* __restrict__ descs) {
+    __shared__ JpegHuff T[4];
+    const JpegDesc d = descs[blockIdx.y];
+    const int t = threadIdx.x, i = blockIdx.x * JD_LANES + t;
+    if ((int)blockIdx.x * JD_LANES >= d.nsub) return;
+    jd_load_tables(d.huff, T, t, JD_LANES);
+    if (i >= d.nsub) return;
+    const JdSub s = jd_sub(d, i);
+    const unsigned long long entry = d.entry[i];
+    int err = 0;
+    if (s.j > 0 && d.exits[i - 1] != entry) err |= JD_ERR_SYNC;
+    const long long seg_first = (long long)s.seg * d.ri * d.bpm;
+    const long long seg_end = seg_first + (long long)min(d.ri, d.nmcu - s.seg * d.ri) * d.bpm;
+    const long long first = seg_first + (d.scan[i] - d.scan[d.seg_sub[s.seg]]);
+    d.first[i] = (int)min(first, (long long)d.nblocks);
+    const int room = (int)max(min(seg_end - first, (long long)d.nblocks), 0LL);
+    JdState st = jd_unpack(entry);
+    bool inv;
+    const int n = jd_run(d, T, s.b0, s.b1, st, s.end, room, d.coef, (int)min(first, (long long)d.nblocks), &inv);
+    if (inv) err |= JD_ERR_CODE;
+    if (n != d.count[i]) err |= JD_ERR_COUNT;
+    if (i + 1 == d.seg_sub[s.seg + 1] && (first + n != seg_end || st.b != 0 || st.z != 0)) err |= JD_ERR_COUNT;
+    if (err) atomicOr(d.status, err);
+}
+
+// one workgroup per (segment, component, file): inclusive sum of the DC differences in MCU order
+__global__ void __launch_bounds__(256) jd_dc_kernel(const JpegDesc* __restrict__ descs) {
+    __shared__ int sh[256];
+    const JpegDesc d = descs[blockIdx.z];
+    const int seg = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+    if (seg >= d.nseg || c >= d.ncomp) return;
+    const int m0 = seg * d.ri, nm = min(d.ri, d.nmcu - m0);
+    const int per = (d.ncomp == 3 && c == 0) ? 4 : 1;
+    const int items = nm * per;
+    int carry = 0;
+    for (int base = 0; base < items; base += 256 * 8) {
+        int v[8], sum = 0;
+        for (int e = 0; e < 8; ++e) {
+            const int k = base + t * 8 + e;
+            int x = 0;
+            if (k < items) {
+                const int blk = (m0 + k / per) * d.bpm + (d.ncomp == 3 ? (c == 0 ? k % per : 3 + c) : 0);
+                if ((unsigned)blk < (unsigned)d.nblocks) x = d.coef[(size_t)blk * 64];
+            }
+            sum += x;
+            v[e] = sum;
+        }
+        sh[t] = sum;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int a = t >= o ? sh[t - o] : 0;
+            __syncthreads();
+            sh[t] += a;
+            __syncthreads();
+        }
+        const int excl = carry + sh[t] - sum;
+        for (int e = 0; e < 8; ++e) {
+            const int k = base + t * 8 + e;
+            if (k < items) {
+                const int blk = (m0 + k / per) * d.bpm + (d.ncomp == 3 ? (c == 0 ? k % per : 3 + c) : 0);
+                if ((unsigned)blk < (unsigned)d.nblocks) d.coef[(size_t)blk * 64] = (short)(excl + v[e]);
+            }
+        }
+        carry += sh[255];
+        __syncthreads();
+    }
+}
+
+// eight blocks per workgroup, eight lanes per block (a row, then a column, then a row again: thumb.hip's order)
+__global__ void __launch_bounds__(64) jd_idct_kernel(const JpegDesc* __restrict__ descs) {
+    __shared__ int blk[8][64];
+    const JpegDesc d = descs[blockIdx.y];
+    const int t = threadIdx.x, b = t >> 3, l = t & 7;
+    const int id = blockIdx.x * 8 + b;
+    if ((int)blockIdx.x * 8 >= d.nblocks) return;
+    const bool valid = id < d.nblocks;
+    const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
+    const int c = d.bpm == 1 ? 0 : (j < 4 ? 0 : j - 3);
+    if (valid) {
+        const short* co = d.coef + (size_t)id * 64 + l * 8;
+        const unsigned short* q = d.quant + c * 64 + l * 8;
+        for (int i = 0; i < 8; ++i) blk[b][l * 8 + i] = (int)co[i] * (int)q[i];
+    }
+    __syncthreads();
+    if (valid) idct8(&blk[b][l], 8, true);
+    __syncthreads();
+    if (valid) {
+        int* row = &blk[b][l * 8];
+        idct8(row, 1, false);
+        const int mx = mcu % d.mcux, my = mcu / d.mcux;
+        uint8_t* o;
+        if (d.bpm == 1) o = d.plane[0] + (size_t)(my * 8 + l) * (d.mcux * 8) + mx * 8;
+        else if (c == 0) o = d.plane[0] + (size_t)(my * 16 + (j >> 1) * 8 + l) * (d.mcux * 16) + mx * 16 + (j & 1) * 8;
+        else o = (c == 1 ? d.plane[1] : d.plane[2]) + (size_t)(my * 8 + l) * (d.mcux * 8) + mx * 8;
+        for (int i = 0; i < 8; ++i) o[i] = (uint8_t)row[i];
+    }
+}
+
+__global__ void __launch_bounds__(256) jd_output_kernel(const JpegDesc* __restrict__ descs) {
+    const JpegDesc d = descs[blockIdx.z];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= d.W || y >= d.H) return;
+    if (d.ncomp == 1) {
+        d.out[(size_t)y * d.pitch + x] = d.plane[0][(size_t)y * (d.mcux * 8) + x];
+        return;
+    }
+    const int wp = d.mcux * 16, ch = (d.H + 1) / 2, cw = (d.W + 1) / 2;
+    uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
+    o[0] = d.plane[0][(size_t)y * wp + x];
+    o[1] = (uint8_t)th_fancy(d.plane[1], wp / 2, ch, cw, y, x);
+    o[2] = (uint8_t)th_fancy(d.plane[2], wp / 2, ch, cw, y, x);
+    if (d.px == 4) o[3] = 255;
+}
+
+}  // namespace
+
+hipError_t launch_jd_sync(const JpegDesc* descs, int n, int max_groups, int pass, hipStream_t s) {
+    hipLaunchKernelGGL(jd_sync_kernel, dim3((unsigned)max_groups, (unsigned)n), dim3(JD_LANES), 0, s, descs, pass);
+    return hipGetLastError();
+}
+hipError_t launch_jd_scan(const JpegDesc* descs, int n, hipStream_t s) {
+    hipLaunchKernelGGL(jd_scan_kernel, dim3((unsigned)n), dim3(256), 0, s, descs);
+    return hipGetLastError();
+}
+hipError_t launch_jd_write(const JpegDesc* descs, int n, int max_groups, hipStream_t s) {
+    hipLaunchKernelGGL(jd_write_kernel, dim3((unsigned)max_groups, (unsigned)n), dim3(JD_LANES), 0, s, descs);
+    return hipGetLastError();
+}
+hipError_t launch_jd_dc(const JpegDesc* descs, int n, int max_seg, hipStream_t s) {
+    hipLaunchKernelGGL(jd_dc_kernel, dim3((unsigned)max_seg, 3u, (unsigned)n), dim3(256), 0, s, descs);
+    return hipGetLastError();
+}
+hipError_t launch_jd_idct(const JpegDesc* descs, int n, int max_blocks, hipStream_t s) {
+    hipLaunchKernelGGL(jd_idct_kernel, dim3((unsigned)((max_blocks + 7) / 8), (unsigned)n), dim3(64), 0, s, descs);
+    return hipGetLastError();
+}
+hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, hipStream_t s) {
+    hipLaunchKernelGGL(jd_output_kernel, dim3((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n), dim3(256), 0, s, descs);
+    return hipGetLastError();
+}

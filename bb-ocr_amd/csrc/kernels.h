@@ -220,3 +220,41 @@ hipError_t launch_th_jpeg(const uint8_t* src, size_t pitch, int C, int H, int W,
 hipError_t launch_th_upsample(const uint8_t* yp, int wp, const uint8_t* cbp, const uint8_t* crp, int H, int W, int gray_only, uint8_t* rgb,
                               uint8_t* gray, uint8_t* ycc, hipStream_t s);
 hipError_t launch_th_direct(const uint8_t* src, size_t pitch, int layout, int H, int W, uint8_t* rgb, uint8_t* gray, hipStream_t s);
+
+// ------------------------------------------------------------------ baseline JPEG decoder (jpegdec.hip): speculative Huffman decoding with self-synchronisation
+constexpr int JD_LANES = 64;                                   // subsequences per workgroup of the synchronisation and write passes
+constexpr int JD_SUBSEQ_BITS = 1024;                           // default subsequence length
+struct JpegHuff {                                              // one Huffman table as the lanes read it from LDS (jdhuff.c's derived table)
+    unsigned short look[512];                                  // 9-bit look-ahead: (length << 8) | symbol, 0 = the code is longer (or none)
+    int maxcode[18];                                           // largest code of length l, -1 = none
+    int valoff[18];                                            // index of the first symbol of length l minus its code
+    unsigned char val[256];
+};
+struct JpegDesc {                                              // one file of a batch; every pointer is device memory
+    const uint8_t* data;                                       // entropy-coded bytes without stuffing and restart markers, segment after segment
+    const int* seg_byte;                                       // [nseg + 1] first byte of each segment in `data`
+    const int* seg_sub;                                        // [nseg + 1] first subsequence of each segment
+    const int* sub_seg;                                        // [nsub] segment of each subsequence
+    unsigned long long* entry;                                 // [nsub] packed state (jd_pack) a lane starts from / ends in
+    unsigned long long* exits;
+    int* count;                                                // [nsub] blocks completed by the subsequence
+    int* scan;                                                 // [nsub] exclusive scan of count over the file
+    int* first;                                                // [nsub] first output block (written by the write pass)
+    int* flags;                                                // [passes + 1] flags[k] != 0: pass k changed a state
+    int* status;                                               // JD_ERR_* bits
+    short* coef;                                               // [nblocks][64] natural order, MCU block order
+    uint8_t* plane[3];                                         // Y [mcuy * 16 | 8][mcux * 16 | 8], Cb, Cr at half that
+    uint8_t* out;
+    long long pitch;
+    const JpegHuff* huff;                                      // [4]: DC 0, DC 1, AC 0, AC 1
+    const unsigned short* quant;                               // [ncomp][64] natural order
+    int W, H, ncomp, bpm, mcux, mcuy, nmcu, ri, nseg, nsub, S, nblocks, px, passes;
+    int tab_dc[3], tab_ac[3];                                  // per component: index into huff
+};
+enum : int { JD_ERR_SYNC = 1, JD_ERR_CODE = 2, JD_ERR_COUNT = 4 };
+hipError_t launch_jd_sync(const JpegDesc* descs, int n, int max_groups, int pass, hipStream_t s);
+hipError_t launch_jd_scan(const JpegDesc* descs, int n, hipStream_t s);
+hipError_t launch_jd_write(const JpegDesc* descs, int n, int max_groups, hipStream_t s);
+hipError_t launch_jd_dc(const JpegDesc* descs, int n, int max_seg, hipStream_t s);
+hipError_t launch_jd_idct(const JpegDesc* descs, int n, int max_blocks, hipStream_t s);
+hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, hipStream_t s);

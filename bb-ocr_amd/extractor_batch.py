@@ -19,10 +19,19 @@ import os
 import numpy as np
 
 
-def _ocr_input(image_path, image_index=None, decode_once=True):
+def _jpg_page(source):
+    """``("jpg", JpegPage, None)`` when the device decoder takes the file (a path or its bytes), else None"""
+    from .reader import jpeg_page
+
+    page = jpeg_page(source)
+    return None if page is None else ("jpg", page, None)
+
+
+def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False):
     """``ocr_input_image`` for the batching loop: ``("ycc", triples, None)`` when the file easyocr would be given is a YCbCr-coded JPEG
     (decoded once, RGB + Y plane derived on the card: reader.decode_file_ycc) -- every thumbnail is, it is written as one -- else
-    ``("rgb", rgb, gray)``."""
+    ``("rgb", rgb, gray)``.  ``device_decode``: the file easyocr would be given travels as its bytes (``("jpg", JpegPage, None)``) when the
+    device decoder takes it -- the original at or below the limit (only its header is read here), or the thumbnail as written."""
     from PIL import Image
 
     from .reader import decode_file, decode_file_ycc, reformat_input
@@ -37,10 +46,16 @@ def _ocr_input(image_path, image_index=None, decode_once=True):
             buf = io.BytesIO()
             img.save(buf, format="JPEG", quality=(90 if cover else 95))
             data = buf.getvalue()
+            page = _jpg_page(data) if device_decode else None
+            if page is not None:
+                return page
             ycc = decode_file_ycc(data, padded=True) if decode_once else None
             return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(data))
     except Exception:
         pass                                                      # :511-514: any failure falls back to the original file
+    page = _jpg_page(image_path) if device_decode else None
+    if page is not None:
+        return page
     ycc = decode_file_ycc(os.fspath(image_path), padded=True) if decode_once else None
     return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(reformat_input(os.fspath(image_path)))
 
@@ -70,13 +85,22 @@ def _ocr_input_array(page, image_index=None, decode_once=True):
     return ("rgb",) + tuple(decode_file(buf.getvalue()))
 
 
-def _ocr_input_device(reader, image_path, image_index=None, decode_once=True):
+def _ocr_input_device(reader, image_path, image_index=None, decode_once=True, device_decode=False):
     """``_ocr_input`` with the down-scaling on the card: a YCbCr-coded JPEG above the page's limit is decoded once on the host, uploaded
-    and thumbnailed + JPEG round-tripped on the device (``("dev", rgb_dev, gray_dev)``); every other file takes ``_ocr_input``."""
+    and thumbnailed + JPEG round-tripped on the device (``("dev", rgb_dev, gray_dev)``); every other file takes ``_ocr_input``.
+    ``device_decode``: a colour file the device decoder takes is decoded there as well -- above the limit it goes from its bytes to the
+    OCR input without ever existing as host pixels; at or below it travels as ``"jpg"``."""
     from .preprocess import ocr_input_ycc_device, ocr_thumbnail_rule
     from .reader import decode_file_ycc
 
     m, _ = ocr_thumbnail_rule(image_index)
+    page = _jpg_page(image_path) if device_decode else None
+    if page is not None and page[1].shape[2] == 3:
+        if max(page[1].shape[:2]) <= m:
+            return page
+        ycc, status = reader.decode_jpeg_batch([page[1]], padded=True)
+        if status[0] == 0:
+            return ("dev",) + tuple(ocr_input_ycc_device(reader, ycc[0], image_index))
     ycc = decode_file_ycc(os.fspath(image_path), padded=True)
     if ycc is None:
         return _ocr_input(image_path, image_index, decode_once)        # PNG, gray or CMYK JPEG, ...: the host path
@@ -133,14 +157,17 @@ def ocr_input_image(image_path, image_index=None):
 
 
 def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
-                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, **readtext_kw):
+                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, device_decode=False, **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
     batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
     ``use_preprocessing`` / ``edge_crop_percent`` / ``crop_for_ocr`` / ``crop_margin``: the extractor's settings of the same names
     (``ocr_page_crop``); with all of them off the pages are read as before.  ``device_thumbnail=True``: the down-scaling + JPEG round trip
     of :486-512 runs on the card (csrc/thumb.hip, identical pixels): a cropped page stays on the card from upload to OCR, and a
-    YCbCr-coded JPEG above the limit is uploaded as decoded and shrunk there."""
+    YCbCr-coded JPEG above the limit is uploaded as decoded and shrunk there.  ``device_decode=True``: the decode step only reads the file
+    and plans it (``bbocr_host_jpeg_plan``); baseline JPEG files -- the thumbnails included -- reach the card as their bytes and are
+    decoded there, a whole batch by one call (csrc/jpegdec.hip, identical pixels); every other file, and a file whose data turns out
+    damaged, takes the host decode as before.  (The crop settings read the page like ``cv2.imread`` and keep their host decode.)"""
     from .preprocess import ocr_input_device
 
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
@@ -153,9 +180,9 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
                 return ("dev",) + tuple(ocr_input_device(reader, page, i))
             return _ocr_input_array(page, i, decode_once)
     elif device_thumbnail:
-        decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once)
+        decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once, device_decode)
     else:
-        decode = lambda path, i: _ocr_input(path, i, decode_once)
+        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode)
     res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, **readtext_kw)
     return {i: " ".join(t[1] for t in r) for i, r in res.items()}
 
@@ -168,7 +195,20 @@ def _plain_input(path, i=None):
     return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(reformat_input(os.fspath(path)))
 
 
-def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=_plain_input, **readtext_kw):
+def _plain_input_device(path, i=None):
+    """``_plain_input`` with the device decoder: the file's bytes when it takes them"""
+    return _jpg_page(path) or _plain_input(path, i)
+
+
+def _host_input(page):
+    """The host decode of a ``JpegPage`` (the retry of a page whose device decode failed): what ``_plain_input`` returns for its file"""
+    from .reader import decode_file, decode_file_ycc
+
+    ycc = decode_file_ycc(page.data, padded=True)
+    return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(page.data))
+
+
+def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, **readtext_kw):
     """``{index: readtext result}`` for the files ``image_paths[i]``, i in ``indices`` (default: all): the result lists
     ``Reader.readtext(path)`` returns page by page, from 64-page device batches.  A page whose decode or OCR fails maps to ``[]``.
 
@@ -177,12 +217,16 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     (reader.decode_file_ycc: both planes are then derived on the card).  The files are therefore decoded by ``decode_workers`` threads (default:
     the host's cores, at most 16; PIL releases the GIL while decoding) and a shape group is sent to the device as soon as it is
     full, so the decode of later pages overlaps the device batch of earlier ones (ctypes releases the GIL during the C call).
-    ``decode(path, index)`` returns ``("ycc", triples, None)`` or ``("rgb", rgb, gray)``."""
+    ``decode(path, index)`` returns ``("ycc", triples, None)`` or ``("rgb", rgb, gray)``.  ``device_decode=True`` (or a ``decode`` that
+    returns ``("jpg", JpegPage, None)``): baseline JPEG files are only read and planned here and travel as their bytes, grouped by decoded
+    shape; the upload stage decodes a group on the card with one call, straight into the batch tensor."""
     import collections
     import queue
     import threading
     from concurrent.futures import ThreadPoolExecutor
 
+    if decode is None:
+        decode = _plain_input_device if device_decode else _plain_input
     if indices is None:
         indices = range(len(image_paths))
     idxs = [i for i in indices if 0 <= i < len(image_paths)]
@@ -217,6 +261,11 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
             by_shape = {}
 
             def flush(group):
+                if hasattr(group[0][1], "data") and isinstance(group[0][1].data, bytes):
+                    batches.put(("jpg", [p[0] for p in group], [p[1] for p in group]))     # file bytes: decoded by the upload stage
+                    for _ in group:
+                        slots.release()
+                    return
                 if not isinstance(group[0][1], np.ndarray):
                     # "dev" pages (already in HBM): one concatenation on the card, nothing to upload
                     import torch
@@ -281,6 +330,15 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
         the card idle for that long, and the two workers fell into step.  Readers without the upload entry (test doubles) pass through."""
         if item[0] == "dev":
             return item
+        if item[0] == "jpg":
+            _, ids, pages = item
+            try:
+                # ONE decode call for the group, on the context's JPEG stream outside the call slots: it runs while both device workers
+                # are inside their calls, like an upload
+                batch, status = reader.decode_jpeg_batch(pages, padded=True)
+                return "jpgdev", ids, pages, batch, status
+            except Exception:
+                return "jpgdev", ids, pages, None, [-1] * len(ids)       # the device worker decodes every page on the host
         ids, rgb, gray = item
         to_dev = getattr(reader, "_to_dev", None)
         if to_dev is None:
@@ -290,7 +348,38 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
         except Exception:
             return item                                  # the device worker retries from the host pages and reports per page
 
+    def ocr_host_page(i, page):
+        """the existing host path for one page of a "jpg" group"""
+        try:
+            kind, rgb, gray = _host_input(page)
+            if kind == "ycc":
+                texts[i] = reader.readtext_ycc_arrays([rgb], **readtext_kw)[0]
+            else:
+                texts[i] = reader.readtext_arrays([rgb], [gray], **readtext_kw)[0]
+        except Exception:
+            texts[i] = []
+
     def ocr(item):
+        if item[0] == "jpgdev":
+            _, ids, pages, batch, status = item
+            good = [k for k in range(len(ids)) if status[k] == 0]
+            if good:
+                try:
+                    if len(good) < len(ids):
+                        batch = batch[good]
+                    if batch.ndim == 4:
+                        rgb_dev, gray_dev = reader.pages_from_ycc(batch)
+                    else:                                # 1-component files: the samples, replicated for RGB
+                        rgb_dev, gray_dev = batch[..., None].expand(-1, -1, -1, 3).contiguous(), batch
+                    res = reader.readtext_device(rgb_dev, gray_dev, **readtext_kw)
+                    for k, r in zip(good, res):
+                        texts[ids[k]] = r
+                except Exception:
+                    good = []
+            for k in range(len(ids)):
+                if k not in good:
+                    ocr_host_page(ids[k], pages[k])
+            return
         if item[0] == "dev":                             # device pages: the page-by-page retry reads slices of the same tensors
             _, ids, rgb_dev, gray_dev = item
             try:

@@ -146,6 +146,40 @@ def decode_file_ycc(source, padded=False):
         return None
 
 
+class JpegPage:
+    """A baseline JPEG file the device decoder takes (``jpeg_plan``): its bytes and the shape of its decode, ``(H, W, components)``.  The
+    page kind ``"jpg"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one ``bbocr_jpeg_decode`` call."""
+    __slots__ = ("data", "shape")
+
+    def __init__(self, data, plan):
+        self.data = data
+        self.shape = (int(plan.height), int(plan.width), int(plan.components))
+
+
+def jpeg_plan(data):
+    """``bbocr_host_jpeg_plan`` of a file's bytes (no GPU): geometry, sampling, restart interval, scan range, ``supported`` and the
+    ``BBOCR_JPEG_*`` reason a file outside the device decoder's scope is refused with."""
+    plan = _lib.bbocr_jpeg_plan()
+    rc = _lib.load().bbocr_host_jpeg_plan(data, len(data), C.byref(plan))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_jpeg_plan failed with status {rc}")
+    return plan
+
+
+def jpeg_page(source):
+    """``JpegPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)."""
+    try:
+        if isinstance(source, (bytes, bytearray)):
+            data = bytes(source)
+        else:
+            with open(os.path.expanduser(os.fspath(source)), "rb") as f:
+                data = f.read()
+        plan = jpeg_plan(data)
+        return JpegPage(data, plan) if plan.supported else None
+    except Exception:
+        return None
+
+
 def reformat_input(image, device_gray=False, parallel_decode=False):
     """easyocr/utils.py::reformat_input -> (RGB uint8 HWC, gray uint8 HW); decode is host work (PIL).
 
@@ -302,7 +336,7 @@ class Reader:
     def __init__(self, lang_list, gpu=True, model_storage_directory=None, user_network_directory=None,
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
-                 rec_max_cols=0, precision=None, call_slots=0, host_threads=None, **_ignored):
+                 rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, **_ignored):
         import torch
 
         if list(lang_list) != ["en"]:
@@ -326,6 +360,9 @@ class Reader:
         if host_threads is None:
             host_threads = auto_host_threads()
         self.host_threads = int(host_threads)
+        if device_decode is None:   # baseline JPEG files decoded on the card (csrc/jpegdec.hip) by readtext(path); off unless asked for
+            device_decode = os.environ.get("BBOCR_DEVICE_DECODE", "0").strip() == "1"
+        self.device_decode = bool(device_decode)
         cfg = _lib.bbocr_config(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
                                 precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads)
         h = C.c_void_p()
@@ -537,6 +574,49 @@ class Reader:
                                                   C.c_void_p(gray.data_ptr())))
         return rgb, gray
 
+    def decode_jpeg_batch(self, pages, padded=False):
+        """``JpegPage`` s of ONE shape -> ``(batch, status)``: the device tensor ``uint8 [n,H,W,3]`` (``padded``: ``[n,H,W,4]``) of libjpeg's
+        YCbCr triples -- what ``pages_from_ycc`` takes -- or ``[n,H,W]`` for 1-component files, decoded by ONE ``bbocr_jpeg_decode`` call
+        (only the files' bytes cross the link), and the per-file status list (0, or negative: that page of the batch is undefined)."""
+        torch = self._torch
+        pages = list(pages)
+        if not pages or any(p.shape != pages[0].shape for p in pages):
+            raise ValueError("decode_jpeg_batch: pages of one decoded shape")
+        H, W, comps = pages[0].shape
+        px = 1 if comps == 1 else (4 if padded else 3)
+        t = torch.empty((len(pages), H, W) + ((px,) if comps == 3 else ()), dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream(self.device_index).synchronize()
+        n = len(pages)
+        files = (C.c_void_p * n)(*[C.cast(C.c_char_p(p.data), C.c_void_p) for p in pages])
+        sizes = (C.c_size_t * n)(*[len(p.data) for p in pages])
+        outs = (C.c_void_p * n)(*[t.data_ptr() + k * H * W * px for k in range(n)])
+        pitches = (C.c_longlong * n)(*([W * px] * n))
+        status = (C.c_int * n)()
+        layout = 3 if padded else 4                               # BBOCR_PAGE_YCBCR4 / BBOCR_PAGE_YCBCR3
+        self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
+        return t, list(status)
+
+    def decode_jpeg_device(self, sources):
+        """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them (libjpeg's RGB and its Y
+        plane; a grey file: the samples, replicated for RGB), decoded on the card, or ``None`` for a file the plan refuses or whose
+        entropy-coded data is damaged.  Files of one decoded shape share one decode call."""
+        pages = [jpeg_page(s) for s in sources]
+        out = [None] * len(pages)
+        groups = {}
+        for i, p in enumerate(pages):
+            if p is not None:
+                groups.setdefault(p.shape, []).append(i)
+        for shape, idxs in groups.items():
+            t, status = self.decode_jpeg_batch([pages[i] for i in idxs])
+            if shape[2] == 3:
+                rgb, gray = self.pages_from_ycc(t)
+            else:
+                rgb, gray = t[..., None].expand(-1, -1, -1, 3).contiguous(), t
+            for k, i in enumerate(idxs):
+                if status[k] == 0:
+                    out[i] = (rgb[k], gray[k])
+        return out
+
     def readtext_ycc_arrays(self, ycc, **kw):
         """Host array ``uint8 [B,H,W,3]`` of once-decoded JPEG pages (``decode_file_ycc``) -> per-page results, identical to
         ``readtext_arrays(rgb, gray)`` of the same files decoded twice."""
@@ -578,12 +658,21 @@ class Reader:
         self._unsupported(decoder, allowlist, blocklist, rotation_info, paragraph, output_format)
         # one page per call is latency-bound: RGB and the Y plane decoded side by side on two threads (4.9 ms) beat the single YCbCr decode
         # (decode_file_ycc, ~5.6 ms on one core) that the throughput-bound callers (extractor_batch) take
-        img, grey = reformat_input(image, device_gray=True, parallel_decode=True)
+        dev = None
+        if self.device_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
+            dev = self.decode_jpeg_device([image])[0]          # None: refused or damaged -> the host decode below, unchanged
+        if dev is None:
+            img, grey = reformat_input(image, device_gray=True, parallel_decode=True)
         kw = dict(min_size=min_size, contrast_ths=contrast_ths, adjust_contrast=adjust_contrast, text_threshold=text_threshold,
                   low_text=low_text, link_threshold=link_threshold, canvas_size=canvas_size, mag_ratio=mag_ratio, slope_ths=slope_ths,
                   ycenter_ths=ycenter_ths, height_ths=height_ths, width_ths=width_ths, add_margin=add_margin, detail=detail,
                   allowlist=allowlist, blocklist=blocklist, paragraph=paragraph, x_ths=x_ths, y_ths=y_ths, decoder=decoder,
                   beamWidth=beamWidth, rotation_info=rotation_info)
+        if dev is not None:
+            # a file given as bytes keeps upstream's rule for arrays (the gray plane derived from the colour image), as with the option off
+            gray_dev = None if isinstance(image, (bytes, bytearray)) else dev[1][None]
+            result = self.readtext_device(dev[0][None], gray_dev, **kw)[0]
+            return format_output(result, output_format, paragraph, detail)
         result = self.readtext_device(self._to_dev(img[None]), self._to_dev(grey[None]) if grey is not None else None, **kw)[0]
         return format_output(result, output_format, paragraph, detail)
 
@@ -621,6 +710,7 @@ class Reader:
         from .extractor_batch import read_files
 
         paths = list(paths)
+        kw.setdefault("device_decode", self.device_decode)
         res = read_files(self, paths, None, max_batch, decode_workers, **kw)
         return [res[i] for i in range(len(paths))]
 

@@ -33,7 +33,8 @@ enum bbocr_status {
     BBOCR_ERR_WEIGHTS = -3,  /* missing or mis-shaped tensor in a state-dict */
     BBOCR_ERR_STATE = -4,    /* weights not loaded, context destroyed, ... */
     BBOCR_ERR_OVERFLOW = -5, /* a device work buffer was too small (reported, never silent) */
-    BBOCR_ERR_INTERNAL = -6
+    BBOCR_ERR_INTERNAL = -6,
+    BBOCR_ERR_DATA = -7      /* per-file status of bbocr_jpeg_decode: the entropy-coded data is not what the headers promise */
 };
 
 /* Streams: every context owns non-blocking HIP streams.  On entry each call waits for the legacy default stream (where torch
@@ -341,6 +342,58 @@ int bbocr_host_thumbnail_plan(int H, int W, int max_dim, int* out_h, int* out_w,
 int bbocr_host_resample_coeffs(int in_size, float in0, float in1, int out_size, int* bounds, int* coeffs, int max_ksize, int* ksize);
 /* host only: jpeg_set_quality(quality, TRUE)'s luminance (0..63) and chrominance (64..127) tables, natural order */
 int bbocr_host_jpeg_qtables(int quality, uint16_t* out);
+
+
+/* ---- baseline JPEG files decoded on the device (csrc/jpegdec.hip), to the bit of libjpeg-turbo / Pillow: only the file's bytes cross the
+ * link.  Taken: SOF0, 8 bit, Huffman, ONE interleaved scan, 3 components YCbCr 4:2:0 (JFIF, or Adobe transform 1: decode_file_ycc's
+ * rule) or 1 component, any DQT / DHT / DRI, any size.  Everything else is refused by the plan, and the caller keeps its host path.
+ * EXIF orientation is ignored, as the host path ignores it. */
+enum {
+    BBOCR_JPEG_OK = 0,
+    BBOCR_JPEG_NOT_JPEG = 1,    /* no SOI: another container */
+    BBOCR_JPEG_TRUNCATED = 2,   /* the headers end before SOS (a marker segment cut short, EOI before any scan) */
+    BBOCR_JPEG_NO_EOI = 3,      /* the entropy-coded data runs to the end of the file */
+    BBOCR_JPEG_SOF = 4,         /* extended, progressive, lossless or arithmetic-coded frame; no or a second frame header */
+    BBOCR_JPEG_PRECISION = 5,   /* 12-bit samples, 16-bit quantisation table */
+    BBOCR_JPEG_COMPONENTS = 6,  /* CMYK / YCCK / two components */
+    BBOCR_JPEG_SAMPLING = 7,    /* 4:4:4, 4:2:2, 4:4:0, ... */
+    BBOCR_JPEG_COLORSPACE = 8,  /* three components without JFIF or Adobe transform 1: may be RGB-coded */
+    BBOCR_JPEG_MULTISCAN = 9,   /* a scan that does not hold every component, or more after the first */
+    BBOCR_JPEG_TABLES = 10,     /* a table the scan names is missing or malformed */
+    BBOCR_JPEG_RESTART = 11     /* restart markers out of sequence, or not one per interval */
+};
+typedef struct bbocr_jpeg_plan {
+    int width, height, components;
+    int sampling[3][2];         /* (h, v) per component */
+    int restart_interval;       /* MCUs, 0 = none */
+    int mcu_cols, mcu_rows;
+    int segments;               /* restart segments = entry points known without decoding */
+    long long scan_offset;      /* first entropy-coded byte */
+    long long scan_bytes;       /* up to the marker that ends the scan (stuffing and restart markers included) */
+    int supported;              /* 1: bbocr_jpeg_decode takes the file */
+    int reason;                 /* BBOCR_JPEG_* */
+    int reserved[4];
+} bbocr_jpeg_plan;
+/* host only, no GPU: one linear pass over the file (markers, then the scan's FF bytes); no entropy bit is decoded.  Fields a refused
+ * file's headers did not reach stay 0. */
+int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* plan);
+/* n files (HOST bytes) -> pixels in DEVICE memory, one call per batch: dev_out[k] receives file k's libjpeg YCbCr triples (out_color_space
+ * JCS_YCbCr, what decode_file_ycc holds), rows pitches[k] bytes apart, 3 (layout BBOCR_PAGE_YCBCR3) or 4 (BBOCR_PAGE_YCBCR4, fourth byte
+ * 255) bytes per pixel -- bbocr_op_ycc_to_rgb's two inputs -- or, for a 1-component file, the samples themselves, one byte per pixel.
+ * status[k]: 0, BBOCR_ERR_ARG (null pointer, pitch shorter than a row, a file the plan refuses) or BBOCR_ERR_DATA (the entropy-coded
+ * data decodes to another block count than the headers promise, or holds a bit pattern without a code: dev_out[k] is then undefined);
+ * the other files of the batch are decoded all the same and the context stays usable.  Runs on a stream of its own outside the call
+ * slots, one batch at a time per context (bbocr_upload_pages' contract): a batch decodes while two pipeline calls are in flight.  Work
+ * buffers belong to the context and grow on demand.  Returns with its work finished, also when it fails. */
+int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, uint8_t* const* dev_out,
+                      const long long* pitches, int* status);
+/* its intermediates of ONE file (parity tests), cut into subsequences of subseq_bits bits (0 = the decoder's 1024; a multiple of 8 in
+ * 32 .. 65536): stage 0 = the exact entry state of every subsequence, int32 [subsequences][4] = (bit in the unstuffed scan, block in the
+ * MCU, zig-zag position, first output block); 1 = quantised coefficients int16 [blocks][64] in natural order, blocks in MCU order, DC
+ * terms summed; 2 = the component planes before upsampling, Y [mcu_rows * 16][mcu_cols * 16] then Cb, Cr at half that (1 component:
+ * [mcu_rows * 8][mcu_cols * 8]); 3 = the pixels, tight.  *file_status as status[k] above. */
+int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
+                        int* file_status);
 
 #ifdef __cplusplus
 }
