@@ -13,8 +13,13 @@ restated exactly, including its JPEG round trip (the reference writes the thumbn
 """
 from __future__ import annotations
 
+import collections
+import dataclasses
 import io
 import os
+import queue
+import threading
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -27,37 +32,47 @@ def _jpg_page(source):
     return None if page is None else ("jpg", page, None)
 
 
+def _host_page(source, decode_once=True):
+    """The host decode of a file (a path or its bytes) as a page: ``("ycc", triples, None)`` when it is a YCbCr-coded JPEG and
+    ``decode_once`` (decoded once, RGB + Y plane derived on the card: reader.decode_file_ycc), else ``("rgb", rgb, gray)``."""
+    from .reader import decode_file, decode_file_ycc
+
+    if not isinstance(source, (bytes, bytearray)):
+        source = os.fspath(source)
+    ycc = decode_file_ycc(source, padded=True) if decode_once else None
+    return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(source))
+
+
+def _thumbnail_jpeg(size, image_index, load_rgb):
+    """The host's down-scaling step (:486-512) for a page of ``size`` (either order): above the page's limit (``ocr_thumbnail_rule``) the
+    RGB image ``load_rgb()`` returns is ``Image.thumbnail``-ed and written as JPEG -> the file's bytes; None (nothing loaded) otherwise."""
+    from .preprocess import ocr_thumbnail_rule
+
+    max_dim, quality = ocr_thumbnail_rule(image_index)
+    if max(size) <= max_dim:
+        return None
+    img = load_rgb()
+    img.thumbnail((max_dim, max_dim))
+    buf = io.BytesIO()
+    img.save(buf, format="JPEG", quality=quality)
+    return buf.getvalue()
+
+
 def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False):
     """``ocr_input_image`` for the batching loop: ``("ycc", triples, None)`` when the file easyocr would be given is a YCbCr-coded JPEG
-    (decoded once, RGB + Y plane derived on the card: reader.decode_file_ycc) -- every thumbnail is, it is written as one -- else
-    ``("rgb", rgb, gray)``.  ``device_decode``: the file easyocr would be given travels as its bytes (``("jpg", JpegPage, None)``) when the
-    device decoder takes it -- the original at or below the limit (only its header is read here), or the thumbnail as written."""
+    (``_host_page``) -- every thumbnail is, it is written as one -- else ``("rgb", rgb, gray)``.  ``device_decode``: the file easyocr
+    would be given travels as its bytes (``("jpg", JpegPage, None)``) when the device decoder takes it -- the original at or below the
+    limit (only its header is read here), or the thumbnail as written."""
     from PIL import Image
 
-    from .reader import decode_file, decode_file_ycc, reformat_input
-
-    cover = image_index is None or image_index == 0
-    max_dim = 1600 if cover else 2400
+    source = image_path
     try:
         img = Image.open(image_path)
-        if max(img.size) > max_dim:
-            img = img.convert("RGB")
-            img.thumbnail((max_dim, max_dim))
-            buf = io.BytesIO()
-            img.save(buf, format="JPEG", quality=(90 if cover else 95))
-            data = buf.getvalue()
-            page = _jpg_page(data) if device_decode else None
-            if page is not None:
-                return page
-            ycc = decode_file_ycc(data, padded=True) if decode_once else None
-            return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(data))
+        source = _thumbnail_jpeg(img.size, image_index, lambda: img.convert("RGB")) or image_path
     except Exception:
         pass                                                      # :511-514: any failure falls back to the original file
-    page = _jpg_page(image_path) if device_decode else None
-    if page is not None:
-        return page
-    ycc = decode_file_ycc(os.fspath(image_path), padded=True) if decode_once else None
-    return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(reformat_input(os.fspath(image_path)))
+    page = _jpg_page(source) if device_decode else None
+    return page if page is not None else _host_page(source, decode_once)
 
 
 def _ocr_input_array(page, image_index=None, decode_once=True):
@@ -65,19 +80,12 @@ def _ocr_input_array(page, image_index=None, decode_once=True):
     [H,W,3] uint8.  Gray pages are read back as three equal channels, so the RGB thumbnail is the gray one replicated."""
     from PIL import Image
 
-    from .reader import decode_file, decode_file_ycc
+    from .reader import decode_file
 
-    cover = image_index is None or image_index == 0
-    max_dim = 1600 if cover else 2400
     rgb = np.ascontiguousarray(np.repeat(page[:, :, None], 3, axis=2) if page.ndim == 2 else page[:, :, ::-1])
-    if max(page.shape[0], page.shape[1]) > max_dim:
-        img = Image.fromarray(rgb)
-        img.thumbnail((max_dim, max_dim))
-        buf = io.BytesIO()
-        img.save(buf, format="JPEG", quality=(90 if cover else 95))
-        data = buf.getvalue()
-        ycc = decode_file_ycc(data, padded=True) if decode_once else None
-        return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(data))
+    data = _thumbnail_jpeg(page.shape[:2], image_index, lambda: Image.fromarray(rgb))
+    if data is not None:
+        return _host_page(data, decode_once)
     if page.ndim == 2:
         return ("rgb", rgb, np.ascontiguousarray(page))
     buf = io.BytesIO()                                            # a colour page: through the PNG file the reference writes
@@ -141,16 +149,11 @@ def ocr_input_image(image_path, image_index=None):
 
     from .reader import decode_file, reformat_input
 
-    cover = image_index is None or image_index == 0
-    max_dim = 1600 if cover else 2400
     try:
         img = Image.open(image_path)
-        if max(img.size) > max_dim:
-            img = img.convert("RGB")
-            img.thumbnail((max_dim, max_dim))
-            buf = io.BytesIO()
-            img.save(buf, format="JPEG", quality=(90 if cover else 95))
-            return decode_file(buf.getvalue())                    # what easyocr's loader sees: a JPEG file on disk
+        data = _thumbnail_jpeg(img.size, image_index, lambda: img.convert("RGB"))
+        if data is not None:
+            return decode_file(data)                              # what easyocr's loader sees: a JPEG file on disk
     except Exception:
         pass                                                      # :511-514: any failure falls back to the original file
     return reformat_input(os.fspath(image_path))
@@ -189,10 +192,7 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
 
 def _plain_input(path, i=None):
     """Decode step of ``read_files`` without the extractor's thumbnail rule: what ``Reader.readtext(path)`` would hold."""
-    from .reader import decode_file_ycc, reformat_input
-
-    ycc = decode_file_ycc(os.fspath(path), padded=True)
-    return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(reformat_input(os.fspath(path)))
+    return _host_page(path)
 
 
 def _plain_input_device(path, i=None):
@@ -200,12 +200,203 @@ def _plain_input_device(path, i=None):
     return _jpg_page(path) or _plain_input(path, i)
 
 
-def _host_input(page):
-    """The host decode of a ``JpegPage`` (the retry of a page whose device decode failed): what ``_plain_input`` returns for its file"""
-    from .reader import decode_file, decode_file_ycc
+@dataclasses.dataclass
+class Batch:
+    """What the stages of ``read_files`` hand on: the pages ``ids`` of one ``kind`` and one shape.  ``host`` / ``dev``: the kind's host and
+    device payload (``KINDS``), None where there is none (yet, or after a failed upload); ``status``: per page, non-zero where the device
+    payload does not hold it -- such a page is read on its own (``read_page``); None: it holds every page."""
+    kind: str
+    ids: list
+    host: object = None
+    dev: object = None
+    status: list = None
 
-    ycc = decode_file_ycc(page.data, padded=True)
-    return ("ycc", ycc, None) if ycc is not None else ("rgb",) + tuple(decode_file(page.data))
+
+def _dev_stack(ids, pages):
+    import torch
+
+    rgb, gray = torch.stack([a for a, _ in pages]), torch.stack([g for _, g in pages])
+    torch.cuda.current_stream(rgb.device).synchronize()       # the library runs on its own stream
+    return Batch("dev", ids, dev=(rgb, gray))
+
+
+def _jpg_to_device(reader, b):
+    # ONE decode call for the group, on the context's JPEG stream outside the call slots: it runs while both device workers are inside
+    # their calls, like an upload.  (When it raises, the device worker decodes every page on the host.)
+    dev, b.status = reader.decode_jpeg_batch(b.host, padded=True)
+    return dev
+
+
+def _jpg_read(reader, b, kw):
+    from .reader import Reader
+
+    good = [k for k, s in enumerate(b.status) if s == 0]
+    pages = b.dev if len(good) == len(b.ids) else b.dev[good]
+    return reader.readtext_device(*Reader.pages_from_jpeg(reader, pages), **kw)     # (unbound: a test double need not have the method)
+
+
+def _jpg_read_page(reader, b, k, kw):
+    kind, a, g = _host_page(b.host[k].data)              # the host decode of the file: what _plain_input returns for it
+    return KINDS[kind].read_page(reader, KINDS[kind].stack(b.ids[k:k + 1], [(a, g)]), 0, kw)
+
+
+# The page kinds.  A decoded page is the pair (a, b) of the decode callback's ``(kind, a, b)``; its grouping key is ``_page_key``.  Per kind:
+#   stack(ids, pages) -> Batch           the assembler's step for a group
+#   to_device(reader, batch) -> dev      the upload stage's step: the device payload (it may raise: the batch then travels without one)
+#   read(reader, batch, kw)              ONE device call on the device payload, for the pages of status 0 -> their results
+#   read_host(reader, batch, kw)         the same from the host payload, where a kind has one that a call takes; else None
+#   read_page(reader, batch, k, kw)      page k alone, the retry unit -> its result
+Kind = collections.namedtuple("Kind", "stack to_device read read_host read_page")
+KINDS = {
+    # host pages travel as LISTS: the Reader uploads them one by one into the device batch (no 236-MB np.stack on this thread)
+    "rgb": Kind(stack=lambda ids, pages: Batch("rgb", ids, host=([a for a, _ in pages], [g for _, g in pages])),
+                to_device=lambda r, b: (r._to_dev(b.host[0]), r._to_dev(b.host[1])),
+                read=lambda r, b, kw: r.readtext_device(*b.dev, **kw),
+                read_host=lambda r, b, kw: r.readtext_arrays(*b.host, **kw),
+                read_page=lambda r, b, k, kw: r.readtext_arrays(b.host[0][k:k + 1], b.host[1][k:k + 1], **kw)[0]),
+    # once-decoded YCbCr pages: RGB and the Y plane are derived on the card
+    "ycc": Kind(stack=lambda ids, pages: Batch("ycc", ids, host=[a for a, _ in pages]),
+                to_device=lambda r, b: r._to_dev(b.host),
+                read=lambda r, b, kw: r.readtext_device(*r.pages_from_ycc(b.dev), **kw),
+                read_host=lambda r, b, kw: r.readtext_ycc_arrays(b.host, **kw),
+                read_page=lambda r, b, k, kw: r.readtext_ycc_arrays(b.host[k:k + 1], **kw)[0]),
+    # pages already in HBM: one concatenation on the card, nothing to upload; the page-by-page retry reads slices of the same tensors
+    "dev": Kind(stack=_dev_stack, to_device=lambda r, b: b.dev, read=lambda r, b, kw: r.readtext_device(*b.dev, **kw), read_host=None,
+                read_page=lambda r, b, k, kw: r.readtext_device(b.dev[0][k:k + 1], b.dev[1][k:k + 1], **kw)[0]),
+    # file bytes (JpegPage): decoded by the upload stage; a page it could not decode takes the host decode
+    "jpg": Kind(stack=lambda ids, pages: Batch("jpg", ids, host=[p for p, _ in pages]), to_device=_jpg_to_device, read=_jpg_read,
+                read_host=None, read_page=_jpg_read_page),
+}
+
+
+def _page_key(kind, a):
+    """Grouping key of a decoded page: every kind's first element carries the page's shape (a ``JpegPage``: that of its decode)"""
+    return kind, tuple(a.shape)
+
+
+def _read_batch(reader, batch, kw):
+    """``{index: result}`` of a batch: one call for its pages of status 0, on the device payload, then (where the kind can) on the host
+    payload; when that fails, and for a page of another status, page by page -- the reference loses ONE page when its OCR fails
+    (enhanced_extractor.py:529-531), and that page maps to ``[]``."""
+    kind = KINDS[batch.kind]
+    status = batch.status or [0] * len(batch.ids)
+    good = [k for k, s in enumerate(status) if s == 0]
+    res = {}
+    attempts = [kind.read] if batch.dev is not None and good else []
+    if kind.read_host is not None:
+        attempts.append(kind.read_host)
+    for read in attempts:
+        try:
+            res = dict(zip(good, read(reader, batch, kw)))
+            break
+        except Exception:
+            pass
+    for k in range(len(batch.ids)):
+        if k not in res:
+            try:
+                res[k] = kind.read_page(reader, batch, k, kw)
+            except Exception:
+                res[k] = []
+    return {batch.ids[k]: r for k, r in res.items()}
+
+
+def _default_decode_workers(reader, n_files):
+    """half of the process's CPU share (affinity mask and cgroup quota, bbocr_host_cpu_share), at most 8: the library's own host pool, the
+    upload stage and the two device-call threads need the rest (16-CPU share: 4 threads 700-780 pages/s, 8: 720-790, 16: 755-825)"""
+    try:
+        share = int(reader._lib.bbocr_host_cpu_share())
+    except Exception:
+        share = os.cpu_count() or 1
+    return max(1, min(8, share // 2, n_files))
+
+
+def _assemble(decode_one, idxs, max_batch, decode_workers, batches):
+    """Assembler thread: decode pool -> groups of one kind and shape -> ``batches`` (a full group travels as one ``Batch``; None ends it).
+    Back-pressure end to end: at most `window` decoded pages exist outside the two assembled batches the queue may hold (a decode is only
+    submitted once a slot is free, and a slot is released when its page has been copied into a batch), so the resident set is bounded by
+    ~4 batches however many files are queued."""
+    window = max(2 * max_batch, 2 * decode_workers)
+    slots = threading.Semaphore(window)
+    groups = {}
+
+    def flush(key):
+        group = groups.pop(key)
+        batches.put(KINDS[key[0]].stack([i for i, _ in group], [page for _, page in group]))
+        for _ in group:
+            slots.release()
+
+    try:
+        with ThreadPoolExecutor(max_workers=decode_workers) as pool:
+            pending = collections.deque()
+            it = iter(idxs)
+            done_submitting = False
+            while pending or not done_submitting:
+                while not done_submitting and len(pending) < window and slots.acquire(blocking=not pending):
+                    i = next(it, None)
+                    if i is None:
+                        slots.release()
+                        done_submitting = True
+                        break
+                    pending.append((i, pool.submit(decode_one, i)))
+                if not pending:
+                    continue
+                i, fut = pending.popleft()
+                page = fut.result()
+                del fut                                         # the future would keep the decoded arrays alive
+                if page is None or page[0] not in KINDS:
+                    slots.release()
+                    continue
+                kind, a, b = page                               # the decode callback's tuple ends here
+                key = _page_key(kind, a)
+                groups.setdefault(key, []).append((i, (a, b)))
+                if len(groups[key]) >= max_batch:
+                    flush(key)
+                elif not pending and not done_submitting:
+                    # nothing is being decoded: the next submission needs a slot.  If every slot is held by pages waiting in partial
+                    # groups (many distinct shapes), send the largest group -- only then: while decodes are pending their pages hold
+                    # slots too, and flushing on that account cut full batches into single pages (round 3: the faster the decode
+                    # pool, the smaller the device batches)
+                    if slots.acquire(blocking=False):
+                        slots.release()
+                    else:
+                        flush(max(groups, key=lambda k: len(groups[k])))
+            for key in list(groups):
+                flush(key)
+    finally:
+        batches.put(None)
+
+
+def _upload(reader, batch):
+    """Stage between the assembler and the device calls: the batch's pages reach the card (one GIL-free C call on the context's upload
+    stream, outside the call slots) while both device workers are still inside their calls -- a worker that uploaded its own batch left
+    the card idle for that long, and the two workers fell into step.  Readers without the upload entry (test doubles) and a failed upload
+    leave the batch without a device payload: the device worker reads it from the host pages and reports per page."""
+    try:
+        batch.dev = KINDS[batch.kind].to_device(reader, batch)
+    except Exception:
+        pass
+    return batch
+
+
+def _device_stage(reader, batches, texts, kw):
+    """This thread is the upload stage, one batch ahead of the device workers; two device batches in flight on the one Reader
+    (bbocr_config::call_slots, the reference's own ThreadPoolExecutor contract, batch_processor_enhanced.py:215): the H2D copy and
+    detector of batch k+1 run while batch k's host thread finishes its boxes and strings."""
+    in_flight = threading.Semaphore(2)
+    with ThreadPoolExecutor(max_workers=2, thread_name_prefix="bbocr-ocr") as device_pool:
+        futs = []
+        while True:
+            batch = batches.get()
+            if batch is None:
+                break
+            batch = _upload(reader, batch)
+            in_flight.acquire()
+            fut = device_pool.submit(lambda b: texts.update(_read_batch(reader, b, kw)), batch)
+            fut.add_done_callback(lambda _f: in_flight.release())
+            futs.append(fut)
+            del batch
+        for fut in futs:
+            fut.result()
 
 
 def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, **readtext_kw):
@@ -217,14 +408,11 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     (reader.decode_file_ycc: both planes are then derived on the card).  The files are therefore decoded by ``decode_workers`` threads (default:
     the host's cores, at most 16; PIL releases the GIL while decoding) and a shape group is sent to the device as soon as it is
     full, so the decode of later pages overlaps the device batch of earlier ones (ctypes releases the GIL during the C call).
-    ``decode(path, index)`` returns ``("ycc", triples, None)`` or ``("rgb", rgb, gray)``.  ``device_decode=True`` (or a ``decode`` that
-    returns ``("jpg", JpegPage, None)``): baseline JPEG files are only read and planned here and travel as their bytes, grouped by decoded
-    shape; the upload stage decodes a group on the card with one call, straight into the batch tensor."""
-    import collections
-    import queue
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
-
+    ``decode(path, index)`` returns ``("ycc", triples, None)``, ``("rgb", rgb, gray)``, ``("dev", rgb_dev, gray_dev)`` or
+    ``("jpg", JpegPage, None)``.  ``device_decode=True`` (or a ``decode`` that returns ``"jpg"`` pages): baseline JPEG files are only read
+    and planned here and travel as their bytes, grouped by decoded shape; the upload stage decodes a group on the card with one call,
+    straight into the batch tensor.  Three overlapped stages: decode pool -> assembler thread (``_assemble``) -> this thread
+    (``_device_stage``: upload, two device calls in flight, result strings); what they hand on is a ``Batch`` of one of the ``KINDS``."""
     if decode is None:
         decode = _plain_input_device if device_decode else _plain_input
     if indices is None:
@@ -234,21 +422,7 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     if not idxs:
         return texts
     if decode_workers is None:
-        # half of the process's CPU share (affinity mask and cgroup quota, bbocr_host_cpu_share), at most 8: the library's own host pool, the
-        # upload stage and the two device-call threads need the rest (16-CPU share: 4 threads 700-780 pages/s, 8: 720-790, 16: 755-825)
-        try:
-            share = int(reader._lib.bbocr_host_cpu_share())
-        except Exception:
-            share = os.cpu_count() or 1
-        decode_workers = max(1, min(8, share // 2, len(idxs)))
-
-    # three overlapped stages: decode pool -> assembler thread (groups pages by shape, hands a full group on as one batch)
-    # -> this thread (device call + result strings).  Back-pressure end to end: at most `window` decoded pages exist outside the two
-    # assembled batches the queue may hold (a decode is only submitted once a slot is free, and a slot is released when its page has
-    # been copied into a batch), so the resident set is bounded by ~4 batches however many files are queued.
-    batches = queue.Queue(maxsize=2)
-    window = max(2 * max_batch, 2 * decode_workers)
-    slots = threading.Semaphore(window)
+        decode_workers = _default_decode_workers(reader, len(idxs))
 
     def decode_one(i):
         try:
@@ -256,191 +430,9 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
         except Exception:
             return None
 
-    def assemble():
-        try:
-            by_shape = {}
-
-            def flush(group):
-                if hasattr(group[0][1], "data") and isinstance(group[0][1].data, bytes):
-                    batches.put(("jpg", [p[0] for p in group], [p[1] for p in group]))     # file bytes: decoded by the upload stage
-                    for _ in group:
-                        slots.release()
-                    return
-                if not isinstance(group[0][1], np.ndarray):
-                    # "dev" pages (already in HBM): one concatenation on the card, nothing to upload
-                    import torch
-
-                    rgb, gray = torch.stack([p[1] for p in group]), torch.stack([p[2] for p in group])
-                    torch.cuda.current_stream(rgb.device).synchronize()                       # the library runs on its own stream
-                    batches.put(("dev", [p[0] for p in group], rgb, gray))
-                    for _ in group:
-                        slots.release()
-                    return
-                # pages travel as LISTS: the Reader uploads them one by one into the device batch (no 236-MB np.stack on this thread)
-                gray = None if group[0][2] is None else [p[2] for p in group]                 # None: a group of once-decoded YCbCr pages
-                batches.put(([p[0] for p in group], [p[1] for p in group], gray))
-                for _ in group:
-                    slots.release()
-
-            with ThreadPoolExecutor(max_workers=decode_workers) as pool:
-                pending = collections.deque()
-                it = iter(idxs)
-                done_submitting = False
-                while pending or not done_submitting:
-                    while not done_submitting and len(pending) < window and slots.acquire(blocking=not pending):
-                        i = next(it, None)
-                        if i is None:
-                            slots.release()
-                            done_submitting = True
-                            break
-                        pending.append((i, pool.submit(decode_one, i)))
-                    if not pending:
-                        continue
-                    i, fut = pending.popleft()
-                    page = fut.result()
-                    del fut                                         # the future would keep the decoded arrays alive
-                    if page is None:
-                        slots.release()
-                        continue
-                    kind, rgb, gray = page                          # kind "ycc": rgb holds the YCbCr triples, gray is None
-                    key = (kind, tuple(rgb.shape))                  # kind "dev": device tensors (rgb, gray)
-                    group = by_shape.setdefault(key, [])
-                    group.append((i, rgb, gray))
-                    if len(group) >= max_batch:
-                        flush(by_shape.pop(key))
-                    elif not pending and not done_submitting:
-                        # nothing is being decoded: the next submission needs a slot.  If every slot is held by pages waiting in partial
-                        # groups (many distinct shapes), send the largest group -- only then: while decodes are pending their pages hold
-                        # slots too, and flushing on that account cut full batches into single pages (round 3: the faster the decode
-                        # pool, the smaller the device batches)
-                        if slots.acquire(blocking=False):
-                            slots.release()
-                        else:
-                            big = max(by_shape, key=lambda k: len(by_shape[k]))
-                            flush(by_shape.pop(big))
-                for group in by_shape.values():
-                    if group:
-                        flush(group)
-        finally:
-            batches.put(None)
-
-    def upload(item):
-        """Stage between the assembler and the device calls: the batch's pages reach the card (one GIL-free C call on the context's upload
-        stream, outside the call slots) while both device workers are still inside their calls -- a worker that uploaded its own batch left
-        the card idle for that long, and the two workers fell into step.  Readers without the upload entry (test doubles) pass through."""
-        if item[0] == "dev":
-            return item
-        if item[0] == "jpg":
-            _, ids, pages = item
-            try:
-                # ONE decode call for the group, on the context's JPEG stream outside the call slots: it runs while both device workers
-                # are inside their calls, like an upload
-                batch, status = reader.decode_jpeg_batch(pages, padded=True)
-                return "jpgdev", ids, pages, batch, status
-            except Exception:
-                return "jpgdev", ids, pages, None, [-1] * len(ids)       # the device worker decodes every page on the host
-        ids, rgb, gray = item
-        to_dev = getattr(reader, "_to_dev", None)
-        if to_dev is None:
-            return item
-        try:
-            return ids, to_dev(rgb), (to_dev(gray) if gray is not None else None), rgb, gray
-        except Exception:
-            return item                                  # the device worker retries from the host pages and reports per page
-
-    def ocr_host_page(i, page):
-        """the existing host path for one page of a "jpg" group"""
-        try:
-            kind, rgb, gray = _host_input(page)
-            if kind == "ycc":
-                texts[i] = reader.readtext_ycc_arrays([rgb], **readtext_kw)[0]
-            else:
-                texts[i] = reader.readtext_arrays([rgb], [gray], **readtext_kw)[0]
-        except Exception:
-            texts[i] = []
-
-    def ocr(item):
-        if item[0] == "jpgdev":
-            _, ids, pages, batch, status = item
-            good = [k for k in range(len(ids)) if status[k] == 0]
-            if good:
-                try:
-                    if len(good) < len(ids):
-                        batch = batch[good]
-                    if batch.ndim == 4:
-                        rgb_dev, gray_dev = reader.pages_from_ycc(batch)
-                    else:                                # 1-component files: the samples, replicated for RGB
-                        rgb_dev, gray_dev = batch[..., None].expand(-1, -1, -1, 3).contiguous(), batch
-                    res = reader.readtext_device(rgb_dev, gray_dev, **readtext_kw)
-                    for k, r in zip(good, res):
-                        texts[ids[k]] = r
-                except Exception:
-                    good = []
-            for k in range(len(ids)):
-                if k not in good:
-                    ocr_host_page(ids[k], pages[k])
-            return
-        if item[0] == "dev":                             # device pages: the page-by-page retry reads slices of the same tensors
-            _, ids, rgb_dev, gray_dev = item
-            try:
-                res = reader.readtext_device(rgb_dev, gray_dev, **readtext_kw)
-            except Exception:
-                res = []
-                for k in range(len(ids)):
-                    try:
-                        res.append(reader.readtext_device(rgb_dev[k:k + 1], gray_dev[k:k + 1], **readtext_kw)[0])
-                    except Exception:
-                        res.append([])
-            for i, r in zip(ids, res):
-                texts[i] = r
-            return
-        if len(item) == 5:                               # uploaded: device tensors + the host pages for the page-by-page retry
-            ids, rgb_dev, gray_dev, rgb, gray = item
-            try:
-                if gray is None:
-                    res = reader.readtext_device(*reader.pages_from_ycc(rgb_dev), **readtext_kw)
-                else:
-                    res = reader.readtext_device(rgb_dev, gray_dev, **readtext_kw)
-                for i, r in zip(ids, res):
-                    texts[i] = r
-                return
-            except Exception:
-                pass
-            del rgb_dev, gray_dev
-        else:
-            ids, rgb, gray = item
-        read = (lambda a, g: reader.readtext_ycc_arrays(a, **readtext_kw)) if gray is None else (lambda a, g: reader.readtext_arrays(a, g, **readtext_kw))
-        try:
-            res = read(rgb, gray)
-        except Exception:
-            # the reference loses ONE page when its OCR fails (enhanced_extractor.py:529-531): retry the batch page by page
-            res = []
-            for k in range(len(ids)):
-                try:
-                    res.append(read(rgb[k:k + 1], None if gray is None else gray[k:k + 1])[0])
-                except Exception:
-                    res.append([])
-        for i, r in zip(ids, res):
-            texts[i] = r
-
-    worker = threading.Thread(target=assemble, daemon=True)
+    batches = queue.Queue(maxsize=2)
+    worker = threading.Thread(target=_assemble, args=(decode_one, idxs, max_batch, decode_workers, batches), daemon=True)
     worker.start()
-    # two device batches in flight on the one Reader (bbocr_config::call_slots, the reference's own ThreadPoolExecutor contract,
-    # batch_processor_enhanced.py:215): the H2D copy and detector of batch k+1 run while batch k's host thread finishes its boxes and strings
-    in_flight = threading.Semaphore(2)
-    with ThreadPoolExecutor(max_workers=2, thread_name_prefix="bbocr-ocr") as device_pool:
-        futs = []
-        while True:
-            item = batches.get()
-            if item is None:
-                break
-            item = upload(item)                          # this thread is the upload stage: it runs one batch ahead of the device workers
-            in_flight.acquire()
-            fut = device_pool.submit(ocr, item)
-            fut.add_done_callback(lambda _f: in_flight.release())
-            futs.append(fut)
-            del item
-        for fut in futs:
-            fut.result()
+    _device_stage(reader, batches, texts, readtext_kw)
     worker.join()
     return texts

@@ -596,6 +596,13 @@ class Reader:
         self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
         return t, list(status)
 
+    def pages_from_jpeg(self, batch):
+        """The tensor of ``decode_jpeg_batch`` -> ``(rgb_dev, gray_dev)``: ``pages_from_ycc`` of the triples ``[n,H,W,3 or 4]``; for
+        1-component files ``[n,H,W]`` the samples, replicated for RGB."""
+        if batch.ndim == 4:
+            return self.pages_from_ycc(batch)
+        return batch[..., None].expand(-1, -1, -1, 3).contiguous(), batch
+
     def decode_jpeg_device(self, sources):
         """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them (libjpeg's RGB and its Y
         plane; a grey file: the samples, replicated for RGB), decoded on the card, or ``None`` for a file the plan refuses or whose
@@ -606,12 +613,9 @@ class Reader:
         for i, p in enumerate(pages):
             if p is not None:
                 groups.setdefault(p.shape, []).append(i)
-        for shape, idxs in groups.items():
+        for idxs in groups.values():
             t, status = self.decode_jpeg_batch([pages[i] for i in idxs])
-            if shape[2] == 3:
-                rgb, gray = self.pages_from_ycc(t)
-            else:
-                rgb, gray = t[..., None].expand(-1, -1, -1, 3).contiguous(), t
+            rgb, gray = self.pages_from_jpeg(t)
             for k, i in enumerate(idxs):
                 if status[k] == 0:
                     out[i] = (rgb[k], gray[k])
@@ -658,22 +662,21 @@ class Reader:
         self._unsupported(decoder, allowlist, blocklist, rotation_info, paragraph, output_format)
         # one page per call is latency-bound: RGB and the Y plane decoded side by side on two threads (4.9 ms) beat the single YCbCr decode
         # (decode_file_ycc, ~5.6 ms on one core) that the throughput-bound callers (extractor_batch) take
-        dev = None
+        rgb_dev = None
         if self.device_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
             dev = self.decode_jpeg_device([image])[0]          # None: refused or damaged -> the host decode below, unchanged
-        if dev is None:
+            if dev is not None:
+                # a file given as bytes keeps upstream's rule for arrays (the gray plane derived from the colour image), as with the option off
+                rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
+        if rgb_dev is None:
             img, grey = reformat_input(image, device_gray=True, parallel_decode=True)
+            rgb_dev, gray_dev = self._to_dev(img[None]), (self._to_dev(grey[None]) if grey is not None else None)
         kw = dict(min_size=min_size, contrast_ths=contrast_ths, adjust_contrast=adjust_contrast, text_threshold=text_threshold,
                   low_text=low_text, link_threshold=link_threshold, canvas_size=canvas_size, mag_ratio=mag_ratio, slope_ths=slope_ths,
                   ycenter_ths=ycenter_ths, height_ths=height_ths, width_ths=width_ths, add_margin=add_margin, detail=detail,
                   allowlist=allowlist, blocklist=blocklist, paragraph=paragraph, x_ths=x_ths, y_ths=y_ths, decoder=decoder,
                   beamWidth=beamWidth, rotation_info=rotation_info)
-        if dev is not None:
-            # a file given as bytes keeps upstream's rule for arrays (the gray plane derived from the colour image), as with the option off
-            gray_dev = None if isinstance(image, (bytes, bytearray)) else dev[1][None]
-            result = self.readtext_device(dev[0][None], gray_dev, **kw)[0]
-            return format_output(result, output_format, paragraph, detail)
-        result = self.readtext_device(self._to_dev(img[None]), self._to_dev(grey[None]) if grey is not None else None, **kw)[0]
+        result = self.readtext_device(rgb_dev, gray_dev, **kw)[0]
         return format_output(result, output_format, paragraph, detail)
 
     def readtext_batched(self, image, n_width=None, n_height=None, **kw):

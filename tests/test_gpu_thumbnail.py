@@ -194,6 +194,41 @@ def test_extract_texts_device_thumbnail_with_crops(reader, mixed_files):
     assert extractor_batch.extract_texts(reader, files, device_thumbnail=True, **kw) == extractor_batch.extract_texts(reader, files, **kw)
 
 
+def test_extract_texts_device_pages_are_retried_page_by_page(reader, tmp_path):
+    """A batch of pages that live on the card (kind "dev") whose device call fails is read again page by page, from slices of the same
+    tensors: the texts are those of the call that did not fail."""
+    from PIL import Image
+
+    from bb_ocr_amd import extractor_batch, synth
+
+    paths = []
+    for k in range(3):
+        paths.append(tmp_path / f"p{k}.png")
+        Image.fromarray(synth.page(60 + k, width=400, height=300, lines=5, margin=24)[0]).save(paths[-1])
+
+    class FailsOnce:
+        """the reader, except that its first device call holding more than one page raises"""
+
+        def __init__(self):
+            self.sizes = []
+
+        def __getattr__(self, name):
+            return getattr(reader, name)
+
+        def readtext_device(self, rgb_dev, gray_dev=None, **kw):
+            self.sizes.append(int(rgb_dev.shape[0]))
+            if rgb_dev.shape[0] > 1 and len(self.sizes) == 1:
+                raise RuntimeError("boom")
+            return reader.readtext_device(rgb_dev, gray_dev, **kw)
+
+    kw = dict(edge_crop_percent=5, device_thumbnail=True)
+    want = extractor_batch.extract_texts(reader, paths, **kw)
+    proxy = FailsOnce()
+    assert extractor_batch.extract_texts(proxy, paths, **kw) == want
+    assert proxy.sizes == [3, 1, 1, 1]
+    assert all(want[k] for k in range(3)) and len(set(want.values())) == 3        # (a retry that mixed the pages up would show)
+
+
 def test_errors(reader):
     from bb_ocr_amd.preprocess import ocr_input_device
 
