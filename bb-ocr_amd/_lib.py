@@ -43,7 +43,7 @@ class bbocr_preproc_params(C.Structure):
 class bbocr_jpeg_plan(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("sampling", (C.c_int * 2) * 3), ("restart_interval", C.c_int),
                 ("mcu_cols", C.c_int), ("mcu_rows", C.c_int), ("segments", C.c_int), ("scan_offset", C.c_longlong), ("scan_bytes", C.c_longlong),
-                ("supported", C.c_int), ("reason", C.c_int), ("reserved", C.c_int * 4)]
+                ("supported", C.c_int), ("reason", C.c_int), ("orientation", C.c_int), ("reserved", C.c_int * 3)]
 
 
 class bbocr_boxlist(C.Structure):
@@ -129,6 +129,10 @@ PROTOTYPES = {
     "bbocr_host_jpeg_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_jpeg_plan)]),
     "bbocr_jpeg_decode": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "bbocr_jpeg_imread": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                    C.POINTER(C.c_int)]),
+    "bbocr_page_orient": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int)]),
     "bbocr_op_jpeg_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
 }
 

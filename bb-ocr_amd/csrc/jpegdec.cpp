@@ -18,11 +18,53 @@ struct JpegParsed {
     std::vector<std::pair<size_t, size_t>> segs;   // byte ranges of the restart segments in the file (stuffing included)
 };
 
+// EXIF orientation as cv2.imread applies it: the first APP1 segment that starts with "Exif\0\0" before SOS, a TIFF header of either byte
+// order, IFD0 only, tag 0x0112 as one SHORT or LONG of value 1 .. 8.  Anything else -- no such segment or tag, another type or count,
+// another value, an IFD that does not lie inside the segment -- is 1.  Every read is checked against the segment.
+int exif_orientation(const uint8_t* f, size_t n) {
+    size_t p = 2;
+    while (p + 4 <= n && f[p] == 0xFF) {
+        const int m = f[p + 1];
+        if (m == 0xFF) { ++p; continue; }
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) { p += 2; continue; }
+        if (m == 0xDA || m == 0xD9) break;
+        const size_t L = ((size_t)f[p + 2] << 8) | f[p + 3];
+        if (L < 2 || p + 2 + L > n) break;
+        const uint8_t* s = f + p + 4;
+        const size_t sl = L - 2;
+        p += 2 + L;
+        if (m != 0xE1 || sl < 6 || std::memcmp(s, "Exif\0\0", 6) != 0) continue;
+        const uint8_t* t = s + 6;
+        const size_t tl = sl - 6;
+        if (tl < 8) return 1;
+        const bool le = t[0] == 'I' && t[1] == 'I';
+        if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+        auto u16 = [&](size_t o) { return le ? (unsigned)t[o] | ((unsigned)t[o + 1] << 8) : ((unsigned)t[o] << 8) | (unsigned)t[o + 1]; };
+        auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
+        if (u16(2) != 42) return 1;
+        const size_t ifd = u32(4);
+        if (ifd > tl || tl - ifd < 2) return 1;
+        const size_t cnt = u16(ifd);
+        if ((tl - ifd - 2) / 12 < cnt) return 1;                  // the directory runs off the segment
+        for (size_t i = 0; i < cnt; ++i) {
+            const size_t e = ifd + 2 + 12 * i;
+            if (u16(e) != 0x0112) continue;
+            const unsigned type = u16(e + 2);
+            if ((type != 3 && type != 4) || u32(e + 4) != 1) return 1;
+            const unsigned v = type == 3 ? u16(e + 8) : u32(e + 8);
+            return v >= 1 && v <= 8 ? (int)v : 1;
+        }
+        return 1;
+    }
+    return 1;
+}
+
 // jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.  Returns the reason.
 int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
     bbocr_jpeg_plan& pl = out.plan;
     pl = bbocr_jpeg_plan{};
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
+    pl.orientation = exif_orientation(f, n);                     // of its own walk: malformed EXIF never changes what follows
     size_t p = 2;
     unsigned short qt[4][64];
     bool have_qt[4] = {false, false, false, false};
@@ -402,6 +444,50 @@ int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
         std::vector<int> st;
         jpeg_run(ctx, fs.data(), jobs, JD_SUBSEQ_BITS, outs.data(), ps.data(), px, st);
         for (size_t i = 0; i < which.size(); ++i) status[which[i]] = st[i] ? BBOCR_ERR_DATA : BBOCR_OK;
+    });
+}
+
+int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dev_out, const long long* pitches,
+                      int* status) {
+    return jpeg_guarded(ctx, [&] {
+        if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
+        std::vector<FileJob> jobs;
+        std::vector<int> which;
+        std::vector<const uint8_t*> fs;
+        std::vector<uint8_t*> outs;
+        std::vector<long long> ps;
+        std::vector<size_t> offs;
+        jobs.reserve((size_t)n);
+        size_t page_bytes = 0;
+        for (int k = 0; k < n; ++k) {
+            status[k] = BBOCR_ERR_ARG;
+            if (!files[k] || !dev_out[k] || bytes[k] >= ((size_t)1 << 28)) continue;
+            FileJob j;
+            if (jpeg_parse(files[k], bytes[k], j.ps, true) != BBOCR_JPEG_OK) continue;
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            if (pitches[k] < 3LL * (pl.orientation >= 5 ? pl.height : pl.width)) continue;
+            // the un-oriented decode: Pillow's padded pixels (a dword per pixel) or the grey samples, tight rows
+            ps.push_back((long long)pl.width * (pl.components == 3 ? 4 : 1));
+            offs.push_back(page_bytes);
+            page_bytes = align_up(page_bytes + (size_t)ps.back() * (size_t)pl.height, 256);
+            jobs.push_back(std::move(j));
+            which.push_back(k);
+            fs.push_back(files[k]);
+        }
+        if (jobs.empty()) return;
+        ctx->jd_page.ensure(page_bytes);
+        for (size_t o : offs) outs.push_back((uint8_t*)ctx->jd_page.p + o);
+        std::vector<int> st;
+        jpeg_run(ctx, fs.data(), jobs, JD_SUBSEQ_BITS, outs.data(), ps.data(), 4, st);
+        for (size_t i = 0; i < which.size(); ++i) {
+            const int k = which[i];
+            status[k] = st[i] ? BBOCR_ERR_DATA : BBOCR_OK;
+            if (st[i]) continue;
+            const bbocr_jpeg_plan& pl = jobs[i].ps.plan;
+            HIPCHK(launch_page_orient(outs[i], pl.height, pl.width, (size_t)ps[i], pl.components == 3 ? TH_YCC4 : TH_GRAY, pl.orientation, TH_BGR,
+                                      dev_out[k], (size_t)pitches[k], ctx->jpeg_stream));
+        }
+        HIPCHK(hipStreamSynchronize(ctx->jpeg_stream));
     });
 }
 

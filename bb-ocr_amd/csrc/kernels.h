@@ -221,6 +221,13 @@ hipError_t launch_th_upsample(const uint8_t* yp, int wp, const uint8_t* cbp, con
                               uint8_t* gray, uint8_t* ycc, hipStream_t s);
 hipError_t launch_th_direct(const uint8_t* src, size_t pitch, int layout, int H, int W, uint8_t* rgb, uint8_t* gray, hipStream_t s);
 
+// ------------------------------------------------------------------ EXIF orientation + colour order of a page (orient.hip): cv2.imread's last step
+constexpr int ORIENT_TILE = 64;                                // pixels per tile edge (bb_ocr_amd.preprocess.ORIENT_TILE: the tests' shapes)
+bool page_orient_pair_ok(int layout, int dst_layout);          // BGR / RGB from every TH_* layout, GRAY from GRAY
+// src [H,W] pixels of `layout`, rows `pitch` apart -> dst in `dst_layout`, [H,W] (orientation 1-4) or [W,H] (5-8), rows `dst_pitch` apart
+hipError_t launch_page_orient(const uint8_t* src, int H, int W, size_t pitch, int layout, int orientation, int dst_layout, uint8_t* dst,
+                              size_t dst_pitch, hipStream_t s);
+
 // ------------------------------------------------------------------ baseline JPEG decoder (jpegdec.hip): speculative Huffman decoding with self-synchronisation
 constexpr int JD_LANES = 64;                                   // subsequences per workgroup of the synchronisation and write passes
 constexpr int JD_SUBSEQ_BITS = 1024;                           // default subsequence length

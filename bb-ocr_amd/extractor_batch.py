@@ -117,14 +117,16 @@ def _ocr_input_device(reader, image_path, image_index=None, decode_once=True, de
     return ("dev",) + tuple(ocr_input_ycc_device(reader, reader._to_dev(ycc), image_index))
 
 
-def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, on_device=False):
+def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, on_device=False,
+                  device_decode=False):
     """The page ``extract_text_with_ocr`` would hand to the down-scaling step (:425-485), as a host array: decoded like ``cv2.imread``
     (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
     final crop comes back.  A step that returns None in the reference leaves the page as it was.  ``on_device=True``: the crop stays on
-    the card, as a (possibly strided) view of the device page."""
-    from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, preprocess_bgr_device
+    the card, as a (possibly strided) view of the device page.  ``device_decode=True``: the page is read by
+    ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels)."""
+    from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, imread_bgr_device, preprocess_bgr_device
 
-    page = reader._to_dev(_imread_bgr(image_path))
+    page = imread_bgr_device(reader, image_path) if device_decode else reader._to_dev(_imread_bgr(image_path))
     if use_preprocessing:
         page = preprocess_bgr_device(reader, page)
     if edge_crop_percent > 0.0:
@@ -170,7 +172,8 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     YCbCr-coded JPEG above the limit is uploaded as decoded and shrunk there.  ``device_decode=True``: the decode step only reads the file
     and plans it (``bbocr_host_jpeg_plan``); baseline JPEG files -- the thumbnails included -- reach the card as their bytes and are
     decoded there, a whole batch by one call (csrc/jpegdec.hip, identical pixels); every other file, and a file whose data turns out
-    damaged, takes the host decode as before.  (The crop settings read the page like ``cv2.imread`` and keep their host decode.)"""
+    damaged, takes the host decode as before.  With the crop settings the page is read like ``cv2.imread``, EXIF orientation included, and
+    ``device_decode=True`` does that on the card as well (``preprocess.imread_bgr_device``: csrc/jpegdec.hip + csrc/orient.hip)."""
     from .preprocess import ocr_input_device
 
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
@@ -178,7 +181,8 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
             raise ValueError("crop_margin must be >= 0")
 
         def decode(path, i):
-            page = ocr_page_crop(reader, path, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=device_thumbnail)
+            page = ocr_page_crop(reader, path, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=device_thumbnail,
+                                 device_decode=device_decode)
             if device_thumbnail:
                 return ("dev",) + tuple(ocr_input_device(reader, page, i))
             return _ocr_input_array(page, i, decode_once)

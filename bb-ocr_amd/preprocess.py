@@ -6,12 +6,15 @@
 and runs the seven stages as HIP kernels (csrc/preproc.hip) through ``bbocr_preprocess_book_cover``; ``..._device`` keeps the
 result in HBM so it can go straight into ``Reader.readtext_device``.
 
-Decoding is host work (PIL).  ``cv2.imread`` applies the EXIF orientation and returns BGR; ``_imread_bgr`` does the same with
-Pillow (the JPEG decoders of OpenCV and Pillow builds may differ in the last bit of a pixel, which is outside this backend).
+``cv2.imread`` applies the EXIF orientation and returns BGR; ``_imread_bgr`` does the same on the host with Pillow (the JPEG decoders
+of OpenCV and Pillow builds may differ in the last bit of a pixel, which is outside this backend).  ``imread_bgr_device`` yields the same
+page on the card: a baseline JPEG file goes from its bytes to the oriented BGR page without existing as host pixels (csrc/jpegdec.hip +
+csrc/orient.hip); every other file is decoded once on the host, un-oriented, and oriented + channel-ordered on the card.
 """
 from __future__ import annotations
 
 import ctypes as C
+import io
 import os
 
 import numpy as np
@@ -29,6 +32,86 @@ def _imread_bgr(image_path):
     pil = ImageOps.exif_transpose(pil)
     rgb = np.asarray(pil.convert("RGB"))
     return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+ORIENT_TILE = 64                                  # csrc/kernels.h ORIENT_TILE: page_orient's tile edge in pixels (the tests' shapes)
+IMREAD_JPEG, IMREAD_YCC, IMREAD_RGB = "jpeg", "ycc", "rgb"       # the path imread_bgr_device took (``.imread_path`` of its result)
+
+
+def exif_orientation(value):
+    """The rule of ``bbocr_jpeg_plan::orientation`` for a tag value read elsewhere: 1 .. 8 as it is, anything else 1"""
+    return int(value) if isinstance(value, int) and 1 <= value <= 8 else 1
+
+
+def orient_page_device(reader, page_dev, layout, orientation, dst_layout=None):
+    """``bbocr_page_orient`` of a uint8 device page of the given ``PAGE_*`` layout (rows of packed pixels; a strided row pitch is read in
+    place): the page in EXIF ``orientation`` (1 .. 8, ``ImageOps.exif_transpose``'s geometry) as ``dst_layout`` -- ``PAGE_BGR`` (default) or
+    ``PAGE_RGB`` ``[H',W',3]`` from every layout, ``PAGE_GRAY`` ``[H',W']`` from a gray page.  A new tensor; the source is left as it is."""
+    import torch
+
+    dst_layout = PAGE_BGR if dst_layout is None else dst_layout
+    if not isinstance(page_dev, torch.Tensor) or page_dev.dtype != torch.uint8 or page_dev.ndim not in (2, 3):
+        raise ValueError("expected a uint8 [H,W] or [H,W,C] device tensor")
+    if not page_dev.is_cuda or page_dev.device.index != reader.device_index:
+        raise ValueError(f"expected a tensor on {reader.device}")
+    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
+    ch = 1 if page_dev.ndim == 2 else int(page_dev.shape[2])
+    want = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}.get(layout)
+    st = page_dev.stride()
+    if want is None or ch != want or H < 1 or W < 1 or st[1] != ch or (page_dev.ndim == 3 and st[2] != 1) or st[0] < W * ch:
+        raise ValueError(f"page of shape {tuple(page_dev.shape)} / strides {st} does not hold layout {layout}")
+    if dst_layout not in (PAGE_BGR, PAGE_RGB) and not (dst_layout == PAGE_GRAY and layout == PAGE_GRAY):
+        raise ValueError(f"no conversion from layout {layout} to layout {dst_layout}")
+    if not isinstance(orientation, int) or not 1 <= orientation <= 8:
+        raise ValueError("orientation must be 1 .. 8")
+    oh, ow = (W, H) if orientation >= 5 else (H, W)
+    out = torch.empty((oh, ow) if dst_layout == PAGE_GRAY else (oh, ow, 3), dtype=torch.uint8, device=page_dev.device)
+    torch.cuda.current_stream(reader.device_index).synchronize()       # the library runs on its own stream
+    rh, rw = C.c_int(), C.c_int()
+    reader._check(reader._lib.bbocr_page_orient(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, int(st[0]), int(layout), int(orientation),
+                                                int(dst_layout), C.c_void_p(out.data_ptr()), int(out.stride(0)), C.byref(rh), C.byref(rw)))
+    return out
+
+
+def imread_bgr_device(reader, source):
+    """``reader._to_dev(_imread_bgr(source))`` without the host's oriented page: ``cv2.imread``'s BGR page, uint8 ``[H',W',3]`` on the
+    reader's device, bit for bit.  ``source``: a path or the file's bytes.  Three paths, tried in this order; the one taken is recorded
+    as ``.imread_path`` of the returned tensor:
+
+    * ``IMREAD_JPEG`` -- the device decoder's plan takes the file: only its bytes cross the link (``bbocr_jpeg_imread``);
+    * ``IMREAD_YCC``  -- a YCbCr-coded JPEG the plan refuses (progressive, 4:4:4, ...) or whose entropy-coded data the device decoder
+      reports damaged: ``decode_file_ycc`` on the host, the un-oriented triples uploaded, oriented and converted on the card;
+    * ``IMREAD_RGB``  -- everything else: Pillow's un-oriented ``convert("RGB")``, uploaded, oriented and channel-swapped on the card.
+
+    The orientation is the plan's (EXIF IFD0, OpenCV's rule) for the first two and ``Image.getexif()`` under the same 1 .. 8 rule for the
+    third.  ``_imread_bgr`` (Pillow's ``exif_transpose``) also honours an XMP ``tiff:Orientation`` when the EXIF block has no tag; OpenCV
+    and this function do not."""
+    from PIL import Image
+
+    from .reader import decode_file_ycc, jpeg_page, jpeg_plan
+
+    if isinstance(source, (bytes, bytearray)):
+        data = bytes(source)
+    else:
+        with open(os.path.expanduser(os.fspath(source)), "rb") as f:
+            data = f.read()
+    plan = jpeg_plan(data)
+    out = path = None
+    if plan.supported:
+        pages, status = reader.imread_jpeg_batch([jpeg_page(data)])
+        if status[0] == 0:
+            out, path = pages[0], IMREAD_JPEG
+    if out is None:
+        ycc = decode_file_ycc(data, padded=True)
+        if ycc is not None:
+            layout = PAGE_YCBCR4 if ycc.shape[2] == 4 else PAGE_YCBCR3
+            out, path = orient_page_device(reader, reader._to_dev(ycc), layout, exif_orientation(plan.orientation)), IMREAD_YCC
+    if out is None:
+        pil = Image.open(io.BytesIO(data))
+        o = exif_orientation(pil.getexif().get(0x0112))
+        out, path = orient_page_device(reader, reader._to_dev(np.asarray(pil.convert("RGB"))), PAGE_RGB, o), IMREAD_RGB
+    out.imread_path = path
+    return out
 
 
 def preprocess_bgr_device(reader, bgr_dev, legacy=False, **overrides):
@@ -60,19 +143,20 @@ def preprocess_bgr_device(reader, bgr_dev, legacy=False, **overrides):
     return out
 
 
-def preprocess_for_book_cover(image_path, output_path=None, reader=None, legacy=False):
+def preprocess_for_book_cover(image_path, output_path=None, reader=None, legacy=False, device_decode=False):
     """Drop-in for the reference function: ``(gray uint8 array, output_path, steps_applied)``.  ``image_path`` may also be a
     decoded BGR array.  ``reader`` supplies the device context (any ``bb_ocr_amd.Reader``).  ``legacy=True`` runs the older
-    ``preprocess_for_book_cover`` of pipeline_components/img_to_json/ocr_testing/preprocessing/image_preprocessor.py:221-252."""
+    ``preprocess_for_book_cover`` of pipeline_components/img_to_json/ocr_testing/preprocessing/image_preprocessor.py:221-252.
+    ``device_decode=True``: a path is read by ``imread_bgr_device`` (same pixels)."""
     if reader is None:
         raise ValueError("preprocess_for_book_cover needs a bb_ocr_amd.Reader (device context)")
     if isinstance(image_path, np.ndarray):
-        bgr = np.ascontiguousarray(image_path)
+        page = reader._to_dev(np.ascontiguousarray(image_path))
     else:
         if not os.path.exists(image_path):
             raise ValueError(f"Could not load image from {image_path}")      # image_preprocessor.py:19-20
-        bgr = _imread_bgr(image_path)
-    out = preprocess_bgr_device(reader, reader._to_dev(bgr), legacy=legacy).cpu().numpy()
+        page = imread_bgr_device(reader, image_path) if device_decode else reader._to_dev(_imread_bgr(image_path))
+    out = preprocess_bgr_device(reader, page, legacy=legacy).cpu().numpy()
     if output_path:
         from PIL import Image
 
@@ -195,11 +279,18 @@ def _read_page(image_path_or_array):
     return _imread_bgr(image_path_or_array)
 
 
-def auto_crop_text_region(image_path_or_array, margin=128, reader=None):
+def auto_crop_text_region(image_path_or_array, margin=128, reader=None, device_decode=False):
     """Drop-in for ``_auto_crop_text_region(image_path, margin)``: the cropped page (an array, where the reference writes it to a PNG
-    and returns the path) or None.  A path is decoded like ``cv2.imread`` (BGR, EXIF-transposed); an array may be gray or BGR."""
+    and returns the path) or None.  A path is decoded like ``cv2.imread`` (BGR, EXIF-transposed); an array may be gray or BGR.
+    ``device_decode=True``: a path is read by ``imread_bgr_device``, and only the crop comes back from the card (same pixels)."""
     if reader is None:
         raise ValueError("auto_crop_text_region needs a bb_ocr_amd.Reader (device context)")
+    if device_decode and not isinstance(image_path_or_array, np.ndarray):
+        if not os.path.exists(image_path_or_array):
+            return None
+        page = imread_bgr_device(reader, image_path_or_array)
+        b = auto_crop_box_device(reader, page, margin)
+        return None if b is None else page[b[1]:b[3], b[0]:b[2]].contiguous().cpu().numpy()
     img = _read_page(image_path_or_array)
     if img is None:
         return None

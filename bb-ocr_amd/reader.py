@@ -148,12 +148,15 @@ def decode_file_ycc(source, padded=False):
 
 class JpegPage:
     """A baseline JPEG file the device decoder takes (``jpeg_plan``): its bytes and the shape of its decode, ``(H, W, components)``.  The
-    page kind ``"jpg"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one ``bbocr_jpeg_decode`` call."""
-    __slots__ = ("data", "shape")
+    page kind ``"jpg"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one ``bbocr_jpeg_decode`` call.
+    ``orientation``: the plan's EXIF orientation (1 .. 8), which ``shape`` does not reflect -- ``readtext`` reads files un-oriented, and
+    only ``Reader.imread_jpeg_batch`` (``cv2.imread``'s page) applies it."""
+    __slots__ = ("data", "shape", "orientation")
 
     def __init__(self, data, plan):
         self.data = data
         self.shape = (int(plan.height), int(plan.width), int(plan.components))
+        self.orientation = int(plan.orientation)
 
 
 def jpeg_plan(data):
@@ -595,6 +598,28 @@ class Reader:
         layout = 3 if padded else 4                               # BBOCR_PAGE_YCBCR4 / BBOCR_PAGE_YCBCR3
         self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
         return t, list(status)
+
+    def imread_jpeg_batch(self, pages):
+        """``JpegPage`` s of any shapes -> ``(tensors, status)``: per page ``cv2.imread``'s BGR page ``uint8 [H',W',3]`` on the device -- the
+        decode with the page's EXIF orientation applied (``H'``, ``W'`` swapped for orientations 5 .. 8), a grey file replicated -- by ONE
+        ``bbocr_jpeg_imread`` call, and the per-file status list (non-zero: that tensor is undefined)."""
+        torch = self._torch
+        pages = list(pages)
+        if not pages:
+            raise ValueError("imread_jpeg_batch: no pages")
+        outs = []
+        for p in pages:
+            H, W, _ = p.shape
+            outs.append(torch.empty((W, H, 3) if p.orientation >= 5 else (H, W, 3), dtype=torch.uint8, device=self.device))
+        torch.cuda.current_stream(self.device_index).synchronize()
+        n = len(pages)
+        files = (C.c_void_p * n)(*[C.cast(C.c_char_p(p.data), C.c_void_p) for p in pages])
+        sizes = (C.c_size_t * n)(*[len(p.data) for p in pages])
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+        pitches = (C.c_longlong * n)(*[t.shape[1] * 3 for t in outs])
+        status = (C.c_int * n)()
+        self._check(self._lib.bbocr_jpeg_imread(self._h, files, sizes, n, ptrs, pitches, status))
+        return outs, list(status)
 
     def pages_from_jpeg(self, batch):
         """The tensor of ``decode_jpeg_batch`` -> ``(rgb_dev, gray_dev)``: ``pages_from_ycc`` of the triples ``[n,H,W,3 or 4]``; for

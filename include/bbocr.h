@@ -326,6 +326,16 @@ int bbocr_op_autocrop_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, i
 enum { BBOCR_PAGE_GRAY = 0, BBOCR_PAGE_BGR = 1, BBOCR_PAGE_RGB = 2, BBOCR_PAGE_YCBCR4 = 3, BBOCR_PAGE_YCBCR3 = 4 };
 int bbocr_ocr_thumbnail(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int max_dim, int quality, uint8_t* dev_rgb,
                         uint8_t* dev_gray, int* out_h, int* out_w);
+/* ---- EXIF orientation + channel order of one u8 page on the device (csrc/orient.hip): what cv2.imread does behind its decoder.  Source:
+ * [H,W] pixels of any BBOCR_PAGE_* layout, rows `pitch` bytes apart.  Destination: [H',W',c] in dst_layout, rows dst_pitch apart, (H', W') =
+ * (H, W) for orientations 1 .. 4 and (W, H) for 5 .. 8; BBOCR_PAGE_BGR or BBOCR_PAGE_RGB from every source (GRAY replicated, YCbCr through
+ * libjpeg's integer conversion), BBOCR_PAGE_GRAY from GRAY.  Geometry = PIL.ImageOps.exif_transpose = OpenCV's ExifTransform:
+ *   1 as it is, 2 mirror columns, 3 rotate 180, 4 mirror rows, 5 transpose, 6 rotate 90 clockwise, 7 transverse, 8 rotate 90 counter-clockwise.
+ * out_h / out_w receive (H', W'); dev_dst = NULL is a size query.  Source and destination must not overlap.  Bytes of a destination row
+ * behind W' * c are left as they are.  A pipeline call: runs in a call slot, returns with its work finished.  BBOCR_ERR_ARG before anything
+ * is queued: null pointers, H or W < 1, an unknown layout or layout pair, orientation outside 1 .. 8, a pitch shorter than a row. */
+int bbocr_page_orient(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int orientation, int dst_layout,
+                      uint8_t* dev_dst, long long dst_pitch, int* out_h, int* out_w);
 /* its parts (parity tests): stage 0 = the thumbnail alone (reduce + resize) as RGB [out_h,out_w,3] in dev_dst (a page at or below
  * max_dim: the page as RGB); stage 1 = the JPEG round trip alone of a gray or RGB page, RGB -> dev_dst [H,W,3], Y -> dev_gray [H,W];
  * stage 2 = the upsampled YCbCr triple of that round trip, before the colour conversion, in dev_dst [H,W,3].  Stages 1 and 2 need
@@ -347,7 +357,8 @@ int bbocr_host_jpeg_qtables(int quality, uint16_t* out);
 /* ---- baseline JPEG files decoded on the device (csrc/jpegdec.hip), to the bit of libjpeg-turbo / Pillow: only the file's bytes cross the
  * link.  Taken: SOF0, 8 bit, Huffman, ONE interleaved scan, 3 components YCbCr 4:2:0 (JFIF, or Adobe transform 1: decode_file_ycc's
  * rule) or 1 component, any DQT / DHT / DRI, any size.  Everything else is refused by the plan, and the caller keeps its host path.
- * EXIF orientation is ignored, as the host path ignores it. */
+ * bbocr_jpeg_decode ignores the EXIF orientation, as the host path of readtext ignores it; the plan reports it, and bbocr_jpeg_imread
+ * applies it: cv2.imread's page, which the extractor's crop settings read. */
 enum {
     BBOCR_JPEG_OK = 0,
     BBOCR_JPEG_NOT_JPEG = 1,    /* no SOI: another container */
@@ -372,7 +383,13 @@ typedef struct bbocr_jpeg_plan {
     long long scan_bytes;       /* up to the marker that ends the scan (stuffing and restart markers included) */
     int supported;              /* 1: bbocr_jpeg_decode takes the file */
     int reason;                 /* BBOCR_JPEG_* */
-    int reserved[4];
+    int orientation;            /* EXIF orientation 1 .. 8 as cv2.imread applies it, 1 = none: the first APP1 "Exif\0\0" segment before SOS, TIFF header
+                                 * of either byte order, IFD0 only, tag 0x0112 as ONE SHORT or LONG of value 1 .. 8.  Everything else is 1: no such
+                                 * segment or tag, a tag only in IFD1, another type or count, value 0 / 9 / 65535, an IFD offset or entry count that
+                                 * leaves the segment.  Filled for every file that starts with SOI, refused ones included; malformed EXIF changes no
+                                 * other field.  XMP's tiff:Orientation is not read (OpenCV does not read it; Pillow's exif_transpose does, when the
+                                 * EXIF block has no tag: the one difference to preprocess._imread_bgr). */
+    int reserved[3];
 } bbocr_jpeg_plan;
 /* host only, no GPU: one linear pass over the file (markers, then the scan's FF bytes); no entropy bit is decoded.  Fields a refused
  * file's headers did not reach stay 0. */
@@ -387,6 +404,12 @@ int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* pla
  * buffers belong to the context and grow on demand.  Returns with its work finished, also when it fails. */
 int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, uint8_t* const* dev_out,
                       const long long* pitches, int* status);
+/* cv2.imread(path) of n files on the device: bbocr_jpeg_decode followed by the orientation the plan reports, written as BGR (a
+ * 1-component file replicated).  dev_out[k]: uint8 [H',W',3], rows pitches[k] >= 3 * W' bytes apart, (H', W') = the plan's (height, width),
+ * swapped for orientations 5 .. 8.  Same stream, same one-batch-at-a-time contract and same per-file status as bbocr_jpeg_decode (a
+ * pitch shorter than the ORIENTED row: BBOCR_ERR_ARG).  The un-oriented decode lives in a buffer of the context that grows on demand. */
+int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dev_out, const long long* pitches,
+                      int* status);
 /* its intermediates of ONE file (parity tests), cut into subsequences of subseq_bits bits (0 = the decoder's 1024; a multiple of 8 in
  * 32 .. 65536): stage 0 = the exact entry state of every subsequence, int32 [subsequences][4] = (bit in the unstuffed scan, block in the
  * MCU, zig-zag position, first output block); 1 = quantised coefficients int16 [blocks][64] in natural order, blocks in MCU order, DC
