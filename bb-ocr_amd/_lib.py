@@ -19,6 +19,8 @@ class bbocr_config(C.Structure):
 
 
 PRECISIONS = {"bf16": 0, "fp16": 1, "exact": 2, "mixed": 3, "exact_rec": 4}
+PAGE_GRAY, PAGE_BGR, PAGE_RGB, PAGE_YCBCR4, PAGE_YCBCR3 = 0, 1, 2, 3, 4          # bbocr.h BBOCR_PAGE_*: layouts of a device page
+PAGE_PX_BYTES = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}    # bytes per pixel (csrc/kernels.h page_px_bytes)
 
 
 class bbocr_tensor_desc(C.Structure):

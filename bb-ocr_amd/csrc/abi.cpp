@@ -116,8 +116,8 @@ void bbocr_destroy(bbocr_ctx* c) {
     free_weights(c);
     slot_destroy(c);
     if (c->zero_page) (void)hipFree(c->zero_page);
-    if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
-    if (c->jpeg_stream) (void)hipStreamDestroy(c->jpeg_stream);
+    for (SideLane* l : {&c->upload_lane, &c->jpeg_lane})
+        if (l->stream) (void)hipStreamDestroy(l->stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

@@ -52,27 +52,26 @@ AcPlan ac_plan(bbocr_ctx* c, int H, int W) {
     const size_t n = (size_t)H * W, nw = (size_t)p.WW * H;
     // every component of the merged mask holds a whole 13 x 5 dilation window (clipped at the edges), so at most n / that many exist
     p.cap = (int)(n / ((size_t)std::min(W, 7) * std::min(H, 3))) + 1;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_blur = carve(n), o_clahe = carve(n), o_rows = carve(4 * n), o_part = carve(n), o_grad = carve(n);
+    Carve cv;
+    const size_t o_blur = cv.add(n), o_clahe = cv.add(n), o_rows = cv.add(4 * n), o_part = cv.add(n), o_grad = cv.add(n);
     size_t o_bits[5];
-    for (auto& o : o_bits) o = carve(nw * 4);
-    const size_t o_hist = carve(512 * 4), o_small = carve(16), o_boxes = carve((size_t)p.cap * 16);
-    c->ac_work.ensure(off);
-    char* b = (char*)c->ac_work.p;
-    p.blur = (uint8_t*)(b + o_blur);
-    p.clahe = (uint8_t*)(b + o_clahe);
-    p.rbox = (uint16_t*)(b + o_rows);
+    for (auto& o : o_bits) o = cv.add(nw * 4);
+    const size_t o_hist = cv.add(512 * 4), o_small = cv.add(16), o_boxes = cv.add((size_t)p.cap * 16);
+    c->ac_work.ensure(cv.off);
+    void* b = c->ac_work.p;
+    p.blur = Carve::at<uint8_t>(b, o_blur);
+    p.clahe = Carve::at<uint8_t>(b, o_clahe);
+    p.rbox = Carve::at<uint16_t>(b, o_rows);
     p.rgau = p.rbox + n;
-    p.label = (int*)(b + o_rows);
-    p.part = (uint8_t*)(b + o_part);
+    p.label = Carve::at<int>(b, o_rows);
+    p.part = Carve::at<uint8_t>(b, o_part);
     p.flag = p.part;
-    p.grad = (uint8_t*)(b + o_grad);
-    for (int i = 0; i < 5; ++i) p.bits[i] = (uint32_t*)(b + o_bits[i]);
-    p.hist = (unsigned int*)(b + o_hist);
-    p.thr = (int*)(b + o_small);
+    p.grad = Carve::at<uint8_t>(b, o_grad);
+    for (int i = 0; i < 5; ++i) p.bits[i] = Carve::at<uint32_t>(b, o_bits[i]);
+    p.hist = Carve::at<unsigned int>(b, o_hist);
+    p.thr = Carve::at<int>(b, o_small);
     p.count = p.thr + 2;
-    p.boxes = (int*)(b + o_boxes);
+    p.boxes = Carve::at<int>(b, o_boxes);
     return p;
 }
 
@@ -107,11 +106,8 @@ void ac_enqueue(bbocr_ctx* c, const AcPlan& p, const uint8_t* src, size_t pitch,
 }
 
 void ac_check_args(const void* src, int H, int W, long long pitch, int channels) {
-    if (!src) fail(BBOCR_ERR_ARG, "null device pointer");
-    if (H < 1 || W < 1) fail(BBOCR_ERR_ARG, "bad image shape");
     if (channels != 1 && channels != 3) fail(BBOCR_ERR_ARG, "channels must be 1 or 3");
-    if (pitch < (long long)W * channels) fail(BBOCR_ERR_ARG, "row pitch smaller than a row");
-    if ((long long)H * W >= (1LL << 30)) fail(BBOCR_ERR_ARG, "image too large");
+    check_page({src, H, W, pitch, channels == 1 ? PAGE_GRAY : PAGE_BGR});
     // clahe.cpp pads both axes to the 8x8 grid when either does not divide; the padding must stay inside the image (preprocess.cpp::pp_clahe)
     const bool pad = (H % 8) || (W % 8);
     if (pad && ((8 - H % 8) >= H || (8 - W % 8) >= W)) fail(BBOCR_ERR_ARG, "image smaller than the CLAHE tile grid");

@@ -105,9 +105,40 @@ struct Arena {   // bump allocator over one device buffer; a dry pass sizes it, 
     }
 };
 
+struct Carve {   // offsets into one buffer at 256-byte steps: add() while the buffer is sized, at<T>() once it exists
+    size_t off = 0;
+    size_t add(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+    template <typename T> static T* at(void* base, size_t o) { return (T*)((char*)base + o); }
+};
+
 struct Act {   // bf16 NHWC activation
     uint16_t* p;
     int N, H, W, C;
+};
+
+// A page in device memory as the page-level entry points take it: H rows of W packed pixels of a PAGE_* layout, `pitch` bytes apart.
+struct DevPage {
+    const void* p;
+    int H, W;
+    long long pitch;
+    int layout;
+};
+constexpr unsigned page_set(int layout) { return 1u << layout; }
+constexpr unsigned PAGE_ANY = page_set(PAGE_YCC3 + 1) - 1;
+// the one rule of a valid page; `allowed`: page_set() bits of the layouts the caller takes
+inline void check_page(const DevPage& g, unsigned allowed = PAGE_ANY) {
+    if (!g.p) fail(BBOCR_ERR_ARG, "null device pointer");
+    if (g.H < 1 || g.W < 1) fail(BBOCR_ERR_ARG, "bad image shape");
+    if ((long long)g.H * g.W >= (1LL << 30)) fail(BBOCR_ERR_ARG, "image too large");
+    if (g.layout < PAGE_GRAY || g.layout > PAGE_YCC3 || !(allowed & page_set(g.layout))) fail(BBOCR_ERR_ARG, "layout must be one of the BBOCR_PAGE_* taken here");
+    if (g.pitch < (long long)g.W * page_px_bytes(g.layout)) fail(BBOCR_ERR_ARG, "row pitch smaller than a row");
+}
+
+// A mutex plus a lazily created non-blocking stream on the root, outside the call slots: work on a lane never waits for a running call
+// (lane_guarded below).  One call at a time per lane.
+struct SideLane {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
 };
 
 
@@ -168,10 +199,8 @@ struct bbocr_ctx : WeightView {
     unsigned int ignore_mask[4] = {0, 0, 0, 0};   // recogniser class mask of the running call (bbocr_params::ignore_mask)
     int beam_width = 0;                           // > 0: decoder='beamsearch' for the running call (bbocr_params::decoder / beam_width)
     hipStream_t cur = nullptr;                // stream the layer helpers launch on
-    hipStream_t upload_stream = nullptr;      // root only: bbocr_upload_pages copies here, outside the call slots (an upload never waits for a running call)
-    std::mutex upload_mu;
-    hipStream_t jpeg_stream = nullptr;        // root only: bbocr_jpeg_decode runs here, outside the call slots like an upload (jpegdec.cpp)
-    std::mutex jpeg_mu;                       // one decode batch at a time per context; guards the jd_* buffers
+    SideLane upload_lane;                     // root only: bbocr_upload_pages copies here (an upload never waits for a running call)
+    SideLane jpeg_lane;                       // root only: the JPEG batches of jpegdec.cpp run here; its mutex guards the jd_* buffers
     PinBuf jd_pin;                            // the batch's tables + unstuffed entropy bytes, staged for one H2D copy into jd_in
     DevBuf jd_in, jd_work, jd_coef, jd_stage; // per-subsequence states and component planes, coefficients, bbocr_op_jpeg_stage's scratch image
     DevBuf jd_page;                           // bbocr_jpeg_imread: the batch's un-oriented decodes, between the decoder and page_orient
@@ -464,40 +493,65 @@ struct SlotLease {
     }
 };
 
-// every ABI entry point runs inside guarded(): device selected, a call slot leased, exceptions mapped to status codes.  f(slot) does the work.
-template <typename F> inline int guarded(bbocr_ctx* root, F&& f, bool exclusive = false) {
+inline void set_err(bbocr_ctx* root, const std::string& m) {
+    std::lock_guard<std::mutex> lk(root->pool_mu);
+    root->err = m;
+}
+
+// f() as an entry point's status: the one mapping of a failure to a status code and the context's message (bbocr_last_error)
+template <typename F> inline int status_of(bbocr_ctx* root, F&& f) {
     if (!root) return BBOCR_ERR_ARG;
-    auto set_err = [&](const std::string& m) {
-        std::lock_guard<std::mutex> lk(root->pool_mu);
-        root->err = m;
-    };
-    bbocr_ctx* ctx = nullptr;
     try {
-        hipError_t e = hipSetDevice(root->cfg.device);
-        if (e != hipSuccess) fail(BBOCR_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+        f();
+        return BBOCR_OK;
+    } catch (const StatusError& se) {
+        set_err(root, se.msg);
+        return se.code;
+    } catch (const std::exception& ex) {
+        set_err(root, ex.what());
+        return BBOCR_ERR_INTERNAL;
+    } catch (...) {
+        set_err(root, "unknown failure");
+        return BBOCR_ERR_INTERNAL;
+    }
+}
+
+// every pipeline entry point runs inside guarded(): device selected, a call slot leased, exceptions mapped to status codes.  f(slot) does the work.
+template <typename F> inline int guarded(bbocr_ctx* root, F&& f, bool exclusive = false) {
+    return status_of(root, [&] {
+        HIPCHK(hipSetDevice(root->cfg.device));
         SlotLease lease(root, exclusive);
-        ctx = lease.slot;
+        bbocr_ctx* ctx = lease.slot;
         try {
             ctx->cur = ctx->stream;
             // the library runs on its own non-blocking streams: what the caller queued on the default stream (torch's) -- fills of
             // output buffers, input copies -- must be complete before our kernels touch the same memory
-            e = hipStreamSynchronize(nullptr);
-            if (e != hipSuccess) fail(BBOCR_ERR_HIP, std::string("default stream: ") + hipGetErrorString(e));
+            HIPCHK(hipStreamSynchronize(nullptr));
             f(ctx);
             publish_times(ctx);
-            return BBOCR_OK;
         } catch (...) {
             guarded_drain(ctx);                      // still inside the lease: nobody else touches this slot's buffers meanwhile
             throw;
         }
-    } catch (const StatusError& se) {
-        set_err(se.msg);
-        return se.code;
-    } catch (const std::exception& ex) {
-        set_err(ex.what());
-        return BBOCR_ERR_INTERNAL;
-    } catch (...) {
-        set_err("unknown failure");
-        return BBOCR_ERR_INTERNAL;
-    }
+    });
+}
+
+// an entry point outside the call slots runs inside lane_guarded(): device selected, the lane's mutex held, its stream made on first use,
+// the default stream waited for where the caller's fills and allocations matter (wait_default).  f(stream) does the work; when it fails
+// the lane's stream is drained before the status is returned, so that nothing queued still reads or writes caller-owned memory.
+template <typename F> inline int lane_guarded(bbocr_ctx* root, SideLane bbocr_ctx::*which, bool wait_default, F&& f) {
+    return status_of(root, [&] {
+        HIPCHK(hipSetDevice(root->cfg.device));
+        SideLane& lane = root->*which;
+        std::lock_guard<std::mutex> lk(lane.mu);
+        try {
+            if (!lane.stream) HIPCHK(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
+            if (wait_default) HIPCHK(hipStreamSynchronize(nullptr));
+            f(lane.stream);
+        } catch (...) {
+            if (lane.stream) (void)hipStreamSynchronize(lane.stream);
+            (void)hipGetLastError();
+            throw;
+        }
+    });
 }

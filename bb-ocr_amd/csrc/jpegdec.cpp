@@ -224,43 +224,65 @@ bool derive_table(const HuffSpec& h, JpegHuff& t) {
     return true;
 }
 
-struct FileJob {
+struct FileJob {                              // one admitted file of a batch
     JpegParsed ps;
+    const uint8_t* file = nullptr;            // its bytes (caller-owned)
+    uint8_t* out = nullptr;                   // where the decoder writes its pixels, rows `pitch` bytes apart
+    long long pitch = 0;
+    int k = 0;                                // its index in the caller's arrays (status[])
     int nsub = 0, groups = 0, nblocks = 0;
     size_t o_huff, o_quant, o_segbyte, o_segsub, o_subseg, o_data, data_bytes;   // offsets in the input blob
     size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[3], o_coef; // offsets in the work / coefficient buffers
+    size_t o_page = 0;                        // bbocr_jpeg_imread: offset of the un-oriented decode in jd_page
 };
 
-void jpeg_stream_ready(bbocr_ctx* root) {
-    if (!root->jpeg_stream) HIPCHK(hipStreamCreateWithFlags(&root->jpeg_stream, hipStreamNonBlocking));
+// Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan refuses (the caller plans first: a
+// refused file is its error); every other file becomes a job once dest(job) -- the entry point's own rule -- has checked the caller's
+// destination and set the job's `out` and `pitch` (false: refused like the others).
+template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* files, const size_t* bytes, int n, int* status, D&& dest) {
+    std::vector<FileJob> jobs;
+    jobs.reserve((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        status[k] = BBOCR_ERR_ARG;
+        if (!files[k] || bytes[k] >= ((size_t)1 << 28)) continue;
+        FileJob j;
+        if (jpeg_parse(files[k], bytes[k], j.ps, true) != BBOCR_JPEG_OK) continue;
+        j.file = files[k];
+        j.k = k;
+        if (dest(j)) jobs.push_back(std::move(j));
+    }
+    return jobs;
 }
 
-// The whole decode of `n` planned files; out[k] / pitch[k] / px: where the pixels go.  Fills dev_status[k] (JD_ERR_* bits) and leaves the
-// jobs for the stage entry point.  Everything is queued on the root's JPEG stream and finished on return.
-void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>& jobs, int S, uint8_t* const* outs, const long long* pitches,
-              int px, std::vector<int>& dev_status, std::vector<JpegDesc>* descs_out = nullptr) {
+// the decoder's verdict on each job (jpeg_run's dev_status) as the caller's status
+void jpeg_report(const std::vector<FileJob>& jobs, const std::vector<int>& dev_status, int* status) {
+    for (size_t i = 0; i < jobs.size(); ++i) status[jobs[i].k] = dev_status[i] ? BBOCR_ERR_DATA : BBOCR_OK;
+}
+
+// The whole decode of the admitted jobs on the JPEG lane's stream `st`; px: bytes per pixel of a 3-component file's output.  Fills
+// dev_status[i] (JD_ERR_* bits of job i) and leaves the descriptors for the stage entry point.  Everything queued is finished on return.
+void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S, int px, std::vector<int>& dev_status,
+              std::vector<JpegDesc>* descs_out = nullptr) {
     const int n = (int)jobs.size();
-    hipStream_t st = root->jpeg_stream;
-    size_t in_off = align_up(sizeof(JpegDesc) * (size_t)n, 256), work_off = align_up(4 * (size_t)n, 256), coef_off = 0;
-    auto carve = [](size_t& off, size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+    Carve in{align_up(sizeof(JpegDesc) * (size_t)n, 256)}, work{align_up(4 * (size_t)n, 256)}, coef;
     int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;
     for (FileJob& j : jobs) {
         const bbocr_jpeg_plan& pl = j.ps.plan;
-        j.o_huff = carve(in_off, 4 * sizeof(JpegHuff));
-        j.o_quant = carve(in_off, 3 * 64 * 2);
-        j.o_segbyte = carve(in_off, 4 * ((size_t)pl.segments + 1));
-        j.o_segsub = carve(in_off, 4 * ((size_t)pl.segments + 1));
-        j.o_data = carve(in_off, (size_t)pl.scan_bytes + 8);
+        j.o_huff = in.add(4 * sizeof(JpegHuff));
+        j.o_quant = in.add(3 * 64 * 2);
+        j.o_segbyte = in.add(4 * ((size_t)pl.segments + 1));
+        j.o_segsub = in.add(4 * ((size_t)pl.segments + 1));
+        j.o_data = in.add((size_t)pl.scan_bytes + 8);
         // subsequences: every segment is cut on its own, so at most one per segment more than scan bits / S
-        j.o_subseg = carve(in_off, 4 * ((size_t)pl.segments + (size_t)pl.scan_bytes * 8 / S + 1));
+        j.o_subseg = in.add(4 * ((size_t)pl.segments + (size_t)pl.scan_bytes * 8 / S + 1));
         j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? 6 : 1);
         max_seg = std::max(max_seg, pl.segments);
         max_blocks = std::max(max_blocks, j.nblocks);
         max_h = std::max(max_h, pl.height);
         max_w = std::max(max_w, pl.width);
     }
-    root->jd_pin.ensure(in_off);
-    root->jd_in.ensure(in_off);
+    root->jd_pin.ensure(in.off);
+    root->jd_in.ensure(in.off);
     char* hb = (char*)root->jd_pin.p;
     char* db = (char*)root->jd_in.p;
     for (FileJob& j : jobs) {                                             // fill the blob: unstuff, cut, derive
@@ -277,8 +299,8 @@ void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>
         size_t w = 0;
         int nsub = 0;
         for (int s = 0; s < pl.segments; ++s) {
-            const uint8_t* a = files[&j - jobs.data()] + j.ps.segs[s].first;
-            const uint8_t* e = files[&j - jobs.data()] + j.ps.segs[s].second;
+            const uint8_t* a = j.file + j.ps.segs[s].first;
+            const uint8_t* e = j.file + j.ps.segs[s].second;
             seg_byte[s] = (int)w;
             seg_sub[s] = nsub;
             while (a < e) {                                               // copy up to and including the next FF, drop the 00 behind it
@@ -300,22 +322,22 @@ void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>
         j.nsub = nsub;
         j.groups = (nsub + JD_LANES - 1) / JD_LANES;
         max_groups = std::max(max_groups, j.groups);
-        j.w_entry = carve(work_off, 8 * (size_t)nsub);
-        j.w_exits = carve(work_off, 8 * (size_t)nsub);
-        j.w_count = carve(work_off, 4 * (size_t)nsub);
-        j.w_scan = carve(work_off, 4 * (size_t)nsub);
-        j.w_first = carve(work_off, 4 * (size_t)nsub);
+        j.w_entry = work.add(8 * (size_t)nsub);
+        j.w_exits = work.add(8 * (size_t)nsub);
+        j.w_count = work.add(4 * (size_t)nsub);
+        j.w_scan = work.add(4 * (size_t)nsub);
+        j.w_first = work.add(4 * (size_t)nsub);
         const size_t mcu = pl.components == 3 ? 16 : 8, ysz = (size_t)pl.mcu_cols * mcu * pl.mcu_rows * mcu;
-        j.w_plane[0] = carve(work_off, ysz);
-        j.w_plane[1] = carve(work_off, pl.components == 3 ? ysz / 4 : 0);
-        j.w_plane[2] = carve(work_off, pl.components == 3 ? ysz / 4 : 0);
-        j.o_coef = carve(coef_off, (size_t)j.nblocks * 128);
+        j.w_plane[0] = work.add(ysz);
+        j.w_plane[1] = work.add(pl.components == 3 ? ysz / 4 : 0);
+        j.w_plane[2] = work.add(pl.components == 3 ? ysz / 4 : 0);
+        j.o_coef = coef.add((size_t)j.nblocks * 128);
     }
     const int passes = max_groups + 1;
-    size_t flags_off = work_off;
-    for (FileJob& j : jobs) j.w_flags = carve(work_off, 4 * (size_t)passes);
-    root->jd_work.ensure(work_off);
-    root->jd_coef.ensure(std::max<size_t>(coef_off, 256));
+    const size_t flags_off = work.off;
+    for (FileJob& j : jobs) j.w_flags = work.add(4 * (size_t)passes);
+    root->jd_work.ensure(work.off);
+    root->jd_coef.ensure(std::max<size_t>(coef.off, 256));
     char* wb = (char*)root->jd_work.p;
     JpegDesc* descs = (JpegDesc*)hb;
     for (int k = 0; k < n; ++k) {
@@ -335,8 +357,8 @@ void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>
         d.status = (int*)wb + k;
         d.coef = (short*)((char*)root->jd_coef.p + j.o_coef);
         for (int c = 0; c < 3; ++c) d.plane[c] = (uint8_t*)(wb + j.w_plane[c]);
-        d.out = outs[k];
-        d.pitch = pitches[k];
+        d.out = j.out;
+        d.pitch = j.pitch;
         d.huff = (const JpegHuff*)(db + j.o_huff);
         d.quant = (const unsigned short*)(db + j.o_quant);
         d.W = pl.width;
@@ -357,10 +379,10 @@ void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>
         descs[k] = d;
     }
     if (descs_out) descs_out->assign(descs, descs + n);
-    HIPCHK(hipMemcpyAsync(db, hb, in_off, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(db, hb, in.off, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(wb, 0, align_up(4 * (size_t)n, 256), st));                    // status words
-    HIPCHK(hipMemsetAsync(wb + flags_off, 0, work_off - flags_off, st));                // pass flags
-    HIPCHK(hipMemsetAsync(root->jd_coef.p, 0, std::max<size_t>(coef_off, 256), st));
+    HIPCHK(hipMemsetAsync(wb + flags_off, 0, work.off - flags_off, st));                // pass flags
+    HIPCHK(hipMemsetAsync(root->jd_coef.p, 0, std::max<size_t>(coef.off, 256), st));
     const JpegDesc* dd = (const JpegDesc*)db;
     for (int pass = 0; pass < passes; ++pass) HIPCHK(launch_jd_sync(dd, n, max_groups, pass, st));
     HIPCHK(launch_jd_scan(dd, n, st));
@@ -371,35 +393,6 @@ void jpeg_run(bbocr_ctx* root, const uint8_t* const* files, std::vector<FileJob>
     dev_status.assign((size_t)n, 0);
     HIPCHK(hipMemcpyAsync(dev_status.data(), wb, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-}
-
-// entry points outside the call slots: errors reported like every other entry point's, the stream drained when a call fails
-template <typename F> int jpeg_guarded(bbocr_ctx* root, F&& f) {
-    if (!root) return BBOCR_ERR_ARG;
-    auto set_err = [&](const std::string& m) {
-        std::lock_guard<std::mutex> lk(root->pool_mu);
-        root->err = m;
-    };
-    try {
-        HIPCHK(hipSetDevice(root->cfg.device));
-        std::lock_guard<std::mutex> lk(root->jpeg_mu);
-        try {
-            jpeg_stream_ready(root);
-            HIPCHK(hipStreamSynchronize(nullptr));             // what the caller queued on the default stream (torch's allocations and fills)
-            f();
-            return BBOCR_OK;
-        } catch (...) {
-            if (root->jpeg_stream) (void)hipStreamSynchronize(root->jpeg_stream);
-            (void)hipGetLastError();
-            throw;
-        }
-    } catch (const StatusError& se) {
-        set_err(se.msg);
-        return se.code;
-    } catch (const std::exception& ex) {
-        set_err(ex.what());
-        return BBOCR_ERR_INTERNAL;
-    }
 }
 
 }  // namespace
@@ -418,102 +411,79 @@ int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* pla
 
 int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, uint8_t* const* dev_out,
                       const long long* pitches, int* status) {
-    return jpeg_guarded(ctx, [&] {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
         if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
         if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
-        const int px = layout == BBOCR_PAGE_YCBCR4 ? 4 : 3;
-        std::vector<FileJob> jobs;
-        std::vector<int> which;
-        std::vector<const uint8_t*> fs;
-        std::vector<uint8_t*> outs;
-        std::vector<long long> ps;
-        jobs.reserve((size_t)n);
-        for (int k = 0; k < n; ++k) {
-            status[k] = BBOCR_ERR_ARG;
-            if (!files[k] || !dev_out[k] || bytes[k] >= ((size_t)1 << 28)) continue;
-            FileJob j;
-            if (jpeg_parse(files[k], bytes[k], j.ps, true) != BBOCR_JPEG_OK) continue;      // the caller plans first: a refused file is its error
-            if (pitches[k] < (long long)j.ps.plan.width * (j.ps.plan.components == 3 ? px : 1)) continue;
-            jobs.push_back(std::move(j));
-            which.push_back(k);
-            fs.push_back(files[k]);
-            outs.push_back(dev_out[k]);
-            ps.push_back(pitches[k]);
-        }
+        std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            j.out = dev_out[j.k];
+            j.pitch = pitches[j.k];
+            return j.out && j.pitch >= (long long)pl.width * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY);
+        });
         if (jobs.empty()) return;
-        std::vector<int> st;
-        jpeg_run(ctx, fs.data(), jobs, JD_SUBSEQ_BITS, outs.data(), ps.data(), px, st);
-        for (size_t i = 0; i < which.size(); ++i) status[which[i]] = st[i] ? BBOCR_ERR_DATA : BBOCR_OK;
+        std::vector<int> ds;
+        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, page_px_bytes(layout), ds);
+        jpeg_report(jobs, ds, status);
     });
 }
 
 int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dev_out, const long long* pitches,
                       int* status) {
-    return jpeg_guarded(ctx, [&] {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
         if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
-        std::vector<FileJob> jobs;
-        std::vector<int> which;
-        std::vector<const uint8_t*> fs;
-        std::vector<uint8_t*> outs;
-        std::vector<long long> ps;
-        std::vector<size_t> offs;
-        jobs.reserve((size_t)n);
-        size_t page_bytes = 0;
-        for (int k = 0; k < n; ++k) {
-            status[k] = BBOCR_ERR_ARG;
-            if (!files[k] || !dev_out[k] || bytes[k] >= ((size_t)1 << 28)) continue;
-            FileJob j;
-            if (jpeg_parse(files[k], bytes[k], j.ps, true) != BBOCR_JPEG_OK) continue;
+        // the un-oriented decodes go to jd_page: Pillow's padded pixels (a dword per pixel) or the grey samples, tight rows
+        auto decoded = [](const bbocr_jpeg_plan& pl) { return pl.components == 3 ? PAGE_YCC4 : PAGE_GRAY; };
+        Carve pages;
+        std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
             const bbocr_jpeg_plan& pl = j.ps.plan;
-            if (pitches[k] < 3LL * (pl.orientation >= 5 ? pl.height : pl.width)) continue;
-            // the un-oriented decode: Pillow's padded pixels (a dword per pixel) or the grey samples, tight rows
-            ps.push_back((long long)pl.width * (pl.components == 3 ? 4 : 1));
-            offs.push_back(page_bytes);
-            page_bytes = align_up(page_bytes + (size_t)ps.back() * (size_t)pl.height, 256);
-            jobs.push_back(std::move(j));
-            which.push_back(k);
-            fs.push_back(files[k]);
-        }
+            if (!dev_out[j.k] || pitches[j.k] < (long long)page_px_bytes(PAGE_BGR) * (pl.orientation >= 5 ? pl.height : pl.width)) return false;
+            j.pitch = (long long)pl.width * page_px_bytes(decoded(pl));
+            j.o_page = pages.add((size_t)j.pitch * (size_t)pl.height);
+            return true;
+        });
         if (jobs.empty()) return;
-        ctx->jd_page.ensure(page_bytes);
-        for (size_t o : offs) outs.push_back((uint8_t*)ctx->jd_page.p + o);
-        std::vector<int> st;
-        jpeg_run(ctx, fs.data(), jobs, JD_SUBSEQ_BITS, outs.data(), ps.data(), 4, st);
-        for (size_t i = 0; i < which.size(); ++i) {
-            const int k = which[i];
-            status[k] = st[i] ? BBOCR_ERR_DATA : BBOCR_OK;
-            if (st[i]) continue;
-            const bbocr_jpeg_plan& pl = jobs[i].ps.plan;
-            HIPCHK(launch_page_orient(outs[i], pl.height, pl.width, (size_t)ps[i], pl.components == 3 ? TH_YCC4 : TH_GRAY, pl.orientation, TH_BGR,
-                                      dev_out[k], (size_t)pitches[k], ctx->jpeg_stream));
+        ctx->jd_page.ensure(pages.off);
+        for (FileJob& j : jobs) j.out = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
+        std::vector<int> ds;
+        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, page_px_bytes(PAGE_YCC4), ds);
+        jpeg_report(jobs, ds, status);
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            const FileJob& j = jobs[i];
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            if (ds[i]) continue;
+            HIPCHK(launch_page_orient(j.out, pl.height, pl.width, (size_t)j.pitch, decoded(pl), pl.orientation, PAGE_BGR, dev_out[j.k],
+                                      (size_t)pitches[j.k], st));
         }
-        HIPCHK(hipStreamSynchronize(ctx->jpeg_stream));
+        HIPCHK(hipStreamSynchronize(st));
     });
 }
 
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status) {
-    return jpeg_guarded(ctx, [&] {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
         if (!file || !dev_dst || stage < 0 || stage > 3 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
         const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
         if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
-        std::vector<FileJob> jobs(1);
-        if (jpeg_parse(file, bytes, jobs[0].ps, true) != BBOCR_JPEG_OK) fail(BBOCR_ERR_ARG, "the plan refuses this file");
+        int status = 0;
+        std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            const size_t pix = (size_t)pl.width * pl.height * pl.components;
+            if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
+            ctx->jd_stage.ensure(pix);                           // the pixels go to a scratch image unless they are the stage's output
+            j.out = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+            j.pitch = (long long)pl.width * pl.components;
+            return true;
+        });
+        if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file");
         const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
         const int C = pl.components;
         const size_t mcu = C == 3 ? 16 : 8, ysz = (size_t)pl.mcu_cols * mcu * pl.mcu_rows * mcu;
-        const size_t pix = (size_t)pl.width * pl.height * C;
-        // the pixels go to a scratch image unless they are the stage's output
-        ctx->jd_stage.ensure(pix);
-        uint8_t* out = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
-        if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
-        const long long pitch = (long long)pl.width * C;
-        std::vector<int> st;
+        std::vector<int> ds;
         std::vector<JpegDesc> descs;
-        jpeg_run(ctx, &file, jobs, S, &out, &pitch, 3, st, &descs);
-        if (file_status) *file_status = st[0] ? BBOCR_ERR_DATA : BBOCR_OK;
+        jpeg_run(ctx, s, jobs, S, 3, ds, &descs);
+        jpeg_report(jobs, ds, &status);
+        if (file_status) *file_status = status;
         const JpegDesc& d = descs[0];
-        hipStream_t s = ctx->jpeg_stream;
         if (stage == 0) {
             const size_t ns = (size_t)d.nsub;
             if (dst_bytes < ns * 16) fail(BBOCR_ERR_ARG, "destination too small");

@@ -205,8 +205,11 @@ hipError_t launch_ac_rect(const uint32_t* src, uint32_t* tmp, uint32_t* dst, int
 hipError_t launch_ac_components(const uint32_t* bits, int H, int W, int WW, int* label, uint8_t* flag, int* count, int cap, int* boxes, hipStream_t s);
 hipError_t launch_ac_unpack(const uint32_t* bits, const int* label, int H, int W, int WW, uint8_t* dst, hipStream_t s);
 
+// ------------------------------------------------------------------ device pages: rows of packed pixels, the layouts of bbocr.h BBOCR_PAGE_*
+enum : int { PAGE_GRAY = 0, PAGE_BGR = 1, PAGE_RGB = 2, PAGE_YCC4 = 3, PAGE_YCC3 = 4 };
+__host__ __device__ constexpr int page_px_bytes(int layout) { return layout == PAGE_GRAY ? 1 : (layout == PAGE_YCC4 ? 4 : 3); }
+
 // ------------------------------------------------------------------ OCR-input thumbnail + JPEG round trip (thumb.hip), enhanced_extractor.py:486-512
-enum : int { TH_GRAY = 0, TH_BGR = 1, TH_RGB = 2, TH_YCC4 = 3, TH_YCC3 = 4 };   // bbocr.h BBOCR_PAGE_*
 constexpr int TH_PRECISION_BITS = 22;                                             // Pillow Resample.c, 8 bpc
 struct ThQuant { unsigned short q[2][64]; };                                       // luminance, chrominance (natural order)
 hipError_t launch_th_reduce(const uint8_t* src, size_t pitch, int layout, int H, int W, int fx, int fy, uint8_t* dst, int rh, int rw, int C,
@@ -223,7 +226,7 @@ hipError_t launch_th_direct(const uint8_t* src, size_t pitch, int layout, int H,
 
 // ------------------------------------------------------------------ EXIF orientation + colour order of a page (orient.hip): cv2.imread's last step
 constexpr int ORIENT_TILE = 64;                                // pixels per tile edge (bb_ocr_amd.preprocess.ORIENT_TILE: the tests' shapes)
-bool page_orient_pair_ok(int layout, int dst_layout);          // BGR / RGB from every TH_* layout, GRAY from GRAY
+bool page_orient_pair_ok(int layout, int dst_layout);          // BGR / RGB from every PAGE_* layout, GRAY from GRAY
 // src [H,W] pixels of `layout`, rows `pitch` apart -> dst in `dst_layout`, [H,W] (orientation 1-4) or [W,H] (5-8), rows `dst_pitch` apart
 hipError_t launch_page_orient(const uint8_t* src, int H, int W, size_t pitch, int layout, int orientation, int dst_layout, uint8_t* dst,
                               size_t dst_pitch, hipStream_t s);

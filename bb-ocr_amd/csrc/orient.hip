@@ -28,10 +28,8 @@ struct OrientArgs {
     int tiles_minor;                                            // tiles along the DESTINATION's rows: consecutive workgroups are neighbours there
 };
 
-template <int LAYOUT> __device__ __forceinline__ constexpr int src_bytes() { return LAYOUT == TH_GRAY ? 1 : (LAYOUT == TH_YCC4 ? 4 : 3); }
-
 template <int LAYOUT, int DST> __global__ void __launch_bounds__(256) page_orient_kernel(const OrientArgs a) {
-    constexpr int SB = src_bytes<LAYOUT>(), DC = DST == TH_GRAY ? 1 : 3;
+    constexpr int SB = page_px_bytes(LAYOUT), DC = page_px_bytes(DST);
     __shared__ __attribute__((aligned(16))) uint8_t raw[OR_T * OR_RAW_PITCH];
     __shared__ __attribute__((aligned(16))) uint8_t out[OR_T * OR_OUT_PITCH];
     const int t = threadIdx.x;
@@ -89,11 +87,11 @@ template <int LAYOUT, int DST> __global__ void __launch_bounds__(256) page_orien
         if (r >= th || c >= tw) continue;
         const uint8_t* q = raw + r * OR_RAW_PITCH + ((sa0 + r * sp3) & 3) + c * SB;
         uint8_t px[3];                                          // R, G, B (gray: the sample three times)
-        if (LAYOUT == TH_GRAY) {
+        if (LAYOUT == PAGE_GRAY) {
             px[0] = px[1] = px[2] = q[0];
-        } else if (LAYOUT == TH_RGB) {
+        } else if (LAYOUT == PAGE_RGB) {
             px[0] = q[0]; px[1] = q[1]; px[2] = q[2];
-        } else if (LAYOUT == TH_BGR) {
+        } else if (LAYOUT == PAGE_BGR) {
             px[0] = q[2]; px[1] = q[1]; px[2] = q[0];
         } else {
             jpeg_ycc_to_rgb(q[0], q[1], q[2], px);
@@ -101,9 +99,9 @@ template <int LAYOUT, int DST> __global__ void __launch_bounds__(256) page_orien
         const int lu = a.swap ? c : r, lv = a.swap ? r : c;
         const int lr = a.fy ? nr - 1 - lu : lu, lc = a.fx ? nc - 1 - lv : lv;
         uint8_t* w = out + lr * OR_OUT_PITCH + ((da0 + lr * dp3) & 3) + lc * DC;
-        if (DST == TH_GRAY) {
+        if (DST == PAGE_GRAY) {
             w[0] = px[0];
-        } else if (DST == TH_RGB) {
+        } else if (DST == PAGE_RGB) {
             w[0] = px[0]; w[1] = px[1]; w[2] = px[2];
         } else {
             w[0] = px[2]; w[1] = px[1]; w[2] = px[0];
@@ -130,8 +128,8 @@ template <int LAYOUT, int DST> __global__ void __launch_bounds__(256) page_orien
 }
 
 template <int LAYOUT> hipError_t orient_dst(const OrientArgs& a, int dst_layout, unsigned grid, hipStream_t s) {
-    if (dst_layout == TH_BGR) hipLaunchKernelGGL((page_orient_kernel<LAYOUT, TH_BGR>), dim3(grid), dim3(256), 0, s, a);
-    else if (dst_layout == TH_RGB) hipLaunchKernelGGL((page_orient_kernel<LAYOUT, TH_RGB>), dim3(grid), dim3(256), 0, s, a);
+    if (dst_layout == PAGE_BGR) hipLaunchKernelGGL((page_orient_kernel<LAYOUT, PAGE_BGR>), dim3(grid), dim3(256), 0, s, a);
+    else if (dst_layout == PAGE_RGB) hipLaunchKernelGGL((page_orient_kernel<LAYOUT, PAGE_RGB>), dim3(grid), dim3(256), 0, s, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -139,8 +137,8 @@ template <int LAYOUT> hipError_t orient_dst(const OrientArgs& a, int dst_layout,
 }  // namespace
 
 bool page_orient_pair_ok(int layout, int dst_layout) {
-    if (layout < TH_GRAY || layout > TH_YCC3) return false;
-    return dst_layout == TH_BGR || dst_layout == TH_RGB || (dst_layout == TH_GRAY && layout == TH_GRAY);
+    if (layout < PAGE_GRAY || layout > PAGE_YCC3) return false;
+    return dst_layout == PAGE_BGR || dst_layout == PAGE_RGB || (dst_layout == PAGE_GRAY && layout == PAGE_GRAY);
 }
 
 hipError_t launch_page_orient(const uint8_t* src, int H, int W, size_t pitch, int layout, int orientation, int dst_layout, uint8_t* dst,
@@ -154,15 +152,15 @@ hipError_t launch_page_orient(const uint8_t* src, int H, int W, size_t pitch, in
     a.tiles_minor = a.swap ? tiles_y : tiles_x;
     const unsigned grid = (unsigned)tiles_x * (unsigned)tiles_y;
     switch (layout) {
-        case TH_GRAY:
-            if (dst_layout == TH_GRAY) {
-                hipLaunchKernelGGL((page_orient_kernel<TH_GRAY, TH_GRAY>), dim3(grid), dim3(256), 0, s, a);
+        case PAGE_GRAY:
+            if (dst_layout == PAGE_GRAY) {
+                hipLaunchKernelGGL((page_orient_kernel<PAGE_GRAY, PAGE_GRAY>), dim3(grid), dim3(256), 0, s, a);
                 return hipGetLastError();
             }
-            return orient_dst<TH_GRAY>(a, dst_layout, grid, s);
-        case TH_BGR: return orient_dst<TH_BGR>(a, dst_layout, grid, s);
-        case TH_RGB: return orient_dst<TH_RGB>(a, dst_layout, grid, s);
-        case TH_YCC4: return orient_dst<TH_YCC4>(a, dst_layout, grid, s);
-        default: return orient_dst<TH_YCC3>(a, dst_layout, grid, s);
+            return orient_dst<PAGE_GRAY>(a, dst_layout, grid, s);
+        case PAGE_BGR: return orient_dst<PAGE_BGR>(a, dst_layout, grid, s);
+        case PAGE_RGB: return orient_dst<PAGE_RGB>(a, dst_layout, grid, s);
+        case PAGE_YCC4: return orient_dst<PAGE_YCC4>(a, dst_layout, grid, s);
+        default: return orient_dst<PAGE_YCC3>(a, dst_layout, grid, s);
     }
 }

@@ -151,14 +151,8 @@ ThCoef thumb_coeffs(bbocr_ctx* c, const ThPlan& p) {
 // so running it anyway changes no pixel
 bool th_vertical_first(const ThPlan& p) { return (long long)p.rh > 100LL * p.rw; }
 
-int layout_bytes(int layout) { return layout == TH_GRAY ? 1 : (layout == TH_YCC4 ? 4 : 3); }
-
 void th_check(const void* src, int H, int W, long long pitch, int layout, int max_dim, int quality) {
-    if (!src) fail(BBOCR_ERR_ARG, "null device pointer");
-    if (H < 1 || W < 1) fail(BBOCR_ERR_ARG, "bad image shape");
-    if (layout < TH_GRAY || layout > TH_YCC3) fail(BBOCR_ERR_ARG, "layout must be one of BBOCR_PAGE_*");
-    if (pitch < (long long)W * layout_bytes(layout)) fail(BBOCR_ERR_ARG, "row pitch smaller than a row");
-    if ((long long)H * W >= (1LL << 30)) fail(BBOCR_ERR_ARG, "image too large");
+    check_page({src, H, W, pitch, layout});
     if (max_dim < 1) fail(BBOCR_ERR_ARG, "max_dim must be >= 1");
     if (quality > 100) fail(BBOCR_ERR_ARG, "quality must be <= 100");
 }
@@ -168,20 +162,18 @@ struct ThWork {
     uint8_t *rgb, *reduced, *hpass, *resized, *yp, *cbp, *crp;
 };
 ThWork th_work(bbocr_ctx* c, int H, int W, int layout, const ThPlan& p, int rows, bool thumb, int jh, int jw) {
-    const int C = layout == TH_GRAY ? 1 : 3;
-    const bool ycc = layout == TH_YCC4 || layout == TH_YCC3;
+    const int C = layout == PAGE_GRAY ? 1 : 3;
+    const bool ycc = layout == PAGE_YCC4 || layout == PAGE_YCC3;
     const size_t hp = (size_t)((jh + 15) / 16) * 16, wp = (size_t)((jw + 15) / 16) * 16;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_rgb = carve(ycc && thumb ? (size_t)H * W * 3 : 0);
-    const size_t o_red = carve(thumb && (p.fx > 1 || p.fy > 1) ? (size_t)p.rh * p.rw * C : 0);
-    const size_t o_h = carve(thumb ? std::max((size_t)rows * p.ow, (size_t)p.oh * p.rw) * C : 0);
-    const size_t o_res = carve(thumb ? (size_t)p.oh * p.ow * C : 0);
-    const size_t o_y = carve(hp * wp), o_cb = carve(hp * wp / 4), o_cr = carve(hp * wp / 4);
-    c->arena.buf.ensure(off);
-    char* b = (char*)c->arena.buf.p;
-    return ThWork{(uint8_t*)(b + o_rgb), (uint8_t*)(b + o_red), (uint8_t*)(b + o_h), (uint8_t*)(b + o_res), (uint8_t*)(b + o_y), (uint8_t*)(b + o_cb),
-                  (uint8_t*)(b + o_cr)};
+    Carve cv;
+    const size_t o_rgb = cv.add(ycc && thumb ? (size_t)H * W * 3 : 0);
+    const size_t o_red = cv.add(thumb && (p.fx > 1 || p.fy > 1) ? (size_t)p.rh * p.rw * C : 0);
+    const size_t o_h = cv.add(thumb ? std::max((size_t)rows * p.ow, (size_t)p.oh * p.rw) * C : 0);
+    const size_t o_res = cv.add(thumb ? (size_t)p.oh * p.ow * C : 0);
+    const size_t o_y = cv.add(hp * wp), o_cb = cv.add(hp * wp / 4), o_cr = cv.add(hp * wp / 4);
+    c->arena.buf.ensure(cv.off);
+    auto at = [b = c->arena.buf.p](size_t o) { return Carve::at<uint8_t>(b, o); };
+    return ThWork{at(o_rgb), at(o_red), at(o_h), at(o_res), at(o_y), at(o_cb), at(o_cr)};
 }
 
 // Enqueues the JPEG round trip of an RGB (C 3) or gray (C 1) page; ycc != null: the upsampled triple instead of rgb / gray
@@ -196,18 +188,18 @@ void th_jpeg(bbocr_ctx* c, const ThWork& w, const uint8_t* src, size_t pitch, in
 
 // Enqueues reduce + resample of the page into w.resized (C channels, tight rows); returns C
 int th_resize(bbocr_ctx* c, const ThWork& w, const uint8_t* src, size_t pitch, int layout, int H, int W, const ThPlan& p, const ThCoef& k) {
-    const int C = layout == TH_GRAY ? 1 : 3;
-    if (layout == TH_YCC4 || layout == TH_YCC3) {
+    const int C = layout == PAGE_GRAY ? 1 : 3;
+    if (layout == PAGE_YCC4 || layout == PAGE_YCC3) {
         HIPCHK(launch_th_direct(src, pitch, layout, H, W, w.rgb, nullptr, c->stream));
         src = w.rgb;
         pitch = (size_t)W * 3;
-        layout = TH_RGB;
+        layout = PAGE_RGB;
     }
     if (p.fx > 1 || p.fy > 1) {
         HIPCHK(launch_th_reduce(src, pitch, layout, H, W, p.fx, p.fy, w.reduced, p.rh, p.rw, C, c->stream));
         src = w.reduced;
         pitch = (size_t)p.rw * C;
-        layout = C == 1 ? TH_GRAY : TH_RGB;
+        layout = C == 1 ? PAGE_GRAY : PAGE_RGB;
     }
     if (th_vertical_first(p)) {                                  // the vertical pass runs on the source bytes (per channel, any order)
         HIPCHK(launch_th_resample_v(src, pitch, 0, p.rw * C, p.oh, k.bv, k.kv, k.ksv, w.hpass, (size_t)p.rw * C, c->stream));
@@ -279,7 +271,7 @@ int bbocr_ocr_thumbnail(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, lo
         const ThWork w = th_work(ctx, H, W, layout, p, k.y1 - k.y0, true, p.oh, p.ow);
         const int C = th_resize(ctx, w, dev_src, (size_t)pitch, layout, H, W, p, k);
         if (quality > 0) th_jpeg(ctx, w, w.resized, (size_t)p.ow * C, C, p.oh, p.ow, quality, dev_rgb, dev_gray, nullptr);
-        else HIPCHK(launch_th_direct(w.resized, (size_t)p.ow * C, C == 1 ? TH_GRAY : TH_RGB, p.oh, p.ow, dev_rgb, dev_gray, ctx->stream));
+        else HIPCHK(launch_th_direct(w.resized, (size_t)p.ow * C, C == 1 ? PAGE_GRAY : PAGE_RGB, p.oh, p.ow, dev_rgb, dev_gray, ctx->stream));
         slot_sync(ctx, ctx->stream);
     });
 }
@@ -289,7 +281,7 @@ int bbocr_op_thumbnail_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, 
     return guarded(ctx, [&](bbocr_ctx* ctx) {
         th_check(dev_src, H, W, pitch, layout, max_dim, quality);
         if (!dev_dst || !out_h || !out_w || stage < 0 || stage > 2 || (stage == 1 && !dev_gray)) fail(BBOCR_ERR_ARG, "bad arguments");
-        if (stage > 0 && (quality < 1 || (layout != TH_GRAY && layout != TH_RGB))) fail(BBOCR_ERR_ARG, "stages 1 and 2 take a gray or RGB page and a quality");
+        if (stage > 0 && (quality < 1 || (layout != PAGE_GRAY && layout != PAGE_RGB))) fail(BBOCR_ERR_ARG, "stages 1 and 2 take a gray or RGB page and a quality");
         if (stage == 0) {
             const ThPlan p = thumb_plan(H, W, max_dim);
             *out_h = p.oh;
@@ -300,14 +292,14 @@ int bbocr_op_thumbnail_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, 
                 const ThCoef k = thumb_coeffs(ctx, p);
                 const ThWork w = th_work(ctx, H, W, layout, p, k.y1 - k.y0, true, 1, 1);
                 const int C = th_resize(ctx, w, dev_src, (size_t)pitch, layout, H, W, p, k);
-                HIPCHK(launch_th_direct(w.resized, (size_t)p.ow * C, C == 1 ? TH_GRAY : TH_RGB, p.oh, p.ow, dev_dst, nullptr, ctx->stream));
+                HIPCHK(launch_th_direct(w.resized, (size_t)p.ow * C, C == 1 ? PAGE_GRAY : PAGE_RGB, p.oh, p.ow, dev_dst, nullptr, ctx->stream));
             }
         } else {
             *out_h = H;
             *out_w = W;
             const ThPlan p{};
             const ThWork w = th_work(ctx, H, W, layout, p, 0, false, H, W);
-            const int C = layout == TH_GRAY ? 1 : 3;
+            const int C = layout == PAGE_GRAY ? 1 : 3;
             th_jpeg(ctx, w, dev_src, (size_t)pitch, C, H, W, quality, stage == 1 ? dev_dst : nullptr, stage == 1 ? dev_gray : nullptr,
                     stage == 2 ? dev_dst : nullptr);
         }

@@ -14,12 +14,12 @@
 
 namespace {
 
-// channel c (R, G, B) of pixel (y, x) of a page in one of the TH_* layouts
+// channel c (R, G, B) of pixel (y, x) of a page in one of the PAGE_* layouts
 __device__ __forceinline__ int th_px(const uint8_t* __restrict__ src, size_t pitch, int layout, int y, int x, int c) {
     const uint8_t* row = src + (size_t)y * pitch;
     switch (layout) {
-        case TH_GRAY: return row[x];
-        case TH_BGR: return row[3 * x + 2 - c];
+        case PAGE_GRAY: return row[x];
+        case PAGE_BGR: return row[3 * x + 2 - c];
         default: return row[3 * x + c];
     }
 }
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(64) th_jpeg_mcu_kernel(const uint8_t* __restri
                                                          uint8_t* __restrict__ yp, int wp, uint8_t* __restrict__ cbp, uint8_t* __restrict__ crp) {
     __shared__ int blk[6][64];
     const int t = threadIdx.x, mx = blockIdx.x, my = blockIdx.y;
-    const int layout = C == 1 ? TH_GRAY : TH_RGB;
+    const int layout = C == 1 ? PAGE_GRAY : PAGE_RGB;
     const int nblk = C == 1 ? 4 : 6;
     for (int p = 0; p < 4; ++p) {                              // 256 pixels, edge-replicated beyond the page (expand_right / bottom_edge)
         const int id = t + 64 * p, py = id >> 4, px = id & 15;
@@ -200,8 +200,8 @@ __global__ void __launch_bounds__(256) th_direct_kernel(const uint8_t* __restric
     if (x >= W || y >= H) return;
     const size_t i = (size_t)y * W + x;
     const uint8_t* p = src + (size_t)y * pitch;
-    if (layout == TH_YCC4 || layout == TH_YCC3) {
-        const int s = layout == TH_YCC4 ? 4 : 3;
+    if (layout == PAGE_YCC4 || layout == PAGE_YCC3) {
+        const int s = layout == PAGE_YCC4 ? 4 : 3;
         jpeg_ycc_to_rgb(p[s * x], p[s * x + 1], p[s * x + 2], rgb + 3 * i);
         if (gray) gray[i] = p[s * x];
         return;
@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(256) th_direct_kernel(const uint8_t* __restric
     rgb[3 * i] = (uint8_t)r;
     rgb[3 * i + 1] = (uint8_t)g;
     rgb[3 * i + 2] = (uint8_t)b;
-    if (gray) gray[i] = layout == TH_GRAY ? (uint8_t)r : (uint8_t)((r * 9797 + g * 19234 + b * 3737) >> 15);   // libpng rgb_to_gray
+    if (gray) gray[i] = layout == PAGE_GRAY ? (uint8_t)r : (uint8_t)((r * 9797 + g * 19234 + b * 3737) >> 15);   // libpng rgb_to_gray
 }
 
 dim3 px_grid(int H, int W) { return dim3((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)); }

@@ -19,6 +19,8 @@ import os
 
 import numpy as np
 
+from ._lib import PAGE_BGR, PAGE_GRAY, PAGE_PX_BYTES, PAGE_RGB, PAGE_YCBCR3, PAGE_YCBCR4  # noqa: F401  (re-exported)
+
 LEGACY_STEPS = ["original", "grayscale", "resize(scale_factor=1.5)", "denoise(strength=5)", "increase_contrast(factor=1.3)",
                 "clahe(clip_limit=2.0)", "sharpen(amount=0.2)"]
 STEPS = ["original", "grayscale", "resize(scale_factor=1.5)", "denoise(strength=3)", "increase_contrast(factor=1.9)",
@@ -43,6 +45,36 @@ def exif_orientation(value):
     return int(value) if isinstance(value, int) and 1 <= value <= 8 else 1
 
 
+def page_descriptor(shape, strides, dtype, layouts):
+    """``(H, W, row pitch in bytes, channels)`` of a page given as a tensor's ``shape``, ``strides`` (in elements) and ``dtype``: uint8,
+    ``[H,W]`` or ``[H,W,C]`` with ``H, W >= 1``, ``C`` the bytes per pixel of one of the allowed ``PAGE_*`` ``layouts``, pixels packed along a
+    row, rows at least one row apart (a strided view such as a crop of a larger page qualifies).  ``ValueError`` for anything else."""
+    import torch
+
+    ch = int(shape[2]) if len(shape) == 3 else 1
+    ok = dtype == torch.uint8 and len(shape) in (2, 3) and any(PAGE_PX_BYTES.get(l) == ch for l in layouts)
+    if not ok or shape[0] < 1 or shape[1] < 1 or strides[1] != ch or (len(shape) == 3 and strides[2] != 1) or strides[0] < shape[1] * ch:
+        raise ValueError(f"expected a uint8 page of layout {tuple(layouts)} (BBOCR_PAGE_*) as rows of packed pixels, not {dtype} of shape "
+                         f"{tuple(shape)} / strides {tuple(strides)}")
+    return int(shape[0]), int(shape[1]), int(strides[0]), ch
+
+
+def _on_device(reader, t):
+    if not t.is_cuda or t.device.index != reader.device_index:
+        raise ValueError(f"expected a tensor on {reader.device}")
+
+
+def _page_layout(reader, page_dev, layouts=(PAGE_GRAY, PAGE_BGR)):
+    """``page_descriptor`` of a tensor on the reader's device (by default a gray [H,W] or BGR [H,W,3] page)."""
+    import torch
+
+    if not isinstance(page_dev, torch.Tensor):
+        raise ValueError("expected a uint8 [H,W] or [H,W,C] device tensor")
+    d = page_descriptor(page_dev.shape, page_dev.stride(), page_dev.dtype, layouts)
+    _on_device(reader, page_dev)
+    return d
+
+
 def orient_page_device(reader, page_dev, layout, orientation, dst_layout=None):
     """``bbocr_page_orient`` of a uint8 device page of the given ``PAGE_*`` layout (rows of packed pixels; a strided row pitch is read in
     place): the page in EXIF ``orientation`` (1 .. 8, ``ImageOps.exif_transpose``'s geometry) as ``dst_layout`` -- ``PAGE_BGR`` (default) or
@@ -50,16 +82,7 @@ def orient_page_device(reader, page_dev, layout, orientation, dst_layout=None):
     import torch
 
     dst_layout = PAGE_BGR if dst_layout is None else dst_layout
-    if not isinstance(page_dev, torch.Tensor) or page_dev.dtype != torch.uint8 or page_dev.ndim not in (2, 3):
-        raise ValueError("expected a uint8 [H,W] or [H,W,C] device tensor")
-    if not page_dev.is_cuda or page_dev.device.index != reader.device_index:
-        raise ValueError(f"expected a tensor on {reader.device}")
-    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
-    ch = 1 if page_dev.ndim == 2 else int(page_dev.shape[2])
-    want = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}.get(layout)
-    st = page_dev.stride()
-    if want is None or ch != want or H < 1 or W < 1 or st[1] != ch or (page_dev.ndim == 3 and st[2] != 1) or st[0] < W * ch:
-        raise ValueError(f"page of shape {tuple(page_dev.shape)} / strides {st} does not hold layout {layout}")
+    H, W, pitch, _ = _page_layout(reader, page_dev, (layout,))
     if dst_layout not in (PAGE_BGR, PAGE_RGB) and not (dst_layout == PAGE_GRAY and layout == PAGE_GRAY):
         raise ValueError(f"no conversion from layout {layout} to layout {dst_layout}")
     if not isinstance(orientation, int) or not 1 <= orientation <= 8:
@@ -68,7 +91,7 @@ def orient_page_device(reader, page_dev, layout, orientation, dst_layout=None):
     out = torch.empty((oh, ow) if dst_layout == PAGE_GRAY else (oh, ow, 3), dtype=torch.uint8, device=page_dev.device)
     torch.cuda.current_stream(reader.device_index).synchronize()       # the library runs on its own stream
     rh, rw = C.c_int(), C.c_int()
-    reader._check(reader._lib.bbocr_page_orient(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, int(st[0]), int(layout), int(orientation),
+    reader._check(reader._lib.bbocr_page_orient(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, pitch, int(layout), int(orientation),
                                                 int(dst_layout), C.c_void_p(out.data_ptr()), int(out.stride(0)), C.byref(rh), C.byref(rw)))
     return out
 
@@ -88,17 +111,13 @@ def imread_bgr_device(reader, source):
     and this function do not."""
     from PIL import Image
 
-    from .reader import decode_file_ycc, jpeg_page, jpeg_plan
+    from .reader import JpegPage, _file_bytes, decode_file_ycc, jpeg_plan
 
-    if isinstance(source, (bytes, bytearray)):
-        data = bytes(source)
-    else:
-        with open(os.path.expanduser(os.fspath(source)), "rb") as f:
-            data = f.read()
+    data = _file_bytes(source)
     plan = jpeg_plan(data)
     out = path = None
     if plan.supported:
-        pages, status = reader.imread_jpeg_batch([jpeg_page(data)])
+        pages, status = reader.imread_jpeg_batch([JpegPage(data, plan)])
         if status[0] == 0:
             out, path = pages[0], IMREAD_JPEG
     if out is None:
@@ -180,22 +199,6 @@ def central_edge_crop_box(h, w, percent):
     return (x0, y0, x1, y1)
 
 
-def _page_layout(reader, page_dev):
-    """(H, W, row pitch in bytes, channels) of a uint8 gray [H,W] or BGR [H,W,3] device tensor, strided views included."""
-    import torch
-
-    if not isinstance(page_dev, torch.Tensor) or page_dev.dtype != torch.uint8 or page_dev.ndim not in (2, 3):
-        raise ValueError("expected a uint8 gray [H,W] or BGR [H,W,3] device tensor")
-    if not page_dev.is_cuda or page_dev.device.index != reader.device_index:
-        raise ValueError(f"expected a tensor on {reader.device}")
-    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
-    ch = 1 if page_dev.ndim == 2 else int(page_dev.shape[2])
-    st = page_dev.stride()
-    if ch not in (1, 3) or st[1] != ch or (ch == 3 and st[2] != 1) or H < 1 or W < 1 or st[0] < W * ch:
-        raise ValueError("expected rows of packed pixels (gray, or interleaved BGR) with a row stride of at least one row")
-    return H, W, int(st[0]), ch
-
-
 def auto_crop_box_device(reader, page_dev, margin=128, with_components=False):
     """``_auto_crop_text_region`` (enhanced_extractor.py:239-372) on the device: the crop box ``(x0, y0, x1, y1)`` of a uint8 gray
     [H,W] or BGR [H,W,3] tensor on the reader's device (a strided view such as an edge crop of a larger page is read in place), or None
@@ -220,9 +223,6 @@ def auto_crop_box_device(reader, page_dev, margin=128, with_components=False):
 
 
 # ------------------------------------------------------------------------------------------------ the OCR input itself (:486-512)
-PAGE_GRAY, PAGE_BGR, PAGE_RGB, PAGE_YCBCR4, PAGE_YCBCR3 = 0, 1, 2, 3, 4          # bbocr.h BBOCR_PAGE_*
-
-
 def ocr_thumbnail_rule(image_index=None):
     """(max_dim, JPEG quality) of the extractor's down-scaling step: 1600 / 90 for the cover (``image_index`` None or 0), else 2400 / 95."""
     return (1600, 90) if image_index is None or image_index == 0 else (2400, 95)
@@ -233,21 +233,12 @@ def ocr_thumbnail_device(reader, page_dev, layout, max_dim, quality):
     in place) -> ``(rgb_dev [h,w,3], gray_dev [h,w])``."""
     import torch
 
-    if not isinstance(page_dev, torch.Tensor) or page_dev.dtype != torch.uint8 or page_dev.ndim not in (2, 3):
-        raise ValueError("expected a uint8 [H,W] or [H,W,C] device tensor")
-    if not page_dev.is_cuda or page_dev.device.index != reader.device_index:
-        raise ValueError(f"expected a tensor on {reader.device}")
-    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
-    ch = 1 if page_dev.ndim == 2 else int(page_dev.shape[2])
-    want = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}.get(layout)
-    st = page_dev.stride()
-    if want is None or ch != want or st[1] != ch or (ch > 1 and st[2] != 1) or st[0] < W * ch:
-        raise ValueError(f"page of shape {tuple(page_dev.shape)} / strides {st} does not hold layout {layout}")
+    H, W, pitch, _ = _page_layout(reader, page_dev, (layout,))
     oh, ow = C.c_int(), C.c_int()
     reader._check(reader._lib.bbocr_thumbnail_dims(H, W, int(max_dim), C.byref(oh), C.byref(ow)))
     rgb = torch.empty((oh.value, ow.value, 3), dtype=torch.uint8, device=page_dev.device)
     gray = torch.empty((oh.value, ow.value), dtype=torch.uint8, device=page_dev.device)
-    reader._check(reader._lib.bbocr_ocr_thumbnail(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, int(st[0]), int(layout), int(max_dim),
+    reader._check(reader._lib.bbocr_ocr_thumbnail(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, pitch, int(layout), int(max_dim),
                                                   int(quality), C.c_void_p(rgb.data_ptr()), C.c_void_p(gray.data_ptr()), C.byref(oh),
                                                   C.byref(ow)))
     return rgb, gray

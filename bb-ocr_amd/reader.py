@@ -60,6 +60,21 @@ def _decode_pool():
     return _DECODE_POOL
 
 
+def _file_bytes(source):
+    """The bytes of a file given as a path or as its bytes"""
+    if isinstance(source, (bytes, bytearray)):
+        return bytes(source)
+    with open(os.path.expanduser(os.fspath(source)), "rb") as f:
+        return f.read()
+
+
+def _open_image(source):
+    """``PIL.Image.open`` of a path or of a file's bytes"""
+    from PIL import Image
+
+    return Image.open(io.BytesIO(source)) if isinstance(source, (bytes, bytearray)) else Image.open(os.path.expanduser(str(source)))
+
+
 def decode_file(source, parallel=False):
     """What upstream's path branch holds after ``cv2.imread(path, IMREAD_GRAYSCALE)`` + ``loadImage(path)`` (skimage -> RGB):
     ``(rgb uint8 HWC, gray uint8 HW)``.  ONE stated rule for the gray plane, by container:
@@ -69,18 +84,13 @@ def decode_file(source, parallel=False):
       * every other colour file (OpenCV's PNG reader: ``png_set_rgb_to_gray(1, 0.299, 0.587)``): libpng's truncating
         15-bit sum ``(9797 R + 19234 G + 3737 B) >> 15``, grey pixels unchanged.
     ``source`` is a path or a bytes object holding the file."""
-    from PIL import Image
-
-    def _open():
-        return Image.open(io.BytesIO(source)) if isinstance(source, (bytes, bytearray)) else Image.open(os.path.expanduser(str(source)))
-
-    pil = _open()
+    pil = _open_image(source)
     if pil.format in ("JPEG", "MPO") and pil.mode in ("RGB", "YCbCr"):
         # two libjpeg passes over the same file (RGB, and the Y plane alone).  `parallel` (the single-page call Reader.readtext(path),
         # the reference's own pattern): side by side on two threads -- PIL releases the GIL while it decodes, so the page costs one decode
         # time instead of two (8.9 -> 4.9 ms for 1280x960).  Callers that already decode on a thread pool (extractor_batch) keep it serial.
         def _y_plane():
-            y = _open()
+            y = _open_image(source)
             y.draft("L", y.size)
             return np.ascontiguousarray(y.convert("L"))
 
@@ -122,10 +132,8 @@ def decode_file_ycc(source, padded=False):
     ``padded=True`` (decode pools): the result may be ``uint8 [H,W,4]`` -- Pillow's own pixel storage (Y Cb Cr x), exported without a copy
     through the Arrow C data interface (Pillow >= 11.2 + pyarrow) -- instead of the tight ``[H,W,3]`` that ``tobytes`` assembles while holding
     the interpreter lock (1.3 ms per page: with eight decode threads that serialised copy was what bounded the pool)."""
-    from PIL import Image
-
     try:
-        pil = Image.open(io.BytesIO(source)) if isinstance(source, (bytes, bytearray)) else Image.open(os.path.expanduser(str(source)))
+        pil = _open_image(source)
         if pil.format not in ("JPEG", "MPO") or pil.mode != "RGB":
             return None                                              # greyscale / CMYK / YCCK files and other containers
         if "jfif" not in pil.info and pil.info.get("adobe_transform") != 1:
@@ -172,11 +180,7 @@ def jpeg_plan(data):
 def jpeg_page(source):
     """``JpegPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)."""
     try:
-        if isinstance(source, (bytes, bytearray)):
-            data = bytes(source)
-        else:
-            with open(os.path.expanduser(os.fspath(source)), "rb") as f:
-                data = f.read()
+        data = _file_bytes(source)
         plan = jpeg_plan(data)
         return JpegPage(data, plan) if plan.supported else None
     except Exception:
@@ -577,6 +581,12 @@ class Reader:
                                                   C.c_void_p(gray.data_ptr())))
         return rgb, gray
 
+    @staticmethod
+    def _jpeg_files(pages):
+        """The ``files`` and ``sizes`` arrays of a JPEG batch call (the pages keep their bytes alive)"""
+        n = len(pages)
+        return (C.c_void_p * n)(*[C.cast(C.c_char_p(p.data), C.c_void_p) for p in pages]), (C.c_size_t * n)(*[len(p.data) for p in pages])
+
     def decode_jpeg_batch(self, pages, padded=False):
         """``JpegPage`` s of ONE shape -> ``(batch, status)``: the device tensor ``uint8 [n,H,W,3]`` (``padded``: ``[n,H,W,4]``) of libjpeg's
         YCbCr triples -- what ``pages_from_ycc`` takes -- or ``[n,H,W]`` for 1-component files, decoded by ONE ``bbocr_jpeg_decode`` call
@@ -586,16 +596,15 @@ class Reader:
         if not pages or any(p.shape != pages[0].shape for p in pages):
             raise ValueError("decode_jpeg_batch: pages of one decoded shape")
         H, W, comps = pages[0].shape
-        px = 1 if comps == 1 else (4 if padded else 3)
+        layout = _lib.PAGE_YCBCR4 if padded else _lib.PAGE_YCBCR3
+        px = _lib.PAGE_PX_BYTES[_lib.PAGE_GRAY if comps == 1 else layout]
         t = torch.empty((len(pages), H, W) + ((px,) if comps == 3 else ()), dtype=torch.uint8, device=self.device)
         torch.cuda.current_stream(self.device_index).synchronize()
         n = len(pages)
-        files = (C.c_void_p * n)(*[C.cast(C.c_char_p(p.data), C.c_void_p) for p in pages])
-        sizes = (C.c_size_t * n)(*[len(p.data) for p in pages])
+        files, sizes = self._jpeg_files(pages)
         outs = (C.c_void_p * n)(*[t.data_ptr() + k * H * W * px for k in range(n)])
         pitches = (C.c_longlong * n)(*([W * px] * n))
         status = (C.c_int * n)()
-        layout = 3 if padded else 4                               # BBOCR_PAGE_YCBCR4 / BBOCR_PAGE_YCBCR3
         self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
         return t, list(status)
 
@@ -613,8 +622,7 @@ class Reader:
             outs.append(torch.empty((W, H, 3) if p.orientation >= 5 else (H, W, 3), dtype=torch.uint8, device=self.device))
         torch.cuda.current_stream(self.device_index).synchronize()
         n = len(pages)
-        files = (C.c_void_p * n)(*[C.cast(C.c_char_p(p.data), C.c_void_p) for p in pages])
-        sizes = (C.c_size_t * n)(*[len(p.data) for p in pages])
+        files, sizes = self._jpeg_files(pages)
         ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
         pitches = (C.c_longlong * n)(*[t.shape[1] * 3 for t in outs])
         status = (C.c_int * n)()

@@ -261,7 +261,8 @@ int bbocr_op_ycc_to_rgb(bbocr_ctx* ctx, const uint8_t* dev_ycc, size_t npix, int
 /* n separately allocated host pages of bytes_each bytes (the arrays a decode pool returns) -> one device buffer [n][bytes_each], copied
  * inside ONE call: a Python host releases its interpreter lock once per batch instead of once per page, and needs no host-side
  * concatenation of the pages (236 MB for 64 pages of 1280x960).  pixel_stride above: 3 = tight triples, 4 = Pillow's own 4-byte pixel
- * storage (Y Cb Cr x) uploaded as it is. */
+ * storage (Y Cb Cr x) uploaded as it is.  Every page pointer is checked before the first copy is queued: a call refused with
+ * BBOCR_ERR_ARG has written nothing to dev_dst. */
 int bbocr_upload_pages(bbocr_ctx* ctx, const void* const* host_pages, int n, size_t bytes_each, void* dev_dst);
 /* recogniser inputs for explicit boxes of ONE gray page: fills crops bf16 [n,64,imgW] (in box order); returns their count in *n_out.
  * contrast != 0 applies adjust_contrast_grey first.  mode 0: the boxes whose own padded width is imgW (Reader.recognize's per-box

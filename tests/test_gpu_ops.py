@@ -147,10 +147,15 @@ def test_jpeg_colour_conversion_on_device_is_libjpegs(reader):
     with pytest.raises(ValueError):
         reader._to_dev([])
     import ctypes as C_
-    dst = torch.empty((2, 16), dtype=torch.uint8, device="cuda")
+    dst = torch.full((2, 16), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
     ptrs = (C_.c_void_p * 2)(tight[0].ctypes.data, None)                       # a null page: status code and message, no fault
     assert reader._lib.bbocr_upload_pages(reader._h, ptrs, 2, 16, C_.c_void_p(dst.data_ptr())) == -1
     assert b"null page" in reader._lib.bbocr_last_error(reader._h)
+    assert bool((dst == 0xA5).all())                                           # every page is checked before the first copy is queued
+    ptrs = (C_.c_void_p * 2)(tight[0].ctypes.data, tight[1].ctypes.data)       # the same two pages, both valid: both arrive
+    assert reader._lib.bbocr_upload_pages(reader._h, ptrs, 2, 16, C_.c_void_p(dst.data_ptr())) == 0
+    assert np.array_equal(dst.cpu().numpy(), np.stack([tight[0].reshape(-1)[:16], tight[1].reshape(-1)[:16]]))
 
 
 def test_ctc_matches_oracle(reader):
