@@ -136,6 +136,12 @@ PROTOTYPES = {
     "bbocr_page_orient": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int)]),
     "bbocr_op_jpeg_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_jpeg_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bbocr_host_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bbocr_jpeg_encode": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t,
+                                    C.POINTER(C.c_size_t)]),
+    "bbocr_op_jpeg_encode_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
 }
 
 _lib = None

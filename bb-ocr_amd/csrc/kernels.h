@@ -224,6 +224,67 @@ hipError_t launch_th_upsample(const uint8_t* yp, int wp, const uint8_t* cbp, con
                               uint8_t* gray, uint8_t* ycc, hipStream_t s);
 hipError_t launch_th_direct(const uint8_t* src, size_t pitch, int layout, int H, int W, uint8_t* rgb, uint8_t* gray, hipStream_t s);
 
+// ------------------------------------------------------------------ baseline JPEG encoder (jpegenc.hip): the file Pillow saves, from a device page
+// Passes: coefficients (one MCU per wavefront) -> bit length per block + scan inside tiles of JE_TILE blocks -> scan of the tile sums
+// -> packing -> 0xFF count per tile of JE_STUFF_TILE bytes -> scan of those -> scatter with the stuffed zero bytes.
+constexpr int JE_TILE = 256;                                   // blocks per workgroup of the size and packing passes
+constexpr int JE_STUFF_TILE = 2048;                            // scan bytes per workgroup of the stuffing passes
+constexpr int JE_BLOCK_MAX_BITS = 22 + 63 * 26;                // DC: 11-bit code + 11 bits; 63 x (16-bit code + 10 bits)
+struct JeHuff { uint32_t dc[2][16], ac[2][256]; };             // luminance, chrominance: (code << 5) | length per symbol, 0 = no code
+struct JeStdTable { unsigned char bits[16], vals[162]; int n; };
+// ITU T.81 Annex K.3, in the order libjpeg writes them: DC luminance, AC luminance, DC chrominance, AC chrominance
+constexpr JeStdTable JE_STD[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D},
+     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1,
+      0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52, 0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25, 0x26,
+      0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56,
+      0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85,
+      0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA,
+      0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6,
+      0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9,
+      0xFA}, 162},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
+     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+      0x91, 0xA1, 0xB1, 0xC1, 0x09, 0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25, 0xF1, 0x17, 0x18, 0x19,
+      0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55,
+      0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8,
+      0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4,
+      0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9,
+      0xFA}, 162},
+};
+constexpr JeHuff je_std_huff() {                               // Annex C: codes of increasing length, counted up within a length
+    JeHuff h{};
+    for (int t = 0; t < 4; ++t) {
+        uint32_t* out = (t & 1) ? h.ac[t >> 1] : h.dc[t >> 1];
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int i = 0; i < JE_STD[t].bits[len - 1]; ++i) out[JE_STD[t].vals[k++]] = (code++ << 5) | (uint32_t)len;
+            code <<= 1;
+        }
+    }
+    return h;
+}
+inline int je_blocks(int H, int W, int components) {            // blocks in the scan
+    return components == 1 ? ((H + 7) / 8) * ((W + 7) / 8) : 6 * ((H + 15) / 16) * ((W + 15) / 16);
+}
+// coef [blocks][64] int16 zig-zag, blocks in MCU order; `components` 1 (a gray page) or 3 (any layout; a gray page: zero chroma blocks)
+hipError_t launch_je_coef(const uint8_t* src, size_t pitch, int layout, int components, int H, int W, const ThQuant& q, short* coef, hipStream_t s);
+// local [n]: bit offset of block b inside its tile of JE_TILE blocks; tile_bits [tiles + 1]: the tiles' bit counts (the scan below turns
+// them into offsets)
+hipError_t launch_je_sizes(const short* coef, int n, int components, unsigned int* local, unsigned long long* tile_bits, hipStream_t s);
+// v [n + 1]: exclusive prefix sum in place, the total in v[n]; one workgroup
+hipError_t launch_je_scan(unsigned long long* v, int n, hipStream_t s);
+hipError_t launch_je_offsets(const unsigned int* local, const unsigned long long* tile_off, int n, long long* out, hipStream_t s);   // [n + 1]
+// words: zeroed, ceil(total bits / 32) words; the last byte of the scan is filled with 1-bits
+hipError_t launch_je_pack(const short* coef, int n, int components, const unsigned int* local, const unsigned long long* tile_off, uint32_t* words,
+                          hipStream_t s);
+hipError_t launch_je_ff_count(const uint8_t* scan, long long bytes, unsigned long long* tile_ff, hipStream_t s);       // [tiles + 1]
+hipError_t launch_je_stuff(const uint8_t* scan, long long bytes, const unsigned long long* tile_off, uint8_t* out, hipStream_t s);
+
 // ------------------------------------------------------------------ EXIF orientation + colour order of a page (orient.hip): cv2.imread's last step
 constexpr int ORIENT_TILE = 64;                                // pixels per tile edge (bb_ocr_amd.preprocess.ORIENT_TILE: the tests' shapes)
 bool page_orient_pair_ok(int layout, int dst_layout);          // BGR / RGB from every PAGE_* layout, GRAY from GRAY

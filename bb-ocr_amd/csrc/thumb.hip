@@ -77,36 +77,6 @@ __global__ void __launch_bounds__(256) th_resample_v_kernel(const uint8_t* __res
     dst[(size_t)y * dpitch + e] = th_clip8(ss);
 }
 
-// ---- libjpeg's ISLOW transforms (jfdctint.c here; the constants, jidctint.c and the fancy upsampling are in jpeg_dev.h)
-// one 1-D forward pass over v[0], v[s], ..., v[7 s]
-__device__ __forceinline__ void fdct8(int* v, int s, bool first) {
-    const long long t0 = v[0] + v[7 * s], t7 = v[0] - v[7 * s], t1 = v[s] + v[6 * s], t6 = v[s] - v[6 * s];
-    const long long t2 = v[2 * s] + v[5 * s], t5 = v[2 * s] - v[5 * s], t3 = v[3 * s] + v[4 * s], t4 = v[3 * s] - v[4 * s];
-    const long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    const int sh = first ? CB - P1 : CB + P1;
-    v[0] = (int)(first ? (t10 + t11) << P1 : dsc(t10 + t11, P1));
-    v[4 * s] = (int)(first ? (t10 - t11) << P1 : dsc(t10 - t11, P1));
-    long long z1 = (t12 + t13) * F0541;
-    v[2 * s] = (int)dsc(z1 + t13 * F0765, sh);
-    v[6 * s] = (int)dsc(z1 - t12 * F1847, sh);
-    z1 = t4 + t7;
-    long long z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const long long z5 = (z3 + z4) * F1175;
-    z1 *= -F0899;
-    z2 *= -F2562;
-    z3 = z3 * -F1961 + z5;
-    z4 = z4 * -F0390 + z5;
-    v[7 * s] = (int)dsc(t4 * F0298 + z1 + z3, sh);
-    v[5 * s] = (int)dsc(t5 * F2053 + z2 + z4, sh);
-    v[3 * s] = (int)dsc(t6 * F3072 + z2 + z3, sh);
-    v[s] = (int)dsc(t7 * F1501 + z1 + z4, sh);
-}
-
-// jccolor.c::rgb_ycc_convert
-__device__ __forceinline__ int th_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
-__device__ __forceinline__ int th_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
-__device__ __forceinline__ int th_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
-
 // One MCU per workgroup of 64 lanes (one wavefront).  Blocks 0-3 hold Y (2x2), 4 Cb, 5 Cr; a gray page (C == 1: R = G = B, hence
 // Cb = Cr = 128 exactly, whose blocks come back as 128 everywhere) runs the four Y blocks only.
 __global__ void __launch_bounds__(64) th_jpeg_mcu_kernel(const uint8_t* __restrict__ src, size_t pitch, int C, int H, int W, ThQuant q,

@@ -118,25 +118,31 @@ def _ocr_input_device(reader, image_path, image_index=None, decode_once=True, de
 
 
 def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, on_device=False,
-                  device_decode=False):
+                  device_decode=False, applied=None):
     """The page ``extract_text_with_ocr`` would hand to the down-scaling step (:425-485), as a host array: decoded like ``cv2.imread``
     (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
     final crop comes back.  A step that returns None in the reference leaves the page as it was.  ``on_device=True``: the crop stays on
     the card, as a (possibly strided) view of the device page.  ``device_decode=True``: the page is read by
-    ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels)."""
+    ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels).
+    ``applied``: a list that receives the names of the steps that changed the page (where it stays empty the reference goes on with the
+    original file)."""
     from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, imread_bgr_device, preprocess_bgr_device
 
+    applied = [] if applied is None else applied
     page = imread_bgr_device(reader, image_path) if device_decode else reader._to_dev(_imread_bgr(image_path))
     if use_preprocessing:
         page = preprocess_bgr_device(reader, page)
+        applied.append("preprocess")
     if edge_crop_percent > 0.0:
         b = central_edge_crop_box(page.shape[0], page.shape[1], edge_crop_percent)
         if b is not None:
             page = page[b[1]:b[3], b[0]:b[2]]
+            applied.append("edge_crop")
     if crop_for_ocr:
         b = auto_crop_box_device(reader, page, crop_margin)
         if b is not None:
             page = page[b[1]:b[3], b[0]:b[2]]
+            applied.append("auto_crop")
     if on_device:
         return page
     return page.contiguous().cpu().numpy()
@@ -440,3 +446,66 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     _device_stage(reader, batches, texts, readtext_kw)
     worker.join()
     return texts
+
+
+# ------------------------------------------------------------------------------------------------ the model input (:763-813)
+def _model_image_plain(reader, path, max_dim, quality, device_decode):
+    """``_encode_image_for_model`` of the file itself: ``Image.open`` does not transpose, and carries the file's comment into the JPEG it
+    saves.  The pixels reach the card as the file's bytes (``device_decode`` and the device decoder takes them) or as Pillow's RGB decode;
+    a file the device decoder refuses or reports damaged takes ``model_image_host``."""
+    from PIL import Image
+
+    from .preprocess import PAGE_GRAY, PAGE_RGB, PAGE_YCBCR4, model_image_device, model_image_host
+
+    if device_decode:
+        page = _jpg_page(path)
+        if page is not None:
+            comment = Image.open(path).info.get("comment")                # headers only
+            dev, status = reader.decode_jpeg_batch([page[1]], padded=True)
+            if status[0] == 0:
+                return model_image_device(reader, dev[0], PAGE_GRAY if dev.ndim == 3 else PAGE_YCBCR4, max_dim, quality, comment)
+        return model_image_host(path, max_dim, quality)
+    img = Image.open(path)
+    rgb = np.asarray(img.convert("RGB"))
+    return model_image_device(reader, reader._to_dev(rgb), PAGE_RGB, max_dim, quality, img.info.get("comment"))
+
+
+def encode_images_for_model(reader, image_paths, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128,
+                            device_decode=False, rule=None):
+    """The base64 strings the extractor sends to the vision model (enhanced_extractor.py:763-813), one per image, string for string: the
+    preprocess -> edge-crop -> auto-crop chain of the OCR input (``ocr_page_crop``, on the card), then ``_encode_image_for_model``
+    (:399-411) with ``rule(i) -> (max_dim, quality)`` (default ``preprocess.model_image_rule``: 2000 / 88 for image 0, 3200 / 95 for the
+    others; the quality is clamped to 50 .. 95) -- thumbnail and JPEG encoder on the card as well (``preprocess.model_image_device``:
+    csrc/thumb.hip + csrc/jpegenc.hip), so that only the file's bytes cross the link.  Where the chain changes the page the reference reads
+    it through ``cv2.imread`` (EXIF orientation applied; the PNG it writes carries no comment); where no step applies it encodes the
+    original file, which ``Image.open`` does not transpose and whose comment the saved JPEG keeps.  ``device_decode=True``: baseline JPEG
+    files are decoded on the card too.  A file Pillow cannot read maps to the base64 of its bytes, like :409-411."""
+    import base64
+
+    from .preprocess import PAGE_BGR, PAGE_GRAY, model_image_device, model_image_quality, model_image_rule
+
+    if crop_margin < 0:
+        raise ValueError("crop_margin must be >= 0")
+    rule = rule or model_image_rule
+    out = []
+    for i, path in enumerate(image_paths):
+        max_dim, quality = rule(i)
+        quality = model_image_quality(quality)
+        data = None
+        if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
+            applied = []
+            try:
+                page = ocr_page_crop(reader, path, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=True,
+                                     device_decode=device_decode, applied=applied)
+            except (OSError, ValueError):
+                applied = []                                          # :778-797: a step that fails leaves the original file
+            if applied:
+                data = model_image_device(reader, page, PAGE_GRAY if page.ndim == 2 else PAGE_BGR, max_dim, quality)
+        if data is None:
+            try:
+                data = _model_image_plain(reader, path, max_dim, quality, device_decode)
+            except OSError:                                           # Pillow cannot read the file
+                with open(path, "rb") as f:
+                    data = f.read()
+        out.append(base64.b64encode(data).decode("utf-8"))
+    return out

@@ -298,3 +298,43 @@ def central_edge_crop(image_path_or_array, percent):
         return None
     b = central_edge_crop_box(img.shape[0], img.shape[1], percent)
     return None if b is None else img[b[1]:b[3], b[0]:b[2]].copy()
+
+
+# ------------------------------------------------------------------------------------------------ the model input (:399-411, :801-812)
+def model_image_rule(image_index):
+    """(max_dim, JPEG quality) the extractor passes to ``_encode_image_for_model`` (:809-810): 2000 / 88 for image 0, else 3200 / 95."""
+    return (2000, 88) if image_index == 0 else (3200, 95)
+
+
+def model_image_quality(quality):
+    """``_encode_image_for_model``'s clamp of its ``jpeg_quality`` (:406)"""
+    return int(max(50, min(95, quality)))
+
+
+def model_image_host(source, max_dim, quality):
+    """``_encode_image_for_model(path, max_dim=max_dim, jpeg_quality=quality)`` (:399-408) before its base64 step, restated with Pillow:
+    ``Image.open(...).convert("RGB")``, ``thumbnail((max_dim, max_dim))``, ``save(format="JPEG", quality=clamp(quality, 50, 95))`` -> the
+    file's bytes.  ``source``: a path or the file's bytes, or a page the reference would have written as a PNG on the way (gray [H,W] or
+    BGR [H,W,3] uint8).  The yardstick of ``model_image_device``, and the path of sources the device decoder does not take."""
+    from PIL import Image
+
+    if isinstance(source, np.ndarray):
+        img = Image.fromarray(np.ascontiguousarray(source if source.ndim == 2 else source[:, :, ::-1])).convert("RGB")
+    else:
+        img = Image.open(io.BytesIO(source) if isinstance(source, (bytes, bytearray)) else source).convert("RGB")
+    img.thumbnail((max_dim, max_dim))
+    buf = io.BytesIO()
+    img.save(buf, format="JPEG", quality=model_image_quality(quality))
+    return buf.getvalue()
+
+
+def model_image_device(reader, page_dev, layout, max_dim, quality, comment=None):
+    """``model_image_host`` of a page that is on the card, byte for byte: a uint8 device page of the given ``PAGE_*`` layout (rows of packed
+    pixels; a strided row pitch is read in place) above ``max_dim`` is thumbnailed there (``bbocr_ocr_thumbnail`` with quality 0: the
+    resized RGB page, no round trip), then ``Reader.encode_jpeg`` writes the file (three components, quality clamped to 50 .. 95 like the
+    reference's); a page at or below ``max_dim`` is encoded as it is.  ``comment``: the source file's ``info["comment"]``, which Pillow
+    carries into the file it saves."""
+    H, W, _, _ = _page_layout(reader, page_dev, (layout,))
+    if max(H, W) > int(max_dim):
+        page_dev, layout = ocr_thumbnail_device(reader, page_dev, layout, max_dim, 0)[0], PAGE_RGB
+    return reader.encode_jpeg(page_dev, layout, quality=model_image_quality(quality), components=3, comment=comment)

@@ -636,6 +636,43 @@ class Reader:
             return self.pages_from_ycc(batch)
         return batch[..., None].expand(-1, -1, -1, 3).contiguous(), batch
 
+    def encode_jpeg(self, page_dev, layout=None, quality=85, components=None, comment=None):
+        """A uint8 device page -> the bytes of the JPEG file Pillow saves for it (``Image.fromarray(...).save(buf, "JPEG", quality=quality)``),
+        written on the card by ``bbocr_jpeg_encode`` (csrc/jpegenc.hip): baseline JFIF, 4:2:0, standard Huffman tables.  ``page_dev``:
+        ``[H,W]`` or ``[H,W,C]`` rows of packed pixels of a ``PAGE_*`` ``layout`` (default: GRAY for ``[H,W]``, RGB for 3 bytes per pixel,
+        YCBCR4 for 4); a strided row pitch (a crop of a larger page) is read in place.  ``components``: 3 = YCbCr (a gray page: what Pillow
+        saves for its ``convert("RGB")``), 1 = one component (gray pages only, Pillow's ``"L"`` save); default 1 for a gray page, else 3.
+        ``comment``: bytes of a COM segment (Pillow's ``info["comment"]``), at most 65533.  ``ValueError`` for anything else."""
+        from .preprocess import _page_layout
+
+        if layout is None:
+            ch = page_dev.shape[2] if getattr(page_dev, "ndim", 0) == 3 else 1
+            layout = {1: _lib.PAGE_GRAY, 3: _lib.PAGE_RGB, 4: _lib.PAGE_YCBCR4}.get(int(ch), _lib.PAGE_RGB)
+        if layout not in _lib.PAGE_PX_BYTES:
+            raise ValueError(f"unknown page layout {layout!r}")
+        H, W, pitch, _ = _page_layout(self, page_dev, (layout,))
+        if components is None:
+            components = 1 if layout == _lib.PAGE_GRAY else 3
+        if components not in (1, 3) or (components == 1 and layout != _lib.PAGE_GRAY):
+            raise ValueError("components must be 3, or 1 for a gray page")
+        if H > 65535 or W > 65535:
+            raise ValueError("a JPEG file holds at most 65535 x 65535 pixels")
+        if not isinstance(quality, int) or not 1 <= quality <= 100:
+            raise ValueError("quality must be an int in 1 .. 100")
+        if isinstance(comment, str):
+            comment = comment.encode()
+        comment = bytes(comment) if comment else b""
+        if len(comment) > 65533:
+            raise ValueError("a comment holds at most 65533 bytes")
+        cap = int(self._lib.bbocr_jpeg_encode_bound(H, W, components))
+        out = np.empty(cap, np.uint8)                                   # (untouched pages of it cost nothing)
+        n = C.c_size_t()
+        self._torch.cuda.current_stream(self.device_index).synchronize()      # the library runs on its own stream
+        self._check(self._lib.bbocr_jpeg_encode(self._h, C.c_void_p(page_dev.data_ptr()), H, W, pitch, int(layout), int(components), int(quality),
+                                                C.cast(C.c_char_p(comment), C.c_void_p) if comment else None, len(comment),
+                                                C.c_void_p(out.ctypes.data), cap, C.byref(n)))
+        return out[:n.value].tobytes()
+
     def decode_jpeg_device(self, sources):
         """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them (libjpeg's RGB and its Y
         plane; a grey file: the samples, replicated for RGB), decoded on the card, or ``None`` for a file the plan refuses or whose

@@ -419,6 +419,36 @@ int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status);
 
+/* ---- the extractor's model-input JPEG (enhanced_extractor.py:399-411, _encode_image_for_model's img.save(format="JPEG", quality=q)) written
+ * on the device (csrc/jpegenc.hip): one u8 page in device memory -- any BBOCR_PAGE_* layout, rows `pitch` bytes apart, a crop of a larger
+ * plane is a pointer + pitch -- becomes the file Pillow 12 / libjpeg-turbo saves for the page's RGB pixels (YCbCr pages: libjpeg's RGB),
+ * byte for byte: baseline JFIF, SOF0, 8 bit, one interleaved scan, no restart interval, the standard Huffman tables,
+ * jpeg_set_quality(quality, TRUE), ISLOW; components 3 = YCbCr 4:2:0 (a gray page: all-zero chroma blocks), components 1 = one component
+ * (gray pages only, Pillow's "L" save).  The header -- SOI, APP0 JFIF 1.01 (units 0, density 1:1), COM when comment_bytes > 0, DQT per
+ * table, SOF0, DHT per table, SOS -- and EOI are written on the host; only the bytes the scan produced cross the link.
+ *
+ * bbocr_jpeg_encode_bound: host only; a capacity that always suffices, 0 for H or W outside 1 .. 65535 or components not 1 or 3:
+ *     66160 + 2 * ceil(blocks * (22 + 63 * 26) / 8) + 2,   blocks = 6 * ceil(H/16) * ceil(W/16)  (components 1: ceil(H/8) * ceil(W/8))
+ * -- the longest header (a 65533-byte comment), a block of at most 22 bits for its DC term and 26 for each of its 63 AC terms, every scan
+ * byte stuffed, EOI.
+ * bbocr_host_jpeg_header: host only; everything up to and including SOS into out[capacity], *bytes = its length (also set when the
+ * capacity is too small, which is BBOCR_ERR_ARG).
+ * bbocr_jpeg_encode: the complete file into host_out[capacity], *bytes = its length.  A pipeline call: runs in a call slot next to
+ * readtext calls, scratch from the slot, returns with its work finished.  BBOCR_ERR_ARG before anything is queued: a null pointer, H or
+ * W outside 1 .. 65535, an unknown layout, a pitch shorter than a row, quality outside 1 .. 100, components not 1 or 3 or 1 with a
+ * colour layout, a comment longer than 65533 bytes, a capacity below the bound. */
+size_t bbocr_jpeg_encode_bound(int H, int W, int components);
+int bbocr_host_jpeg_header(int H, int W, int components, int quality, const uint8_t* comment, int comment_bytes, uint8_t* out, size_t capacity,
+                           size_t* bytes);
+int bbocr_jpeg_encode(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int components, int quality,
+                      const uint8_t* comment, int comment_bytes, uint8_t* host_out, size_t capacity, size_t* bytes);
+/* its intermediates in DEVICE memory dev_dst[dst_bytes] (parity tests), *bytes = what was written: stage 0 = the quantised coefficients,
+ * int16 [blocks][64] in zig-zag order, blocks in MCU order (Y00 Y01 Y10 Y11 Cb Cr; one component: raster order), dummy Y blocks as
+ * libjpeg fills them; 1 = int64 [blocks + 1], every block's bit offset in the unstuffed scan, then the total; 2 = the unstuffed scan, its
+ * last byte filled with 1-bits (dst_bytes >= ceil(blocks * (22 + 63 * 26) / 8)). */
+int bbocr_op_jpeg_encode_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int components,
+                               int quality, void* dev_dst, size_t dst_bytes, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif
