@@ -48,6 +48,11 @@ class bbocr_jpeg_plan(C.Structure):
                 ("supported", C.c_int), ("reason", C.c_int), ("orientation", C.c_int), ("reserved", C.c_int * 3)]
 
 
+class bbocr_page(C.Structure):
+    _fields_ = [("dev_rgb", C.c_void_p), ("dev_gray", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("rgb_pitch", C.c_longlong),
+                ("gray_pitch", C.c_longlong)]
+
+
 class bbocr_boxlist(C.Structure):
     _fields_ = [
         ("n_images", C.c_int), ("poly_off", C.POINTER(C.c_int)), ("polys", C.POINTER(C.c_int)),
@@ -92,6 +97,12 @@ PROTOTYPES = {
     "bbocr_recognize": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(bbocr_boxlist), C.POINTER(bbocr_params),
                                   C.POINTER(C.POINTER(bbocr_result))]),
     "bbocr_readtext_batch": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(bbocr_params), C.POINTER(C.POINTER(bbocr_result))]),
+    "bbocr_readtext_pages": (C.c_int, [_vp, C.POINTER(bbocr_page), C.c_int, C.POINTER(bbocr_params), C.POINTER(C.POINTER(bbocr_result))]),
+    "bbocr_host_pages_plan": (C.c_int, [C.POINTER(bbocr_page), C.c_int, C.POINTER(bbocr_params), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "bbocr_op_pack_pages": (C.c_int, [_vp, C.POINTER(bbocr_page), C.c_int, _vp, _vp]),
+    "bbocr_op_crops_pages": (C.c_int, [_vp, C.POINTER(bbocr_page), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_int), C.c_int, C.c_float, _vp, C.POINTER(C.c_int), C.c_int]),
     "bbocr_free_boxlist": (None, [C.POINTER(bbocr_boxlist)]),
     "bbocr_free_result": (None, [C.POINTER(bbocr_result)]),
     "bbocr_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),

@@ -86,7 +86,8 @@ void slot_destroy(bbocr_ctx* c) {
     DevBuf* bufs[] = {&c->arena.buf, &c->heat, &c->gray, &c->resized, &c->ccl_label, &c->ccl_stat, &c->ccl_slot, &c->ccl_comps, &c->ccl_rowext,
                       &c->ccl_counters, &c->crop_desc, &c->crop_desc2, &c->crop_scratch, &c->crop_hscratch, &c->crop_wscratch, &c->crop_luts, &c->crop_hist,
                       &c->ctc_idx, &c->ctc_pmax, &c->ctc_out_idx, &c->ctc_out, &c->seq_v, &c->seq_xp, &c->seq_h, &c->seq_lin, &c->seq_logits,
-                      &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out};
+                      &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out,
+                      &c->pg_rgb, &c->pg_tab};
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->seq_stream) (void)hipStreamDestroy(c->seq_stream);
@@ -226,7 +227,7 @@ int bbocr_recognize(bbocr_ctx* ctx, const uint8_t* dev_gray, int B, int H, int W
         import_boxes(boxes, hb);
         std::vector<BoxJob> jobs;
         std::vector<int> off;
-        recognize_impl(ctx, dev_gray, B, H, W, hb, pp, jobs, off);
+        recognize_impl(ctx, GrayPages{dev_gray, H, W}, B, hb, pp, jobs, off);
         prof_collect(ctx);
         *out = export_result(B, jobs, off);
         ctx->times[7] = (float)ms_since(t0);
@@ -280,7 +281,7 @@ int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* 
             // every page but the last pass's has its boxes: their crops go through the recogniser's conv stack (queued behind the
             // detector on `stream`) while the last pass's CCL + host geometry run -- that stretch would otherwise leave the card idle
             if (subs.size() >= 2 && k + 2 == subs.size() && pp.rotation_info[0] == 0 && ctx->crnn_loaded)
-                rec_early_begin(ctx, dev_gray, b0 + nb, B, H, W, hb, pp, early);
+                rec_early_begin(ctx, GrayPages{dev_gray, H, W}, b0 + nb, B, hb, pp, early);
         }
         HIPCHK(hipEventSynchronize(ctx->det_t1));   // the detector's end, not the stream's: the early recogniser part may be running behind it
         float det_ms = 0.f;
@@ -288,7 +289,7 @@ int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* 
         ctx->times[0] = det_ms;          // GPU span of the detector; box extraction (times[1], times[2]) overlaps it except for the last sub-batch
         std::vector<BoxJob> jobs;
         std::vector<int> off;
-        recognize_impl(ctx, dev_gray, B, H, W, hb, pp, jobs, off, &early);
+        recognize_impl(ctx, GrayPages{dev_gray, H, W}, B, hb, pp, jobs, off, &early);
         prof_collect(ctx);
         *out = export_result(B, jobs, off);
         ctx->times[7] = (float)ms_since(t_all);

@@ -1,6 +1,78 @@
 // C ABI of libbbocr (include/bbocr.h), stage-level entry points: single kernels and host stages exposed so that the parity tests can pin each one.
 #include "ctx.h"
 
+// bbocr_op_crops / bbocr_op_crops_pages inside a call slot: the boxes of n pages (page k: hori [hori_off[k], hori_off[k+1]), free_q likewise)
+// planned as recognize_impl plans them and cropped by one set of launches into the bucket tensor [crops][64][imgW], page after page
+static void op_crops(bbocr_ctx* ctx, const GrayPages& g, int n, const int* hori, const int* hori_off, const double* free_q, const int* free_off, int imgW,
+                     float contrast, uint16_t* dev_out, int* n_out, int mode) {
+    if (!dev_out || !n_out || imgW < 64 || (imgW & 63) || mode < 0 || mode > 4) fail(BBOCR_ERR_ARG, "bad crop arguments");
+    std::vector<BoxJob> jobs;
+    auto take = [&](BoxJob& j) {
+        if (mode == 0) {                       // per-box branch: the boxes whose own padded width is imgW
+            if (j.d.imgW == imgW) jobs.push_back(j);
+            return;
+        }
+        j.d.imgW = imgW;                       // batched branch (rotation_info): forced width, np.rot90(crop, mode - 1)
+        j.d.rot = mode - 1;
+        if (j.d.rot & 1) std::swap(j.d.rw, j.d.rh);
+        crop_refit_fw(j.d);
+        jobs.push_back(j);
+    };
+    for (int k = 0; k < n; ++k) {
+        for (int i = hori_off[k]; i < hori_off[k + 1]; ++i) {
+            BoxJob j;
+            std::array<int, 4> b;
+            memcpy(b.data(), hori + (size_t)i * 4, 16);
+            if (plan_horizontal(b, k, g.h(k), g.w(k), j)) take(j);
+        }
+        for (int i = free_off[k]; i < free_off[k + 1]; ++i) {
+            BoxJob j;
+            std::array<double, 8> f;
+            memcpy(f.data(), free_q + (size_t)i * 8, 64);
+            if (plan_free(f, k, j)) take(j);
+        }
+    }
+    *n_out = (int)jobs.size();
+    if (jobs.empty()) return;
+    size_t a_total = 0, w_total = 0;
+    rec_layout_scratch(jobs, 0, a_total, w_total);
+    bool any_warp = false, any_tall = false;
+    std::vector<CropDesc> descs;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        CropDesc& d = jobs[i].d;
+        d.slot = (int)i;                       // row of the bucket tensor [n, 64, imgW]
+        any_warp |= d.warp != 0;
+        any_tall |= !(d.fw == d.rw && d.rh == 64);
+        descs.push_back(d);
+    }
+    ctx->crop_scratch.ensure(std::max<size_t>(a_total, 16));
+    ctx->crop_hscratch.ensure(std::max<size_t>(a_total, 16));
+    ctx->crop_wscratch.ensure(std::max<size_t>(w_total, 16));
+    ctx->crop_desc.ensure(descs.size() * sizeof(CropDesc));
+    ctx->crop_luts.ensure(descs.size() * 256);
+    HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(launch_crops(g.gray, g.H, g.W, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(), imgW, any_warp, any_tall,
+                        (uint8_t*)ctx->crop_wscratch.p, (uint8_t*)ctx->crop_scratch.p, (uint8_t*)ctx->crop_hscratch.p,
+                        (const uint8_t*)ctx->crop_luts.p, dev_out, 1, ctx->stream, 0, 0, 0, g.tab_dev));
+    if (contrast > 0) {
+        ctx->crop_hist.ensure(descs.size() * 256 * 4);
+        HIPCHK(launch_crop_hist((const uint8_t*)ctx->crop_scratch.p, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(),
+                                (unsigned int*)ctx->crop_hist.p, ctx->stream));
+        std::vector<unsigned int> hist(descs.size() * 256);
+        HIPCHK(hipMemcpyAsync(hist.data(), ctx->crop_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+        std::vector<uint8_t> luts(descs.size() * 256);
+        for (size_t k = 0; k < descs.size(); ++k)       // a crop whose contrast is high enough stays as it is (lut_off -1), as in recognize_impl's retry
+            if (contrast_lut(&hist[k * 256], (size_t)descs[k].rw * descs[k].rh, (double)contrast, &luts[k * 256])) descs[k].lut_off = (int)(k * 256);
+        HIPCHK(hipMemcpyAsync(ctx->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(launch_crops(g.gray, g.H, g.W, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(), imgW, any_warp, any_tall,
+                        (uint8_t*)ctx->crop_wscratch.p, (uint8_t*)ctx->crop_scratch.p, (uint8_t*)ctx->crop_hscratch.p,
+                        (const uint8_t*)ctx->crop_luts.p, dev_out, 2, ctx->stream, 0, 0, rec_mode(ctx), g.tab_dev));
+    slot_sync(ctx, ctx->stream);
+}
+
 extern "C" {
 
 int bbocr_op_preprocess_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, uint8_t* dev_dst, int dh, int dw, double param) {
@@ -224,70 +296,28 @@ int bbocr_upload_pages(bbocr_ctx* root, const void* const* host_pages, int n, si
 int bbocr_op_crops(bbocr_ctx* ctx, const uint8_t* dev_gray, int H, int W, const int* hori, int n_hori, const double* free_q, int n_free, int imgW,
                    float contrast, uint16_t* dev_out, int* n_out, int mode) {
     return guarded(ctx, [&](bbocr_ctx* ctx) {
-        if (!dev_gray || !dev_out || !n_out || imgW < 64 || (imgW & 63) || mode < 0 || mode > 4) fail(BBOCR_ERR_ARG, "bad crop arguments");
-        std::vector<BoxJob> jobs;
-        auto take = [&](BoxJob& j) {
-            if (mode == 0) {                       // per-box branch: the boxes whose own padded width is imgW
-                if (j.d.imgW == imgW) jobs.push_back(j);
-                return;
-            }
-            j.d.imgW = imgW;                       // batched branch (rotation_info): forced width, np.rot90(crop, mode - 1)
-            j.d.rot = mode - 1;
-            if (j.d.rot & 1) std::swap(j.d.rw, j.d.rh);
-            crop_refit_fw(j.d);
-            jobs.push_back(j);
-        };
-        for (int i = 0; i < n_hori; ++i) {
-            BoxJob j;
-            std::array<int, 4> b;
-            memcpy(b.data(), hori + (size_t)i * 4, 16);
-            if (plan_horizontal(b, 0, H, W, j)) take(j);
+        if (!dev_gray) fail(BBOCR_ERR_ARG, "bad crop arguments");
+        const int hori_off[2] = {0, n_hori}, free_off[2] = {0, n_free};
+        op_crops(ctx, GrayPages{dev_gray, H, W}, 1, hori, hori_off, free_q, free_off, imgW, contrast, dev_out, n_out, mode);
+    });
+}
+
+int bbocr_op_crops_pages(bbocr_ctx* ctx, const bbocr_page* pages, int n, const int* hori, const int* hori_off, const double* free_q,
+                         const int* free_off, int imgW, float contrast, uint16_t* dev_out, int* n_out, int mode) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!pages || n <= 0 || n > 65535 || !hori_off || !free_off) fail(BBOCR_ERR_ARG, "bad crop arguments");
+        // the page table: offsets from the first page's plane (the pages are allocations of their own; the kernels add a signed offset)
+        std::vector<CropPage> tab(n);
+        for (int k = 0; k < n; ++k) {
+            const bbocr_page& g = pages[k];
+            const long long pitch = g.gray_pitch ? g.gray_pitch : (long long)g.W;
+            if (!g.dev_gray || g.H <= 0 || g.W <= 0 || (long long)g.H * g.W >= (1LL << 30) || pitch < g.W) fail(BBOCR_ERR_ARG, "bad gray page");
+            tab[k] = CropPage{(long long)(g.dev_gray - pages[0].dev_gray), pitch, g.H, g.W};
         }
-        for (int i = 0; i < n_free; ++i) {
-            BoxJob j;
-            std::array<double, 8> f;
-            memcpy(f.data(), free_q + (size_t)i * 8, 64);
-            if (plan_free(f, 0, j)) take(j);
-        }
-        *n_out = (int)jobs.size();
-        if (jobs.empty()) return;
-        size_t a_total = 0, w_total = 0;
-        rec_layout_scratch(jobs, 0, a_total, w_total);
-        bool any_warp = false, any_tall = false;
-        std::vector<CropDesc> descs;
-        for (size_t i = 0; i < jobs.size(); ++i) {
-            CropDesc& d = jobs[i].d;
-            d.slot = (int)i;                       // row of the bucket tensor [n, 64, imgW]
-            any_warp |= d.warp != 0;
-            any_tall |= !(d.fw == d.rw && d.rh == 64);
-            descs.push_back(d);
-        }
-        ctx->crop_scratch.ensure(std::max<size_t>(a_total, 16));
-        ctx->crop_hscratch.ensure(std::max<size_t>(a_total, 16));
-        ctx->crop_wscratch.ensure(std::max<size_t>(w_total, 16));
-        ctx->crop_desc.ensure(descs.size() * sizeof(CropDesc));
-        ctx->crop_luts.ensure(descs.size() * 256);
-        HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(launch_crops(dev_gray, H, W, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(), imgW, any_warp, any_tall,
-                            (uint8_t*)ctx->crop_wscratch.p, (uint8_t*)ctx->crop_scratch.p, (uint8_t*)ctx->crop_hscratch.p,
-                            (const uint8_t*)ctx->crop_luts.p, dev_out, 1, ctx->stream));
-        if (contrast > 0) {
-            ctx->crop_hist.ensure(descs.size() * 256 * 4);
-            HIPCHK(launch_crop_hist((const uint8_t*)ctx->crop_scratch.p, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(),
-                                    (unsigned int*)ctx->crop_hist.p, ctx->stream));
-            std::vector<unsigned int> hist(descs.size() * 256);
-            HIPCHK(hipMemcpyAsync(hist.data(), ctx->crop_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-            slot_sync(ctx, ctx->stream);
-            std::vector<uint8_t> luts(descs.size() * 256);
-            for (size_t k = 0; k < descs.size(); ++k)       // a crop whose contrast is high enough stays as it is (lut_off -1), as in recognize_impl's retry
-                if (contrast_lut(&hist[k * 256], (size_t)descs[k].rw * descs[k].rh, (double)contrast, &luts[k * 256])) descs[k].lut_off = (int)(k * 256);
-            HIPCHK(hipMemcpyAsync(ctx->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
-        }
-        HIPCHK(launch_crops(dev_gray, H, W, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(), imgW, any_warp, any_tall,
-                            (uint8_t*)ctx->crop_wscratch.p, (uint8_t*)ctx->crop_scratch.p, (uint8_t*)ctx->crop_hscratch.p,
-                            (const uint8_t*)ctx->crop_luts.p, dev_out, 2, ctx->stream, 0, 0, rec_mode(ctx)));
-        slot_sync(ctx, ctx->stream);
+        ctx->pg_tab.ensure(tab.size() * sizeof(CropPage));
+        HIPCHK(hipMemcpyAsync(ctx->pg_tab.p, tab.data(), tab.size() * sizeof(CropPage), hipMemcpyHostToDevice, ctx->stream));   // (op_crops ends synchronised)
+        op_crops(ctx, GrayPages{pages[0].dev_gray, 0, 0, tab.data(), (const CropPage*)ctx->pg_tab.p}, n, hori, hori_off, free_q, free_off, imgW, contrast,
+                 dev_out, n_out, mode);
     });
 }
 

@@ -121,8 +121,7 @@ hipError_t launch_maxpool(const uint16_t* in, uint16_t* out, int N, int H, int W
 // point (R 9798, G 19235, B 3735, round to nearest; pinned by the reference's stored pre-processing outputs, tests/golden/legacy_preprocess).
 __global__ void __launch_bounds__(256) gray_kernel(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ gray, size_t npix) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
-        const int c0 = rgb[i * 3], c1 = rgb[i * 3 + 1], c2 = rgb[i * 3 + 2];
-        gray[i] = (uint8_t)((c2 * 9798 + c1 * 19235 + c0 * 3735 + (1 << 14)) >> 15);
+        gray[i] = bgr2gray_px(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]);
     }
 }
 // ---- libjpeg's YCbCr -> RGB (jdcolor.c::ycc_rgb_convert, the conversion behind every RGB decode of a JFIF file: cv2.imread, skimage /

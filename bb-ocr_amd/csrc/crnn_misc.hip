@@ -10,11 +10,21 @@
 // ------------------------------------------------------------------------------------------------ warpPerspective
 // cv2.warpPerspective(gray, M, (ww, wh)), INTER_LINEAR, BORDER_CONSTANT 0: coordinates rounded to 1/32 px (cvRound of a
 // double), weights (32-ax)(32-ay)*32 etc. (exact 15-bit table entries), result (sum + 2^14) >> 15.
+// PAGES: d.img indexes the page table (pages of their own shapes, bbocr_readtext_pages) -- the source plane, its bounds and its row
+// pitch are the page's own; else plane d.img of the batch [B][H][W]
+template <bool PAGES>
 __global__ void __launch_bounds__(256) crop_warp_kernel(const uint8_t* __restrict__ gray, int H, int W, const CropDesc* __restrict__ descs,
-                                                        int first, uint8_t* __restrict__ wscratch) {
+                                                        int first, uint8_t* __restrict__ wscratch, const CropPage* __restrict__ pages) {
     const CropDesc d = descs[first + blockIdx.y];
     if (!d.warp) return;
-    const uint8_t* src = gray + (size_t)d.img * H * W;
+    const uint8_t* src;
+    size_t pitch;
+    if constexpr (PAGES) {
+        const CropPage pg = pages[d.img];
+        src = gray + pg.off; H = pg.H; W = pg.W; pitch = (size_t)pg.pitch;
+    } else {
+        src = gray + (size_t)d.img * H * W; pitch = (size_t)W;
+    }
     uint8_t* dst = wscratch + d.warp_off;
     const int total = d.sw * d.sh;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
@@ -33,7 +43,7 @@ __global__ void __launch_bounds__(256) crop_warp_kernel(const uint8_t* __restric
         const int sx = (int)sxl, sy = (int)syl;
         const int ax = (int)(X & 31), ay = (int)(Y & 31);
         auto tap = [&](int yy, int xx) -> int {
-            return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? (int)src[(size_t)yy * W + xx] : 0;
+            return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? (int)src[(size_t)yy * pitch + xx] : 0;
         };
         const int acc = tap(sy, sx) * ((32 - ax) * (32 - ay) * 32) + tap(sy, sx + 1) * (ax * (32 - ay) * 32) +
                         tap(sy + 1, sx) * ((32 - ax) * ay * 32) + tap(sy + 1, sx + 1) * (ax * ay * 32);
@@ -55,13 +65,19 @@ __device__ __forceinline__ void cv_lin_coef_d(int d, int ssize, double scale, in
     s1 = sx + 1 < ssize ? sx + 1 : ssize - 1;
 }
 
+template <bool PAGES>
 __global__ void __launch_bounds__(256) crop_resize_kernel(const uint8_t* __restrict__ gray, int H, int W, const CropDesc* __restrict__ descs,
-                                                          int first, const uint8_t* __restrict__ wscratch, uint8_t* __restrict__ scratch) {
+                                                          int first, const uint8_t* __restrict__ wscratch, uint8_t* __restrict__ scratch,
+                                                          const CropPage* __restrict__ pages) {
     const CropDesc d = descs[first + blockIdx.y];
     const uint8_t* src;
-    int stride;
-    if (d.warp) { src = wscratch + d.warp_off; stride = d.sw; }
-    else { src = gray + (size_t)d.img * H * W + (size_t)d.sy0 * W + d.sx0; stride = W; }
+    size_t stride;
+    if (d.warp) { src = wscratch + d.warp_off; stride = (size_t)d.sw; }
+    else if constexpr (PAGES) {      // the source rectangle was clamped to the page's own H x W on the host (plan_horizontal)
+        const CropPage pg = pages[d.img];
+        src = gray + pg.off + (size_t)d.sy0 * (size_t)pg.pitch + d.sx0; stride = (size_t)pg.pitch;
+    }
+    else { src = gray + (size_t)d.img * H * W + (size_t)d.sy0 * W + d.sx0; stride = (size_t)W; }
     uint8_t* dst = scratch + d.a_off;
     // d.rw x d.rh is the stage-A image AFTER np.rot90(crop, d.rot) (rotation_info variants); cv2.resize works on the unrotated crop
     const int sw = d.sw, sh = d.sh, dw = (d.rot & 1) ? d.rh : d.rw, dh = (d.rot & 1) ? d.rw : d.rh;
@@ -226,11 +242,14 @@ __global__ void __launch_bounds__(256) crop_final_kernel(const CropDesc* __restr
 
 hipError_t launch_crops(const uint8_t* gray, int H, int W, const CropDesc* descs_dev, int first, int count, int imgW, int any_warp,
                         int any_tall, uint8_t* wscratch, uint8_t* scratch, uint8_t* hscratch, const uint8_t* luts, uint16_t* out_bucket,
-                        int stage_mask, hipStream_t s, int wide_row_stride, int gap, int mode) {
+                        int stage_mask, hipStream_t s, int wide_row_stride, int gap, int mode, const CropPage* pages) {
     if (count <= 0) return hipSuccess;
-    if (stage_mask & 1) {
-        if (any_warp) hipLaunchKernelGGL(crop_warp_kernel, dim3(16, count), dim3(256), 0, s, gray, H, W, descs_dev, first, wscratch);
-        hipLaunchKernelGGL(crop_resize_kernel, dim3(16, count), dim3(256), 0, s, gray, H, W, descs_dev, first, wscratch, scratch);
+    if ((stage_mask & 1) && pages) {
+        if (any_warp) hipLaunchKernelGGL(crop_warp_kernel<true>, dim3(16, count), dim3(256), 0, s, gray, 0, 0, descs_dev, first, wscratch, pages);
+        hipLaunchKernelGGL(crop_resize_kernel<true>, dim3(16, count), dim3(256), 0, s, gray, 0, 0, descs_dev, first, wscratch, scratch, pages);
+    } else if (stage_mask & 1) {
+        if (any_warp) hipLaunchKernelGGL(crop_warp_kernel<false>, dim3(16, count), dim3(256), 0, s, gray, H, W, descs_dev, first, wscratch, pages);
+        hipLaunchKernelGGL(crop_resize_kernel<false>, dim3(16, count), dim3(256), 0, s, gray, H, W, descs_dev, first, wscratch, scratch, pages);
     }
     if (stage_mask & 2) {
         if (any_tall) hipLaunchKernelGGL(crop_pil_h_kernel, dim3(8, count), dim3(256), 0, s, descs_dev, first, scratch, luts, hscratch);

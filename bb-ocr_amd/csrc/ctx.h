@@ -1,6 +1,7 @@
 // Internal header of libbbocr: context, small host helpers and the functions the translation units share.
 // Translation units: weights.cpp (BN folding, MFMA packing), detector.cpp (CRAFT forward, box extraction), recognizer.cpp (crops,
-// CRNN, CTC), preprocess.cpp (the f2 chain), abi.cpp (context + pipeline entry points of include/bbocr.h), abi_ops.cpp (stage-level
+// CRNN, CTC), preprocess.cpp (the f2 chain), abi.cpp (context + pipeline entry points of include/bbocr.h), pages.cpp (the pipeline call
+// for pages of mixed shapes, its plan and page tables), abi_ops.cpp (stage-level
 // entry points used by the parity tests).
 #pragma once
 #include "../../include/bbocr.h"
@@ -235,6 +236,8 @@ struct bbocr_ctx : WeightView {
 
     Arena arena;
     DevBuf heat, gray, resized;
+    DevBuf pg_rgb, pg_tab;                    // bbocr_readtext_pages: the packed RGB pages (shape group by shape group; `gray` holds the planes), the page tables
+    PinBuf pg_pin;                            // staging of the page tables' upload
     DevBuf ccl_label, ccl_stat, ccl_slot, ccl_comps, ccl_rowext, ccl_counters;
     DevBuf crop_desc, crop_scratch, crop_hscratch, crop_wscratch, crop_luts, crop_hist;
     DevBuf ctc_idx, ctc_pmax, ctc_out_idx, ctc_out, ctc_probs, crop_desc2;
@@ -285,6 +288,24 @@ struct RgbSource { const uint8_t* rgb; int Himg, Wimg; };   // conv1_2 with conv
 struct DetDims {
     int H32, W32, h, w, th, tw;
     double ratio;
+};
+
+struct DetPlan {           // det_plan: the detector passes of B pages of one shape H x W
+    int H, W;
+    DetDims d;
+    std::vector<int> passes;                 // pages per pass
+    size_t arena_bytes, resized_bytes;       // activation arena of the largest pass; its resized pages (0: the pages are not resized)
+};
+
+// The gray planes a recognition reads: B pages of ONE shape back to back at `gray`, or -- tab != null, bbocr_readtext_pages -- pages of
+// their own shapes, page b at gray + tab[b].off (tab_dev: the same table on the device, what the crop kernels index with CropDesc::img)
+struct GrayPages {
+    const uint8_t* gray;
+    int H, W;
+    const CropPage* tab = nullptr;
+    const CropPage* tab_dev = nullptr;
+    int h(int b) const { return tab ? tab[b].H : H; }
+    int w(int b) const { return tab ? tab[b].W : W; }
 };
 
 struct HostBoxes {
@@ -363,6 +384,11 @@ bool craft_up4(bbocr_ctx* c, const Act& s1, const uint16_t* z, uint16_t* u4b);  
 void craft_cls_tail(bbocr_ctx* c, const Act& c2, float* heat);
 DetDims det_dims(int H, int W, int canvas, double mag);
 void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bbocr_params& p, float* heat, const std::function<void(int, int)>& after_sub = nullptr);
+DetPlan det_plan(bbocr_ctx* c, int B, int H, int W, const bbocr_params& p, bool overlapped);      // detect_impl's three steps
+void det_size(bbocr_ctx* c, size_t arena_bytes, size_t resized_bytes);
+void det_run(bbocr_ctx* c, const DetPlan& s, const uint8_t* rgb, float* heat, const std::function<void(int, int)>& after_sub = nullptr);
+int ccl_cap_comps(int B, int h, int w);
+void ccl_size(bbocr_ctx* c, size_t npx, int cap_comps);
 void boxes_impl(bbocr_ctx* c, const float* heat, int B, int h, int w, double ratio, const bbocr_params& p, HostBoxes& hb, hipStream_t st);
 bbocr_boxlist* export_boxes(const HostBoxes& hb);
 void import_boxes(const bbocr_boxlist* bl, HostBoxes& hb);
@@ -380,8 +406,8 @@ void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
 void crnn_sequence(bbocr_ctx* c, size_t rows_pad, const int* tiles_dev, int ntiles, float* logits);
 void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, bool beam);
 double ctc_decode(const CtcOut& o, const int* idx, const std::vector<int>* beam_text, std::vector<int>& text);
-void rec_early_begin(bbocr_ctx* c, const uint8_t* gray, int pages, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p, RecEarly& e);
-void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p, std::vector<BoxJob>& jobs, std::vector<int>& box_off, RecEarly* early = nullptr);
+void rec_early_begin(bbocr_ctx* c, const GrayPages& g, int pages, int B, const HostBoxes& hb, const bbocr_params& p, RecEarly& e);
+void recognize_impl(bbocr_ctx* c, const GrayPages& g, int B, const HostBoxes& hb, const bbocr_params& p, std::vector<BoxJob>& jobs, std::vector<int>& box_off, RecEarly* early = nullptr);
 bbocr_result* export_result(int B, const std::vector<BoxJob>& jobs, const std::vector<int>& box_off);
 void pp_resize(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, int dh, int dw, bool src_bgr = false);   // enqueues; the caller waits
 void pp_gauss(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, double sigma);

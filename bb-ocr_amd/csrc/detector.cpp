@@ -275,18 +275,22 @@ DetDims det_dims(int H, int W, int canvas, double mag) {
     return d;
 }
 
-void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bbocr_params& p, float* heat,
-                        const std::function<void(int, int)>& after_sub) {
+// The detector passes of B pages of one shape and what they need: det_plan touches no device buffer, det_size grows the slot's buffers
+// for a plan, det_run enqueues it.  bbocr_readtext_pages plans every shape group of a call first and sizes the buffers ONCE, for the
+// largest: a buffer re-allocated for a later, larger group would be freed under the passes of the earlier ones.
+DetPlan det_plan(bbocr_ctx* c, int B, int H, int W, const bbocr_params& p, bool overlapped) {
     if (!c->craft_loaded) fail(BBOCR_ERR_STATE, "detector weights not loaded");
     if (B <= 0 || H <= 0 || W <= 0) fail(BBOCR_ERR_ARG, "bad page batch shape");
-    const DetDims d = det_dims(H, W, p.canvas_size, p.mag_ratio);
+    DetPlan s;
+    s.H = H; s.W = W;
+    const DetDims d = s.d = det_dims(H, W, p.canvas_size, p.mag_ratio);
     if (d.th <= 0 || d.tw <= 0) fail(BBOCR_ERR_ARG, "page collapses to zero size");
     // Pages per detector pass.  Explicit det_sub_batch: uniform passes of that size.  Auto: passes as large as a 96 GB
     // activation arena allows (sized by a dry run on one page; at most 64 pages), and -- when the caller overlaps box
     // extraction with the next pass (readtext_batch) -- a short last pass of 8 pages (of 1280x960; fewer, larger ones by pixel count),
     // because only the LAST pass's CCL + host geometry is exposed: 64 pages run as [56, 8], 16 A4@300dpi scans as [14, 2] -- when the call
     // is alone on its context.
-    std::vector<int> passes;
+    std::vector<int>& passes = s.passes;
     int sb_other = 0;
     if (c->cfg.det_sub_batch > 0) {
         for (int b0 = 0; b0 < B; b0 += c->cfg.det_sub_batch) passes.push_back(std::min(c->cfg.det_sub_batch, B - b0));
@@ -303,7 +307,7 @@ void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bb
         // last pass is turned into boxes, so the short pass has nothing left to hide and only costs its own inefficiency (round 4, two calls
         // in flight: [56, 8] 942, one pass of 64 959, [32, 32] 947 images/s)
         const bool alone = !other_call_in_flight(c);
-        const int tail = (alone && after_sub && B * equiv >= 24.0 && cap > tail_pages && B > tail_pages) ? tail_pages : 0;
+        const int tail = (alone && overlapped && B * equiv >= 24.0 && cap > tail_pages && B > tail_pages) ? tail_pages : 0;
         const int body = B - tail, nbig = cdiv(body, cap);
         for (int i = 0; i < nbig; ++i) passes.push_back(body / nbig + (i < body % nbig ? 1 : 0));
         if (tail) passes.push_back(tail);
@@ -312,17 +316,27 @@ void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bb
     // work buffers are sized for whichever of the two schedules has the larger pass: a context whose calls are sometimes alone and
     // sometimes not must not re-allocate a 60-GB arena when the schedule flips
     const int sb = std::max(sb_other, *std::max_element(passes.begin(), passes.end()));
-    const bool need_resize = (d.th != H || d.tw != W);
-    if (need_resize) c->resized.ensure((size_t)sb * d.th * d.tw * 3);
+    s.resized_bytes = (d.th != H || d.tw != W) ? (size_t)sb * d.th * d.tw * 3 : 0;
     c->arena.begin(true);
     craft_forward_any(c, nullptr, sb, d.th, d.tw, d.H32, d.W32, nullptr);
-    c->arena.buf.ensure(c->arena.off);
+    s.arena_bytes = c->arena.off;
+    return s;
+}
+
+void det_size(bbocr_ctx* c, size_t arena_bytes, size_t resized_bytes) {
+    if (resized_bytes) c->resized.ensure(resized_bytes);
+    c->arena.buf.ensure(arena_bytes);
+}
+
+// rgb: the plan's B pages [B][H][W][3]; heat: [B][h][w][2]
+void det_run(bbocr_ctx* c, const DetPlan& s, const uint8_t* rgb, float* heat, const std::function<void(int, int)>& after_sub) {
+    const DetDims& d = s.d;
     int b0 = 0;
-    for (const int nb : passes) {
+    for (const int nb : s.passes) {
         EnqLock enq(c);                       // one detector pass = one contiguous block on the compute stream
-        const uint8_t* src = rgb + (size_t)b0 * H * W * 3;
-        if (need_resize) {
-            HIPCHK(launch_resize_u8(src, nb, H, W, 3, (uint8_t*)c->resized.p, d.th, d.tw, c->stream));
+        const uint8_t* src = rgb + (size_t)b0 * s.H * s.W * 3;
+        if (s.resized_bytes) {
+            HIPCHK(launch_resize_u8(src, nb, s.H, s.W, 3, (uint8_t*)c->resized.p, d.th, d.tw, c->stream));
             src = (const uint8_t*)c->resized.p;
         }
         c->arena.begin(false);
@@ -332,22 +346,35 @@ void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bb
     }
 }
 
+void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bbocr_params& p, float* heat,
+                        const std::function<void(int, int)>& after_sub) {
+    const DetPlan s = det_plan(c, B, H, W, p, after_sub != nullptr);
+    det_size(c, s.arena_bytes, s.resized_bytes);
+    det_run(c, s, rgb, heat, after_sub);
+}
+
 // ------------------------------------------------------------------------------------------------ boxes
+
+// theoretical maxima, so that no heat-map can overflow them: an accepted component has >= 10 pixels (getDetBoxes_core's size
+// filter), and the (component, row) extents cannot outnumber the pixels
+int ccl_cap_comps(int B, int h, int w) { return (int)std::min<size_t>(0x3fffffff, (size_t)B * ((size_t)h * w / 10 + 1)); }
+// the CCL buffers of one boxes_impl call over npx heat-map pixels (a call over several passes sizes them once, for the largest)
+void ccl_size(bbocr_ctx* c, size_t npx, int cap_comps) {
+    c->ccl_label.ensure(npx * 4);
+    c->ccl_stat.ensure(npx * 24);
+    c->ccl_slot.ensure(npx * 4);
+    c->ccl_comps.ensure((size_t)cap_comps * sizeof(CclOut));
+    c->ccl_rowext.ensure(std::min<size_t>(0x3fffffff, npx) * 8);
+    c->ccl_counters.ensure(16);
+}
 
 void boxes_impl(bbocr_ctx* c, const float* heat, int B, int h, int w, double ratio, const bbocr_params& p, HostBoxes& hb,
                        hipStream_t st) {
     if (B <= 0 || h <= 0 || w <= 0 || !(ratio > 0)) fail(BBOCR_ERR_ARG, "bad heat-map shape");
     const size_t npx = (size_t)B * h * w;
-    // theoretical maxima, so that no heat-map can overflow them: an accepted component has >= 10 pixels (getDetBoxes_core's size
-    // filter), and the (component, row) extents cannot outnumber the pixels
-    const int cap_comps = (int)std::min<size_t>(0x3fffffff, (size_t)B * ((size_t)h * w / 10 + 1));
+    const int cap_comps = ccl_cap_comps(B, h, w);
     const int cap_rows = (int)std::min<size_t>(0x3fffffff, npx);
-    c->ccl_label.ensure(npx * 4);
-    c->ccl_stat.ensure(npx * 24);
-    c->ccl_slot.ensure(npx * 4);
-    c->ccl_comps.ensure((size_t)cap_comps * sizeof(CclOut));
-    c->ccl_rowext.ensure((size_t)cap_rows * 8);
-    c->ccl_counters.ensure(16);
+    ccl_size(c, npx, cap_comps);
     if (!c->ccl_t0) { HIPCHK(hipEventCreate(&c->ccl_t0)); HIPCHK(hipEventCreate(&c->ccl_t1)); }
     HIPCHK(hipEventRecord(c->ccl_t0, st));
     HIPCHK(launch_ccl(heat, B, h, w, (float)p.low_text, (float)p.link_threshold, (double)p.text_threshold, (int*)c->ccl_label.p,

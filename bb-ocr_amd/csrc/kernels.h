@@ -83,6 +83,8 @@ void pack_conv1_1_weights_fused(const float* w /*[64][3][3][3] folded*/, uint16_
 hipError_t launch_maxpool(const uint16_t* in, uint16_t* out, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                           int relu_in, hipStream_t s);
 hipError_t launch_gray(const uint8_t* rgb, uint8_t* gray, size_t npix, hipStream_t s);
+// cv2 BGR2GRAY of one pixel, channels as given (the formula is stated at gray_kernel, craft_misc.hip); also pages.hip's derived gray plane
+__device__ __forceinline__ uint8_t bgr2gray_px(int c0, int c1, int c2) { return (uint8_t)((c2 * 9798 + c1 * 19235 + c0 * 3735 + (1 << 14)) >> 15); }
 hipError_t launch_ycc_to_rgb_gray(const uint8_t* ycc, int stride, uint8_t* rgb, uint8_t* gray, size_t npix, hipStream_t s);
 // jdcolor.c::ycc_rgb_convert of one pixel (the formulas are stated at ycc_to_rgb_gray_kernel, craft_misc.hip); also thumb.hip's last pass
 __device__ __forceinline__ void jpeg_ycc_to_rgb(int y, int cb, int cr, uint8_t* rgb) {
@@ -132,10 +134,17 @@ struct CropDesc {      // one recogniser input, filled on the host
     int rot;           // rotation_info variant: the stage-A image is np.rot90(resized crop, rot); rw x rh are its dimensions AFTER the rotation
     double Minv[9];    // dst -> src homography (already inverted)
 };
+struct CropPage {      // a gray page of its own shape (bbocr_readtext_pages): CropDesc::img indexes a device table of these
+    long long off;     // byte offset of the page's first pixel from the `gray` pointer of the launch
+    long long pitch;   // bytes per row
+    int H, W;
+};
 // stage_mask bit0: gather (warp) + cv2 resize into scratch; bit1: (PIL bicubic) + LUT + normalise + pad into out_bucket
+// pages != null: the source of crop d is the page pages[d.img] (its own bounds and pitch) instead of plane d.img of [B][H][W]
 hipError_t launch_crops(const uint8_t* gray, int H, int W, const CropDesc* descs_dev, int first, int count, int imgW, int any_warp,
                         int any_tall, uint8_t* wscratch, uint8_t* scratch, uint8_t* hscratch, const uint8_t* luts, uint16_t* out_bucket,
-                        int stage_mask, hipStream_t s, int wide_row_stride = 0, int gap = 0, int mode = 0);   // wide_row_stride > 0: ONE image [64][Wt], slot = first column
+                        int stage_mask, hipStream_t s, int wide_row_stride = 0, int gap = 0, int mode = 0,   // wide_row_stride > 0: ONE image [64][Wt], slot = first column
+                        const CropPage* pages = nullptr);
 // Recogniser tensor modes (bbocr_config::precision): REC_BF16 / REC_F16 = 16-bit elements; REC_SPLIT = the exact mode: the crop image
 // holds CODES (0 = padding zero, 1 + grey level otherwise -- conv0 rebuilds the fp32 input ((g/255 - 0.5)/0.5) exactly), every later
 // activation is a pair of fp16 tensors [hi C | lo C] per pixel with value = hi + lo / 2048 (lo scaled so that it stays in fp16's
@@ -208,6 +217,23 @@ hipError_t launch_ac_unpack(const uint32_t* bits, const int* label, int H, int W
 // ------------------------------------------------------------------ device pages: rows of packed pixels, the layouts of bbocr.h BBOCR_PAGE_*
 enum : int { PAGE_GRAY = 0, PAGE_BGR = 1, PAGE_RGB = 2, PAGE_YCC4 = 3, PAGE_YCC3 = 4 };
 __host__ __device__ constexpr int page_px_bytes(int layout) { return layout == PAGE_GRAY ? 1 : (layout == PAGE_YCC4 ? 4 : 3); }
+
+// ------------------------------------------------------------------ pages of mixed shapes -> the detector's and the recogniser's inputs (pages.hip)
+constexpr int PK_TILE_PX = 4096;                               // pixels per workgroup of the pack kernel: 16 per lane
+constexpr int PK_MAX_TILES = (1 << 24) - 1;                    // HIP launches fewer than 2^32 threads per grid dimension: 256 * tiles < 2^32
+struct PackPage {                                              // one page of a bbocr_readtext_pages call, as the pack kernel reads it
+    const uint8_t* rgb;                                        // [H][W][3], rows rgb_pitch bytes apart
+    const uint8_t* gray;                                       // [H][W], rows gray_pitch apart, or null: derived from rgb (bgr2gray_px)
+    long long rgb_pitch, gray_pitch;
+    long long rgb_off, gray_off;                               // byte offsets of the page's tight copies in the two staging buffers
+    int H, W;
+    int tile0;                                                 // first tile of this page in the flat tile list (ceil(H * W / PK_TILE_PX) tiles each)
+    int vec;                                                   // bit 0: RGB copy, bit 1: gray plane -- 16-byte accesses (pointers, pitches and offsets allow them)
+};
+int pack_page_vec(const PackPage& g, const uint8_t* rgb_staging, const uint8_t* gray_staging);   // the `vec` bits of a page whose other fields are set, for these staging buffers
+// every page's RGB tight into rgb_staging + rgb_off and its gray plane (given or derived) tight into gray_staging + gray_off: ONE launch over
+// the flat tile list of all n pages (ntiles = tile0 + tiles of the last page); pages_dev: the table on the device
+hipError_t launch_pack_pages(const PackPage* pages_dev, int n, int ntiles, uint8_t* rgb_staging, uint8_t* gray_staging, hipStream_t s);
 
 // ------------------------------------------------------------------ OCR-input thumbnail + JPEG round trip (thumb.hip), enhanced_extractor.py:486-512
 constexpr int TH_PRECISION_BITS = 22;                                             // Pillow Resample.c, 8 bpc

@@ -176,15 +176,15 @@ uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part) {
 
 // enqueue a part: descriptor upload, crops (stage A = gather / warp + cv2 resize when asked, stage B = AlignCollate into the wide image),
 // conv stack, pooled rows into seq_v
-static void rec_launch_part(bbocr_ctx* c, const uint8_t* gray, int H, int W, const RecPart& part, DevBuf& desc_buf, bool stage_a) {
+static void rec_launch_part(bbocr_ctx* c, const GrayPages& g, const RecPart& part, DevBuf& desc_buf, bool stage_a) {
     if (part.descs.empty()) return;
     EnqLock enq(c);                           // one feature part = one contiguous block on the compute stream
     const CropDesc* dd = rec_upload_descs(c, part, desc_buf);
     const int n = (int)part.descs.size(), Wt = (int)part.cols;
     auto crops = [&](uint16_t* wide, int stage) {
-        HIPCHK(launch_crops(gray, H, W, dd, 0, n, 0, part.any_warp, part.any_tall, (uint8_t*)c->crop_wscratch.p, (uint8_t*)c->crop_scratch.p,
+        HIPCHK(launch_crops(g.gray, g.H, g.W, dd, 0, n, 0, part.any_warp, part.any_tall, (uint8_t*)c->crop_wscratch.p, (uint8_t*)c->crop_scratch.p,
                             (uint8_t*)c->crop_hscratch.p, (const uint8_t*)c->crop_luts.p, wide, stage, c->stream, wide ? Wt : 0, wide ? REC_GAP : 0,
-                            wide ? rec_mode(c) : 0));
+                            wide ? rec_mode(c) : 0, g.tab_dev));
     };
     if (stage_a) crops(nullptr, 1);
     uint16_t* wide = rec_wide_image(c, part);
@@ -313,7 +313,7 @@ static std::vector<std::vector<int>> rec_split_runs(const bbocr_ctx* c, const st
 }
 
 // run one recognition pass over `sel` (indices into jobs); descs must already carry lut_off for a contrast pass.
-static void recognise_pass(bbocr_ctx* c, const uint8_t* gray, int H, int W, std::vector<BoxJob>& jobs, const std::vector<int>& sel,
+static void recognise_pass(bbocr_ctx* c, const GrayPages& g, std::vector<BoxJob>& jobs, const std::vector<int>& sel,
                            bool stage_a, std::vector<std::vector<int>>& texts, std::vector<double>& confs) {
     texts.assign(sel.size(), {});
     confs.assign(sel.size(), 0.0);
@@ -327,7 +327,7 @@ static void recognise_pass(bbocr_ctx* c, const uint8_t* gray, int H, int W, std:
         for (size_t i = 0; i < part.order.size(); ++i) part.order[i] = ks[part.order[i]];
         auto t0 = clk::now();
         c->seq_v.ensure(align_up(part.rows, 256) * 256 * 2 * rec_mul(c));
-        rec_launch_part(c, gray, H, W, part, c->crop_desc, stage_a);
+        rec_launch_part(c, g, part, c->crop_desc, stage_a);
         c->times[3] += (float)ms_since(t0);
         RecRun run;
         rec_add_tables(run, part, lstm_tile_seqs(rec_mode(c)));
@@ -381,11 +381,11 @@ static void rec_check_params(bbocr_ctx* c, const bbocr_params& p) {
 }
 
 // Reader.recognize's per-box branch: horizontal boxes first, then free boxes, page by page
-static void rec_plan_pages(const HostBoxes& hb, int b0, int b1, int H, int W, std::vector<BoxJob>& jobs, std::vector<int>& box_off) {
+static void rec_plan_pages(const HostBoxes& hb, int b0, int b1, const GrayPages& g, std::vector<BoxJob>& jobs, std::vector<int>& box_off) {
     for (int b = b0; b < b1; ++b) {
         for (const auto& hbx : hb.hori[b]) {
             BoxJob j;
-            if (plan_horizontal(hbx, b, H, W, j)) jobs.push_back(j);
+            if (plan_horizontal(hbx, b, g.h(b), g.w(b), j)) jobs.push_back(j);
         }
         for (const auto& fq : hb.freeb[b]) {
             BoxJob j;
@@ -413,11 +413,10 @@ void rec_layout_scratch(std::vector<BoxJob>& jobs, size_t first, size_t& a_total
 // pages existed (readtext_batch: while the last detector pass's CCL + host geometry run).  recognize_impl picks it up and adds the rest.
 // rec_early_begin enqueues the feature part of pages [0, pages) of a B-page batch; the buffers that must survive until the rest arrives (stage-A
 // crops for the contrast retry, pooled rows) are sized for the whole batch by extrapolation
-void rec_early_begin(bbocr_ctx* c, const uint8_t* gray, int pages, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p,
-                            RecEarly& e) {
+void rec_early_begin(bbocr_ctx* c, const GrayPages& g, int pages, int B, const HostBoxes& hb, const bbocr_params& p, RecEarly& e) {
     rec_check_params(c, p);
     e.box_off.assign(pages + 1, 0);
-    rec_plan_pages(hb, 0, pages, H, W, e.jobs, e.box_off);
+    rec_plan_pages(hb, 0, pages, g, e.jobs, e.box_off);
     if (e.jobs.empty()) return;
     rec_layout_scratch(e.jobs, 0, e.a_total, e.w_total);
     std::vector<int> all(e.jobs.size());
@@ -431,13 +430,13 @@ void rec_early_begin(bbocr_ctx* c, const uint8_t* gray, int pages, int B, int H,
     c->crop_luts.ensure(256);
     c->seq_v.ensure(align_up((size_t)((double)e.part.rows * grow), 256) * 256 * 2 * rec_mul(c));
     auto t0 = clk::now();
-    rec_launch_part(c, gray, H, W, e.part, c->crop_desc, true);
+    rec_launch_part(c, g, e.part, c->crop_desc, true);
     c->times[3] += (float)ms_since(t0);
     e.pages = pages;
     e.active = true;
 }
 
-void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, const HostBoxes& hb, const bbocr_params& p,
+void recognize_impl(bbocr_ctx* c, const GrayPages& g, int B, const HostBoxes& hb, const bbocr_params& p,
                            std::vector<BoxJob>& jobs, std::vector<int>& box_off, RecEarly* early) {
     rec_check_params(c, p);
     jobs.clear();
@@ -457,11 +456,11 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
         jobs = std::move(early->jobs);
         n_early = jobs.size();
         for (int b = 0; b <= early->pages; ++b) box_off[b] = early->box_off[b];
-        rec_plan_pages(hb, early->pages, B, H, W, jobs, box_off);
+        rec_plan_pages(hb, early->pages, B, g, jobs, box_off);
     }
     for (int b = 0; b < B && !resume; ++b) {
         if (nrot == 0) {
-            rec_plan_pages(hb, b, b + 1, H, W, jobs, box_off);
+            rec_plan_pages(hb, b, b + 1, g, jobs, box_off);
             continue;
         } else {
             std::vector<BoxJob> page;
@@ -471,7 +470,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
             }
             for (const auto& hbx : hb.hori[b]) {
                 BoxJob j;
-                if (plan_horizontal(hbx, b, H, W, j)) page.push_back(j);
+                if (plan_horizontal(hbx, b, g.h(b), g.w(b), j)) page.push_back(j);
             }
             std::stable_sort(page.begin(), page.end(), [](const BoxJob& x, const BoxJob& y) { return x.quad[1] < y.quad[1]; });
             int page_w = 64;                      // max(max_width, imgH); max_width = ceil(max ratio) * 64 = the widest own bucket
@@ -527,7 +526,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
         if (early->part.rows + part2.rows <= rec_max_rows(c)) {
             c->seq_v.ensure_keep(align_up(early->part.rows + part2.rows, 256) * 256 * 2 * rec_mul(c), early->part.rows * 256 * 2 * rec_mul(c));
             auto t0 = clk::now();
-            rec_launch_part(c, gray, H, W, part2, c->crop_desc2, true);
+            rec_launch_part(c, g, part2, c->crop_desc2, true);
             c->times[3] += (float)ms_since(t0);
             rec_add_tables(run, part2, lstm_tile_seqs(rec_mode(c)));
             rec_finish(c, run, texts, confs);
@@ -535,7 +534,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
             rec_finish(c, run, texts, confs);
             std::vector<std::vector<int>> t2;
             std::vector<double> c2;
-            recognise_pass(c, gray, H, W, jobs, rest, true, t2, c2);
+            recognise_pass(c, g, jobs, rest, true, t2, c2);
             for (size_t i = 0; i < rest.size(); ++i) { texts[rest[i]] = t2[i]; confs[rest[i]] = c2[i]; }
         }
         early->active = false;
@@ -548,7 +547,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
         c->crop_luts.ensure(256);
         std::vector<int> all(jobs.size());
         for (size_t i = 0; i < jobs.size(); ++i) all[i] = (int)i;
-        recognise_pass(c, gray, H, W, jobs, all, true, texts, confs);
+        recognise_pass(c, g, jobs, all, true, texts, confs);
     }
     for (size_t i = 0; i < jobs.size(); ++i) { jobs[i].text = texts[i]; jobs[i].conf = confs[i]; }
     // second round: adjust_contrast_grey for low-confidence boxes
@@ -584,7 +583,7 @@ void recognize_impl(bbocr_ctx* c, const uint8_t* gray, int B, int H, int W, cons
         HIPCHK(hipMemcpyAsync(c->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, c->stream));   // `luts` outlives the pass below, which ends synchronised
         std::vector<std::vector<int>> t2;
         std::vector<double> c2;
-        recognise_pass(c, gray, H, W, jobs, redo, false, t2, c2);
+        recognise_pass(c, g, jobs, redo, false, t2, c2);
         for (size_t k = 0; k < redo.size(); ++k) {
             BoxJob& j = jobs[redo[k]];
             j.d.lut_off = -1;

@@ -168,7 +168,8 @@ def ocr_input_image(image_path, image_index=None):
 
 
 def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
-                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, device_decode=False, **readtext_kw):
+                  edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, device_decode=False, mixed=None,
+                  **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
     batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
@@ -179,7 +180,8 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     and plans it (``bbocr_host_jpeg_plan``); baseline JPEG files -- the thumbnails included -- reach the card as their bytes and are
     decoded there, a whole batch by one call (csrc/jpegdec.hip, identical pixels); every other file, and a file whose data turns out
     damaged, takes the host decode as before.  With the crop settings the page is read like ``cv2.imread``, EXIF orientation included, and
-    ``device_decode=True`` does that on the card as well (``preprocess.imread_bgr_device``: csrc/jpegdec.hip + csrc/orient.hip)."""
+    ``device_decode=True`` does that on the card as well (``preprocess.imread_bgr_device``: csrc/jpegdec.hip + csrc/orient.hip).
+    ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches."""
     from .preprocess import ocr_input_device
 
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
@@ -196,7 +198,7 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
         decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once, device_decode)
     else:
         decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode)
-    res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, **readtext_kw)
+    res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, mixed=mixed, **readtext_kw)
     return {i: " ".join(t[1] for t in r) for i, r in res.items()}
 
 
@@ -279,6 +281,62 @@ KINDS = {
 }
 
 
+def _mixed_stack(ids, pages):
+    """``pages``: the decode callback's ``(kind, a, b)`` tuples themselves -- a mixed batch holds pages of any kind and shape"""
+    return Batch("mixed", ids, host=list(pages))
+
+
+def _mixed_to_device(reader, b):
+    """Every page of a mixed batch as ``(rgb_dev [H,W,3], gray_dev [H,W] or None)``, by its own kind's upload step -- kept as a list, not
+    stacked.  ``"jpg"`` pages of one decoded shape share one decode call.  ``status``: non-zero where a page did not reach the card.
+    A failure is kept per page, as the reference's failure rule is per page: such a page is read on its own from its host copy
+    (``_read_batch``) while the others still share the call.  The price: an upload failure that hits EVERY page (the card out of memory)
+    turns the batch into single-page host reads without an error -- slower, same results -- exactly as a failed ``_upload`` does for a
+    batch of one shape."""
+    from .reader import Reader
+
+    n = len(b.ids)
+    dev, b.status = [None] * n, [-1] * n
+    jpg = {}
+    for k, (kind, a, g) in enumerate(b.host):
+        try:
+            if kind == "jpg":
+                jpg.setdefault(a.shape, []).append(k)
+                continue
+            if kind == "dev":                                  # already on the card: the (possibly strided) views are read in place
+                dev[k], b.status[k] = (a, g), 0
+                continue
+            sub = KINDS[kind].stack(b.ids[k:k + 1], [(a, g)])
+            d = KINDS[kind].to_device(reader, sub)
+            rgb, gray = reader.pages_from_ycc(d) if kind == "ycc" else d
+            dev[k], b.status[k] = (rgb[0], None if gray is None else gray[0]), 0
+        except Exception:
+            pass
+    for ks in jpg.values():
+        try:
+            t, status = reader.decode_jpeg_batch([b.host[k][1] for k in ks], padded=True)
+            rgb, gray = Reader.pages_from_jpeg(reader, t)
+            for j, k in enumerate(ks):
+                if status[j] == 0:
+                    dev[k], b.status[k] = (rgb[j], gray[j]), 0
+        except Exception:
+            pass
+    return dev
+
+
+def _mixed_read_page(reader, b, k, kw):
+    kind, a, g = b.host[k]
+    sub = KINDS[kind].stack(b.ids[k:k + 1], [(a, g)])
+    return KINDS[kind].read_page(reader, sub, 0, kw)
+
+
+# pages of any kind and shape in one batch (``mixed=True``): ONE ``readtext_pages`` call reads the pages that reached the card; the retry
+# unit is the page, read as its own kind reads it
+KINDS["mixed"] = Kind(stack=_mixed_stack, to_device=_mixed_to_device,
+                      read=lambda r, b, kw: r.readtext_pages([b.dev[k] for k, s in enumerate(b.status) if s == 0], **kw),
+                      read_host=None, read_page=_mixed_read_page)
+
+
 def _page_key(kind, a):
     """Grouping key of a decoded page: every kind's first element carries the page's shape (a ``JpegPage``: that of its decode)"""
     return kind, tuple(a.shape)
@@ -320,17 +378,26 @@ def _default_decode_workers(reader, n_files):
     return max(1, min(8, share // 2, n_files))
 
 
-def _assemble(decode_one, idxs, max_batch, decode_workers, batches):
+def _assemble(decode_one, idxs, max_batch, decode_workers, batches, mixed=False):
     """Assembler thread: decode pool -> groups of one kind and shape -> ``batches`` (a full group travels as one ``Batch``; None ends it).
+    ``mixed``: ONE group for every kind and shape, closed by page count and by the pixel budget (``reader.mixed_pixel_budget``).
     Back-pressure end to end: at most `window` decoded pages exist outside the two assembled batches the queue may hold (a decode is only
     submitted once a slot is free, and a slot is released when its page has been copied into a batch), so the resident set is bounded by
     ~4 batches however many files are queued."""
     window = max(2 * max_batch, 2 * decode_workers)
     slots = threading.Semaphore(window)
     groups = {}
+    open_px = 0                                                 # mixed: pixels of the pages in the one open group
+    if mixed:
+        from .reader import mixed_pixel_budget
+
+        budget = mixed_pixel_budget()
 
     def flush(key):
+        nonlocal open_px
         group = groups.pop(key)
+        if key == ("mixed",):
+            open_px = 0
         batches.put(KINDS[key[0]].stack([i for i, _ in group], [page for _, page in group]))
         for _ in group:
             slots.release()
@@ -357,8 +424,16 @@ def _assemble(decode_one, idxs, max_batch, decode_workers, batches):
                     slots.release()
                     continue
                 kind, a, b = page                               # the decode callback's tuple ends here
-                key = _page_key(kind, a)
-                groups.setdefault(key, []).append((i, (a, b)))
+                if mixed:
+                    key = ("mixed",)
+                    px = a.shape[0] * a.shape[1]
+                    if key in groups and open_px + px > budget:
+                        flush(key)                              # the page would overrun the pixel budget: it opens the next batch
+                    groups.setdefault(key, []).append((i, page))
+                    open_px += px
+                else:
+                    key = _page_key(kind, a)
+                    groups.setdefault(key, []).append((i, (a, b)))
                 if len(groups[key]) >= max_batch:
                     flush(key)
                 elif not pending and not done_submitting:
@@ -409,7 +484,8 @@ def _device_stage(reader, batches, texts, kw):
             fut.result()
 
 
-def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, **readtext_kw):
+def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, mixed=None,
+               **readtext_kw):
     """``{index: readtext result}`` for the files ``image_paths[i]``, i in ``indices`` (default: all): the result lists
     ``Reader.readtext(path)`` returns page by page, from 64-page device batches.  A page whose decode or OCR fails maps to ``[]``.
 
@@ -422,7 +498,15 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     ``("jpg", JpegPage, None)``.  ``device_decode=True`` (or a ``decode`` that returns ``"jpg"`` pages): baseline JPEG files are only read
     and planned here and travel as their bytes, grouped by decoded shape; the upload stage decodes a group on the card with one call,
     straight into the batch tensor.  Three overlapped stages: decode pool -> assembler thread (``_assemble``) -> this thread
-    (``_device_stage``: upload, two device calls in flight, result strings); what they hand on is a ``Batch`` of one of the ``KINDS``."""
+    (``_device_stage``: upload, two device calls in flight, result strings); what they hand on is a ``Batch`` of one of the ``KINDS``.
+    ``mixed`` (None: the environment variable ``BBOCR_MIXED_BATCH``, off unless ``1``): batches are closed by page count
+    (``max_batch``, at most ``BBOCR_MAX_DEVICE_BATCH``) and a pixel budget instead of by shape, pages of all four kinds travel together, and each
+    batch is read by one ``Reader.readtext_pages`` call; same results, same failure rule."""
+    from .reader import mixed_batch_enabled
+
+    mixed = mixed_batch_enabled(mixed)
+    if mixed:
+        max_batch = max(1, min(max_batch, int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))))
     if decode is None:
         decode = _plain_input_device if device_decode else _plain_input
     if indices is None:
@@ -441,7 +525,7 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
             return None
 
     batches = queue.Queue(maxsize=2)
-    worker = threading.Thread(target=_assemble, args=(decode_one, idxs, max_batch, decode_workers, batches), daemon=True)
+    worker = threading.Thread(target=_assemble, args=(decode_one, idxs, max_batch, decode_workers, batches, mixed), daemon=True)
     worker.start()
     _device_stage(reader, batches, texts, readtext_kw)
     worker.join()

@@ -312,6 +312,32 @@ def get_paragraph(raw_result, x_ths=1, y_ths=0.5, mode="ltr"):
     return result
 
 
+def mixed_batch_enabled(mixed=None):
+    """The ``mixed`` keyword of the batching callers: None means the environment variable ``BBOCR_MIXED_BATCH`` (``1`` = on; off when unset)"""
+    return os.environ.get("BBOCR_MIXED_BATCH", "0").strip() == "1" if mixed is None else bool(mixed)
+
+
+def mixed_pixel_budget():
+    """Pixels per mixed device batch: ``BBOCR_MIXED_PIXEL_BUDGET``, default 64 pages of 1280x960"""
+    return int(os.environ.get("BBOCR_MIXED_PIXEL_BUDGET", str(64 * 1280 * 960)))
+
+
+def mixed_batches(pixels, max_pages, budget=None):
+    """Indices ``0 .. len(pixels) - 1`` cut, in order, into batches of at most ``max_pages`` pages and at most ``budget`` pixels (a page
+    larger than the budget travels alone)"""
+    budget = mixed_pixel_budget() if budget is None else budget
+    out, cur, used = [], [], 0
+    for i, px in enumerate(pixels):
+        if cur and (len(cur) >= max_pages or used + px > budget):
+            out.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += px
+    if cur:
+        out.append(cur)
+    return out
+
+
 def auto_host_threads(local_world=None, cpus=None):
     """``bbocr_config::host_threads`` for this process: 0 (the library sizes its pools from the process's own CPU share) unless several
     ranks share the node un-pinned (torchrun sets LOCAL_WORLD_SIZE): then this rank's share of the CPUs it may run on, at most 16."""
@@ -560,6 +586,57 @@ class Reader:
         res = C.POINTER(_lib.bbocr_result)()
         gp = C.c_void_p(gray_dev.data_ptr()) if gray_dev is not None else C.c_void_p(None)
         self._check(self._lib.bbocr_readtext_batch(self._h, C.c_void_p(rgb_dev.data_ptr()), gp, B, H, W, C.byref(p), C.byref(res)))
+        return self._shape_results(res, kw)
+
+    def _page_view(self, t, name, px):
+        """A page about to cross the C ABI as pointer + row pitch: a uint8 tensor ``[H,W,3]`` (``px`` 3) or ``[H,W]`` (``px`` 1) on this
+        Reader's device.  A view with packed pixels and a positive row stride is taken as it is -- only one whose pixels are not packed (a
+        channel flip, a column step) is made contiguous first.  -> ``(tensor to keep alive, pitch in bytes)``; ``ValueError`` otherwise."""
+        torch = self._torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch uint8 device tensor, got {type(t).__name__}")
+        if not t.is_cuda or t.device.index != self.device_index:
+            raise ValueError(f"{name}: tensor lives on {t.device}, this Reader runs on {self.device}")
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{name}: dtype must be uint8, got {t.dtype}")
+        if t.ndim != (3 if px == 3 else 2) or (px == 3 and t.shape[2] != 3) or min(t.shape) <= 0:
+            raise ValueError(f"{name}: bad shape {tuple(t.shape)}, expected " + ("[H,W,3]" if px == 3 else "[H,W]"))
+        packed = t.stride(1) == px and (px == 1 or t.stride(2) == 1)
+        if not packed or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * px):
+            t = t.contiguous()
+        return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1] * px)
+
+    def readtext_pages(self, pages, **kw):
+        """Pages of individually given shapes already resident in HBM, read by ONE device call (``bbocr_readtext_pages``): ``pages`` is a
+        list of uint8 device tensors ``[H,W,3]`` or of ``(rgb, gray)`` pairs (``gray`` ``[H,W]`` or None: derived on the card, as
+        ``readtext_device`` derives it).  Strided views -- crops of larger device pages -- are passed by pointer and row pitch and read in
+        place.  Keywords and return value are ``readtext_device``'s: one result list per page, equal to what ``readtext_device`` returns
+        for each page on its own."""
+        pages = list(pages)
+        if not pages:
+            raise ValueError("readtext_pages: no pages")
+        arr = (_lib.bbocr_page * len(pages))()
+        keep = []
+        for k, page in enumerate(pages):
+            rgb, gray = page if isinstance(page, (tuple, list)) else (page, None)
+            rgb, pitch = self._page_view(rgb, f"page {k} rgb", 3)
+            keep.append(rgb)
+            arr[k].dev_rgb, arr[k].H, arr[k].W, arr[k].rgb_pitch = rgb.data_ptr(), rgb.shape[0], rgb.shape[1], pitch
+            if gray is not None:
+                gray, gpitch = self._page_view(gray, f"page {k} gray", 1)
+                if tuple(gray.shape) != tuple(rgb.shape[:2]):
+                    raise ValueError(f"page {k} gray: bad shape {tuple(gray.shape)}, expected {tuple(rgb.shape[:2])}")
+                keep.append(gray)
+                arr[k].dev_gray, arr[k].gray_pitch = gray.data_ptr(), gpitch
+        p = self._params(kw)
+        res = C.POINTER(_lib.bbocr_result)()
+        self._torch.cuda.current_stream(self.device_index).synchronize()     # copies made above; the library runs on its own stream
+        self._check(self._lib.bbocr_readtext_pages(self._h, arr, len(pages), C.byref(p), C.byref(res)))
+        del keep
+        return self._shape_results(res, kw)
+
+    def _shape_results(self, res, kw):
+        """The tail of a pipeline call: ``bbocr_result`` -> per-page lists, through ``get_paragraph`` when asked for"""
         if kw.get("paragraph"):
             # Reader.readtext tail: get_paragraph on the raw result, then detail == 0 keeps the text only
             pages = [get_paragraph(page, x_ths=kw.get("x_ths", 1.0), y_ths=kw.get("y_ths", 0.5), mode="ltr") for page in self._collect(res, 1)]
@@ -701,6 +778,23 @@ class Reader:
         rgb, gray = self.pages_from_ycc(self._to_dev(ycc))
         return self.readtext_device(rgb, gray, **kw)
 
+    def _stream(self, submit, batches, in_flight):
+        """``submit(executor, batch) -> future`` for every batch, results IN ORDER, ``in_flight`` calls running and one batch queued behind
+        them: the one loop of ``readtext_stream`` and ``readtext_pages_stream``.  A lazy producer (H2D copies) is drained no further
+        ahead than that, so at most ``in_flight + 1`` batches are resident on the card, and each result is yielded as soon as it is next."""
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+
+        in_flight = max(1, int(in_flight))
+        with ThreadPoolExecutor(max_workers=in_flight, thread_name_prefix="bbocr-call") as ex:
+            pending = deque()
+            for b in batches:
+                pending.append(submit(ex, b))
+                if len(pending) > in_flight:                 # one batch queued behind the running ones: a worker never waits for the producer
+                    yield pending.popleft().result()
+            while pending:
+                yield pending.popleft().result()
+
     def readtext_stream(self, batches, in_flight=2, **kw):
         """Device page batches in, per-batch results out, IN ORDER, with up to ``in_flight`` calls running on this Reader at once.
 
@@ -709,19 +803,18 @@ class Reader:
         thread finishes box geometry, CTC read-back and result marshalling.  ``batches`` yields uint8 ``[B,H,W,3]`` device tensors or
         ``(rgb, gray)`` pairs (it may produce them lazily, e.g. H2D copies: it is drained one batch ahead of the workers).  Results are those
         of calling ``readtext_device`` batch by batch."""
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
 
-        in_flight = max(1, int(in_flight))
-        with ThreadPoolExecutor(max_workers=in_flight, thread_name_prefix="bbocr-call") as ex:
-            pending = deque()
-            for b in batches:
-                rgb, gray = b if isinstance(b, tuple) else (b, None)
-                pending.append(ex.submit(self.readtext_device, rgb, gray, **kw))
-                if len(pending) > in_flight:                 # one batch queued behind the running ones: a worker never waits for the producer
-                    yield pending.popleft().result()
-            while pending:
-                yield pending.popleft().result()
+        def submit(ex, b):
+            rgb, gray = b if isinstance(b, tuple) else (b, None)
+            return ex.submit(self.readtext_device, rgb, gray, **kw)
+
+        return self._stream(submit, batches, in_flight)
+
+    def readtext_pages_stream(self, batches, in_flight=2, **kw):
+        """``readtext_stream`` for pages of mixed shapes: ``batches`` yields page LISTS as ``readtext_pages`` takes them (it may produce them
+        lazily, drained one batch ahead of the workers, as there), each list is one ``readtext_pages`` call, and the results are those of
+        calling it list by list, in order."""
+        return self._stream(lambda ex, b: ex.submit(self.readtext_pages, b, **kw), batches, in_flight)
 
     def readtext(self, image, decoder="greedy", beamWidth=5, batch_size=1, workers=0, allowlist=None, blocklist=None, detail=1,
                  rotation_info=None, paragraph=False, min_size=20, contrast_ths=0.1, adjust_contrast=0.5, filter_ths=0.003,
@@ -749,8 +842,10 @@ class Reader:
         result = self.readtext_device(rgb_dev, gray_dev, **kw)[0]
         return format_output(result, output_format, paragraph, detail)
 
-    def readtext_batched(self, image, n_width=None, n_height=None, **kw):
-        """List (or 4-D array) of pages -> list of per-page results.  Equal-size pages share one device batch."""
+    def readtext_batched(self, image, n_width=None, n_height=None, mixed=None, **kw):
+        """List (or 4-D array) of pages -> list of per-page results.  Equal-size pages share one device batch.  ``mixed`` (None: the
+        environment variable ``BBOCR_MIXED_BATCH``, off unless it is ``1``): pages of ANY sizes share device batches -- closed by page count
+        and a pixel budget (``mixed_batches``), each read by one ``readtext_pages`` call, two calls in flight; same results."""
         self._unsupported(kw.get("decoder", "greedy"), kw.get("allowlist"), kw.get("blocklist"), kw.get("rotation_info"),
                           kw.get("paragraph", False), kw.get("output_format", "standard"))
         output_format = kw.pop("output_format", "standard")
@@ -763,10 +858,17 @@ class Reader:
             pages = [(np.asarray(Image.fromarray(a).resize((n_width, n_height), Image.BILINEAR)),
                       np.asarray(Image.fromarray(g).resize((n_width, n_height), Image.BILINEAR))) for a, g in pages]
         out = [None] * len(pages)
+        max_pages = int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))     # pages per device batch; larger groups stream, two batches in flight
+        if mixed_batch_enabled(mixed):
+            chunks = mixed_batches([a.shape[0] * a.shape[1] for a, _ in pages], max_pages)
+            feed = ([(self._to_dev(pages[i][0]), self._to_dev(pages[i][1])) for i in ch] for ch in chunks)
+            for ch, res in zip(chunks, self.readtext_pages_stream(feed, **kw)):
+                for i, r in zip(ch, res):
+                    out[i] = format_output(r, output_format, kw.get("paragraph", False), kw.get("detail", 1))
+            return out
         by_shape = {}
         for i, (a, g) in enumerate(pages):
             by_shape.setdefault(a.shape, []).append(i)
-        max_pages = int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))     # pages per device batch; larger groups stream, two batches in flight
         for _, idxs in by_shape.items():
             chunks = [idxs[k:k + max_pages] for k in range(0, len(idxs), max_pages)]
             # (lists: the pages reach the card in one upload call per batch, without a host-side np.stack)
@@ -779,7 +881,7 @@ class Reader:
     def readtext_files(self, paths, max_batch=64, decode_workers=None, **kw):
         """Image FILES in, ``Reader.readtext(path)``'s result per file out (same order), through the decode pool / upload stage / two device
         batches in flight of ``extractor_batch.read_files``: JPEG files are decoded once (YCbCr triples), pages of one size share device
-        batches.  A file that cannot be decoded or read maps to ``[]``."""
+        batches -- with ``mixed=True`` (None: ``BBOCR_MIXED_BATCH``) pages of any sizes do.  A file that cannot be decoded or read maps to ``[]``."""
         from .extractor_batch import read_files
 
         paths = list(paths)

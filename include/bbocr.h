@@ -205,6 +205,36 @@ int bbocr_recognize(bbocr_ctx* ctx, const uint8_t* dev_gray, int B, int H, int W
 int bbocr_readtext_batch(bbocr_ctx* ctx, const uint8_t* dev_rgb, const uint8_t* dev_gray, int B, int H, int W, const bbocr_params* p,
                          bbocr_result** out);
 
+/* ---- pages of mixed shapes in one call ----
+ * One page of bbocr_readtext_pages: uint8 RGB in device memory, rows rgb_pitch bytes apart, and optionally its gray plane.  A strided
+ * view -- a crop of a larger device page -- is a pointer + pitch and is read in place; no byte outside the H rows of W pixels is read
+ * (the padding of a view may belong to another tensor).  Pages may start at any byte and have any pitch >= the row. */
+typedef struct bbocr_page {
+    const uint8_t* dev_rgb;   /* [H][W][3] uint8, device */
+    const uint8_t* dev_gray;  /* [H][W] uint8, device, or NULL: derived from dev_rgb as bbocr_readtext_batch derives it */
+    int H, W;
+    long long rgb_pitch, gray_pitch;   /* bytes per row; 0 = tight (3 * W, W) */
+} bbocr_page;
+/* all stages in one call for n pages of individually given shapes: the result is what n one-page bbocr_readtext_batch calls return, bit
+ * for bit, n_images == n in the caller's order.  One launch (csrc/pages.hip) packs the pages shape group by shape group -- two pages are
+ * in one group when their (H, W) are equal -- the detector runs group after group with no host wait in between, box extraction of a
+ * pass overlaps the next pass, and ONE recognition pass reads the crops of all pages, whatever page they came from.  Every work buffer
+ * is sized before the first pass is queued.  bbocr_stage_times: [0] is the detector's GPU span over all groups.  BBOCR_ERR_ARG before
+ * anything is queued: n <= 0 or n > 65535, a null dev_rgb, H or W <= 0 or H * W >= 2^30, a pitch smaller than the row, a page that
+ * collapses to zero size under canvas_size / mag_ratio. */
+int bbocr_readtext_pages(bbocr_ctx* ctx, const bbocr_page* pages, int n, const bbocr_params* p, bbocr_result** out);
+/* host only, no GPU: the plan bbocr_readtext_pages makes of a page list (it runs this very function); the pointers of the pages are only
+ * compared with NULL.  group_of_page [n]: groups are numbered by first appearance; slot_in_group [n]: position among the group's pages, in
+ * the caller's order; rgb_off / gray_off [n]: byte offset of the page's tight copy in the RGB / gray staging buffer -- a group's pages
+ * stand back to back in slot order, [nb][H][W][3] and [nb][H][W], groups in number order, every group's block at a multiple of 256;
+ * *n_groups; staging_bytes [2]: size of the RGB and of the gray staging buffer.  Any output pointer may be NULL.  p NULL: the defaults. */
+int bbocr_host_pages_plan(const bbocr_page* pages, int n, const bbocr_params* p, int* group_of_page, int* slot_in_group, long long* rgb_off,
+                          long long* gray_off, int* n_groups, long long* staging_bytes);
+/* the pack launch alone (parity tests): the pages into caller-owned staging buffers of bbocr_host_pages_plan's sizes (default
+ * parameters), laid out as it says.  The staging buffers may start at any byte: a page is moved with 16-byte accesses where its source
+ * pointer, its pitch and the ADDRESS of its staging copy (base + offset) are multiples of 16, byte by byte otherwise */
+int bbocr_op_pack_pages(bbocr_ctx* ctx, const bbocr_page* pages, int n, uint8_t* dev_rgb_staging, uint8_t* dev_gray_staging);
+
 void bbocr_free_boxlist(bbocr_boxlist* b);
 void bbocr_free_result(bbocr_result* r);
 
@@ -269,6 +299,12 @@ int bbocr_upload_pages(bbocr_ctx* ctx, const void* const* host_pages, int n, siz
  * branch); mode 1..4: EVERY box at the forced width imgW, rotated by np.rot90(crop, mode - 1) (the batched branch rotation_info takes) */
 int bbocr_op_crops(bbocr_ctx* ctx, const uint8_t* dev_gray, int H, int W, const int* hori, int n_hori, const double* free_q, int n_free,
                    int imgW, float contrast, uint16_t* dev_out, int* n_out, int mode);
+/* the same for explicit boxes of n gray pages of their own shapes (the page-table variant of the crop kernels, what bbocr_readtext_pages
+ * launches): pages[k].dev_gray / gray_pitch / H / W are read (in place; dev_rgb is ignored), page k's boxes are hori [hori_off[k],
+ * hori_off[k+1]) and free_q [free_off[k], free_off[k+1]).  dev_out receives the crops page after page, per page in bbocr_op_crops' order:
+ * what n bbocr_op_crops calls write, back to back. */
+int bbocr_op_crops_pages(bbocr_ctx* ctx, const bbocr_page* pages, int n, const int* hori, const int* hori_off, const double* free_q,
+                         const int* free_off, int imgW, float contrast, uint16_t* dev_out, int* n_out, int mode);
 
 /* ---- OCR pre-processing chain of the reference ----
  * pipeline_demo/ocr_testing/preprocessing/image_preprocessor.py::preprocess_for_book_cover (:147-160) on ONE decoded page:
