@@ -6,7 +6,8 @@
 //
 // Mapping (D = A x B per v_mfma_f32_16x16x32_bf16):
 //   A = weights   [16 couts][32 k]   lane l: row l&15, k = 8(l>>4)+j      (LDS image == global packed image, glds copy)
-//   B = activation[32 k][16 pixels]  lane l: pixel l&15, k = 8(l>>4)+j    (LDS patch [4 channel-groups][NP pixels] x 16 B)
+//   B = activation[32 k][16 pixels]  lane l: pixel l&15, k = 8(l>>4)+j    (LDS patch: conv3x3_dma_kernel [2 planes][NP pixels][2 groups] x 16 B,
+//                                                                          the other kernels [4 channel-groups][NP pixels] x 16 B)
 //   D             [16 couts][16 px]  lane l: pixel l&15, couts 4(l>>4)+r  -> cout permutation in the packed weights makes
 //                                     each lane own two runs of 8 contiguous couts: per store instruction the four lane
 //                                     groups of a pixel write 64 contiguous bytes (see conv_epilogue).
@@ -674,8 +675,16 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv_mfma_kernel(const ConvAr
 // Variant for 3x3 / pad 1 / dilation 1 layers (every big layer of CRAFT and the CRNN): BOTH operands reach LDS by LDS-DMA
 // (global_load_lds_dwordx4), so the main loop holds no global->register loads at all, hipcc inserts no vmcnt waits of its
 // own, and the schedule is fully static:
-//   * activation patch: wave w copies channel group w of the NEXT chunk, one 64-pixel DMA per tap for the first NPB taps
-//     (per-lane source address = the pixel's 16 bytes, or a zero page for padding); LDS image [group][NP = 64*NPB pixels];
+//   * activation patch of the NEXT chunk, NPB DMAs per wave dealt over the first taps.  LDS image: [2 planes h][NP pixels][2 groups] x 16 B,
+//     channel group g of pixel p at h * NP * 32 + p * 32 + (g & 1) * 16 with h = g >> 1.  One DMA covers 32 pixels of one plane: lane L
+//     fetches the 16 bytes of group 2h + (L & 1) of pixel (L >> 1) (or a zero page for padding), so a wave-instruction reads 32-byte
+//     runs from 32 pixels (not 16 bytes from 64) and lands as 1 KiB contiguous.  Wave w owns plane w >> 1 and its 32-pixel blocks
+//     (w & 1), (w & 1) + 2, ...; where the plane has an odd number of blocks (NPS = 324: 11) the odd wave fetches its last block twice --
+//     every wave issues exactly NPB DMAs per chunk, the counted vmcnt schedule below depends on it.
+//     The image is linear in the pixel index (every fragment read is base + immediate) and free of bank conflicts for ds_read_b128 at
+//     every tap shift and every NP: a 16-lane read group is 8 consecutive pixels of an even group (even 16-byte slots, 8 distinct ones
+//     mod 16) and the other 8 pixels of its odd twin (odd slots); the two planes belong to different read groups.  ([4 groups][NP]
+//     needed NP % 16 == 0 for that: the 324-pixel patch of conv1_2 conflicted between its group planes.)
 //   * weights: slice ks+RING-1 is issued at k-step ks, first among the k-step's VMEM operations;
 //   * every k-step ends with `s_waitcnt vmcnt(N)` + s_barrier where N (a compile-time constant per tap) is the number of
 //     operations issued after slice ks+1, so DMAs ride across RING-2 barriers and nothing ever drains to vmcnt(0).
@@ -696,12 +705,14 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
     static_assert(NW == 4, "one wave per 8-channel group of the patch");
     constexpr int WBUF = BN * 64, WPIECES = WBUF / 16, WPT = WPIECES / NT;
     static_assert(WPIECES % NT == 0 && (RING == 3 || RING == 4), "uniform DMA issue");
-    // NPS: pixels per channel group in the LDS patch image; NPS < NPB*64 (exactly PH*PW) trims the patch to what the tile needs,
-    // the last 64-pixel DMA block then runs with the lanes beyond NPS masked off
+    // NPS: pixels in the LDS patch image; NPS < NPB*64 (exactly PH*PW) trims the patch to what the tile needs, the last 32-pixel DMA block
+    // of a plane then runs with the lanes beyond NPS masked off
     constexpr int NP = NPS, PSLOTS = NTAP + 1 - RING;     // taps 0 .. NTAP-RING may issue patch DMAs
     constexpr int PPER = (NPB + PSLOTS - 1) / PSLOTS;     // patch DMA blocks per tap at most
     static_assert(NPS <= NPB * 64 && NPS > (NPB - 1) * 64 && NPS % 4 == 0, "patch size");
     static_assert(PSLOTS >= 1 && PPER * PSLOTS >= NPB, "patch does not fit the DMA schedule");
+    constexpr int NBLK = (NPS + 31) / 32;                 // 32-pixel DMA blocks per plane: 2 * NPB, or one fewer (then one is fetched twice)
+    static_assert(NBLK == 2 * NPB || NBLK == 2 * NPB - 1, "every wave issues NPB patch DMAs per chunk");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const wbuf = smem;                    // [RING][WBUF]
     unsigned char* const pbuf = smem + RING * WBUF;      // [2][NP*64]
@@ -737,7 +748,12 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
         g.oy0 = ty * a.TH; g.ox0 = tx * a.TW;
         g.wsrc = (const unsigned char*)a.wpk + (size_t)g.nt * nk * WBUF;
     };
-    // per-lane source pixel of each 64-pixel patch block (or -1: padding -> zero page)
+    // the wave's i-th 32-pixel block of its plane (wave-uniform); beyond the last block: the one fetched before, again
+    auto blk_of = [&](int i) {
+        const int b = 2 * i + (wave & 1);
+        return (NBLK == 2 * NPB || b < NBLK) ? b : b - 2;
+    };
+    // per-lane source pixel of each of the wave's patch blocks (or -1: padding -> zero page)
     int spix[NPB];
     const int pw_magic = (65536 + a.PW - 1) / a.PW;     // pix / PW == (pix * magic) >> 16 exactly for pix < 448, PW <= 66
     const int stack_magic = ((1 << 20) + a.stack) / (a.stack + 1);   // vy / (stack+1) == (vy * magic) >> 20 (launch_conv checks the exactness bound)
@@ -745,7 +761,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
         const int iy0 = g.oy0 - PAD, ix0 = g.ox0 - PAD;
 #pragma unroll
         for (int pb = 0; pb < NPB; ++pb) {
-            const int pix = pb * 64 + lane;
+            const int pix = blk_of(pb) * 32 + (lane >> 1);
             const int py = (pix * pw_magic) >> 16, px = pix - py * a.PW;
             int ly = iy0 + py;
             const int lx = ix0 + px;                                // sub-lattice coordinates
@@ -768,16 +784,18 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
     geom(tile, cur);
     if constexpr (!FUSE1) geom_pix(cur);
 
+    const size_t lane_c8 = (lane & 1) * 8;       // lane pair = the two channel groups of a plane (the addend of the address multiply-add)
     auto issue_p = [&](int sp, int chunk, int par, auto pb_c) {
         constexpr int pb = decltype(pb_c)::value;
         const int c = chunk * 32;
         const bool s0 = c < a.C0;
         const uint16_t* src = s0 ? a.in0 : a.in1;
         const int cs = s0 ? a.in0_cs : a.in1_cs;
-        const int cb = (s0 ? c : c - a.C0) + wave * 8;
-        const uint16_t* gp = sp >= 0 ? src + (size_t)sp * cs + cb : (const uint16_t*)a.zero;
-        if ((pb + 1) * 64 <= NPS || pb * 64 + lane < NPS)     // (still one vmcnt event per wave: every wave has lanes below NPS)
-            lds_dma16(gp, pbuf + par * patch_bytes + (wave * NP + pb * 64) * 16);
+        const int cb = (s0 ? c : c - a.C0) + (wave >> 1) * 16;               // wave-uniform; the lane's own 8 channels ride in lane_c8
+        const uint16_t* gp = sp >= 0 ? (src + cb) + ((size_t)sp * cs + lane_c8) : (const uint16_t*)a.zero;
+        const int blk = blk_of(pb);
+        if (NPS % 32 == 0 || blk * 32 + (lane >> 1) < NPS)    // (still one vmcnt event per wave: every block has pixels below NPS)
+            lds_dma16(gp, pbuf + par * patch_bytes + (wave >> 1) * (NP * 32) + blk * 1024);
     };
     auto issue_w = [&](const unsigned char* slice, int slot) {
 #pragma unroll
@@ -788,9 +806,9 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
     for (int f = 0; f < MF; ++f) {
         const int F = wm * MF + f;
         const int fr = F / fpr, fc = F - fr * fpr;
-        frag_off[f] = (fr * PW + fc * 16) * 16;
+        frag_off[f] = (fr * PW + fc * 16) * 32;
     }
-    const int lane_patch_off = ((lane >> 4) * NP + (lane & 15)) * 16;
+    const int lane_patch_off = (lane >> 5) * (NP * 32) + (lane & 15) * 32 + ((lane >> 4) & 1) * 16;
     const int lane_w_off = wn * 4 * 1024 + lane * 16;
 
     // patch DMA schedule inside a chunk: PCNT(tap) blocks at tap (first taps take two while NPB > PSLOTS)
@@ -926,7 +944,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
                             const float x0 = __builtin_amdgcn_fmed3f(d[q][k >> 2][k & 3], 0.f, cap), x1 = __builtin_amdgcn_fmed3f(d[q][(k + 1) >> 2][(k + 1) & 3], 0.f, cap);
                             o[i] = El<EL>::pack2(x0, x1);
                         }
-                        *(u32x4*)(pbuf + h * patch_bytes + (g * NP + pp) * 16) = o;
+                        *(u32x4*)(pbuf + h * patch_bytes + (g >> 1) * (NP * 32) + pp * 32 + (g & 1) * 16) = o;
                     }
                 }
             }
@@ -955,7 +973,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
         constexpr bool MORE = decltype(more_c)::value;
         constexpr int ky = tap / KS, kx = tap % KS;
         const unsigned char* wb = wbuf + wslot * WBUF + lane_w_off;
-        const unsigned char* pb = pbuf + par * patch_bytes + lane_patch_off + (ky * PW + kx) * 16;
+        const unsigned char* pb = pbuf + par * patch_bytes + lane_patch_off + (ky * PW + kx) * 32;
         typename El<EL>::v8 af[NF], bq[MF];
 #pragma unroll
         for (int j = 0; j < NF; ++j) af[j] = *(const typename El<EL>::v8*)(wb + j * 1024);
@@ -980,7 +998,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 2) conv3x3_dma_kernel(const Conv
         }
         __builtin_amdgcn_sched_barrier(0);
         constexpr int kyn = (tap + 1) / KS, kxn = (tap + 1) % KS;
-        const unsigned char* pbn = pbuf + par * patch_bytes + lane_patch_off + (kyn * PW + kxn) * 16;
+        const unsigned char* pbn = pbuf + par * patch_bytes + lane_patch_off + (kyn * PW + kxn) * 32;
 #pragma unroll
         for (int g = 0; g < MF / 2; ++g) {
 #pragma unroll
@@ -1398,23 +1416,32 @@ hipError_t launch_up4_fused(const ConvPlan& p1, const ConvPlan& p3, ConvArgs a, 
 // ================================================================================================ 1x1, LDS-DMA staged
 // 1x1 convolutions (fc7, the U-net "concat + 1x1" layers, the LSTM input projections, the linear layers, the class
 // projection) are plain GEMMs over the flattened pixel axis: [pixels, Cin] x [Cin, Cout].  One k-step per 32-channel chunk;
-// BOTH operand tiles of k-step ks+RING-1 are issued by LDS-DMA at k-step ks (weights: lane-linear slice; activations: wave w
-// gathers channel group w of 256 consecutive pixels, 16 B per lane), and the barrier waits with the constant counted
-// vmcnt((RING-2) * DMAs-per-k-step).  No halo, so the tile is simply 256 consecutive pixels of N*H*W.
+// BOTH operand tiles of k-step ks+RING-1 are issued by LDS-DMA at k-step ks, and the barrier waits with the constant counted
+// vmcnt((RING-2) * DMAs-per-k-step).  No halo, so the tile is simply 256 consecutive pixels of N*H*W.  Weights: lane-linear slice.
+// Activations: pixel-major tile [256 pixels][4 slots] x 16 B, slot j of pixel p holding channel group j ^ (2 * ((p >> 2) & 1)).  One DMA
+// covers 16 pixels x 64 B -- lane L fetches group (L & 3) ^ swz of pixel (L >> 2): whole 64-byte runs, a quarter of the lines per
+// instruction of the old 64-pixel x 16-byte gather (tools/micro/gather_shapes.hip: 2.2 x its landing rate beside MFMAs) -- and lands
+// linearly (destination linear, source permuted, read swizzled with the same involution).  Each wave issues 16 / NW of the tile's 16
+// blocks per k-step, as many DMAs as before.  Bank conflicts of the fragment reads: lane (pl = l & 15, g = l >> 4) reads the 16-byte
+// slot 4 pl + (g ^ 2 ((pl >> 2) & 1)) of its fragment, bank group (4 (pl & 3) + (g ^ 2 ((pl >> 2) & 1))) mod 16.  A ds_read_b128 lane group
+// holds, of a pair g, g ^ 1, the quad-rows pl >> 2 = 0 and 3 of one group and 1 and 2 of its twin: their slots g, g ^ 2, g ^ 3, g ^ 1 are
+// the four different ones, and inside a quad-row pl & 3 takes its four values -- 16 lanes, 16 bank groups.  Tiles start on multiples of 256 pixels
+// and fragments on multiples of 16, so the XOR is a per-lane constant and fragment f is base + f * 1024.
 template <int EL, int WM, int WN, int MF, int RING, bool ADDUP>
 __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_dma_kernel(const ConvArgs a) {
     constexpr int NW = WM * WN, NT = NW * 64, BN = WN * 64;
-    static_assert(NW == 4 || NW == 8, "wave w gathers channel group w & 3 of the activation tile (8 waves: half of the pixel blocks each)");
+    static_assert(NW == 4 || NW == 8, "wave w gathers 16 / NW of the 16-pixel blocks of the activation tile");
     constexpr int WBUF = BN * 64, WPIECES = WBUF / 16, WPT = WPIECES / NT;
     constexpr int NPX = WM * MF * 16, NPB = NPX / 64, PBUF = NPX * 64, SLOT = WBUF + PBUF;
-    constexpr int PBW = NPB / (NW / 4);            // activation blocks (64 pixels x 8 channels) a wave gathers per k-step
-    static_assert(WPIECES % NT == 0 && NPX % 64 == 0 && NPB % (NW / 4) == 0 && RING >= 3, "uniform DMA issue");
+    constexpr int PBW = NPB / (NW / 4);            // activation blocks (16 pixels x 32 channels) a wave gathers per k-step
+    static_assert(WPIECES % NT == 0 && NPX == 256 && NPB % (NW / 4) == 0 && RING >= 3, "uniform DMA issue");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [RING][weights WBUF | activations PBUF]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int kg = wave & 3, pb0 = (wave >> 2) * PBW;
+    const size_t kg8 = ((lane & 3) ^ (((lane >> 4) & 1) * 2)) * 8;   // first channel of the lane's source group (the addend of the address multiply-add)
+    const int pb0 = wave * PBW;                                      // the wave's first block
     int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int nt = bid % a.ntiles_n;
     const int tile = bid / a.ntiles_n;
@@ -1423,7 +1450,7 @@ __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_
     int pix[PBW];
 #pragma unroll
     for (int i = 0; i < PBW; ++i) {
-        const int p = px0 + (pb0 + i) * 64 + lane;
+        const int p = px0 + (pb0 + i) * 16 + (lane >> 2);
         pix[i] = p < a.OW ? p : -1;
     }
     const unsigned char* wsrc = (const unsigned char*)a.wpk + (size_t)nt * nk * WBUF;
@@ -1435,14 +1462,14 @@ __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_
         const bool s0 = c < a.C0;
         const uint16_t* src = s0 ? a.in0 : a.in1;
         const int cs = s0 ? a.in0_cs : a.in1_cs;
-        const int cb = (s0 ? c : c - a.C0) + kg * 8;
+        const int cb = s0 ? c : c - a.C0;
 #pragma unroll
         for (int i = 0; i < PBW; ++i) {
-            const uint16_t* g = pix[i] >= 0 ? src + (size_t)pix[i] * cs + cb : (const uint16_t*)a.zero;
-            lds_dma16(g, sb + WBUF + (kg * NPX + (pb0 + i) * 64) * 16);
+            const uint16_t* g = pix[i] >= 0 ? (src + cb) + ((size_t)(unsigned)pix[i] * (unsigned)cs + kg8) : (const uint16_t*)a.zero;
+            lds_dma16(g, sb + WBUF + (pb0 + i) * 1024);
         }
     };
-    const int lane_p_off = WBUF + ((lane >> 4) * NPX + (lane & 15)) * 16 + wm * MF * 256;
+    const int lane_p_off = WBUF + (lane & 15) * 64 + ((lane >> 4) ^ (((lane >> 2) & 1) * 2)) * 16 + wm * MF * 1024;
     const int lane_w_off = wn * 4 * 1024 + lane * 16;
     f32x4 acc[MF][4];
 #pragma unroll
@@ -1468,7 +1495,7 @@ __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_
 #pragma unroll
         for (int j = 0; j < 4; ++j) af[j] = *(const typename El<EL>::v8*)(sb + lane_w_off + j * 1024);
 #pragma unroll
-        for (int f = 0; f < MF; ++f) bq[f] = *(const typename El<EL>::v8*)(sb + lane_p_off + f * 256);
+        for (int f = 0; f < MF; ++f) bq[f] = *(const typename El<EL>::v8*)(sb + lane_p_off + f * 1024);
         if ((ks * 32 < a.C0) ? a.relu_in0 : a.relu_in1) {
             const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
