@@ -45,7 +45,8 @@ class bbocr_preproc_params(C.Structure):
 class bbocr_jpeg_plan(C.Structure):
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("sampling", (C.c_int * 2) * 3), ("restart_interval", C.c_int),
                 ("mcu_cols", C.c_int), ("mcu_rows", C.c_int), ("segments", C.c_int), ("scan_offset", C.c_longlong), ("scan_bytes", C.c_longlong),
-                ("supported", C.c_int), ("reason", C.c_int), ("orientation", C.c_int), ("reserved", C.c_int * 3)]
+                ("supported", C.c_int), ("reason", C.c_int), ("orientation", C.c_int), ("reserved", C.c_int * 2),
+                ("chroma", C.c_int)]                             # 1 = 4:4:4, 2 = 4:2:2, 3 = 4:4:0: decodable although `supported` is 0
 
 
 class bbocr_page(C.Structure):

@@ -86,6 +86,24 @@ __device__ __forceinline__ int th_fancy(const uint8_t* __restrict__ c, int cpitc
     return (3 * s + sn + ((x & 1) ? 7 : 8)) >> 4;
 }
 
+// one chroma sample of h2v1_fancy_upsample (4:2:2) at output (y, x): the row has cw valid samples; h2v1_upsample when cw <= 2.  The end
+// samples come out copied: their neighbour is clamped to themselves.
+__device__ __forceinline__ int th_fancy_h2v1(const uint8_t* __restrict__ c, int cpitch, int cw, int y, int x) {
+    const uint8_t* r = c + (size_t)y * cpitch;
+    const int cx = x >> 1;
+    if (cw <= 2) return r[cx];
+    const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0);
+    return (3 * r[cx] + r[nx] + ((x & 1) ? 2 : 1)) >> 2;
+}
+
+// one chroma sample of h1v2_fancy_upsample (4:4:0) at output (y, x): the plane has ch valid rows; the rows above the first and below the
+// last are those rows again
+__device__ __forceinline__ int th_fancy_h1v2(const uint8_t* __restrict__ c, int cpitch, int ch, int y, int x) {
+    const int cy = y >> 1;
+    const int ny = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
+    return (3 * c[(size_t)cy * cpitch + x] + c[(size_t)ny * cpitch + x] + ((y & 1) ? 2 : 1)) >> 2;
+}
+
 // ---- jchuff.c::encode_one_block of one block of quantised coefficients in zig-zag order, as a bit count and as bits.  JeHuff (kernels.h)
 // holds (code << 5) | length per symbol.  Also compiled for the host, where a stand-alone program runs both against Pillow's scan.
 #ifdef __HIP_DEVICE_COMPILE__

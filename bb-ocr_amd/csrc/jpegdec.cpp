@@ -59,8 +59,17 @@ int exif_orientation(const uint8_t* f, size_t n) {
     return 1;
 }
 
-// jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.  Returns the reason.
-int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
+// The chroma layouts outside `supported` that the decoder takes all the same (bbocr_jpeg_plan::chroma): luma (1,1), (2,1) or (1,2) over
+// chroma (1,1), (1,1).  0: any other sampling.
+int chroma_class(const bbocr_jpeg_plan& pl) {
+    if (pl.sampling[1][0] != 1 || pl.sampling[1][1] != 1 || pl.sampling[2][0] != 1 || pl.sampling[2][1] != 1) return 0;
+    const int h = pl.sampling[0][0], v = pl.sampling[0][1];
+    return h == 1 && v == 1 ? BBOCR_JPEG_CHROMA_444 : (h == 2 && v == 1 ? BBOCR_JPEG_CHROMA_422 : (h == 1 && v == 2 ? BBOCR_JPEG_CHROMA_440 : 0));
+}
+
+// jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.  Returns the reason;
+// `cls` receives the chroma class of a file whose sampling alone is outside today's scope, and the walk goes on as for a supported file.
+int jpeg_walk(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs, int& cls) {
     bbocr_jpeg_plan& pl = out.plan;
     pl = bbocr_jpeg_plan{};
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
@@ -141,8 +150,10 @@ int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
             if (nc == 3) {
                 if (!jfif && adobe != 1) return BBOCR_JPEG_COLORSPACE;
                 if (pl.sampling[0][0] != 2 || pl.sampling[0][1] != 2 || pl.sampling[1][0] != 1 || pl.sampling[1][1] != 1 || pl.sampling[2][0] != 1 ||
-                    pl.sampling[2][1] != 1)
-                    return BBOCR_JPEG_SAMPLING;
+                    pl.sampling[2][1] != 1) {
+                    cls = chroma_class(pl);
+                    if (!cls) return BBOCR_JPEG_SAMPLING;
+                }
             }
             if (sl < 1 || s[0] != nc || sl < 1 + 2 * (size_t)nc + 3) return BBOCR_JPEG_MULTISCAN;
             for (int i = 0; i < nc; ++i) {
@@ -158,9 +169,9 @@ int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
         }
         p += L;
     }
-    const int mcu = pl.components == 3 ? 16 : 8;
-    pl.mcu_cols = (pl.width + mcu - 1) / mcu;
-    pl.mcu_rows = (pl.height + mcu - 1) / mcu;
+    const int mcu_w = pl.components == 3 ? 8 * pl.sampling[0][0] : 8, mcu_h = pl.components == 3 ? 8 * pl.sampling[0][1] : 8;
+    pl.mcu_cols = (pl.width + mcu_w - 1) / mcu_w;
+    pl.mcu_rows = (pl.height + mcu_h - 1) / mcu_h;
     pl.restart_interval = dri;
     pl.scan_offset = (long long)scan_off;
     const long long nmcu = (long long)pl.mcu_cols * pl.mcu_rows;
@@ -197,9 +208,36 @@ int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
     if ((long long)nseg != (nmcu + ri - 1) / ri) return BBOCR_JPEG_RESTART;
     pl.segments = nseg;
     pl.scan_bytes = (long long)(end - scan_off);
-    pl.supported = 1;
     return BBOCR_JPEG_OK;
 }
+
+// The plan of a file and its reason.  A file of a chroma class that passed every later check keeps reason BBOCR_JPEG_SAMPLING and
+// supported 0, with `chroma` set and the whole plan filled; one that failed a later check is refused as before, nothing behind the
+// sampling test filled.
+int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
+    int cls = 0;
+    const int reason = jpeg_walk(f, n, out, want_segs, cls);
+    bbocr_jpeg_plan& pl = out.plan;
+    pl.supported = reason == BBOCR_JPEG_OK && !cls;
+    if (!cls) return reason;
+    if (reason == BBOCR_JPEG_OK) {
+        pl.chroma = cls;
+    } else {
+        pl.restart_interval = pl.mcu_cols = pl.mcu_rows = pl.segments = 0;
+        pl.scan_offset = pl.scan_bytes = 0;
+    }
+    return BBOCR_JPEG_SAMPLING;
+}
+
+// the decoder takes the file: inside today's scope, or of a chroma class
+bool jpeg_taken(const bbocr_jpeg_plan& pl) { return pl.supported || pl.chroma; }
+
+// luma blocks of an MCU across and down (1 x 1 for a one-component file)
+int luma_h(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? pl.sampling[0][0] : 1; }
+int luma_v(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? pl.sampling[0][1] : 1; }
+// bytes of the Y plane and of one chroma plane before upsampling (whole MCUs)
+size_t luma_plane_bytes(const bbocr_jpeg_plan& pl) { return (size_t)pl.mcu_cols * 8 * luma_h(pl) * (size_t)pl.mcu_rows * 8 * luma_v(pl); }
+size_t chroma_plane_bytes(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? (size_t)pl.mcu_cols * 8 * (size_t)pl.mcu_rows * 8 : 0; }
 
 // jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
 bool derive_table(const HuffSpec& h, JpegHuff& t) {
@@ -236,8 +274,8 @@ struct FileJob {                              // one admitted file of a batch
     size_t o_page = 0;                        // bbocr_jpeg_imread: offset of the un-oriented decode in jd_page
 };
 
-// Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan refuses (the caller plans first: a
-// refused file is its error); every other file becomes a job once dest(job) -- the entry point's own rule -- has checked the caller's
+// Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan neither supports nor gives a chroma
+// class (the caller plans first: a refused file is its error); every other file becomes a job once dest(job) -- the entry point's own rule -- has checked the caller's
 // destination and set the job's `out` and `pitch` (false: refused like the others).
 template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* files, const size_t* bytes, int n, int* status, D&& dest) {
     std::vector<FileJob> jobs;
@@ -246,7 +284,8 @@ template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* file
         status[k] = BBOCR_ERR_ARG;
         if (!files[k] || bytes[k] >= ((size_t)1 << 28)) continue;
         FileJob j;
-        if (jpeg_parse(files[k], bytes[k], j.ps, true) != BBOCR_JPEG_OK) continue;
+        jpeg_parse(files[k], bytes[k], j.ps, true);
+        if (!jpeg_taken(j.ps.plan)) continue;
         j.file = files[k];
         j.k = k;
         if (dest(j)) jobs.push_back(std::move(j));
@@ -275,7 +314,7 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.o_data = in.add((size_t)pl.scan_bytes + 8);
         // subsequences: every segment is cut on its own, so at most one per segment more than scan bits / S
         j.o_subseg = in.add(4 * ((size_t)pl.segments + (size_t)pl.scan_bytes * 8 / S + 1));
-        j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? 6 : 1);
+        j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? luma_h(pl) * luma_v(pl) + 2 : 1);
         max_seg = std::max(max_seg, pl.segments);
         max_blocks = std::max(max_blocks, j.nblocks);
         max_h = std::max(max_h, pl.height);
@@ -327,10 +366,9 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.w_count = work.add(4 * (size_t)nsub);
         j.w_scan = work.add(4 * (size_t)nsub);
         j.w_first = work.add(4 * (size_t)nsub);
-        const size_t mcu = pl.components == 3 ? 16 : 8, ysz = (size_t)pl.mcu_cols * mcu * pl.mcu_rows * mcu;
-        j.w_plane[0] = work.add(ysz);
-        j.w_plane[1] = work.add(pl.components == 3 ? ysz / 4 : 0);
-        j.w_plane[2] = work.add(pl.components == 3 ? ysz / 4 : 0);
+        j.w_plane[0] = work.add(luma_plane_bytes(pl));
+        j.w_plane[1] = work.add(chroma_plane_bytes(pl));
+        j.w_plane[2] = work.add(chroma_plane_bytes(pl));
         j.o_coef = coef.add((size_t)j.nblocks * 128);
     }
     const int passes = max_groups + 1;
@@ -364,7 +402,9 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         d.W = pl.width;
         d.H = pl.height;
         d.ncomp = pl.components;
-        d.bpm = pl.components == 3 ? 6 : 1;
+        d.hs = luma_h(pl);
+        d.vs = luma_v(pl);
+        d.bpm = pl.components == 3 ? d.hs * d.vs + 2 : 1;
         d.mcux = pl.mcu_cols;
         d.mcuy = pl.mcu_rows;
         d.nmcu = pl.mcu_cols * pl.mcu_rows;
@@ -404,7 +444,6 @@ int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* pla
     JpegParsed ps;
     const int reason = jpeg_parse(file, bytes, ps, false);
     *plan = ps.plan;
-    plan->supported = reason == BBOCR_JPEG_OK;
     plan->reason = reason;
     return BBOCR_OK;
 }
@@ -476,8 +515,7 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
         });
         if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file");
         const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
-        const int C = pl.components;
-        const size_t mcu = C == 3 ? 16 : 8, ysz = (size_t)pl.mcu_cols * mcu * pl.mcu_rows * mcu;
+        const size_t ysz = luma_plane_bytes(pl), csz = chroma_plane_bytes(pl);
         std::vector<int> ds;
         std::vector<JpegDesc> descs;
         jpeg_run(ctx, s, jobs, S, 3, ds, &descs);
@@ -503,7 +541,6 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
             if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
             HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
         } else if (stage == 2) {
-            const size_t csz = C == 3 ? ysz / 4 : 0;
             if (dst_bytes < ysz + 2 * csz) fail(BBOCR_ERR_ARG, "destination too small");
             HIPCHK(hipMemcpyAsync(dev_dst, d.plane[0], ysz, hipMemcpyDeviceToDevice, s));
             if (csz) {

@@ -1,5 +1,6 @@
-// Baseline JPEG decoding on the device (SOF0, Huffman, one interleaved scan, YCbCr 4:2:0 or grey), to the bit of libjpeg-turbo: the
-// entropy stage by speculative decoding with self-synchronisation (Weissenberger & Schmidt), then thumb.hip's decoder half (jpeg_dev.h).
+// Baseline JPEG decoding on the device (SOF0, Huffman, one interleaved scan, YCbCr 4:2:0, 4:4:4, 4:2:2, 4:4:0 or grey), to the bit of
+// libjpeg-turbo: the entropy stage by speculative decoding with self-synchronisation (Weissenberger & Schmidt), then thumb.hip's decoder
+// half (jpeg_dev.h).
 //   jd_sync     one lane per S-bit subsequence: decode from the assumed state (block 0 of the MCU, coefficient 0), then take the left
 //               neighbour's exit state and decode again until no state of the workgroup changes; launched once more per workgroup
 //               a segment spans, a launch returning at once when the launch before it changed nothing
@@ -7,7 +8,9 @@
 //   jd_write    decode from the exact entry states into the zeroed coefficient buffer (natural order); checks what the file promised
 //   jd_dc       per component and restart segment: running sum of the DC differences
 //   jd_idct     dequantise + jidctint.c per block into the component planes
-//   jd_output   h2v2 fancy upsampling -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane, into the caller's tensor
+//   jd_output   fancy upsampling by sampling class (h2v2, h2v1, h1v2, none) -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane,
+//               into the caller's tensor
+// An MCU holds hs x vs luma blocks (row after row), then one Cb and one Cr block: 2 x 2 for 4:2:0, 1 x 1 / 2 x 1 / 1 x 2 for the others.
 // The bytes are untrusted: every stream read is clamped to its segment (past the end: 1-bits), every store is index-checked, every loop
 // has a trip count fixed by the host's plan (S, lanes per workgroup, items per segment).
 #include "common.h"
@@ -39,6 +42,12 @@ __device__ __forceinline__ unsigned jd_peek16(const uint8_t* __restrict__ data, 
     return (w >> (8 - (p & 7))) & 0xFFFFu;
 }
 
+// component of block b of an MCU
+__device__ __forceinline__ int jd_comp(const JpegDesc& d, int b) {
+    const int nl = d.hs * d.vs;
+    return d.bpm == 1 ? 0 : (b < nl ? 0 : b - nl + 1);
+}
+
 __device__ __forceinline__ void jd_load_tables(const JpegHuff* __restrict__ g, JpegHuff* lds, int t, int nt) {
     const int* src = (const int*)g;
     int* dst = (int*)lds;
@@ -56,7 +65,7 @@ __device__ int jd_run(const JpegDesc& d, const JpegHuff* T, unsigned b0, unsigne
     *invalid = false;
     const uint8_t* __restrict__ data = d.data;
     for (int it = 0; it < d.S + 32 && p < end && n < max_blocks; ++it) {
-        const int c = d.bpm == 1 ? 0 : (b < 4 ? 0 : b - 3);
+        const int c = jd_comp(d, b);
         const int ti = z == 0 ? (c == 0 ? d.tab_dc[0] : (c == 1 ? d.tab_dc[1] : d.tab_dc[2])) : (c == 0 ? d.tab_ac[0] : (c == 1 ? d.tab_ac[1] : d.tab_ac[2]));
         const JpegHuff& H = T[ti & 3];
         const unsigned v = jd_peek16(data, b0, b1, p);
@@ -236,7 +245,7 @@ __global__ void __launch_bounds__(256) jd_dc_kernel(const JpegDesc* __restrict__
     const int seg = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
     if (seg >= d.nseg || c >= d.ncomp) return;
     const int m0 = seg * d.ri, nm = min(d.ri, d.nmcu - m0);
-    const int per = (d.ncomp == 3 && c == 0) ? 4 : 1;
+    const int nl = d.hs * d.vs, per = (d.ncomp == 3 && c == 0) ? nl : 1;
     const int items = nm * per;
     int carry = 0;
     for (int base = 0; base < items; base += 256 * 8) {
@@ -245,7 +254,7 @@ __global__ void __launch_bounds__(256) jd_dc_kernel(const JpegDesc* __restrict__
             const int k = base + t * 8 + e;
             int x = 0;
             if (k < items) {
-                const int blk = (m0 + k / per) * d.bpm + (d.ncomp == 3 ? (c == 0 ? k % per : 3 + c) : 0);
+                const int blk = (m0 + k / per) * d.bpm + (d.ncomp == 3 ? (c == 0 ? k % per : nl - 1 + c) : 0);
                 if ((unsigned)blk < (unsigned)d.nblocks) x = d.coef[(size_t)blk * 64];
             }
             sum += x;
@@ -263,7 +272,7 @@ __global__ void __launch_bounds__(256) jd_dc_kernel(const JpegDesc* __restrict__
         for (int e = 0; e < 8; ++e) {
             const int k = base + t * 8 + e;
             if (k < items) {
-                const int blk = (m0 + k / per) * d.bpm + (d.ncomp == 3 ? (c == 0 ? k % per : 3 + c) : 0);
+                const int blk = (m0 + k / per) * d.bpm + (d.ncomp == 3 ? (c == 0 ? k % per : nl - 1 + c) : 0);
                 if ((unsigned)blk < (unsigned)d.nblocks) d.coef[(size_t)blk * 64] = (short)(excl + v[e]);
             }
         }
@@ -281,7 +290,7 @@ __global__ void __launch_bounds__(64) jd_idct_kernel(const JpegDesc* __restrict_
     if ((int)blockIdx.x * 8 >= d.nblocks) return;
     const bool valid = id < d.nblocks;
     const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
-    const int c = d.bpm == 1 ? 0 : (j < 4 ? 0 : j - 3);
+    const int c = jd_comp(d, j);
     if (valid) {
         const short* co = d.coef + (size_t)id * 64 + l * 8;
         const unsigned short* q = d.quant + c * 64 + l * 8;
@@ -296,7 +305,7 @@ __global__ void __launch_bounds__(64) jd_idct_kernel(const JpegDesc* __restrict_
         const int mx = mcu % d.mcux, my = mcu / d.mcux;
         uint8_t* o;
         if (d.bpm == 1) o = d.plane[0] + (size_t)(my * 8 + l) * (d.mcux * 8) + mx * 8;
-        else if (c == 0) o = d.plane[0] + (size_t)(my * 16 + (j >> 1) * 8 + l) * (d.mcux * 16) + mx * 16 + (j & 1) * 8;
+        else if (c == 0) o = d.plane[0] + (size_t)(my * 8 * d.vs + (j / d.hs) * 8 + l) * (d.mcux * 8 * d.hs) + mx * 8 * d.hs + (j % d.hs) * 8;
         else o = (c == 1 ? d.plane[1] : d.plane[2]) + (size_t)(my * 8 + l) * (d.mcux * 8) + mx * 8;
         for (int i = 0; i < 8; ++i) o[i] = (uint8_t)row[i];
     }
@@ -310,11 +319,16 @@ __global__ void __launch_bounds__(256) jd_output_kernel(const JpegDesc* __restri
         d.out[(size_t)y * d.pitch + x] = d.plane[0][(size_t)y * (d.mcux * 8) + x];
         return;
     }
-    const int wp = d.mcux * 16, ch = (d.H + 1) / 2, cw = (d.W + 1) / 2;
+    const int wp = d.mcux * 8 * d.hs, cp = d.mcux * 8, ch = (d.H + 1) / 2, cw = (d.W + 1) / 2;
     uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
     o[0] = d.plane[0][(size_t)y * wp + x];
-    o[1] = (uint8_t)th_fancy(d.plane[1], wp / 2, ch, cw, y, x);
-    o[2] = (uint8_t)th_fancy(d.plane[2], wp / 2, ch, cw, y, x);
+    for (int c = 1; c < 3; ++c) {
+        const uint8_t* __restrict__ pl = d.plane[c];
+        int v;
+        if (d.hs == 2) v = d.vs == 2 ? th_fancy(pl, cp, ch, cw, y, x) : th_fancy_h2v1(pl, cp, cw, y, x);
+        else v = d.vs == 2 ? th_fancy_h1v2(pl, cp, ch, y, x) : pl[(size_t)y * cp + x];
+        o[c] = (uint8_t)v;
+    }
     if (d.px == 4) o[3] = 255;
 }
 

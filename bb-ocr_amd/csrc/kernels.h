@@ -340,12 +340,13 @@ struct JpegDesc {                                              // one file of a 
     int* flags;                                                // [passes + 1] flags[k] != 0: pass k changed a state
     int* status;                                               // JD_ERR_* bits
     short* coef;                                               // [nblocks][64] natural order, MCU block order
-    uint8_t* plane[3];                                         // Y [mcuy * 16 | 8][mcux * 16 | 8], Cb, Cr at half that
+    uint8_t* plane[3];                                         // Y [mcuy * 8 vs][mcux * 8 hs], then Cb, Cr [mcuy * 8][mcux * 8] each
     uint8_t* out;
     long long pitch;
     const JpegHuff* huff;                                      // [4]: DC 0, DC 1, AC 0, AC 1
     const unsigned short* quant;                               // [ncomp][64] natural order
     int W, H, ncomp, bpm, mcux, mcuy, nmcu, ri, nseg, nsub, S, nblocks, px, passes;
+    int hs, vs;                                                // luma blocks of an MCU across / down: bpm = hs * vs + 2 (1 component: 1, 1, bpm 1)
     int tab_dc[3], tab_ac[3];                                  // per component: index into huff
 };
 enum : int { JD_ERR_SYNC = 1, JD_ERR_CODE = 2, JD_ERR_COUNT = 4 };

@@ -24,11 +24,12 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 
-def _jpg_page(source):
-    """``("jpg", JpegPage, None)`` when the device decoder takes the file (a path or its bytes), else None"""
-    from .reader import jpeg_page
+def _jpg_page(source, device_decode=True):
+    """``("jpg", JpegPage, None)`` when the device decoder takes the file (a path or its bytes), else None.  ``device_decode``: the
+    caller's option; ``"chroma"`` adds 4:4:4, 4:2:2 and 4:4:0 files (``reader.jpeg_chroma``)."""
+    from .reader import jpeg_chroma, jpeg_page
 
-    page = jpeg_page(source)
+    page = jpeg_page(source, jpeg_chroma(device_decode))
     return None if page is None else ("jpg", page, None)
 
 
@@ -71,7 +72,7 @@ def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=Fal
         source = _thumbnail_jpeg(img.size, image_index, lambda: img.convert("RGB")) or image_path
     except Exception:
         pass                                                      # :511-514: any failure falls back to the original file
-    page = _jpg_page(source) if device_decode else None
+    page = _jpg_page(source, device_decode) if device_decode else None
     return page if page is not None else _host_page(source, decode_once)
 
 
@@ -102,7 +103,7 @@ def _ocr_input_device(reader, image_path, image_index=None, decode_once=True, de
     from .reader import decode_file_ycc
 
     m, _ = ocr_thumbnail_rule(image_index)
-    page = _jpg_page(image_path) if device_decode else None
+    page = _jpg_page(image_path, device_decode) if device_decode else None
     if page is not None and page[1].shape[2] == 3:
         if max(page[1].shape[:2]) <= m:
             return page
@@ -123,13 +124,13 @@ def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent
     (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
     final crop comes back.  A step that returns None in the reference leaves the page as it was.  ``on_device=True``: the crop stays on
     the card, as a (possibly strided) view of the device page.  ``device_decode=True``: the page is read by
-    ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels).
-    ``applied``: a list that receives the names of the steps that changed the page (where it stays empty the reference goes on with the
+    ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels);
+    ``device_decode="chroma"``: 4:4:4, 4:2:2 and 4:4:0 files as well.  ``applied``: a list that receives the names of the steps that changed the page (where it stays empty the reference goes on with the
     original file)."""
     from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, imread_bgr_device, preprocess_bgr_device
 
     applied = [] if applied is None else applied
-    page = imread_bgr_device(reader, image_path) if device_decode else reader._to_dev(_imread_bgr(image_path))
+    page = imread_bgr_device(reader, image_path, device_decode) if device_decode else reader._to_dev(_imread_bgr(image_path))
     if use_preprocessing:
         page = preprocess_bgr_device(reader, page)
         applied.append("preprocess")
@@ -181,6 +182,7 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     decoded there, a whole batch by one call (csrc/jpegdec.hip, identical pixels); every other file, and a file whose data turns out
     damaged, takes the host decode as before.  With the crop settings the page is read like ``cv2.imread``, EXIF orientation included, and
     ``device_decode=True`` does that on the card as well (``preprocess.imread_bgr_device``: csrc/jpegdec.hip + csrc/orient.hip).
+    ``device_decode="chroma"``: the same, and 4:4:4, 4:2:2 and 4:4:0 files -- which ``True`` leaves to the host -- are decoded there too.
     ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches."""
     from .preprocess import ocr_input_device
 
@@ -207,9 +209,9 @@ def _plain_input(path, i=None):
     return _host_page(path)
 
 
-def _plain_input_device(path, i=None):
+def _plain_input_device(path, i=None, device_decode=True):
     """``_plain_input`` with the device decoder: the file's bytes when it takes them"""
-    return _jpg_page(path) or _plain_input(path, i)
+    return _jpg_page(path, device_decode) or _plain_input(path, i)
 
 
 @dataclasses.dataclass
@@ -497,7 +499,7 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     ``decode(path, index)`` returns ``("ycc", triples, None)``, ``("rgb", rgb, gray)``, ``("dev", rgb_dev, gray_dev)`` or
     ``("jpg", JpegPage, None)``.  ``device_decode=True`` (or a ``decode`` that returns ``"jpg"`` pages): baseline JPEG files are only read
     and planned here and travel as their bytes, grouped by decoded shape; the upload stage decodes a group on the card with one call,
-    straight into the batch tensor.  Three overlapped stages: decode pool -> assembler thread (``_assemble``) -> this thread
+    straight into the batch tensor (``device_decode="chroma"``: 4:4:4, 4:2:2 and 4:4:0 files too).  Three overlapped stages: decode pool -> assembler thread (``_assemble``) -> this thread
     (``_device_stage``: upload, two device calls in flight, result strings); what they hand on is a ``Batch`` of one of the ``KINDS``.
     ``mixed`` (None: the environment variable ``BBOCR_MIXED_BATCH``, off unless ``1``): batches are closed by page count
     (``max_batch``, at most ``BBOCR_MAX_DEVICE_BATCH``) and a pixel budget instead of by shape, pages of all four kinds travel together, and each
@@ -508,7 +510,7 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     if mixed:
         max_batch = max(1, min(max_batch, int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))))
     if decode is None:
-        decode = _plain_input_device if device_decode else _plain_input
+        decode = (lambda path, i: _plain_input_device(path, i, device_decode)) if device_decode else _plain_input
     if indices is None:
         indices = range(len(image_paths))
     idxs = [i for i in indices if 0 <= i < len(image_paths)]
@@ -542,7 +544,7 @@ def _model_image_plain(reader, path, max_dim, quality, device_decode):
     from .preprocess import PAGE_GRAY, PAGE_RGB, PAGE_YCBCR4, model_image_device, model_image_host
 
     if device_decode:
-        page = _jpg_page(path)
+        page = _jpg_page(path, device_decode)
         if page is not None:
             comment = Image.open(path).info.get("comment")                # headers only
             dev, status = reader.decode_jpeg_batch([page[1]], padded=True)
@@ -563,7 +565,7 @@ def encode_images_for_model(reader, image_paths, use_preprocessing=False, edge_c
     csrc/thumb.hip + csrc/jpegenc.hip), so that only the file's bytes cross the link.  Where the chain changes the page the reference reads
     it through ``cv2.imread`` (EXIF orientation applied; the PNG it writes carries no comment); where no step applies it encodes the
     original file, which ``Image.open`` does not transpose and whose comment the saved JPEG keeps.  ``device_decode=True``: baseline JPEG
-    files are decoded on the card too.  A file Pillow cannot read maps to the base64 of its bytes, like :409-411."""
+    files are decoded on the card too (``"chroma"``: 4:4:4, 4:2:2 and 4:4:0 files among them).  A file Pillow cannot read maps to the base64 of its bytes, like :409-411."""
     import base64
 
     from .preprocess import PAGE_BGR, PAGE_GRAY, model_image_device, model_image_quality, model_image_rule

@@ -96,12 +96,13 @@ def orient_page_device(reader, page_dev, layout, orientation, dst_layout=None):
     return out
 
 
-def imread_bgr_device(reader, source):
+def imread_bgr_device(reader, source, device_decode=None):
     """``reader._to_dev(_imread_bgr(source))`` without the host's oriented page: ``cv2.imread``'s BGR page, uint8 ``[H',W',3]`` on the
     reader's device, bit for bit.  ``source``: a path or the file's bytes.  Three paths, tried in this order; the one taken is recorded
     as ``.imread_path`` of the returned tensor:
 
-    * ``IMREAD_JPEG`` -- the device decoder's plan takes the file: only its bytes cross the link (``bbocr_jpeg_imread``);
+    * ``IMREAD_JPEG`` -- the device decoder's plan takes the file: only its bytes cross the link (``bbocr_jpeg_imread``); with
+      ``device_decode="chroma"`` (None: the reader's ``jpeg_chroma``) that includes a 4:4:4, 4:2:2 or 4:4:0 file (``plan.chroma``);
     * ``IMREAD_YCC``  -- a YCbCr-coded JPEG the plan refuses (progressive, 4:4:4, ...) or whose entropy-coded data the device decoder
       reports damaged: ``decode_file_ycc`` on the host, the un-oriented triples uploaded, oriented and converted on the card;
     * ``IMREAD_RGB``  -- everything else: Pillow's un-oriented ``convert("RGB")``, uploaded, oriented and channel-swapped on the card.
@@ -111,12 +112,13 @@ def imread_bgr_device(reader, source):
     and this function do not."""
     from PIL import Image
 
-    from .reader import JpegPage, _file_bytes, decode_file_ycc, jpeg_plan
+    from .reader import JpegPage, _file_bytes, decode_file_ycc, jpeg_chroma, jpeg_plan
 
+    chroma = getattr(reader, "jpeg_chroma", False) if device_decode is None else jpeg_chroma(device_decode)
     data = _file_bytes(source)
     plan = jpeg_plan(data)
     out = path = None
-    if plan.supported:
+    if plan.supported or (chroma and plan.chroma):
         pages, status = reader.imread_jpeg_batch([JpegPage(data, plan)])
         if status[0] == 0:
             out, path = pages[0], IMREAD_JPEG
@@ -166,7 +168,8 @@ def preprocess_for_book_cover(image_path, output_path=None, reader=None, legacy=
     """Drop-in for the reference function: ``(gray uint8 array, output_path, steps_applied)``.  ``image_path`` may also be a
     decoded BGR array.  ``reader`` supplies the device context (any ``bb_ocr_amd.Reader``).  ``legacy=True`` runs the older
     ``preprocess_for_book_cover`` of pipeline_components/img_to_json/ocr_testing/preprocessing/image_preprocessor.py:221-252.
-    ``device_decode=True``: a path is read by ``imread_bgr_device`` (same pixels)."""
+    ``device_decode=True``: a path is read by ``imread_bgr_device`` (same pixels); ``"chroma"``: 4:4:4, 4:2:2 and 4:4:0 files are decoded
+    on the card as well."""
     if reader is None:
         raise ValueError("preprocess_for_book_cover needs a bb_ocr_amd.Reader (device context)")
     if isinstance(image_path, np.ndarray):
@@ -174,7 +177,7 @@ def preprocess_for_book_cover(image_path, output_path=None, reader=None, legacy=
     else:
         if not os.path.exists(image_path):
             raise ValueError(f"Could not load image from {image_path}")      # image_preprocessor.py:19-20
-        page = imread_bgr_device(reader, image_path) if device_decode else reader._to_dev(_imread_bgr(image_path))
+        page = imread_bgr_device(reader, image_path, device_decode) if device_decode else reader._to_dev(_imread_bgr(image_path))
     out = preprocess_bgr_device(reader, page, legacy=legacy).cpu().numpy()
     if output_path:
         from PIL import Image
@@ -273,13 +276,14 @@ def _read_page(image_path_or_array):
 def auto_crop_text_region(image_path_or_array, margin=128, reader=None, device_decode=False):
     """Drop-in for ``_auto_crop_text_region(image_path, margin)``: the cropped page (an array, where the reference writes it to a PNG
     and returns the path) or None.  A path is decoded like ``cv2.imread`` (BGR, EXIF-transposed); an array may be gray or BGR.
-    ``device_decode=True``: a path is read by ``imread_bgr_device``, and only the crop comes back from the card (same pixels)."""
+    ``device_decode=True``: a path is read by ``imread_bgr_device``, and only the crop comes back from the card (same pixels);
+    ``"chroma"``: 4:4:4, 4:2:2 and 4:4:0 files are decoded on the card as well."""
     if reader is None:
         raise ValueError("auto_crop_text_region needs a bb_ocr_amd.Reader (device context)")
     if device_decode and not isinstance(image_path_or_array, np.ndarray):
         if not os.path.exists(image_path_or_array):
             return None
-        page = imread_bgr_device(reader, image_path_or_array)
+        page = imread_bgr_device(reader, image_path_or_array, device_decode)
         b = auto_crop_box_device(reader, page, margin)
         return None if b is None else page[b[1]:b[3], b[0]:b[2]].contiguous().cpu().numpy()
     img = _read_page(image_path_or_array)

@@ -169,7 +169,8 @@ class JpegPage:
 
 def jpeg_plan(data):
     """``bbocr_host_jpeg_plan`` of a file's bytes (no GPU): geometry, sampling, restart interval, scan range, ``supported`` and the
-    ``BBOCR_JPEG_*`` reason a file outside the device decoder's scope is refused with."""
+    ``BBOCR_JPEG_*`` reason a file outside the device decoder's scope is refused with; ``chroma``: 1 / 2 / 3 for a 4:4:4 / 4:2:2 / 4:4:0
+    file that the decoder takes when asked to (``device_decode="chroma"``) although ``supported`` is 0."""
     plan = _lib.bbocr_jpeg_plan()
     rc = _lib.load().bbocr_host_jpeg_plan(data, len(data), C.byref(plan))
     if rc != 0:
@@ -177,12 +178,22 @@ def jpeg_plan(data):
     return plan
 
 
-def jpeg_page(source):
-    """``JpegPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)."""
+DECODE_CHROMA = "chroma"     # the value of ``device_decode`` / ``BBOCR_DEVICE_DECODE`` that adds 4:4:4, 4:2:2 and 4:4:0 files to the device decoder's
+
+
+def jpeg_chroma(device_decode):
+    """True for ``device_decode="chroma"``: device decode with the wider scope -- the files whose plan has ``chroma`` set although
+    ``supported`` is 0.  Every other value (``True``, ``"1"``, ``False``, ``None``) is today's scope."""
+    return isinstance(device_decode, str) and device_decode.strip().lower() == DECODE_CHROMA
+
+
+def jpeg_page(source, chroma=False):
+    """``JpegPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path).
+    ``chroma``: a 4:4:4, 4:2:2 or 4:4:0 file (``plan.chroma``) is taken as well."""
     try:
         data = _file_bytes(source)
         plan = jpeg_plan(data)
-        return JpegPage(data, plan) if plan.supported else None
+        return JpegPage(data, plan) if plan.supported or (chroma and plan.chroma) else None
     except Exception:
         return None
 
@@ -394,8 +405,10 @@ class Reader:
             host_threads = auto_host_threads()
         self.host_threads = int(host_threads)
         if device_decode is None:   # baseline JPEG files decoded on the card (csrc/jpegdec.hip) by readtext(path); off unless asked for
-            device_decode = os.environ.get("BBOCR_DEVICE_DECODE", "0").strip() == "1"
+            env = os.environ.get("BBOCR_DEVICE_DECODE", "0").strip().lower()
+            device_decode = DECODE_CHROMA if env == DECODE_CHROMA else env == "1"
         self.device_decode = bool(device_decode)
+        self.jpeg_chroma = jpeg_chroma(device_decode)     # "chroma": 4:4:4, 4:2:2 and 4:4:0 files are decoded on the card as well
         cfg = _lib.bbocr_config(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
                                 precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads)
         h = C.c_void_p()
@@ -750,11 +763,18 @@ class Reader:
                                                 C.c_void_p(out.ctypes.data), cap, C.byref(n)))
         return out[:n.value].tobytes()
 
-    def decode_jpeg_device(self, sources):
+    @property
+    def decode_option(self):
+        """This Reader's ``device_decode`` as the functions of ``extractor_batch`` and ``preprocess`` take it: ``"chroma"``, True or False"""
+        return DECODE_CHROMA if self.jpeg_chroma else self.device_decode
+
+    def decode_jpeg_device(self, sources, chroma=None):
         """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them (libjpeg's RGB and its Y
         plane; a grey file: the samples, replicated for RGB), decoded on the card, or ``None`` for a file the plan refuses or whose
-        entropy-coded data is damaged.  Files of one decoded shape share one decode call."""
-        pages = [jpeg_page(s) for s in sources]
+        entropy-coded data is damaged.  Files of one decoded shape share one decode call.  ``chroma`` (None: this Reader's
+        ``jpeg_chroma``): 4:4:4, 4:2:2 and 4:4:0 files are decoded as well."""
+        chroma = self.jpeg_chroma if chroma is None else bool(chroma)
+        pages = [jpeg_page(s, chroma) for s in sources]
         out = [None] * len(pages)
         groups = {}
         for i, p in enumerate(pages):
@@ -885,7 +905,7 @@ class Reader:
         from .extractor_batch import read_files
 
         paths = list(paths)
-        kw.setdefault("device_decode", self.device_decode)
+        kw.setdefault("device_decode", self.decode_option)
         res = read_files(self, paths, None, max_batch, decode_workers, **kw)
         return [res[i] for i in range(len(paths))]
 

@@ -394,6 +394,9 @@ int bbocr_host_jpeg_qtables(int quality, uint16_t* out);
 /* ---- baseline JPEG files decoded on the device (csrc/jpegdec.hip), to the bit of libjpeg-turbo / Pillow: only the file's bytes cross the
  * link.  Taken: SOF0, 8 bit, Huffman, ONE interleaved scan, 3 components YCbCr 4:2:0 (JFIF, or Adobe transform 1: decode_file_ycc's
  * rule) or 1 component, any DQT / DHT / DRI, any size.  Everything else is refused by the plan, and the caller keeps its host path.
+ * Opt-in beside that scope: 3 components sampled 4:4:4, 4:2:2 or 4:4:0 that are otherwise inside it.  The plan still reports them as
+ * refused (supported 0, reason BBOCR_JPEG_SAMPLING) and names their class in `chroma`; bbocr_jpeg_decode / bbocr_jpeg_imread take a file
+ * whose `chroma` is not 0, so a caller that asks for them hands such a file over and every other caller behaves as before.
  * bbocr_jpeg_decode ignores the EXIF orientation, as the host path of readtext ignores it; the plan reports it, and bbocr_jpeg_imread
  * applies it: cv2.imread's page, which the extractor's crop settings read. */
 enum {
@@ -404,12 +407,17 @@ enum {
     BBOCR_JPEG_SOF = 4,         /* extended, progressive, lossless or arithmetic-coded frame; no or a second frame header */
     BBOCR_JPEG_PRECISION = 5,   /* 12-bit samples, 16-bit quantisation table */
     BBOCR_JPEG_COMPONENTS = 6,  /* CMYK / YCCK / two components */
-    BBOCR_JPEG_SAMPLING = 7,    /* 4:4:4, 4:2:2, 4:4:0, ... */
+    BBOCR_JPEG_SAMPLING = 7,    /* any sampling but 4:2:0; 4:4:4, 4:2:2 and 4:4:0 files are decodable all the same when plan.chroma != 0 */
     BBOCR_JPEG_COLORSPACE = 8,  /* three components without JFIF or Adobe transform 1: may be RGB-coded */
     BBOCR_JPEG_MULTISCAN = 9,   /* a scan that does not hold every component, or more after the first */
     BBOCR_JPEG_TABLES = 10,     /* a table the scan names is missing or malformed */
     BBOCR_JPEG_RESTART = 11     /* restart markers out of sequence, or not one per interval */
 };
+enum { BBOCR_JPEG_CHROMA_444 = 1, BBOCR_JPEG_CHROMA_422 = 2, BBOCR_JPEG_CHROMA_440 = 3 };   /* bbocr_jpeg_plan::chroma */
+/* A file of a chroma class (chroma != 0) has supported == 0 and reason == BBOCR_JPEG_SAMPLING like every other file outside 4:2:0, and
+ * every other field filled exactly as for a supported file: mcu_cols / mcu_rows count MCUs of 8 h x 8 v pixels, (h, v) = sampling[0],
+ * and segments, scan_offset, scan_bytes describe its scan.  Such a file passed every check behind the sampling test (colour space, one
+ * interleaved scan, tables, restart sequence, EOI); one that fails any of them has chroma == 0 and those fields 0. */
 typedef struct bbocr_jpeg_plan {
     int width, height, components;
     int sampling[3][2];         /* (h, v) per component */
@@ -418,7 +426,7 @@ typedef struct bbocr_jpeg_plan {
     int segments;               /* restart segments = entry points known without decoding */
     long long scan_offset;      /* first entropy-coded byte */
     long long scan_bytes;       /* up to the marker that ends the scan (stuffing and restart markers included) */
-    int supported;              /* 1: bbocr_jpeg_decode takes the file */
+    int supported;              /* 1: bbocr_jpeg_decode takes the file (it also takes one whose `chroma` is not 0) */
     int reason;                 /* BBOCR_JPEG_* */
     int orientation;            /* EXIF orientation 1 .. 8 as cv2.imread applies it, 1 = none: the first APP1 "Exif\0\0" segment before SOS, TIFF header
                                  * of either byte order, IFD0 only, tag 0x0112 as ONE SHORT or LONG of value 1 .. 8.  Everything else is 1: no such
@@ -426,7 +434,9 @@ typedef struct bbocr_jpeg_plan {
                                  * leaves the segment.  Filled for every file that starts with SOI, refused ones included; malformed EXIF changes no
                                  * other field.  XMP's tiff:Orientation is not read (OpenCV does not read it; Pillow's exif_transpose does, when the
                                  * EXIF block has no tag: the one difference to preprocess._imread_bgr). */
-    int reserved[3];
+    int reserved[2];
+    int chroma;                 /* 0: inside today's scope, or refused for another reason; BBOCR_JPEG_CHROMA_444 (luma sampled 1x1), _422 (2x1) or
+                                 * _440 (1x2) over 1x1 chroma: bbocr_jpeg_decode / bbocr_jpeg_imread take the file although `supported` is 0 */
 } bbocr_jpeg_plan;
 /* host only, no GPU: one linear pass over the file (markers, then the scan's FF bytes); no entropy bit is decoded.  Fields a refused
  * file's headers did not reach stay 0. */
@@ -434,7 +444,7 @@ int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* pla
 /* n files (HOST bytes) -> pixels in DEVICE memory, one call per batch: dev_out[k] receives file k's libjpeg YCbCr triples (out_color_space
  * JCS_YCbCr, what decode_file_ycc holds), rows pitches[k] bytes apart, 3 (layout BBOCR_PAGE_YCBCR3) or 4 (BBOCR_PAGE_YCBCR4, fourth byte
  * 255) bytes per pixel -- bbocr_op_ycc_to_rgb's two inputs -- or, for a 1-component file, the samples themselves, one byte per pixel.
- * status[k]: 0, BBOCR_ERR_ARG (null pointer, pitch shorter than a row, a file the plan refuses) or BBOCR_ERR_DATA (the entropy-coded
+ * status[k]: 0, BBOCR_ERR_ARG (null pointer, pitch shorter than a row, a file the plan refuses and gives no chroma class) or BBOCR_ERR_DATA (the entropy-coded
  * data decodes to another block count than the headers promise, or holds a bit pattern without a code: dev_out[k] is then undefined);
  * the other files of the batch are decoded all the same and the context stays usable.  Runs on a stream of its own outside the call
  * slots, one batch at a time per context (bbocr_upload_pages' contract): a batch decodes while two pipeline calls are in flight.  Work
@@ -451,6 +461,7 @@ int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
  * 32 .. 65536): stage 0 = the exact entry state of every subsequence, int32 [subsequences][4] = (bit in the unstuffed scan, block in the
  * MCU, zig-zag position, first output block); 1 = quantised coefficients int16 [blocks][64] in natural order, blocks in MCU order, DC
  * terms summed; 2 = the component planes before upsampling, Y [mcu_rows * 16][mcu_cols * 16] then Cb, Cr at half that (1 component:
+ * [mcu_rows * 8][mcu_cols * 8]; a file of a chroma class: Y [mcu_rows * 8 v][mcu_cols * 8 h], then Cb and Cr, each
  * [mcu_rows * 8][mcu_cols * 8]); 3 = the pixels, tight.  *file_status as status[k] above. */
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status);

@@ -7,6 +7,9 @@ Prints JSON lines and appends them to --out:
   * decode64    one bbocr_jpeg_decode call for a 64-page batch of 1280x960 quality-90 synthetic pages, ms per page, against
                 decode_file_ycc of the same files on one core;
   * photo       one 5712x4284 photograph, the same two ways;
+  * decode64_444 / decode64_422 / decode64_440   the 64-page batch saved 4:4:4 and 4:2:2, and 64 copies of one page's lossless transposition
+                (4:4:0, built by tests/jpeg_chroma_ref.make_440: Pillow writes no such file) -- the files ``device_decode="chroma"`` adds --
+                one bbocr_jpeg_decode call against what they cost without it: decode_file_ycc on one core plus the upload of the triples;
   * extract     extract_texts over --extract pages (extractor_bench.py's page set) with device_decode off / on, alternating, each twice;
   * photos      extract_texts(device_thumbnail=True) over --photos 5712x4284 pages with device_decode off / on.
 --device-only: the decode64 and photo device legs alone (for a separate `rocprofv3 --kernel-trace --stats` run).
@@ -54,7 +57,7 @@ def main():
     photo = jpeg(Image.fromarray(synth.page(900, width=1280, height=960, lines=20)[0]).resize((5712, 4284), Image.BICUBIC), quality=92)
 
     def device_ms(datas):
-        batch = [jpeg_page(d) for d in datas]
+        batch = [jpeg_page(d, chroma=True) for d in datas]
         _, status = reader.decode_jpeg_batch(batch, padded=True)                 # warm-up: buffers grow here
         assert not any(status)
         torch.cuda.synchronize()
@@ -79,7 +82,26 @@ def main():
                 jpeg_plan(d)
             row["plan_ms_per_file"] = round((time.perf_counter() - t) * 1e3 / len(datas), 4)
         emit(**row)
+    def host_upload_ms(datas):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        reader._to_dev([decode_file_ycc(d, padded=True) for d in datas])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
     if not a.device_only:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from jpeg_chroma_ref import make_440
+
+        imgs = [Image.fromarray(synth.page(1234 + i)[0]) for i in range(64)]
+        classes = (("decode64_444", [jpeg(im, quality=90, subsampling=0) for im in imgs]),
+                   ("decode64_422", [jpeg(im, quality=90, subsampling=1) for im in imgs]),
+                   ("decode64_440", [make_440(jpeg(imgs[0].transpose(Image.TRANSPOSE), quality=90, subsampling=1))] * 64))
+        for name, datas in classes:
+            assert all(jpeg_plan(d).chroma and not jpeg_plan(d).supported for d in datas)
+            emit(leg=name, files=len(datas), kbytes_per_file=round(sum(map(len, datas)) / len(datas) / 1024, 1),
+                 device_ms_per_page=round(device_ms(datas) / len(datas), 3),
+                 host_decode_upload_ms_per_page=round(min(host_upload_ms(datas) for _ in range(3)) / len(datas), 3))
         with tempfile.TemporaryDirectory() as d:
             if a.extract > 0:
                 uniq = [Image.fromarray(synth.page(1234 + i)[0]) for i in range(8)]
