@@ -19,6 +19,7 @@ class bbocr_config(C.Structure):
 
 
 PRECISIONS = {"bf16": 0, "fp16": 1, "exact": 2, "mixed": 3, "exact_rec": 4}
+BEAM_DEVICE_MAX = 32                                                             # bbocr.h BBOCR_BEAM_DEVICE_MAX
 PAGE_GRAY, PAGE_BGR, PAGE_RGB, PAGE_YCBCR4, PAGE_YCBCR3 = 0, 1, 2, 3, 4          # bbocr.h BBOCR_PAGE_*: layouts of a device page
 PAGE_PX_BYTES = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}    # bytes per pixel (csrc/kernels.h page_px_bytes)
 
@@ -118,6 +119,9 @@ PROTOTYPES = {
     "bbocr_crnn_logits": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "bbocr_op_ctc": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                C.POINTER(C.c_uint), C.c_int]),
+    "bbocr_op_ctc_probs": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_uint), _vp]),
+    "bbocr_op_ctc_beam": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int)]),
     "bbocr_op_resize_u8": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int]),
     "bbocr_op_ycc_to_rgb": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "bbocr_upload_pages": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, C.c_size_t, _vp]),

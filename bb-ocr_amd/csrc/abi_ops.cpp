@@ -235,32 +235,89 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
                  const unsigned int* ignore_mask, int beam_width) {
     return guarded(ctx, [&](bbocr_ctx* ctx) {
         if (!dev_logits || !text_off || !text_idx || !conf || n <= 0 || T <= 0 || C <= 0 || C > cs) fail(BBOCR_ERR_ARG, "bad ctc arguments");
-        const bool beam = beam_width > 0;
         const size_t rows = (size_t)n * T;
-        ctc_size(ctx, rows, n, cs, beam);
         std::vector<int> seqs;
         for (int i = 0; i < n; ++i) { seqs.push_back(i * T); seqs.push_back(T); }
+        const int route = ctc_route(beam_width, C, seqs.data(), n);       // as rec_finish routes a recognition pass
+        ctc_size(ctx, rows, n, cs, route);
         ctx->seq_tables.ensure(seqs.size() * 4);
         HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, n, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
-                          (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask, beam ? (float*)ctx->ctc_probs.p : nullptr));
-        std::vector<int> oidx(rows);
+                          (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask,
+                          route != CTC_GREEDY ? (float*)ctx->ctc_probs.p : nullptr));
+        std::vector<int> oidx(rows), blen(route == CTC_BEAM_DEVICE ? n : 0);
         std::vector<CtcOut> oo(n);
-        std::vector<float> probs(beam ? rows * cs : 0);
+        std::vector<float> probs(route == CTC_BEAM_HOST ? rows * cs : 0);
         std::vector<std::vector<int>> beam_texts;
-        HIPCHK(hipMemcpyAsync(oidx.data(), ctx->ctc_out_idx.p, oidx.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(oo.data(), ctx->ctc_out.p, oo.size() * sizeof(CtcOut), hipMemcpyDeviceToHost, ctx->stream));
-        if (beam) HIPCHK(hipMemcpyAsync(probs.data(), ctx->ctc_probs.p, probs.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (route == CTC_BEAM_DEVICE) {            // the search's text takes the place of the greedy classes
+            HIPCHK(launch_ctc_beam((const float*)ctx->ctc_probs.p, rows, C, cs, (const int*)ctx->seq_tables.p, n, T, beam_width,
+                                   (int*)ctx->ctc_beam_idx.p, (int*)ctx->ctc_beam_len.p, ctx->stream));
+            HIPCHK(hipMemcpyAsync(oidx.data(), ctx->ctc_beam_idx.p, oidx.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(blen.data(), ctx->ctc_beam_len.p, blen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(oidx.data(), ctx->ctc_out_idx.p, oidx.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (route == CTC_BEAM_HOST)
+                HIPCHK(hipMemcpyAsync(probs.data(), ctx->ctc_probs.p, probs.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
         slot_sync(ctx, ctx->stream);
-        if (beam) ctc_beam_search_batch(probs.data(), seqs.data(), n, C, cs, beam_width, beam_texts, &host_pool(ctx));
+        if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), n, C, cs, beam_width, beam_texts, &host_pool(ctx));
         std::vector<int> text;
         int o = 0;
         for (int i = 0; i < n; ++i) {
             text_off[i] = o;
-            conf[i] = ctc_decode(oo[i], oidx.data() + (size_t)i * T, beam ? &beam_texts[i] : nullptr, text);
+            if (route == CTC_BEAM_HOST) conf[i] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), text);
+            else conf[i] = ctc_decode(oo[i], oidx.data() + (size_t)i * T, route == CTC_BEAM_DEVICE ? std::clamp(blen[i], 0, T) : oo[i].len, text);
             for (int v : text) text_idx[o++] = v;
         }
         text_off[n] = o;
+    });
+}
+
+int bbocr_op_ctc_probs(bbocr_ctx* ctx, const float* dev_logits, size_t rows, int C, int cs, const unsigned int* ignore_mask, float* dev_probs_out) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!dev_logits || !dev_probs_out || rows == 0 || rows > (size_t)INT32_MAX || C <= 0 || C > 128 || C > cs) fail(BBOCR_ERR_ARG, "bad ctc arguments");
+        // launch_ctc with one sequence over all rows: the rows kernel is per row, the collapse's output is not read
+        ctc_size(ctx, rows, 1, cs, CTC_GREEDY);
+        const int seq[2] = {0, (int)rows};
+        ctx->seq_tables.ensure(sizeof(seq));
+        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seq, sizeof(seq), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, 1, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
+                          (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask, dev_probs_out));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+int bbocr_op_ctc_beam(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width, int* text_off,
+                      int* text_idx) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!dev_probs || !seqs || !text_off || !text_idx || nseq <= 0 || rows > (size_t)INT32_MAX || C <= 0 || C > 128 || cs < C || beam_width < 1 ||
+            beam_width > BBOCR_BEAM_DEVICE_MAX)
+            fail(BBOCR_ERR_ARG, "bad beam-search arguments");
+        int max_T = 0;
+        for (int i = 0; i < nseq; ++i) {
+            const long long first = seqs[2 * i], T = seqs[2 * i + 1];
+            if (first < 0 || T < 0 || first + T > (long long)rows) fail(BBOCR_ERR_ARG, "a sequence lies outside the rows");
+            max_T = std::max(max_T, (int)T);
+        }
+        if (!ctc_beam_on_device(beam_width, C, max_T)) fail(BBOCR_ERR_ARG, "the longest sequence does not fit the device search at this width");
+        ctx->seq_tables.ensure((size_t)nseq * 8);
+        ctx->ctc_beam_idx.ensure(std::max<size_t>(rows, 1) * 4);
+        ctx->ctc_beam_len.ensure((size_t)nseq * 4);
+        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs, (size_t)nseq * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(launch_ctc_beam(dev_probs, rows, C, cs, (const int*)ctx->seq_tables.p, nseq, max_T, beam_width, (int*)ctx->ctc_beam_idx.p,
+                               (int*)ctx->ctc_beam_len.p, ctx->stream));
+        std::vector<int> bidx(rows), blen(nseq);
+        if (rows) HIPCHK(hipMemcpyAsync(bidx.data(), ctx->ctc_beam_idx.p, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(blen.data(), ctx->ctc_beam_len.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+        int o = 0;
+        for (int i = 0; i < nseq; ++i) {
+            text_off[i] = o;
+            const int n = std::clamp(blen[i], 0, seqs[2 * i + 1]);
+            for (int k = 0; k < n; ++k) text_idx[o++] = bidx[(size_t)seqs[2 * i] + k];
+        }
+        text_off[nseq] = o;
     });
 }
 

@@ -240,7 +240,7 @@ struct bbocr_ctx : WeightView {
     PinBuf pg_pin;                            // staging of the page tables' upload
     DevBuf ccl_label, ccl_stat, ccl_slot, ccl_comps, ccl_rowext, ccl_counters;
     DevBuf crop_desc, crop_scratch, crop_hscratch, crop_wscratch, crop_luts, crop_hist;
-    DevBuf ctc_idx, ctc_pmax, ctc_out_idx, ctc_out, ctc_probs, crop_desc2;
+    DevBuf ctc_idx, ctc_pmax, ctc_out_idx, ctc_out, ctc_probs, ctc_beam_idx, ctc_beam_len, crop_desc2;
     PinBuf desc_pin, desc_pin2;               // staging of crop_desc / crop_desc2 uploads
     PinBuf ctc_pin;                           // CTC results land here (pinned: the 1.7 MB D2H copy of a 64-page pass runs at link speed)
     DevBuf seq_v, seq_xp, seq_h, seq_lin, seq_logits, seq_tables;
@@ -404,8 +404,10 @@ uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part);
 void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide);
 void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
 void crnn_sequence(bbocr_ctx* c, size_t rows_pad, const int* tiles_dev, int ntiles, float* logits);
-void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, bool beam);
-double ctc_decode(const CtcOut& o, const int* idx, const std::vector<int>* beam_text, std::vector<int>& text);
+enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2 };   // where the text of a CTC pass comes from (ctc_route)
+int ctc_route(int beam_width, int C, const int* seqs, int nseq);   // seqs: {first row, T} per sequence (host)
+void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route);
+double ctc_decode(const CtcOut& o, const int* idx, int n, std::vector<int>& text);
 void rec_early_begin(bbocr_ctx* c, const GrayPages& g, int pages, int B, const HostBoxes& hb, const bbocr_params& p, RecEarly& e);
 void recognize_impl(bbocr_ctx* c, const GrayPages& g, int B, const HostBoxes& hb, const bbocr_params& p, std::vector<BoxJob>& jobs, std::vector<int>& box_off, RecEarly* early = nullptr);
 bbocr_result* export_result(int B, const std::vector<BoxJob>& jobs, const std::vector<int>& box_off);

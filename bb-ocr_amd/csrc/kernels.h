@@ -177,11 +177,19 @@ struct CtcOut { int len; int cnt; float prod; int pad; };
 // seqs_dev: int2 per sequence {first row, T}; logits fp32 [rows, cs]; out_idx is row-indexed like the pool
 hipError_t launch_ctc(const float* logits, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int* idx_tmp, float* pmax_tmp,
                       int* out_idx, CtcOut* out, hipStream_t s, const unsigned int* ignore = nullptr, float* probs_out = nullptr);   // ignore: 4 x 32-bit class mask or null
-// decoder='beamsearch' (easyocr/utils.py::ctcBeamSearch, host): probs fp32 [rows, cs] as ctc_rows_kernel writes them; seqs = {first row, T}
+// decoder='beamsearch' (easyocr/utils.py::ctcBeamSearch, host: the definition, and the path of beams wider than BBOCR_BEAM_DEVICE_MAX): probs fp32 [rows, cs] as ctc_rows_kernel writes them; seqs = {first row, T}
 void ctc_beam_search_host(const float* mat, int T, int C, int cs, int beam_width, std::vector<int>& text);
 class HostPool;
 void ctc_beam_search_batch(const float* probs, const int* seqs, int nseq, int C, int cs, int beam_width, std::vector<std::vector<int>>& texts,
                            HostPool* pool = nullptr);     // pool: the calling slot's workers (null: the calling thread alone)
+// the same search on the device (ctc_beam.hip), one wave per sequence: text of sequence i into out_text[first row of i ...] (row-indexed like
+// launch_ctc's out_idx), its length into out_len[i].  max_T: the longest T of the table (sizes the labellings' LDS block).  Widths above
+// BBOCR_BEAM_DEVICE_MAX or tables whose LDS block would pass kCtcBeamLdsLimit are hipErrorInvalidValue: ask ctc_beam_on_device first.
+constexpr size_t kCtcBeamLdsLimit = 65536;
+size_t ctc_beam_lds_bytes(int beam_width, int C, int max_T);
+bool ctc_beam_on_device(int beam_width, int C, int max_T);
+hipError_t launch_ctc_beam(const float* probs, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int max_T, int beam_width, int* out_text,
+                           int* out_len, hipStream_t s);
 
 // ------------------------------------------------------------------ OCR pre-processing chain (preproc.hip), SURVEY 8 row f2
 int pp_resize_tile_rows(int H, int W, int dh, int dw);

@@ -211,20 +211,33 @@ void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs) {
     run.rows += part.rows;
 }
 
-// device buffers of one launch_ctc over `rows` time steps of `nseq` sequences (cs: row stride of the logits; beam: the probabilities are kept)
-void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, bool beam) {
+// where a CTC pass's text comes from: the greedy collapse, or ctcBeamSearch on the device (widths up to BBOCR_BEAM_DEVICE_MAX whose longest
+// sequence fits the kernel's LDS block) or on the host (wider beams, longer sequences: the probabilities cross to the host)
+int ctc_route(int beam_width, int C, const int* seqs, int nseq) {
+    if (beam_width <= 0) return CTC_GREEDY;
+    int max_T = 0;
+    for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
+    return ctc_beam_on_device(beam_width, C, max_T) ? CTC_BEAM_DEVICE : CTC_BEAM_HOST;
+}
+
+// device buffers of one launch_ctc over `rows` time steps of `nseq` sequences (cs: row stride of the logits; a beam route keeps the
+// probabilities, the device route adds the search's row-indexed text and its lengths)
+void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route) {
     c->ctc_idx.ensure(rows * 4);
     c->ctc_pmax.ensure(rows * 4);
     c->ctc_out_idx.ensure(rows * 4);
     c->ctc_out.ensure((size_t)nseq * sizeof(CtcOut));
-    if (beam) c->ctc_probs.ensure(rows * cs * sizeof(float));
+    if (route != CTC_GREEDY) c->ctc_probs.ensure(rows * cs * sizeof(float));
+    if (route == CTC_BEAM_DEVICE) {
+        c->ctc_beam_idx.ensure(rows * 4);
+        c->ctc_beam_len.ensure((size_t)nseq * 4);
+    }
 }
 
-// CtcOut -> (text, confidence) of one sequence: the greedy path's classes (idx: the sequence's rows of launch_ctc's out_idx) unless the beam
-// search's text is given; the confidence is the greedy path's either way
-double ctc_decode(const CtcOut& o, const int* idx, const std::vector<int>* beam_text, std::vector<int>& text) {
-    if (beam_text) text = *beam_text;
-    else text.assign(idx, idx + o.len);
+// CtcOut -> (text, confidence) of one sequence: the text is the n classes at idx (the sequence's rows of launch_ctc's out_idx and o.len, or a
+// beam search's answer); the confidence is the greedy path's either way
+double ctc_decode(const CtcOut& o, const int* idx, int n, std::vector<int>& text) {
+    text.assign(idx, idx + n);
     // custom_mean: prod ** (2 / sqrt(len)); an all-blank sequence scores np.array([0])
     return o.cnt > 0 ? std::pow((double)o.prod, 2.0 / std::sqrt((double)o.cnt)) : 0.0;
 }
@@ -251,13 +264,17 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     c->seq_tables.ensure((tiles.size() + seqs.size()) * 4);
     int* tiles_dev = (int*)c->seq_tables.p;
     int* seqs_dev = tiles_dev + tiles.size();
-    const bool beam = c->beam_width > 0;
-    ctc_size(c, rows, nseq, 112, beam);
+    const int route = ctc_route(c->beam_width, 97, seqs.data(), nseq);
+    ctc_size(c, rows, nseq, 112, route);
+    // pinned read-back block: greedy classes [rows] | CtcOut [nseq] | device route: beam text [rows] | its lengths [nseq]
     const size_t oo_off = align_up(rows * 4, 16);
-    c->ctc_pin.ensure(oo_off + (size_t)nseq * sizeof(CtcOut));
+    const size_t bi_off = align_up(oo_off + (size_t)nseq * sizeof(CtcOut), 16), bl_off = bi_off + align_up(rows * 4, 16);
+    c->ctc_pin.ensure(route == CTC_BEAM_DEVICE ? bl_off + (size_t)nseq * 4 : bi_off);
     const int* oidx = (const int*)c->ctc_pin.p;
     const CtcOut* oo = (const CtcOut*)((const char*)c->ctc_pin.p + oo_off);
-    std::vector<float> probs(beam ? rows * 112 : 0);
+    const int* bidx = (const int*)((const char*)c->ctc_pin.p + bi_off);
+    const int* blen = (const int*)((const char*)c->ctc_pin.p + bl_off);
+    std::vector<float> probs(route == CTC_BEAM_HOST ? rows * 112 : 0);      // only the host route moves the probabilities off the card
     std::vector<std::vector<int>> beam_texts;
     if (!c->seq_t1) { HIPCHK(hipEventCreate(&c->seq_t1)); HIPCHK(hipEventCreate(&c->seq_t2)); }
     {
@@ -276,10 +293,19 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
         crnn_sequence(c, rows_pad, tiles_dev, ntiles, (float*)c->seq_logits.p);
         HIPCHK(hipEventRecord(c->seq_t1, ss));
         HIPCHK(launch_ctc((const float*)c->seq_logits.p, rows, 97, 112, seqs_dev, nseq, (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p,
-                          (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, c->ignore_mask, beam ? (float*)c->ctc_probs.p : nullptr));
-        HIPCHK(hipMemcpyAsync(c->ctc_pin.p, c->ctc_out_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));
+                          (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, c->ignore_mask, route != CTC_GREEDY ? (float*)c->ctc_probs.p : nullptr));
+        if (route != CTC_BEAM_DEVICE) HIPCHK(hipMemcpyAsync(c->ctc_pin.p, c->ctc_out_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));    // the search's text replaces it
         HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + oo_off, c->ctc_out.p, (size_t)nseq * sizeof(CtcOut), hipMemcpyDeviceToHost, ss));
-        if (beam) HIPCHK(hipMemcpyAsync(probs.data(), c->ctc_probs.p, probs.size() * sizeof(float), hipMemcpyDeviceToHost, ss));
+        if (route == CTC_BEAM_DEVICE) {
+            int max_T = 0;
+            for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
+            HIPCHK(launch_ctc_beam((const float*)c->ctc_probs.p, rows, 97, 112, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_beam_idx.p,
+                                   (int*)c->ctc_beam_len.p, ss));
+            HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bi_off, c->ctc_beam_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));
+            HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bl_off, c->ctc_beam_len.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, ss));
+        } else if (route == CTC_BEAM_HOST) {
+            HIPCHK(hipMemcpyAsync(probs.data(), c->ctc_probs.p, probs.size() * sizeof(float), hipMemcpyDeviceToHost, ss));
+        }
         HIPCHK(hipEventRecord(c->seq_t2, ss));
     }
     HIPCHK(hipEventSynchronize(c->seq_t2));
@@ -288,10 +314,12 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     c->times[4] += (float)ms_since(t0) - ctc_ms;     // host wait for the recogniser's device work (conv stack of the parts + sequence stage)
     c->times[5] += ctc_ms;                           // CTC kernels + read-back (device span) ...
     t0 = clk::now();                                 // ... + the host decode below
-    if (beam) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, 97, 112, c->beam_width, beam_texts, &host_pool(c));   // the confidence stays the greedy path's
-    for (int i = 0; i < nseq; ++i) {
+    if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, 97, 112, c->beam_width, beam_texts, &host_pool(c));
+    for (int i = 0; i < nseq; ++i) {       // the confidence stays the greedy path's for every route
         const int k = run.seq_k[i];
-        confs[k] = ctc_decode(oo[i], oidx + seqs[2 * i], beam ? &beam_texts[i] : nullptr, texts[k]);
+        if (route == CTC_BEAM_HOST) confs[k] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), texts[k]);
+        else if (route == CTC_BEAM_DEVICE) confs[k] = ctc_decode(oo[i], bidx + seqs[2 * i], std::clamp(blen[i], 0, seqs[2 * i + 1]), texts[k]);
+        else confs[k] = ctc_decode(oo[i], oidx + seqs[2 * i], oo[i].len, texts[k]);
     }
     c->times[5] += (float)ms_since(t0);
 }

@@ -996,6 +996,24 @@ class Reader:
             self._lib.bbocr_free_boxlist(bl)
         return hori, free, polys
 
+    def ctc_beam_device(self, probs_dev, seqs, beam_width, C=97):
+        """The device beam search alone (bbocr_op_ctc_beam): fp32 [rows, cs] device tensor of probabilities, seqs = [(first row, T)], width
+        <= _lib.BEAM_DEVICE_MAX -> one list of class indices per sequence (ctcBeamSearch's text, blank and repeats dropped)."""
+        import ctypes as ct             # the argument C (classes, as in bbocr.h) hides the module's alias here
+
+        torch = self._torch
+        if (not isinstance(probs_dev, torch.Tensor) or not probs_dev.is_cuda or probs_dev.device.index != self.device_index
+                or probs_dev.dtype != torch.float32 or probs_dev.ndim != 2 or not probs_dev.is_contiguous()):
+            raise ValueError(f"probabilities: expected a contiguous float32 [rows,cs] tensor on {self.device}")
+        flat = [int(v) for s in seqs for v in s]
+        n = len(flat) // 2
+        tab = (ct.c_int * max(len(flat), 1))(*flat)
+        off = (ct.c_int * (n + 1))()
+        idx = (ct.c_int * max(1, sum(max(t, 0) for t in flat[1::2])))()
+        self._check(self._lib.bbocr_op_ctc_beam(self._h, ct.c_void_p(probs_dev.data_ptr()), probs_dev.shape[0], tab, n, int(C),
+                                                probs_dev.shape[1], int(beam_width), off, idx))
+        return [idx[off[i]:off[i + 1]] for i in range(n)]
+
     def recognize_device(self, gray_dev, horizontal_lists, free_lists, **kw):
         self._dev_u8(gray_dev, "gray", 3)
         B, H, W = gray_dev.shape

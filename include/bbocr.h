@@ -88,6 +88,11 @@ typedef struct bbocr_tensor_desc {
 
 /* keyword arguments of easyocr.Reader.readtext that affect this path (same names, same defaults) */
 enum { BBOCR_DECODER_GREEDY = 0, BBOCR_DECODER_BEAMSEARCH = 1 };
+/* Widest beam the device search takes.  The kernel keeps one sequence's whole search in the LDS of one workgroup (64 KB): the step's entry
+ * table, beam_width * (1 + C) floats, plus the live labellings as bytes, 2 * beam_width * T (double-buffered), plus under 3 KB of row and
+ * beam state.  At width 32 and C = 128 that is 32 * 129 * 4 = 16,512 B of entries and 64 B per time step: T up to 708, above the 639 steps
+ * of a crop as wide as the default canvas (2560 / 4 - 1).  Width 64 would halve that to T <= 250. */
+#define BBOCR_BEAM_DEVICE_MAX 32
 
 typedef struct bbocr_params {
     double text_threshold; /* 0.7 */
@@ -106,8 +111,11 @@ typedef struct bbocr_params {
     unsigned int ignore_mask[4]; /* recognizer_predict's ignore_idx as a bit mask over class indices 0..127 (allowlist / blocklist):
                                   * those classes are zeroed and the rest renormalised before the arg-max; 0 = none (english_g2 default) */
     int decoder;           /* BBOCR_DECODER_GREEDY (0, readtext's default, the reference's call) or BBOCR_DECODER_BEAMSEARCH (1):
-                            * easyocr/utils.py::ctcBeamSearch without a language model, run on the host over the device's probabilities;
-                            * the confidence is the greedy path's custom_mean for both, as upstream computes it */
+                            * easyocr/utils.py::ctcBeamSearch without a language model over the device's probabilities.  Widths up to
+                            * BBOCR_BEAM_DEVICE_MAX are searched on the device (one wave per sequence; only the text is read back);
+                            * wider beams, and sequences too long for the kernel's LDS block, are searched on the host, which reads the
+                            * probabilities back.  Both give the same text.  The confidence is the greedy path's custom_mean for every
+                            * decoder, as upstream computes it */
     int beam_width;        /* 5 (readtext's beamWidth); used when decoder == BBOCR_DECODER_BEAMSEARCH */
     int rotation_info[4];  /* readtext's rotation_info: up to three angles out of {90, 180, 270}, zero-terminated (all 0 = None, the
                             * reference's call).  Non-empty: Reader.recognize's batched branch -- every crop of a page padded to the page's
@@ -261,7 +269,8 @@ int bbocr_host_component_polys(const int* comps, const int* rowext, int n, int w
 /* utils.group_text_box + Reader.detect's min_size filter on n polygons of one image */
 int bbocr_host_group_boxes(const int* polys, int n, const bbocr_params* p, bbocr_boxlist** out);
 /* easyocr/utils.py::ctcBeamSearch (CTCLabelConverter.decode_beamsearch, no language model) on host probabilities fp32 [n,T,cs]
- * (C <= cs classes, class 0 = blank): text_off [n+1], text_idx (<= n*T).  The host half of bbocr_params::decoder == BEAMSEARCH */
+ * (C <= cs classes, class 0 = blank): text_off [n+1], text_idx (<= n*T).  The definition of bbocr_params::decoder == BEAMSEARCH, the path of
+ * beams wider than BBOCR_BEAM_DEVICE_MAX, and the yardstick of bbocr_op_ctc_beam */
 int bbocr_host_ctc_beam(const float* probs, int n, int T, int C, int cs, int beam_width, int* text_off, int* text_idx);
 
 /* ---- single-operator entry points (used by the parity tests; same kernels the pipeline runs) ---- */
@@ -281,6 +290,17 @@ int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW
  * (bbocr_params::ignore_mask) or NULL; beam_width <= 0: greedy, > 0: ctcBeamSearch with that width (bbocr_params::decoder) */
 int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, int cs, int* text_off, int* text_idx, double* conf,
                  const unsigned int* ignore_mask, int beam_width);
+/* the probabilities alone, as the CTC stage's row kernel writes them: softmax of logits fp32 [rows,cs] over C <= 128 classes, the classes of
+ * ignore_mask (or NULL) zeroed, the rest renormalised -> dev_probs_out fp32 [rows,cs] (device; columns >= C are not written) */
+int bbocr_op_ctc_probs(bbocr_ctx* ctx, const float* dev_logits, size_t rows, int C, int cs, const unsigned int* ignore_mask,
+                       float* dev_probs_out);
+/* the device beam search alone (the kernel behind decoder == BEAMSEARCH for widths <= BBOCR_BEAM_DEVICE_MAX): dev_probs fp32 [rows,cs]
+ * (device), seqs (host) = {first row, T} per sequence, ragged, T = 0 allowed -> text_off [nseq+1], text_idx (<= the sum of T), both host.
+ * The text equals bbocr_host_ctc_beam's on the same rows, exactly.  BBOCR_ERR_ARG before anything is queued: a null pointer, cs < C,
+ * C > 128, beam_width < 1 or > BBOCR_BEAM_DEVICE_MAX, a sequence outside [0, rows), a T too long for the kernel's LDS block at this width
+ * (see BBOCR_BEAM_DEVICE_MAX) */
+int bbocr_op_ctc_beam(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width,
+                      int* text_off, int* text_idx);
 /* cv2.resize(INTER_LINEAR) on uint8 [N,sh,sw,C] -> [N,dh,dw,C] (device) */
 int bbocr_op_resize_u8(bbocr_ctx* ctx, const uint8_t* dev_src, int N, int sh, int sw, int C, uint8_t* dev_dst, int dh, int dw);
 /* JPEG pages decoded ONCE on the host into libjpeg's YCbCr triples (out_color_space = JCS_YCbCr; PIL: draft("YCbCr")): uint8 [npix,3]
