@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("BBOCR_LIB_PATH") or os.path.join(_HERE, "libbbocr.so"
 
 class bbocr_config(C.Structure):
     _fields_ = [("device", C.c_int), ("det_sub_batch", C.c_int), ("rec_max_cols", C.c_int), ("precision", C.c_int), ("call_slots", C.c_int),
-                ("host_threads", C.c_int), ("reserved", C.c_int * 2)]
+                ("host_threads", C.c_int), ("rec_quant", C.c_int), ("reserved", C.c_int * 1)]
 
 
 PRECISIONS = {"bf16": 0, "fp16": 1, "exact": 2, "mixed": 3, "exact_rec": 4}
@@ -117,6 +117,8 @@ PROTOTYPES = {
     "bbocr_op_conv2d": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "bbocr_crnn_logits": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    "bbocr_op_qlinear": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_float)]),
+    "bbocr_op_qlstm": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "bbocr_op_ctc": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                C.POINTER(C.c_uint), C.c_int]),
     "bbocr_op_ctc_probs": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_uint), _vp]),

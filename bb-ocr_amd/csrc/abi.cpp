@@ -27,7 +27,8 @@ int bbocr_create(const bbocr_config* cfg, bbocr_ctx** out) {
         c = new bbocr_ctx();
         c->root = c;
         if (cfg) c->cfg = *cfg;
-        if (c->cfg.precision < BBOCR_PREC_BF16 || c->cfg.precision > BBOCR_PREC_EXACT_REC || c->cfg.call_slots < 0 || c->cfg.call_slots > kMaxSlots) {
+        if (c->cfg.precision < BBOCR_PREC_BF16 || c->cfg.precision > BBOCR_PREC_EXACT_REC || c->cfg.call_slots < 0 || c->cfg.call_slots > kMaxSlots ||
+            c->cfg.rec_quant < 0 || c->cfg.rec_quant > 1 || (c->cfg.rec_quant == 1 && !rec_split(c))) {     // rec_quant quantises the exact conv stack's features
             delete c;                      // an unknown value must not silently mean one of the modes
             return BBOCR_ERR_ARG;
         }
@@ -87,7 +88,7 @@ void slot_destroy(bbocr_ctx* c) {
                       &c->ccl_counters, &c->crop_desc, &c->crop_desc2, &c->crop_scratch, &c->crop_hscratch, &c->crop_wscratch, &c->crop_luts, &c->crop_hist,
                       &c->ctc_idx, &c->ctc_pmax, &c->ctc_out_idx, &c->ctc_out, &c->seq_v, &c->seq_xp, &c->seq_h, &c->seq_lin, &c->seq_logits,
                       &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out,
-                      &c->pg_rgb, &c->pg_tab};
+                      &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp};
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->seq_stream) (void)hipStreamDestroy(c->seq_stream);

@@ -223,10 +223,69 @@ int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW
         crnn_features_wide(ctx, part, dd, wide);
         RecRun run;
         rec_add_tables(run, part, lstm_tile_seqs(rec_mode(ctx)));
-        ctx->seq_tables.ensure(run.tiles.size() * 4);
-        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, run.tiles.data(), run.tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        crnn_sequence(ctx, rows_pad, (const int*)ctx->seq_tables.p, (int)(run.tiles.size() / 4), (float*)ctx->seq_logits.p);
+        rec_seq_tiles(ctx, run);
+        ctx->seq_tables.ensure((run.tiles.size() + run.seqs.size()) * 4);
+        int* tiles_dev = (int*)ctx->seq_tables.p;
+        int* seqs_dev = tiles_dev + run.tiles.size();
+        HIPCHK(hipMemcpyAsync(tiles_dev, run.tiles.data(), run.tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(seqs_dev, run.seqs.data(), run.seqs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        crnn_sequence(ctx, rows, rows_pad, tiles_dev, (int)(run.tiles.size() / 4), seqs_dev, (int)(run.seqs.size() / 2), (float*)ctx->seq_logits.p);
         HIPCHK(hipMemcpyAsync(dev_logits, ctx->seq_logits.p, rows * 112 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+// the segment table of the two rec_quant entry points: pairs {first row, T} that tile [0, rows) in order; uploaded behind `ahead` ints
+static const int* q8_op_seqs(bbocr_ctx* ctx, const int* seqs, int nseq, int rows, const std::vector<int>& ahead) {
+    if (!rec_quant(ctx)) fail(BBOCR_ERR_STATE, "this context was not created with rec_quant = 1");
+    if (!ctx->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
+    if (!seqs || nseq <= 0 || rows <= 0) fail(BBOCR_ERR_ARG, "bad segment table");
+    long long at = 0;
+    for (int i = 0; i < nseq; ++i) {
+        if (seqs[2 * i] != at || seqs[2 * i + 1] <= 0) fail(BBOCR_ERR_ARG, "the segments must tile the rows in order");
+        at += seqs[2 * i + 1];
+    }
+    if (at != rows) fail(BBOCR_ERR_ARG, "the segments must tile the rows in order");
+    ctx->seq_tables.ensure((ahead.size() + (size_t)nseq * 2) * 4);
+    int* d = (int*)ctx->seq_tables.p;
+    if (!ahead.empty()) HIPCHK(hipMemcpyAsync(d, ahead.data(), ahead.size() * 4, hipMemcpyHostToDevice, ctx->stream));     // (the callers end synchronised)
+    HIPCHK(hipMemcpyAsync(d + ahead.size(), seqs, (size_t)nseq * 8, hipMemcpyHostToDevice, ctx->stream));
+    return d + ahead.size();
+}
+
+int bbocr_op_qlinear(bbocr_ctx* ctx, const float* dev_x, int rows, const int* seqs, int nseq, int layer, float* dev_out, uint8_t* dev_codes,
+                     float* seg_params) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!dev_x || !dev_out || !dev_codes || !seg_params || layer < 0 || layer > 4) fail(BBOCR_ERR_ARG, "bad qlinear arguments");
+        const int* seqs_dev = q8_op_seqs(ctx, seqs, nseq, rows, {});
+        const bbocr_ctx::Q8Layer& L = layer < 2 ? ctx->q_ih[layer] : (layer < 4 ? ctx->q_lin[layer - 2] : ctx->q_pred);
+        const int K = (layer == 2 || layer == 3) ? 512 : 256, N = layer < 2 ? 2048 : (layer < 4 ? 256 : 112);
+        const size_t rows_pad = align_up((size_t)rows, 256);
+        ctx->seq_q8.ensure(rows_pad * 512);
+        ctx->seq_rowp.ensure(rows_pad * 16);
+        ctx->seq_xp.ensure(rows_pad * 2048 * 4);
+        ctx->seq_lin.ensure((size_t)nseq * 8);
+        HIPCHK(launch_q8_quantize(dev_x, 0, K, (size_t)rows, rows_pad, seqs_dev, nseq, (float*)ctx->seq_rowp.p, (int8_t*)ctx->seq_q8.p, dev_codes,
+                                  (float*)ctx->seq_lin.p, ctx->stream));
+        HIPCHK(launch_q8_gemm((const int8_t*)ctx->seq_q8.p, rows_pad, K, L.w, N, (const float*)ctx->seq_rowp.p, L.scale, L.bias, (float*)ctx->seq_xp.p, N,
+                              ctx->stream));
+        HIPCHK(hipMemcpyAsync(dev_out, ctx->seq_xp.p, (size_t)rows * N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(seg_params, ctx->seq_lin.p, (size_t)nseq * 8, hipMemcpyDeviceToHost, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+int bbocr_op_qlstm(bbocr_ctx* ctx, const float* dev_g, int rows, const int* seqs, int nseq, int layer, float* dev_h, float* dev_c, uint8_t* dev_hcodes,
+                   float* dev_hparams) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!dev_g || !dev_h || !dev_c || !dev_hcodes || !dev_hparams || layer < 0 || layer > 1) fail(BBOCR_ERR_ARG, "bad qlstm arguments");
+        RecRun run;
+        if (seqs && nseq > 0) run.seqs.assign(seqs, seqs + (size_t)nseq * 2);
+        rec_seq_tiles(ctx, run);
+        const int* seqs_dev = q8_op_seqs(ctx, seqs, nseq, rows, run.tiles);
+        const bbocr_ctx::Q8Layer& L = ctx->q_hh[layer];
+        HIPCHK(launch_lstm_q8(dev_g, L.w, L.scale, L.bias, dev_h, seqs_dev, (const int*)ctx->seq_tables.p, (int)(run.tiles.size() / 4), dev_c, dev_hcodes,
+                              dev_hparams, ctx->stream));
         slot_sync(ctx, ctx->stream);
     });
 }

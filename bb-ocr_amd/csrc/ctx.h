@@ -168,6 +168,10 @@ struct WeightView {
     ConvPlan r1, r2, r3, r4, r5, r6, xproj[2], lin[2], pred;
     uint16_t* whh[2] = {nullptr, nullptr};
     float whh_scale[2] = {1.f, 1.f};   // exact mode: 2^-s of the packed W_hh (pack_lstm_whh_split)
+    // rec_quant (bbocr_config::rec_quant): the eleven tensors of the sequence half as symmetric qint8, packed for quant.hip; scales per
+    // 16-column block (the two directions of a projection have their own), fp32 biases.  xproj / lin / pred / whh above stay empty then.
+    struct Q8Layer { int8_t* w = nullptr; float* scale = nullptr; float* bias = nullptr; };
+    Q8Layer q_ih[2], q_hh[2], q_lin[2], q_pred;      // q_ih: 256 -> 2048 (b_ih); q_hh: packed by pack_q8_whh, scale [2], bias b_hh [2][1024]
     void* zero_page = nullptr;   // 256 zero bytes (padding source of the LDS-DMA conv variant)
 };
 
@@ -244,12 +248,14 @@ struct bbocr_ctx : WeightView {
     PinBuf desc_pin, desc_pin2;               // staging of crop_desc / crop_desc2 uploads
     PinBuf ctc_pin;                           // CTC results land here (pinned: the 1.7 MB D2H copy of a 64-page pass runs at link speed)
     DevBuf seq_v, seq_xp, seq_h, seq_lin, seq_logits, seq_tables;
+    DevBuf seq_q8, seq_rowp;                  // rec_quant: the coded rows int8 [rows, 512] and their float4 parameters
 };
 
 // element type of a network's MFMA operands / stored activations (El<> in common.h), from bbocr_config::precision
 inline int det_el(const bbocr_ctx* c) { return (c->cfg.precision == BBOCR_PREC_FP16 || c->cfg.precision == BBOCR_PREC_EXACT || c->cfg.precision == BBOCR_PREC_EXACT_REC) ? 1 : 0; }
 inline int rec_el(const bbocr_ctx* c) { return c->cfg.precision != BBOCR_PREC_BF16 ? 1 : 0; }     // MIXED: bf16 detector, fp16 recogniser
 inline bool rec_split(const bbocr_ctx* c) { return c->cfg.precision == BBOCR_PREC_EXACT || c->cfg.precision == BBOCR_PREC_EXACT_REC; }   // recogniser tensors are [hi | lo] fp16 pairs
+inline bool rec_quant(const bbocr_ctx* c) { return c->cfg.rec_quant == 1; }     // sequence half in dynamic int8 (quant.hip); needs rec_split
 inline bool det_split(const bbocr_ctx* c) { return c->cfg.precision == BBOCR_PREC_EXACT; }   // and so are the detector's (split-fp16 plans in every layer)
 
 // ------------------------------------------------------------------------------------------------ shared types
@@ -403,7 +409,8 @@ const CropDesc* rec_upload_descs(bbocr_ctx* c, const RecPart& part, DevBuf& desc
 uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part);
 void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide);
 void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
-void crnn_sequence(bbocr_ctx* c, size_t rows_pad, const int* tiles_dev, int ntiles, float* logits);
+void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_dev, int ntiles, const int* seqs_dev, int nseq, float* logits);
+void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);     // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}
 enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2 };   // where the text of a CTC pass comes from (ctc_route)
 int ctc_route(int beam_width, int C, const int* seqs, int nseq);   // seqs: {first row, T} per sequence (host)
 void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route);

@@ -173,6 +173,24 @@ void pack_lstm_whh8(const float* whh_fwd, const float* whh_bwd, uint16_t* out, i
 size_t lstm_whh_split_packed_elems();
 float pack_lstm_whh_split(const float* whh_fwd, const float* whh_bwd, uint16_t* out);   // -> acc_scale (2^-s)
 int lstm8_xproj_channel(int dir, int gate, int unit);
+// ---- rec_quant (quant.hip): the sequence half in torch's dynamic int8 arithmetic, per crop.  seqs_dev: int2 {first row, T} per crop (the CTC
+// stage's table).  launch_q8_quantize: parameter + coding pass over x (src_pair 0: fp32 [rows, K]; 1: the exact mode's fp16 pair [rows, K | K]) ->
+// rowp float4 [rows_pad] {scale, 1 / scale, zero point, 0}, a8 int8 [rows_pad, K] = code - zero point (rows past `rows` cleared), optionally the
+// codes uint8 [rows, K] and segp float2 [nseq] {scale, zero point}.  launch_q8_gemm: out fp32 [rows_pad, ldo] = fmaf(acc, rowp.scale *
+// wscale[col / 16], bias[col]) over N columns (N % 64 == 0, or 112 with K = 256) of weights packed by pack_q8_weights.
+size_t q8_packed_bytes(int N, int K);
+void pack_q8_weights(const int8_t* q /*[N][K]*/, int N, int K, int8_t* out);
+void pack_q8_whh(const int8_t* q_fwd, const int8_t* q_bwd /*[1024][256]*/, int8_t* out /*2 x 256 KB*/);
+hipError_t launch_q8_quantize(const void* x, int src_pair, int K, size_t rows, size_t rows_pad, const int* seqs_dev, int nseq, float* rowp, int8_t* a8,
+                              uint8_t* codes, float* segp, hipStream_t s);
+hipError_t launch_q8_gemm(const int8_t* a8, size_t rows_pad, int K, const int8_t* wpk, int N, const float* rowp, const float* wscale, const float* bias,
+                          float* out, int ldo, hipStream_t s);
+// G fp32 [rows, 2048] (column dir * 1024 + gate * 256 + unit) -> out fp32 [rows, 512] (fwd | bwd).  tiles_dev: int4 {first sequence, sequences
+// (1..16), longest T, 0} per workgroup, indexing seqs_dev.  whh_scale [2], bhh [2][1024].  Optional, row-indexed like out: c_out (the cell state),
+// hcodes uint8 [rows, 512] and hparams float2 [rows][2] = codes and {scale, zero point} of the h that ENTERED that step.
+constexpr int LSTM_Q8_SEQS = 16;
+hipError_t launch_lstm_q8(const float* G, const int8_t* whh_pk, const float* whh_scale, const float* bhh, float* out, const int* seqs_dev,
+                          const int* tiles_dev, int ntiles, float* c_out, uint8_t* hcodes, float* hparams, hipStream_t s);
 struct CtcOut { int len; int cnt; float prod; int pad; };
 // seqs_dev: int2 per sequence {first row, T}; logits fp32 [rows, cs]; out_idx is row-indexed like the pool
 hipError_t launch_ctc(const float* logits, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int* idx_tmp, float* pmax_tmp,

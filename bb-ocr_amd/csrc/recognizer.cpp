@@ -94,9 +94,50 @@ void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs
 // Sequence half of the recogniser over the POOLED time steps of every bucket (rows = sum n_i*T_i, padded to x256):
 // v bf16 [rows,256] (ctx->seq_v) -> logits fp32 [rows,112].  The two linear layers and both input projections are
 // single GEMMs over all rows; each BiLSTM layer is ONE launch whose workgroups carry their own sequence length.
-void crnn_sequence(bbocr_ctx* c, size_t rows_pad, const int* tiles_dev, int ntiles, float* logits) {
+// rec_quant: every matrix product as [parameter pass, coding pass, int8 GEMM] with one set of activation parameters per crop (seqs_dev), the
+// recurrence as lstm_q8_kernel; all tensors between the products are fp32.
+static void crnn_sequence_q8(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_dev, int ntiles, const int* seqs_dev, int nseq, float* logits) {
+    c->seq_xp.ensure(rows_pad * 2048 * 4);
+    c->seq_h.ensure(rows_pad * 512 * 4);
+    c->seq_lin.ensure(rows_pad * 256 * 4);
+    c->seq_q8.ensure(rows_pad * 512);
+    c->seq_rowp.ensure(rows_pad * 16);
+    int8_t* a8 = (int8_t*)c->seq_q8.p;
+    float* rowp = (float*)c->seq_rowp.p;
+    auto qlinear = [&](const void* x, int pair, int K, const bbocr_ctx::Q8Layer& L, int N, float* out) {
+        HIPCHK(launch_q8_quantize(x, pair, K, rows, rows_pad, seqs_dev, nseq, rowp, a8, nullptr, nullptr, c->cur));
+        HIPCHK(launch_q8_gemm(a8, rows_pad, K, L.w, N, rowp, L.scale, L.bias, out, N, c->cur));
+    };
+    const void* cur = c->seq_v.p;                     // the conv stack's features: the exact mode's fp16 pair, rebuilt in fp32 by the coding pass
+    for (int l = 0; l < 2; ++l) {
+        qlinear(cur, l == 0, 256, c->q_ih[l], 2048, (float*)c->seq_xp.p);
+        HIPCHK(launch_lstm_q8((const float*)c->seq_xp.p, c->q_hh[l].w, c->q_hh[l].scale, c->q_hh[l].bias, (float*)c->seq_h.p, seqs_dev, tiles_dev, ntiles,
+                              nullptr, nullptr, nullptr, c->cur));
+        float* dst = (float*)(l == 0 ? c->seq_lin.p : c->seq_v.p);
+        qlinear(c->seq_h.p, 0, 512, c->q_lin[l], 256, dst);
+        cur = dst;
+    }
+    qlinear(cur, 0, 256, c->q_pred, 112, logits);
+}
+
+// the int8 recurrence's workgroups take LSTM_Q8_SEQS consecutive sequences of the table, each with its own T
+void rec_seq_tiles(const bbocr_ctx* c, RecRun& run) {
+    if (!rec_quant(c)) return;
+    run.tiles.clear();
+    const int nseq = (int)(run.seqs.size() / 2);
+    for (int s0 = 0; s0 < nseq; s0 += LSTM_Q8_SEQS) {
+        const int n = std::min(LSTM_Q8_SEQS, nseq - s0);
+        int tmax = 0;
+        for (int i = 0; i < n; ++i) tmax = std::max(tmax, run.seqs[2 * (s0 + i) + 1]);
+        const int t[4] = {s0, n, tmax, 0};
+        run.tiles.insert(run.tiles.end(), t, t + 4);
+    }
+}
+
+void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_dev, int ntiles, const int* seqs_dev, int nseq, float* logits) {
     c->prof_group = 1;
     c->arena.dry = false;
+    if (rec_quant(c)) { crnn_sequence_q8(c, rows, rows_pad, tiles_dev, ntiles, seqs_dev, nseq, logits); return; }
     const bool sp = rec_split(c);
     const int m = rec_mul(c);
     c->seq_xp.ensure(rows_pad * 2048 * (sp ? 4 : 2));            // exact mode: the input projection stays fp32
@@ -248,6 +289,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     if (rows == 0) return;
     const size_t rows_pad = align_up(rows, 256);
     auto t0 = clk::now();
+    rec_seq_tiles(c, run);
     {   // longest sequences first: the launch ends with the shortest tails
         std::vector<int>& tiles = run.tiles;
         const size_t nt = tiles.size() / 4;
@@ -290,7 +332,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
         struct Restore { bbocr_ctx* c; ~Restore() { c->cur = c->stream; } } restore{c};
         HIPCHK(hipMemcpyAsync(tiles_dev, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, ss));
         HIPCHK(hipMemcpyAsync(seqs_dev, seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, ss));
-        crnn_sequence(c, rows_pad, tiles_dev, ntiles, (float*)c->seq_logits.p);
+        crnn_sequence(c, rows, rows_pad, tiles_dev, ntiles, seqs_dev, nseq, (float*)c->seq_logits.p);
         HIPCHK(hipEventRecord(c->seq_t1, ss));
         HIPCHK(launch_ctc((const float*)c->seq_logits.p, rows, 97, 112, seqs_dev, nseq, (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p,
                           (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, c->ignore_mask, route != CTC_GREEDY ? (float*)c->ctc_probs.p : nullptr));

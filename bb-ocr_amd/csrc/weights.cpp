@@ -1,5 +1,6 @@
 // Weight tables: eval-mode BatchNorm folded into the convolutions, bf16 rounding, MFMA fragment packing (easyocr Reader.__init__ / get_detector / get_recognizer).
 #include "ctx.h"
+#include <limits>
 
 // ------------------------------------------------------------------------------------------------ weights
 
@@ -120,7 +121,7 @@ void free_weights(bbocr_ctx* c) {
 // bbocr_alloc_weights) import it: no fp32 state-dict, no host hop and no re-packing on the receivers (~49 MB in
 // bf16 instead of 98 MB of fp32).
 namespace {
-struct BlobHeader { unsigned long long magic; int precision, nblocks; unsigned long long bytes; int craft, crnn; unsigned long long layout_hash; int pad[6]; };
+struct BlobHeader { unsigned long long magic; int precision, nblocks; unsigned long long bytes; int craft, crnn; unsigned long long layout_hash; int rec_quant; int pad[5]; };
 static_assert(sizeof(BlobHeader) == 64, "blob header");
 constexpr unsigned long long BLOB_MAGIC = 0x62626f6372776231ULL;   // "bbocrwb1"
 unsigned long long layout_hash(const bbocr_ctx* c) {     // FNV-1a over the per-block sizes: equal totals with different blocks do not pass
@@ -152,7 +153,7 @@ void weights_export(bbocr_ctx* c, void* dev_dst, size_t bytes) {
     if (bytes != weights_blob_bytes(c)) fail(BBOCR_ERR_ARG, "weight blob: wrong size");
     BlobHeader h{};
     h.magic = BLOB_MAGIC; h.precision = c->cfg.precision; h.nblocks = (int)c->owned.size(); h.bytes = bytes;
-    h.craft = c->craft_loaded; h.crnn = c->crnn_loaded; h.layout_hash = layout_hash(c);
+    h.craft = c->craft_loaded; h.crnn = c->crnn_loaded; h.layout_hash = layout_hash(c); h.rec_quant = c->cfg.rec_quant;
     char* d = (char*)dev_dst;
     HIPCHK(hipMemcpyAsync(d, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     size_t off = sizeof(h);
@@ -168,10 +169,13 @@ void weights_export(bbocr_ctx* c, void* dev_dst, size_t bytes) {
 }
 
 void weights_import(bbocr_ctx* c, const void* dev_src, size_t bytes) {
-    if (bytes != weights_blob_bytes(c)) fail(BBOCR_ERR_ARG, "weight blob: size does not match this context's layout (same precision / networks on every rank?)");
+    if (bytes < sizeof(BlobHeader)) fail(BBOCR_ERR_ARG, "weight blob: too small");
     const char* s = (const char*)dev_src;
     BlobHeader h{};
     HIPCHK(hipMemcpy(&h, s, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.magic == BLOB_MAGIC && h.rec_quant != c->cfg.rec_quant)       // before the size check: the two kinds differ in size as well
+        fail(BBOCR_ERR_WEIGHTS, "weight blob: made with rec_quant = " + std::to_string(h.rec_quant) + ", this context has " + std::to_string(c->cfg.rec_quant));
+    if (bytes != weights_blob_bytes(c)) fail(BBOCR_ERR_ARG, "weight blob: size does not match this context's layout (same precision / networks on every rank?)");
     if (h.magic != BLOB_MAGIC || h.precision != c->cfg.precision || h.nblocks != (int)c->owned.size() || h.bytes != bytes ||
         h.craft != (int)c->craft_loaded || h.crnn != (int)c->crnn_loaded || h.layout_hash != layout_hash(c))
         fail(BBOCR_ERR_WEIGHTS, "weight blob does not match this context (precision, networks or layout differ)");
@@ -302,6 +306,64 @@ void load_craft(bbocr_ctx* c, const TensorMap& tm) {
     c->craft_loaded = true;
 }
 
+// rec_quant: default_weight_observer (MinMaxObserver, per_tensor_symmetric, qint8) + torch.quantize_per_tensor of one weight tensor
+static float quantize_weight_q8(const float* w, size_t n, std::vector<int8_t>& q) {
+    float mn = 0.f, mx = 0.f;
+    for (size_t i = 0; i < n; ++i) { mn = std::min(mn, w[i]); mx = std::max(mx, w[i]); }
+    float scale = std::max(-mn, mx) / 127.5f;
+    scale = std::max(scale, std::numeric_limits<float>::epsilon());
+    const float inv = 1.0f / scale;
+    q.resize(n);
+    for (size_t i = 0; i < n; ++i) q[i] = (int8_t)std::min(127.f, std::max(-128.f, std::nearbyintf(w[i] * inv)));
+    return scale;
+}
+
+// one quantised Linear W [N][K] (+ bias [N]) -> packed fragments, its scale for each of the ceil(N / 16) column blocks, bias padded to them
+static void load_q8_linear(bbocr_ctx* c, bbocr_ctx::Q8Layer& L, const float* w, const float* b, int N, int K) {
+    std::vector<int8_t> q, pk(q8_packed_bytes(N, K));
+    const float s = quantize_weight_q8(w, (size_t)N * K, q);
+    pack_q8_weights(q.data(), N, K, pk.data());
+    const int NF = (N + 15) / 16;
+    std::vector<float> bp((size_t)NF * 16, 0.f);
+    std::copy(b, b + N, bp.begin());
+    L.w = upload(c, pk);
+    L.scale = upload(c, std::vector<float>(NF, s));
+    L.bias = upload(c, bp);
+}
+
+// the sequence half of a rec_quant context: eleven tensors, each with its own scale; biases stay fp32 and apart (b_ih with the input
+// projection, b_hh with the recurrent product, as DynamicQuantizedLSTM's cell adds them)
+static void load_crnn_q8(bbocr_ctx* c, const TensorMap& tm) {
+    for (int l = 0; l < 2; ++l) {
+        const std::string sm = "SequenceModeling." + std::to_string(l) + ".";
+        std::vector<int8_t> qih[2], qhh[2];
+        std::vector<float> s_ih(128), s_hh(2), b_ih(2048), b_hh(2048);
+        for (int d = 0; d < 2; ++d) {
+            const std::string sfx = d ? "_reverse" : "";
+            const float s = quantize_weight_q8(tm.get(sm + "rnn.weight_ih_l0" + sfx, (size_t)1024 * 256), (size_t)1024 * 256, qih[d]);
+            std::fill(s_ih.begin() + d * 64, s_ih.begin() + (d + 1) * 64, s);
+            s_hh[d] = quantize_weight_q8(tm.get(sm + "rnn.weight_hh_l0" + sfx, (size_t)1024 * 256), (size_t)1024 * 256, qhh[d]);
+            const float* bi = tm.get(sm + "rnn.bias_ih_l0" + sfx, 1024);
+            const float* bh = tm.get(sm + "rnn.bias_hh_l0" + sfx, 1024);
+            std::copy(bi, bi + 1024, b_ih.begin() + d * 1024);
+            std::copy(bh, bh + 1024, b_hh.begin() + d * 1024);
+        }
+        qih[0].insert(qih[0].end(), qih[1].begin(), qih[1].end());          // [2048][256]: forward rows, then backward rows
+        std::vector<int8_t> pk(q8_packed_bytes(2048, 256));
+        pack_q8_weights(qih[0].data(), 2048, 256, pk.data());
+        c->q_ih[l].w = upload(c, pk);
+        c->q_ih[l].scale = upload(c, s_ih);
+        c->q_ih[l].bias = upload(c, b_ih);
+        std::vector<int8_t> hk((size_t)2 * 1024 * 256);
+        pack_q8_whh(qhh[0].data(), qhh[1].data(), hk.data());
+        c->q_hh[l].w = upload(c, hk);
+        c->q_hh[l].scale = upload(c, s_hh);
+        c->q_hh[l].bias = upload(c, b_hh);
+        load_q8_linear(c, c->q_lin[l], tm.get(sm + "linear.weight", (size_t)256 * 512), tm.get(sm + "linear.bias", 256), 256, 512);
+    }
+    load_q8_linear(c, c->q_pred, tm.get("Prediction.weight", (size_t)97 * 256), tm.get("Prediction.bias", 97), 97, 256);
+}
+
 void load_crnn(bbocr_ctx* c, const TensorMap& tm) {
     const std::string fe = "FeatureExtraction.ConvNet.";
     {
@@ -324,6 +386,11 @@ void load_crnn(bbocr_ctx* c, const TensorMap& tm) {
     load_layer(c, tm, c->r4, fe + "11", fe + "12", 128, 256, 3, 1, 1, rec_el(c), rec_split(c));
     load_layer(c, tm, c->r5, fe + "14", fe + "15", 256, 256, 3, 1, 1, rec_el(c), rec_split(c));
     load_layer(c, tm, c->r6, fe + "18", "", 256, 256, 2, 0, 1, rec_el(c), rec_split(c));
+    if (rec_quant(c)) {
+        load_crnn_q8(c, tm);
+        c->crnn_loaded = true;
+        return;
+    }
     for (int l = 0; l < 2; ++l) {
         const std::string sm = "SequenceModeling." + std::to_string(l) + ".";
         // input projection of both directions as one 1x1 conv with the channel permutation the LSTM kernel reads

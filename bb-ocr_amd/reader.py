@@ -380,7 +380,7 @@ class Reader:
     def __init__(self, lang_list, gpu=True, model_storage_directory=None, user_network_directory=None,
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
-                 rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, **_ignored):
+                 rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, **_ignored):
         import torch
 
         if list(lang_list) != ["en"]:
@@ -393,6 +393,13 @@ class Reader:
         self.device_index = torch.cuda.current_device() if device_index is None else int(device_index)
         self.device = f"cuda:{self.device_index}"
         self._lib = _lib.load()
+        if rec_quant is None:       # the sequence half in easyocr's CPU default arithmetic (dynamic int8, bbocr_config::rec_quant); `quantize` stays ignored
+            rec_quant = os.environ.get("BBOCR_REC_QUANT", "").strip() == "1"
+        self.rec_quant = bool(rec_quant)
+        if self.rec_quant and precision is None:
+            precision = "exact_rec"     # what is quantised are the fp32 path's features: the exact recogniser delivers them to 1e-5
+        if self.rec_quant and precision in ("bf16", "fp16", "mixed"):
+            raise ValueError("rec_quant needs precision 'exact' or 'exact_rec'")
         if precision is None:       # the reference constructs Reader(["en"], gpu=...) (enhanced_extractor.py:153): the mode comes from the environment
             # default "fp16": the cheapest mode whose boxes AND strings equalled the fp32 CPU path's on everything measured -- 2,051 boxes
             # of synthetic pages, 471 of dense A4 scans, 110 on the reference's seven real images.  "mixed" (bf16
@@ -410,7 +417,8 @@ class Reader:
         self.device_decode = bool(device_decode)
         self.jpeg_chroma = jpeg_chroma(device_decode)     # "chroma": 4:4:4, 4:2:2 and 4:4:0 files are decoded on the card as well
         cfg = _lib.bbocr_config(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
-                                precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads)
+                                precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads,
+                                rec_quant=int(self.rec_quant))
         h = C.c_void_p()
         rc = self._lib.bbocr_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -466,6 +474,58 @@ class Reader:
         """Fill a ``Reader(weights="empty")`` from another rank's blob (same precision, same networks)."""
         self._dev_u8(blob, "weight blob", 1, (self.weights_blob_size(),))
         self._check(self._lib.bbocr_weights_import(self._h, C.c_void_p(blob.data_ptr()), blob.numel()))
+
+    # -- rec_quant stage entry points (bbocr_op_qlinear / bbocr_op_qlstm): what the tests pin against tests/quant_ref.py -------
+    def _q_seqs(self, seqs):
+        flat = [int(v) for pair in seqs for v in pair]
+        return (C.c_int * len(flat))(*flat), len(flat) // 2
+
+    def _dev_f32(self, t, name, shape):
+        torch = self._torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device_index or t.dtype != torch.float32 \
+                or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or min(t.shape) <= 0:
+            raise ValueError(f"{name}: expected a contiguous float32 tensor {tuple(shape)} on {self.device}")
+        return t
+
+    def qlinear_device(self, x, seqs, layer):
+        """One dynamically quantised product of a ``rec_quant`` Reader.  x: float32 device tensor [rows, K]; seqs: (first row, T) per crop, tiling
+        the rows in order; layer: 0 / 1 input projection of BiLSTM 0 / 1 (K 256 -> 2048), 2 / 3 the Linear behind it (512 -> 256), 4 Prediction
+        (256 -> 112).  -> (out float32 [rows, N], codes uint8 [rows, K], params float32 [crops, 2] = (scale, zero point)) -- out and codes on
+        the device, params a numpy array."""
+        import numpy as np
+
+        torch = self._torch
+        if layer not in (0, 1, 2, 3, 4):
+            raise ValueError("layer: 0 / 1 input projections, 2 / 3 the Linear layers, 4 Prediction")
+        K = 512 if layer in (2, 3) else 256
+        N = {0: 2048, 1: 2048, 2: 256, 3: 256, 4: 112}[layer]
+        rows = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else 0
+        self._dev_f32(x, "x", (rows, K))
+        tab, nseq = self._q_seqs(seqs)
+        out = torch.empty((rows, N), dtype=torch.float32, device=self.device)
+        codes = torch.empty((rows, K), dtype=torch.uint8, device=self.device)
+        params = np.zeros((nseq, 2), np.float32)
+        self._check(self._lib.bbocr_op_qlinear(self._h, C.c_void_p(x.data_ptr()), rows, tab, nseq, int(layer), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(codes.data_ptr()), params.ctypes.data_as(C.POINTER(C.c_float))))
+        return out, codes, params
+
+    def qlstm_device(self, g, seqs, layer):
+        """The int8 recurrence of BiLSTM ``layer`` of a ``rec_quant`` Reader.  g: float32 device tensor [rows, 2048], the input projection
+        (column dir * 1024 + gate * 256 + unit); seqs as in qlinear_device.  -> device tensors (h [rows, 512], c [rows, 512], hcodes uint8
+        [rows, 512], hparams [rows, 2, 2]): h and c AFTER step t of each direction, and the codes and (scale, zero point) of the h that entered it."""
+        torch = self._torch
+        if layer not in (0, 1):
+            raise ValueError("layer: 0 or 1")
+        rows = int(g.shape[0]) if hasattr(g, "shape") and len(g.shape) == 2 else 0
+        self._dev_f32(g, "g", (rows, 2048))
+        tab, nseq = self._q_seqs(seqs)
+        h = torch.zeros((rows, 512), dtype=torch.float32, device=self.device)
+        c = torch.zeros((rows, 512), dtype=torch.float32, device=self.device)
+        hcodes = torch.zeros((rows, 512), dtype=torch.uint8, device=self.device)
+        hparams = torch.zeros((rows, 2, 2), dtype=torch.float32, device=self.device)
+        self._check(self._lib.bbocr_op_qlstm(self._h, C.c_void_p(g.data_ptr()), rows, tab, nseq, int(layer), C.c_void_p(h.data_ptr()),
+                                             C.c_void_p(c.data_ptr()), C.c_void_p(hcodes.data_ptr()), C.c_void_p(hparams.data_ptr())))
+        return h, c, hcodes, hparams
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None

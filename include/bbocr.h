@@ -72,7 +72,15 @@ typedef struct bbocr_config {
                          * PROCESS may use: scheduler affinity mask and cgroup CPU quota -- not the machine's core count, which every one of
                          * the 8 ranks of a node would claim for itself).  Ranks that are not pinned pass their share (the Python host:
                          * share / LOCAL_WORLD_SIZE).  The pool is created once per slot and kept; no thread is spawned per call. */
-    int reserved[2];
+    int rec_quant;      /* 0 (default): the recogniser as `precision` says.  1: its SEQUENCE half -- both BiLSTMs, the two Linear layers behind them
+                         * and Prediction -- in the arithmetic easyocr's quantize=True default runs on a CPU device: torch's x86 / fbgemm DYNAMIC
+                         * int8 quantisation (symmetric qint8 weights per tensor, 7-bit activation codes whose scale and zero point are taken per
+                         * crop and, for the recurrent product, per direction and time step; int32 accumulation on v_mfma_i32_16x16x64_i8), every
+                         * crop on its own as readtext(batch_size=1) runs it.  The conv stack, the 3-row mean and CTC are unchanged.  Allowed with
+                         * BBOCR_PREC_EXACT and BBOCR_PREC_EXACT_REC only (what is quantised are the fp32 path's features, which those modes deliver
+                         * to 1e-5); any other precision or value: bbocr_create returns BBOCR_ERR_ARG.  The weight blob carries the flag: a blob of
+                         * the other kind is refused (BBOCR_ERR_WEIGHTS).  DESIGN.md section 4 states the arithmetic. */
+    int reserved[1];
 } bbocr_config;
 enum { BBOCR_PREC_BF16 = 0, BBOCR_PREC_FP16 = 1, BBOCR_PREC_EXACT = 2, BBOCR_PREC_MIXED = 3, BBOCR_PREC_EXACT_REC = 4 };
 
@@ -286,6 +294,20 @@ int bbocr_op_conv2d(bbocr_ctx* ctx, const uint16_t* dev_in, int N, int H, int W,
  * normalised to [-1, 1]; BBOCR_PREC_EXACT: CODES, 0 = padding zero, 1 + grey level otherwise, from which the first layer rebuilds the
  * fp32 input ((g/255 - 0.5)/0.5) exactly) -> logits fp32 [n,T,112] (device), T = imgW/4-1 */
 int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW, float* dev_logits);
+/* rec_quant contexts only: ONE dynamically quantised matrix product of the sequence half.  dev_x fp32 [rows, K] (device), seqs (host): nseq
+ * pairs {first row, T} that tile [0, rows) in order -- one set of activation parameters per pair (crop).  layer: 0 / 1 = the input
+ * projection of BiLSTM 0 / 1 (K 256 -> N 2048: column dir * 1024 + gate * 256 + unit, bias b_ih), 2 / 3 = the Linear behind BiLSTM 0 / 1
+ * (512 -> 256), 4 = Prediction (256 -> 112: 97 classes, the rest 0).  Outputs: dev_out fp32 [rows, N], dev_codes uint8 [rows, K] (the 7-bit
+ * codes, device), seg_params (host) [nseq][2] = {scale, zero point}. */
+int bbocr_op_qlinear(bbocr_ctx* ctx, const float* dev_x, int rows, const int* seqs, int nseq, int layer, float* dev_out, uint8_t* dev_codes,
+                     float* seg_params);
+/* rec_quant contexts only: the recurrence of BiLSTM `layer` (0 / 1), both directions.  dev_g fp32 [rows, 2048]: the input projection as
+ * bbocr_op_qlinear writes it; seqs as there (sequences of any mix of lengths; 16 share a workgroup).  Outputs (device, row = first row + t):
+ * dev_h, dev_c fp32 [rows, 512] (forward | backward) = h and c AFTER step t; dev_hcodes uint8 [rows, 512] and dev_hparams fp32 [rows][2][2] =
+ * the codes and {scale, zero point} of the h that ENTERED step t of each direction (h of t - 1 forward, of t + 1 backward, zeros at a
+ * direction's first step). */
+int bbocr_op_qlstm(bbocr_ctx* ctx, const float* dev_g, int rows, const int* seqs, int nseq, int layer, float* dev_h, float* dev_c, uint8_t* dev_hcodes,
+                   float* dev_hparams);
 /* CTC decode of logits fp32 [n,T,cs]: host outputs text_off [n+1], text_idx (<= n*T), conf [n]; ignore_mask: 4 x 32-bit class mask
  * (bbocr_params::ignore_mask) or NULL; beam_width <= 0: greedy, > 0: ctcBeamSearch with that width (bbocr_params::decoder) */
 int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, int cs, int* text_off, int* text_idx, double* conf,
