@@ -358,6 +358,7 @@ struct RecEarly {
 };
 
 constexpr int REC_GAP = 4;
+constexpr int REC_STAGES = 8;        // stages of the recogniser's conv stack (crnn_features_stages)
 
 // ------------------------------------------------------------------------------------------------ shared functions
 template <typename T> inline T* upload(bbocr_ctx* c, const std::vector<T>& v) {
@@ -408,6 +409,8 @@ void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int>& sel,
 const CropDesc* rec_upload_descs(bbocr_ctx* c, const RecPart& part, DevBuf& desc_buf);
 uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part);
 void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide);
+Act crnn_stage_shape(const bbocr_ctx* c, const RecPart& part, int stage);
+Act crnn_features_stages(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, Act a, int first, int last);
 void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
 void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_dev, int ntiles, const int* seqs_dev, int nseq, float* logits);
 void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);     // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}

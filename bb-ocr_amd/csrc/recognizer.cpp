@@ -66,29 +66,58 @@ static inline int rec_mul(const bbocr_ctx* c) { return rec_split(c) ? 2 : 1; }
 // 4 zero columns between neighbours (CropDesc::slot = first column), so each layer is ONE launch over [H, Wt] whatever the mix of width
 // buckets.  The separator columns are each layer's zero padding; convolutions write into them, so they are cleared on every layer output
 // (4 >> shift columns per crop).  The 3-row mean is gathered straight into every crop's pooled rows of c->seq_v (CropDesc::pad_).
+// The stack is REC_STAGES stages, a stage = a layer with the gap clear that follows it:
+//   0 conv0 + ReLU + pool | 1 r1 + pool | 2 r2 | 3 r3 + (2,1) pool | 4 r4 | 5 r5 + (2,1) pool | 6 r6 | 7 3-row mean + gather
+// crnn_stage_shape: the wide tensor stage `stage` reads (p = null); stage == REC_STAGES: what the last one leaves, the part's rows of seq_v.
+Act crnn_stage_shape(const bbocr_ctx* c, const RecPart& part, int stage) {
+    static const int H[REC_STAGES] = {64, 32, 16, 16, 8, 8, 4, 3}, C[REC_STAGES] = {1, 32, 64, 128, 128, 256, 256, 256};
+    const int m = rec_mul(c), Wt = (int)part.cols;
+    if (stage < 0 || stage > REC_STAGES) fail(BBOCR_ERR_INTERNAL, "recogniser conv stack: no such stage");
+    if (stage == REC_STAGES) return Act{nullptr, 1, 1, (int)part.rows, 256 * m};
+    const int W = stage == 0 ? Wt : (stage == 1 ? Wt / 2 : (stage == 7 ? Wt / 4 - 1 : Wt / 4));
+    return Act{nullptr, 1, H[stage], W, stage == 0 ? 1 : C[stage] * m};
+}
+
+// Stages first..last on `a`, the input of stage `first` in the wide layout (crnn_stage_shape; its gap columns zero).  Returns the output of
+// stage `last`: an arena tensor, or after stage 7 c->seq_v (whose rows CropDesc::pad_ + t were written).  A recognition pass runs 0..7
+// (crnn_features_wide), the per-stage tests (tools/micro/stage_shim.hip) any range.
 // descs: the part's descriptors on the device.  In a dry arena pass nothing is launched.
-void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide) {
+Act crnn_features_stages(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, Act a, int first, int last) {
     Arena& ar = c->arena;
     c->prof_group = 1;
-    const int m = rec_mul(c), Wt = (int)part.cols, count = (int)part.descs.size();
-    Act c0{ar.alloc<uint16_t>((size_t)32 * (Wt / 2) * 32 * m), 1, 32, Wt / 2, 32 * m};
-    if (!ar.dry) HIPCHK(launch_crnn_conv0(wide, c->r0_wb, c->r0_wb + 288, c0.p, 1, Wt, rec_mode(c), c->cur, c->r0_afrag));
-    auto gaps = [&](const Act& a, int shift) {
-        if (!ar.dry) HIPCHK(launch_crnn_zero_gaps(a.p, descs, 0, count, a.H, a.W, a.C, shift, c->cur));
+    const int m = rec_mul(c), count = (int)part.descs.size();
+    if (first < 0 || last >= REC_STAGES || first > last) fail(BBOCR_ERR_INTERNAL, "recogniser conv stack: bad stage range");
+    auto gaps = [&](const Act& t, int shift) {
+        if (!ar.dry) HIPCHK(launch_crnn_zero_gaps(t.p, descs, 0, count, t.H, t.W, t.C, shift, c->cur));
     };
-    gaps(c0, 1);
-    Act q1 = conv_pool_act(c, c->r1, c0, false, true, 64, 1, false, nullptr);
-    gaps(q1, 2);
-    Act c2 = conv_act(c, c->r2, q1, false, nullptr, false, true, 128);
-    gaps(c2, 2);
-    Act q2 = conv_pool_act(c, c->r3, c2, false, true, 128, 2, false, nullptr);
-    gaps(q2, 2);
-    Act c4 = conv_act(c, c->r4, q2, false, nullptr, false, true, 256);
-    gaps(c4, 2);
-    Act q3 = conv_pool_act(c, c->r5, c4, false, true, 256, 2, false, nullptr);
-    gaps(q3, 2);
-    Act c6 = conv_act(c, c->r6, q3, false, nullptr, false, true, 256);   // [1, 3, Wt/4 - 1, 256]
-    if (!ar.dry) HIPCHK(launch_rowmean3_gather(c6.p, c6.W, 256, descs, 0, count, (uint16_t*)c->seq_v.p, rec_mode(c), c->cur));
+    for (int s = first; s <= last; ++s) {
+        const Act want = crnn_stage_shape(c, part, s);
+        if (a.N != want.N || a.H != want.H || a.W != want.W || a.C != want.C) fail(BBOCR_ERR_INTERNAL, "recogniser conv stack: stage input of another shape");
+        switch (s) {
+        case 0: {
+            const int Wt = a.W;
+            Act c0{ar.alloc<uint16_t>((size_t)32 * (Wt / 2) * 32 * m), 1, 32, Wt / 2, 32 * m};
+            if (!ar.dry) HIPCHK(launch_crnn_conv0(a.p, c->r0_wb, c->r0_wb + 288, c0.p, 1, Wt, rec_mode(c), c->cur, c->r0_afrag));
+            gaps(c0, 1);
+            a = c0;
+            break;
+        }
+        case 1: a = conv_pool_act(c, c->r1, a, false, true, 64, 1, false, nullptr); gaps(a, 2); break;
+        case 2: a = conv_act(c, c->r2, a, false, nullptr, false, true, 128); gaps(a, 2); break;
+        case 3: a = conv_pool_act(c, c->r3, a, false, true, 128, 2, false, nullptr); gaps(a, 2); break;
+        case 4: a = conv_act(c, c->r4, a, false, nullptr, false, true, 256); gaps(a, 2); break;
+        case 5: a = conv_pool_act(c, c->r5, a, false, true, 256, 2, false, nullptr); gaps(a, 2); break;
+        case 6: a = conv_act(c, c->r6, a, false, nullptr, false, true, 256); break;   // [1, 3, Wt/4 - 1, 256]
+        default:
+            if (!ar.dry) HIPCHK(launch_rowmean3_gather(a.p, a.W, 256, descs, 0, count, (uint16_t*)c->seq_v.p, rec_mode(c), c->cur));
+            a = Act{(uint16_t*)c->seq_v.p, 1, 1, (int)part.rows, 256 * m};
+        }
+    }
+    return a;
+}
+
+void crnn_features_wide(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, const uint16_t* wide) {
+    (void)crnn_features_stages(c, part, descs, Act{(uint16_t*)wide, 1, 64, (int)part.cols, 1}, 0, REC_STAGES - 1);
 }
 
 // Sequence half of the recogniser over the POOLED time steps of every bucket (rows = sum n_i*T_i, padded to x256):

@@ -1,4 +1,4 @@
-"""-m gpu: every fused launch of the fast-mode detector, pool5 and the BiLSTM recurrence, ONE stage at a time with the production plans and
+"""-m gpu: every fused launch of the fast-mode detector, pool5, the BiLSTM recurrence and the recogniser's conv stack, ONE stage at a time with the production plans and
 packed side tables of a live context (tools/micro/stage_shim.hip), against the fp64 reference of its own operation (tests/stage_ref.py) under
 the tolerance rule stated there.  An L2 norm over a heat-map cannot see an error confined to a page border, a tile seam, the first pixel of the
 second page of a batch or one time step of 79; these checks are per element, and a failure names the element and the region it lies in.
@@ -50,14 +50,15 @@ class Stage:
     def __init__(self, so, states, el):
         import bb_ocr_amd
 
-        self.el, self.dtype = el, R.DTYPES[el]
+        self.el, self.dtype = el, R.DTYPES["fp16" if el == "exact" else el]     # exact: split fp16, stored values are [hi | lo] fp16 pairs
         self.reader = bb_ocr_amd.Reader(["en"], gpu=True, weights=states, precision=el)      # loads libbbocr.so (after torch's HIP runtime)
         self.lib = C.CDLL(so)
         self.lib.stage_shim_error.restype = C.c_char_p
-        self.W = R.Weights(states[0], el)
+        self.W = R.Weights(states[0], "f32" if el == "exact" else el)
+        self.RW = R.Weights(states[1], "f32" if el == "exact" else el)            # the recogniser's conv stack
         self.crnn = states[1]
         self.h = self.reader._h
-        assert self.lib.stage_shim_det_el(self.h) == self.lib.stage_shim_rec_el(self.h) == (1 if el == "fp16" else 0)
+        assert self.lib.stage_shim_det_el(self.h) == self.lib.stage_shim_rec_el(self.h) == (0 if el == "bf16" else 1)
 
     def call(self, fn, *args):
         """tensors go as (pointer, element count); synchronises torch's stream first (the library runs on its own non-blocking one)"""
@@ -87,6 +88,13 @@ class Stage:
 @pytest.fixture(scope="module", params=["bf16", "fp16"])
 def st(request, shim_path, stage_states):
     s = Stage(shim_path, stage_states, request.param)
+    yield s
+    s.reader.close()
+
+
+@pytest.fixture(scope="module")
+def st_exact(shim_path, stage_states):
+    s = Stage(shim_path, stage_states, "exact")       # the precision of conftest's reader_exact
     yield s
     s.reader.close()
 
@@ -291,3 +299,160 @@ def test_bilstm_mixed_tiles(st, layer, sigma):
                 s, t, d, _u = [int(v[0]) for v in torch.nonzero(m, as_tuple=True)]
                 where.append(f"tile {k} ({n} x T={T}, first row {r0}): {int(m.sum())} beyond tight, first at sequence {s}, t {t}, {'bwd' if d else 'fwd'}")
         raise AssertionError(str(e) + "; " + "; ".join(where)) from None
+
+
+# ------------------------------------------------------------------------------------------------ recogniser conv stack over the wide image
+REC_PARTS = {"A": R.REC_PART_A, "B": R.REC_PART_B}
+REC_ALONE = [1, 6, 0, 19]       # part A's crops also run as parts of their own: the first 64 (box 1), a 128 (box 6), the 320 (box 0), the last 64 (box 19)
+SPLIT_LO_SCALE = 2048.0
+
+
+class RecPlan:
+    """rec_plan_part's layout of `widths` (box order), from production: slot / row0 per BOX, the plan's order, the totals"""
+
+    def __init__(self, st, widths):
+        n = len(widths)
+        arr = lambda: (C.c_int * n)()
+        self.widths, self.cw = list(widths), (C.c_int * n)(*widths)
+        slot, row0, order, cols, rows = arr(), arr(), arr(), C.c_int(), C.c_int()
+        rc = st.lib.stage_rec_plan(self.cw, n, slot, row0, order, C.byref(cols), C.byref(rows))
+        assert rc == 0, f"stage_rec_plan: status {rc} {st.lib.stage_shim_error().decode()}"
+        self.order, self.cols, self.rows = list(order), cols.value, rows.value
+        assert sorted(self.order) == list(range(n))
+        self.slot, self.row0 = [0] * n, [0] * n
+        for k, i in enumerate(self.order):
+            self.slot[i], self.row0[i] = slot[k], row0[k]
+
+    def gap_columns(self, s):
+        """the separator columns at a horizontal down-scale of 2^s"""
+        m = torch.zeros(self.cols >> s, dtype=torch.bool)
+        for sl, w in zip(self.slot, self.widths):
+            m[(sl + w) >> s:(sl + w + R.REC_GAP) >> s] = True
+        return m
+
+
+def _rec_run(st, plan, first, last, wide_in, extra_rows=8):
+    """stages first..last on the device -> (output tensor on the host after two agreeing runs, its per-stage shape).  After stage 7 the
+    output has extra_rows NaN rows behind the part's."""
+    m = 2 if st.el == "exact" else 1
+    if last == 7:
+        shape = (plan.rows + extra_rows, 256 * m)
+    else:
+        H, s, Cc = R.REC_IN[last + 1]
+        shape = (H, (plan.cols >> s) - (1 if last == 6 else 0), Cc * m)
+    d = wide_in.contiguous().cuda()
+
+    def run():
+        o = st.out(shape)
+        st.call("stage_rec_features", plan.cw, len(plan.widths), first, last, d, o)
+        return o
+
+    return st.twice(run)
+
+
+def _rec_crops(plan, last, out):
+    """per-box views of a stage output: the crop's columns (last < 7) / rows (last = 7)"""
+    if last == 7:
+        return [out[r:r + w // 4 - 1] for r, w in zip(plan.row0, plan.widths)]
+    s = R.REC_IN[last + 1][1]
+    return [out[:, sl >> s:(sl >> s) + R.rec_in_shape(last + 1, w)[1]] for sl, w in zip(plan.slot, plan.widths)]
+
+
+def _rec_structure(st, plan, first, last, out, wide_of, name):
+    """checks 2, 3 and 4: separators +0 bit for bit, the gather's rows, every REC_ALONE crop alone = the same crop inside the part"""
+    bits = out.view(torch.int16)
+    if last <= 5:
+        gap = plan.gap_columns(R.REC_IN[last + 1][1])
+        dirty = (bits[:, gap] != 0).any(dim=2).any(dim=0)
+        cols = torch.nonzero(gap).flatten()[dirty].tolist()
+        assert not cols, f"{name}: separator columns {cols[:8]} of stage {last}'s output are not +0 (crop edges at {sorted(plan.slot)[:4]}...)"
+    if last == 7:
+        assert torch.isnan(out[plan.rows:].float()).all(), f"{name}: rows behind the part's {plan.rows} were written"
+        assert not torch.isnan(out[:plan.rows].float()).any(), f"{name}: some of the part's {plan.rows} rows were not written"
+    if len(plan.widths) > 1:
+        inside = _rec_crops(plan, last, bits)
+        for i in REC_ALONE:
+            solo = RecPlan(st, [plan.widths[i]])
+            got = _rec_crops(solo, last, _rec_run(st, solo, first, last, wide_of(solo, [i])).view(torch.int16))[0]
+            diff = got != inside[i]
+            assert not diff.any(), f"{name}: crop {i} (bucket {plan.widths[i]}) run as a part of its own differs from the same crop inside the part in " \
+                f"{int(diff.sum())} values; " + R.rec_where(diff.reshape(-1), [plan.widths[i]], [tuple(diff.shape) if diff.dim() == 3 else (1,) + tuple(diff.shape)], [i])
+
+
+@pytest.mark.parametrize("part", ["A", "B"])
+@pytest.mark.parametrize("rng", R.REC_RANGES, ids=lambda r: f"{r[0]}-{r[1]}")
+def test_rec_features_stages(st, rng, part):
+    """Stages first..last of crnn_features_stages over a part of mixed width buckets against each crop's OWN fp64 reference (a crop alone with
+    ordinary zero padding: tests/stage_ref.py never sees the wide layout), per element; separators, gather rows and crop independence bit for
+    bit.  Single stages have E = 0 and carry the numerical weight; the pairs (k, k + 1) are where a clear left out after stage k would show in
+    values; the chain 0..7 has an allowance seven |W| maps deep that decides nothing (E ~ 4e6 for bf16) and, as torch-fp32 itself misses the 1e-3 cap
+    behind seven roundings, a cap of twice torch-fp32's own share on the same part (R.rec_chain_cap); there the placement -- rows, T, crop
+    order -- is also checked without a tolerance (R.rec_misplaced)."""
+    first, last = rng
+    widths = REC_PARTS[part]
+    plan = RecPlan(st, widths)
+    assert (plan.slot, plan.row0) == tuple([v[plan.order.index(i)] for i in range(len(widths))] for v in R.rec_plan_like(widths)[:2])
+    assert (plan.order, plan.cols, plan.rows) == R.rec_plan_like(widths)[2:] and plan.cols == {"A": 1744, "B": 68}[part]
+    xs = R.rec_inputs(widths, first, st.el, plan.order)
+    wide_of = lambda pl, boxes: R.rec_wide_pack(pl.slot, pl.cols, [xs[i] for i in boxes], first, torch.float64)[0].to(st.dtype)
+    name = f"rec {first}..{last} {st.el} part {part}"
+    out = _rec_run(st, plan, first, last, wide_of(plan, range(len(widths))))
+    _rec_structure(st, plan, first, last, out, wide_of, name)
+    got = [g[None] if last < 7 else g[None, None] for g in _rec_crops(plan, last, out)]
+    refs = [R.refs_rec(st.RW, x, first, last, st.el) for x in xs]
+    rq, rn = R.rec_flat([r[0] for r in refs]), R.rec_flat([r[1] for r in refs])
+    E = 0.0 if first == last else R.rec_flat([r[2] for r in refs])
+    g64 = R.rec_flat(got)
+    cap = 1e-3
+    if rng == (0, 7):
+        cap, standin = R.rec_chain_cap(st.RW, widths, xs, rq, st.el)
+        print(f"[stage] {name}: torch-fp32's own share beyond tight {standin:.3g}, cap {cap:.3g}")
+    try:
+        _check(st, f"rec {first}..{last}", f"part {part}", g64, (rq, rn, E), st.el, index_names=("element of the part",), cap=cap)
+    except AssertionError as e:
+        tight, allow = R.bounds(rq, rn, E, st.el)
+        shapes = [tuple(r[0].shape[1:]) for r in refs]
+        miss_a, miss_t = ~((g64 - rn).abs() <= allow), ~((g64 - rq).abs() <= tight)
+        raise AssertionError(f"{e}; beyond the allowance: {R.rec_where(miss_a, widths, shapes) or 'none'}; beyond the tight bound: "
+                             f"{R.rec_where(miss_t, widths, shapes) or 'none'}") from None
+    if rng == (0, 7):
+        bad = R.rec_misplaced(got, [r[0] for r in refs], widths)
+        assert not bad, f"{name}: " + "; ".join(bad)
+
+
+def _pair_value(t, Cc):
+    """[.., 2 Cc] fp16 pairs [hi | lo] -> fp64 values hi + lo / SPLIT_LO_SCALE"""
+    return t[..., :Cc].double() + t[..., Cc:].double() / SPLIT_LO_SCALE
+
+
+@pytest.mark.parametrize("part", ["A", "B"])
+def test_rec_features_exact(st_exact, part):
+    """Exact mode (split fp16: crnn_conv0_kernel<REC_SPLIT> on the codes 1 + grey, [hi | lo] pairs, the split 3-row mean): separators after
+    stages 0..5, gather rows and crop independence bit for bit, and the chain 0..7 against the fp64 network on the fp32-normalised pixels:
+    relative L2 <= 2e-5 per crop (the mode's bound in test_crnn_logits_fp16_and_exact) and per time step -- unless torch-fp32, which this mode
+    promises to follow, is itself beyond 1e-5 on some step, then twice its worst step (on these inputs it is about 3e-7: the bound is 2e-5)."""
+    st = st_exact
+    widths = REC_PARTS[part]
+    plan = RecPlan(st, widths)
+    px = R.rec_pixels(widths, R.REC_SEED, plan.order)
+    codes = [(g.to(torch.int16) + 1)[None, :, :, None] for g in px]
+    wide_of = lambda pl, boxes: R.rec_wide_pack(pl.slot, pl.cols, [codes[i] for i in boxes], 0, torch.int16)[0]
+    for last in range(8):
+        name = f"rec 0..{last} exact part {part}"
+        out = _rec_run(st, plan, 0, last, wide_of(plan, range(len(widths))))
+        _rec_structure(st, plan, 0, last, out, wide_of, name)
+    worst32 = worst_crop = worst_step = 0.0
+    for i, (g, rows) in enumerate(zip(px, _rec_crops(plan, 7, out))):
+        x = R.rec_normalise(g, "f32")
+        ref = R.rec_chain(st.RW, x, 0, 7, None, q=False)[0, 0]
+        r32 = R.rec_chain(st.RW, x, 0, 7, None, q=False, dt=torch.float32)[0, 0].double()
+        got = _pair_value(rows, 256)
+        worst32 = max(worst32, float(((r32 - ref).norm(dim=1) / ref.norm(dim=1)).max()))
+        crop, step = float((got - ref).norm() / ref.norm()), (got - ref).norm(dim=1) / ref.norm(dim=1)
+        worst_crop, worst_step = max(worst_crop, crop), max(worst_step, float(step.max()))
+        print(f"[stage] rec exact part {part} crop {i} (bucket {widths[i]}): relative L2 {crop:.3g}, worst time step {float(step.max()):.3g} at t = {int(step.argmax())}")
+    bound = 2e-5 if worst32 <= 1e-5 else 2.0 * worst32
+    print(f"[stage] rec exact part {part}: worst crop {worst_crop:.3g}, worst time step {worst_step:.3g}; torch-fp32's worst time step {worst32:.3g}, bound {bound:.3g}")
+    _record("rec 0..7", "exact", f"part {part}", {"worst_crop": worst_crop, "worst_step": worst_step, "fp32_worst_step": worst32, "step_bound": bound})
+    assert worst_crop <= 2e-5, f"{name}: a crop's relative L2 {worst_crop:.3g} > 2e-5"
+    assert worst_step <= bound, f"{name}: a time step's relative L2 {worst_step:.3g} > {bound:.3g}"

@@ -1,5 +1,6 @@
 // Test-only shim (tests/test_gpu_stages.py): runs ONE stage of the fast-mode detector / recogniser with the production plans and packed side
 // tables of a live context, so that each fused launch can be compared with an fp64 reference of its own operation (tests/stage_ref.py).
+// stage_rec_features runs any range of the stages of the recogniser's conv stack (crnn_features_stages, the function a recognition pass runs).
 // No kernels of its own.  Built by the test as a shared object against the in-tree library:
 //   hipcc -O2 -std=c++20 -shared -fPIC --offload-arch=gfx950 -Ibb-ocr_amd/csrc -Iinclude tools/micro/stage_shim.hip -Lbb-ocr_amd -lbbocr -o stage_shim.so
 // Every function takes the bbocr_ctx* of a Reader, device pointers of caller-owned tensors with their element counts (checked against the
@@ -58,6 +59,40 @@ template <typename F> hipError_t with_arena(bbocr_ctx* c, uint16_t* out, size_t 
     if ((size_t)o.N * o.H * o.W * o.C != out_elems) fail(BBOCR_ERR_INTERNAL, "stage shim: output size differs from the caller's tensor");
     return hipMemcpyAsync(out, o.p, out_elems * 2, hipMemcpyDeviceToDevice, c->stream);
 }
+
+// the n crops of the given padded widths planned as one part, as bbocr_crnn_logits and a recognition pass plan theirs
+bool rec_widths_ok(const int* widths, int n) {
+    if (!widths || n <= 0 || n > 4096) return false;
+    long long cols = 0;
+    for (int i = 0; i < n; ++i) {
+        if (widths[i] < 64 || (widths[i] & 63) || widths[i] > 2560) return false;
+        cols += widths[i] + REC_GAP;
+    }
+    return cols < (1LL << 20);
+}
+void rec_part_of(const int* widths, int n, RecPart& part) {
+    std::vector<BoxJob> jobs(n);
+    std::vector<int> all(n);
+    for (int i = 0; i < n; ++i) { jobs[i].d = CropDesc{}; jobs[i].d.imgW = widths[i]; all[i] = i; }
+    rec_plan_part(jobs, all, 0, 0, part);
+}
+// host only; 0 or the shim's status of what rec_plan_part threw (nothing crosses the extern "C" boundary)
+int plan_part(const int* widths, int n, RecPart& part) {
+    try {
+        rec_part_of(widths, n, part);
+        return 0;
+    } catch (const StatusError& se) {
+        g_err = se.msg;
+        return SHIM_STATUS + std::abs(se.code);
+    } catch (const std::exception& ex) {
+        g_err = ex.what();
+        return SHIM_UNKNOWN;
+    } catch (...) {
+        g_err = "unknown failure";
+        return SHIM_UNKNOWN;
+    }
+}
+size_t act_elems(const Act& a) { return (size_t)a.N * a.H * a.W * a.C; }
 }  // namespace
 
 extern "C" {
@@ -171,6 +206,51 @@ int stage_lstm(bbocr_ctx* c, int layer, const uint16_t* xproj, uint16_t* out, si
         const hipError_t s = hipStreamSynchronize(c->stream);
         (void)hipFree(tiles_dev);
         return e != hipSuccess ? e : s;
+    });
+}
+
+// rec_plan_part on n crops of the given padded widths (host only).  Per descriptor k of the plan: its first column in the wide image, its
+// first pooled row, and the position in `widths` of the crop it stands for; cols / rows: the part's totals.
+int stage_rec_plan(const int* widths, int n, int* slot_out, int* row0_out, int* order_out, int* cols, int* rows) {
+    g_err.clear();
+    NEED(rec_widths_ok(widths, n) && slot_out && row0_out && order_out && cols && rows);
+    RecPart part;
+    if (const int rc = plan_part(widths, n, part)) return rc;
+    NEED((int)part.descs.size() == n && (int)part.order.size() == n);
+    for (int k = 0; k < n; ++k) {
+        slot_out[k] = part.descs[k].slot;
+        row0_out[k] = part.descs[k].pad_;
+        order_out[k] = part.order[k];
+    }
+    *cols = (int)part.cols;
+    *rows = (int)part.rows;
+    return 0;
+}
+
+// Stages first..last of the recogniser's conv stack (crnn_features_stages) over the part planned from `widths`: `in` is the input of stage
+// `first` in the wide layout (crnn_stage_shape; stage 0: [64][cols] element-type pixels, exact mode: codes 1 + grey; gap columns zero),
+// `out` receives the output of stage `last`.  After stage 7 that is seq_v: `out` is [R][256 * m] with R >= the part's rows, its content goes
+// into seq_v first and all R rows come back, so rows the gather did not write keep what the caller put there.
+int stage_rec_features(bbocr_ctx* c, const int* widths, int n, int first, int last, const uint16_t* in, size_t in_elems, uint16_t* out, size_t out_elems) {
+    g_err.clear();
+    NEED(c && c->crnn_loaded && in && out && rec_widths_ok(widths, n) && first >= 0 && first <= last && last < REC_STAGES);
+    RecPart part;
+    if (const int rc = plan_part(widths, n, part)) return rc;
+    const bool to_seq = last == REC_STAGES - 1;
+    const Act ia = crnn_stage_shape(c, part, first), oa = crnn_stage_shape(c, part, last + 1);
+    NEED(in_elems == act_elems(ia));
+    NEED(to_seq ? (out_elems >= act_elems(oa) && out_elems % (size_t)oa.C == 0 && out_elems < ((size_t)1 << 28)) : out_elems == act_elems(oa));
+    return run_stage(c, [&] {
+        const CropDesc* dd = rec_upload_descs(c, part, c->crop_desc);
+        if (to_seq) {
+            c->seq_v.ensure(align_up(out_elems / (size_t)oa.C, 256) * (size_t)oa.C * 2);
+            HIPCHK(hipMemcpyAsync(c->seq_v.p, out, out_elems * 2, hipMemcpyDeviceToDevice, c->stream));
+        }
+        Act a = ia;
+        a.p = (uint16_t*)in;
+        const Act o = in_arena(c, [&] { return crnn_features_stages(c, part, dd, a, first, last); });
+        if (!to_seq && act_elems(o) != out_elems) fail(BBOCR_ERR_INTERNAL, "stage shim: output size differs from the caller's tensor");
+        return hipMemcpyAsync(out, o.p, out_elems * 2, hipMemcpyDeviceToDevice, c->stream);
     });
 }
 
