@@ -389,6 +389,25 @@ void craft_up_stage(bbocr_ctx* c, const ConvPlan& py, const ConvPlan& ps, const 
 bool craft_up3b_post(bbocr_ctx* c, const Act& u3a, uint16_t* u3b, uint16_t* z);      // true: the one fused launch ran; false: the two launches
 bool craft_up4(bbocr_ctx* c, const Act& s1, const uint16_t* z, uint16_t* u4b);       // likewise
 void craft_cls_tail(bbocr_ctx* c, const Act& c2, float* heat);
+// The exact-mode detector (craft_forward_exact): its stage functions and the table of its conv launches, in the pass's order.  Every Act is a
+// pair tensor [hi | lo] whose C counts both halves.
+struct ExactConvRow {
+    const char* name;
+    ConvPlan bbocr_ctx::* plan;
+    bool relu_out;
+    int store;             // logical channels stored
+    int pool_mode;         // 0: none, 1: MaxPool2d(2, 2) in the epilogue
+    bool pool_relu;        // ReLU on the pooled values (the full tensor stays as relu_out says)
+    bool keep_full;        // the un-pooled tensor is written too (a U-net skip)
+};
+int craft_exact_rows();
+const ExactConvRow& craft_exact_row(int row);
+Act craft_exact_conv(bbocr_ctx* c, int row, const Act& in, Act* full = nullptr);
+Act craft_exact_conv1_1(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, int Wimg, int H32, int W32);
+Act craft_exact_relu(bbocr_ctx* c, const Act& a);
+Act craft_exact_upcat(bbocr_ctx* c, const Act& y, const Act& skip);
+Act craft_exact_pool5(bbocr_ctx* c, const Act& s4);
+void craft_exact_cls_tail(bbocr_ctx* c, const Act& c3, float* heat);
 DetDims det_dims(int H, int W, int canvas, double mag);
 void detect_impl(bbocr_ctx* c, const uint8_t* rgb, int B, int H, int W, const bbocr_params& p, float* heat, const std::function<void(int, int)>& after_sub = nullptr);
 DetPlan det_plan(bbocr_ctx* c, int B, int H, int W, const bbocr_params& p, bool overlapped);      // detect_impl's three steps
@@ -413,7 +432,10 @@ Act crnn_stage_shape(const bbocr_ctx* c, const RecPart& part, int stage);
 Act crnn_features_stages(bbocr_ctx* c, const RecPart& part, const CropDesc* descs, Act a, int first, int last);
 void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
 void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_dev, int ntiles, const int* seqs_dev, int nseq, float* logits);
-void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);     // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}
+void crnn_seq_xproj(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp);         // crnn_sequence's three GEMMs
+void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint16_t* out);
+void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logits);
+void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);    // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}
 enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2 };   // where the text of a CTC pass comes from (ctc_route)
 int ctc_route(int beam_width, int C, const int* seqs, int nseq);   // seqs: {first row, T} per sequence (host)
 void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route);

@@ -215,45 +215,111 @@ static void craft_forward(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, in
 // element-wise passes on the pair values (craft_pair.hip), the U-net 1x1s over the materialised concat, the classifier tail in fp32.
 // 3x the MFMA work of the fp16 pass plus the un-fused intermediates: the price of threshold decisions that follow the fp32 CPU path's
 // on ANY heat-map, not only on maps with margins.
+// The pass is the stage functions below plus ONE table of its conv launches in the order it runs them; craft_forward_exact takes its
+// launches from that table row by row, and the per-stage tests (tools/micro/stage_shim.hip) run the same functions and the same rows.
+static Act pair_act(bbocr_ctx* c, int N, int H, int W, int C) { return arena_act(c, N, H, W, 2 * C); }      // Act::C counts both halves
+
+static const ExactConvRow kExactConvs[] = {
+    // name      plan                  relu_out store pool pool_relu keep_full
+    {"conv1_2", &bbocr_ctx::conv1_2, true, 64, 1, false, false},
+    {"conv2_1", &bbocr_ctx::conv2_1, true, 128, 0, false, false},
+    {"conv2_2", &bbocr_ctx::conv2_2, false, 128, 1, true, true},      // slice1 ends on BN (s1, kept); slice2 opens with ReLU + pool
+    {"conv3_1", &bbocr_ctx::conv3_1, true, 256, 0, false, false},
+    {"conv3_2", &bbocr_ctx::conv3_2, false, 256, 0, false, false},    // s2
+    {"conv3_3", &bbocr_ctx::conv3_3, true, 256, 1, false, false},
+    {"conv4_1", &bbocr_ctx::conv4_1, true, 512, 0, false, false},
+    {"conv4_2", &bbocr_ctx::conv4_2, false, 512, 0, false, false},    // s3
+    {"conv4_3", &bbocr_ctx::conv4_3, true, 512, 1, false, false},
+    {"conv5_1", &bbocr_ctx::conv5_1, true, 512, 0, false, false},
+    {"conv5_2", &bbocr_ctx::conv5_2, false, 512, 0, false, false},    // s4
+    {"fc6", &bbocr_ctx::fc6, false, 1024, 0, false, false},
+    {"fc7", &bbocr_ctx::fc7, false, 1024, 0, false, false},
+    {"up1a", &bbocr_ctx::up1a, true, 512, 0, false, false},
+    {"up1b", &bbocr_ctx::up1b, true, 256, 0, false, false},
+    {"up2a", &bbocr_ctx::up2s, true, 256, 0, false, false},           // over cat[up(y), skip]
+    {"up2b", &bbocr_ctx::up2b, true, 128, 0, false, false},
+    {"up3a", &bbocr_ctx::up3s, true, 128, 0, false, false},
+    {"up3b", &bbocr_ctx::up3b, true, 64, 0, false, false},
+    {"up4a", &bbocr_ctx::up4s, true, 64, 0, false, false},
+    {"up4b", &bbocr_ctx::up4b, true, 32, 0, false, false},
+    {"cls0", &bbocr_ctx::cls0, true, 32, 0, false, false},
+    {"cls2", &bbocr_ctx::cls2, true, 32, 0, false, false},
+    {"cls4", &bbocr_ctx::cls4, true, 16, 0, false, false},
+};
+int craft_exact_rows() { return (int)(sizeof(kExactConvs) / sizeof(kExactConvs[0])); }
+const ExactConvRow& craft_exact_row(int row) {
+    if (row < 0 || row >= craft_exact_rows()) fail(BBOCR_ERR_INTERNAL, "exact detector: no such conv row");
+    return kExactConvs[row];
+}
+
+// row `row` of the table on the pair tensor `in`: the (pooled, if the row pools) output; *full receives the un-pooled one of a row that keeps it
+Act craft_exact_conv(bbocr_ctx* c, int row, const Act& in, Act* full) {
+    const ExactConvRow& r = craft_exact_row(row);
+    const ConvPlan& p = c->*(r.plan);
+    if (r.keep_full != (full != nullptr)) fail(BBOCR_ERR_INTERNAL, "exact detector: a row keeps its full tensor exactly when the caller takes it");
+    if (!r.pool_mode) return conv_act(c, p, in, false, nullptr, false, r.relu_out, r.store);
+    return conv_pool_act(c, p, in, false, r.relu_out, r.store, r.pool_mode, r.pool_relu, full, nullptr);
+}
+
+// normalise + conv1_1 + BN + ReLU in fp32 from the uint8 pages on the zero canvas -> pair [nb, H32, W32, 64 | 64]
+Act craft_exact_conv1_1(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, int Wimg, int H32, int W32) {
+    Act o = pair_act(c, nb, H32, W32, 64);
+    if (!c->arena.dry) HIPCHK(launch_pair_conv1_1(rgb, nb, Himg, Wimg, H32, W32, c->c11_w32, c->c11_b, o.p, c->cur));
+    return o;
+}
+Act craft_exact_relu(bbocr_ctx* c, const Act& a) {
+    Act o = pair_act(c, a.N, a.H, a.W, a.C / 2);
+    if (!c->arena.dry) HIPCHK(launch_pair_relu(a.p, o.p, (size_t)a.N * a.H * a.W, a.C / 2, c->cur));
+    return o;
+}
+// torch.cat([F.interpolate(y, size of skip), skip], dim = 1)
+Act craft_exact_upcat(bbocr_ctx* c, const Act& y, const Act& skip) {
+    Act o = pair_act(c, skip.N, skip.H, skip.W, y.C / 2 + skip.C / 2);
+    if (!c->arena.dry) HIPCHK(launch_pair_upcat(y.p, y.H, y.W, y.C / 2, skip.p, skip.C / 2, o.p, skip.N, skip.H, skip.W, c->cur));
+    return o;
+}
+// slice5's MaxPool2d(3, 1, 1), no ReLU
+Act craft_exact_pool5(bbocr_ctx* c, const Act& s4) {
+    Act o = pair_act(c, s4.N, s4.H, s4.W, s4.C / 2);
+    if (!c->arena.dry) HIPCHK(launch_pair_maxpool3x3s1(s4.p, o.p, s4.N, s4.H, s4.W, s4.C / 2, c->cur));
+    return o;
+}
+// conv_cls.6 + ReLU + conv_cls.8 in fp32 on conv_cls.4's pair [.., 16 | 16] -> heat fp32 [.., 2]
+void craft_exact_cls_tail(bbocr_ctx* c, const Act& c3, float* heat) {
+    if (c3.C != 32) fail(BBOCR_ERR_INTERNAL, "exact detector: the classifier tail reads a 16-channel pair");
+    if (!c->arena.dry) HIPCHK(launch_pair_cls_tail(c3.p, c->cls6_w32, c->cls_tail, heat, (size_t)c3.N * c3.H * c3.W, c->cur));
+}
+
 static void craft_forward_exact(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, int Wimg, int H32, int W32, float* heat) {
-    Arena& ar = c->arena;
     c->prof_group = 0;
-    auto pair = [&](int N, int H, int W, int C) { return Act{ar.alloc<uint16_t>((size_t)N * H * W * C * 2), N, H, W, C * 2}; };   // Act::C counts both halves
-    auto relu = [&](const Act& a) {
-        Act o = pair(a.N, a.H, a.W, a.C / 2);
-        if (!ar.dry) HIPCHK(launch_pair_relu(a.p, o.p, (size_t)a.N * a.H * a.W, a.C / 2, c->cur));
-        return o;
-    };
-    auto upcat = [&](const Act& y, const Act& skip) {
-        Act o = pair(skip.N, skip.H, skip.W, y.C / 2 + skip.C / 2);
-        if (!ar.dry) HIPCHK(launch_pair_upcat(y.p, y.H, y.W, y.C / 2, skip.p, skip.C / 2, o.p, skip.N, skip.H, skip.W, c->cur));
-        return o;
-    };
-    auto conv = [&](const ConvPlan& p, const Act& a, bool relu_out, int store) { return conv_act(c, p, a, false, nullptr, false, relu_out, store); };
-    Act x0 = pair(nb, H32, W32, 64);
-    if (!ar.dry) HIPCHK(launch_pair_conv1_1(rgb, nb, Himg, Wimg, H32, W32, c->c11_w32, c->c11_b, x0.p, c->cur));
-    Act p1 = conv_pool_act(c, c->conv1_2, x0, false, true, 64, 1, false, nullptr);
-    Act a3 = conv(c->conv2_1, p1, true, 128);
+    int row = 0;                                                       // the table is consumed in its own order
+    auto conv = [&](const Act& a, Act* full = nullptr) { return craft_exact_conv(c, row++, a, full); };
+    Act x0 = craft_exact_conv1_1(c, rgb, nb, Himg, Wimg, H32, W32);
+    Act p1 = conv(x0);                                                 // conv1_2 + pool
+    Act a3 = conv(p1);                                                 // conv2_1
     Act s1;
-    Act p2 = conv_pool_act(c, c->conv2_2, a3, false, false, 128, 1, true, &s1);     // slice1 ends on BN (s1); slice2 opens with ReLU + pool
-    Act a5 = conv(c->conv3_1, p2, true, 256);
-    Act s2 = conv(c->conv3_2, a5, false, 256);
-    Act p3 = conv_pool_act(c, c->conv3_3, relu(s2), false, true, 256, 1, false, nullptr);
-    Act a8 = conv(c->conv4_1, p3, true, 512);
-    Act s3 = conv(c->conv4_2, a8, false, 512);
-    Act p4 = conv_pool_act(c, c->conv4_3, relu(s3), false, true, 512, 1, false, nullptr);
-    Act a11 = conv(c->conv5_1, p4, true, 512);
-    Act s4 = conv(c->conv5_2, a11, false, 512);
-    Act p5 = pair(s4.N, s4.H, s4.W, 512);
-    if (!ar.dry) HIPCHK(launch_pair_maxpool3x3s1(s4.p, p5.p, s4.N, s4.H, s4.W, 512, c->cur));
-    Act f6 = conv(c->fc6, p5, false, 1024);
-    Act f7 = conv(c->fc7, f6, false, 1024);
-    Act u1b = conv(c->up1b, conv(c->up1a, upcat(f7, s4), true, 512), true, 256);
-    Act u2b = conv(c->up2b, conv(c->up2s, upcat(u1b, s3), true, 256), true, 128);
-    Act u3b = conv(c->up3b, conv(c->up3s, upcat(u2b, s2), true, 128), true, 64);
-    Act u4b = conv(c->up4b, conv(c->up4s, upcat(u3b, s1), true, 64), true, 32);
-    Act c3 = conv(c->cls4, conv(c->cls2, conv(c->cls0, u4b, true, 32), true, 32), true, 16);
-    if (!ar.dry) HIPCHK(launch_pair_cls_tail(c3.p, c->cls6_w32, c->cls_tail, heat, (size_t)c3.N * c3.H * c3.W, c->cur));
+    Act p2 = conv(a3, &s1);                                            // conv2_2
+    Act a5 = conv(p2);                                                 // conv3_1
+    Act s2 = conv(a5);                                                 // conv3_2
+    Act p3 = conv(craft_exact_relu(c, s2));                            // conv3_3 + pool
+    Act a8 = conv(p3);                                                 // conv4_1
+    Act s3 = conv(a8);                                                 // conv4_2
+    Act p4 = conv(craft_exact_relu(c, s3));                            // conv4_3 + pool
+    Act a11 = conv(p4);                                                // conv5_1
+    Act s4 = conv(a11);                                                // conv5_2
+    Act f6 = conv(craft_exact_pool5(c, s4));                           // fc6
+    Act f7 = conv(f6);                                                 // fc7
+    Act u1a = conv(craft_exact_upcat(c, f7, s4));                      // up1a (same size: a plain concat)
+    Act u1b = conv(u1a);
+    Act u2a = conv(craft_exact_upcat(c, u1b, s3));
+    Act u2b = conv(u2a);
+    Act u3a = conv(craft_exact_upcat(c, u2b, s2));
+    Act u3b = conv(u3a);
+    Act u4a = conv(craft_exact_upcat(c, u3b, s1));
+    Act u4b = conv(u4a);
+    Act c3 = conv(conv(conv(u4b)));                                    // conv_cls.0, .2, .4
+    if (row != craft_exact_rows()) fail(BBOCR_ERR_INTERNAL, "exact detector: the pass and its conv table disagree");
+    craft_exact_cls_tail(c, c3, heat);
 }
 
 static void craft_forward_any(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, int Wimg, int H32, int W32, float* heat) {

@@ -167,7 +167,7 @@ hipError_t launch_rowmean3_gather(const uint16_t* in, int Wc, int C, const CropD
 // tiles hold up to lstm_tile_seqs(mode) sequences
 hipError_t launch_lstm(const void* xproj, const uint16_t* whh_pk, uint16_t* out, const int* tiles_dev, int ntiles, int mode, float acc_scale,
                        hipStream_t s);
-int lstm_tile_seqs(int mode);    // sequences per LSTM workgroup (tile table entries): 16, or 32 for REC_SPLIT
+int lstm_tile_seqs(int mode);    // sequences per LSTM workgroup (tile table entries): 16 in every mode as built (REC_SPLIT: 16 * LSTMX_NG, lstm.hip)
 size_t lstm_whh_packed_elems();
 void pack_lstm_whh8(const float* whh_fwd, const float* whh_bwd, uint16_t* out, int el);
 size_t lstm_whh_split_packed_elems();

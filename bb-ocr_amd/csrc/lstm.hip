@@ -254,9 +254,9 @@ float pack_lstm_whh_split(const float* whh_fwd, const float* whh_bwd, uint16_t* 
 #define LSTMX_RING (LSTMX_NG == 1 ? 8 : 5)
 #endif
 #define LSTMX_SEQS (16 * LSTMX_NG)
-// What bounds this kernel is the L2 -> CU stream of the weight fragments (1 MB per workgroup and time step), so one workgroup carries
-// TWO 16-sequence groups through every fragment pair it loads (6 MFMAs per pair): half the streamed bytes per sequence, and the 2,200
-// sequences of a 64-page step fit the 256 CUs in one round.  The lo half of h is kept UNSCALED here (fp16 keeps subnormals in
+// What bounds this kernel is the L2 -> CU stream of the weight fragments (1 MB per workgroup and time step).  A workgroup carries
+// LSTMX_NG 16-sequence groups through every fragment pair it loads (3 MFMAs per pair and group); NG = 1 is what is built: two groups
+// halve the streamed bytes per sequence but measured slower (above).  The lo half of h is kept UNSCALED here (fp16 keeps subnormals in
 // v_mfma_f32_16x16x32_f16 -- tools/micro/mfma_f16_denorm.hip -- and |h| <= 1 bounds its absolute error by 3e-8), so the h_lo term
 // shares the accumulator of the other two; the linear layer that reads the output pair is packed with lo scale 1 accordingly.
 __global__ void __launch_bounds__(512, 1) lstm_exact_kernel(const float* __restrict__ xproj, const uint16_t* __restrict__ whh, uint16_t* __restrict__ out,

@@ -172,17 +172,31 @@ void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_
     c->seq_xp.ensure(rows_pad * 2048 * (sp ? 4 : 2));            // exact mode: the input projection stays fp32
     c->seq_h.ensure(rows_pad * 512 * 2 * m);
     c->seq_lin.ensure(rows_pad * 256 * 2 * m);
-    const int Hh = (int)(rows_pad / 256);
-    Act cur{(uint16_t*)c->seq_v.p, 1, Hh, 256, 256 * m};
+    const uint16_t* cur = (const uint16_t*)c->seq_v.p;
     for (int l = 0; l < 2; ++l) {
-        run_conv(c, c->xproj[l], cur, false, nullptr, false, false, c->seq_xp.p, 2048, 2048, sp);
+        crnn_seq_xproj(c, l, cur, rows_pad, c->seq_xp.p);
         HIPCHK(launch_lstm(c->seq_xp.p, c->whh[l], (uint16_t*)c->seq_h.p, tiles_dev, ntiles, rec_mode(c), c->whh_scale[l], c->cur));
-        Act hh{(uint16_t*)c->seq_h.p, 1, Hh, 256, 512 * m};
         uint16_t* dst = (uint16_t*)(l == 0 ? c->seq_lin.p : c->seq_v.p);
-        run_conv(c, c->lin[l], hh, false, nullptr, false, false, dst, 256 * m, 256, false);
-        cur.p = dst;
+        crnn_seq_lin(c, l, (const uint16_t*)c->seq_h.p, rows_pad, dst);
+        cur = dst;
     }
-    run_conv(c, c->pred, cur, false, nullptr, false, false, logits, 112, 112, true);
+    crnn_seq_pred(c, cur, rows_pad, logits);
+}
+
+// The sequence half's three GEMMs as 1x1 convs over the rows laid out as an image [1, rows_pad / 256, 256, C] (rows_pad: a multiple of 256).
+// Exact mode: x and h are [hi | lo] pairs and the plans are split-fp16 plans; the input projection and the logits leave as fp32.
+static Act seq_rows(const bbocr_ctx* c, const uint16_t* p, size_t rows_pad, int C) { return Act{(uint16_t*)p, 1, (int)(rows_pad / 256), 256, C * rec_mul(c)}; }
+// x [rows_pad, 256] -> the LSTM's input projection [rows_pad, 2048] in lstm8_xproj_channel's order (fp32 in the exact mode)
+void crnn_seq_xproj(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp) {
+    run_conv(c, c->xproj[l], seq_rows(c, x, rows_pad, 256), false, nullptr, false, false, xp, 2048, 2048, rec_split(c));
+}
+// h [rows_pad, 512] (exact: the LSTM's pair, lo half unscaled) -> [rows_pad, 256]
+void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint16_t* out) {
+    run_conv(c, c->lin[l], seq_rows(c, h, rows_pad, 512), false, nullptr, false, false, out, 256 * rec_mul(c), 256, false);
+}
+// x [rows_pad, 256] -> logits fp32 [rows_pad, 112] (97 classes; the columns behind them belong to no class)
+void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logits) {
+    run_conv(c, c->pred, seq_rows(c, x, rows_pad, 256), false, nullptr, false, false, logits, 112, 112, true);
 }
 
 // A recognition pass = feature PARTS + one sequence stage.  A part is a set of crops standing side by side in ONE wide image

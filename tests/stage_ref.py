@@ -27,6 +27,17 @@ of test_conv_mfma_vs_fp64):
 
 E = the image, through the stage's second linear map with |W|, of one element-type ulp of every internally rounded value (ReLU and max-pool are
 1-Lipschitz and pass it through); for the recurrence, which has no single second map, E = 2 max |ref_q - ref_nq| of the case.
+
+The exact mode's split-fp16 stages (pair tensors [hi | lo], split plans, the pair kernels, lstm_exact_kernel; second half of this module) have a
+rule of their own -- the acc term above is two orders of magnitude over that mode's real error.  Per element (EXACT_RULE has the derivation):
+
+  |got - ref| <= u |ref| + (2^-21 + 2 q32) S + 2^-35
+
+u = 2^-22 (pair output) / 2^-24 (fp32 output); S = |W| * |x| + |b|; 2^-21 = the split representation's worst case; q32 = max |standin - ref| / S
+of the same case, standin = the launch's three product terms accumulated in float32 32 products at a time (the float32 FMA chain for
+pair_conv1_1, crnn_conv0_kernel and pair_cls_tail), computed on the CPU and required to stay <= 2^-22.  Selections (pair ReLU, MaxPool(3,1,1),
+the same-size upcat) hold bit for bit; the up-sampling upcat: 2^-22 |ref| + 2^-23 (blend of the four |neighbours|); the recurrence, per tile:
+max |got - ref| <= 8 max |fp32 - ref| + 2^-22.
 """
 from __future__ import annotations
 
@@ -273,38 +284,58 @@ def pool5(x, mut=None):
 
 # ------------------------------------------------------------------------------------------------ BiLSTM recurrence
 def lstm_weights(sd, layer, el):
-    """(W_hh forward, W_hh backward) [1024, 256] fp64, rounded where pack_lstm_whh8 rounds them"""
+    """(W_hh forward, W_hh backward) [1024, 256] fp64, rounded where pack_lstm_whh8 rounds them (el None / 'exact': the fp32 weights; the
+    exact mode's split happens in lstm_dir)"""
     k = f"SequenceModeling.{layer}.rnn.weight_hh_l0"
-    f = lambda s: rnd(torch.from_numpy(np.asarray(sd[s]).astype(np.float64)), el)
+    f = lambda s: rnd(torch.from_numpy(np.asarray(sd[s]).astype(np.float64)), None if el == "exact" else el)
     return f(k), f(k + "_reverse")
 
 
-def lstm_dir(whh, x, reverse, el, q=True, dt=torch.float64, mut=None, pad_x=None):
+def lstm_dir(whh, x, reverse, el, q=True, dt=torch.float64, mut=None, pad_x=None, s=None, c0=None, c_out=None):
     """One direction of torch.nn.LSTM(256, 256) behind the input projection: x [n, T, 1024] = x W_ih^T + b_ih + b_hh (gate order i, f, g, o)
     -> the UNROUNDED h_t [n, T, 256] of every step; with q the value that crosses to the next step is rounded (h crosses LDS as 16 bits).
-    pad_x [n, P, 1024] (mut 'bwd_padded_start'): rows behind the sequence that a backward pass started at the padded length would consume."""
+    pad_x [n, P, 1024] (mut 'bwd_padded_start'): rows behind the sequence that a backward pass started at the padded length would consume.
+    el = 'exact' (lstm_exact_kernel): x is the fp32 input projection; with q, h (an fp32 register) crosses a step as the UNSCALED pair
+    hi = fp16(h), lo = fp16(h - hi) and W_hh is split like pack_lstm_whh_split with the exponent s (one over both directions: bilstm passes
+    it): pre = x + (h_hi w_hi + h_hi w_lo + h_lo w_hi) 2^-s; the returned h_t are the fp32 values the kernel stores as pairs.  Its mistakes:
+    'h_lo_dropped', 'bwd_t_off_by_one' (the backward direction writes step t at row t - 1 and drops t = 0).
+    c0: the initial cell state (the 'cell state carried into the next tile' mistake); c_out: a list that receives the final one."""
     n, T, _ = x.shape
     x = x.to(dt)
-    w = whh.to(dt).t()
+    split = el == "exact" and q
+    if split:
+        s, w_hi, _, w_lo = split_weights(whh, 1.0, split_exponent(whh) if s is None else s)
+        w, wl, sc = w_hi.to(dt).t(), w_lo.to(dt).t(), 2.0 ** -s
+    else:
+        w = whh.to(dt).t()
     h = torch.zeros((n, 256), dtype=dt)
-    c = torch.zeros((n, 256), dtype=dt)
+    hl = torch.zeros((n, 256), dtype=dt)
+    c = torch.zeros((n, 256), dtype=dt) if c0 is None else c0.to(dt)
     out = torch.zeros((n, T, 256), dtype=dt)
     order = {"gate_order": (0, 2, 1, 3)}.get(mut, (0, 1, 2, 3))
 
-    def step(xt, h, c):
-        pre = xt + h @ w
+    def step(xt, h, hl, c):
+        pre = xt + ((h @ w + h @ wl + hl @ w) * sc if split else h @ w)
         gi, gf, gg, go = (pre[:, 256 * k:256 * (k + 1)] for k in order)
         c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
         hu = torch.sigmoid(go) * torch.tanh(c)
-        return hu, (rnd(hu, el) if q else hu), c
+        if split:
+            hu = hu.float()
+            hi, lo = pair_encode(hu, 1.0)
+            return hu.to(dt), hi.to(dt), (torch.zeros_like(hi) if mut == "h_lo_dropped" else lo).to(dt), c
+        return hu, (hu if el == "exact" or not q else rnd(hu, el)), hl, c
 
     if mut == "bwd_padded_start" and reverse:
         for t in range(pad_x.shape[1] - 1, -1, -1):
-            _, h, c = step(pad_x[:, t].to(dt), h, c)
-    for s in range(T):
-        t = T - 1 - s if reverse else s
-        hu, h, c = step(x[:, t], h, c)
-        out[:, t] = hu
+            _, h, hl, c = step(pad_x[:, t].to(dt), h, hl, c)
+    for k in range(T):
+        t = T - 1 - k if reverse else k
+        hu, h, hl, c = step(x[:, t], h, hl, c)
+        tw = t - 1 if (mut == "bwd_t_off_by_one" and reverse) else t
+        if tw >= 0:
+            out[:, tw] = hu
+    if c_out is not None:
+        c_out.append(c)
     return out
 
 
@@ -330,16 +361,26 @@ def lstm_seq_carry_c(whh, x, reverse, el, q=True, dt=torch.float64):
     return torch.cat(outs)
 
 
-def bilstm(whh_f, whh_b, x, el, q=True, dt=torch.float64, mut=None, pad_x=None):
-    """x [n, T, 2, 1024] (direction, gate * 256 + unit) -> [n, T, 512] (fwd | bwd)"""
+def bilstm(whh_f, whh_b, x, el, q=True, dt=torch.float64, mut=None, pad_x=None, c0=None, c_out=None):
+    """x [n, T, 2, 1024] (direction, gate * 256 + unit) -> [n, T, 512] (fwd | bwd).  el = 'exact' with q: as lstm_exact_kernel's pair store
+    leaves it (lo scale 1); c0 = (fwd, bwd) initial cell states, c_out: a list that receives the final (fwd, bwd)"""
     if mut == "carry_c":
         return torch.cat([lstm_seq_carry_c(whh_f, x[:, :, 0], False, el, q, dt), lstm_seq_carry_c(whh_b, x[:, :, 1], True, el, q, dt)], dim=2)
-    return torch.cat([lstm_dir(whh_f, x[:, :, 0], False, el, q, dt, mut, None if pad_x is None else pad_x[:, :, 0]),
-                      lstm_dir(whh_b, x[:, :, 1], True, el, q, dt, mut, None if pad_x is None else pad_x[:, :, 1])], dim=2)
+    s = split_exponent(whh_f, whh_b) if el == "exact" else None
+    cs = []
+    o = torch.cat([lstm_dir(w, x[:, :, d], bool(d), el, q, dt, mut, None if pad_x is None else pad_x[:, :, d], s, None if c0 is None else c0[d], cs)
+                   for d, w in enumerate((whh_f, whh_b))], dim=2)
+    if c_out is not None:
+        c_out.append(tuple(cs))
+    return pair_roundtrip(o, 1.0) if (el == "exact" and q) else o
 
 
 def refs_bilstm(whh_f, whh_b, x, el):
+    """(ref_q, ref_nq, E).  el = 'exact': ref_q = the split recurrence in fp64, ref_nq = fp64 without any split, and E = the tile's bound
+    8 max |fp32 - ref_nq| + 2^-22 with fp32 = the un-split recurrence in float32 (EXACT_RULE)"""
     rq, rn = bilstm(whh_f, whh_b, x, el, True), bilstm(whh_f, whh_b, x, el, False)
+    if el == "exact":
+        return rq, rn, lstm_exact_bound(rn, bilstm(whh_f, whh_b, x, el, False, torch.float32).double())
     return rq, rn, 2.0 * (rq - rn).abs().max().item()
 
 
@@ -653,3 +694,555 @@ def fails_allowance(mutated, ref_q, ref_nq, E, el_out):
     _, allow = bounds(ref_q, ref_nq, E, el_out)
     m = mutated.double()
     return bool(((m - ref_q).abs() > allow).any()) and bool(((m - ref_nq).abs() > allow).any())
+
+
+# ================================================================================================ exact mode: pair tensors, split-fp16 plans
+# (the rule for these stages is stated in EXACT_RULE below and quoted in the module docstring's last paragraph)
+EXACT_RULE = """Rule for the exact mode's split-fp16 stages, per element:
+
+  |got - ref| <= u |ref| + (2^-21 + 2 q32) S + 2^-35
+
+ref   fp64 on the decoded inputs with the fp32-folded weights, no split;
+S     the stage's linear map with absolute values, |W| * |x| + |b| (max-pool passes the bound of its window through);
+u     2^-22 for a pair output (hi carries 11 bits, lo 11 bits of the residual), 2^-24 for an fp32 output;
+2^-21 the representation's worst case: w_hi + w_lo holds w 2^s to 2^-22, the dropped a_lo w_lo term is at most 2^-11 2^-11;
+q32   max |standin - ref| / S of the same case, standin = the launch's three product terms accumulated in float32, 32 products at a time in
+      k order: it stands for fp32 accumulation, which has no useful worst-case bound, and is computed from the reference on the CPU, never
+      from a kernel; the factor 2 is there because the MFMA's summation order inside a k-step is not the stand-in's.  The CPU suite asserts
+      q32 <= 2^-22 on every case the GPU tests run.
+
+pair_conv1_1 and pair_cls_tail are fp32 FMA chains: the same formula with standin = the float32 chain in the kernel's tap order; the
+classifier tail's two maps (16 -> 16 -> 2) share one S = |W2| (|W1| |x| + |b1|) + |b2|, which is the first map's bound carried through |W2|.
+ReLU, MaxPool(3,1,1) and the same-size upcat are selections: bit for bit.  The up-sampling upcat: 2^-22 |ref| + 2^-23 (the blend of the four
+|neighbours|) against the fp64 blend.  The recurrence has no S: per tile, max |got - ref| <= 8 max |fp32 - ref| + 2^-22, fp32 = the same
+recurrence in float32 without any split (three extra 2^-22 roundings per step -- h, W_hh, device expf / tanhf -- on top of fp32's own, and a
+factor 2 for accumulation order)."""
+SPLIT_LO = 2048.0
+U_PAIR, U_F32, SPLIT_REP, SPLIT_ABS, Q32_MAX = 2.0 ** -22, 2.0 ** -24, 2.0 ** -21, 2.0 ** -35, 2.0 ** -22
+
+
+def pair_encode(v32, lo_scale=SPLIT_LO):
+    """fp32 values -> (hi, lo) fp16: hi = fp16(v), lo = fp16((v - hi) lo_scale), round to nearest even (v - hi and the power-of-two product are
+    exact in fp32)"""
+    v = v32.float()
+    hi = v.to(torch.float16)
+    return hi, ((v - hi.float()) * np.float32(lo_scale)).to(torch.float16)
+
+
+def pair_value(hi, lo, lo_scale=SPLIT_LO, dt=torch.float64):
+    """decode; dt = float32 is pair_load8's arithmetic (hi + lo * (1 / lo_scale)) and is exact for every pair pair_encode makes"""
+    return hi.to(dt) + lo.to(dt) * (1.0 / lo_scale)
+
+
+def pair_pack(v32, lo_scale=SPLIT_LO):
+    """[.., C] fp32 values -> the pair tensor [.., C hi | C lo] fp16"""
+    return torch.cat(pair_encode(v32, lo_scale), dim=-1)
+
+
+def pair_halves(t):
+    C = t.shape[-1] // 2
+    return t[..., :C], t[..., C:]
+
+
+def pair_decode(t, lo_scale=SPLIT_LO, dt=torch.float64):
+    return pair_value(*pair_halves(t), lo_scale, dt)
+
+
+def pair_roundtrip(v, lo_scale=SPLIT_LO):
+    """the value a kernel's pair store leaves, fp64 (v is cast to fp32 first: the kernels split an fp32 register)"""
+    return pair_value(*pair_encode(v.float(), lo_scale), lo_scale)
+
+
+def split_exponent(*ws):
+    """s of upload_split_plan / pack_lstm_whh_split: 2^9 <= max |w| 2^s < 2^10, clamped to [-14, 24]"""
+    mx = max(float(w.abs().max()) for w in ws)
+    s = 9 - int(np.floor(np.log2(mx))) if mx > 0 else 0
+    return max(-14, min(24, s))
+
+
+def split_weights(w, lo_scale=SPLIT_LO, s=None):
+    """w (fp32 values) -> (s, w_hi, w_mid, w_lo) fp64: w_hi = fp16(w 2^s), w_lo = fp16(w 2^s - w_hi), and the block the lo activations meet,
+    w_mid = fp16(w_hi / lo_scale) (the packer rounds every block to fp16; for lo_scale 1 it is w_hi)"""
+    s = split_exponent(w) if s is None else s
+    v = w.float() * np.float32(2.0 ** s)
+    hi = v.to(torch.float16).float()
+    lo = (v - hi).to(torch.float16).float()
+    mid = (hi * np.float32(1.0 / lo_scale)).to(torch.float16).float()
+    return s, hi.double(), mid.double(), lo.double()
+
+
+def _k_order(t):
+    """[A, C, T, ...] -> [A, T * C, ...]: k runs over the taps, inside a tap over the channels [a_hi | a_lo | a_hi]"""
+    return t.transpose(1, 2).reshape(t.shape[0], t.shape[1] * t.shape[2], *t.shape[3:])
+
+
+def split_conv(w, b, a_pair, pad=0, dil=1, lo_scale=SPLIT_LO, w_lo_scale=None, mut=None):
+    """A split plan's launch on the pair tensor a_pair [N, H, W, C | C] (lo stored x lo_scale), before its epilogue: NCHW pre-activations
+    {'ref', 'model', 'standin', 'S'}.  w [Cout, C, K, K], b: fp64 tensors of fp32 values.  w_lo_scale: what the plan was PACKED for (a mistake
+    when it differs from lo_scale).  mut: 'drop_a_lo', 'drop_w_lo', 'mid_unscaled', 'no_acc_scale' -- None for the launch itself."""
+    hi, lo = pair_halves(a_pair)
+    ah, al = nchw(hi.double()), nchw(lo.double())                     # al: the STORED lo half
+    x = ah + al / lo_scale
+    s, wh, wm, wl = split_weights(w, lo_scale if w_lo_scale is None else w_lo_scale)
+    if mut == "mid_unscaled":
+        wm = wh
+    if mut == "drop_a_lo":
+        wm = torch.zeros_like(wm)
+    if mut == "drop_w_lo":
+        wl = torch.zeros_like(wl)
+    sc = 1.0 if mut == "no_acc_scale" else 2.0 ** -s
+    ref = conv(x, w, b, pad=pad, dil=dil)
+    S = conv(x.abs(), w.abs(), b.abs(), pad=pad, dil=dil)
+    model = (conv(ah, wh, None, pad, dil) + conv(al, wm, None, pad, dil) + conv(ah, wl, None, pad, dil)) * sc + b[None, :, None, None]
+    # the stand-in: float32, the three terms as ONE k sequence, a partial sum of 32 products added to the accumulator at a time
+    K = w.shape[-1]
+    cols = F.unfold(torch.cat([ah, al, ah], dim=1).float(), K, dilation=dil, padding=pad)          # [N, 3C * T, L], channel-major
+    N, C3 = cols.shape[0], 3 * ah.shape[1]
+    cols = _k_order(cols.reshape(N, C3, K * K, -1))
+    wk = _k_order(torch.cat([wh, wm, wl], dim=1).float().reshape(w.shape[0], C3, K * K))
+    acc = torch.zeros((N, w.shape[0], cols.shape[-1]), dtype=torch.float32)
+    for k in range(0, wk.shape[1], 32):
+        acc = acc + torch.matmul(wk[None, :, k:k + 32], cols[:, k:k + 32])
+    standin = (acc * np.float32(sc) + b.float()[None, :, None]).reshape(ref.shape).double()
+    return {"ref": ref, "model": model, "standin": standin, "S": S}
+
+
+def split_epilogue(y, relu_out, pool, pool_relu, keep_full, store=True, mut=None):
+    """The conv epilogue on NCHW pre-activations -> {'full': .., 'pool': ..} NHWC (the outputs the row writes).  store: the value goes through
+    an fp32 register and the pair store (model, standin, got); False: nothing is rounded (ref, S: max-pool passes a bound through).
+    mut 'pool_split_first': the four values are split before the max, which is then taken on hi and lo separately."""
+    full = F.relu(y) if relu_out else y
+    if store:
+        full = full.float().double()
+    out = {}
+    if keep_full or not pool:
+        out["full"] = nhwc(pair_roundtrip(full) if store else full)
+    if pool:
+        if mut == "pool_split_first":
+            hi, lo = pair_encode(full.float())
+            p = pair_value(F.max_pool2d(hi.float(), 2).half(), F.max_pool2d(lo.float(), 2).half())
+            out["pool"] = nhwc(F.relu(p) if pool_relu else p)
+            return out
+        p = F.max_pool2d(full, 2)
+        p = F.relu(p) if pool_relu else p
+        out["pool"] = nhwc(pair_roundtrip(p) if store else p)
+    return out
+
+
+def split_bound(ref, S, q32, u):
+    return u * ref.abs() + (SPLIT_REP + 2.0 * q32) * S + SPLIT_ABS
+
+
+def split_q32(standin_val, ref, S):
+    """max |standin - ref| / S over the elements with S > 0 (standin_val: the stand-in's fp32 value BEFORE the output store)"""
+    m = S > 0
+    return float(((standin_val - ref).abs()[m] / S[m]).max()) if m.any() else 0.0
+
+
+def split_check(got, ref, S, q32, u, name=""):
+    """apply the rule -> {'worst': max |got - ref| / bound, 'q32', 'kernel': max |got - ref| / S}; AssertionError with a localised report"""
+    got = got.double()
+    assert got.shape == ref.shape == S.shape, (got.shape, ref.shape, S.shape)
+    finite = torch.isfinite(got)
+    bound = split_bound(ref, S, q32, u)
+    d = (got - ref).abs()
+    rel = torch.where(finite, d / bound, torch.full_like(d, float("inf")))
+    m = S > 0
+    stats = {"worst": float(rel.max()), "q32": q32, "kernel": float((d[m & finite] / S[m & finite]).max()) if (m & finite).any() else 0.0}
+    print(f"[stage] {name}: max |got - ref| / bound {stats['worst']:.3g}, q32 {q32:.3g}, kernel max |got - ref| / S {stats['kernel']:.3g}")
+    miss = ~(d <= bound)
+    if miss.any():
+        w = int(torch.argmax(rel))
+        idx = np.unravel_index(w, tuple(got.shape))
+        msg = f"{name}: {int(miss.sum())} of {miss.numel()} elements beyond the bound ({int((~finite).sum())} non-finite); worst at {tuple(int(v) for v in idx)}: got " \
+              f"{got.flatten()[w].item():.9g}, ref {ref.flatten()[w].item():.9g}, bound {bound.flatten()[w].item():.3g}, S {S.flatten()[w].item():.3g}"
+        if got.dim() == 4:
+            msg += f"; by region {localise(miss)}"
+        raise AssertionError(msg)
+    return stats
+
+
+def split_fails(mutated, ref, S, q32, u):
+    return bool(((mutated.double() - ref).abs() > split_bound(ref, S, q32, u)).any())
+
+
+# The conv launches of craft_forward_exact, in its order (detector.cpp's table; the GPU suite asserts that production's rows equal these):
+# name, conv, bn, relu_out, store, pool, pool_relu, keep_full, K, dilation, input may be negative (its producer has no ReLU)
+EXACT_CONVS = [
+    ("conv1_2", "basenet.slice1.3", "basenet.slice1.4", True, 64, 1, False, False, 3, 1, False),
+    ("conv2_1", "basenet.slice1.7", "basenet.slice1.8", True, 128, 0, False, False, 3, 1, False),
+    ("conv2_2", "basenet.slice1.10", "basenet.slice1.11", False, 128, 1, True, True, 3, 1, False),
+    ("conv3_1", "basenet.slice2.14", "basenet.slice2.15", True, 256, 0, False, False, 3, 1, False),
+    ("conv3_2", "basenet.slice2.17", "basenet.slice2.18", False, 256, 0, False, False, 3, 1, False),
+    ("conv3_3", "basenet.slice3.20", "basenet.slice3.21", True, 256, 1, False, False, 3, 1, False),
+    ("conv4_1", "basenet.slice3.24", "basenet.slice3.25", True, 512, 0, False, False, 3, 1, False),
+    ("conv4_2", "basenet.slice3.27", "basenet.slice3.28", False, 512, 0, False, False, 3, 1, False),
+    ("conv4_3", "basenet.slice4.30", "basenet.slice4.31", True, 512, 1, False, False, 3, 1, False),
+    ("conv5_1", "basenet.slice4.34", "basenet.slice4.35", True, 512, 0, False, False, 3, 1, False),
+    ("conv5_2", "basenet.slice4.37", "basenet.slice4.38", False, 512, 0, False, False, 3, 1, False),
+    ("fc6", "basenet.slice5.1", None, False, 1024, 0, False, False, 3, 6, True),
+    ("fc7", "basenet.slice5.2", None, False, 1024, 0, False, False, 1, 1, True),
+    ("up1a", "upconv1.conv.0", "upconv1.conv.1", True, 512, 0, False, False, 1, 1, True),
+    ("up1b", "upconv1.conv.3", "upconv1.conv.4", True, 256, 0, False, False, 3, 1, False),
+    ("up2a", "upconv2.conv.0", "upconv2.conv.1", True, 256, 0, False, False, 1, 1, True),
+    ("up2b", "upconv2.conv.3", "upconv2.conv.4", True, 128, 0, False, False, 3, 1, False),
+    ("up3a", "upconv3.conv.0", "upconv3.conv.1", True, 128, 0, False, False, 1, 1, True),
+    ("up3b", "upconv3.conv.3", "upconv3.conv.4", True, 64, 0, False, False, 3, 1, False),
+    ("up4a", "upconv4.conv.0", "upconv4.conv.1", True, 64, 0, False, False, 1, 1, True),
+    ("up4b", "upconv4.conv.3", "upconv4.conv.4", True, 32, 0, False, False, 3, 1, False),
+    ("cls0", "conv_cls.0", None, True, 32, 0, False, False, 3, 1, False),
+    ("cls2", "conv_cls.2", None, True, 32, 0, False, False, 3, 1, False),
+    ("cls4", "conv_cls.4", None, True, 16, 0, False, False, 3, 1, False),
+]
+EXACT_ROW = {r[0]: i for i, r in enumerate(EXACT_CONVS)}
+# what the GPU tests run through the table: row, (N, H, W) at the layer's own resolution, and the route launch_conv_el takes for it
+EXACT_CONV_CASES = [
+    ("conv1_2", (1, 16, 16), "3x3 DMA, BN 64, pooled shared epilogue (one exact tile)"),
+    ("conv1_2", (3, 34, 50), "3x3 DMA, BN 64, pooled shared epilogue (ragged, odd tile counts, pages 2 and 3)"),
+    ("conv2_2", (2, 18, 30), "3x3 DMA, BN 128, pooled shared epilogue with store_full + pool_relu"),
+    ("conv3_1", (1, 19, 37), "3x3 DMA, BN 128, two cout tiles, relu_out"),
+    ("fc6", (1, 2, 2), "sub-lattice (LH = 1, most phases hold no pixel)"),
+    ("fc6", (2, 15, 20), "sub-lattice (phases of 3 and of 2 rows, two pages stacked)"),
+    ("fc6", (1, 13, 6), "sub-lattice (width below the dilation)"),
+    ("fc7", (2, 7, 5), "1x1 DMA, K = 3 x 1,024"),
+    ("up1a", (1, 2, 2), "1x1 DMA, K = 4,608"),
+    ("up1a", (3, 7, 5), "1x1 DMA, K = 4,608"),
+    ("up4b", (2, 16, 32), "3x3 DMA, 16x16 tiles, <= 32-cout route (64 -> 32: store 32, six k-chunks)"),
+    ("up4b", (2, 18, 30), "3x3 DMA, BN 64, 8x32 tiles (10x34 patch: the three-deep ring, not the <= 32-cout instantiation)"),
+    ("cls4", (1, 16, 16), "3x3 DMA, 16x16 tiles, <= 32-cout route (32 -> 16, store 16, pair pixel stride 32)"),
+    ("cls4", (2, 24, 40), "3x3 DMA, 16x16 tiles, <= 32-cout route (32 -> 16, store 16, pair pixel stride 32)"),
+]
+
+
+def exact_conv_input(name, shape, cin, signed):
+    """the GPU tests' input of a table row: a random pair tensor [N, H, W, cin | cin], negative values only where the producer has no ReLU"""
+    N, H, W = shape
+    g = torch.Generator().manual_seed(900 + EXACT_ROW[name] * 16 + N * H * W % 13)
+    v = torch.randn((N, H, W, cin), generator=g)
+    return pair_pack(v if signed else v.abs())
+
+
+def exact_conv_case(W, name, shape, mut=None, cout=None):
+    """One table row on the GPU tests' input -> (a_pair, {output name: {'ref', 'model', 'standin', 'S', 'q32'}}), outputs NHWC fp64.
+    W: Weights(sd, 'f32').  cout: only the first `cout` output channels (the sensitivity tests' shortcut; a subset that fails is a failure)."""
+    _, ck, bk, relu_out, store, pool, pool_relu, keep_full, K, dil, signed = EXACT_CONVS[EXACT_ROW[name]]
+    w, b = W.layer(ck, bk)
+    a_pair = exact_conv_input(name, shape, w.shape[1], signed)
+    if cout:
+        w, b = w[:cout], b[:cout]
+    pad = dil if K == 3 else 0
+    pre = split_conv(w, b, a_pair, pad, dil, mut=None if mut == "pool_split_first" else mut)
+    epi = lambda y, st, m=None: split_epilogue(y, relu_out, pool, pool_relu, keep_full, st, m)
+    ref, S = epi(pre["ref"], False), split_epilogue(pre["S"], False, pool, False, keep_full, False)
+    model, standin = epi(pre["model"], True, mut if mut == "pool_split_first" else None), epi(pre["standin"], True)
+    sval = split_epilogue(pre["standin"], relu_out, pool, pool_relu, keep_full, False)          # the stand-in's fp32 value before the store
+    return a_pair, {k: {"ref": ref[k], "model": model[k], "standin": standin[k], "S": S[k], "q32": split_q32(sval[k], ref[k], S[k])} for k in ref}
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: element-wise pair kernels
+def pair_relu(t, mut=None):
+    """decode (fp32) -> max(v, 0) -> encode.  mut 'halves': ReLU taken on hi and lo separately"""
+    if mut == "halves":
+        return torch.clamp(t.float(), min=0).half()
+    return pair_pack(torch.clamp(pair_decode(t, dt=torch.float32), min=0))
+
+
+def pair_pool5(t, mut=None):
+    """MaxPool2d(3, 1, 1) on the decoded fp32 values of a pair tensor [N, H, W, C | C].  mut 'halves': on hi and lo separately"""
+    if mut == "halves":
+        return nhwc(F.max_pool2d(nchw(t.float()), 3, 1, 1)).half()
+    return pair_pack(nhwc(F.max_pool2d(nchw(pair_decode(t, dt=torch.float32)), 3, 1, 1)))
+
+
+def pair_plane(shape, seed):
+    """the selection kernels' input: a pair tensor [N, H, W, 512 | 512] with values of both signs and pairs whose halves have opposite signs;
+    channel 0 holds ONE hi (1.0) with a lo that grows strictly along the scan order, so in every window the maximum by hi alone (a tie: the
+    first pixel wins) is not the maximum by value (the last pixel)"""
+    N, H, W = shape
+    v = (torch.rand((N, H, W, 512), generator=torch.Generator().manual_seed(seed)) * 8 - 4).float()
+    v[..., 0] = 1.0 + (torch.arange(H * W, dtype=torch.float32).reshape(1, H, W) - H * W / 2) / (H * W) * np.float32(1.9 * 2.0 ** -12)
+    t = pair_pack(v)
+    hi, lo = pair_halves(t)
+    assert (hi[..., 0] == 1.0).all() and lo[0, ..., 0].unique().numel() == H * W
+    assert ((hi.float() > 0) & (lo.float() < 0)).any() and ((hi.float() < 0) & (lo.float() > 0)).any()
+    return t
+
+
+def upcat_same_inputs(shape):
+    """the same-size upcat cases' inputs: (f7-like pair [N, H, W, 1024 | 1024], s4-like pair [N, H, W, 512 | 512])"""
+    N, H, W = shape
+    g = torch.Generator().manual_seed(710)
+    return pair_pack(torch.randn((N, H, W, 1024), generator=g) * 3), pair_pack(torch.randn((N, H, W, 512), generator=g) * 3)
+
+
+def pair_upcat_same(y, skip, mut=None):
+    """torch.cat([y, skip], dim = channels) of two pair tensors of one size (upcat(f7, s4)): decode -> encode of every value.
+    mut 'halves_swapped': the skip's channels in front"""
+    a, b = pair_decode(y, dt=torch.float32), pair_decode(skip, dt=torch.float32)
+    return pair_pack(torch.cat([b, a] if mut == "halves_swapped" else [a, b], dim=-1))
+
+
+def _up2_matrix(h, clamp0=True):
+    """[2h, h]: torch's upsample_bilinear2d (scale 2, align_corners = False) along one axis; clamp0 False: the source index is not clamped at 0
+    (dst 0 -> src -0.25, truncated to 0 with weight -0.25 on the neighbour; with h = 1 the neighbour is the pixel itself and nothing changes)"""
+    M = torch.zeros((2 * h, h), dtype=torch.float64)
+    for d in range(2 * h):
+        sx = (d + 0.5) * 0.5 - 0.5
+        if clamp0:
+            sx = max(sx, 0.0)
+        x0 = int(sx)
+        x1 = x0 + (1 if x0 < h - 1 else 0)
+        M[d, x0] += 1.0 - (sx - x0)
+        M[d, x1] += sx - x0
+    return M
+
+
+def pair_upcat_up(y, mut=None):
+    """the up-sampled half of upcat: decoded y [N, h, w, C] -> (fp64 blend [N, 2h, 2w, C], the blend of |y|: what the bound is taken from).
+    mut 'edge_unclamped' / 'src_unclamped': upsample2's far-edge mistake / the source index not clamped at 0"""
+    v = nchw(pair_decode(y))
+    if mut == "src_unclamped":
+        u = torch.einsum("ah,nchw,bw->ncab", _up2_matrix(v.shape[2], False), v, _up2_matrix(v.shape[3], False))
+    else:
+        u = upsample2(v, mut)
+    return nhwc(u), nhwc(upsample2(v.abs()))
+
+
+def upcat_up_bound(ref, blend_abs):
+    return U_PAIR * ref.abs() + 2.0 ** -23 * blend_abs
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: conv1_1 and the classifier tail
+C11_GEOMS = [(17, 33, 32, 64), (32, 32, 32, 32), (1, 1, 32, 32), (50, 70, 64, 96)]      # (Himg, Wimg, H32, W32)
+
+
+def c11_pages(geom, N, content):
+    """the pages of the exact conv1_1 cases, uint8 [N, Himg, Wimg, 3]: 'zeros', 'white', or 'random' = every channel of every pixel 0 or 255
+    at random (seeded): per-pixel random, so a shifted or swapped tap shows, and with two input levels the float32 chain's q32 stays
+    <= 2^-22 on all four geometries (the CPU suite asserts it)"""
+    Hi, Wi = geom[:2]
+    if content == "random":
+        return torch.randint(0, 2, (N, Hi, Wi, 3), generator=torch.Generator().manual_seed(100 + Hi), dtype=torch.uint8) * 255
+    return torch.full((N, Hi, Wi, 3), 255 if content == "white" else 0, dtype=torch.uint8)
+
+
+def exact_c11(W, rgb_u8, Himg, Wimg, H32, W32, mut=None):
+    """pair_conv1_1 -> {'ref', 'standin', 'S'} NHWC [N, H32, W32, 64] (ref: fp64 on the fp32-normalised canvas, ReLU'd; standin: the float32
+    FMA chain from the bias over k = (ky 3 + kx) 3 + ch, ReLU'd, BEFORE the pair store).  mut 'canvas_as_padding': a canvas pixel beyond the
+    page enters as the conv's zero padding instead of the normalised raw zero"""
+    xn = normalise(rgb_u8, Himg, Wimg, H32, W32, "f32", True, torch.float32, "canvas_norm0" if mut == "canvas_as_padding" else None).double()
+    w, b = W.c11()
+    ref = F.relu(conv(xn, w, b, pad=1))
+    S = conv(xn.abs(), w.abs(), b.abs(), pad=1)
+    cols = F.unfold(xn.float(), 3, padding=1).reshape(xn.shape[0], 3, 9, -1)                     # [N, ch, tap, L]
+    acc = b.float()[None, :, None].expand(xn.shape[0], 64, cols.shape[-1]).clone()
+    w32 = w.float().reshape(64, 3, 9)
+    for tap in range(9):
+        for ch in range(3):
+            acc = _fma32(w32[None, :, ch, tap, None], cols[:, None, ch, tap], acc)
+    standin = F.relu(acc).reshape(ref.shape).double()
+    return {"ref": nhwc(ref), "standin": nhwc(standin), "S": nhwc(S)}
+
+
+def _fma32(a, b, c):
+    """fmaf on float32 tensors: the product and the sum in fp64 (exact for fp32 operands up to one rounding of the sum: 48-bit product + 24-bit
+    addend rounded to 53 bits, then to 24 -- a double rounding that differs from fmaf in at most a vanishing share of cases, inside the factor
+    2 the rule puts on q32)"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def exact_cls_tail(W, c3_pair, mut=None):
+    """pair_cls_tail on conv_cls.4's pair [N, H, W, 16 | 16] -> {'ref', 'standin', 'S'} [N, H, W, 2]: heat = W2 relu(W1 v + b1) + b2, everything
+    fp32 in the kernel; S = |W2| (|W1| |v| + |b1|) + |b2|"""
+    sd = W.sd
+    f = lambda k: torch.from_numpy(np.asarray(sd[k]).astype(np.float64))
+    w1, b1, w2, b2 = f("conv_cls.6.weight").reshape(16, 16), f("conv_cls.6.bias"), f("conv_cls.8.weight").reshape(2, 16), f("conv_cls.8.bias")
+    v = pair_decode(c3_pair)
+    h = F.relu(v @ w1.t() + b1)
+    ref = h @ w2.t() + b2
+    S = (v.abs() @ w1.abs().t() + b1.abs()) @ w2.abs().t() + b2.abs()
+    v32 = v.float()
+    p = b2.float().expand(*v.shape[:-1], 2).clone()
+    for o in range(16):
+        hh = b1.float()[o].expand(v.shape[:-1]).clone()
+        for k in range(16):
+            hh = _fma32(w1.float()[o, k], v32[..., k], hh)
+        hh = F.relu(hh)
+        p = torch.stack([_fma32(w2.float()[0, o], hh, p[..., 0]), _fma32(w2.float()[1, o], hh, p[..., 1])], dim=-1)
+    return {"ref": ref, "standin": p.double(), "S": S}
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: the network composed
+def exact_forward(W, rgb_u8, Himg, Wimg, H32, W32, dt=torch.float64):
+    """craft_forward_exact's operation order on un-split values, the conv launches taken from EXACT_CONVS row by row -> (heat NHWC, u4b NCHW).
+    With W = Weights(sd, None) this is oracle.nets.CRAFT in double (the CPU suite's composition test, which also proves the table's order)."""
+    rows = iter(EXACT_CONVS)
+
+    def cv(x):
+        _, ck, bk, relu_out, _, pool, pool_relu, keep_full, K, dil, _ = next(rows)
+        w, b = W.layer(ck, bk)
+        y = conv(x, w, b, pad=dil if K == 3 else 0, dil=dil)
+        full = F.relu(y) if relu_out else y
+        if not pool:
+            return full
+        p = F.max_pool2d(full, 2)
+        p = F.relu(p) if pool_relu else p
+        return (p, full) if keep_full else p
+
+    up = lambda y, skip: torch.cat([y if y.shape[2:] == skip.shape[2:] else upsample2(y), skip], dim=1)
+    xn = normalise(rgb_u8, Himg, Wimg, H32, W32, None, False, dt)
+    w, b = W.c11()
+    x0 = F.relu(conv(xn, w, b, pad=1))
+    p1 = cv(x0)
+    a3 = cv(p1)
+    p2, s1 = cv(a3)
+    s2 = cv(cv(p2))
+    p3 = cv(F.relu(s2))
+    s3 = cv(cv(p3))
+    p4 = cv(F.relu(s3))
+    s4 = cv(cv(p4))
+    f7 = cv(cv(F.max_pool2d(s4, 3, 1, 1)))
+    u1b = cv(cv(up(f7, s4)))
+    u2b = cv(cv(up(u1b, s3)))
+    u3b = cv(cv(up(u2b, s2)))
+    u4b = cv(cv(up(u3b, s1)))
+    c3 = cv(cv(cv(u4b)))
+    assert next(rows, None) is None
+    w1, b1, w2, b2 = W.tail()
+    return nhwc(conv(F.relu(conv(c3, w1, b1)), w2, b2)), u4b
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: sequence half
+def seq_gemm_weights(sd, which, layer, perm=None):
+    """(w [Cout, K, 1, 1], b, lo_scale of the INPUT pair) of the sequence half's GEMMs as weights.cpp builds them: which 0 xproj (both directions,
+    rows permuted by perm = lstm8_xproj_channel; bias = b_ih + b_hh in fp32), 1 lin (the input is the LSTM's pair: lo unscaled), 2 pred"""
+    f = lambda k: torch.from_numpy(np.asarray(sd[k]).astype(np.float32))
+    sm = f"SequenceModeling.{layer}."
+    if which == 0:
+        w = torch.zeros((2048, 256), dtype=torch.float32)
+        b = torch.zeros(2048, dtype=torch.float32)
+        for d, sfx in enumerate(("", "_reverse")):
+            w[perm[d * 1024:(d + 1) * 1024]] = f(sm + "rnn.weight_ih_l0" + sfx)
+            b[perm[d * 1024:(d + 1) * 1024]] = f(sm + "rnn.bias_ih_l0" + sfx) + f(sm + "rnn.bias_hh_l0" + sfx)
+        lo = SPLIT_LO
+    elif which == 1:
+        w, b, lo = f(sm + "linear.weight"), f(sm + "linear.bias"), 1.0
+    else:
+        w, b, lo = f("Prediction.weight"), f("Prediction.bias"), SPLIT_LO
+    return w.double()[:, :, None, None], b.double(), lo
+
+
+def lstm_exact_bound(ref, fp32):
+    """the recurrence's bound of a tile (EXACT_RULE); refs_bilstm(.., 'exact') returns it as its allowance"""
+    return 8.0 * float((fp32 - ref).abs().max()) + 2.0 ** -22
+
+
+EXACT_TILES = lambda cap: [(cap, 15), (3, 79), (1, 15), (cap, 255), (5, 639)]
+
+
+def exact_lstm_inputs(cap, layer, sigma):
+    """the GPU test's fp32 input projections per tile [n, T, 2, 1024]"""
+    gen = torch.Generator().manual_seed(850 + layer)
+    return [(torch.randn((n, T, 2, 1024), generator=gen) * sigma).float() for n, T in EXACT_TILES(cap)]
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: models of the named mistakes
+def fc6_phase_model(w, b, x, mut=None, d=6):
+    """The dilated 3x3 (padding = dilation d) the way the sub-lattice path walks it: d * d plain 3x3 convs, one per phase image
+    x[:, :, py::d, px::d], the phase images of a page stacked along y in the order q = py d + px with ONE shared zero row between neighbours.
+    x NCHW fp64 -> NCHW.  mut None reproduces conv(x, w, b, pad = d, dil = d); the mistakes:
+    'row_beyond'        a phase with fewer rows than LH = ceil(H / d) reads its missing row from memory: the rows behind the page (the next
+                        page's first rows; zeros behind the last page) instead of treating it as padding
+    'separator_nonzero' the shared row between two stacked phase images holds the neighbour's edge row instead of zero
+    'page_offset'       the phase images of pages >= 1 are taken one phase image further along the stack"""
+    N, Cc, H, Wd = x.shape
+    LH = -(-H // d)
+    behind = torch.cat([x, torch.zeros_like(x[:1])])[1:]                         # page n + 1 (zeros behind the last)
+    subs = [x[:, :, q // d::d, q % d::d] for q in range(d * d)]
+
+    def like(t, ref):                                                            # crop / zero-pad t to ref's spatial shape
+        t = t[:, :, :ref.shape[2], :ref.shape[3]]
+        return F.pad(t, (0, ref.shape[3] - t.shape[3], 0, ref.shape[2] - t.shape[2]))
+
+    y = torch.zeros((N, w.shape[0], H, Wd), dtype=x.dtype)
+    for q, sub in enumerate(subs):
+        py, px = q // d, q % d
+        lh, lw = sub.shape[2:]
+        if lw == 0 or lh == 0:
+            continue
+        src = sub
+        if mut == "page_offset" and N > 1:
+            src = torch.cat([sub[:1], like(subs[(q + 1) % (d * d)][1:], sub)])
+        p = F.pad(src, (1, 1, 1, 1))
+        if mut == "row_beyond" and lh < LH and lh * d + py - H < H:
+            p[:, :, -1, 1:-1] = behind[:, :, lh * d + py - H, px::d]
+        if mut == "separator_nonzero":
+            if q + 1 < d * d and subs[q + 1].shape[2] > 0:
+                p[:, :, -1:, 1:-1] = like(subs[q + 1][:, :, :1], src[:, :, :1])
+            if q > 0 and subs[q - 1].shape[2] > 0:
+                p[:, :, :1, 1:-1] = like(subs[q - 1][:, :, -1:], src[:, :, :1])
+        y[:, :, py::d, px::d] = conv(p, w, b)
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: the recogniser's conv stack, a stage alone
+def exact_rec_inputs(widths, k, order=None):
+    """the GPU tests' input of stage k alone, per crop in box order: k = 0 the fp32-normalised pixels [1, 64, w, 1] (fp64 values; the device gets
+    the codes 1 + grey of rec_pixels); k >= 1 a pair tensor [1, H, w', C | C] of non-negative values (every producer ends on a ReLU)"""
+    if k == 0:
+        return [rec_normalise(g, "f32") for g in rec_pixels(widths, REC_SEED, order)]
+    g = torch.Generator().manual_seed(REC_SEED + 100 + k)
+    return [pair_pack(torch.randn((1,) + rec_in_shape(k, w), generator=g).abs()) for w in widths]
+
+
+def rec_wide_pack_pair(slots, cols, xs, k):
+    """pair tensors of the crops (box order; slots: their first pixel columns) as the wide input of stage k >= 1, [H, W, C | C] fp16; separator
+    columns +0, in front of stage 7 the value REC_SEP7 (rec_wide_pack)"""
+    H, s, C = REC_IN[k]
+    wide = torch.zeros((H, (cols >> s) - (1 if k == 7 else 0), 2 * C), dtype=torch.float16)
+    if k == 7:
+        wide[..., :C] = REC_SEP7
+    for x, sl in zip(xs, slots):
+        wide[:, sl >> s:(sl >> s) + x.shape[2]] = x[0]
+    return wide
+
+
+def exact_rec_stage(W, k, x, mut=None):
+    """stage k of crnn_features_stages on ONE crop in the exact mode -> NHWC {'ref', 'model', 'standin', 'sval', 'S'} (sval: the stand-in's fp32
+    value before the pair store).  k = 0: crnn_conv0_kernel<REC_SPLIT>, a float32 chain of 9 FMAs from the bias in tap order, ReLU, 2x2 max;
+    1..6: split plans r1..r6 + ReLU (+ the pools of rec_stage); 7: ((a + b) + c) / 3 in float32 on the decoded rows."""
+    pool = {0: 2, 1: 2, 3: (2, 1), 5: (2, 1)}.get(k)
+    post = lambda y: F.max_pool2d(F.relu(y), pool) if pool else F.relu(y)
+    if k == 7:
+        v = nchw(pair_decode(x))
+        v32 = v.float()
+        sval = (((v32[:, :, 0] + v32[:, :, 1]) + v32[:, :, 2]) / np.float32(3.0))[:, :, None].double()
+        out = {"ref": v.mean(dim=2, keepdim=True), "model": sval, "sval": sval, "S": v.abs().mean(dim=2, keepdim=True)}
+    elif k == 0:
+        w, b = W.r0()
+        xc = nchw(x.double())
+        cols = F.unfold(xc.float(), 3, padding=1)                                   # [1, 9, L], tap = ky 3 + kx
+        acc = b.float()[None, :, None].expand(1, 32, cols.shape[-1]).clone()
+        w32 = w.float().reshape(32, 9)
+        for tap in range(9):
+            acc = _fma32(w32[None, :, tap, None], cols[:, None, tap], acc)
+        sval = post(acc.reshape(1, 32, xc.shape[2], xc.shape[3])).double()
+        out = {"ref": post(conv(xc, w, b, pad=1)), "model": sval, "sval": sval,
+               "S": F.max_pool2d(conv(xc.abs(), w.abs(), b.abs(), pad=1), pool)}
+    else:
+        w, b = W.r(k)
+        pre = split_conv(w, b, x, pad=0 if k == 6 else 1, mut=mut)
+        out = {"ref": post(pre["ref"]), "model": post(pre["model"].float().double()), "sval": post(pre["standin"]),
+               "S": F.max_pool2d(pre["S"], pool) if pool else pre["S"]}
+    out["standin"] = pair_roundtrip(out["sval"])
+    out["model"] = pair_roundtrip(out["model"])
+    return {n: nhwc(t) for n, t in out.items()}
+
+
+def exact_rec_part(W, k, xs, mut=None):
+    """exact_rec_stage over the crops of a part, flattened (rec_flat) -> dict of vectors + 'q32' of the part + per-crop output shapes"""
+    per = [exact_rec_stage(W, k, x, mut) for x in xs]
+    out = {n: rec_flat([p[n] for p in per]) for n in per[0]}
+    out["q32"] = split_q32(out["sval"], out["ref"], out["S"])
+    out["shapes"] = [tuple(p["ref"].shape[1:]) for p in per]
+    return out

@@ -3,6 +3,9 @@ packed side tables of a live context (tools/micro/stage_shim.hip), against the f
 the tolerance rule stated there.  An L2 norm over a heat-map cannot see an error confined to a page border, a tile seam, the first pixel of the
 second page of a batch or one time step of 79; these checks are per element, and a failure names the element and the region it lies in.
 
+The exact mode's split-fp16 stages follow in the second half: rows of craft_forward_exact's conv table, the five pair kernels, every stage of the
+recogniser's conv stack alone, xproj / lin / pred and lstm_exact_kernel, under the split-stage rule (stage_ref.EXACT_RULE).
+
 hipErrorNotSupported (801) from a stage is a failure: production would silently take its fallback path on that shape.
 Set BBOCR_STAGE_STATS=<file> to collect one JSON line per case (the table of DESIGN.md section 5)."""
 import ctypes as C
@@ -67,6 +70,8 @@ class Stage:
             if torch.is_tensor(x):
                 assert x.is_cuda and x.is_contiguous()
                 a += [C.c_void_p(x.data_ptr()), C.c_size_t(x.numel())]
+            elif x is None:                                   # an output the stage does not write
+                a += [C.c_void_p(None), C.c_size_t(0)]
             else:
                 a.append(x)
         torch.cuda.synchronize()
@@ -243,13 +248,15 @@ def test_pool5_bit_exact(st, shape):
 
 
 # ------------------------------------------------------------------------------------------------ BiLSTM recurrence, mixed tile table
-TILES = [(16, 15), (3, 79), (1, 15), (16, 255), (5, 639)]     # (sequences, T): T = imgW / 4 - 1 of the buckets 64, 320, 1024, 2560
+def _tiles(cap):
+    return [(cap, 15), (3, 79), (1, 15), (cap, 255), (5, 639)]     # (sequences, T): T = imgW / 4 - 1 of the buckets 64, 320, 1024, 2560
 
 
 @pytest.mark.parametrize("sigma", [1.5, 0.3])
 @pytest.mark.parametrize("layer", [0, 1])
 def test_bilstm_mixed_tiles(st, layer, sigma):
-    assert st.lib.stage_shim_tile_seqs(st.h) == 16
+    TILES = _tiles(st.lib.stage_shim_tile_seqs(st.h))     # the tile capacity is production's, not a constant of the test
+    assert TILES[0][0] >= 1
     perm = torch.tensor([st.lib.stage_shim_xproj_channel(d, g, u) for d in range(2) for g in range(4) for u in range(256)], dtype=torch.long)
     assert sorted(perm.tolist()) == list(range(2048))
     gen = torch.Generator().manual_seed(800 + layer)
@@ -456,3 +463,307 @@ def test_rec_features_exact(st_exact, part):
     _record("rec 0..7", "exact", f"part {part}", {"worst_crop": worst_crop, "worst_step": worst_step, "fp32_worst_step": worst32, "step_bound": bound})
     assert worst_crop <= 2e-5, f"{name}: a crop's relative L2 {worst_crop:.3g} > 2e-5"
     assert worst_step <= bound, f"{name}: a time step's relative L2 {worst_step:.3g} > {bound:.3g}"
+
+
+# ================================================================================================ exact mode: split-fp16 stages, one at a time
+# The rule (R.EXACT_RULE): |got - ref| <= u |ref| + (2^-21 + 2 q32) S + 2^-35 per element, q32 from the reference's own float32 stand-in.
+def _exact_stats(stage, case, stats):
+    _record(stage, "exact", case, stats)
+
+
+def test_exact_table_is_the_references_table(st_exact):
+    """craft_forward_exact's conv table (detector.cpp), row by row, is R.EXACT_CONVS -- whose order the CPU suite proves against
+    oracle.nets.CRAFT; a row deleted or moved in production changes what the pass runs, and this test and the cases below with it"""
+    st = st_exact
+    assert st.lib.stage_exact_rows() == len(R.EXACT_CONVS)
+    for i, (name, ck, bk, relu_out, store, pool, pool_relu, keep_full, K, dil, _) in enumerate(R.EXACT_CONVS):
+        nm, info = C.create_string_buffer(16), (C.c_int * 8)()
+        rc = st.lib.stage_exact_row_info(st.h, i, nm, info)
+        assert rc == 0, f"stage_exact_row_info: status {rc} {st.lib.stage_shim_error().decode()}"
+        w, _b = st.W.layer(ck, bk)
+        assert (nm.value.decode(), list(info)) == (name, [w.shape[1], int(relu_out), store, pool, int(pool_relu), int(keep_full), K, dil]), (i, name)
+        assert store == w.shape[0] and K == w.shape[2]
+
+
+@pytest.mark.parametrize("name,shape,route", R.EXACT_CONV_CASES, ids=[f"{n}-{'x'.join(map(str, s))}" for n, s, _ in R.EXACT_CONV_CASES])
+def test_exact_conv_rows(st_exact, name, shape, route):
+    """Rows of the exact detector's conv table on random pair tensors, through craft_exact_conv.  Route per case (launch_conv_el):
+    conv1_2 1x16x16 / 3x34x50: 3x3 DMA, BN 64, pooled shared epilogue;  conv2_2 2x18x30: 3x3 DMA, BN 128, pooled shared epilogue with store_full and
+    pool_relu (both outputs checked);  conv3_1 1x19x37: 3x3 DMA, BN 128, plain pair epilogue, two cout tiles;  fc6 1x2x2 / 2x15x20 / 1x13x6: the
+    dilated sub-lattice path (a.sub, a.stack, the magic-number row division);  fc7 2x7x5, up1a 1x2x2 / 3x7x5: 1x1 DMA (K = 3,072 / 4,608);
+    up4b 2x16x32, cls4 1x16x16 / 2x24x40: 16x16 tiles (18x18 patch) and so the <= 32-cout instantiation -- up4b with 32 stored couts and six
+    k-chunks, cls4 with 16 and three;  up4b 2x18x30: 8x32 tiles (10x34 patch), the ordinary three-deep ring of the BN 64 3x3 DMA kernel."""
+    st = st_exact
+    a_pair, outs = R.exact_conv_case(st.W, name, shape)
+    row = R.EXACT_ROW[name]
+    _, _, _, _, store, pool, _, keep_full, _, _, _ = R.EXACT_CONVS[row]
+    N, H, W = shape
+    d = a_pair.cuda()
+    main = "pool" if pool else "full"
+    shp = {k: tuple(o["ref"].shape[:3]) + (2 * store,) for k, o in outs.items()}
+    n_main = int(np.prod(shp[main]))
+
+    def run():
+        o = st.out(shp[main])
+        f = st.out(shp["full"]) if keep_full else None
+        st.call("stage_exact_conv", row, d, N, H, W, o, f)
+        return torch.cat([o.reshape(-1)] + ([f.reshape(-1)] if keep_full else []))
+
+    flat = st.twice(run)
+    got = {main: flat[:n_main].reshape(shp[main])}
+    if keep_full:
+        got["full"] = flat[n_main:].reshape(shp["full"])
+    for k, o in outs.items():
+        assert o["q32"] <= R.Q32_MAX
+        case = f"{N}x{H}x{W}" + (f" {k}" if len(outs) > 1 else "")
+        _exact_stats(f"exact {name}", case, R.split_check(R.pair_decode(got[k]), o["ref"], o["S"], o["q32"], R.U_PAIR, f"exact {name} {case} [{route}]"))
+
+
+@pytest.mark.parametrize("content", ["random", "zeros", "white"])
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("geom", R.C11_GEOMS)
+def test_exact_conv1_1(st_exact, geom, N, content):
+    """pair_conv1_1: a canvas pixel beyond the page is a normalised raw zero, a pixel beyond the canvas the conv's zero padding"""
+    st = st_exact
+    Hi, Wi, H32, W32 = geom
+    rgb = R.c11_pages(geom, N, content)
+    d = rgb.cuda()
+
+    def run():
+        o = st.out((N, H32, W32, 128))
+        st.call("stage_exact_conv1_1", d, N, Hi, Wi, H32, W32, o)
+        return o
+
+    got = R.pair_decode(st.twice(run))
+    r = R.exact_c11(st.W, rgb, Hi, Wi, H32, W32)
+    q32 = R.split_q32(r["standin"], r["ref"], r["S"])
+    assert q32 <= R.Q32_MAX
+    case = f"{N}x{Hi}x{Wi} on {H32}x{W32} {content}"
+    _exact_stats("exact conv1_1", case, R.split_check(got, r["ref"], r["S"], q32, R.U_PAIR, f"exact conv1_1 {case}"))
+
+
+def _bits_equal(got, want, name):
+    diff = got.view(torch.int16) != want.view(torch.int16)
+    assert not diff.any(), f"{name}: {int(diff.sum())} of {diff.numel()} 16-bit values differ; by region {R.localise(diff)}"
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 2), (2, 6, 10), (1, 30, 40)])
+@pytest.mark.parametrize("op", ["relu", "pool5"])
+def test_exact_pair_selection_kernels(st_exact, op, shape):
+    """pair_relu / pair_maxpool3x3s1 are selections on the decoded value: bit for bit the numpy restatement decode -> select -> encode, and the
+    decoded output is exactly the selected input value"""
+    st = st_exact
+    N, H, W = shape
+    x = R.pair_plane(shape, 700)
+    d = x.cuda()
+
+    def run():
+        o = st.out((N, H, W, 1024))
+        st.call(f"stage_exact_{op}", d, N, H, W, 512, o)
+        return o
+
+    got = st.twice(run)
+    want = R.pair_relu(x) if op == "relu" else R.pair_pool5(x)
+    _bits_equal(got, want, f"exact {op} {shape}")
+    v = R.pair_decode(x)
+    sel = torch.clamp(v, min=0) if op == "relu" else R.nhwc(torch.nn.functional.max_pool2d(R.nchw(v), 3, 1, 1))
+    assert torch.equal(R.pair_decode(got), sel)
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 2), (2, 3, 5)])
+def test_exact_upcat_same_size(st_exact, shape):
+    """upcat(f7, s4): a plain channel concat of two pair tensors, bit for bit"""
+    st = st_exact
+    N, H, W = shape
+    y, sk = R.upcat_same_inputs(shape)
+    dy, ds = y.cuda(), sk.cuda()
+
+    def run():
+        o = st.out((N, H, W, 2 * 1536))
+        st.call("stage_exact_upcat", dy, H, W, 1024, ds, 512, N, H, W, o)
+        return o
+
+    got = st.twice(run)
+    _bits_equal(got, R.pair_upcat_same(y, sk), f"exact upcat same size {shape}")
+    assert torch.equal(R.pair_decode(got), torch.cat([R.pair_decode(y), R.pair_decode(sk)], dim=-1))
+
+
+@pytest.mark.parametrize("shape,chans", [((1, 1, 1), (256, 512)), ((2, 3, 5), (128, 256)), ((1, 20, 28), (64, 128))])
+def test_exact_upcat_upsampling(st_exact, shape, chans):
+    """cat([F.interpolate(y, 2x, bilinear, align_corners = False), skip]): the up-sampled channels against the fp64 blend of the decoded values,
+    bound 2^-22 |ref| + 2^-23 (blend of the four |neighbours|); the skip's channels bit for bit"""
+    st = st_exact
+    N, h, w = shape
+    Cy, Cs = chans
+    g = torch.Generator().manual_seed(720)
+    y, sk = R.pair_pack(torch.randn((N, h, w, Cy), generator=g) * 3), R.pair_pack(torch.randn((N, 2 * h, 2 * w, Cs), generator=g) * 3)
+    dy, ds = y.cuda(), sk.cuda()
+
+    def run():
+        o = st.out((N, 2 * h, 2 * w, 2 * (Cy + Cs)))
+        st.call("stage_exact_upcat", dy, h, w, Cy, ds, Cs, N, 2 * h, 2 * w, o)
+        return o
+
+    got = st.twice(run)
+    hi, lo = R.pair_halves(got)
+    # the skip's channels pass through decode -> encode like every value here: the VALUE is the input's exactly, the bits those of the re-encoded
+    # value (a pair whose lo is exactly half an ulp of its hi re-encodes to the neighbouring hi: 2 of 61,440 values of the 2x3x5 case)
+    skip_out = torch.cat([hi[..., Cy:], lo[..., Cy:]], dim=-1).contiguous()
+    _bits_equal(skip_out, R.pair_pack(R.pair_decode(sk, dt=torch.float32)), f"exact upcat {shape}: skip channels")
+    assert torch.equal(R.pair_decode(skip_out), R.pair_decode(sk))
+    ref, blend = R.pair_upcat_up(y)
+    val = R.pair_value(hi[..., :Cy], lo[..., :Cy])
+    bound = R.upcat_up_bound(ref, blend)
+    err = (val - ref).abs()
+    worst = float((err / bound.clamp(min=1e-300)).max())
+    print(f"[stage] exact upcat 2x {shape}: max |got - ref| / bound {worst:.3g}")
+    _exact_stats("exact upcat 2x", f"{N}x{h}x{w}", {"worst": worst})
+    miss = ~(err <= bound)
+    assert not miss.any(), f"exact upcat 2x {shape}: {int(miss.sum())} up-sampled values beyond the bound (worst {worst:.3g} x); by region {R.localise(miss)}"
+
+
+@pytest.mark.parametrize("shape,scale", [((1, 16, 16), 1.0), ((2, 40, 56), 1.0), ((2, 40, 56), 6.0)])
+def test_exact_cls_tail(st_exact, shape, scale):
+    st = st_exact
+    N, H, W = shape
+    c3 = R.pair_pack(torch.randn((N, H, W, 16), generator=torch.Generator().manual_seed(600)).abs() * scale)
+    d = c3.cuda()
+
+    def run():
+        o = st.out((N, H, W, 2), torch.float32)
+        st.call("stage_exact_cls_tail", d, N, H, W, o)
+        return o
+
+    got = st.twice(run).double()
+    r = R.exact_cls_tail(st.W, c3)
+    q32 = R.split_q32(r["standin"], r["ref"], r["S"])
+    assert q32 <= R.Q32_MAX
+    case = f"{N}x{H}x{W} x{scale:g}"
+    _exact_stats("exact cls tail", case, R.split_check(got, r["ref"], r["S"], q32, R.U_F32, f"exact cls tail {case}"))
+
+
+# ------------------------------------------------------------------------------------------------ exact mode: the sequence half
+SEQ_ROWS, SEQ_ROWS_PAD = 300, 512
+
+
+def _xproj_perm(st):
+    perm = torch.tensor([st.lib.stage_shim_xproj_channel(d, g, u) for d in range(2) for g in range(4) for u in range(256)], dtype=torch.long)
+    assert sorted(perm.tolist()) == list(range(2048))
+    return perm
+
+
+@pytest.mark.parametrize("which,layer", [(0, 0), (0, 1), (1, 0), (1, 1), (2, 0)], ids=["xproj0", "xproj1", "lin0", "lin1", "pred"])
+def test_exact_sequence_gemms(st_exact, which, layer):
+    """xproj[l], lin[l] and pred through crnn_sequence's own helpers on 300 rows padded to 512.  lin reads the LSTM's pair, whose lo half is
+    UNSCALED (its plan is the one packed with lo_scale 1); pred's columns 97..111 belong to no class and are not read."""
+    st = st_exact
+    w, b, lo_scale = R.seq_gemm_weights(st.crnn, which, layer, _xproj_perm(st))
+    K, cout = w.shape[1], w.shape[0]
+    g = torch.Generator().manual_seed(860 + 10 * which + layer)
+    v = torch.randn((SEQ_ROWS_PAD, K), generator=g)
+    v = torch.tanh(v) if which == 1 else v
+    v[SEQ_ROWS:] = 0
+    a_pair = R.pair_pack(v, lo_scale)
+    d = a_pair.cuda()
+    f32 = which != 1
+    width = {0: 2048, 1: 512, 2: 112}[which]
+
+    def run():
+        o = st.out((SEQ_ROWS_PAD, width), torch.float32 if f32 else None)
+        torch.cuda.synchronize()
+        rc = st.lib.stage_exact_seq_gemm(st.h, which, layer, C.c_void_p(d.data_ptr()), C.c_size_t(d.numel()), C.c_size_t(SEQ_ROWS_PAD), C.c_void_p(o.data_ptr()),
+                                         C.c_size_t(o.numel()))
+        assert rc == 0, f"stage_exact_seq_gemm: status {rc} {st.lib.stage_shim_error().decode()}"
+        return o
+
+    out = st.twice(run)
+    pre = R.split_conv(w, b, a_pair.reshape(1, SEQ_ROWS_PAD // 256, 256, 2 * K), lo_scale=lo_scale)
+    rows = lambda t: R.nhwc(t).reshape(SEQ_ROWS_PAD, cout)
+    ref, S = rows(pre["ref"]), rows(pre["S"])
+    q32 = R.split_q32(rows(pre["standin"]), ref, S)
+    assert q32 <= R.Q32_MAX
+    got = out.double()[:, :cout] if f32 else R.pair_decode(out)
+    name = f"exact {('xproj', 'lin', 'pred')[which]}" + ("" if which == 2 else f"[{layer}]")
+    _exact_stats(name, f"{SEQ_ROWS} rows", R.split_check(got, ref, S, q32, R.U_F32 if f32 else R.U_PAIR, name))
+
+
+@pytest.mark.parametrize("sigma", [1.5, 0.3])
+@pytest.mark.parametrize("layer", [0, 1])
+def test_exact_bilstm_mixed_tiles(st_exact, layer, sigma):
+    """lstm_exact_kernel on a mixed tile table built from production's tile capacity: nothing written behind the last row, every tile alone
+    equals itself in the table bit for bit, and per tile max |got - ref| <= 8 max |fp32 - ref| + 2^-22 (R.EXACT_RULE); the output pair is
+    decoded with lo scale 1"""
+    st = st_exact
+    cap = st.lib.stage_shim_tile_seqs(st.h)
+    assert cap >= 1
+    tiles = R.EXACT_TILES(cap)
+    perm = _xproj_perm(st)
+    xs = R.exact_lstm_inputs(cap, layer, sigma)
+    rows = sum(n * T for n, T in tiles)
+    rows_pad = (rows + 255) // 256 * 256
+    xproj = torch.zeros((rows_pad, 2048), dtype=torch.float32)
+    table, row0 = [], 0
+    for (n, T), x in zip(tiles, xs):
+        xproj[row0:row0 + n * T, perm] = x.reshape(n * T, 2048)
+        table.append((row0, n, T, 0))
+        row0 += n * T
+    dx = xproj.cuda()
+
+    def launch(entries):
+        o = st.out((rows_pad, 1024))
+        t = np.ascontiguousarray(np.array(entries, dtype=np.int32))
+        torch.cuda.synchronize()
+        rc = st.lib.stage_lstm(st.h, layer, C.c_void_p(dx.data_ptr()), C.c_void_p(o.data_ptr()), C.c_size_t(rows_pad), t.ctypes.data_as(C.POINTER(C.c_int)), len(entries))
+        assert rc == 0, f"stage_lstm: status {rc} {st.lib.stage_shim_error().decode()}"
+        return o
+
+    got = st.twice(lambda: launch(table))
+    assert torch.isnan(got[rows:].float()).all()         # nothing is written behind the last sequence
+    for k, (r0, n, T, _) in enumerate(table):
+        alone = launch([table[k]]).cpu()
+        assert torch.equal(alone[r0:r0 + n * T].view(torch.int16), got[r0:r0 + n * T].view(torch.int16)), f"tile {k} differs when launched alone"
+    wf, wb = R.lstm_weights(st.crnn, layer, "exact")
+    val = R.pair_decode(got[:rows], 1.0)
+    worst, standin_worst, problems = 0.0, 0.0, []
+    for k, ((r0, n, T, _), x) in enumerate(zip(table, xs)):
+        _model, ref, bound = R.refs_bilstm(wf, wb, x, "exact")
+        standin = R.bilstm(wf, wb, x, "exact", True, torch.float32)
+        standin_worst = max(standin_worst, float((standin - ref).abs().max()) / bound)
+        err = (val[r0:r0 + n * T].reshape(n, T, 512) - ref).abs()
+        ok = torch.isfinite(err) & (err <= bound)
+        worst = max(worst, float(torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf"))).max()) / bound)
+        if not ok.all():
+            s, t, ch = [int(v[0]) for v in torch.nonzero(~ok, as_tuple=True)]
+            problems.append(f"tile {k} ({n} x T={T}, first row {r0}): {int((~ok).sum())} beyond {bound:.3g}, first at sequence {s}, t {t}, {'bwd' if ch >= 256 else 'fwd'} unit {ch % 256}")
+    print(f"[stage] exact bilstm layer {layer} sigma {sigma:g}: max |got - ref| / bound {worst:.3g}, the float32 split stand-in's {standin_worst:.3g}")
+    _exact_stats(f"exact bilstm layer {layer}", f"sigma {sigma:g}", {"worst": worst, "standin": standin_worst})
+    assert not problems, "; ".join(problems)
+
+
+@pytest.mark.parametrize("part", ["A", "B"])
+@pytest.mark.parametrize("k", range(R.REC_STAGES))
+def test_exact_rec_stage_alone(st_exact, k, part):
+    """every stage of crnn_features_stages ALONE in the exact mode, parts A and B, per element under R.EXACT_RULE against each crop's own fp64
+    reference: stage 0 takes the codes 1 + grey (crnn_conv0_kernel<REC_SPLIT>, a float32 FMA chain), stages 1..6 are split plans on pair
+    tensors, stage 7 the float32 3-row mean on the decoded pairs + gather.  (Separators, gather rows and crop independence: bit for bit in
+    test_rec_features_exact.)"""
+    st = st_exact
+    widths = REC_PARTS[part]
+    plan = RecPlan(st, widths)
+    xs = R.exact_rec_inputs(widths, k, plan.order)
+    if k == 0:
+        codes = [(g.to(torch.int16) + 1)[None, :, :, None] for g in R.rec_pixels(widths, R.REC_SEED, plan.order)]
+        wide = R.rec_wide_pack(plan.slot, plan.cols, codes, 0, torch.int16)[0]
+    else:
+        wide = R.rec_wide_pack_pair(plan.slot, plan.cols, xs, k)
+    out = _rec_run(st, plan, k, k, wide)
+    got = R.rec_flat([R.pair_decode(g) for g in _rec_crops(plan, k, out)])
+    p = R.exact_rec_part(st.RW, k, xs)
+    assert p["q32"] <= R.Q32_MAX
+    name = f"exact rec stage {k} part {part}"
+    try:
+        stats = R.split_check(got, p["ref"], p["S"], p["q32"], R.U_PAIR, name)
+    except AssertionError as e:
+        miss = ~((got - p["ref"]).abs() <= R.split_bound(p["ref"], p["S"], p["q32"], R.U_PAIR))
+        raise AssertionError(f"{e}; {R.rec_where(miss, widths, p['shapes'])}") from None
+    _exact_stats(f"exact rec stage {k}", f"part {part}", stats)

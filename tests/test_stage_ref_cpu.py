@@ -8,6 +8,9 @@
 * the recogniser's conv stack likewise: the per-crop references composed are oracle.nets.CRNN's feature half, the wide-image model without a
   mistake is the per-crop reference (zero separators + the clears = crops that do not see each other), every named mistake of R.REC_MUTS fails
   the check that the GPU test of its stage applies, on that test's inputs, and the fp32 stand-in passes the rule on every range run there.
+* the exact mode's split-fp16 stages (second half): the pair coding and split weights, the exact detector's stages composed in its conv
+  table's order = oracle.nets.CRAFT, the conditions of R.EXACT_RULE (q32, model and stand-in inside the rule) on every GPU case's own input,
+  and one failing check per named mistake -- or the reason why a check cannot see it.
 """
 import os
 import shutil
@@ -334,3 +337,251 @@ def test_stage_shim_compiles(tmp_path):
                          "-c", os.path.join(ROOT, "tools", "micro", "stage_shim.hip"), "-o", str(tmp_path / "stage_shim.o")],
                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert cc.returncode == 0, cc.stdout.decode()[-2000:]
+
+
+# ================================================================================================ exact mode (split-fp16 stages)
+# Pins of the references, the conditions of R.EXACT_RULE on the GPU tests' own inputs, and one failing check per named mistake.
+@pytest.fixture(scope="module")
+def WX(craft_sd):
+    return R.Weights(craft_sd, "f32")
+
+
+def test_exact_stage_chain_is_the_oracle_craft(craft_sd):
+    """craft_forward_exact's order, the conv launches read from R.EXACT_CONVS row by row, is oracle.nets.CRAFT in double: this pins the
+    references AND the table's order (the GPU suite asserts that production's table is R.EXACT_CONVS)"""
+    from oracle import nets
+
+    rgb = _rgb(1, 90, 120, 1)
+    heat, u4b = R.exact_forward(R.Weights(craft_sd, None), rgb, 90, 120, 96, 128)
+    net = nets.load_state_dict_any(nets.CRAFT(), {k: torch.from_numpy(np.asarray(v)) for k, v in craft_sd.items()}).double().eval()
+    with torch.no_grad():
+        want, feat = net(R.normalise(rgb, 90, 120, 96, 128, None, False, torch.float64))
+    assert heat.shape == want.shape == (1, 48, 64, 2)
+    assert (u4b - feat).abs().max().item() <= 1e-9 * max(1.0, feat.abs().max().item())
+    assert (heat - want).abs().max().item() <= 1e-9
+
+
+def test_exact_recurrence_unsplit_is_torch_lstm():
+    torch.manual_seed(6)
+    rnn = torch.nn.LSTM(256, 256, bidirectional=True, batch_first=True).double()
+    x = torch.randn(3, 21, 256, dtype=torch.float64)
+    with torch.no_grad():
+        want, _ = rnn(x)
+        xp = torch.stack([x @ rnn.weight_ih_l0.t() + rnn.bias_ih_l0 + rnn.bias_hh_l0,
+                          x @ rnn.weight_ih_l0_reverse.t() + rnn.bias_ih_l0_reverse + rnn.bias_hh_l0_reverse], dim=2)
+        got = R.bilstm(rnn.weight_hh_l0, rnn.weight_hh_l0_reverse, xp, "exact", q=False)
+    assert (got - want).abs().max().item() <= 1e-12
+
+
+def test_pair_coding_round_trip():
+    g = torch.Generator().manual_seed(7)
+    for scale in (1e-3, 1.0, 300.0):
+        for lo_scale in (R.SPLIT_LO, 1.0):
+            v = (torch.randn(20000, generator=g) * scale).float()
+            hi, lo = R.pair_encode(v, lo_scale)
+            val = R.pair_value(hi, lo, lo_scale)
+            assert ((val - v.double()).abs() <= 2.0 ** -22 * v.double().abs() + (2.0 ** -35 if lo_scale > 1 else 2.0 ** -25)).all()
+            assert torch.equal(R.pair_value(hi, lo, lo_scale, torch.float32).double(), val)            # decoding in fp32 is exact
+            assert torch.equal(hi, v.half())
+    assert ((hi.float() > 0) & (lo.float() < 0)).any()
+
+
+def test_split_weights_are_upload_split_plans(WX):
+    w, _ = WX.layer("basenet.slice5.1")
+    s, hi, mid, lo = R.split_weights(w)
+    mx = float(w.abs().max()) * 2.0 ** s
+    assert 512 <= mx < 1024
+    assert ((hi + lo) * 2.0 ** -s - w).abs().max().item() <= 2.0 ** -22 * float(w.abs().max()) * 2       # w_hi + w_lo holds w 2^s to 2^-22 of the largest weight's binade
+    assert torch.equal(mid, (hi / 2048).half().double()) and torch.equal(R.split_weights(w, 1.0)[2], hi)
+
+
+CONV_MUTS = ["drop_a_lo", "drop_w_lo", "mid_unscaled", "no_acc_scale"]
+
+
+@pytest.mark.parametrize("name,shape,route", R.EXACT_CONV_CASES, ids=[f"{n}-{'x'.join(map(str, s))}" for n, s, _ in R.EXACT_CONV_CASES])
+def test_exact_conv_cases_conditions_and_mistakes(WX, name, shape, route):
+    """on the GPU test's own input of every table-row case: q32 <= 2^-22, model and stand-in pass the rule, and each of 'a_lo term dropped',
+    'w_lo term dropped', 'w_hi / 2048 block left unscaled', 'acc_scale not applied' -- on rows that pool: 'pooled value split before the
+    max' (the max then runs on hi and lo separately) -- fails it"""
+    _, outs = R.exact_conv_case(WX, name, shape)
+    for k, o in outs.items():
+        assert o["q32"] <= R.Q32_MAX, (k, o["q32"])
+        assert not R.split_fails(o["model"], o["ref"], o["S"], o["q32"], R.U_PAIR)
+        assert not R.split_fails(o["standin"], o["ref"], o["S"], o["q32"], R.U_PAIR)
+        assert float(((o["standin"] - o["ref"]).abs() / R.split_bound(o["ref"], o["S"], o["q32"], R.U_PAIR)).max()) <= 0.5      # inside half the bound
+    muts = CONV_MUTS + (["pool_split_first"] if "pool" in outs else [])
+    for mut in muts:
+        _, bad = R.exact_conv_case(WX, name, shape, mut=mut, cout=32)
+        keys = ["pool"] if mut == "pool_split_first" else list(outs)
+        for k in keys:
+            o = outs[k]
+            c = bad[k]["model"].shape[-1]
+            assert R.split_fails(bad[k]["model"], o["ref"][..., :c], o["S"][..., :c], o["q32"], R.U_PAIR), f"{name} {shape} {k}: '{mut}' stays inside the bound"
+            with pytest.raises(AssertionError):
+                R.split_check(bad[k]["model"], o["ref"][..., :c], o["S"][..., :c], o["q32"], R.U_PAIR, f"{name} {mut}")
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 2), (2, 15, 20), (1, 13, 6)])
+def test_exact_fc6_sub_lattice_mistakes(WX, shape):
+    """the sub-lattice path's own mistakes (R.fc6_phase_model), first 32 couts of the GPU test's fc6 cases.  Not visible BY CONSTRUCTION:
+    'row_beyond' on a one-page batch reads whatever lies behind the tensor (the model has zeros there: no statement), and 'page_offset'
+    needs a second page; 2x15x20 sees all three"""
+    a_pair, outs = R.exact_conv_case(WX, "fc6", shape)
+    o = outs["full"]
+    w, b = WX.layer("basenet.slice5.1")
+    x = R.nchw(R.pair_decode(a_pair))
+    assert (R.nhwc(R.fc6_phase_model(w[:32], b[:32], x)) - o["ref"][..., :32]).abs().max().item() <= 1e-9
+    visible = {"separator_nonzero"} | ({"row_beyond", "page_offset"} if shape[0] > 1 else set())
+    for mut in ("row_beyond", "separator_nonzero", "page_offset"):
+        bad = R.pair_roundtrip(R.nhwc(R.fc6_phase_model(w[:32], b[:32], x, mut)))
+        assert R.split_fails(bad, o["ref"][..., :32], o["S"][..., :32], o["q32"], R.U_PAIR) == (mut in visible), (mut, shape)
+
+
+@pytest.mark.parametrize("content", ["random", "zeros", "white"])
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("geom", R.C11_GEOMS)
+def test_exact_conv1_1_conditions_and_mistake(WX, geom, N, content):
+    """pair_conv1_1 on the GPU test's pages: q32 <= 2^-22, the float32 FMA chain passes the rule, and 'canvas beyond the page treated as
+    padding' fails it wherever the page is smaller than the canvas"""
+    Hi, Wi, H32, W32 = geom
+    rgb = R.c11_pages(geom, N, content)
+    if content == "random":
+        assert set(rgb.unique().tolist()) <= {0, 255} and (Hi * Wi == 1 or rgb.unique().numel() == 2)
+    r = R.exact_c11(WX, rgb, Hi, Wi, H32, W32)
+    q32 = R.split_q32(r["standin"], r["ref"], r["S"])
+    print(f"[stage] exact conv1_1 {geom} N={N} {content}: q32 {q32:.3g}")
+    assert q32 <= R.Q32_MAX
+    assert not R.split_fails(R.pair_roundtrip(r["standin"]), r["ref"], r["S"], q32, R.U_PAIR)
+    bad = R.exact_c11(WX, rgb, Hi, Wi, H32, W32, "canvas_as_padding")
+    assert R.split_fails(R.pair_roundtrip(bad["standin"]), r["ref"], r["S"], q32, R.U_PAIR) == ((Hi, Wi) != (H32, W32))
+
+
+@pytest.mark.parametrize("shape,scale", [((1, 16, 16), 1.0), ((2, 40, 56), 1.0), ((2, 40, 56), 6.0)])
+def test_exact_cls_tail_conditions(WX, shape, scale):
+    c3 = R.pair_pack(torch.randn(shape + (16,), generator=torch.Generator().manual_seed(600)).abs() * scale)
+    r = R.exact_cls_tail(WX, c3)
+    q32 = R.split_q32(r["standin"], r["ref"], r["S"])
+    assert q32 <= R.Q32_MAX
+    assert not R.split_fails(r["standin"], r["ref"], r["S"], q32, R.U_F32)
+    half = R.pair_halves(c3)[0].double()                                   # the lo half of the input ignored
+    sd = WX.sd
+    f = lambda k: torch.from_numpy(np.asarray(sd[k]).astype(np.float64))
+    hid = F.relu(half @ f("conv_cls.6.weight").reshape(16, 16).t() + f("conv_cls.6.bias"))
+    assert R.split_fails(hid @ f("conv_cls.8.weight").reshape(2, 16).t() + f("conv_cls.8.bias"), r["ref"], r["S"], q32, R.U_F32)
+    if scale > 1:           # the pushed case: the tail's ReLU clips a sizeable share
+        pre = R.pair_decode(c3) @ f("conv_cls.6.weight").reshape(16, 16).t() + f("conv_cls.6.bias")
+        assert 0.2 < float((pre < 0).double().mean()) < 0.8
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 2), (2, 6, 10), (1, 30, 40)])
+def test_exact_selection_kernels_mistakes(shape):
+    """ReLU / max-pool taken on hi and lo separately differ from the selection on the value, bit-wise, on the GPU test's planes; and on the
+    plane of ONE hi the maximum by hi alone (first pixel of the window) is never the maximum by value"""
+    x = R.pair_plane(shape, 700)
+    v = R.pair_decode(x)
+    for fn in (R.pair_relu, R.pair_pool5):
+        want = fn(x)
+        assert not torch.equal(fn(x, "halves").view(torch.int16), want.view(torch.int16))
+    assert torch.equal(R.pair_decode(R.pair_relu(x)), torch.clamp(v, min=0))
+    pooled = R.nhwc(F.max_pool2d(R.nchw(v), 3, 1, 1))
+    assert torch.equal(R.pair_decode(R.pair_pool5(x)), pooled)
+    first = R.nhwc(-F.max_pool2d(-R.nchw(v), 3, 1, 1))[..., 0]                # channel 0 grows along the scan order: a window's first pixel is its minimum
+    assert (pooled[..., 0] > first).all()
+
+
+def test_exact_upcat_mistakes():
+    g = torch.Generator().manual_seed(720)
+    for (N, h, w), (Cy, Cs) in (((1, 1, 1), (256, 512)), ((2, 3, 5), (128, 256)), ((1, 20, 28), (64, 128))):
+        y = R.pair_pack(torch.randn((N, h, w, Cy), generator=g) * 3)
+        sk = R.pair_pack(torch.randn((N, 2 * h, 2 * w, Cs), generator=g) * 3)
+        ref, blend = R.pair_upcat_up(y)
+        bound = R.upcat_up_bound(ref, blend)
+        v32 = R.nchw(R.pair_decode(y, dt=torch.float32))
+        standin = R.pair_roundtrip(R.nhwc(F.interpolate(v32, scale_factor=2, mode="bilinear", align_corners=False)))
+        assert ((standin - ref).abs() <= bound).all()
+        for mut in ("edge_unclamped", "src_unclamped"):
+            bad = R.pair_roundtrip(R.pair_upcat_up(y, mut)[0])
+            # a 1 x 1 source has no neighbour to take by mistake: both mistakes are invisible there by construction
+            assert bool(((bad - ref).abs() > bound).any()) == ((h, w) != (1, 1)), (mut, h, w)
+    for shape in ((1, 2, 2), (2, 3, 5)):                     # the same-size cases' own inputs
+        a, b = R.upcat_same_inputs(shape)
+        assert not torch.equal(R.pair_upcat_same(a, b, "halves_swapped").view(torch.int16), R.pair_upcat_same(a, b).view(torch.int16))
+
+
+SEQ_CASES = [(0, 0), (0, 1), (1, 0), (1, 1), (2, 0)]
+
+
+@pytest.mark.parametrize("which,layer", SEQ_CASES)
+def test_exact_sequence_gemm_conditions_and_mistakes(crnn_sd3, which, layer):
+    """the GPU test's inputs of xproj / lin / pred (the xproj permutation only renames output channels: the identity here)"""
+    w, b, lo_scale = R.seq_gemm_weights(crnn_sd3, which, layer, torch.arange(2048))
+    K = w.shape[1]
+    g = torch.Generator().manual_seed(860 + 10 * which + layer)
+    v = torch.randn((512, K), generator=g)
+    v = torch.tanh(v) if which == 1 else v
+    v[300:] = 0
+    a = R.pair_pack(v, lo_scale).reshape(1, 2, 256, 2 * K)
+    u = R.U_PAIR if which == 1 else R.U_F32
+    store = (lambda t: R.pair_roundtrip(t)) if which == 1 else (lambda t: t.float().double())
+    pre = R.split_conv(w, b, a, lo_scale=lo_scale)
+    q32 = R.split_q32(pre["standin"], pre["ref"], pre["S"])
+    assert q32 <= R.Q32_MAX
+    for k in ("model", "standin"):
+        assert not R.split_fails(store(pre[k]), pre["ref"], pre["S"], q32, u)
+    # lin: packed with lo_scale 1, its "w_hi / lo_scale" block IS w_hi ('mid_unscaled' is the convention there); its mistake is lo_scale 2048
+    muts = [dict(mut=m) for m in CONV_MUTS if not (which == 1 and m == "mid_unscaled")] + ([dict(w_lo_scale=R.SPLIT_LO)] if which == 1 else [])
+    for kw in muts:
+        bad = R.split_conv(w, b, a, lo_scale=lo_scale, **kw)
+        assert R.split_fails(store(bad["model"]), pre["ref"], pre["S"], q32, u), kw
+
+
+@pytest.fixture(scope="module")
+def crnn_sd3():
+    from bb_ocr_amd import weights
+
+    return weights.synthetic_crnn_state(3)             # the state of the GPU suite's readers
+
+
+@pytest.mark.parametrize("sigma", [1.5, 0.3])
+@pytest.mark.parametrize("layer", [0, 1])
+def test_exact_recurrence_rule_and_mistakes(crnn_sd3, layer, sigma):
+    """every tile of the GPU test (tile capacity 16): the float32 split stand-in stays inside the bound, and these exceed it: h_lo dropped, the
+    backward direction's time index off by one, the cell state carried into the next tile, the output's lo half scaled by 2048.  'A sequence
+    index >= n writing its clamped row' is not visible in values BY CONSTRUCTION (the surplus lanes of a tile read sequence n - 1's input and
+    compute sequence n - 1's values: writing them to its rows changes nothing); written to their OWN rows they land behind the tile, which
+    the GPU test's NaN rows behind the last tile (5 < cap sequences) and its tile-alone comparison see"""
+    wf, wb = R.lstm_weights(crnn_sd3, layer, "exact")
+    prev_c = None
+    for x in R.exact_lstm_inputs(16, layer, sigma):
+        model, ref, bound = R.refs_bilstm(wf, wb, x, "exact")
+        worst = lambda t: float((t - ref).abs().max())
+        cs = []
+        assert worst(model) <= bound
+        assert worst(R.bilstm(wf, wb, x, "exact", True, torch.float32, c_out=cs)) <= bound
+        for mut in ("h_lo_dropped", "bwd_t_off_by_one"):
+            assert worst(R.bilstm(wf, wb, x, "exact", mut=mut)) > bound, mut
+        if prev_c is not None:
+            c0 = tuple(c[:1].expand(x.shape[0], -1).double() for c in prev_c)
+            assert worst(R.bilstm(wf, wb, x, "exact", c0=c0)) > bound
+        prev_c = cs[0]
+        hi, lo = R.pair_encode(model.float(), 1.0)
+        assert worst(R.pair_value(hi, (lo.float() * 2048).half(), 1.0)) > bound            # lo stored x 2048, decoded with scale 1
+
+
+@pytest.mark.parametrize("part", ["A", "B"])
+@pytest.mark.parametrize("k", range(8))
+def test_exact_rec_stage_conditions(crnn_sd3, k, part):
+    """every stage of the recogniser's conv stack alone, on the GPU test's parts: q32 <= 2^-22, model and stand-in inside the rule, the per-crop
+    reference is rec_stage (the fast modes' reference of the same stage), and a dropped lo term fails the split stages"""
+    W = R.Weights(crnn_sd3, "f32")
+    widths = {"A": R.REC_PART_A, "B": R.REC_PART_B}[part]
+    xs = R.exact_rec_inputs(widths, k)
+    p = R.exact_rec_part(W, k, xs)
+    assert p["q32"] <= R.Q32_MAX, p["q32"]
+    for n in ("model", "standin"):
+        assert not R.split_fails(p[n], p["ref"], p["S"], p["q32"], R.U_PAIR), n
+    x0 = xs[0] if k == 0 else R.pair_decode(xs[0])
+    assert (R.rec_stage(W, k, x0).reshape(-1) - R.exact_rec_stage(W, k, xs[0])["ref"].reshape(-1)).abs().max().item() <= 1e-12
+    if 1 <= k <= 6 and part == "B":
+        for mut in ("drop_a_lo", "drop_w_lo"):
+            assert R.split_fails(R.exact_rec_part(W, k, xs, mut)["model"], p["ref"], p["S"], p["q32"], R.U_PAIR), mut

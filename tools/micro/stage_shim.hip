@@ -1,5 +1,5 @@
-// Test-only shim (tests/test_gpu_stages.py): runs ONE stage of the fast-mode detector / recogniser with the production plans and packed side
-// tables of a live context, so that each fused launch can be compared with an fp64 reference of its own operation (tests/stage_ref.py).
+// Test-only shim (tests/test_gpu_stages.py): runs ONE stage of the detector / recogniser (fast modes, and the exact mode's split-fp16 stages)
+// with the production plans and packed side tables of a live context, so that each fused launch can be compared with an fp64 reference of its own operation (tests/stage_ref.py).
 // stage_rec_features runs any range of the stages of the recogniser's conv stack (crnn_features_stages, the function a recognition pass runs).
 // No kernels of its own.  Built by the test as a shared object against the in-tree library:
 //   hipcc -O2 -std=c++20 -shared -fPIC --offload-arch=gfx950 -Ibb-ocr_amd/csrc -Iinclude tools/micro/stage_shim.hip -Lbb-ocr_amd -lbbocr -o stage_shim.so
@@ -38,6 +38,7 @@ template <typename F> int run_stage(bbocr_ctx* c, F&& f) {
 }
 
 bool fast_detector(const bbocr_ctx* c) { return c->craft_loaded && !det_split(c); }
+bool exact_detector(const bbocr_ctx* c) { return c->craft_loaded && det_split(c); }
 size_t px(int N, int H, int W) { return (size_t)N * H * W; }
 bool dims_ok(int N, int H, int W) { return N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 26); }
 #define NEED(cond)                                                         \
@@ -188,10 +189,106 @@ int stage_pool5(bbocr_ctx* c, const uint16_t* in, size_t in_elems, int N, int H,
     });
 }
 
+// ------------------------------------------------------------------------------------------------ exact mode (split-fp16 plans, pair tensors)
+// The stage functions and the conv table of craft_forward_exact (detector.cpp) on a live exact context.  Pair tensors [.., C | C] are passed
+// with BOTH halves counted in their element counts.
+int stage_exact_rows() { return craft_exact_rows(); }
+// row of the table: name (up to 15 characters) and {logical Cin, relu_out, store, pool mode, pool_relu, keep_full, K, dilation}
+int stage_exact_row_info(bbocr_ctx* c, int row, char* name16, int* info8) {
+    g_err.clear();
+    NEED(c && exact_detector(c) && name16 && info8 && row >= 0 && row < craft_exact_rows());
+    const ExactConvRow& r = craft_exact_row(row);
+    const ConvPlan& p = c->*(r.plan);
+    NEED(p.split && p.KH == p.KW);
+    snprintf(name16, 16, "%s", r.name);
+    const int v[8] = {p.Cin / 3, r.relu_out, r.store, r.pool_mode, r.pool_relu, r.keep_full, p.KH, p.dil};
+    std::copy(v, v + 8, info8);
+    return 0;
+}
+
+// row `row` on the pair tensor in [N, H, W, Cin | Cin] -> out: the row's (pooled, if it pools) output pair; full: the un-pooled pair of a
+// row that keeps it (null / 0 otherwise)
+int stage_exact_conv(bbocr_ctx* c, int row, const uint16_t* in, size_t in_elems, int N, int H, int W, uint16_t* out, size_t out_elems, uint16_t* full,
+                     size_t full_elems) {
+    NEED(c && exact_detector(c) && in && out && dims_ok(N, H, W) && row >= 0 && row < craft_exact_rows());
+    const ExactConvRow& r = craft_exact_row(row);
+    const ConvPlan& p = c->*(r.plan);
+    NEED(p.split && in_elems == px(N, H, W) * 2 * (size_t)(p.Cin / 3));
+    const int OH = H + 2 * p.pad_h - (p.KH - 1) * p.dil, OW = W + 2 * p.pad_w - (p.KW - 1) * p.dil;
+    NEED(OH > 0 && OW > 0 && (!r.pool_mode || (OH % 2 == 0 && OW % 2 == 0)));
+    NEED(out_elems == (r.pool_mode ? px(N, OH / 2, OW / 2) : px(N, OH, OW)) * 2 * (size_t)r.store);
+    NEED(r.keep_full ? (full && full_elems == px(N, OH, OW) * 2 * (size_t)r.store) : (!full && !full_elems));
+    return run_stage(c, [&] {
+        Act f{};
+        const Act a{(uint16_t*)in, N, H, W, 2 * (p.Cin / 3)};
+        const hipError_t e = with_arena(c, out, out_elems, [&] { return craft_exact_conv(c, row, a, r.keep_full ? &f : nullptr); });
+        if (e != hipSuccess || !r.keep_full) return e;
+        if (act_elems(f) != full_elems) fail(BBOCR_ERR_INTERNAL, "stage shim: full output size differs from the caller's tensor");
+        return hipMemcpyAsync(full, f.p, full_elems * 2, hipMemcpyDeviceToDevice, c->stream);
+    });
+}
+
+// normalise + conv1_1 + BN + ReLU in fp32: rgb uint8 [N, Himg, Wimg, 3] on the zero canvas H32 x W32 -> out pair [N, H32, W32, 64 | 64]
+int stage_exact_conv1_1(bbocr_ctx* c, const uint8_t* rgb, size_t rgb_elems, int N, int Himg, int Wimg, int H32, int W32, uint16_t* out, size_t out_elems) {
+    NEED(c && exact_detector(c) && rgb && out && dims_ok(N, H32, W32) && Himg > 0 && Wimg > 0 && Himg <= H32 && Wimg <= W32);
+    NEED(rgb_elems == px(N, Himg, Wimg) * 3 && out_elems == px(N, H32, W32) * 128);
+    return run_stage(c, [&] { return with_arena(c, out, out_elems, [&] { return craft_exact_conv1_1(c, rgb, N, Himg, Wimg, H32, W32); }); });
+}
+
+// ReLU on the pair values: in / out [N, H, W, C | C]
+int stage_exact_relu(bbocr_ctx* c, const uint16_t* in, size_t in_elems, int N, int H, int W, int C, uint16_t* out, size_t out_elems) {
+    NEED(c && exact_detector(c) && in && out && dims_ok(N, H, W) && C > 0 && C % 8 == 0 && in_elems == px(N, H, W) * 2 * (size_t)C && out_elems == in_elems);
+    return run_stage(c, [&] { return with_arena(c, out, out_elems, [&] { return craft_exact_relu(c, Act{(uint16_t*)in, N, H, W, 2 * C}); }); });
+}
+
+// MaxPool2d(3, 1, 1) on the pair values: in / out [N, H, W, C | C]
+int stage_exact_pool5(bbocr_ctx* c, const uint16_t* in, size_t in_elems, int N, int H, int W, int C, uint16_t* out, size_t out_elems) {
+    NEED(c && exact_detector(c) && in && out && dims_ok(N, H, W) && C > 0 && C % 8 == 0 && in_elems == px(N, H, W) * 2 * (size_t)C && out_elems == in_elems);
+    return run_stage(c, [&] { return with_arena(c, out, out_elems, [&] { return craft_exact_pool5(c, Act{(uint16_t*)in, N, H, W, 2 * C}); }); });
+}
+
+// cat([interpolate(y), skip]): y pair [N, yh, yw, Cy | Cy] (the skip's size, or half of it), skip pair [N, H, W, Cs | Cs] -> out pair [N, H, W, Cy + Cs | Cy + Cs]
+int stage_exact_upcat(bbocr_ctx* c, const uint16_t* y, size_t y_elems, int yh, int yw, int Cy, const uint16_t* skip, size_t skip_elems, int Cs, int N, int H,
+                      int W, uint16_t* out, size_t out_elems) {
+    NEED(c && exact_detector(c) && y && skip && out && dims_ok(N, H, W) && Cy > 0 && Cs > 0 && Cy % 8 == 0 && Cs % 8 == 0);
+    NEED((yh == H && yw == W) || (2 * yh == H && 2 * yw == W));
+    NEED(y_elems == px(N, yh, yw) * 2 * (size_t)Cy && skip_elems == px(N, H, W) * 2 * (size_t)Cs && out_elems == px(N, H, W) * 2 * (size_t)(Cy + Cs));
+    return run_stage(c, [&] {
+        return with_arena(c, out, out_elems, [&] { return craft_exact_upcat(c, Act{(uint16_t*)y, N, yh, yw, 2 * Cy}, Act{(uint16_t*)skip, N, H, W, 2 * Cs}); });
+    });
+}
+
+// conv_cls.6 + ReLU + conv_cls.8 in fp32: c3 pair [N, H, W, 16 | 16] -> heat fp32 [N, H, W, 2]
+int stage_exact_cls_tail(bbocr_ctx* c, const uint16_t* c3, size_t c3_elems, int N, int H, int W, float* heat, size_t heat_elems) {
+    NEED(c && exact_detector(c) && c3 && heat && dims_ok(N, H, W) && c3_elems == px(N, H, W) * 32 && heat_elems == px(N, H, W) * 2);
+    return run_stage(c, [&] {
+        c->arena.begin(false);                    // nothing is carved from the arena here
+        craft_exact_cls_tail(c, Act{(uint16_t*)c3, N, H, W, 32}, heat);
+        return hipSuccess;
+    });
+}
+
+// One GEMM of the sequence half (crnn_sequence's own helpers) on a live exact context, rows_pad rows (a multiple of 256):
+// which 0: xproj[layer], x pair [rows_pad, 256 | 256] -> fp32 [rows_pad, 2048];  1: lin[layer], h pair [rows_pad, 512 | 512] with the lo
+// half UNSCALED -> pair [rows_pad, 256 | 256];  2: pred, x pair [rows_pad, 256 | 256] -> fp32 [rows_pad, 112]
+int stage_exact_seq_gemm(bbocr_ctx* c, int which, int layer, const uint16_t* in, size_t in_elems, size_t rows_pad, void* out, size_t out_elems) {
+    NEED(c && c->crnn_loaded && rec_split(c) && !rec_quant(c) && which >= 0 && which <= 2 && (layer == 0 || layer == 1) && in && out);
+    NEED(rows_pad > 0 && rows_pad % 256 == 0 && rows_pad < ((size_t)1 << 22));
+    NEED(in_elems == rows_pad * (which == 1 ? 1024 : 512) && out_elems == rows_pad * (which == 0 ? 2048 : (which == 1 ? 512 : 112)));
+    return run_stage(c, [&] {
+        c->arena.begin(false);                    // run_conv is a no-op in a dry pass; nothing is carved from the arena here
+        if (which == 0) crnn_seq_xproj(c, layer, in, rows_pad, out);
+        else if (which == 1) crnn_seq_lin(c, layer, in, rows_pad, (uint16_t*)out);
+        else crnn_seq_pred(c, in, rows_pad, (float*)out);
+        return hipSuccess;
+    });
+}
+
 // BiLSTM recurrence of layer l over a tile table given on the HOST (int4 {first row, sequences, T, 0} per workgroup): xproj [rows_pad, 2048]
 // in the permuted channel order, out [rows_pad, 512] (fwd | bwd).  rows_pad: a multiple of 256, as the sequence stage allocates.
-int stage_lstm(bbocr_ctx* c, int layer, const uint16_t* xproj, uint16_t* out, size_t rows_pad, const int* tiles_host, int ntiles) {
-    NEED(c && c->crnn_loaded && !rec_split(c) && (layer == 0 || layer == 1) && c->whh[layer] && xproj && out && tiles_host && ntiles > 0 && ntiles <= 65535);
+// Exact mode: xproj is FP32 [rows_pad, 2048] and out the pair [rows_pad, 512 | 512] with the lo half unscaled (twice the bytes each).
+int stage_lstm(bbocr_ctx* c, int layer, const void* xproj, uint16_t* out, size_t rows_pad, const int* tiles_host, int ntiles) {
+    NEED(c && c->crnn_loaded && !rec_quant(c) && (layer == 0 || layer == 1) && c->whh[layer] && xproj && out && tiles_host && ntiles > 0 && ntiles <= 65535);
     NEED(rows_pad > 0 && rows_pad % 256 == 0 && rows_pad < ((size_t)1 << 24));
     const int cap = lstm_tile_seqs(rec_mode(c));
     for (int i = 0; i < ntiles; ++i) {
