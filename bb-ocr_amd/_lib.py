@@ -154,6 +154,12 @@ PROTOTYPES = {
     "bbocr_page_orient": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int)]),
     "bbocr_op_jpeg_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_jpeg_decode_scaled": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "bbocr_jpeg_scaled_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_op_jpeg_scaled_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_thumbnail_box": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
+    "bbocr_host_resize_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "bbocr_jpeg_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "bbocr_host_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bbocr_jpeg_encode": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t,

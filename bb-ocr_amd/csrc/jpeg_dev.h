@@ -44,6 +44,40 @@ __device__ __forceinline__ void idct8(int* v, int s, bool first) {
     }
 }
 
+// ---- libjpeg's reduced-size inverse transforms (jidctred.c), which a decode at scale 1/2, 1/4 or 1/8 runs: one 1-D pass over the eight
+// inputs v[0], v[s], ..., v[7 s] that leaves its N outputs in v[0], ..., v[(N - 1) s].  The first (column) pass descales to PASS1_BITS
+// fraction bits; the second (row) pass returns the samples through the post-IDCT range-limit table.
+__device__ __forceinline__ int jd_range_limit(long long x) {
+    const int r = (int)x & 1023;                                        // RANGE_MASK
+    return r < 128 ? r + 128 : (r < 512 ? 255 : (r < 896 ? 0 : r - 896));
+}
+
+// jpeg_idct_4x4: input 4 is never read
+__device__ __forceinline__ void idct4(int* v, int s, bool first) {
+    const long long i0 = v[0], i1 = v[s], i2 = v[2 * s], i3 = v[3 * s], i5 = v[5 * s], i6 = v[6 * s], i7 = v[7 * s];
+    const long long t0 = i0 << (CB + 1), t2 = i2 * F1847 - i6 * F0765;
+    const long long t10 = t0 + t2, t12 = t0 - t2;
+    const long long oa = -i7 * 1730 + i5 * 11893 - i3 * 17799 + i1 * 8697;      // FIX 0.211164243, 1.451774981, 2.172734803, 1.061594337
+    const long long ob = -i7 * 4176 - i5 * 4926 + i3 * F0899 + i1 * F2562;      // FIX 0.509795579, 0.601344887, 0.899976223, 2.562915447
+    const int sh = first ? CB - P1 + 1 : CB + P1 + 3 + 1;
+    const long long o[4] = {dsc(t10 + ob, sh), dsc(t12 + oa, sh), dsc(t12 - oa, sh), dsc(t10 - ob, sh)};
+    for (int i = 0; i < 4; ++i) v[i * s] = first ? (int)o[i] : jd_range_limit(o[i]);
+}
+
+// jpeg_idct_2x2: inputs 2, 4 and 6 are never read
+__device__ __forceinline__ void idct2(int* v, int s, bool first) {
+    const long long t10 = (long long)v[0] << (CB + 2);
+    const long long t0 = -(long long)v[7 * s] * 5906 + (long long)v[5 * s] * 6967 - (long long)v[3 * s] * 10426 +
+                         (long long)v[s] * 29692;                                // FIX 0.720959822, 0.850430095, 1.272758580, 3.624509785
+    const int sh = first ? CB - P1 + 2 : CB + P1 + 3 + 2;
+    const long long a = dsc(t10 + t0, sh), b = dsc(t10 - t0, sh);
+    v[0] = first ? (int)a : jd_range_limit(a);
+    v[s] = first ? (int)b : jd_range_limit(b);
+}
+
+// jpeg_idct_1x1 of the dequantised DC term
+__device__ __forceinline__ int idct1(int dc) { return jd_range_limit(dsc((long long)dc, 3)); }
+
 // ---- jfdctint.c
 // one 1-D forward pass over v[0], v[s], ..., v[7 s]
 __device__ __forceinline__ void fdct8(int* v, int s, bool first) {

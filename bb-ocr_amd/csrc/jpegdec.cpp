@@ -1,6 +1,8 @@
 // Baseline JPEG decoding, host side: the marker parser (bbocr_host_jpeg_plan: one linear pass, no entropy bit decoded), the per-batch
 // tables of jpegdec.hip (unstuffed segment bytes, subsequence lists, derived Huffman tables) and its launch sequence.  A batch runs on
 // its own stream of the root context, outside the call slots (the contract of bbocr_upload_pages): files decode while two OCR calls run.
+// A batch may be decoded at scale 1/2, 1/4 or 1/8 (bbocr_jpeg_decode_scaled, Pillow's draft): same tables and entropy stages, planes of
+// the output's size, jpegdec.hip's scaled IDCT and output kernels; 4:2:0 and grey files only.
 #include "ctx.h"
 
 namespace {
@@ -238,6 +240,13 @@ int luma_v(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? pl.sampling[
 // bytes of the Y plane and of one chroma plane before upsampling (whole MCUs)
 size_t luma_plane_bytes(const bbocr_jpeg_plan& pl) { return (size_t)pl.mcu_cols * 8 * luma_h(pl) * (size_t)pl.mcu_rows * 8 * luma_v(pl); }
 size_t chroma_plane_bytes(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? (size_t)pl.mcu_cols * 8 * (size_t)pl.mcu_rows * 8 : 0; }
+// A decode at scale 1 / s (s 2, 4 or 8; 4:2:0 and grey files): every plane has the output's size in whole MCUs, rows of scaled_plane_w
+// samples -- an MCU is 16 / s samples wide and high in each plane of a 4:2:0 file, 8 / s in a grey file's
+bool jpeg_scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+int scaled_mcu_edge(const bbocr_jpeg_plan& pl, int s) { return (pl.components == 3 ? 16 : 8) / s; }
+size_t scaled_plane_w(const bbocr_jpeg_plan& pl, int s) { return (size_t)pl.mcu_cols * scaled_mcu_edge(pl, s); }
+size_t scaled_plane_bytes(const bbocr_jpeg_plan& pl, int s) { return scaled_plane_w(pl, s) * (size_t)pl.mcu_rows * scaled_mcu_edge(pl, s); }
+int scaled_dim(int v, int s) { return (v + s - 1) / s; }
 
 // jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
 bool derive_table(const HuffSpec& h, JpegHuff& t) {
@@ -276,8 +285,10 @@ struct FileJob {                              // one admitted file of a batch
 
 // Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan neither supports nor gives a chroma
 // class (the caller plans first: a refused file is its error); every other file becomes a job once dest(job) -- the entry point's own rule -- has checked the caller's
-// destination and set the job's `out` and `pitch` (false: refused like the others).
-template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* files, const size_t* bytes, int n, int* status, D&& dest) {
+// destination and set the job's `out` and `pitch` (false: refused like the others).  chroma_classes false (a scaled decode): only the
+// files the plan supports, 4:2:0 and grey.
+template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* files, const size_t* bytes, int n, int* status, D&& dest,
+                                                       bool chroma_classes = true) {
     std::vector<FileJob> jobs;
     jobs.reserve((size_t)n);
     for (int k = 0; k < n; ++k) {
@@ -285,7 +296,7 @@ template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* file
         if (!files[k] || bytes[k] >= ((size_t)1 << 28)) continue;
         FileJob j;
         jpeg_parse(files[k], bytes[k], j.ps, true);
-        if (!jpeg_taken(j.ps.plan)) continue;
+        if (!jpeg_taken(j.ps.plan) || (!chroma_classes && !j.ps.plan.supported)) continue;
         j.file = files[k];
         j.k = k;
         if (dest(j)) jobs.push_back(std::move(j));
@@ -300,8 +311,9 @@ void jpeg_report(const std::vector<FileJob>& jobs, const std::vector<int>& dev_s
 
 // The whole decode of the admitted jobs on the JPEG lane's stream `st`; px: bytes per pixel of a 3-component file's output.  Fills
 // dev_status[i] (JD_ERR_* bits of job i) and leaves the descriptors for the stage entry point.  Everything queued is finished on return.
+// scale 2, 4 or 8: the decode at that fraction (the jobs are 4:2:0 or grey files; `out` holds the scaled size).
 void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S, int px, std::vector<int>& dev_status,
-              std::vector<JpegDesc>* descs_out = nullptr) {
+              std::vector<JpegDesc>* descs_out = nullptr, int scale = 1) {
     const int n = (int)jobs.size();
     Carve in{align_up(sizeof(JpegDesc) * (size_t)n, 256)}, work{align_up(4 * (size_t)n, 256)}, coef;
     int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;
@@ -317,8 +329,8 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? luma_h(pl) * luma_v(pl) + 2 : 1);
         max_seg = std::max(max_seg, pl.segments);
         max_blocks = std::max(max_blocks, j.nblocks);
-        max_h = std::max(max_h, pl.height);
-        max_w = std::max(max_w, pl.width);
+        max_h = std::max(max_h, scaled_dim(pl.height, scale));
+        max_w = std::max(max_w, scaled_dim(pl.width, scale));
     }
     root->jd_pin.ensure(in.off);
     root->jd_in.ensure(in.off);
@@ -366,9 +378,9 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.w_count = work.add(4 * (size_t)nsub);
         j.w_scan = work.add(4 * (size_t)nsub);
         j.w_first = work.add(4 * (size_t)nsub);
-        j.w_plane[0] = work.add(luma_plane_bytes(pl));
-        j.w_plane[1] = work.add(chroma_plane_bytes(pl));
-        j.w_plane[2] = work.add(chroma_plane_bytes(pl));
+        j.w_plane[0] = work.add(scale == 1 ? luma_plane_bytes(pl) : scaled_plane_bytes(pl, scale));
+        j.w_plane[1] = work.add(scale == 1 ? chroma_plane_bytes(pl) : (pl.components == 3 ? scaled_plane_bytes(pl, scale) : 0));
+        j.w_plane[2] = work.add(scale == 1 ? chroma_plane_bytes(pl) : (pl.components == 3 ? scaled_plane_bytes(pl, scale) : 0));
         j.o_coef = coef.add((size_t)j.nblocks * 128);
     }
     const int passes = max_groups + 1;
@@ -428,8 +440,13 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     HIPCHK(launch_jd_scan(dd, n, st));
     HIPCHK(launch_jd_write(dd, n, max_groups, st));
     HIPCHK(launch_jd_dc(dd, n, max_seg, st));
-    HIPCHK(launch_jd_idct(dd, n, max_blocks, st));
-    HIPCHK(launch_jd_output(dd, n, max_h, max_w, st));
+    if (scale == 1) {
+        HIPCHK(launch_jd_idct(dd, n, max_blocks, st));
+        HIPCHK(launch_jd_output(dd, n, max_h, max_w, st));
+    } else {
+        HIPCHK(launch_jd_idct_scaled(dd, n, max_blocks, scale, st));
+        HIPCHK(launch_jd_output_scaled(dd, n, max_h, max_w, scale, st));
+    }
     dev_status.assign((size_t)n, 0);
     HIPCHK(hipMemcpyAsync(dev_status.data(), wb, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -448,22 +465,35 @@ int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* pla
     return BBOCR_OK;
 }
 
-int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, uint8_t* const* dev_out,
-                      const long long* pitches, int* status) {
+int bbocr_jpeg_decode_scaled(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, int scale,
+                             uint8_t* const* dev_out, const long long* pitches, int* status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
         if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
         if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
+        if (!jpeg_scale_ok(scale)) fail(BBOCR_ERR_ARG, "scale must be 1, 2, 4 or 8");
         std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
             const bbocr_jpeg_plan& pl = j.ps.plan;
             j.out = dev_out[j.k];
             j.pitch = pitches[j.k];
-            return j.out && j.pitch >= (long long)pl.width * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY);
-        });
+            return j.out && j.pitch >= (long long)scaled_dim(pl.width, scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY);
+        }, scale == 1);
         if (jobs.empty()) return;
         std::vector<int> ds;
-        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, page_px_bytes(layout), ds);
+        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, page_px_bytes(layout), ds, nullptr, scale);
         jpeg_report(jobs, ds, status);
     });
+}
+
+int bbocr_jpeg_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, uint8_t* const* dev_out,
+                      const long long* pitches, int* status) {
+    return bbocr_jpeg_decode_scaled(ctx, files, bytes, n, layout, 1, dev_out, pitches, status);
+}
+
+int bbocr_jpeg_scaled_dims(int H, int W, int scale, int* out_h, int* out_w) {
+    if (H < 1 || W < 1 || !jpeg_scale_ok(scale) || !out_h || !out_w) return BBOCR_ERR_ARG;
+    *out_h = scaled_dim(H, scale);
+    *out_w = scaled_dim(W, scale);
+    return BBOCR_OK;
 }
 
 int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dev_out, const long long* pitches,
@@ -548,6 +578,37 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
                 HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz + csz, d.plane[2], csz, hipMemcpyDeviceToDevice, s));
             }
         }
+        HIPCHK(hipStreamSynchronize(s));
+    });
+}
+
+int bbocr_op_jpeg_scaled_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
+                               int* file_status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
+        if (!file || !dev_dst || (stage != 2 && stage != 3) || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
+        if (scale != 2 && scale != 4 && scale != 8) fail(BBOCR_ERR_ARG, "scale must be 2, 4 or 8");
+        int status = 0;
+        std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            const size_t pix = (size_t)scaled_dim(pl.width, scale) * scaled_dim(pl.height, scale) * pl.components;
+            if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
+            ctx->jd_stage.ensure(pix);
+            j.out = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+            j.pitch = (long long)scaled_dim(pl.width, scale) * pl.components;
+            return true;
+        }, false);
+        if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file, or it is of a chroma class");
+        const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
+        const size_t psz = scaled_plane_bytes(pl, scale);
+        if (stage == 2 && dst_bytes < psz * pl.components) fail(BBOCR_ERR_ARG, "destination too small");
+        std::vector<int> ds;
+        std::vector<JpegDesc> descs;
+        jpeg_run(ctx, s, jobs, JD_SUBSEQ_BITS, 3, ds, &descs, scale);
+        jpeg_report(jobs, ds, &status);
+        if (file_status) *file_status = status;
+        if (stage == 2)
+            for (int c = 0; c < pl.components; ++c)
+                HIPCHK(hipMemcpyAsync((char*)dev_dst + psz * c, descs[0].plane[c], psz, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
     });
 }

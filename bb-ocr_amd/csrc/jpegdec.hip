@@ -10,6 +10,8 @@
 //   jd_idct     dequantise + jidctint.c per block into the component planes
 //   jd_output   fancy upsampling by sampling class (h2v2, h2v1, h1v2, none) -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane,
 //               into the caller's tensor
+//   jd_idct_scaled / jd_output_scaled   the same two stages of a decode at scale 1/2, 1/4 or 1/8 (Pillow's draft): jidctred.c's reduced
+//               IDCTs per component, no upsampling (4:2:0 and grey files only)
 // An MCU holds hs x vs luma blocks (row after row), then one Cb and one Cr block: 2 x 2 for 4:2:0, 1 x 1 / 2 x 1 / 1 x 2 for the others.
 // The bytes are untrusted: every stream read is clamped to its segment (past the end: 1-bits), every store is index-checked, every loop
 // has a trip count fixed by the host's plan (S, lanes per workgroup, items per segment).
@@ -332,6 +334,95 @@ __global__ void __launch_bounds__(256) jd_output_kernel(const JpegDesc* __restri
     if (d.px == 4) o[3] = 255;
 }
 
+// ---- the decode at scale 1 / SC (SC 2, 4 or 8: libjpeg's scale_num / scale_denom, Pillow's draft): jdmaster.c gives every component its
+// own DCT_scaled_size -- luma blocks come out n x n with n = 8 / SC, the chroma blocks of a 4:2:0 file 2n x 2n (8 x 8 at SC 2: jidctint.c
+// itself), a grey file's blocks n x n -- so each plane has the output's size and jd_output_scaled only interleaves.
+// Plane geometry (whole MCUs): every plane of a file is mcuy * e rows of mcux * e samples, e = 2n for a 4:2:0 file and n for a grey one.
+
+// e: an MCU's edge in every plane of the file; the luma blocks of a 4:2:0 file have half that edge, every other block the whole
+template <int SC> __device__ __forceinline__ int jd_mcu_edge(const JpegDesc& d) { return d.bpm == 1 ? 8 / SC : 16 / SC; }
+
+// Eight blocks per workgroup, eight lanes per block as in jd_idct: a lane dequantises one row of coefficients (one 16-byte load), runs one
+// column of the first pass (the columns the second pass never reads are skipped, as in jidctred.c), then the lanes below the block's edge
+// run one row each of the second pass and store it as one word of `edge` bytes.
+template <int SC> __global__ void __launch_bounds__(64) jd_idct_scaled_kernel(const JpegDesc* __restrict__ descs) {
+    __shared__ int blk[8][64];
+    const JpegDesc d = descs[blockIdx.y];
+    const int t = threadIdx.x, b = t >> 3, l = t & 7;
+    const int id = blockIdx.x * 8 + b;
+    if ((int)blockIdx.x * 8 >= d.nblocks) return;
+    const bool valid = id < d.nblocks;
+    const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
+    const int c = jd_comp(d, j);
+    const int e = jd_mcu_edge<SC>(d);
+    const int n = (d.bpm != 1 && c == 0) ? e / 2 : e;                // the block's edge
+    if (valid) {
+        const uint4 raw = *(const uint4*)(d.coef + (size_t)id * 64 + l * 8);     // 16-byte aligned: blocks are 128 bytes apart
+        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+        const unsigned short* q = d.quant + c * 64 + l * 8;
+        for (int i = 0; i < 4; ++i) {
+            blk[b][l * 8 + 2 * i] = (int)(short)(w[i] & 0xFFFFu) * (int)q[2 * i];
+            blk[b][l * 8 + 2 * i + 1] = (int)(short)(w[i] >> 16) * (int)q[2 * i + 1];
+        }
+    }
+    __syncthreads();
+    if (valid) {
+        int* col = &blk[b][l];
+        if (n == 8) idct8(col, 8, true);
+        else if (n == 4) { if (l != 4) idct4(col, 8, true); }
+        else if (n == 2) { if (l == 0 || (l & 1)) idct2(col, 8, true); }
+    }
+    __syncthreads();
+    if (valid && l < n) {
+        int* row = &blk[b][l * 8];
+        if (n == 8) idct8(row, 1, false);
+        else if (n == 4) idct4(row, 1, false);
+        else if (n == 2) idct2(row, 1, false);
+        else row[0] = idct1(row[0]);
+        const int pw = d.mcux * e;
+        const int mx = mcu % d.mcux, my = mcu / d.mcux;
+        // a luma block of a 4:2:0 file sits at (j / 2, j % 2) of its MCU
+        const int by = (d.bpm != 1 && c == 0) ? (j >> 1) * n : 0, bx = (d.bpm != 1 && c == 0) ? (j & 1) * n : 0;
+        uint8_t* o = d.plane[c] + (size_t)(my * e + by + l) * pw + mx * e + bx;
+        if (n == 8) {
+            uint2 v;
+            v.x = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
+            v.y = (unsigned)row[4] | ((unsigned)row[5] << 8) | ((unsigned)row[6] << 16) | ((unsigned)row[7] << 24);
+            *(uint2*)o = v;                                           // pw and the offsets are multiples of 8, the planes 256-byte aligned
+        } else if (n == 4) {
+            *(unsigned*)o = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
+        } else if (n == 2) {
+            *(unsigned short*)o = (unsigned short)(row[0] | (row[1] << 8));
+        } else {
+            o[0] = (uint8_t)row[0];
+        }
+    }
+}
+
+// the planes -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane, OW x OH pixels into the caller's tensor
+template <int SC> __global__ void __launch_bounds__(256) jd_output_scaled_kernel(const JpegDesc* __restrict__ descs) {
+    const JpegDesc d = descs[blockIdx.z];
+    const int OW = (d.W + SC - 1) / SC, OH = (d.H + SC - 1) / SC;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= OW || y >= OH) return;
+    const int pw = d.mcux * jd_mcu_edge<SC>(d);
+    const size_t i = (size_t)y * pw + x;
+    if (d.ncomp == 1) {
+        d.out[(size_t)y * d.pitch + x] = d.plane[0][i];
+        return;
+    }
+    uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
+    const unsigned Y = d.plane[0][i], cb = d.plane[1][i], cr = d.plane[2][i];
+    if (d.px == 4 && ((d.pitch | (long long)(size_t)d.out) & 3) == 0) {
+        *(unsigned*)o = Y | (cb << 8) | (cr << 16) | (255u << 24);
+    } else {
+        o[0] = (uint8_t)Y;
+        o[1] = (uint8_t)cb;
+        o[2] = (uint8_t)cr;
+        if (d.px == 4) o[3] = 255;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_jd_sync(const JpegDesc* descs, int n, int max_groups, int pass, hipStream_t s) {
@@ -356,5 +447,23 @@ hipError_t launch_jd_idct(const JpegDesc* descs, int n, int max_blocks, hipStrea
 }
 hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, hipStream_t s) {
     hipLaunchKernelGGL(jd_output_kernel, dim3((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n), dim3(256), 0, s, descs);
+    return hipGetLastError();
+}
+// scale: 2, 4 or 8; the descriptors are of 4:2:0 or grey files only (hs == vs == 2, or one component)
+hipError_t launch_jd_idct_scaled(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s) {
+    const dim3 grid((unsigned)((max_blocks + 7) / 8), (unsigned)n);
+    if (scale == 2) hipLaunchKernelGGL(jd_idct_scaled_kernel<2>, grid, dim3(64), 0, s, descs);
+    else if (scale == 4) hipLaunchKernelGGL(jd_idct_scaled_kernel<4>, grid, dim3(64), 0, s, descs);
+    else if (scale == 8) hipLaunchKernelGGL(jd_idct_scaled_kernel<8>, grid, dim3(64), 0, s, descs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// max_h, max_w: of the scaled outputs
+hipError_t launch_jd_output_scaled(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s) {
+    const dim3 grid((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n);
+    if (scale == 2) hipLaunchKernelGGL(jd_output_scaled_kernel<2>, grid, dim3(256), 0, s, descs);
+    else if (scale == 4) hipLaunchKernelGGL(jd_output_scaled_kernel<4>, grid, dim3(256), 0, s, descs);
+    else if (scale == 8) hipLaunchKernelGGL(jd_output_scaled_kernel<8>, grid, dim3(256), 0, s, descs);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }

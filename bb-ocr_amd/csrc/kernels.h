@@ -366,7 +366,7 @@ struct JpegDesc {                                              // one file of a 
     int* flags;                                                // [passes + 1] flags[k] != 0: pass k changed a state
     int* status;                                               // JD_ERR_* bits
     short* coef;                                               // [nblocks][64] natural order, MCU block order
-    uint8_t* plane[3];                                         // Y [mcuy * 8 vs][mcux * 8 hs], then Cb, Cr [mcuy * 8][mcux * 8] each
+    uint8_t* plane[3];                                         // Y [mcuy * 8 vs][mcux * 8 hs], then Cb, Cr [mcuy * 8][mcux * 8] each (a scaled decode: see launch_jd_idct_scaled)
     uint8_t* out;
     long long pitch;
     const JpegHuff* huff;                                      // [4]: DC 0, DC 1, AC 0, AC 1
@@ -382,3 +382,7 @@ hipError_t launch_jd_write(const JpegDesc* descs, int n, int max_groups, hipStre
 hipError_t launch_jd_dc(const JpegDesc* descs, int n, int max_seg, hipStream_t s);
 hipError_t launch_jd_idct(const JpegDesc* descs, int n, int max_blocks, hipStream_t s);
 hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, hipStream_t s);
+// the decode at scale 1/2, 1/4 or 1/8 (4:2:0 and grey files): reduced IDCTs into planes of the output's size, then the interleave; the
+// entropy stages above are the same.  The planes are then mcuy * e rows of mcux * e samples each, e = 16 / scale (grey: 8 / scale).
+hipError_t launch_jd_idct_scaled(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s);
+hipError_t launch_jd_output_scaled(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s);

@@ -1,6 +1,7 @@
 // OCR-input thumbnail + JPEG round trip (enhanced_extractor.py:486-512), host side: Pillow's thumbnail geometry (preserve_aspect_ratio,
 // resize's reducing_gap rule), the resample coefficient tables (precompute_coeffs + normalize_coeffs_8bpc), libjpeg's quality-scaled
-// quantisation tables, and the launch sequence of thumb.hip.
+// quantisation tables, and the launch sequence of thumb.hip.  Also the resize with a fractional source box that Image.thumbnail runs after
+// a JPEG draft (bbocr_thumbnail_box: the trace previews, enhanced_extractor.py:184-199), on the same kernels.
 #include "ctx.h"
 
 #include <cmath>
@@ -64,6 +65,26 @@ ThPlan thumb_plan(int H, int W, int max_dim) {
     p.box[2] = (float)((double)W / p.fx);
     p.box[3] = (float)((double)H / p.fy);
     return p;
+}
+
+// Image.resize((ow, oh), BICUBIC, box=(0, 0, bw, bh), reducing_gap=2.0) for a box that ends inside the last pixel (W - 1 < bw <= W, the
+// same down): what Image.thumbnail does after a JPEG draft, whose box is the original size over the draft scale.  The reduce factors
+// come from the box, _get_safe_box of such a box is the whole image (the filter's support reaches past the last pixel whenever a factor
+// exceeds 1), and the box handed on is (0, 0, bw / fx, bh / fy) as C floats.  false: the box is not of that kind.
+bool resize_plan(int H, int W, int oh, int ow, double bw, double bh, ThPlan* out) {
+    if (!(bw > (double)W - 1.0 && bw <= (double)W && bh > (double)H - 1.0 && bh <= (double)H)) return false;
+    ThPlan p{};
+    p.oh = oh;
+    p.ow = ow;
+    p.fx = std::max((int)(bw / ow / 2.0), 1);
+    p.fy = std::max((int)(bh / oh / 2.0), 1);
+    p.rw = (W + p.fx - 1) / p.fx;
+    p.rh = (H + p.fy - 1) / p.fy;
+    p.box[0] = p.box[1] = 0.0f;
+    p.box[2] = (float)(bw / p.fx);
+    p.box[3] = (float)(bh / p.fy);
+    *out = p;
+    return true;
 }
 
 double bicubic(double x) {
@@ -272,6 +293,31 @@ int bbocr_ocr_thumbnail(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, lo
         const int C = th_resize(ctx, w, dev_src, (size_t)pitch, layout, H, W, p, k);
         if (quality > 0) th_jpeg(ctx, w, w.resized, (size_t)p.ow * C, C, p.oh, p.ow, quality, dev_rgb, dev_gray, nullptr);
         else HIPCHK(launch_th_direct(w.resized, (size_t)p.ow * C, C == 1 ? PAGE_GRAY : PAGE_RGB, p.oh, p.ow, dev_rgb, dev_gray, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+int bbocr_host_resize_plan(int H, int W, int out_h, int out_w, double box_w, double box_h, int factors[2], float resize_box[4]) {
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1 || !factors || !resize_box) return BBOCR_ERR_ARG;
+    ThPlan p;
+    if (!resize_plan(H, W, out_h, out_w, box_w, box_h, &p)) return BBOCR_ERR_ARG;
+    factors[0] = p.fx;
+    factors[1] = p.fy;
+    for (int i = 0; i < 4; ++i) resize_box[i] = p.box[i];
+    return BBOCR_OK;
+}
+
+int bbocr_thumbnail_box(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int out_h, int out_w, double box_w,
+                        double box_h, uint8_t* dev_dst) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        check_page({dev_src, H, W, pitch, layout});
+        if (!dev_dst || out_h < 1 || out_w < 1) fail(BBOCR_ERR_ARG, "bad arguments");
+        ThPlan p;
+        if (!resize_plan(H, W, out_h, out_w, box_w, box_h, &p)) fail(BBOCR_ERR_ARG, "the box must start at (0, 0) and end inside the last pixel");
+        const ThCoef k = thumb_coeffs(ctx, p);
+        const ThWork w = th_work(ctx, H, W, layout, p, k.y1 - k.y0, true, 1, 1);
+        const int C = th_resize(ctx, w, dev_src, (size_t)pitch, layout, H, W, p, k);
+        HIPCHK(hipMemcpyAsync(dev_dst, w.resized, (size_t)p.oh * p.ow * C, hipMemcpyDeviceToDevice, ctx->stream));
         slot_sync(ctx, ctx->stream);
     });
 }

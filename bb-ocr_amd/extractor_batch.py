@@ -119,31 +119,38 @@ def _ocr_input_device(reader, image_path, image_index=None, decode_once=True, de
 
 
 def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, on_device=False,
-                  device_decode=False, applied=None):
+                  device_decode=False, applied=None, pages=None):
     """The page ``extract_text_with_ocr`` would hand to the down-scaling step (:425-485), as a host array: decoded like ``cv2.imread``
     (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
     final crop comes back.  A step that returns None in the reference leaves the page as it was.  ``on_device=True``: the crop stays on
     the card, as a (possibly strided) view of the device page.  ``device_decode=True``: the page is read by
     ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels);
     ``device_decode="chroma"``: 4:4:4, 4:2:2 and 4:4:0 files as well.  ``applied``: a list that receives the names of the steps that changed the page (where it stays empty the reference goes on with the
-    original file)."""
+    original file).  ``pages``: a dict that receives, under the same names, the device page each of those steps left (views of one another
+    where the step is a crop) -- what ``trace_previews`` draws from."""
     from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, imread_bgr_device, preprocess_bgr_device
 
     applied = [] if applied is None else applied
+
+    def done(step):
+        applied.append(step)
+        if pages is not None:
+            pages[step] = page
+
     page = imread_bgr_device(reader, image_path, device_decode) if device_decode else reader._to_dev(_imread_bgr(image_path))
     if use_preprocessing:
         page = preprocess_bgr_device(reader, page)
-        applied.append("preprocess")
+        done("preprocess")
     if edge_crop_percent > 0.0:
         b = central_edge_crop_box(page.shape[0], page.shape[1], edge_crop_percent)
         if b is not None:
             page = page[b[1]:b[3], b[0]:b[2]]
-            applied.append("edge_crop")
+            done("edge_crop")
     if crop_for_ocr:
         b = auto_crop_box_device(reader, page, crop_margin)
         if b is not None:
             page = page[b[1]:b[3], b[0]:b[2]]
-            applied.append("auto_crop")
+            done("auto_crop")
     if on_device:
         return page
     return page.contiguous().cpu().numpy()
@@ -594,4 +601,36 @@ def encode_images_for_model(reader, image_paths, use_preprocessing=False, edge_c
                 with open(path, "rb") as f:
                     data = f.read()
         out.append(base64.b64encode(data).decode("utf-8"))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the processing trace's previews (:184-199)
+TRACE_KEYS = {"preprocess": "preprocessed_b64", "edge_crop": "edge_cropped_b64", "auto_crop": "auto_cropped_b64"}
+
+
+def trace_previews(reader, image_paths, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_decode=True):
+    """The preview strings ``extract_text_with_ocr`` puts into an image's trace (``capture_trace=True``, :421-476), one dict per image,
+    string for string: ``original_b64`` -- ``_image_to_data_url`` of the file itself (``Image.open`` does not transpose; an unloaded JPEG
+    is decoded at the draft scale) -- and, where the step changed the page, ``preprocessed_b64``, ``edge_cropped_b64`` and
+    ``auto_cropped_b64`` of the PNG the reference wrote after it; a key is absent where its step is off or returns None in the
+    reference.  The pages are those of ``ocr_page_crop`` (pre-processed once, crops as views; the file is read once and decoded once per scale: at the draft scale for the
+    original's preview, at full scale for the crop chain -- both run the entropy stages) thumbnailed on the card
+    (``preprocess.preview_device``): only pages of at most 800 pixels come back.  ``device_decode``: baseline 4:2:0 / grey JPEG files are
+    decoded on the card, for the original's preview at the draft scale; everything else takes ``preprocess.preview_host``."""
+    from .preprocess import preview_device
+    from .reader import _file_bytes
+
+    if crop_margin < 0:
+        raise ValueError("crop_margin must be >= 0")
+    out = []
+    for path in image_paths:
+        source = _file_bytes(path) if device_decode else path             # read once for both decodes
+        trace = {"original_b64": preview_device(reader, source, device_decode=device_decode)}
+        if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
+            pages = {}
+            ocr_page_crop(reader, source, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=True,
+                          device_decode=device_decode, pages=pages)
+            for step, page in pages.items():
+                trace[TRACE_KEYS[step]] = preview_device(reader, page)
+        out.append(trace)
     return out

@@ -265,6 +265,104 @@ def ocr_input_ycc_device(reader, ycc_dev, image_index=None):
     return ocr_thumbnail_device(reader, ycc_dev, layout, m, q)
 
 
+# ------------------------------------------------------------------------------------------------ the trace previews (:184-199)
+PREVIEW_MAX_DIM = 800                                   # _image_to_data_url's max_dim
+
+
+def _png_data_url(img):
+    """``img.save(buf, format="PNG")`` as the ``data:image/png;base64,...`` string of ``_image_to_data_url``"""
+    import base64
+
+    buf = io.BytesIO()
+    img.save(buf, format="PNG")
+    return "data:image/png;base64," + base64.b64encode(buf.getvalue()).decode("utf-8")
+
+
+def preview_host(source, max_dim=PREVIEW_MAX_DIM):
+    """``_image_to_data_url(path, max_dim=max_dim)`` (:184-199) restated with Pillow: ``Image.open(path)``, ``thumbnail((max_dim, max_dim))``
+    -- which decodes an unloaded JPEG file at the draft scale -- ``save(format="PNG")``, base64.  ``source``: a path or the file's bytes, or a
+    page the reference would have written as a PNG on the way (gray [H,W] or BGR [H,W,3] uint8).  The mode is kept (L stays L), the
+    file's ICC profile goes into the PNG, and the EXIF orientation is not applied.  The yardstick of ``preview_device``, and the path of
+    sources the device does not take."""
+    from PIL import Image
+
+    if isinstance(source, np.ndarray):
+        img = Image.fromarray(np.ascontiguousarray(source if source.ndim == 2 else source[:, :, ::-1]))
+    else:
+        img = Image.open(io.BytesIO(source) if isinstance(source, (bytes, bytearray)) else source)
+    img.thumbnail((max_dim, max_dim))
+    return _png_data_url(img)
+
+
+def thumbnail_box_device(reader, page_dev, layout, out_h, out_w, box_w, box_h):
+    """``bbocr_thumbnail_box``: ``Image.resize((out_w, out_h), BICUBIC, box=(0, 0, box_w, box_h), reducing_gap=2.0)`` of a uint8 device page
+    of the given ``PAGE_*`` layout (a strided row pitch is read in place), for a box that ends inside the last pixel -> RGB
+    ``[out_h,out_w,3]``, or ``[out_h,out_w]`` for a gray page."""
+    import torch
+
+    H, W, pitch, _ = _page_layout(reader, page_dev, (layout,))
+    out = torch.empty((out_h, out_w) if layout == PAGE_GRAY else (out_h, out_w, 3), dtype=torch.uint8, device=page_dev.device)
+    torch.cuda.current_stream(reader.device_index).synchronize()       # the library runs on its own stream
+    reader._check(reader._lib.bbocr_thumbnail_box(reader._h, C.c_void_p(page_dev.data_ptr()), H, W, pitch, int(layout), int(out_h), int(out_w),
+                                                  float(box_w), float(box_h), C.c_void_p(out.data_ptr())))
+    return out
+
+
+def _preview_jpeg_device(reader, data, plan, max_dim):
+    """``Image.open(file).thumbnail((max_dim, max_dim))`` of a file the plan supports, on the card: the pixels (RGB [h,w,3] or gray [h,w],
+    a device tensor), or None when the decoder reports the entropy-coded data damaged"""
+    from .reader import JpegPage, draft_scale
+
+    H, W = int(plan.height), int(plan.width)
+    oh, ow = C.c_int(), C.c_int()
+    reader._check(reader._lib.bbocr_thumbnail_dims(H, W, int(max_dim), C.byref(oh), C.byref(ow)))
+    oh, ow = oh.value, ow.value
+    thumb = max(H, W) > int(max_dim)
+    s = draft_scale(W, H, int(max_dim * 2.0), int(max_dim * 2.0)) if thumb else 1        # thumbnail(): draft(None, size * reducing_gap)
+    t, status = reader.decode_jpeg_batch([JpegPage(data, plan)], padded=True, scale=s)
+    if status[0] != 0:
+        return None
+    page = t[0]
+    layout = PAGE_GRAY if page.ndim == 2 else PAGE_YCBCR4
+    if not thumb or (page.shape[0], page.shape[1]) == (oh, ow):         # no resize: the (drafted) decode itself
+        return page if layout == PAGE_GRAY else reader.pages_from_ycc(t)[0][0]
+    return thumbnail_box_device(reader, page, layout, oh, ow, W / s, H / s)
+
+
+def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True):
+    """``preview_host(source, max_dim)``, character for character, with the pixels made on the card; only the page of at most ``max_dim``
+    pixels comes back, and Pillow writes the PNG from it.
+
+    * a JPEG path or bytes the device decoder's plan supports (4:2:0 or grey baseline) and ``device_decode``: plan -> draft scale ->
+      ``bbocr_jpeg_decode_scaled`` -> libjpeg's RGB -> ``bbocr_thumbnail_box``; the file's ICC profile is carried into the PNG as Pillow
+      carries it;
+    * a page already on the card (a uint8 tensor, gray [H,W] or BGR [H,W,3], a strided view included -- the f2 output or a crop): the
+      whole-image thumbnail (``bbocr_ocr_thumbnail`` without its JPEG round trip); a gray page stays mode L;
+    * everything else (PNG, progressive / 4:4:4 / 4:2:2 / 4:4:0 / CMYK JPEG, a file whose data is damaged, host arrays): ``preview_host``."""
+    from PIL import Image
+
+    from .reader import _file_bytes, jpeg_plan
+
+    px, icc = None, None
+    if hasattr(source, "is_cuda"):
+        H, W, _, ch = _page_layout(reader, source)
+        rgb, gray = ocr_thumbnail_device(reader, source, PAGE_GRAY if ch == 1 else PAGE_BGR, max_dim, 0)
+        px = gray if ch == 1 else rgb
+    elif device_decode and not isinstance(source, np.ndarray):
+        data = _file_bytes(source)
+        plan = jpeg_plan(data)
+        if plan.supported:
+            px = _preview_jpeg_device(reader, data, plan, max_dim)
+            icc = Image.open(io.BytesIO(data)).info.get("icc_profile")          # headers only
+            source = data
+    if px is None:
+        return preview_host(source, max_dim)
+    img = Image.fromarray(px.cpu().numpy())
+    if icc:
+        img.info["icc_profile"] = icc
+    return _png_data_url(img)
+
+
 def _read_page(image_path_or_array):
     if isinstance(image_path_or_array, np.ndarray):
         return np.ascontiguousarray(image_path_or_array)

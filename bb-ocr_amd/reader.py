@@ -178,7 +178,18 @@ def jpeg_plan(data):
     return plan
 
 
-DECODE_CHROMA = "chroma"     # the value of ``device_decode`` / ``BBOCR_DEVICE_DECODE`` that adds 4:4:4, 4:2:2 and 4:4:0 files to the device decoder's
+JPEG_SCALES = (1, 2, 4, 8)   # bbocr_jpeg_decode_scaled's scales: libjpeg's scale_denom for the ISLOW decode Pillow's draft configures
+
+
+def draft_scale(W, H, req_w, req_h):
+    """``JpegImageFile.draft(None, (req_w, req_h))``'s scale for a ``W x H`` file: the largest of 8, 4, 2, 1 that is at most
+    ``min(W // req_w, H // req_h)`` -- the file then decodes to ``ceil(W / scale) x ceil(H / scale)`` and ``Image.thumbnail`` resizes from
+    the box ``(0, 0, W / scale, H / scale)``."""
+    s = min(W // req_w, H // req_h)
+    return 8 if s >= 8 else 4 if s >= 4 else 2 if s >= 2 else 1
+
+
+DECODE_CHROMA = "chroma"   # the value of ``device_decode`` / ``BBOCR_DEVICE_DECODE`` that adds 4:4:4, 4:2:2 and 4:4:0 files to the device decoder's
 
 
 def jpeg_chroma(device_decode):
@@ -737,15 +748,20 @@ class Reader:
         n = len(pages)
         return (C.c_void_p * n)(*[C.cast(C.c_char_p(p.data), C.c_void_p) for p in pages]), (C.c_size_t * n)(*[len(p.data) for p in pages])
 
-    def decode_jpeg_batch(self, pages, padded=False):
+    def decode_jpeg_batch(self, pages, padded=False, scale=1):
         """``JpegPage`` s of ONE shape -> ``(batch, status)``: the device tensor ``uint8 [n,H,W,3]`` (``padded``: ``[n,H,W,4]``) of libjpeg's
         YCbCr triples -- what ``pages_from_ycc`` takes -- or ``[n,H,W]`` for 1-component files, decoded by ONE ``bbocr_jpeg_decode`` call
-        (only the files' bytes cross the link), and the per-file status list (0, or negative: that page of the batch is undefined)."""
+        (only the files' bytes cross the link), and the per-file status list (0, or negative: that page of the batch is undefined).
+        ``scale`` 2, 4 or 8: the decode at that fraction, Pillow's ``draft`` (``bbocr_jpeg_decode_scaled``): ``H`` and ``W`` are then
+        ``ceil(. / scale)`` of the pages', and a 4:4:4, 4:2:2 or 4:4:0 file gets a negative status."""
         torch = self._torch
         pages = list(pages)
         if not pages or any(p.shape != pages[0].shape for p in pages):
             raise ValueError("decode_jpeg_batch: pages of one decoded shape")
+        if scale not in JPEG_SCALES:
+            raise ValueError(f"scale must be one of {JPEG_SCALES}")
         H, W, comps = pages[0].shape
+        H, W = -(-H // scale), -(-W // scale)
         layout = _lib.PAGE_YCBCR4 if padded else _lib.PAGE_YCBCR3
         px = _lib.PAGE_PX_BYTES[_lib.PAGE_GRAY if comps == 1 else layout]
         t = torch.empty((len(pages), H, W) + ((px,) if comps == 3 else ()), dtype=torch.uint8, device=self.device)
@@ -755,7 +771,10 @@ class Reader:
         outs = (C.c_void_p * n)(*[t.data_ptr() + k * H * W * px for k in range(n)])
         pitches = (C.c_longlong * n)(*([W * px] * n))
         status = (C.c_int * n)()
-        self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
+        if scale == 1:
+            self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
+        else:
+            self._check(self._lib.bbocr_jpeg_decode_scaled(self._h, files, sizes, n, layout, scale, outs, pitches, status))
         return t, list(status)
 
     def imread_jpeg_batch(self, pages):
@@ -828,12 +847,13 @@ class Reader:
         """This Reader's ``device_decode`` as the functions of ``extractor_batch`` and ``preprocess`` take it: ``"chroma"``, True or False"""
         return DECODE_CHROMA if self.jpeg_chroma else self.device_decode
 
-    def decode_jpeg_device(self, sources, chroma=None):
+    def decode_jpeg_device(self, sources, chroma=None, scale=1):
         """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them (libjpeg's RGB and its Y
         plane; a grey file: the samples, replicated for RGB), decoded on the card, or ``None`` for a file the plan refuses or whose
         entropy-coded data is damaged.  Files of one decoded shape share one decode call.  ``chroma`` (None: this Reader's
-        ``jpeg_chroma``): 4:4:4, 4:2:2 and 4:4:0 files are decoded as well."""
-        chroma = self.jpeg_chroma if chroma is None else bool(chroma)
+        ``jpeg_chroma``): 4:4:4, 4:2:2 and 4:4:0 files are decoded as well.  ``scale`` 2, 4 or 8: the decode at that fraction (Pillow's
+        ``draft``: ``ceil(H / scale) x ceil(W / scale)``), of 4:2:0 and grey files only -- every other file is ``None``."""
+        chroma = (self.jpeg_chroma if chroma is None else bool(chroma)) and scale == 1
         pages = [jpeg_page(s, chroma) for s in sources]
         out = [None] * len(pages)
         groups = {}
@@ -841,7 +861,7 @@ class Reader:
             if p is not None:
                 groups.setdefault(p.shape, []).append(i)
         for idxs in groups.values():
-            t, status = self.decode_jpeg_batch([pages[i] for i in idxs])
+            t, status = self.decode_jpeg_batch([pages[i] for i in idxs], scale=scale)
             rgb, gray = self.pages_from_jpeg(t)
             for k, i in enumerate(idxs):
                 if status[k] == 0:

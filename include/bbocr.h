@@ -426,6 +426,16 @@ int bbocr_thumbnail_dims(int H, int W, int max_dim, int* out_h, int* out_w);
 /* host only: the plan of that thumbnail -- output size, reduce factors (x, y), the reduced region (x0, y0, x1, y1) and the float box
  * (x0, y0, x1, y1) handed to the bicubic resample in the reduced image */
 int bbocr_host_thumbnail_plan(int H, int W, int max_dim, int* out_h, int* out_w, int factors[2], int reduce_box[4], float resize_box[4]);
+/* ---- the resize Image.thumbnail runs after a JPEG draft: Image.resize((out_w, out_h), BICUBIC, box=(0, 0, box_w, box_h),
+ * reducing_gap=2.0) of an H x W page for a float box that ends inside the last pixel (W - 1 < box_w <= W, H - 1 < box_h <= H; the draft's
+ * box is the original size over the draft scale, e.g. 535.5 rows of a 536-row decode).  The reduce factors are int(box / out / 2) or 1,
+ * the reduce step covers the whole page, and the bicubic resample gets the box (0, 0, box_w / fx, box_h / fy) as C floats.  dev_dst
+ * receives RGB [out_h,out_w,3] (YCbCr pages: libjpeg's RGB), or the samples [out_h,out_w] of a BBOCR_PAGE_GRAY page; any layout, rows
+ * `pitch` bytes apart.  A pipeline call like bbocr_ocr_thumbnail; any other box: BBOCR_ERR_ARG.  bbocr_host_resize_plan: host only, the
+ * factors (x, y) and the box handed to the resample. */
+int bbocr_thumbnail_box(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int out_h, int out_w, double box_w,
+                        double box_h, uint8_t* dev_dst);
+int bbocr_host_resize_plan(int H, int W, int out_h, int out_w, double box_w, double box_h, int factors[2], float resize_box[4]);
 /* host only: Pillow's bicubic coefficients of one axis (precompute_coeffs + normalize_coeffs_8bpc): bounds [out][2] = (first, count),
  * coeffs [out][max_ksize] (22-bit fixed point).  *ksize is always set; bounds = coeffs = NULL is a size query. */
 int bbocr_host_resample_coeffs(int in_size, float in0, float in1, int out_size, int* bounds, int* coeffs, int max_ksize, int* ksize);
@@ -507,6 +517,23 @@ int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
  * [mcu_rows * 8][mcu_cols * 8]); 3 = the pixels, tight.  *file_status as status[k] above. */
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status);
+/* ---- the decode at reduced scale: what Pillow's draft (decoderconfig == (scale, 0)) and hence Image.thumbnail of an unloaded JPEG file get
+ * from libjpeg-turbo, to the bit.  bbocr_jpeg_decode_scaled is bbocr_jpeg_decode -- same arguments, stream, contract and status codes --
+ * with one `scale` per batch: 1 (bbocr_jpeg_decode itself), 2, 4 or 8.  At scale s > 1 file k comes out ceil(height / s) rows of
+ * ceil(width / s) pixels (bbocr_jpeg_scaled_dims; pitches[k] at least such a row): luma blocks through jidctred.c's n x n IDCT, n = 8 / s,
+ * the chroma blocks of a 4:2:0 file through the 2n x 2n one (jdmaster.c's per-component DCT_scaled_size), so that nothing is upsampled; the
+ * entropy stages are those of the full-scale decode.  Only the files inside the plan's own scope (supported == 1: 4:2:0 or one component)
+ * are decoded at s > 1: a file of a chroma class (4:4:4, 4:2:2, 4:4:0), like every file the plan refuses, gets status[k] = BBOCR_ERR_ARG,
+ * the rest of the batch is decoded, and the caller keeps its host path for it. */
+int bbocr_jpeg_decode_scaled(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, int scale,
+                             uint8_t* const* dev_out, const long long* pitches, int* status);
+/* host only: (ceil(H / scale), ceil(W / scale)); scale 1, 2, 4 or 8 */
+int bbocr_jpeg_scaled_dims(int H, int W, int scale, int* out_h, int* out_w);
+/* intermediates of ONE file's decode at scale 2, 4 or 8 (parity tests), numbered like bbocr_op_jpeg_stage's: stage 2 = the component
+ * planes, each [mcu_rows * e][mcu_cols * e] with e = 16 / scale for a 4:2:0 file (Y, then Cb, then Cr: all of the output's size) and
+ * e = 8 / scale for a 1-component file (Y alone); 3 = the pixels, tight.  A file outside the scaled decode's scope: BBOCR_ERR_ARG. */
+int bbocr_op_jpeg_scaled_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
+                               int* file_status);
 
 /* ---- the extractor's model-input JPEG (enhanced_extractor.py:399-411, _encode_image_for_model's img.save(format="JPEG", quality=q)) written
  * on the device (csrc/jpegenc.hip): one u8 page in device memory -- any BBOCR_PAGE_* layout, rows `pitch` bytes apart, a crop of a larger
