@@ -55,16 +55,9 @@ static void op_crops(bbocr_ctx* ctx, const GrayPages& g, int n, const int* hori,
                         (uint8_t*)ctx->crop_wscratch.p, (uint8_t*)ctx->crop_scratch.p, (uint8_t*)ctx->crop_hscratch.p,
                         (const uint8_t*)ctx->crop_luts.p, dev_out, 1, ctx->stream, 0, 0, 0, g.tab_dev));
     if (contrast > 0) {
-        ctx->crop_hist.ensure(descs.size() * 256 * 4);
-        HIPCHK(launch_crop_hist((const uint8_t*)ctx->crop_scratch.p, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(),
-                                (unsigned int*)ctx->crop_hist.p, ctx->stream));
-        std::vector<unsigned int> hist(descs.size() * 256);
-        HIPCHK(hipMemcpyAsync(hist.data(), ctx->crop_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        slot_sync(ctx, ctx->stream);
-        std::vector<uint8_t> luts(descs.size() * 256);
-        for (size_t k = 0; k < descs.size(); ++k)       // a crop whose contrast is high enough stays as it is (lut_off -1), as in recognize_impl's retry
-            if (contrast_lut(&hist[k * 256], (size_t)descs[k].rw * descs[k].rh, (double)contrast, &luts[k * 256])) descs[k].lut_off = (int)(k * 256);
-        HIPCHK(hipMemcpyAsync(ctx->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, ctx->stream));
+        std::vector<uint8_t> luts;       // a crop whose contrast is high enough stays as it is (lut_off -1), as in recognize_impl's retry
+        (void)crop_contrast_luts(ctx, (const CropDesc*)ctx->crop_desc.p, descs, (double)contrast, luts);
+        if (!luts.empty()) HIPCHK(hipMemcpyAsync(ctx->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(ctx->crop_desc.p, descs.data(), descs.size() * sizeof(CropDesc), hipMemcpyHostToDevice, ctx->stream));
     }
     HIPCHK(launch_crops(g.gray, g.H, g.W, (const CropDesc*)ctx->crop_desc.p, 0, (int)descs.size(), imgW, any_warp, any_tall,
@@ -167,6 +160,33 @@ int bbocr_host_ctc_beam(const float* probs, int n, int T, int C, int cs, int bea
             for (int v : texts[i]) text_idx[o++] = v;
         }
         text_off[n] = o;
+    } catch (...) {
+        return BBOCR_ERR_INTERNAL;
+    }
+    return BBOCR_OK;
+}
+
+int bbocr_host_crop_plan(int H, int W, const int* hori, int n_hori, const double* free_q, int n_free, int* taken, int* geom, double* minv) {
+    if (H <= 0 || W <= 0 || n_hori < 0 || n_free < 0 || (n_hori > 0 && !hori) || (n_free > 0 && !free_q) || !taken || !geom || !minv) return BBOCR_ERR_ARG;
+    try {
+        for (int i = 0; i < n_hori + n_free; ++i) {
+            BoxJob j;
+            memset(&j.d, 0, sizeof(j.d));
+            if (i < n_hori) {
+                std::array<int, 4> b;
+                memcpy(b.data(), hori + (size_t)i * 4, 16);
+                taken[i] = plan_horizontal(b, 0, H, W, j);
+            } else {
+                std::array<double, 8> f;
+                memcpy(f.data(), free_q + (size_t)(i - n_hori) * 8, 64);
+                taken[i] = plan_free(f, 0, j);
+            }
+            if (!taken[i]) memset(&j.d, 0, sizeof(j.d));
+            const CropDesc& d = j.d;
+            const int v[9] = {d.sx0, d.sy0, d.sw, d.sh, d.rw, d.rh, d.fw, d.imgW, d.warp};
+            std::copy(v, v + 9, geom + (size_t)i * 9);
+            std::copy(d.Minv, d.Minv + 9, minv + (size_t)i * 9);
+        }
     } catch (...) {
         return BBOCR_ERR_INTERNAL;
     }

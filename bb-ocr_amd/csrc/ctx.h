@@ -424,6 +424,8 @@ int rec_mode(const bbocr_ctx* c);
 void crop_refit_fw(CropDesc& d);
 void rec_layout_scratch(std::vector<BoxJob>& jobs, size_t first, size_t& a_total, size_t& w_total);
 bool contrast_lut(const unsigned int* hist, size_t npx, double target, uint8_t* lut);
+std::vector<int> crop_contrast_luts(bbocr_ctx* c, const CropDesc* descs_dev, std::vector<CropDesc>& descs, double target, std::vector<uint8_t>& luts);
+void rec_launch_crops(bbocr_ctx* c, const GrayPages& g, const RecPart& part, const CropDesc* dd, uint16_t* wide, int stage);
 void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int>& sel, int res0, size_t row_base, RecPart& part);
 const CropDesc* rec_upload_descs(bbocr_ctx* c, const RecPart& part, DevBuf& desc_buf);
 uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part);

@@ -258,21 +258,24 @@ uint16_t* rec_wide_image(bbocr_ctx* c, const RecPart& part) {
     return c->arena.alloc<uint16_t>((size_t)64 * part.cols);
 }
 
+// the crop launches of a part whose descriptors are on the device at dd: stage 1 = gather / warp + cv2 resize into the crop scratch (wide: null),
+// stage 2 = AlignCollate into the wide image [64][part.cols] in the context's recogniser mode
+void rec_launch_crops(bbocr_ctx* c, const GrayPages& g, const RecPart& part, const CropDesc* dd, uint16_t* wide, int stage) {
+    const int n = (int)part.descs.size(), Wt = (int)part.cols;
+    HIPCHK(launch_crops(g.gray, g.H, g.W, dd, 0, n, 0, part.any_warp, part.any_tall, (uint8_t*)c->crop_wscratch.p, (uint8_t*)c->crop_scratch.p,
+                        (uint8_t*)c->crop_hscratch.p, (const uint8_t*)c->crop_luts.p, wide, stage, c->stream, wide ? Wt : 0, wide ? REC_GAP : 0,
+                        wide ? rec_mode(c) : 0, g.tab_dev));
+}
+
 // enqueue a part: descriptor upload, crops (stage A = gather / warp + cv2 resize when asked, stage B = AlignCollate into the wide image),
 // conv stack, pooled rows into seq_v
 static void rec_launch_part(bbocr_ctx* c, const GrayPages& g, const RecPart& part, DevBuf& desc_buf, bool stage_a) {
     if (part.descs.empty()) return;
     EnqLock enq(c);                           // one feature part = one contiguous block on the compute stream
     const CropDesc* dd = rec_upload_descs(c, part, desc_buf);
-    const int n = (int)part.descs.size(), Wt = (int)part.cols;
-    auto crops = [&](uint16_t* wide, int stage) {
-        HIPCHK(launch_crops(g.gray, g.H, g.W, dd, 0, n, 0, part.any_warp, part.any_tall, (uint8_t*)c->crop_wscratch.p, (uint8_t*)c->crop_scratch.p,
-                            (uint8_t*)c->crop_hscratch.p, (const uint8_t*)c->crop_luts.p, wide, stage, c->stream, wide ? Wt : 0, wide ? REC_GAP : 0,
-                            wide ? rec_mode(c) : 0, g.tab_dev));
-    };
-    if (stage_a) crops(nullptr, 1);
+    if (stage_a) rec_launch_crops(c, g, part, dd, nullptr, 1);
     uint16_t* wide = rec_wide_image(c, part);
-    crops(wide, 2);
+    rec_launch_crops(c, g, part, dd, wide, 2);
     crnn_features_wide(c, part, dd, wide);
     if (!c->feat_ev) HIPCHK(hipEventCreateWithFlags(&c->feat_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->feat_ev, c->stream));      // what the sequence stage (on seq_stream) waits for
@@ -484,6 +487,26 @@ bool contrast_lut(const unsigned int* hist, size_t npx, double target, uint8_t* 
     return true;
 }
 
+// adjust_contrast_grey's decision for stage-A crops that lie in the crop scratch (descs: their descriptors, on the device at descs_dev): the
+// histograms, ONE host wait, then per crop whose contrast is below the target its LUT appended to `luts` and lut_off set to it.  Returns the
+// indices of those crops; the others stay as they are (lut_off untouched).  Neither `luts` nor the changed descriptors are uploaded here.
+std::vector<int> crop_contrast_luts(bbocr_ctx* c, const CropDesc* descs_dev, std::vector<CropDesc>& descs, double target, std::vector<uint8_t>& luts) {
+    c->crop_hist.ensure(descs.size() * 256 * 4);
+    HIPCHK(launch_crop_hist((const uint8_t*)c->crop_scratch.p, descs_dev, 0, (int)descs.size(), (unsigned int*)c->crop_hist.p, c->stream));
+    std::vector<unsigned int> hist(descs.size() * 256);
+    HIPCHK(hipMemcpyAsync(hist.data(), c->crop_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    slot_sync(c, c->stream);
+    std::vector<int> changed;
+    for (size_t k = 0; k < descs.size(); ++k) {
+        uint8_t lut[256];
+        if (!contrast_lut(&hist[k * 256], (size_t)descs[k].rw * descs[k].rh, target, lut)) continue;
+        descs[k].lut_off = (int)luts.size();
+        luts.insert(luts.end(), lut, lut + 256);
+        changed.push_back((int)k);
+    }
+    return changed;
+}
+
 static void rec_check_params(bbocr_ctx* c, const bbocr_params& p) {
     if (!c->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
     if (p.ignore_mask[0] & 1u) fail(BBOCR_ERR_ARG, "the CTC blank (class 0) cannot be ignored");
@@ -672,23 +695,14 @@ void recognize_impl(bbocr_ctx* c, const GrayPages& g, int B, const HostBoxes& hb
     std::vector<CropDesc> ld(low.size());
     for (size_t k = 0; k < low.size(); ++k) ld[k] = jobs[low[k]].d;
     c->crop_desc.ensure(ld.size() * sizeof(CropDesc));
-    c->crop_hist.ensure(ld.size() * 256 * 4);
     HIPCHK(hipMemcpyAsync(c->crop_desc.p, ld.data(), ld.size() * sizeof(CropDesc), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_crop_hist((const uint8_t*)c->crop_scratch.p, (const CropDesc*)c->crop_desc.p, 0, (int)ld.size(), (unsigned int*)c->crop_hist.p,
-                            c->stream));
-    std::vector<unsigned int> hist(ld.size() * 256);
-    HIPCHK(hipMemcpyAsync(hist.data(), c->crop_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    slot_sync(c, c->stream);
     // adjust_contrast_grey leaves a crop whose contrast is already >= the target untouched: its second prediction would be computed
     // from bit-identical input, equals the first one, and get_text's `pred1[1] > pred2[1] ? pred1 : pred2` picks the same pair either
     // way.  Only the crops that really change are run again.
     std::vector<int> redo;
     std::vector<uint8_t> luts;
-    for (size_t k = 0; k < low.size(); ++k) {
-        uint8_t lut[256];
-        if (!contrast_lut(&hist[k * 256], (size_t)ld[k].rw * ld[k].rh, p.adjust_contrast, lut)) continue;
-        jobs[low[k]].d.lut_off = (int)luts.size();
-        luts.insert(luts.end(), lut, lut + 256);
+    for (int k : crop_contrast_luts(c, (const CropDesc*)c->crop_desc.p, ld, p.adjust_contrast, luts)) {
+        jobs[low[k]].d.lut_off = ld[k].lut_off;
         redo.push_back(low[k]);
     }
     if (!redo.empty()) {

@@ -280,6 +280,13 @@ int bbocr_host_group_boxes(const int* polys, int n, const bbocr_params* p, bbocr
  * (C <= cs classes, class 0 = blank): text_off [n+1], text_idx (<= n*T).  The definition of bbocr_params::decoder == BEAMSEARCH, the path of
  * beams wider than BBOCR_BEAM_DEVICE_MAX, and the yardstick of bbocr_op_ctc_beam */
 int bbocr_host_ctc_beam(const float* probs, int n, int T, int C, int cs, int beam_width, int* text_off, int* text_idx);
+/* the crop plan of explicit boxes of ONE H x W gray page, as bbocr_op_crops and a recognition pass make it (utils.get_image_list's clamp /
+ * four_point_transform geometry and resize target, AlignCollate's content width): hori [n_hori][4] = x_min, x_max, y_min, y_max, free_q
+ * [n_free][4][2].  Box k (the horizontal boxes, then the free ones): taken[k] = 0 for a box the pass skips (empty after clamping, a quad
+ * with a side shorter than a pixel; its other outputs are zero), else 1 with geom[k][9] = source rectangle sx0, sy0, sw, sh (free box: 0, 0
+ * and the warp's maxWidth x maxHeight), cv2.resize target rw x rh, content width fw, own padded width imgW, warp (1 = free box) and minv[k][9]
+ * = the inverted perspective matrix warpPerspective samples with (free boxes; zero otherwise) */
+int bbocr_host_crop_plan(int H, int W, const int* hori, int n_hori, const double* free_q, int n_free, int* taken, int* geom, double* minv);
 
 /* ---- single-operator entry points (used by the parity tests; same kernels the pipeline runs) ---- */
 /* conv2d on device tensors: in bf16 NHWC [N,H,W,Cin] (as uint16 bits), weights fp32 OIHW on the host (+bias or NULL),
@@ -336,9 +343,10 @@ int bbocr_op_ycc_to_rgb(bbocr_ctx* ctx, const uint8_t* dev_ycc, size_t npix, int
  * storage (Y Cb Cr x) uploaded as it is.  Every page pointer is checked before the first copy is queued: a call refused with
  * BBOCR_ERR_ARG has written nothing to dev_dst. */
 int bbocr_upload_pages(bbocr_ctx* ctx, const void* const* host_pages, int n, size_t bytes_each, void* dev_dst);
-/* recogniser inputs for explicit boxes of ONE gray page: fills crops bf16 [n,64,imgW] (in box order); returns their count in *n_out.
- * contrast != 0 applies adjust_contrast_grey first.  mode 0: the boxes whose own padded width is imgW (Reader.recognize's per-box
- * branch); mode 1..4: EVERY box at the forced width imgW, rotated by np.rot90(crop, mode - 1) (the batched branch rotation_info takes) */
+/* recogniser inputs for explicit boxes of ONE gray page: fills crops [n,64,imgW] (in box order) of 16-bit elements of the context's
+ * RECOGNISER type, as bbocr_crnn_logits reads them (bf16 / fp16 values normalised to [-1, 1]; BBOCR_PREC_EXACT: codes 1 + grey level, the
+ * pad columns carry the last content column's code); returns their count in *n_out.  contrast != 0 applies adjust_contrast_grey first.
+ * mode 0: the boxes whose own padded width is imgW (Reader.recognize's per-box branch); mode 1..4: EVERY box at the forced width imgW, rotated by np.rot90(crop, mode - 1) (the batched branch rotation_info takes) */
 int bbocr_op_crops(bbocr_ctx* ctx, const uint8_t* dev_gray, int H, int W, const int* hori, int n_hori, const double* free_q, int n_free,
                    int imgW, float contrast, uint16_t* dev_out, int* n_out, int mode);
 /* the same for explicit boxes of n gray pages of their own shapes (the page-table variant of the crop kernels, what bbocr_readtext_pages

@@ -6,6 +6,8 @@ second page of a batch or one time step of 79; these checks are per element, and
 The exact mode's split-fp16 stages follow in the second half: rows of craft_forward_exact's conv table, the five pair kernels, every stage of the
 recogniser's conv stack alone, xproj / lin / pred and lstm_exact_kernel, under the split-stage rule (stage_ref.EXACT_RULE).
 
+Last, the crop stage into the wide layout every production pass uses (stage_crops_wide), bit exact against oracle/recog.py in all three modes.
+
 hipErrorNotSupported (801) from a stage is a failure: production would silently take its fallback path on that shape.
 Set BBOCR_STAGE_STATS=<file> to collect one JSON line per case (the table of DESIGN.md section 5)."""
 import ctypes as C
@@ -767,3 +769,52 @@ def test_exact_rec_stage_alone(st_exact, k, part):
         miss = ~((got - p["ref"]).abs() <= R.split_bound(p["ref"], p["S"], p["q32"], R.U_PAIR))
         raise AssertionError(f"{e}; {R.rec_where(miss, widths, p['shapes'])}") from None
     _exact_stats(f"exact rec stage {k}", f"part {part}", stats)
+
+
+# ------------------------------------------------------------------------------------------------ the crop stage into the wide layout
+def _crops_wide(st, contrast):
+    """what every production pass runs -- all crops of a part side by side in ONE [64][cols] image, slot = first column, REC_GAP zero
+    columns after each crop -- planned and launched by the production functions (stage_crops_wide) on the shared cases of
+    tests/crop_cases.py, bit exact against oracle/recog.py at each crop's own padded width; contrast > 0: the LUTs of the contrast retry"""
+    import crop_cases as cc
+
+    el = st.el
+    nh, nf = len(cc.HORI), len(cc.FREE)
+    harr = (C.c_int * (4 * nh))(*[int(v) for b in cc.HORI for v in b])
+    farr = (C.c_double * (8 * nf))(*[float(v) for q in cc.FREE for p in q for v in p])
+    box, slot, imgw = ((C.c_int * (nh + nf))() for _ in range(3))
+    n, cols = C.c_int(), C.c_int()
+    rc = st.lib.stage_crops_wide_plan(cc.H, cc.W, harr, nh, farr, nf, box, slot, imgw, C.byref(n), C.byref(cols))
+    assert rc == 0, st.lib.stage_shim_error().decode()
+    n, cols = n.value, cols.value
+    items = cc.stage_a_cases()
+    kept = [k for k, it in enumerate(items) if it]
+    assert sorted(box[:n]) == kept, "the plan keeps other boxes than the oracle"
+    at = 0
+    for i in range(n):                         # the crops tile the image: slot, imgW columns, REC_GAP columns, the next slot
+        assert slot[i] == at and imgw[i] == items[box[i]][1], (i, slot[i], at, imgw[i], cc.describe(box[i]))
+        at += imgw[i] + R.REC_GAP
+    assert at == cols
+    regimes = [cc.classify(*cc.source_size(k)) for k in box[:n]]
+    assert len(set(imgw[:n])) >= 3 and any(r[1] for r in regimes) and any(k >= nh for k in box[:n])     # widths, a tall crop, a warped one
+    d = torch.from_numpy(cc.make_page().copy()).cuda()
+    out = torch.full((64, cols), cc.SENTINEL, dtype=torch.int16, device="cuda")
+    st.call("stage_crops_wide", d, cc.H, cc.W, harr, nh, farr, nf, C.c_double(contrast), out)
+    got = out.cpu().numpy()
+    for i in range(n):
+        k, s, w = box[i], slot[i], imgw[i]
+        what = f"wide layout {el}, contrast {contrast}, crop {i} at columns [{s}, {s + w}) = {cc.describe(k)}"
+        cc.assert_same(got[:, s:s + w], cc.to_el(cc.reference(k, None, contrast), el), what)
+        gap = got[:, s + w:s + w + R.REC_GAP]
+        assert not gap.any(), f"{what}: the {R.REC_GAP} columns behind it are not zero, first at (row, column) {cc.first_diff(gap, np.zeros_like(gap))}"
+    assert not (got == cc.SENTINEL).any(), f"wide layout {el}: sentinel left at (row, column) {tuple(np.argwhere(got == cc.SENTINEL)[0])}"
+
+
+@pytest.mark.parametrize("contrast", [0.0, 0.5])
+def test_crops_wide_layout(st, contrast):
+    _crops_wide(st, contrast)
+
+
+@pytest.mark.parametrize("contrast", [0.0, 0.5])
+def test_crops_wide_layout_exact(st_exact, contrast):
+    _crops_wide(st_exact, contrast)

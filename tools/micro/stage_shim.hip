@@ -1,6 +1,7 @@
 // Test-only shim (tests/test_gpu_stages.py): runs ONE stage of the detector / recogniser (fast modes, and the exact mode's split-fp16 stages)
 // with the production plans and packed side tables of a live context, so that each fused launch can be compared with an fp64 reference of its own operation (tests/stage_ref.py).
 // stage_rec_features runs any range of the stages of the recogniser's conv stack (crnn_features_stages, the function a recognition pass runs).
+// stage_crops_wide runs the crop stage of a recognition pass into the wide layout (rec_launch_crops, the call rec_launch_part makes).
 // No kernels of its own.  Built by the test as a shared object against the in-tree library:
 //   hipcc -O2 -std=c++20 -shared -fPIC --offload-arch=gfx950 -Ibb-ocr_amd/csrc -Iinclude tools/micro/stage_shim.hip -Lbb-ocr_amd -lbbocr -o stage_shim.so
 // Every function takes the bbocr_ctx* of a Reader, device pointers of caller-owned tensors with their element counts (checked against the
@@ -94,6 +95,52 @@ int plan_part(const int* widths, int n, RecPart& part) {
     }
 }
 size_t act_elems(const Act& a) { return (size_t)a.N * a.H * a.W * a.C; }
+
+// the boxes of ONE H x W page (hori [n_hori][4], then free_q [n_free][4][2]) planned as a recognition pass plans them: plan_horizontal /
+// plan_free (a skipped box leaves no job; box[i] = position of job i in the caller's list), scratch offsets, all of them one part
+struct CropPlan {
+    std::vector<BoxJob> jobs;
+    std::vector<int> box;
+    RecPart part;
+    size_t a_total = 0, w_total = 0;
+};
+bool crop_boxes_ok(int H, int W, const int* hori, int n_hori, const double* free_q, int n_free) {
+    return dims_ok(1, H, W) && n_hori >= 0 && n_free >= 0 && n_hori + n_free > 0 && n_hori + n_free <= 4096 && (hori || !n_hori) && (free_q || !n_free);
+}
+int plan_crops(int H, int W, const int* hori, int n_hori, const double* free_q, int n_free, CropPlan& p) {
+    try {
+        for (int i = 0; i < n_hori + n_free; ++i) {
+            BoxJob j;
+            bool taken;
+            if (i < n_hori) {
+                std::array<int, 4> b;
+                memcpy(b.data(), hori + (size_t)i * 4, 16);
+                taken = plan_horizontal(b, 0, H, W, j);
+            } else {
+                std::array<double, 8> f;
+                memcpy(f.data(), free_q + (size_t)(i - n_hori) * 8, 64);
+                taken = plan_free(f, 0, j);
+            }
+            if (!taken) continue;
+            p.jobs.push_back(j);
+            p.box.push_back(i);
+        }
+        rec_layout_scratch(p.jobs, 0, p.a_total, p.w_total);
+        std::vector<int> all(p.jobs.size());
+        for (size_t i = 0; i < all.size(); ++i) all[i] = (int)i;
+        rec_plan_part(p.jobs, all, 0, 0, p.part);
+        return 0;
+    } catch (const StatusError& se) {
+        g_err = se.msg;
+        return SHIM_STATUS + std::abs(se.code);
+    } catch (const std::exception& ex) {
+        g_err = ex.what();
+        return SHIM_UNKNOWN;
+    } catch (...) {
+        g_err = "unknown failure";
+        return SHIM_UNKNOWN;
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -348,6 +395,54 @@ int stage_rec_features(bbocr_ctx* c, const int* widths, int n, int first, int la
         const Act o = in_arena(c, [&] { return crnn_features_stages(c, part, dd, a, first, last); });
         if (!to_seq && act_elems(o) != out_elems) fail(BBOCR_ERR_INTERNAL, "stage shim: output size differs from the caller's tensor");
         return hipMemcpyAsync(out, o.p, out_elems * 2, hipMemcpyDeviceToDevice, c->stream);
+    });
+}
+
+// The wide layout of the crops of one page's boxes (host only).  Per descriptor k of the part, in the order they stand in the wide image: the
+// position of its box in the caller's list (hori, then free_q), its first column and its padded width; n: descriptors (boxes not skipped);
+// cols: columns of the wide image.  The three arrays hold n_hori + n_free entries.
+int stage_crops_wide_plan(int H, int W, const int* hori, int n_hori, const double* free_q, int n_free, int* box_out, int* slot_out, int* imgw_out, int* n,
+                          int* cols) {
+    g_err.clear();
+    NEED(crop_boxes_ok(H, W, hori, n_hori, free_q, n_free) && box_out && slot_out && imgw_out && n && cols);
+    CropPlan p;
+    if (const int rc = plan_crops(H, W, hori, n_hori, free_q, n_free, p)) return rc;
+    for (size_t k = 0; k < p.part.descs.size(); ++k) {
+        box_out[k] = p.box[p.part.order[k]];
+        slot_out[k] = p.part.descs[k].slot;
+        imgw_out[k] = p.part.descs[k].imgW;
+    }
+    *n = (int)p.part.descs.size();
+    *cols = (int)p.part.cols;
+    return 0;
+}
+
+// The crop stage of a recognition pass over that plan: gray uint8 [H][W] -> stage A (gather / warp + cv2 resize) into the context's crop
+// scratch, contrast > 0: adjust_contrast_grey's LUTs as the contrast retry derives them, stage B (AlignCollate) into `wide` [64][cols] in the
+// context's recogniser mode.  Only the columns of the crops and the REC_GAP columns after each are written.
+int stage_crops_wide(bbocr_ctx* c, const uint8_t* gray, size_t gray_elems, int H, int W, const int* hori, int n_hori, const double* free_q, int n_free,
+                     double contrast, uint16_t* wide, size_t wide_elems) {
+    g_err.clear();
+    NEED(c && c->crnn_loaded && gray && wide && crop_boxes_ok(H, W, hori, n_hori, free_q, n_free) && gray_elems == px(1, H, W) && contrast >= 0);
+    CropPlan p;
+    if (const int rc = plan_crops(H, W, hori, n_hori, free_q, n_free, p)) return rc;
+    NEED(!p.part.descs.empty() && p.part.cols < ((size_t)1 << 20) && wide_elems == (size_t)64 * p.part.cols);
+    std::vector<uint8_t> luts;                    // the source of an asynchronous copy: lives until run_stage has waited for the stream
+    return run_stage(c, [&] {
+        c->crop_scratch.ensure(std::max<size_t>(p.a_total, 16));
+        c->crop_hscratch.ensure(std::max<size_t>(p.a_total, 16));
+        c->crop_wscratch.ensure(std::max<size_t>(p.w_total, 16));
+        c->crop_luts.ensure(256);
+        const GrayPages g{gray, H, W};
+        const CropDesc* dd = rec_upload_descs(c, p.part, c->crop_desc);
+        rec_launch_crops(c, g, p.part, dd, nullptr, 1);
+        if (contrast > 0 && !crop_contrast_luts(c, dd, p.part.descs, contrast, luts).empty()) {
+            c->crop_luts.ensure(luts.size());
+            HIPCHK(hipMemcpyAsync(c->crop_luts.p, luts.data(), luts.size(), hipMemcpyHostToDevice, c->stream));
+            dd = rec_upload_descs(c, p.part, c->crop_desc);          // the descriptors with their lut_off (the first upload has been waited for)
+        }
+        rec_launch_crops(c, g, p.part, dd, wide, 2);
+        return hipSuccess;
     });
 }
 
