@@ -50,6 +50,19 @@ class bbocr_jpeg_plan(C.Structure):
                 ("chroma", C.c_int)]                             # 1 = 4:4:4, 2 = 4:2:2, 3 = 4:4:0: decodable although `supported` is 0
 
 
+JPEG_FORM_YCBCR, JPEG_FORM_IMREAD = 0, 1                                         # bbocr.h BBOCR_JPEG_FORM_*
+JPEG_UP_NONE, JPEG_UP_H2V1_FANCY, JPEG_UP_H1V2_FANCY, JPEG_UP_H2V2_NOT_NEEDED, JPEG_UP_REPLICATE = range(5)    # bbocr.h BBOCR_JPEG_UP_*
+
+
+class bbocr_jpeg_output(C.Structure):
+    _fields_ = [("scale", C.c_int), ("form", C.c_int), ("dev_out", C.POINTER(C.c_void_p)), ("pitches", C.POINTER(C.c_longlong))]
+
+
+class bbocr_jpeg_scaled_comp(C.Structure):
+    _fields_ = [("block", C.c_int), ("plane_rows", C.c_int), ("plane_cols", C.c_int), ("valid_rows", C.c_int), ("valid_cols", C.c_int),
+                ("upsample", C.c_int)]
+
+
 class bbocr_page(C.Structure):
     _fields_ = [("dev_rgb", C.c_void_p), ("dev_gray", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("rgb_pitch", C.c_longlong),
                 ("gray_pitch", C.c_longlong)]
@@ -160,6 +173,11 @@ PROTOTYPES = {
                                            C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "bbocr_jpeg_scaled_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bbocr_op_jpeg_scaled_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_jpeg_decode_scales": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(bbocr_jpeg_output), C.c_int,
+                                           C.POINTER(C.c_int)]),
+    "bbocr_jpeg_counters": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bbocr_host_jpeg_scaled_geometry": (C.c_int, [C.POINTER(bbocr_jpeg_plan), C.c_int, C.POINTER(bbocr_jpeg_scaled_comp)]),
+    "bbocr_op_jpeg_scaled_class_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
     "bbocr_thumbnail_box": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),
     "bbocr_host_resize_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     "bbocr_jpeg_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

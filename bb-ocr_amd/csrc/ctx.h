@@ -210,6 +210,7 @@ struct bbocr_ctx : WeightView {
     PinBuf jd_pin;                            // the batch's tables + unstuffed entropy bytes, staged for one H2D copy into jd_in
     DevBuf jd_in, jd_work, jd_coef, jd_stage; // per-subsequence states and component planes, coefficients, bbocr_op_jpeg_stage's scratch image
     DevBuf jd_page;                           // bbocr_jpeg_imread: the batch's un-oriented decodes, between the decoder and page_orient
+    long long jd_count[4] = {0, 0, 0, 0};     // bbocr_jpeg_counters: files decoded, entropy runs, IDCT passes, output passes (per file each)
     hipStream_t seq_stream = nullptr;         // per slot: the recogniser's SEQUENCE stage (projections, BiLSTMs, linears, CTC, read-back) -- latency-bound
                                               // launches of 100-300 workgroups that leave most of the card idle -- runs here, behind an event of this
                                               // slot's feature parts, so that it overlaps the OTHER call's detector instead of queueing in front of it

@@ -2,7 +2,9 @@
 // tables of jpegdec.hip (unstuffed segment bytes, subsequence lists, derived Huffman tables) and its launch sequence.  A batch runs on
 // its own stream of the root context, outside the call slots (the contract of bbocr_upload_pages): files decode while two OCR calls run.
 // A batch may be decoded at scale 1/2, 1/4 or 1/8 (bbocr_jpeg_decode_scaled, Pillow's draft): same tables and entropy stages, planes of
-// the output's size, jpegdec.hip's scaled IDCT and output kernels; 4:2:0 and grey files only.
+// the output's size, jpegdec.hip's scaled IDCT and output kernels; 4:2:0 and grey files only.  bbocr_jpeg_decode_scales runs the entropy
+// stages once per file and one IDCT + output pass per requested output (scale 1, 2, 4, 8; YCbCr pixels or, at scale 1, bbocr_jpeg_imread's
+// oriented page), the files of a chroma class at every scale.
 #include "ctx.h"
 
 namespace {
@@ -247,6 +249,19 @@ int scaled_mcu_edge(const bbocr_jpeg_plan& pl, int s) { return (pl.components ==
 size_t scaled_plane_w(const bbocr_jpeg_plan& pl, int s) { return (size_t)pl.mcu_cols * scaled_mcu_edge(pl, s); }
 size_t scaled_plane_bytes(const bbocr_jpeg_plan& pl, int s) { return scaled_plane_w(pl, s) * (size_t)pl.mcu_rows * scaled_mcu_edge(pl, s); }
 int scaled_dim(int v, int s) { return (v + s - 1) / s; }
+// ... of a file of a chroma class: every block is n x n, n = 8 / s, so the Y plane is mcu_rows * n * v rows of mcu_cols * n * h samples and
+// each chroma plane mcu_rows * n rows of mcu_cols * n (jpegdec.hip's jd_idct_scaled_c)
+size_t class_luma_bytes(const bbocr_jpeg_plan& pl, int s) {
+    return (size_t)pl.mcu_cols * (8 / s) * luma_h(pl) * (size_t)pl.mcu_rows * (8 / s) * luma_v(pl);
+}
+size_t class_chroma_bytes(const bbocr_jpeg_plan& pl, int s) { return (size_t)pl.mcu_cols * (8 / s) * (size_t)pl.mcu_rows * (8 / s); }
+// bytes of component c's plane in a decode at scale s (1: the full-scale decode)
+size_t plane_bytes(const bbocr_jpeg_plan& pl, int s, int c) {
+    if (c > 0 && pl.components != 3) return 0;
+    if (s == 1) return c == 0 ? luma_plane_bytes(pl) : chroma_plane_bytes(pl);
+    if (pl.chroma) return c == 0 ? class_luma_bytes(pl, s) : class_chroma_bytes(pl, s);
+    return scaled_plane_bytes(pl, s);
+}
 
 // jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
 bool derive_table(const HuffSpec& h, JpegHuff& t) {
@@ -271,16 +286,19 @@ bool derive_table(const HuffSpec& h, JpegHuff& t) {
     return true;
 }
 
+constexpr int kMaxPasses = 4;                 // IDCT + output passes over one batch's coefficients: one per scale
+struct JpegPass { int scale, px; };           // px: bytes per pixel of a 3-component file's output
+
 struct FileJob {                              // one admitted file of a batch
     JpegParsed ps;
     const uint8_t* file = nullptr;            // its bytes (caller-owned)
-    uint8_t* out = nullptr;                   // where the decoder writes its pixels, rows `pitch` bytes apart
-    long long pitch = 0;
+    uint8_t* out[kMaxPasses] = {nullptr};     // per pass: where the decoder writes its pixels, rows `pitch` bytes apart
+    long long pitch[kMaxPasses] = {0};
     int k = 0;                                // its index in the caller's arrays (status[])
     int nsub = 0, groups = 0, nblocks = 0;
     size_t o_huff, o_quant, o_segbyte, o_segsub, o_subseg, o_data, data_bytes;   // offsets in the input blob
-    size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[3], o_coef; // offsets in the work / coefficient buffers
-    size_t o_page = 0;                        // bbocr_jpeg_imread: offset of the un-oriented decode in jd_page
+    size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[kMaxPasses][3], o_coef; // offsets in the work / coefficient buffers
+    size_t o_page = 0;                        // bbocr_jpeg_imread and the imread form: offset of the un-oriented decode in jd_page
 };
 
 // Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan neither supports nor gives a chroma
@@ -309,14 +327,20 @@ void jpeg_report(const std::vector<FileJob>& jobs, const std::vector<int>& dev_s
     for (size_t i = 0; i < jobs.size(); ++i) status[jobs[i].k] = dev_status[i] ? BBOCR_ERR_DATA : BBOCR_OK;
 }
 
-// The whole decode of the admitted jobs on the JPEG lane's stream `st`; px: bytes per pixel of a 3-component file's output.  Fills
-// dev_status[i] (JD_ERR_* bits of job i) and leaves the descriptors for the stage entry point.  Everything queued is finished on return.
-// scale 2, 4 or 8: the decode at that fraction (the jobs are 4:2:0 or grey files; `out` holds the scaled size).
-void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S, int px, std::vector<int>& dev_status,
-              std::vector<JpegDesc>* descs_out = nullptr, int scale = 1) {
-    const int n = (int)jobs.size();
-    Carve in{align_up(sizeof(JpegDesc) * (size_t)n, 256)}, work{align_up(4 * (size_t)n, 256)}, coef;
-    int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;
+// The whole decode of the admitted jobs on the JPEG lane's stream `st`.  Fills dev_status[i] (JD_ERR_* bits of job i) and leaves the
+// descriptors of the first pass for the stage entry points.  Everything queued is finished on return.
+// The entropy stages run once; then every pass (at most kMaxPasses) runs its IDCT and output stage over the shared coefficients into
+// planes of its own and the jobs' out[p] / pitch[p].  A pass of scale 2, 4 or 8 is the decode at that fraction (`out[p]` holds the scaled
+// size): the 4:2:0 and grey files through jd_idct_scaled / jd_output_scaled, the files of a chroma class through their _c siblings -- the
+// jobs are ordered so that each kind is one run of descriptors (the order of `jobs` may change; dev_status follows it).
+void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S, const std::vector<JpegPass>& passes_out,
+              std::vector<int>& dev_status, std::vector<JpegDesc>* descs_out = nullptr) {
+    const int n = (int)jobs.size(), np = (int)passes_out.size();
+    int n_plain = n;                                                      // the jobs in front of the first file of a chroma class
+    if (std::any_of(passes_out.begin(), passes_out.end(), [](const JpegPass& p) { return p.scale > 1; }))
+        n_plain = (int)(std::stable_partition(jobs.begin(), jobs.end(), [](const FileJob& j) { return j.ps.plan.supported != 0; }) - jobs.begin());
+    Carve in{align_up(sizeof(JpegDesc) * (size_t)n * np, 256)}, work{align_up(4 * (size_t)n, 256)}, coef;
+    int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;                // max_h, max_w: at full scale
     for (FileJob& j : jobs) {
         const bbocr_jpeg_plan& pl = j.ps.plan;
         j.o_huff = in.add(4 * sizeof(JpegHuff));
@@ -329,8 +353,8 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? luma_h(pl) * luma_v(pl) + 2 : 1);
         max_seg = std::max(max_seg, pl.segments);
         max_blocks = std::max(max_blocks, j.nblocks);
-        max_h = std::max(max_h, scaled_dim(pl.height, scale));
-        max_w = std::max(max_w, scaled_dim(pl.width, scale));
+        max_h = std::max(max_h, pl.height);
+        max_w = std::max(max_w, pl.width);
     }
     root->jd_pin.ensure(in.off);
     root->jd_in.ensure(in.off);
@@ -378,9 +402,8 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.w_count = work.add(4 * (size_t)nsub);
         j.w_scan = work.add(4 * (size_t)nsub);
         j.w_first = work.add(4 * (size_t)nsub);
-        j.w_plane[0] = work.add(scale == 1 ? luma_plane_bytes(pl) : scaled_plane_bytes(pl, scale));
-        j.w_plane[1] = work.add(scale == 1 ? chroma_plane_bytes(pl) : (pl.components == 3 ? scaled_plane_bytes(pl, scale) : 0));
-        j.w_plane[2] = work.add(scale == 1 ? chroma_plane_bytes(pl) : (pl.components == 3 ? scaled_plane_bytes(pl, scale) : 0));
+        for (int p = 0; p < np; ++p)
+            for (int c = 0; c < 3; ++c) j.w_plane[p][c] = work.add(plane_bytes(pl, passes_out[p].scale, c));
         j.o_coef = coef.add((size_t)j.nblocks * 128);
     }
     const int passes = max_groups + 1;
@@ -406,9 +429,6 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         d.flags = (int*)(wb + j.w_flags);
         d.status = (int*)wb + k;
         d.coef = (short*)((char*)root->jd_coef.p + j.o_coef);
-        for (int c = 0; c < 3; ++c) d.plane[c] = (uint8_t*)(wb + j.w_plane[c]);
-        d.out = j.out;
-        d.pitch = j.pitch;
         d.huff = (const JpegHuff*)(db + j.o_huff);
         d.quant = (const unsigned short*)(db + j.o_quant);
         d.W = pl.width;
@@ -425,10 +445,15 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         d.nsub = j.nsub;
         d.S = S;
         d.nblocks = j.nblocks;
-        d.px = pl.components == 3 ? px : 1;
         d.passes = passes;
         for (int c = 0; c < 3; ++c) { d.tab_dc[c] = j.ps.tab_dc[c]; d.tab_ac[c] = j.ps.tab_ac[c]; }
-        descs[k] = d;
+        for (int p = 0; p < np; ++p) {                                    // pass p's descriptors: descs[p * n ..]; the entropy stages read pass 0's
+            for (int c = 0; c < 3; ++c) d.plane[c] = (uint8_t*)(wb + j.w_plane[p][c]);
+            d.out = j.out[p];
+            d.pitch = j.pitch[p];
+            d.px = pl.components == 3 ? passes_out[p].px : 1;
+            descs[(size_t)p * n + k] = d;
+        }
     }
     if (descs_out) descs_out->assign(descs, descs + n);
     HIPCHK(hipMemcpyAsync(db, hb, in.off, hipMemcpyHostToDevice, st));
@@ -440,13 +465,27 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     HIPCHK(launch_jd_scan(dd, n, st));
     HIPCHK(launch_jd_write(dd, n, max_groups, st));
     HIPCHK(launch_jd_dc(dd, n, max_seg, st));
-    if (scale == 1) {
-        HIPCHK(launch_jd_idct(dd, n, max_blocks, st));
-        HIPCHK(launch_jd_output(dd, n, max_h, max_w, st));
-    } else {
-        HIPCHK(launch_jd_idct_scaled(dd, n, max_blocks, scale, st));
-        HIPCHK(launch_jd_output_scaled(dd, n, max_h, max_w, scale, st));
+    for (int p = 0; p < np; ++p) {
+        const JpegDesc* dp = dd + (size_t)p * n;
+        const int scale = passes_out[p].scale, ph = scaled_dim(max_h, scale), pw = scaled_dim(max_w, scale);
+        if (scale == 1) {
+            HIPCHK(launch_jd_idct(dp, n, max_blocks, st));
+            HIPCHK(launch_jd_output(dp, n, ph, pw, st));
+            continue;
+        }
+        if (n_plain) {
+            HIPCHK(launch_jd_idct_scaled(dp, n_plain, max_blocks, scale, st));
+            HIPCHK(launch_jd_output_scaled(dp, n_plain, ph, pw, scale, st));
+        }
+        if (n > n_plain) {
+            HIPCHK(launch_jd_idct_scaled_c(dp + n_plain, n - n_plain, max_blocks, scale, st));
+            HIPCHK(launch_jd_output_scaled_c(dp + n_plain, n - n_plain, ph, pw, scale, st));
+        }
     }
+    root->jd_count[0] += n;
+    root->jd_count[1] += n;
+    root->jd_count[2] += (long long)n * np;
+    root->jd_count[3] += (long long)n * np;
     dev_status.assign((size_t)n, 0);
     HIPCHK(hipMemcpyAsync(dev_status.data(), wb, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -473,13 +512,13 @@ int bbocr_jpeg_decode_scaled(bbocr_ctx* ctx, const uint8_t* const* files, const 
         if (!jpeg_scale_ok(scale)) fail(BBOCR_ERR_ARG, "scale must be 1, 2, 4 or 8");
         std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
             const bbocr_jpeg_plan& pl = j.ps.plan;
-            j.out = dev_out[j.k];
-            j.pitch = pitches[j.k];
-            return j.out && j.pitch >= (long long)scaled_dim(pl.width, scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY);
+            j.out[0] = dev_out[j.k];
+            j.pitch[0] = pitches[j.k];
+            return j.out[0] && j.pitch[0] >= (long long)scaled_dim(pl.width, scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY);
         }, scale == 1);
         if (jobs.empty()) return;
         std::vector<int> ds;
-        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, page_px_bytes(layout), ds, nullptr, scale);
+        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, {{scale, page_px_bytes(layout)}}, ds);
         jpeg_report(jobs, ds, status);
     });
 }
@@ -506,21 +545,21 @@ int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
         std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
             const bbocr_jpeg_plan& pl = j.ps.plan;
             if (!dev_out[j.k] || pitches[j.k] < (long long)page_px_bytes(PAGE_BGR) * (pl.orientation >= 5 ? pl.height : pl.width)) return false;
-            j.pitch = (long long)pl.width * page_px_bytes(decoded(pl));
-            j.o_page = pages.add((size_t)j.pitch * (size_t)pl.height);
+            j.pitch[0] = (long long)pl.width * page_px_bytes(decoded(pl));
+            j.o_page = pages.add((size_t)j.pitch[0] * (size_t)pl.height);
             return true;
         });
         if (jobs.empty()) return;
         ctx->jd_page.ensure(pages.off);
-        for (FileJob& j : jobs) j.out = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
+        for (FileJob& j : jobs) j.out[0] = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
         std::vector<int> ds;
-        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, page_px_bytes(PAGE_YCC4), ds);
+        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, {{1, page_px_bytes(PAGE_YCC4)}}, ds);
         jpeg_report(jobs, ds, status);
         for (size_t i = 0; i < jobs.size(); ++i) {
             const FileJob& j = jobs[i];
             const bbocr_jpeg_plan& pl = j.ps.plan;
             if (ds[i]) continue;
-            HIPCHK(launch_page_orient(j.out, pl.height, pl.width, (size_t)j.pitch, decoded(pl), pl.orientation, PAGE_BGR, dev_out[j.k],
+            HIPCHK(launch_page_orient(j.out[0], pl.height, pl.width, (size_t)j.pitch[0], decoded(pl), pl.orientation, PAGE_BGR, dev_out[j.k],
                                       (size_t)pitches[j.k], st));
         }
         HIPCHK(hipStreamSynchronize(st));
@@ -539,8 +578,8 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
             const size_t pix = (size_t)pl.width * pl.height * pl.components;
             if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
             ctx->jd_stage.ensure(pix);                           // the pixels go to a scratch image unless they are the stage's output
-            j.out = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
-            j.pitch = (long long)pl.width * pl.components;
+            j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+            j.pitch[0] = (long long)pl.width * pl.components;
             return true;
         });
         if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file");
@@ -548,7 +587,7 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
         const size_t ysz = luma_plane_bytes(pl), csz = chroma_plane_bytes(pl);
         std::vector<int> ds;
         std::vector<JpegDesc> descs;
-        jpeg_run(ctx, s, jobs, S, 3, ds, &descs);
+        jpeg_run(ctx, s, jobs, S, {{1, 3}}, ds, &descs);
         jpeg_report(jobs, ds, &status);
         if (file_status) *file_status = status;
         const JpegDesc& d = descs[0];
@@ -593,8 +632,8 @@ int bbocr_op_jpeg_scaled_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, s
             const size_t pix = (size_t)scaled_dim(pl.width, scale) * scaled_dim(pl.height, scale) * pl.components;
             if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
             ctx->jd_stage.ensure(pix);
-            j.out = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
-            j.pitch = (long long)scaled_dim(pl.width, scale) * pl.components;
+            j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+            j.pitch[0] = (long long)scaled_dim(pl.width, scale) * pl.components;
             return true;
         }, false);
         if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file, or it is of a chroma class");
@@ -603,12 +642,132 @@ int bbocr_op_jpeg_scaled_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, s
         if (stage == 2 && dst_bytes < psz * pl.components) fail(BBOCR_ERR_ARG, "destination too small");
         std::vector<int> ds;
         std::vector<JpegDesc> descs;
-        jpeg_run(ctx, s, jobs, JD_SUBSEQ_BITS, 3, ds, &descs, scale);
+        jpeg_run(ctx, s, jobs, JD_SUBSEQ_BITS, {{scale, 3}}, ds, &descs);
         jpeg_report(jobs, ds, &status);
         if (file_status) *file_status = status;
         if (stage == 2)
             for (int c = 0; c < pl.components; ++c)
                 HIPCHK(hipMemcpyAsync((char*)dev_dst + psz * c, descs[0].plane[c], psz, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    });
+}
+
+int bbocr_jpeg_decode_scales(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, const bbocr_jpeg_output* outputs,
+                             int n_outputs, int* status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
+        if (!files || !bytes || !outputs || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
+        if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
+        if (n_outputs < 1 || n_outputs > kMaxPasses) fail(BBOCR_ERR_ARG, "1 .. 4 outputs, one per scale");
+        int imread = -1;                                                  // the output of the imread form
+        for (int o = 0; o < n_outputs; ++o) {
+            const bbocr_jpeg_output& O = outputs[o];
+            if (!O.dev_out || !O.pitches || !jpeg_scale_ok(O.scale)) fail(BBOCR_ERR_ARG, "an output needs destinations, pitches and a scale of 1, 2, 4 or 8");
+            if (O.form != BBOCR_JPEG_FORM_YCBCR && O.form != BBOCR_JPEG_FORM_IMREAD) fail(BBOCR_ERR_ARG, "unknown output form");
+            if (O.form == BBOCR_JPEG_FORM_IMREAD && O.scale != 1) fail(BBOCR_ERR_ARG, "the imread form exists at scale 1 only");
+            for (int q = 0; q < o; ++q)
+                if (outputs[q].scale == O.scale) fail(BBOCR_ERR_ARG, "a scale is named twice");
+            if (O.form == BBOCR_JPEG_FORM_IMREAD) imread = o;
+        }
+        // the imread form's un-oriented decode goes to jd_page, as in bbocr_jpeg_imread
+        auto decoded = [](const bbocr_jpeg_plan& pl) { return pl.components == 3 ? PAGE_YCC4 : PAGE_GRAY; };
+        Carve pages;
+        std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            for (int o = 0; o < n_outputs; ++o) {
+                const bbocr_jpeg_output& O = outputs[o];
+                if (!O.dev_out[j.k]) return false;
+                if (o == imread) {
+                    if (O.pitches[j.k] < (long long)page_px_bytes(PAGE_BGR) * (pl.orientation >= 5 ? pl.height : pl.width)) return false;
+                    j.pitch[o] = (long long)pl.width * page_px_bytes(decoded(pl));
+                } else {
+                    if (O.pitches[j.k] < (long long)scaled_dim(pl.width, O.scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY)) return false;
+                    j.out[o] = O.dev_out[j.k];
+                    j.pitch[o] = O.pitches[j.k];
+                }
+            }
+            if (imread >= 0) j.o_page = pages.add((size_t)j.pitch[imread] * (size_t)pl.height);
+            return true;
+        });
+        if (jobs.empty()) return;
+        std::vector<JpegPass> passes;
+        for (int o = 0; o < n_outputs; ++o) passes.push_back({outputs[o].scale, page_px_bytes(o == imread ? (int)PAGE_YCC4 : layout)});
+        if (imread >= 0) {
+            ctx->jd_page.ensure(pages.off);
+            for (FileJob& j : jobs) j.out[imread] = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
+        }
+        std::vector<int> ds;
+        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, passes, ds);
+        jpeg_report(jobs, ds, status);
+        if (imread < 0) return;
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            const FileJob& j = jobs[i];
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            if (ds[i]) continue;
+            HIPCHK(launch_page_orient(j.out[imread], pl.height, pl.width, (size_t)j.pitch[imread], decoded(pl), pl.orientation, PAGE_BGR,
+                                      outputs[imread].dev_out[j.k], (size_t)outputs[imread].pitches[j.k], st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+    });
+}
+
+int bbocr_jpeg_counters(bbocr_ctx* ctx, long long* out) {
+    return status_of(ctx, [&] {
+        if (!out) fail(BBOCR_ERR_ARG, "bad counter arguments");
+        std::lock_guard<std::mutex> lk(ctx->jpeg_lane.mu);
+        std::memcpy(out, ctx->jd_count, sizeof ctx->jd_count);
+    });
+}
+
+int bbocr_host_jpeg_scaled_geometry(const bbocr_jpeg_plan* plan, int scale, bbocr_jpeg_scaled_comp* comps) {
+    if (!plan || !comps || (scale != 2 && scale != 4 && scale != 8) || !jpeg_taken(*plan)) return BBOCR_ERR_ARG;
+    const bbocr_jpeg_plan& pl = *plan;
+    if ((pl.components != 1 && pl.components != 3) || pl.mcu_cols < 1 || pl.mcu_rows < 1) return BBOCR_ERR_ARG;
+    const int n = 8 / scale, h = luma_h(pl), v = luma_v(pl), oh = scaled_dim(pl.height, scale), ow = scaled_dim(pl.width, scale);
+    std::memset(comps, 0, 3 * sizeof *comps);
+    for (int c = 0; c < pl.components; ++c) {
+        bbocr_jpeg_scaled_comp& g = comps[c];
+        if (pl.components == 3 && !pl.chroma) {                           // 4:2:0: chroma blocks twice the edge, every plane of the output's size
+            g = {c == 0 ? n : 2 * n, pl.mcu_rows * 2 * n, pl.mcu_cols * 2 * n, oh, ow, c == 0 ? BBOCR_JPEG_UP_NONE : BBOCR_JPEG_UP_H2V2_NOT_NEEDED};
+        } else if (c == 0) {
+            g = {n, pl.mcu_rows * n * v, pl.mcu_cols * n * h, oh, ow, BBOCR_JPEG_UP_NONE};
+        } else {
+            const int up = h * v == 1 ? BBOCR_JPEG_UP_NONE : (scale == 8 ? BBOCR_JPEG_UP_REPLICATE : (h == 2 ? BBOCR_JPEG_UP_H2V1_FANCY : BBOCR_JPEG_UP_H1V2_FANCY));
+            g = {n, pl.mcu_rows * n, pl.mcu_cols * n, scaled_dim(oh, v), scaled_dim(ow, h), up};
+        }
+    }
+    return BBOCR_OK;
+}
+
+int bbocr_op_jpeg_scaled_class_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
+                                     int* file_status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
+        if (!file || !dev_dst || (stage != 2 && stage != 3) || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
+        if (scale != 2 && scale != 4 && scale != 8) fail(BBOCR_ERR_ARG, "scale must be 2, 4 or 8");
+        int status = 0;
+        std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
+            const bbocr_jpeg_plan& pl = j.ps.plan;
+            if (!pl.chroma) return false;
+            const size_t pix = (size_t)scaled_dim(pl.width, scale) * scaled_dim(pl.height, scale) * 3;
+            if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
+            ctx->jd_stage.ensure(pix);
+            j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+            j.pitch[0] = (long long)scaled_dim(pl.width, scale) * 3;
+            return true;
+        });
+        if (jobs.empty()) fail(BBOCR_ERR_ARG, "not a file of a chroma class the plan takes");
+        const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
+        const size_t ysz = class_luma_bytes(pl, scale), csz = class_chroma_bytes(pl, scale);
+        if (stage == 2 && dst_bytes < ysz + 2 * csz) fail(BBOCR_ERR_ARG, "destination too small");
+        std::vector<int> ds;
+        std::vector<JpegDesc> descs;
+        jpeg_run(ctx, s, jobs, JD_SUBSEQ_BITS, {{scale, 3}}, ds, &descs);
+        jpeg_report(jobs, ds, &status);
+        if (file_status) *file_status = status;
+        if (stage == 2) {
+            HIPCHK(hipMemcpyAsync(dev_dst, descs[0].plane[0], ysz, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz, descs[0].plane[1], csz, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz + csz, descs[0].plane[2], csz, hipMemcpyDeviceToDevice, s));
+        }
         HIPCHK(hipStreamSynchronize(s));
     });
 }

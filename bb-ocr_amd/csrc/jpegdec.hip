@@ -12,6 +12,8 @@
 //               into the caller's tensor
 //   jd_idct_scaled / jd_output_scaled   the same two stages of a decode at scale 1/2, 1/4 or 1/8 (Pillow's draft): jidctred.c's reduced
 //               IDCTs per component, no upsampling (4:2:0 and grey files only)
+//   jd_idct_scaled_c / jd_output_scaled_c   those two stages for the files of a chroma class (4:4:4, 4:2:2, 4:4:0): n x n blocks for every
+//               component, chroma upsampled at the reduced size (fancy at 1/2 and 1/4, replicated at 1/8)
 // An MCU holds hs x vs luma blocks (row after row), then one Cb and one Cr block: 2 x 2 for 4:2:0, 1 x 1 / 2 x 1 / 1 x 2 for the others.
 // The bytes are untrusted: every stream read is clamped to its segment (past the end: 1-bits), every store is index-checked, every loop
 // has a trip count fixed by the host's plan (S, lanes per workgroup, items per segment).
@@ -423,6 +425,89 @@ template <int SC> __global__ void __launch_bounds__(256) jd_output_scaled_kernel
     }
 }
 
+// ---- the decode at scale 1 / SC of a file of a chroma class (4:4:4, 4:2:2, 4:4:0).  jdmaster.c doubles a component's DCT_scaled_size only
+// when both directions allow it; here one does not, so EVERY block comes out n x n, n = 8 / SC, and the chroma keeps the file's sampling:
+// Y [mcuy * n * vs][mcux * n * hs], Cb and Cr [mcuy * n][mcux * n].  jd_output_scaled_c upsamples: jdsample.c's fancy h2v1 / h1v2 at SC 2
+// and 4, plain replication at SC 8 (min_DCT_scaled_size 1 turns fancy upsampling off), nothing for 4:4:4.
+
+// A block's 8 x 8 words in LDS with rows JD_ROW words apart and blocks JD_BLK: a half-wave's 4 blocks x 8 lanes then touch 32 different
+// banks ((8 b + l) mod 32 in the column pass, (8 b + 9 l) mod 32 in the row pass and the dequantising stores), where blk[8][64] of
+// jd_idct_scaled puts the 4 blocks of a half-wave on one bank.
+constexpr int JD_ROW = 9, JD_BLK = 72;
+
+// jd_idct_scaled's shape: eight blocks per wavefront, one 16-byte coefficient load per lane, the first-pass columns the second pass never
+// reads skipped, one word of n bytes stored per row.  The MCU geometry is data (hs, vs) as in jd_idct.
+template <int SC> __global__ void __launch_bounds__(64) jd_idct_scaled_c_kernel(const JpegDesc* __restrict__ descs) {
+    __shared__ int blk[8][JD_BLK];
+    constexpr int n = 8 / SC;
+    const JpegDesc d = descs[blockIdx.y];
+    const int t = threadIdx.x, b = t >> 3, l = t & 7;
+    const int id = blockIdx.x * 8 + b;
+    if ((int)blockIdx.x * 8 >= d.nblocks) return;
+    const bool valid = id < d.nblocks;
+    const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
+    const int c = jd_comp(d, j);
+    if (valid && (n > 1 || l == 0)) {                                   // n == 1: the DC term alone is read
+        const uint4 raw = *(const uint4*)(d.coef + (size_t)id * 64 + l * 8);     // 16-byte aligned: blocks are 128 bytes apart
+        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+        const unsigned short* q = d.quant + c * 64 + l * 8;
+        for (int i = 0; i < 4; ++i) {
+            blk[b][l * JD_ROW + 2 * i] = (int)(short)(w[i] & 0xFFFFu) * (int)q[2 * i];
+            blk[b][l * JD_ROW + 2 * i + 1] = (int)(short)(w[i] >> 16) * (int)q[2 * i + 1];
+        }
+    }
+    __syncthreads();
+    if (valid) {
+        int* col = &blk[b][l];
+        if (n == 4) { if (l != 4) idct4(col, JD_ROW, true); }
+        else if (n == 2) { if (l == 0 || (l & 1)) idct2(col, JD_ROW, true); }
+    }
+    __syncthreads();
+    if (valid && l < n) {
+        int* row = &blk[b][l * JD_ROW];
+        if (n == 4) idct4(row, 1, false);
+        else if (n == 2) idct2(row, 1, false);
+        else row[0] = idct1(row[0]);
+        const int hs = c == 0 ? d.hs : 1, vs = c == 0 ? d.vs : 1;
+        const int pw = d.mcux * n * hs;
+        const int mx = mcu % d.mcux, my = mcu / d.mcux;
+        // luma block j of an MCU sits at (j / hs, j % hs)
+        const int by = c == 0 ? (j / d.hs) * n : 0, bx = c == 0 ? (j % d.hs) * n : 0;
+        uint8_t* o = d.plane[c] + (size_t)(my * vs * n + by + l) * pw + mx * n * hs + bx;    // pw and the offsets are multiples of n
+        if (n == 4) *(unsigned*)o = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
+        else if (n == 2) *(unsigned short*)o = (unsigned short)(row[0] | (row[1] << 8));
+        else o[0] = (uint8_t)row[0];
+    }
+}
+
+// one output pixel per lane; every chroma read stays inside the valid extent ceil(OH / vs) x ceil(OW / hs), not the padded plane
+template <int SC> __global__ void __launch_bounds__(256) jd_output_scaled_c_kernel(const JpegDesc* __restrict__ descs) {
+    constexpr int n = 8 / SC;
+    const JpegDesc d = descs[blockIdx.z];
+    const int OW = (d.W + SC - 1) / SC, OH = (d.H + SC - 1) / SC;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= OW || y >= OH || d.ncomp != 3) return;
+    const int yp = d.mcux * n * d.hs, cp = d.mcux * n;
+    const int ch = (OH + d.vs - 1) / d.vs, cw = (OW + d.hs - 1) / d.hs;
+    unsigned v[3];
+    v[0] = d.plane[0][(size_t)y * yp + x];
+    for (int c = 1; c < 3; ++c) {
+        const uint8_t* __restrict__ pl = d.plane[c];
+        if (d.hs == 2) v[c] = SC == 8 ? pl[(size_t)y * cp + (x >> 1)] : (unsigned)th_fancy_h2v1(pl, cp, cw, y, x);
+        else if (d.vs == 2) v[c] = SC == 8 ? pl[(size_t)(y >> 1) * cp + x] : (unsigned)th_fancy_h1v2(pl, cp, ch, y, x);
+        else v[c] = pl[(size_t)y * cp + x];
+    }
+    uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
+    if (d.px == 4 && ((d.pitch | (long long)(size_t)d.out) & 3) == 0) {
+        *(unsigned*)o = v[0] | (v[1] << 8) | (v[2] << 16) | (255u << 24);
+    } else {
+        o[0] = (uint8_t)v[0];
+        o[1] = (uint8_t)v[1];
+        o[2] = (uint8_t)v[2];
+        if (d.px == 4) o[3] = 255;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_jd_sync(const JpegDesc* descs, int n, int max_groups, int pass, hipStream_t s) {
@@ -464,6 +549,23 @@ hipError_t launch_jd_output_scaled(const JpegDesc* descs, int n, int max_h, int 
     if (scale == 2) hipLaunchKernelGGL(jd_output_scaled_kernel<2>, grid, dim3(256), 0, s, descs);
     else if (scale == 4) hipLaunchKernelGGL(jd_output_scaled_kernel<4>, grid, dim3(256), 0, s, descs);
     else if (scale == 8) hipLaunchKernelGGL(jd_output_scaled_kernel<8>, grid, dim3(256), 0, s, descs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// scale: 2, 4 or 8; the descriptors are of files of a chroma class only (3 components, hs * vs <= 2)
+hipError_t launch_jd_idct_scaled_c(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s) {
+    const dim3 grid((unsigned)((max_blocks + 7) / 8), (unsigned)n);
+    if (scale == 2) hipLaunchKernelGGL(jd_idct_scaled_c_kernel<2>, grid, dim3(64), 0, s, descs);
+    else if (scale == 4) hipLaunchKernelGGL(jd_idct_scaled_c_kernel<4>, grid, dim3(64), 0, s, descs);
+    else if (scale == 8) hipLaunchKernelGGL(jd_idct_scaled_c_kernel<8>, grid, dim3(64), 0, s, descs);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_jd_output_scaled_c(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s) {
+    const dim3 grid((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n);
+    if (scale == 2) hipLaunchKernelGGL(jd_output_scaled_c_kernel<2>, grid, dim3(256), 0, s, descs);
+    else if (scale == 4) hipLaunchKernelGGL(jd_output_scaled_c_kernel<4>, grid, dim3(256), 0, s, descs);
+    else if (scale == 8) hipLaunchKernelGGL(jd_output_scaled_c_kernel<8>, grid, dim3(256), 0, s, descs);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -386,3 +386,8 @@ hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, 
 // entropy stages above are the same.  The planes are then mcuy * e rows of mcux * e samples each, e = 16 / scale (grey: 8 / scale).
 hipError_t launch_jd_idct_scaled(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s);
 hipError_t launch_jd_output_scaled(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s);
+// the same two stages for files of a chroma class (4:4:4, 4:2:2, 4:4:0; hs, vs = the luma sampling): every block n x n, n = 8 / scale, into
+// Y [mcuy * n * vs][mcux * n * hs] and Cb, Cr [mcuy * n][mcux * n]; the output stage upsamples the chroma (h2v1 / h1v2 fancy at scale 2 and
+// 4, replication at scale 8) from its valid extent ceil(OH / vs) x ceil(OW / hs)
+hipError_t launch_jd_idct_scaled_c(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s);
+hipError_t launch_jd_output_scaled_c(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s);

@@ -119,7 +119,7 @@ def _ocr_input_device(reader, image_path, image_index=None, decode_once=True, de
 
 
 def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, on_device=False,
-                  device_decode=False, applied=None, pages=None):
+                  device_decode=False, applied=None, pages=None, page=None):
     """The page ``extract_text_with_ocr`` would hand to the down-scaling step (:425-485), as a host array: decoded like ``cv2.imread``
     (BGR, EXIF-transposed), uploaded, pre-processed on the card (gray), edge-cropped (a view) and auto-cropped on the card; only the
     final crop comes back.  A step that returns None in the reference leaves the page as it was.  ``on_device=True``: the crop stays on
@@ -127,7 +127,8 @@ def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent
     ``preprocess.imread_bgr_device`` -- a baseline JPEG file is decoded, oriented and channel-ordered on the card (same pixels);
     ``device_decode="chroma"``: 4:4:4, 4:2:2 and 4:4:0 files as well.  ``applied``: a list that receives the names of the steps that changed the page (where it stays empty the reference goes on with the
     original file).  ``pages``: a dict that receives, under the same names, the device page each of those steps left (views of one another
-    where the step is a crop) -- what ``trace_previews`` draws from."""
+    where the step is a crop) -- what ``trace_previews`` draws from.  ``page``: ``cv2.imread``'s page of the file, already on the card (BGR
+    ``[H',W',3]``, as ``imread_bgr_device`` returns it): the file is then not read again."""
     from .preprocess import _imread_bgr, auto_crop_box_device, central_edge_crop_box, imread_bgr_device, preprocess_bgr_device
 
     applied = [] if applied is None else applied
@@ -137,7 +138,8 @@ def ocr_page_crop(reader, image_path, use_preprocessing=False, edge_crop_percent
         if pages is not None:
             pages[step] = page
 
-    page = imread_bgr_device(reader, image_path, device_decode) if device_decode else reader._to_dev(_imread_bgr(image_path))
+    if page is None:
+        page = imread_bgr_device(reader, image_path, device_decode) if device_decode else reader._to_dev(_imread_bgr(image_path))
     if use_preprocessing:
         page = preprocess_bgr_device(reader, page)
         done("preprocess")
@@ -613,24 +615,54 @@ def trace_previews(reader, image_paths, use_preprocessing=False, edge_crop_perce
     string for string: ``original_b64`` -- ``_image_to_data_url`` of the file itself (``Image.open`` does not transpose; an unloaded JPEG
     is decoded at the draft scale) -- and, where the step changed the page, ``preprocessed_b64``, ``edge_cropped_b64`` and
     ``auto_cropped_b64`` of the PNG the reference wrote after it; a key is absent where its step is off or returns None in the
-    reference.  The pages are those of ``ocr_page_crop`` (pre-processed once, crops as views; the file is read once and decoded once per scale: at the draft scale for the
-    original's preview, at full scale for the crop chain -- both run the entropy stages) thumbnailed on the card
-    (``preprocess.preview_device``): only pages of at most 800 pixels come back.  ``device_decode``: baseline 4:2:0 / grey JPEG files are
-    decoded on the card, for the original's preview at the draft scale; everything else takes ``preprocess.preview_host``."""
+    reference.  The pages are those of ``ocr_page_crop`` (pre-processed once, crops as views) thumbnailed on the card
+    (``preprocess.preview_device``): only pages of at most 800 pixels come back.  ``device_decode``: baseline 4:2:0 / grey JPEG files --
+    ``"chroma"``: 4:4:4, 4:2:2 and 4:4:0 files as well -- are decoded on the card; everything else takes ``preprocess.preview_host``.  A
+    file the decoder takes is read once and, with a crop setting on, decoded ONCE (``Reader.decode_jpeg_scales_batch``): one run of the
+    entropy stages yields the decode at the draft scale for the original's preview and ``cv2.imread``'s full-scale page the crop chain
+    starts from; when the draft scale is 1 the two are one decode, oriented on the card."""
     from .preprocess import preview_device
     from .reader import _file_bytes
 
     if crop_margin < 0:
         raise ValueError("crop_margin must be >= 0")
+    chain = use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr
     out = []
     for path in image_paths:
-        source = _file_bytes(path) if device_decode else path             # read once for both decodes
-        trace = {"original_b64": preview_device(reader, source, device_decode=device_decode)}
-        if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
+        source = _file_bytes(path) if device_decode else path             # read once
+        once = _trace_decode_once(reader, source, device_decode) if device_decode and chain else None
+        trace = {"original_b64": once[0] if once else preview_device(reader, source, device_decode=device_decode)}
+        if chain:
             pages = {}
             ocr_page_crop(reader, source, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=True,
-                          device_decode=device_decode, pages=pages)
+                          device_decode=device_decode, pages=pages, page=once[1] if once else None)
             for step, page in pages.items():
                 trace[TRACE_KEYS[step]] = preview_device(reader, page)
         out.append(trace)
     return out
+
+
+def _trace_decode_once(reader, data, device_decode):
+    """Both uses of a traced file from one run of the entropy stages: ``(original_b64, cv2.imread's page on the card)``, or None for a
+    file the device decoder does not take or whose entropy-coded data it reports damaged (the caller keeps its two-step path)."""
+    import io
+
+    from PIL import Image
+
+    from .preprocess import PAGE_GRAY, PAGE_YCBCR4, PREVIEW_MAX_DIM, _preview_of_decode, _preview_string, orient_page_device, preview_draft_scale
+    from .reader import JpegPage, jpeg_chroma, jpeg_plan
+
+    plan = jpeg_plan(data)
+    if not (plan.supported or (jpeg_chroma(device_decode) and plan.chroma)):
+        return None
+    s = preview_draft_scale(plan, PREVIEW_MAX_DIM)
+    decodes, status = reader.decode_jpeg_scales_batch([JpegPage(data, plan)], (1,) if s == 1 else (1, s), imread=s != 1)
+    if status[0] != 0:
+        return None
+    drafted = decodes[0][s]
+    if s == 1:                                                            # one decode: the un-oriented pixels, oriented for the crop chain
+        page = orient_page_device(reader, drafted, PAGE_GRAY if drafted.ndim == 2 else PAGE_YCBCR4, int(plan.orientation))
+    else:
+        page = decodes[0][1]
+    icc = Image.open(io.BytesIO(data)).info.get("icc_profile")              # headers only
+    return _preview_string(_preview_of_decode(reader, drafted, plan, s, PREVIEW_MAX_DIM), icc), page

@@ -308,59 +308,95 @@ def thumbnail_box_device(reader, page_dev, layout, out_h, out_w, box_w, box_h):
     return out
 
 
-def _preview_jpeg_device(reader, data, plan, max_dim):
-    """``Image.open(file).thumbnail((max_dim, max_dim))`` of a file the plan supports, on the card: the pixels (RGB [h,w,3] or gray [h,w],
-    a device tensor), or None when the decoder reports the entropy-coded data damaged"""
-    from .reader import JpegPage, draft_scale
+def preview_draft_scale(plan, max_dim=PREVIEW_MAX_DIM):
+    """The scale ``Image.thumbnail((max_dim, max_dim))`` decodes an unloaded JPEG file of the plan's size at: ``draft(None, size *
+    reducing_gap)``'s, 1 for a file that is not resized"""
+    from .reader import draft_scale
 
+    H, W = int(plan.height), int(plan.width)
+    return draft_scale(W, H, int(max_dim * 2.0), int(max_dim * 2.0)) if max(H, W) > int(max_dim) else 1
+
+
+def _preview_of_decode(reader, page, plan, s, max_dim):
+    """``Image.thumbnail((max_dim, max_dim))``'s pixels from the file's decode at its draft scale ``s`` (``page``: the decoder's own tensor,
+    padded YCbCr [oh,ow,4] or gray [oh,ow]): RGB [h,w,3] or gray [h,w] on the card"""
     H, W = int(plan.height), int(plan.width)
     oh, ow = C.c_int(), C.c_int()
     reader._check(reader._lib.bbocr_thumbnail_dims(H, W, int(max_dim), C.byref(oh), C.byref(ow)))
     oh, ow = oh.value, ow.value
-    thumb = max(H, W) > int(max_dim)
-    s = draft_scale(W, H, int(max_dim * 2.0), int(max_dim * 2.0)) if thumb else 1        # thumbnail(): draft(None, size * reducing_gap)
-    t, status = reader.decode_jpeg_batch([JpegPage(data, plan)], padded=True, scale=s)
-    if status[0] != 0:
-        return None
-    page = t[0]
     layout = PAGE_GRAY if page.ndim == 2 else PAGE_YCBCR4
-    if not thumb or (page.shape[0], page.shape[1]) == (oh, ow):         # no resize: the (drafted) decode itself
-        return page if layout == PAGE_GRAY else reader.pages_from_ycc(t)[0][0]
+    if max(H, W) <= int(max_dim) or (page.shape[0], page.shape[1]) == (oh, ow):         # no resize: the (drafted) decode itself
+        return page if layout == PAGE_GRAY else reader.pages_from_ycc(page[None])[0][0]
     return thumbnail_box_device(reader, page, layout, oh, ow, W / s, H / s)
 
 
-def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True):
-    """``preview_host(source, max_dim)``, character for character, with the pixels made on the card; only the page of at most ``max_dim``
-    pixels comes back, and Pillow writes the PNG from it.
+def _preview_jpeg_device(reader, data, plan, max_dim):
+    """``Image.open(file).thumbnail((max_dim, max_dim))`` of a file the decoder takes, on the card: the pixels (RGB [h,w,3] or gray [h,w],
+    a device tensor), or None when the decoder reports the entropy-coded data damaged.  A file of a chroma class goes through
+    ``bbocr_jpeg_decode_scales``, which decodes it at every scale; every other file through ``bbocr_jpeg_decode_scaled`` as before."""
+    from .reader import JpegPage
 
-    * a JPEG path or bytes the device decoder's plan supports (4:2:0 or grey baseline) and ``device_decode``: plan -> draft scale ->
-      ``bbocr_jpeg_decode_scaled`` -> libjpeg's RGB -> ``bbocr_thumbnail_box``; the file's ICC profile is carried into the PNG as Pillow
-      carries it;
-    * a page already on the card (a uint8 tensor, gray [H,W] or BGR [H,W,3], a strided view included -- the f2 output or a crop): the
-      whole-image thumbnail (``bbocr_ocr_thumbnail`` without its JPEG round trip); a gray page stays mode L;
-    * everything else (PNG, progressive / 4:4:4 / 4:2:2 / 4:4:0 / CMYK JPEG, a file whose data is damaged, host arrays): ``preview_host``."""
+    s = preview_draft_scale(plan, max_dim)
+    if plan.supported:
+        t, status = reader.decode_jpeg_batch([JpegPage(data, plan)], padded=True, scale=s)
+        page = t[0]
+    else:
+        decodes, status = reader.decode_jpeg_scales_batch([JpegPage(data, plan)], (s,))
+        page = decodes[0][s]
+    if status[0] != 0:
+        return None
+    return _preview_of_decode(reader, page, plan, s, max_dim)
+
+
+def _preview_string(px, icc):
+    """the preview of the pixels made on the card (a device tensor): Pillow writes the PNG, the file's ICC profile embedded"""
     from PIL import Image
 
-    from .reader import _file_bytes, jpeg_plan
-
-    px, icc = None, None
-    if hasattr(source, "is_cuda"):
-        H, W, _, ch = _page_layout(reader, source)
-        rgb, gray = ocr_thumbnail_device(reader, source, PAGE_GRAY if ch == 1 else PAGE_BGR, max_dim, 0)
-        px = gray if ch == 1 else rgb
-    elif device_decode and not isinstance(source, np.ndarray):
-        data = _file_bytes(source)
-        plan = jpeg_plan(data)
-        if plan.supported:
-            px = _preview_jpeg_device(reader, data, plan, max_dim)
-            icc = Image.open(io.BytesIO(data)).info.get("icc_profile")          # headers only
-            source = data
-    if px is None:
-        return preview_host(source, max_dim)
     img = Image.fromarray(px.cpu().numpy())
     if icc:
         img.info["icc_profile"] = icc
     return _png_data_url(img)
+
+
+PREVIEW_JPEG, PREVIEW_PAGE, PREVIEW_HOST = "device-jpeg", "device-page", "host"     # preview_device's routes (info["route"])
+
+
+def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, info=None):
+    """``preview_host(source, max_dim)``, character for character, with the pixels made on the card; only the page of at most ``max_dim``
+    pixels comes back, and Pillow writes the PNG from it.  ``info``: a dict that receives the route taken as ``info["route"]`` (the
+    strings are equal whichever it is):
+
+    * ``"device-jpeg"`` -- a JPEG path or bytes the device decoder's plan supports (4:2:0 or grey baseline) and ``device_decode``: plan ->
+      draft scale -> ``bbocr_jpeg_decode_scaled`` -> libjpeg's RGB -> ``bbocr_thumbnail_box``; the file's ICC profile is carried into the
+      PNG as Pillow carries it.  ``device_decode="chroma"``: a 4:4:4, 4:2:2 or 4:4:0 file (``plan.chroma``) as well, decoded at its
+      draft scale by ``bbocr_jpeg_decode_scales``;
+    * ``"device-page"`` -- a page already on the card (a uint8 tensor, gray [H,W] or BGR [H,W,3], a strided view included -- the f2 output
+      or a crop): the whole-image thumbnail (``bbocr_ocr_thumbnail`` without its JPEG round trip); a gray page stays mode L;
+    * ``"host"`` -- everything else (PNG, progressive / CMYK JPEG, 4:4:4 / 4:2:2 / 4:4:0 JPEG unless asked for, a file whose data is
+      damaged, host arrays): ``preview_host``."""
+    from PIL import Image
+
+    from .reader import _file_bytes, jpeg_chroma, jpeg_plan
+
+    px, icc, route = None, None, PREVIEW_HOST
+    if hasattr(source, "is_cuda"):
+        H, W, _, ch = _page_layout(reader, source)
+        rgb, gray = ocr_thumbnail_device(reader, source, PAGE_GRAY if ch == 1 else PAGE_BGR, max_dim, 0)
+        px, route = (gray if ch == 1 else rgb), PREVIEW_PAGE
+    elif device_decode and not isinstance(source, np.ndarray):
+        data = _file_bytes(source)
+        plan = jpeg_plan(data)
+        if plan.supported or (jpeg_chroma(device_decode) and plan.chroma):
+            px = _preview_jpeg_device(reader, data, plan, max_dim)
+            icc = Image.open(io.BytesIO(data)).info.get("icc_profile")          # headers only
+            source = data
+            if px is not None:
+                route = PREVIEW_JPEG
+    if info is not None:
+        info["route"] = route
+    if px is None:
+        return preview_host(source, max_dim)
+    return _preview_string(px, icc)
 
 
 def _read_page(image_path_or_array):

@@ -868,6 +868,75 @@ class Reader:
                     out[i] = (rgb[k], gray[k])
         return out
 
+    def jpeg_counters(self):
+        """``bbocr_jpeg_counters``: this Reader's totals since it was made, per file of every JPEG batch -- ``{"files", "entropy_runs",
+        "idct_passes", "output_passes"}``.  A ``decode_jpeg_scales`` call with two scales adds 1, 1, 2, 2 per file."""
+        out = (C.c_longlong * 4)()
+        self._check(self._lib.bbocr_jpeg_counters(self._h, out))
+        return dict(zip(("files", "entropy_runs", "idct_passes", "output_passes"), (int(v) for v in out)))
+
+    def decode_jpeg_scales_batch(self, pages, scales, imread=False):
+        """``JpegPage`` s of any shapes -> ``(decodes, status)`` by ONE ``bbocr_jpeg_decode_scales`` call: the entropy stages run once per
+        file, then one IDCT + output pass per scale.  ``decodes[k]`` maps each scale to the decoder's own device tensor -- ``uint8
+        [oh,ow,4]`` Pillow's padded YCbCr pixels (``pages_from_ycc``'s input) or ``[oh,ow]`` for a 1-component file, ``oh, ow = ceil(. /
+        scale)`` -- and, with ``imread``, scale 1 to ``cv2.imread``'s oriented BGR page (``imread_jpeg_batch``'s).  Files of a chroma class are
+        decoded at every scale.  ``status[k]`` non-zero: that file's tensors are undefined."""
+        torch = self._torch
+        pages = list(pages)
+        scales = tuple(int(s) for s in scales)
+        if not pages or not scales or len(set(scales)) != len(scales) or any(s not in JPEG_SCALES for s in scales):
+            raise ValueError(f"decode_jpeg_scales_batch: pages, and different scales out of {JPEG_SCALES}")
+        if imread and 1 not in scales:
+            raise ValueError("imread: the oriented page exists at scale 1 only")
+        n = len(pages)
+        outs = (_lib.bbocr_jpeg_output * len(scales))()
+        decodes = [{} for _ in pages]
+        keep = []
+        for o, s in enumerate(scales):
+            form = _lib.JPEG_FORM_IMREAD if imread and s == 1 else _lib.JPEG_FORM_YCBCR
+            ts = []
+            for p in pages:
+                H, W, comps = p.shape
+                if form == _lib.JPEG_FORM_IMREAD:
+                    shape = (W, H, 3) if p.orientation >= 5 else (H, W, 3)
+                else:
+                    shape = (-(-H // s), -(-W // s)) + ((4,) if comps == 3 else ())
+                ts.append(torch.empty(shape, dtype=torch.uint8, device=self.device))
+            ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+            pitches = (C.c_longlong * n)(*[t.shape[1] * (t.shape[2] if t.ndim == 3 else 1) for t in ts])
+            keep.append((ptrs, pitches))
+            outs[o].scale, outs[o].form, outs[o].dev_out, outs[o].pitches = s, form, ptrs, pitches
+            for k, t in enumerate(ts):
+                decodes[k][s] = t
+        torch.cuda.current_stream(self.device_index).synchronize()
+        files, sizes = self._jpeg_files(pages)
+        status = (C.c_int * n)()
+        self._check(self._lib.bbocr_jpeg_decode_scales(self._h, files, sizes, n, _lib.PAGE_YCBCR4, outs, len(scales), status))
+        del keep
+        return decodes, list(status)
+
+    def decode_jpeg_scales(self, sources, scales=(1, 2), chroma=None, imread=False):
+        """Paths or bytes objects -> per source ``{scale: pages}``, or ``None`` for a file the plan refuses or whose entropy-coded data is
+        damaged -- all scales of all files from ONE device call that runs the entropy stages once per file (``decode_jpeg_device`` called
+        once per scale runs them once per scale).  ``pages`` is ``(rgb_dev [oh,ow,3], gray_dev [oh,ow])`` as ``decode_jpeg_device`` defines
+        them, ``oh, ow = ceil(. / scale)``; with ``imread`` the scale-1 entry is ``cv2.imread``'s page instead: BGR ``[H',W',3]``, EXIF
+        orientation applied.  ``chroma`` (None: this Reader's ``jpeg_chroma``): 4:4:4, 4:2:2 and 4:4:0 files are decoded as well -- here at
+        EVERY scale, where ``decode_jpeg_device(scale=2)`` leaves them to the host."""
+        chroma = self.jpeg_chroma if chroma is None else bool(chroma)
+        pages = [jpeg_page(s, chroma) for s in sources]
+        out = [None] * len(pages)
+        idxs = [i for i, p in enumerate(pages) if p is not None]
+        if not idxs:
+            return out
+        decodes, status = self.decode_jpeg_scales_batch([pages[i] for i in idxs], scales, imread=imread)
+        for k, i in enumerate(idxs):
+            if status[k] != 0:
+                continue
+            out[i] = {}
+            for s, t in decodes[k].items():
+                out[i][s] = t if imread and s == 1 else tuple(x[0] for x in self.pages_from_jpeg(t[None]))
+        return out
+
     def readtext_ycc_arrays(self, ycc, **kw):
         """Host array ``uint8 [B,H,W,3]`` of once-decoded JPEG pages (``decode_file_ycc``) -> per-page results, identical to
         ``readtext_arrays(rgb, gray)`` of the same files decoded twice."""

@@ -532,7 +532,8 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
  * the chroma blocks of a 4:2:0 file through the 2n x 2n one (jdmaster.c's per-component DCT_scaled_size), so that nothing is upsampled; the
  * entropy stages are those of the full-scale decode.  Only the files inside the plan's own scope (supported == 1: 4:2:0 or one component)
  * are decoded at s > 1: a file of a chroma class (4:4:4, 4:2:2, 4:4:0), like every file the plan refuses, gets status[k] = BBOCR_ERR_ARG,
- * the rest of the batch is decoded, and the caller keeps its host path for it. */
+ * the rest of the batch is decoded, and the caller keeps its host path for it -- or hands it to bbocr_jpeg_decode_scales below, which
+ * decodes those classes at every scale. */
 int bbocr_jpeg_decode_scaled(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, int scale,
                              uint8_t* const* dev_out, const long long* pitches, int* status);
 /* host only: (ceil(H / scale), ceil(W / scale)); scale 1, 2, 4 or 8 */
@@ -542,6 +543,57 @@ int bbocr_jpeg_scaled_dims(int H, int W, int scale, int* out_h, int* out_w);
  * e = 8 / scale for a 1-component file (Y alone); 3 = the pixels, tight.  A file outside the scaled decode's scope: BBOCR_ERR_ARG. */
 int bbocr_op_jpeg_scaled_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
                                int* file_status);
+/* ---- several decodes of a batch from ONE entropy pass, every chroma class at every scale.  bbocr_jpeg_decode_scales plans each file,
+ * removes the stuffing and runs the entropy stages once, then runs one IDCT + output pass per entry of outputs[0 .. n_outputs) over the
+ * shared coefficients.  An output names a scale (1, 2, 4 or 8; each at most once), a form and per-file destinations:
+ *   BBOCR_JPEG_FORM_YCBCR   what bbocr_jpeg_decode (scale 1) / bbocr_jpeg_decode_scaled (2, 4, 8) write for the file: YCbCr triples in
+ *                           `layout` (BBOCR_PAGE_YCBCR3 or _YCBCR4) or a 1-component file's samples, ceil(height / scale) rows of
+ *                           ceil(width / scale) pixels, rows pitches[k] bytes apart;
+ *   BBOCR_JPEG_FORM_IMREAD  scale 1 only: bbocr_jpeg_imread's oriented BGR page and its pitch rule.
+ * It takes every file bbocr_jpeg_decode takes (supported, or chroma != 0), at EVERY scale: a 4:4:4, 4:2:2 or 4:4:0 file at scale s > 1
+ * comes out as libjpeg-turbo / Pillow's draft decode it -- every block through the n x n reduced IDCT, n = 8 / s (jdmaster.c doubles a
+ * component's block only when both directions allow it), the chroma planes, ceil(OH / v) x ceil(OW / h) valid samples for luma sampling
+ * (h, v), upsampled at the reduced size by h2v1_fancy_upsample / h1v2_fancy_upsample at s = 2 and 4 and by replication at s = 8
+ * (jdsample.c turns fancy upsampling off when min_DCT_scaled_size is 1).  Each output equals what the single-purpose call writes for the
+ * file, bit for bit.  status[k] (one per file, for all of its outputs): as bbocr_jpeg_decode's; a null destination or a short pitch in any
+ * output refuses the file (BBOCR_ERR_ARG).  n_outputs outside 1 .. 4, a repeated scale, an unknown form, the imread form at scale > 1, a
+ * null array: BBOCR_ERR_ARG before anything is queued.  Stream, one-batch-at-a-time contract and work buffers: bbocr_jpeg_decode's; the
+ * component planes are sized per output, the coefficient buffer is shared by the outputs. */
+enum { BBOCR_JPEG_FORM_YCBCR = 0, BBOCR_JPEG_FORM_IMREAD = 1 };
+typedef struct bbocr_jpeg_output {
+    int scale;                   /* 1, 2, 4 or 8 */
+    int form;                    /* BBOCR_JPEG_FORM_* */
+    uint8_t* const* dev_out;     /* [n] DEVICE destinations, one per file */
+    const long long* pitches;    /* [n] bytes between rows */
+} bbocr_jpeg_output;
+int bbocr_jpeg_decode_scales(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, const bbocr_jpeg_output* outputs,
+                             int n_outputs, int* status);
+/* read-only totals of this context's JPEG lane since bbocr_create, per file of every batch: out[0] = files decoded, out[1] = runs of the
+ * entropy stages, out[2] = IDCT passes, out[3] = output passes.  A two-output bbocr_jpeg_decode_scales call of one file adds 1, 1, 2, 2. */
+int bbocr_jpeg_counters(bbocr_ctx* ctx, long long* out);
+/* host only: the planes of a decode at scale 2, 4 or 8 of a file the decoder takes (plan->supported or plan->chroma), per component
+ * comps[0 .. components): the block's edge, the plane in whole MCUs as the device keeps it, the valid extent inside it (what libjpeg
+ * calls downsampled_height x downsampled_width) and how the output stage brings the component to the output's size.  comps[components .. 3)
+ * are zeroed.  Another scale, a refused plan: BBOCR_ERR_ARG. */
+enum {
+    BBOCR_JPEG_UP_NONE = 0,            /* the plane has the output's sampling */
+    BBOCR_JPEG_UP_H2V1_FANCY = 1,      /* 4:2:2 at scale 2 and 4: h2v1_fancy_upsample (h2v1_upsample when at most 2 samples wide) */
+    BBOCR_JPEG_UP_H1V2_FANCY = 2,      /* 4:4:0 at scale 2 and 4: h1v2_fancy_upsample */
+    BBOCR_JPEG_UP_H2V2_NOT_NEEDED = 3, /* 4:2:0 chroma: blocks of twice the edge, already the output's size */
+    BBOCR_JPEG_UP_REPLICATE = 4        /* 4:2:2 and 4:4:0 at scale 8: out[x] = c[x / h], out[y] = c[y / v] */
+};
+typedef struct bbocr_jpeg_scaled_comp {
+    int block;                   /* edge of one block's samples */
+    int plane_rows, plane_cols;
+    int valid_rows, valid_cols;
+    int upsample;                /* BBOCR_JPEG_UP_* */
+} bbocr_jpeg_scaled_comp;
+int bbocr_host_jpeg_scaled_geometry(const bbocr_jpeg_plan* plan, int scale, bbocr_jpeg_scaled_comp* comps);
+/* bbocr_op_jpeg_scaled_stage for ONE file of a chroma class (plan.chroma != 0; every other file: BBOCR_ERR_ARG): stage 2 = the component
+ * planes in bbocr_host_jpeg_scaled_geometry's sizes, Y [mcu_rows * n * v][mcu_cols * n * h], then Cb, then Cr, each
+ * [mcu_rows * n][mcu_cols * n], n = 8 / scale; 3 = the pixels, tight YCbCr triples. */
+int bbocr_op_jpeg_scaled_class_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
+                                     int* file_status);
 
 /* ---- the extractor's model-input JPEG (enhanced_extractor.py:399-411, _encode_image_for_model's img.save(format="JPEG", quality=q)) written
  * on the device (csrc/jpegenc.hip): one u8 page in device memory -- any BBOCR_PAGE_* layout, rows `pitch` bytes apart, a crop of a larger
