@@ -1,10 +1,12 @@
 // Baseline JPEG decoding, host side: the marker parser (bbocr_host_jpeg_plan: one linear pass, no entropy bit decoded), the per-batch
 // tables of jpegdec.hip (unstuffed segment bytes, subsequence lists, derived Huffman tables) and its launch sequence.  A batch runs on
 // its own stream of the root context, outside the call slots (the contract of bbocr_upload_pages): files decode while two OCR calls run.
-// A batch may be decoded at scale 1/2, 1/4 or 1/8 (bbocr_jpeg_decode_scaled, Pillow's draft): same tables and entropy stages, planes of
-// the output's size, jpegdec.hip's scaled IDCT and output kernels; 4:2:0 and grey files only.  bbocr_jpeg_decode_scales runs the entropy
-// stages once per file and one IDCT + output pass per requested output (scale 1, 2, 4, 8; YCbCr pixels or, at scale 1, bbocr_jpeg_imread's
-// oriented page), the files of a chroma class at every scale.
+// A batch runs the entropy stages once per file and one IDCT + output pass per requested output: scale 1, or 1/2, 1/4, 1/8 (Pillow's
+// draft); YCbCr pixels or, at scale 1, the oriented BGR page of cv2.imread.  jpeg_geometry is the one statement of what a scale and a
+// sampling mean for a pass -- block edges, planes, valid extents, upsampling rule; the device reads it from the descriptors, the plane
+// sizes and bbocr_host_jpeg_scaled_geometry are taken from it.  Every pixel entry point is jpeg_decode_outputs with its own list of
+// outputs (bbocr_jpeg_decode_scaled refuses the files of a chroma class at a draft scale: its documented scope), every stage entry point
+// jpeg_stage_run.
 #include "ctx.h"
 
 namespace {
@@ -239,29 +241,35 @@ bool jpeg_taken(const bbocr_jpeg_plan& pl) { return pl.supported || pl.chroma; }
 // luma blocks of an MCU across and down (1 x 1 for a one-component file)
 int luma_h(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? pl.sampling[0][0] : 1; }
 int luma_v(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? pl.sampling[0][1] : 1; }
-// bytes of the Y plane and of one chroma plane before upsampling (whole MCUs)
-size_t luma_plane_bytes(const bbocr_jpeg_plan& pl) { return (size_t)pl.mcu_cols * 8 * luma_h(pl) * (size_t)pl.mcu_rows * 8 * luma_v(pl); }
-size_t chroma_plane_bytes(const bbocr_jpeg_plan& pl) { return pl.components == 3 ? (size_t)pl.mcu_cols * 8 * (size_t)pl.mcu_rows * 8 : 0; }
-// A decode at scale 1 / s (s 2, 4 or 8; 4:2:0 and grey files): every plane has the output's size in whole MCUs, rows of scaled_plane_w
-// samples -- an MCU is 16 / s samples wide and high in each plane of a 4:2:0 file, 8 / s in a grey file's
 bool jpeg_scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
-int scaled_mcu_edge(const bbocr_jpeg_plan& pl, int s) { return (pl.components == 3 ? 16 : 8) / s; }
-size_t scaled_plane_w(const bbocr_jpeg_plan& pl, int s) { return (size_t)pl.mcu_cols * scaled_mcu_edge(pl, s); }
-size_t scaled_plane_bytes(const bbocr_jpeg_plan& pl, int s) { return scaled_plane_w(pl, s) * (size_t)pl.mcu_rows * scaled_mcu_edge(pl, s); }
 int scaled_dim(int v, int s) { return (v + s - 1) / s; }
-// ... of a file of a chroma class: every block is n x n, n = 8 / s, so the Y plane is mcu_rows * n * v rows of mcu_cols * n * h samples and
-// each chroma plane mcu_rows * n rows of mcu_cols * n (jpegdec.hip's jd_idct_scaled_c)
-size_t class_luma_bytes(const bbocr_jpeg_plan& pl, int s) {
-    return (size_t)pl.mcu_cols * (8 / s) * luma_h(pl) * (size_t)pl.mcu_rows * (8 / s) * luma_v(pl);
+
+static_assert((int)JD_UP_NONE == (int)BBOCR_JPEG_UP_NONE && (int)JD_UP_H2V1_FANCY == (int)BBOCR_JPEG_UP_H2V1_FANCY &&
+                  (int)JD_UP_H1V2_FANCY == (int)BBOCR_JPEG_UP_H1V2_FANCY && (int)JD_UP_H2V2_NOT_NEEDED == (int)BBOCR_JPEG_UP_H2V2_NOT_NEEDED &&
+                  (int)JD_UP_REPLICATE == (int)BBOCR_JPEG_UP_REPLICATE,
+              "kernels.h's JD_UP_* begin with bbocr.h's BBOCR_JPEG_UP_*");
+
+// A decode at scale 1 / s (s 1, 2, 4 or 8) of a file the decoder takes: OH x OW pixels and, per component, the geometry of jpegdec.hip's
+// IDCT + output pass.  jdmaster.c gives a component the block edge n = 8 / s, and twice that when its sampling is below luma's in BOTH
+// directions and n < 8 -- 4:2:0 chroma at a draft scale, whose plane then has the output's size.  Everywhere else chroma keeps the file's
+// sampling: planes of whole MCUs of one n x n block, the valid extent ceil(OH / v) x ceil(OW / h), brought to the output's size by
+// jdsample.c's fancy upsampling (by replication at s = 8: min_DCT_scaled_size 1 turns the fancy kind off).
+struct JpegGeometry { int OH, OW; JpegComp comp[3]; };
+JpegGeometry jpeg_geometry(const bbocr_jpeg_plan& pl, int s) {
+    JpegGeometry g{};
+    const int n = 8 / s, h = luma_h(pl), v = luma_v(pl), oh = g.OH = scaled_dim(pl.height, s), ow = g.OW = scaled_dim(pl.width, s);
+    g.comp[0] = {n, h, v, pl.mcu_rows * n * v, pl.mcu_cols * n * h, oh, ow, JD_UP_NONE};
+    for (int c = 1; c < pl.components; ++c) {
+        if (h * v == 4 && s > 1) {
+            g.comp[c] = {2 * n, 1, 1, pl.mcu_rows * 2 * n, pl.mcu_cols * 2 * n, oh, ow, JD_UP_H2V2_NOT_NEEDED};
+            continue;
+        }
+        const int up = h * v == 1 ? JD_UP_NONE : (s == 8 ? JD_UP_REPLICATE : (h * v == 4 ? JD_UP_H2V2_FANCY : (h == 2 ? JD_UP_H2V1_FANCY : JD_UP_H1V2_FANCY)));
+        g.comp[c] = {n, 1, 1, pl.mcu_rows * n, pl.mcu_cols * n, scaled_dim(oh, v), scaled_dim(ow, h), up};
+    }
+    return g;
 }
-size_t class_chroma_bytes(const bbocr_jpeg_plan& pl, int s) { return (size_t)pl.mcu_cols * (8 / s) * (size_t)pl.mcu_rows * (8 / s); }
-// bytes of component c's plane in a decode at scale s (1: the full-scale decode)
-size_t plane_bytes(const bbocr_jpeg_plan& pl, int s, int c) {
-    if (c > 0 && pl.components != 3) return 0;
-    if (s == 1) return c == 0 ? luma_plane_bytes(pl) : chroma_plane_bytes(pl);
-    if (pl.chroma) return c == 0 ? class_luma_bytes(pl, s) : class_chroma_bytes(pl, s);
-    return scaled_plane_bytes(pl, s);
-}
+size_t plane_size(const JpegComp& c) { return (size_t)c.plane_rows * (size_t)c.pitch; }
 
 // jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
 bool derive_table(const HuffSpec& h, JpegHuff& t) {
@@ -298,7 +306,8 @@ struct FileJob {                              // one admitted file of a batch
     int nsub = 0, groups = 0, nblocks = 0;
     size_t o_huff, o_quant, o_segbyte, o_segsub, o_subseg, o_data, data_bytes;   // offsets in the input blob
     size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[kMaxPasses][3], o_coef; // offsets in the work / coefficient buffers
-    size_t o_page = 0;                        // bbocr_jpeg_imread and the imread form: offset of the un-oriented decode in jd_page
+    size_t o_page = 0;                        // the imread form: offset of the un-oriented decode in jd_page
+    JpegGeometry geo[kMaxPasses];             // per pass (filled by jpeg_run)
 };
 
 // Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan neither supports nor gives a chroma
@@ -331,14 +340,10 @@ void jpeg_report(const std::vector<FileJob>& jobs, const std::vector<int>& dev_s
 // descriptors of the first pass for the stage entry points.  Everything queued is finished on return.
 // The entropy stages run once; then every pass (at most kMaxPasses) runs its IDCT and output stage over the shared coefficients into
 // planes of its own and the jobs' out[p] / pitch[p].  A pass of scale 2, 4 or 8 is the decode at that fraction (`out[p]` holds the scaled
-// size): the 4:2:0 and grey files through jd_idct_scaled / jd_output_scaled, the files of a chroma class through their _c siblings -- the
-// jobs are ordered so that each kind is one run of descriptors (the order of `jobs` may change; dev_status follows it).
+// size); its descriptors carry jpeg_geometry's table, so one launch pair serves every file of the batch.
 void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S, const std::vector<JpegPass>& passes_out,
               std::vector<int>& dev_status, std::vector<JpegDesc>* descs_out = nullptr) {
     const int n = (int)jobs.size(), np = (int)passes_out.size();
-    int n_plain = n;                                                      // the jobs in front of the first file of a chroma class
-    if (std::any_of(passes_out.begin(), passes_out.end(), [](const JpegPass& p) { return p.scale > 1; }))
-        n_plain = (int)(std::stable_partition(jobs.begin(), jobs.end(), [](const FileJob& j) { return j.ps.plan.supported != 0; }) - jobs.begin());
     Carve in{align_up(sizeof(JpegDesc) * (size_t)n * np, 256)}, work{align_up(4 * (size_t)n, 256)}, coef;
     int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;                // max_h, max_w: at full scale
     for (FileJob& j : jobs) {
@@ -402,8 +407,10 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         j.w_count = work.add(4 * (size_t)nsub);
         j.w_scan = work.add(4 * (size_t)nsub);
         j.w_first = work.add(4 * (size_t)nsub);
-        for (int p = 0; p < np; ++p)
-            for (int c = 0; c < 3; ++c) j.w_plane[p][c] = work.add(plane_bytes(pl, passes_out[p].scale, c));
+        for (int p = 0; p < np; ++p) {
+            j.geo[p] = jpeg_geometry(pl, passes_out[p].scale);
+            for (int c = 0; c < 3; ++c) j.w_plane[p][c] = work.add(plane_size(j.geo[p].comp[c]));
+        }
         j.o_coef = coef.add((size_t)j.nblocks * 128);
     }
     const int passes = max_groups + 1;
@@ -448,7 +455,12 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         d.passes = passes;
         for (int c = 0; c < 3; ++c) { d.tab_dc[c] = j.ps.tab_dc[c]; d.tab_ac[c] = j.ps.tab_ac[c]; }
         for (int p = 0; p < np; ++p) {                                    // pass p's descriptors: descs[p * n ..]; the entropy stages read pass 0's
-            for (int c = 0; c < 3; ++c) d.plane[c] = (uint8_t*)(wb + j.w_plane[p][c]);
+            for (int c = 0; c < 3; ++c) {
+                d.plane[c] = (uint8_t*)(wb + j.w_plane[p][c]);
+                d.comp[c] = j.geo[p].comp[c];
+            }
+            d.OW = j.geo[p].OW;
+            d.OH = j.geo[p].OH;
             d.out = j.out[p];
             d.pitch = j.pitch[p];
             d.px = pl.components == 3 ? passes_out[p].px : 1;
@@ -467,20 +479,8 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     HIPCHK(launch_jd_dc(dd, n, max_seg, st));
     for (int p = 0; p < np; ++p) {
         const JpegDesc* dp = dd + (size_t)p * n;
-        const int scale = passes_out[p].scale, ph = scaled_dim(max_h, scale), pw = scaled_dim(max_w, scale);
-        if (scale == 1) {
-            HIPCHK(launch_jd_idct(dp, n, max_blocks, st));
-            HIPCHK(launch_jd_output(dp, n, ph, pw, st));
-            continue;
-        }
-        if (n_plain) {
-            HIPCHK(launch_jd_idct_scaled(dp, n_plain, max_blocks, scale, st));
-            HIPCHK(launch_jd_output_scaled(dp, n_plain, ph, pw, scale, st));
-        }
-        if (n > n_plain) {
-            HIPCHK(launch_jd_idct_scaled_c(dp + n_plain, n - n_plain, max_blocks, scale, st));
-            HIPCHK(launch_jd_output_scaled_c(dp + n_plain, n - n_plain, ph, pw, scale, st));
-        }
+        HIPCHK(launch_jd_idct(dp, n, max_blocks, st));
+        HIPCHK(launch_jd_output(dp, n, scaled_dim(max_h, passes_out[p].scale), scaled_dim(max_w, passes_out[p].scale), st));
     }
     root->jd_count[0] += n;
     root->jd_count[1] += n;
@@ -490,6 +490,103 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     HIPCHK(hipMemcpyAsync(dev_status.data(), wb, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
 }
+
+// The pixel entry points' body on the JPEG lane's stream: one entropy pass over the batch, then one IDCT + output pass per entry of
+// outputs[0 .. n_outputs).  An output of the imread form is decoded un-oriented into jd_page -- Pillow's padded pixels (a dword per pixel)
+// or the grey samples, tight rows -- and page_orient writes the caller's BGR page from there.  chroma_classes false: only the files the
+// plan supports, 4:2:0 and grey.  Argument errors are raised before anything is queued; a refused file's destinations are never written.
+void jpeg_decode_outputs(bbocr_ctx* ctx, hipStream_t st, const uint8_t* const* files, const size_t* bytes, int n, int layout,
+                         const bbocr_jpeg_output* outputs, int n_outputs, int* status, bool chroma_classes) {
+    if (!files || !bytes || !outputs || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
+    if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
+    if (n_outputs < 1 || n_outputs > kMaxPasses) fail(BBOCR_ERR_ARG, "1 .. 4 outputs, one per scale");
+    int imread = -1;                                                      // the output of the imread form
+    for (int o = 0; o < n_outputs; ++o) {
+        const bbocr_jpeg_output& O = outputs[o];
+        if (!O.dev_out || !O.pitches || !jpeg_scale_ok(O.scale)) fail(BBOCR_ERR_ARG, "an output needs destinations, pitches and a scale of 1, 2, 4 or 8");
+        if (O.form != BBOCR_JPEG_FORM_YCBCR && O.form != BBOCR_JPEG_FORM_IMREAD) fail(BBOCR_ERR_ARG, "unknown output form");
+        if (O.form == BBOCR_JPEG_FORM_IMREAD && O.scale != 1) fail(BBOCR_ERR_ARG, "the imread form exists at scale 1 only");
+        for (int q = 0; q < o; ++q)
+            if (outputs[q].scale == O.scale) fail(BBOCR_ERR_ARG, "a scale is named twice");
+        if (O.form == BBOCR_JPEG_FORM_IMREAD) imread = o;
+    }
+    auto decoded = [](const bbocr_jpeg_plan& pl) { return pl.components == 3 ? PAGE_YCC4 : PAGE_GRAY; };
+    Carve pages;
+    std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
+        const bbocr_jpeg_plan& pl = j.ps.plan;
+        for (int o = 0; o < n_outputs; ++o) {
+            const bbocr_jpeg_output& O = outputs[o];
+            if (!O.dev_out[j.k]) return false;
+            if (o == imread) {
+                if (O.pitches[j.k] < (long long)page_px_bytes(PAGE_BGR) * (pl.orientation >= 5 ? pl.height : pl.width)) return false;
+                j.pitch[o] = (long long)pl.width * page_px_bytes(decoded(pl));
+            } else {
+                if (O.pitches[j.k] < (long long)scaled_dim(pl.width, O.scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY)) return false;
+                j.out[o] = O.dev_out[j.k];
+                j.pitch[o] = O.pitches[j.k];
+            }
+        }
+        if (imread >= 0) j.o_page = pages.add((size_t)j.pitch[imread] * (size_t)pl.height);
+        return true;
+    }, chroma_classes);
+    if (jobs.empty()) return;
+    std::vector<JpegPass> passes;
+    for (int o = 0; o < n_outputs; ++o) passes.push_back({outputs[o].scale, page_px_bytes(o == imread ? (int)PAGE_YCC4 : layout)});
+    if (imread >= 0) {
+        ctx->jd_page.ensure(pages.off);
+        for (FileJob& j : jobs) j.out[imread] = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
+    }
+    std::vector<int> ds;
+    jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, passes, ds);
+    jpeg_report(jobs, ds, status);
+    if (imread < 0) return;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const FileJob& j = jobs[i];
+        const bbocr_jpeg_plan& pl = j.ps.plan;
+        if (ds[i]) continue;
+        HIPCHK(launch_page_orient(j.out[imread], pl.height, pl.width, (size_t)j.pitch[imread], decoded(pl), pl.orientation, PAGE_BGR,
+                                  outputs[imread].dev_out[j.k], (size_t)outputs[imread].pitches[j.k], st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+}
+
+// The stage entry points' body: ONE file decoded at `scale` with S-bit subsequences, then stage 2 = the component planes in
+// jpeg_geometry's sizes, Y, Cb, Cr one after the other, or stage 3 = the pixels, tight, copied to dev_dst.  cls: the files it takes -- -1
+// every file the decoder takes, 0 the 4:2:0 and grey ones only, 1 those of a chroma class only.  Returns the file's descriptor (the
+// entropy stages' intermediates).
+JpegDesc jpeg_stage_run(bbocr_ctx* ctx, hipStream_t s, int stage, const uint8_t* file, size_t bytes, int S, int scale, int cls, void* dev_dst,
+                        size_t dst_bytes, int* file_status) {
+    if (!file || !dev_dst || stage < 0 || stage > 3 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
+    int status = 0;
+    std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
+        const bbocr_jpeg_plan& pl = j.ps.plan;
+        if (cls >= 0 && cls != (pl.chroma != 0)) return false;
+        const JpegGeometry g = jpeg_geometry(pl, scale);
+        const size_t pix = (size_t)g.OW * g.OH * pl.components;
+        const size_t planes = plane_size(g.comp[0]) + plane_size(g.comp[1]) + plane_size(g.comp[2]);
+        if ((stage == 3 && dst_bytes < pix) || (stage == 2 && dst_bytes < planes)) fail(BBOCR_ERR_ARG, "destination too small");
+        ctx->jd_stage.ensure(pix);                               // the pixels go to a scratch image unless they are the stage's output
+        j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
+        j.pitch[0] = (long long)g.OW * pl.components;
+        return true;
+    });
+    if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file, or this entry point does not take its sampling");
+    std::vector<int> ds;
+    std::vector<JpegDesc> descs;
+    jpeg_run(ctx, s, jobs, S, {{scale, 3}}, ds, &descs);
+    jpeg_report(jobs, ds, &status);
+    if (file_status) *file_status = status;
+    const JpegDesc& d = descs[0];
+    size_t off = 0;
+    for (int c = 0; stage == 2 && c < d.ncomp; ++c) {
+        HIPCHK(hipMemcpyAsync((char*)dev_dst + off, d.plane[c], plane_size(d.comp[c]), hipMemcpyDeviceToDevice, s));
+        off += plane_size(d.comp[c]);
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return d;
+}
+
+bool draft_scale(int s) { return s == 2 || s == 4 || s == 8; }
 
 }  // namespace
 
@@ -507,19 +604,8 @@ int bbocr_host_jpeg_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_plan* pla
 int bbocr_jpeg_decode_scaled(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, int scale,
                              uint8_t* const* dev_out, const long long* pitches, int* status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
-        if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
-        if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
-        if (!jpeg_scale_ok(scale)) fail(BBOCR_ERR_ARG, "scale must be 1, 2, 4 or 8");
-        std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            j.out[0] = dev_out[j.k];
-            j.pitch[0] = pitches[j.k];
-            return j.out[0] && j.pitch[0] >= (long long)scaled_dim(pl.width, scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY);
-        }, scale == 1);
-        if (jobs.empty()) return;
-        std::vector<int> ds;
-        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, {{scale, page_px_bytes(layout)}}, ds);
-        jpeg_report(jobs, ds, status);
+        const bbocr_jpeg_output out{scale, BBOCR_JPEG_FORM_YCBCR, dev_out, pitches};
+        jpeg_decode_outputs(ctx, st, files, bytes, n, layout, &out, 1, status, scale == 1);
     });
 }
 
@@ -538,59 +624,23 @@ int bbocr_jpeg_scaled_dims(int H, int W, int scale, int* out_h, int* out_w) {
 int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dev_out, const long long* pitches,
                       int* status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
-        if (!files || !bytes || !dev_out || !pitches || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
-        // the un-oriented decodes go to jd_page: Pillow's padded pixels (a dword per pixel) or the grey samples, tight rows
-        auto decoded = [](const bbocr_jpeg_plan& pl) { return pl.components == 3 ? PAGE_YCC4 : PAGE_GRAY; };
-        Carve pages;
-        std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            if (!dev_out[j.k] || pitches[j.k] < (long long)page_px_bytes(PAGE_BGR) * (pl.orientation >= 5 ? pl.height : pl.width)) return false;
-            j.pitch[0] = (long long)pl.width * page_px_bytes(decoded(pl));
-            j.o_page = pages.add((size_t)j.pitch[0] * (size_t)pl.height);
-            return true;
-        });
-        if (jobs.empty()) return;
-        ctx->jd_page.ensure(pages.off);
-        for (FileJob& j : jobs) j.out[0] = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
-        std::vector<int> ds;
-        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, {{1, page_px_bytes(PAGE_YCC4)}}, ds);
-        jpeg_report(jobs, ds, status);
-        for (size_t i = 0; i < jobs.size(); ++i) {
-            const FileJob& j = jobs[i];
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            if (ds[i]) continue;
-            HIPCHK(launch_page_orient(j.out[0], pl.height, pl.width, (size_t)j.pitch[0], decoded(pl), pl.orientation, PAGE_BGR, dev_out[j.k],
-                                      (size_t)pitches[j.k], st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
+        const bbocr_jpeg_output out{1, BBOCR_JPEG_FORM_IMREAD, dev_out, pitches};
+        jpeg_decode_outputs(ctx, st, files, bytes, n, BBOCR_PAGE_YCBCR4, &out, 1, status, true);   // the layout: of YCbCr outputs, here none
     });
+}
+
+int bbocr_jpeg_decode_scales(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, const bbocr_jpeg_output* outputs,
+                             int n_outputs, int* status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true,
+                        [&](hipStream_t st) { jpeg_decode_outputs(ctx, st, files, bytes, n, layout, outputs, n_outputs, status, true); });
 }
 
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
-        if (!file || !dev_dst || stage < 0 || stage > 3 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
         const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
         if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
-        int status = 0;
-        std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            const size_t pix = (size_t)pl.width * pl.height * pl.components;
-            if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
-            ctx->jd_stage.ensure(pix);                           // the pixels go to a scratch image unless they are the stage's output
-            j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
-            j.pitch[0] = (long long)pl.width * pl.components;
-            return true;
-        });
-        if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file");
-        const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
-        const size_t ysz = luma_plane_bytes(pl), csz = chroma_plane_bytes(pl);
-        std::vector<int> ds;
-        std::vector<JpegDesc> descs;
-        jpeg_run(ctx, s, jobs, S, {{1, 3}}, ds, &descs);
-        jpeg_report(jobs, ds, &status);
-        if (file_status) *file_status = status;
-        const JpegDesc& d = descs[0];
+        const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, S, 1, -1, dev_dst, dst_bytes, file_status);
         if (stage == 0) {
             const size_t ns = (size_t)d.nsub;
             if (dst_bytes < ns * 16) fail(BBOCR_ERR_ARG, "destination too small");
@@ -609,13 +659,6 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
         } else if (stage == 1) {
             if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
             HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
-        } else if (stage == 2) {
-            if (dst_bytes < ysz + 2 * csz) fail(BBOCR_ERR_ARG, "destination too small");
-            HIPCHK(hipMemcpyAsync(dev_dst, d.plane[0], ysz, hipMemcpyDeviceToDevice, s));
-            if (csz) {
-                HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz, d.plane[1], csz, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz + csz, d.plane[2], csz, hipMemcpyDeviceToDevice, s));
-            }
         }
         HIPCHK(hipStreamSynchronize(s));
     });
@@ -624,89 +667,16 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
 int bbocr_op_jpeg_scaled_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
                                int* file_status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
-        if (!file || !dev_dst || (stage != 2 && stage != 3) || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
-        if (scale != 2 && scale != 4 && scale != 8) fail(BBOCR_ERR_ARG, "scale must be 2, 4 or 8");
-        int status = 0;
-        std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            const size_t pix = (size_t)scaled_dim(pl.width, scale) * scaled_dim(pl.height, scale) * pl.components;
-            if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
-            ctx->jd_stage.ensure(pix);
-            j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
-            j.pitch[0] = (long long)scaled_dim(pl.width, scale) * pl.components;
-            return true;
-        }, false);
-        if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file, or it is of a chroma class");
-        const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
-        const size_t psz = scaled_plane_bytes(pl, scale);
-        if (stage == 2 && dst_bytes < psz * pl.components) fail(BBOCR_ERR_ARG, "destination too small");
-        std::vector<int> ds;
-        std::vector<JpegDesc> descs;
-        jpeg_run(ctx, s, jobs, JD_SUBSEQ_BITS, {{scale, 3}}, ds, &descs);
-        jpeg_report(jobs, ds, &status);
-        if (file_status) *file_status = status;
-        if (stage == 2)
-            for (int c = 0; c < pl.components; ++c)
-                HIPCHK(hipMemcpyAsync((char*)dev_dst + psz * c, descs[0].plane[c], psz, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
+        if ((stage != 2 && stage != 3) || !draft_scale(scale)) fail(BBOCR_ERR_ARG, "stage 2 or 3 at scale 2, 4 or 8");
+        jpeg_stage_run(ctx, s, stage, file, bytes, JD_SUBSEQ_BITS, scale, 0, dev_dst, dst_bytes, file_status);
     });
 }
 
-int bbocr_jpeg_decode_scales(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout, const bbocr_jpeg_output* outputs,
-                             int n_outputs, int* status) {
-    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
-        if (!files || !bytes || !outputs || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
-        if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
-        if (n_outputs < 1 || n_outputs > kMaxPasses) fail(BBOCR_ERR_ARG, "1 .. 4 outputs, one per scale");
-        int imread = -1;                                                  // the output of the imread form
-        for (int o = 0; o < n_outputs; ++o) {
-            const bbocr_jpeg_output& O = outputs[o];
-            if (!O.dev_out || !O.pitches || !jpeg_scale_ok(O.scale)) fail(BBOCR_ERR_ARG, "an output needs destinations, pitches and a scale of 1, 2, 4 or 8");
-            if (O.form != BBOCR_JPEG_FORM_YCBCR && O.form != BBOCR_JPEG_FORM_IMREAD) fail(BBOCR_ERR_ARG, "unknown output form");
-            if (O.form == BBOCR_JPEG_FORM_IMREAD && O.scale != 1) fail(BBOCR_ERR_ARG, "the imread form exists at scale 1 only");
-            for (int q = 0; q < o; ++q)
-                if (outputs[q].scale == O.scale) fail(BBOCR_ERR_ARG, "a scale is named twice");
-            if (O.form == BBOCR_JPEG_FORM_IMREAD) imread = o;
-        }
-        // the imread form's un-oriented decode goes to jd_page, as in bbocr_jpeg_imread
-        auto decoded = [](const bbocr_jpeg_plan& pl) { return pl.components == 3 ? PAGE_YCC4 : PAGE_GRAY; };
-        Carve pages;
-        std::vector<FileJob> jobs = jpeg_admit(files, bytes, n, status, [&](FileJob& j) {
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            for (int o = 0; o < n_outputs; ++o) {
-                const bbocr_jpeg_output& O = outputs[o];
-                if (!O.dev_out[j.k]) return false;
-                if (o == imread) {
-                    if (O.pitches[j.k] < (long long)page_px_bytes(PAGE_BGR) * (pl.orientation >= 5 ? pl.height : pl.width)) return false;
-                    j.pitch[o] = (long long)pl.width * page_px_bytes(decoded(pl));
-                } else {
-                    if (O.pitches[j.k] < (long long)scaled_dim(pl.width, O.scale) * page_px_bytes(pl.components == 3 ? layout : PAGE_GRAY)) return false;
-                    j.out[o] = O.dev_out[j.k];
-                    j.pitch[o] = O.pitches[j.k];
-                }
-            }
-            if (imread >= 0) j.o_page = pages.add((size_t)j.pitch[imread] * (size_t)pl.height);
-            return true;
-        });
-        if (jobs.empty()) return;
-        std::vector<JpegPass> passes;
-        for (int o = 0; o < n_outputs; ++o) passes.push_back({outputs[o].scale, page_px_bytes(o == imread ? (int)PAGE_YCC4 : layout)});
-        if (imread >= 0) {
-            ctx->jd_page.ensure(pages.off);
-            for (FileJob& j : jobs) j.out[imread] = Carve::at<uint8_t>(ctx->jd_page.p, j.o_page);
-        }
-        std::vector<int> ds;
-        jpeg_run(ctx, st, jobs, JD_SUBSEQ_BITS, passes, ds);
-        jpeg_report(jobs, ds, status);
-        if (imread < 0) return;
-        for (size_t i = 0; i < jobs.size(); ++i) {
-            const FileJob& j = jobs[i];
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            if (ds[i]) continue;
-            HIPCHK(launch_page_orient(j.out[imread], pl.height, pl.width, (size_t)j.pitch[imread], decoded(pl), pl.orientation, PAGE_BGR,
-                                      outputs[imread].dev_out[j.k], (size_t)outputs[imread].pitches[j.k], st));
-        }
-        HIPCHK(hipStreamSynchronize(st));
+int bbocr_op_jpeg_scaled_class_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
+                                     int* file_status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
+        if ((stage != 2 && stage != 3) || !draft_scale(scale)) fail(BBOCR_ERR_ARG, "stage 2 or 3 at scale 2, 4 or 8");
+        jpeg_stage_run(ctx, s, stage, file, bytes, JD_SUBSEQ_BITS, scale, 1, dev_dst, dst_bytes, file_status);
     });
 }
 
@@ -719,57 +689,14 @@ int bbocr_jpeg_counters(bbocr_ctx* ctx, long long* out) {
 }
 
 int bbocr_host_jpeg_scaled_geometry(const bbocr_jpeg_plan* plan, int scale, bbocr_jpeg_scaled_comp* comps) {
-    if (!plan || !comps || (scale != 2 && scale != 4 && scale != 8) || !jpeg_taken(*plan)) return BBOCR_ERR_ARG;
-    const bbocr_jpeg_plan& pl = *plan;
-    if ((pl.components != 1 && pl.components != 3) || pl.mcu_cols < 1 || pl.mcu_rows < 1) return BBOCR_ERR_ARG;
-    const int n = 8 / scale, h = luma_h(pl), v = luma_v(pl), oh = scaled_dim(pl.height, scale), ow = scaled_dim(pl.width, scale);
-    std::memset(comps, 0, 3 * sizeof *comps);
-    for (int c = 0; c < pl.components; ++c) {
-        bbocr_jpeg_scaled_comp& g = comps[c];
-        if (pl.components == 3 && !pl.chroma) {                           // 4:2:0: chroma blocks twice the edge, every plane of the output's size
-            g = {c == 0 ? n : 2 * n, pl.mcu_rows * 2 * n, pl.mcu_cols * 2 * n, oh, ow, c == 0 ? BBOCR_JPEG_UP_NONE : BBOCR_JPEG_UP_H2V2_NOT_NEEDED};
-        } else if (c == 0) {
-            g = {n, pl.mcu_rows * n * v, pl.mcu_cols * n * h, oh, ow, BBOCR_JPEG_UP_NONE};
-        } else {
-            const int up = h * v == 1 ? BBOCR_JPEG_UP_NONE : (scale == 8 ? BBOCR_JPEG_UP_REPLICATE : (h == 2 ? BBOCR_JPEG_UP_H2V1_FANCY : BBOCR_JPEG_UP_H1V2_FANCY));
-            g = {n, pl.mcu_rows * n, pl.mcu_cols * n, scaled_dim(oh, v), scaled_dim(ow, h), up};
-        }
+    if (!plan || !comps || !draft_scale(scale) || !jpeg_taken(*plan)) return BBOCR_ERR_ARG;
+    if ((plan->components != 1 && plan->components != 3) || plan->mcu_cols < 1 || plan->mcu_rows < 1) return BBOCR_ERR_ARG;
+    const JpegGeometry g = jpeg_geometry(*plan, scale);
+    for (int c = 0; c < 3; ++c) {                                         // comps[components .. 3) come out zeroed
+        const JpegComp& k = g.comp[c];
+        comps[c] = {k.n, k.plane_rows, k.pitch, k.valid_rows, k.valid_cols, k.up};
     }
     return BBOCR_OK;
-}
-
-int bbocr_op_jpeg_scaled_class_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int scale, void* dev_dst, size_t dst_bytes,
-                                     int* file_status) {
-    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
-        if (!file || !dev_dst || (stage != 2 && stage != 3) || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
-        if (scale != 2 && scale != 4 && scale != 8) fail(BBOCR_ERR_ARG, "scale must be 2, 4 or 8");
-        int status = 0;
-        std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
-            const bbocr_jpeg_plan& pl = j.ps.plan;
-            if (!pl.chroma) return false;
-            const size_t pix = (size_t)scaled_dim(pl.width, scale) * scaled_dim(pl.height, scale) * 3;
-            if (stage == 3 && dst_bytes < pix) fail(BBOCR_ERR_ARG, "destination too small");
-            ctx->jd_stage.ensure(pix);
-            j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
-            j.pitch[0] = (long long)scaled_dim(pl.width, scale) * 3;
-            return true;
-        });
-        if (jobs.empty()) fail(BBOCR_ERR_ARG, "not a file of a chroma class the plan takes");
-        const bbocr_jpeg_plan& pl = jobs[0].ps.plan;
-        const size_t ysz = class_luma_bytes(pl, scale), csz = class_chroma_bytes(pl, scale);
-        if (stage == 2 && dst_bytes < ysz + 2 * csz) fail(BBOCR_ERR_ARG, "destination too small");
-        std::vector<int> ds;
-        std::vector<JpegDesc> descs;
-        jpeg_run(ctx, s, jobs, JD_SUBSEQ_BITS, {{scale, 3}}, ds, &descs);
-        jpeg_report(jobs, ds, &status);
-        if (file_status) *file_status = status;
-        if (stage == 2) {
-            HIPCHK(hipMemcpyAsync(dev_dst, descs[0].plane[0], ysz, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz, descs[0].plane[1], csz, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync((char*)dev_dst + ysz + csz, descs[0].plane[2], csz, hipMemcpyDeviceToDevice, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    });
 }
 
 }  // extern "C"

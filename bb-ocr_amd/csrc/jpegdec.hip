@@ -7,13 +7,12 @@
 //   jd_scan     exclusive scan of the block counts: first output block of every subsequence
 //   jd_write    decode from the exact entry states into the zeroed coefficient buffer (natural order); checks what the file promised
 //   jd_dc       per component and restart segment: running sum of the DC differences
-//   jd_idct     dequantise + jidctint.c per block into the component planes
-//   jd_output   fancy upsampling by sampling class (h2v2, h2v1, h1v2, none) -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane,
-//               into the caller's tensor
-//   jd_idct_scaled / jd_output_scaled   the same two stages of a decode at scale 1/2, 1/4 or 1/8 (Pillow's draft): jidctred.c's reduced
-//               IDCTs per component, no upsampling (4:2:0 and grey files only)
-//   jd_idct_scaled_c / jd_output_scaled_c   those two stages for the files of a chroma class (4:4:4, 4:2:2, 4:4:0): n x n blocks for every
-//               component, chroma upsampled at the reduced size (fancy at 1/2 and 1/4, replicated at 1/8)
+//   jd_idct     dequantise + jidctint.c (8 x 8) or jidctred.c (4 x 4, 2 x 2, 1 x 1: a decode at scale 1/2, 1/4 or 1/8, Pillow's draft) per
+//               block into the component planes
+//   jd_output   the chroma planes brought to the output's size (fancy h2v2, h2v1, h1v2, replication, or as they are) -> YCbCr triples
+//               (3 or 4 bytes per pixel) or the grey plane, into the caller's tensor
+// The last two run once per requested output over the same coefficients.  What a scale and a sampling mean for them -- each component's
+// block edge, its place in the MCU, its plane and the upsampling rule -- is data: JpegDesc::comp, filled by jpegdec.cpp's jpeg_geometry.
 // An MCU holds hs x vs luma blocks (row after row), then one Cb and one Cr block: 2 x 2 for 4:2:0, 1 x 1 / 2 x 1 / 1 x 2 for the others.
 // The bytes are untrusted: every stream read is clamped to its segment (past the end: 1-bits), every store is index-checked, every loop
 // has a trip count fixed by the host's plan (S, lanes per workgroup, items per segment).
@@ -285,168 +284,27 @@ __global__ void __launch_bounds__(256) jd_dc_kernel(const JpegDesc* __restrict__
     }
 }
 
-// eight blocks per workgroup, eight lanes per block (a row, then a column, then a row again: thumb.hip's order)
-__global__ void __launch_bounds__(64) jd_idct_kernel(const JpegDesc* __restrict__ descs) {
-    __shared__ int blk[8][64];
-    const JpegDesc d = descs[blockIdx.y];
-    const int t = threadIdx.x, b = t >> 3, l = t & 7;
-    const int id = blockIdx.x * 8 + b;
-    if ((int)blockIdx.x * 8 >= d.nblocks) return;
-    const bool valid = id < d.nblocks;
-    const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
-    const int c = jd_comp(d, j);
-    if (valid) {
-        const short* co = d.coef + (size_t)id * 64 + l * 8;
-        const unsigned short* q = d.quant + c * 64 + l * 8;
-        for (int i = 0; i < 8; ++i) blk[b][l * 8 + i] = (int)co[i] * (int)q[i];
-    }
-    __syncthreads();
-    if (valid) idct8(&blk[b][l], 8, true);
-    __syncthreads();
-    if (valid) {
-        int* row = &blk[b][l * 8];
-        idct8(row, 1, false);
-        const int mx = mcu % d.mcux, my = mcu / d.mcux;
-        uint8_t* o;
-        if (d.bpm == 1) o = d.plane[0] + (size_t)(my * 8 + l) * (d.mcux * 8) + mx * 8;
-        else if (c == 0) o = d.plane[0] + (size_t)(my * 8 * d.vs + (j / d.hs) * 8 + l) * (d.mcux * 8 * d.hs) + mx * 8 * d.hs + (j % d.hs) * 8;
-        else o = (c == 1 ? d.plane[1] : d.plane[2]) + (size_t)(my * 8 + l) * (d.mcux * 8) + mx * 8;
-        for (int i = 0; i < 8; ++i) o[i] = (uint8_t)row[i];
-    }
-}
-
-__global__ void __launch_bounds__(256) jd_output_kernel(const JpegDesc* __restrict__ descs) {
-    const JpegDesc d = descs[blockIdx.z];
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= d.W || y >= d.H) return;
-    if (d.ncomp == 1) {
-        d.out[(size_t)y * d.pitch + x] = d.plane[0][(size_t)y * (d.mcux * 8) + x];
-        return;
-    }
-    const int wp = d.mcux * 8 * d.hs, cp = d.mcux * 8, ch = (d.H + 1) / 2, cw = (d.W + 1) / 2;
-    uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
-    o[0] = d.plane[0][(size_t)y * wp + x];
-    for (int c = 1; c < 3; ++c) {
-        const uint8_t* __restrict__ pl = d.plane[c];
-        int v;
-        if (d.hs == 2) v = d.vs == 2 ? th_fancy(pl, cp, ch, cw, y, x) : th_fancy_h2v1(pl, cp, cw, y, x);
-        else v = d.vs == 2 ? th_fancy_h1v2(pl, cp, ch, y, x) : pl[(size_t)y * cp + x];
-        o[c] = (uint8_t)v;
-    }
-    if (d.px == 4) o[3] = 255;
-}
-
-// ---- the decode at scale 1 / SC (SC 2, 4 or 8: libjpeg's scale_num / scale_denom, Pillow's draft): jdmaster.c gives every component its
-// own DCT_scaled_size -- luma blocks come out n x n with n = 8 / SC, the chroma blocks of a 4:2:0 file 2n x 2n (8 x 8 at SC 2: jidctint.c
-// itself), a grey file's blocks n x n -- so each plane has the output's size and jd_output_scaled only interleaves.
-// Plane geometry (whole MCUs): every plane of a file is mcuy * e rows of mcux * e samples, e = 2n for a 4:2:0 file and n for a grey one.
-
-// e: an MCU's edge in every plane of the file; the luma blocks of a 4:2:0 file have half that edge, every other block the whole
-template <int SC> __device__ __forceinline__ int jd_mcu_edge(const JpegDesc& d) { return d.bpm == 1 ? 8 / SC : 16 / SC; }
-
-// Eight blocks per workgroup, eight lanes per block as in jd_idct: a lane dequantises one row of coefficients (one 16-byte load), runs one
-// column of the first pass (the columns the second pass never reads are skipped, as in jidctred.c), then the lanes below the block's edge
-// run one row each of the second pass and store it as one word of `edge` bytes.
-template <int SC> __global__ void __launch_bounds__(64) jd_idct_scaled_kernel(const JpegDesc* __restrict__ descs) {
-    __shared__ int blk[8][64];
-    const JpegDesc d = descs[blockIdx.y];
-    const int t = threadIdx.x, b = t >> 3, l = t & 7;
-    const int id = blockIdx.x * 8 + b;
-    if ((int)blockIdx.x * 8 >= d.nblocks) return;
-    const bool valid = id < d.nblocks;
-    const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
-    const int c = jd_comp(d, j);
-    const int e = jd_mcu_edge<SC>(d);
-    const int n = (d.bpm != 1 && c == 0) ? e / 2 : e;                // the block's edge
-    if (valid) {
-        const uint4 raw = *(const uint4*)(d.coef + (size_t)id * 64 + l * 8);     // 16-byte aligned: blocks are 128 bytes apart
-        const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
-        const unsigned short* q = d.quant + c * 64 + l * 8;
-        for (int i = 0; i < 4; ++i) {
-            blk[b][l * 8 + 2 * i] = (int)(short)(w[i] & 0xFFFFu) * (int)q[2 * i];
-            blk[b][l * 8 + 2 * i + 1] = (int)(short)(w[i] >> 16) * (int)q[2 * i + 1];
-        }
-    }
-    __syncthreads();
-    if (valid) {
-        int* col = &blk[b][l];
-        if (n == 8) idct8(col, 8, true);
-        else if (n == 4) { if (l != 4) idct4(col, 8, true); }
-        else if (n == 2) { if (l == 0 || (l & 1)) idct2(col, 8, true); }
-    }
-    __syncthreads();
-    if (valid && l < n) {
-        int* row = &blk[b][l * 8];
-        if (n == 8) idct8(row, 1, false);
-        else if (n == 4) idct4(row, 1, false);
-        else if (n == 2) idct2(row, 1, false);
-        else row[0] = idct1(row[0]);
-        const int pw = d.mcux * e;
-        const int mx = mcu % d.mcux, my = mcu / d.mcux;
-        // a luma block of a 4:2:0 file sits at (j / 2, j % 2) of its MCU
-        const int by = (d.bpm != 1 && c == 0) ? (j >> 1) * n : 0, bx = (d.bpm != 1 && c == 0) ? (j & 1) * n : 0;
-        uint8_t* o = d.plane[c] + (size_t)(my * e + by + l) * pw + mx * e + bx;
-        if (n == 8) {
-            uint2 v;
-            v.x = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
-            v.y = (unsigned)row[4] | ((unsigned)row[5] << 8) | ((unsigned)row[6] << 16) | ((unsigned)row[7] << 24);
-            *(uint2*)o = v;                                           // pw and the offsets are multiples of 8, the planes 256-byte aligned
-        } else if (n == 4) {
-            *(unsigned*)o = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
-        } else if (n == 2) {
-            *(unsigned short*)o = (unsigned short)(row[0] | (row[1] << 8));
-        } else {
-            o[0] = (uint8_t)row[0];
-        }
-    }
-}
-
-// the planes -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane, OW x OH pixels into the caller's tensor
-template <int SC> __global__ void __launch_bounds__(256) jd_output_scaled_kernel(const JpegDesc* __restrict__ descs) {
-    const JpegDesc d = descs[blockIdx.z];
-    const int OW = (d.W + SC - 1) / SC, OH = (d.H + SC - 1) / SC;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= OW || y >= OH) return;
-    const int pw = d.mcux * jd_mcu_edge<SC>(d);
-    const size_t i = (size_t)y * pw + x;
-    if (d.ncomp == 1) {
-        d.out[(size_t)y * d.pitch + x] = d.plane[0][i];
-        return;
-    }
-    uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
-    const unsigned Y = d.plane[0][i], cb = d.plane[1][i], cr = d.plane[2][i];
-    if (d.px == 4 && ((d.pitch | (long long)(size_t)d.out) & 3) == 0) {
-        *(unsigned*)o = Y | (cb << 8) | (cr << 16) | (255u << 24);
-    } else {
-        o[0] = (uint8_t)Y;
-        o[1] = (uint8_t)cb;
-        o[2] = (uint8_t)cr;
-        if (d.px == 4) o[3] = 255;
-    }
-}
-
-// ---- the decode at scale 1 / SC of a file of a chroma class (4:4:4, 4:2:2, 4:4:0).  jdmaster.c doubles a component's DCT_scaled_size only
-// when both directions allow it; here one does not, so EVERY block comes out n x n, n = 8 / SC, and the chroma keeps the file's sampling:
-// Y [mcuy * n * vs][mcux * n * hs], Cb and Cr [mcuy * n][mcux * n].  jd_output_scaled_c upsamples: jdsample.c's fancy h2v1 / h1v2 at SC 2
-// and 4, plain replication at SC 8 (min_DCT_scaled_size 1 turns fancy upsampling off), nothing for 4:4:4.
-
 // A block's 8 x 8 words in LDS with rows JD_ROW words apart and blocks JD_BLK: a half-wave's 4 blocks x 8 lanes then touch 32 different
-// banks ((8 b + l) mod 32 in the column pass, (8 b + 9 l) mod 32 in the row pass and the dequantising stores), where blk[8][64] of
-// jd_idct_scaled puts the 4 blocks of a half-wave on one bank.
+// banks ((8 b + l) mod 32 in the column pass, (8 b + 9 l) mod 32 in the row pass and the dequantising stores); rows 8 words apart would
+// put the 4 blocks of a half-wave on one bank.
 constexpr int JD_ROW = 9, JD_BLK = 72;
 
-// jd_idct_scaled's shape: eight blocks per wavefront, one 16-byte coefficient load per lane, the first-pass columns the second pass never
-// reads skipped, one word of n bytes stored per row.  The MCU geometry is data (hs, vs) as in jd_idct.
-template <int SC> __global__ void __launch_bounds__(64) jd_idct_scaled_c_kernel(const JpegDesc* __restrict__ descs) {
+// Eight blocks per wavefront, eight lanes per block (a row, then a column, then a row again: thumb.hip's order).  A lane dequantises one row
+// of coefficients (one 16-byte load), runs one column of the first pass (the columns the second pass never reads are skipped, as in
+// jidctred.c), then the lanes below the block's edge n run one row each of the second pass and store it as one word of n bytes.  jdmaster.c
+// gives every component its own DCT_scaled_size, so the blocks of one wavefront may differ in n: comp[c] says which, and where block jj of
+// component c of an MCU goes -- (jj / bw, jj % bw) of the MCU's bh x bw blocks in a plane of `pitch` samples a row.
+__global__ void __launch_bounds__(64) jd_idct_kernel(const JpegDesc* __restrict__ descs) {
     __shared__ int blk[8][JD_BLK];
-    constexpr int n = 8 / SC;
-    const JpegDesc d = descs[blockIdx.y];
+    const JpegDesc& d = descs[blockIdx.y];                              // in place: comp[c] and plane[c] are read at a lane's own c
     const int t = threadIdx.x, b = t >> 3, l = t & 7;
     const int id = blockIdx.x * 8 + b;
     if ((int)blockIdx.x * 8 >= d.nblocks) return;
     const bool valid = id < d.nblocks;
     const int j = valid ? id % d.bpm : 0, mcu = valid ? id / d.bpm : 0;
     const int c = jd_comp(d, j);
+    const JpegComp g = d.comp[c];
+    const int n = g.n;
     if (valid && (n > 1 || l == 0)) {                                   // n == 1: the DC term alone is read
         const uint4 raw = *(const uint4*)(d.coef + (size_t)id * 64 + l * 8);     // 16-byte aligned: blocks are 128 bytes apart
         const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
@@ -459,43 +317,57 @@ template <int SC> __global__ void __launch_bounds__(64) jd_idct_scaled_c_kernel(
     __syncthreads();
     if (valid) {
         int* col = &blk[b][l];
-        if (n == 4) { if (l != 4) idct4(col, JD_ROW, true); }
+        if (n == 8) idct8(col, JD_ROW, true);
+        else if (n == 4) { if (l != 4) idct4(col, JD_ROW, true); }
         else if (n == 2) { if (l == 0 || (l & 1)) idct2(col, JD_ROW, true); }
     }
     __syncthreads();
     if (valid && l < n) {
         int* row = &blk[b][l * JD_ROW];
-        if (n == 4) idct4(row, 1, false);
+        if (n == 8) idct8(row, 1, false);
+        else if (n == 4) idct4(row, 1, false);
         else if (n == 2) idct2(row, 1, false);
         else row[0] = idct1(row[0]);
-        const int hs = c == 0 ? d.hs : 1, vs = c == 0 ? d.vs : 1;
-        const int pw = d.mcux * n * hs;
+        const int jj = c == 0 ? j : 0;                                  // the block's index within its component
         const int mx = mcu % d.mcux, my = mcu / d.mcux;
-        // luma block j of an MCU sits at (j / hs, j % hs)
-        const int by = c == 0 ? (j / d.hs) * n : 0, bx = c == 0 ? (j % d.hs) * n : 0;
-        uint8_t* o = d.plane[c] + (size_t)(my * vs * n + by + l) * pw + mx * n * hs + bx;    // pw and the offsets are multiples of n
-        if (n == 4) *(unsigned*)o = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
-        else if (n == 2) *(unsigned short*)o = (unsigned short)(row[0] | (row[1] << 8));
-        else o[0] = (uint8_t)row[0];
+        // pitch and both offsets are multiples of n, the planes 256-byte aligned: the word below is aligned
+        uint8_t* o = d.plane[c] + (size_t)((my * g.bh + jj / g.bw) * n + l) * g.pitch + (mx * g.bw + jj % g.bw) * n;
+        if (n == 8) {
+            uint2 v;
+            v.x = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
+            v.y = (unsigned)row[4] | ((unsigned)row[5] << 8) | ((unsigned)row[6] << 16) | ((unsigned)row[7] << 24);
+            *(uint2*)o = v;
+        } else if (n == 4) {
+            *(unsigned*)o = (unsigned)row[0] | ((unsigned)row[1] << 8) | ((unsigned)row[2] << 16) | ((unsigned)row[3] << 24);
+        } else if (n == 2) {
+            *(unsigned short*)o = (unsigned short)(row[0] | (row[1] << 8));
+        } else {
+            o[0] = (uint8_t)row[0];
+        }
     }
 }
 
-// one output pixel per lane; every chroma read stays inside the valid extent ceil(OH / vs) x ceil(OW / hs), not the padded plane
-template <int SC> __global__ void __launch_bounds__(256) jd_output_scaled_c_kernel(const JpegDesc* __restrict__ descs) {
-    constexpr int n = 8 / SC;
+// The planes -> YCbCr triples (3 or 4 bytes per pixel) or the grey plane, OW x OH pixels into the caller's tensor: one pixel per lane.
+// comp[c].up says how a chroma sample is found (jdsample.c); every chroma read stays inside the valid extent, not the padded plane.
+__global__ void __launch_bounds__(256) jd_output_kernel(const JpegDesc* __restrict__ descs) {
     const JpegDesc d = descs[blockIdx.z];
-    const int OW = (d.W + SC - 1) / SC, OH = (d.H + SC - 1) / SC;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= OW || y >= OH || d.ncomp != 3) return;
-    const int yp = d.mcux * n * d.hs, cp = d.mcux * n;
-    const int ch = (OH + d.vs - 1) / d.vs, cw = (OW + d.hs - 1) / d.hs;
-    unsigned v[3];
-    v[0] = d.plane[0][(size_t)y * yp + x];
+    if (x >= d.OW || y >= d.OH) return;
+    unsigned v[3] = {d.plane[0][(size_t)y * d.comp[0].pitch + x], 0, 0};
+    if (d.ncomp == 1) {
+        d.out[(size_t)y * d.pitch + x] = (uint8_t)v[0];
+        return;
+    }
     for (int c = 1; c < 3; ++c) {
         const uint8_t* __restrict__ pl = d.plane[c];
-        if (d.hs == 2) v[c] = SC == 8 ? pl[(size_t)y * cp + (x >> 1)] : (unsigned)th_fancy_h2v1(pl, cp, cw, y, x);
-        else if (d.vs == 2) v[c] = SC == 8 ? pl[(size_t)(y >> 1) * cp + x] : (unsigned)th_fancy_h1v2(pl, cp, ch, y, x);
-        else v[c] = pl[(size_t)y * cp + x];
+        const JpegComp& g = d.comp[c];
+        switch (g.up) {
+        case JD_UP_H2V2_FANCY: v[c] = (unsigned)th_fancy(pl, g.pitch, g.valid_rows, g.valid_cols, y, x); break;
+        case JD_UP_H2V1_FANCY: v[c] = (unsigned)th_fancy_h2v1(pl, g.pitch, g.valid_cols, y, x); break;
+        case JD_UP_H1V2_FANCY: v[c] = (unsigned)th_fancy_h1v2(pl, g.pitch, g.valid_rows, y, x); break;
+        case JD_UP_REPLICATE: v[c] = pl[(size_t)(y / d.comp[0].bh) * g.pitch + x / d.comp[0].bw]; break;   // one sample per luma MCU cell
+        default: v[c] = pl[(size_t)y * g.pitch + x];                    // the plane has the output's sampling
+        }
     }
     uint8_t* o = d.out + (size_t)y * d.pitch + (size_t)x * d.px;
     if (d.px == 4 && ((d.pitch | (long long)(size_t)d.out) & 3) == 0) {
@@ -532,40 +404,5 @@ hipError_t launch_jd_idct(const JpegDesc* descs, int n, int max_blocks, hipStrea
 }
 hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, hipStream_t s) {
     hipLaunchKernelGGL(jd_output_kernel, dim3((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n), dim3(256), 0, s, descs);
-    return hipGetLastError();
-}
-// scale: 2, 4 or 8; the descriptors are of 4:2:0 or grey files only (hs == vs == 2, or one component)
-hipError_t launch_jd_idct_scaled(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s) {
-    const dim3 grid((unsigned)((max_blocks + 7) / 8), (unsigned)n);
-    if (scale == 2) hipLaunchKernelGGL(jd_idct_scaled_kernel<2>, grid, dim3(64), 0, s, descs);
-    else if (scale == 4) hipLaunchKernelGGL(jd_idct_scaled_kernel<4>, grid, dim3(64), 0, s, descs);
-    else if (scale == 8) hipLaunchKernelGGL(jd_idct_scaled_kernel<8>, grid, dim3(64), 0, s, descs);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-// max_h, max_w: of the scaled outputs
-hipError_t launch_jd_output_scaled(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s) {
-    const dim3 grid((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n);
-    if (scale == 2) hipLaunchKernelGGL(jd_output_scaled_kernel<2>, grid, dim3(256), 0, s, descs);
-    else if (scale == 4) hipLaunchKernelGGL(jd_output_scaled_kernel<4>, grid, dim3(256), 0, s, descs);
-    else if (scale == 8) hipLaunchKernelGGL(jd_output_scaled_kernel<8>, grid, dim3(256), 0, s, descs);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-// scale: 2, 4 or 8; the descriptors are of files of a chroma class only (3 components, hs * vs <= 2)
-hipError_t launch_jd_idct_scaled_c(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s) {
-    const dim3 grid((unsigned)((max_blocks + 7) / 8), (unsigned)n);
-    if (scale == 2) hipLaunchKernelGGL(jd_idct_scaled_c_kernel<2>, grid, dim3(64), 0, s, descs);
-    else if (scale == 4) hipLaunchKernelGGL(jd_idct_scaled_c_kernel<4>, grid, dim3(64), 0, s, descs);
-    else if (scale == 8) hipLaunchKernelGGL(jd_idct_scaled_c_kernel<8>, grid, dim3(64), 0, s, descs);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-hipError_t launch_jd_output_scaled_c(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s) {
-    const dim3 grid((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 3) / 4), (unsigned)n);
-    if (scale == 2) hipLaunchKernelGGL(jd_output_scaled_c_kernel<2>, grid, dim3(256), 0, s, descs);
-    else if (scale == 4) hipLaunchKernelGGL(jd_output_scaled_c_kernel<4>, grid, dim3(256), 0, s, descs);
-    else if (scale == 8) hipLaunchKernelGGL(jd_output_scaled_c_kernel<8>, grid, dim3(256), 0, s, descs);
-    else return hipErrorInvalidValue;
     return hipGetLastError();
 }

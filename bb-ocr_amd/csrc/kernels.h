@@ -353,6 +353,16 @@ struct JpegHuff {                                              // one Huffman ta
     int valoff[18];                                            // index of the first symbol of length l minus its code
     unsigned char val[256];
 };
+// How the output stage brings a component's plane to the output's size.  The first five are include/bbocr.h's BBOCR_JPEG_UP_* (pinned in
+// jpegdec.cpp); a decode at scale 1 of a 4:2:0 file adds the sixth.
+enum : int { JD_UP_NONE = 0, JD_UP_H2V1_FANCY = 1, JD_UP_H1V2_FANCY = 2, JD_UP_H2V2_NOT_NEEDED = 3, JD_UP_REPLICATE = 4, JD_UP_H2V2_FANCY = 5 };
+struct JpegComp {                                              // one component's plane in one IDCT + output pass (jpegdec.cpp's jpeg_geometry)
+    int n;                                                     // edge of one block's samples: 8, 4, 2 or 1
+    int bw, bh;                                                // the component's blocks of an MCU across / down
+    int plane_rows, pitch;                                     // the plane in whole MCUs: mcuy * bh * n rows of pitch = mcux * bw * n samples
+    int valid_rows, valid_cols;                                // the extent the output stage reads
+    int up;                                                    // JD_UP_*
+};
 struct JpegDesc {                                              // one file of a batch; every pointer is device memory
     const uint8_t* data;                                       // entropy-coded bytes without stuffing and restart markers, segment after segment
     const int* seg_byte;                                       // [nseg + 1] first byte of each segment in `data`
@@ -366,9 +376,11 @@ struct JpegDesc {                                              // one file of a 
     int* flags;                                                // [passes + 1] flags[k] != 0: pass k changed a state
     int* status;                                               // JD_ERR_* bits
     short* coef;                                               // [nblocks][64] natural order, MCU block order
-    uint8_t* plane[3];                                         // Y [mcuy * 8 vs][mcux * 8 hs], then Cb, Cr [mcuy * 8][mcux * 8] each (a scaled decode: see launch_jd_idct_scaled)
-    uint8_t* out;
+    uint8_t* plane[3];                                         // Y, Cb, Cr of this pass: comp[c].plane_rows rows of comp[c].pitch samples
+    uint8_t* out;                                              // this pass's pixels: OH rows of OW, rows `pitch` bytes apart
     long long pitch;
+    JpegComp comp[3];                                          // this pass's geometry: all the IDCT and the output stage know of sampling and scale
+    int OW, OH;
     const JpegHuff* huff;                                      // [4]: DC 0, DC 1, AC 0, AC 1
     const unsigned short* quant;                               // [ncomp][64] natural order
     int W, H, ncomp, bpm, mcux, mcuy, nmcu, ri, nseg, nsub, S, nblocks, px, passes;
@@ -380,14 +392,7 @@ hipError_t launch_jd_sync(const JpegDesc* descs, int n, int max_groups, int pass
 hipError_t launch_jd_scan(const JpegDesc* descs, int n, hipStream_t s);
 hipError_t launch_jd_write(const JpegDesc* descs, int n, int max_groups, hipStream_t s);
 hipError_t launch_jd_dc(const JpegDesc* descs, int n, int max_seg, hipStream_t s);
+// One IDCT + output pass over descs[0 .. n) (one descriptor per file and pass): every block through the transform of its component's edge
+// into the component's plane, then the planes -> OW x OH pixels at `out`.  max_blocks, max_h, max_w: the largest nblocks, OH, OW of the pass.
 hipError_t launch_jd_idct(const JpegDesc* descs, int n, int max_blocks, hipStream_t s);
 hipError_t launch_jd_output(const JpegDesc* descs, int n, int max_h, int max_w, hipStream_t s);
-// the decode at scale 1/2, 1/4 or 1/8 (4:2:0 and grey files): reduced IDCTs into planes of the output's size, then the interleave; the
-// entropy stages above are the same.  The planes are then mcuy * e rows of mcux * e samples each, e = 16 / scale (grey: 8 / scale).
-hipError_t launch_jd_idct_scaled(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s);
-hipError_t launch_jd_output_scaled(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s);
-// the same two stages for files of a chroma class (4:4:4, 4:2:2, 4:4:0; hs, vs = the luma sampling): every block n x n, n = 8 / scale, into
-// Y [mcuy * n * vs][mcux * n * hs] and Cb, Cr [mcuy * n][mcux * n]; the output stage upsamples the chroma (h2v1 / h1v2 fancy at scale 2 and
-// 4, replication at scale 8) from its valid extent ceil(OH / vs) x ceil(OW / hs)
-hipError_t launch_jd_idct_scaled_c(const JpegDesc* descs, int n, int max_blocks, int scale, hipStream_t s);
-hipError_t launch_jd_output_scaled_c(const JpegDesc* descs, int n, int max_h, int max_w, int scale, hipStream_t s);

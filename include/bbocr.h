@@ -574,7 +574,8 @@ int bbocr_jpeg_counters(bbocr_ctx* ctx, long long* out);
 /* host only: the planes of a decode at scale 2, 4 or 8 of a file the decoder takes (plan->supported or plan->chroma), per component
  * comps[0 .. components): the block's edge, the plane in whole MCUs as the device keeps it, the valid extent inside it (what libjpeg
  * calls downsampled_height x downsampled_width) and how the output stage brings the component to the output's size.  comps[components .. 3)
- * are zeroed.  Another scale, a refused plan: BBOCR_ERR_ARG. */
+ * are zeroed.  Another scale, a refused plan: BBOCR_ERR_ARG.  These are the values the decoder itself runs on: the same table sizes its
+ * planes and is what its IDCT and output stages read from their descriptors. */
 enum {
     BBOCR_JPEG_UP_NONE = 0,            /* the plane has the output's sampling */
     BBOCR_JPEG_UP_H2V1_FANCY = 1,      /* 4:2:2 at scale 2 and 4: h2v1_fancy_upsample (h2v1_upsample when at most 2 samples wide) */

@@ -1,5 +1,5 @@
-"""-m gpu: the scaled decode of the chroma classes and the shared entropy pass on the device (csrc/jpegdec.hip's jd_idct_scaled_c /
-jd_output_scaled_c, bbocr_jpeg_decode_scales, bbocr_op_jpeg_scaled_class_stage, bbocr_jpeg_counters) against the restatement of
+"""-m gpu: the scaled decode of the chroma classes and the shared entropy pass on the device (csrc/jpegdec.hip's jd_idct / jd_output on
+the host's geometry table, bbocr_jpeg_decode_scales, bbocr_op_jpeg_scaled_class_stage, bbocr_jpeg_counters) against the restatement of
 tests/jpeg_scaled_chroma_ref.py, the installed Pillow's draft and the single-purpose entry points, bit for bit; then the previews that
 ride on them (preprocess.preview_device(device_decode="chroma"), extractor_batch.trace_previews) against preprocess.preview_host."""
 import ctypes as C
@@ -221,15 +221,17 @@ def test_decode_scales_equals_the_single_purpose_calls_and_pillow(reader):
 
 @pytest.mark.parametrize("layout,pad,offset", [(YCBCR3, 0, 0), (YCBCR3, 5, 1), (YCBCR4, 0, 0), (YCBCR4, 8, 4), (YCBCR4, 3, 0), (YCBCR4, 0, 3)])
 def test_destination_layouts_and_guard_bytes(reader, layout, pad, offset):
-    """3 and 4 bytes per pixel, odd pitches and destinations at odd byte offsets (the output kernels' byte path), whole words (their dword
-    path): the pixels are Pillow's and no byte outside them is written"""
+    """3 and 4 bytes per pixel, odd pitches and destinations at odd byte offsets (the output kernel's byte path), whole words (its dword
+    path), at scale 1 and the draft scales, every class: the pixels are Pillow's and no byte outside them is written.  The 1 x 1 and
+    3 x 2 files (H x W) reach the narrow-plane branch of the h2v2 fancy upsampling"""
     datas = [d for size in ((17, 15), (2, 37), (33, 50)) for _, d, _, _ in stage_files(size)]
     datas += [save(picture("noise", 50, 33, "RGB"), quality=85), save(picture("noise", 50, 33, "L"), quality=85)]
-    got, status = decode_scales(reader, datas, [(2, YCBCR), (4, YCBCR), (8, YCBCR)], layout=layout, pad=pad, offset=offset)
+    datas += [save(picture("noise", w, h, mode), quality=85) for mode in ("RGB", "L") for h, w in ((1, 1), (3, 2))]
+    got, status = decode_scales(reader, datas, [(1, YCBCR), (2, YCBCR), (4, YCBCR), (8, YCBCR)], layout=layout, pad=pad, offset=offset)
     assert status == [0] * len(datas)
     for k, d in enumerate(datas):
-        for s in SCALES:
-            assert np.array_equal(strip(got[k][s]), pillow_draft(d, s)), (k, s)
+        for s in (1,) + tuple(SCALES):
+            assert np.array_equal(strip(got[k][s]), want_at(d, s)), (k, s)
 
 
 def test_argument_errors_are_returned_before_any_work(reader):

@@ -1,8 +1,10 @@
 """Baseline JPEG decoding on the device (csrc/jpegdec.hip) against the host's libjpeg-turbo (Pillow), on one box.
 
     python tools/jpeg_decode_bench.py [--reps 10] [--extract 1024] [--photos 16] [--out profiles/bench_jpeg_decode.jsonl] [--device-only]
+                                      [--label NAME]
 
-Prints JSON lines and appends them to --out:
+Prints JSON lines and appends them to --out; `--label` names the build in every line (A/B runs of two libraries on one machine:
+BBOCR_LIB_PATH selects the library):
   * plan        bbocr_host_jpeg_plan per file (the only host work per file: one pass over the markers and the scan's FF bytes);
   * decode64    one bbocr_jpeg_decode call for a 64-page batch of 1280x960 quality-90 synthetic pages, ms per page, against
                 decode_file_ycc of the same files on one core;
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--photos", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_jpeg_decode.jsonl"))
     ap.add_argument("--device-only", action="store_true")
+    ap.add_argument("--label", default="in-tree")
     a = ap.parse_args()
     import torch
     from PIL import Image
@@ -44,6 +47,7 @@ def main():
     rows = []
 
     def emit(**row):
+        row["build"] = a.label
         print(json.dumps(row), flush=True)
         rows.append(row)
 
