@@ -63,6 +63,23 @@ class bbocr_jpeg_scaled_comp(C.Structure):
                 ("upsample", C.c_int)]
 
 
+CONV_ROUTE_IDS = ("NONE", "GEN64_P4", "GEN64_P8", "GEN64_P16", "GEN128_P4", "GEN128_P8", "GEN128_P16", "DMA64_FUSE1", "DMA64_POSTW", "RESW_POOL64",
+                  "RESW_1CH", "RESW_2CH", "DMA64_324_NF2", "DMA64_324", "DMA64_384", "DMA64_448", "DMA128_384", "DMA128_448", "DMA2X2_64",
+                  "DMA2X2_128", "DMA1X1_64", "DMA1X1_128", "DMA1X1_256", "DMA1X1_ADDUP")       # include/bbocr.h BBOCR_ROUTE_*, in order
+CONV_ROUTE_FIELDS = ("id", "status", "el", "wm", "wn", "mf", "piter", "npb", "ring", "nps", "fuse1", "nf", "epi", "ks", "addup", "resw", "OH", "OW",
+                     "TH", "TW", "PH", "PW", "NP", "sub", "stack", "tiles_x", "tiles_y", "ntiles_n", "nchunks", "ntaps", "lean", "grid", "threads",
+                     "persistent", "lds_bytes", "tail", "split_off")
+
+
+class bbocr_conv_route(C.Structure):
+    _fields_ = [(k, C.c_int) for k in CONV_ROUTE_FIELDS]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in CONV_ROUTE_FIELDS}
+        d["id"] = CONV_ROUTE_IDS[d["id"]]
+        return d
+
+
 class bbocr_page(C.Structure):
     _fields_ = [("dev_rgb", C.c_void_p), ("dev_gray", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("rgb_pitch", C.c_longlong),
                 ("gray_pitch", C.c_longlong)]
@@ -131,6 +148,8 @@ PROTOTYPES = {
                                        C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "bbocr_op_conv2d": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "bbocr_host_conv_route": (C.c_int, [C.c_int] * 16 + [C.POINTER(bbocr_conv_route)]),
+    "bbocr_op_conv2d_route": (C.c_int, [_vp, C.POINTER(bbocr_conv_route)]),
     "bbocr_crnn_logits": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "bbocr_op_qlinear": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_float)]),
     "bbocr_op_qlstm": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, _vp, _vp, _vp, _vp]),

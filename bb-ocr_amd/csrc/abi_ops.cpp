@@ -194,29 +194,92 @@ int bbocr_host_crop_plan(int H, int W, const int* hori, int n_hori, const double
 }
 
 // ---------------------------------------------------------------------------------------- single-operator entry points
+// bbocr_conv_route is ConvRoute (kernels.h) under its public name: the same ints in the same order
+static_assert(sizeof(bbocr_conv_route) == sizeof(ConvRoute) && offsetof(bbocr_conv_route, id) == offsetof(ConvRoute, id) &&
+                  offsetof(bbocr_conv_route, piter) == offsetof(ConvRoute, piter) && offsetof(bbocr_conv_route, resw) == offsetof(ConvRoute, resw) &&
+                  offsetof(bbocr_conv_route, OH) == offsetof(ConvRoute, OH) && offsetof(bbocr_conv_route, lean) == offsetof(ConvRoute, lean) &&
+                  offsetof(bbocr_conv_route, grid) == offsetof(ConvRoute, grid) && offsetof(bbocr_conv_route, lds_bytes) == offsetof(ConvRoute, lds_bytes) &&
+                  offsetof(bbocr_conv_route, split_off) == offsetof(ConvRoute, split_off),
+              "bbocr_conv_route mirrors ConvRoute");
+static_assert(BBOCR_ROUTE_COUNT == (int)CONV_ROUTE_COUNT && BBOCR_ROUTE_GEN64_P4 == (int)CONV_ROUTE_GEN64_P4 && BBOCR_ROUTE_GEN128_P16 == (int)CONV_ROUTE_GEN128_P16 &&
+                  BBOCR_ROUTE_DMA64_FUSE1 == (int)CONV_ROUTE_DMA64_FUSE1 && BBOCR_ROUTE_RESW_2CH == (int)CONV_ROUTE_RESW_2CH &&
+                  BBOCR_ROUTE_DMA64_448 == (int)CONV_ROUTE_DMA64_448 && BBOCR_ROUTE_DMA128_448 == (int)CONV_ROUTE_DMA128_448 &&
+                  BBOCR_ROUTE_DMA2X2_128 == (int)CONV_ROUTE_DMA2X2_128 && BBOCR_ROUTE_DMA1X1_ADDUP == (int)CONV_ROUTE_DMA1X1_ADDUP,
+              "BBOCR_ROUTE_* mirror ConvRouteId");
+
+// The ConvPlan and the ConvArgs of one bbocr_op_conv2d call: the launch and the dry run of bbocr_host_conv_route both start here.  The
+// pointers decide routes only by being null or not (a dry run passes stand-ins); the weights are uploaded by the caller that launches.
+static ConvArgs op_conv_setup(ConvPlan& p, int el, const uint16_t* in, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int dil,
+                              int relu_in, int relu_out, int out_f32, void* out, int pool_mode, int pool_relu, uint16_t* pool_out, const void* zero) {
+    if (!in || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 31) || Cout <= 0 || KH <= 0 || KW <= 0) fail(BBOCR_ERR_ARG, "bad conv arguments");
+    if (pool_mode < 0 || pool_mode > 2 || (pool_mode ? (!pool_out || out_f32) : !out)) fail(BBOCR_ERR_ARG, "bad conv output arguments");
+    p = make_plan(Cin, Cout, KH, KW, pad, dil, el);
+    const int store = cdiv(Cout, 16) * 16;
+    ConvArgs a = conv_args(p, Act{(uint16_t*)in, N, H, W, Cin});
+    a.relu_in0 = relu_in != 0; a.relu_out = relu_out != 0; a.out_f32 = out_f32 != 0;
+    a.out = out; a.out_cs = store; a.cout_store = store;
+    a.pool_mode = pool_mode; a.pool_relu = pool_relu != 0; a.store_full = (pool_mode && out) ? 1 : 0; a.pool_cs = store; a.pool_out = pool_out;
+    a.zero = zero;
+    return a;
+}
+
 int bbocr_op_conv2d(bbocr_ctx* ctx, const uint16_t* dev_in, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout, int KH,
                     int KW, int pad, int dil, int relu_in, int relu_out, int out_f32, void* dev_out, int pool_mode, int pool_relu,
                     uint16_t* dev_pool_out) {
     return guarded(ctx, [&](bbocr_ctx* ctx) {
-        if (!dev_in || !w || Cin <= 0 || (Cin & 31) || Cout <= 0 || KH <= 0 || KW <= 0) fail(BBOCR_ERR_ARG, "bad conv arguments");
-        if (pool_mode < 0 || pool_mode > 2 || (pool_mode ? (!dev_pool_out || out_f32) : !dev_out)) fail(BBOCR_ERR_ARG, "bad conv output arguments");
-        ConvPlan p = make_plan(Cin, Cout, KH, KW, pad, dil, det_el(ctx));     // element type of the context's precision (bf16 / fp16)
+        if (!w) fail(BBOCR_ERR_ARG, "bad conv arguments");
+        {
+            std::lock_guard<std::mutex> lk(ctx->root->pool_mu);
+            ctx->root->op_conv_route = ConvRoute{};
+        }
+        ConvPlan p;
+        ConvArgs a = op_conv_setup(p, det_el(ctx), dev_in, N, H, W, Cin, Cout, KH, KW, pad, dil, relu_in, relu_out, out_f32, dev_out, pool_mode,
+                                   pool_relu, dev_pool_out, ctx->zero_page);     // element type of the context's precision (bf16 / fp16)
         std::vector<float> wv(w, w + (size_t)Cout * Cin * KH * KW), bv(Cout, 0.f);
         if (bias) std::copy(bias, bias + Cout, bv.begin());
         const size_t owned0 = ctx->owned.size();
         upload_plan(ctx, p, wv, bv);
-        const int store = cdiv(Cout, 16) * 16;
-        ConvArgs a = conv_args(p, Act{(uint16_t*)dev_in, N, H, W, Cin});
-        a.relu_in0 = relu_in != 0; a.relu_out = relu_out != 0; a.out_f32 = out_f32 != 0;
-        a.out = dev_out; a.out_cs = store; a.cout_store = store;
-        a.pool_mode = pool_mode; a.pool_relu = pool_relu != 0; a.store_full = (pool_mode && dev_out) ? 1 : 0; a.pool_cs = store; a.pool_out = dev_pool_out;
-        a.zero = ctx->zero_page;
-        const hipError_t e = launch_conv(p, a, ctx->stream);
+        ConvRoute route{};
+        const hipError_t e = launch_conv(p, a, ctx->stream, &route);
         const hipError_t e2 = hipStreamSynchronize(ctx->stream);
         while (ctx->owned.size() > owned0) { (void)hipFree(ctx->owned.back()); ctx->owned.pop_back(); ctx->owned_bytes.pop_back(); }
+        {
+            std::lock_guard<std::mutex> lk(ctx->root->pool_mu);
+            ctx->root->op_conv_route = route;
+        }
         HIPCHK(e);
         HIPCHK(e2);
     }, /*exclusive=*/true);      // uploads a temporary plan into the root's weight list
+}
+
+int bbocr_op_conv2d_route(bbocr_ctx* ctx, bbocr_conv_route* out) {
+    if (!ctx || !out) return BBOCR_ERR_ARG;
+    bbocr_ctx* root = ctx->root ? ctx->root : ctx;
+    std::lock_guard<std::mutex> lk(root->pool_mu);
+    memcpy(out, &root->op_conv_route, sizeof(*out));
+    return BBOCR_OK;
+}
+
+int bbocr_host_conv_route(int el, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int dil, int relu_in, int relu_out, int out_f32,
+                          int pool_mode, int pool_relu, int store_full, bbocr_conv_route* out) {
+    if (!out || (el != 0 && el != 1)) return BBOCR_ERR_ARG;
+    memset(out, 0, sizeof(*out));
+    try {
+        // stand-ins for the device pointers of the call: the dispatch only asks whether they are there
+        static uint16_t here[8];
+        const bool full = !pool_mode || store_full;
+        ConvPlan p;
+        ConvArgs a = op_conv_setup(p, el, here, N, H, W, Cin, Cout, KH, KW, pad, dil, relu_in, relu_out, out_f32, full ? (void*)here : nullptr, pool_mode,
+                                   pool_relu, pool_mode ? here : nullptr, here);
+        ConvRoute route{};
+        const hipError_t e = launch_conv(p, a, nullptr, &route, /*dry=*/true);
+        memcpy(out, &route, sizeof(*out));
+        return e == hipSuccess ? BBOCR_OK : BBOCR_ERR_HIP;      // what bbocr_op_conv2d returns for the refusal; out->status has the HIP code
+    } catch (const StatusError& se) {
+        return se.code;
+    } catch (...) {
+        return BBOCR_ERR_INTERNAL;
+    }
 }
 
 int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW, float* dev_logits) {

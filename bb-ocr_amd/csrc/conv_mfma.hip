@@ -1187,21 +1187,39 @@ __global__ void __launch_bounds__(256, 2) conv3x3_resw_kernel(const ConvArgs a) 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ route report (host)
+// Every terminal of the dispatch below calls this with the ConvArgs it is about to launch, then adds its family's template numbers.  A dry
+// run (launch_conv's `dry`) returns right behind it: the report is written by the code that launches, there is no second copy of the rules.
+static ConvRoute* route_fill(ConvRoute* r, int id, const ConvArgs& a, int el, int wm, int wn, int mf, long long grid, size_t lds) {
+    if (!r) return nullptr;
+    *r = ConvRoute{};
+    r->id = id; r->el = el; r->wm = wm; r->wn = wn; r->mf = mf;
+    r->OH = a.OH; r->OW = a.OW; r->TH = a.TH; r->TW = a.TW; r->PH = a.PH; r->PW = a.PW; r->NP = a.NP; r->sub = a.sub; r->stack = a.stack;
+    r->tiles_x = a.tiles_x; r->tiles_y = a.tiles_y; r->ntiles_n = a.ntiles_n; r->nchunks = a.nchunks; r->ntaps = a.ntaps; r->lean = a.lean;
+    r->grid = (int)grid; r->threads = wm * wn * 64; r->lds_bytes = (int)lds;
+    r->tail = a.tail != nullptr; r->split_off = a.split_off;
+    return r;
+}
+
 template <int EL>
-static hipError_t launch_resw(const ConvArgs& a, hipStream_t s) {
+static hipError_t launch_resw(const ConvArgs& a, hipStream_t s, ConvRoute* route, bool dry) {
     const int ntiles = a.N * a.tiles_x * a.tiles_y;
-    const int ncu = device_cus();
-    auto go = [&](auto kern, size_t smem, int per_cu, LdsOptIn& attr) -> hipError_t {
+    auto go = [&](auto kern, size_t smem, int per_cu, LdsOptIn& attr, int id, int variant, int nf) -> hipError_t {
+        ConvRoute* r = route_fill(route, id, a, EL, 4, 1, 4, ntiles, smem);
+        if (r) { r->resw = variant; r->persistent = per_cu; r->npb = 6; r->nps = 324; r->nf = nf; r->ks = 3; }
+        if (dry) return hipSuccess;
+        const int ncu = device_cus();
         if (hipError_t e = lds_opt_in(attr, (const void*)kern, smem); e != hipSuccess) return e;
         const int grid = ntiles < ncu * per_cu ? ntiles : ncu * per_cu;
+        if (r) r->grid = grid;
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, a);
         return hipGetLastError();
     };
     constexpr size_t P = 324 * 64, W1 = 9 * 2048, W2 = 18 * 2048;
     static LdsOptIn at[3];
-    if (a.cout_store == 64) return go(conv3x3_resw_kernel<EL, 1, true, 4, true>, 9 * 4096 + 2 * P, 2, at[2]);       // 78.3 KB: two workgroups per CU
-    if (a.nchunks == 1) return go(conv3x3_resw_kernel<EL, 1, true>, W1 + 2 * P, 2, at[0]);         // 59.9 KB: two workgroups per CU
-    return go(conv3x3_resw_kernel<EL, 2, false>, W2 + 2 * P, 2, at[1]);                            // 78.3 KB: two
+    if (a.cout_store == 64) return go(conv3x3_resw_kernel<EL, 1, true, 4, true>, 9 * 4096 + 2 * P, 2, at[2], CONV_ROUTE_RESW_POOL64, 1, 4);       // 78.3 KB: two workgroups per CU
+    if (a.nchunks == 1) return go(conv3x3_resw_kernel<EL, 1, true>, W1 + 2 * P, 2, at[0], CONV_ROUTE_RESW_1CH, 2, 2);         // 59.9 KB: two workgroups per CU
+    return go(conv3x3_resw_kernel<EL, 2, false>, W2 + 2 * P, 2, at[1], CONV_ROUTE_RESW_2CH, 3, 2);                            // 78.3 KB: two
 }
 
 // ================================================================================================ CRAFT upconv4 in one launch
@@ -1514,10 +1532,13 @@ __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_
 }
 
 template <int EL, int WM, int WN, int MF, bool ADDUP>
-static hipError_t launch_dma1x1_k(const ConvArgs& a, long long grid, hipStream_t s) {
+static hipError_t launch_dma1x1_k(const ConvArgs& a, long long grid, hipStream_t s, ConvRoute* route, bool dry) {
     constexpr int RING = 3, NPX = WM * MF * 16;
     auto k = conv1x1_dma_kernel<EL, WM, WN, MF, RING, ADDUP>;
     const size_t smem = (size_t)RING * ((size_t)WN * 64 * 64 + (size_t)NPX * 64);
+    constexpr int id = ADDUP ? CONV_ROUTE_DMA1X1_ADDUP : (WN == 1 ? CONV_ROUTE_DMA1X1_64 : (WN == 2 ? CONV_ROUTE_DMA1X1_128 : CONV_ROUTE_DMA1X1_256));
+    if (ConvRoute* r = route_fill(route, id, a, EL, WM, WN, MF, grid, smem)) { r->ring = RING; r->addup = ADDUP; r->ks = 1; }
+    if (dry) return hipSuccess;
     static LdsOptIn attr;
     if (hipError_t e = lds_opt_in(attr, (const void*)k, smem); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3((int)grid), dim3(WM * WN * 64), smem, s, a);
@@ -1525,7 +1546,7 @@ static hipError_t launch_dma1x1_k(const ConvArgs& a, long long grid, hipStream_t
 }
 
 template <int EL, int WM, int WN, int MF>
-static hipError_t launch_dma1x1(ConvArgs a, hipStream_t s) {
+static hipError_t launch_dma1x1(ConvArgs a, hipStream_t s, ConvRoute* route, bool dry) {
     constexpr int NPX = WM * MF * 16;
     const long long total = (long long)a.N * a.H * a.W;
     if (total > 0x7fffffffLL) return hipErrorInvalidValue;
@@ -1535,7 +1556,7 @@ static hipError_t launch_dma1x1(ConvArgs a, hipStream_t s) {
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
     // the epilogue that adds an up-sampled tensor is its own instantiation: its register needs must not leak into the others
     // (8-wave tiles, one workgroup per CU: a ring of 4 measured no faster than 3 -- 389 vs 383 us on fc7)
-    return a.addup ? launch_dma1x1_k<EL, WM, WN, MF, true>(a, grid, s) : launch_dma1x1_k<EL, WM, WN, MF, false>(a, grid, s);
+    return a.addup ? launch_dma1x1_k<EL, WM, WN, MF, true>(a, grid, s, route, dry) : launch_dma1x1_k<EL, WM, WN, MF, false>(a, grid, s, route, dry);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -1567,8 +1588,11 @@ void pack_conv_weights(const ConvPlan& p, const float* w, uint16_t* out) {
 }
 
 template <int EL, int WM, int WN, int MF, int PITER>
-static hipError_t launch_one(const ConvArgs& a, size_t smem, int grid, hipStream_t s) {
+static hipError_t launch_one(const ConvArgs& a, size_t smem, int grid, hipStream_t s, ConvRoute* route, bool dry) {
     auto k = conv_mfma_kernel<EL, WM, WN, MF, PITER>;
+    constexpr int id = (WN == 1 ? CONV_ROUTE_GEN64_P4 : CONV_ROUTE_GEN128_P4) + (PITER == 4 ? 0 : (PITER == 8 ? 1 : 2));
+    if (ConvRoute* r = route_fill(route, id, a, EL, WM, WN, MF, grid, smem)) { r->piter = PITER; r->ring = 2; }
+    if (dry) return hipSuccess;
     static LdsOptIn attr;    // per instantiation and device: high-water mark of the opt-in dynamic LDS size
     if (hipError_t e = lds_opt_in(attr, (const void*)k, smem); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(WM * WN * 64), smem, s, a);
@@ -1576,21 +1600,19 @@ static hipError_t launch_one(const ConvArgs& a, size_t smem, int grid, hipStream
 }
 
 template <int EL, int WM, int WN, int MF, int PITER>
-static hipError_t launch_cfg(const ConvArgs& a, int grid, hipStream_t s) {
+static hipError_t launch_cfg(const ConvArgs& a, int grid, hipStream_t s, ConvRoute* route, bool dry) {
     const size_t smem = (size_t)2 * WN * 64 * 64 + (size_t)2 * a.NP * 64;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    return launch_one<EL, WM, WN, MF, PITER>(a, smem, grid, s);
+    return launch_one<EL, WM, WN, MF, PITER>(a, smem, grid, s, route, dry);
 }
 
 template <int EL, int WM, int WN, int MF, int NPB, int RING, int NPS = NPB * 64, bool FUSE1 = false, int NF = 4, int EPI = 0, int KS = 3>
-static hipError_t launch_dma_one(ConvArgs a, int grid, hipStream_t s) {
+static hipError_t launch_dma_one(ConvArgs a, int grid, hipStream_t s, int id, ConvRoute* route, bool dry) {
     auto k = conv3x3_dma_kernel<EL, WM, WN, MF, NPB, RING, NPS, FUSE1, NF, EPI, KS>;
     const size_t smem_max = (size_t)RING * WN * 64 * 64 + (size_t)2 * NPS * 64;
     // a single 32-channel chunk (conv_cls: Cin = 32) never touches the second patch buffer: without it a workgroup needs 33 KB and
     // FOUR share a CU -- these launches are bound by per-tile latency, not by MFMA or HBM
     const size_t smem = (a.nchunks == 1 && !FUSE1) ? smem_max - (size_t)NPS * 64 : smem_max;
-    static LdsOptIn attr;
-    if (hipError_t e = lds_opt_in(attr, (const void*)k, smem_max); e != hipSuccess) return e;
     {   // which epilogue (conv_epilogue_plain_lean / conv_epilogue_pool2x2_lean / the shared one): plain layers whose waves store all their 64 couts
         a.lean = 0;
         const bool plain = !FUSE1 && EPI == 0 && KS == 3 && NF == 4 && a.sub == 1 && !a.out_f32 && !a.tail && !a.split_off && !a.addup && !a.post_w &&
@@ -1598,26 +1620,32 @@ static hipError_t launch_dma_one(ConvArgs a, int grid, hipStream_t s) {
         if (plain && a.pool_mode == 0 && a.out) a.lean = 1;
         else if (plain && a.pool_mode == 1 && !a.store_full && a.TH == 16 && a.TW == 16 && a.pool_out) a.lean = 3;
     }
+    if (ConvRoute* r = route_fill(route, id, a, EL, WM, WN, MF, grid, smem)) {
+        r->npb = NPB; r->ring = RING; r->nps = NPS; r->fuse1 = FUSE1; r->nf = NF; r->epi = EPI; r->ks = KS;
+    }
+    if (dry) return hipSuccess;
+    static LdsOptIn attr;
+    if (hipError_t e = lds_opt_in(attr, (const void*)k, smem_max); e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(WM * WN * 64), smem, s, a);
     return hipGetLastError();
 }
 
 template <int EL, int WM, int WN, int MF>
-static hipError_t launch_dma(const ConvArgs& a, int npb, int grid, hipStream_t s) {
+static hipError_t launch_dma(const ConvArgs& a, int npb, int grid, hipStream_t s, ConvRoute* route, bool dry) {
     if constexpr (WN == 1) {
         if (a.c11_w) {   // conv1_2 with the conv1_1 producer fused in
             if (!(npb == 6 && a.PH == 18 && a.PW == 18 && a.TH == 16 && a.TW == 16 && a.nchunks == 2 && a.sub == 1)) return hipErrorInvalidValue;
             // the kernel's only epilogue: 64 stored couts, MaxPool2d(2,2) fused, nothing but the pooled 16-bit tensor kept
             if (!(a.pool_mode == 1 && !a.store_full && !a.split_off && !a.out_f32 && !a.tail && a.cout_store == 64 && a.ntiles_n == 1 && a.acc_scale > 0.f))
                 return hipErrorInvalidValue;
-            return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, true>(a, grid, s);
+            return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, true>(a, grid, s, CONV_ROUTE_DMA64_FUSE1, route, dry);
         }
     }
     if (a.post_w) {   // 1x1 64 -> 64 behind the layer: 16 x 16 tiles of a plain 64-cout layer only, anything else is declined
         if constexpr (WN == 1)
             if (npb == 6 && a.PH == 18 && a.PW == 18 && a.cout_store == 64 && a.ntiles_n == 1 && a.sub == 1 && !a.pool_mode && !a.split_off &&
                 !a.out_f32 && !a.tail && !a.addup)
-                return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 4, 1>(a, grid, s);
+                return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 4, 1>(a, grid, s, CONV_ROUTE_DMA64_POSTW, route, dry);
         return hipErrorNotSupported;
     }
     if constexpr (WN == 1) {
@@ -1625,21 +1653,21 @@ static hipError_t launch_dma(const ConvArgs& a, int npb, int grid, hipStream_t s
         // trimmed to its 18 x 18 = 324 pixels and a 3-deep weight ring are 53,760 B of LDS (3 x 53,760 <= 160 KB)
         if (npb == 6 && a.PH * a.PW == 324) {
             if (a.cout_store <= 32 && a.nchunks <= 2 && a.sub == 1 && !a.C1 && !a.pool_mode && a.TH == 16 && a.TW == 16 && a.ntiles_n == 1)
-                return launch_resw<EL>(a, s);
+                return launch_resw<EL>(a, s, route, dry);
             // one input chunk, 64 couts, MaxPool2d(2,2) fused and only the pooled tensor kept (the CRNN's 32 -> 64 layer): nine 4 KB slices resident
             if (a.cout_store == 64 && a.nchunks == 1 && a.sub == 1 && !a.C1 && a.pool_mode == 1 && !a.store_full && !a.split_off && !a.out_f32 &&
                 !a.tail && !a.relu_in0 && a.TH == 16 && a.TW == 16 && a.ntiles_n == 1 && a.acc_scale > 0.f)
-                return launch_resw<EL>(a, s);
-            if (a.cout_store <= 32) return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 2>(a, grid, s);
-            return launch_dma_one<EL, WM, WN, MF, 6, 3, 324>(a, grid, s);
+                return launch_resw<EL>(a, s, route, dry);
+            if (a.cout_store <= 32) return launch_dma_one<EL, WM, WN, MF, 6, 3, 324, false, 2>(a, grid, s, CONV_ROUTE_DMA64_324_NF2, route, dry);
+            return launch_dma_one<EL, WM, WN, MF, 6, 3, 324>(a, grid, s, CONV_ROUTE_DMA64_324, route, dry);
         }
-        if (npb == 6) return launch_dma_one<EL, WM, WN, MF, 6, 3>(a, grid, s);      // measured faster than the 4-deep ring at this tile
+        if (npb == 6) return launch_dma_one<EL, WM, WN, MF, 6, 3>(a, grid, s, CONV_ROUTE_DMA64_384, route, dry);      // measured faster than the 4-deep ring at this tile
     } else if (npb == 6) {
-        const size_t wb = (size_t)WN * 64 * 64, pb = (size_t)2 * npb * 64 * 64;
-        // the deepest ring that still lets two workgroups share a CU
-        return 4 * wb + pb <= 80 * 1024 ? launch_dma_one<EL, WM, WN, MF, 6, 4>(a, grid, s) : launch_dma_one<EL, WM, WN, MF, 6, 3>(a, grid, s);
+        // the deepest ring that still lets two workgroups share a CU: four 8 KB weight slices + two 24 KB patch buffers = 80 KB
+        static_assert(WN != 2 || 4 * (size_t)WN * 64 * 64 + (size_t)2 * 6 * 64 * 64 <= 80 * 1024, "a 4-deep ring fits twice per CU");
+        return launch_dma_one<EL, WM, WN, MF, 6, 4>(a, grid, s, CONV_ROUTE_DMA128_384, route, dry);
     }
-    if (npb == 7) return launch_dma_one<EL, WM, WN, MF, 7, 3>(a, grid, s);
+    if (npb == 7) return launch_dma_one<EL, WM, WN, MF, 7, 3>(a, grid, s, WN == 1 ? CONV_ROUTE_DMA64_448 : CONV_ROUTE_DMA128_448, route, dry);
     return hipErrorInvalidValue;
 }
 
@@ -1648,7 +1676,7 @@ int conv_plan_bn(int Cout) {   // couts per workgroup tile (64-cout tiles measur
 }
 
 template <int EL>
-static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
+static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s, ConvRoute* route, bool dry) {
     const int BN = p.BN;
     constexpr int NWV = 4;       // waves per workgroup
     constexpr int BM = 256;      // output pixels per workgroup tile
@@ -1687,7 +1715,7 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
             a.bias = p.d_b;
             const long long g = (long long)a.N * a.tiles_x * a.tiles_y * a.ntiles_n;
             if (g > 0 && g <= 0x7fffffffLL)
-                return BN == 128 ? launch_dma<EL, 2, 2, 8>(a, a.NP / 64, (int)g, s) : launch_dma<EL, 4, 1, 4>(a, a.NP / 64, (int)g, s);
+                return BN == 128 ? launch_dma<EL, 2, 2, 8>(a, a.NP / 64, (int)g, s, route, dry) : launch_dma<EL, 4, 1, 4>(a, a.NP / 64, (int)g, s, route, dry);
             a.sub = 1;
             a.stack = 0;
         }
@@ -1731,27 +1759,32 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s) {
                      a.cout_store == p.Cout_pad))
         return hipErrorInvalidValue;
     if (p.KH == 1 && p.KW == 1 && p.pad_h == 0 && p.pad_w == 0 && a.zero && !a.pool_mode)
-        return BN == 256 ? launch_dma1x1<EL, 2, 4, 8>(a, s) : (BN == 128 ? launch_dma1x1<EL, 2, 2, 8>(a, s) : launch_dma1x1<EL, 4, 1, 4>(a, s));
+        return BN == 256 ? launch_dma1x1<EL, 2, 4, 8>(a, s, route, dry) : (BN == 128 ? launch_dma1x1<EL, 2, 2, 8>(a, s, route, dry) : launch_dma1x1<EL, 4, 1, 4>(a, s, route, dry));
     if (dma2x2)
-        return BN == 128 ? launch_dma_one<EL, 2, 2, 8, 6, 4, 384, false, 4, 0, 2>(a, grid, s) : launch_dma_one<EL, 4, 1, 4, 6, 3, 384, false, 4, 0, 2>(a, grid, s);
+        return BN == 128 ? launch_dma_one<EL, 2, 2, 8, 6, 4, 384, false, 4, 0, 2>(a, grid, s, CONV_ROUTE_DMA2X2_128, route, dry)
+                         : launch_dma_one<EL, 4, 1, 4, 6, 3, 384, false, 4, 0, 2>(a, grid, s, CONV_ROUTE_DMA2X2_64, route, dry);
     if (p.KH == 3 && p.KW == 3 && p.dil == 1 && p.pad_h == 1 && p.pad_w == 1 && a.zero) {
         const int npb = cdiv(a.PH * a.PW, 64);
         if (npb == 6 || npb == 7) {
             a.NP = npb * 64;
-            return BN == 128 ? launch_dma<EL, 2, 2, 8>(a, npb, grid, s) : launch_dma<EL, 4, 1, 4>(a, npb, grid, s);
+            return BN == 128 ? launch_dma<EL, 2, 2, 8>(a, npb, grid, s, route, dry) : launch_dma<EL, 4, 1, 4>(a, npb, grid, s, route, dry);
         }
     }
     // the generic kernel below knows neither the fused conv1_1 producer (in0 would be read as a 64-channel tensor: an out-of-bounds access on
     // the uint8 page, a GPU fault in round 4) nor the up-sampling epilogue nor the 1x1 behind the layer: refuse, never run garbage
     if (a.c11_w || a.addup || a.post_w) return hipErrorNotSupported;
     const int piter = cdiv(a.NP / 16, NWV);
-    if (BN == 128) return piter <= 4 ? launch_cfg<EL, 2, 2, 8, 4>(a, grid, s) : (piter <= 8 ? launch_cfg<EL, 2, 2, 8, 8>(a, grid, s) : launch_cfg<EL, 2, 2, 8, 16>(a, grid, s));
-    if (BN == 64) return piter <= 4 ? launch_cfg<EL, 4, 1, 4, 4>(a, grid, s) : (piter <= 8 ? launch_cfg<EL, 4, 1, 4, 8>(a, grid, s) : launch_cfg<EL, 4, 1, 4, 16>(a, grid, s));
+    if (BN == 128) return piter <= 4 ? launch_cfg<EL, 2, 2, 8, 4>(a, grid, s, route, dry) : (piter <= 8 ? launch_cfg<EL, 2, 2, 8, 8>(a, grid, s, route, dry) : launch_cfg<EL, 2, 2, 8, 16>(a, grid, s, route, dry));
+    if (BN == 64) return piter <= 4 ? launch_cfg<EL, 4, 1, 4, 4>(a, grid, s, route, dry) : (piter <= 8 ? launch_cfg<EL, 4, 1, 4, 8>(a, grid, s, route, dry) : launch_cfg<EL, 4, 1, 4, 16>(a, grid, s, route, dry));
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv(const ConvPlan& p, ConvArgs a, hipStream_t s) {
+hipError_t launch_conv(const ConvPlan& p, ConvArgs a, hipStream_t s, ConvRoute* route, bool dry) {
+    if (route) *route = ConvRoute{};          // id CONV_ROUTE_NONE until a terminal is reached
     a.acc_scale = p.acc_scale;
-    if (a.split_off && (a.out_f32 || a.tail || a.addup || p.el != 1)) return hipErrorInvalidValue;   // hi|lo outputs: fp16 stores only
-    return p.el ? launch_conv_el<1>(p, a, s) : launch_conv_el<0>(p, a, s);
+    hipError_t e = hipErrorInvalidValue;
+    if (!(a.split_off && (a.out_f32 || a.tail || a.addup || p.el != 1)))                             // hi|lo outputs: fp16 stores only
+        e = p.el ? launch_conv_el<1>(p, a, s, route, dry) : launch_conv_el<0>(p, a, s, route, dry);
+    if (route) route->status = (int)e;
+    return e;
 }

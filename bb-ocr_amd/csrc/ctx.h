@@ -190,6 +190,7 @@ struct bbocr_ctx : WeightView {
     std::mutex enq_mu;                        // root only: held while a slot queues ONE block of launches (a detector pass, a recogniser part, a
                                               // sequence stage) on the shared compute stream, so that blocks of concurrent calls do not interleave kernel
                                               // by kernel (the per-launch HIP events of the roofline leg would then time foreign kernels too)
+    ConvRoute op_conv_route{};                // root only (guarded by pool_mu): what the last bbocr_op_conv2d launch recorded (bbocr_op_conv2d_route)
     bool slot_busy = false;                   // this slot is running a call
     hipStream_t stream = nullptr;             // the compute stream (root's; slots share it: kernels of concurrent calls run in issue order)
     DevBuf pp_gray, pp_a, pp_b, pp_c, pp_tab;  // pre-processing chain (f2): planes and small tables

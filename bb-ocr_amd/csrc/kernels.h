@@ -67,11 +67,53 @@ struct ConvPlan {      // host-side description of one packed conv layer
     float* d_b = nullptr;      // device bias [Cout_pad]
 };
 
+// Which kernel launch_conv took: one id per terminal of the dispatch (conv_mfma.hip, launch_conv_el and the launchers under it).  Host side
+// only -- it is NOT part of ConvArgs, whose layout the kernels' register counts depend on.  include/bbocr.h mirrors the ids (BBOCR_ROUTE_*)
+// and the struct (bbocr_conv_route: the same ints in the same order, pinned by static_asserts in abi_ops.cpp).
+enum ConvRouteId : int {
+    CONV_ROUTE_NONE = 0,            // nothing launched (a refusal)
+    // conv_mfma_kernel, the register-staged generic kernel: <EL, 4, 1, 4, PITER> (64 couts per tile) / <EL, 2, 2, 8, PITER> (128)
+    CONV_ROUTE_GEN64_P4, CONV_ROUTE_GEN64_P8, CONV_ROUTE_GEN64_P16, CONV_ROUTE_GEN128_P4, CONV_ROUTE_GEN128_P8, CONV_ROUTE_GEN128_P16,
+    // conv3x3_dma_kernel, 64 couts per tile: conv1_1 fused in (FUSE1) / 1x1 behind the layer (EPI 1)
+    CONV_ROUTE_DMA64_FUSE1, CONV_ROUTE_DMA64_POSTW,
+    // conv3x3_resw_kernel: <EL, 1, true, 4, true> (64 couts, pooled) / <EL, 1, true> (one chunk) / <EL, 2, false> (two chunks)
+    CONV_ROUTE_RESW_POOL64, CONV_ROUTE_RESW_1CH, CONV_ROUTE_RESW_2CH,
+    // conv3x3_dma_kernel, 64 couts: 324-slot patch with two / four cout fragments per wave, 384 slots, 448 slots (NPB 7)
+    CONV_ROUTE_DMA64_324_NF2, CONV_ROUTE_DMA64_324, CONV_ROUTE_DMA64_384, CONV_ROUTE_DMA64_448,
+    // conv3x3_dma_kernel, 128 couts: 384 slots behind a 4-deep weight ring, 448 slots behind a 3-deep one
+    CONV_ROUTE_DMA128_384, CONV_ROUTE_DMA128_448,
+    // conv3x3_dma_kernel with KS = 2 (2x2, padding 0)
+    CONV_ROUTE_DMA2X2_64, CONV_ROUTE_DMA2X2_128,
+    // conv1x1_dma_kernel: by couts per tile without the up-sampling epilogue; with it (ADDUP, any tile width: see ConvRoute::wn)
+    CONV_ROUTE_DMA1X1_64, CONV_ROUTE_DMA1X1_128, CONV_ROUTE_DMA1X1_256, CONV_ROUTE_DMA1X1_ADDUP,
+    CONV_ROUTE_COUNT
+};
+struct ConvRoute {
+    int id;                                                     // ConvRouteId
+    int status;                                                 // hipError_t the launcher returned (0: launched, or would have been)
+    // template numbers of the terminal (0 where the family has none)
+    int el, wm, wn, mf;
+    int piter;                                                  // conv_mfma_kernel
+    int npb, ring, nps, fuse1, nf, epi, ks;                     // conv3x3_dma_kernel
+    int addup;                                                  // conv1x1_dma_kernel (its RING is `ring`)
+    int resw;                                                   // conv3x3_resw_kernel: 1 <1, true, 4, true>, 2 <1, true>, 3 <2, false>
+    // geometry the launchers settled
+    int OH, OW, TH, TW, PH, PW, NP, sub, stack, tiles_x, tiles_y, ntiles_n, nchunks, ntaps, lean;
+    int grid, threads;                                          // workgroups, threads per workgroup
+    int persistent;                                             // > 0: the grid is min(tiles, persistent * compute units); a dry run, which
+                                                                // asks no device, reports the tile count as `grid`
+    int lds_bytes;                                              // dynamic LDS of the launch
+    int tail, split_off;                                        // epilogue switches of ConvArgs that select no kernel but change what is stored
+};
+
 int conv_plan_bn(int Cout);   // cout tile (64/128/256) of the launch configuration used for a layer
 size_t conv_packed_elems(const ConvPlan& p);
 // w: fp32 [Cout][Cin][KH][KW] already BN-folded; out: bf16 bits, layout [ntile][chunk][tap][frag][lane][8]
 void pack_conv_weights(const ConvPlan& p, const float* w, uint16_t* out);
-hipError_t launch_conv(const ConvPlan& p, ConvArgs a, hipStream_t s);   // a.zero must be set (device zero page)
+// a.zero must be set (device zero page).  route: filled by the terminal the dispatch reaches (id CONV_ROUTE_NONE and the status when it
+// refuses the shape).  dry: walk the same dispatch and return at the terminal, before any HIP call -- the status is the one a launch would
+// give for a shape refusal; pointers of `a` and `p` are only tested for null then.
+hipError_t launch_conv(const ConvPlan& p, ConvArgs a, hipStream_t s, ConvRoute* route = nullptr, bool dry = false);
 // upconv4 of CRAFT fused: u4b = relu(conv3x3(relu(up(z) + W_s s1 + b_s)) + b): p1 = the 1x1 plan over s1 (128 -> 64), p3 = the 3x3 plan (64 -> 32).
 // a: in0 = s1 (in0_cs = 128), addup = z (up_cs = 64), N/H/W of the full-resolution image, out/out_cs/cout_store of u4b.  Returns
 // hipErrorNotSupported when the shapes are not the ones the kernel is built for (the caller then runs the two launches).

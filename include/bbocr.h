@@ -297,6 +297,53 @@ int bbocr_host_crop_plan(int H, int W, const int* hori, int n_hori, const double
 int bbocr_op_conv2d(bbocr_ctx* ctx, const uint16_t* dev_in, int N, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                     int KH, int KW, int pad, int dil, int relu_in, int relu_out, int out_f32, void* dev_out, int pool_mode, int pool_relu,
                     uint16_t* dev_pool_out);
+/* Which conv kernel a bbocr_op_conv2d call takes.  The library's launch code picks one of about thirty kernel instantiations from the
+ * layer's shape; the terminal it reaches writes this report (one id per terminal, its template numbers, the geometry it settled). */
+enum {
+    BBOCR_ROUTE_NONE = 0,    /* nothing launched: the shape was refused, `status` has the HIP error code */
+    /* conv_mfma_kernel, the register-staged generic kernel: 64 / 128 couts per tile, PITER 4 / 8 / 16 */
+    BBOCR_ROUTE_GEN64_P4, BBOCR_ROUTE_GEN64_P8, BBOCR_ROUTE_GEN64_P16, BBOCR_ROUTE_GEN128_P4, BBOCR_ROUTE_GEN128_P8, BBOCR_ROUTE_GEN128_P16,
+    /* conv3x3_dma_kernel, 64 couts: conv1_1 fused in / a 1x1 behind the layer (the networks' own launches only) */
+    BBOCR_ROUTE_DMA64_FUSE1, BBOCR_ROUTE_DMA64_POSTW,
+    /* conv3x3_resw_kernel (resident weights, persistent tile loop): 64 couts pooled / one input chunk / two */
+    BBOCR_ROUTE_RESW_POOL64, BBOCR_ROUTE_RESW_1CH, BBOCR_ROUTE_RESW_2CH,
+    /* conv3x3_dma_kernel, 64 couts: 324-slot patch with 2 / 4 cout fragments per wave, 384 slots, 448 slots */
+    BBOCR_ROUTE_DMA64_324_NF2, BBOCR_ROUTE_DMA64_324, BBOCR_ROUTE_DMA64_384, BBOCR_ROUTE_DMA64_448,
+    /* conv3x3_dma_kernel, 128 couts: 384 slots (4-deep weight ring), 448 slots (3-deep) */
+    BBOCR_ROUTE_DMA128_384, BBOCR_ROUTE_DMA128_448,
+    /* conv3x3_dma_kernel as the 2x2 / padding 0 conv */
+    BBOCR_ROUTE_DMA2X2_64, BBOCR_ROUTE_DMA2X2_128,
+    /* conv1x1_dma_kernel: 64 / 128 / 256 couts per tile; with the up-sampling epilogue (the networks' own launches only) */
+    BBOCR_ROUTE_DMA1X1_64, BBOCR_ROUTE_DMA1X1_128, BBOCR_ROUTE_DMA1X1_256, BBOCR_ROUTE_DMA1X1_ADDUP,
+    BBOCR_ROUTE_COUNT
+};
+typedef struct bbocr_conv_route {
+    int id;                  /* BBOCR_ROUTE_* */
+    int status;              /* HIP error code of the launch (0: launched, or -- dry run -- would have been) */
+    int el, wm, wn, mf;      /* template numbers of the kernel; 0 where its family has none: element type (0 bf16, 1 fp16), waves along pixels /
+                              * couts, 16-pixel fragments per wave */
+    int piter;               /* conv_mfma_kernel: 16-pixel patch pieces a wave stages per chunk */
+    int npb, ring, nps, fuse1, nf, epi, ks;   /* conv3x3_dma_kernel: 64-pixel patch blocks, weight ring depth, patch slots, conv1_1 fused, cout
+                                               * fragments per wave, epilogue, kernel size (conv1x1_dma_kernel: ring, ks = 1) */
+    int addup;               /* conv1x1_dma_kernel: the up-sampling epilogue */
+    int resw;                /* conv3x3_resw_kernel: 1 = 64 couts pooled, 2 = one chunk, 3 = two chunks */
+    int OH, OW, TH, TW, PH, PW, NP, sub, stack, tiles_x, tiles_y, ntiles_n, nchunks, ntaps, lean;   /* geometry: output, tile, patch, patch
+                              * slots, dilation phases (> 1: the sub-lattice route) and rows of one phase image, tile counts, 32-channel input
+                              * chunks, taps, epilogue of conv3x3_dma_kernel (0 shared, 1 plain lean, 3 pooled lean) */
+    int grid, threads;       /* workgroups, threads per workgroup */
+    int persistent;          /* > 0: the launch caps the grid at persistent x compute units and loops over tiles; a dry run, which asks no
+                              * device, reports the tile count as grid */
+    int lds_bytes;           /* dynamic LDS */
+    int tail, split_off;     /* epilogue switches that select no kernel (the networks' own launches only) */
+} bbocr_conv_route;
+/* pure host, no context, usable without a GPU: the route bbocr_op_conv2d would take for these arguments on a context of element type el
+ * (0 bf16, 1 fp16), from a dry run of the launch code itself (the same dispatch, returning before the first HIP call).  store_full: with
+ * pool_mode, whether dev_out is given too.  BBOCR_ERR_HIP with out->id = BBOCR_ROUTE_NONE and out->status set: the shape is refused, as
+ * bbocr_op_conv2d would refuse it. */
+int bbocr_host_conv_route(int el, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int dil, int relu_in, int relu_out,
+                          int out_f32, int pool_mode, int pool_relu, int store_full, bbocr_conv_route* out);
+/* the route the last bbocr_op_conv2d call on this context launched, recorded by the launch itself (id BBOCR_ROUTE_NONE: none yet, or refused) */
+int bbocr_op_conv2d_route(bbocr_ctx* ctx, bbocr_conv_route* out);
 /* recogniser network only: crops [n,64,imgW] (device, 16-bit elements of the context's RECOGNISER type: bf16 (BF16) / fp16 (FP16, MIXED) values already
  * normalised to [-1, 1]; BBOCR_PREC_EXACT: CODES, 0 = padding zero, 1 + grey level otherwise, from which the first layer rebuilds the
  * fp32 input ((g/255 - 0.5)/0.5) exactly) -> logits fp32 [n,T,112] (device), T = imgW/4-1 */

@@ -7,7 +7,8 @@ Per shape two checks that share one input:
        selected (tap, 8-channel group) pairs cycle with o through ALL ntaps x Cin / 8 of them (a second launch where Cout is smaller).
   (ii) random weights against torch's fp64 convolution of the same bf16-rounded operands, tolerance of tests/test_gpu_ops.py.
 
-Routing by launch_conv (bf16: first template argument 0), confirmed from one kernel trace of this file:
+Routing by launch_conv (bf16: first template argument 0), asserted per launch through the route the launch records (ROUTES below,
+bbocr_op_conv2d_route):
   trunk_tile            3x3 64 -> 128, N 2, 19 x 37       conv3x3_dma_kernel<0, 2, 2, 8, 7, 3, 448>    4 x 64 tiles (6 x 66 patch: NPB = 7, 14 blocks per
                                                                                                 plane), partial tiles on both axes, two chunks
   three_chunks_relu_in  3x3 96 -> 128, 16 x 16, relu_in   conv3x3_dma_kernel<0, 2, 2, 8, 6, 4, 384>    16 x 16 tile, in-place ReLU pass over the patch
@@ -44,6 +45,19 @@ CASES = {
 }
 
 
+# the docstring's routing table as bbocr_conv_route fields: what every launch of a case must record
+ROUTES = {
+    "trunk_tile": dict(id="DMA128_448", wm=2, wn=2, mf=8, npb=7, ring=3, nps=448, TH=4, TW=64, PH=6, PW=66, nchunks=2),
+    "three_chunks_relu_in": dict(id="DMA128_384", wm=2, wn=2, mf=8, npb=6, ring=4, nps=384, TH=16, TW=16, nchunks=3),
+    "cout64_pool": dict(id="DMA64_384", wm=4, wn=1, mf=4, npb=6, ring=3, nps=384, TH=8, TW=32, PH=10, PW=34),
+    "cout64_nps324_pool": dict(id="DMA64_324", wm=4, wn=1, mf=4, npb=6, ring=3, nps=324, nf=4, TH=16, TW=16),
+    "dilated": dict(id="DMA128_384", wm=2, wn=2, mf=8, npb=6, ring=4, nps=384, sub=6, stack=3),
+    "ks2": dict(id="DMA2X2_128", wm=2, wn=2, mf=8, npb=6, ring=4, nps=384, fuse1=0, nf=4, epi=0, ks=2),
+    "1x1_4waves": dict(id="DMA1X1_64", wm=4, wn=1, mf=4, ring=3, addup=0, nchunks=5, tiles_x=3),
+    "1x1_256couts": dict(id="DMA1X1_128", wm=2, wn=2, mf=8, ring=3, addup=0, ntiles_n=2),
+}
+
+
 def _bf16(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
@@ -64,6 +78,17 @@ def _run(reader, xd, shape, w, b, relu_in, pool_mode):
                                      C.c_void_p(out.data_ptr()) if pool_mode else None)
     reader._check(rc)
     return out.float().cpu()
+
+
+def _assert_route(reader, name):
+    from bb_ocr_amd import _lib
+
+    r = _lib.bbocr_conv_route()
+    reader._check(reader._lib.bbocr_op_conv2d_route(reader._h, C.byref(r)))
+    got = r.as_dict()
+    assert got["el"] == 0 and got["status"] == 0
+    diff = {k: (v, got[k]) for k, v in ROUTES[name].items() if got[k] != v}
+    assert not diff, f"{name}: the launch took another kernel than the table says (expected, recorded): {diff}"
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -95,6 +120,7 @@ def test_gather_layout(reader, name):
         if pool_mode:
             want = F.max_pool2d(want.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
         got = _run(reader, xd, shape, w, None, relu_in, pool_mode)
+        _assert_route(reader, name)
         assert got.shape == want.shape
         bad = (got != want) & ~((got == 0) & (want == 0))         # -0.0 == 0.0; NaN (unwritten) != anything
         assert not bad.any(), f"{name}: {int(bad.sum())} of {bad.numel()} selected values differ, first at {tuple(bad.nonzero()[0].tolist())}"
@@ -109,6 +135,7 @@ def test_gather_layout(reader, name):
         ref = F.max_pool2d(ref, 2)
     ref = ref.permute(0, 2, 3, 1).float()
     got = _run(reader, xd, shape, w, b, relu_in, pool_mode)
+    _assert_route(reader, name)
     assert torch.isfinite(got).all()
     tol = 6e-3 * max(scale, 1.0)             # fp32 accumulate; bf16 output rounding 2^-8 relative (tests/test_gpu_ops.py)
     err = (got - ref).abs().max().item()

@@ -45,7 +45,7 @@ def _conv(reader, dtype, N, H, W, Cin, Cout, K, pad, dil, relu_in, relu_out, out
     (1, 24, 40, 64, 128, 3, 1, 1, 1, 0, 0, 0),     # BN=128, ReLU on load (integer max on fp16 bits)
     (1, 15, 20, 64, 256, 3, 6, 6, 0, 0, 0, 0),     # dilation 6 (fc6 phases)
     (2, 12, 20, 96, 256, 1, 0, 1, 0, 1, 0, 0),     # 1x1 DMA kernel
-    (1, 4, 70, 64, 256, 2, 0, 1, 0, 1, 0, 0),      # 2x2 valid: register-staged generic kernel
+    (1, 4, 70, 64, 256, 2, 0, 1, 0, 1, 0, 0),      # 2x2 valid: the LDS-DMA kernel with KS = 2 (route DMA2X2_128; the generic kernel's rows: tests/conv_route_cases.py)
     (1, 5, 40, 256, 97, 1, 0, 1, 0, 0, 1, 0),      # fp32 out
     (3, 40, 52, 512, 512, 3, 1, 1, 0, 1, 0, 0),    # long K loop
     (2, 32, 48, 64, 64, 3, 1, 1, 0, 1, 0, 1),      # fused 2x2 pool
