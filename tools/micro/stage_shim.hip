@@ -2,6 +2,7 @@
 // with the production plans and packed side tables of a live context, so that each fused launch can be compared with an fp64 reference of its own operation (tests/stage_ref.py).
 // stage_rec_features runs any range of the stages of the recogniser's conv stack (crnn_features_stages, the function a recognition pass runs).
 // stage_crops_wide runs the crop stage of a recognition pass into the wide layout (rec_launch_crops, the call rec_launch_part makes).
+// stage_ctc_greedy runs the greedy CTC stage over a ragged sequence table (launch_ctc, the call rec_finish makes) into caller-owned tensors.
 // No kernels of its own.  Built by the test as a shared object against the in-tree library:
 //   hipcc -O2 -std=c++20 -shared -fPIC --offload-arch=gfx950 -Ibb-ocr_amd/csrc -Iinclude tools/micro/stage_shim.hip -Lbb-ocr_amd -lbbocr -o stage_shim.so
 // Every function takes the bbocr_ctx* of a Reader, device pointers of caller-owned tensors with their element counts (checked against the
@@ -444,6 +445,37 @@ int stage_crops_wide(bbocr_ctx* c, const uint8_t* gray, size_t gray_elems, int H
         rec_launch_crops(c, g, p.part, dd, wide, 2);
         return hipSuccess;
     });
+}
+
+// The greedy CTC stage as a recognition pass launches it (rec_finish): the ragged table seqs_host = nseq x {first row, T} goes into the
+// context's seq_tables, then ONE launch_ctc over logits fp32 [rows, cs] (C classes per row) on c->stream.  Everything it writes is the caller's:
+// idx / pmax / out_idx [rows], ctc_out int32 [>= 4 * nseq] (CtcOut = {len, cnt, prod, pad} per sequence), probs [rows, cs] or null (the
+// greedy route keeps no probabilities).  mask4: the 4 x 32-bit class mask or null.  T = 0 is a sequence; one that leaves [0, rows) is refused
+// before anything is queued.  C > 128 is launch_ctc's own refusal (hipErrorInvalidValue, nothing launched).
+int stage_ctc_greedy(bbocr_ctx* c, const float* logits, size_t logits_elems, int rows, int C, int cs, const int* seqs_host, int nseq,
+                     const unsigned int* mask4, int* idx, size_t idx_elems, float* pmax, size_t pmax_elems, int* out_idx, size_t out_idx_elems, int* ctc_out,
+                     size_t ctc_out_elems, float* probs, size_t probs_elems) {
+    g_err.clear();
+    NEED(c && logits && seqs_host && idx && pmax && out_idx && ctc_out && rows > 0 && rows < (1 << 24) && nseq > 0 && nseq < (1 << 20) && C > 0 && C <= cs && cs <= 4096);
+    NEED(logits_elems == (size_t)rows * cs && idx_elems == (size_t)rows && pmax_elems == (size_t)rows && out_idx_elems == (size_t)rows);
+    NEED(ctc_out_elems >= (size_t)nseq * (sizeof(CtcOut) / 4) && (probs ? probs_elems == (size_t)rows * cs : probs_elems == 0));
+    for (int i = 0; i < nseq; ++i) {
+        const long long first = seqs_host[2 * i], T = seqs_host[2 * i + 1];
+        NEED(first >= 0 && T >= 0 && first + T <= rows);
+    }
+    return run_stage(c, [&] {
+        c->seq_tables.ensure((size_t)nseq * 8);
+        int* seqs_dev = (int*)c->seq_tables.p;
+        HIPCHK(hipMemcpyAsync(seqs_dev, seqs_host, (size_t)nseq * 8, hipMemcpyHostToDevice, c->stream));     // run_stage waits for the stream
+        return launch_ctc(logits, (size_t)rows, C, cs, seqs_dev, nseq, idx, pmax, out_idx, (CtcOut*)ctc_out, c->stream, mask4, probs);
+    });
+}
+
+// the confidence a recognition pass derives from one CtcOut (ctc_decode: the host pow)
+double stage_ctc_decode(int len, int cnt, float prod) {
+    const CtcOut o{len, cnt, prod, 0};
+    std::vector<int> text;
+    return ctc_decode(o, nullptr, 0, text);
 }
 
 }  // extern "C"
