@@ -89,7 +89,18 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
-#define HIP_TRY(expr)                                                                      \
+// LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4: lane l's 16 bytes land at lds + 16 l), issued as inline assembly.  The builtin
+// (__builtin_amdgcn_global_load_lds) is modelled by hipcc's waitcnt pass as a FLAT access that touches LDS: while one is outstanding -- in
+// these kernels always, their vmcnt waits are counted, never 0 -- every LDS dependency is waited for with a full `s_waitcnt lgkmcnt(0)`,
+// so ds_reads issued ahead of their use could never stay in flight across an MFMA group.  Behind the asm the compiler tracks only the
+// ds_reads (counted lgkmcnt); ordering against the DMA'd bytes is what the kernels' explicit `s_waitcnt vmcnt(N)` + s_barrier do anyway.
+// `lds` must be wave-uniform.  M0 is written here and by nothing else in these kernels (conv_mfma.hip, seq_proj.hip).
+__device__ __forceinline__ void lds_dma16(const void* gptr, const void* lds) {
+    const unsigned la = (unsigned)(size_t)(const __attribute__((address_space(3))) void*)lds;
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr), "s"(la) : "memory");
+}
+
+#define HIP_TRY(expr)                                                                     \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \
         if (_e != hipSuccess) {                                                            \

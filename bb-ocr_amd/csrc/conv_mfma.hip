@@ -19,17 +19,6 @@
 #include <type_traits>
 #include <utility>
 
-// LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4: lane l's 16 bytes land at lds + 16 l), issued as inline assembly.  The builtin
-// (__builtin_amdgcn_global_load_lds) is modelled by hipcc's waitcnt pass as a FLAT access that touches LDS: while one is outstanding -- in
-// these kernels always, their vmcnt waits are counted, never 0 -- every LDS dependency is waited for with a full `s_waitcnt lgkmcnt(0)`,
-// so ds_reads issued ahead of their use could never stay in flight across an MFMA group.  Behind the asm the compiler tracks only the
-// ds_reads (counted lgkmcnt); ordering against the DMA'd bytes is what the kernels' explicit `s_waitcnt vmcnt(N)` + s_barrier do anyway.
-// `lds` must be wave-uniform.  M0 is written here and by nothing else in these kernels.
-__device__ __forceinline__ void lds_dma16(const void* gptr, const void* lds) {
-    const unsigned la = (unsigned)(size_t)(const __attribute__((address_space(3))) void*)lds;
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr), "s"(la) : "memory");
-}
-
 // ---- shared epilogue: bias (+ReLU) (+fused max-pool).  Lane (pixel pl, group g) holds, per 16-pixel fragment, 16 outputs
 // acc[j][r]; the cout permutation of pack_conv_weights maps them to cout = tile + wn*64 + (j>>1)*32 + g*8 + (j&1)*4 + r:
 // TWO runs of 8 contiguous couts, 32 apart, so that one store instruction writes, for every pixel, 64 contiguous bytes

@@ -383,6 +383,7 @@ void load_crnn(bbocr_ctx* c, const TensorMap& tm);
 ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1 = nullptr, const Act* addup = nullptr);
 hipError_t launch_conv_profiled(bbocr_ctx* c, const ConvPlan& p, ConvArgs a, bool may_decline = false);   // may_decline: hipErrorNotSupported is returned, not thrown
 void run_conv(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, void* out, int out_cs, int cout_store, bool out_f32, const Act* addup = nullptr);
+hipError_t launch_seq_proj_profiled(bbocr_ctx* c, const ConvPlan& p, const uint16_t* x, size_t rows_pad, uint16_t* out);   // hipErrorNotSupported is returned, not thrown
 void prof_collect(bbocr_ctx* c);
 Act conv_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, int store);
 Act conv_pool_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, bool relu_out, int store, int mode, bool pool_relu, Act* full, const RgbSource* rgb = nullptr);
@@ -437,6 +438,7 @@ Act crnn_features_stages(bbocr_ctx* c, const RecPart& part, const CropDesc* desc
 void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs);
 void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_dev, int ntiles, const int* seqs_dev, int nseq, float* logits);
 void crnn_seq_xproj(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp);         // crnn_sequence's three GEMMs
+void crnn_seq_xproj_conv(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp);    // xproj through run_conv (exact mode; declined shapes)
 void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint16_t* out);
 void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logits);
 void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);    // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}

@@ -36,6 +36,14 @@ hipError_t launch_conv_profiled(bbocr_ctx* c, const ConvPlan& p, ConvArgs a, boo
     return hipSuccess;
 }
 
+// launch_seq_proj booked like the conv launch it stands in for; hipErrorNotSupported (a plan or shape it declines) is returned, not thrown
+hipError_t launch_seq_proj_profiled(bbocr_ctx* c, const ConvPlan& p, const uint16_t* x, size_t rows_pad, uint16_t* out) {
+    const double flops = 2.0 * (double)rows_pad * (double)p.Cout * p.Cin;
+    const hipError_t e = profiled(c, flops, [&] { return launch_seq_proj(p, x, rows_pad, out, c->cur); });
+    if (e != hipErrorNotSupported) HIPCHK(e);
+    return e;
+}
+
 // ConvArgs of a launch over a0 (a1: a second source behind it, virtual channel concat; addup: the half-resolution tensor whose 2x
 // up-sampling the epilogue adds): sources and image shape.  The caller adds the output and the epilogue switches.
 // Split-fp16 plans (ConvPlan::split, exact recogniser mode): the activation `a0` is a pair tensor [hi | lo] whose Act::C counts BOTH

@@ -215,6 +215,12 @@ void pack_lstm_whh8(const float* whh_fwd, const float* whh_bwd, uint16_t* out, i
 size_t lstm_whh_split_packed_elems();
 float pack_lstm_whh_split(const float* whh_fwd, const float* whh_bwd, uint16_t* out);   // -> acc_scale (2^-s)
 int lstm8_xproj_channel(int dir, int gate, int unit);
+// BiLSTM input projection of the 16-bit modes (seq_proj.hip): x [rows_pad, 256] -> out [rows_pad, 2048], weights resident in registers, rows
+// streamed; bit-identical to launch_conv on the same plan.  p: c->xproj[l] (reads the packed image and bias as they are).  rows_pad: a
+// multiple of 256.  hipErrorNotSupported for any other plan or shape: the caller runs the conv route.
+struct SeqProjPlan { int grid, chunks, ring; long long nslots, chunk_slots; };   // workgroups, row chunks (grid / 4), slots of the LDS ring, 64-row slots in all / per chunk
+SeqProjPlan seq_proj_plan(size_t rows_pad, int ncu);                        // chunk i covers slots [i * chunk_slots, min(nslots, (i + 1) * chunk_slots))
+hipError_t launch_seq_proj(const ConvPlan& p, const uint16_t* x, size_t rows_pad, uint16_t* out, hipStream_t s);
 // ---- rec_quant (quant.hip): the sequence half in torch's dynamic int8 arithmetic, per crop.  seqs_dev: int2 {first row, T} per crop (the CTC
 // stage's table).  launch_q8_quantize: parameter + coding pass over x (src_pair 0: fp32 [rows, K]; 1: the exact mode's fp16 pair [rows, K | K]) ->
 // rowp float4 [rows_pad] {scale, 1 / scale, zero point, 0}, a8 int8 [rows_pad, K] = code - zero point (rows past `rows` cleared), optionally the

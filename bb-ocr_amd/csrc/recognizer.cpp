@@ -187,8 +187,17 @@ void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_
 // Exact mode: x and h are [hi | lo] pairs and the plans are split-fp16 plans; the input projection and the logits leave as fp32.
 static Act seq_rows(const bbocr_ctx* c, const uint16_t* p, size_t rows_pad, int C) { return Act{(uint16_t*)p, 1, (int)(rows_pad / 256), 256, C * rec_mul(c)}; }
 // x [rows_pad, 256] -> the LSTM's input projection [rows_pad, 2048] in lstm8_xproj_channel's order (fp32 in the exact mode)
-void crnn_seq_xproj(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp) {
+// as a 1x1 conv (conv1x1_dma_kernel's 256 x 256 tiles): the exact mode's path, and the path of any shape launch_seq_proj declines
+void crnn_seq_xproj_conv(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp) {
     run_conv(c, c->xproj[l], seq_rows(c, x, rows_pad, 256), false, nullptr, false, false, xp, 2048, 2048, rec_split(c));
+}
+// the 16-bit modes stream the rows past register-resident weights (seq_proj.hip); the values are crnn_seq_xproj_conv's bit for bit
+void crnn_seq_xproj(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, void* xp) {
+    if (!rec_split(c)) {
+        if (c->arena.dry) return;
+        if (launch_seq_proj_profiled(c, c->xproj[l], x, rows_pad, (uint16_t*)xp) == hipSuccess) return;
+    }
+    crnn_seq_xproj_conv(c, l, x, rows_pad, xp);
 }
 // h [rows_pad, 512] (exact: the LSTM's pair, lo half unscaled) -> [rows_pad, 256]
 void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint16_t* out) {
