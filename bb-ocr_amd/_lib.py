@@ -21,6 +21,7 @@ class bbocr_config(C.Structure):
 PRECISIONS = {"bf16": 0, "fp16": 1, "exact": 2, "mixed": 3, "exact_rec": 4}
 BEAM_DEVICE_MAX = 32                                                             # bbocr.h BBOCR_BEAM_DEVICE_MAX
 PAGE_GRAY, PAGE_BGR, PAGE_RGB, PAGE_YCBCR4, PAGE_YCBCR3 = 0, 1, 2, 3, 4          # bbocr.h BBOCR_PAGE_*: layouts of a device page
+PNG_CHUNK = 16384                                                                # bbocr.h BBOCR_PNG_CHUNK
 PAGE_PX_BYTES = {PAGE_GRAY: 1, PAGE_BGR: 3, PAGE_RGB: 3, PAGE_YCBCR4: 4, PAGE_YCBCR3: 3}    # bytes per pixel (csrc/kernels.h page_px_bytes)
 
 
@@ -205,6 +206,11 @@ PROTOTYPES = {
                                     C.POINTER(C.c_size_t)]),
     "bbocr_op_jpeg_encode_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t,
                                              C.POINTER(C.c_size_t)]),
+    "bbocr_png_encode_bound": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    "bbocr_png_encode": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bbocr_op_deflate": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bbocr_op_png_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_size_t, _vp, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
 }
 
 _lib = None

@@ -87,7 +87,7 @@ void slot_destroy(bbocr_ctx* c) {
     DevBuf* bufs[] = {&c->arena.buf, &c->heat, &c->gray, &c->resized, &c->ccl_label, &c->ccl_stat, &c->ccl_slot, &c->ccl_comps, &c->ccl_rowext,
                       &c->ccl_counters, &c->crop_desc, &c->crop_desc2, &c->crop_scratch, &c->crop_hscratch, &c->crop_wscratch, &c->crop_luts, &c->crop_hist,
                       &c->ctc_idx, &c->ctc_pmax, &c->ctc_out_idx, &c->ctc_out, &c->seq_v, &c->seq_xp, &c->seq_h, &c->seq_lin, &c->seq_logits,
-                      &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out,
+                      &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out, &c->pe_out,
                       &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp};
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);

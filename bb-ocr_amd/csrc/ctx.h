@@ -200,6 +200,7 @@ struct bbocr_ctx : WeightView {
     int th_coef_ks[2] = {0, 0};
     int th_coef_rows[2] = {0, 0};
     DevBuf je_scan, je_out;                    // model-input JPEG encoder (jpegenc.cpp): the unstuffed scan + stuffing counters, the stuffed scan
+    DevBuf pe_out;                             // device PNG writer (pngenc.cpp): the compacted deflate blocks
     DevBuf pp_cubic;                           // cubic-resize weight tables, kept on the device while (W, dw, H, dh) repeats
     int pp_cubic_key[4] = {0, 0, 0, 0};
     unsigned long long pp_cubic_K[2] = {0, 0};

@@ -385,6 +385,31 @@ hipError_t launch_je_pack(const short* coef, int n, int components, const unsign
 hipError_t launch_je_ff_count(const uint8_t* scan, long long bytes, unsigned long long* tile_ff, hipStream_t s);       // [tiles + 1]
 hipError_t launch_je_stuff(const uint8_t* scan, long long bytes, const unsigned long long* tile_off, uint8_t* out, hipStream_t s);
 
+// ------------------------------------------------------------------ lossless PNG writer (pngenc.hip): filters, run matches, dynamic Huffman per chunk
+// Passes: adaptive filter per row -> per chunk of PNG_CHUNK stream bytes: tokens, histogram, code lengths, block size, Adler-32 sums
+// -> scan of the chunk sizes (launch_je_scan) -> per chunk: bit packing in LDS, written at the chunk's place in the compacted buffer.
+// tests/png_ref.py states every rule; the device is held to it byte for byte.
+constexpr int PNG_CHUNK = 16384;                               // BBOCR_PNG_CHUNK: stream bytes per deflate block; no match leaves its chunk
+constexpr int PNG_LITLEN = 286, PNG_CL = 19;                   // literal/length symbols, code-length symbols (RFC 1951)
+constexpr int PNG_HIST_ROW = 288;                              // uint32 per chunk: 286 symbol counts, the match count, the token count
+constexpr int PNG_REC = 320;                                   // bytes per chunk record, see PngRec
+constexpr int PNG_STORED = 0, PNG_DYNAMIC = 1;
+constexpr int PNG_LIMIT15 = 1, PNG_LIMIT7 = 2;                 // PngRec::flags: a code was deeper than its limit before the limiter ran
+struct PngRec {                                                // what the packing pass reads of a chunk (bbocr_op_png_stage stage 2)
+    uint8_t kind, flags;
+    uint8_t litlen[PNG_LITLEN];                                // code lengths, 0 = unused
+    uint8_t dist;                                              // length of distance symbol 0: 1 when the chunk has matches, else 0
+    uint8_t cl[PNG_CL];                                        // lengths of the code-length code, in symbol order
+    uint8_t pad[PNG_REC - 2 - PNG_LITLEN - 1 - PNG_CL];
+};
+static_assert(sizeof(PngRec) == PNG_REC, "PngRec layout");
+// the filtered stream of a page: per row [filter byte][W * c bytes], c = 1 (gray) or 3 (RGB order; a BGR page is swapped on read)
+hipError_t launch_png_filter(const uint8_t* src, size_t pitch, int layout, int H, int W, uint8_t* stream, hipStream_t s);
+// hist [chunks][PNG_HIST_ROW], rec [chunks], size [chunks + 1] (bytes of each chunk's block; the scan turns them into offsets), adler [chunks][2]
+hipError_t launch_png_codes(const uint8_t* stream, size_t n, int chunks, uint32_t* hist, PngRec* rec, unsigned long long* size, uint32_t* adler,
+                            hipStream_t s);
+hipError_t launch_png_pack(const uint8_t* stream, size_t n, int chunks, const PngRec* rec, const unsigned long long* off, uint8_t* out, hipStream_t s);
+
 // ------------------------------------------------------------------ EXIF orientation + colour order of a page (orient.hip): cv2.imread's last step
 constexpr int ORIENT_TILE = 64;                                // pixels per tile edge (bb_ocr_amd.preprocess.ORIENT_TILE: the tests' shapes)
 bool page_orient_pair_ok(int layout, int dst_layout);          // BGR / RGB from every PAGE_* layout, GRAY from GRAY

@@ -610,7 +610,8 @@ def encode_images_for_model(reader, image_paths, use_preprocessing=False, edge_c
 TRACE_KEYS = {"preprocess": "preprocessed_b64", "edge_crop": "edge_cropped_b64", "auto_crop": "auto_cropped_b64"}
 
 
-def trace_previews(reader, image_paths, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_decode=True):
+def trace_previews(reader, image_paths, use_preprocessing=False, edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_decode=True,
+                   png=None):
     """The preview strings ``extract_text_with_ocr`` puts into an image's trace (``capture_trace=True``, :421-476), one dict per image,
     string for string: ``original_b64`` -- ``_image_to_data_url`` of the file itself (``Image.open`` does not transpose; an unloaded JPEG
     is decoded at the draft scale) -- and, where the step changed the page, ``preprocessed_b64``, ``edge_cropped_b64`` and
@@ -620,29 +621,32 @@ def trace_previews(reader, image_paths, use_preprocessing=False, edge_crop_perce
     ``"chroma"``: 4:4:4, 4:2:2 and 4:4:0 files as well -- are decoded on the card; everything else takes ``preprocess.preview_host``.  A
     file the decoder takes is read once and, with a crop setting on, decoded ONCE (``Reader.decode_jpeg_scales_batch``): one run of the
     entropy stages yields the decode at the draft scale for the original's preview and ``cv2.imread``'s full-scale page the crop chain
-    starts from; when the draft scale is 1 the two are one decode, oriented on the card."""
-    from .preprocess import preview_device
+    starts from; when the draft scale is 1 the two are one decode, oriented on the card.  ``png="device"`` (opt-in; default
+    ``preprocess.png_writer()``): the PNG files of the previews made on the card are written there too (``Reader.encode_png``) -- the strings
+    are then not the reference's, but each decodes to the same image (mode, size, pixels, ICC profile)."""
+    from .preprocess import png_writer, preview_device
     from .reader import _file_bytes
 
     if crop_margin < 0:
         raise ValueError("crop_margin must be >= 0")
     chain = use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr
+    png = png_writer(png)
     out = []
     for path in image_paths:
         source = _file_bytes(path) if device_decode else path             # read once
-        once = _trace_decode_once(reader, source, device_decode) if device_decode and chain else None
-        trace = {"original_b64": once[0] if once else preview_device(reader, source, device_decode=device_decode)}
+        once = _trace_decode_once(reader, source, device_decode, png) if device_decode and chain else None
+        trace = {"original_b64": once[0] if once else preview_device(reader, source, device_decode=device_decode, png=png)}
         if chain:
             pages = {}
             ocr_page_crop(reader, source, use_preprocessing, edge_crop_percent, crop_for_ocr, crop_margin, on_device=True,
                           device_decode=device_decode, pages=pages, page=once[1] if once else None)
             for step, page in pages.items():
-                trace[TRACE_KEYS[step]] = preview_device(reader, page)
+                trace[TRACE_KEYS[step]] = preview_device(reader, page, png=png)
         out.append(trace)
     return out
 
 
-def _trace_decode_once(reader, data, device_decode):
+def _trace_decode_once(reader, data, device_decode, png="pillow"):
     """Both uses of a traced file from one run of the entropy stages: ``(original_b64, cv2.imread's page on the card)``, or None for a
     file the device decoder does not take or whose entropy-coded data it reports damaged (the caller keeps its two-step path)."""
     import io
@@ -665,4 +669,4 @@ def _trace_decode_once(reader, data, device_decode):
     else:
         page = decodes[0][1]
     icc = Image.open(io.BytesIO(data)).info.get("icc_profile")              # headers only
-    return _preview_string(_preview_of_decode(reader, drafted, plan, s, PREVIEW_MAX_DIM), icc), page
+    return _preview_string(_preview_of_decode(reader, drafted, plan, s, PREVIEW_MAX_DIM), icc, reader, png), page

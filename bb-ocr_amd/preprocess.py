@@ -348,10 +348,30 @@ def _preview_jpeg_device(reader, data, plan, max_dim):
     return _preview_of_decode(reader, page, plan, s, max_dim)
 
 
-def _preview_string(px, icc):
-    """the preview of the pixels made on the card (a device tensor): Pillow writes the PNG, the file's ICC profile embedded"""
+PNG_PILLOW, PNG_DEVICE = "pillow", "device"               # who writes a preview's PNG file (the `png` argument)
+
+
+def png_writer(png=None):
+    """The ``png`` argument of the preview functions resolved: ``"pillow"`` (the reference's strings) or ``"device"`` (``Reader.encode_png``:
+    other strings that decode to the same image).  None: ``"device"`` when the environment has ``BBOCR_PNG_DEVICE=1``, else ``"pillow"``."""
+    if png is None:
+        return PNG_DEVICE if os.environ.get("BBOCR_PNG_DEVICE") == "1" else PNG_PILLOW
+    if png not in (PNG_PILLOW, PNG_DEVICE):
+        raise ValueError(f"png must be {PNG_PILLOW!r} or {PNG_DEVICE!r}, not {png!r}")
+    return png
+
+
+def _preview_string(px, icc, reader=None, png=PNG_PILLOW):
+    """the preview of the pixels made on the card (a device tensor, gray [h,w] or RGB [h,w,3]), the file's ICC profile embedded:
+    ``png="pillow"`` -- the pixels come back and Pillow writes the PNG; ``"device"`` -- ``reader.encode_png`` writes it on the card and only
+    the file comes back (lossless, same mode / size / pixels / profile when decoded, but not Pillow's bytes)"""
     from PIL import Image
 
+    if png == PNG_DEVICE:
+        import base64
+
+        data = reader.encode_png(px, PAGE_GRAY if px.ndim == 2 else PAGE_RGB, icc)
+        return "data:image/png;base64," + base64.b64encode(data).decode("utf-8")
     img = Image.fromarray(px.cpu().numpy())
     if icc:
         img.info["icc_profile"] = icc
@@ -361,10 +381,13 @@ def _preview_string(px, icc):
 PREVIEW_JPEG, PREVIEW_PAGE, PREVIEW_HOST = "device-jpeg", "device-page", "host"     # preview_device's routes (info["route"])
 
 
-def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, info=None):
+def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, info=None, png=None):
     """``preview_host(source, max_dim)``, character for character, with the pixels made on the card; only the page of at most ``max_dim``
     pixels comes back, and Pillow writes the PNG from it.  ``info``: a dict that receives the route taken as ``info["route"]`` (the
-    strings are equal whichever it is):
+    strings are equal whichever it is).  ``png="device"`` (opt-in; default ``png_writer()``: ``"pillow"`` unless ``BBOCR_PNG_DEVICE=1``):
+    on the two device routes the PNG file is written on the card as well (``Reader.encode_png``) and the pixels never come back.  The string
+    is then NOT the reference's: the file is lossless and decodes to the same image -- mode, size, pixels, ``info["icc_profile"]`` -- but
+    its bytes are not Pillow's.  The ``"host"`` route keeps Pillow either way.
 
     * ``"device-jpeg"`` -- a JPEG path or bytes the device decoder's plan supports (4:2:0 or grey baseline) and ``device_decode``: plan ->
       draft scale -> ``bbocr_jpeg_decode_scaled`` -> libjpeg's RGB -> ``bbocr_thumbnail_box``; the file's ICC profile is carried into the
@@ -378,6 +401,7 @@ def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, 
 
     from .reader import _file_bytes, jpeg_chroma, jpeg_plan
 
+    png = png_writer(png)
     px, icc, route = None, None, PREVIEW_HOST
     if hasattr(source, "is_cuda"):
         H, W, _, ch = _page_layout(reader, source)
@@ -396,7 +420,7 @@ def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, 
         info["route"] = route
     if px is None:
         return preview_host(source, max_dim)
-    return _preview_string(px, icc)
+    return _preview_string(px, icc, reader, png)
 
 
 def _read_page(image_path_or_array):

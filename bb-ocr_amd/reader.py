@@ -842,6 +842,49 @@ class Reader:
                                                 C.c_void_p(out.ctypes.data), cap, C.byref(n)))
         return out[:n.value].tobytes()
 
+    def encode_png(self, page_dev, layout=None, icc_profile=None):
+        """A uint8 device page -> the bytes of a lossless 8-bit PNG file of it, written on the card by ``bbocr_png_encode``
+        (csrc/pngenc.hip): adaptive filters, run matches, dynamic Huffman codes per 16 KiB chunk.  NOT the bytes Pillow writes: opened
+        with Pillow the file has the mode (``L`` / ``RGB``), size, pixels and ``info["icc_profile"]`` of Pillow's file.  ``page_dev``:
+        ``[H,W]`` or ``[H,W,3]`` rows of packed pixels of ``layout`` GRAY, RGB or BGR (default: GRAY for ``[H,W]``, RGB for ``[H,W,3]``); a
+        strided row pitch (a crop of a larger page) is read in place.  ``icc_profile``: bytes of an iCCP chunk.  ``ValueError`` for
+        anything else, 4-byte layouts included."""
+        from .preprocess import _page_layout
+
+        if layout is None:
+            layout = _lib.PAGE_GRAY if getattr(page_dev, "ndim", 0) == 2 else _lib.PAGE_RGB
+        if layout not in (_lib.PAGE_GRAY, _lib.PAGE_RGB, _lib.PAGE_BGR):
+            raise ValueError(f"a PNG file is written from a GRAY, RGB or BGR page, not layout {layout!r}")
+        H, W, pitch, _ = _page_layout(self, page_dev, (layout,))
+        icc = bytes(icc_profile) if icc_profile else b""
+        cap = int(self._lib.bbocr_png_encode_bound(H, W, _lib.PAGE_PX_BYTES[layout], len(icc)))
+        if cap == 0:
+            raise ValueError("the page or the profile is too large for a PNG file")
+        out = np.empty(cap, np.uint8)                                   # (untouched pages of it cost nothing)
+        n = C.c_size_t()
+        self._torch.cuda.current_stream(self.device_index).synchronize()      # the library runs on its own stream
+        self._check(self._lib.bbocr_png_encode(self._h, C.c_void_p(page_dev.data_ptr()), H, W, pitch, int(layout),
+                                               C.cast(C.c_char_p(icc), C.c_void_p) if icc else None, len(icc), C.c_void_p(out.ctypes.data), cap,
+                                               C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def deflate_device(self, bytes_dev):
+        """A contiguous 1-D uint8 device tensor -> the zlib stream ``bbocr_op_deflate`` makes of it (the PNG writer's chunks, run matches and
+        dynamic Huffman codes); ``zlib.decompress`` gives the bytes back."""
+        torch = self._torch
+        if not isinstance(bytes_dev, torch.Tensor) or bytes_dev.dtype != torch.uint8 or bytes_dev.ndim != 1 or not bytes_dev.is_contiguous():
+            raise ValueError("expected a contiguous 1-D uint8 device tensor")
+        if not bytes_dev.is_cuda or bytes_dev.device.index != self.device_index:
+            raise ValueError(f"expected a tensor on {self.device}")
+        nb = int(bytes_dev.numel())
+        cap = 2 + -(-nb // _lib.PNG_CHUNK) * 5 + nb + 6
+        out = np.empty(cap, np.uint8)
+        n = C.c_size_t()
+        torch.cuda.current_stream(self.device_index).synchronize()
+        self._check(self._lib.bbocr_op_deflate(self._h, C.c_void_p(bytes_dev.data_ptr()) if nb else None, nb, C.c_void_p(out.ctypes.data), cap,
+                                               C.byref(n)))
+        return out[:n.value].tobytes()
+
     @property
     def decode_option(self):
         """This Reader's ``device_decode`` as the functions of ``extractor_batch`` and ``preprocess`` take it: ``"chroma"``, True or False"""

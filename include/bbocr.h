@@ -673,6 +673,48 @@ int bbocr_jpeg_encode(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long
 int bbocr_op_jpeg_encode_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int layout, int components,
                                int quality, void* dev_dst, size_t dst_bytes, size_t* bytes);
 
+/* ---- the trace previews' PNG file (enhanced_extractor.py:184-199, _image_to_data_url's img.save(format="PNG")) written on the device
+ * (csrc/pngenc.hip): one u8 page in device memory -- BBOCR_PAGE_GRAY (colour type 0), BBOCR_PAGE_RGB or BBOCR_PAGE_BGR (colour type 2, BGR
+ * swapped on read), rows `pitch` bytes apart -- becomes an 8-bit, non-interlaced PNG file.  The file is LOSSLESS but NOT the bytes Pillow
+ * writes (zlib's serial match search cannot be reproduced faster on a GPU): opened with Pillow it has the mode (L or RGB), the size, the
+ * pixels and the info["icc_profile"] of the file Pillow would have written.  The call is opt-in everywhere; its bytes are reproducible from
+ * call to call and are defined by tests/png_ref.py:
+ *   filter   per row the PNG filter (None, Sub, Up, Average, Paeth) with the smallest sum of |(int8) x|, ties to the lowest number;
+ *   tokens   the filtered stream, H * (1 + W * channels) bytes, is cut into chunks of BBOCR_PNG_CHUNK bytes, each one deflate block of its
+ *            own; a maximal run of L equal bytes inside a chunk is its first byte as a literal, then while R >= 3 (R = L - 1 at first) a
+ *            match of min(R, 258) at distance 1, then the last 0 .. 2 bytes as literals;
+ *   codes    per chunk a dynamic block: length-limited Huffman codes (15 bits; 7 for the code-length code) that are a pure integer
+ *            function of the chunk's histogram, one distance code of length 1 when the chunk has matches;
+ *   emit     header + tokens + end of block + an empty stored block (000, pad, 00 00 FF FF), so that every chunk's output is whole
+ *            bytes; when that is not shorter than a stored block (5 + n bytes) the chunk is stored instead; no block is final;
+ *   file     signature, IHDR, iCCP when icc_bytes > 0 (name "ICC Profile", the profile in stored deflate blocks), ONE IDAT (78 01, the
+ *            chunks' blocks, the final empty block 03 00, Adler-32), IEND; CRC-32 and the framing on the host.
+ *
+ * bbocr_png_encode_bound: host only; a capacity that always suffices:
+ *     59 + (icc_bytes ? 31 + icc_bytes + 5 * ceil(icc_bytes / 65535) : 0) + ceil(stream / 16384) * 5 + stream + 2 + 4,
+ *     stream = H * (1 + W * channels)
+ * -- signature, IHDR, IDAT's and IEND's framing and the zlib header; the iCCP chunk; every chunk stored; the final block; Adler-32.  0 for
+ * H or W below 1, channels not 1 or 3, or a chunk whose payload would exceed 2^31 - 1 bytes.
+ * bbocr_png_encode: the complete file into host_out[capacity], *bytes = its length.  A pipeline call: runs in a call slot next to readtext
+ * calls, scratch from the slot, returns with its work finished.  BBOCR_ERR_ARG before anything is queued: a null pointer, a layout other
+ * than the three above, a pitch shorter than a row, a page for which the bound is 0, a capacity below the bound.
+ * bbocr_op_deflate: the tokens / codes / emit stages and the zlib framing (78 01 ... 03 00, Adler-32) of an arbitrary DEVICE byte stream
+ * of n <= 2^31 - 1 bytes, into host_out[capacity >= 2 + ceil(n / 16384) * 5 + n + 6]; zlib's inflate reads it back.
+ * bbocr_op_png_stage: intermediates in DEVICE memory dev_dst[dst_bytes] (parity tests), *bytes = what was written, by the functions the
+ * full call runs.  Stage 0 = the filtered stream of the page (dev_src, H, W, pitch, layout; n is ignored).  Stages 1 .. 3 take dev_src as
+ * a byte stream of n bytes (H, W, pitch, layout are ignored), chunks = ceil(n / 16384): 1 = uint32 [chunks][288], per chunk the counts of
+ * the 286 literal/length symbols (end of block: 1), then the match count, then the token count; 2 = uint8 [chunks][320], per chunk the
+ * block kind (0 stored, 1 dynamic), flags (bit 0: a literal/length code was deeper than 15 bits before the limiter, bit 1: a code-length
+ * code deeper than 7), the 286 literal/length code lengths, the distance code's length, the 19 lengths of the code-length code in symbol
+ * order, zeros; 3 = int64 [chunks + 1], the byte offsets of the chunks' blocks in the compacted buffer, then its length. */
+#define BBOCR_PNG_CHUNK 16384
+size_t bbocr_png_encode_bound(int H, int W, int channels, size_t icc_bytes);
+int bbocr_png_encode(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long long pitch, int layout, const uint8_t* icc, size_t icc_bytes,
+                     uint8_t* host_out, size_t capacity, size_t* bytes);
+int bbocr_op_deflate(bbocr_ctx* ctx, const uint8_t* dev_bytes, size_t n, uint8_t* host_out, size_t capacity, size_t* bytes);
+int bbocr_op_png_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int layout, size_t n, void* dev_dst,
+                       size_t dst_bytes, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif
