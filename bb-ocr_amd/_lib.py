@@ -51,6 +51,22 @@ class bbocr_jpeg_plan(C.Structure):
                 ("chroma", C.c_int)]                             # 1 = 4:4:4, 2 = 4:2:2, 3 = 4:4:0: decodable although `supported` is 0
 
 
+JPEG_MAX_SCANS = 64                                                              # bbocr.h BBOCR_JPEG_MAX_SCANS
+JPEG_NOT_JPEG, JPEG_SOF, JPEG_SCRIPT, JPEG_SCANS = 1, 4, 12, 13                   # bbocr.h BBOCR_JPEG_*: no SOI, "not SOF2", and the reasons the progressive plan adds
+
+
+class bbocr_jpeg_scan(C.Structure):
+    _fields_ = [("components", C.c_int), ("component", C.c_int * 3), ("dc_table", C.c_int * 3), ("ac_table", C.c_int * 3), ("ss", C.c_int),
+                ("se", C.c_int), ("ah", C.c_int), ("al", C.c_int), ("restart_interval", C.c_int), ("segments", C.c_int), ("offset", C.c_longlong),
+                ("bytes", C.c_longlong)]
+
+
+class bbocr_jpeg_progressive_plan(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("sampling", (C.c_int * 2) * 3), ("mcu_cols", C.c_int),
+                ("mcu_rows", C.c_int), ("chroma", C.c_int), ("orientation", C.c_int), ("supported", C.c_int), ("reason", C.c_int),
+                ("n_scans", C.c_int), ("reserved", C.c_int), ("scans", bbocr_jpeg_scan * JPEG_MAX_SCANS)]
+
+
 JPEG_FORM_YCBCR, JPEG_FORM_IMREAD = 0, 1                                         # bbocr.h BBOCR_JPEG_FORM_*
 JPEG_UP_NONE, JPEG_UP_H2V1_FANCY, JPEG_UP_H1V2_FANCY, JPEG_UP_H2V2_NOT_NEEDED, JPEG_UP_REPLICATE = range(5)    # bbocr.h BBOCR_JPEG_UP_*
 
@@ -196,6 +212,10 @@ PROTOTYPES = {
     "bbocr_jpeg_decode_scales": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(bbocr_jpeg_output), C.c_int,
                                            C.POINTER(C.c_int)]),
     "bbocr_jpeg_counters": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "bbocr_host_jpeg_progressive_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_jpeg_progressive_plan)]),
+    "bbocr_jpeg_decode_progressive": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(bbocr_jpeg_output),
+                                                C.c_int, C.POINTER(C.c_int)]),
+    "bbocr_op_jpeg_progressive_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
     "bbocr_host_jpeg_scaled_geometry": (C.c_int, [C.POINTER(bbocr_jpeg_plan), C.c_int, C.POINTER(bbocr_jpeg_scaled_comp)]),
     "bbocr_op_jpeg_scaled_class_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
     "bbocr_thumbnail_box": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp]),

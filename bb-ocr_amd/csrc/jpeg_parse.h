@@ -1,0 +1,384 @@
+// Host-side JPEG parsing that more than one program runs: what jpegdec.cpp's baseline walk and the progressive walk share (EXIF
+// orientation, Huffman table specs and their derived form, the removal of stuffing), and the whole host side of a progressive file --
+// bbocr_host_jpeg_progressive_plan's walk over the markers (prog_parse) and the tables of one scan as jpegprog.h's jp_decode_segment
+// reads them (prog_fill_scan).  No GPU call: tools/jpegprog_hostcheck.cpp builds it with the sanitisers.
+#pragma once
+#include "../../include/bbocr.h"
+#include <algorithm>
+#include <cstring>
+#include <utility>
+#include <vector>
+#include "jpegprog.h"
+
+namespace jpeg_host {
+
+constexpr unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct HuffSpec { bool have = false; unsigned char counts[16] = {0}; unsigned char vals[256] = {0}; int total = 0; };
+
+// EXIF orientation as cv2.imread applies it: the first APP1 segment that starts with "Exif\0\0" before SOS, a TIFF header of either byte
+// order, IFD0 only, tag 0x0112 as one SHORT or LONG of value 1 .. 8.  Anything else -- no such segment or tag, another type or count,
+// another value, an IFD that does not lie inside the segment -- is 1.  Every read is checked against the segment.
+inline int exif_orientation(const uint8_t* f, size_t n) {
+    size_t p = 2;
+    while (p + 4 <= n && f[p] == 0xFF) {
+        const int m = f[p + 1];
+        if (m == 0xFF) { ++p; continue; }
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) { p += 2; continue; }
+        if (m == 0xDA || m == 0xD9) break;
+        const size_t L = ((size_t)f[p + 2] << 8) | f[p + 3];
+        if (L < 2 || p + 2 + L > n) break;
+        const uint8_t* s = f + p + 4;
+        const size_t sl = L - 2;
+        p += 2 + L;
+        if (m != 0xE1 || sl < 6 || std::memcmp(s, "Exif\0\0", 6) != 0) continue;
+        const uint8_t* t = s + 6;
+        const size_t tl = sl - 6;
+        if (tl < 8) return 1;
+        const bool le = t[0] == 'I' && t[1] == 'I';
+        if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+        auto u16 = [&](size_t o) { return le ? (unsigned)t[o] | ((unsigned)t[o + 1] << 8) : ((unsigned)t[o] << 8) | (unsigned)t[o + 1]; };
+        auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
+        if (u16(2) != 42) return 1;
+        const size_t ifd = u32(4);
+        if (ifd > tl || tl - ifd < 2) return 1;
+        const size_t cnt = u16(ifd);
+        if ((tl - ifd - 2) / 12 < cnt) return 1;                  // the directory runs off the segment
+        for (size_t i = 0; i < cnt; ++i) {
+            const size_t e = ifd + 2 + 12 * i;
+            if (u16(e) != 0x0112) continue;
+            const unsigned type = u16(e + 2);
+            if ((type != 3 && type != 4) || u32(e + 4) != 1) return 1;
+            const unsigned v = type == 3 ? u16(e + 8) : u32(e + 8);
+            return v >= 1 && v <= 8 ? (int)v : 1;
+        }
+        return 1;
+    }
+    return 1;
+}
+
+// The chroma layouts beside 4:2:0 that the decoder takes: luma (1,1), (2,1) or (1,2) over chroma (1,1), (1,1).  0: any other sampling.
+inline int chroma_class_of(const int s[3][2]) {
+    if (s[1][0] != 1 || s[1][1] != 1 || s[2][0] != 1 || s[2][1] != 1) return 0;
+    const int h = s[0][0], v = s[0][1];
+    return h == 1 && v == 1 ? BBOCR_JPEG_CHROMA_444 : (h == 2 && v == 1 ? BBOCR_JPEG_CHROMA_422 : (h == 1 && v == 2 ? BBOCR_JPEG_CHROMA_440 : 0));
+}
+
+// jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
+inline bool derive_table(const HuffSpec& h, JpegHuff& t) {
+    std::memset(&t, 0, sizeof t);
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int cnt = h.counts[l - 1];
+        t.valoff[l] = k - code;
+        if (cnt) {
+            if (code + cnt > (1 << l)) return false;
+            for (int i = 0; i < cnt; ++i, ++k, ++code)
+                if (l <= 9)
+                    for (int e = 0; e < (1 << (9 - l)); ++e) t.look[(code << (9 - l)) + e] = (unsigned short)((l << 8) | h.vals[k]);
+            t.maxcode[l] = code - 1;
+        } else {
+            t.maxcode[l] = -1;
+        }
+        code <<= 1;
+    }
+    t.maxcode[0] = t.maxcode[17] = -1;
+    std::memcpy(t.val, h.vals, 256);
+    return true;
+}
+
+// one DHT segment's tables into huff[class][id], ids below max_id; false: malformed
+template <int IDS> bool read_dht(const uint8_t* s, size_t sl, HuffSpec (&huff)[2][IDS]) {
+    size_t q = 0;
+    while (q < sl) {
+        if (q + 17 > sl) return false;
+        const int tc = s[q] >> 4, th = s[q] & 15;
+        int tot = 0;
+        for (int i = 0; i < 16; ++i) tot += s[q + 1 + i];
+        if (tc > 1 || th >= IDS || tot > 256 || q + 17 + tot > sl) return false;
+        HuffSpec& h = huff[tc][th];
+        h.have = true;
+        h.total = tot;
+        std::memcpy(h.counts, s + q + 1, 16);
+        std::memset(h.vals, 0, 256);
+        std::memcpy(h.vals, s + q + 17, (size_t)tot);
+        q += 17 + (size_t)tot;
+    }
+    return true;
+}
+
+// the bytes [a, e) of a restart segment without their stuffing: every FF is kept, the 00 behind it dropped.  Returns the count.
+inline size_t unstuff(const uint8_t* a, const uint8_t* e, uint8_t* dst) {
+    size_t w = 0;
+    while (a < e) {                                                   // copy up to and including the next FF, drop the 00 behind it
+        const uint8_t* ff = (const uint8_t*)std::memchr(a, 0xFF, (size_t)(e - a));
+        const size_t len = ff ? (size_t)(ff - a) + 1 : (size_t)(e - a);
+        std::memcpy(dst + w, a, len);
+        w += len;
+        a += len;
+        if (ff && a < e && *a == 0x00) ++a;
+    }
+    return w;
+}
+
+// The entropy-coded data that starts at `from`: its restart segments' byte ranges (want_segs) and their number, up to the marker that
+// ends it, whose FF is *end.  BBOCR_JPEG_OK, _RESTART (markers out of sequence) or _NO_EOI (the data runs to the end of the file).
+inline int scan_segments(const uint8_t* f, size_t n, size_t from, bool want_segs, std::vector<std::pair<size_t, size_t>>& segs, int& nseg,
+                         size_t& end) {
+    size_t q = from, start = from;
+    nseg = 0;
+    while (q < n) {
+        const void* hit = std::memchr(f + q, 0xFF, n - q);
+        if (!hit) break;
+        q = (size_t)((const uint8_t*)hit - f);
+        if (q + 1 >= n) break;
+        const int b = f[q + 1];
+        if (b == 0x00) {
+            q += 2;
+        } else if (b == 0xFF) {
+            q += 1;
+        } else if (b >= 0xD0 && b <= 0xD7) {
+            if (b - 0xD0 != nseg % 8) return BBOCR_JPEG_RESTART;
+            if (want_segs) segs.emplace_back(start, q);
+            ++nseg;
+            q += 2;
+            start = q;
+        } else {
+            if (want_segs) segs.emplace_back(start, q);
+            ++nseg;
+            end = q;
+            return BBOCR_JPEG_OK;
+        }
+    }
+    return BBOCR_JPEG_NO_EOI;
+}
+
+// ---- progressive files
+struct ProgScan {
+    HuffSpec tab[3];                                  // per scan component: its DC (Ss = 0) or AC table as it stood at this SOS
+    std::vector<std::pair<size_t, size_t>> segs;      // byte ranges of the restart segments in the file (stuffing included)
+};
+struct ProgParsed {
+    bbocr_jpeg_progressive_plan plan;
+    unsigned short quant[3][64];                      // per component, natural order
+    std::vector<ProgScan> scans;
+};
+
+// component c's own block raster (what a non-interleaved scan walks), and its blocks across / down an MCU
+inline void prog_comp_raster(const bbocr_jpeg_progressive_plan& pl, int c, int& bw, int& bh, int& ch, int& cv) {
+    const int hmax = pl.components == 3 ? pl.sampling[0][0] : 1, vmax = pl.components == 3 ? pl.sampling[0][1] : 1;
+    ch = pl.components == 3 ? pl.sampling[c][0] : 1;
+    cv = pl.components == 3 ? pl.sampling[c][1] : 1;
+    bw = ((pl.width * ch + hmax - 1) / hmax + 7) / 8;
+    bh = ((pl.height * cv + vmax - 1) / vmax + 7) / 8;
+}
+inline int prog_scan_units(const bbocr_jpeg_progressive_plan& pl, const bbocr_jpeg_scan& sc) {
+    if (sc.components > 1) return pl.mcu_cols * pl.mcu_rows;
+    int bw, bh, ch, cv;
+    prog_comp_raster(pl, sc.component[0], bw, bh, ch, cv);
+    return bw * bh;
+}
+
+// jdmarker.c's walk over a whole SOF2 file: headers, then scan after scan (jdphuff.c's checks of the script as T.81 G.1.1 states them),
+// up to EOI.  Returns the reason; plan.n_scans scans are described when it returns, refused or not.
+inline int prog_walk(const uint8_t* f, size_t n, ProgParsed& out, bool want_segs) {
+    bbocr_jpeg_progressive_plan& pl = out.plan;
+    std::memset(&pl, 0, sizeof pl);
+    out.scans.clear();
+    if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
+    pl.orientation = exif_orientation(f, n);
+    size_t p = 2;
+    unsigned short qt[4][64];
+    bool have_qt[4] = {false, false, false, false};
+    HuffSpec huff[2][4];
+    bool have_sof = false, jfif = false;
+    int adobe = -1, comp_id[4] = {0}, comp_tq[4] = {0}, dri = 0;
+    signed char bits[3][64];                                          // the Al a coefficient has reached, -1: not sent yet
+    std::memset(bits, -1, sizeof bits);
+    for (;;) {
+        for (;;) {
+            if (p + 2 > n || f[p] != 0xFF) return pl.n_scans ? BBOCR_JPEG_NO_EOI : BBOCR_JPEG_TRUNCATED;
+            if (f[p + 1] == 0xFF) { ++p; continue; }
+            break;
+        }
+        const int m = f[p + 1];
+        p += 2;
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (m == 0xD9) break;
+        if (p + 2 > n) return BBOCR_JPEG_TRUNCATED;
+        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
+        if (L < 2 || p + L > n) return BBOCR_JPEG_TRUNCATED;
+        const uint8_t* s = f + p + 2;
+        const size_t sl = L - 2;
+        if (m == 0xC2) {
+            if (have_sof || sl < 6) return BBOCR_JPEG_SOF;
+            if (s[0] != 8) return BBOCR_JPEG_PRECISION;
+            pl.height = (s[1] << 8) | s[2];
+            pl.width = (s[3] << 8) | s[4];
+            pl.components = s[5];
+            if (pl.height == 0 || pl.width == 0 || sl < 6 + 3 * (size_t)pl.components) return BBOCR_JPEG_SOF;
+            for (int i = 0; i < pl.components && i < 4; ++i) {
+                comp_id[i] = s[6 + 3 * i];
+                if (i < 3) { pl.sampling[i][0] = s[7 + 3 * i] >> 4; pl.sampling[i][1] = s[7 + 3 * i] & 15; }
+                comp_tq[i] = s[8 + 3 * i];
+            }
+            have_sof = true;
+        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
+            return BBOCR_JPEG_SOF;                           // baseline (bbocr_host_jpeg_plan's), extended, lossless, arithmetic
+        } else if (m == 0xC4) {
+            if (!read_dht(s, sl, huff)) return BBOCR_JPEG_TABLES;
+        } else if (m == 0xDB) {
+            if (pl.n_scans) return BBOCR_JPEG_MULTISCAN;     // the IDCT stage dequantises once, behind the last scan
+            size_t q = 0;
+            while (q < sl) {
+                if (s[q] >> 4) return BBOCR_JPEG_PRECISION;
+                const int id = s[q] & 15;
+                if (id > 3 || q + 65 > sl) return BBOCR_JPEG_TABLES;
+                for (int k = 0; k < 64; ++k) qt[id][kZigzag[k]] = s[q + 1 + k];
+                have_qt[id] = true;
+                q += 65;
+            }
+        } else if (m == 0xDD) {
+            if (sl < 2) return BBOCR_JPEG_TRUNCATED;
+            dri = (s[0] << 8) | s[1];
+        } else if (m == 0xE0 && sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) {
+            jfif = true;
+        } else if (m == 0xEE && sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
+            adobe = s[11];
+        } else if (m == 0xDA) {
+            if (!have_sof) return BBOCR_JPEG_SOF;
+            const int nc = pl.components;
+            if (pl.n_scans == 0) {                           // the frame, by the rules of the baseline walk
+                if (nc != 1 && nc != 3) return BBOCR_JPEG_COMPONENTS;
+                if (nc == 3) {
+                    if (!jfif && adobe != 1) return BBOCR_JPEG_COLORSPACE;
+                    const bool s420 = pl.sampling[0][0] == 2 && pl.sampling[0][1] == 2 && pl.sampling[1][0] == 1 && pl.sampling[1][1] == 1 &&
+                                      pl.sampling[2][0] == 1 && pl.sampling[2][1] == 1;
+                    pl.chroma = s420 ? 0 : chroma_class_of(pl.sampling);
+                    if (!s420 && !pl.chroma) return BBOCR_JPEG_SAMPLING;
+                }
+                for (int i = 0; i < nc; ++i) {
+                    if (comp_tq[i] > 3 || !have_qt[comp_tq[i]]) return BBOCR_JPEG_TABLES;
+                    std::memcpy(out.quant[i], qt[comp_tq[i]], sizeof qt[0]);
+                }
+                const int mcu_w = nc == 3 ? 8 * pl.sampling[0][0] : 8, mcu_h = nc == 3 ? 8 * pl.sampling[0][1] : 8;
+                pl.mcu_cols = (pl.width + mcu_w - 1) / mcu_w;
+                pl.mcu_rows = (pl.height + mcu_h - 1) / mcu_h;
+            }
+            if (pl.n_scans == BBOCR_JPEG_MAX_SCANS) return BBOCR_JPEG_SCANS;
+            bbocr_jpeg_scan sc{};
+            ProgScan ps;
+            const int ns = sl >= 1 ? s[0] : 0;
+            if (ns < 1 || ns > 3 || ns > nc || sl < 1 + 2 * (size_t)ns + 3) return BBOCR_JPEG_MULTISCAN;
+            sc.components = ns;
+            for (int i = 0; i < ns; ++i) {
+                int c = -1;
+                for (int k = 0; k < nc; ++k)
+                    if (comp_id[k] == s[1 + 2 * i]) { c = k; break; }
+                if (c < 0 || (i > 0 && c <= sc.component[i - 1])) return BBOCR_JPEG_MULTISCAN;
+                sc.component[i] = c;
+                sc.dc_table[i] = s[2 + 2 * i] >> 4;
+                sc.ac_table[i] = s[2 + 2 * i] & 15;
+            }
+            sc.ss = s[1 + 2 * ns];
+            sc.se = s[2 + 2 * ns];
+            sc.ah = s[3 + 2 * ns] >> 4;
+            sc.al = s[3 + 2 * ns] & 15;
+            if (sc.ss == 0 ? sc.se != 0 : (ns != 1 || sc.se < sc.ss || sc.se > 63)) return BBOCR_JPEG_SCRIPT;
+            if (sc.ah > 13 || sc.al > 13) return BBOCR_JPEG_SCRIPT;
+            for (int i = 0; i < ns; ++i) {
+                signed char* b = bits[sc.component[i]];
+                if (sc.ss > 0 && b[0] < 0) return BBOCR_JPEG_SCRIPT;                      // AC before the component's first DC scan
+                for (int k = sc.ss; k <= sc.se; ++k) {
+                    if (b[k] < 0 ? sc.ah != 0 : (sc.ah != b[k] || sc.al != sc.ah - 1)) return BBOCR_JPEG_SCRIPT;
+                    b[k] = (signed char)sc.al;
+                }
+                if (!(sc.ss == 0 && sc.ah > 0)) {                                          // a DC refinement reads raw bits
+                    const int id = sc.ss == 0 ? sc.dc_table[i] : sc.ac_table[i];
+                    JpegHuff probe;
+                    if (id > 3 || !huff[sc.ss == 0 ? 0 : 1][id].have || !derive_table(huff[sc.ss == 0 ? 0 : 1][id], probe)) return BBOCR_JPEG_TABLES;
+                    ps.tab[i] = huff[sc.ss == 0 ? 0 : 1][id];
+                }
+            }
+            sc.restart_interval = dri;
+            sc.offset = (long long)(p + L);
+            const long long units = prog_scan_units(pl, sc), ri = dri ? dri : units;
+            int nseg = 0;
+            size_t end = 0;
+            const int r = scan_segments(f, n, p + L, want_segs, ps.segs, nseg, end);
+            if (r != BBOCR_JPEG_OK) return r;
+            if ((long long)nseg != (units + ri - 1) / ri) return BBOCR_JPEG_RESTART;
+            sc.segments = nseg;
+            sc.bytes = (long long)end - sc.offset;
+            pl.scans[pl.n_scans++] = sc;
+            out.scans.push_back(std::move(ps));
+            p = end;
+            continue;
+        }
+        p += L;
+    }
+    if (!pl.n_scans) return BBOCR_JPEG_TRUNCATED;
+    for (int c = 0; c < pl.components; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (bits[c][k] != 0) return BBOCR_JPEG_SCRIPT;                                 // incomplete: libjpeg-turbo would smooth
+    return BBOCR_JPEG_OK;
+}
+inline int prog_parse(const uint8_t* f, size_t n, ProgParsed& out, bool want_segs) {
+    const int reason = prog_walk(f, n, out, want_segs);
+    out.plan.reason = reason;
+    out.plan.supported = reason == BBOCR_JPEG_OK;
+    return reason;
+}
+
+// tables a scan reads: one per scan component, none in a DC refinement (raw bits)
+inline int prog_scan_tables(const bbocr_jpeg_scan& s) { return s.ss == 0 && s.ah > 0 ? 0 : s.components; }
+// subsequences of S bits a scan is cut into at most: every segment is cut on its own (0 for a refinement, which is not cut)
+inline size_t prog_scan_subs(const bbocr_jpeg_scan& s, int S) { return s.ah > 0 ? 0 : (size_t)s.segments + (size_t)s.bytes * 8 / (size_t)S + 1; }
+
+// Scan k of a parsed file as jpegprog.h reads it: the unstuffed bytes into data[scan.bytes + 8], seg_byte[segments + 1], the derived
+// tables into huff[prog_scan_tables], for a first scan its subsequences of S bits into seg_sub[segments + 1] and sub_seg[prog_scan_subs],
+// and every field of `sc` but its pointers, which the caller owns.
+inline void prog_fill_scan(const ProgParsed& pp, int k, const uint8_t* file, int S, uint8_t* data, int* seg_byte, JpegHuff* huff, int* seg_sub,
+                           int* sub_seg, JpScan& sc) {
+    const bbocr_jpeg_progressive_plan& pl = pp.plan;
+    const bbocr_jpeg_scan& s = pl.scans[k];
+    size_t w = 0;
+    int nsub = 0;
+    for (int g = 0; g < s.segments; ++g) {
+        seg_byte[g] = (int)w;
+        w += unstuff(file + pp.scans[k].segs[g].first, file + pp.scans[k].segs[g].second, data + w);
+        if (s.ah == 0) {
+            const int cnt = (int)std::max<size_t>(((w - (size_t)seg_byte[g]) * 8 + S - 1) / S, 1);
+            seg_sub[g] = nsub;
+            for (int i = 0; i < cnt; ++i) sub_seg[nsub + i] = g;
+            nsub += cnt;
+        }
+    }
+    seg_byte[s.segments] = (int)w;
+    if (s.ah == 0) seg_sub[s.segments] = nsub;
+    sc.nsub = nsub;
+    sc.S = S;
+    for (int i = 0; i < prog_scan_tables(s); ++i) derive_table(pp.scans[k].tab[i], huff[i]);      // prefix codes: the plan checked
+    sc.nseg = s.segments;
+    sc.ncs = s.components;
+    for (int i = 0; i < 3; ++i) sc.comp[i] = s.component[i];
+    sc.Ss = s.ss;
+    sc.Se = s.se;
+    sc.Ah = s.ah;
+    sc.Al = s.al;
+    sc.nunits = prog_scan_units(pl, s);
+    sc.ri = s.restart_interval ? s.restart_interval : std::max(sc.nunits, 1);
+    int bh;
+    prog_comp_raster(pl, s.component[0], sc.bw, bh, sc.ch, sc.cv);
+    sc.hs = pl.components == 3 ? pl.sampling[0][0] : 1;
+    sc.vs = pl.components == 3 ? pl.sampling[0][1] : 1;
+    sc.coff = s.component[0] == 0 ? 0 : sc.hs * sc.vs + s.component[0] - 1;
+    sc.bpm = pl.components == 3 ? sc.hs * sc.vs + 2 : 1;
+    sc.mcux = pl.mcu_cols;
+    sc.ncomp = pl.components;
+    sc.nblocks = pl.mcu_cols * pl.mcu_rows * sc.bpm;
+}
+
+}  // namespace jpeg_host

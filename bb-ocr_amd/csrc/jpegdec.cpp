@@ -6,16 +6,16 @@
 // sampling mean for a pass -- block edges, planes, valid extents, upsampling rule; the device reads it from the descriptors, the plane
 // sizes and bbocr_host_jpeg_scaled_geometry are taken from it.  Every pixel entry point is jpeg_decode_outputs with its own list of
 // outputs (bbocr_jpeg_decode_scaled refuses the files of a chroma class at a draft scale: its documented scope), every stage entry point
-// jpeg_stage_run.
+// jpeg_stage_run.  A progressive file (bbocr_jpeg_decode_progressive alone admits one) is a job whose frame is a plan without a scan -- the
+// baseline entropy stages find nothing to do for it -- and whose scans (jpeg_parse.h) run through jpegprog.hip's launches instead, level
+// by level, into the same coefficient buffer; everything behind the coefficients is shared.
 #include "ctx.h"
+#include "jpeg_parse.h"
 
 namespace {
 
-constexpr unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+using namespace jpeg_host;
 
-struct HuffSpec { bool have = false; unsigned char counts[16] = {0}; unsigned char vals[256] = {0}; int total = 0; };
 struct JpegParsed {
     bbocr_jpeg_plan plan{};
     unsigned short quant[3][64];              // per component, natural order
@@ -24,54 +24,9 @@ struct JpegParsed {
     std::vector<std::pair<size_t, size_t>> segs;   // byte ranges of the restart segments in the file (stuffing included)
 };
 
-// EXIF orientation as cv2.imread applies it: the first APP1 segment that starts with "Exif\0\0" before SOS, a TIFF header of either byte
-// order, IFD0 only, tag 0x0112 as one SHORT or LONG of value 1 .. 8.  Anything else -- no such segment or tag, another type or count,
-// another value, an IFD that does not lie inside the segment -- is 1.  Every read is checked against the segment.
-int exif_orientation(const uint8_t* f, size_t n) {
-    size_t p = 2;
-    while (p + 4 <= n && f[p] == 0xFF) {
-        const int m = f[p + 1];
-        if (m == 0xFF) { ++p; continue; }
-        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) { p += 2; continue; }
-        if (m == 0xDA || m == 0xD9) break;
-        const size_t L = ((size_t)f[p + 2] << 8) | f[p + 3];
-        if (L < 2 || p + 2 + L > n) break;
-        const uint8_t* s = f + p + 4;
-        const size_t sl = L - 2;
-        p += 2 + L;
-        if (m != 0xE1 || sl < 6 || std::memcmp(s, "Exif\0\0", 6) != 0) continue;
-        const uint8_t* t = s + 6;
-        const size_t tl = sl - 6;
-        if (tl < 8) return 1;
-        const bool le = t[0] == 'I' && t[1] == 'I';
-        if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
-        auto u16 = [&](size_t o) { return le ? (unsigned)t[o] | ((unsigned)t[o + 1] << 8) : ((unsigned)t[o] << 8) | (unsigned)t[o + 1]; };
-        auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
-        if (u16(2) != 42) return 1;
-        const size_t ifd = u32(4);
-        if (ifd > tl || tl - ifd < 2) return 1;
-        const size_t cnt = u16(ifd);
-        if ((tl - ifd - 2) / 12 < cnt) return 1;                  // the directory runs off the segment
-        for (size_t i = 0; i < cnt; ++i) {
-            const size_t e = ifd + 2 + 12 * i;
-            if (u16(e) != 0x0112) continue;
-            const unsigned type = u16(e + 2);
-            if ((type != 3 && type != 4) || u32(e + 4) != 1) return 1;
-            const unsigned v = type == 3 ? u16(e + 8) : u32(e + 8);
-            return v >= 1 && v <= 8 ? (int)v : 1;
-        }
-        return 1;
-    }
-    return 1;
-}
-
 // The chroma layouts outside `supported` that the decoder takes all the same (bbocr_jpeg_plan::chroma): luma (1,1), (2,1) or (1,2) over
 // chroma (1,1), (1,1).  0: any other sampling.
-int chroma_class(const bbocr_jpeg_plan& pl) {
-    if (pl.sampling[1][0] != 1 || pl.sampling[1][1] != 1 || pl.sampling[2][0] != 1 || pl.sampling[2][1] != 1) return 0;
-    const int h = pl.sampling[0][0], v = pl.sampling[0][1];
-    return h == 1 && v == 1 ? BBOCR_JPEG_CHROMA_444 : (h == 2 && v == 1 ? BBOCR_JPEG_CHROMA_422 : (h == 1 && v == 2 ? BBOCR_JPEG_CHROMA_440 : 0));
-}
+int chroma_class(const bbocr_jpeg_plan& pl) { return chroma_class_of(pl.sampling); }
 
 // jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.  Returns the reason;
 // `cls` receives the chroma class of a file whose sampling alone is outside today's scope, and the walk goes on as for a supported file.
@@ -117,21 +72,7 @@ int jpeg_walk(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs, int& 
         } else if (m >= 0xC1 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
             return BBOCR_JPEG_SOF;                           // extended, progressive, lossless, arithmetic conditioning
         } else if (m == 0xC4) {
-            size_t q = 0;
-            while (q < sl) {
-                if (q + 17 > sl) return BBOCR_JPEG_TABLES;
-                const int tc = s[q] >> 4, th = s[q] & 15;
-                int tot = 0;
-                for (int i = 0; i < 16; ++i) tot += s[q + 1 + i];
-                if (tc > 1 || th > 1 || tot > 256 || q + 17 + tot > sl) return BBOCR_JPEG_TABLES;
-                HuffSpec& h = out.huff[tc][th];
-                h.have = true;
-                h.total = tot;
-                std::memcpy(h.counts, s + q + 1, 16);
-                std::memset(h.vals, 0, 256);
-                std::memcpy(h.vals, s + q + 17, (size_t)tot);
-                q += 17 + (size_t)tot;
-            }
+            if (!read_dht(s, sl, out.huff)) return BBOCR_JPEG_TABLES;
         } else if (m == 0xDB) {
             size_t q = 0;
             while (q < sl) {
@@ -181,34 +122,10 @@ int jpeg_walk(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs, int& 
     pl.restart_interval = dri;
     pl.scan_offset = (long long)scan_off;
     const long long nmcu = (long long)pl.mcu_cols * pl.mcu_rows;
-    size_t q = scan_off, start = scan_off, end = 0;
-    bool found = false;
+    size_t end = 0;
     int nseg = 0;
-    while (q < n) {
-        const void* hit = std::memchr(f + q, 0xFF, n - q);
-        if (!hit) break;
-        q = (size_t)((const uint8_t*)hit - f);
-        if (q + 1 >= n) break;
-        const int b = f[q + 1];
-        if (b == 0x00) {
-            q += 2;
-        } else if (b == 0xFF) {
-            q += 1;
-        } else if (b >= 0xD0 && b <= 0xD7) {
-            if (b - 0xD0 != nseg % 8) return BBOCR_JPEG_RESTART;
-            if (want_segs) out.segs.emplace_back(start, q);
-            ++nseg;
-            q += 2;
-            start = q;
-        } else {
-            if (want_segs) out.segs.emplace_back(start, q);
-            ++nseg;
-            end = q;
-            found = true;
-            break;
-        }
-    }
-    if (!found) return BBOCR_JPEG_NO_EOI;
+    const int walked = scan_segments(f, n, scan_off, want_segs, out.segs, nseg, end);
+    if (walked != BBOCR_JPEG_OK) return walked;
     if (f[end + 1] != 0xD9) return BBOCR_JPEG_MULTISCAN;
     const long long ri = dri ? dri : nmcu;
     if ((long long)nseg != (nmcu + ri - 1) / ri) return BBOCR_JPEG_RESTART;
@@ -271,29 +188,6 @@ JpegGeometry jpeg_geometry(const bbocr_jpeg_plan& pl, int s) {
 }
 size_t plane_size(const JpegComp& c) { return (size_t)c.plane_rows * (size_t)c.pitch; }
 
-// jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
-bool derive_table(const HuffSpec& h, JpegHuff& t) {
-    std::memset(&t, 0, sizeof t);
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int cnt = h.counts[l - 1];
-        t.valoff[l] = k - code;
-        if (cnt) {
-            if (code + cnt > (1 << l)) return false;
-            for (int i = 0; i < cnt; ++i, ++k, ++code)
-                if (l <= 9)
-                    for (int e = 0; e < (1 << (9 - l)); ++e) t.look[(code << (9 - l)) + e] = (unsigned short)((l << 8) | h.vals[k]);
-            t.maxcode[l] = code - 1;
-        } else {
-            t.maxcode[l] = -1;
-        }
-        code <<= 1;
-    }
-    t.maxcode[0] = t.maxcode[17] = -1;
-    std::memcpy(t.val, h.vals, 256);
-    return true;
-}
-
 constexpr int kMaxPasses = 4;                 // IDCT + output passes over one batch's coefficients: one per scale
 struct JpegPass { int scale, px; };           // px: bytes per pixel of a 3-component file's output
 
@@ -308,21 +202,50 @@ struct FileJob {                              // one admitted file of a batch
     size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[kMaxPasses][3], o_coef; // offsets in the work / coefficient buffers
     size_t o_page = 0;                        // the imread form: offset of the un-oriented decode in jd_page
     JpegGeometry geo[kMaxPasses];             // per pass (filled by jpeg_run)
+    std::shared_ptr<ProgParsed> prog;         // a progressive file: its scans; `ps` then holds the frame alone, as a plan without a scan
+    struct ScanBlob { size_t o_data, o_segbyte, o_huff, o_segsub, o_subseg, subs, w_entry, w_exits, w_count, w_scan, w_flags; };
+    std::vector<ScanBlob> scan_blob;          // per scan: offsets in the input blob
 };
+
+// The frame of a progressive file the plan supports as the stages behind the entropy side read it: a baseline plan of the same size and
+// sampling without a scan (0 segments, 0 bytes), so that the baseline entropy stages find nothing to do for it.
+void frame_of(const ProgParsed& pp, JpegParsed& ps) {
+    const bbocr_jpeg_progressive_plan& q = pp.plan;
+    bbocr_jpeg_plan& pl = ps.plan;
+    pl = bbocr_jpeg_plan{};
+    pl.width = q.width;
+    pl.height = q.height;
+    pl.components = q.components;
+    std::memcpy(pl.sampling, q.sampling, sizeof pl.sampling);
+    pl.mcu_cols = q.mcu_cols;
+    pl.mcu_rows = q.mcu_rows;
+    pl.orientation = q.orientation;
+    pl.chroma = q.chroma;
+    pl.supported = !q.chroma;
+    std::memcpy(ps.quant, pp.quant, sizeof ps.quant);
+    for (int c = 0; c < 3; ++c) ps.tab_dc[c] = ps.tab_ac[c] = 0;
+    ps.segs.clear();
+}
 
 // Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan neither supports nor gives a chroma
 // class (the caller plans first: a refused file is its error); every other file becomes a job once dest(job) -- the entry point's own rule -- has checked the caller's
 // destination and set the job's `out` and `pitch` (false: refused like the others).  chroma_classes false (a scaled decode): only the
-// files the plan supports, 4:2:0 and grey.
+// files the plan supports, 4:2:0 and grey.  progressive: a file both refuse is planned as a progressive one
+// (bbocr_host_jpeg_progressive_plan) and admitted when that plan supports it.
 template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* files, const size_t* bytes, int n, int* status, D&& dest,
-                                                       bool chroma_classes = true) {
+                                                       bool chroma_classes = true, bool progressive = false) {
     std::vector<FileJob> jobs;
     jobs.reserve((size_t)n);
     for (int k = 0; k < n; ++k) {
         status[k] = BBOCR_ERR_ARG;
         if (!files[k] || bytes[k] >= ((size_t)1 << 28)) continue;
         FileJob j;
-        jpeg_parse(files[k], bytes[k], j.ps, true);
+        const int reason = jpeg_parse(files[k], bytes[k], j.ps, true);
+        if (progressive && !jpeg_taken(j.ps.plan) && reason != BBOCR_JPEG_NOT_JPEG) {   // whatever the baseline walk stopped at
+            j.prog = std::make_shared<ProgParsed>();
+            if (prog_parse(files[k], bytes[k], *j.prog, true) != BBOCR_JPEG_OK) continue;
+            frame_of(*j.prog, j.ps);
+        }
         if (!jpeg_taken(j.ps.plan) || (!chroma_classes && !j.ps.plan.supported)) continue;
         j.file = files[k];
         j.k = k;
@@ -342,12 +265,59 @@ void jpeg_report(const std::vector<FileJob>& jobs, const std::vector<int>& dev_s
 // planes of its own and the jobs' out[p] / pitch[p].  A pass of scale 2, 4 or 8 is the decode at that fraction (`out[p]` holds the scaled
 // size); its descriptors carry jpeg_geometry's table, so one launch pair serves every file of the batch.
 void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S, const std::vector<JpegPass>& passes_out,
-              std::vector<int>& dev_status, std::vector<JpegDesc>* descs_out = nullptr) {
+              std::vector<int>& dev_status, std::vector<JpegDesc>* descs_out = nullptr, int scan_limit = 0) {
     const int n = (int)jobs.size(), np = (int)passes_out.size();
     Carve in{align_up(sizeof(JpegDesc) * (size_t)n * np, 256)}, work{align_up(4 * (size_t)n, 256)}, coef;
     int max_groups = 1, max_seg = 1, max_blocks = 1, max_h = 1, max_w = 1;                // max_h, max_w: at full scale
+    // A progressive file's scans (the first scan_limit of them) in launches by level: a scan waits for the earlier scans that hold one of
+    // its components and overlap its band, and for no other -- scans of one level write different coefficients, each as 16-bit stores --
+    // so libjpeg's ten-scan script is three launches: every first scan, then the refinements, then luma's last one.
+    auto scans_of = [&](const FileJob& j) { return !j.prog ? 0 : (scan_limit > 0 ? std::min(scan_limit, j.prog->plan.n_scans) : j.prog->plan.n_scans); };
+    struct LevelScan { int job, k; };
+    std::vector<std::vector<LevelScan>> levels;
+    size_t total_scans = 0;
+    for (int i = 0; i < n; ++i) {
+        const FileJob& j = jobs[i];
+        std::vector<int> level((size_t)scans_of(j), 0);
+        for (int k = 0; k < scans_of(j); ++k) {
+            const bbocr_jpeg_scan& b = j.prog->plan.scans[k];
+            for (int e = 0; e < k; ++e) {
+                const bbocr_jpeg_scan& a = j.prog->plan.scans[e];
+                bool shares = false;
+                for (int x = 0; x < a.components; ++x)
+                    for (int y = 0; y < b.components; ++y) shares |= a.component[x] == b.component[y];
+                if (shares && a.ss <= b.se && b.ss <= a.se) level[k] = std::max(level[k], level[e] + 1);
+            }
+            if (levels.size() <= (size_t)level[k]) levels.resize((size_t)level[k] + 1);
+            levels[level[k]].push_back({i, k});
+            ++total_scans;
+        }
+    }
+    std::vector<int> level_groups(levels.size(), 1);
+    int prog_groups = 1, prog_max_seg = 1;                                    // of the first scans: workgroups of 64 subsequences, segments
+    const size_t o_scans = in.add(sizeof(JpScan) * std::max<size_t>(total_scans, 1));
     for (FileJob& j : jobs) {
         const bbocr_jpeg_plan& pl = j.ps.plan;
+        j.scan_blob.resize((size_t)scans_of(j));
+        for (int k = 0; k < scans_of(j); ++k) {
+            const bbocr_jpeg_scan& sc = j.prog->plan.scans[k];
+            FileJob::ScanBlob& b = j.scan_blob[k];
+            b = {};
+            b.o_data = in.add((size_t)sc.bytes + 8);
+            b.o_segbyte = in.add(4 * ((size_t)sc.segments + 1));
+            b.o_huff = in.add(std::max<size_t>(prog_scan_tables(sc), 1) * sizeof(JpegHuff));
+            b.subs = prog_scan_subs(sc, S);
+            if (b.subs) {                                                     // a first scan: subsequence lists and states, as for a baseline scan
+                b.o_segsub = in.add(4 * ((size_t)sc.segments + 1));
+                b.o_subseg = in.add(4 * b.subs);
+                b.w_entry = work.add(8 * b.subs);
+                b.w_exits = work.add(8 * b.subs);
+                b.w_count = work.add(4 * b.subs);
+                b.w_scan = work.add(4 * b.subs);
+                prog_groups = std::max(prog_groups, (int)((b.subs + 63) / 64));
+            }
+            prog_max_seg = std::max(prog_max_seg, sc.segments);
+        }
         j.o_huff = in.add(4 * sizeof(JpegHuff));
         j.o_quant = in.add(3 * 64 * 2);
         j.o_segbyte = in.add(4 * ((size_t)pl.segments + 1));
@@ -383,14 +353,7 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
             const uint8_t* e = j.file + j.ps.segs[s].second;
             seg_byte[s] = (int)w;
             seg_sub[s] = nsub;
-            while (a < e) {                                               // copy up to and including the next FF, drop the 00 behind it
-                const uint8_t* ff = (const uint8_t*)std::memchr(a, 0xFF, (size_t)(e - a));
-                const size_t len = ff ? (size_t)(ff - a) + 1 : (size_t)(e - a);
-                std::memcpy(data + w, a, len);
-                w += len;
-                a += len;
-                if (ff && a < e && *a == 0x00) ++a;
-            }
+            w += unstuff(a, e, data + w);
             const size_t bits = (w - (size_t)seg_byte[s]) * 8;
             const int cnt = (int)std::max<size_t>((bits + S - 1) / S, 1);
             for (int k = 0; k < cnt; ++k) sub_seg[nsub + k] = s;
@@ -416,6 +379,10 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     const int passes = max_groups + 1;
     const size_t flags_off = work.off;
     for (FileJob& j : jobs) j.w_flags = work.add(4 * (size_t)passes);
+    const int prog_passes = prog_groups + 1;
+    for (FileJob& j : jobs)
+        for (FileJob::ScanBlob& b : j.scan_blob)
+            if (b.subs) b.w_flags = work.add(4 * (size_t)prog_passes);
     root->jd_work.ensure(work.off);
     root->jd_coef.ensure(std::max<size_t>(coef.off, 256));
     char* wb = (char*)root->jd_work.p;
@@ -467,6 +434,35 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
             descs[(size_t)p * n + k] = d;
         }
     }
+    JpScan* scans = (JpScan*)(hb + o_scans);
+    std::memset(scans, 0, sizeof(JpScan) * std::max<size_t>(total_scans, 1));
+    {
+        size_t at = 0;
+        for (size_t L = 0; L < levels.size(); ++L)
+            for (const LevelScan& e : levels[L]) {
+                const FileJob& j = jobs[e.job];
+                const FileJob::ScanBlob& b = j.scan_blob[e.k];
+                JpScan& sc = scans[at++];
+                prog_fill_scan(*j.prog, e.k, j.file, S, (uint8_t*)(hb + b.o_data), (int*)(hb + b.o_segbyte), (JpegHuff*)(hb + b.o_huff),
+                               (int*)(hb + b.o_segsub), (int*)(hb + b.o_subseg), sc);
+                if (b.subs) {
+                    sc.seg_sub = (const int*)(db + b.o_segsub);
+                    sc.sub_seg = (const int*)(db + b.o_subseg);
+                    sc.entry = (unsigned long long*)(wb + b.w_entry);
+                    sc.exits = (unsigned long long*)(wb + b.w_exits);
+                    sc.count = (int*)(wb + b.w_count);
+                    sc.scan = (int*)(wb + b.w_scan);
+                    sc.flags = (int*)(wb + b.w_flags);
+                    sc.passes = prog_passes;
+                }
+                sc.data = (const uint8_t*)(db + b.o_data);
+                sc.seg_byte = (const int*)(db + b.o_segbyte);
+                sc.huff = (const JpegHuff*)(db + b.o_huff);
+                sc.coef = descs[e.job].coef;
+                sc.status = descs[e.job].status;
+                level_groups[L] = std::max(level_groups[L], jp_scan_groups(sc.Ss, sc.Ah, sc.nseg, sc.nunits));
+            }
+    }
     if (descs_out) descs_out->assign(descs, descs + n);
     HIPCHK(hipMemcpyAsync(db, hb, in.off, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(wb, 0, align_up(4 * (size_t)n, 256), st));                    // status words
@@ -477,6 +473,15 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     HIPCHK(launch_jd_scan(dd, n, st));
     HIPCHK(launch_jd_write(dd, n, max_groups, st));
     HIPCHK(launch_jd_dc(dd, n, max_seg, st));
+    {
+        size_t at = 0;
+        for (size_t L = 0; L < levels.size(); at += levels[L].size(), ++L)
+            for (size_t c = 0; c < levels[L].size(); c += 32768) {        // a launch holds at most 65535 scans (the grid's second dimension)
+                HIPCHK(launch_jp_first((const JpScan*)(db + o_scans) + at + c, (int)std::min<size_t>(levels[L].size() - c, 32768), prog_groups,
+                                       prog_passes, prog_max_seg, st));
+                HIPCHK(launch_jp_scan((const JpScan*)(db + o_scans) + at + c, (int)std::min<size_t>(levels[L].size() - c, 32768), level_groups[L], st));
+            }
+    }
     for (int p = 0; p < np; ++p) {
         const JpegDesc* dp = dd + (size_t)p * n;
         HIPCHK(launch_jd_idct(dp, n, max_blocks, st));
@@ -496,7 +501,7 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
 // or the grey samples, tight rows -- and page_orient writes the caller's BGR page from there.  chroma_classes false: only the files the
 // plan supports, 4:2:0 and grey.  Argument errors are raised before anything is queued; a refused file's destinations are never written.
 void jpeg_decode_outputs(bbocr_ctx* ctx, hipStream_t st, const uint8_t* const* files, const size_t* bytes, int n, int layout,
-                         const bbocr_jpeg_output* outputs, int n_outputs, int* status, bool chroma_classes) {
+                         const bbocr_jpeg_output* outputs, int n_outputs, int* status, bool chroma_classes, bool progressive = false) {
     if (!files || !bytes || !outputs || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
     if (layout != BBOCR_PAGE_YCBCR3 && layout != BBOCR_PAGE_YCBCR4) fail(BBOCR_ERR_ARG, "layout must be BBOCR_PAGE_YCBCR3 or BBOCR_PAGE_YCBCR4");
     if (n_outputs < 1 || n_outputs > kMaxPasses) fail(BBOCR_ERR_ARG, "1 .. 4 outputs, one per scale");
@@ -528,7 +533,7 @@ void jpeg_decode_outputs(bbocr_ctx* ctx, hipStream_t st, const uint8_t* const* f
         }
         if (imread >= 0) j.o_page = pages.add((size_t)j.pitch[imread] * (size_t)pl.height);
         return true;
-    }, chroma_classes);
+    }, chroma_classes, progressive);
     if (jobs.empty()) return;
     std::vector<JpegPass> passes;
     for (int o = 0; o < n_outputs; ++o) passes.push_back({outputs[o].scale, page_px_bytes(o == imread ? (int)PAGE_YCC4 : layout)});
@@ -555,7 +560,7 @@ void jpeg_decode_outputs(bbocr_ctx* ctx, hipStream_t st, const uint8_t* const* f
 // every file the decoder takes, 0 the 4:2:0 and grey ones only, 1 those of a chroma class only.  Returns the file's descriptor (the
 // entropy stages' intermediates).
 JpegDesc jpeg_stage_run(bbocr_ctx* ctx, hipStream_t s, int stage, const uint8_t* file, size_t bytes, int S, int scale, int cls, void* dev_dst,
-                        size_t dst_bytes, int* file_status) {
+                        size_t dst_bytes, int* file_status, bool progressive = false, int scan_limit = 0) {
     if (!file || !dev_dst || stage < 0 || stage > 3 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
     int status = 0;
     std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
@@ -569,11 +574,11 @@ JpegDesc jpeg_stage_run(bbocr_ctx* ctx, hipStream_t s, int stage, const uint8_t*
         j.out[0] = stage == 3 ? (uint8_t*)dev_dst : (uint8_t*)ctx->jd_stage.p;
         j.pitch[0] = (long long)g.OW * pl.components;
         return true;
-    });
+    }, true, progressive);
     if (jobs.empty()) fail(BBOCR_ERR_ARG, "the plan refuses this file, or this entry point does not take its sampling");
     std::vector<int> ds;
     std::vector<JpegDesc> descs;
-    jpeg_run(ctx, s, jobs, S, {{scale, 3}}, ds, &descs);
+    jpeg_run(ctx, s, jobs, S, {{scale, 3}}, ds, &descs, scan_limit);
     jpeg_report(jobs, ds, &status);
     if (file_status) *file_status = status;
     const JpegDesc& d = descs[0];
@@ -633,6 +638,35 @@ int bbocr_jpeg_decode_scales(bbocr_ctx* ctx, const uint8_t* const* files, const 
                              int n_outputs, int* status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true,
                         [&](hipStream_t st) { jpeg_decode_outputs(ctx, st, files, bytes, n, layout, outputs, n_outputs, status, true); });
+}
+
+int bbocr_host_jpeg_progressive_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_progressive_plan* plan) {
+    if (!file || !plan) return BBOCR_ERR_ARG;
+    ProgParsed pp;
+    prog_parse(file, bytes, pp, false);
+    *plan = pp.plan;
+    return BBOCR_OK;
+}
+
+int bbocr_jpeg_decode_progressive(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout,
+                                  const bbocr_jpeg_output* outputs, int n_outputs, int* status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true,
+                        [&](hipStream_t st) { jpeg_decode_outputs(ctx, st, files, bytes, n, layout, outputs, n_outputs, status, true, true); });
+}
+
+int bbocr_op_jpeg_progressive_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int n_scans, int subseq_bits, void* dev_dst,
+                                    size_t dst_bytes, int* file_status) {
+    return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
+        const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
+        if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
+        if (stage < 1 || stage > 3 || n_scans < 0 || n_scans > BBOCR_JPEG_MAX_SCANS) fail(BBOCR_ERR_ARG, "stage 1, 2 or 3 after 0 .. 64 scans");
+        const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, S, 1, -1, dev_dst, dst_bytes, file_status, true, n_scans);
+        if (stage == 1) {
+            if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
+            HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    });
 }
 
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,

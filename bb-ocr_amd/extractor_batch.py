@@ -26,10 +26,11 @@ import numpy as np
 
 def _jpg_page(source, device_decode=True):
     """``("jpg", JpegPage, None)`` when the device decoder takes the file (a path or its bytes), else None.  ``device_decode``: the
-    caller's option; ``"chroma"`` adds 4:4:4, 4:2:2 and 4:4:0 files (``reader.jpeg_chroma``)."""
-    from .reader import jpeg_chroma, jpeg_page
+    caller's option; ``"chroma"`` adds 4:4:4, 4:2:2 and 4:4:0 files (``reader.jpeg_chroma``), ``"progressive"`` those and progressive
+    files (``reader.jpeg_progressive``)."""
+    from .reader import jpeg_chroma, jpeg_page, jpeg_progressive
 
-    page = jpeg_page(source, jpeg_chroma(device_decode))
+    page = jpeg_page(source, jpeg_chroma(device_decode), jpeg_progressive(device_decode))
     return None if page is None else ("jpg", page, None)
 
 
@@ -654,10 +655,10 @@ def _trace_decode_once(reader, data, device_decode, png="pillow"):
     from PIL import Image
 
     from .preprocess import PAGE_GRAY, PAGE_YCBCR4, PREVIEW_MAX_DIM, _preview_of_decode, _preview_string, orient_page_device, preview_draft_scale
-    from .reader import JpegPage, jpeg_chroma, jpeg_plan
+    from .reader import JpegPage, jpeg_chroma, jpeg_device_plan, jpeg_progressive
 
-    plan = jpeg_plan(data)
-    if not (plan.supported or (jpeg_chroma(device_decode) and plan.chroma)):
+    plan = jpeg_device_plan(data, jpeg_chroma(device_decode), jpeg_progressive(device_decode))
+    if plan is None:
         return None
     s = preview_draft_scale(plan, PREVIEW_MAX_DIM)
     decodes, status = reader.decode_jpeg_scales_batch([JpegPage(data, plan)], (1,) if s == 1 else (1, s), imread=s != 1)

@@ -112,14 +112,16 @@ def imread_bgr_device(reader, source, device_decode=None):
     and this function do not."""
     from PIL import Image
 
-    from .reader import JpegPage, _file_bytes, decode_file_ycc, jpeg_chroma, jpeg_plan
+    from .reader import JpegPage, _file_bytes, decode_file_ycc, jpeg_chroma, jpeg_device_plan, jpeg_plan, jpeg_progressive
 
     chroma = getattr(reader, "jpeg_chroma", False) if device_decode is None else jpeg_chroma(device_decode)
+    progressive = getattr(reader, "jpeg_progressive", False) if device_decode is None else jpeg_progressive(device_decode)
     data = _file_bytes(source)
     plan = jpeg_plan(data)
     out = path = None
-    if plan.supported or (chroma and plan.chroma):
-        pages, status = reader.imread_jpeg_batch([JpegPage(data, plan)])
+    taken = jpeg_device_plan(data, chroma, progressive, plan)       # "progressive": a progressive file under its own plan
+    if taken is not None:
+        pages, status = reader.imread_jpeg_batch([JpegPage(data, taken)])
         if status[0] == 0:
             out, path = pages[0], IMREAD_JPEG
     if out is None:
@@ -392,14 +394,15 @@ def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, 
     * ``"device-jpeg"`` -- a JPEG path or bytes the device decoder's plan supports (4:2:0 or grey baseline) and ``device_decode``: plan ->
       draft scale -> ``bbocr_jpeg_decode_scaled`` -> libjpeg's RGB -> ``bbocr_thumbnail_box``; the file's ICC profile is carried into the
       PNG as Pillow carries it.  ``device_decode="chroma"``: a 4:4:4, 4:2:2 or 4:4:0 file (``plan.chroma``) as well, decoded at its
-      draft scale by ``bbocr_jpeg_decode_scales``;
+      draft scale by ``bbocr_jpeg_decode_scales``; ``device_decode="progressive"``: those, and a progressive file its own plan supports
+      (``bbocr_jpeg_decode_progressive``);
     * ``"device-page"`` -- a page already on the card (a uint8 tensor, gray [H,W] or BGR [H,W,3], a strided view included -- the f2 output
       or a crop): the whole-image thumbnail (``bbocr_ocr_thumbnail`` without its JPEG round trip); a gray page stays mode L;
     * ``"host"`` -- everything else (PNG, progressive / CMYK JPEG, 4:4:4 / 4:2:2 / 4:4:0 JPEG unless asked for, a file whose data is
       damaged, host arrays): ``preview_host``."""
     from PIL import Image
 
-    from .reader import _file_bytes, jpeg_chroma, jpeg_plan
+    from .reader import _file_bytes, jpeg_chroma, jpeg_device_plan, jpeg_progressive
 
     png = png_writer(png)
     px, icc, route = None, None, PREVIEW_HOST
@@ -409,8 +412,8 @@ def preview_device(reader, source, max_dim=PREVIEW_MAX_DIM, device_decode=True, 
         px, route = (gray if ch == 1 else rgb), PREVIEW_PAGE
     elif device_decode and not isinstance(source, np.ndarray):
         data = _file_bytes(source)
-        plan = jpeg_plan(data)
-        if plan.supported or (jpeg_chroma(device_decode) and plan.chroma):
+        plan = jpeg_device_plan(data, jpeg_chroma(device_decode), jpeg_progressive(device_decode))
+        if plan is not None:
             px = _preview_jpeg_device(reader, data, plan, max_dim)
             icc = Image.open(io.BytesIO(data)).info.get("icc_profile")          # headers only
             source = data

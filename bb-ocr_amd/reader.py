@@ -158,13 +158,16 @@ class JpegPage:
     """A baseline JPEG file the device decoder takes (``jpeg_plan``): its bytes and the shape of its decode, ``(H, W, components)``.  The
     page kind ``"jpg"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one ``bbocr_jpeg_decode`` call.
     ``orientation``: the plan's EXIF orientation (1 .. 8), which ``shape`` does not reflect -- ``readtext`` reads files un-oriented, and
-    only ``Reader.imread_jpeg_batch`` (``cv2.imread``'s page) applies it."""
-    __slots__ = ("data", "shape", "orientation")
+    only ``Reader.imread_jpeg_batch`` (``cv2.imread``'s page) applies it.  ``progressive``: the page was made from
+    ``jpeg_progressive_plan`` -- a progressive file, for which the Reader's batch calls use ``bbocr_jpeg_decode_progressive``."""
+    __slots__ = ("data", "shape", "orientation", "progressive")
 
     def __init__(self, data, plan):
         self.data = data
         self.shape = (int(plan.height), int(plan.width), int(plan.components))
         self.orientation = int(plan.orientation)
+        # made from ``jpeg_progressive_plan``: a progressive file, which only ``bbocr_jpeg_decode_progressive`` decodes
+        self.progressive = isinstance(plan, _lib.bbocr_jpeg_progressive_plan)
 
 
 def jpeg_plan(data):
@@ -175,6 +178,17 @@ def jpeg_plan(data):
     rc = _lib.load().bbocr_host_jpeg_plan(data, len(data), C.byref(plan))
     if rc != 0:
         raise RuntimeError(f"bbocr_host_jpeg_plan failed with status {rc}")
+    return plan
+
+
+def jpeg_progressive_plan(data):
+    """``bbocr_host_jpeg_progressive_plan`` of a file's bytes (no GPU): the frame, ``supported`` / ``reason`` and the scan script --
+    ``plan.scans[k]`` for ``k < plan.n_scans``: components, ``ss, se, ah, al``, the restart interval in force, segments, byte range and
+    table ids.  A baseline file is refused by this plan (reason ``BBOCR_JPEG_SOF``): it has ``jpeg_plan``."""
+    plan = _lib.bbocr_jpeg_progressive_plan()
+    rc = _lib.load().bbocr_host_jpeg_progressive_plan(data, len(data), C.byref(plan))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_jpeg_progressive_plan failed with status {rc}")
     return plan
 
 
@@ -192,19 +206,42 @@ def draft_scale(W, H, req_w, req_h):
 DECODE_CHROMA = "chroma"   # the value of ``device_decode`` / ``BBOCR_DEVICE_DECODE`` that adds 4:4:4, 4:2:2 and 4:4:0 files to the device decoder's
 
 
+DECODE_PROGRESSIVE = "progressive"   # the value that means "chroma" plus the progressive files ``jpeg_progressive_plan`` supports
+
+
+def jpeg_progressive(device_decode):
+    """True for ``device_decode="progressive"``: ``"chroma"``'s scope and progressive files"""
+    return isinstance(device_decode, str) and device_decode.strip().lower() == DECODE_PROGRESSIVE
+
+
 def jpeg_chroma(device_decode):
-    """True for ``device_decode="chroma"``: device decode with the wider scope -- the files whose plan has ``chroma`` set although
-    ``supported`` is 0.  Every other value (``True``, ``"1"``, ``False``, ``None``) is today's scope."""
-    return isinstance(device_decode, str) and device_decode.strip().lower() == DECODE_CHROMA
+    """True for ``device_decode="chroma"`` (and ``"progressive"``, which includes it): device decode with the wider scope -- the files
+    whose plan has ``chroma`` set although ``supported`` is 0.  Every other value (``True``, ``"1"``, ``False``, ``None``) is today's scope."""
+    return isinstance(device_decode, str) and device_decode.strip().lower() in (DECODE_CHROMA, DECODE_PROGRESSIVE)
 
 
-def jpeg_page(source, chroma=False):
+def jpeg_device_plan(data, chroma=False, progressive=False, plan=None):
+    """The plan under which the device decoder takes a file's bytes, or ``None``: ``jpeg_plan``'s (``plan``, when the caller has it) if it
+    supports the file or, with ``chroma``, names its class; with ``progressive``, ``jpeg_progressive_plan``'s for a progressive file it
+    supports.  ``JpegPage(data, that plan)`` is the page to decode."""
+    plan = jpeg_plan(data) if plan is None else plan
+    if plan.supported or (chroma and plan.chroma):
+        return plan
+    if progressive and plan.reason != _lib.JPEG_NOT_JPEG:   # any file with an SOI: the baseline walk may stop before it reaches the SOF2 marker
+        pplan = jpeg_progressive_plan(data)
+        if pplan.supported:
+            return pplan
+    return None
+
+
+def jpeg_page(source, chroma=False, progressive=False):
     """``JpegPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path).
-    ``chroma``: a 4:4:4, 4:2:2 or 4:4:0 file (``plan.chroma``) is taken as well."""
+    ``chroma``: a 4:4:4, 4:2:2 or 4:4:0 file (``plan.chroma``) is taken as well; ``progressive``: so is a progressive file that
+    ``jpeg_progressive_plan`` supports."""
     try:
         data = _file_bytes(source)
-        plan = jpeg_plan(data)
-        return JpegPage(data, plan) if plan.supported or (chroma and plan.chroma) else None
+        plan = jpeg_device_plan(data, chroma, progressive)
+        return JpegPage(data, plan) if plan is not None else None
     except Exception:
         return None
 
@@ -424,9 +461,10 @@ class Reader:
         self.host_threads = int(host_threads)
         if device_decode is None:   # baseline JPEG files decoded on the card (csrc/jpegdec.hip) by readtext(path); off unless asked for
             env = os.environ.get("BBOCR_DEVICE_DECODE", "0").strip().lower()
-            device_decode = DECODE_CHROMA if env == DECODE_CHROMA else env == "1"
+            device_decode = env if env in (DECODE_CHROMA, DECODE_PROGRESSIVE) else env == "1"
         self.device_decode = bool(device_decode)
         self.jpeg_chroma = jpeg_chroma(device_decode)     # "chroma": 4:4:4, 4:2:2 and 4:4:0 files are decoded on the card as well
+        self.jpeg_progressive = jpeg_progressive(device_decode)   # "progressive": those, and progressive files (csrc/jpegprog.hip)
         cfg = _lib.bbocr_config(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
                                 precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads,
                                 rec_quant=int(self.rec_quant))
@@ -771,7 +809,10 @@ class Reader:
         outs = (C.c_void_p * n)(*[t.data_ptr() + k * H * W * px for k in range(n)])
         pitches = (C.c_longlong * n)(*([W * px] * n))
         status = (C.c_int * n)()
-        if scale == 1:
+        if any(p.progressive for p in pages):              # the call that takes every file of the others, and progressive ones
+            out = _lib.bbocr_jpeg_output(scale, _lib.JPEG_FORM_YCBCR, outs, pitches)
+            self._check(self._lib.bbocr_jpeg_decode_progressive(self._h, files, sizes, n, layout, C.byref(out), 1, status))
+        elif scale == 1:
             self._check(self._lib.bbocr_jpeg_decode(self._h, files, sizes, n, layout, outs, pitches, status))
         else:
             self._check(self._lib.bbocr_jpeg_decode_scaled(self._h, files, sizes, n, layout, scale, outs, pitches, status))
@@ -795,7 +836,11 @@ class Reader:
         ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
         pitches = (C.c_longlong * n)(*[t.shape[1] * 3 for t in outs])
         status = (C.c_int * n)()
-        self._check(self._lib.bbocr_jpeg_imread(self._h, files, sizes, n, ptrs, pitches, status))
+        if any(p.progressive for p in pages):
+            out = _lib.bbocr_jpeg_output(1, _lib.JPEG_FORM_IMREAD, ptrs, pitches)
+            self._check(self._lib.bbocr_jpeg_decode_progressive(self._h, files, sizes, n, _lib.PAGE_YCBCR4, C.byref(out), 1, status))
+        else:
+            self._check(self._lib.bbocr_jpeg_imread(self._h, files, sizes, n, ptrs, pitches, status))
         return outs, list(status)
 
     def pages_from_jpeg(self, batch):
@@ -887,17 +932,25 @@ class Reader:
 
     @property
     def decode_option(self):
-        """This Reader's ``device_decode`` as the functions of ``extractor_batch`` and ``preprocess`` take it: ``"chroma"``, True or False"""
-        return DECODE_CHROMA if self.jpeg_chroma else self.device_decode
+        """This Reader's ``device_decode`` as the functions of ``extractor_batch`` and ``preprocess`` take it: ``"progressive"``,
+        ``"chroma"``, True or False"""
+        return DECODE_PROGRESSIVE if self.jpeg_progressive else DECODE_CHROMA if self.jpeg_chroma else self.device_decode
 
-    def decode_jpeg_device(self, sources, chroma=None, scale=1):
+    @staticmethod
+    def jpeg_progressive_plan(source):
+        """``jpeg_progressive_plan`` of a path or a bytes object: the plan of a multi-scan file, its script included (no GPU)"""
+        return jpeg_progressive_plan(_file_bytes(source))
+
+    def decode_jpeg_device(self, sources, chroma=None, scale=1, progressive=None):
         """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them (libjpeg's RGB and its Y
         plane; a grey file: the samples, replicated for RGB), decoded on the card, or ``None`` for a file the plan refuses or whose
         entropy-coded data is damaged.  Files of one decoded shape share one decode call.  ``chroma`` (None: this Reader's
         ``jpeg_chroma``): 4:4:4, 4:2:2 and 4:4:0 files are decoded as well.  ``scale`` 2, 4 or 8: the decode at that fraction (Pillow's
-        ``draft``: ``ceil(H / scale) x ceil(W / scale)``), of 4:2:0 and grey files only -- every other file is ``None``."""
+        ``draft``: ``ceil(H / scale) x ceil(W / scale)``), of 4:2:0 and grey files only -- every other file is ``None``.  ``progressive``
+        (None: this Reader's ``jpeg_progressive``): progressive files are decoded as well, of every sampling at every scale."""
+        progressive = self.jpeg_progressive if progressive is None else bool(progressive)   # such files are decoded too, at every scale
         chroma = (self.jpeg_chroma if chroma is None else bool(chroma)) and scale == 1
-        pages = [jpeg_page(s, chroma) for s in sources]
+        pages = [jpeg_page(s, chroma, progressive) for s in sources]
         out = [None] * len(pages)
         groups = {}
         for i, p in enumerate(pages):
@@ -954,11 +1007,12 @@ class Reader:
         torch.cuda.current_stream(self.device_index).synchronize()
         files, sizes = self._jpeg_files(pages)
         status = (C.c_int * n)()
-        self._check(self._lib.bbocr_jpeg_decode_scales(self._h, files, sizes, n, _lib.PAGE_YCBCR4, outs, len(scales), status))
+        call = self._lib.bbocr_jpeg_decode_progressive if any(p.progressive for p in pages) else self._lib.bbocr_jpeg_decode_scales
+        self._check(call(self._h, files, sizes, n, _lib.PAGE_YCBCR4, outs, len(scales), status))
         del keep
         return decodes, list(status)
 
-    def decode_jpeg_scales(self, sources, scales=(1, 2), chroma=None, imread=False):
+    def decode_jpeg_scales(self, sources, scales=(1, 2), chroma=None, imread=False, progressive=None):
         """Paths or bytes objects -> per source ``{scale: pages}``, or ``None`` for a file the plan refuses or whose entropy-coded data is
         damaged -- all scales of all files from ONE device call that runs the entropy stages once per file (``decode_jpeg_device`` called
         once per scale runs them once per scale).  ``pages`` is ``(rgb_dev [oh,ow,3], gray_dev [oh,ow])`` as ``decode_jpeg_device`` defines
@@ -966,7 +1020,8 @@ class Reader:
         orientation applied.  ``chroma`` (None: this Reader's ``jpeg_chroma``): 4:4:4, 4:2:2 and 4:4:0 files are decoded as well -- here at
         EVERY scale, where ``decode_jpeg_device(scale=2)`` leaves them to the host."""
         chroma = self.jpeg_chroma if chroma is None else bool(chroma)
-        pages = [jpeg_page(s, chroma) for s in sources]
+        progressive = self.jpeg_progressive if progressive is None else bool(progressive)     # progressive files are decoded as well
+        pages = [jpeg_page(s, chroma, progressive) for s in sources]
         out = [None] * len(pages)
         idxs = [i for i, p in enumerate(pages) if p is not None]
         if not idxs:

@@ -518,7 +518,9 @@ enum {
     BBOCR_JPEG_COLORSPACE = 8,  /* three components without JFIF or Adobe transform 1: may be RGB-coded */
     BBOCR_JPEG_MULTISCAN = 9,   /* a scan that does not hold every component, or more after the first */
     BBOCR_JPEG_TABLES = 10,     /* a table the scan names is missing or malformed */
-    BBOCR_JPEG_RESTART = 11     /* restart markers out of sequence, or not one per interval */
+    BBOCR_JPEG_RESTART = 11,    /* restart markers out of sequence, or not one per interval */
+    BBOCR_JPEG_SCRIPT = 12,     /* bbocr_host_jpeg_progressive_plan only: the progression is invalid (T.81 G.1.1) or incomplete */
+    BBOCR_JPEG_SCANS = 13       /* bbocr_host_jpeg_progressive_plan only: more than BBOCR_JPEG_MAX_SCANS scans */
 };
 enum { BBOCR_JPEG_CHROMA_444 = 1, BBOCR_JPEG_CHROMA_422 = 2, BBOCR_JPEG_CHROMA_440 = 3 };   /* bbocr_jpeg_plan::chroma */
 /* A file of a chroma class (chroma != 0) has supported == 0 and reason == BBOCR_JPEG_SAMPLING like every other file outside 4:2:0, and
@@ -618,6 +620,63 @@ int bbocr_jpeg_decode_scales(bbocr_ctx* ctx, const uint8_t* const* files, const 
 /* read-only totals of this context's JPEG lane since bbocr_create, per file of every batch: out[0] = files decoded, out[1] = runs of the
  * entropy stages, out[2] = IDCT passes, out[3] = output passes.  A two-output bbocr_jpeg_decode_scales call of one file adds 1, 1, 2, 2. */
 int bbocr_jpeg_counters(bbocr_ctx* ctx, long long* out);
+/* ---- progressive JPEG files (SOF2) decoded on the device (csrc/jpegprog.hip), opt-in beside everything above: bbocr_host_jpeg_plan keeps
+ * refusing them (reason BBOCR_JPEG_SOF) and every call above keeps answering BBOCR_ERR_ARG for them.  A plan of their own describes the
+ * scan script; bbocr_jpeg_decode_progressive takes the files it supports.  Taken: SOF2, 8 bit, Huffman, 1 component or 3 components under
+ * bbocr_host_jpeg_plan's colour rule, sampled 4:2:0, 4:4:4, 4:2:2 or 4:4:0, at most BBOCR_JPEG_MAX_SCANS scans whose script is valid by
+ * T.81 G.1.1 -- a DC scan has Ss = Se = 0 and may interleave, an AC scan holds one component with 1 <= Ss <= Se <= 63 behind that
+ * component's first DC scan, a coefficient's first scan has Ah = 0, a refinement has Ah = the Al before it and Al = Ah - 1 -- and COMPLETE:
+ * every coefficient 0 .. 63 of every component reaches Al = 0 (libjpeg-turbo smooths between the blocks of a file whose script is not,
+ * so its pixels are not what the coefficients alone give).  Reasons: the ones above, where BBOCR_JPEG_SOF now means "not SOF2" -- a
+ * baseline file is refused by THIS plan, it has bbocr_host_jpeg_plan -- and BBOCR_JPEG_MULTISCAN means a DQT behind the first SOS or a scan
+ * header that names a component the frame does not have (or one twice, or out of frame order); BBOCR_JPEG_SCRIPT; BBOCR_JPEG_SCANS.
+ * A non-interleaved scan walks its component's own block raster, ceil(ceil(width * h / hmax) / 8) blocks a row, and its restart
+ * interval counts those blocks; an interleaved one counts MCUs. */
+#define BBOCR_JPEG_MAX_SCANS 64
+typedef struct bbocr_jpeg_scan {
+    int components;              /* 1 .. 3 components in this scan; more than one: interleaved (DC scans only) */
+    int component[3];            /* their indices in the frame, ascending */
+    int dc_table[3], ac_table[3]; /* per scan component: the table ids (0 .. 3) its header names; the decoder keeps the tables' contents as they
+                                  * stand at this SOS, since a DHT between scans may redefine an id */
+    int ss, se, ah, al;
+    int restart_interval;        /* in force at this SOS (a DRI may sit between scans): MCUs or blocks, 0 = none */
+    int segments;                /* restart segments of this scan */
+    long long offset;            /* first entropy-coded byte */
+    long long bytes;             /* up to the marker that ends the scan (stuffing and restart markers included) */
+} bbocr_jpeg_scan;
+typedef struct bbocr_jpeg_progressive_plan {
+    int width, height, components;
+    int sampling[3][2];          /* (h, v) per component */
+    int mcu_cols, mcu_rows;
+    int chroma;                  /* 0: 4:2:0 or one component; BBOCR_JPEG_CHROMA_* otherwise */
+    int orientation;             /* bbocr_jpeg_plan's rule */
+    int supported;               /* 1: bbocr_jpeg_decode_progressive takes the file */
+    int reason;                  /* BBOCR_JPEG_* */
+    int n_scans;                 /* scans described below: all of a supported file's, those read before the refusal otherwise */
+    int reserved;
+    bbocr_jpeg_scan scans[BBOCR_JPEG_MAX_SCANS];
+} bbocr_jpeg_progressive_plan;
+/* host only, no GPU: one linear pass over the markers and the scans' FF bytes; no entropy bit is decoded */
+int bbocr_host_jpeg_progressive_plan(const uint8_t* file, size_t bytes, bbocr_jpeg_progressive_plan* plan);
+/* bbocr_jpeg_decode_scales -- same arguments, stream, one-batch-at-a-time contract, status codes and outputs -- that takes every file that
+ * call takes AND the progressive files the plan above supports, so a mixed batch is one call.  A progressive file's scans run into the
+ * zeroed coefficient buffer in file order wherever one builds on another: a scan waits for the earlier scans that hold one of its
+ * components and overlap its band, the others of the whole batch share a set of launches (libjpeg's ten-scan script: three).  DC first
+ * and AC first scans are cut into subsequences and decoded speculatively with self-synchronisation, like a baseline scan (an
+ * end-of-band run counts its blocks at its symbol); a DC refinement is a parallel pass over its blocks; an AC refinement cannot be entered
+ * in the middle and is decoded by one wavefront per (file, scan, restart segment), the corrections of a block applied by its lanes.  So a
+ * batch fills the card, and one file without restart markers, a few serial wavefronts in its refinement scans, is slower than on the
+ * host.  status[k] = BBOCR_ERR_DATA: in some scan a bit pattern without a code, a
+ * refinement symbol of another size than 1, a segment that ends before or behind the blocks it promises, or an end-of-band run that
+ * leaves it.  The IDCT and output stages are those of every other file. */
+int bbocr_jpeg_decode_progressive(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, int layout,
+                                  const bbocr_jpeg_output* outputs, int n_outputs, int* status);
+/* intermediates of ONE file that bbocr_jpeg_decode_progressive takes (parity tests), numbered like bbocr_op_jpeg_stage's: stage 1 = the
+ * quantised coefficients after the first n_scans scans (0 = all; a baseline file has one), int16 [blocks][64] in natural order, blocks
+ * in MCU order -- a block outside its component's raster holds what the interleaved scans gave it; 2 = the component planes; 3 = the pixels,
+ * tight.  subseq_bits as there: it cuts the scan of a baseline file and the DC first and AC first scans of a progressive one. */
+int bbocr_op_jpeg_progressive_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int n_scans, int subseq_bits, void* dev_dst,
+                                    size_t dst_bytes, int* file_status);
 /* host only: the planes of a decode at scale 2, 4 or 8 of a file the decoder takes (plan->supported or plan->chroma), per component
  * comps[0 .. components): the block's edge, the plane in whole MCUs as the device keeps it, the valid extent inside it (what libjpeg
  * calls downsampled_height x downsampled_width) and how the output stage brings the component to the output's size.  comps[components .. 3)

@@ -1,7 +1,7 @@
 """Baseline JPEG decoding on the device (csrc/jpegdec.hip) against the host's libjpeg-turbo (Pillow), on one box.
 
     python tools/jpeg_decode_bench.py [--reps 10] [--extract 1024] [--photos 16] [--out profiles/bench_jpeg_decode.jsonl] [--device-only]
-                                      [--label NAME]
+                                      [--label NAME] [--progressive-only]
 
 Prints JSON lines and appends them to --out; `--label` names the build in every line (A/B runs of two libraries on one machine:
 BBOCR_LIB_PATH selects the library):
@@ -12,6 +12,10 @@ BBOCR_LIB_PATH selects the library):
   * decode64_444 / decode64_422 / decode64_440   the 64-page batch saved 4:4:4 and 4:2:2, and 64 copies of one page's lossless transposition
                 (4:4:0, built by tests/jpeg_chroma_ref.make_440: Pillow writes no such file) -- the files ``device_decode="chroma"`` adds --
                 one bbocr_jpeg_decode call against what they cost without it: decode_file_ycc on one core plus the upload of the triples;
+  * decode64_prog420 / decode64_prog444 / decode1_prog / photo_prog   the files ``device_decode="progressive"`` adds: the 64-page batch saved
+                progressive as 4:2:0 and as 4:4:4, one such page alone, and tests/golden/photos/IMG_9684.JPG saved progressive -- one
+                bbocr_jpeg_decode_progressive call against Pillow's decode on one core plus the upload of the triples, the two alternated
+                in one process (best of --reps each); --progressive-only runs these rows alone;
   * extract     extract_texts over --extract pages (extractor_bench.py's page set) with device_decode off / on, alternating, each twice;
   * photos      extract_texts(device_thumbnail=True) over --photos 5712x4284 pages with device_decode off / on.
 --device-only: the decode64 and photo device legs alone (for a separate `rocprofv3 --kernel-trace --stats` run).
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_jpeg_decode.jsonl"))
     ap.add_argument("--device-only", action="store_true")
     ap.add_argument("--label", default="in-tree")
+    ap.add_argument("--progressive-only", action="store_true")
     a = ap.parse_args()
     import torch
     from PIL import Image
@@ -76,6 +81,47 @@ def main():
             assert decode_file_ycc(d, padded=True) is not None
         return (time.perf_counter() - t) * 1e3
 
+    def host_upload_ms(datas):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        reader._to_dev([decode_file_ycc(d, padded=True) for d in datas])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    def progressive_rows():
+        imgs = [Image.fromarray(synth.page(1234 + i)[0]) for i in range(64)]
+        golden = Image.open(os.path.join(ROOT, "tests", "golden", "photos", "IMG_9684.JPG"))
+        p420 = [jpeg(im, quality=90, progressive=True) for im in imgs]
+        legs = (("decode64_prog420", p420), ("decode64_prog444", [jpeg(im, quality=90, progressive=True, subsampling=0) for im in imgs]),
+                ("decode1_prog", p420[:1]), ("photo_prog", [jpeg(golden, quality=90, progressive=True)]))
+        for name, datas in legs:
+            batch = [jpeg_page(d, chroma=True, progressive=True) for d in datas]
+            assert all(p is not None and p.progressive for p in batch)
+            _, status = reader.decode_jpeg_batch(batch, padded=True)             # warm-up: buffers grow here
+            assert not any(status)
+            dev, host = [], []
+            for _ in range(a.reps):                                              # alternated: both see the same machine
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                reader.decode_jpeg_batch(batch, padded=True)
+                dev.append((time.perf_counter() - t) * 1e3)
+                host.append(host_upload_ms(datas))
+            emit(leg=name, files=len(datas), kbytes_per_file=round(sum(map(len, datas)) / len(datas) / 1024, 1), reps=a.reps,
+                 size="%dx%d" % (batch[0].shape[1], batch[0].shape[0]), device_ms_per_page=round(min(dev) / len(datas), 3),
+                 device_ms_per_page_mean=round(sum(dev) / len(dev) / len(datas), 3),
+                 host_decode_upload_ms_per_page=round(min(host) / len(datas), 3),
+                 host_decode_upload_ms_per_page_mean=round(sum(host) / len(host) / len(datas), 3))
+
+    def write_rows():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "a") as f:
+            for row in rows:
+                f.write(json.dumps(row) + "\n")
+
+    if a.progressive_only:
+        progressive_rows()
+        write_rows()
+        return
     for name, datas in (("decode64", pages), ("photo", [photo])):
         row = dict(leg=name, files=len(datas), kbytes_per_file=round(sum(map(len, datas)) / len(datas) / 1024, 1),
                    device_ms_per_page=round(device_ms(datas) / len(datas), 3))
@@ -86,13 +132,6 @@ def main():
                 jpeg_plan(d)
             row["plan_ms_per_file"] = round((time.perf_counter() - t) * 1e3 / len(datas), 4)
         emit(**row)
-    def host_upload_ms(datas):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        reader._to_dev([decode_file_ycc(d, padded=True) for d in datas])
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t) * 1e3
-
     if not a.device_only:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from jpeg_chroma_ref import make_440
@@ -106,6 +145,7 @@ def main():
             emit(leg=name, files=len(datas), kbytes_per_file=round(sum(map(len, datas)) / len(datas) / 1024, 1),
                  device_ms_per_page=round(device_ms(datas) / len(datas), 3),
                  host_decode_upload_ms_per_page=round(min(host_upload_ms(datas) for _ in range(3)) / len(datas), 3))
+        progressive_rows()
         with tempfile.TemporaryDirectory() as d:
             if a.extract > 0:
                 uniq = [Image.fromarray(synth.page(1234 + i)[0]) for i in range(8)]
@@ -138,10 +178,7 @@ def main():
                     ref = ref or texts
                     emit(leg="photos", device_thumbnail=True, device_decode=dev, pages=len(paths), seconds=round(dt, 2),
                          pages_per_s=round(len(paths) / dt, 2), texts_equal_first_run=texts == ref)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "a") as f:
-        for row in rows:
-            f.write(json.dumps(row) + "\n")
+    write_rows()
 
 
 if __name__ == "__main__":
