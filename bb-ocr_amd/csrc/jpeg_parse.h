@@ -1,7 +1,8 @@
-// Host-side JPEG parsing that more than one program runs: what jpegdec.cpp's baseline walk and the progressive walk share (EXIF
-// orientation, Huffman table specs and their derived form, the removal of stuffing), and the whole host side of a progressive file --
-// bbocr_host_jpeg_progressive_plan's walk over the markers (prog_parse) and the tables of one scan as jpegprog.h's jp_decode_segment
-// reads them (prog_fill_scan).  No GPU call: tools/jpegprog_hostcheck.cpp builds it with the sanitisers.
+// Host-side JPEG parsing, the whole of it: EXIF orientation, Huffman table specs and their derived form, the removal of stuffing; one
+// marker walk in pieces (next_segment, take_header, check_frame, take_quant, frame_mcus) under the two walks that differ in their SOS
+// handling -- bbocr_host_jpeg_plan's (jpeg_parse) and bbocr_host_jpeg_progressive_plan's (prog_parse); and the tables of a scan as the
+// device reads them (cut_scan: unstuffed segments cut into subsequences; prog_fill_scan: a progressive scan for jpegprog.h's
+// jp_decode_segment).  The zig-zag order is jpeg_spec.h's JPEG_ZZ.  No GPU call: tools/jpegprog_hostcheck.cpp builds it with the sanitisers.
 #pragma once
 #include "../../include/bbocr.h"
 #include <algorithm>
@@ -11,10 +12,6 @@
 #include "jpegprog.h"
 
 namespace jpeg_host {
-
-constexpr unsigned char kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 struct HuffSpec { bool have = false; unsigned char counts[16] = {0}; unsigned char vals[256] = {0}; int total = 0; };
 
@@ -89,15 +86,15 @@ inline bool derive_table(const HuffSpec& h, JpegHuff& t) {
     return true;
 }
 
-// one DHT segment's tables into huff[class][id], ids below max_id; false: malformed
-template <int IDS> bool read_dht(const uint8_t* s, size_t sl, HuffSpec (&huff)[2][IDS]) {
+// one DHT segment's tables into huff[class][id], ids below `ids`; false: malformed
+inline bool read_dht(const uint8_t* s, size_t sl, HuffSpec (&huff)[2][4], int ids) {
     size_t q = 0;
     while (q < sl) {
         if (q + 17 > sl) return false;
         const int tc = s[q] >> 4, th = s[q] & 15;
         int tot = 0;
         for (int i = 0; i < 16; ++i) tot += s[q + 1 + i];
-        if (tc > 1 || th >= IDS || tot > 256 || q + 17 + tot > sl) return false;
+        if (tc > 1 || th >= ids || tot > 256 || q + 17 + tot > sl) return false;
         HuffSpec& h = huff[tc][th];
         h.have = true;
         h.total = tot;
@@ -155,6 +152,175 @@ inline int scan_segments(const uint8_t* f, size_t n, size_t from, bool want_segs
     return BBOCR_JPEG_NO_EOI;
 }
 
+// ---- the marker walk: what bbocr_host_jpeg_plan's (jpeg_walk) and bbocr_host_jpeg_progressive_plan's (prog_walk) share.  Both keep
+// the frame in a bbocr_jpeg_plan -- for a progressive file a plan without a scan, which is how the stages behind the coefficients see it.
+struct JpegHeader {                                   // what the marker segments have said so far
+    unsigned short qt[4][64];                         // natural order
+    bool have_qt[4] = {false, false, false, false};
+    HuffSpec huff[2][4];                              // [class][id]
+    bool have_sof = false, jfif = false;
+    int adobe = -1, comp_id[4] = {0}, comp_tq[4] = {0}, dri = 0;
+};
+struct JpegParsed {                                   // a baseline file, or the frame of a progressive one
+    bbocr_jpeg_plan plan;
+    unsigned short quant[3][64] = {};                 // per component, natural order
+    HuffSpec huff[2][2];                              // [class][id]
+    int tab_dc[3] = {0, 0, 0}, tab_ac[3] = {0, 0, 0};
+    std::vector<std::pair<size_t, size_t>> segs;      // byte ranges of the restart segments in the file (stuffing included)
+};
+
+// The marker segment at or behind p: fill bytes, SOI, RSTn and TEM are passed over.  SEG_OK: marker g.m, payload g.s[g.sl], the next
+// marker at g.next; SEG_EOI; SEG_LOST: no marker where one must stand; SEG_CUT: the segment runs off the file.
+struct Segment { int m; const uint8_t* s; size_t sl, next; };
+enum { SEG_OK = 0, SEG_EOI, SEG_LOST, SEG_CUT };
+inline int next_segment(const uint8_t* f, size_t n, size_t p, Segment& g) {
+    for (;;) {
+        if (p + 2 > n || f[p] != 0xFF) return SEG_LOST;
+        if (f[p + 1] == 0xFF) { ++p; continue; }
+        g.m = f[p + 1];
+        p += 2;
+        if (g.m == 0xD8 || (g.m >= 0xD0 && g.m <= 0xD7) || g.m == 0x01) continue;
+        if (g.m == 0xD9) return SEG_EOI;
+        if (p + 2 > n) return SEG_CUT;
+        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
+        if (L < 2 || p + L > n) return SEG_CUT;
+        g.s = f + p + 2;
+        g.sl = L - 2;
+        g.next = p + L;
+        return SEG_OK;
+    }
+}
+
+// A segment of the headers: the frame header `sof` into the frame (every other SOFn is BBOCR_JPEG_SOF: the other walk's, extended,
+// lossless, arithmetic), DHT with ids below dht_ids, DQT, DRI, JFIF and Adobe into h.  Any other segment is passed over.
+inline int take_header(const Segment& g, int sof, int dht_ids, JpegHeader& h, bbocr_jpeg_plan& fr) {
+    const uint8_t* s = g.s;
+    const size_t sl = g.sl;
+    const int m = g.m;
+    if (m == sof) {
+        if (h.have_sof || sl < 6) return BBOCR_JPEG_SOF;
+        if (s[0] != 8) return BBOCR_JPEG_PRECISION;
+        fr.height = (s[1] << 8) | s[2];
+        fr.width = (s[3] << 8) | s[4];
+        fr.components = s[5];
+        if (fr.height == 0 || fr.width == 0 || sl < 6 + 3 * (size_t)fr.components) return BBOCR_JPEG_SOF;
+        for (int i = 0; i < fr.components && i < 4; ++i) {
+            h.comp_id[i] = s[6 + 3 * i];
+            if (i < 3) { fr.sampling[i][0] = s[7 + 3 * i] >> 4; fr.sampling[i][1] = s[7 + 3 * i] & 15; }
+            h.comp_tq[i] = s[8 + 3 * i];
+        }
+        h.have_sof = true;
+    } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
+        return BBOCR_JPEG_SOF;
+    } else if (m == 0xC4) {
+        if (!read_dht(s, sl, h.huff, dht_ids)) return BBOCR_JPEG_TABLES;
+    } else if (m == 0xDB) {
+        size_t q = 0;
+        while (q < sl) {
+            if (s[q] >> 4) return BBOCR_JPEG_PRECISION;
+            const int id = s[q] & 15;
+            if (id > 3 || q + 65 > sl) return BBOCR_JPEG_TABLES;
+            for (int k = 0; k < 64; ++k) h.qt[id][JPEG_ZZ[k]] = s[q + 1 + k];
+            h.have_qt[id] = true;
+            q += 65;
+        }
+    } else if (m == 0xDD) {
+        if (sl < 2) return BBOCR_JPEG_TRUNCATED;
+        h.dri = (s[0] << 8) | s[1];
+    } else if (m == 0xE0 && sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) {
+        h.jfif = true;
+    } else if (m == 0xEE && sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
+        h.adobe = s[11];
+    }
+    return BBOCR_JPEG_OK;
+}
+
+// The frame rules at the first SOS: 1 or 3 components, YCbCr, 4:2:0 or a chroma class (cls; 0 for 4:2:0 and for one component)
+inline int check_frame(const JpegHeader& h, const bbocr_jpeg_plan& fr, int& cls) {
+    cls = 0;
+    if (!h.have_sof) return BBOCR_JPEG_SOF;
+    if (fr.components != 1 && fr.components != 3) return BBOCR_JPEG_COMPONENTS;
+    if (fr.components == 1) return BBOCR_JPEG_OK;
+    if (!h.jfif && h.adobe != 1) return BBOCR_JPEG_COLORSPACE;
+    const int(&s)[3][2] = fr.sampling;
+    if (s[0][0] == 2 && s[0][1] == 2 && s[1][0] == 1 && s[1][1] == 1 && s[2][0] == 1 && s[2][1] == 1) return BBOCR_JPEG_OK;
+    cls = chroma_class_of(s);
+    return cls ? BBOCR_JPEG_OK : BBOCR_JPEG_SAMPLING;
+}
+// component i's quantisation table into quant[i]; false: the frame names one no DQT brought
+inline bool take_quant(const JpegHeader& h, int i, unsigned short (&quant)[3][64]) {
+    if (h.comp_tq[i] > 3 || !h.have_qt[h.comp_tq[i]]) return false;
+    std::memcpy(quant[i], h.qt[h.comp_tq[i]], sizeof h.qt[0]);
+    return true;
+}
+inline void frame_mcus(bbocr_jpeg_plan& fr) {
+    const int mcu_w = fr.components == 3 ? 8 * fr.sampling[0][0] : 8, mcu_h = fr.components == 3 ? 8 * fr.sampling[0][1] : 8;
+    fr.mcu_cols = (fr.width + mcu_w - 1) / mcu_w;
+    fr.mcu_rows = (fr.height + mcu_h - 1) / mcu_h;
+}
+
+// ---- baseline files.  jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.
+// Returns the reason; `cls` receives the chroma class of a file whose sampling alone is outside bbocr_jpeg_plan::supported, and the walk
+// goes on as for a supported file.
+inline int jpeg_walk(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs, int& cls) {
+    bbocr_jpeg_plan& pl = out.plan;
+    std::memset(&pl, 0, sizeof pl);
+    if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
+    pl.orientation = exif_orientation(f, n);                     // of its own walk: malformed EXIF never changes what follows
+    JpegHeader h;
+    Segment g;
+    for (size_t p = 2;; p = g.next) {
+        if (next_segment(f, n, p, g) != SEG_OK) return BBOCR_JPEG_TRUNCATED;     // EOI before SOS and lost marker sync too
+        if (g.m == 0xDA) break;
+        const int r = take_header(g, 0xC0, 2, h, pl);
+        if (r != BBOCR_JPEG_OK) return r;
+    }
+    const int r = check_frame(h, pl, cls);
+    if (r != BBOCR_JPEG_OK) return r;
+    const int nc = pl.components;
+    if (g.sl < 1 || g.s[0] != nc || g.sl < 1 + 2 * (size_t)nc + 3) return BBOCR_JPEG_MULTISCAN;
+    for (int i = 0; i < nc; ++i) {
+        if (g.s[1 + 2 * i] != h.comp_id[i]) return BBOCR_JPEG_MULTISCAN;
+        const int td = g.s[2 + 2 * i] >> 4, ta = g.s[2 + 2 * i] & 15;
+        if (td > 1 || ta > 1 || !h.huff[0][td].have || !h.huff[1][ta].have || !take_quant(h, i, out.quant)) return BBOCR_JPEG_TABLES;
+        out.tab_dc[i] = td;
+        out.tab_ac[i] = 2 + ta;
+    }
+    for (int c = 0; c < 2; ++c)
+        for (int id = 0; id < 2; ++id) out.huff[c][id] = h.huff[c][id];
+    frame_mcus(pl);
+    pl.restart_interval = h.dri;
+    pl.scan_offset = (long long)g.next;
+    const long long nmcu = (long long)pl.mcu_cols * pl.mcu_rows, ri = h.dri ? h.dri : nmcu;
+    size_t end = 0;
+    int nseg = 0;
+    const int walked = scan_segments(f, n, g.next, want_segs, out.segs, nseg, end);
+    if (walked != BBOCR_JPEG_OK) return walked;
+    if (f[end + 1] != 0xD9) return BBOCR_JPEG_MULTISCAN;
+    if ((long long)nseg != (nmcu + ri - 1) / ri) return BBOCR_JPEG_RESTART;
+    pl.segments = nseg;
+    pl.scan_bytes = (long long)(end - g.next);
+    return BBOCR_JPEG_OK;
+}
+
+// The plan of a file and its reason.  A file of a chroma class that passed every later check keeps reason BBOCR_JPEG_SAMPLING and
+// supported 0, with `chroma` set and the whole plan filled; one that failed a later check is refused as before, nothing behind the
+// sampling test filled.
+inline int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
+    int cls = 0;
+    const int reason = jpeg_walk(f, n, out, want_segs, cls);
+    bbocr_jpeg_plan& pl = out.plan;
+    pl.supported = reason == BBOCR_JPEG_OK && !cls;
+    if (!cls) return reason;
+    if (reason == BBOCR_JPEG_OK) {
+        pl.chroma = cls;
+    } else {
+        pl.restart_interval = pl.mcu_cols = pl.mcu_rows = pl.segments = 0;
+        pl.scan_offset = pl.scan_bytes = 0;
+    }
+    return BBOCR_JPEG_SAMPLING;
+}
+
 // ---- progressive files
 struct ProgScan {
     HuffSpec tab[3];                                  // per scan component: its DC (Ss = 0) or AC table as it stood at this SOS
@@ -162,22 +328,22 @@ struct ProgScan {
 };
 struct ProgParsed {
     bbocr_jpeg_progressive_plan plan;
-    unsigned short quant[3][64];                      // per component, natural order
+    JpegParsed frame;                                 // the frame, its quantisation tables and `supported` as jpeg_parse would give them
     std::vector<ProgScan> scans;
 };
 
 // component c's own block raster (what a non-interleaved scan walks), and its blocks across / down an MCU
-inline void prog_comp_raster(const bbocr_jpeg_progressive_plan& pl, int c, int& bw, int& bh, int& ch, int& cv) {
-    const int hmax = pl.components == 3 ? pl.sampling[0][0] : 1, vmax = pl.components == 3 ? pl.sampling[0][1] : 1;
-    ch = pl.components == 3 ? pl.sampling[c][0] : 1;
-    cv = pl.components == 3 ? pl.sampling[c][1] : 1;
-    bw = ((pl.width * ch + hmax - 1) / hmax + 7) / 8;
-    bh = ((pl.height * cv + vmax - 1) / vmax + 7) / 8;
+inline void prog_comp_raster(const bbocr_jpeg_plan& fr, int c, int& bw, int& bh, int& ch, int& cv) {
+    const int hmax = fr.components == 3 ? fr.sampling[0][0] : 1, vmax = fr.components == 3 ? fr.sampling[0][1] : 1;
+    ch = fr.components == 3 ? fr.sampling[c][0] : 1;
+    cv = fr.components == 3 ? fr.sampling[c][1] : 1;
+    bw = ((fr.width * ch + hmax - 1) / hmax + 7) / 8;
+    bh = ((fr.height * cv + vmax - 1) / vmax + 7) / 8;
 }
-inline int prog_scan_units(const bbocr_jpeg_progressive_plan& pl, const bbocr_jpeg_scan& sc) {
-    if (sc.components > 1) return pl.mcu_cols * pl.mcu_rows;
+inline int prog_scan_units(const bbocr_jpeg_plan& fr, const bbocr_jpeg_scan& sc) {
+    if (sc.components > 1) return fr.mcu_cols * fr.mcu_rows;
     int bw, bh, ch, cv;
-    prog_comp_raster(pl, sc.component[0], bw, bh, ch, cv);
+    prog_comp_raster(fr, sc.component[0], bw, bh, ch, cv);
     return bw * bh;
 }
 
@@ -185,180 +351,147 @@ inline int prog_scan_units(const bbocr_jpeg_progressive_plan& pl, const bbocr_jp
 // up to EOI.  Returns the reason; plan.n_scans scans are described when it returns, refused or not.
 inline int prog_walk(const uint8_t* f, size_t n, ProgParsed& out, bool want_segs) {
     bbocr_jpeg_progressive_plan& pl = out.plan;
+    bbocr_jpeg_plan& fr = out.frame.plan;
     std::memset(&pl, 0, sizeof pl);
+    std::memset(&fr, 0, sizeof fr);
     out.scans.clear();
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
-    pl.orientation = exif_orientation(f, n);
-    size_t p = 2;
-    unsigned short qt[4][64];
-    bool have_qt[4] = {false, false, false, false};
-    HuffSpec huff[2][4];
-    bool have_sof = false, jfif = false;
-    int adobe = -1, comp_id[4] = {0}, comp_tq[4] = {0}, dri = 0;
+    fr.orientation = exif_orientation(f, n);
+    JpegHeader h;
+    Segment g;
     signed char bits[3][64];                                          // the Al a coefficient has reached, -1: not sent yet
     std::memset(bits, -1, sizeof bits);
-    for (;;) {
-        for (;;) {
-            if (p + 2 > n || f[p] != 0xFF) return pl.n_scans ? BBOCR_JPEG_NO_EOI : BBOCR_JPEG_TRUNCATED;
-            if (f[p + 1] == 0xFF) { ++p; continue; }
-            break;
-        }
-        const int m = f[p + 1];
-        p += 2;
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xD9) break;
-        if (p + 2 > n) return BBOCR_JPEG_TRUNCATED;
-        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
-        if (L < 2 || p + L > n) return BBOCR_JPEG_TRUNCATED;
-        const uint8_t* s = f + p + 2;
-        const size_t sl = L - 2;
-        if (m == 0xC2) {
-            if (have_sof || sl < 6) return BBOCR_JPEG_SOF;
-            if (s[0] != 8) return BBOCR_JPEG_PRECISION;
-            pl.height = (s[1] << 8) | s[2];
-            pl.width = (s[3] << 8) | s[4];
-            pl.components = s[5];
-            if (pl.height == 0 || pl.width == 0 || sl < 6 + 3 * (size_t)pl.components) return BBOCR_JPEG_SOF;
-            for (int i = 0; i < pl.components && i < 4; ++i) {
-                comp_id[i] = s[6 + 3 * i];
-                if (i < 3) { pl.sampling[i][0] = s[7 + 3 * i] >> 4; pl.sampling[i][1] = s[7 + 3 * i] & 15; }
-                comp_tq[i] = s[8 + 3 * i];
-            }
-            have_sof = true;
-        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
-            return BBOCR_JPEG_SOF;                           // baseline (bbocr_host_jpeg_plan's), extended, lossless, arithmetic
-        } else if (m == 0xC4) {
-            if (!read_dht(s, sl, huff)) return BBOCR_JPEG_TABLES;
-        } else if (m == 0xDB) {
-            if (pl.n_scans) return BBOCR_JPEG_MULTISCAN;     // the IDCT stage dequantises once, behind the last scan
-            size_t q = 0;
-            while (q < sl) {
-                if (s[q] >> 4) return BBOCR_JPEG_PRECISION;
-                const int id = s[q] & 15;
-                if (id > 3 || q + 65 > sl) return BBOCR_JPEG_TABLES;
-                for (int k = 0; k < 64; ++k) qt[id][kZigzag[k]] = s[q + 1 + k];
-                have_qt[id] = true;
-                q += 65;
-            }
-        } else if (m == 0xDD) {
-            if (sl < 2) return BBOCR_JPEG_TRUNCATED;
-            dri = (s[0] << 8) | s[1];
-        } else if (m == 0xE0 && sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) {
-            jfif = true;
-        } else if (m == 0xEE && sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
-            adobe = s[11];
-        } else if (m == 0xDA) {
-            if (!have_sof) return BBOCR_JPEG_SOF;
-            const int nc = pl.components;
-            if (pl.n_scans == 0) {                           // the frame, by the rules of the baseline walk
-                if (nc != 1 && nc != 3) return BBOCR_JPEG_COMPONENTS;
-                if (nc == 3) {
-                    if (!jfif && adobe != 1) return BBOCR_JPEG_COLORSPACE;
-                    const bool s420 = pl.sampling[0][0] == 2 && pl.sampling[0][1] == 2 && pl.sampling[1][0] == 1 && pl.sampling[1][1] == 1 &&
-                                      pl.sampling[2][0] == 1 && pl.sampling[2][1] == 1;
-                    pl.chroma = s420 ? 0 : chroma_class_of(pl.sampling);
-                    if (!s420 && !pl.chroma) return BBOCR_JPEG_SAMPLING;
-                }
-                for (int i = 0; i < nc; ++i) {
-                    if (comp_tq[i] > 3 || !have_qt[comp_tq[i]]) return BBOCR_JPEG_TABLES;
-                    std::memcpy(out.quant[i], qt[comp_tq[i]], sizeof qt[0]);
-                }
-                const int mcu_w = nc == 3 ? 8 * pl.sampling[0][0] : 8, mcu_h = nc == 3 ? 8 * pl.sampling[0][1] : 8;
-                pl.mcu_cols = (pl.width + mcu_w - 1) / mcu_w;
-                pl.mcu_rows = (pl.height + mcu_h - 1) / mcu_h;
-            }
-            if (pl.n_scans == BBOCR_JPEG_MAX_SCANS) return BBOCR_JPEG_SCANS;
-            bbocr_jpeg_scan sc{};
-            ProgScan ps;
-            const int ns = sl >= 1 ? s[0] : 0;
-            if (ns < 1 || ns > 3 || ns > nc || sl < 1 + 2 * (size_t)ns + 3) return BBOCR_JPEG_MULTISCAN;
-            sc.components = ns;
-            for (int i = 0; i < ns; ++i) {
-                int c = -1;
-                for (int k = 0; k < nc; ++k)
-                    if (comp_id[k] == s[1 + 2 * i]) { c = k; break; }
-                if (c < 0 || (i > 0 && c <= sc.component[i - 1])) return BBOCR_JPEG_MULTISCAN;
-                sc.component[i] = c;
-                sc.dc_table[i] = s[2 + 2 * i] >> 4;
-                sc.ac_table[i] = s[2 + 2 * i] & 15;
-            }
-            sc.ss = s[1 + 2 * ns];
-            sc.se = s[2 + 2 * ns];
-            sc.ah = s[3 + 2 * ns] >> 4;
-            sc.al = s[3 + 2 * ns] & 15;
-            if (sc.ss == 0 ? sc.se != 0 : (ns != 1 || sc.se < sc.ss || sc.se > 63)) return BBOCR_JPEG_SCRIPT;
-            if (sc.ah > 13 || sc.al > 13) return BBOCR_JPEG_SCRIPT;
-            for (int i = 0; i < ns; ++i) {
-                signed char* b = bits[sc.component[i]];
-                if (sc.ss > 0 && b[0] < 0) return BBOCR_JPEG_SCRIPT;                      // AC before the component's first DC scan
-                for (int k = sc.ss; k <= sc.se; ++k) {
-                    if (b[k] < 0 ? sc.ah != 0 : (sc.ah != b[k] || sc.al != sc.ah - 1)) return BBOCR_JPEG_SCRIPT;
-                    b[k] = (signed char)sc.al;
-                }
-                if (!(sc.ss == 0 && sc.ah > 0)) {                                          // a DC refinement reads raw bits
-                    const int id = sc.ss == 0 ? sc.dc_table[i] : sc.ac_table[i];
-                    JpegHuff probe;
-                    if (id > 3 || !huff[sc.ss == 0 ? 0 : 1][id].have || !derive_table(huff[sc.ss == 0 ? 0 : 1][id], probe)) return BBOCR_JPEG_TABLES;
-                    ps.tab[i] = huff[sc.ss == 0 ? 0 : 1][id];
-                }
-            }
-            sc.restart_interval = dri;
-            sc.offset = (long long)(p + L);
-            const long long units = prog_scan_units(pl, sc), ri = dri ? dri : units;
-            int nseg = 0;
-            size_t end = 0;
-            const int r = scan_segments(f, n, p + L, want_segs, ps.segs, nseg, end);
+    for (size_t p = 2;; p = g.next) {
+        const int seg = next_segment(f, n, p, g);
+        if (seg == SEG_EOI) break;
+        if (seg != SEG_OK) return seg == SEG_LOST && pl.n_scans ? BBOCR_JPEG_NO_EOI : BBOCR_JPEG_TRUNCATED;
+        if (g.m != 0xDA) {
+            if (g.m == 0xDB && pl.n_scans) return BBOCR_JPEG_MULTISCAN;     // the IDCT stage dequantises once, behind the last scan
+            const int r = take_header(g, 0xC2, 4, h, fr);
             if (r != BBOCR_JPEG_OK) return r;
-            if ((long long)nseg != (units + ri - 1) / ri) return BBOCR_JPEG_RESTART;
-            sc.segments = nseg;
-            sc.bytes = (long long)end - sc.offset;
-            pl.scans[pl.n_scans++] = sc;
-            out.scans.push_back(std::move(ps));
-            p = end;
             continue;
         }
-        p += L;
+        const uint8_t* s = g.s;
+        const size_t sl = g.sl;
+        const int nc = fr.components;
+        if (pl.n_scans == 0) {                               // the frame, by the rules of the baseline walk
+            const int r = check_frame(h, fr, fr.chroma);
+            if (r != BBOCR_JPEG_OK) return r;
+            for (int i = 0; i < nc; ++i)
+                if (!take_quant(h, i, out.frame.quant)) return BBOCR_JPEG_TABLES;
+            frame_mcus(fr);
+        }
+        if (pl.n_scans == BBOCR_JPEG_MAX_SCANS) return BBOCR_JPEG_SCANS;
+        bbocr_jpeg_scan sc{};
+        ProgScan ps;
+        const int ns = sl >= 1 ? s[0] : 0;
+        if (ns < 1 || ns > 3 || ns > nc || sl < 1 + 2 * (size_t)ns + 3) return BBOCR_JPEG_MULTISCAN;
+        sc.components = ns;
+        for (int i = 0; i < ns; ++i) {
+            int c = -1;
+            for (int k = 0; k < nc; ++k)
+                if (h.comp_id[k] == s[1 + 2 * i]) { c = k; break; }
+            if (c < 0 || (i > 0 && c <= sc.component[i - 1])) return BBOCR_JPEG_MULTISCAN;
+            sc.component[i] = c;
+            sc.dc_table[i] = s[2 + 2 * i] >> 4;
+            sc.ac_table[i] = s[2 + 2 * i] & 15;
+        }
+        sc.ss = s[1 + 2 * ns];
+        sc.se = s[2 + 2 * ns];
+        sc.ah = s[3 + 2 * ns] >> 4;
+        sc.al = s[3 + 2 * ns] & 15;
+        if (sc.ss == 0 ? sc.se != 0 : (ns != 1 || sc.se < sc.ss || sc.se > 63)) return BBOCR_JPEG_SCRIPT;
+        if (sc.ah > 13 || sc.al > 13) return BBOCR_JPEG_SCRIPT;
+        for (int i = 0; i < ns; ++i) {
+            signed char* b = bits[sc.component[i]];
+            if (sc.ss > 0 && b[0] < 0) return BBOCR_JPEG_SCRIPT;                      // AC before the component's first DC scan
+            for (int k = sc.ss; k <= sc.se; ++k) {
+                if (b[k] < 0 ? sc.ah != 0 : (sc.ah != b[k] || sc.al != sc.ah - 1)) return BBOCR_JPEG_SCRIPT;
+                b[k] = (signed char)sc.al;
+            }
+            if (!(sc.ss == 0 && sc.ah > 0)) {                                          // a DC refinement reads raw bits
+                const int id = sc.ss == 0 ? sc.dc_table[i] : sc.ac_table[i];
+                JpegHuff probe;
+                if (id > 3 || !h.huff[sc.ss == 0 ? 0 : 1][id].have || !derive_table(h.huff[sc.ss == 0 ? 0 : 1][id], probe)) return BBOCR_JPEG_TABLES;
+                ps.tab[i] = h.huff[sc.ss == 0 ? 0 : 1][id];
+            }
+        }
+        sc.restart_interval = h.dri;
+        sc.offset = (long long)g.next;
+        const long long units = prog_scan_units(fr, sc), ri = h.dri ? h.dri : units;
+        int nseg = 0;
+        size_t end = 0;
+        const int r = scan_segments(f, n, g.next, want_segs, ps.segs, nseg, end);
+        if (r != BBOCR_JPEG_OK) return r;
+        if ((long long)nseg != (units + ri - 1) / ri) return BBOCR_JPEG_RESTART;
+        sc.segments = nseg;
+        sc.bytes = (long long)end - sc.offset;
+        pl.scans[pl.n_scans++] = sc;
+        out.scans.push_back(std::move(ps));
+        g.next = end;
     }
     if (!pl.n_scans) return BBOCR_JPEG_TRUNCATED;
-    for (int c = 0; c < pl.components; ++c)
+    for (int c = 0; c < fr.components; ++c)
         for (int k = 0; k < 64; ++k)
             if (bits[c][k] != 0) return BBOCR_JPEG_SCRIPT;                                 // incomplete: libjpeg-turbo would smooth
     return BBOCR_JPEG_OK;
 }
+// the walk, then the frame as the public plan states it
 inline int prog_parse(const uint8_t* f, size_t n, ProgParsed& out, bool want_segs) {
     const int reason = prog_walk(f, n, out, want_segs);
-    out.plan.reason = reason;
-    out.plan.supported = reason == BBOCR_JPEG_OK;
+    bbocr_jpeg_progressive_plan& pl = out.plan;
+    bbocr_jpeg_plan& fr = out.frame.plan;
+    pl.width = fr.width;
+    pl.height = fr.height;
+    pl.components = fr.components;
+    std::memcpy(pl.sampling, fr.sampling, sizeof pl.sampling);
+    pl.mcu_cols = fr.mcu_cols;
+    pl.mcu_rows = fr.mcu_rows;
+    pl.chroma = fr.chroma;
+    pl.orientation = fr.orientation;
+    pl.reason = reason;
+    pl.supported = reason == BBOCR_JPEG_OK;
+    fr.supported = pl.supported && !fr.chroma;
     return reason;
 }
 
 // tables a scan reads: one per scan component, none in a DC refinement (raw bits)
 inline int prog_scan_tables(const bbocr_jpeg_scan& s) { return s.ss == 0 && s.ah > 0 ? 0 : s.components; }
-// subsequences of S bits a scan is cut into at most: every segment is cut on its own (0 for a refinement, which is not cut)
-inline size_t prog_scan_subs(const bbocr_jpeg_scan& s, int S) { return s.ah > 0 ? 0 : (size_t)s.segments + (size_t)s.bytes * 8 / (size_t)S + 1; }
+// subsequences of S bits a scan of `segments` restart segments and `bytes` bytes is cut into at most: every segment is cut on its own
+inline size_t scan_subs_bound(int segments, long long bytes, int S) { return (size_t)segments + (size_t)bytes * 8 / (size_t)S + 1; }
+// ... a progressive scan (0 for a refinement, which is not cut)
+inline size_t prog_scan_subs(const bbocr_jpeg_scan& s, int S) { return s.ah > 0 ? 0 : scan_subs_bound(s.segments, s.bytes, S); }
 
-// Scan k of a parsed file as jpegprog.h reads it: the unstuffed bytes into data[scan.bytes + 8], seg_byte[segments + 1], the derived
-// tables into huff[prog_scan_tables], for a first scan its subsequences of S bits into seg_sub[segments + 1] and sub_seg[prog_scan_subs],
-// and every field of `sc` but its pointers, which the caller owns.
-inline void prog_fill_scan(const ProgParsed& pp, int k, const uint8_t* file, int S, uint8_t* data, int* seg_byte, JpegHuff* huff, int* seg_sub,
-                           int* sub_seg, JpScan& sc) {
-    const bbocr_jpeg_progressive_plan& pl = pp.plan;
-    const bbocr_jpeg_scan& s = pl.scans[k];
+// The restart segments `segs` of a scan of `file` as the device reads them: their bytes without the stuffing, one segment after the
+// other, into data (at most the scan's bytes) and seg_byte[segments + 1]; S > 0: every segment cut on its own into subsequences of S
+// bits, at least one, into seg_sub[segments + 1] and sub_seg[scan_subs_bound].  Returns the bytes; nsub receives the subsequences.
+inline size_t cut_scan(const uint8_t* file, const std::vector<std::pair<size_t, size_t>>& segs, int S, uint8_t* data, int* seg_byte, int* seg_sub,
+                       int* sub_seg, int& nsub) {
+    const int nseg = (int)segs.size();
     size_t w = 0;
-    int nsub = 0;
-    for (int g = 0; g < s.segments; ++g) {
+    nsub = 0;
+    for (int g = 0; g < nseg; ++g) {
         seg_byte[g] = (int)w;
-        w += unstuff(file + pp.scans[k].segs[g].first, file + pp.scans[k].segs[g].second, data + w);
-        if (s.ah == 0) {
+        w += unstuff(file + segs[g].first, file + segs[g].second, data + w);
+        if (S > 0) {
             const int cnt = (int)std::max<size_t>(((w - (size_t)seg_byte[g]) * 8 + S - 1) / S, 1);
             seg_sub[g] = nsub;
             for (int i = 0; i < cnt; ++i) sub_seg[nsub + i] = g;
             nsub += cnt;
         }
     }
-    seg_byte[s.segments] = (int)w;
-    if (s.ah == 0) seg_sub[s.segments] = nsub;
-    sc.nsub = nsub;
+    seg_byte[nseg] = (int)w;
+    if (S > 0) seg_sub[nseg] = nsub;
+    return w;
+}
+
+// Scan k of a parsed file as jpegprog.h reads it: cut_scan's tables (a refinement is not cut), the derived tables into
+// huff[prog_scan_tables], and every field of `sc` but its pointers, which the caller owns.
+inline void prog_fill_scan(const ProgParsed& pp, int k, const uint8_t* file, int S, uint8_t* data, int* seg_byte, JpegHuff* huff, int* seg_sub,
+                           int* sub_seg, JpScan& sc) {
+    const bbocr_jpeg_plan& fr = pp.frame.plan;
+    const bbocr_jpeg_scan& s = pp.plan.scans[k];
+    cut_scan(file, pp.scans[k].segs, s.ah == 0 ? S : 0, data, seg_byte, seg_sub, sub_seg, sc.nsub);
     sc.S = S;
     for (int i = 0; i < prog_scan_tables(s); ++i) derive_table(pp.scans[k].tab[i], huff[i]);      // prefix codes: the plan checked
     sc.nseg = s.segments;
@@ -368,17 +501,17 @@ inline void prog_fill_scan(const ProgParsed& pp, int k, const uint8_t* file, int
     sc.Se = s.se;
     sc.Ah = s.ah;
     sc.Al = s.al;
-    sc.nunits = prog_scan_units(pl, s);
+    sc.nunits = prog_scan_units(fr, s);
     sc.ri = s.restart_interval ? s.restart_interval : std::max(sc.nunits, 1);
     int bh;
-    prog_comp_raster(pl, s.component[0], sc.bw, bh, sc.ch, sc.cv);
-    sc.hs = pl.components == 3 ? pl.sampling[0][0] : 1;
-    sc.vs = pl.components == 3 ? pl.sampling[0][1] : 1;
+    prog_comp_raster(fr, s.component[0], sc.bw, bh, sc.ch, sc.cv);
+    sc.hs = fr.components == 3 ? fr.sampling[0][0] : 1;
+    sc.vs = fr.components == 3 ? fr.sampling[0][1] : 1;
     sc.coff = s.component[0] == 0 ? 0 : sc.hs * sc.vs + s.component[0] - 1;
-    sc.bpm = pl.components == 3 ? sc.hs * sc.vs + 2 : 1;
-    sc.mcux = pl.mcu_cols;
-    sc.ncomp = pl.components;
-    sc.nblocks = pl.mcu_cols * pl.mcu_rows * sc.bpm;
+    sc.bpm = fr.components == 3 ? sc.hs * sc.vs + 2 : 1;
+    sc.mcux = fr.mcu_cols;
+    sc.ncomp = fr.components;
+    sc.nblocks = fr.mcu_cols * fr.mcu_rows * sc.bpm;
 }
 
 }  // namespace jpeg_host

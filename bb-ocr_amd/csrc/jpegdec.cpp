@@ -1,5 +1,6 @@
-// Baseline JPEG decoding, host side: the marker parser (bbocr_host_jpeg_plan: one linear pass, no entropy bit decoded), the per-batch
-// tables of jpegdec.hip (unstuffed segment bytes, subsequence lists, derived Huffman tables) and its launch sequence.  A batch runs on
+// JPEG decoding, host side: the per-batch tables of jpegdec.hip and jpegprog.hip (unstuffed segment bytes and subsequence lists from
+// jpeg_parse.h's cut_scan, carved and bound by ScanOffsets for a baseline scan and a progressive one alike; derived Huffman tables) and
+// the launch sequence.  The marker walks behind bbocr_host_jpeg_plan and bbocr_host_jpeg_progressive_plan are jpeg_parse.h's.  A batch runs on
 // its own stream of the root context, outside the call slots (the contract of bbocr_upload_pages): files decode while two OCR calls run.
 // A batch runs the entropy stages once per file and one IDCT + output pass per requested output: scale 1, or 1/2, 1/4, 1/8 (Pillow's
 // draft); YCbCr pixels or, at scale 1, the oriented BGR page of cv2.imread.  jpeg_geometry is the one statement of what a scale and a
@@ -15,142 +16,6 @@
 namespace {
 
 using namespace jpeg_host;
-
-struct JpegParsed {
-    bbocr_jpeg_plan plan{};
-    unsigned short quant[3][64];              // per component, natural order
-    HuffSpec huff[2][2];                      // [class][id]
-    int tab_dc[3], tab_ac[3];
-    std::vector<std::pair<size_t, size_t>> segs;   // byte ranges of the restart segments in the file (stuffing included)
-};
-
-// The chroma layouts outside `supported` that the decoder takes all the same (bbocr_jpeg_plan::chroma): luma (1,1), (2,1) or (1,2) over
-// chroma (1,1), (1,1).  0: any other sampling.
-int chroma_class(const bbocr_jpeg_plan& pl) { return chroma_class_of(pl.sampling); }
-
-// jdmarker.c's walk over the headers up to SOS, then over the entropy-coded data up to the marker that ends it.  Returns the reason;
-// `cls` receives the chroma class of a file whose sampling alone is outside today's scope, and the walk goes on as for a supported file.
-int jpeg_walk(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs, int& cls) {
-    bbocr_jpeg_plan& pl = out.plan;
-    pl = bbocr_jpeg_plan{};
-    if (n < 4 || f[0] != 0xFF || f[1] != 0xD8) return BBOCR_JPEG_NOT_JPEG;
-    pl.orientation = exif_orientation(f, n);                     // of its own walk: malformed EXIF never changes what follows
-    size_t p = 2;
-    unsigned short qt[4][64];
-    bool have_qt[4] = {false, false, false, false};
-    bool have_sof = false, jfif = false;
-    int adobe = -1, comp_id[4] = {0}, comp_tq[4] = {0}, dri = 0;
-    size_t scan_off = 0;
-    for (;;) {
-        for (;;) {
-            if (p + 2 > n || f[p] != 0xFF) return BBOCR_JPEG_TRUNCATED;
-            if (f[p + 1] == 0xFF) { ++p; continue; }
-            break;
-        }
-        const int m = f[p + 1];
-        p += 2;
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xD9) return BBOCR_JPEG_TRUNCATED;
-        if (p + 2 > n) return BBOCR_JPEG_TRUNCATED;
-        const size_t L = ((size_t)f[p] << 8) | f[p + 1];
-        if (L < 2 || p + L > n) return BBOCR_JPEG_TRUNCATED;
-        const uint8_t* s = f + p + 2;
-        const size_t sl = L - 2;
-        if (m == 0xC0) {
-            if (have_sof || sl < 6) return BBOCR_JPEG_SOF;
-            if (s[0] != 8) return BBOCR_JPEG_PRECISION;
-            pl.height = (s[1] << 8) | s[2];
-            pl.width = (s[3] << 8) | s[4];
-            pl.components = s[5];
-            if (pl.height == 0 || pl.width == 0 || sl < 6 + 3 * (size_t)pl.components) return BBOCR_JPEG_SOF;
-            for (int i = 0; i < pl.components && i < 4; ++i) {
-                comp_id[i] = s[6 + 3 * i];
-                if (i < 3) { pl.sampling[i][0] = s[7 + 3 * i] >> 4; pl.sampling[i][1] = s[7 + 3 * i] & 15; }
-                comp_tq[i] = s[8 + 3 * i];
-            }
-            have_sof = true;
-        } else if (m >= 0xC1 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
-            return BBOCR_JPEG_SOF;                           // extended, progressive, lossless, arithmetic conditioning
-        } else if (m == 0xC4) {
-            if (!read_dht(s, sl, out.huff)) return BBOCR_JPEG_TABLES;
-        } else if (m == 0xDB) {
-            size_t q = 0;
-            while (q < sl) {
-                if (s[q] >> 4) return BBOCR_JPEG_PRECISION;
-                const int id = s[q] & 15;
-                if (id > 3 || q + 65 > sl) return BBOCR_JPEG_TABLES;
-                for (int k = 0; k < 64; ++k) qt[id][kZigzag[k]] = s[q + 1 + k];
-                have_qt[id] = true;
-                q += 65;
-            }
-        } else if (m == 0xDD) {
-            if (sl < 2) return BBOCR_JPEG_TRUNCATED;
-            dri = (s[0] << 8) | s[1];
-        } else if (m == 0xE0 && sl >= 5 && std::memcmp(s, "JFIF\0", 5) == 0) {
-            jfif = true;
-        } else if (m == 0xEE && sl >= 12 && std::memcmp(s, "Adobe", 5) == 0) {
-            adobe = s[11];
-        } else if (m == 0xDA) {
-            if (!have_sof) return BBOCR_JPEG_SOF;
-            const int nc = pl.components;
-            if (nc != 1 && nc != 3) return BBOCR_JPEG_COMPONENTS;
-            if (nc == 3) {
-                if (!jfif && adobe != 1) return BBOCR_JPEG_COLORSPACE;
-                if (pl.sampling[0][0] != 2 || pl.sampling[0][1] != 2 || pl.sampling[1][0] != 1 || pl.sampling[1][1] != 1 || pl.sampling[2][0] != 1 ||
-                    pl.sampling[2][1] != 1) {
-                    cls = chroma_class(pl);
-                    if (!cls) return BBOCR_JPEG_SAMPLING;
-                }
-            }
-            if (sl < 1 || s[0] != nc || sl < 1 + 2 * (size_t)nc + 3) return BBOCR_JPEG_MULTISCAN;
-            for (int i = 0; i < nc; ++i) {
-                if (s[1 + 2 * i] != comp_id[i]) return BBOCR_JPEG_MULTISCAN;
-                const int td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
-                if (td > 1 || ta > 1 || !out.huff[0][td].have || !out.huff[1][ta].have || comp_tq[i] > 3 || !have_qt[comp_tq[i]]) return BBOCR_JPEG_TABLES;
-                out.tab_dc[i] = td;
-                out.tab_ac[i] = 2 + ta;
-                std::memcpy(out.quant[i], qt[comp_tq[i]], sizeof qt[0]);
-            }
-            scan_off = p + L;
-            break;
-        }
-        p += L;
-    }
-    const int mcu_w = pl.components == 3 ? 8 * pl.sampling[0][0] : 8, mcu_h = pl.components == 3 ? 8 * pl.sampling[0][1] : 8;
-    pl.mcu_cols = (pl.width + mcu_w - 1) / mcu_w;
-    pl.mcu_rows = (pl.height + mcu_h - 1) / mcu_h;
-    pl.restart_interval = dri;
-    pl.scan_offset = (long long)scan_off;
-    const long long nmcu = (long long)pl.mcu_cols * pl.mcu_rows;
-    size_t end = 0;
-    int nseg = 0;
-    const int walked = scan_segments(f, n, scan_off, want_segs, out.segs, nseg, end);
-    if (walked != BBOCR_JPEG_OK) return walked;
-    if (f[end + 1] != 0xD9) return BBOCR_JPEG_MULTISCAN;
-    const long long ri = dri ? dri : nmcu;
-    if ((long long)nseg != (nmcu + ri - 1) / ri) return BBOCR_JPEG_RESTART;
-    pl.segments = nseg;
-    pl.scan_bytes = (long long)(end - scan_off);
-    return BBOCR_JPEG_OK;
-}
-
-// The plan of a file and its reason.  A file of a chroma class that passed every later check keeps reason BBOCR_JPEG_SAMPLING and
-// supported 0, with `chroma` set and the whole plan filled; one that failed a later check is refused as before, nothing behind the
-// sampling test filled.
-int jpeg_parse(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs) {
-    int cls = 0;
-    const int reason = jpeg_walk(f, n, out, want_segs, cls);
-    bbocr_jpeg_plan& pl = out.plan;
-    pl.supported = reason == BBOCR_JPEG_OK && !cls;
-    if (!cls) return reason;
-    if (reason == BBOCR_JPEG_OK) {
-        pl.chroma = cls;
-    } else {
-        pl.restart_interval = pl.mcu_cols = pl.mcu_rows = pl.segments = 0;
-        pl.scan_offset = pl.scan_bytes = 0;
-    }
-    return BBOCR_JPEG_SAMPLING;
-}
 
 // the decoder takes the file: inside today's scope, or of a chroma class
 bool jpeg_taken(const bbocr_jpeg_plan& pl) { return pl.supported || pl.chroma; }
@@ -191,6 +56,41 @@ size_t plane_size(const JpegComp& c) { return (size_t)c.plane_rows * (size_t)c.p
 constexpr int kMaxPasses = 4;                 // IDCT + output passes over one batch's coefficients: one per scale
 struct JpegPass { int scale, px; };           // px: bytes per pixel of a 3-component file's output
 
+// Where a scan that cut_scan cuts lies: its tables in the input blob, the states of its subsequences in the work buffer.  subs: the
+// subsequences the blob has room for; 0: the scan is not cut (a refinement) and has its bytes and seg_byte alone.
+struct ScanOffsets {
+    size_t data, seg_byte, seg_sub, sub_seg, subs, entry, exits, count, scan, flags;
+    void blob(Carve& in, int segments, long long bytes, size_t room) {
+        *this = {};
+        subs = room;
+        data = in.add((size_t)bytes + 8);
+        seg_byte = in.add(4 * ((size_t)segments + 1));
+        if (!subs) return;
+        seg_sub = in.add(4 * ((size_t)segments + 1));
+        sub_seg = in.add(4 * subs);
+    }
+    void states(Carve& work, size_t nsub) {
+        entry = work.add(8 * nsub);
+        exits = work.add(8 * nsub);
+        count = work.add(4 * nsub);
+        scan = work.add(4 * nsub);
+    }
+    // the descriptor's pointers into the device's copy of the blob (db) and the work buffer (wb)
+    void bind(char* db, char* wb, int passes, JpegSubs& d) const {
+        d.data = (const uint8_t*)(db + data);
+        d.seg_byte = (const int*)(db + seg_byte);
+        if (!subs) return;
+        d.seg_sub = (const int*)(db + seg_sub);
+        d.sub_seg = (const int*)(db + sub_seg);
+        d.entry = (unsigned long long*)(wb + entry);
+        d.exits = (unsigned long long*)(wb + exits);
+        d.count = (int*)(wb + count);
+        d.scan = (int*)(wb + scan);
+        d.flags = (int*)(wb + flags);
+        d.passes = passes;
+    }
+};
+
 struct FileJob {                              // one admitted file of a batch
     JpegParsed ps;
     const uint8_t* file = nullptr;            // its bytes (caller-owned)
@@ -198,34 +98,15 @@ struct FileJob {                              // one admitted file of a batch
     long long pitch[kMaxPasses] = {0};
     int k = 0;                                // its index in the caller's arrays (status[])
     int nsub = 0, groups = 0, nblocks = 0;
-    size_t o_huff, o_quant, o_segbyte, o_segsub, o_subseg, o_data, data_bytes;   // offsets in the input blob
-    size_t w_entry, w_exits, w_count, w_scan, w_first, w_flags, w_plane[kMaxPasses][3], o_coef; // offsets in the work / coefficient buffers
+    ScanOffsets cut;                          // its scan (a progressive file: no segment, no byte)
+    size_t o_huff, o_quant;                   // offsets in the input blob
+    size_t w_first, w_plane[kMaxPasses][3], o_coef; // offsets in the work / coefficient buffers
     size_t o_page = 0;                        // the imread form: offset of the un-oriented decode in jd_page
     JpegGeometry geo[kMaxPasses];             // per pass (filled by jpeg_run)
     std::shared_ptr<ProgParsed> prog;         // a progressive file: its scans; `ps` then holds the frame alone, as a plan without a scan
-    struct ScanBlob { size_t o_data, o_segbyte, o_huff, o_segsub, o_subseg, subs, w_entry, w_exits, w_count, w_scan, w_flags; };
-    std::vector<ScanBlob> scan_blob;          // per scan: offsets in the input blob
+    struct ScanBlob { ScanOffsets cut; size_t o_huff; };
+    std::vector<ScanBlob> scan_blob;          // per scan of a progressive file
 };
-
-// The frame of a progressive file the plan supports as the stages behind the entropy side read it: a baseline plan of the same size and
-// sampling without a scan (0 segments, 0 bytes), so that the baseline entropy stages find nothing to do for it.
-void frame_of(const ProgParsed& pp, JpegParsed& ps) {
-    const bbocr_jpeg_progressive_plan& q = pp.plan;
-    bbocr_jpeg_plan& pl = ps.plan;
-    pl = bbocr_jpeg_plan{};
-    pl.width = q.width;
-    pl.height = q.height;
-    pl.components = q.components;
-    std::memcpy(pl.sampling, q.sampling, sizeof pl.sampling);
-    pl.mcu_cols = q.mcu_cols;
-    pl.mcu_rows = q.mcu_rows;
-    pl.orientation = q.orientation;
-    pl.chroma = q.chroma;
-    pl.supported = !q.chroma;
-    std::memcpy(ps.quant, pp.quant, sizeof ps.quant);
-    for (int c = 0; c < 3; ++c) ps.tab_dc[c] = ps.tab_ac[c] = 0;
-    ps.segs.clear();
-}
 
 // Admission of a batch: status[k] = BBOCR_ERR_ARG for a null or oversized file and for one the plan neither supports nor gives a chroma
 // class (the caller plans first: a refused file is its error); every other file becomes a job once dest(job) -- the entry point's own rule -- has checked the caller's
@@ -244,7 +125,7 @@ template <typename D> std::vector<FileJob> jpeg_admit(const uint8_t* const* file
         if (progressive && !jpeg_taken(j.ps.plan) && reason != BBOCR_JPEG_NOT_JPEG) {   // whatever the baseline walk stopped at
             j.prog = std::make_shared<ProgParsed>();
             if (prog_parse(files[k], bytes[k], *j.prog, true) != BBOCR_JPEG_OK) continue;
-            frame_of(*j.prog, j.ps);
+            j.ps = j.prog->frame;                                                       // a plan without a scan
         }
         if (!jpeg_taken(j.ps.plan) || (!chroma_classes && !j.ps.plan.supported)) continue;
         j.file = files[k];
@@ -302,29 +183,17 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         for (int k = 0; k < scans_of(j); ++k) {
             const bbocr_jpeg_scan& sc = j.prog->plan.scans[k];
             FileJob::ScanBlob& b = j.scan_blob[k];
-            b = {};
-            b.o_data = in.add((size_t)sc.bytes + 8);
-            b.o_segbyte = in.add(4 * ((size_t)sc.segments + 1));
+            b.cut.blob(in, sc.segments, sc.bytes, prog_scan_subs(sc, S));
             b.o_huff = in.add(std::max<size_t>(prog_scan_tables(sc), 1) * sizeof(JpegHuff));
-            b.subs = prog_scan_subs(sc, S);
-            if (b.subs) {                                                     // a first scan: subsequence lists and states, as for a baseline scan
-                b.o_segsub = in.add(4 * ((size_t)sc.segments + 1));
-                b.o_subseg = in.add(4 * b.subs);
-                b.w_entry = work.add(8 * b.subs);
-                b.w_exits = work.add(8 * b.subs);
-                b.w_count = work.add(4 * b.subs);
-                b.w_scan = work.add(4 * b.subs);
-                prog_groups = std::max(prog_groups, (int)((b.subs + 63) / 64));
+            if (b.cut.subs) {                                                 // a first scan: states as for a baseline scan
+                b.cut.states(work, b.cut.subs);
+                prog_groups = std::max(prog_groups, (int)((b.cut.subs + 63) / 64));
             }
             prog_max_seg = std::max(prog_max_seg, sc.segments);
         }
         j.o_huff = in.add(4 * sizeof(JpegHuff));
         j.o_quant = in.add(3 * 64 * 2);
-        j.o_segbyte = in.add(4 * ((size_t)pl.segments + 1));
-        j.o_segsub = in.add(4 * ((size_t)pl.segments + 1));
-        j.o_data = in.add((size_t)pl.scan_bytes + 8);
-        // subsequences: every segment is cut on its own, so at most one per segment more than scan bits / S
-        j.o_subseg = in.add(4 * ((size_t)pl.segments + (size_t)pl.scan_bytes * 8 / S + 1));
+        j.cut.blob(in, pl.segments, pl.scan_bytes, scan_subs_bound(pl.segments, pl.scan_bytes, S));
         j.nblocks = pl.mcu_cols * pl.mcu_rows * (pl.components == 3 ? luma_h(pl) * luma_v(pl) + 2 : 1);
         max_seg = std::max(max_seg, pl.segments);
         max_blocks = std::max(max_blocks, j.nblocks);
@@ -342,34 +211,12 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
             for (int id = 0; id < 2; ++id)
                 if (!derive_table(j.ps.huff[cls][id], ht[cls * 2 + id])) std::memset(&ht[cls * 2 + id], 0, sizeof(JpegHuff));   // no code: the file fails
         std::memcpy(hb + j.o_quant, j.ps.quant, sizeof j.ps.quant);
-        int* seg_byte = (int*)(hb + j.o_segbyte);
-        int* seg_sub = (int*)(hb + j.o_segsub);
-        int* sub_seg = (int*)(hb + j.o_subseg);
-        uint8_t* data = (uint8_t*)(hb + j.o_data);
-        size_t w = 0;
-        int nsub = 0;
-        for (int s = 0; s < pl.segments; ++s) {
-            const uint8_t* a = j.file + j.ps.segs[s].first;
-            const uint8_t* e = j.file + j.ps.segs[s].second;
-            seg_byte[s] = (int)w;
-            seg_sub[s] = nsub;
-            w += unstuff(a, e, data + w);
-            const size_t bits = (w - (size_t)seg_byte[s]) * 8;
-            const int cnt = (int)std::max<size_t>((bits + S - 1) / S, 1);
-            for (int k = 0; k < cnt; ++k) sub_seg[nsub + k] = s;
-            nsub += cnt;
-        }
-        seg_byte[pl.segments] = (int)w;
-        seg_sub[pl.segments] = nsub;
-        j.data_bytes = w;
-        j.nsub = nsub;
-        j.groups = (nsub + JD_LANES - 1) / JD_LANES;
+        const ScanOffsets& o = j.cut;
+        cut_scan(j.file, j.ps.segs, S, (uint8_t*)(hb + o.data), (int*)(hb + o.seg_byte), (int*)(hb + o.seg_sub), (int*)(hb + o.sub_seg), j.nsub);
+        j.groups = (j.nsub + JD_LANES - 1) / JD_LANES;
         max_groups = std::max(max_groups, j.groups);
-        j.w_entry = work.add(8 * (size_t)nsub);
-        j.w_exits = work.add(8 * (size_t)nsub);
-        j.w_count = work.add(4 * (size_t)nsub);
-        j.w_scan = work.add(4 * (size_t)nsub);
-        j.w_first = work.add(4 * (size_t)nsub);
+        j.cut.states(work, (size_t)j.nsub);
+        j.w_first = work.add(4 * (size_t)j.nsub);
         for (int p = 0; p < np; ++p) {
             j.geo[p] = jpeg_geometry(pl, passes_out[p].scale);
             for (int c = 0; c < 3; ++c) j.w_plane[p][c] = work.add(plane_size(j.geo[p].comp[c]));
@@ -378,11 +225,11 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
     }
     const int passes = max_groups + 1;
     const size_t flags_off = work.off;
-    for (FileJob& j : jobs) j.w_flags = work.add(4 * (size_t)passes);
+    for (FileJob& j : jobs) j.cut.flags = work.add(4 * (size_t)passes);
     const int prog_passes = prog_groups + 1;
     for (FileJob& j : jobs)
         for (FileJob::ScanBlob& b : j.scan_blob)
-            if (b.subs) b.w_flags = work.add(4 * (size_t)prog_passes);
+            if (b.cut.subs) b.cut.flags = work.add(4 * (size_t)prog_passes);
     root->jd_work.ensure(work.off);
     root->jd_coef.ensure(std::max<size_t>(coef.off, 256));
     char* wb = (char*)root->jd_work.p;
@@ -391,16 +238,8 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         const FileJob& j = jobs[k];
         const bbocr_jpeg_plan& pl = j.ps.plan;
         JpegDesc d{};
-        d.data = (const uint8_t*)(db + j.o_data);
-        d.seg_byte = (const int*)(db + j.o_segbyte);
-        d.seg_sub = (const int*)(db + j.o_segsub);
-        d.sub_seg = (const int*)(db + j.o_subseg);
-        d.entry = (unsigned long long*)(wb + j.w_entry);
-        d.exits = (unsigned long long*)(wb + j.w_exits);
-        d.count = (int*)(wb + j.w_count);
-        d.scan = (int*)(wb + j.w_scan);
+        j.cut.bind(db, wb, passes, d);
         d.first = (int*)(wb + j.w_first);
-        d.flags = (int*)(wb + j.w_flags);
         d.status = (int*)wb + k;
         d.coef = (short*)((char*)root->jd_coef.p + j.o_coef);
         d.huff = (const JpegHuff*)(db + j.o_huff);
@@ -419,7 +258,6 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
         d.nsub = j.nsub;
         d.S = S;
         d.nblocks = j.nblocks;
-        d.passes = passes;
         for (int c = 0; c < 3; ++c) { d.tab_dc[c] = j.ps.tab_dc[c]; d.tab_ac[c] = j.ps.tab_ac[c]; }
         for (int p = 0; p < np; ++p) {                                    // pass p's descriptors: descs[p * n ..]; the entropy stages read pass 0's
             for (int c = 0; c < 3; ++c) {
@@ -442,21 +280,11 @@ void jpeg_run(bbocr_ctx* root, hipStream_t st, std::vector<FileJob>& jobs, int S
             for (const LevelScan& e : levels[L]) {
                 const FileJob& j = jobs[e.job];
                 const FileJob::ScanBlob& b = j.scan_blob[e.k];
+                const ScanOffsets& o = b.cut;
                 JpScan& sc = scans[at++];
-                prog_fill_scan(*j.prog, e.k, j.file, S, (uint8_t*)(hb + b.o_data), (int*)(hb + b.o_segbyte), (JpegHuff*)(hb + b.o_huff),
-                               (int*)(hb + b.o_segsub), (int*)(hb + b.o_subseg), sc);
-                if (b.subs) {
-                    sc.seg_sub = (const int*)(db + b.o_segsub);
-                    sc.sub_seg = (const int*)(db + b.o_subseg);
-                    sc.entry = (unsigned long long*)(wb + b.w_entry);
-                    sc.exits = (unsigned long long*)(wb + b.w_exits);
-                    sc.count = (int*)(wb + b.w_count);
-                    sc.scan = (int*)(wb + b.w_scan);
-                    sc.flags = (int*)(wb + b.w_flags);
-                    sc.passes = prog_passes;
-                }
-                sc.data = (const uint8_t*)(db + b.o_data);
-                sc.seg_byte = (const int*)(db + b.o_segbyte);
+                prog_fill_scan(*j.prog, e.k, j.file, S, (uint8_t*)(hb + o.data), (int*)(hb + o.seg_byte), (JpegHuff*)(hb + b.o_huff),
+                               (int*)(hb + o.seg_sub), (int*)(hb + o.sub_seg), sc);
+                o.bind(db, wb, prog_passes, sc);
                 sc.huff = (const JpegHuff*)(db + b.o_huff);
                 sc.coef = descs[e.job].coef;
                 sc.status = descs[e.job].status;
@@ -593,6 +421,17 @@ JpegDesc jpeg_stage_run(bbocr_ctx* ctx, hipStream_t s, int stage, const uint8_t*
 
 bool draft_scale(int s) { return s == 2 || s == 4 || s == 8; }
 
+// bbocr_op_jpeg_stage and bbocr_op_jpeg_progressive_stage: the subsequence length they name, and their stage 1 (the coefficients)
+int stage_subseq_bits(int subseq_bits) {
+    const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
+    if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
+    return S;
+}
+void stage_coefficients(const JpegDesc& d, void* dev_dst, size_t dst_bytes, hipStream_t s) {
+    if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
+    HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
+}
+
 }  // namespace
 
 extern "C" {
@@ -657,14 +496,10 @@ int bbocr_jpeg_decode_progressive(bbocr_ctx* ctx, const uint8_t* const* files, c
 int bbocr_op_jpeg_progressive_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int n_scans, int subseq_bits, void* dev_dst,
                                     size_t dst_bytes, int* file_status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
-        const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
-        if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
+        const int S = stage_subseq_bits(subseq_bits);
         if (stage < 1 || stage > 3 || n_scans < 0 || n_scans > BBOCR_JPEG_MAX_SCANS) fail(BBOCR_ERR_ARG, "stage 1, 2 or 3 after 0 .. 64 scans");
         const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, S, 1, -1, dev_dst, dst_bytes, file_status, true, n_scans);
-        if (stage == 1) {
-            if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
-            HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
-        }
+        if (stage == 1) stage_coefficients(d, dev_dst, dst_bytes, s);
         HIPCHK(hipStreamSynchronize(s));
     });
 }
@@ -672,9 +507,7 @@ int bbocr_op_jpeg_progressive_stage(bbocr_ctx* ctx, int stage, const uint8_t* fi
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
-        const int S = subseq_bits == 0 ? JD_SUBSEQ_BITS : subseq_bits;
-        if (S < 32 || S > 65536 || (S & 7)) fail(BBOCR_ERR_ARG, "subseq_bits: a multiple of 8 in 32 .. 65536, or 0");
-        const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, S, 1, -1, dev_dst, dst_bytes, file_status);
+        const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, stage_subseq_bits(subseq_bits), 1, -1, dev_dst, dst_bytes, file_status);
         if (stage == 0) {
             const size_t ns = (size_t)d.nsub;
             if (dst_bytes < ns * 16) fail(BBOCR_ERR_ARG, "destination too small");
@@ -684,15 +517,15 @@ int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t b
             HIPCHK(hipMemcpyAsync(first.data(), d.first, ns * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             for (size_t i = 0; i < ns; ++i) {
-                rows[4 * i] = (int)(unsigned)entry[i];
-                rows[4 * i + 1] = (int)((entry[i] >> 32) & 7);
-                rows[4 * i + 2] = (int)((entry[i] >> 40) & 63);
+                const JpegState st = jpeg_unpack(entry[i]);
+                rows[4 * i] = (int)st.p;
+                rows[4 * i + 1] = st.b;
+                rows[4 * i + 2] = st.z;
                 rows[4 * i + 3] = first[i];
             }
             HIPCHK(hipMemcpyAsync(dev_dst, rows.data(), ns * 16, hipMemcpyHostToDevice, s));
         } else if (stage == 1) {
-            if (dst_bytes < (size_t)d.nblocks * 128) fail(BBOCR_ERR_ARG, "destination too small");
-            HIPCHK(hipMemcpyAsync(dev_dst, d.coef, (size_t)d.nblocks * 128, hipMemcpyDeviceToDevice, s));
+            stage_coefficients(d, dev_dst, dst_bytes, s);
         }
         HIPCHK(hipStreamSynchronize(s));
     });

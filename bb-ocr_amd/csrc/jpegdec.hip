@@ -1,6 +1,6 @@
 // Baseline JPEG decoding on the device (SOF0, Huffman, one interleaved scan, YCbCr 4:2:0, 4:4:4, 4:2:2, 4:4:0 or grey), to the bit of
 // libjpeg-turbo: the entropy stage by speculative decoding with self-synchronisation (Weissenberger & Schmidt), then thumb.hip's decoder
-// half (jpeg_dev.h).
+// half (jpeg_dev.h).  The first three kernels are jpeg_spec.h's passes, which jpegprog.hip runs too, over this file's jd_run (JdCodec).
 //   jd_sync     one lane per S-bit subsequence: decode from the assumed state (block 0 of the MCU, coefficient 0), then take the left
 //               neighbour's exit state and decode again until no state of the workgroup changes; launched once more per workgroup
 //               a segment spans, a launch returning at once when the launch before it changed nothing
@@ -17,22 +17,10 @@
 // The bytes are untrusted: every stream read is clamped to its segment (past the end: 1-bits), every store is index-checked, every loop
 // has a trip count fixed by the host's plan (S, lanes per workgroup, items per segment).
 #include "common.h"
-#include "kernels.h"
+#include "jpeg_spec.h"
 #include "jpeg_dev.h"
 
 namespace {
-
-__device__ const unsigned char JD_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct JdState { unsigned p; int b, z; };                     // bit in `data`, block in the MCU, zig-zag position
-__device__ __forceinline__ unsigned long long jd_pack(const JdState& s) {
-    return (unsigned long long)s.p | ((unsigned long long)(unsigned)s.b << 32) | ((unsigned long long)(unsigned)s.z << 40);
-}
-__device__ __forceinline__ JdState jd_unpack(unsigned long long v) {
-    return JdState{(unsigned)v, (int)((v >> 32) & 7), (int)((v >> 40) & 63)};
-}
 
 // 16 bits at bit p of the segment whose bytes are [b0, b1); past the end: ones
 __device__ __forceinline__ unsigned jd_peek16(const uint8_t* __restrict__ data, unsigned b0, unsigned b1, unsigned p) {
@@ -51,17 +39,10 @@ __device__ __forceinline__ int jd_comp(const JpegDesc& d, int b) {
     return d.bpm == 1 ? 0 : (b < nl ? 0 : b - nl + 1);
 }
 
-__device__ __forceinline__ void jd_load_tables(const JpegHuff* __restrict__ g, JpegHuff* lds, int t, int nt) {
-    const int* src = (const int*)g;
-    int* dst = (int*)lds;
-    for (int i = t; i < (int)(4 * sizeof(JpegHuff) / 4); i += nt) dst[i] = src[i];
-    __syncthreads();
-}
-
 // Decode from st while its bit is before `end` and fewer than max_blocks blocks are complete.  Returns the blocks completed; *invalid: a
 // look-ahead without a code was met (the state's bit is then `end`).  coef != null: coefficients of block first_block + n are stored
 // (DC terms as differences).  At most S + 32 symbols: each takes at least one bit.
-__device__ int jd_run(const JpegDesc& d, const JpegHuff* T, unsigned b0, unsigned b1, JdState& st, unsigned end, int max_blocks, short* coef,
+__device__ int jd_run(const JpegDesc& d, const JpegHuff* T, unsigned b0, unsigned b1, JpegState& st, unsigned end, int max_blocks, short* coef,
                       int first_block, bool* invalid) {
     unsigned p = st.p;
     int b = st.b, z = st.z, n = 0;
@@ -112,7 +93,7 @@ __device__ int jd_run(const JpegDesc& d, const JpegHuff* T, unsigned b0, unsigne
                 val = bits >= (1 << (sz - 1)) ? bits : bits - (1 << sz) + 1;
             }
             const int blk = first_block + n;
-            if (coef && z <= 63 && (unsigned)blk < (unsigned)d.nblocks) coef[(size_t)blk * 64 + JD_ZZ[z]] = (short)val;
+            if (coef && z <= 63 && (unsigned)blk < (unsigned)d.nblocks) coef[(size_t)blk * 64 + JPEG_ZZ[z]] = (short)val;
             z += 1;
         }
         if (z > 63) {
@@ -127,118 +108,48 @@ __device__ int jd_run(const JpegDesc& d, const JpegHuff* T, unsigned b0, unsigne
     return n;
 }
 
-struct JdSub { int seg, j; unsigned b0, b1, start, end; };
-__device__ __forceinline__ JdSub jd_sub(const JpegDesc& d, int i) {
-    JdSub s;
-    s.seg = min(max(d.sub_seg[i], 0), d.nseg - 1);
-    s.j = i - d.seg_sub[s.seg];
-    s.b0 = (unsigned)d.seg_byte[s.seg];
-    s.b1 = (unsigned)d.seg_byte[s.seg + 1];
-    s.start = s.b0 * 8u + (unsigned)s.j * (unsigned)d.S;
-    s.end = min(s.start + (unsigned)d.S, s.b1 * 8u);
-    return s;
-}
+// The baseline scan as jpeg_spec.h's passes see it: units are MCUs of bpm blocks, a segment starts at coefficient 0 of block 0 and
+// must end there, the write pass records the first block of every subsequence (stage 0 of bbocr_op_jpeg_stage).
+struct JdCodec {
+    using Desc = JpegDesc;
+    struct Lds { JpegHuff* T; };                                 // T[4] of the kernel's LDS
+    static __device__ __forceinline__ bool cut(const JpegDesc&) { return true; }
+    static __device__ __forceinline__ void load(const JpegDesc& d, const Lds& lds, int t, int nt) {
+        const int* src = (const int*)d.huff;
+        int* dst = (int*)lds.T;
+        for (int i = t; i < (int)(4 * sizeof(JpegHuff) / 4); i += nt) dst[i] = src[i];
+        __syncthreads();
+    }
+    static __device__ __forceinline__ int unit_blocks(const JpegDesc& d) { return d.bpm; }
+    static __device__ __forceinline__ int units(const JpegDesc& d) { return d.nmcu; }
+    static __device__ __forceinline__ JpegState start(const JpegDesc&, unsigned p) { return JpegState{p, 0, 0}; }
+    static __device__ __forceinline__ int run(const JpegDesc& d, const Lds& lds, int, const JpegSub& s, JpegState& st, int max_blocks, bool store,
+                                              long long first, bool* invalid, bool* over) {
+        *over = false;
+        return jd_run(d, lds.T, s.b0, s.b1, st, s.end, max_blocks, store ? d.coef : nullptr, (int)min(first, (long long)d.nblocks), invalid);
+    }
+    static __device__ __forceinline__ bool at_end(const JpegDesc&, const JpegState& st, const JpegSub&) { return st.b == 0 && st.z == 0; }
+    static __device__ __forceinline__ void note_first(const JpegDesc& d, int i, long long first) { d.first[i] = (int)min(first, (long long)d.nblocks); }
+};
 
 __global__ void __launch_bounds__(JD_LANES) jd_sync_kernel(const JpegDesc* __restrict__ descs, int pass) {
     __shared__ JpegHuff T[4];
     __shared__ unsigned long long ex[JD_LANES];
     const JpegDesc d = descs[blockIdx.y];
-    const int t = threadIdx.x, i = blockIdx.x * JD_LANES + t;
-    if ((int)blockIdx.x * JD_LANES >= d.nsub || pass >= d.passes) return;
-    if (pass > 0 && d.flags[pass - 1] == 0) return;           // the pass before changed nothing: every state is final
-    jd_load_tables(d.huff, T, t, JD_LANES);
-    const bool valid = i < d.nsub;
-    JdSub s{};
-    unsigned long long entry = 0, exit_ = 0;
-    int count = 0;
-    bool inv;
-    if (valid) {
-        s = jd_sub(d, i);
-        if (pass == 0) {
-            JdState st{s.start, 0, 0};
-            entry = jd_pack(st);
-            count = jd_run(d, T, s.b0, s.b1, st, s.end, 0x7fffffff, nullptr, 0, &inv);
-            exit_ = jd_pack(st);
-        } else {
-            entry = d.entry[i];
-            exit_ = d.exits[i];
-            count = d.count[i];
-        }
-    }
-    bool any = false;
-    for (int iter = 0; iter <= JD_LANES; ++iter) {
-        ex[t] = exit_;
-        __syncthreads();
-        bool ch = false;
-        if (valid && s.j > 0) {                               // subsequence 0 of a segment is exact by construction
-            unsigned long long prev = entry;
-            if (t > 0) prev = ex[t - 1];
-            else if (pass > 0) prev = __hip_atomic_load(&d.exits[i - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev != entry) {
-                entry = prev;
-                JdState st = jd_unpack(entry);
-                count = jd_run(d, T, s.b0, s.b1, st, s.end, 0x7fffffff, nullptr, 0, &inv);
-                exit_ = jd_pack(st);
-                ch = true;
-            }
-        }
-        if (!__syncthreads_or(ch)) break;
-        any = true;
-    }
-    if (valid) {
-        d.entry[i] = entry;
-        __hip_atomic_store(&d.exits[i], exit_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        d.count[i] = count;
-    }
-    if (t == 0 && (pass == 0 ? blockIdx.x == 0 : any)) d.flags[pass] = 1;
+    jpeg_sync_pass<JdCodec>(d, {T}, ex, pass);
 }
 
 // one workgroup per file
 __global__ void __launch_bounds__(256) jd_scan_kernel(const JpegDesc* __restrict__ descs) {
-    __shared__ int sh[256];
+    __shared__ long long sh[256];
     const JpegDesc d = descs[blockIdx.x];
-    const int t = threadIdx.x;
-    int carry = 0;
-    for (int base = 0; base < d.nsub; base += 256) {
-        const int i = base + t;
-        const int v = i < d.nsub ? d.count[i] : 0;
-        sh[t] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const int a = t >= o ? sh[t - o] : 0;
-            __syncthreads();
-            sh[t] += a;
-            __syncthreads();
-        }
-        if (i < d.nsub) d.scan[i] = carry + sh[t] - v;
-        carry += sh[255];
-        __syncthreads();
-    }
+    jpeg_prefix_pass<JdCodec>(d, sh);
 }
 
 __global__ void __launch_bounds__(JD_LANES) jd_write_kernel(const JpegDesc* __restrict__ descs) {
     __shared__ JpegHuff T[4];
     const JpegDesc d = descs[blockIdx.y];
-    const int t = threadIdx.x, i = blockIdx.x * JD_LANES + t;
-    if ((int)blockIdx.x * JD_LANES >= d.nsub) return;
-    jd_load_tables(d.huff, T, t, JD_LANES);
-    if (i >= d.nsub) return;
-    const JdSub s = jd_sub(d, i);
-    const unsigned long long entry = d.entry[i];
-    int err = 0;
-    if (s.j > 0 && d.exits[i - 1] != entry) err |= JD_ERR_SYNC;
-    const long long seg_first = (long long)s.seg * d.ri * d.bpm;
-    const long long seg_end = seg_first + (long long)min(d.ri, d.nmcu - s.seg * d.ri) * d.bpm;
-    const long long first = seg_first + (d.scan[i] - d.scan[d.seg_sub[s.seg]]);
-    d.first[i] = (int)min(first, (long long)d.nblocks);
-    const int room = (int)max(min(seg_end - first, (long long)d.nblocks), 0LL);
-    JdState st = jd_unpack(entry);
-    bool inv;
-    const int n = jd_run(d, T, s.b0, s.b1, st, s.end, room, d.coef, (int)min(first, (long long)d.nblocks), &inv);
-    if (inv) err |= JD_ERR_CODE;
-    if (n != d.count[i]) err |= JD_ERR_COUNT;
-    if (i + 1 == d.seg_sub[s.seg + 1] && (first + n != seg_end || st.b != 0 || st.z != 0)) err |= JD_ERR_COUNT;
-    if (err) atomicOr(d.status, err);
+    jpeg_write_pass<JdCodec>(d, {T});
 }
 
 // one workgroup per (segment, component, file): inclusive sum of the DC differences in MCU order

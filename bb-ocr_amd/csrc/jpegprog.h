@@ -1,20 +1,14 @@
 // Progressive JPEG (SOF2), the entropy side of one scan into the coefficient buffer of jpegdec.hip (int16 [blocks][64], natural order,
 // blocks in MCU order): T.81 G.1.2 as libjpeg-turbo's jdphuff.c carries it out (decode_mcu_DC_first, _AC_first, _DC_refine, _AC_refine),
 // stated by tests/jpeg_progressive_ref.py.  What decodes is here and compiles for the device and for the host: jp_run_first (a first scan
-// from any state, the unit of jpegprog.hip's speculative passes), jp_dc_refine_unit, jp_refine_walk (an AC refinement's symbol by mask
+// from any state, the unit of the speculative passes -- jpeg_spec.h's, with its state, subsequence lookup and zig-zag table), jp_dc_refine_unit, jp_refine_walk (an AC refinement's symbol by mask
 // arithmetic).  jp_decode_segment strings them together in the host's order, one restart segment after the other
 // (tools/jpegprog_hostcheck.cpp: the same routines under the sanitisers); jpegprog.hip runs them in the device's.
 // The bytes are untrusted: every stream read is clamped to the segment (past its end: 1-bits), every coefficient access is
 // index-checked, every loop's trip count is fixed by the plan (units of the segment, the band Ss .. Se, S + 32 symbols a subsequence).
 #pragma once
-#include <stdint.h>
-#include "kernels.h"
+#include "jpeg_spec.h"
 
-#if defined(__HIPCC__)
-#define JP_HD __host__ __device__ __forceinline__
-#else
-#define JP_HD inline
-#endif
 // The descriptor's pointers are global memory.  Read out of a structure they are generic to the compiler, and a generic access waits for
 // every store before it; the device build says what they are.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -23,34 +17,21 @@
 #define JP_GLOBAL
 #endif
 
-struct JpScan {                        // one scan of one file; the pointers are device memory (host memory in the host build)
-    const uint8_t* data;               // the scan's entropy-coded bytes without stuffing and restart markers, segment after segment
-    const int* seg_byte;               // [nseg + 1] first byte of each segment in `data`
+// One scan of one file; the pointers are device memory (host memory in the host build).  Every scan has data, seg_byte and nseg (0: the
+// file has no scan of this index); a first scan (Ah = 0) is cut into subsequences of S bits and decoded speculatively, as jpegdec.hip
+// decodes a baseline scan, and has the rest of JpegSubs too.  An end-of-band run counts its blocks at its symbol.
+struct JpScan : JpegSubs {
     const JpegHuff* huff;              // [ncs] per scan component: its DC table (Ss = 0) or AC table as it stood at this SOS
     short* coef;                       // the file's coefficient buffer
     int* status;                       // JD_ERR_* bits
     int nblocks;                       // blocks of the buffer
-    int nseg;                          // 0: the file has no scan of this index
     int ncs, comp[3];                  // scan components: their indices in the frame
     int Ss, Se, Ah, Al;
     int ri, nunits;                    // units a segment / in the scan: MCUs (ncs > 1) or the component's blocks
     int bw;                            // ncs == 1: blocks a row of the component's raster
     int ch, cv, coff;                  // ncs == 1: the component's blocks across / down an MCU, its first block in the MCU
     int hs, vs, bpm, mcux, ncomp;      // the frame: JpegDesc's
-    // a first scan (Ah = 0) is cut into subsequences of S bits and decoded speculatively, as jpegdec.hip decodes a baseline scan
-    const int* seg_sub;                // [nseg + 1] first subsequence of each segment
-    const int* sub_seg;                // [nsub] segment of each subsequence
-    unsigned long long* entry;         // [nsub] packed state (jp_pack) a lane starts from / ends in
-    unsigned long long* exits;
-    int* count;                        // [nsub] blocks completed by the subsequence (the blocks of an end-of-band run: at its symbol)
-    int* scan;                         // [nsub] exclusive scan of count
-    int* flags;                        // [passes] flags[k] != 0: synchronisation pass k changed a state
-    int nsub, S, passes;
 };
-
-constexpr unsigned char JP_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // The bit reader of one segment, bytes [b0, b1) of `d`: a 64-bit window over bytes wb .. wb + 7 (wb a multiple of 4) and the 32 bits
 // behind it, fetched one step ahead of their use so that the walk does not wait for them.
@@ -219,12 +200,8 @@ JP_HD int jp_ac_refine_block(int Ss, int Se, int Al, const JpegHuff& H, const un
     return 0;
 }
 
-// ---- the first scans (Ah = 0): DC first and AC first, decodable from any bit once the state there is known
-struct JpState { unsigned p; int b, z; };                          // bit in `data`, block in the unit (DC), zig-zag position in the band (AC)
-JP_HD unsigned long long jp_pack(const JpState& s) {
-    return (unsigned long long)s.p | ((unsigned long long)(unsigned)s.b << 32) | ((unsigned long long)(unsigned)s.z << 40);
-}
-JP_HD JpState jp_unpack(unsigned long long v) { return JpState{(unsigned)v, (int)((v >> 32) & 7), (int)((v >> 40) & 63)}; }
+// ---- the first scans (Ah = 0): DC first and AC first, decodable from any bit once the state there is known -- jpeg_spec.h's JpegState:
+// the bit in `data`, the block in the unit (DC), the zig-zag position in the band (AC)
 JP_HD int jp_unit_total(const JpScan& sc) {
     int n = 0;
     for (int ci = 0; ci < sc.ncs && ci < 3; ++ci) n += jp_unit_blocks(sc, ci);
@@ -247,13 +224,15 @@ JP_HD long long jp_ordinal_block(const JpScan& sc, int bpu, long long o) {
     return jp_block(sc, (int)(o / bpu), ci, j);
 }
 // The start state of a segment: block 0 of the unit, the band's first coefficient.
-JP_HD JpState jp_start(const JpScan& sc, unsigned p) { return JpState{p, 0, sc.Ss}; }
+JP_HD JpegState jp_start(const JpScan& sc, unsigned p) { return JpegState{p, 0, sc.Ss}; }
+// ... and where its last subsequence, bits [.., b1 * 8), must end: there again, less than a byte of padding left
+JP_HD bool jp_at_end(const JpScan& sc, const JpegState& st, unsigned b1) { return st.b == 0 && st.z == sc.Ss && st.p <= b1 * 8u && b1 * 8u - st.p < 8u; }
 
 // Decode from st while its bit is before `end` and fewer than max_blocks blocks are complete.  Returns the blocks completed; an
 // end-of-band run counts its blocks at its symbol, since they take no bits -- the state stays (bit, place in the band).  *invalid: a
 // pattern without a code, a DC category above 15 or a coefficient behind the block; *over: a run that leaves the max_blocks.  store:
 // coefficients of block first + n (in scan order) are stored, DC terms as differences.  At most S + 32 symbols: each takes a bit.
-JP_HD int jp_run_first(const JpScan& sc, const JpegHuff* T, const unsigned char* ZZ, int bpu, unsigned b0, unsigned b1, JpState& st, unsigned end,
+JP_HD int jp_run_first(const JpScan& sc, const JpegHuff* T, const unsigned char* ZZ, int bpu, unsigned b0, unsigned b1, JpegState& st, unsigned end,
                        int max_blocks, bool store, long long first, bool* invalid, bool* over) {
     JpBits s = jp_open_at(sc.data, b0, b1, st.p);
     JP_GLOBAL short* coef = (JP_GLOBAL short*)sc.coef;
@@ -314,7 +293,8 @@ JP_HD long long jp_dc_item_block(const JpScan& sc, int seg, int ci, int i) {
     return jp_block(sc, seg * sc.ri + i / nb, ci, i % nb);
 }
 
-// ZZ: JP_ZZ.
+// One restart segment in the host's order.  ZZ: JPEG_ZZ.  A first scan goes subsequence by subsequence through jpeg_spec.h's lookup and
+// packed state, as the device's lanes do one beside the other.
 JP_HD int jp_decode_segment(const JpScan& sc, const JpegHuff* T, const unsigned char* ZZ, int seg) {
     if (seg < 0 || seg >= sc.nseg || sc.ri < 1 || sc.bw < 1 || sc.ch < 1 || sc.cv < 1) return JD_ERR_COUNT;
     const JP_GLOBAL int* seg_byte = (const JP_GLOBAL int*)sc.seg_byte;
@@ -329,19 +309,21 @@ JP_HD int jp_decode_segment(const JpScan& sc, const JpegHuff* T, const unsigned 
         return err;
     }
     if (Ah == 0) {                                                    // the host's order of the device's subsequences: one after the other
-        const int bpu = jp_unit_total(sc), S = sc.S < 32 ? 32 : sc.S;
-        const unsigned b0 = (unsigned)seg_byte[seg], b1 = (unsigned)seg_byte[seg + 1];
-        JpState st = jp_start(sc, b0 * 8u);
+        const int bpu = jp_unit_total(sc);
+        const unsigned b1 = (unsigned)seg_byte[seg + 1];
+        unsigned long long state = jpeg_pack(jp_start(sc, (unsigned)seg_byte[seg] * 8u));   // packed, as a lane hands it to its neighbour
         long long done = 0;
         const long long want = (long long)nu * bpu;
-        for (unsigned a = b0 * 8u; (a < b1 * 8u || a == b0 * 8u) && !err; a += (unsigned)S) {
+        for (int i = sc.seg_sub[seg]; i < sc.seg_sub[seg + 1] && !err; ++i) {
             bool invalid, over;
-            const unsigned end = a + (unsigned)S < b1 * 8u ? a + (unsigned)S : b1 * 8u;
-            done += jp_run_first(sc, T, ZZ, bpu, b0, b1, st, end, (int)(want - done), true, u0 * bpu + done, &invalid, &over);
+            const JpegSub s = jpeg_sub(sc, i);
+            JpegState st = jpeg_unpack(state);
+            done += jp_run_first(sc, T, ZZ, bpu, s.b0, s.b1, st, s.end, (int)(want - done), true, u0 * bpu + done, &invalid, &over);
+            state = jpeg_pack(st);
             if (invalid) err = JD_ERR_CODE;
             else if (over) err = JD_ERR_COUNT;
         }
-        if (!err && (done != want || st.b != 0 || st.z != Ss || st.p > b1 * 8u || b1 * 8u - st.p >= 8u)) err = JD_ERR_COUNT;
+        if (!err && (done != want || !jp_at_end(sc, jpeg_unpack(state), b1))) err = JD_ERR_COUNT;
         if (dc && !err)
             for (int ci = 0; ci < sc.ncs && ci < 3; ++ci) {
                 unsigned sum = 0;

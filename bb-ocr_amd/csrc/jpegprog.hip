@@ -1,5 +1,6 @@
 // Progressive JPEG decoding on the device: the entropy stages of the scans of one dependency level over a batch (jpegdec.cpp).
-//   first scans (DC first, AC first)   jpegdec.hip's speculative scheme on jpegprog.h's jp_run_first: jp_sync (one lane per S-bit
+//   first scans (DC first, AC first)   jpegdec.hip's speculative scheme -- jpeg_spec.h's passes, here over jpegprog.h's jp_run_first
+//               (JpCodec) --: jp_sync (one lane per S-bit
 //               subsequence decodes from the assumed state, then from its left neighbour's exit state until no state changes), jp_prefix
 //               (first block of every subsequence), jp_write (decode from the exact states into the coefficient buffer), jp_dc (a DC
 //               scan's running sums per component and restart segment, shifted by Al).  A DC block ends after its symbol; the blocks of
@@ -15,134 +16,49 @@ namespace {
 
 __device__ __forceinline__ bool jp_first(const JpScan& sc) { return sc.nseg > 0 && sc.Ah == 0; }
 
-__device__ __forceinline__ void jp_load_tables(const JpScan& sc, JpegHuff* T, unsigned char* ZZ, int t, int nt) {
-    const int ncs = min(max(sc.ncs, 0), 3);
-    const int* src = (const int*)sc.huff;
-    int* dst = (int*)T;
-    for (int i = t; i < ncs * (int)(sizeof(JpegHuff) / 4); i += nt) dst[i] = src[i];
-    if (t < 64) ZZ[t] = JP_ZZ[t];
-    __syncthreads();
-}
+// A first scan as jpeg_spec.h's passes see it: units are MCUs or the component's blocks, a segment starts at the band's first
+// coefficient of block 0 and must end there with less than a byte left; an end-of-band run may leave the segment (`over`).
+struct JpCodec {
+    using Desc = JpScan;
+    struct Lds { JpegHuff* T; unsigned char* ZZ; };            // T[3], ZZ[64] of the kernel's LDS
+    static __device__ __forceinline__ bool cut(const JpScan& sc) { return jp_first(sc); }
+    static __device__ __forceinline__ void load(const JpScan& sc, const Lds& lds, int t, int nt) {
+        const int ncs = min(max(sc.ncs, 0), 3);
+        const int* src = (const int*)sc.huff;
+        int* dst = (int*)lds.T;
+        for (int i = t; i < ncs * (int)(sizeof(JpegHuff) / 4); i += nt) dst[i] = src[i];
+        if (t < 64) lds.ZZ[t] = JPEG_ZZ[t];
+        __syncthreads();
+    }
+    static __device__ __forceinline__ int unit_blocks(const JpScan& sc) { return jp_unit_total(sc); }
+    static __device__ __forceinline__ int units(const JpScan& sc) { return sc.nunits; }
+    static __device__ __forceinline__ JpegState start(const JpScan& sc, unsigned p) { return jp_start(sc, p); }
+    static __device__ __forceinline__ int run(const JpScan& sc, const Lds& lds, int bpu, const JpegSub& s, JpegState& st, int max_blocks, bool store,
+                                              long long first, bool* invalid, bool* over) {
+        return jp_run_first(sc, lds.T, lds.ZZ, bpu, s.b0, s.b1, st, s.end, max_blocks, store, first, invalid, over);
+    }
+    static __device__ __forceinline__ bool at_end(const JpScan& sc, const JpegState& st, const JpegSub& s) { return jp_at_end(sc, st, s.b1); }
+    static __device__ __forceinline__ void note_first(const JpScan&, int, long long) {}
+};
 
-struct JpSub { int seg, j; unsigned b0, b1, start, end; };
-__device__ __forceinline__ JpSub jp_sub(const JpScan& sc, int i) {
-    JpSub s;
-    s.seg = min(max(sc.sub_seg[i], 0), sc.nseg - 1);
-    s.j = i - sc.seg_sub[s.seg];
-    s.b0 = (unsigned)sc.seg_byte[s.seg];
-    s.b1 = (unsigned)sc.seg_byte[s.seg + 1];
-    s.start = s.b0 * 8u + (unsigned)s.j * (unsigned)sc.S;
-    s.end = min(s.start + (unsigned)sc.S, s.b1 * 8u);
-    return s;
-}
-
-// jpegdec.hip's jd_sync_kernel on a first scan: launched once more per workgroup a scan spans, a launch returning at once when the
-// launch before it changed nothing
-__global__ void __launch_bounds__(64) jp_sync_kernel(const JpScan* __restrict__ scans, int pass) {
+// the descriptor in place: a copy would live in scratch
+__global__ void __launch_bounds__(JD_LANES) jp_sync_kernel(const JpScan* __restrict__ scans, int pass) {
     __shared__ JpegHuff T[3];
     __shared__ unsigned char ZZ[64];
-    __shared__ unsigned long long ex[64];
-    const JpScan& sc = scans[blockIdx.y];
-    const int t = threadIdx.x, i = blockIdx.x * 64 + t;
-    if (!jp_first(sc) || (int)blockIdx.x * 64 >= sc.nsub || pass >= sc.passes) return;
-    if (pass > 0 && sc.flags[pass - 1] == 0) return;           // the pass before changed nothing: every state is final
-    jp_load_tables(sc, T, ZZ, t, 64);
-    const int bpu = jp_unit_total(sc);
-    const bool valid = i < sc.nsub;
-    JpSub s{};
-    unsigned long long entry = 0, exit_ = 0;
-    int count = 0;
-    bool inv, over;
-    if (valid) {
-        s = jp_sub(sc, i);
-        if (pass == 0) {
-            JpState st = jp_start(sc, s.start);
-            entry = jp_pack(st);
-            count = jp_run_first(sc, T, ZZ, bpu, s.b0, s.b1, st, s.end, 0x7fffffff, false, 0, &inv, &over);
-            exit_ = jp_pack(st);
-        } else {
-            entry = sc.entry[i];
-            exit_ = sc.exits[i];
-            count = sc.count[i];
-        }
-    }
-    bool any = false;
-    for (int iter = 0; iter <= 64; ++iter) {
-        ex[t] = exit_;
-        __syncthreads();
-        bool ch = false;
-        if (valid && s.j > 0) {                                // subsequence 0 of a segment is exact by construction
-            unsigned long long prev = entry;
-            if (t > 0) prev = ex[t - 1];
-            else if (pass > 0) prev = __hip_atomic_load(&sc.exits[i - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev != entry) {
-                entry = prev;
-                JpState st = jp_unpack(entry);
-                count = jp_run_first(sc, T, ZZ, bpu, s.b0, s.b1, st, s.end, 0x7fffffff, false, 0, &inv, &over);
-                exit_ = jp_pack(st);
-                ch = true;
-            }
-        }
-        if (!__syncthreads_or(ch)) break;
-        any = true;
-    }
-    if (valid) {
-        sc.entry[i] = entry;
-        __hip_atomic_store(&sc.exits[i], exit_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sc.count[i] = count;
-    }
-    if (t == 0 && (pass == 0 ? blockIdx.x == 0 : any)) sc.flags[pass] = 1;
+    __shared__ unsigned long long ex[JD_LANES];
+    jpeg_sync_pass<JpCodec>(scans[blockIdx.y], {T, ZZ}, ex, pass);
 }
 
-// one workgroup per scan: exclusive scan of the block counts
+// one workgroup per scan
 __global__ void __launch_bounds__(256) jp_prefix_kernel(const JpScan* __restrict__ scans) {
     __shared__ long long sh[256];
-    const JpScan& sc = scans[blockIdx.x];
-    if (!jp_first(sc)) return;
-    const int t = threadIdx.x;
-    long long carry = 0;
-    for (int base = 0; base < sc.nsub; base += 256) {
-        const int i = base + t;
-        const long long v = i < sc.nsub ? sc.count[i] : 0;
-        sh[t] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const long long a = t >= o ? sh[t - o] : 0;
-            __syncthreads();
-            sh[t] += a;
-            __syncthreads();
-        }
-        if (i < sc.nsub) sc.scan[i] = (int)min(carry + sh[t] - v, 0x7fffffffLL);      // runs of a damaged stream may sum past the scan: saturate
-        carry += sh[255];
-        __syncthreads();
-    }
+    jpeg_prefix_pass<JpCodec>(scans[blockIdx.x], sh);
 }
 
-__global__ void __launch_bounds__(64) jp_write_kernel(const JpScan* __restrict__ scans) {
+__global__ void __launch_bounds__(JD_LANES) jp_write_kernel(const JpScan* __restrict__ scans) {
     __shared__ JpegHuff T[3];
     __shared__ unsigned char ZZ[64];
-    const JpScan& sc = scans[blockIdx.y];
-    const int t = threadIdx.x, i = blockIdx.x * 64 + t;
-    if (!jp_first(sc) || (int)blockIdx.x * 64 >= sc.nsub) return;
-    jp_load_tables(sc, T, ZZ, t, 64);
-    if (i >= sc.nsub) return;
-    const int bpu = jp_unit_total(sc);
-    const JpSub s = jp_sub(sc, i);
-    const unsigned long long entry = sc.entry[i];
-    int err = 0;
-    if (s.j > 0 && sc.exits[i - 1] != entry) err |= JD_ERR_SYNC;
-    const long long seg_first = (long long)s.seg * sc.ri * bpu;
-    const long long seg_end = seg_first + (long long)min(sc.ri, sc.nunits - s.seg * sc.ri) * bpu;
-    const long long first = seg_first + ((long long)sc.scan[i] - sc.scan[sc.seg_sub[s.seg]]);
-    const int room = (int)max(min(seg_end - first, 0x7fffffffLL), 0LL);
-    JpState st = jp_unpack(entry);
-    bool inv, over;
-    const int n = jp_run_first(sc, T, ZZ, bpu, s.b0, s.b1, st, s.end, room, true, first, &inv, &over);
-    if (inv) err |= JD_ERR_CODE;
-    if (over || n != sc.count[i]) err |= JD_ERR_COUNT;
-    if (i + 1 == sc.seg_sub[s.seg + 1] &&
-        (first + n != seg_end || st.b != 0 || st.z != sc.Ss || st.p > s.b1 * 8u || s.b1 * 8u - st.p >= 8u)) err |= JD_ERR_COUNT;
-    if (err) atomicOr(sc.status, err);
+    jpeg_write_pass<JpCodec>(scans[blockIdx.y], {T, ZZ});
 }
 
 // one wavefront per (segment, scan component, scan) of a DC first scan: inclusive sum of the differences in scan order, 64 at a time
@@ -269,7 +185,7 @@ __global__ void __launch_bounds__(64) jp_scan_kernel(const JpScan* __restrict__ 
     const int* src = (const int*)sc.huff;
     int* dst = (int*)T;
     for (int i = t; i < (int)(sizeof(JpegHuff) / 4); i += 64) dst[i] = src[i];
-    ZZ[t] = JP_ZZ[t];
+    ZZ[t] = JPEG_ZZ[t];
     __syncthreads();
     const int err = jp_ac_refine_wave(sc, T[0], ZZ, seg, t);
     if (err && t == 0) atomicOr(sc.status, err);

@@ -436,17 +436,20 @@ struct JpegComp {                                              // one component'
     int valid_rows, valid_cols;                                // the extent the output stage reads
     int up;                                                    // JD_UP_*
 };
-struct JpegDesc {                                              // one file of a batch; every pointer is device memory
+struct JpegSubs {                                              // a scan cut into subsequences of S bits for the speculative passes (jpeg_spec.h)
     const uint8_t* data;                                       // entropy-coded bytes without stuffing and restart markers, segment after segment
     const int* seg_byte;                                       // [nseg + 1] first byte of each segment in `data`
     const int* seg_sub;                                        // [nseg + 1] first subsequence of each segment
     const int* sub_seg;                                        // [nsub] segment of each subsequence
-    unsigned long long* entry;                                 // [nsub] packed state (jd_pack) a lane starts from / ends in
+    unsigned long long* entry;                                 // [nsub] packed state (jpeg_pack) a lane starts from / ends in
     unsigned long long* exits;
     int* count;                                                // [nsub] blocks completed by the subsequence
-    int* scan;                                                 // [nsub] exclusive scan of count over the file
+    int* scan;                                                 // [nsub] exclusive scan of count over the scan
+    int* flags;                                                // [passes] flags[k] != 0: synchronisation pass k changed a state
+    int nseg, nsub, S, passes;
+};
+struct JpegDesc : JpegSubs {                                   // one file of a batch and its one scan; every pointer is device memory
     int* first;                                                // [nsub] first output block (written by the write pass)
-    int* flags;                                                // [passes + 1] flags[k] != 0: pass k changed a state
     int* status;                                               // JD_ERR_* bits
     short* coef;                                               // [nblocks][64] natural order, MCU block order
     uint8_t* plane[3];                                         // Y, Cb, Cr of this pass: comp[c].plane_rows rows of comp[c].pitch samples
@@ -456,7 +459,7 @@ struct JpegDesc {                                              // one file of a 
     int OW, OH;
     const JpegHuff* huff;                                      // [4]: DC 0, DC 1, AC 0, AC 1
     const unsigned short* quant;                               // [ncomp][64] natural order
-    int W, H, ncomp, bpm, mcux, mcuy, nmcu, ri, nseg, nsub, S, nblocks, px, passes;
+    int W, H, ncomp, bpm, mcux, mcuy, nmcu, ri, nblocks, px;
     int hs, vs;                                                // luma blocks of an MCU across / down: bpm = hs * vs + 2 (1 component: 1, 1, bpm 1)
     int tab_dc[3], tab_ac[3];                                  // per component: index into huff
 };
