@@ -241,7 +241,9 @@ def get_det_boxes_core(textmap, linkmap, text_threshold=0.7, link_threshold=0.4,
         if size < 10:
             continue
         comp = labels[y:y + h, x:x + w] == k
-        if np.max(textmap[y:y + h, x:x + w][comp]) < text_threshold:
+        # numpy 1.26 (pinned upstream) compares the f32 maximum with the python float in f64: f32(0.7) < 0.7.  NEP 50 (numpy 2) would
+        # round the threshold to f32 instead
+        if float(np.max(textmap[y:y + h, x:x + w][comp])) < float(text_threshold):
             continue
         seg = comp & (text_score[y:y + h, x:x + w] == 1)     # link-only pixels removed
         niter = int(math.sqrt(size * min(w, h) / (w * h)) * 2)

@@ -51,6 +51,15 @@ def test_detect_dims_match_resize_aspect_ratio(lib, H, W, canvas):
     assert (v[3].value, v[2].value) == size_heatmap and r.value == ratio
     if (H, W) == (3504, 2480):
         assert (v[0].value, v[1].value) == (2560, 1824)        # A4 @300 dpi
+    # mag_ratio off its default: shrinking, enlarging, and mag * max(H, W) beyond the canvas (which then caps the target)
+    capped = 0
+    for mag in (0.5, 0.6, 1.5, 2.0):
+        assert lib.bbocr_detect_dims(H, W, canvas, mag, *[C.byref(x) for x in v], C.byref(r)) == 0
+        canvas_img, ratio, size_heatmap = imgproc.resize_aspect_ratio(np.zeros((H, W, 3), np.uint8), canvas, mag)
+        assert (v[0].value, v[1].value) == canvas_img.shape[:2], mag
+        assert (v[3].value, v[2].value) == size_heatmap and r.value == ratio, mag
+        capped += mag * max(H, W) > canvas
+    assert capped == {(960, 1280, 2560): 0, (3504, 2480, 2560): 2, (971, 1014, 2560): 0, (300, 500, 320): 2, (64, 96, 2560): 0}[(H, W, canvas)]
 
 
 def test_errors_are_status_codes_not_aborts(lib):

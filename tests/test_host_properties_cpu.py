@@ -54,8 +54,9 @@ def _polys(draw):
 
 @settings(max_examples=150, deadline=None, suppress_health_check=[HealthCheck.too_slow, HealthCheck.function_scoped_fixture])
 @given(polys=_polys(), width_ths=st.sampled_from([0.5, 1.0, 0.0]), add_margin=st.sampled_from([0.1, 0.0, 0.3]), min_size=st.sampled_from([20, 0, 60]),
-       slope_ths=st.sampled_from([0.1, 0.0, 0.5]))
-def test_group_text_box_matches_oracle(lib, polys, width_ths, add_margin, min_size, slope_ths):
+       slope_ths=st.sampled_from([0.1, 0.0, 0.5]), ycenter_ths=st.sampled_from([0.5, 0.0, 0.2, 1.5]),
+       height_ths=st.sampled_from([0.5, 0.0, 0.1, 2.0]))
+def test_group_text_box_matches_oracle(lib, polys, width_ths, add_margin, min_size, slope_ths, ycenter_ths, height_ths):
     """utils.group_text_box + Reader.detect's min_size filter: C++ (boxpost.cpp) == oracle on arbitrary polygon lists, in order."""
     from bb_ocr_amd import _lib
     from oracle import boxes as obox
@@ -63,6 +64,7 @@ def test_group_text_box_matches_oracle(lib, polys, width_ths, add_margin, min_si
     p = _lib.bbocr_params()
     lib.bbocr_default_params(C.byref(p))
     p.width_ths, p.add_margin, p.min_size, p.slope_ths = width_ths, add_margin, min_size, slope_ths
+    p.ycenter_ths, p.height_ths = ycenter_ths, height_ths
     arr = np.array(polys, dtype=np.int32).reshape(-1, 8)
     bl = C.POINTER(_lib.bbocr_boxlist)()
     ptr = arr.ctypes.data_as(C.POINTER(C.c_int)) if len(arr) else None
@@ -71,7 +73,7 @@ def test_group_text_box_matches_oracle(lib, polys, width_ths, add_margin, min_si
     hori = [[b.hori[i * 4 + k] for k in range(4)] for i in range(b.hori_off[1])]
     free = [[b.free_q[i * 8 + k] for k in range(8)] for i in range(b.free_off[1])]
     lib.bbocr_free_boxlist(bl)
-    oh, of = obox.group_text_box([list(map(int, q)) for q in polys], slope_ths, 0.5, 0.5, width_ths, add_margin)
+    oh, of = obox.group_text_box([list(map(int, q)) for q in polys], slope_ths, ycenter_ths, height_ths, width_ths, add_margin)
     oh = [i for i in oh if max(i[1] - i[0], i[3] - i[2]) > min_size]
     of = [i for i in of if max(max(c[0] for c in i) - min(c[0] for c in i), max(c[1] for c in i) - min(c[1] for c in i)) > min_size]
     assert hori == [list(map(int, x)) for x in oh]
