@@ -15,10 +15,11 @@ LIB_PATH = os.environ.get("BBOCR_LIB_PATH") or os.path.join(_HERE, "libbbocr.so"
 
 class bbocr_config(C.Structure):
     _fields_ = [("device", C.c_int), ("det_sub_batch", C.c_int), ("rec_max_cols", C.c_int), ("precision", C.c_int), ("call_slots", C.c_int),
-                ("host_threads", C.c_int), ("rec_quant", C.c_int), ("reserved", C.c_int * 1)]
+                ("host_threads", C.c_int), ("rec_quant", C.c_int), ("rec_classes", C.c_int)]
 
 
 PRECISIONS = {"bf16": 0, "fp16": 1, "exact": 2, "mixed": 3, "exact_rec": 4}
+REC_CLASSES_MAX = 8192                                                           # bbocr.h BBOCR_REC_CLASSES_MAX
 BEAM_DEVICE_MAX = 32                                                             # bbocr.h BBOCR_BEAM_DEVICE_MAX
 PAGE_GRAY, PAGE_BGR, PAGE_RGB, PAGE_YCBCR4, PAGE_YCBCR3 = 0, 1, 2, 3, 4          # bbocr.h BBOCR_PAGE_*: layouts of a device page
 PNG_CHUNK = 16384                                                                # bbocr.h BBOCR_PNG_CHUNK
@@ -155,6 +156,8 @@ PROTOTYPES = {
     "bbocr_free_boxlist": (None, [C.POINTER(bbocr_boxlist)]),
     "bbocr_free_result": (None, [C.POINTER(bbocr_result)]),
     "bbocr_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "bbocr_last_ctc_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "bbocr_set_class_mask": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_int]),
     "bbocr_set_profiling": (C.c_int, [_vp, C.c_int]),
     "bbocr_conv_profile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "bbocr_host_cpu_share": (C.c_int, []),
@@ -173,6 +176,9 @@ PROTOTYPES = {
     "bbocr_op_ctc": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                C.POINTER(C.c_uint), C.c_int]),
     "bbocr_op_ctc_probs": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_uint), _vp]),
+    "bbocr_op_ctc_rows": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "bbocr_op_pred": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),
+    "bbocr_op_pred_ctc": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp]),
     "bbocr_op_ctc_beam": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int)]),
     "bbocr_op_resize_u8": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int]),

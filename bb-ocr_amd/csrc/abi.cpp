@@ -28,7 +28,10 @@ int bbocr_create(const bbocr_config* cfg, bbocr_ctx** out) {
         c->root = c;
         if (cfg) c->cfg = *cfg;
         if (c->cfg.precision < BBOCR_PREC_BF16 || c->cfg.precision > BBOCR_PREC_EXACT_REC || c->cfg.call_slots < 0 || c->cfg.call_slots > kMaxSlots ||
-            c->cfg.rec_quant < 0 || c->cfg.rec_quant > 1 || (c->cfg.rec_quant == 1 && !rec_split(c))) {     // rec_quant quantises the exact conv stack's features
+            c->cfg.rec_quant < 0 || c->cfg.rec_quant > 1 || (c->cfg.rec_quant == 1 && !rec_split(c)) ||     // rec_quant quantises the exact conv stack's features
+            c->cfg.rec_classes < 0 || rec_classes(c) < 2 || rec_classes(c) > BBOCR_REC_CLASSES_MAX ||
+            // the int8 sequence half is built, packed and tested for english_g2's 97 classes in 112 stored columns: any other count is out of its scope
+            (c->cfg.rec_quant == 1 && rec_classes(c) != kRecClassesDefault)) {
             delete c;                      // an unknown value must not silently mean one of the modes
             return BBOCR_ERR_ARG;
         }
@@ -88,7 +91,7 @@ void slot_destroy(bbocr_ctx* c) {
                       &c->ccl_counters, &c->crop_desc, &c->crop_desc2, &c->crop_scratch, &c->crop_hscratch, &c->crop_wscratch, &c->crop_luts, &c->crop_hist,
                       &c->ctc_idx, &c->ctc_pmax, &c->ctc_out_idx, &c->ctc_out, &c->seq_v, &c->seq_xp, &c->seq_h, &c->seq_lin, &c->seq_logits,
                       &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out, &c->pe_out,
-                      &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp};
+                      &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp, &c->ctc_mask};
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->seq_stream) (void)hipStreamDestroy(c->seq_stream);
@@ -97,19 +100,29 @@ void slot_destroy(bbocr_ctx* c) {
 
 // stage times of the call a thread has just finished (bbocr_stage_times): per calling thread, because one context serves several
 namespace {
-struct ThreadTimes { const bbocr_ctx* root = nullptr; float ms[8] = {0}; };
+struct ThreadTimes { const bbocr_ctx* root = nullptr; float ms[8] = {0}; int ctc_route = -1; };
 thread_local ThreadTimes tl_times;
 thread_local std::string tl_err;
+struct ThreadMask { const bbocr_ctx* root = nullptr; std::vector<unsigned int> words; };
+thread_local ThreadMask tl_mask;       // bbocr_set_class_mask: the calling thread's class mask for ONE context (the last it set one on)
 }  // namespace
+const unsigned int* thread_class_mask(const bbocr_ctx* root, int* n_words) {
+    const bool mine = tl_mask.root == root && !tl_mask.words.empty();
+    *n_words = mine ? (int)tl_mask.words.size() : 0;
+    return mine ? tl_mask.words.data() : nullptr;
+}
 void publish_times(const bbocr_ctx* s) {
     tl_times.root = s->root;
     memcpy(tl_times.ms, s->times, sizeof(tl_times.ms));
+    tl_times.ctc_route = s->ctc_last_route;
 }
 
 extern "C" {
 
 void bbocr_destroy(bbocr_ctx* c) {
     if (!c) return;
+    if (tl_mask.root == c) tl_mask = ThreadMask();      // a context created later at this address must not inherit the calling thread's mask
+    if (tl_times.root == c) tl_times = ThreadTimes();
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     dist_release(c);
@@ -341,6 +354,25 @@ void bbocr_free_result(bbocr_result* r) {
     if (!r) return;
     free(r->box_off); free(r->quads); free(r->is_free); free(r->text_off); free(r->text_idx); free(r->conf);
     free(r);
+}
+
+int bbocr_set_class_mask(bbocr_ctx* ctx, const uint32_t* words, int n_words) {
+    // no call slot: nothing of the context is touched but its error text; the mask waits in the calling thread for its next pipeline call
+    return status_of(ctx, [&] {
+        if (!rec_wide(ctx)) fail(BBOCR_ERR_ARG, "bbocr_set_class_mask is for contexts of more than 128 classes; bbocr_params::ignore_mask rules here");
+        const int C = rec_classes(ctx), max_words = (C + 31) / 32;
+        if (n_words < 0 || n_words > max_words || (n_words > 0 && !words)) fail(BBOCR_ERR_ARG, "class mask: 0 .. " + std::to_string(max_words) + " words");
+        if (n_words > 0 && (words[0] & 1u)) fail(BBOCR_ERR_ARG, "the CTC blank (class 0) cannot be ignored");
+        if (n_words == max_words && (C & 31) && (words[n_words - 1] >> (C & 31))) fail(BBOCR_ERR_ARG, "class mask: a bit behind the last class is set");
+        tl_mask.root = n_words > 0 ? ctx : nullptr;
+        tl_mask.words.assign(words, words + n_words);
+    });
+}
+
+int bbocr_last_ctc_route(bbocr_ctx* ctx, int* route) {
+    if (!ctx || !route) return BBOCR_ERR_ARG;
+    *route = tl_times.root == ctx ? tl_times.ctc_route : -1;
+    return BBOCR_OK;
 }
 
 int bbocr_set_profiling(bbocr_ctx* ctx, int on) {

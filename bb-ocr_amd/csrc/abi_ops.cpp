@@ -296,7 +296,9 @@ int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW
         rec_plan_part(jobs, all, 0, 0, part);
         const size_t rows = part.rows, rows_pad = align_up(rows, 256);
         ctx->seq_v.ensure(rows_pad * 256 * 2 * (rec_split(ctx) ? 2 : 1));
-        ctx->seq_logits.ensure(rows_pad * 112 * 4);
+        const size_t cs = (size_t)rec_cs(ctx);
+        if (rec_wide(ctx) && rows_pad * cs * 4 > ((size_t)1 << 30)) fail(BBOCR_ERR_ARG, "crop batch too large: the logits of a wide model are kept at or below 1 GiB");
+        ctx->seq_logits.ensure(rows_pad * cs * 4);
         const CropDesc* dd = rec_upload_descs(ctx, part, ctx->crop_desc);
         uint16_t* wide = rec_wide_image(ctx, part);
         HIPCHK(hipMemsetAsync(wide, 0, 64 * part.cols * 2, ctx->stream));
@@ -313,7 +315,7 @@ int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW
         HIPCHK(hipMemcpyAsync(tiles_dev, run.tiles.data(), run.tiles.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(seqs_dev, run.seqs.data(), run.seqs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
         crnn_sequence(ctx, rows, rows_pad, tiles_dev, (int)(run.tiles.size() / 4), seqs_dev, (int)(run.seqs.size() / 2), (float*)ctx->seq_logits.p);
-        HIPCHK(hipMemcpyAsync(dev_logits, ctx->seq_logits.p, rows * 112 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dev_logits, ctx->seq_logits.p, rows * cs * 4, hipMemcpyDeviceToDevice, ctx->stream));
         slot_sync(ctx, ctx->stream);
     });
 }
@@ -342,7 +344,7 @@ int bbocr_op_qlinear(bbocr_ctx* ctx, const float* dev_x, int rows, const int* se
         if (!dev_x || !dev_out || !dev_codes || !seg_params || layer < 0 || layer > 4) fail(BBOCR_ERR_ARG, "bad qlinear arguments");
         const int* seqs_dev = q8_op_seqs(ctx, seqs, nseq, rows, {});
         const bbocr_ctx::Q8Layer& L = layer < 2 ? ctx->q_ih[layer] : (layer < 4 ? ctx->q_lin[layer - 2] : ctx->q_pred);
-        const int K = (layer == 2 || layer == 3) ? 512 : 256, N = layer < 2 ? 2048 : (layer < 4 ? 256 : 112);
+        const int K = (layer == 2 || layer == 3) ? 512 : 256, N = layer < 2 ? 2048 : (layer < 4 ? 256 : rec_cs(ctx));
         const size_t rows_pad = align_up((size_t)rows, 256);
         ctx->seq_q8.ensure(rows_pad * 512);
         ctx->seq_rowp.ensure(rows_pad * 16);
@@ -373,20 +375,40 @@ int bbocr_op_qlstm(bbocr_ctx* ctx, const float* dev_g, int rows, const int* seqs
     });
 }
 
+// classes a CTC entry point takes on this context: beyond 128 only where the context itself is that wide (bbocr_config::rec_classes) -- on
+// an english_g2 context a wider C stays the argument error it always was
+static int op_ctc_max_classes(const bbocr_ctx* ctx) { return rec_wide(ctx) ? BBOCR_REC_CLASSES_MAX : 128; }
+
+// the host class mask of a CTC entry point over more than 128 classes -> the slot's device words (ceil(C / 32)); null: no mask, or C <= 128
+// (launch_ctc takes its four words by value).  The callers end synchronised.
+static const unsigned int* op_wide_mask(bbocr_ctx* ctx, int C, const unsigned int* host_words) {
+    if (C <= 128 || !host_words) return nullptr;
+    const size_t bytes = (size_t)(C + 31) / 32 * 4;
+    ctx->ctc_mask.ensure(bytes);
+    HIPCHK(hipMemcpyAsync(ctx->ctc_mask.p, host_words, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return (const unsigned int*)ctx->ctc_mask.p;
+}
+
 int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, int cs, int* text_off, int* text_idx, double* conf,
                  const unsigned int* ignore_mask, int beam_width) {
     return guarded(ctx, [&](bbocr_ctx* ctx) {
-        if (!dev_logits || !text_off || !text_idx || !conf || n <= 0 || T <= 0 || C <= 0 || C > cs) fail(BBOCR_ERR_ARG, "bad ctc arguments");
+        if (!dev_logits || !text_off || !text_idx || !conf || n <= 0 || T <= 0 || C <= 0 || C > cs || C > op_ctc_max_classes(ctx)) fail(BBOCR_ERR_ARG, "bad ctc arguments");
         const size_t rows = (size_t)n * T;
+        const unsigned int* mask_dev = op_wide_mask(ctx, C, ignore_mask);
         std::vector<int> seqs;
         for (int i = 0; i < n; ++i) { seqs.push_back(i * T); seqs.push_back(T); }
         const int route = ctc_route(beam_width, C, seqs.data(), n);       // as rec_finish routes a recognition pass
         ctc_size(ctx, rows, n, cs, route);
         ctx->seq_tables.ensure(seqs.size() * 4);
         HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, n, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
-                          (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask,
-                          route != CTC_GREEDY ? (float*)ctx->ctc_probs.p : nullptr));
+        if (C > 128)
+            HIPCHK(launch_ctc_wide(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, n, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
+                                   (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, mask_dev,
+                                   route != CTC_GREEDY ? (float*)ctx->ctc_probs.p : nullptr));
+        else
+            HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, n, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
+                              (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask,
+                              route != CTC_GREEDY ? (float*)ctx->ctc_probs.p : nullptr));
         std::vector<int> oidx(rows), blen(route == CTC_BEAM_DEVICE ? n : 0);
         std::vector<CtcOut> oo(n);
         std::vector<float> probs(route == CTC_BEAM_HOST ? rows * cs : 0);
@@ -418,14 +440,76 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
 
 int bbocr_op_ctc_probs(bbocr_ctx* ctx, const float* dev_logits, size_t rows, int C, int cs, const unsigned int* ignore_mask, float* dev_probs_out) {
     return guarded(ctx, [&](bbocr_ctx* ctx) {
-        if (!dev_logits || !dev_probs_out || rows == 0 || rows > (size_t)INT32_MAX || C <= 0 || C > 128 || C > cs) fail(BBOCR_ERR_ARG, "bad ctc arguments");
+        if (!dev_logits || !dev_probs_out || rows == 0 || rows > (size_t)INT32_MAX || C <= 0 || C > op_ctc_max_classes(ctx) || C > cs) fail(BBOCR_ERR_ARG, "bad ctc arguments");
+        const unsigned int* mask_dev = op_wide_mask(ctx, C, ignore_mask);
         // launch_ctc with one sequence over all rows: the rows kernel is per row, the collapse's output is not read
         ctc_size(ctx, rows, 1, cs, CTC_GREEDY);
         const int seq[2] = {0, (int)rows};
         ctx->seq_tables.ensure(sizeof(seq));
         HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seq, sizeof(seq), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, 1, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
-                          (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask, dev_probs_out));
+        if (C > 128)
+            HIPCHK(launch_ctc_wide(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, 1, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
+                                   (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, mask_dev, dev_probs_out));
+        else
+            HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, 1, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
+                              (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask, dev_probs_out));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+int bbocr_op_ctc_rows(bbocr_ctx* ctx, const float* dev_logits, size_t rows, int C, int cs, const unsigned int* ignore_mask, const int* seqs, int nseq,
+                      float* dev_probs_out, int* dev_idx, float* dev_pmax, int* dev_out_idx, int* dev_ctc_out) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!dev_logits || !dev_idx || !dev_pmax || !dev_out_idx || !dev_ctc_out || !seqs || nseq <= 0 || rows == 0 || rows > (size_t)INT32_MAX || C <= 0 ||
+            C > op_ctc_max_classes(ctx) || C > cs)
+            fail(BBOCR_ERR_ARG, "bad ctc arguments");
+        for (int i = 0; i < nseq; ++i) {
+            const long long first = seqs[2 * i], T = seqs[2 * i + 1];
+            if (first < 0 || T < 0 || first + T > (long long)rows) fail(BBOCR_ERR_ARG, "a sequence lies outside the rows");
+        }
+        const unsigned int* mask_dev = op_wide_mask(ctx, C, ignore_mask);
+        ctx->seq_tables.ensure((size_t)nseq * 8);
+        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs, (size_t)nseq * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (C > 128)
+            HIPCHK(launch_ctc_wide(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, nseq, dev_idx, dev_pmax, dev_out_idx, (CtcOut*)dev_ctc_out,
+                                   ctx->stream, mask_dev, dev_probs_out));
+        else
+            HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, nseq, dev_idx, dev_pmax, dev_out_idx, (CtcOut*)dev_ctc_out, ctx->stream,
+                              ignore_mask, dev_probs_out));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+int bbocr_op_pred(bbocr_ctx* ctx, const uint16_t* dev_x, size_t rows, float* dev_logits) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!ctx->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
+        if (rec_split(ctx) || rec_quant(ctx)) fail(BBOCR_ERR_STATE, "bbocr_op_pred takes the 16-bit recogniser modes");
+        const size_t rows_pad = align_up(rows, 256), cs = (size_t)rec_cs(ctx);
+        if (!dev_x || !dev_logits || rows == 0 || rows_pad * cs * 4 > ((size_t)1 << 30)) fail(BBOCR_ERR_ARG, "bad pred arguments");
+        // as a sequence pass holds them: x in seq_v, padded with zero rows to whole 256-row tiles; logits in seq_logits
+        ctx->seq_v.ensure(rows_pad * 256 * 2);
+        ctx->seq_logits.ensure(rows_pad * cs * 4);
+        HIPCHK(hipMemsetAsync(ctx->seq_v.p, 0, rows_pad * 256 * 2, ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->seq_v.p, dev_x, rows * 256 * 2, hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->arena.dry = false;
+        crnn_seq_pred(ctx, (const uint16_t*)ctx->seq_v.p, rows_pad, (float*)ctx->seq_logits.p);
+        HIPCHK(hipMemcpyAsync(dev_logits, ctx->seq_logits.p, rows * cs * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+    });
+}
+
+int bbocr_op_pred_ctc(bbocr_ctx* ctx, const uint16_t* dev_x, size_t rows, const uint32_t* dev_mask_words, int n_words, int* dev_idx, float* dev_pmax) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!ctx->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
+        if (!ctx->pred_wide) fail(BBOCR_ERR_STATE, "the fused Prediction + CTC kernel serves contexts of more than 128 classes in a 16-bit precision");
+        const int C = rec_classes(ctx), max_words = (C + 31) / 32;
+        if (!dev_x || !dev_idx || !dev_pmax || rows == 0 || rows > (size_t)INT32_MAX || n_words < 0 || n_words > max_words || (n_words > 0 && !dev_mask_words))
+            fail(BBOCR_ERR_ARG, "bad pred_ctc arguments");
+        // the kernel reads ceil(C / 32) words: the caller's, with zeros behind them
+        ctx->ctc_mask.ensure((size_t)max_words * 4);
+        HIPCHK(hipMemsetAsync(ctx->ctc_mask.p, 0, (size_t)max_words * 4, ctx->stream));
+        if (n_words > 0) HIPCHK(hipMemcpyAsync(ctx->ctc_mask.p, dev_mask_words, (size_t)n_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(launch_pred_ctc(rec_el(ctx), dev_x, rows, ctx->pred_wide, ctx->pred_wide_b, C, (const unsigned int*)ctx->ctc_mask.p, dev_idx, dev_pmax, ctx->stream));
         slot_sync(ctx, ctx->stream);
     });
 }

@@ -54,6 +54,54 @@ __global__ void __launch_bounds__(256) ctc_rows_kernel(const float* __restrict__
     }
 }
 
+// The same quantities over MORE than 128 classes (a recogniser other than english_g2: latin_g2 352, zh_sim_g2 6,719): one wave per row,
+// class c = lane + 64 k in step k, so every load of a step is 256 contiguous bytes and a lane meets its classes in ascending order.  A row
+// no longer fits two registers per lane, so it is walked four times (maximum; sum of exp; sum of the unmasked quotients; final quotient +
+// arg-max) and e = expf(x - max), q = e / sum are recomputed per walk from the same operands, i.e. to the same bits; a 27-KB row stays in L2
+// between the walks.  Each lane adds its ceil(C / 64) terms in ascending class order, then the 6-step butterfly (tests/wide_ctc_ref.py
+// derives its allowance from exactly this order).  mask: ceil(C / 32) device words or null.  Columns >= C are neither read nor written.
+__global__ void __launch_bounds__(256) ctc_rows_wide_kernel(const float* __restrict__ logits, size_t rows, int C, int cs, int* __restrict__ idx,
+                                                            float* __restrict__ pmax, const unsigned int* __restrict__ mask,
+                                                            float* __restrict__ probs) {
+    const int lane = threadIdx.x & 63;
+    const size_t wave0 = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const size_t nwaves = ((size_t)gridDim.x * 256) >> 6;
+    for (size_t row = wave0; row < rows; row += nwaves) {
+        const float* p = logits + row * cs;
+        float m = -INFINITY;
+        for (int c = lane; c < C; c += 64) m = fmaxf(m, p[c]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        float sum = 0.f;
+        for (int c = lane; c < C; c += 64) sum += expf(p[c] - m);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+        auto quot = [&](int c) {
+            const float q = expf(p[c] - m) / sum;
+            return (mask && ((mask[c >> 5] >> (c & 31)) & 1u)) ? 0.f : q;
+        };
+        float norm = 0.f;
+        for (int c = lane; c < C; c += 64) norm += quot(c);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) norm += __shfl_xor(norm, o);
+        // arg-max over the final probabilities, first index wins ties (numpy argmax): strict > inside a lane, whose classes ascend
+        float bp = -1.f;
+        int bi = 0x7fffffff;
+        for (int c = lane; c < C; c += 64) {
+            const float q = quot(c) / norm;
+            if (probs) probs[row * cs + c] = q;
+            if (q > bp) { bp = q; bi = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float op = __shfl_xor(bp, o);
+            const int oi = __shfl_xor(bi, o);
+            if (op > bp || (op == bp && oi < bi)) { bp = op; bi = oi; }
+        }
+        if (lane == 0) { idx[row] = bi < C ? bi : 0; pmax[row] = bp; }      // a row of NaNs compares to nothing: the blank, never a class outside the table
+    }
+}
+
 // one wave per sequence: collapse repeats / blanks with ballot + prefix popcount; confidence product kept strictly
 // sequential in t (float32), as numpy's multiply.reduce does.
 // seqs[i] = {first row, T}: sequences of different lengths (buckets) share one launch
@@ -106,5 +154,22 @@ hipError_t launch_ctc(const float* logits, size_t rows, int C, int cs, const int
     hipLaunchKernelGGL(ctc_rows_kernel, dim3(grid), dim3(256), 0, s, logits, rows, C, cs, idx_tmp, pmax_tmp,
                        make_uint4(ignore ? ignore[0] : 0u, ignore ? ignore[1] : 0u, ignore ? ignore[2] : 0u, ignore ? ignore[3] : 0u), probs_out);
     hipLaunchKernelGGL(ctc_collapse_kernel, dim3(nseq), dim3(64), 0, s, idx_tmp, pmax_tmp, (const int2*)seqs_dev, out_idx, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_wide(const float* logits, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int* idx_tmp, float* pmax_tmp,
+                           int* out_idx, CtcOut* out, hipStream_t s, const unsigned int* mask_dev, float* probs_out) {
+    if (nseq <= 0 || rows == 0) return hipSuccess;
+    if (C < 1 || C > cs) return hipErrorInvalidValue;
+    const size_t blocks = (rows + 3) / 4;
+    const int grid = (int)(blocks < 8192 ? blocks : 8192);
+    hipLaunchKernelGGL(ctc_rows_wide_kernel, dim3(grid), dim3(256), 0, s, logits, rows, C, cs, idx_tmp, pmax_tmp, mask_dev, probs_out);
+    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(nseq), dim3(64), 0, s, idx_tmp, pmax_tmp, (const int2*)seqs_dev, out_idx, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_collapse(const int* idx, const float* pmax, const int* seqs_dev, int nseq, int* out_idx, CtcOut* out, hipStream_t s) {
+    if (nseq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(nseq), dim3(64), 0, s, idx, pmax, (const int2*)seqs_dev, out_idx, out);
     return hipGetLastError();
 }

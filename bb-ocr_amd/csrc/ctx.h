@@ -166,6 +166,8 @@ struct WeightView {
     float* r0_wb = nullptr;      // w[9][32] (tap-major) b[32]
     uint16_t* r0_afrag = nullptr;  // taps 0..7 three-way split into element-type terms, as MFMA A fragments (crnn_conv0_mfma_kernel)
     ConvPlan r1, r2, r3, r4, r5, r6, xproj[2], lin[2], pred;
+    uint16_t* pred_wide = nullptr;   // more than 128 classes, 16-bit modes: Prediction.weight as pred_ctc_kernel's A fragments (pack_pred_ctc_weights)
+    float* pred_wide_b = nullptr;    // and its bias, padded to whole 16-class fragments
     uint16_t* whh[2] = {nullptr, nullptr};
     float whh_scale[2] = {1.f, 1.f};   // exact mode: 2^-s of the packed W_hh (pack_lstm_whh_split)
     // rec_quant (bbocr_config::rec_quant): the eleven tensors of the sequence half as symmetric qint8, packed for quant.hip; scales per
@@ -206,6 +208,9 @@ struct bbocr_ctx : WeightView {
     unsigned long long pp_cubic_K[2] = {0, 0};
     unsigned int ignore_mask[4] = {0, 0, 0, 0};   // recogniser class mask of the running call (bbocr_params::ignore_mask)
     int beam_width = 0;                           // > 0: decoder='beamsearch' for the running call (bbocr_params::decoder / beam_width)
+    std::vector<unsigned int> class_mask;         // more than 128 classes: the calling thread's bbocr_set_class_mask words, padded to ceil(C / 32)
+    DevBuf ctc_mask;                              // ... on the device (uploaded by the sequence stage that reads them)
+    int ctc_last_route = -1;                      // what ctc_route answered for this slot's latest sequence pass (CTC_*); published per calling thread with the stage times (bbocr_last_ctc_route)
     hipStream_t cur = nullptr;                // stream the layer helpers launch on
     SideLane upload_lane;                     // root only: bbocr_upload_pages copies here (an upload never waits for a running call)
     SideLane jpeg_lane;                       // root only: the JPEG batches of jpegdec.cpp run here; its mutex guards the jd_* buffers
@@ -259,6 +264,12 @@ inline int det_el(const bbocr_ctx* c) { return (c->cfg.precision == BBOCR_PREC_F
 inline int rec_el(const bbocr_ctx* c) { return c->cfg.precision != BBOCR_PREC_BF16 ? 1 : 0; }     // MIXED: bf16 detector, fp16 recogniser
 inline bool rec_split(const bbocr_ctx* c) { return c->cfg.precision == BBOCR_PREC_EXACT || c->cfg.precision == BBOCR_PREC_EXACT_REC; }   // recogniser tensors are [hi | lo] fp16 pairs
 inline bool rec_quant(const bbocr_ctx* c) { return c->cfg.rec_quant == 1; }     // sequence half in dynamic int8 (quant.hip); needs rec_split
+// classes of the recogniser (bbocr_config::rec_classes, 0 = english_g2's 97) and the row stride of its fp32 logits / probabilities: whole
+// 16-column groups, as the conv epilogue stores them (97 -> 112)
+constexpr int kRecClassesDefault = 97;
+inline int rec_classes(const bbocr_ctx* c) { return c->cfg.rec_classes > 0 ? c->cfg.rec_classes : kRecClassesDefault; }
+inline int rec_cs(const bbocr_ctx* c) { return (rec_classes(c) + 15) / 16 * 16; }
+inline bool rec_wide(const bbocr_ctx* c) { return rec_classes(c) > 128; }       // beyond ctc_rows_kernel, bbocr_params::ignore_mask and the device beam search
 inline bool det_split(const bbocr_ctx* c) { return c->cfg.precision == BBOCR_PREC_EXACT; }   // and so are the detector's (split-fp16 plans in every layer)
 
 // ------------------------------------------------------------------------------------------------ shared types
@@ -443,8 +454,12 @@ void crnn_seq_xproj_conv(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad
 void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint16_t* out);
 void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logits);
 void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);    // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}
-enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2 };   // where the text of a CTC pass comes from (ctc_route)
-int ctc_route(int beam_width, int C, const int* seqs, int nseq);   // seqs: {first row, T} per sequence (host)
+// where the text of a CTC pass comes from (ctc_route).  CTC_GREEDY_FUSED: greedy over more than 128 classes with Prediction inside the CTC
+// kernel (pred_ctc.hip) -- the pass has no logits
+enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2, CTC_GREEDY_FUSED = 3 };
+// seqs: {first row, T} per sequence (host); fused_ok: the caller holds Prediction's input and pred_ctc_kernel's weights (a 16-bit recognition pass)
+int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok = false);
+const unsigned int* thread_class_mask(const bbocr_ctx* root, int* n_words);   // abi.cpp: the calling thread's bbocr_set_class_mask words for `root`, or null
 void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route);
 double ctc_decode(const CtcOut& o, const int* idx, int n, std::vector<int>& text);
 void rec_early_begin(bbocr_ctx* c, const GrayPages& g, int pages, int B, const HostBoxes& hb, const bbocr_params& p, RecEarly& e);

@@ -243,6 +243,21 @@ struct CtcOut { int len; int cnt; float prod; int pad; };
 // seqs_dev: int2 per sequence {first row, T}; logits fp32 [rows, cs]; out_idx is row-indexed like the pool
 hipError_t launch_ctc(const float* logits, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int* idx_tmp, float* pmax_tmp,
                       int* out_idx, CtcOut* out, hipStream_t s, const unsigned int* ignore = nullptr, float* probs_out = nullptr);   // ignore: 4 x 32-bit class mask or null
+// the same stage over MORE than 128 classes (ctc_rows_wide_kernel: one wavefront per row, classes strided over the lanes 64 at a time, so every
+// load is 256 contiguous bytes), then ctc_collapse_kernel as above.  mask_dev: ceil(C / 32) words on the device (bit c of word c >> 5 removes
+// class c) or null.  Columns >= C of a row are neither read nor written.
+hipError_t launch_ctc_wide(const float* logits, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int* idx_tmp, float* pmax_tmp,
+                           int* out_idx, CtcOut* out, hipStream_t s, const unsigned int* mask_dev = nullptr, float* probs_out = nullptr);
+// ctc_collapse_kernel alone, over idx / pmax that another kernel wrote (pred_ctc.hip)
+hipError_t launch_ctc_collapse(const int* idx, const float* pmax, const int* seqs_dev, int nseq, int* out_idx, CtcOut* out, hipStream_t s);
+// Prediction + softmax + mask + arg-max as one kernel that stores no logits (pred_ctc.hip): x [rows, 256] 16-bit elements of type el, wpk / bias
+// from pack_pred_ctc_weights -> idx [rows], pmax [rows].  C > 128 is what it is built for; any C >= 2 is computed.
+constexpr int kPredCtcRows = 64;                       // rows of x a workgroup keeps in registers
+size_t pred_ctc_packed_elems(int C);                   // 16-bit elements of the packed weights: ceil(C / 16) fragments x 8 k-steps x 64 lanes x 8
+size_t pred_ctc_bias_elems(int C);
+void pack_pred_ctc_weights(int el, const float* w /* [C][256] */, const float* b /* [C] */, int C, uint16_t* wpk, float* bias);
+hipError_t launch_pred_ctc(int el, const uint16_t* x, size_t rows, const uint16_t* wpk, const float* bias, int C, const unsigned int* mask_dev,
+                           int* idx, float* pmax, hipStream_t s);
 // decoder='beamsearch' (easyocr/utils.py::ctcBeamSearch, host: the definition, and the path of beams wider than BBOCR_BEAM_DEVICE_MAX): probs fp32 [rows, cs] as ctc_rows_kernel writes them; seqs = {first row, T}
 void ctc_beam_search_host(const float* mat, int T, int C, int cs, int beam_width, std::vector<int>& text);
 class HostPool;

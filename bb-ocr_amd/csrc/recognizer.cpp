@@ -146,7 +146,7 @@ static void crnn_sequence_q8(bbocr_ctx* c, size_t rows, size_t rows_pad, const i
         qlinear(c->seq_h.p, 0, 512, c->q_lin[l], 256, dst);
         cur = dst;
     }
-    qlinear(cur, 0, 256, c->q_pred, 112, logits);
+    qlinear(cur, 0, 256, c->q_pred, rec_cs(c), logits);
 }
 
 // the int8 recurrence's workgroups take LSTM_Q8_SEQS consecutive sequences of the table, each with its own T
@@ -180,7 +180,7 @@ void crnn_sequence(bbocr_ctx* c, size_t rows, size_t rows_pad, const int* tiles_
         crnn_seq_lin(c, l, (const uint16_t*)c->seq_h.p, rows_pad, dst);
         cur = dst;
     }
-    crnn_seq_pred(c, cur, rows_pad, logits);
+    if (logits) crnn_seq_pred(c, cur, rows_pad, logits);      // null: the pass's CTC route holds Prediction itself (CTC_GREEDY_FUSED) and reads seq_v
 }
 
 // The sequence half's three GEMMs as 1x1 convs over the rows laid out as an image [1, rows_pad / 256, 256, C] (rows_pad: a multiple of 256).
@@ -203,9 +203,9 @@ void crnn_seq_xproj(bbocr_ctx* c, int l, const uint16_t* x, size_t rows_pad, voi
 void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint16_t* out) {
     run_conv(c, c->lin[l], seq_rows(c, h, rows_pad, 512), false, nullptr, false, false, out, 256 * rec_mul(c), 256, false);
 }
-// x [rows_pad, 256] -> logits fp32 [rows_pad, 112] (97 classes; the columns behind them belong to no class)
+// x [rows_pad, 256] -> logits fp32 [rows_pad, rec_cs] (english_g2: 97 classes in 112 columns; the columns behind the classes belong to no class)
 void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logits) {
-    run_conv(c, c->pred, seq_rows(c, x, rows_pad, 256), false, nullptr, false, false, logits, 112, 112, true);
+    run_conv(c, c->pred, seq_rows(c, x, rows_pad, 256), false, nullptr, false, false, logits, rec_cs(c), rec_cs(c), true);
 }
 
 // A recognition pass = feature PARTS + one sequence stage.  A part is a set of crops standing side by side in ONE wide image
@@ -215,7 +215,16 @@ void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logi
 // readtext_batch uses two parts: the crops of the first detector pass's pages go through the conv stack while the last pass's boxes
 // are still being extracted (CCL + host geometry), so that stretch no longer leaves the card idle.
 // pooled time steps per sequence pass (~6.6 KB of work buffers each); bbocr_config::rec_max_cols (pixel columns, 4 per time step) overrides
-static size_t rec_max_rows(const bbocr_ctx* c) { return c->cfg.rec_max_cols > 0 ? (size_t)std::max(64, c->cfg.rec_max_cols / 4) : (size_t)1500000; }
+// More than 128 classes on the unfused route (beam search, the exact modes): the pass also holds rows_pad * rec_cs fp32 logits, and as many
+// probabilities for a beam search -- each buffer is kept at or below kRecWideBufBytes, which at 6,719 classes is 39,936 rows
+constexpr size_t kRecWideBufBytes = (size_t)1 << 30;
+static bool rec_fused_ok(const bbocr_ctx* c) { return rec_wide(c) && !rec_split(c) && !rec_quant(c) && c->pred_wide; }
+static size_t rec_max_rows(const bbocr_ctx* c) {
+    size_t lim = c->cfg.rec_max_cols > 0 ? (size_t)std::max(64, c->cfg.rec_max_cols / 4) : (size_t)1500000;
+    if (rec_wide(c) && !(rec_fused_ok(c) && c->beam_width <= 0))
+        lim = std::min(lim, std::max<size_t>(256, kRecWideBufBytes / ((size_t)rec_cs(c) * 4) / 256 * 256));
+    return lim;
+}
 
 // lay the crops `sel` (indices into jobs; result position = res0 + position in sel) out as one part whose rows start at row_base
 void rec_plan_part(const std::vector<BoxJob>& jobs, const std::vector<int>& sel, int res0, size_t row_base, RecPart& part) {
@@ -309,8 +318,8 @@ void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs) {
 
 // where a CTC pass's text comes from: the greedy collapse, or ctcBeamSearch on the device (widths up to BBOCR_BEAM_DEVICE_MAX whose longest
 // sequence fits the kernel's LDS block) or on the host (wider beams, longer sequences: the probabilities cross to the host)
-int ctc_route(int beam_width, int C, const int* seqs, int nseq) {
-    if (beam_width <= 0) return CTC_GREEDY;
+int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok) {
+    if (beam_width <= 0) return (C > 128 && fused_ok) ? CTC_GREEDY_FUSED : CTC_GREEDY;
     int max_T = 0;
     for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
     return ctc_beam_on_device(beam_width, C, max_T) ? CTC_BEAM_DEVICE : CTC_BEAM_HOST;
@@ -323,7 +332,7 @@ void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route) {
     c->ctc_pmax.ensure(rows * 4);
     c->ctc_out_idx.ensure(rows * 4);
     c->ctc_out.ensure((size_t)nseq * sizeof(CtcOut));
-    if (route != CTC_GREEDY) c->ctc_probs.ensure(rows * cs * sizeof(float));
+    if (route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE) c->ctc_probs.ensure(rows * cs * sizeof(float));
     if (route == CTC_BEAM_DEVICE) {
         c->ctc_beam_idx.ensure(rows * 4);
         c->ctc_beam_len.ensure((size_t)nseq * 4);
@@ -357,12 +366,16 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     }
     const std::vector<int>&tiles = run.tiles, &seqs = run.seqs;
     const int ntiles = (int)(tiles.size() / 4), nseq = (int)(seqs.size() / 2);
-    c->seq_logits.ensure(rows_pad * 112 * 4);
+    const int C = rec_classes(c), cs = rec_cs(c);
+    const int route = ctc_route(c->beam_width, C, seqs.data(), nseq, rec_fused_ok(c));
+    c->ctc_last_route = route;
+    const bool fused = route == CTC_GREEDY_FUSED, beam = route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE;
+    if (!fused) c->seq_logits.ensure(rows_pad * cs * 4);
     c->seq_tables.ensure((tiles.size() + seqs.size()) * 4);
     int* tiles_dev = (int*)c->seq_tables.p;
     int* seqs_dev = tiles_dev + tiles.size();
-    const int route = ctc_route(c->beam_width, 97, seqs.data(), nseq);
-    ctc_size(c, rows, nseq, 112, route);
+    ctc_size(c, rows, nseq, cs, route);
+    if (rec_wide(c)) c->ctc_mask.ensure(c->class_mask.size() * 4);
     // pinned read-back block: greedy classes [rows] | CtcOut [nseq] | device route: beam text [rows] | its lengths [nseq]
     const size_t oo_off = align_up(rows * 4, 16);
     const size_t bi_off = align_up(oo_off + (size_t)nseq * sizeof(CtcOut), 16), bl_off = bi_off + align_up(rows * 4, 16);
@@ -371,7 +384,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     const CtcOut* oo = (const CtcOut*)((const char*)c->ctc_pin.p + oo_off);
     const int* bidx = (const int*)((const char*)c->ctc_pin.p + bi_off);
     const int* blen = (const int*)((const char*)c->ctc_pin.p + bl_off);
-    std::vector<float> probs(route == CTC_BEAM_HOST ? rows * 112 : 0);      // only the host route moves the probabilities off the card
+    std::vector<float> probs(route == CTC_BEAM_HOST ? rows * cs : 0);      // only the host route moves the probabilities off the card
     std::vector<std::vector<int>> beam_texts;
     if (!c->seq_t1) { HIPCHK(hipEventCreate(&c->seq_t1)); HIPCHK(hipEventCreate(&c->seq_t2)); }
     {
@@ -387,16 +400,26 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
         struct Restore { bbocr_ctx* c; ~Restore() { c->cur = c->stream; } } restore{c};
         HIPCHK(hipMemcpyAsync(tiles_dev, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, ss));
         HIPCHK(hipMemcpyAsync(seqs_dev, seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, ss));
-        crnn_sequence(c, rows, rows_pad, tiles_dev, ntiles, seqs_dev, nseq, (float*)c->seq_logits.p);
+        if (rec_wide(c)) HIPCHK(hipMemcpyAsync(c->ctc_mask.p, c->class_mask.data(), c->class_mask.size() * 4, hipMemcpyHostToDevice, ss));
+        crnn_sequence(c, rows, rows_pad, tiles_dev, ntiles, seqs_dev, nseq, fused ? nullptr : (float*)c->seq_logits.p);
         HIPCHK(hipEventRecord(c->seq_t1, ss));
-        HIPCHK(launch_ctc((const float*)c->seq_logits.p, rows, 97, 112, seqs_dev, nseq, (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p,
-                          (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, c->ignore_mask, route != CTC_GREEDY ? (float*)c->ctc_probs.p : nullptr));
+        if (fused) {             // Prediction inside the CTC kernel: the second BiLSTM stage's output (seq_v) in, no logits anywhere
+            HIPCHK(launch_pred_ctc(rec_el(c), (const uint16_t*)c->seq_v.p, rows, c->pred_wide, c->pred_wide_b, C, (const unsigned int*)c->ctc_mask.p,
+                                   (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p, ss));
+            HIPCHK(launch_ctc_collapse((const int*)c->ctc_idx.p, (const float*)c->ctc_pmax.p, seqs_dev, nseq, (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss));
+        } else if (rec_wide(c)) {
+            HIPCHK(launch_ctc_wide((const float*)c->seq_logits.p, rows, C, cs, seqs_dev, nseq, (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p,
+                                   (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, (const unsigned int*)c->ctc_mask.p, beam ? (float*)c->ctc_probs.p : nullptr));
+        } else {
+            HIPCHK(launch_ctc((const float*)c->seq_logits.p, rows, C, cs, seqs_dev, nseq, (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p,
+                              (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, c->ignore_mask, beam ? (float*)c->ctc_probs.p : nullptr));
+        }
         if (route != CTC_BEAM_DEVICE) HIPCHK(hipMemcpyAsync(c->ctc_pin.p, c->ctc_out_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));    // the search's text replaces it
         HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + oo_off, c->ctc_out.p, (size_t)nseq * sizeof(CtcOut), hipMemcpyDeviceToHost, ss));
         if (route == CTC_BEAM_DEVICE) {
             int max_T = 0;
             for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
-            HIPCHK(launch_ctc_beam((const float*)c->ctc_probs.p, rows, 97, 112, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_beam_idx.p,
+            HIPCHK(launch_ctc_beam((const float*)c->ctc_probs.p, rows, C, cs, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_beam_idx.p,
                                    (int*)c->ctc_beam_len.p, ss));
             HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bi_off, c->ctc_beam_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));
             HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bl_off, c->ctc_beam_len.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, ss));
@@ -411,7 +434,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     c->times[4] += (float)ms_since(t0) - ctc_ms;     // host wait for the recogniser's device work (conv stack of the parts + sequence stage)
     c->times[5] += ctc_ms;                           // CTC kernels + read-back (device span) ...
     t0 = clk::now();                                 // ... + the host decode below
-    if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, 97, 112, c->beam_width, beam_texts, &host_pool(c));
+    if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, C, cs, c->beam_width, beam_texts, &host_pool(c));
     for (int i = 0; i < nseq; ++i) {       // the confidence stays the greedy path's for every route
         const int k = run.seq_k[i];
         if (route == CTC_BEAM_HOST) confs[k] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), texts[k]);
@@ -519,7 +542,14 @@ std::vector<int> crop_contrast_luts(bbocr_ctx* c, const CropDesc* descs_dev, std
 static void rec_check_params(bbocr_ctx* c, const bbocr_params& p) {
     if (!c->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
     if (p.ignore_mask[0] & 1u) fail(BBOCR_ERR_ARG, "the CTC blank (class 0) cannot be ignored");
+    c->ctc_last_route = -1;          // until a sequence pass of this call has been routed (bbocr_last_ctc_route)
     for (int i = 0; i < 4; ++i) c->ignore_mask[i] = p.ignore_mask[i];
+    if (rec_wide(c)) {       // the calling thread's bbocr_set_class_mask words, copied into this slot: another call's mask is another slot's
+        int n = 0;
+        const unsigned int* w = thread_class_mask(c->root, &n);
+        c->class_mask.assign((size_t)(rec_classes(c) + 31) / 32, 0u);
+        for (int i = 0; i < n && i < (int)c->class_mask.size(); ++i) c->class_mask[i] = w[i];
+    }
     if (p.decoder != BBOCR_DECODER_GREEDY && p.decoder != BBOCR_DECODER_BEAMSEARCH) fail(BBOCR_ERR_ARG, "unknown decoder");
     if (p.decoder == BBOCR_DECODER_BEAMSEARCH && p.beam_width <= 0) fail(BBOCR_ERR_ARG, "beam_width must be positive");
     c->beam_width = p.decoder == BBOCR_DECODER_BEAMSEARCH ? p.beam_width : 0;

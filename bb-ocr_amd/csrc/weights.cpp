@@ -121,7 +121,7 @@ void free_weights(bbocr_ctx* c) {
 // bbocr_alloc_weights) import it: no fp32 state-dict, no host hop and no re-packing on the receivers (~49 MB in
 // bf16 instead of 98 MB of fp32).
 namespace {
-struct BlobHeader { unsigned long long magic; int precision, nblocks; unsigned long long bytes; int craft, crnn; unsigned long long layout_hash; int rec_quant; int pad[5]; };
+struct BlobHeader { unsigned long long magic; int precision, nblocks; unsigned long long bytes; int craft, crnn; unsigned long long layout_hash; int rec_quant; int rec_classes; int pad[4]; };   // rec_classes: 0 in blobs written before the field existed = 97
 static_assert(sizeof(BlobHeader) == 64, "blob header");
 constexpr unsigned long long BLOB_MAGIC = 0x62626f6372776231ULL;   // "bbocrwb1"
 unsigned long long layout_hash(const bbocr_ctx* c) {     // FNV-1a over the per-block sizes: equal totals with different blocks do not pass
@@ -154,6 +154,7 @@ void weights_export(bbocr_ctx* c, void* dev_dst, size_t bytes) {
     BlobHeader h{};
     h.magic = BLOB_MAGIC; h.precision = c->cfg.precision; h.nblocks = (int)c->owned.size(); h.bytes = bytes;
     h.craft = c->craft_loaded; h.crnn = c->crnn_loaded; h.layout_hash = layout_hash(c); h.rec_quant = c->cfg.rec_quant;
+    h.rec_classes = (c->crnn_loaded && rec_classes(c) != kRecClassesDefault) ? rec_classes(c) : 0;      // english_g2's blob stays byte for byte what it was
     char* d = (char*)dev_dst;
     HIPCHK(hipMemcpyAsync(d, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     size_t off = sizeof(h);
@@ -175,6 +176,9 @@ void weights_import(bbocr_ctx* c, const void* dev_src, size_t bytes) {
     HIPCHK(hipMemcpy(&h, s, sizeof(h), hipMemcpyDeviceToHost));
     if (h.magic == BLOB_MAGIC && h.rec_quant != c->cfg.rec_quant)       // before the size check: the two kinds differ in size as well
         fail(BBOCR_ERR_WEIGHTS, "weight blob: made with rec_quant = " + std::to_string(h.rec_quant) + ", this context has " + std::to_string(c->cfg.rec_quant));
+    if (h.magic == BLOB_MAGIC && h.crnn && c->crnn_loaded && (h.rec_classes > 0 ? h.rec_classes : kRecClassesDefault) != rec_classes(c))
+        fail(BBOCR_ERR_WEIGHTS, "weight blob: made for " + std::to_string(h.rec_classes > 0 ? h.rec_classes : kRecClassesDefault) +
+                                    " recogniser classes, this context has " + std::to_string(rec_classes(c)));
     if (bytes != weights_blob_bytes(c)) fail(BBOCR_ERR_ARG, "weight blob: size does not match this context's layout (same precision / networks on every rank?)");
     if (h.magic != BLOB_MAGIC || h.precision != c->cfg.precision || h.nblocks != (int)c->owned.size() || h.bytes != bytes ||
         h.craft != (int)c->craft_loaded || h.crnn != (int)c->crnn_loaded || h.layout_hash != layout_hash(c))
@@ -306,6 +310,17 @@ void load_craft(bbocr_ctx* c, const TensorMap& tm) {
     c->craft_loaded = true;
 }
 
+// Prediction.weight / .bias of a context of rec_classes classes: a tensor of another class count is named with both numbers
+static const float* pred_tensor(const bbocr_ctx* c, const TensorMap& tm, const std::string& name, size_t numel) {
+    if (!tm.zeros) {
+        auto it = tm.m.find(name);
+        if (it != tm.m.end() && it->second->ndim >= 1 && it->second->shape[0] != rec_classes(c))
+            fail(BBOCR_ERR_WEIGHTS, "tensor '" + name + "' has " + std::to_string((long long)it->second->shape[0]) + " classes, this context was created for " +
+                                        std::to_string(rec_classes(c)) + " (bbocr_config::rec_classes)");
+    }
+    return tm.get(name, numel);
+}
+
 // rec_quant: default_weight_observer (MinMaxObserver, per_tensor_symmetric, qint8) + torch.quantize_per_tensor of one weight tensor
 static float quantize_weight_q8(const float* w, size_t n, std::vector<int8_t>& q) {
     float mn = 0.f, mx = 0.f;
@@ -361,7 +376,8 @@ static void load_crnn_q8(bbocr_ctx* c, const TensorMap& tm) {
         c->q_hh[l].bias = upload(c, b_hh);
         load_q8_linear(c, c->q_lin[l], tm.get(sm + "linear.weight", (size_t)256 * 512), tm.get(sm + "linear.bias", 256), 256, 512);
     }
-    load_q8_linear(c, c->q_pred, tm.get("Prediction.weight", (size_t)97 * 256), tm.get("Prediction.bias", 97), 97, 256);
+    const int C = rec_classes(c);
+    load_q8_linear(c, c->q_pred, pred_tensor(c, tm, "Prediction.weight", (size_t)C * 256), pred_tensor(c, tm, "Prediction.bias", C), C, 256);
 }
 
 void load_crnn(bbocr_ctx* c, const TensorMap& tm) {
@@ -431,13 +447,22 @@ void load_crnn(bbocr_ctx* c, const TensorMap& tm) {
         }
     }
     {
-        std::vector<float> pw(tm.get("Prediction.weight", (size_t)97 * 256), tm.get("Prediction.weight", (size_t)97 * 256) + 97 * 256);
-        std::vector<float> pb(tm.get("Prediction.bias", 97), tm.get("Prediction.bias", 97) + 97);
+        const int C = rec_classes(c);
+        const float* w = pred_tensor(c, tm, "Prediction.weight", (size_t)C * 256);
+        const float* b = pred_tensor(c, tm, "Prediction.bias", C);
+        std::vector<float> pw(w, w + (size_t)C * 256), pb(b, b + C);
         if (rec_split(c)) {
-            upload_split_plan(c, c->pred, 256, 97, 1, 1, 0, pw, pb);
+            upload_split_plan(c, c->pred, 256, C, 1, 1, 0, pw, pb);
         } else {
-            c->pred = make_plan(256, 97, 1, 1, 0, 1, rec_el(c));
+            c->pred = make_plan(256, C, 1, 1, 0, 1, rec_el(c));
             upload_plan(c, c->pred, pw, pb);
+            if (rec_wide(c)) {      // the greedy route's fused kernel reads its own packing (pred_ctc.hip); c->pred stays: beam search, bbocr_crnn_logits
+                std::vector<uint16_t> pk(pred_ctc_packed_elems(C));
+                std::vector<float> bp(pred_ctc_bias_elems(C));
+                pack_pred_ctc_weights(rec_el(c), pw.data(), pb.data(), C, pk.data(), bp.data());
+                c->pred_wide = upload(c, pk);
+                c->pred_wide_b = upload(c, bp);
+            }
         }
     }
     c->crnn_loaded = true;

@@ -300,20 +300,88 @@ def format_output(result, output_format="standard", paragraph=False, detail=1):
 
 
 def ignore_mask(character, lang_char, allowlist=None, blocklist=None):
-    """easyocr.Reader.recognize's ``ignore_char`` rule as the 128-bit class mask of ``bbocr_params.ignore_mask``: with an allowlist
+    """easyocr.Reader.recognize's ``ignore_char`` rule as a class mask, bit ``c & 31`` of word ``c >> 5`` removing class ``c``: with an allowlist
     every character outside it, else the blocklist, else the characters of the model that are not in the language list (none for
-    ``['en']`` + english_g2).  Class index = position in ``character`` (0 is the CTC blank and is never ignored)."""
+    ``['en']`` + english_g2).  Class index = position in ``character`` (0 is the CTC blank and is never ignored).  Up to 128 classes these
+    are the four words of ``bbocr_params.ignore_mask``; a wider model gets ``ceil(len(character) / 32)`` words for ``bbocr_set_class_mask``."""
     if allowlist:
         ignore = set(character[1:]) - set(allowlist)
     elif blocklist:
         ignore = set(blocklist)
     else:
         ignore = set(character[1:]) - set(lang_char)
-    words = [0, 0, 0, 0]
+    words = [0] * max(4, (len(character) + 31) // 32)
     for i, ch in enumerate(character):
         if i and ch in ignore:
             words[i >> 5] |= 1 << (i & 31)
     return words
+
+
+_NETWORK_PARAMS = {"input_channel": 1, "output_channel": 256, "hidden_size": 256}     # every generation-2 model of easyocr, english_g2 included
+
+
+def resolve_recog_network(lang_list, recog_network="standard", model_storage_directory=None, user_network_directory=None, character=None,
+                          lang_char=None):
+    """What ``Reader.__init__`` needs to know about the recogniser, without a device: ``{"character", "lang_char", "model_path", "lang_list"}``.
+
+    ``recog_network="standard"`` is english_g2 and wants ``lang_list == ["en"]``.  Any other name follows easyocr's custom-model convention:
+    ``NAME.yaml`` in the user network directory (default ``~/.EasyOCR/user_network``) gives ``network_params``, ``imgH``, ``lang_list`` and
+    ``character_list``; ``NAME.pth`` in the model directory (default ``~/.EasyOCR/model``) holds the state-dict.  The architecture is fixed --
+    the CRNN every generation-2 model shares -- so ``NAME.py`` is never imported and other ``network_params`` / ``imgH`` are a ValueError.
+    ``character`` (a string or a list of class strings, WITHOUT the blank) stands in for the yaml on hosts that have no model files.
+    ``character = ['[blank]'] + list(character_list)`` as CTCLabelConverter builds it.  ``lang_char`` defaults to every character of the
+    model: easyocr's per-language ``*_char.txt`` tables are not shipped, so nothing is ignored unless the caller says so."""
+    model_path = None
+    if character is not None:
+        chars = list(character)
+    elif recog_network == "standard":
+        if list(lang_list) != ["en"]:
+            raise ValueError(f"{list(lang_list)} is not supported by recog_network='standard' (english_g2, ['en']): pass recog_network=NAME of a "
+                             "generation-2 model with its NAME.yaml / NAME.pth, or character=")
+        chars = list(CHARSET)
+    else:
+        import yaml
+
+        user_dir = user_network_directory or os.path.expanduser("~/.EasyOCR/user_network")
+        model_dir = model_storage_directory or os.environ.get("BBOCR_WEIGHTS_DIR") or os.path.expanduser("~/.EasyOCR/model")
+        path = os.path.join(user_dir, recog_network + ".yaml")
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"{path} not found (recog_network={recog_network!r}; this backend never downloads model files)")
+        with open(path, encoding="utf8") as fh:
+            cfg = yaml.safe_load(fh) or {}
+        params = cfg.get("network_params") or {}
+        got = {k: params.get(k) for k in _NETWORK_PARAMS}
+        if got != _NETWORK_PARAMS:
+            raise ValueError(f"{path}: network_params {got} -- only the generation-2 CRNN {_NETWORK_PARAMS} is implemented")
+        if cfg.get("imgH", 64) != 64:
+            raise ValueError(f"{path}: imgH {cfg.get('imgH')!r} -- only 64 is implemented")
+        if cfg.get("character_list") is None:
+            raise ValueError(f"{path}: no character_list")
+        chars = list(cfg["character_list"])
+        lang_list = cfg.get("lang_list") or lang_list
+        model_path = os.path.join(model_dir, recog_network + ".pth")
+    chars = [str(c) for c in chars]
+    if not 2 <= len(chars) + 1 <= _lib.REC_CLASSES_MAX:
+        raise ValueError(f"{len(chars) + 1} classes (blank included): 2 .. {_lib.REC_CLASSES_MAX} are supported")
+    return {"character": ["[blank]"] + chars, "lang_char": list(chars) if lang_char is None else list(lang_char), "model_path": model_path,
+            "lang_list": list(lang_list)}
+
+
+def text_table(character):
+    """``bbocr_result.text_idx`` -> text for any character list: a uint32 array of code points when every class is ONE code point (a numpy
+    take and one utf-32 decode serve a whole result), else the list itself (a class of several code points: joined box by box)."""
+    if all(len(c) == 1 for c in character[1:]):
+        return np.array([ord("?")] + [ord(c) for c in character[1:]], dtype="<u4")
+    return list(character)
+
+
+def decode_text(table, idx, text_off):
+    """the strings of a result: ``idx`` = its class indices (int array), ``text_off`` = [boxes + 1] offsets into it"""
+    if isinstance(table, np.ndarray):
+        chars = table[idx].tobytes().decode("utf-32-le") if len(idx) else ""       # one code point per class: the offsets stay valid
+        return [chars[a:b] for a, b in zip(text_off[:-1], text_off[1:])]
+    idx = np.asarray(idx).tolist()
+    return ["".join(table[i] for i in idx[a:b]) for a, b in zip(text_off[:-1], text_off[1:])]
 
 
 def get_paragraph(raw_result, x_ths=1, y_ths=0.5, mode="ltr"):
@@ -428,11 +496,16 @@ class Reader:
     def __init__(self, lang_list, gpu=True, model_storage_directory=None, user_network_directory=None,
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
-                 rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, **_ignored):
+                 rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, character=None,
+                 lang_char=None, **_ignored):
         import torch
 
-        if list(lang_list) != ["en"]:
-            raise ValueError(f"{lang_list} is not supported: this backend ships the English (english_g2) model only")
+        net = resolve_recog_network(lang_list, recog_network, model_storage_directory, user_network_directory, character, lang_char)
+        if rec_quant is None:       # the sequence half in easyocr's CPU default arithmetic (dynamic int8, bbocr_config::rec_quant); `quantize` stays ignored
+            rec_quant = os.environ.get("BBOCR_REC_QUANT", "").strip() == "1"
+        if rec_quant and len(net["character"]) != len(CHARACTER):
+            raise ValueError(f"rec_quant is implemented for english_g2's {len(CHARACTER)} classes only, this model has {len(net['character'])} "
+                             "(bbocr_create refuses the pair)")
         if detect_network != "craft":
             raise ValueError("only detect_network='craft' is implemented")
         if not torch.cuda.is_available():
@@ -441,8 +514,6 @@ class Reader:
         self.device_index = torch.cuda.current_device() if device_index is None else int(device_index)
         self.device = f"cuda:{self.device_index}"
         self._lib = _lib.load()
-        if rec_quant is None:       # the sequence half in easyocr's CPU default arithmetic (dynamic int8, bbocr_config::rec_quant); `quantize` stays ignored
-            rec_quant = os.environ.get("BBOCR_REC_QUANT", "").strip() == "1"
         self.rec_quant = bool(rec_quant)
         if self.rec_quant and precision is None:
             precision = "exact_rec"     # what is quantised are the fp32 path's features: the exact recogniser delivers them to 1e-5
@@ -467,21 +538,23 @@ class Reader:
         self.jpeg_progressive = jpeg_progressive(device_decode)   # "progressive": those, and progressive files (csrc/jpegprog.hip)
         cfg = _lib.bbocr_config(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
                                 precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads,
-                                rec_quant=int(self.rec_quant))
+                                rec_quant=int(self.rec_quant), rec_classes=0 if net["character"] == CHARACTER else len(net["character"]))
         h = C.c_void_p()
         rc = self._lib.bbocr_create(C.byref(cfg), C.byref(h))
         if rc != 0:
             raise RuntimeError(f"bbocr_create failed with status {rc}")
         self._h = h
-        self.character = CHARACTER
-        self.lang_char = list(CHARSET)
+        self.character = CHARACTER if net["character"] == CHARACTER else net["character"]
+        self.lang_char = net["lang_char"]
+        self._wide = len(self.character) > 128                                  # the class mask travels through bbocr_set_class_mask
+        self._text_table = None if self.character is CHARACTER else text_table(self.character)   # None: the English latin-1 fast path
         if isinstance(weights, str) and weights == "empty":
             # multi-GPU receiver: the packed plans are laid out without values and filled by import_weights_blob (dist.broadcast_packed)
             for which, wanted in ((0, detector), (1, recognizer)):
                 if wanted:
                     self._check(self._lib.bbocr_alloc_weights(self._h, which))
             return
-        craft_state, crnn_state = self._resolve_weights(weights, model_storage_directory)
+        craft_state, crnn_state = self._resolve_weights(weights, model_storage_directory, net["model_path"], detector, recognizer)
         if detector:
             self._load(0, craft_state)
         if recognizer:
@@ -489,12 +562,18 @@ class Reader:
 
     # -- weights -------------------------------------------------------------------
     @staticmethod
-    def _resolve_weights(weights, model_storage_directory):
+    def _resolve_weights(weights, model_storage_directory, model_path=None, detector=True, recognizer=True):
         if isinstance(weights, tuple):
             return weights
         if weights == "synthetic" or os.environ.get("BBOCR_SYNTHETIC_WEIGHTS", "") == "1":
             return _weights.designed_craft_state(0), _weights.synthetic_crnn_state(0)
         directory = model_storage_directory or os.environ.get("BBOCR_WEIGHTS_DIR") or os.path.expanduser("~/.EasyOCR/model")
+        if model_path is not None:        # a custom recogniser (recog_network=NAME): its NAME.pth beside the detector's checkpoint
+            wanted = [os.path.join(directory, "craft_mlt_25k.pth") if detector else None, model_path if recognizer else None]
+            for p in wanted:                      # only the half that was asked for is looked for and read
+                if p is not None and not os.path.exists(p):
+                    raise FileNotFoundError(f"{p} not found (this backend never downloads model files)")
+            return tuple(None if p is None else _weights.load_checkpoint(p) for p in wanted)
         return _weights.load_checkpoint_dir(directory)
 
     def _load(self, which, state):
@@ -594,8 +673,13 @@ class Reader:
         for k in _DET_KW + ("contrast_ths", "adjust_contrast"):
             if k in kw and kw[k] is not None:
                 setattr(p, k, kw[k])
-        for i, w in enumerate(ignore_mask(self.character, self.lang_char, kw.get("allowlist"), kw.get("blocklist"))):
-            p.ignore_mask[i] = w
+        words = ignore_mask(self.character, self.lang_char, kw.get("allowlist"), kw.get("blocklist"))
+        if self._wide:                   # kept by the library for THIS thread's next pipeline call; always set, so that no earlier mask lingers
+            arr = (C.c_uint32 * len(words))(*words)
+            self._check(self._lib.bbocr_set_class_mask(self._h, arr, len(words) if any(words) else 0))
+        else:
+            for i, w in enumerate(words):
+                p.ignore_mask[i] = w
         decoder = kw.get("decoder", "greedy")
         self._unsupported(decoder, None, None, None, False, "standard")
         rotation = list(kw.get("rotation_info") or [])
@@ -663,7 +747,10 @@ class Reader:
                 nt = text_off[-1]
                 # every box's text in ONE decode, then plain str slices (a per-box join over numpy objects cost 3 ms per 64 pages); a euro sign
                 # is one character before and after the substitution, so the offsets stay valid
-                chars = _CLASS_BYTES[np.ctypeslib.as_array(r.text_idx, shape=(max(nt, 1),))[:nt]].tobytes().decode("latin-1") if nt else ""
+                tidx = np.ctypeslib.as_array(r.text_idx, shape=(max(nt, 1),))[:nt]
+                if self._text_table is not None:                                     # any other character list: code points, or joined strings
+                    texts = decode_text(self._text_table, tidx, text_off)
+                chars = _CLASS_BYTES[tidx].tobytes().decode("latin-1") if nt and self._text_table is None else ""
                 if "\x80" in chars:
                     chars = chars.replace("\x80", "\u20ac")
                 boxes = quads.astype(np.int64).reshape(nb, 4, 2).tolist()          # horizontal boxes: python ints, like upstream
@@ -671,13 +758,22 @@ class Reader:
                 if free.size:                                                        # free boxes keep their float corners
                     for i, q in zip(free.tolist(), quads[free].reshape(-1, 4, 2).tolist()):
                         boxes[i] = q
-                items = list(zip(boxes, [chars[a:b] for a, b in zip(text_off[:-1], text_off[1:])], conf))
+                if self._text_table is None:
+                    texts = [chars[a:b] for a, b in zip(text_off[:-1], text_off[1:])]
+                items = list(zip(boxes, texts, conf))
             out = [items[box_off[b]:box_off[b + 1]] for b in range(B)]
         finally:
             self._lib.bbocr_free_result(res_p)
         if detail == 0:
             return [[item[1] for item in page] for page in out]
         return out
+
+    def last_ctc_route(self):
+        """Where the text of this thread's last recognise / readtext call came from (bbocr_last_ctc_route): 0 greedy, 1 beam search on the host,
+        2 beam search on the device, 3 greedy with Prediction inside the CTC kernel (more than 128 classes, 16-bit modes), -1 no pass yet"""
+        route = C.c_int(-1)
+        self._check(self._lib.bbocr_last_ctc_route(self._h, C.byref(route)))
+        return int(route.value)
 
     def stage_times(self):
         ms = (C.c_float * 8)()
@@ -1245,8 +1341,12 @@ class Reader:
 
     def ctc_beam_device(self, probs_dev, seqs, beam_width, C=97):
         """The device beam search alone (bbocr_op_ctc_beam): fp32 [rows, cs] device tensor of probabilities, seqs = [(first row, T)], width
-        <= _lib.BEAM_DEVICE_MAX -> one list of class indices per sequence (ctcBeamSearch's text, blank and repeats dropped)."""
+        <= _lib.BEAM_DEVICE_MAX -> one list of class indices per sequence (ctcBeamSearch's text, blank and repeats dropped).  C <= 128: the
+        kernel keeps labels as bytes; a wider model's beam search runs on the host."""
         import ctypes as ct             # the argument C (classes, as in bbocr.h) hides the module's alias here
+
+        if int(C) > 128:
+            raise ValueError("the device beam search takes at most 128 classes")
 
         torch = self._torch
         if (not isinstance(probs_dev, torch.Tensor) or not probs_dev.is_cuda or probs_dev.device.index != self.device_index

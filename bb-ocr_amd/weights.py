@@ -119,8 +119,9 @@ def designed_craft_state(seed: int = 0) -> dict:
 
 
 def synthetic_crnn_state(seed: int = 0, logit_gain: float = 120.0, ih_gain: float = 4.0, hh_gain: float = 1.0,
-                         lin_gain: float = 4.0) -> dict:
-    """Seeded random CRNN (english_g2 architecture: 1x64xW -> T x 97).
+                         lin_gain: float = 4.0, num_class: int = 97) -> dict:
+    """Seeded random CRNN (english_g2 architecture: 1x64xW -> T x ``num_class``; 97 = english_g2, any other count = another generation-2
+    model's Prediction layer on the same network -- the tensors in front of it do not depend on the count).
 
     PyTorch-default initialisation makes a random CRNN emit one constant class with ~1/97
     confidence, which would send every box through the contrast-retry pass.  The gains widen the
@@ -153,8 +154,8 @@ def synthetic_crnn_state(seed: int = 0, logit_gain: float = 120.0, ih_gain: floa
         kl = 1.0 / np.sqrt(512.0)
         sd[sm + "linear.weight"] = (rng.uniform(-kl, kl, (256, 512)) * lin_gain).astype(np.float32)
         sd[sm + "linear.bias"] = rng.uniform(-kl, kl, 256).astype(np.float32)
-    sd["Prediction.weight"] = (rng.uniform(-k, k, (97, 256)) * logit_gain).astype(np.float32)
-    sd["Prediction.bias"] = (rng.uniform(-k, k, 97) * logit_gain).astype(np.float32)
+    sd["Prediction.weight"] = (rng.uniform(-k, k, (int(num_class), 256)) * logit_gain).astype(np.float32)
+    sd["Prediction.bias"] = (rng.uniform(-k, k, int(num_class)) * logit_gain).astype(np.float32)
     return sd
 
 

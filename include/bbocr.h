@@ -78,10 +78,20 @@ typedef struct bbocr_config {
                          * crop and, for the recurrent product, per direction and time step; int32 accumulation on v_mfma_i32_16x16x64_i8), every
                          * crop on its own as readtext(batch_size=1) runs it.  The conv stack, the 3-row mean and CTC are unchanged.  Allowed with
                          * BBOCR_PREC_EXACT and BBOCR_PREC_EXACT_REC only (what is quantised are the fp32 path's features, which those modes deliver
-                         * to 1e-5); any other precision or value: bbocr_create returns BBOCR_ERR_ARG.  The weight blob carries the flag: a blob of
+                         * to 1e-5); any other precision or value: bbocr_create returns BBOCR_ERR_ARG, and so it does with rec_classes
+                         * other than 97 (0): the int8 Prediction is built for english_g2's 97 classes alone.  The weight blob carries the flag: a blob of
                          * the other kind is refused (BBOCR_ERR_WEIGHTS).  DESIGN.md section 4 states the arithmetic. */
-    int reserved[1];
+    int rec_classes;    /* classes of the recogniser's Prediction layer, the CTC blank (class 0) included: 0 (default) = 97, english_g2.  Every
+                         * generation-2 model of easyocr shares the CRNN and differs in this number alone (latin_g2 352, zh_sim_g2 6,719).  Valid:
+                         * 2 .. BBOCR_REC_CLASSES_MAX; bbocr_load_weights then wants Prediction.weight [rec_classes, 256] and Prediction.bias
+                         * [rec_classes] (BBOCR_ERR_WEIGHTS otherwise), the weight blob carries the count (a blob of another count:
+                         * BBOCR_ERR_WEIGHTS) and bbocr_result::text_idx holds 1 .. rec_classes - 1.  Up to 128 classes nothing else changes.
+                         * Above 128 the class mask comes from bbocr_set_class_mask, decoder == BEAMSEARCH is searched on the host, and greedy
+                         * passes of the 16-bit precisions run Prediction + softmax + arg-max as ONE kernel that never stores the logits
+                         * (pred_ctc.hip).  rec_quant == 1 with any count but 97, or a count outside the range: bbocr_create
+                         * returns BBOCR_ERR_ARG. */
 } bbocr_config;
+#define BBOCR_REC_CLASSES_MAX 8192
 enum { BBOCR_PREC_BF16 = 0, BBOCR_PREC_FP16 = 1, BBOCR_PREC_EXACT = 2, BBOCR_PREC_MIXED = 3, BBOCR_PREC_EXACT_REC = 4 };
 
 /* One tensor of an upstream state-dict (easyocr/craft.py::CRAFT or easyocr/model/vgg_model.py::Model key names,
@@ -259,6 +269,23 @@ void bbocr_free_result(bbocr_result* r);
  * [3] crops (S6/S7), [4] recogniser net (S8), [5] CTC decode (S9), [6] contrast retry pass, [7] total */
 int bbocr_stage_times(bbocr_ctx* ctx, float* ms, int n);
 
+/* recognizer_predict's ignore_idx for a context of MORE than 128 classes (bbocr_config::rec_classes), whose classes bbocr_params::ignore_mask
+ * cannot name: bit c of words[c >> 5] removes class c; n_words <= ceil(rec_classes / 32), the words behind them count as 0; n_words = 0
+ * clears the mask.  Bits at or behind rec_classes, and bit 0 (the CTC blank), are BBOCR_ERR_ARG.  A thread holds ONE mask, for ONE context:
+ * setting a mask on another context drops the one it held (that context's calls from this thread then run without a mask), so a thread
+ * that alternates between wide contexts sets the mask before each call, as the Python Reader does.  bbocr_destroy called from the thread
+ * drops its mask for that context; a mask another thread still holds for a destroyed context must be cleared by that thread (n_words = 0 on
+ * any live context, or a new mask) before it uses a context created later.  The mask is kept FOR THE CALLING THREAD (as
+ * bbocr_last_error and bbocr_stage_times are) and read by that thread's later recognise / readtext calls on this context, so two calls in
+ * flight never see each other's mask.  On a context of at most 128 classes: BBOCR_ERR_ARG, and bbocr_params::ignore_mask rules as before
+ * (on a wider context its four words are not read, the blank's bit excepted, which stays an argument error). */
+int bbocr_set_class_mask(bbocr_ctx* ctx, const uint32_t* words, int n_words);
+/* where the text of the LAST sequence pass of the calling thread's last recognise / readtext call on this context came from: 0 greedy
+ * (Prediction launch + row kernel + collapse), 1 beam search on the host, 2 beam search on the device, 3 greedy with Prediction inside the CTC
+ * kernel (more than 128 classes, 16-bit precisions: no logits stored); -1: no such pass (no call, a call without boxes, or the thread's
+ * last call was on another context: like bbocr_stage_times this is the record of the calling thread's LAST call) */
+int bbocr_last_ctc_route(bbocr_ctx* ctx, int* route);
+
 /* Per-launch timing of the dominant kernel (conv_mfma) with HIP events recorded on the context's stream.
  * group 0 = detector convs, 1 = recogniser convs/GEMMs.  on = 1 times group 0 only (54 launches per 64-page step: the roofline
  * leg of bench.py), on = 2 both groups (about ten times as many events: ~1.5 % of a step), 0 = off.  Totals accumulate from the call on:
@@ -346,7 +373,8 @@ int bbocr_host_conv_route(int el, int N, int H, int W, int Cin, int Cout, int KH
 int bbocr_op_conv2d_route(bbocr_ctx* ctx, bbocr_conv_route* out);
 /* recogniser network only: crops [n,64,imgW] (device, 16-bit elements of the context's RECOGNISER type: bf16 (BF16) / fp16 (FP16, MIXED) values already
  * normalised to [-1, 1]; BBOCR_PREC_EXACT: CODES, 0 = padding zero, 1 + grey level otherwise, from which the first layer rebuilds the
- * fp32 input ((g/255 - 0.5)/0.5) exactly) -> logits fp32 [n,T,112] (device), T = imgW/4-1 */
+ * fp32 input ((g/255 - 0.5)/0.5) exactly) -> logits fp32 [n,T,cs] (device), T = imgW/4-1, cs = rec_classes rounded up to 16 (112 for the
+ * 97 classes of english_g2; the columns behind the classes hold 0).  More than 128 classes: always through the unfused Prediction launch */
 int bbocr_crnn_logits(bbocr_ctx* ctx, const uint16_t* dev_crops, int n, int imgW, float* dev_logits);
 /* rec_quant contexts only: ONE dynamically quantised matrix product of the sequence half.  dev_x fp32 [rows, K] (device), seqs (host): nseq
  * pairs {first row, T} that tile [0, rows) in order -- one set of activation parameters per pair (crop).  layer: 0 / 1 = the input
@@ -362,14 +390,31 @@ int bbocr_op_qlinear(bbocr_ctx* ctx, const float* dev_x, int rows, const int* se
  * direction's first step). */
 int bbocr_op_qlstm(bbocr_ctx* ctx, const float* dev_g, int rows, const int* seqs, int nseq, int layer, float* dev_h, float* dev_c, uint8_t* dev_hcodes,
                    float* dev_hparams);
-/* CTC decode of logits fp32 [n,T,cs]: host outputs text_off [n+1], text_idx (<= n*T), conf [n]; ignore_mask: 4 x 32-bit class mask
- * (bbocr_params::ignore_mask) or NULL; beam_width <= 0: greedy, > 0: ctcBeamSearch with that width (bbocr_params::decoder) */
+/* CTC decode of logits fp32 [n,T,cs]: host outputs text_off [n+1], text_idx (<= n*T), conf [n]; ignore_mask (host): the class mask, 4 words
+ * for C <= 128 (bbocr_params::ignore_mask), ceil(C / 32) words for a wider C (the wide rows kernel, one wavefront per row), or NULL;
+ * beam_width <= 0: greedy, > 0: ctcBeamSearch with that width (bbocr_params::decoder; C > 128: on the host).  C > 128 is taken on a context
+ * created with rec_classes > 128 (then up to BBOCR_REC_CLASSES_MAX) and is BBOCR_ERR_ARG on any other, here and in the two entry points below */
 int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, int cs, int* text_off, int* text_idx, double* conf,
                  const unsigned int* ignore_mask, int beam_width);
-/* the probabilities alone, as the CTC stage's row kernel writes them: softmax of logits fp32 [rows,cs] over C <= 128 classes, the classes of
- * ignore_mask (or NULL) zeroed, the rest renormalised -> dev_probs_out fp32 [rows,cs] (device; columns >= C are not written) */
+/* the probabilities alone, as the CTC stage's row kernel writes them: softmax of logits fp32 [rows,cs] over C classes (C <= 128: ctc_rows_kernel,
+ * wider: ctc_rows_wide_kernel), the classes of ignore_mask (host words as in bbocr_op_ctc, or NULL) zeroed, the rest renormalised ->
+ * dev_probs_out fp32 [rows,cs] (device; columns >= C are neither read nor written) */
 int bbocr_op_ctc_probs(bbocr_ctx* ctx, const float* dev_logits, size_t rows, int C, int cs, const unsigned int* ignore_mask,
                        float* dev_probs_out);
+/* the same with arg-max, collapse and confidence product kept: dev_probs_out may be NULL; idx, pmax [rows], out_idx [rows] and ctc_out
+ * [nseq][4] = {len, cnt, prod bits, 0} are DEVICE tensors the caller owns (what a recognition pass reads back); seqs (host) = {first row, T} */
+int bbocr_op_ctc_rows(bbocr_ctx* ctx, const float* dev_logits, size_t rows, int C, int cs, const unsigned int* ignore_mask, const int* seqs,
+                      int nseq, float* dev_probs_out, int* dev_idx, float* dev_pmax, int* dev_out_idx, int* dev_ctc_out);
+/* Prediction alone, as a sequence pass of a 16-bit precision launches it on the unfused route (the conv plan over rows padded to whole
+ * 256-row tiles): dev_x [rows, 256] elements of the recogniser type -> dev_logits fp32 [rows, cs], cs = rec_classes rounded up to 16 */
+int bbocr_op_pred(bbocr_ctx* ctx, const uint16_t* dev_x, size_t rows, float* dev_logits);
+/* contexts of more than 128 classes in a 16-bit precision: Prediction + softmax + mask + arg-max of a recognition pass's greedy route as the
+ * ONE kernel that stores no logits (pred_ctc.hip), alone, with the context's Prediction weights.  dev_x: [rows, 256] elements of the
+ * recogniser type (the second BiLSTM stage's output); dev_mask_words: n_words (<= ceil(rec_classes / 32)) DEVICE words or NULL; outputs
+ * (device): dev_idx int32 [rows] = the unmasked class of the largest logit (lowest index among equals), dev_pmax fp32 [rows] = its
+ * renormalised probability (e_best / sum_all) / (sum_unmasked / sum_all) */
+int bbocr_op_pred_ctc(bbocr_ctx* ctx, const uint16_t* dev_x, size_t rows, const uint32_t* dev_mask_words, int n_words, int* dev_idx,
+                      float* dev_pmax);
 /* the device beam search alone (the kernel behind decoder == BEAMSEARCH for widths <= BBOCR_BEAM_DEVICE_MAX): dev_probs fp32 [rows,cs]
  * (device), seqs (host) = {first row, T} per sequence, ragged, T = 0 allowed -> text_off [nseq+1], text_idx (<= the sum of T), both host.
  * The text equals bbocr_host_ctc_beam's on the same rows, exactly.  BBOCR_ERR_ARG before anything is queued: a null pointer, cs < C,
