@@ -18,6 +18,11 @@ class bbocr_config(C.Structure):
                 ("host_threads", C.c_int), ("rec_quant", C.c_int), ("rec_classes", C.c_int)]
 
 
+class bbocr_config_v2(C.Structure):
+    """bbocr.h bbocr_config_v2: bbocr_config (whose 32 bytes stand) with the later fields appended; what bbocr_create_v2 takes"""
+    _fields_ = bbocr_config._fields_ + [("beam_wide", C.c_int)]
+
+
 PRECISIONS = {"bf16": 0, "fp16": 1, "exact": 2, "mixed": 3, "exact_rec": 4}
 REC_CLASSES_MAX = 8192                                                           # bbocr.h BBOCR_REC_CLASSES_MAX
 BEAM_DEVICE_MAX = 32                                                             # bbocr.h BBOCR_BEAM_DEVICE_MAX
@@ -123,6 +128,7 @@ class bbocr_result(C.Structure):
 _vp = C.c_void_p
 PROTOTYPES = {
     "bbocr_create": (C.c_int, [C.POINTER(bbocr_config), C.POINTER(_vp)]),
+    "bbocr_create_v2": (C.c_int, [C.POINTER(bbocr_config_v2), C.POINTER(_vp)]),
     "bbocr_destroy": (None, [_vp]),
     "bbocr_last_error": (C.c_char_p, [_vp]),
     "bbocr_default_params": (None, [C.POINTER(bbocr_params)]),
@@ -157,6 +163,7 @@ PROTOTYPES = {
     "bbocr_free_result": (None, [C.POINTER(bbocr_result)]),
     "bbocr_stage_times": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "bbocr_last_ctc_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "bbocr_last_ctc_host_sequences": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "bbocr_set_class_mask": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_int]),
     "bbocr_set_profiling": (C.c_int, [_vp, C.c_int]),
     "bbocr_conv_profile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
@@ -181,6 +188,9 @@ PROTOTYPES = {
     "bbocr_op_pred_ctc": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp]),
     "bbocr_op_ctc_beam": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int)]),
+    "bbocr_op_ctc_beam_wide": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_host_ctc_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "bbocr_op_resize_u8": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int]),
     "bbocr_op_ycc_to_rgb": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "bbocr_upload_pages": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, C.c_size_t, _vp]),

@@ -20,16 +20,22 @@ void bbocr_default_params(bbocr_params* p) {
 }
 
 int bbocr_create(const bbocr_config* cfg, bbocr_ctx** out) {
+    bbocr_config_v2 v2{};
+    if (cfg) v2.base = *cfg;
+    return bbocr_create_v2(&v2, out);
+}
+
+int bbocr_create_v2(const bbocr_config_v2* cfg, bbocr_ctx** out) {
     if (!out) return BBOCR_ERR_ARG;
     *out = nullptr;
     bbocr_ctx* c = nullptr;
     try {
         c = new bbocr_ctx();
         c->root = c;
-        if (cfg) c->cfg = *cfg;
+        if (cfg) { c->cfg = cfg->base; c->cfg_beam_wide = cfg->beam_wide; }
         if (c->cfg.precision < BBOCR_PREC_BF16 || c->cfg.precision > BBOCR_PREC_EXACT_REC || c->cfg.call_slots < 0 || c->cfg.call_slots > kMaxSlots ||
             c->cfg.rec_quant < 0 || c->cfg.rec_quant > 1 || (c->cfg.rec_quant == 1 && !rec_split(c)) ||     // rec_quant quantises the exact conv stack's features
-            c->cfg.rec_classes < 0 || rec_classes(c) < 2 || rec_classes(c) > BBOCR_REC_CLASSES_MAX ||
+            c->cfg.rec_classes < 0 || rec_classes(c) < 2 || rec_classes(c) > BBOCR_REC_CLASSES_MAX || c->cfg_beam_wide < 0 || c->cfg_beam_wide > 1 ||
             // the int8 sequence half is built, packed and tested for english_g2's 97 classes in 112 stored columns: any other count is out of its scope
             (c->cfg.rec_quant == 1 && rec_classes(c) != kRecClassesDefault)) {
             delete c;                      // an unknown value must not silently mean one of the modes
@@ -63,6 +69,7 @@ bbocr_ctx* slot_create(bbocr_ctx* root) {
     bbocr_ctx* s = new bbocr_ctx();
     s->root = root;
     s->cfg = root->cfg;
+    s->cfg_beam_wide = root->cfg_beam_wide;
     s->stream = root->stream;
     hipError_t e = hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking);
     if (e == hipSuccess) e = create_seq_stream(&s->seq_stream);
@@ -90,7 +97,7 @@ void slot_destroy(bbocr_ctx* c) {
     DevBuf* bufs[] = {&c->arena.buf, &c->heat, &c->gray, &c->resized, &c->ccl_label, &c->ccl_stat, &c->ccl_slot, &c->ccl_comps, &c->ccl_rowext,
                       &c->ccl_counters, &c->crop_desc, &c->crop_desc2, &c->crop_scratch, &c->crop_hscratch, &c->crop_wscratch, &c->crop_luts, &c->crop_hist,
                       &c->ctc_idx, &c->ctc_pmax, &c->ctc_out_idx, &c->ctc_out, &c->seq_v, &c->seq_xp, &c->seq_h, &c->seq_lin, &c->seq_logits,
-                      &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out, &c->pe_out,
+                      &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ctc_cand, &c->ctc_cand_n, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out, &c->pe_out,
                       &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp, &c->ctc_mask};
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -100,7 +107,7 @@ void slot_destroy(bbocr_ctx* c) {
 
 // stage times of the call a thread has just finished (bbocr_stage_times): per calling thread, because one context serves several
 namespace {
-struct ThreadTimes { const bbocr_ctx* root = nullptr; float ms[8] = {0}; int ctc_route = -1; };
+struct ThreadTimes { const bbocr_ctx* root = nullptr; float ms[8] = {0}; int ctc_route = -1; int ctc_host_seqs = 0; };
 thread_local ThreadTimes tl_times;
 thread_local std::string tl_err;
 struct ThreadMask { const bbocr_ctx* root = nullptr; std::vector<unsigned int> words; };
@@ -115,6 +122,7 @@ void publish_times(const bbocr_ctx* s) {
     tl_times.root = s->root;
     memcpy(tl_times.ms, s->times, sizeof(tl_times.ms));
     tl_times.ctc_route = s->ctc_last_route;
+    tl_times.ctc_host_seqs = s->ctc_host_seqs;
 }
 
 extern "C" {
@@ -372,6 +380,12 @@ int bbocr_set_class_mask(bbocr_ctx* ctx, const uint32_t* words, int n_words) {
 int bbocr_last_ctc_route(bbocr_ctx* ctx, int* route) {
     if (!ctx || !route) return BBOCR_ERR_ARG;
     *route = tl_times.root == ctx ? tl_times.ctc_route : -1;
+    return BBOCR_OK;
+}
+
+int bbocr_last_ctc_host_sequences(bbocr_ctx* ctx, int* n) {
+    if (!ctx || !n) return BBOCR_ERR_ARG;
+    *n = tl_times.root == ctx ? tl_times.ctc_host_seqs : 0;
     return BBOCR_OK;
 }
 

@@ -397,7 +397,8 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
         const unsigned int* mask_dev = op_wide_mask(ctx, C, ignore_mask);
         std::vector<int> seqs;
         for (int i = 0; i < n; ++i) { seqs.push_back(i * T); seqs.push_back(T); }
-        const int route = ctc_route(beam_width, C, seqs.data(), n);       // as rec_finish routes a recognition pass
+        const int route = ctc_route(beam_width, C, seqs.data(), n, false, rec_beam_wide(ctx));       // as rec_finish routes a recognition pass
+        const bool dev_beam = route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE;
         ctc_size(ctx, rows, n, cs, route);
         ctx->seq_tables.ensure(seqs.size() * 4);
         HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -409,14 +410,18 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
             HIPCHK(launch_ctc(dev_logits, rows, C, cs, (const int*)ctx->seq_tables.p, n, (int*)ctx->ctc_idx.p, (float*)ctx->ctc_pmax.p,
                               (int*)ctx->ctc_out_idx.p, (CtcOut*)ctx->ctc_out.p, ctx->stream, ignore_mask,
                               route != CTC_GREEDY ? (float*)ctx->ctc_probs.p : nullptr));
-        std::vector<int> oidx(rows), blen(route == CTC_BEAM_DEVICE ? n : 0);
+        std::vector<int> oidx(rows), blen(dev_beam ? n : 0);
         std::vector<CtcOut> oo(n);
         std::vector<float> probs(route == CTC_BEAM_HOST ? rows * cs : 0);
         std::vector<std::vector<int>> beam_texts;
         HIPCHK(hipMemcpyAsync(oo.data(), ctx->ctc_out.p, oo.size() * sizeof(CtcOut), hipMemcpyDeviceToHost, ctx->stream));
-        if (route == CTC_BEAM_DEVICE) {            // the search's text takes the place of the greedy classes
-            HIPCHK(launch_ctc_beam((const float*)ctx->ctc_probs.p, rows, C, cs, (const int*)ctx->seq_tables.p, n, T, beam_width,
-                                   (int*)ctx->ctc_beam_idx.p, (int*)ctx->ctc_beam_len.p, ctx->stream));
+        if (dev_beam) {            // the search's text takes the place of the greedy classes
+            if (route == CTC_BEAM_DEVICE_WIDE)
+                HIPCHK(launch_ctc_beam_wide((const float*)ctx->ctc_probs.p, rows, C, cs, (const int*)ctx->seq_tables.p, n, T, beam_width,
+                                            (int*)ctx->ctc_cand_n.p, (int*)ctx->ctc_cand.p, (int*)ctx->ctc_beam_idx.p, (int*)ctx->ctc_beam_len.p, ctx->stream));
+            else
+                HIPCHK(launch_ctc_beam((const float*)ctx->ctc_probs.p, rows, C, cs, (const int*)ctx->seq_tables.p, n, T, beam_width,
+                                       (int*)ctx->ctc_beam_idx.p, (int*)ctx->ctc_beam_len.p, ctx->stream));
             HIPCHK(hipMemcpyAsync(oidx.data(), ctx->ctc_beam_idx.p, oidx.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(blen.data(), ctx->ctc_beam_len.p, blen.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
         } else {
@@ -426,12 +431,14 @@ int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, i
         }
         slot_sync(ctx, ctx->stream);
         if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), n, C, cs, beam_width, beam_texts, &host_pool(ctx));
+        if (route == CTC_BEAM_DEVICE_WIDE)
+            ctc_beam_wide_fallback(ctx, ctx->stream, (const float*)ctx->ctc_probs.p, seqs.data(), n, C, cs, beam_width, blen.data(), beam_texts);
         std::vector<int> text;
         int o = 0;
         for (int i = 0; i < n; ++i) {
             text_off[i] = o;
-            if (route == CTC_BEAM_HOST) conf[i] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), text);
-            else conf[i] = ctc_decode(oo[i], oidx.data() + (size_t)i * T, route == CTC_BEAM_DEVICE ? std::clamp(blen[i], 0, T) : oo[i].len, text);
+            if (route == CTC_BEAM_HOST || (route == CTC_BEAM_DEVICE_WIDE && blen[i] < 0)) conf[i] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), text);
+            else conf[i] = ctc_decode(oo[i], oidx.data() + (size_t)i * T, dev_beam ? std::clamp(blen[i], 0, T) : oo[i].len, text);
             for (int v : text) text_idx[o++] = v;
         }
         text_off[n] = o;
@@ -545,6 +552,53 @@ int bbocr_op_ctc_beam(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const
         }
         text_off[nseq] = o;
     });
+}
+
+int bbocr_op_ctc_beam_wide(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width, int* text_off,
+                           int* text_idx, int* n_host) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        if (!dev_probs || !seqs || !text_off || !text_idx || nseq <= 0 || rows > (size_t)INT32_MAX || C <= 128 || C > op_ctc_max_classes(ctx) || cs < C ||
+            beam_width < 1 || beam_width > BBOCR_BEAM_DEVICE_MAX)
+            fail(BBOCR_ERR_ARG, "bad beam-search arguments");
+        int max_T = 0;
+        for (int i = 0; i < nseq; ++i) {
+            const long long first = seqs[2 * i], T = seqs[2 * i + 1];
+            if (first < 0 || T < 0 || first + T > (long long)rows) fail(BBOCR_ERR_ARG, "a sequence lies outside the rows");
+            max_T = std::max(max_T, (int)T);
+        }
+        if (!ctc_beam_wide_on_device(beam_width, C, max_T)) fail(BBOCR_ERR_ARG, "the longest sequence does not fit the device search at this width");
+        ctx->seq_tables.ensure((size_t)nseq * 8);
+        ctx->ctc_beam_idx.ensure(std::max<size_t>(rows, 1) * 4);
+        ctx->ctc_beam_len.ensure((size_t)nseq * 4);
+        ctx->ctc_cand.ensure(std::max<size_t>(rows, 1) * (size_t)kBeamWideCand * 8);
+        ctx->ctc_cand_n.ensure(std::max<size_t>(rows, 1) * 4);
+        HIPCHK(hipMemcpyAsync(ctx->seq_tables.p, seqs, (size_t)nseq * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(launch_ctc_beam_wide(dev_probs, rows, C, cs, (const int*)ctx->seq_tables.p, nseq, max_T, beam_width, (int*)ctx->ctc_cand_n.p,
+                                    (int*)ctx->ctc_cand.p, (int*)ctx->ctc_beam_idx.p, (int*)ctx->ctc_beam_len.p, ctx->stream));
+        std::vector<int> bidx(rows), blen(nseq);
+        if (rows) HIPCHK(hipMemcpyAsync(bidx.data(), ctx->ctc_beam_idx.p, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(blen.data(), ctx->ctc_beam_len.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+        std::vector<std::vector<int>> host_texts;
+        const int nh = ctc_beam_wide_fallback(ctx, ctx->stream, dev_probs, seqs, nseq, C, cs, beam_width, blen.data(), host_texts);
+        int o = 0;
+        for (int i = 0; i < nseq; ++i) {
+            text_off[i] = o;
+            if (blen[i] < 0) {
+                for (int v : host_texts[i]) text_idx[o++] = v;
+                continue;
+            }
+            const int n = std::min(blen[i], seqs[2 * i + 1]);
+            for (int k = 0; k < n; ++k) text_idx[o++] = bidx[(size_t)seqs[2 * i] + k];
+        }
+        text_off[nseq] = o;
+        if (n_host) *n_host = nh;
+    });
+}
+
+int bbocr_host_ctc_route(int beam_wide, int beam_width, int C, const int* seqs, int nseq) {
+    if ((nseq > 0 && !seqs) || nseq < 0) return BBOCR_ERR_ARG;
+    return ctc_route(beam_width, C, seqs, nseq, false, beam_wide == 1 && C > 128);
 }
 
 int bbocr_op_resize_u8(bbocr_ctx* ctx, const uint8_t* dev_src, int N, int sh, int sw, int C, uint8_t* dev_dst, int dh, int dw) {

@@ -185,6 +185,7 @@ struct WeightView {
 // with the last pass's box geometry, CTC read-back and result export (the ~8 % of a step that left the card idle).
 struct bbocr_ctx : WeightView {
     bbocr_config cfg{};
+    int cfg_beam_wide = 0;                    // bbocr_config_v2::beam_wide (bbocr_create: 0)
     bbocr_ctx* root = nullptr;                // slot -> its root; the root points at itself
     std::vector<bbocr_ctx*> slots;            // root only: extra call slots, created when a second call arrives while the first is running
     std::mutex pool_mu;                       // root only: guards slot_busy / slots / err / prof totals / last_times
@@ -210,6 +211,7 @@ struct bbocr_ctx : WeightView {
     int beam_width = 0;                           // > 0: decoder='beamsearch' for the running call (bbocr_params::decoder / beam_width)
     std::vector<unsigned int> class_mask;         // more than 128 classes: the calling thread's bbocr_set_class_mask words, padded to ceil(C / 32)
     DevBuf ctc_mask;                              // ... on the device (uploaded by the sequence stage that reads them)
+    int ctc_host_seqs = 0;                        // sequences of this slot's latest call that a CTC_BEAM_DEVICE_WIDE pass left to the host search (bbocr_last_ctc_host_sequences)
     int ctc_last_route = -1;                      // what ctc_route answered for this slot's latest sequence pass (CTC_*); published per calling thread with the stage times (bbocr_last_ctc_route)
     hipStream_t cur = nullptr;                // stream the layer helpers launch on
     SideLane upload_lane;                     // root only: bbocr_upload_pages copies here (an upload never waits for a running call)
@@ -252,7 +254,7 @@ struct bbocr_ctx : WeightView {
     PinBuf pg_pin;                            // staging of the page tables' upload
     DevBuf ccl_label, ccl_stat, ccl_slot, ccl_comps, ccl_rowext, ccl_counters;
     DevBuf crop_desc, crop_scratch, crop_hscratch, crop_wscratch, crop_luts, crop_hist;
-    DevBuf ctc_idx, ctc_pmax, ctc_out_idx, ctc_out, ctc_probs, ctc_beam_idx, ctc_beam_len, crop_desc2;
+    DevBuf ctc_idx, ctc_pmax, ctc_out_idx, ctc_out, ctc_probs, ctc_beam_idx, ctc_beam_len, ctc_cand, ctc_cand_n, crop_desc2;
     PinBuf desc_pin, desc_pin2;               // staging of crop_desc / crop_desc2 uploads
     PinBuf ctc_pin;                           // CTC results land here (pinned: the 1.7 MB D2H copy of a 64-page pass runs at link speed)
     DevBuf seq_v, seq_xp, seq_h, seq_lin, seq_logits, seq_tables;
@@ -269,7 +271,8 @@ inline bool rec_quant(const bbocr_ctx* c) { return c->cfg.rec_quant == 1; }     
 constexpr int kRecClassesDefault = 97;
 inline int rec_classes(const bbocr_ctx* c) { return c->cfg.rec_classes > 0 ? c->cfg.rec_classes : kRecClassesDefault; }
 inline int rec_cs(const bbocr_ctx* c) { return (rec_classes(c) + 15) / 16 * 16; }
-inline bool rec_wide(const bbocr_ctx* c) { return rec_classes(c) > 128; }       // beyond ctc_rows_kernel, bbocr_params::ignore_mask and the device beam search
+inline bool rec_wide(const bbocr_ctx* c) { return rec_classes(c) > 128; }       // beyond ctc_rows_kernel, bbocr_params::ignore_mask and ctc_beam_kernel
+inline bool rec_beam_wide(const bbocr_ctx* c) { return c->cfg_beam_wide == 1 && rec_wide(c); }   // beam searches of a wide context go to ctc_beam_wide.hip
 inline bool det_split(const bbocr_ctx* c) { return c->cfg.precision == BBOCR_PREC_EXACT; }   // and so are the detector's (split-fp16 plans in every layer)
 
 // ------------------------------------------------------------------------------------------------ shared types
@@ -455,10 +458,16 @@ void crnn_seq_lin(bbocr_ctx* c, int l, const uint16_t* h, size_t rows_pad, uint1
 void crnn_seq_pred(bbocr_ctx* c, const uint16_t* x, size_t rows_pad, float* logits);
 void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);    // rec_quant: run.tiles rebuilt as the int8 recurrence's {first sequence, n, longest T, 0}
 // where the text of a CTC pass comes from (ctc_route).  CTC_GREEDY_FUSED: greedy over more than 128 classes with Prediction inside the CTC
-// kernel (pred_ctc.hip) -- the pass has no logits
-enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2, CTC_GREEDY_FUSED = 3 };
-// seqs: {first row, T} per sequence (host); fused_ok: the caller holds Prediction's input and pred_ctc_kernel's weights (a 16-bit recognition pass)
-int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok = false);
+// kernel (pred_ctc.hip) -- the pass has no logits.  CTC_BEAM_DEVICE_WIDE: the device search over more than 128 classes (ctc_beam_wide.hip),
+// taken only by a context created with bbocr_config_v2::beam_wide
+enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2, CTC_GREEDY_FUSED = 3, CTC_BEAM_DEVICE_WIDE = 4 };
+// seqs: {first row, T} per sequence (host); fused_ok: the caller holds Prediction's input and pred_ctc_kernel's weights (a 16-bit recognition pass);
+// beam_wide: bbocr_config_v2::beam_wide of the context
+int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok = false, bool beam_wide = false);
+// after the wait of a CTC_BEAM_DEVICE_WIDE pass: the sequences the kernel left to the host (blen[i] == -1, a row of more than kBeamWideCand
+// candidates) are searched by ctc_beam_search_host from their own rows of probs_dev, copied over `s` -> texts[i] (sized nseq); returns their number
+int ctc_beam_wide_fallback(bbocr_ctx* c, hipStream_t s, const float* probs_dev, const int* seqs, int nseq, int C, int cs, int beam_width, const int* blen,
+                           std::vector<std::vector<int>>& texts);
 const unsigned int* thread_class_mask(const bbocr_ctx* root, int* n_words);   // abi.cpp: the calling thread's bbocr_set_class_mask words for `root`, or null
 void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route);
 double ctc_decode(const CtcOut& o, const int* idx, int n, std::vector<int>& text);
@@ -559,6 +568,7 @@ struct SlotLease {
         if (slot != root) {
             static_cast<WeightView&>(*slot) = static_cast<const WeightView&>(*root);   // weights may have been loaded since the slot was made
             slot->cfg = root->cfg;
+            slot->cfg_beam_wide = root->cfg_beam_wide;
             slot->profiling = root->profiling;
         }
     }

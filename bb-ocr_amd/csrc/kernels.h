@@ -271,6 +271,16 @@ size_t ctc_beam_lds_bytes(int beam_width, int C, int max_T);
 bool ctc_beam_on_device(int beam_width, int C, int max_T);
 hipError_t launch_ctc_beam(const float* probs, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int max_T, int beam_width, int* out_text,
                            int* out_len, hipStream_t s);
+// the device search for 128 < C <= BBOCR_REC_CLASSES_MAX (ctc_beam_wide.hip; bbocr_config_v2::beam_wide): ctc_beam_cand_kernel lists every row's
+// candidates (cand_n int32 [rows]: the count; cand [rows][kBeamWideCand] {class, p bits}: the first kBeamWideCand of them, ascending), then
+// ctc_beam_wide_kernel searches one sequence per wave from that list and the two values it gathers from the full row.  Outputs as
+// launch_ctc_beam's, except that a sequence with a row of more than kBeamWideCand candidates gets out_len = -1 and no text: the caller
+// searches it on the host.  Ask ctc_beam_wide_on_device first (width, class range, LDS block of the longest sequence).
+constexpr int kBeamWideCand = 128;
+size_t ctc_beam_wide_lds_bytes(int beam_width, int max_T);
+bool ctc_beam_wide_on_device(int beam_width, int C, int max_T);
+hipError_t launch_ctc_beam_wide(const float* probs, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int max_T, int beam_width, int* cand_n,
+                                int* cand, int* out_text, int* out_len, hipStream_t s);
 
 // ------------------------------------------------------------------ OCR pre-processing chain (preproc.hip), SURVEY 8 row f2
 int pp_resize_tile_rows(int H, int W, int dh, int dw);

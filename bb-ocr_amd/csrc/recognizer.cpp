@@ -317,12 +317,39 @@ void rec_add_tables(RecRun& run, const RecPart& part, int tile_seqs) {
 }
 
 // where a CTC pass's text comes from: the greedy collapse, or ctcBeamSearch on the device (widths up to BBOCR_BEAM_DEVICE_MAX whose longest
-// sequence fits the kernel's LDS block) or on the host (wider beams, longer sequences: the probabilities cross to the host)
-int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok) {
+// sequence fits the kernel's LDS block) or on the host (wider beams, longer sequences: the probabilities cross to the host).  More than 128
+// classes are searched on the device only where the context asks for it (bbocr_config_v2::beam_wide), under the same two conditions.
+int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok, bool beam_wide) {
     if (beam_width <= 0) return (C > 128 && fused_ok) ? CTC_GREEDY_FUSED : CTC_GREEDY;
     int max_T = 0;
     for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
+    if (beam_wide && ctc_beam_wide_on_device(beam_width, C, max_T)) return CTC_BEAM_DEVICE_WIDE;
     return ctc_beam_on_device(beam_width, C, max_T) ? CTC_BEAM_DEVICE : CTC_BEAM_HOST;
+}
+
+int ctc_beam_wide_fallback(bbocr_ctx* c, hipStream_t s, const float* probs_dev, const int* seqs, int nseq, int C, int cs, int beam_width, const int* blen,
+                           std::vector<std::vector<int>>& texts) {
+    texts.assign((size_t)nseq, {});
+    std::vector<int> over, tab;            // the overflowed sequences; their {first row, T} in the host copy
+    size_t rows = 0;
+    for (int i = 0; i < nseq; ++i)
+        if (blen[i] < 0) {
+            over.push_back(i);
+            tab.push_back((int)rows);
+            tab.push_back(seqs[2 * i + 1]);
+            rows += (size_t)seqs[2 * i + 1];
+        }
+    if (over.empty()) return 0;
+    std::vector<float> probs(rows * (size_t)cs);
+    for (size_t k = 0; k < over.size(); ++k)
+        if (tab[2 * k + 1] > 0)
+            HIPCHK(hipMemcpyAsync(probs.data() + (size_t)tab[2 * k] * cs, probs_dev + (size_t)seqs[2 * over[k]] * cs, (size_t)tab[2 * k + 1] * cs * sizeof(float),
+                                  hipMemcpyDeviceToHost, s));
+    slot_sync(c, s);
+    std::vector<std::vector<int>> found;
+    ctc_beam_search_batch(probs.data(), tab.data(), (int)over.size(), C, cs, beam_width, found, &host_pool(c));
+    for (size_t k = 0; k < over.size(); ++k) texts[over[k]].swap(found[k]);
+    return (int)over.size();
 }
 
 // device buffers of one launch_ctc over `rows` time steps of `nseq` sequences (cs: row stride of the logits; a beam route keeps the
@@ -332,10 +359,14 @@ void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route) {
     c->ctc_pmax.ensure(rows * 4);
     c->ctc_out_idx.ensure(rows * 4);
     c->ctc_out.ensure((size_t)nseq * sizeof(CtcOut));
-    if (route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE) c->ctc_probs.ensure(rows * cs * sizeof(float));
-    if (route == CTC_BEAM_DEVICE) {
+    if (route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE) c->ctc_probs.ensure(rows * cs * sizeof(float));
+    if (route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE) {
         c->ctc_beam_idx.ensure(rows * 4);
         c->ctc_beam_len.ensure((size_t)nseq * 4);
+    }
+    if (route == CTC_BEAM_DEVICE_WIDE) {         // the rows' candidate lists: 1 KB per row, and their counts
+        c->ctc_cand.ensure(rows * (size_t)kBeamWideCand * 8);
+        c->ctc_cand_n.ensure(rows * 4);
     }
 }
 
@@ -367,9 +398,10 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     const std::vector<int>&tiles = run.tiles, &seqs = run.seqs;
     const int ntiles = (int)(tiles.size() / 4), nseq = (int)(seqs.size() / 2);
     const int C = rec_classes(c), cs = rec_cs(c);
-    const int route = ctc_route(c->beam_width, C, seqs.data(), nseq, rec_fused_ok(c));
+    const int route = ctc_route(c->beam_width, C, seqs.data(), nseq, rec_fused_ok(c), rec_beam_wide(c));
     c->ctc_last_route = route;
-    const bool fused = route == CTC_GREEDY_FUSED, beam = route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE;
+    const bool dev_beam = route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE;       // text and lengths come back, not probabilities
+    const bool fused = route == CTC_GREEDY_FUSED, beam = route == CTC_BEAM_HOST || dev_beam;
     if (!fused) c->seq_logits.ensure(rows_pad * cs * 4);
     c->seq_tables.ensure((tiles.size() + seqs.size()) * 4);
     int* tiles_dev = (int*)c->seq_tables.p;
@@ -379,7 +411,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     // pinned read-back block: greedy classes [rows] | CtcOut [nseq] | device route: beam text [rows] | its lengths [nseq]
     const size_t oo_off = align_up(rows * 4, 16);
     const size_t bi_off = align_up(oo_off + (size_t)nseq * sizeof(CtcOut), 16), bl_off = bi_off + align_up(rows * 4, 16);
-    c->ctc_pin.ensure(route == CTC_BEAM_DEVICE ? bl_off + (size_t)nseq * 4 : bi_off);
+    c->ctc_pin.ensure(dev_beam ? bl_off + (size_t)nseq * 4 : bi_off);
     const int* oidx = (const int*)c->ctc_pin.p;
     const CtcOut* oo = (const CtcOut*)((const char*)c->ctc_pin.p + oo_off);
     const int* bidx = (const int*)((const char*)c->ctc_pin.p + bi_off);
@@ -414,13 +446,17 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
             HIPCHK(launch_ctc((const float*)c->seq_logits.p, rows, C, cs, seqs_dev, nseq, (int*)c->ctc_idx.p, (float*)c->ctc_pmax.p,
                               (int*)c->ctc_out_idx.p, (CtcOut*)c->ctc_out.p, ss, c->ignore_mask, beam ? (float*)c->ctc_probs.p : nullptr));
         }
-        if (route != CTC_BEAM_DEVICE) HIPCHK(hipMemcpyAsync(c->ctc_pin.p, c->ctc_out_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));    // the search's text replaces it
+        if (!dev_beam) HIPCHK(hipMemcpyAsync(c->ctc_pin.p, c->ctc_out_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));    // the search's text replaces it
         HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + oo_off, c->ctc_out.p, (size_t)nseq * sizeof(CtcOut), hipMemcpyDeviceToHost, ss));
-        if (route == CTC_BEAM_DEVICE) {
+        if (dev_beam) {
             int max_T = 0;
             for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
-            HIPCHK(launch_ctc_beam((const float*)c->ctc_probs.p, rows, C, cs, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_beam_idx.p,
-                                   (int*)c->ctc_beam_len.p, ss));
+            if (route == CTC_BEAM_DEVICE_WIDE)
+                HIPCHK(launch_ctc_beam_wide((const float*)c->ctc_probs.p, rows, C, cs, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_cand_n.p,
+                                            (int*)c->ctc_cand.p, (int*)c->ctc_beam_idx.p, (int*)c->ctc_beam_len.p, ss));
+            else
+                HIPCHK(launch_ctc_beam((const float*)c->ctc_probs.p, rows, C, cs, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_beam_idx.p,
+                                       (int*)c->ctc_beam_len.p, ss));
             HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bi_off, c->ctc_beam_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));
             HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bl_off, c->ctc_beam_len.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, ss));
         } else if (route == CTC_BEAM_HOST) {
@@ -435,10 +471,14 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     c->times[5] += ctc_ms;                           // CTC kernels + read-back (device span) ...
     t0 = clk::now();                                 // ... + the host decode below
     if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, C, cs, c->beam_width, beam_texts, &host_pool(c));
+    if (route == CTC_BEAM_DEVICE_WIDE) {   // the probabilities are still resident: only the overflowed sequences' rows cross the link
+        hipStream_t ss = (c->seq_stream && c->feat_ev) ? c->seq_stream : c->stream;
+        c->ctc_host_seqs += ctc_beam_wide_fallback(c, ss, (const float*)c->ctc_probs.p, seqs.data(), nseq, C, cs, c->beam_width, blen, beam_texts);
+    }
     for (int i = 0; i < nseq; ++i) {       // the confidence stays the greedy path's for every route
         const int k = run.seq_k[i];
-        if (route == CTC_BEAM_HOST) confs[k] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), texts[k]);
-        else if (route == CTC_BEAM_DEVICE) confs[k] = ctc_decode(oo[i], bidx + seqs[2 * i], std::clamp(blen[i], 0, seqs[2 * i + 1]), texts[k]);
+        if (route == CTC_BEAM_HOST || (route == CTC_BEAM_DEVICE_WIDE && blen[i] < 0)) confs[k] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), texts[k]);
+        else if (dev_beam) confs[k] = ctc_decode(oo[i], bidx + seqs[2 * i], std::clamp(blen[i], 0, seqs[2 * i + 1]), texts[k]);
         else confs[k] = ctc_decode(oo[i], oidx + seqs[2 * i], oo[i].len, texts[k]);
     }
     c->times[5] += (float)ms_since(t0);
@@ -543,6 +583,7 @@ static void rec_check_params(bbocr_ctx* c, const bbocr_params& p) {
     if (!c->crnn_loaded) fail(BBOCR_ERR_STATE, "recogniser weights not loaded");
     if (p.ignore_mask[0] & 1u) fail(BBOCR_ERR_ARG, "the CTC blank (class 0) cannot be ignored");
     c->ctc_last_route = -1;          // until a sequence pass of this call has been routed (bbocr_last_ctc_route)
+    c->ctc_host_seqs = 0;
     for (int i = 0; i < 4; ++i) c->ignore_mask[i] = p.ignore_mask[i];
     if (rec_wide(c)) {       // the calling thread's bbocr_set_class_mask words, copied into this slot: another call's mask is another slot's
         int n = 0;

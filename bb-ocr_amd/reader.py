@@ -497,7 +497,7 @@ class Reader:
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
                  rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, character=None,
-                 lang_char=None, **_ignored):
+                 lang_char=None, beam_wide=None, **_ignored):
         import torch
 
         net = resolve_recog_network(lang_list, recog_network, model_storage_directory, user_network_directory, character, lang_char)
@@ -536,11 +536,17 @@ class Reader:
         self.device_decode = bool(device_decode)
         self.jpeg_chroma = jpeg_chroma(device_decode)     # "chroma": 4:4:4, 4:2:2 and 4:4:0 files are decoded on the card as well
         self.jpeg_progressive = jpeg_progressive(device_decode)   # "progressive": those, and progressive files (csrc/jpegprog.hip)
-        cfg = _lib.bbocr_config(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
-                                precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads,
-                                rec_quant=int(self.rec_quant), rec_classes=0 if net["character"] == CHARACTER else len(net["character"]))
+        if beam_wide is None:       # decoder='beamsearch' of a model of more than 128 classes searched on the card (csrc/ctc_beam_wide.hip); off unless asked for
+            beam_wide = os.environ.get("BBOCR_BEAM_WIDE", "").strip() == "1"
+        self.beam_wide = bool(beam_wide)
+        kw = dict(device=self.device_index, det_sub_batch=int(det_sub_batch), rec_max_cols=int(rec_max_cols),
+                  precision=_lib.PRECISIONS[precision], call_slots=int(call_slots), host_threads=self.host_threads,
+                  rec_quant=int(self.rec_quant), rec_classes=0 if net["character"] == CHARACTER else len(net["character"]))
         h = C.c_void_p()
-        rc = self._lib.bbocr_create(C.byref(cfg), C.byref(h))
+        if self.beam_wide:          # the appended field travels in bbocr_config_v2; without it bbocr_create's 32 bytes say everything
+            rc = self._lib.bbocr_create_v2(C.byref(_lib.bbocr_config_v2(beam_wide=1, **kw)), C.byref(h))
+        else:
+            rc = self._lib.bbocr_create(C.byref(_lib.bbocr_config(**kw)), C.byref(h))
         if rc != 0:
             raise RuntimeError(f"bbocr_create failed with status {rc}")
         self._h = h
@@ -770,10 +776,18 @@ class Reader:
 
     def last_ctc_route(self):
         """Where the text of this thread's last recognise / readtext call came from (bbocr_last_ctc_route): 0 greedy, 1 beam search on the host,
-        2 beam search on the device, 3 greedy with Prediction inside the CTC kernel (more than 128 classes, 16-bit modes), -1 no pass yet"""
+        2 beam search on the device, 3 greedy with Prediction inside the CTC kernel (more than 128 classes, 16-bit modes), 4 beam search on the
+        device over more than 128 classes (beam_wide), -1 no pass yet"""
         route = C.c_int(-1)
         self._check(self._lib.bbocr_last_ctc_route(self._h, C.byref(route)))
         return int(route.value)
+
+    def last_ctc_host_sequences(self):
+        """Sequences of this thread's last recognise / readtext call that the wide device beam search (route 4) left to the host search
+        because one of their rows had more than 128 candidate classes (bbocr_last_ctc_host_sequences)"""
+        n = C.c_int(0)
+        self._check(self._lib.bbocr_last_ctc_host_sequences(self._h, C.byref(n)))
+        return int(n.value)
 
     def stage_times(self):
         ms = (C.c_float * 8)()
@@ -1342,7 +1356,7 @@ class Reader:
     def ctc_beam_device(self, probs_dev, seqs, beam_width, C=97):
         """The device beam search alone (bbocr_op_ctc_beam): fp32 [rows, cs] device tensor of probabilities, seqs = [(first row, T)], width
         <= _lib.BEAM_DEVICE_MAX -> one list of class indices per sequence (ctcBeamSearch's text, blank and repeats dropped).  C <= 128: the
-        kernel keeps labels as bytes; a wider model's beam search runs on the host."""
+        kernel keeps labels as bytes; a wider model's beam search runs on the host, or through ctc_beam_wide_device's kernels (beam_wide)."""
         import ctypes as ct             # the argument C (classes, as in bbocr.h) hides the module's alias here
 
         if int(C) > 128:
@@ -1360,6 +1374,26 @@ class Reader:
         self._check(self._lib.bbocr_op_ctc_beam(self._h, ct.c_void_p(probs_dev.data_ptr()), probs_dev.shape[0], tab, n, int(C),
                                                 probs_dev.shape[1], int(beam_width), off, idx))
         return [idx[off[i]:off[i + 1]] for i in range(n)]
+
+    def ctc_beam_wide_device(self, probs_dev, seqs, beam_width, C):
+        """The device beam search over more than 128 classes alone (bbocr_op_ctc_beam_wide), on a Reader of such a model: arguments as
+        ctc_beam_device's, 128 < C <= _lib.REC_CLASSES_MAX -> (texts, n_host): one list of class indices per sequence, and the number of
+        sequences that had a row of more than 128 candidate classes and were searched on the host."""
+        import ctypes as ct             # the argument C (classes, as in bbocr.h) hides the module's alias here
+
+        torch = self._torch
+        if (not isinstance(probs_dev, torch.Tensor) or not probs_dev.is_cuda or probs_dev.device.index != self.device_index
+                or probs_dev.dtype != torch.float32 or probs_dev.ndim != 2 or not probs_dev.is_contiguous()):
+            raise ValueError(f"probabilities: expected a contiguous float32 [rows,cs] tensor on {self.device}")
+        flat = [int(v) for s in seqs for v in s]
+        n = len(flat) // 2
+        tab = (ct.c_int * max(len(flat), 1))(*flat)
+        off = (ct.c_int * (n + 1))()
+        idx = (ct.c_int * max(1, sum(max(t, 0) for t in flat[1::2])))()
+        n_host = ct.c_int(-1)
+        self._check(self._lib.bbocr_op_ctc_beam_wide(self._h, ct.c_void_p(probs_dev.data_ptr()), probs_dev.shape[0], tab, n, int(C),
+                                                     probs_dev.shape[1], int(beam_width), off, idx, ct.byref(n_host)))
+        return [idx[off[i]:off[i + 1]] for i in range(n)], n_host.value
 
     def recognize_device(self, gray_dev, horizontal_lists, free_lists, **kw):
         self._dev_u8(gray_dev, "gray", 3)

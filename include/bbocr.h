@@ -86,11 +86,24 @@ typedef struct bbocr_config {
                          * 2 .. BBOCR_REC_CLASSES_MAX; bbocr_load_weights then wants Prediction.weight [rec_classes, 256] and Prediction.bias
                          * [rec_classes] (BBOCR_ERR_WEIGHTS otherwise), the weight blob carries the count (a blob of another count:
                          * BBOCR_ERR_WEIGHTS) and bbocr_result::text_idx holds 1 .. rec_classes - 1.  Up to 128 classes nothing else changes.
-                         * Above 128 the class mask comes from bbocr_set_class_mask, decoder == BEAMSEARCH is searched on the host, and greedy
+                         * Above 128 the class mask comes from bbocr_set_class_mask, decoder == BEAMSEARCH is searched on the host (on the device
+                         * with bbocr_config_v2::beam_wide == 1, below), and greedy
                          * passes of the 16-bit precisions run Prediction + softmax + arg-max as ONE kernel that never stores the logits
                          * (pred_ctc.hip).  rec_quant == 1 with any count but 97, or a count outside the range: bbocr_create
                          * returns BBOCR_ERR_ARG. */
 } bbocr_config;
+/* bbocr_config with the fields added since its layout was fixed, appended behind it: what bbocr_create_v2 takes.  bbocr_config itself keeps
+ * its 32 bytes, so a caller built against an earlier header (or the earlier ctypes structure) that hands bbocr_create a 32-byte block is
+ * still read correctly; bbocr_create means every field below at its default. */
+typedef struct bbocr_config_v2 {
+    bbocr_config base;  /* the fields above, unchanged */
+    int beam_wide;      /* 0 (default): decoder == BEAMSEARCH over more than 128 classes is searched on the host, which reads the probabilities
+                         * back.  1: widths up to BBOCR_BEAM_DEVICE_MAX are searched on the device (ctc_beam_wide.hip: a candidate list per row,
+                         * then one wave per sequence; only text and lengths are read back, the text is the host search's exactly).  A sequence
+                         * with a row of more than 128 candidate classes (p >= 0.5 / rec_classes) alone is searched on the host, from its own
+                         * rows.  On a context of at most 128 classes the field changes nothing.  Any other value: bbocr_create_v2
+                         * returns BBOCR_ERR_ARG. */
+} bbocr_config_v2;
 #define BBOCR_REC_CLASSES_MAX 8192
 enum { BBOCR_PREC_BF16 = 0, BBOCR_PREC_FP16 = 1, BBOCR_PREC_EXACT = 2, BBOCR_PREC_MIXED = 3, BBOCR_PREC_EXACT_REC = 4 };
 
@@ -109,7 +122,10 @@ enum { BBOCR_DECODER_GREEDY = 0, BBOCR_DECODER_BEAMSEARCH = 1 };
 /* Widest beam the device search takes.  The kernel keeps one sequence's whole search in the LDS of one workgroup (64 KB): the step's entry
  * table, beam_width * (1 + C) floats, plus the live labellings as bytes, 2 * beam_width * T (double-buffered), plus under 3 KB of row and
  * beam state.  At width 32 and C = 128 that is 32 * 129 * 4 = 16,512 B of entries and 64 B per time step: T up to 708, above the 639 steps
- * of a crop as wide as the default canvas (2560 / 4 - 1).  Width 64 would halve that to T <= 250. */
+ * of a crop as wide as the default canvas (2560 / 4 - 1).  Width 64 would halve that to T <= 250.
+ * The search over more than 128 classes (bbocr_config_v2::beam_wide) keeps the same table over at most 128 candidates per step and the
+ * labellings as 16-bit symbols, 4 * beam_width * T bytes: at width 32 that is 19,856 B of tables and state and 128 B per time step, T up
+ * to 356; at width 5, T up to 3,076.  A longer sequence sends its pass to the host search. */
 #define BBOCR_BEAM_DEVICE_MAX 32
 
 typedef struct bbocr_params {
@@ -164,6 +180,8 @@ typedef struct bbocr_result {
 } bbocr_result;
 
 int bbocr_create(const bbocr_config* cfg, bbocr_ctx** out);
+/* bbocr_create with bbocr_config_v2's appended field, beam_wide; bbocr_create of cfg is bbocr_create_v2 of {*cfg, 0} */
+int bbocr_create_v2(const bbocr_config_v2* cfg, bbocr_ctx** out);
 void bbocr_destroy(bbocr_ctx* ctx);
 const char* bbocr_last_error(bbocr_ctx* ctx);
 void bbocr_default_params(bbocr_params* p);
@@ -282,9 +300,14 @@ int bbocr_stage_times(bbocr_ctx* ctx, float* ms, int n);
 int bbocr_set_class_mask(bbocr_ctx* ctx, const uint32_t* words, int n_words);
 /* where the text of the LAST sequence pass of the calling thread's last recognise / readtext call on this context came from: 0 greedy
  * (Prediction launch + row kernel + collapse), 1 beam search on the host, 2 beam search on the device, 3 greedy with Prediction inside the CTC
- * kernel (more than 128 classes, 16-bit precisions: no logits stored); -1: no such pass (no call, a call without boxes, or the thread's
+ * kernel (more than 128 classes, 16-bit precisions: no logits stored), 4 beam search on the device over more than 128 classes
+ * (bbocr_config_v2::beam_wide; sequences whose rows overflow the candidate list are searched on the host within the same pass); -1: no such pass (no call, a call without boxes, or the thread's
  * last call was on another context: like bbocr_stage_times this is the record of the calling thread's LAST call) */
 int bbocr_last_ctc_route(bbocr_ctx* ctx, int* route);
+/* the sequences of the calling thread's last recognise / readtext call on this context that route 4 left to the host search (a row of more
+ * than 128 candidate classes), summed over the call's sequence passes; 0 on every other route.  On trained models it stays 0 or near it: a
+ * count that does not says that the candidate list is too short for the model's rows */
+int bbocr_last_ctc_host_sequences(bbocr_ctx* ctx, int* n);
 
 /* Per-launch timing of the dominant kernel (conv_mfma) with HIP events recorded on the context's stream.
  * group 0 = detector convs, 1 = recogniser convs/GEMMs.  on = 1 times group 0 only (54 launches per 64-page step: the roofline
@@ -392,7 +415,7 @@ int bbocr_op_qlstm(bbocr_ctx* ctx, const float* dev_g, int rows, const int* seqs
                    float* dev_hparams);
 /* CTC decode of logits fp32 [n,T,cs]: host outputs text_off [n+1], text_idx (<= n*T), conf [n]; ignore_mask (host): the class mask, 4 words
  * for C <= 128 (bbocr_params::ignore_mask), ceil(C / 32) words for a wider C (the wide rows kernel, one wavefront per row), or NULL;
- * beam_width <= 0: greedy, > 0: ctcBeamSearch with that width (bbocr_params::decoder; C > 128: on the host).  C > 128 is taken on a context
+ * beam_width <= 0: greedy, > 0: ctcBeamSearch with that width (bbocr_params::decoder; C > 128: on the host, or on the device on a context with beam_wide).  C > 128 is taken on a context
  * created with rec_classes > 128 (then up to BBOCR_REC_CLASSES_MAX) and is BBOCR_ERR_ARG on any other, here and in the two entry points below */
 int bbocr_op_ctc(bbocr_ctx* ctx, const float* dev_logits, int n, int T, int C, int cs, int* text_off, int* text_idx, double* conf,
                  const unsigned int* ignore_mask, int beam_width);
@@ -422,6 +445,17 @@ int bbocr_op_pred_ctc(bbocr_ctx* ctx, const uint16_t* dev_x, size_t rows, const 
  * (see BBOCR_BEAM_DEVICE_MAX) */
 int bbocr_op_ctc_beam(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width,
                       int* text_off, int* text_idx);
+/* the device beam search over more than 128 classes alone (the kernels behind decoder == BEAMSEARCH on a context with beam_wide): arguments
+ * and outputs as bbocr_op_ctc_beam's, for 128 < C <= BBOCR_REC_CLASSES_MAX on a context created with rec_classes > 128 (beam_wide need not be
+ * set).  *n_host (may be NULL): the sequences that had a row of more than 128 candidates and were searched on the host.  The text equals
+ * bbocr_host_ctc_beam's on the same rows, exactly.  BBOCR_ERR_ARG before anything is queued, with nothing written: a null pointer, cs < C, C
+ * outside that range or a narrower context, beam_width < 1 or > BBOCR_BEAM_DEVICE_MAX, a sequence outside [0, rows), a T too long for the
+ * kernel's LDS block at this width (see BBOCR_BEAM_DEVICE_MAX) */
+int bbocr_op_ctc_beam_wide(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width,
+                           int* text_off, int* text_idx, int* n_host);
+/* ctc_route, the rule by which a sequence pass picks its CTC route (the values of bbocr_last_ctc_route), on the host alone: beam_wide as in
+ * bbocr_config, beam_width <= 0 for greedy, C classes, seqs = {first row, T} per sequence.  No context, no device. */
+int bbocr_host_ctc_route(int beam_wide, int beam_width, int C, const int* seqs, int nseq);
 /* cv2.resize(INTER_LINEAR) on uint8 [N,sh,sw,C] -> [N,dh,dw,C] (device) */
 int bbocr_op_resize_u8(bbocr_ctx* ctx, const uint8_t* dev_src, int N, int sh, int sw, int C, uint8_t* dev_dst, int dh, int dw);
 /* JPEG pages decoded ONCE on the host into libjpeg's YCbCr triples (out_color_space = JCS_YCbCr; PIL: draft("YCbCr")): uint8 [npix,3]
