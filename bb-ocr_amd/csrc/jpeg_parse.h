@@ -63,8 +63,9 @@ inline int chroma_class_of(const int s[3][2]) {
     return h == 1 && v == 1 ? BBOCR_JPEG_CHROMA_444 : (h == 2 && v == 1 ? BBOCR_JPEG_CHROMA_422 : (h == 1 && v == 2 ? BBOCR_JPEG_CHROMA_440 : 0));
 }
 
-// jdhuff.c::jpeg_make_d_derived_tbl; false: the counts do not describe a prefix code
-inline bool derive_table(const HuffSpec& h, JpegHuff& t) {
+// jdhuff.c::jpeg_make_d_derived_tbl; false where it raises JERR_BAD_HUFF_TABLE: behind the codes of a length the next code no longer has
+// that length (the counts do not describe a prefix code, or they assign the code of all ones), or a DC table (dc) names a category above 15
+inline bool derive_table(const HuffSpec& h, JpegHuff& t, bool dc = false) {
     std::memset(&t, 0, sizeof t);
     int code = 0, k = 0;
     for (int l = 1; l <= 16; ++l) {
@@ -79,8 +80,12 @@ inline bool derive_table(const HuffSpec& h, JpegHuff& t) {
         } else {
             t.maxcode[l] = -1;
         }
+        if (code >= (1 << l)) return false;
         code <<= 1;
     }
+    if (dc)
+        for (int i = 0; i < h.total; ++i)
+            if (h.vals[i] > 15) return false;
     t.maxcode[0] = t.maxcode[17] = -1;
     std::memcpy(t.val, h.vals, 256);
     return true;
@@ -121,11 +126,16 @@ inline size_t unstuff(const uint8_t* a, const uint8_t* e, uint8_t* dst) {
 }
 
 // The entropy-coded data that starts at `from`: its restart segments' byte ranges (want_segs) and their number, up to the marker that
-// ends it, whose FF is *end.  BBOCR_JPEG_OK, _RESTART (markers out of sequence) or _NO_EOI (the data runs to the end of the file).
+// ends it, whose FF is *end.  Fill bytes in front of a marker (T.81 B.1.1.2) are no entropy-coded data: a segment ends at the first FF of
+// the run its marker closes.  BBOCR_JPEG_OK, _RESTART (markers out of sequence) or _NO_EOI (the data runs to the end of the file).
 inline int scan_segments(const uint8_t* f, size_t n, size_t from, bool want_segs, std::vector<std::pair<size_t, size_t>>& segs, int& nseg,
                          size_t& end) {
     size_t q = from, start = from;
     nseg = 0;
+    auto first_ff = [&](size_t at) {
+        while (at > start && f[at - 1] == 0xFF) --at;
+        return at;
+    };
     while (q < n) {
         const void* hit = std::memchr(f + q, 0xFF, n - q);
         if (!hit) break;
@@ -138,12 +148,12 @@ inline int scan_segments(const uint8_t* f, size_t n, size_t from, bool want_segs
             q += 1;
         } else if (b >= 0xD0 && b <= 0xD7) {
             if (b - 0xD0 != nseg % 8) return BBOCR_JPEG_RESTART;
-            if (want_segs) segs.emplace_back(start, q);
+            if (want_segs) segs.emplace_back(start, first_ff(q));
             ++nseg;
             q += 2;
             start = q;
         } else {
-            if (want_segs) segs.emplace_back(start, q);
+            if (want_segs) segs.emplace_back(start, first_ff(q));
             ++nseg;
             end = q;
             return BBOCR_JPEG_OK;
@@ -283,6 +293,8 @@ inline int jpeg_walk(const uint8_t* f, size_t n, JpegParsed& out, bool want_segs
         if (g.s[1 + 2 * i] != h.comp_id[i]) return BBOCR_JPEG_MULTISCAN;
         const int td = g.s[2 + 2 * i] >> 4, ta = g.s[2 + 2 * i] & 15;
         if (td > 1 || ta > 1 || !h.huff[0][td].have || !h.huff[1][ta].have || !take_quant(h, i, out.quant)) return BBOCR_JPEG_TABLES;
+        JpegHuff probe;                                              // what libjpeg refuses when it derives the scan's tables
+        if (!derive_table(h.huff[0][td], probe, true) || !derive_table(h.huff[1][ta], probe)) return BBOCR_JPEG_TABLES;
         out.tab_dc[i] = td;
         out.tab_ac[i] = 2 + ta;
     }
@@ -412,7 +424,7 @@ inline int prog_walk(const uint8_t* f, size_t n, ProgParsed& out, bool want_segs
             if (!(sc.ss == 0 && sc.ah > 0)) {                                          // a DC refinement reads raw bits
                 const int id = sc.ss == 0 ? sc.dc_table[i] : sc.ac_table[i];
                 JpegHuff probe;
-                if (id > 3 || !h.huff[sc.ss == 0 ? 0 : 1][id].have || !derive_table(h.huff[sc.ss == 0 ? 0 : 1][id], probe)) return BBOCR_JPEG_TABLES;
+                if (id > 3 || !h.huff[sc.ss == 0 ? 0 : 1][id].have || !derive_table(h.huff[sc.ss == 0 ? 0 : 1][id], probe, sc.ss == 0)) return BBOCR_JPEG_TABLES;
                 ps.tab[i] = h.huff[sc.ss == 0 ? 0 : 1][id];
             }
         }

@@ -386,10 +386,10 @@ void jpeg_decode_outputs(bbocr_ctx* ctx, hipStream_t st, const uint8_t* const* f
 // The stage entry points' body: ONE file decoded at `scale` with S-bit subsequences, then stage 2 = the component planes in
 // jpeg_geometry's sizes, Y, Cb, Cr one after the other, or stage 3 = the pixels, tight, copied to dev_dst.  cls: the files it takes -- -1
 // every file the decoder takes, 0 the 4:2:0 and grey ones only, 1 those of a chroma class only.  Returns the file's descriptor (the
-// entropy stages' intermediates).
+// entropy stages' intermediates); bits: receives the decoder's JD_ERR_* bits for the file.
 JpegDesc jpeg_stage_run(bbocr_ctx* ctx, hipStream_t s, int stage, const uint8_t* file, size_t bytes, int S, int scale, int cls, void* dev_dst,
-                        size_t dst_bytes, int* file_status, bool progressive = false, int scan_limit = 0) {
-    if (!file || !dev_dst || stage < 0 || stage > 3 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
+                        size_t dst_bytes, int* file_status, bool progressive = false, int scan_limit = 0, int* bits = nullptr) {
+    if (!file || !dev_dst || stage < 0 || stage > 4 || bytes >= ((size_t)1 << 28)) fail(BBOCR_ERR_ARG, "bad stage arguments");
     int status = 0;
     std::vector<FileJob> jobs = jpeg_admit(&file, &bytes, 1, &status, [&](FileJob& j) {
         const bbocr_jpeg_plan& pl = j.ps.plan;
@@ -409,6 +409,7 @@ JpegDesc jpeg_stage_run(bbocr_ctx* ctx, hipStream_t s, int stage, const uint8_t*
     jpeg_run(ctx, s, jobs, S, {{scale, 3}}, ds, &descs, scan_limit);
     jpeg_report(jobs, ds, &status);
     if (file_status) *file_status = status;
+    if (bits) *bits = ds[0];
     const JpegDesc& d = descs[0];
     size_t off = 0;
     for (int c = 0; stage == 2 && c < d.ncomp; ++c) {
@@ -507,8 +508,12 @@ int bbocr_op_jpeg_progressive_stage(bbocr_ctx* ctx, int stage, const uint8_t* fi
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t s) {
-        const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, stage_subseq_bits(subseq_bits), 1, -1, dev_dst, dst_bytes, file_status);
-        if (stage == 0) {
+        int bits = 0;
+        const JpegDesc d = jpeg_stage_run(ctx, s, stage, file, bytes, stage_subseq_bits(subseq_bits), 1, -1, dev_dst, dst_bytes, file_status, false, 0, &bits);
+        if (stage == 4) {
+            if (dst_bytes < 4) fail(BBOCR_ERR_ARG, "destination too small");
+            HIPCHK(hipMemcpyAsync(dev_dst, &bits, 4, hipMemcpyHostToDevice, s));
+        } else if (stage == 0) {
             const size_t ns = (size_t)d.nsub;
             if (dst_bytes < ns * 16) fail(BBOCR_ERR_ARG, "destination too small");
             std::vector<unsigned long long> entry(ns);

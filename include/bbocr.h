@@ -650,7 +650,9 @@ int bbocr_jpeg_imread(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
  * MCU, zig-zag position, first output block); 1 = quantised coefficients int16 [blocks][64] in natural order, blocks in MCU order, DC
  * terms summed; 2 = the component planes before upsampling, Y [mcu_rows * 16][mcu_cols * 16] then Cb, Cr at half that (1 component:
  * [mcu_rows * 8][mcu_cols * 8]; a file of a chroma class: Y [mcu_rows * 8 v][mcu_cols * 8 h], then Cb and Cr, each
- * [mcu_rows * 8][mcu_cols * 8]); 3 = the pixels, tight.  *file_status as status[k] above. */
+ * [mcu_rows * 8][mcu_cols * 8]); 3 = the pixels, tight; 4 = the status word the write pass raised for the file, int32 [1]: 0, or the sum
+ * of 1 (a subsequence entered in another state than its left neighbour left), 2 (a bit pattern without a code) and 4 (another block count
+ * than the headers promise, or a restart segment that ends inside a block).  *file_status as status[k] above. */
 int bbocr_op_jpeg_stage(bbocr_ctx* ctx, int stage, const uint8_t* file, size_t bytes, int subseq_bits, void* dev_dst, size_t dst_bytes,
                         int* file_status);
 /* ---- the decode at reduced scale: what Pillow's draft (decoderconfig == (scale, 0)) and hence Image.thumbnail of an unloaded JPEG file get

@@ -2,12 +2,13 @@
 
 Three parts, each the yardstick of one layer of csrc/jpegdec.*:
   * ``parse``      the marker parser: what ``bbocr_host_jpeg_plan`` must report (geometry, sampling, restart interval, scan range,
-                   ``supported`` + reason);
+                   ``supported`` + reason); a Huffman table the scan names and libjpeg refuses (``table_ok``) is TABLES, and fill bytes
+                   in front of RSTn or the closing marker belong to no restart segment;
   * ``decode_coefficients``  the sequential Huffman decoder: quantised coefficients per block in natural order (DC terms absolute), and
                    the exact state at the first symbol boundary at or after every ``S``-bit subsequence start;
   * ``device_model``  the passes of the device decoder on the same bits: speculative decode of every subsequence from the assumed state,
                    synchronisation to a fixed point (inside groups of ``group`` lanes, then across them), exclusive scan of the block
-                   counts, write pass.
+                   counts, write pass -- and the status word the write pass raises (``ERR_*``).
 ``decode_pixels`` completes the coefficients to samples with tests/jpeg_ref.py (ISLOW IDCT, range limit, fancy upsampling).
 """
 from __future__ import annotations
@@ -127,6 +128,8 @@ def _parse(data: bytes) -> dict:
                 td, ta = t >> 4, t & 15
                 if (0, td) not in huff or (1, ta) not in huff or sof["comps"][i][3] not in qt:
                     raise Refused(TABLES)
+                if not table_ok(*huff[(0, td)], dc=True) or not table_ok(*huff[(1, ta)]):
+                    raise Refused(TABLES)                      # jdhuff.c::jpeg_make_d_derived_tbl: JERR_BAD_HUFF_TABLE
                 tabs.append((td, ta))
             scan_off = p + L
             break
@@ -139,6 +142,13 @@ def _parse(data: bytes) -> dict:
     segs = []
     q = start = scan_off
     end = None
+
+    def first_ff(q):
+        """a marker's FF at q: the first FF of the run of fill bytes (T.81 B.1.1.2) it closes; the segment ends there"""
+        while q > start and data[q - 1] == 0xFF:
+            q -= 1
+        return q
+
     while q < n:
         q = data.find(b"\xff", q)
         if q < 0 or q + 1 >= n:
@@ -151,11 +161,11 @@ def _parse(data: bytes) -> dict:
         elif 0xD0 <= b <= 0xD7:
             if b - 0xD0 != len(segs) % 8:
                 raise Refused(RESTART)
-            segs.append((start, q))
+            segs.append((start, first_ff(q)))
             q += 2
             start = q
         else:
-            segs.append((start, q))
+            segs.append((start, first_ff(q)))
             end = q
             break
     if end is None:
@@ -168,6 +178,18 @@ def _parse(data: bytes) -> dict:
     return dict(width=sof["width"], height=sof["height"], components=nc, sampling=[(c[1], c[2]) for c in sof["comps"]],
                 restart_interval=dri, mcu_cols=mcux, mcu_rows=mcuy, segments=segs, scan_offset=scan_off, scan_bytes=end - scan_off,
                 quant=[qt[c[3]] for c in sof["comps"]], huff=huff, tables=tabs, supported=True, reason=OK)
+
+
+def table_ok(counts, vals, dc=False):
+    """jdhuff.c::jpeg_make_d_derived_tbl's two checks: behind the codes of every length the next code still has that length (no code
+    is all ones, none lies beyond), and a DC table names no category above 15"""
+    code = 0
+    for l in range(1, 17):
+        code += counts[l - 1]
+        if code >= (1 << l):
+            return False
+        code <<= 1
+    return not dc or all(v <= 15 for v in vals)
 
 
 def parse(data: bytes) -> dict:
@@ -317,9 +339,14 @@ def _dc_sums(coef, st: Stream):
             coef[m, 0] = np.cumsum(coef[m, 0])
 
 
-def device_model(data: bytes, plan: dict, S: int = 1024, group: int = 64):
-    """The device's passes.  -> (coef, entry states) as ``decode_coefficients`` returns them, and the number of cross-group passes."""
-    st = Stream(data, plan)
+ERR_SYNC, ERR_CODE, ERR_COUNT = 1, 2, 4                          # kernels.h JD_ERR_*: the bits of the write pass's status word
+
+
+def device_model(data: bytes, plan: dict, S: int = 1024, group: int = 64, status: bool = False, stream: Stream = None):
+    """The device's passes.  -> (coef, entry states) as ``decode_coefficients`` returns them, and the number of cross-group passes;
+    ``status``: and the status word of the write pass, by jpeg_spec.h::jpeg_write_pass's three rules on the model's own counts and
+    states.  ``stream``: the file's Stream when it is not this module's (another MCU layout)."""
+    st = stream or Stream(data, plan)
     subs = subsequences(st, S)
     n = len(subs)
     first = [i == 0 or subs[i - 1][0] != subs[i][0] for i in range(n)]
@@ -332,12 +359,13 @@ def device_model(data: bytes, plan: dict, S: int = 1024, group: int = 64):
     def relax(lo, hi, bound):
         """lanes lo..hi-1 take their left neighbour's exit state until nothing changes (at most ``bound`` rounds)"""
         any_change = False
+        base = max(lo, 1) - 1
         for _ in range(bound):
-            prev = list(exits)
+            prev = exits[base:hi]                                  # the round reads the exit states of the round before
             changed = False
-            for i in range(max(lo, 1), hi):
-                if not first[i] and prev[i - 1] != entry[i]:
-                    entry[i] = prev[i - 1]
+            for i in range(base + 1, hi):
+                if not first[i] and prev[i - 1 - base] != entry[i]:
+                    entry[i] = prev[i - 1 - base]
                     exits[i], counts[i], _ok = _run(st, subs[i][0], entry[i], subs[i][2], big)
                     changed = True
             if not changed:
@@ -369,14 +397,26 @@ def device_model(data: bytes, plan: dict, S: int = 1024, group: int = 64):
             run = subs[i][0] * st.ri * st.bpm
         first_block.append(run)
         run += counts[i]
-    # 4. write pass
-    coef = np.zeros((st.nmcu * st.bpm, 64), np.int32)
+    # 4. write pass, and what it checks: the neighbour's exit state is the entry state (SYNC), every look-ahead has a code (CODE), the
+    # blocks written are the blocks counted, and a segment's last subsequence ends on the segment's last block, at a block's start (COUNT)
+    nblocks = st.nmcu * st.bpm
+    coef = np.zeros((nblocks, 64), np.int32)
+    word = 0
     for i, (s, _, end) in enumerate(subs):
         seg_end = s * st.ri * st.bpm + st.seg_blocks(s)
-        _run(st, s, entry[i], end, max(seg_end - first_block[i], 0), coef, first_block[i])
+        room = max(seg_end - first_block[i], 0)
+        state, wrote, ok = _run(st, s, entry[i], end, room, coef, first_block[i])
+        if not first[i] and exits[i - 1] != entry[i]:
+            word |= ERR_SYNC
+        if not ok:
+            word |= ERR_CODE
+        if wrote != counts[i]:
+            word |= ERR_COUNT
+        if (i + 1 == n or first[i + 1]) and (first_block[i] + wrote != seg_end or state[1:] != (0, 0)):
+            word |= ERR_COUNT
     _dc_sums(coef, st)
     states = np.array([(st.seg_byte[subs[i][0]] * 8 + entry[i][0], entry[i][1], entry[i][2], first_block[i]) for i in range(n)], np.int64)
-    return coef, states, passes
+    return (coef, states, passes, word) if status else (coef, states, passes)
 
 
 # ------------------------------------------------------------------------------------------------ coefficients -> samples

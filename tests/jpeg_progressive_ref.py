@@ -41,8 +41,15 @@ def scan_units(plan, scan):
 
 
 def _segments(data, start):
-    """([(first, end)] of the restart segments of the entropy-coded data at ``start``, offset of the marker that ends it) or a reason"""
+    """([(first, end)] of the restart segments of the entropy-coded data at ``start``, offset of the marker that ends it) or a reason;
+    a segment ends at the first FF of the run of fill bytes its marker closes"""
     q, a, n, segs = start, start, len(data), []
+
+    def first_ff(q):
+        while q > a and data[q - 1] == 0xFF:
+            q -= 1
+        return q
+
     while q < n:
         q = data.find(b"\xFF", q)
         if q < 0 or q + 1 >= n:
@@ -55,24 +62,13 @@ def _segments(data, start):
         elif 0xD0 <= b <= 0xD7:
             if b - 0xD0 != len(segs) % 8:
                 return RESTART
-            segs.append((a, q))
+            segs.append((a, first_ff(q)))
             q += 2
             a = q
         else:
-            segs.append((a, q))
+            segs.append((a, first_ff(q)))
             return segs, q
     return NO_EOI
-
-
-def _prefix_code(counts):
-    """jdhuff.c's check of a table's counts: the codes of every length fit that length"""
-    code = 0
-    for l in range(1, 17):
-        code += counts[l - 1]
-        if code > (1 << l):
-            return False
-        code <<= 1
-    return True
 
 
 def _walk(data, plan):
@@ -206,7 +202,7 @@ def _walk(data, plan):
                     bits[c][k] = al
                 if not (ss == 0 and ah > 0):
                     key = (0, dct[i]) if ss == 0 else (1, act[i])
-                    if key[1] > 3 or key not in huff or not _prefix_code(huff[key][0]):
+                    if key[1] > 3 or key not in huff or not J.table_ok(*huff[key], dc=ss == 0):
                         return TABLES
                     tabs.append(huff[key])
             scan = dict(comps=comps, dc_table=dct, ac_table=act, ss=ss, se=se, ah=ah, al=al, restart_interval=dri, offset=p + L, huff=tabs)

@@ -8,8 +8,9 @@ import pytest
 import torch
 
 import jpeg_chroma_ref as K
+import jpeg_entropy_ref as J
 import orient_ref as R
-from test_gpu_jpeg_decode import stage
+from test_gpu_jpeg_decode import stage, status_word
 from test_gpu_orient import host_imread
 from test_jpeg_chroma_cpu import matrix, stage_input
 from test_jpeg_decode_cpu import picture, pillow_pixels, save
@@ -155,6 +156,8 @@ def test_damaged_entropy_data_is_a_status_code(reader):
     assert jpeg_plan(bad).chroma == K.C422 and jpeg_plan(bad).scan_bytes == plan.scan_bytes
     t, status = reader.decode_jpeg_batch([JpegPage(d, jpeg_plan(d)) for d in (files[0], bad, files[2])])
     assert status[0] == 0 and status[2] == 0 and status[1] < 0
+    word = J.device_model(bad, K.parse(bad), status=True, stream=K.Stream(bad, K.parse(bad)))[3]      # exactly the model's bits
+    assert word != 0 and status_word(reader, bad) == word
     t = t.cpu().numpy()
     assert np.array_equal(t[0], pillow_pixels(files[0])) and np.array_equal(t[2], pillow_pixels(files[2]))
     assert reader.decode_jpeg_device([bad], chroma=True) == [None]

@@ -45,6 +45,17 @@ def stage(reader, stg, data, S, shape, dtype):
     return dst.cpu().numpy()
 
 
+def status_word(reader, data, S=0):
+    """stage 4 of bbocr_op_jpeg_stage: the JD_ERR_* bits the write pass raised for the file (jpeg_entropy_ref.ERR_*)"""
+    dst = torch.full((1,), -1, dtype=torch.int32, device=reader.device)
+    st = C.c_int(1)
+    buf = (C.c_ubyte * len(data)).from_buffer_copy(data)
+    reader._check(reader._lib.bbocr_op_jpeg_stage(reader._h, 4, buf, len(data), S, C.c_void_p(dst.data_ptr()), 4, C.byref(st)))
+    word = int(dst.cpu()[0])
+    assert (st.value == 0) == (word == 0) and 0 <= word < 8
+    return word
+
+
 def test_matrix_in_one_call_per_shape_equals_pillow(reader):
     files = matrix()
     assert len(files) == 120
@@ -220,6 +231,8 @@ def test_damaged_entropy_data_is_a_status_code(reader):
     pages = [JpegPage(d, jpeg_plan(d)) for d in (files[0], bad, files[2])]
     t, status = reader.decode_jpeg_batch(pages)
     assert status[0] == 0 and status[2] == 0 and status[1] < 0
+    word = J.device_model(bad, J.parse(bad), status=True)[3]       # exactly the bits the model of the passes names
+    assert word != 0 and status_word(reader, bad) == word
     t = t.cpu().numpy()
     assert np.array_equal(t[0], pillow_pixels(files[0])) and np.array_equal(t[2], pillow_pixels(files[2]))
     assert reader.decode_jpeg_device([bad]) == [None]

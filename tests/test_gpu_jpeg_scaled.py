@@ -8,6 +8,7 @@ import torch
 
 import jpeg_entropy_ref as J
 import jpeg_scaled_ref as S
+from test_gpu_jpeg_decode import status_word
 from test_jpeg_decode_cpu import PHOTOS, matrix, picture, pillow_pixels, save
 from test_jpeg_scaled_cpu import SCALES, pillow_draft, small_matrix
 
@@ -134,6 +135,8 @@ def test_damaged_entropy_data_is_a_status_code(reader):
     bad[a:a + 64] = bytes((37 * k + 11) % 251 for k in range(64))     # no FF: the markers and the plan stay as they were
     got, status = decode_scaled(reader, [files[0], bytes(bad), files[2]], 2)
     assert status[0] == 0 and status[2] == 0 and status[1] < 0 and status[1] != ERR_ARG
+    word = J.device_model(bytes(bad), J.parse(bytes(bad)), status=True)[3]      # the entropy stages are the full-scale decode's: the model's bits
+    assert word != 0 and status_word(reader, bytes(bad)) == word
     assert np.array_equal(got[0], pillow_draft(files[0], 2)) and np.array_equal(got[2], pillow_draft(files[2], 2))
     again, status = decode_scaled(reader, [files[1]], 2)
     assert status == [0] and np.array_equal(again[0], pillow_draft(files[1], 2))
