@@ -86,6 +86,17 @@ class bbocr_jpeg_scaled_comp(C.Structure):
                 ("upsample", C.c_int)]
 
 
+class bbocr_png_plan(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("color_type", C.c_int), ("channels", C.c_int), ("bpp", C.c_int),
+                ("row_bytes", C.c_longlong), ("palette_entries", C.c_int), ("idat_chunks", C.c_int), ("idat_bytes", C.c_longlong),
+                ("supported", C.c_int), ("reason", C.c_int), ("reserved", C.c_int * 2)]
+
+
+# bbocr.h BBOCR_PNG_*: why bbocr_host_png_plan refuses a file
+(PNG_OK, PNG_NOT_PNG, PNG_TRUNCATED, PNG_CRC, PNG_DIMENSIONS, PNG_DEPTH, PNG_INTERLACE, PNG_PALETTE, PNG_IDAT_ORDER, PNG_APNG, PNG_ZLIB,
+ PNG_HEADER) = range(12)
+
+
 CONV_ROUTE_IDS = ("NONE", "GEN64_P4", "GEN64_P8", "GEN64_P16", "GEN128_P4", "GEN128_P8", "GEN128_P16", "DMA64_FUSE1", "DMA64_POSTW", "RESW_POOL64",
                   "RESW_1CH", "RESW_2CH", "DMA64_324_NF2", "DMA64_324", "DMA64_384", "DMA64_448", "DMA128_384", "DMA128_448", "DMA2X2_64",
                   "DMA2X2_128", "DMA1X1_64", "DMA1X1_128", "DMA1X1_256", "DMA1X1_ADDUP")       # include/bbocr.h BBOCR_ROUTE_*, in order
@@ -247,6 +258,10 @@ PROTOTYPES = {
     "bbocr_op_deflate": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bbocr_op_png_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_size_t, _vp, C.c_size_t,
                                      C.POINTER(C.c_size_t)]),
+    "bbocr_host_png_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_png_plan)]),
+    "bbocr_png_decode": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "bbocr_op_png_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -34,6 +34,14 @@ def _jpg_page(source, device_decode=True):
     return None if page is None else ("jpg", page, None)
 
 
+def _png_page(source):
+    """``("png", PngPage, None)`` when the device PNG decoder takes the file (a path or its bytes), else None"""
+    from .reader import png_page
+
+    page = png_page(source)
+    return None if page is None else ("png", page, None)
+
+
 def _host_page(source, decode_once=True):
     """The host decode of a file (a path or its bytes) as a page: ``("ycc", triples, None)`` when it is a YCbCr-coded JPEG and
     ``decode_once`` (decoded once, RGB + Y plane derived on the card: reader.decode_file_ycc), else ``("rgb", rgb, gray)``."""
@@ -60,7 +68,7 @@ def _thumbnail_jpeg(size, image_index, load_rgb):
     return buf.getvalue()
 
 
-def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False):
+def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False, png_decode=False):
     """``ocr_input_image`` for the batching loop: ``("ycc", triples, None)`` when the file easyocr would be given is a YCbCr-coded JPEG
     (``_host_page``) -- every thumbnail is, it is written as one -- else ``("rgb", rgb, gray)``.  ``device_decode``: the file easyocr
     would be given travels as its bytes (``("jpg", JpegPage, None)``) when the device decoder takes it -- the original at or below the
@@ -74,6 +82,8 @@ def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=Fal
     except Exception:
         pass                                                      # :511-514: any failure falls back to the original file
     page = _jpg_page(source, device_decode) if device_decode else None
+    if page is None and png_decode and source is image_path:       # the original file, at or below the limit (a thumbnail is a JPEG)
+        page = _png_page(source)
     return page if page is not None else _host_page(source, decode_once)
 
 
@@ -180,7 +190,7 @@ def ocr_input_image(image_path, image_index=None):
 
 def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
                   edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, device_decode=False, mixed=None,
-                  **readtext_kw):
+                  png_decode=None, **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
     batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
@@ -193,8 +203,12 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     damaged, takes the host decode as before.  With the crop settings the page is read like ``cv2.imread``, EXIF orientation included, and
     ``device_decode=True`` does that on the card as well (``preprocess.imread_bgr_device``: csrc/jpegdec.hip + csrc/orient.hip).
     ``device_decode="chroma"``: the same, and 4:4:4, 4:2:2 and 4:4:0 files -- which ``True`` leaves to the host -- are decoded there too.
-    ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches."""
+    ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches.
+    ``png_decode`` (None: the Reader's ``png_decode``): a PNG file at or below its page's limit that the device PNG decoder takes reaches
+    the card as its bytes (kind ``"png"``); with the crop settings or ``device_thumbnail`` on, and above the limit, a PNG keeps today's path."""
     from .preprocess import ocr_input_device
+
+    png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
 
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
         if crop_margin < 0:
@@ -209,7 +223,7 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     elif device_thumbnail:
         decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once, device_decode)
     else:
-        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode)
+        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode, png_decode)
     res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, mixed=mixed, **readtext_kw)
     return {i: " ".join(t[1] for t in r) for i, r in res.items()}
 
@@ -219,9 +233,9 @@ def _plain_input(path, i=None):
     return _host_page(path)
 
 
-def _plain_input_device(path, i=None, device_decode=True):
-    """``_plain_input`` with the device decoder: the file's bytes when it takes them"""
-    return _jpg_page(path, device_decode) or _plain_input(path, i)
+def _plain_input_device(path, i=None, device_decode=True, png_decode=False):
+    """``_plain_input`` with the device decoders: the file's bytes when one of them takes them (``png_decode``: PNG files too)"""
+    return (_jpg_page(path, device_decode) if device_decode else None) or (_png_page(path) if png_decode else None) or _plain_input(path, i)
 
 
 @dataclasses.dataclass
@@ -264,6 +278,18 @@ def _jpg_read_page(reader, b, k, kw):
     return KINDS[kind].read_page(reader, KINDS[kind].stack(b.ids[k:k + 1], [(a, g)]), 0, kw)
 
 
+def _png_to_device(reader, b):
+    # ONE decode call for the group, on the context's decode stream outside the call slots, like a "jpg" group's
+    dev, b.status = reader.decode_png_batch(b.host)
+    return dev
+
+
+def _png_read(reader, b, kw):
+    good = [k for k, s in enumerate(b.status) if s == 0]
+    rgb, gray = b.dev if len(good) == len(b.ids) else (b.dev[0][good], b.dev[1][good])
+    return reader.readtext_device(rgb, gray, **kw)
+
+
 # The page kinds.  A decoded page is the pair (a, b) of the decode callback's ``(kind, a, b)``; its grouping key is ``_page_key``.  Per kind:
 #   stack(ids, pages) -> Batch           the assembler's step for a group
 #   to_device(reader, batch) -> dev      the upload stage's step: the device payload (it may raise: the batch then travels without one)
@@ -290,6 +316,9 @@ KINDS = {
     # file bytes (JpegPage): decoded by the upload stage; a page it could not decode takes the host decode
     "jpg": Kind(stack=lambda ids, pages: Batch("jpg", ids, host=[p for p, _ in pages]), to_device=_jpg_to_device, read=_jpg_read,
                 read_host=None, read_page=_jpg_read_page),
+    # file bytes (PngPage): both planes decoded by the upload stage; a page it could not decode takes the host decode of its bytes
+    "png": Kind(stack=lambda ids, pages: Batch("png", ids, host=[p for p, _ in pages]), to_device=_png_to_device, read=_png_read,
+                read_host=None, read_page=_jpg_read_page),
 }
 
 
@@ -300,7 +329,7 @@ def _mixed_stack(ids, pages):
 
 def _mixed_to_device(reader, b):
     """Every page of a mixed batch as ``(rgb_dev [H,W,3], gray_dev [H,W] or None)``, by its own kind's upload step -- kept as a list, not
-    stacked.  ``"jpg"`` pages of one decoded shape share one decode call.  ``status``: non-zero where a page did not reach the card.
+    stacked.  ``"jpg"`` pages of one decoded shape share one decode call, and so do ``"png"`` pages.  ``status``: non-zero where a page did not reach the card.
     A failure is kept per page, as the reference's failure rule is per page: such a page is read on its own from its host copy
     (``_read_batch``) while the others still share the call.  The price: an upload failure that hits EVERY page (the card out of memory)
     turns the batch into single-page host reads without an error -- slower, same results -- exactly as a failed ``_upload`` does for a
@@ -309,11 +338,11 @@ def _mixed_to_device(reader, b):
 
     n = len(b.ids)
     dev, b.status = [None] * n, [-1] * n
-    jpg = {}
+    jpg, png = {}, {}
     for k, (kind, a, g) in enumerate(b.host):
         try:
-            if kind == "jpg":
-                jpg.setdefault(a.shape, []).append(k)
+            if kind in ("jpg", "png"):
+                (jpg if kind == "jpg" else png).setdefault(a.shape, []).append(k)
                 continue
             if kind == "dev":                                  # already on the card: the (possibly strided) views are read in place
                 dev[k], b.status[k] = (a, g), 0
@@ -328,6 +357,14 @@ def _mixed_to_device(reader, b):
         try:
             t, status = reader.decode_jpeg_batch([b.host[k][1] for k in ks], padded=True)
             rgb, gray = Reader.pages_from_jpeg(reader, t)
+            for j, k in enumerate(ks):
+                if status[j] == 0:
+                    dev[k], b.status[k] = (rgb[j], gray[j]), 0
+        except Exception:
+            pass
+    for ks in png.values():
+        try:
+            (rgb, gray), status = reader.decode_png_batch([b.host[k][1] for k in ks])
             for j, k in enumerate(ks):
                 if status[j] == 0:
                     dev[k], b.status[k] = (rgb[j], gray[j]), 0
@@ -497,7 +534,7 @@ def _device_stage(reader, batches, texts, kw):
 
 
 def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, mixed=None,
-               **readtext_kw):
+               png_decode=None, **readtext_kw):
     """``{index: readtext result}`` for the files ``image_paths[i]``, i in ``indices`` (default: all): the result lists
     ``Reader.readtext(path)`` returns page by page, from 64-page device batches.  A page whose decode or OCR fails maps to ``[]``.
 
@@ -513,14 +550,18 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     (``_device_stage``: upload, two device calls in flight, result strings); what they hand on is a ``Batch`` of one of the ``KINDS``.
     ``mixed`` (None: the environment variable ``BBOCR_MIXED_BATCH``, off unless ``1``): batches are closed by page count
     (``max_batch``, at most ``BBOCR_MAX_DEVICE_BATCH``) and a pixel budget instead of by shape, pages of all four kinds travel together, and each
-    batch is read by one ``Reader.readtext_pages`` call; same results, same failure rule."""
+    batch is read by one ``Reader.readtext_pages`` call; same results, same failure rule.
+    ``png_decode`` (None: the Reader's ``png_decode``, off by default): PNG files the device decoder takes (``reader.png_plan``) travel as
+    their bytes too, kind ``"png"``, and a group is decoded by one ``bbocr_png_decode`` call (csrc/pngdec.hip, identical pixels); a file
+    the plan refuses (Adam7, 16 bit, APNG, ...) or whose data turns out damaged takes the host decode as before."""
     from .reader import mixed_batch_enabled
 
     mixed = mixed_batch_enabled(mixed)
+    png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
     if mixed:
         max_batch = max(1, min(max_batch, int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))))
     if decode is None:
-        decode = (lambda path, i: _plain_input_device(path, i, device_decode)) if device_decode else _plain_input
+        decode = (lambda path, i: _plain_input_device(path, i, device_decode, png_decode)) if device_decode or png_decode else _plain_input
     if indices is None:
         indices = range(len(image_paths))
     idxs = [i for i in indices if 0 <= i < len(image_paths)]

@@ -246,6 +246,43 @@ def jpeg_page(source, chroma=False, progressive=False):
         return None
 
 
+class PngPage:
+    """A PNG file the device decoder takes (``png_plan``): its bytes and the shape of its decode, ``(H, W, 3)`` -- every PNG page has an RGB
+    and a gray plane.  The page kind ``"png"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one ``bbocr_png_decode``
+    call."""
+    __slots__ = ("data", "shape", "plan")
+
+    def __init__(self, data, plan):
+        self.data = data
+        self.shape = (int(plan.height), int(plan.width), 3)
+        self.plan = plan
+
+
+def png_plan(data):
+    """``bbocr_host_png_plan`` of a file's bytes (no GPU): geometry, depth, colour type, the filtered scanline's ``channels`` / ``row_bytes`` /
+    ``bpp``, ``palette_entries``, the IDAT chunks' count and total payload, ``supported`` and the ``BBOCR_PNG_*`` reason of a refusal."""
+    plan = _lib.bbocr_png_plan()
+    rc = _lib.load().bbocr_host_png_plan(data, len(data), C.byref(plan))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_png_plan failed with status {rc}")
+    return plan
+
+
+def png_page(source):
+    """``PngPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)"""
+    try:
+        data = _file_bytes(source)
+        plan = png_plan(data)
+        return PngPage(data, plan) if plan.supported else None
+    except Exception:
+        return None
+
+
+def png_decode_enabled(png_decode=None):
+    """The ``png_decode`` keyword: None means the environment variable ``BBOCR_PNG_DECODE`` (``1`` = on; off when unset)"""
+    return os.environ.get("BBOCR_PNG_DECODE", "0").strip() == "1" if png_decode is None else bool(png_decode)
+
+
 def reformat_input(image, device_gray=False, parallel_decode=False):
     """easyocr/utils.py::reformat_input -> (RGB uint8 HWC, gray uint8 HW); decode is host work (PIL).
 
@@ -497,7 +534,7 @@ class Reader:
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
                  rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, character=None,
-                 lang_char=None, beam_wide=None, **_ignored):
+                 lang_char=None, beam_wide=None, png_decode=None, **_ignored):
         import torch
 
         net = resolve_recog_network(lang_list, recog_network, model_storage_directory, user_network_directory, character, lang_char)
@@ -536,6 +573,9 @@ class Reader:
         self.device_decode = bool(device_decode)
         self.jpeg_chroma = jpeg_chroma(device_decode)     # "chroma": 4:4:4, 4:2:2 and 4:4:0 files are decoded on the card as well
         self.jpeg_progressive = jpeg_progressive(device_decode)   # "progressive": those, and progressive files (csrc/jpegprog.hip)
+        # PNG files decoded on the card (csrc/pngdec.hip) by readtext(path) and the file callers; an option of its own (None:
+        # BBOCR_PNG_DECODE=1), not a value of device_decode, whose strings are a ladder of JPEG scopes; off unless asked for
+        self.png_decode = png_decode_enabled(png_decode)
         if beam_wide is None:       # decoder='beamsearch' of a model of more than 128 classes searched on the card (csrc/ctc_beam_wide.hip); off unless asked for
             beam_wide = os.environ.get("BBOCR_BEAM_WIDE", "").strip() == "1"
         self.beam_wide = bool(beam_wide)
@@ -1023,6 +1063,67 @@ class Reader:
                                                C.byref(n)))
         return out[:n.value].tobytes()
 
+    def decode_png_batch(self, pages):
+        """``PngPage`` s of ONE shape -> ``((rgb, gray), status)``: the device tensors ``uint8 [n,H,W,3]`` and ``[n,H,W]`` that ``decode_file``
+        + upload would hold, written by ONE ``bbocr_png_decode`` call (only the files' IDAT payloads cross the link), and the per-file
+        status list (0, or negative: that page of both tensors is undefined)."""
+        torch = self._torch
+        pages = list(pages)
+        if not pages or any(p.shape != pages[0].shape for p in pages):
+            raise ValueError("decode_png_batch: pages of one decoded shape")
+        H, W, _ = pages[0].shape
+        n = len(pages)
+        rgb = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+        gray = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+        status = self._png_decode_into(pages, [rgb.data_ptr() + k * H * W * 3 for k in range(n)], [W * 3] * n,
+                                       [gray.data_ptr() + k * H * W for k in range(n)], [W] * n)
+        return (rgb, gray), status
+
+    def _png_decode_into(self, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches):
+        """``bbocr_png_decode`` of the pages into the given device addresses and row pitches -> the per-file status list"""
+        n = len(pages)
+        files, sizes = self._jpeg_files(pages)
+        status = (C.c_int * n)()
+        self._torch.cuda.current_stream(self.device_index).synchronize()      # the library runs on its own stream
+        self._check(self._lib.bbocr_png_decode(self._h, files, sizes, n, (C.c_void_p * n)(*rgb_ptrs), (C.c_longlong * n)(*rgb_pitches),
+                                               (C.c_void_p * n)(*gray_ptrs), (C.c_longlong * n)(*gray_pitches), status))
+        return list(status)
+
+    def decode_png_device(self, sources):
+        """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them, decoded on the card,
+        or ``None`` for a file the plan refuses or whose data is damaged.  Files of one shape share one decode call."""
+        pages = [png_page(s) for s in sources]
+        out = [None] * len(pages)
+        groups = {}
+        for i, p in enumerate(pages):
+            if p is not None:
+                groups.setdefault(p.shape, []).append(i)
+        for idxs in groups.values():
+            (rgb, gray), status = self.decode_png_batch([pages[i] for i in idxs])
+            for k, i in enumerate(idxs):
+                if status[k] == 0:
+                    out[i] = (rgb[k], gray[k])
+        return out
+
+    def png_decode_stage(self, source, stage):
+        """``bbocr_op_png_decode_stage`` of one file (path or bytes) -> ``(array, file status)``: stage 0 the inflated stream ``uint8
+        [H * (1 + row_bytes)]``, 1 the unfiltered scanlines (same size), 2 ``(rgb [H,W,3], gray [H,W])``"""
+        torch = self._torch
+        data = _file_bytes(source)
+        plan = png_plan(data)
+        if not plan.supported or stage not in (0, 1, 2):
+            raise ValueError("png_decode_stage: a file the plan supports and stage 0, 1 or 2")
+        H, W = int(plan.height), int(plan.width)
+        nb = H * (1 + int(plan.row_bytes)) if stage < 2 else 4 * H * W
+        out = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        st = C.c_int()
+        torch.cuda.current_stream(self.device_index).synchronize()
+        self._check(self._lib.bbocr_op_png_decode_stage(self._h, data, len(data), stage, C.c_void_p(out.data_ptr()), nb, C.byref(st)))
+        a = out.cpu().numpy()
+        if stage < 2:
+            return a, st.value
+        return (a[:3 * H * W].reshape(H, W, 3), a[3 * H * W:].reshape(H, W)), st.value
+
     def deflate_device(self, bytes_dev):
         """A contiguous 1-D uint8 device tensor -> the zlib stream ``bbocr_op_deflate`` makes of it (the PNG writer's chunks, run matches and
         dynamic Huffman codes); ``zlib.decompress`` gives the bytes back."""
@@ -1207,6 +1308,10 @@ class Reader:
             dev = self.decode_jpeg_device([image])[0]          # None: refused or damaged -> the host decode below, unchanged
             if dev is not None:
                 # a file given as bytes keeps upstream's rule for arrays (the gray plane derived from the colour image), as with the option off
+                rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
+        if rgb_dev is None and self.png_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
+            dev = self.decode_png_device([image])[0]           # None: not a PNG, refused or damaged -> the host decode below, unchanged
+            if dev is not None:
                 rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
         if rgb_dev is None:
             img, grey = reformat_input(image, device_gray=True, parallel_decode=True)

@@ -855,6 +855,57 @@ int bbocr_op_deflate(bbocr_ctx* ctx, const uint8_t* dev_bytes, size_t n, uint8_t
 int bbocr_op_png_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int layout, size_t n, void* dev_dst,
                        size_t dst_bytes, size_t* bytes);
 
+/* ---- PNG files decoded on the device (csrc/pngdec.hip; opt-in: Reader(png_decode=True)): what reader.decode_file holds for a PNG file
+ * -- Pillow's convert("RGB") and the gray plane of its stated rule -- from the file's bytes, of which only the IDAT payloads cross the link.
+ * Scope: non-interlaced files of colour type 0 at depth 1 / 2 / 4 / 8, colour type 3 at depth 1 / 2 / 4 / 8 with PLTE, colour types 2, 4
+ * and 6 at depth 8.  tRNS and every other ancillary chunk are skipped (convert("RGB") ignores them).  Defined by tests/png_decode_ref.py.
+ * bbocr_host_png_plan: host only, no GPU: one pass over the chunks.  Fields the walk did not reach stay 0; the IHDR fields of a file that
+ * is refused behind its IHDR are filled. */
+enum {
+    BBOCR_PNG_OK = 0,
+    BBOCR_PNG_NOT_PNG = 1,      /* no signature */
+    BBOCR_PNG_TRUNCATED = 2,    /* a chunk runs past the end of the file, or the file ends before IEND */
+    BBOCR_PNG_CRC = 3,          /* CRC-32 mismatch of any chunk up to IEND -- IHDR, PLTE, IDAT, IEND and the ancillary ones: Pillow refuses such a file */
+    BBOCR_PNG_DIMENSIONS = 4,   /* width or height 0, the filtered stream H * (1 + row_bytes) above 2^31 - 1 bytes, or more than 178,956,970
+                                 * pixels (twice Pillow's MAX_IMAGE_PIXELS, where its decode raises) */
+    BBOCR_PNG_DEPTH = 5,        /* 16-bit samples, or a depth the colour type does not allow */
+    BBOCR_PNG_INTERLACE = 6,    /* Adam7 */
+    BBOCR_PNG_PALETTE = 7,      /* colour type 3 without PLTE, PLTE behind IDAT, a second PLTE, a PLTE of 0, more than 256 or not whole entries */
+    BBOCR_PNG_IDAT_ORDER = 8,   /* IDAT chunks that are not consecutive */
+    BBOCR_PNG_APNG = 9,         /* an acTL chunk */
+    BBOCR_PNG_ZLIB = 10,        /* the zlib header: method other than 8, window above 32 KiB, FDICT set, failing FCHECK, fewer than 2 bytes */
+    BBOCR_PNG_HEADER = 11       /* the first chunk is not a 13-byte IHDR, an unknown colour type, compression, filter or interlace method, no IDAT */
+};
+typedef struct bbocr_png_plan {
+    int width, height, bit_depth, color_type;
+    int channels;               /* samples per pixel of the filtered scanline: 1, 2, 3 or 4 (a palette index counts as one) */
+    int bpp;                    /* the filters' byte distance: channels at depth 8, 1 below */
+    long long row_bytes;        /* of a filtered scanline without its filter byte: ceil(width * channels * bit_depth / 8) */
+    int palette_entries;        /* of PLTE (any colour type), 0 without one */
+    int idat_chunks;
+    long long idat_bytes;       /* the IDAT payloads together: the zlib stream */
+    int supported;              /* 1: bbocr_png_decode takes the file */
+    int reason;                 /* BBOCR_PNG_* */
+    int reserved[2];
+} bbocr_png_plan;
+int bbocr_host_png_plan(const void* file, size_t bytes, bbocr_png_plan* plan);
+/* n files (HOST bytes) -> both planes in DEVICE memory, one call per batch: dst_rgb[k] receives uint8 [H,W,3], rows pitch_rgb[k] bytes
+ * apart, dst_gray[k] uint8 [H,W], rows pitch_gray[k] bytes apart -- one shape per file, so that the call serves a uniform batch and pages
+ * of mixed shapes alike.  RGB: Pillow's convert("RGB") (a gray sample replicated, depths 1 / 2 / 4 scaled by 255 / 85 / 17; alpha dropped;
+ * the palette looked up).  Gray: the stored (scaled) sample for colour types 0 and 4, else (9797 R + 19234 G + 3737 B) >> 15.
+ * status[k]: 0, BBOCR_ERR_ARG (a null pointer, a pitch shorter than a row, a file the plan refuses) or BBOCR_ERR_DATA: the zlib stream is
+ * damaged (the input runs out, block type 3, LEN != ~NLEN, an over-subscribed or incomplete code -- a single code of one bit excepted, as
+ * in zlib --, a bit pattern without a code, a distance beyond the bytes produced, more or fewer bytes than H * (1 + row_bytes), another
+ * Adler-32 than the trailer's), a filter byte is above 4, or a palette index is at or above palette_entries.  Such a file's destinations
+ * are undefined; no byte outside a destination's rows is ever written, the other files decode all the same and the context stays usable.
+ * Stream, one-batch-at-a-time contract and work buffers: bbocr_jpeg_decode's.  Returns with its work finished, also when it fails.
+ * bbocr_op_png_decode_stage: the intermediates of ONE file in DEVICE memory dev_dst[dst_bytes] (parity tests), by the kernels the full call
+ * runs: stage 0 = the inflated stream, H * (1 + row_bytes) bytes (only the inflate stage runs); 1 = the same after the filters are
+ * reversed; 2 = RGB [H,W,3] followed by gray [H,W], tight.  *file_status as status[k] above, of the stages that ran. */
+int bbocr_png_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                     uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
+int bbocr_op_png_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
+
 #ifdef __cplusplus
 }
 #endif
