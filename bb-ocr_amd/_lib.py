@@ -214,6 +214,8 @@ PROTOTYPES = {
     "bbocr_auto_crop": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "bbocr_op_autocrop_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, _vp]),
+    "bbocr_op_autocrop_mask_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, _vp, C.POINTER(C.c_int), C.c_int,
+                                               C.POINTER(C.c_int)]),
     "bbocr_ocr_thumbnail": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp, C.POINTER(C.c_int),
                                       C.POINTER(C.c_int)]),
     "bbocr_op_thumbnail_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp,

@@ -43,15 +43,17 @@ struct AcPlan {
     int *thr, *count, *boxes;
 };
 
-// one carve of the slot's auto-crop buffer; the labels reuse the row planes and the flags the cue plane (both dead by then)
-AcPlan ac_plan(bbocr_ctx* c, int H, int W) {
+// one carve of the slot's auto-crop buffer; the labels reuse the row planes and the flags the cue plane (both dead by then).
+// any_mask: the components are taken of a mask that no morphology has merged (bbocr_op_autocrop_mask_stage, `components`)
+AcPlan ac_plan(bbocr_ctx* c, int H, int W, bool any_mask = false) {
     AcPlan p{};
     p.H = H;
     p.W = W;
     p.WW = (W + 31) / 32;
     const size_t n = (size_t)H * W, nw = (size_t)p.WW * H;
-    // every component of the merged mask holds a whole 13 x 5 dilation window (clipped at the edges), so at most n / that many exist
-    p.cap = (int)(n / ((size_t)std::min(W, 7) * std::min(H, 3))) + 1;
+    // every component of the merged mask holds a whole 13 x 5 dilation window (clipped at the edges), so at most n / that many exist;
+    // of any mask, 8-connected: no two components share a 2 x 2 cell
+    p.cap = any_mask ? (int)(((size_t)(H + 1) / 2) * ((size_t)(W + 1) / 2)) : (int)(n / ((size_t)std::min(W, 7) * std::min(H, 3))) + 1;
     Carve cv;
     const size_t o_blur = cv.add(n), o_clahe = cv.add(n), o_rows = cv.add(4 * n), o_part = cv.add(n), o_grad = cv.add(n);
     size_t o_bits[5];
@@ -75,6 +77,30 @@ AcPlan ac_plan(bbocr_ctx* c, int H, int W) {
     return p;
 }
 
+// the morphology: packed mask bits[0] -> merged mask bits[4]
+void ac_enqueue_merge(bbocr_ctx* c, const AcPlan& p) {
+    const int H = p.H, W = p.W, WW = p.WW;
+    hipStream_t s = c->stream;
+    // per variant: CLOSE (rect kernel, 2 iterations folded by OpenCV into (k - 1) * 2 + 1), OPEN 3x3, dilate 11x3.  Rect erosions and
+    // dilations with the in-bounds-only border compose into one rect each: dilate K2, erode K2 + 3x3, and -- shared by both variants,
+    // dilation distributing over OR -- dilate 3x3 + 11x3 = 13x5 once on the OR of the two.  Radii (x, y):
+    //   9x3 -> 17x5: dilate (8, 2), erode 19x7 (9, 3);   15x5 -> 29x9: dilate (14, 4), erode 31x11 (15, 5);   final dilate (6, 2)
+    uint32_t *m = p.bits[0], *t = p.bits[1], *a = p.bits[2], *v = p.bits[3], *out = p.bits[4];
+    HIPCHK(launch_ac_rect(m, t, a, H, W, WW, 8, 2, 0, nullptr, s));
+    HIPCHK(launch_ac_rect(a, t, out, H, W, WW, 9, 3, 1, nullptr, s));     // variant 1 -> out (scratch until the last step)
+    HIPCHK(launch_ac_rect(m, t, a, H, W, WW, 14, 4, 0, nullptr, s));
+    HIPCHK(launch_ac_rect(a, t, v, H, W, WW, 15, 5, 1, out, s));                               // variant 2 | variant 1 -> v
+    HIPCHK(launch_ac_rect(v, t, out, H, W, WW, 6, 2, 0, nullptr, s));
+}
+
+// the external components of a packed mask: numbered in p.label, counted in p.count, their raw boxes in p.boxes
+void ac_enqueue_components(bbocr_ctx* c, const AcPlan& p, const uint32_t* mask) {
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemsetAsync(p.flag, 0, (size_t)p.H * p.W, s));
+    HIPCHK(hipMemsetAsync(p.count, 0, 4, s));
+    HIPCHK(launch_ac_components(mask, p.H, p.W, p.WW, p.label, p.flag, p.count, p.cap, p.boxes, s));
+}
+
 // enqueues the chain up to `last`: 0 = CLAHE output, 1 = composite mask (bits[0]), 2 = merged mask (bits[4]), 3 = external components
 void ac_enqueue(bbocr_ctx* c, const AcPlan& p, const uint8_t* src, size_t pitch, int channels, int last) {
     const int H = p.H, W = p.W, WW = p.WW;
@@ -89,20 +115,23 @@ void ac_enqueue(bbocr_ctx* c, const AcPlan& p, const uint8_t* src, size_t pitch,
     HIPCHK(launch_ac_cues(p.clahe, H, W, taps, p.rbox, p.rgau, p.part, p.grad, p.hist, p.thr, s));
     HIPCHK(launch_ac_pack(p.clahe, p.part, p.grad, p.thr, H, W, WW, p.bits[0], s));
     if (last == 1) return;
-    // per variant: CLOSE (rect kernel, 2 iterations folded by OpenCV into (k - 1) * 2 + 1), OPEN 3x3, dilate 11x3.  Rect erosions and
-    // dilations with the in-bounds-only border compose into one rect each: dilate K2, erode K2 + 3x3, and -- shared by both variants,
-    // dilation distributing over OR -- dilate 3x3 + 11x3 = 13x5 once on the OR of the two.  Radii (x, y):
-    //   9x3 -> 17x5: dilate (8, 2), erode 19x7 (9, 3);   15x5 -> 29x9: dilate (14, 4), erode 31x11 (15, 5);   final dilate (6, 2)
-    uint32_t *m = p.bits[0], *t = p.bits[1], *a = p.bits[2], *v = p.bits[3], *out = p.bits[4];
-    HIPCHK(launch_ac_rect(m, t, a, H, W, WW, 8, 2, 0, nullptr, s));
-    HIPCHK(launch_ac_rect(a, t, out, H, W, WW, 9, 3, 1, nullptr, s));     // variant 1 -> out (scratch until the last step)
-    HIPCHK(launch_ac_rect(m, t, a, H, W, WW, 14, 4, 0, nullptr, s));
-    HIPCHK(launch_ac_rect(a, t, v, H, W, WW, 15, 5, 1, out, s));                               // variant 2 | variant 1 -> v
-    HIPCHK(launch_ac_rect(v, t, out, H, W, WW, 6, 2, 0, nullptr, s));
+    ac_enqueue_merge(c, p);
     if (last == 2) return;
-    HIPCHK(hipMemsetAsync(p.flag, 0, n, s));
-    HIPCHK(hipMemsetAsync(p.count, 0, 4, s));
-    HIPCHK(launch_ac_components(out, H, W, WW, p.label, p.flag, p.count, p.cap, p.boxes, s));
+    ac_enqueue_components(c, p, p.bits[4]);
+}
+
+// waits for the queued work; the raw boxes (x0, y0, x1, y1 inclusive) of the external components, in the device's enumeration order
+std::vector<int> ac_read_raw_boxes(bbocr_ctx* ctx, const AcPlan& p) {
+    int count = 0;
+    HIPCHK(hipMemcpyAsync(&count, p.count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    slot_sync(ctx, ctx->stream);
+    if (count > p.cap) fail(BBOCR_ERR_OVERFLOW, "more external components than the bound allows");
+    std::vector<int> raw((size_t)count * 4);
+    if (count) {
+        HIPCHK(hipMemcpyAsync(raw.data(), p.boxes, raw.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        slot_sync(ctx, ctx->stream);
+    }
+    return raw;
 }
 
 void ac_check_args(const void* src, int H, int W, long long pitch, int channels) {
@@ -124,15 +153,8 @@ int bbocr_auto_crop(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long l
         if (!box || !found || !n_comps || margin < 0 || max_comps < 0 || (max_comps > 0 && !comp_boxes)) fail(BBOCR_ERR_ARG, "bad arguments");
         const AcPlan p = ac_plan(ctx, H, W);
         ac_enqueue(ctx, p, dev_src, (size_t)pitch, channels, 3);
-        int count = 0;
-        HIPCHK(hipMemcpyAsync(&count, p.count, 4, hipMemcpyDeviceToHost, ctx->stream));
-        slot_sync(ctx, ctx->stream);
-        if (count > p.cap) fail(BBOCR_ERR_OVERFLOW, "more external components than the bound allows");
-        std::vector<int> raw((size_t)count * 4);
-        if (count) {
-            HIPCHK(hipMemcpyAsync(raw.data(), p.boxes, raw.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-            slot_sync(ctx, ctx->stream);
-        }
+        const std::vector<int> raw = ac_read_raw_boxes(ctx, p);
+        const int count = (int)(raw.size() / 4);
         // boundingRect + the reference's area filter, in double like the Python floats (enhanced_extractor.py:287-297)
         const double img_area = (double)H * (double)W;
         std::vector<std::array<int, 4>> kept;
@@ -188,6 +210,35 @@ int bbocr_op_autocrop_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, i
         if (stage == 3) HIPCHK(hipMemcpyAsync(&count, p.count, 4, hipMemcpyDeviceToHost, ctx->stream));
         slot_sync(ctx, ctx->stream);
         if (count > p.cap) fail(BBOCR_ERR_OVERFLOW, "more external components than the bound allows");
+    });
+}
+
+int bbocr_op_autocrop_mask_stage(bbocr_ctx* ctx, int mode, const uint8_t* dev_mask, int H, int W, long long pitch, uint8_t* dev_dst, int* boxes,
+                                 int max_boxes, int* n_boxes) {
+    return guarded(ctx, [&](bbocr_ctx* ctx) {
+        check_page({dev_mask, H, W, pitch, PAGE_GRAY});
+        if (!dev_dst || !n_boxes || max_boxes < 0 || (max_boxes > 0 && !boxes)) fail(BBOCR_ERR_ARG, "bad arguments");
+        if (mode < BBOCR_AC_MASK_MERGED || mode > BBOCR_AC_MASK_COMPONENTS) fail(BBOCR_ERR_ARG, "unknown mode");
+        const AcPlan p = ac_plan(ctx, H, W, mode == BBOCR_AC_MASK_COMPONENTS);
+        HIPCHK(launch_ac_pack_mask(dev_mask, (size_t)pitch, H, W, p.WW, p.bits[0], ctx->stream));
+        if (mode != BBOCR_AC_MASK_COMPONENTS) ac_enqueue_merge(ctx, p);
+        const uint32_t* mask = mode == BBOCR_AC_MASK_COMPONENTS ? p.bits[0] : p.bits[4];
+        if (mode != BBOCR_AC_MASK_MERGED) ac_enqueue_components(ctx, p, mask);
+        HIPCHK(launch_ac_unpack(mask, mode == BBOCR_AC_MASK_MERGED ? nullptr : p.label, H, W, p.WW, dev_dst, ctx->stream));
+        *n_boxes = 0;
+        if (mode == BBOCR_AC_MASK_MERGED) {
+            slot_sync(ctx, ctx->stream);
+            return;
+        }
+        const std::vector<int> raw = ac_read_raw_boxes(ctx, p);
+        *n_boxes = (int)(raw.size() / 4);
+        for (int k = 0; k < std::min(max_boxes, *n_boxes); ++k) {
+            const int* r = &raw[(size_t)k * 4];
+            boxes[4 * k + 0] = r[0];
+            boxes[4 * k + 1] = r[1];
+            boxes[4 * k + 2] = r[2] - r[0] + 1;
+            boxes[4 * k + 3] = r[3] - r[1] + 1;
+        }
     });
 }
 

@@ -160,6 +160,20 @@ __global__ void __launch_bounds__(256) ac_pack_kernel(const uint8_t* __restrict_
     }
 }
 
+// ---- a byte mask (nonzero = set) read through a row pitch, packed the same way (bbocr_op_autocrop_mask_stage): padding bits are 0
+__global__ void __launch_bounds__(256) ac_pack_mask_kernel(const uint8_t* __restrict__ src, size_t pitch, int H, int W, int WW,
+                                                           uint32_t* __restrict__ bits) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= WW) return;
+    const int x0 = j * 32, nx = min(32, W - x0);
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        const uint8_t* row = src + (size_t)y * pitch + x0;
+        uint32_t w = 0;
+        for (int k = 0; k < nx; ++k) w |= (row[k] ? 1u : 0u) << k;
+        bits[(size_t)y * WW + j] = w;
+    }
+}
+
 // ---- rect morphology along rows on the packed mask, radius r < 32: dilate = OR of the shifted words (pixels outside the row are 0),
 // erode = AND (pixels outside the row are 1: OpenCV's default border value never lets the border take part); padding bits stay 0
 __global__ void __launch_bounds__(256) ac_row_morph_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int H, int W, int WW, int r,
@@ -367,6 +381,10 @@ hipError_t launch_ac_cues(const uint8_t* e, int H, int W, const AcTaps& taps, ui
 }
 hipError_t launch_ac_pack(const uint8_t* e, const uint8_t* part, const uint8_t* grad, const int* thr, int H, int W, int WW, uint32_t* bits, hipStream_t s) {
     hipLaunchKernelGGL(ac_pack_kernel, pix_grid(WW, H), dim3(256), 0, s, e, part, grad, thr, H, W, WW, bits);
+    return hipGetLastError();
+}
+hipError_t launch_ac_pack_mask(const uint8_t* src, size_t pitch, int H, int W, int WW, uint32_t* bits, hipStream_t s) {
+    hipLaunchKernelGGL(ac_pack_mask_kernel, pix_grid(WW, H), dim3(256), 0, s, src, pitch, H, W, WW, bits);
     return hipGetLastError();
 }
 hipError_t launch_ac_rect(const uint32_t* src, uint32_t* tmp, uint32_t* dst, int H, int W, int WW, int rx, int ry, int erode, const uint32_t* or_with,

@@ -308,6 +308,7 @@ hipError_t launch_ac_gray_blur(const uint8_t* src, int H, int W, size_t pitch, i
 hipError_t launch_ac_cues(const uint8_t* e, int H, int W, const AcTaps& taps, uint16_t* rbox, uint16_t* rgau, uint8_t* part, uint8_t* grad,
                           unsigned int* hist, int* thr, hipStream_t s);
 hipError_t launch_ac_pack(const uint8_t* e, const uint8_t* part, const uint8_t* grad, const int* thr, int H, int W, int WW, uint32_t* bits, hipStream_t s);
+hipError_t launch_ac_pack_mask(const uint8_t* src, size_t pitch, int H, int W, int WW, uint32_t* bits, hipStream_t s);
 hipError_t launch_ac_rect(const uint32_t* src, uint32_t* tmp, uint32_t* dst, int H, int W, int WW, int rx, int ry, int erode, const uint32_t* or_with,
                           hipStream_t s);
 hipError_t launch_ac_components(const uint32_t* bits, int H, int W, int WW, int* label, uint8_t* flag, int* count, int cap, int* boxes, hipStream_t s);

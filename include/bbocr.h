@@ -524,6 +524,16 @@ int bbocr_auto_crop(bbocr_ctx* ctx, const uint8_t* dev_src, int H, int W, long l
 /* its intermediates as u8 [H,W] in dev_dst (parity tests): stage 0 = CLAHE output, 1 = composite threshold mask (0/255), 2 = merged
  * morphology mask, 3 = pixels of the external (RETR_EXTERNAL) components of the merged mask */
 int bbocr_op_autocrop_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, long long pitch, int channels, uint8_t* dev_dst);
+/* the same morphology and component code on a mask the caller designs (parity tests): dev_mask is a byte plane [H,W], nonzero = set, rows
+ * `pitch` bytes apart; dev_dst receives u8 [H,W] of 0 / 255.  MERGED: the merged morphology mask of dev_mask.  EXTERNAL: the pixels of
+ * the external components of that merged mask.  COMPONENTS: the pixels of the external components of dev_mask itself, no morphology.
+ * The last two report every external component's bounding box before any area filter: *n_boxes of them, the first
+ * min(*n_boxes, max_boxes) as (x, y, w, h) in `boxes`, in no particular order (boxes may be null when max_boxes is 0); MERGED sets
+ * *n_boxes = 0.  Any H, W >= 1: the CLAHE grid rule of the page entries does not apply.  BBOCR_ERR_ARG before anything is queued:
+ * null pointers, H or W < 1, pitch < W, an unknown mode, max_boxes < 0. */
+enum { BBOCR_AC_MASK_MERGED = 0, BBOCR_AC_MASK_EXTERNAL = 1, BBOCR_AC_MASK_COMPONENTS = 2 };
+int bbocr_op_autocrop_mask_stage(bbocr_ctx* ctx, int mode, const uint8_t* dev_mask, int H, int W, long long pitch, uint8_t* dev_dst, int* boxes,
+                                 int max_boxes, int* n_boxes);
 
 /* ---- OCR-input thumbnail (enhanced_extractor.py:486-512, the step between the crops and readtext) of one u8 page on the device: a page
  * whose longer side exceeds max_dim becomes Image.thumbnail((max_dim, max_dim)) in RGB (Pillow 12: reduce by int(size / out / 2) when that

@@ -1,5 +1,6 @@
 """-m gpu: the text-region auto-crop on the device (csrc/autocrop.hip, bbocr_auto_crop / bbocr_op_autocrop_stage) against the CPU
-restatement of tests/autocrop_ref.py, stage by stage and box by box, and through the extractor's OCR input path."""
+restatement of tests/autocrop_ref.py, stage by stage and box by box, and through the extractor's OCR input path; its rect morphology
+and component kernels on the designed masks of tests/autocrop_cases.py (bbocr_op_autocrop_mask_stage)."""
 import ctypes as C
 import os
 import threading
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import autocrop_cases as cases
 import autocrop_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -230,3 +232,128 @@ def test_extract_texts_with_crops(reader, photo_f2):
     # defaults: the keywords off leave the pages as they were
     assert extractor_batch.extract_texts(reader, [PHOTO]) == extractor_batch.extract_texts(reader, [PHOTO], use_preprocessing=False,
                                                                                             edge_crop_percent=0.0, crop_for_ocr=False)
+
+
+# ---- designed masks (tests/autocrop_cases.py) through bbocr_op_autocrop_mask_stage: the rect morphology and the component kernels on
+# structure the pages above never give them.  Every comparison is exact.
+
+MODES = {"merged": 0, "external": 1, "components": 2}
+GUARD = 96
+
+
+def _mask_stage(reader, mask, mode, max_boxes=None):
+    """-> (u8 [H,W] output, sorted (x, y, w, h) boxes, reported count).  The mask is a view inside a larger plane of nonzero bytes, its
+    set pixels any nonzero value; the output lies between guard bytes, which must come back as they were."""
+    H, W = mask.shape
+    host = np.full((H + 3, W + 7), 1, np.uint8)
+    host[2:H + 2, 3:W + 3] = np.where(mask, 1 + (np.arange(mask.size).reshape(H, W) % 255), 0)
+    view = torch.from_numpy(host).to(reader.device)[2:H + 2, 3:W + 3]
+    assert view.stride() == (W + 7, 1)
+    flat = torch.full((GUARD + H * W + GUARD,), 7, dtype=torch.uint8, device=reader.device)
+    cap = ((H + 1) // 2) * ((W + 1) // 2) if max_boxes is None else max_boxes
+    boxes, n = (C.c_int * (4 * cap + 4))(*([-5] * (4 * cap + 4))), C.c_int(-1)
+    reader._check(reader._lib.bbocr_op_autocrop_mask_stage(reader._h, MODES[mode], C.c_void_p(view.data_ptr()), H, W, W + 7,
+                                                           C.c_void_p(flat.data_ptr() + GUARD), boxes, cap, C.byref(n)))
+    got = flat.cpu().numpy()
+    assert (got[:GUARD] == 7).all() and (got[GUARD + H * W:] == 7).all(), "guard bytes around the destination were written"
+    k = min(n.value, cap)
+    assert list(boxes[4 * k:]) == [-5] * (4 * (cap - k) + 4), "box slots beyond the copied ones were written"
+    return got[GUARD:GUARD + H * W].reshape(H, W), sorted(tuple(boxes[4 * i:4 * i + 4]) for i in range(k)), n.value
+
+
+def _u8(m):
+    return np.where(m, 255, 0).astype(np.uint8)
+
+
+def _check_mask_case(reader, name, e):
+    got, boxes, n = _mask_stage(reader, e.mask, "merged")
+    bad = int((got != _u8(e.merged)).sum())
+    assert bad == 0 and n == 0 and boxes == [], f"{name} merged: {bad} of {got.size} pixels differ"
+    for mode, (wmask, wboxes) in (("external", e.external), ("components", e.components)):
+        got, boxes, n = _mask_stage(reader, e.mask, mode)
+        bad = int((got != _u8(wmask)).sum())
+        assert bad == 0, f"{name} {mode}: {bad} of {got.size} pixels differ"
+        assert n == len(wboxes) and boxes == sorted(wboxes), f"{name} {mode}: boxes {boxes[:8]} want {sorted(wboxes)[:8]}"
+
+
+@pytest.mark.parametrize("family", list(cases.FAMILIES))
+def test_mask_stage_designed_cases(reader, family):
+    exp = {n: e for n, e in cases.expected().items() if n in cases.FAMILIES[family]()}
+    assert exp
+    for name, e in exp.items():
+        _check_mask_case(reader, name, e)
+
+
+def test_mask_stage_consecutive_calls_agree(reader):
+    exp = cases.expected()
+    names = [n for n in exp if n.startswith(("random/", "chain/", "lattice/", "checkerboard/", "diamond/", "area/"))]
+    assert len(names) >= 12
+    for mode in MODES:
+        for name in names:
+            a, b = _mask_stage(reader, exp[name].mask, mode), _mask_stage(reader, exp[name].mask, mode)
+            assert np.array_equal(a[0], b[0]) and a[1:] == b[1:], (mode, name)
+    # a large mask, then a small one in the same work buffer, then the page path: nothing of the earlier call shows
+    big, small = exp["random/8x8230/p0.01"], exp["diamond/closed"]
+    _check_mask_case(reader, "big", big)
+    _check_mask_case(reader, "small", small)
+    _check_page(reader, _text_page(1, 64, 64))
+    _check_mask_case(reader, "small", small)
+
+
+def test_mask_stage_box_limit_and_errors(reader):
+    e = cases.expected()["lattice/11x33"]
+    want = sorted(e.components[1])
+    full = _mask_stage(reader, e.mask, "components")
+    assert full[1] == want and full[2] == len(want) == 102
+    # fewer slots than boxes: the count is still the whole count, and only that many boxes are copied (each a real one)
+    _, some, n = _mask_stage(reader, e.mask, "components", max_boxes=5)
+    assert n == 102 and len(some) == 5 and set(some) <= set(want)
+    _, none, n = _mask_stage(reader, e.mask, "components", max_boxes=0)
+    assert n == 102 and none == []
+    f = reader._lib.bbocr_op_autocrop_mask_stage
+    src = torch.ones((16, 40), dtype=torch.uint8, device=reader.device)
+    dst = torch.full((16, 40), 7, dtype=torch.uint8, device=reader.device)
+    sp, dp = C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr())
+    boxes, cnt = (C.c_int * 16)(), C.c_int()
+    assert f(reader._h, 2, sp, 16, 40, 40, dp, None, 0, C.byref(cnt)) == 0 and cnt.value == 1          # no box buffer needed for 0 slots
+    bad = [
+        (2, None, 16, 40, 40, dp, boxes, 4, C.byref(cnt)),
+        (2, sp, 16, 40, 40, None, boxes, 4, C.byref(cnt)),
+        (2, sp, 16, 40, 40, dp, None, 4, C.byref(cnt)),
+        (2, sp, 16, 40, 40, dp, boxes, 4, None),
+        (2, sp, 16, 40, 39, dp, boxes, 4, C.byref(cnt)),          # pitch < W
+        (2, sp, 0, 40, 40, dp, boxes, 4, C.byref(cnt)),
+        (2, sp, 16, 0, 40, dp, boxes, 4, C.byref(cnt)),
+        (3, sp, 16, 40, 40, dp, boxes, 4, C.byref(cnt)),          # unknown modes
+        (-1, sp, 16, 40, 40, dp, boxes, 4, C.byref(cnt)),
+        (2, sp, 16, 40, 40, dp, boxes, -1, C.byref(cnt)),
+    ]
+    dst.fill_(7)
+    for k, args in enumerate(bad):
+        assert f(reader._h, *args) == -1, k                       # BBOCR_ERR_ARG
+    assert f(None, 2, sp, 16, 40, 40, dp, boxes, 4, C.byref(cnt)) == -1
+    assert bool((dst == 7).all())                                 # refused before anything was queued
+    # the context still works afterwards
+    assert _mask_stage(reader, e.mask, "components")[1] == want
+
+
+@pytest.mark.parametrize("shape", cases.BAR_PAGES)
+def test_stages_sparse_bar_pages(reader, shape):
+    # widths that are no multiple of 32, a merged mask with structure: gray, BGR, and both as views of larger planes
+    from scipy import ndimage
+
+    H, W = shape
+    page = cases.bar_page(shape)
+    st = ref.stages(page)
+    assert W % 32 and len(st["boxes"]) >= 3 and 0.02 < st["merged"].mean() < 0.6
+    assert ndimage.label(st["merged"], structure=np.ones((3, 3), bool))[1] == len(st["boxes"])
+    assert _check_page(reader, page, margin=8) is not None
+    bgr = np.repeat(page[:, :, None], 3, axis=2)
+    bgr[:, :, 0] = np.minimum(bgr[:, :, 0], 200)                 # not a gray image in three channels
+    _check_page(reader, bgr, margin=8)
+    big = torch.full((H + 9, W + 21), 255, dtype=torch.uint8, device=reader.device)
+    big[4:H + 4, 11:W + 11] = torch.from_numpy(page).to(reader.device)
+    _check_page(reader, page, dev=big[4:H + 4, 11:W + 11], margin=8)
+    big3 = torch.full((H + 9, W + 21, 3), 255, dtype=torch.uint8, device=reader.device)
+    big3[4:H + 4, 11:W + 11] = torch.from_numpy(bgr).to(reader.device)
+    _check_page(reader, bgr, dev=big3[4:H + 4, 11:W + 11], margin=8)
