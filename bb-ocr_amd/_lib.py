@@ -97,6 +97,19 @@ class bbocr_png_plan(C.Structure):
  PNG_HEADER) = range(12)
 
 
+class bbocr_tiff_plan(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bits", C.c_int), ("samples", C.c_int), ("photometric", C.c_int),
+                ("compression", C.c_int), ("predictor", C.c_int), ("big_endian", C.c_int), ("rows_per_strip", C.c_longlong), ("strips", C.c_int),
+                ("extra_sample", C.c_int), ("row_bytes", C.c_longlong), ("strip_bytes", C.c_longlong), ("supported", C.c_int), ("reason", C.c_int),
+                ("reserved", C.c_int * 2)]
+
+
+# bbocr.h BBOCR_TIFF_*: why bbocr_host_tiff_plan refuses a file
+(TIFF_OK, TIFF_NOT_TIFF, TIFF_BIGTIFF, TIFF_TRUNCATED, TIFF_HEADER, TIFF_DIMENSIONS, TIFF_TILES, TIFF_PLANAR, TIFF_FILL_ORDER, TIFF_DEPTH,
+ TIFF_SUBBYTE, TIFF_GRAY_ALPHA, TIFF_ASSOC_ALPHA, TIFF_PHOTOMETRIC, TIFF_SAMPLES, TIFF_JPEG, TIFF_CCITT, TIFF_COMPRESSION, TIFF_PREDICTOR,
+ TIFF_OLD_LZW, TIFF_STRIPS, TIFF_PALETTE) = range(22)
+
+
 CONV_ROUTE_IDS = ("NONE", "GEN64_P4", "GEN64_P8", "GEN64_P16", "GEN128_P4", "GEN128_P8", "GEN128_P16", "DMA64_FUSE1", "DMA64_POSTW", "RESW_POOL64",
                   "RESW_1CH", "RESW_2CH", "DMA64_324_NF2", "DMA64_324", "DMA64_384", "DMA64_448", "DMA128_384", "DMA128_448", "DMA2X2_64",
                   "DMA2X2_128", "DMA1X1_64", "DMA1X1_128", "DMA1X1_256", "DMA1X1_ADDUP")       # include/bbocr.h BBOCR_ROUTE_*, in order
@@ -264,6 +277,10 @@ PROTOTYPES = {
     "bbocr_png_decode": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "bbocr_op_png_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_host_tiff_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_tiff_plan)]),
+    "bbocr_tiff_decode": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "bbocr_op_tiff_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -42,6 +42,14 @@ def _png_page(source):
     return None if page is None else ("png", page, None)
 
 
+def _tiff_page(source):
+    """``("tiff", TiffPage, None)`` when the device TIFF decoder takes the file (a path or its bytes), else None"""
+    from .reader import tiff_page
+
+    page = tiff_page(source)
+    return None if page is None else ("tiff", page, None)
+
+
 def _host_page(source, decode_once=True):
     """The host decode of a file (a path or its bytes) as a page: ``("ycc", triples, None)`` when it is a YCbCr-coded JPEG and
     ``decode_once`` (decoded once, RGB + Y plane derived on the card: reader.decode_file_ycc), else ``("rgb", rgb, gray)``."""
@@ -68,7 +76,7 @@ def _thumbnail_jpeg(size, image_index, load_rgb):
     return buf.getvalue()
 
 
-def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False, png_decode=False):
+def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False, png_decode=False, tiff_decode=False):
     """``ocr_input_image`` for the batching loop: ``("ycc", triples, None)`` when the file easyocr would be given is a YCbCr-coded JPEG
     (``_host_page``) -- every thumbnail is, it is written as one -- else ``("rgb", rgb, gray)``.  ``device_decode``: the file easyocr
     would be given travels as its bytes (``("jpg", JpegPage, None)``) when the device decoder takes it -- the original at or below the
@@ -84,6 +92,8 @@ def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=Fal
     page = _jpg_page(source, device_decode) if device_decode else None
     if page is None and png_decode and source is image_path:       # the original file, at or below the limit (a thumbnail is a JPEG)
         page = _png_page(source)
+    if page is None and tiff_decode and source is image_path:      # likewise a TIFF file
+        page = _tiff_page(source)
     return page if page is not None else _host_page(source, decode_once)
 
 
@@ -190,7 +200,7 @@ def ocr_input_image(image_path, image_index=None):
 
 def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
                   edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, device_decode=False, mixed=None,
-                  png_decode=None, **readtext_kw):
+                  png_decode=None, tiff_decode=None, **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
     batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
@@ -205,10 +215,12 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     ``device_decode="chroma"``: the same, and 4:4:4, 4:2:2 and 4:4:0 files -- which ``True`` leaves to the host -- are decoded there too.
     ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches.
     ``png_decode`` (None: the Reader's ``png_decode``): a PNG file at or below its page's limit that the device PNG decoder takes reaches
-    the card as its bytes (kind ``"png"``); with the crop settings or ``device_thumbnail`` on, and above the limit, a PNG keeps today's path."""
+    the card as its bytes (kind ``"png"``); with the crop settings or ``device_thumbnail`` on, and above the limit, a PNG keeps today's path.
+    ``tiff_decode`` (None: the Reader's ``tiff_decode``): the same for a TIFF file the device TIFF decoder takes (kind ``"tiff"``)."""
     from .preprocess import ocr_input_device
 
     png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
+    tiff_decode = bool(getattr(reader, "tiff_decode", False)) if tiff_decode is None else bool(tiff_decode)
 
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
         if crop_margin < 0:
@@ -223,7 +235,7 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     elif device_thumbnail:
         decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once, device_decode)
     else:
-        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode, png_decode)
+        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode, png_decode, tiff_decode)
     res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, mixed=mixed, **readtext_kw)
     return {i: " ".join(t[1] for t in r) for i, r in res.items()}
 
@@ -233,9 +245,11 @@ def _plain_input(path, i=None):
     return _host_page(path)
 
 
-def _plain_input_device(path, i=None, device_decode=True, png_decode=False):
-    """``_plain_input`` with the device decoders: the file's bytes when one of them takes them (``png_decode``: PNG files too)"""
-    return (_jpg_page(path, device_decode) if device_decode else None) or (_png_page(path) if png_decode else None) or _plain_input(path, i)
+def _plain_input_device(path, i=None, device_decode=True, png_decode=False, tiff_decode=False):
+    """``_plain_input`` with the device decoders: the file's bytes when one of them takes them (``png_decode``: PNG files too,
+    ``tiff_decode``: TIFF files too)"""
+    return ((_jpg_page(path, device_decode) if device_decode else None) or (_png_page(path) if png_decode else None)
+            or (_tiff_page(path) if tiff_decode else None) or _plain_input(path, i))
 
 
 @dataclasses.dataclass
@@ -290,6 +304,12 @@ def _png_read(reader, b, kw):
     return reader.readtext_device(rgb, gray, **kw)
 
 
+def _tiff_to_device(reader, b):
+    # ONE decode call for the group, on the context's decode stream outside the call slots, like a "png" group's
+    dev, b.status = reader.decode_tiff_batch(b.host)
+    return dev
+
+
 # The page kinds.  A decoded page is the pair (a, b) of the decode callback's ``(kind, a, b)``; its grouping key is ``_page_key``.  Per kind:
 #   stack(ids, pages) -> Batch           the assembler's step for a group
 #   to_device(reader, batch) -> dev      the upload stage's step: the device payload (it may raise: the batch then travels without one)
@@ -319,6 +339,9 @@ KINDS = {
     # file bytes (PngPage): both planes decoded by the upload stage; a page it could not decode takes the host decode of its bytes
     "png": Kind(stack=lambda ids, pages: Batch("png", ids, host=[p for p, _ in pages]), to_device=_png_to_device, read=_png_read,
                 read_host=None, read_page=_jpg_read_page),
+    # file bytes (TiffPage): the "png" kind's grouping and retry rule
+    "tiff": Kind(stack=lambda ids, pages: Batch("tiff", ids, host=[p for p, _ in pages]), to_device=_tiff_to_device, read=_png_read,
+                 read_host=None, read_page=_jpg_read_page),
 }
 
 
@@ -329,7 +352,8 @@ def _mixed_stack(ids, pages):
 
 def _mixed_to_device(reader, b):
     """Every page of a mixed batch as ``(rgb_dev [H,W,3], gray_dev [H,W] or None)``, by its own kind's upload step -- kept as a list, not
-    stacked.  ``"jpg"`` pages of one decoded shape share one decode call, and so do ``"png"`` pages.  ``status``: non-zero where a page did not reach the card.
+    stacked.  ``"jpg"`` pages of one decoded shape share one decode call, and so do ``"png"`` pages; ``"tiff"`` pages of ANY shapes share one
+    (``bbocr_tiff_decode`` takes a shape per file).  ``status``: non-zero where a page did not reach the card.
     A failure is kept per page, as the reference's failure rule is per page: such a page is read on its own from its host copy
     (``_read_batch``) while the others still share the call.  The price: an upload failure that hits EVERY page (the card out of memory)
     turns the batch into single-page host reads without an error -- slower, same results -- exactly as a failed ``_upload`` does for a
@@ -338,9 +362,12 @@ def _mixed_to_device(reader, b):
 
     n = len(b.ids)
     dev, b.status = [None] * n, [-1] * n
-    jpg, png = {}, {}
+    jpg, png, tiff = {}, {}, []
     for k, (kind, a, g) in enumerate(b.host):
         try:
+            if kind == "tiff":
+                tiff.append(k)
+                continue
             if kind in ("jpg", "png"):
                 (jpg if kind == "jpg" else png).setdefault(a.shape, []).append(k)
                 continue
@@ -368,6 +395,14 @@ def _mixed_to_device(reader, b):
             for j, k in enumerate(ks):
                 if status[j] == 0:
                     dev[k], b.status[k] = (rgb[j], gray[j]), 0
+        except Exception:
+            pass
+    if tiff:
+        try:
+            planes, status = reader.decode_tiff_pages([b.host[k][1] for k in tiff])
+            for j, k in enumerate(tiff):
+                if status[j] == 0:
+                    dev[k], b.status[k] = planes[j], 0
         except Exception:
             pass
     return dev
@@ -534,7 +569,7 @@ def _device_stage(reader, batches, texts, kw):
 
 
 def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, mixed=None,
-               png_decode=None, **readtext_kw):
+               png_decode=None, tiff_decode=None, **readtext_kw):
     """``{index: readtext result}`` for the files ``image_paths[i]``, i in ``indices`` (default: all): the result lists
     ``Reader.readtext(path)`` returns page by page, from 64-page device batches.  A page whose decode or OCR fails maps to ``[]``.
 
@@ -553,15 +588,21 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     batch is read by one ``Reader.readtext_pages`` call; same results, same failure rule.
     ``png_decode`` (None: the Reader's ``png_decode``, off by default): PNG files the device decoder takes (``reader.png_plan``) travel as
     their bytes too, kind ``"png"``, and a group is decoded by one ``bbocr_png_decode`` call (csrc/pngdec.hip, identical pixels); a file
-    the plan refuses (Adam7, 16 bit, APNG, ...) or whose data turns out damaged takes the host decode as before."""
+    the plan refuses (Adam7, 16 bit, APNG, ...) or whose data turns out damaged takes the host decode as before.
+    ``tiff_decode`` (None: the Reader's ``tiff_decode``, off by default): likewise TIFF files the device decoder takes (``reader.tiff_plan``:
+    strips of raw, PackBits, LZW or Deflate data), kind ``"tiff"``, a group decoded by one ``bbocr_tiff_decode`` call (csrc/tiffdec.hip,
+    identical pixels) -- with ``mixed`` the TIFF pages of a batch share one call whatever their shapes; a file the plan refuses (tiles,
+    CCITT, 16 bit, ...) or whose data turns out damaged takes the host decode as before."""
     from .reader import mixed_batch_enabled
 
     mixed = mixed_batch_enabled(mixed)
     png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
+    tiff_decode = bool(getattr(reader, "tiff_decode", False)) if tiff_decode is None else bool(tiff_decode)
     if mixed:
         max_batch = max(1, min(max_batch, int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))))
     if decode is None:
-        decode = (lambda path, i: _plain_input_device(path, i, device_decode, png_decode)) if device_decode or png_decode else _plain_input
+        on_device = device_decode or png_decode or tiff_decode
+        decode = (lambda path, i: _plain_input_device(path, i, device_decode, png_decode, tiff_decode)) if on_device else _plain_input
     if indices is None:
         indices = range(len(image_paths))
     idxs = [i for i in indices if 0 <= i < len(image_paths)]

@@ -283,6 +283,44 @@ def png_decode_enabled(png_decode=None):
     return os.environ.get("BBOCR_PNG_DECODE", "0").strip() == "1" if png_decode is None else bool(png_decode)
 
 
+class TiffPage:
+    """A TIFF file the device decoder takes (``tiff_plan``): its bytes and the shape of its decode, ``(H, W, 3)`` -- every TIFF page has an
+    RGB and a gray plane.  The page kind ``"tiff"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one
+    ``bbocr_tiff_decode`` call, and with ``mixed=True`` so are pages of any shapes."""
+    __slots__ = ("data", "shape", "plan")
+
+    def __init__(self, data, plan):
+        self.data = data
+        self.shape = (int(plan.height), int(plan.width), 3)
+        self.plan = plan
+
+
+def tiff_plan(data):
+    """``bbocr_host_tiff_plan`` of a file's bytes (no GPU): one walk over the header and the first IFD -- geometry, ``bits``, ``samples``,
+    ``photometric``, ``compression``, ``predictor``, the byte order, ``rows_per_strip`` / ``strips``, ``row_bytes``, the strips' stored
+    bytes, ``supported`` and the ``BBOCR_TIFF_*`` reason of a refusal."""
+    plan = _lib.bbocr_tiff_plan()
+    rc = _lib.load().bbocr_host_tiff_plan(data, len(data), C.byref(plan))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_tiff_plan failed with status {rc}")
+    return plan
+
+
+def tiff_page(source):
+    """``TiffPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)"""
+    try:
+        data = _file_bytes(source)
+        plan = tiff_plan(data)
+        return TiffPage(data, plan) if plan.supported else None
+    except Exception:
+        return None
+
+
+def tiff_decode_enabled(tiff_decode=None):
+    """The ``tiff_decode`` keyword: None means the environment variable ``BBOCR_TIFF_DECODE`` (``1`` = on; off when unset)"""
+    return os.environ.get("BBOCR_TIFF_DECODE", "0").strip() == "1" if tiff_decode is None else bool(tiff_decode)
+
+
 def reformat_input(image, device_gray=False, parallel_decode=False):
     """easyocr/utils.py::reformat_input -> (RGB uint8 HWC, gray uint8 HW); decode is host work (PIL).
 
@@ -534,7 +572,7 @@ class Reader:
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
                  rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, character=None,
-                 lang_char=None, beam_wide=None, png_decode=None, **_ignored):
+                 lang_char=None, beam_wide=None, png_decode=None, tiff_decode=None, **_ignored):
         import torch
 
         net = resolve_recog_network(lang_list, recog_network, model_storage_directory, user_network_directory, character, lang_char)
@@ -576,6 +614,8 @@ class Reader:
         # PNG files decoded on the card (csrc/pngdec.hip) by readtext(path) and the file callers; an option of its own (None:
         # BBOCR_PNG_DECODE=1), not a value of device_decode, whose strings are a ladder of JPEG scopes; off unless asked for
         self.png_decode = png_decode_enabled(png_decode)
+        # TIFF files decoded on the card (csrc/tiffdec.hip), likewise an option of its own (None: BBOCR_TIFF_DECODE=1); off unless asked for
+        self.tiff_decode = tiff_decode_enabled(tiff_decode)
         if beam_wide is None:       # decoder='beamsearch' of a model of more than 128 classes searched on the card (csrc/ctc_beam_wide.hip); off unless asked for
             beam_wide = os.environ.get("BBOCR_BEAM_WIDE", "").strip() == "1"
         self.beam_wide = bool(beam_wide)
@@ -1124,6 +1164,77 @@ class Reader:
             return a, st.value
         return (a[:3 * H * W].reshape(H, W, 3), a[3 * H * W:].reshape(H, W)), st.value
 
+    def decode_tiff_batch(self, pages):
+        """``TiffPage`` s of ONE shape -> ``((rgb, gray), status)``: the device tensors ``uint8 [n,H,W,3]`` and ``[n,H,W]`` that ``decode_file``
+        + upload would hold, written by ONE ``bbocr_tiff_decode`` call (only the files' strips cross the link), and the per-file status list
+        (0, or negative: that page of both tensors is undefined).  The files may differ in codec, strips, depth and interpretation."""
+        torch = self._torch
+        pages = list(pages)
+        if not pages or any(p.shape != pages[0].shape for p in pages):
+            raise ValueError("decode_tiff_batch: pages of one decoded shape")
+        H, W, _ = pages[0].shape
+        n = len(pages)
+        rgb = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+        gray = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
+        status = self._tiff_decode_into(pages, [rgb.data_ptr() + k * H * W * 3 for k in range(n)], [W * 3] * n,
+                                        [gray.data_ptr() + k * H * W for k in range(n)], [W] * n)
+        return (rgb, gray), status
+
+    def decode_tiff_pages(self, pages):
+        """``TiffPage`` s of ANY shapes -> ``([(rgb [H,W,3], gray [H,W])], status)``: ONE ``bbocr_tiff_decode`` call for all of them, each
+        page into tensors of its own; a page of non-zero status holds undefined pixels"""
+        torch = self._torch
+        pages = list(pages)
+        if not pages:
+            raise ValueError("decode_tiff_pages: at least one page")
+        out = [(torch.empty(p.shape, dtype=torch.uint8, device=self.device), torch.empty(p.shape[:2], dtype=torch.uint8, device=self.device))
+               for p in pages]
+        status = self._tiff_decode_into(pages, [a.data_ptr() for a, _ in out], [3 * p.shape[1] for p in pages],
+                                        [g.data_ptr() for _, g in out], [p.shape[1] for p in pages])
+        return out, status
+
+    def _tiff_decode_into(self, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches):
+        """``bbocr_tiff_decode`` of the pages into the given device addresses and row pitches -> the per-file status list"""
+        n = len(pages)
+        files, sizes = self._jpeg_files(pages)
+        status = (C.c_int * n)()
+        self._torch.cuda.current_stream(self.device_index).synchronize()      # the library runs on its own stream
+        self._check(self._lib.bbocr_tiff_decode(self._h, files, sizes, n, (C.c_void_p * n)(*rgb_ptrs), (C.c_longlong * n)(*rgb_pitches),
+                                                (C.c_void_p * n)(*gray_ptrs), (C.c_longlong * n)(*gray_pitches), status))
+        return list(status)
+
+    def decode_tiff_device(self, sources):
+        """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them, decoded on the card,
+        or ``None`` for a file the plan refuses or whose data is damaged.  All the files share one decode call."""
+        pages = [tiff_page(s) for s in sources]
+        out = [None] * len(pages)
+        idxs = [i for i, p in enumerate(pages) if p is not None]
+        if idxs:
+            planes, status = self.decode_tiff_pages([pages[i] for i in idxs])
+            for k, i in enumerate(idxs):
+                if status[k] == 0:
+                    out[i] = planes[k]
+        return out
+
+    def tiff_decode_stage(self, source, stage):
+        """``bbocr_op_tiff_decode_stage`` of one file (path or bytes) -> ``(array, file status)``: stage 0 the strips' decoded stream
+        ``uint8 [H * row_bytes]``, 1 the same after the predictor, 2 ``(rgb [H,W,3], gray [H,W])``"""
+        torch = self._torch
+        data = _file_bytes(source)
+        plan = tiff_plan(data)
+        if not plan.supported or stage not in (0, 1, 2):
+            raise ValueError("tiff_decode_stage: a file the plan supports and stage 0, 1 or 2")
+        H, W = int(plan.height), int(plan.width)
+        nb = H * int(plan.row_bytes) if stage < 2 else 4 * H * W
+        out = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        st = C.c_int()
+        torch.cuda.current_stream(self.device_index).synchronize()
+        self._check(self._lib.bbocr_op_tiff_decode_stage(self._h, data, len(data), stage, C.c_void_p(out.data_ptr()), nb, C.byref(st)))
+        a = out.cpu().numpy()
+        if stage < 2:
+            return a, st.value
+        return (a[:3 * H * W].reshape(H, W, 3), a[3 * H * W:].reshape(H, W)), st.value
+
     def deflate_device(self, bytes_dev):
         """A contiguous 1-D uint8 device tensor -> the zlib stream ``bbocr_op_deflate`` makes of it (the PNG writer's chunks, run matches and
         dynamic Huffman codes); ``zlib.decompress`` gives the bytes back."""
@@ -1311,6 +1422,10 @@ class Reader:
                 rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
         if rgb_dev is None and self.png_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
             dev = self.decode_png_device([image])[0]           # None: not a PNG, refused or damaged -> the host decode below, unchanged
+            if dev is not None:
+                rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
+        if rgb_dev is None and self.tiff_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
+            dev = self.decode_tiff_device([image])[0]          # None: not a TIFF, refused or damaged -> the host decode below, unchanged
             if dev is not None:
                 rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
         if rgb_dev is None:

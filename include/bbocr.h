@@ -916,6 +916,72 @@ int bbocr_png_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* 
                      uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
 int bbocr_op_png_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
 
+/* ---- TIFF files decoded on the device (csrc/tiffdec.hip; opt-in: Reader(tiff_decode=True)): what reader.decode_file holds for a TIFF file
+ * -- Pillow's convert("RGB") of frame 0 and the gray plane of its stated rule -- from the file's bytes, of which only the strips cross the
+ * link.  Scope: classic TIFF (II or MM), strips, chunky samples, fill order 1, unsigned samples; compression 1 (none), 32773 (PackBits),
+ * 5 (LZW, MSB-first codes with the early change) and 8 / 32946 (one zlib stream per strip); predictor 1, or 2 on 8-bit samples under LZW
+ * or Deflate (libtiff applies the tag to those codecs only); photometric 0 / 1 with one sample of 1 or 8 bits, 2 with 8,8,8 or with
+ * 8,8,8,8 and ExtraSamples 0 or 2 (the fourth sample dropped), 3 with one 8-bit sample and a ColorMap of 3 x 256 SHORTs, of which a colour
+ * is the HIGH byte (value >> 8: Pillow's rule).  The Orientation tag is not applied (decode_file does not).  Defined by
+ * tests/tiff_decode_ref.py.
+ * bbocr_host_tiff_plan: host only, no GPU: one walk over the header and the first IFD.  Fields the walk did not reach stay 0. */
+enum {
+    BBOCR_TIFF_OK = 0,
+    BBOCR_TIFF_NOT_TIFF = 1,     /* fewer than 8 bytes, no II / MM mark, a magic other than 42 or 43 */
+    BBOCR_TIFF_BIGTIFF = 2,      /* magic 43 */
+    BBOCR_TIFF_TRUNCATED = 3,    /* the IFD, a value or a strip runs past the end of the file */
+    BBOCR_TIFF_HEADER = 4,       /* a required tag is missing, has no value or a type other than BYTE / SHORT / LONG; BitsPerSample does not
+                                  * hold SamplesPerPixel values */
+    BBOCR_TIFF_DIMENSIONS = 5,   /* width or height 0 or above 2^31 - 1, more than 178,956,970 pixels (bbocr_host_png_plan's limit), or a
+                                  * decoded stream height * row_bytes above 2^31 - 1 bytes */
+    BBOCR_TIFF_TILES = 6,        /* any of the tile tags 322 .. 325 */
+    BBOCR_TIFF_PLANAR = 7,       /* PlanarConfiguration other than 1 */
+    BBOCR_TIFF_FILL_ORDER = 8,   /* FillOrder other than 1 */
+    BBOCR_TIFF_DEPTH = 9,        /* 16-bit or wider samples, a SampleFormat other than unsigned integer, samples of unequal or odd depth,
+                                  * 1-bit samples under photometric 2 or 3 */
+    BBOCR_TIFF_SUBBYTE = 10,     /* 2- or 4-bit samples */
+    BBOCR_TIFF_GRAY_ALPHA = 11,  /* photometric 0 / 1 with two samples */
+    BBOCR_TIFF_ASSOC_ALPHA = 12, /* ExtraSamples 1: premultiplied alpha */
+    BBOCR_TIFF_PHOTOMETRIC = 13, /* CMYK, YCbCr, CIELab and every other interpretation above 3 */
+    BBOCR_TIFF_SAMPLES = 14,     /* a sample count the interpretation does not allow; four samples without one ExtraSamples value of 0 or 2 */
+    BBOCR_TIFF_JPEG = 15,        /* compression 6 or 7 */
+    BBOCR_TIFF_CCITT = 16,       /* compression 2, 3 or 4 */
+    BBOCR_TIFF_COMPRESSION = 17, /* any other compression */
+    BBOCR_TIFF_PREDICTOR = 18,   /* predictor 3 or unknown; predictor 2 on 1-bit samples or under a codec for which libtiff ignores the tag */
+    BBOCR_TIFF_OLD_LZW = 19,     /* old-style LZW: the first strip starts 00 followed by an odd byte (libtiff's test) */
+    BBOCR_TIFF_STRIPS = 20,      /* no strip table, RowsPerStrip 0, or tables whose length is not ceil(height / rows_per_strip) */
+    BBOCR_TIFF_PALETTE = 21      /* photometric 3 without a ColorMap of 3 x 256 SHORTs */
+};
+typedef struct bbocr_tiff_plan {
+    int width, height, bits, samples, photometric, compression, predictor;
+    int big_endian;             /* the byte order: 0 "II", 1 "MM" */
+    long long rows_per_strip;   /* as used: min(RowsPerStrip, height); the tag absent counts as 2^32 - 1 */
+    int strips;                 /* ceil(height / rows_per_strip) */
+    int extra_sample;           /* the ExtraSamples value of a four-sample file, else -1 */
+    long long row_bytes;        /* ceil(width * samples * bits / 8) */
+    long long strip_bytes;      /* the strips' stored bytes together: what crosses the link */
+    int supported;              /* 1: bbocr_tiff_decode takes the file */
+    int reason;                 /* BBOCR_TIFF_* */
+    int reserved[2];
+} bbocr_tiff_plan;
+int bbocr_host_tiff_plan(const void* file, size_t bytes, bbocr_tiff_plan* plan);
+/* n files (HOST bytes) -> both planes in DEVICE memory, one call per batch whatever mix of codecs and shapes it holds: dst_rgb[k] receives
+ * uint8 [H,W,3], rows pitch_rgb[k] bytes apart, dst_gray[k] uint8 [H,W], rows pitch_gray[k] bytes apart -- one shape per file.  RGB:
+ * Pillow's convert("RGB") (a gray sample replicated, 1-bit samples 0 / 255, photometric 0 inverted, the palette looked up, a fourth sample
+ * dropped).  Gray: the stored (inverted) sample for photometric 0 / 1, else (9797 R + 19234 G + 3737 B) >> 15.
+ * status[k]: 0, BBOCR_ERR_ARG (a null pointer, a pitch shorter than a row, a file the plan refuses) or BBOCR_ERR_DATA: a strip is damaged
+ * -- it runs out of input before it has produced rows_in_strip * row_bytes bytes, a run or a string would write beyond that count, an LZW
+ * strip does not begin with a Clear code, uses a code above the next free entry or follows a Clear with a code that is no literal, a
+ * Deflate strip fails one of bbocr_png_decode's checks (zlib header, stream, Adler-32).  Such a file's destinations are undefined; no byte
+ * outside a destination's rows is ever written, the other files decode all the same and the context stays usable.  Stream,
+ * one-batch-at-a-time contract and work buffers: bbocr_jpeg_decode's.  Returns with its work finished, also when it fails.
+ * bbocr_op_tiff_decode_stage: the intermediates of ONE file in DEVICE memory dev_dst[dst_bytes] (parity tests), by the kernels the full
+ * call runs: stage 0 = the strips' decoded stream, height * row_bytes bytes (only the strip launch runs); 1 = the same after the predictor;
+ * 2 = RGB [H,W,3] followed by gray [H,W], tight.  *file_status as status[k] above, of the stages that ran. */
+int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                      uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
+int bbocr_op_tiff_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
+
 #ifdef __cplusplus
 }
 #endif
