@@ -283,6 +283,39 @@ PROTOTYPES = {
     "bbocr_op_tiff_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
 }
 
+class bbocr_gif_plan(C.Structure):
+    _fields_ = [("screen_w", C.c_int), ("screen_h", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("canvas_w", C.c_int), ("canvas_h", C.c_int), ("interlace", C.c_int), ("table_len", C.c_int), ("local_table", C.c_int),
+                ("transparency", C.c_int), ("min_code", C.c_int), ("mode_l", C.c_int), ("payload_bytes", C.c_longlong), ("supported", C.c_int),
+                ("reason", C.c_int), ("reserved", C.c_int * 2), ("table", C.c_uint8 * 768)]
+
+
+# bbocr.h BBOCR_GIF_*: why bbocr_host_gif_plan refuses a file
+(GIF_OK, GIF_NOT_GIF, GIF_TRUNCATED, GIF_NO_IMAGE, GIF_EMPTY, GIF_PIXELS, GIF_CODE_SIZE) = range(7)
+
+class bbocr_bmp_plan(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bits", C.c_int), ("compression", C.c_int), ("header_size", C.c_int),
+                ("top_down", C.c_int), ("colors", C.c_int), ("mode", C.c_int), ("r_at", C.c_int), ("g_at", C.c_int), ("b_at", C.c_int),
+                ("six_bit_green", C.c_int), ("table_offset", C.c_longlong), ("table_entry", C.c_int), ("supported", C.c_int),
+                ("row_stride", C.c_longlong), ("data_offset", C.c_longlong), ("reason", C.c_int), ("reserved", C.c_int * 3)]
+
+
+# bbocr.h BBOCR_BMP_*: why bbocr_host_bmp_plan refuses a file
+(BMP_OK, BMP_NOT_BMP, BMP_TRUNCATED, BMP_HEADER, BMP_DIMENSIONS, BMP_PIXELS, BMP_DEPTH, BMP_RLE, BMP_COMPRESSION, BMP_MASKS, BMP_PALETTE,
+ BMP_GRAY_TABLE) = range(12)
+
+_FILE_DECODE = (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                          C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_int)])
+PROTOTYPES.update({
+    "bbocr_host_gif_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_gif_plan)]),
+    "bbocr_gif_decode": _FILE_DECODE,
+    "bbocr_gif_decode_timed": (_FILE_DECODE[0], _FILE_DECODE[1] + [C.POINTER(C.c_float)]),
+    "bbocr_op_gif_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_gif_piece_room": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "bbocr_host_bmp_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_bmp_plan)]),
+    "bbocr_bmp_decode": _FILE_DECODE,
+})
+
 _lib = None
 
 

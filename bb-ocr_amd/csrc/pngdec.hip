@@ -7,15 +7,11 @@
 //   pd_output    fully parallel: both planes by reader.decode_file's rule.
 // A file whose status word is not 0 is skipped by the later stages; no stage writes outside the file's scratch or its destinations' rows.
 #include "pngdec.h"
+#include "wave_copy.h"
 
 namespace {
 
 constexpr int kWave = 64;
-
-__device__ inline void drain_and_sync() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's stores are out before the barrier's fence lets the others load
-    __syncthreads();
-}
 
 struct PngiWave {                                         // a workgroup of ONE wavefront
     __device__ static bool leader() { return threadIdx.x == 0; }

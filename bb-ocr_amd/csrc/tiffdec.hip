@@ -13,34 +13,13 @@
 // A strip writes its own status word and ORs it into its file's; a file whose word is not 0 is skipped by the later launches.  No launch
 // writes outside the file's stream or its destinations' rows.
 #include "tiffdec.h"
+#include "wave_copy.h"
 
 namespace {
 
 constexpr int kWave = 64;
 
-__device__ inline void drain_and_sync() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's stores are out before the barrier's fence lets the others load
-    __syncthreads();
-}
-
-struct TiffcWave {                                        // a workgroup of ONE wavefront
-    __device__ static void copy_in(uint8_t* out, size_t o, const uint8_t* in, size_t n) {
-        for (size_t i = threadIdx.x; i < n; i += kWave) out[o + i] = in[i];
-    }
-    __device__ static void fill(uint8_t* out, size_t o, uint8_t v, size_t n) {
-        for (size_t i = threadIdx.x; i < n; i += kWave) out[o + i] = v;
-    }
-    // `synced`: the output up to there was stored before the last drain; only a string that reaches behind it waits for the stores again
-    __device__ static void copy_back(uint8_t* out, size_t o, uint32_t src, uint32_t len, bool kwkwk, size_t& synced) {
-        const uint32_t whole = kwkwk ? len - 1 : len;     // these bytes stand before o
-        if ((size_t)src + whole > synced) {
-            drain_and_sync();
-            synced = o;
-        }
-        for (uint32_t i = threadIdx.x; i < whole; i += kWave) out[o + i] = out[src + i];
-        if (kwkwk && threadIdx.x == 0) out[o + whole] = out[src];          // the entry being defined: its last byte is its first
-    }
-};
+using TiffcWave = WaveCopy;                               // a workgroup of ONE wavefront: wave_copy.h's output policy
 
 struct PngiWaveT {                                        // pngdec.hip's policy for pngi_inflate
     __device__ static bool leader() { return threadIdx.x == 0; }

@@ -50,6 +50,22 @@ def _tiff_page(source):
     return None if page is None else ("tiff", page, None)
 
 
+def _gif_page(source):
+    """``("gif", GifPage, None)`` when the device GIF decoder takes the file (a path or its bytes), else None"""
+    from .reader import gif_page
+
+    page = gif_page(source)
+    return None if page is None else ("gif", page, None)
+
+
+def _bmp_page(source):
+    """``("bmp", BmpPage, None)`` when the device BMP decoder takes the file (a path or its bytes), else None"""
+    from .reader import bmp_page
+
+    page = bmp_page(source)
+    return None if page is None else ("bmp", page, None)
+
+
 def _host_page(source, decode_once=True):
     """The host decode of a file (a path or its bytes) as a page: ``("ycc", triples, None)`` when it is a YCbCr-coded JPEG and
     ``decode_once`` (decoded once, RGB + Y plane derived on the card: reader.decode_file_ycc), else ``("rgb", rgb, gray)``."""
@@ -76,7 +92,7 @@ def _thumbnail_jpeg(size, image_index, load_rgb):
     return buf.getvalue()
 
 
-def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False, png_decode=False, tiff_decode=False):
+def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=False, png_decode=False, tiff_decode=False, gif_decode=False, bmp_decode=False):
     """``ocr_input_image`` for the batching loop: ``("ycc", triples, None)`` when the file easyocr would be given is a YCbCr-coded JPEG
     (``_host_page``) -- every thumbnail is, it is written as one -- else ``("rgb", rgb, gray)``.  ``device_decode``: the file easyocr
     would be given travels as its bytes (``("jpg", JpegPage, None)``) when the device decoder takes it -- the original at or below the
@@ -94,6 +110,10 @@ def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=Fal
         page = _png_page(source)
     if page is None and tiff_decode and source is image_path:      # likewise a TIFF file
         page = _tiff_page(source)
+    if page is None and gif_decode and source is image_path:       # likewise a GIF file
+        page = _gif_page(source)
+    if page is None and bmp_decode and source is image_path:       # likewise a BMP file
+        page = _bmp_page(source)
     return page if page is not None else _host_page(source, decode_once)
 
 
@@ -200,7 +220,7 @@ def ocr_input_image(image_path, image_index=None):
 
 def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, decode_workers=None, decode_once=True, use_preprocessing=False,
                   edge_crop_percent=0.0, crop_for_ocr=False, crop_margin=128, device_thumbnail=False, device_decode=False, mixed=None,
-                  png_decode=None, tiff_decode=None, **readtext_kw):
+                  png_decode=None, tiff_decode=None, gif_decode=None, bmp_decode=None, **readtext_kw):
     """``{index: text}`` for every index of ``ocr_image_indices`` (default: all pages), text = ``" ".join(r[1] for r in results)``
     exactly as :521; a page whose OCR fails gets ``""`` like :529-531.  Pages of equal (down-scaled) shape travel in one device
     batch of at most ``max_batch`` pages (``read_files`` with the reference's OCR-input rule as the decode step).
@@ -216,11 +236,15 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches.
     ``png_decode`` (None: the Reader's ``png_decode``): a PNG file at or below its page's limit that the device PNG decoder takes reaches
     the card as its bytes (kind ``"png"``); with the crop settings or ``device_thumbnail`` on, and above the limit, a PNG keeps today's path.
-    ``tiff_decode`` (None: the Reader's ``tiff_decode``): the same for a TIFF file the device TIFF decoder takes (kind ``"tiff"``)."""
+    ``tiff_decode`` (None: the Reader's ``tiff_decode``): the same for a TIFF file the device TIFF decoder takes (kind ``"tiff"``).
+    ``gif_decode`` (None: the Reader's ``gif_decode``): the same for a GIF file the device GIF decoder takes (kind ``"gif"``).
+    ``bmp_decode`` (None: the Reader's ``bmp_decode``): the same for a BMP file the device BMP decoder takes (kind ``"bmp"``)."""
     from .preprocess import ocr_input_device
 
     png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
     tiff_decode = bool(getattr(reader, "tiff_decode", False)) if tiff_decode is None else bool(tiff_decode)
+    gif_decode = bool(getattr(reader, "gif_decode", False)) if gif_decode is None else bool(gif_decode)
+    bmp_decode = bool(getattr(reader, "bmp_decode", False)) if bmp_decode is None else bool(bmp_decode)
 
     if use_preprocessing or edge_crop_percent > 0.0 or crop_for_ocr:
         if crop_margin < 0:
@@ -235,7 +259,7 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     elif device_thumbnail:
         decode = lambda path, i: _ocr_input_device(reader, path, i, decode_once, device_decode)
     else:
-        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode, png_decode, tiff_decode)
+        decode = lambda path, i: _ocr_input(path, i, decode_once, device_decode, png_decode, tiff_decode, gif_decode, bmp_decode)
     res = read_files(reader, image_paths, ocr_image_indices, max_batch, decode_workers, decode=decode, mixed=mixed, **readtext_kw)
     return {i: " ".join(t[1] for t in r) for i, r in res.items()}
 
@@ -245,11 +269,12 @@ def _plain_input(path, i=None):
     return _host_page(path)
 
 
-def _plain_input_device(path, i=None, device_decode=True, png_decode=False, tiff_decode=False):
+def _plain_input_device(path, i=None, device_decode=True, png_decode=False, tiff_decode=False, gif_decode=False, bmp_decode=False):
     """``_plain_input`` with the device decoders: the file's bytes when one of them takes them (``png_decode``: PNG files too,
-    ``tiff_decode``: TIFF files too)"""
+    ``tiff_decode``: TIFF files too, ``gif_decode``: GIF files too, ``bmp_decode``: BMP files too)"""
     return ((_jpg_page(path, device_decode) if device_decode else None) or (_png_page(path) if png_decode else None)
-            or (_tiff_page(path) if tiff_decode else None) or _plain_input(path, i))
+            or (_tiff_page(path) if tiff_decode else None) or (_gif_page(path) if gif_decode else None)
+            or (_bmp_page(path) if bmp_decode else None) or _plain_input(path, i))
 
 
 @dataclasses.dataclass
@@ -310,6 +335,20 @@ def _tiff_to_device(reader, b):
     return dev
 
 
+def _pages_to_device(decode_pages):
+    """the upload step of a kind whose decode call takes a shape per file (``decode_gif_pages``): ONE call for the group, its planes stacked"""
+    def to_device(reader, b):
+        import torch
+
+        planes, b.status = getattr(reader, decode_pages)(b.host)
+        rgb, gray = torch.stack([a for a, _ in planes]), torch.stack([g for _, g in planes])
+        if rgb.is_cuda:
+            torch.cuda.current_stream(rgb.device).synchronize()   # the library runs on its own stream
+        return rgb, gray
+
+    return to_device
+
+
 # The page kinds.  A decoded page is the pair (a, b) of the decode callback's ``(kind, a, b)``; its grouping key is ``_page_key``.  Per kind:
 #   stack(ids, pages) -> Batch           the assembler's step for a group
 #   to_device(reader, batch) -> dev      the upload stage's step: the device payload (it may raise: the batch then travels without one)
@@ -342,7 +381,16 @@ KINDS = {
     # file bytes (TiffPage): the "png" kind's grouping and retry rule
     "tiff": Kind(stack=lambda ids, pages: Batch("tiff", ids, host=[p for p, _ in pages]), to_device=_tiff_to_device, read=_png_read,
                  read_host=None, read_page=_jpg_read_page),
+    # file bytes (GifPage): likewise; the decode call takes a shape per file, the group's planes are stacked behind it
+    "gif": Kind(stack=lambda ids, pages: Batch("gif", ids, host=[p for p, _ in pages]), to_device=_pages_to_device("decode_gif_pages"),
+                read=_png_read, read_host=None, read_page=_jpg_read_page),
+    # file bytes (BmpPage): likewise
+    "bmp": Kind(stack=lambda ids, pages: Batch("bmp", ids, host=[p for p, _ in pages]), to_device=_pages_to_device("decode_bmp_pages"),
+                read=_png_read, read_host=None, read_page=_jpg_read_page),
 }
+
+# kinds of a mixed batch whose pages of ANY shapes share one decode call: kind -> the Reader's method
+_PAGES_CALL = {"tiff": "decode_tiff_pages", "gif": "decode_gif_pages", "bmp": "decode_bmp_pages"}
 
 
 def _mixed_stack(ids, pages):
@@ -353,7 +401,7 @@ def _mixed_stack(ids, pages):
 def _mixed_to_device(reader, b):
     """Every page of a mixed batch as ``(rgb_dev [H,W,3], gray_dev [H,W] or None)``, by its own kind's upload step -- kept as a list, not
     stacked.  ``"jpg"`` pages of one decoded shape share one decode call, and so do ``"png"`` pages; ``"tiff"`` pages of ANY shapes share one
-    (``bbocr_tiff_decode`` takes a shape per file).  ``status``: non-zero where a page did not reach the card.
+    (``bbocr_tiff_decode`` takes a shape per file), and so do ``"gif"`` and ``"bmp"`` pages (``_PAGES_CALL``).  ``status``: non-zero where a page did not reach the card.
     A failure is kept per page, as the reference's failure rule is per page: such a page is read on its own from its host copy
     (``_read_batch``) while the others still share the call.  The price: an upload failure that hits EVERY page (the card out of memory)
     turns the batch into single-page host reads without an error -- slower, same results -- exactly as a failed ``_upload`` does for a
@@ -362,11 +410,11 @@ def _mixed_to_device(reader, b):
 
     n = len(b.ids)
     dev, b.status = [None] * n, [-1] * n
-    jpg, png, tiff = {}, {}, []
+    jpg, png, any_shape = {}, {}, {}
     for k, (kind, a, g) in enumerate(b.host):
         try:
-            if kind == "tiff":
-                tiff.append(k)
+            if kind in _PAGES_CALL:
+                any_shape.setdefault(kind, []).append(k)
                 continue
             if kind in ("jpg", "png"):
                 (jpg if kind == "jpg" else png).setdefault(a.shape, []).append(k)
@@ -397,10 +445,10 @@ def _mixed_to_device(reader, b):
                     dev[k], b.status[k] = (rgb[j], gray[j]), 0
         except Exception:
             pass
-    if tiff:
+    for kind, ks in any_shape.items():
         try:
-            planes, status = reader.decode_tiff_pages([b.host[k][1] for k in tiff])
-            for j, k in enumerate(tiff):
+            planes, status = getattr(reader, _PAGES_CALL[kind])([b.host[k][1] for k in ks])
+            for j, k in enumerate(ks):
                 if status[j] == 0:
                     dev[k], b.status[k] = planes[j], 0
         except Exception:
@@ -569,7 +617,7 @@ def _device_stage(reader, batches, texts, kw):
 
 
 def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=None, decode=None, device_decode=False, mixed=None,
-               png_decode=None, tiff_decode=None, **readtext_kw):
+               png_decode=None, tiff_decode=None, gif_decode=None, bmp_decode=None, **readtext_kw):
     """``{index: readtext result}`` for the files ``image_paths[i]``, i in ``indices`` (default: all): the result lists
     ``Reader.readtext(path)`` returns page by page, from 64-page device batches.  A page whose decode or OCR fails maps to ``[]``.
 
@@ -592,17 +640,26 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     ``tiff_decode`` (None: the Reader's ``tiff_decode``, off by default): likewise TIFF files the device decoder takes (``reader.tiff_plan``:
     strips of raw, PackBits, LZW or Deflate data), kind ``"tiff"``, a group decoded by one ``bbocr_tiff_decode`` call (csrc/tiffdec.hip,
     identical pixels) -- with ``mixed`` the TIFF pages of a batch share one call whatever their shapes; a file the plan refuses (tiles,
-    CCITT, 16 bit, ...) or whose data turns out damaged takes the host decode as before."""
+    CCITT, 16 bit, ...) or whose data turns out damaged takes the host decode as before.
+    ``gif_decode`` (None: the Reader's ``gif_decode``, off by default): likewise GIF files (``reader.gif_plan``), kind ``"gif"``: the group --
+    with ``mixed`` every GIF page of the batch, whatever its shape -- is decoded by one ``bbocr_gif_decode`` call (csrc/gifdec.hip, identical
+    pixels); a file the plan refuses or whose code stream turns out damaged takes the host decode as before.
+    ``bmp_decode`` (None: the Reader's ``bmp_decode``, off by default): likewise BMP files (``reader.bmp_plan``), kind ``"bmp"``, one
+    ``bbocr_bmp_decode`` call -- one launch -- per group (csrc/bmpdec.hip, identical pixels); a file the plan refuses (RLE, ...) takes the
+    host decode as before."""
     from .reader import mixed_batch_enabled
 
     mixed = mixed_batch_enabled(mixed)
     png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
     tiff_decode = bool(getattr(reader, "tiff_decode", False)) if tiff_decode is None else bool(tiff_decode)
+    gif_decode = bool(getattr(reader, "gif_decode", False)) if gif_decode is None else bool(gif_decode)
+    bmp_decode = bool(getattr(reader, "bmp_decode", False)) if bmp_decode is None else bool(bmp_decode)
     if mixed:
         max_batch = max(1, min(max_batch, int(os.environ.get("BBOCR_MAX_DEVICE_BATCH", "64"))))
     if decode is None:
-        on_device = device_decode or png_decode or tiff_decode
-        decode = (lambda path, i: _plain_input_device(path, i, device_decode, png_decode, tiff_decode)) if on_device else _plain_input
+        on_device = device_decode or png_decode or tiff_decode or gif_decode or bmp_decode
+        decode = ((lambda path, i: _plain_input_device(path, i, device_decode, png_decode, tiff_decode, gif_decode, bmp_decode)) if on_device
+                  else _plain_input)
     if indices is None:
         indices = range(len(image_paths))
     idxs = [i for i in indices if 0 <= i < len(image_paths)]

@@ -321,6 +321,81 @@ def tiff_decode_enabled(tiff_decode=None):
     return os.environ.get("BBOCR_TIFF_DECODE", "0").strip() == "1" if tiff_decode is None else bool(tiff_decode)
 
 
+class GifPage:
+    """A GIF file the device decoder takes (``gif_plan``): its bytes and the shape of its decode, ``(canvas_h, canvas_w, 3)`` -- Pillow's
+    frame 0 on its canvas.  The page kind ``"gif"`` of ``extractor_batch.read_files``: pages of any shapes share one ``bbocr_gif_decode``
+    call."""
+    __slots__ = ("data", "shape", "plan")
+
+    def __init__(self, data, plan):
+        self.data = data
+        self.shape = (int(plan.canvas_h), int(plan.canvas_w), 3)
+        self.plan = plan
+
+
+def gif_plan(data):
+    """``bbocr_host_gif_plan`` of a file's bytes (no GPU): one walk up to the end of frame 0's data -- the screen, the frame rectangle, the
+    canvas, ``interlace``, the table in force (``table_len``, ``local_table``, ``table``: the RGB plane's lookup), ``transparency``,
+    ``min_code``, ``mode_l``, ``payload_bytes``, ``supported`` and the ``BBOCR_GIF_*`` reason of a refusal."""
+    plan = _lib.bbocr_gif_plan()
+    rc = _lib.load().bbocr_host_gif_plan(data, len(data), C.byref(plan))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_gif_plan failed with status {rc}")
+    return plan
+
+
+def gif_page(source):
+    """``GifPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)"""
+    try:
+        data = _file_bytes(source)
+        plan = gif_plan(data)
+        return GifPage(data, plan) if plan.supported else None
+    except Exception:
+        return None
+
+
+def gif_decode_enabled(gif_decode=None):
+    """The ``gif_decode`` keyword: None means the environment variable ``BBOCR_GIF_DECODE`` (``1`` = on; off when unset)"""
+    return os.environ.get("BBOCR_GIF_DECODE", "0").strip() == "1" if gif_decode is None else bool(gif_decode)
+
+
+class BmpPage:
+    """A BMP file the device decoder takes (``bmp_plan``): its bytes and the shape of its decode, ``(H, W, 3)``.  The page kind ``"bmp"`` of
+    ``extractor_batch.read_files``: pages of any shapes share one ``bbocr_bmp_decode`` call."""
+    __slots__ = ("data", "shape", "plan")
+
+    def __init__(self, data, plan):
+        self.data = data
+        self.shape = (int(plan.height), int(plan.width), 3)
+        self.plan = plan
+
+
+def bmp_plan(data):
+    """``bbocr_host_bmp_plan`` of a file's bytes (no GPU): Pillow's ``_bitmap`` restated -- geometry, ``bits``, ``compression``,
+    ``header_size``, ``top_down``, the table (``colors``, ``table_offset``, ``table_entry``), ``mode`` (0 P, 1 Pillow's 1, 2 L, 3 direct
+    colour), the bytes of R, G and B, ``row_stride``, ``data_offset``, ``supported`` and the ``BBOCR_BMP_*`` reason of a refusal."""
+    plan = _lib.bbocr_bmp_plan()
+    rc = _lib.load().bbocr_host_bmp_plan(data, len(data), C.byref(plan))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_bmp_plan failed with status {rc}")
+    return plan
+
+
+def bmp_page(source):
+    """``BmpPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)"""
+    try:
+        data = _file_bytes(source)
+        plan = bmp_plan(data)
+        return BmpPage(data, plan) if plan.supported else None
+    except Exception:
+        return None
+
+
+def bmp_decode_enabled(bmp_decode=None):
+    """The ``bmp_decode`` keyword: None means the environment variable ``BBOCR_BMP_DECODE`` (``1`` = on; off when unset)"""
+    return os.environ.get("BBOCR_BMP_DECODE", "0").strip() == "1" if bmp_decode is None else bool(bmp_decode)
+
+
 def reformat_input(image, device_gray=False, parallel_decode=False):
     """easyocr/utils.py::reformat_input -> (RGB uint8 HWC, gray uint8 HW); decode is host work (PIL).
 
@@ -572,7 +647,7 @@ class Reader:
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
                  rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, character=None,
-                 lang_char=None, beam_wide=None, png_decode=None, tiff_decode=None, **_ignored):
+                 lang_char=None, beam_wide=None, png_decode=None, tiff_decode=None, gif_decode=None, bmp_decode=None, **_ignored):
         import torch
 
         net = resolve_recog_network(lang_list, recog_network, model_storage_directory, user_network_directory, character, lang_char)
@@ -616,6 +691,10 @@ class Reader:
         self.png_decode = png_decode_enabled(png_decode)
         # TIFF files decoded on the card (csrc/tiffdec.hip), likewise an option of its own (None: BBOCR_TIFF_DECODE=1); off unless asked for
         self.tiff_decode = tiff_decode_enabled(tiff_decode)
+        # GIF files decoded on the card (csrc/gifdec.hip), likewise (None: BBOCR_GIF_DECODE=1); off unless asked for
+        self.gif_decode = gif_decode_enabled(gif_decode)
+        # BMP files decoded on the card (csrc/bmpdec.hip), likewise (None: BBOCR_BMP_DECODE=1); off unless asked for
+        self.bmp_decode = bmp_decode_enabled(bmp_decode)
         if beam_wide is None:       # decoder='beamsearch' of a model of more than 128 classes searched on the card (csrc/ctc_beam_wide.hip); off unless asked for
             beam_wide = os.environ.get("BBOCR_BEAM_WIDE", "").strip() == "1"
         self.beam_wide = bool(beam_wide)
@@ -1235,6 +1314,92 @@ class Reader:
             return a, st.value
         return (a[:3 * H * W].reshape(H, W, 3), a[3 * H * W:].reshape(H, W)), st.value
 
+    def _decode_pages_into(self, call, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches):
+        """``call`` (``bbocr_gif_decode``'s signature) of the pages into the given device addresses and row pitches -> the per-file status list"""
+        n = len(pages)
+        files, sizes = self._jpeg_files(pages)
+        status = (C.c_int * n)()
+        self._torch.cuda.current_stream(self.device_index).synchronize()      # the library runs on its own stream
+        self._check(call(self._h, files, sizes, n, (C.c_void_p * n)(*rgb_ptrs), (C.c_longlong * n)(*rgb_pitches), (C.c_void_p * n)(*gray_ptrs),
+                         (C.c_longlong * n)(*gray_pitches), status))
+        return list(status)
+
+    def _decode_pages(self, into, pages, name):
+        torch = self._torch
+        pages = list(pages)
+        if not pages:
+            raise ValueError(f"{name}: at least one page")
+        out = [(torch.empty(p.shape, dtype=torch.uint8, device=self.device), torch.empty(p.shape[:2], dtype=torch.uint8, device=self.device))
+               for p in pages]
+        status = into(pages, [a.data_ptr() for a, _ in out], [3 * p.shape[1] for p in pages], [g.data_ptr() for _, g in out],
+                      [p.shape[1] for p in pages])
+        return out, status
+
+    def _decode_sources(self, page_of, decode_pages, sources):
+        pages = [page_of(s) for s in sources]
+        out = [None] * len(pages)
+        idxs = [i for i, p in enumerate(pages) if p is not None]
+        if idxs:
+            planes, status = decode_pages([pages[i] for i in idxs])
+            for k, i in enumerate(idxs):
+                if status[k] == 0:
+                    out[i] = planes[k]
+        return out
+
+    def _gif_decode_into(self, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches):
+        """``bbocr_gif_decode`` of the pages into the given device addresses and row pitches -> the per-file status list"""
+        return self._decode_pages_into(self._lib.bbocr_gif_decode, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches)
+
+    def decode_gif_pages(self, pages):
+        """``GifPage`` s of ANY shapes -> ``([(rgb [H,W,3], gray [H,W])], status)``: ONE ``bbocr_gif_decode`` call for all of them (only the
+        files' LZW payloads and tables cross the link), each page into tensors of its own; a page of non-zero status holds undefined pixels"""
+        return self._decode_pages(self._gif_decode_into, pages, "decode_gif_pages")
+
+    def decode_gif_device(self, sources):
+        """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them, decoded on the card,
+        or ``None`` for a file the plan refuses or whose data is damaged.  All the files share one decode call."""
+        return self._decode_sources(gif_page, self.decode_gif_pages, sources)
+
+    def _bmp_decode_into(self, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches):
+        """``bbocr_bmp_decode`` of the pages into the given device addresses and row pitches -> the per-file status list"""
+        return self._decode_pages_into(self._lib.bbocr_bmp_decode, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches)
+
+    def decode_bmp_pages(self, pages):
+        """``BmpPage`` s of ANY shapes -> ``([(rgb [H,W,3], gray [H,W])], status)``: ONE ``bbocr_bmp_decode`` call -- one launch -- for all of
+        them, each page into tensors of its own; a page of non-zero status (an argument error) holds undefined pixels"""
+        return self._decode_pages(self._bmp_decode_into, pages, "decode_bmp_pages")
+
+    def decode_bmp_device(self, sources):
+        """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them, decoded on the card,
+        or ``None`` for a file the plan refuses.  All the files share one decode call."""
+        return self._decode_sources(bmp_page, self.decode_bmp_pages, sources)
+
+    def gif_decode_stage(self, source, stage):
+        """``bbocr_op_gif_decode_stage`` of one file (path or bytes) -> ``(bytes, file status)``: stage 0 the piece table (a 16-byte head --
+        count, the scan's error bits -- and 16 bytes per piece: first bit low / high, data codes, end), 1 ``uint32`` offsets per piece and
+        the total, 2 the index stream in stored row order, ``width * height`` bytes"""
+        torch = self._torch
+        data = _file_bytes(source)
+        plan = gif_plan(data)
+        if not plan.supported or stage not in (0, 1, 2):
+            raise ValueError("gif_decode_stage: a file the plan supports and stage 0, 1 or 2")
+        room = int(self._lib.bbocr_gif_piece_room(int(plan.payload_bytes), int(plan.min_code)))
+        st = C.c_int()
+
+        def run(stage, nb):
+            out = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            torch.cuda.current_stream(self.device_index).synchronize()
+            self._check(self._lib.bbocr_op_gif_decode_stage(self._h, data, len(data), stage, C.c_void_p(out.data_ptr()), nb, C.byref(st)))
+            return out.cpu().numpy()
+
+        if stage == 2:
+            return run(2, int(plan.width) * int(plan.height)).tobytes(), st.value
+        head = run(0, 16 + 16 * room)
+        count = int(head[:4].view(np.uint32)[0])
+        if stage == 0:
+            return head[:16 + 16 * count].tobytes(), st.value
+        return run(1, 4 * (room + 1))[:4 * (count + 1)].tobytes(), st.value
+
     def deflate_device(self, bytes_dev):
         """A contiguous 1-D uint8 device tensor -> the zlib stream ``bbocr_op_deflate`` makes of it (the PNG writer's chunks, run matches and
         dynamic Huffman codes); ``zlib.decompress`` gives the bytes back."""
@@ -1426,6 +1591,14 @@ class Reader:
                 rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
         if rgb_dev is None and self.tiff_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
             dev = self.decode_tiff_device([image])[0]          # None: not a TIFF, refused or damaged -> the host decode below, unchanged
+            if dev is not None:
+                rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
+        if rgb_dev is None and self.gif_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
+            dev = self.decode_gif_device([image])[0]           # None: not a GIF, refused or damaged -> the host decode below, unchanged
+            if dev is not None:
+                rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
+        if rgb_dev is None and self.bmp_decode and isinstance(image, (str, os.PathLike, bytes, bytearray)):
+            dev = self.decode_bmp_device([image])[0]           # None: not a BMP or refused -> the host decode below, unchanged
             if dev is not None:
                 rgb_dev, gray_dev = dev[0][None], (None if isinstance(image, (bytes, bytearray)) else dev[1][None])
         if rgb_dev is None:

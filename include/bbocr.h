@@ -982,6 +982,117 @@ int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
                       uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
 int bbocr_op_tiff_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
 
+/* ---- GIF files decoded on the device (csrc/gifdec.hip; opt-in: Reader(gif_decode=True)): what reader.decode_file holds for a GIF file
+ * -- Pillow's convert("RGB") of frame 0 and the gray plane of its stated rule -- from the file's bytes, of which only the de-framed LZW
+ * payload and the colour table cross the link.  The code stream is split at its clear codes: the width of a GIF code depends only on the
+ * count of codes since the last clear, so the position of every code behind a clear is a closed form, a wavefront finds the next clear 64
+ * codes at a time, and every piece between two clears is decoded by a wavefront of its own (csrc/gif_lzw.h).  Defined by
+ * tests/gif_decode_ref.py, which also lists Pillow's rules as restated and the classes that are stricter than Pillow.
+ * bbocr_host_gif_plan: host only, no GPU: the signature, the screen descriptor, the global table, the extensions up to the first image
+ * descriptor (a graphic control extension's transparency index is read, every other extension skipped), the descriptor, the local table,
+ * the minimum code size and the data sub-blocks.  Later frames are not read.  Fields the walk did not reach stay 0 (transparency: -1). */
+enum {
+    BBOCR_GIF_OK = 0,
+    BBOCR_GIF_NOT_GIF = 1,      /* no "GIF87a" / "GIF89a" signature */
+    BBOCR_GIF_TRUNCATED = 2,    /* the file ends inside the structure, the data sub-blocks have no terminator, a block introducer before the
+                                 * image is none of 21 / 2C / 3B, or a graphic control block is shorter than four bytes */
+    BBOCR_GIF_NO_IMAGE = 3,     /* the trailer comes before any image descriptor */
+    BBOCR_GIF_EMPTY = 4,        /* a frame of width or height 0 */
+    BBOCR_GIF_PIXELS = 5,       /* a canvas of more than 178,956,970 pixels (bbocr_host_png_plan's limit) */
+    BBOCR_GIF_CODE_SIZE = 6     /* a minimum code size outside 2 .. 8 */
+};
+typedef struct bbocr_gif_plan {
+    int screen_w, screen_h;
+    int x0, y0, width, height;  /* the frame rectangle */
+    int canvas_w, canvas_h;     /* Pillow's image size: max(screen, x0 + width) by max(screen, y0 + height) */
+    int interlace;
+    int table_len;              /* entries of the table in force -- the local one over the global one --, 0: the file has none */
+    int local_table;            /* 1: the table in force is the local one */
+    int transparency;           /* the index pixels outside the frame hold, or -1 (they hold 0) */
+    int min_code;
+    int mode_l;                 /* 1: Pillow's mode L (every entry i of the table in force is (i, i, i), or no table): gray = the index */
+    long long payload_bytes;    /* the data sub-blocks together: what crosses the link */
+    int supported;              /* 1: bbocr_gif_decode takes the file */
+    int reason;                 /* BBOCR_GIF_* */
+    int reserved[2];
+    uint8_t table[768];         /* the RGB plane's lookup, R G B per index: the table in force, black where it has no entry; mode L: the
+                                 * ramp, or the global table behind a local ramp (Pillow's reading) */
+} bbocr_gif_plan;
+int bbocr_host_gif_plan(const void* file, size_t bytes, bbocr_gif_plan* plan);
+/* n files (HOST bytes) -> both planes [canvas_h, canvas_w] in DEVICE memory, one call per batch whatever mix of shapes, piece counts and
+ * code sizes it holds; destinations as bbocr_tiff_decode's.  Five launches: the scan (one wavefront per file: the piece table -- first
+ * bit, data codes, how the piece ends), the lengths (one wavefront per piece: its decoded byte count and validity), the offsets (an
+ * exclusive prefix sum per file, saturated at width * height, and the file's status), the decode (one wavefront per piece: match copies
+ * into the file's index stream at the piece's offset, clipped at width * height) and the output (de-interlace, placement on the canvas,
+ * table lookup, both planes).  No launch waits on another workgroup.
+ * status[k]: 0, BBOCR_ERR_ARG (a null pointer, a pitch shorter than a row, a file the plan refuses, a payload of 2^28 bytes or more) or
+ * BBOCR_ERR_DATA: before width * height indices exist, the first code behind a clear is no literal, a code lies above the next free
+ * entry, the end code or the payload's end is met, or the stream has more pieces than the piece table holds (min(payload_bits /
+ * (min_code + 1) + 1, max(4096, payload_bytes / 16))).  What follows the full frame is ignored.  Such a file's destinations are
+ * undefined; no byte outside a destination's rows is ever written, the other files decode all the same and the context stays usable.
+ * Stream, one-batch-at-a-time contract and work buffers: bbocr_jpeg_decode's.  Returns with its work finished, also when it fails.
+ * bbocr_op_gif_decode_stage: the intermediates of ONE file in DEVICE memory dev_dst[dst_bytes] (parity tests), by the kernels the full
+ * call runs: stage 0 = the piece table: uint32 count, scan error bits, 0, 0, then per piece uint32 first bit (low, high), data codes, end
+ * (0 clear, 1 end code, 2 end of payload) -- dst_bytes at least 16 + 16 * the table's room; 1 = uint32 offsets[count] and the total;
+ * 2 = the index stream in stored row order, width * height bytes.  *file_status as status[k] above, of the launches that ran. */
+int bbocr_gif_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                     uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
+int bbocr_op_gif_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
+/* Measurement and test helpers, no part of the decode interface.  bbocr_gif_decode_timed: bbocr_gif_decode, and launch_ms[5] (may be
+ * null) = the five launches' times in milliseconds, between events on the stream (tools/bench_gif_bmp_decode.py).
+ * bbocr_gif_piece_room: the piece table's room for a payload, by which a caller of bbocr_op_gif_decode_stage sizes its destination. */
+int bbocr_gif_decode_timed(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                           uint8_t* const* dst_gray, const long long* pitch_gray, int* status, float* launch_ms);
+size_t bbocr_gif_piece_room(long long payload_bytes, int min_code);
+
+/* ---- BMP files decoded on the device (csrc/bmpdec.hip; opt-in: Reader(bmp_decode=True)): what reader.decode_file holds for a BMP file
+ * -- Pillow's convert("RGB") and the gray plane of its stated rule -- from the file's bytes, which cross the link whole.  Pillow's
+ * BmpImagePlugin._bitmap restated: headers of 12, 40, 52, 56, 64, 108 and 124 bytes; bottom-up, or top-down when the height's top byte is
+ * FF; rows ((width * bits + 31) >> 3) & ~3 bytes apart; 1, 4 and 8 bits with a table of B G R entries (3 bytes behind a 12-byte header,
+ * else 4) -- mode 1 when it is exactly black then white, L when an 8-bit file's table is the ramp, P otherwise, an index without an entry
+ * black --; 16 bits 5-5-5 uncompressed or bit fields 5-6-5 / 5-5-5, a channel v expanded as v * 255 / 31 (63) in integers; 24 bits; 32
+ * bits B G R X uncompressed and the eight mask layouts Pillow lists, alpha dropped.  Defined by tests/bmp_decode_ref.py.
+ * bbocr_host_bmp_plan: host only, no GPU.  Fields the walk did not reach stay 0. */
+enum {
+    BBOCR_BMP_OK = 0,
+    BBOCR_BMP_NOT_BMP = 1,      /* no "BM" */
+    BBOCR_BMP_TRUNCATED = 2,    /* the file ends inside the headers, the masks behind a 40-byte header or the table, or is shorter than
+                                 * data_offset + row_stride * height (Pillow raises when a whole row is missing and reads on when less is) */
+    BBOCR_BMP_HEADER = 3,       /* a header size other than 12, 40, 52, 56, 64, 108, 124 */
+    BBOCR_BMP_DIMENSIONS = 4,   /* width 0 or above 2^31 - 1 (a negative width), height 0 */
+    BBOCR_BMP_PIXELS = 5,       /* more than 178,956,970 pixels (bbocr_host_png_plan's limit) */
+    BBOCR_BMP_DEPTH = 6,        /* a depth other than 1, 4, 8, 16, 24, 32 */
+    BBOCR_BMP_RLE = 7,          /* RLE8, RLE4 */
+    BBOCR_BMP_COMPRESSION = 8,  /* JPEG, PNG and every other compression above 3 */
+    BBOCR_BMP_MASKS = 9,        /* bit fields in a layout Pillow does not list, or on a file of 8 bits or fewer */
+    BBOCR_BMP_PALETTE = 10,     /* a table of more than 65,536 entries, or of more than 256 that is no gray ramp: Pillow opens such a file and
+                                 * raises "invalid palette size" when it loads it */
+    BBOCR_BMP_GRAY_TABLE = 11   /* a table that makes Pillow's mode 1 or L on samples of another depth -- a gray ramp on 1 or 4 bits, black then
+                                 * white on 4 or 8 bits: Pillow raises or reads the rows at the wrong depth */
+};
+typedef struct bbocr_bmp_plan {
+    int width, height, bits, compression, header_size;
+    int top_down;
+    int colors;                 /* entries of the table (1, 4, 8 bits), else 0 */
+    int mode;                   /* 0 P, 1 Pillow's mode 1, 2 L, 3 direct colour */
+    int r_at, g_at, b_at;       /* 24 and 32 bits: the byte of a pixel that holds R, G, B */
+    int six_bit_green;          /* 16 bits: 1 for 5-6-5 */
+    long long table_offset;     /* the table's place in the file */
+    int table_entry;            /* 3 or 4 bytes */
+    int supported;              /* 1: bbocr_bmp_decode takes the file */
+    long long row_stride, data_offset;
+    int reason;                 /* BBOCR_BMP_* */
+    int reserved[3];
+} bbocr_bmp_plan;
+int bbocr_host_bmp_plan(const void* file, size_t bytes, bbocr_bmp_plan* plan);
+/* n files (HOST bytes) -> both planes [height, width] in DEVICE memory by ONE launch, whatever mix of shapes and depths; destinations as
+ * bbocr_tiff_decode's.  A workgroup runs over a row, its lanes over the row's pixels: they unpack bits, nibbles, bytes, 16-bit words or 3- and 4-byte groups, flip the row
+ * order and write both planes.  status[k]: 0 or BBOCR_ERR_ARG (a null pointer, a pitch shorter than a row, a file the plan refuses):
+ * every byte the launch reads lies inside the file, as the plan has checked.  Stream, one-batch-at-a-time contract and work buffers:
+ * bbocr_jpeg_decode's.  Returns with its work finished, also when it fails. */
+int bbocr_bmp_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                     uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
+
 #ifdef __cplusplus
 }
 #endif
