@@ -23,7 +23,8 @@
 // acc[j][r]; the cout permutation of pack_conv_weights maps them to cout = tile + wn*64 + (j>>1)*32 + g*8 + (j&1)*4 + r:
 // TWO runs of 8 contiguous couts, 32 apart, so that one store instruction writes, for every pixel, 64 contiguous bytes
 // (4 lane groups x 16 B) instead of four 16-byte pieces with gaps.  v[i], i = j*4+r: run h = i>>3, position i&7.
-template <int EL, int MF, bool ADDUP = false>
+// ADDUP (conv1x1_dma_kernel): 0 nothing added, 1 the 2x up-sampling of a half-resolution tensor, 2 a tensor of the output's own resolution.
+template <int EL, int MF, int ADDUP = 0>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[MF][4], int n, int nt, int oy0, int ox0, int wm, int wn, int fpr,
                                               int lane, int BN, int sub = 1, int sph = 0, int spw = 0) {
     const int g = lane >> 4, pl = lane & 15;
@@ -146,7 +147,42 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[MF
         }
         store_frag_at(base, row, cs, xb, xlim, row_ok, v, f32, 0);
     };
-    if constexpr (ADDUP) {
+    if constexpr (ADDUP == 2) {
+        // 1x1 launch over the flattened N*H*W pixel axis whose epilogue adds z = a.addup [N*H*W][up_cs] at the output pixel itself: the ADDUP == 1
+        // path below without the bilinear gather.  Two 16-byte loads per lane and fragment (its two runs of 8 couts), those of fragment f+1
+        // issued before fragment f is added and stored; the sum is formed in fp32 before the ReLU.
+        // (launch_conv guarantees cout_store % 64 == 0 and up_cs == cout_store here: both runs of every lane exist, in z as in the output.)
+        struct Addend { u32x4 q[2]; };
+        auto issue = [&](int f, Addend& G) {
+            int p = ox0 + (wm * MF + f) * 16 + pl;
+            p = p < a.OW ? p : a.OW - 1;                      // beyond the end: any valid address, the store is predicated
+            const uint16_t* zb = a.addup + (size_t)p * a.up_cs + cout0;
+            G.q[0] = *(const u32x4*)zb;
+            G.q[1] = *(const u32x4*)(zb + 32);
+        };
+        Addend G[2];
+        issue(0, G[0]);
+#pragma unroll
+        for (int f = 0; f < MF; ++f) {
+            if (f + 1 < MF) issue(f + 1, G[(f + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);               // keep the next fragment's loads ahead of this fragment's math
+            const Addend& C = G[f & 1];
+            float v[16];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x2_t t = El<EL>::unpack2(C.q[h][i]);
+                    const int k = h * 8 + i * 2;             // v index j*4+r == run h, position 2i / 2i+1
+                    float x0 = acc[f][k >> 2][k & 3] + bs[k] + t[0], x1 = acc[f][(k + 1) >> 2][(k + 1) & 3] + bs[k + 1] + t[1];
+                    if (a.relu_out) { x0 = fmaxf(x0, 0.f); x1 = fmaxf(x1, 0.f); }
+                    v[k] = x0; v[k + 1] = x1;
+                }
+            store_frag(a.out, 0, a.out_cs, ox0 + (wm * MF + f) * 16, a.OW, true, v, false);
+        }
+        return;
+    }
+    if constexpr (ADDUP == 1) {
         // 1x1 launch over the flattened N*up_H*up_W pixel axis whose epilogue adds up(z): F.interpolate(scale 2, bilinear,
         // align_corners=False) of the low-resolution tensor z = a.addup -- source coordinate (o + 0.5)/2 - 0.5 clamped at 0,
         // neighbour clamped at the far edge, four fp32 blend weights per pixel.  The 8 gather loads of fragment f+1 are issued
@@ -1434,7 +1470,7 @@ hipError_t launch_up4_fused(const ConvPlan& p1, const ConvPlan& p3, ConvArgs a, 
 // holds, of a pair g, g ^ 1, the quad-rows pl >> 2 = 0 and 3 of one group and 1 and 2 of its twin: their slots g, g ^ 2, g ^ 3, g ^ 1 are
 // the four different ones, and inside a quad-row pl & 3 takes its four values -- 16 lanes, 16 bank groups.  Tiles start on multiples of 256 pixels
 // and fragments on multiples of 16, so the XOR is a per-lane constant and fragment f is base + f * 1024.
-template <int EL, int WM, int WN, int MF, int RING, bool ADDUP>
+template <int EL, int WM, int WN, int MF, int RING, int ADDUP>
 __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_dma_kernel(const ConvArgs a) {
     constexpr int NW = WM * WN, NT = NW * 64, BN = WN * 64;
     static_assert(NW == 4 || NW == 8, "wave w gathers 16 / NW of the 16-pixel blocks of the activation tile");
@@ -1520,7 +1556,7 @@ __global__ void __launch_bounds__(WM * WN * 64, (WM * WN == 8 ? 1 : 2)) conv1x1_
     conv_epilogue<EL, MF, ADDUP>(a, acc, 0, nt, 0, px0, wm, wn, 16, lane, BN);
 }
 
-template <int EL, int WM, int WN, int MF, bool ADDUP>
+template <int EL, int WM, int WN, int MF, int ADDUP>
 static hipError_t launch_dma1x1_k(const ConvArgs& a, long long grid, hipStream_t s, ConvRoute* route, bool dry) {
     constexpr int RING = 3, NPX = WM * MF * 16;
     auto k = conv1x1_dma_kernel<EL, WM, WN, MF, RING, ADDUP>;
@@ -1543,9 +1579,11 @@ static hipError_t launch_dma1x1(ConvArgs a, hipStream_t s, ConvRoute* route, boo
     a.tiles_x = (int)((total + NPX - 1) / NPX);
     const long long grid = (long long)a.tiles_x * a.ntiles_n;
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    // the epilogue that adds an up-sampled tensor is its own instantiation: its register needs must not leak into the others
+    // the epilogues that add a tensor (up-sampled: 1, at the output's own resolution: 2) are their own instantiations: their register needs
+    // must not leak into the others
     // (8-wave tiles, one workgroup per CU: a ring of 4 measured no faster than 3 -- 389 vs 383 us on fc7)
-    return a.addup ? launch_dma1x1_k<EL, WM, WN, MF, true>(a, grid, s, route, dry) : launch_dma1x1_k<EL, WM, WN, MF, false>(a, grid, s, route, dry);
+    if (a.addup && a.add_same) return launch_dma1x1_k<EL, WM, WN, MF, 2>(a, grid, s, route, dry);
+    return a.addup ? launch_dma1x1_k<EL, WM, WN, MF, 1>(a, grid, s, route, dry) : launch_dma1x1_k<EL, WM, WN, MF, 0>(a, grid, s, route, dry);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -1747,6 +1785,8 @@ static hipError_t launch_conv_el(const ConvPlan& p, ConvArgs a, hipStream_t s, C
     if (a.addup && !(p.KH == 1 && p.KW == 1 && a.zero && !a.pool_mode && !a.out_f32 && !a.tail && a.cout_store % 64 == 0 &&
                      a.cout_store == p.Cout_pad))
         return hipErrorInvalidValue;
+    // the same-resolution addend is read at the output's own pixel and channel: z must be N*H*W x cout_store, nothing else
+    if (a.add_same && !(a.addup && a.up_H == a.H && a.up_W == a.W && a.up_cs == a.cout_store)) return hipErrorInvalidValue;
     if (p.KH == 1 && p.KW == 1 && p.pad_h == 0 && p.pad_w == 0 && a.zero && !a.pool_mode)
         return BN == 256 ? launch_dma1x1<EL, 2, 4, 8>(a, s, route, dry) : (BN == 128 ? launch_dma1x1<EL, 2, 2, 8>(a, s, route, dry) : launch_dma1x1<EL, 4, 1, 4>(a, s, route, dry));
     if (dma2x2)

@@ -155,6 +155,11 @@ struct WeightView {
     float* cls6_w32 = nullptr;                // exact mode: conv_cls.6.weight fp32 [16][16] (pair_cls_tail_kernel)
     ConvPlan conv1_2, conv2_1, conv2_2, conv3_1, conv3_2, conv3_3, conv4_1, conv4_2, conv4_3, conv5_1, conv5_2, fc6, fc7;
     ConvPlan up1a, up1b, up2b, up3b, up4b, cls0, cls2, cls4;
+    // fast modes: fc6, fc7 and the fc7 half of upconv1's 1x1 folded into ONE dilated 3x3 512 -> 512 (no bias), and the skip half of that 1x1 with
+    // the composite bias, whose epilogue adds fcfold's output (fc_fold.h, weights.cpp::load_fc_fold); fc7 is an exact-mode plan only, fc6 is
+    // still uploaded in the fast modes though nothing launches it (the blob-size pin, see load_fc_fold), up1a (the 1x1 over the whole
+    // concat) stays loaded for its stage entry point
+    ConvPlan fcfold, up1s;
     // U-net 1x1 layers over cat[up(y), skip], split by linearity: upNy = the columns of y (no bias, run at y's resolution),
     // upNs = the columns of the skip tensor (+ bias), whose epilogue adds the 2x bilinear up-sampling of upNy's output
     ConvPlan up2y, up2s, up3y, up3s, up4y, up4s;
@@ -395,15 +400,16 @@ void weights_export(bbocr_ctx* c, void* dev_dst, size_t bytes);
 void weights_import(bbocr_ctx* c, const void* dev_src, size_t bytes);
 void load_craft(bbocr_ctx* c, const TensorMap& tm);
 void load_crnn(bbocr_ctx* c, const TensorMap& tm);
-ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1 = nullptr, const Act* addup = nullptr);
+ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1 = nullptr, const Act* addup = nullptr, const Act* addsame = nullptr);
 hipError_t launch_conv_profiled(bbocr_ctx* c, const ConvPlan& p, ConvArgs a, bool may_decline = false);   // may_decline: hipErrorNotSupported is returned, not thrown
-void run_conv(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, void* out, int out_cs, int cout_store, bool out_f32, const Act* addup = nullptr);
+void run_conv(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, void* out, int out_cs, int cout_store, bool out_f32, const Act* addup = nullptr, const Act* addsame = nullptr);
 hipError_t launch_seq_proj_profiled(bbocr_ctx* c, const ConvPlan& p, const uint16_t* x, size_t rows_pad, uint16_t* out);   // hipErrorNotSupported is returned, not thrown
 void prof_collect(bbocr_ctx* c);
 Act conv_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, int store);
 Act conv_pool_act(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, bool relu_out, int store, int mode, bool pool_relu, Act* full, const RgbSource* rgb = nullptr);
 Act pool_act(bbocr_ctx* c, const Act& a, int kh, int kw, int sh, int sw, int ph, int pw, bool relu_in);
 void craft_up_stage(bbocr_ctx* c, const ConvPlan& py, const ConvPlan& ps, const Act& y, const Act& skip, uint16_t* z, uint16_t* out);
+void craft_fc_stage(bbocr_ctx* c, const Act& p5, const Act& s4, uint16_t* z, uint16_t* out);
 bool craft_up3b_post(bbocr_ctx* c, const Act& u3a, uint16_t* u3b, uint16_t* z);      // true: the one fused launch ran; false: the two launches
 bool craft_up4(bbocr_ctx* c, const Act& s1, const uint16_t* z, uint16_t* u4b);       // likewise
 void craft_cls_tail(bbocr_ctx* c, const Act& c2, float* heat);

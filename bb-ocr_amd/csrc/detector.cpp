@@ -45,10 +45,11 @@ hipError_t launch_seq_proj_profiled(bbocr_ctx* c, const ConvPlan& p, const uint1
 }
 
 // ConvArgs of a launch over a0 (a1: a second source behind it, virtual channel concat; addup: the half-resolution tensor whose 2x
-// up-sampling the epilogue adds): sources and image shape.  The caller adds the output and the epilogue switches.
+// up-sampling the epilogue adds; addsame: a tensor of the output's own shape that the epilogue adds instead): sources and image shape.  The
+// caller adds the output and the epilogue switches.
 // Split-fp16 plans (ConvPlan::split, exact recogniser mode): the activation `a0` is a pair tensor [hi | lo] whose Act::C counts BOTH
 // halves; the launch reads [hi | lo | hi] (in1 = the hi half again) and, unless it writes fp32, stores its output as a pair too.
-ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1, const Act* addup) {
+ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1, const Act* addup, const Act* addsame) {
     ConvArgs a{};
     a.in0 = a0.p; a.C0 = a0.C; a.in0_cs = a0.C;
     a.N = a0.N; a.H = a0.H; a.W = a0.W;
@@ -59,13 +60,17 @@ ConvArgs conv_args(const ConvPlan& p, const Act& a0, const Act* a1, const Act* a
         a.in1 = a1->p; a.C1 = a1->C; a.in1_cs = a1->C;
     }
     if (addup) { a.addup = addup->p; a.up_H = a0.H; a.up_W = a0.W; a.up_cs = addup->C; }
+    if (addsame) {
+        if (addup || addsame->N != a0.N) fail(BBOCR_ERR_INTERNAL, "conv: one addend, of the output's own page count");
+        a.addup = addsame->p; a.up_H = addsame->H; a.up_W = addsame->W; a.up_cs = addsame->C; a.add_same = 1;      // launch_conv checks them against the output
+    }
     return a;
 }
 
 void run_conv(bbocr_ctx* c, const ConvPlan& p, const Act& a0, bool relu0, const Act* a1, bool relu1, bool relu_out, void* out,
-                     int out_cs, int cout_store, bool out_f32, const Act* addup) {
+                     int out_cs, int cout_store, bool out_f32, const Act* addup, const Act* addsame) {
     if (c->arena.dry) return;
-    ConvArgs a = conv_args(p, a0, a1, addup);
+    ConvArgs a = conv_args(p, a0, a1, addup, addsame);
     a.relu_in0 = relu0; a.relu_in1 = p.split ? relu0 : relu1; a.relu_out = relu_out; a.out_f32 = out_f32;
     a.out = out; a.out_cs = out_cs; a.cout_store = cout_store;
     if (p.split && !out_f32) a.split_off = cout_store;          // out_cs is 2 * cout_store then
@@ -139,6 +144,17 @@ void craft_up_stage(bbocr_ctx* c, const ConvPlan& py, const ConvPlan& ps, const 
     run_conv(c, ps, skip, false, nullptr, false, true, out, cout, cout, false, &zz);
 }
 
+// slice5's fc6 (3x3, dilation 6) -> fc7 (1x1) and the fc7 half of upconv1's 1x1 over cat[fc7, relu5_3]: three linear maps with no activation
+// and no BatchNorm between them, folded into one at weight load (fc_fold.h).  z = Wc (*) p5 (no bias, no ReLU: the sub-lattice route fc6
+// took, with half its couts), then out = ReLU(z + Ws s4 + b') in the epilogue of the skip half: the 1024-channel f6 and f7 are never
+// computed, 25.2 instead of 62.9 GFLOP per 1280x960 page
+void craft_fc_stage(bbocr_ctx* c, const Act& p5, const Act& s4, uint16_t* z, uint16_t* out) {
+    const int cout = c->up1s.Cout;
+    const Act zz{z, p5.N, p5.H, p5.W, cout};
+    run_conv(c, c->fcfold, p5, false, nullptr, false, false, z, cout, cout, false);
+    run_conv(c, c->up1s, s4, false, nullptr, false, true, out, cout, cout, false, nullptr, &zz);
+}
+
 // upconv3's 3x3 with z = W_y u3b (the y half of upconv4's 1x1, linear) applied in its epilogue: u3b itself has no other reader and is
 // not stored, one launch and 2 x 9.8 MB per page less; shapes the kernel declines take the two launches through `u3b`
 bool craft_up3b_post(bbocr_ctx* c, const Act& u3a, uint16_t* u3b, uint16_t* z) {
@@ -200,9 +216,8 @@ static void craft_forward(bbocr_ctx* c, const uint8_t* rgb, int nb, int Himg, in
     Act a11 = conv_act(c, c->conv5_1, p4, false, nullptr, false, true, 512);
     Act s4 = conv_act(c, c->conv5_2, a11, false, nullptr, false, false, 512);
     Act p5 = pool_act(c, s4, 3, 3, 1, 1, 1, 1, false);                             // slice5: MaxPool(3,1,1), no ReLU
-    Act f6 = conv_act(c, c->fc6, p5, false, nullptr, false, false, 1024);
-    Act f7 = conv_act(c, c->fc7, f6, false, nullptr, false, false, 1024);
-    Act u1a = conv_act(c, c->up1a, f7, false, &s4, false, true, 512);              // cat([fc7, relu5_3]) -> 1x1
+    Act z1 = arena_act(c, s4.N, s4.H, s4.W, 512), u1a = arena_act(c, s4.N, s4.H, s4.W, 512);
+    craft_fc_stage(c, p5, s4, z1.p, u1a.p);                                        // fc6 -> fc7 -> cat([fc7, relu5_3]) -> 1x1, folded
     Act u1b = conv_act(c, c->up1b, u1a, false, nullptr, false, true, 256);
     Act z2 = arena_act(c, u1b.N, u1b.H, u1b.W, 256), u2a = arena_act(c, s3.N, s3.H, s3.W, 256);
     craft_up_stage(c, c->up2y, c->up2s, u1b, s3, z2.p, u2a.p);

@@ -53,6 +53,9 @@ struct ConvArgs {
     int lean;              // conv3x3_dma_kernel: which epilogue (set by its launcher: 0 shared, 1 plain lean, 3 pooled lean)
     int split_off;         // > 0 (fp16 element type only): every stored value v goes out as the pair hi = fp16(v) at its channel and
                            // lo = fp16(v - hi) at channel + split_off -- the [hi | lo] activation layout of the exact recogniser mode
+    int add_same;          // 1: `addup` is a tensor at the OUTPUT's own resolution [N, H, W, up_cs], added pixel by pixel before bias/ReLU (no
+                           // up-sampling): out = ReLU(z + W_s s + b), the second launch of detector.cpp::craft_fc_stage.  Read by the launcher
+                           // only (it picks the kernel's epilogue); last, so that no other member moves
 };
 
 struct ConvPlan {      // host-side description of one packed conv layer
@@ -84,7 +87,7 @@ enum ConvRouteId : int {
     CONV_ROUTE_DMA128_384, CONV_ROUTE_DMA128_448,
     // conv3x3_dma_kernel with KS = 2 (2x2, padding 0)
     CONV_ROUTE_DMA2X2_64, CONV_ROUTE_DMA2X2_128,
-    // conv1x1_dma_kernel: by couts per tile without the up-sampling epilogue; with it (ADDUP, any tile width: see ConvRoute::wn)
+    // conv1x1_dma_kernel: by couts per tile without an addend in the epilogue; with one (ADDUP: ConvRoute::addup says which, any tile width: see ConvRoute::wn)
     CONV_ROUTE_DMA1X1_64, CONV_ROUTE_DMA1X1_128, CONV_ROUTE_DMA1X1_256, CONV_ROUTE_DMA1X1_ADDUP,
     CONV_ROUTE_COUNT
 };
@@ -95,7 +98,8 @@ struct ConvRoute {
     int el, wm, wn, mf;
     int piter;                                                  // conv_mfma_kernel
     int npb, ring, nps, fuse1, nf, epi, ks;                     // conv3x3_dma_kernel
-    int addup;                                                  // conv1x1_dma_kernel (its RING is `ring`)
+    int addup;                                                  // conv1x1_dma_kernel (its RING is `ring`): 1 the up-sampling epilogue, 2 the
+                                                                // same-resolution addend (ConvArgs::add_same); both under CONV_ROUTE_DMA1X1_ADDUP
     int resw;                                                   // conv3x3_resw_kernel: 1 <1, true, 4, true>, 2 <1, true>, 3 <2, false>
     // geometry the launchers settled
     int OH, OW, TH, TW, PH, PW, NP, sub, stack, tiles_x, tiles_y, ntiles_n, nchunks, ntaps, lean;

@@ -1,5 +1,6 @@
 // Weight tables: eval-mode BatchNorm folded into the convolutions, bf16 rounding, MFMA fragment packing (easyocr Reader.__init__ / get_detector / get_recognizer).
 #include "ctx.h"
+#include "fc_fold.h"
 #include <limits>
 
 // ------------------------------------------------------------------------------------------------ weights
@@ -138,6 +139,7 @@ std::vector<float*> blob_scalars(bbocr_ctx* c) {       // host scalars that depe
     for (ConvPlan* p : {&c->conv1_2, &c->conv2_1, &c->conv2_2, &c->conv3_1, &c->conv3_2, &c->conv3_3, &c->conv4_1, &c->conv4_2, &c->conv4_3, &c->conv5_1,
                         &c->conv5_2, &c->fc6, &c->fc7, &c->up1a, &c->up1b, &c->up2s, &c->up2b, &c->up3s, &c->up3b, &c->up4s, &c->up4b, &c->cls0, &c->cls2, &c->cls4})
         v.push_back(&p->acc_scale);       // exact mode: the detector's split plans (1 otherwise)
+    for (ConvPlan* p : {&c->fcfold, &c->up1s}) v.push_back(&p->acc_scale);      // fast modes: the folded fc6 / fc7 / upconv1 stage (1)
     return v;
 }
 }  // namespace
@@ -145,7 +147,7 @@ std::vector<float*> blob_scalars(bbocr_ctx* c) {       // host scalars that depe
 size_t weights_blob_bytes(const bbocr_ctx* c) {
     size_t n = sizeof(BlobHeader);
     for (size_t b : c->owned_bytes) n += align_up(b, 256);
-    return n + 256;                                     // trailer: 64 floats (blob_scalars: 37 used)
+    return n + 256;                                     // trailer: 64 floats (blob_scalars: 39 used)
 }
 
 void weights_export(bbocr_ctx* c, void* dev_dst, size_t bytes) {
@@ -247,6 +249,36 @@ static void load_craft_exact(bbocr_ctx* c, const TensorMap& tm) {
     c->craft_loaded = true;
 }
 
+// Fast modes: fc6, fc7 and the fc7 half of upconv1's 1x1 are three linear maps in a row and run as their product (fc_fold.h): `fcfold`, ONE dilated
+// 3x3 512 -> 512 without bias (four cout tiles on fc6's sub-lattice route, where fc6 had eight), and `up1s`, the skip half of the 1x1 with
+// the composite bias, whose epilogue adds fcfold's output (detector.cpp::craft_fc_stage).  The weights do not change from call to call: the
+// product is formed here, once per load.  No fast-mode launch reads fc6 or fc7 any more: fc7 is not uploaded; fc6 still is, because the packed
+// blob of a 16-bit context is pinned to SURVEY 8e's ~49 MB (45 .. 60 MB, tests/test_gpu_precision.py::test_weight_blob_export_import) and
+// would be 42.9 MB without both (52.4 with fc6).  up1a, the 1x1 over the whole concat, stays for its stage entry point.
+static void load_fc_fold(bbocr_ctx* c, const TensorMap& tm) {
+    std::vector<float> wu, bu;
+    fold_conv(tm, "upconv1.conv.0", "upconv1.conv.1", 512, 1536, 1, wu, bu);
+    // the long-K 1x1 GEMM runs 256-cout tiles (8 waves): its 128-cout tiles moved 24 KB of LDS-DMA per 2.1 MFLOP k-step and sat at the
+    // DMA fill rate (~8 TB/s, 0.71 PFLOP/s); 32 KB per 4.2 MFLOP now
+    c->up1a = make_plan(1536, 512, 1, 1, 0, 1, det_el(c), 256);
+    upload_plan(c, c->up1a, wu, bu);
+    std::vector<float> w6, b6;
+    fold_conv(tm, "basenet.slice5.1", "", 1024, 512, 9, w6, b6);
+    c->fc6 = make_plan(512, 1024, 3, 3, 6, 6, det_el(c));
+    upload_plan(c, c->fc6, w6, b6);
+    const FcFoldDims d{512, 1024, 1024, 512, 512, 9};
+    std::vector<float> wc((size_t)d.Cout * d.Cin * d.taps, 0.f), ws((size_t)d.Cout * d.Cs, 0.f), bp(d.Cout, 0.f);
+    if (!tm.zeros) {                     // an allocation-only load lays the plans out; bbocr_weights_import fills them
+        std::vector<float> w7, b7;
+        fold_conv(tm, "basenet.slice5.2", "", 1024, 1024, 1, w7, b7);
+        fc_fold(d, w6.data(), b6.data(), w7.data(), b7.data(), wu.data(), bu.data(), wc, ws, bp, &host_pool(c));
+    }
+    c->fcfold = make_plan(512, 512, 3, 3, 6, 6, det_el(c));
+    upload_plan(c, c->fcfold, wc, std::vector<float>(512, 0.f));
+    c->up1s = make_plan(512, 512, 1, 1, 0, 1, det_el(c));
+    upload_plan(c, c->up1s, ws, bp);
+}
+
 void load_craft(bbocr_ctx* c, const TensorMap& tm) {
     if (det_split(c)) { load_craft_exact(c, tm); return; }
     {
@@ -268,11 +300,7 @@ void load_craft(bbocr_ctx* c, const TensorMap& tm) {
     load_layer(c, tm, c->conv4_3, "basenet.slice4.30", "basenet.slice4.31", 512, 512, 3, 1, 1, det_el(c));
     load_layer(c, tm, c->conv5_1, "basenet.slice4.34", "basenet.slice4.35", 512, 512, 3, 1, 1, det_el(c));
     load_layer(c, tm, c->conv5_2, "basenet.slice4.37", "basenet.slice4.38", 512, 512, 3, 1, 1, det_el(c));
-    load_layer(c, tm, c->fc6, "basenet.slice5.1", "", 512, 1024, 3, 6, 6, det_el(c));
-    // the long-K 1x1 GEMMs run 256-cout tiles (8 waves): their 128-cout tiles moved 24 KB of LDS-DMA per 2.1 MFLOP k-step and sat at the
-    // DMA fill rate (~8 TB/s, 0.71 PFLOP/s); 32 KB per 4.2 MFLOP now
-    load_layer(c, tm, c->fc7, "basenet.slice5.2", "", 1024, 1024, 1, 0, 1, det_el(c), false, 256);
-    load_layer(c, tm, c->up1a, "upconv1.conv.0", "upconv1.conv.1", 1536, 512, 1, 0, 1, det_el(c), false, 256);
+    load_fc_fold(c, tm);
     load_layer(c, tm, c->up1b, "upconv1.conv.3", "upconv1.conv.4", 512, 256, 3, 1, 1, det_el(c));
     load_split_1x1(c, tm, c->up2y, c->up2s, "upconv2.conv.0", "upconv2.conv.1", 256, 512, 256);
     load_layer(c, tm, c->up2b, "upconv2.conv.3", "upconv2.conv.4", 256, 128, 3, 1, 1, det_el(c));

@@ -363,7 +363,7 @@ enum {
     BBOCR_ROUTE_DMA128_384, BBOCR_ROUTE_DMA128_448,
     /* conv3x3_dma_kernel as the 2x2 / padding 0 conv */
     BBOCR_ROUTE_DMA2X2_64, BBOCR_ROUTE_DMA2X2_128,
-    /* conv1x1_dma_kernel: 64 / 128 / 256 couts per tile; with the up-sampling epilogue (the networks' own launches only) */
+    /* conv1x1_dma_kernel: 64 / 128 / 256 couts per tile; with an addend in the epilogue, see `addup` (the networks' own launches only) */
     BBOCR_ROUTE_DMA1X1_64, BBOCR_ROUTE_DMA1X1_128, BBOCR_ROUTE_DMA1X1_256, BBOCR_ROUTE_DMA1X1_ADDUP,
     BBOCR_ROUTE_COUNT
 };
@@ -375,7 +375,8 @@ typedef struct bbocr_conv_route {
     int piter;               /* conv_mfma_kernel: 16-pixel patch pieces a wave stages per chunk */
     int npb, ring, nps, fuse1, nf, epi, ks;   /* conv3x3_dma_kernel: 64-pixel patch blocks, weight ring depth, patch slots, conv1_1 fused, cout
                                                * fragments per wave, epilogue, kernel size (conv1x1_dma_kernel: ring, ks = 1) */
-    int addup;               /* conv1x1_dma_kernel: the up-sampling epilogue */
+    int addup;               /* conv1x1_dma_kernel, BBOCR_ROUTE_DMA1X1_ADDUP: 1 = the up-sampling epilogue, 2 = a tensor of the output's own
+                              * resolution added in the epilogue (the folded fc6 / fc7 / upconv1 stage) */
     int resw;                /* conv3x3_resw_kernel: 1 = 64 couts pooled, 2 = one chunk, 3 = two chunks */
     int OH, OW, TH, TW, PH, PW, NP, sub, stack, tiles_x, tiles_y, ntiles_n, nchunks, ntaps, lean;   /* geometry: output, tile, patch, patch
                               * slots, dilation phases (> 1: the sub-lattice route) and rows of one phase image, tile counts, 32-channel input

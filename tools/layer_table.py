@@ -1,7 +1,9 @@
-"""Per-layer table of the detector from a rocprofv3 --kernel-trace CSV (tools/detect_only.py run): duration and TFLOP/s."""
+"""Per-layer table of the detector from a rocprofv3 --kernel-trace CSV (tools/detect_only.py run): duration and TFLOP/s.
+usage: layer_table.py <kernel_trace.csv> <pages> [unfolded]   -- unfolded: a build from before fc6 / fc7 / up1a ran as fcfold + up1s"""
 import csv, sys
+FC = [('fc6',22.649),('fc7',5.033),('up1a',3.775)] if sys.argv[3:4] == ['unfolded'] else [('fcfold',11.325),('up1s',1.258)]
 MACS = [('conv1_2',45.298 + 2.123),('conv2_1',22.649),('conv2_2',45.298),('conv3_1',22.649),('conv3_2',45.298),('conv3_3',45.298),('conv4_1',22.649),
-        ('conv4_2',45.298),('conv4_3',45.298),('conv5_1',11.325),('conv5_2',11.325),('fc6',22.649),('fc7',5.033),('up1a',3.775),('up1b',5.662),
+        ('conv4_2',45.298),('conv4_3',45.298),('conv5_1',11.325),('conv5_2',11.325)] + FC + [('up1b',5.662),
         ('up2y',0.315),('up2s',2.517),('up2b',5.662),('up3y',0.315),('up3s',2.517),('up3b',5.662),('up4y',0.315),('up4s',2.517),('up4b',5.662),('cls0',2.831),('cls2',2.831),('cls4',1.416)]
 path, npages = sys.argv[1], int(sys.argv[2])
 rows = list(csv.DictReader(open(path)))

@@ -178,6 +178,51 @@ int stage_up1a(bbocr_ctx* c, const uint16_t* f7, size_t f7_elems, const uint16_t
     });
 }
 
+// fc6 -> fc7 -> upconv1's 1x1 over cat[fc7, relu5_3] + BN + ReLU as the folded stage (craft_fc_stage: the dilated 3x3 512 -> 512 into z, then the
+// skip half of the 1x1 with z added in its epilogue): p5 [N, H, W, 512] (the pooled relu5_3), s4 [N, H, W, 512] -> out [N, H, W, 512]
+int stage_fc_fold(bbocr_ctx* c, const uint16_t* p5, size_t p5_elems, const uint16_t* s4, size_t s4_elems, int N, int H, int W, uint16_t* out, size_t out_elems) {
+    NEED(c && fast_detector(c) && p5 && s4 && out && dims_ok(N, H, W));
+    NEED(p5_elems == px(N, H, W) * 512 && s4_elems == p5_elems && out_elems == p5_elems);
+    return run_stage(c, [&] {
+        const Act a{(uint16_t*)p5, N, H, W, 512}, k{(uint16_t*)s4, N, H, W, 512};
+        in_arena(c, [&] {
+            const Act z{c->arena.alloc<uint16_t>(px(N, H, W) * 512), N, H, W, 512};
+            craft_fc_stage(c, a, k, z.p, out);
+            return z;
+        });
+        return hipSuccess;
+    });
+}
+
+// the second launch of craft_fc_stage alone: s4 [N, H, W, 512], z [N, H, W, 512] -> out [N, H, W, 512] = ReLU(z + W_s s4 + b')
+int stage_addsame(bbocr_ctx* c, const uint16_t* s4, size_t s4_elems, const uint16_t* z, size_t z_elems, int N, int H, int W, uint16_t* out, size_t out_elems) {
+    NEED(c && fast_detector(c) && s4 && z && out && dims_ok(N, H, W));
+    NEED(s4_elems == px(N, H, W) * 512 && z_elems == s4_elems && out_elems == s4_elems);
+    return run_stage(c, [&] {
+        c->arena.begin(false);                    // run_conv is a no-op in a dry pass; nothing is carved from the arena here
+        const Act sk{(uint16_t*)s4, N, H, W, 512}, zz{(uint16_t*)z, N, H, W, 512};
+        run_conv(c, c->up1s, sk, false, nullptr, false, true, out, 512, 512, false, nullptr, &zz);
+        return hipSuccess;
+    });
+}
+
+// Dry run of that launch (launch_conv's dispatch up to its terminal, nothing is launched and no pointer is followed) with an addend declared as
+// [N, zH, zW, zC]: returns the hipError_t of the dispatch -- hipErrorInvalidValue unless z is N * H * W x 512 -- and the route it reports
+// (id and the `addup` field of ConvRoute).
+int stage_addsame_route(bbocr_ctx* c, int N, int H, int W, int zH, int zW, int zC, int* route_id, int* route_addup) {
+    g_err.clear();
+    NEED(c && fast_detector(c) && dims_ok(N, H, W) && zH > 0 && zW > 0 && zC > 0 && route_id && route_addup);
+    uint16_t* const nowhere = (uint16_t*)c->zero_page;       // a dry run only tests pointers for null
+    const Act sk{nowhere, N, H, W, 512}, zz{nowhere, N, zH, zW, zC};
+    ConvArgs a = conv_args(c->up1s, sk, nullptr, nullptr, &zz);
+    a.relu_out = 1; a.out = nowhere; a.out_cs = 512; a.cout_store = 512; a.zero = c->zero_page;
+    ConvRoute r{};
+    const hipError_t e = launch_conv(c->up1s, a, c->stream, &r, true);
+    *route_id = r.id;
+    *route_addup = r.addup;
+    return (int)e;
+}
+
 // the skip half of a U-net 1x1 with up(z) added in its epilogue (craft_up_stage's second launch; level 4: the first launch of
 // craft_up4's two-launch path): skip [N, H, W, Cs], z [N, H/2, W/2, cout] -> out [N, H, W, cout] = ReLU(up(z) + W_s skip + b)
 int stage_addup(bbocr_ctx* c, int level, const uint16_t* skip, size_t skip_elems, const uint16_t* z, size_t z_elems, int N, int H, int W, uint16_t* out,

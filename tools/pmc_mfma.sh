@@ -24,7 +24,7 @@ for r in csv.DictReader(open(f)):
     d[r["Counter_Name"]] = d.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
 conv = [(k, d) for k, d in sorted(disp.items()) if any(s in d["kernel"] for s in ("conv3x3_dma", "conv1x1_dma", "conv_mfma", "conv3x3_resw", "conv3x3_up4"))]
 start = max(i for i, (k, d) in enumerate(conv) if "conv3x3_dma" in d["kernel"] and ", true" in d["kernel"])
-names = ["conv1_2(+1_1)", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2", "fc6", "fc7", "up1a", "up1b", "up2y", "up2s",
+names = ["conv1_2(+1_1)", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2", "fcfold", "up1s", "up1b", "up2y", "up2s",
          "up2b", "up3y", "up3s", "up3b+4y", "up4s+b", "cls0", "cls2", "cls4(+tail)"]
 print(f"# {npages} pages, last detector pass; clock = GRBM_GUI_ACTIVE / 8 XCDs / duration; MFMA util = 16 x SQ_INSTS_MFMA / (1024 SIMDs x GRBM_GUI_ACTIVE / 8);")
 print(f"# of 2.5 PF = util x clock / 2.4 GHz; parked / stall / issue = SQ_WAIT_ANY / SQ_WAIT_INST_ANY / SQ_ACTIVE_INST_ANY shares of SQ_WAVE_CYCLES")

@@ -21,10 +21,11 @@ def per_layer(d, counter):
 fd, wd, npages, out = sys.argv[1], sys.argv[2], int(sys.argv[3]), sys.argv[4]
 F, W = per_layer(fd, "FETCH_SIZE"), per_layer(wd, "WRITE_SIZE")
 assert len(F) == len(W), (len(F), len(W))
-names = ["conv1_2(+conv1_1)", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2", "fc6", "fc7", "up1a",
+names = ["conv1_2(+conv1_1)", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2", "fcfold", "up1s",
          "up1b", "up2y", "up2s", "up2b", "up3y", "up3s", "up3b", "up4y", "up4s", "up4b", "cls0", "cls2", "cls4(+tail)"]
 if any("conv3x3_up4" in kn for kn, _ in F):      # upconv4 fused: one launch for the 1x1 over s1 and the 3x3
-    names = names[:22] + ["up4s+up4b (fused)"] + names[24:]
+    i = names.index("up4s")
+    names = names[:i] + ["up4s+up4b (fused)"] + names[i + 2:]
 if any("conv3x3_dma" in kn and len(kn[kn.find("<") + 1:kn.find(">")].split(", ")) > 9 and kn[kn.find("<") + 1:kn.find(">")].split(", ")[9] == "1" for kn, _ in F):      # upconv4's y-half 1x1 applied in upconv3.3x3's epilogue
     i = names.index("up3b")
     names = names[:i] + ["up3b+up4y (fused)"] + names[i + 2:]
