@@ -110,6 +110,15 @@ class bbocr_tiff_plan(C.Structure):
  TIFF_OLD_LZW, TIFF_STRIPS, TIFF_PALETTE) = range(22)
 
 
+class bbocr_tiff_fax(C.Structure):
+    _fields_ = [("scheme", C.c_int), ("t4_options", C.c_int), ("fill_order", C.c_int), ("reason", C.c_int), ("reserved", C.c_int * 4)]
+
+
+# bbocr.h BBOCR_FAX_*: why bbocr_host_tiff_fax_plan refuses a file, and the widest row the CCITT decoder takes
+(FAX_OK, FAX_PLAIN, FAX_FILL_ORDER, FAX_DEPTH, FAX_OPTIONS, FAX_WIDTH) = range(6)
+FAX_MAX_WIDTH = 10240
+
+
 CONV_ROUTE_IDS = ("NONE", "GEN64_P4", "GEN64_P8", "GEN64_P16", "GEN128_P4", "GEN128_P8", "GEN128_P16", "DMA64_FUSE1", "DMA64_POSTW", "RESW_POOL64",
                   "RESW_1CH", "RESW_2CH", "DMA64_324_NF2", "DMA64_324", "DMA64_384", "DMA64_448", "DMA128_384", "DMA128_448", "DMA2X2_64",
                   "DMA2X2_128", "DMA1X1_64", "DMA1X1_128", "DMA1X1_256", "DMA1X1_ADDUP")       # include/bbocr.h BBOCR_ROUTE_*, in order
@@ -281,6 +290,10 @@ PROTOTYPES = {
     "bbocr_tiff_decode": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "bbocr_op_tiff_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
+    "bbocr_host_tiff_fax_plan": (C.c_int, [_vp, C.c_size_t, C.POINTER(bbocr_tiff_plan), C.POINTER(bbocr_tiff_fax)]),
+    "bbocr_tiff_decode_fax": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "bbocr_op_tiff_fax_decode_stage": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t, C.POINTER(C.c_int)]),
 }
 
 class bbocr_gif_plan(C.Structure):

@@ -1,6 +1,9 @@
 // The IFD walk behind bbocr_host_tiff_plan and the device TIFF decoder's admission (tiffdec.cpp): host only, no HIP, so that
 // tools/tiffdec_hostcheck.cpp compiles it as it stands.  One walk over the header and the FIRST IFD (Pillow's frame 0); no strip is decoded.
 // The order of the checks is the order of tests/tiff_decode_ref.py's walk: a file with two faults names the same one in both.
+// tiff_fax_parse (bbocr_host_tiff_fax_plan, the admission of bbocr_tiff_decode_fax) is the same walk in its LENIENT mode -- it notes a CCITT
+// compression and a fill order other than 1, goes on and finishes its checks -- followed by the checks of the CCITT decoder
+// (tests/tiff_fax_ref.py's fax_walk).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -17,11 +20,17 @@ struct TiffParsed {
     uint8_t palette[768] = {0};                      // photometric 3: R G B per index, the ColorMap's high bytes
 };
 
+struct TiffLenient {                                 // what the lenient walk went past
+    bool ccitt = false, fill = false;
+    uint32_t fill_order = 1, options = 0;            // FillOrder as stored; tag 292 (compression 3) or 293 (compression 4)
+    bool options_sound = true;                       // that tag is absent, or a BYTE / SHORT / LONG value inside the file
+};
+
 constexpr long long kTiffStreamMax = 0x7FFFFFFFLL;
 constexpr long long kTiffMaxPixels = 2LL * 89478485LL;   // above it Pillow's decode raises (twice Image.MAX_IMAGE_PIXELS)
 
 // -> the BBOCR_TIFF_* reason (also in ps.plan.reason; plan.supported = 1 for BBOCR_TIFF_OK)
-inline int tiff_parse(const uint8_t* f, size_t n, TiffParsed& ps) {
+inline int tiff_parse(const uint8_t* f, size_t n, TiffParsed& ps, TiffLenient* lenient = nullptr) {
     bbocr_tiff_plan& pl = ps.plan;
     pl = bbocr_tiff_plan{};
     pl.extra_sample = -1;
@@ -47,8 +56,8 @@ inline int tiff_parse(const uint8_t* f, size_t n, TiffParsed& ps) {
 
     // the tags read here; a tag that occurs twice counts as its last entry
     enum { T_WIDTH, T_HEIGHT, T_BITS, T_COMPRESSION, T_PHOTOMETRIC, T_FILL, T_OFFSETS, T_SAMPLES, T_ROWS, T_COUNTS, T_PLANAR, T_PREDICTOR, T_COLORMAP,
-           T_EXTRA, T_FORMAT, T_N };
-    static const uint16_t ids[T_N] = {256, 257, 258, 259, 262, 266, 273, 277, 278, 279, 284, 317, 320, 338, 339};
+           T_EXTRA, T_FORMAT, T_T4OPTIONS, T_T6OPTIONS, T_N };
+    static const uint16_t ids[T_N] = {256, 257, 258, 259, 262, 266, 273, 277, 278, 279, 284, 317, 320, 338, 339, 292, 293};
     long long at_entry[T_N];
     for (int t = 0; t < T_N; ++t) at_entry[t] = -1;
     bool tiles = false;
@@ -96,12 +105,18 @@ inline int tiff_parse(const uint8_t* f, size_t n, TiffParsed& ps) {
     if ((r = scalar(T_COMPRESSION, 1, false, comp))) return refuse(r);
     pl.compression = (int)comp;
     if (comp == 6 || comp == 7) return refuse(BBOCR_TIFF_JPEG);
-    if (comp >= 2 && comp <= 4) return refuse(BBOCR_TIFF_CCITT);
-    if (comp != 1 && comp != 5 && comp != 8 && comp != 32946 && comp != 32773) return refuse(BBOCR_TIFF_COMPRESSION);
+    if (comp >= 2 && comp <= 4) {
+        if (!lenient) return refuse(BBOCR_TIFF_CCITT);
+        lenient->ccitt = true;
+    } else if (comp != 1 && comp != 5 && comp != 8 && comp != 32946 && comp != 32773) return refuse(BBOCR_TIFF_COMPRESSION);
     if ((r = scalar(T_PLANAR, 1, false, planar))) return refuse(r);
     if (planar != 1) return refuse(BBOCR_TIFF_PLANAR);
     if ((r = scalar(T_FILL, 1, false, fill))) return refuse(r);
-    if (fill != 1) return refuse(BBOCR_TIFF_FILL_ORDER);
+    if (fill != 1) {
+        if (!lenient) return refuse(BBOCR_TIFF_FILL_ORDER);
+        lenient->fill = true;
+        lenient->fill_order = fill;
+    }
     if ((r = scalar(T_SAMPLES, 1, false, samples))) return refuse(r);
     if (samples == 0 || samples > 64) return refuse(BBOCR_TIFF_SAMPLES);
     pl.samples = (int)samples;
@@ -166,9 +181,45 @@ inline int tiff_parse(const uint8_t* f, size_t n, TiffParsed& ps) {
         pl.strip_bytes += counts[s];
     }
     if (comp == 5 && counts[0] >= 2 && f[offs[0]] == 0 && (f[offs[0] + 1] & 1)) return refuse(BBOCR_TIFF_OLD_LZW);
+    if (lenient && (comp == 3 || comp == 4)) {
+        lenient->options_sound = !values(comp == 3 ? T_T4OPTIONS : T_T6OPTIONS, v, has);
+        lenient->options = has && lenient->options_sound ? v[0] : 0;
+    }
     pl.supported = 1;
     pl.reason = BBOCR_TIFF_OK;
     return BBOCR_TIFF_OK;
+}
+
+// -> ps.plan.supported; ps.plan as for a supported file when the plain or the fax plan takes it, else with the plain walk's reason
+inline bool tiff_fax_parse(const uint8_t* f, size_t n, TiffParsed& ps, bbocr_tiff_fax& fax) {
+    fax = bbocr_tiff_fax{};
+    fax.fill_order = 1;
+    TiffLenient seen;
+    const int r = tiff_parse(f, n, ps, &seen);
+    bbocr_tiff_plan& pl = ps.plan;
+    if (!seen.ccitt && !seen.fill) {
+        fax.reason = r == BBOCR_TIFF_OK ? BBOCR_FAX_OK : BBOCR_FAX_PLAIN;
+        return r == BBOCR_TIFF_OK;
+    }
+    fax.fill_order = (int)seen.fill_order;
+    if (r != BBOCR_TIFF_OK) {
+        fax.reason = BBOCR_FAX_PLAIN;
+        return false;
+    }
+    fax.scheme = seen.ccitt ? pl.compression : 0;
+    fax.t4_options = (int)seen.options;
+    auto refuse = [&](int reason) {
+        pl.supported = 0;
+        pl.reason = seen.ccitt ? BBOCR_TIFF_CCITT : BBOCR_TIFF_FILL_ORDER;
+        fax.reason = reason;
+        return false;
+    };
+    if (!seen.options_sound) return refuse(BBOCR_FAX_OPTIONS);
+    if ((seen.fill_order != 1 && seen.fill_order != 2) || !seen.ccitt) return refuse(BBOCR_FAX_FILL_ORDER);
+    if (pl.bits != 1 || pl.samples != 1) return refuse(BBOCR_FAX_DEPTH);       // (one 1-bit sample: the walk has refused a photometric above 1)
+    if (seen.options & (pl.compression == 3 ? ~5u : ~0u)) return refuse(BBOCR_FAX_OPTIONS);
+    if (pl.width > BBOCR_FAX_MAX_WIDTH) return refuse(BBOCR_FAX_WIDTH);
+    return true;
 }
 
 // rows of strip s

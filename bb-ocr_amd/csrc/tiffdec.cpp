@@ -11,6 +11,7 @@ using namespace tiff_host;
 
 struct TiffJob {                               // one admitted file of a batch
     TiffParsed ps;
+    bbocr_tiff_fax fax{};                      // scheme 0: a file of the plain plan
     const uint8_t* file = nullptr;
     int k = 0;                                 // its index in the caller's arrays
     uint8_t *rgb = nullptr, *gray = nullptr;   // null: into the batch's own planes (the stage entry point)
@@ -36,7 +37,10 @@ size_t job_pieces(const TiffJob& j) {
     return n;
 }
 
-int codec_of(int compression) { return compression == 1 ? TD_RAW : (compression == 32773 ? TD_PACKBITS : (compression == 5 ? TD_LZW : TD_DEFLATE)); }
+int codec_of(int compression) {
+    if (compression >= 2 && compression <= 4) return TD_FAX;       // (only a file admitted under the fax plan)
+    return compression == 1 ? TD_RAW : (compression == 32773 ? TD_PACKBITS : (compression == 5 ? TD_LZW : TD_DEFLATE));
+}
 
 // The decode of the admitted jobs up to `stages` launches (1: strips, 2: + predictor, 3: + output) on the lane's stream.  Fills
 // dev_status[i] (the error bits of job i: its strips' ORed) and, for the stage entry point, the descriptors.  Everything queued is
@@ -51,6 +55,7 @@ void tiff_run(bbocr_ctx* root, hipStream_t st, std::vector<TiffJob>& jobs, int s
     unsigned long long max_pixels = 1;
     int max_pred_rows = 0;
     bool any_lzw = false, any_deflate = false;
+    int fax_width = 0;                         // the widest CCITT file: it sizes the strip launch's line buffers
     for (TiffJob& j : jobs) {
         const bbocr_tiff_plan& pl = j.ps.plan;
         j.o_strip.clear();
@@ -65,6 +70,7 @@ void tiff_run(bbocr_ctx* root, hipStream_t st, std::vector<TiffJob>& jobs, int s
         if (pl.predictor == 2) max_pred_rows = std::max(max_pred_rows, pl.height);
         any_lzw |= pl.compression == 5;
         any_deflate |= pl.compression == 8 || pl.compression == 32946;
+        if (j.fax.scheme) fax_width = std::max(fax_width, pl.width);
     }
     root->jd_pin.ensure(in.off);
     root->jd_in.ensure(in.off);
@@ -108,6 +114,8 @@ void tiff_run(bbocr_ctx* root, hipStream_t st, std::vector<TiffJob>& jobs, int s
                 t.src_bytes = (unsigned)(pieces > 1 ? (stored > from ? std::min(stored - from, kRawPiece) : 0) : stored);
                 t.need = (unsigned)(pieces > 1 ? std::min(need - from, kRawPiece) : need);
                 t.codec = codec_of(pl.compression);
+                t.fax_width = pl.width;
+                t.fax_mode = j.fax.scheme | (j.fax.t4_options & 255) << 8 | j.fax.fill_order << 16;
                 strips[at] = t;
             }
         }
@@ -116,7 +124,7 @@ void tiff_run(bbocr_ctx* root, hipStream_t st, std::vector<TiffJob>& jobs, int s
     HIPCHK(hipMemcpyAsync(db, hb, in.off, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(wb, 0, status_bytes, st));
     const TdDesc* dd = (const TdDesc*)db;
-    HIPCHK(launch_td_strips((const TdStrip*)(db + desc_bytes), (int)total_strips, td_strips_lds(any_lzw, any_deflate), st));
+    HIPCHK(launch_td_strips((const TdStrip*)(db + desc_bytes), (int)total_strips, td_strips_lds(any_lzw, any_deflate, fax_width), st));
     if (stages >= 2 && max_pred_rows > 0) HIPCHK(launch_td_predictor(dd, n, max_pred_rows, st));
     if (stages >= 3) HIPCHK(launch_td_output(dd, n, max_pixels, st));
     dev_status.assign((size_t)n, 0);
@@ -124,28 +132,16 @@ void tiff_run(bbocr_ctx* root, hipStream_t st, std::vector<TiffJob>& jobs, int s
     HIPCHK(hipStreamSynchronize(st));
 }
 
-// a file the decoder takes: planned here, so that the caller's claim is never trusted
-bool tiff_admit(const uint8_t* file, size_t bytes, TiffJob& j) {
+// a file the decoder takes: planned here, so that the caller's claim is never trusted.  fax: under the fax plan (CCITT files as well)
+bool tiff_admit(const uint8_t* file, size_t bytes, TiffJob& j, bool fax = false) {
     if (!file || bytes >= ((size_t)1 << 31)) return false;
-    if (tiff_parse(file, bytes, j.ps) != BBOCR_TIFF_OK) return false;
+    if (fax ? !tiff_fax_parse(file, bytes, j.ps, j.fax) : tiff_parse(file, bytes, j.ps) != BBOCR_TIFF_OK) return false;
     j.file = file;
     return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bbocr_host_tiff_plan(const void* file, size_t bytes, bbocr_tiff_plan* plan) {
-    if (!file || !plan) return BBOCR_ERR_ARG;
-    TiffParsed ps;
-    tiff_parse((const uint8_t*)file, bytes, ps);
-    *plan = ps.plan;
-    return BBOCR_OK;
-}
-
-int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
-                      uint8_t* const* dst_gray, const long long* pitch_gray, int* status) {
+int decode_batch(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                 uint8_t* const* dst_gray, const long long* pitch_gray, int* status, bool fax) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
         if (!files || !bytes || !dst_rgb || !pitch_rgb || !dst_gray || !pitch_gray || !status || n < 1) fail(BBOCR_ERR_ARG, "bad decode arguments");
         std::vector<TiffJob> jobs;
@@ -154,7 +150,7 @@ int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
         for (int k = 0; k < n; ++k) {
             status[k] = BBOCR_ERR_ARG;
             TiffJob j;
-            if (!tiff_admit(files[k], bytes[k], j)) continue;
+            if (!tiff_admit(files[k], bytes[k], j, fax)) continue;
             const bbocr_tiff_plan& pl = j.ps.plan;
             if (!dst_rgb[k] || !dst_gray[k] || pitch_rgb[k] < 3LL * pl.width || pitch_gray[k] < (long long)pl.width) continue;
             if (total_strips + job_pieces(j) > 0x7FFFFFFFu) continue;             // (one strip per workgroup of a one-dimensional grid)
@@ -173,11 +169,11 @@ int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
     });
 }
 
-int bbocr_op_tiff_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status) {
+int decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status, bool fax) {
     return lane_guarded(ctx, &bbocr_ctx::jpeg_lane, true, [&](hipStream_t st) {
         if (!file || !dev_dst || stage < 0 || stage > 2) fail(BBOCR_ERR_ARG, "bad stage arguments");
         std::vector<TiffJob> jobs(1);
-        if (!tiff_admit(file, bytes, jobs[0])) fail(BBOCR_ERR_ARG, "the plan refuses this file");
+        if (!tiff_admit(file, bytes, jobs[0], fax)) fail(BBOCR_ERR_ARG, "the plan refuses this file");
         const bbocr_tiff_plan& pl = jobs[0].ps.plan;
         const size_t px = (size_t)pl.height * (size_t)pl.width;
         const size_t need = stage < 2 ? stream_bytes(pl) : 4 * px;
@@ -194,6 +190,44 @@ int bbocr_op_tiff_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes
         }
         HIPCHK(hipStreamSynchronize(st));
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbocr_host_tiff_plan(const void* file, size_t bytes, bbocr_tiff_plan* plan) {
+    if (!file || !plan) return BBOCR_ERR_ARG;
+    TiffParsed ps;
+    tiff_parse((const uint8_t*)file, bytes, ps);
+    *plan = ps.plan;
+    return BBOCR_OK;
+}
+
+int bbocr_host_tiff_fax_plan(const void* file, size_t bytes, bbocr_tiff_plan* plan, bbocr_tiff_fax* fax) {
+    if (!file || !plan || !fax) return BBOCR_ERR_ARG;
+    TiffParsed ps;
+    tiff_fax_parse((const uint8_t*)file, bytes, ps, *fax);
+    *plan = ps.plan;
+    return BBOCR_OK;
+}
+
+int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                      uint8_t* const* dst_gray, const long long* pitch_gray, int* status) {
+    return decode_batch(ctx, files, bytes, n, dst_rgb, pitch_rgb, dst_gray, pitch_gray, status, false);
+}
+
+int bbocr_tiff_decode_fax(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                          uint8_t* const* dst_gray, const long long* pitch_gray, int* status) {
+    return decode_batch(ctx, files, bytes, n, dst_rgb, pitch_rgb, dst_gray, pitch_gray, status, true);
+}
+
+int bbocr_op_tiff_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status) {
+    return decode_stage(ctx, file, bytes, stage, dev_dst, dst_bytes, file_status, false);
+}
+
+int bbocr_op_tiff_fax_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status) {
+    return decode_stage(ctx, file, bytes, stage, dev_dst, dst_bytes, file_status, true);
 }
 
 }  // extern "C"

@@ -6,7 +6,9 @@
 //                 every lane runs the code loop on the same values and the lanes share out the copy; Deflate: png_inflate.h under
 //                 pngdec.hip's wave policy, the zlib header and the Adler-32 checked per strip.  LDS per wavefront: 32 KB when the batch
 //                 holds an LZW strip (five wavefronts on a CU's 160 KB), sizeof(PngiTables) when it holds Deflate strips only, none
-//                 otherwise.
+//                 otherwise.  CCITT (TD_FAX, batches of bbocr_tiff_decode_fax only): tiff_fax.h under the wave policy below -- a code
+//                 is resolved by one ballot over the lanes' code words, a row is kept as its changing elements in LDS and rendered by
+//                 all lanes; fax_lds_bytes(the batch's widest CCITT file) of LDS, whichever of the sizes above is larger.
 //   td_predictor  predictor 2, in place: one wavefront per row, a prefix sum modulo 256 per sample position -- 64 pixels per step, a wave
 //                 scan, the carry handed from segment to segment.
 //   td_output     fully parallel: both planes by reader.decode_file's rule.
@@ -39,6 +41,83 @@ struct PngiWaveT {                                        // pngdec.hip's policy
         for (int i = (int)threadIdx.x; i < len; i += kWave) out[o + i] = from[dist >= (uint32_t)len ? (uint32_t)i : (uint32_t)i % dist];
     }
 };
+
+struct FaxWave {                                          // tiff_fax.h's policy for a workgroup of ONE wavefront
+    struct Words {                                        // lane l: words l and 64 + l of both colours
+        uint32_t key[2][2];                               // the word left-aligned in 16 bits | the mask of its length << 16
+        uint32_t meta[2][2];                              // length | run << 8; 0: no word (lanes 40 .. 63 of the second set)
+    };
+    __device__ static void load(Words& w) {
+        for (int c = 0; c < 2; ++c)
+            for (int s = 0; s < 2; ++s) {
+                const int i = 64 * s + (int)threadIdx.x;
+                w.key[c][s] = w.meta[c][s] = 0;
+                if (i < FAX_WORDS) {
+                    const FaxWord f = fax_word(c, i);
+                    w.key[c][s] = ((uint32_t)f.code << (16 - f.len)) | ((0xFFFFu << (16 - f.len)) & 0xFFFFu) << 16;
+                    w.meta[c][s] = (uint32_t)f.len | (uint32_t)fax_word_run(i) << 8;
+                }
+            }
+    }
+    __device__ static uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+    __device__ static void sync() { __syncthreads(); }
+    __device__ static bool resolve(const Words& w, int colour, uint32_t head16, int& len, int& run) {
+        const uint32_t k0 = colour ? w.key[1][0] : w.key[0][0], k1 = colour ? w.key[1][1] : w.key[0][1];
+        const uint32_t m0 = colour ? w.meta[1][0] : w.meta[0][0], m1 = colour ? w.meta[1][1] : w.meta[0][1];
+        const unsigned long long hit0 = __ballot(m0 && !((head16 ^ k0) & (k0 >> 16)));
+        const unsigned long long hit1 = __ballot(m1 && !((head16 ^ k1) & (k1 >> 16)));
+        if (!(hit0 | hit1)) return false;                 // (the words are prefix-free: at most one lane of one set matches)
+        const int lane = hit0 ? __ffsll(hit0) - 1 : __ffsll(hit1) - 1;
+        const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)(hit0 ? m0 : m1), lane);
+        len = (int)(m & 255u);
+        run = (int)(m >> 8);
+        return true;
+    }
+    __device__ static void put(uint16_t* line, int i, int v) {
+        if (threadIdx.x == 0) line[i] = (uint16_t)v;
+    }
+    __device__ static int get(const uint16_t* line, int i) { return __builtin_amdgcn_readfirstlane((int)line[i]); }
+    // the n changing elements -> the row's bytes: toggles in the bitmap, a prefix XOR over it, the words stored byte by byte
+    __device__ static void render(const uint16_t* cur, int n, int W, uint32_t* bitmap, uint8_t* out, size_t row_bytes) {
+        const int lane = (int)threadIdx.x, words = (W + 31) / 32;
+        for (int i = lane; i < words; i += kWave) bitmap[i] = 0;
+        __syncthreads();
+        for (int i = lane; i < n; i += kWave) {
+            const int c = cur[i];
+            if (c < W) atomicXor(&bitmap[c >> 5], 0x80000000u >> (c & 31));
+        }
+        __syncthreads();
+        uint32_t carry = 0;                               // the colour at the start of this step's words
+        for (int base = 0; base < words; base += kWave) {
+            const int i = base + lane;
+            const uint32_t t = i < words ? bitmap[i] : 0;
+            uint32_t v = t;
+            v ^= v >> 1;
+            v ^= v >> 2;
+            v ^= v >> 4;
+            v ^= v >> 8;
+            v ^= v >> 16;                                 // bit j from the top = the XOR of the toggles 0 .. j
+            const unsigned long long odd = __ballot(__popc(t) & 1);
+            if ((__popcll(odd & ((1ull << lane) - 1)) & 1) ^ carry) v = ~v;
+            carry ^= (uint32_t)__popcll(odd) & 1u;
+            if (i == words - 1 && (W & 31)) v &= ~0u << (32 - (W & 31));      // the bits behind the width are 0
+            if (i < words)
+                for (int k = 0; k < 4; ++k)
+                    if ((size_t)(4 * i + k) < row_bytes) out[4 * i + k] = (uint8_t)(v >> (24 - 8 * k));
+        }
+        __syncthreads();                                  // (the bitmap is free for the next row)
+    }
+};
+
+__device__ inline int strip_fax(const TdStrip& s, unsigned char* lds) {
+    const int W = s.fax_width;
+    const size_t row_bytes = ((size_t)W + 7) / 8;
+    uint16_t* line0 = (uint16_t*)lds;
+    uint16_t* line1 = (uint16_t*)(lds + fax_line_bytes(W));
+    uint32_t* bitmap = (uint32_t*)(lds + 2 * fax_line_bytes(W));
+    return fax_decode_strip<FaxWave>(s.src, s.src_bytes, s.dst, W, (int)(s.need / row_bytes), s.fax_mode & 255, (s.fax_mode >> 8) & 255, s.fax_mode >> 16,
+                                     line0, line1, bitmap);
+}
 
 __device__ inline int strip_deflate(const TdStrip& s, PngiTables& T) {
     if (!tiffc_zlib_header_ok(s.src, s.src_bytes)) return PNGI_ERR_ZLIB;
@@ -81,6 +160,8 @@ __global__ __launch_bounds__(kWave) void td_strips(const TdStrip* strips) {
         err = tiffc_packbits<TiffcWave>(s.src, s.src_bytes, s.dst, s.need);
     } else if (s.codec == TD_LZW) {
         err = tiffc_lzw<TiffcWave>(s.src, s.src_bytes, s.dst, s.need, (TiffcEntry*)lds);
+    } else if (s.codec == TD_FAX) {
+        err = strip_fax(s, lds);
     } else {
         err = strip_deflate(s, *(PngiTables*)lds);
     }
@@ -147,8 +228,10 @@ __global__ __launch_bounds__(256) void td_output(const TdDesc* descs) {
 
 }  // namespace
 
-size_t td_strips_lds(bool any_lzw, bool any_deflate) {
-    return any_lzw ? sizeof(TiffcEntry) * (size_t)TIFFC_LZW_ENTRIES : (any_deflate ? sizeof(PngiTables) : 0);
+size_t td_strips_lds(bool any_lzw, bool any_deflate, int fax_width) {
+    const size_t plain = any_lzw ? sizeof(TiffcEntry) * (size_t)TIFFC_LZW_ENTRIES : (any_deflate ? sizeof(PngiTables) : 0);
+    const size_t fax = fax_width > 0 ? fax_lds_bytes(fax_width) : 0;
+    return plain > fax ? plain : fax;
 }
 
 hipError_t launch_td_strips(const TdStrip* s, int n, size_t lds_bytes, hipStream_t st) {

@@ -42,12 +42,21 @@ def _png_page(source):
     return None if page is None else ("png", page, None)
 
 
-def _tiff_page(source):
-    """``("tiff", TiffPage, None)`` when the device TIFF decoder takes the file (a path or its bytes), else None"""
+def _tiff_page(source, tiff_decode=True):
+    """``("tiff", TiffPage, None)`` when the device TIFF decoder takes the file (a path or its bytes), else None.  ``tiff_decode``: the
+    option's level as ``_tiff_level`` gives it -- with ``"fax"`` a CCITT file is taken as well"""
     from .reader import tiff_page
 
-    page = tiff_page(source)
+    page = tiff_page(source, tiff_decode == "fax")
     return None if page is None else ("tiff", page, None)
+
+
+def _tiff_level(reader, tiff_decode):
+    """the ``tiff_decode`` keyword of a caller (None: the Reader's) -> False, True or ``"fax"``"""
+    from .reader import tiff_fax
+
+    value = getattr(reader, "tiff_decode", False) if tiff_decode is None else tiff_decode
+    return "fax" if value is not None and tiff_fax(value) else bool(value)
 
 
 def _gif_page(source):
@@ -109,7 +118,7 @@ def _ocr_input(image_path, image_index=None, decode_once=True, device_decode=Fal
     if page is None and png_decode and source is image_path:       # the original file, at or below the limit (a thumbnail is a JPEG)
         page = _png_page(source)
     if page is None and tiff_decode and source is image_path:      # likewise a TIFF file
-        page = _tiff_page(source)
+        page = _tiff_page(source, tiff_decode)
     if page is None and gif_decode and source is image_path:       # likewise a GIF file
         page = _gif_page(source)
     if page is None and bmp_decode and source is image_path:       # likewise a BMP file
@@ -236,13 +245,14 @@ def extract_texts(reader, image_paths, ocr_image_indices=None, max_batch=64, dec
     ``mixed``: ``read_files``' keyword -- pages of different (down-scaled) shapes share device batches.
     ``png_decode`` (None: the Reader's ``png_decode``): a PNG file at or below its page's limit that the device PNG decoder takes reaches
     the card as its bytes (kind ``"png"``); with the crop settings or ``device_thumbnail`` on, and above the limit, a PNG keeps today's path.
-    ``tiff_decode`` (None: the Reader's ``tiff_decode``): the same for a TIFF file the device TIFF decoder takes (kind ``"tiff"``).
+    ``tiff_decode`` (None: the Reader's ``tiff_decode``): the same for a TIFF file the device TIFF decoder takes (kind ``"tiff"``); ``"fax"``:
+    CCITT files as well.
     ``gif_decode`` (None: the Reader's ``gif_decode``): the same for a GIF file the device GIF decoder takes (kind ``"gif"``).
     ``bmp_decode`` (None: the Reader's ``bmp_decode``): the same for a BMP file the device BMP decoder takes (kind ``"bmp"``)."""
     from .preprocess import ocr_input_device
 
     png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
-    tiff_decode = bool(getattr(reader, "tiff_decode", False)) if tiff_decode is None else bool(tiff_decode)
+    tiff_decode = _tiff_level(reader, tiff_decode)
     gif_decode = bool(getattr(reader, "gif_decode", False)) if gif_decode is None else bool(gif_decode)
     bmp_decode = bool(getattr(reader, "bmp_decode", False)) if bmp_decode is None else bool(bmp_decode)
 
@@ -273,7 +283,7 @@ def _plain_input_device(path, i=None, device_decode=True, png_decode=False, tiff
     """``_plain_input`` with the device decoders: the file's bytes when one of them takes them (``png_decode``: PNG files too,
     ``tiff_decode``: TIFF files too, ``gif_decode``: GIF files too, ``bmp_decode``: BMP files too)"""
     return ((_jpg_page(path, device_decode) if device_decode else None) or (_png_page(path) if png_decode else None)
-            or (_tiff_page(path) if tiff_decode else None) or (_gif_page(path) if gif_decode else None)
+            or (_tiff_page(path, tiff_decode) if tiff_decode else None) or (_gif_page(path) if gif_decode else None)
             or (_bmp_page(path) if bmp_decode else None) or _plain_input(path, i))
 
 
@@ -640,7 +650,8 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
     ``tiff_decode`` (None: the Reader's ``tiff_decode``, off by default): likewise TIFF files the device decoder takes (``reader.tiff_plan``:
     strips of raw, PackBits, LZW or Deflate data), kind ``"tiff"``, a group decoded by one ``bbocr_tiff_decode`` call (csrc/tiffdec.hip,
     identical pixels) -- with ``mixed`` the TIFF pages of a batch share one call whatever their shapes; a file the plan refuses (tiles,
-    CCITT, 16 bit, ...) or whose data turns out damaged takes the host decode as before.
+    CCITT, 16 bit, ...) or whose data turns out damaged takes the host decode as before.  ``tiff_decode="fax"``: CCITT files (compression 2,
+    3, 4: ``reader.tiff_fax_plan``) are taken as well, and a call that holds one goes to ``bbocr_tiff_decode_fax`` (csrc/tiff_fax.h).
     ``gif_decode`` (None: the Reader's ``gif_decode``, off by default): likewise GIF files (``reader.gif_plan``), kind ``"gif"``: the group --
     with ``mixed`` every GIF page of the batch, whatever its shape -- is decoded by one ``bbocr_gif_decode`` call (csrc/gifdec.hip, identical
     pixels); a file the plan refuses or whose code stream turns out damaged takes the host decode as before.
@@ -651,7 +662,7 @@ def read_files(reader, image_paths, indices=None, max_batch=64, decode_workers=N
 
     mixed = mixed_batch_enabled(mixed)
     png_decode = bool(getattr(reader, "png_decode", False)) if png_decode is None else bool(png_decode)
-    tiff_decode = bool(getattr(reader, "tiff_decode", False)) if tiff_decode is None else bool(tiff_decode)
+    tiff_decode = _tiff_level(reader, tiff_decode)
     gif_decode = bool(getattr(reader, "gif_decode", False)) if gif_decode is None else bool(gif_decode)
     bmp_decode = bool(getattr(reader, "bmp_decode", False)) if bmp_decode is None else bool(bmp_decode)
     if mixed:

@@ -286,13 +286,16 @@ def png_decode_enabled(png_decode=None):
 class TiffPage:
     """A TIFF file the device decoder takes (``tiff_plan``): its bytes and the shape of its decode, ``(H, W, 3)`` -- every TIFF page has an
     RGB and a gray plane.  The page kind ``"tiff"`` of ``extractor_batch.read_files``: pages of one shape are decoded by one
-    ``bbocr_tiff_decode`` call, and with ``mixed=True`` so are pages of any shapes."""
-    __slots__ = ("data", "shape", "plan")
+    ``bbocr_tiff_decode`` call, and with ``mixed=True`` so are pages of any shapes.  ``fax``: the page is a CCITT file taken under
+    ``tiff_fax_plan`` (``fax_plan``: its ``bbocr_tiff_fax``), so a call that holds it goes to ``bbocr_tiff_decode_fax``."""
+    __slots__ = ("data", "shape", "plan", "fax", "fax_plan")
 
-    def __init__(self, data, plan):
+    def __init__(self, data, plan, fax_plan=None):
         self.data = data
         self.shape = (int(plan.height), int(plan.width), 3)
         self.plan = plan
+        self.fax_plan = fax_plan
+        self.fax = fax_plan is not None and int(fax_plan.scheme) != 0
 
 
 def tiff_plan(data):
@@ -306,18 +309,48 @@ def tiff_plan(data):
     return plan
 
 
-def tiff_page(source):
-    """``TiffPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path)"""
+def tiff_fax_plan(data):
+    """``bbocr_host_tiff_fax_plan`` of a file's bytes (no GPU) -> ``(plan, fax)``: ``tiff_plan``'s walk in the mode that goes on behind a
+    CCITT compression (2, 3, 4) and a fill order other than 1, then the checks of the CCITT decoder.  ``plan.supported``: the plain plan or
+    the fax plan takes the file; ``fax.scheme`` (0: no CCITT file), ``fax.t4_options``, ``fax.fill_order`` and the ``BBOCR_FAX_*``
+    reason."""
+    plan, fax = _lib.bbocr_tiff_plan(), _lib.bbocr_tiff_fax()
+    rc = _lib.load().bbocr_host_tiff_fax_plan(data, len(data), C.byref(plan), C.byref(fax))
+    if rc != 0:
+        raise RuntimeError(f"bbocr_host_tiff_fax_plan failed with status {rc}")
+    return plan, fax
+
+
+def tiff_page(source, fax=False):
+    """``TiffPage`` of a path or a bytes object when the device decoder takes the file, else ``None`` (the caller keeps its host path).
+    ``fax``: under ``tiff_fax_plan``, so a CCITT file is taken as well."""
     try:
         data = _file_bytes(source)
+        if fax:
+            plan, fax_plan = tiff_fax_plan(data)
+            return TiffPage(data, plan, fax_plan) if plan.supported else None
         plan = tiff_plan(data)
         return TiffPage(data, plan) if plan.supported else None
     except Exception:
         return None
 
 
+DECODE_FAX = "fax"
+
+
+def tiff_fax(tiff_decode):
+    """True for ``tiff_decode="fax"`` (None: for ``BBOCR_TIFF_DECODE=fax``): the device TIFF decoder with CCITT files in its scope.  Every
+    other value (``True``, ``"1"``, ``False``) is the plain scope."""
+    if tiff_decode is None:
+        tiff_decode = os.environ.get("BBOCR_TIFF_DECODE", "0")
+    return isinstance(tiff_decode, str) and tiff_decode.strip().lower() == DECODE_FAX
+
+
 def tiff_decode_enabled(tiff_decode=None):
-    """The ``tiff_decode`` keyword: None means the environment variable ``BBOCR_TIFF_DECODE`` (``1`` = on; off when unset)"""
+    """The ``tiff_decode`` keyword: None means the environment variable ``BBOCR_TIFF_DECODE`` (``1`` = on, ``fax`` = on with CCITT files;
+    off when unset).  -> False, True or ``"fax"``"""
+    if tiff_fax(tiff_decode):
+        return DECODE_FAX
     return os.environ.get("BBOCR_TIFF_DECODE", "0").strip() == "1" if tiff_decode is None else bool(tiff_decode)
 
 
@@ -689,7 +722,8 @@ class Reader:
         # PNG files decoded on the card (csrc/pngdec.hip) by readtext(path) and the file callers; an option of its own (None:
         # BBOCR_PNG_DECODE=1), not a value of device_decode, whose strings are a ladder of JPEG scopes; off unless asked for
         self.png_decode = png_decode_enabled(png_decode)
-        # TIFF files decoded on the card (csrc/tiffdec.hip), likewise an option of its own (None: BBOCR_TIFF_DECODE=1); off unless asked for
+        # TIFF files decoded on the card (csrc/tiffdec.hip), likewise an option of its own (None: BBOCR_TIFF_DECODE=1); off unless asked for;
+        # "fax" (BBOCR_TIFF_DECODE=fax): CCITT files as well (csrc/tiff_fax.h)
         self.tiff_decode = tiff_decode_enabled(tiff_decode)
         # GIF files decoded on the card (csrc/gifdec.hip), likewise (None: BBOCR_GIF_DECODE=1); off unless asked for
         self.gif_decode = gif_decode_enabled(gif_decode)
@@ -1273,19 +1307,23 @@ class Reader:
         return out, status
 
     def _tiff_decode_into(self, pages, rgb_ptrs, rgb_pitches, gray_ptrs, gray_pitches):
-        """``bbocr_tiff_decode`` of the pages into the given device addresses and row pitches -> the per-file status list"""
+        """``bbocr_tiff_decode`` of the pages -- ``bbocr_tiff_decode_fax`` when one of them is a CCITT page (``TiffPage.fax``) -- into the
+        given device addresses and row pitches -> the per-file status list"""
         n = len(pages)
         files, sizes = self._jpeg_files(pages)
         status = (C.c_int * n)()
         self._torch.cuda.current_stream(self.device_index).synchronize()      # the library runs on its own stream
-        self._check(self._lib.bbocr_tiff_decode(self._h, files, sizes, n, (C.c_void_p * n)(*rgb_ptrs), (C.c_longlong * n)(*rgb_pitches),
-                                                (C.c_void_p * n)(*gray_ptrs), (C.c_longlong * n)(*gray_pitches), status))
+        call = self._lib.bbocr_tiff_decode_fax if any(getattr(p, "fax", False) for p in pages) else self._lib.bbocr_tiff_decode
+        self._check(call(self._h, files, sizes, n, (C.c_void_p * n)(*rgb_ptrs), (C.c_longlong * n)(*rgb_pitches),
+                   (C.c_void_p * n)(*gray_ptrs), (C.c_longlong * n)(*gray_pitches), status))
         return list(status)
 
-    def decode_tiff_device(self, sources):
+    def decode_tiff_device(self, sources, fax=None):
         """Paths or bytes objects -> per source ``(rgb_dev [H,W,3], gray_dev [H,W])`` as ``decode_file`` defines them, decoded on the card,
-        or ``None`` for a file the plan refuses or whose data is damaged.  All the files share one decode call."""
-        pages = [tiff_page(s) for s in sources]
+        or ``None`` for a file the plan refuses or whose data is damaged.  All the files share one decode call.  ``fax`` (None: the
+        Reader's ``tiff_decode`` is ``"fax"``): CCITT files as well."""
+        fax = tiff_fax(getattr(self, "tiff_decode", False)) if fax is None else bool(fax)
+        pages = [tiff_page(s, fax) for s in sources]
         out = [None] * len(pages)
         idxs = [i for i, p in enumerate(pages) if p is not None]
         if idxs:
@@ -1295,12 +1333,16 @@ class Reader:
                     out[i] = planes[k]
         return out
 
-    def tiff_decode_stage(self, source, stage):
+    def tiff_fax_decode_stage(self, source, stage):
+        """``bbocr_op_tiff_fax_decode_stage``: ``tiff_decode_stage`` for the files ``tiff_fax_plan`` supports, CCITT files among them"""
+        return self.tiff_decode_stage(source, stage, fax=True)
+
+    def tiff_decode_stage(self, source, stage, fax=False):
         """``bbocr_op_tiff_decode_stage`` of one file (path or bytes) -> ``(array, file status)``: stage 0 the strips' decoded stream
         ``uint8 [H * row_bytes]``, 1 the same after the predictor, 2 ``(rgb [H,W,3], gray [H,W])``"""
         torch = self._torch
         data = _file_bytes(source)
-        plan = tiff_plan(data)
+        plan = tiff_fax_plan(data)[0] if fax else tiff_plan(data)
         if not plan.supported or stage not in (0, 1, 2):
             raise ValueError("tiff_decode_stage: a file the plan supports and stage 0, 1 or 2")
         H, W = int(plan.height), int(plan.width)
@@ -1308,7 +1350,8 @@ class Reader:
         out = torch.empty(nb, dtype=torch.uint8, device=self.device)
         st = C.c_int()
         torch.cuda.current_stream(self.device_index).synchronize()
-        self._check(self._lib.bbocr_op_tiff_decode_stage(self._h, data, len(data), stage, C.c_void_p(out.data_ptr()), nb, C.byref(st)))
+        call = self._lib.bbocr_op_tiff_fax_decode_stage if fax else self._lib.bbocr_op_tiff_decode_stage
+        self._check(call(self._h, data, len(data), stage, C.c_void_p(out.data_ptr()), nb, C.byref(st)))
         a = out.cpu().numpy()
         if stage < 2:
             return a, st.value

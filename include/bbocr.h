@@ -983,6 +983,50 @@ int bbocr_tiff_decode(bbocr_ctx* ctx, const uint8_t* const* files, const size_t*
                       uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
 int bbocr_op_tiff_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
 
+/* ---- CCITT TIFF files decoded on the device (csrc/tiff_fax.h, the codec TD_FAX of csrc/tiffdec.hip; opt-in on top of the TIFF decoder:
+ * Reader(tiff_decode="fax")): what document scanners and fax gateways write for a bitonal page.  Scope: compression 2 (modified Huffman:
+ * rows start on a byte boundary, no EOL), 3 (T.4: 1-D, or 2-D with T4Options bit 0; with or without the byte-aligned EOLs of bit 2) and
+ * 4 (T.6); one 1-bit sample, photometric 0 or 1, either byte order, any RowsPerStrip, FillOrder 1 or 2 (with 2 the bits of every stored
+ * byte are reversed on read).  A white run decodes to 0 bits and a black run to 1 bits; the output pass applies the photometric tag as it
+ * does for any 1-bit file.  The reference line of a strip's first row is white.  Accepted: any number of make-up codes before a
+ * terminating code, a zero-length white run at the start of a row, any number of 0 fill bits before an EOL, a leading EOL; bytes behind
+ * the strip's last row (RTC, EOFB) are not read.  STRICTER than libtiff, which patches a bad line and carries on: a strip is decoded
+ * exactly or the file gets BBOCR_ERR_DATA (and its caller takes the host decode) -- a bit pattern that is no code, an extension
+ * (uncompressed mode) code, a row whose runs do not end exactly at the width, a vertical mode that does not move a0 forwards or moves it
+ * past the width, a pass mode whose b2 is the end of the line, a T.4 row without its EOL or tag bit, input that ends early.  Defined by
+ * tests/tiff_fax_ref.py.
+ * The widest row the decoder's line buffers hold (two lists of changing elements and the row's bitmap in LDS, 42,272 bytes at the limit;
+ * A3 at 600 dpi is 7016 pixels wide): */
+#define BBOCR_FAX_MAX_WIDTH 10240
+enum {
+    BBOCR_FAX_OK = 0,           /* the plain plan or the fax plan takes the file */
+    BBOCR_FAX_PLAIN = 1,        /* the walk refuses the file for something other than CCITT or fill order: plan.reason says what (a
+                                 * photometric above 1 is among these: the walk refuses it on one 1-bit sample, DEPTH or PHOTOMETRIC) */
+    BBOCR_FAX_FILL_ORDER = 2,   /* a FillOrder other than 1 or 2, or FillOrder 2 on a file that is not CCITT */
+    BBOCR_FAX_DEPTH = 3,        /* BitsPerSample or SamplesPerPixel other than 1 */
+    BBOCR_FAX_OPTIONS = 4,      /* the uncompressed-mode bit or an unknown bit of T4Options (292) / T6Options (293), or a malformed tag */
+    BBOCR_FAX_WIDTH = 5         /* wider than BBOCR_FAX_MAX_WIDTH */
+};
+typedef struct bbocr_tiff_fax {
+    int scheme;                 /* 0: no CCITT file; else the compression, 2, 3 or 4 */
+    int t4_options;             /* tag 292 of a compression-3 file, tag 293 of a compression-4 file; 0 when absent */
+    int fill_order;             /* FillOrder as stored (1 when absent or not reached) */
+    int reason;                 /* BBOCR_FAX_* */
+    int reserved[4];
+} bbocr_tiff_fax;
+/* bbocr_host_tiff_fax_plan: host only, no GPU: bbocr_host_tiff_plan's walk in the mode that goes on behind a CCITT compression and a fill
+ * order other than 1 and finishes its remaining checks, then the checks above in the order of the enum.  plan: as bbocr_host_tiff_plan fills
+ * it for a supported file (supported 1, reason 0) when either plan takes the file; when the walk refuses the file for another reason, as
+ * it left it (fax->reason BBOCR_FAX_PLAIN); when the fax checks refuse it, every field filled, supported 0 and reason BBOCR_TIFF_CCITT
+ * or BBOCR_TIFF_FILL_ORDER.  bbocr_host_tiff_plan itself answers as before for every file.
+ * bbocr_tiff_decode_fax / bbocr_op_tiff_fax_decode_stage: the contracts of bbocr_tiff_decode / bbocr_op_tiff_decode_stage with the files
+ * admitted by bbocr_host_tiff_fax_plan, so a batch may mix CCITT files with raw, PackBits, LZW and Deflate ones; still three launches, the
+ * CCITT strips one wavefront each in the strip launch.  bbocr_tiff_decode and bbocr_op_tiff_decode_stage keep refusing a CCITT file. */
+int bbocr_host_tiff_fax_plan(const void* file, size_t bytes, bbocr_tiff_plan* plan, bbocr_tiff_fax* fax);
+int bbocr_tiff_decode_fax(bbocr_ctx* ctx, const uint8_t* const* files, const size_t* bytes, int n, uint8_t* const* dst_rgb, const long long* pitch_rgb,
+                          uint8_t* const* dst_gray, const long long* pitch_gray, int* status);
+int bbocr_op_tiff_fax_decode_stage(bbocr_ctx* ctx, const uint8_t* file, size_t bytes, int stage, void* dev_dst, size_t dst_bytes, int* file_status);
+
 /* ---- GIF files decoded on the device (csrc/gifdec.hip; opt-in: Reader(gif_decode=True)): what reader.decode_file holds for a GIF file
  * -- Pillow's convert("RGB") of frame 0 and the gray plane of its stated rule -- from the file's bytes, of which only the de-framed LZW
  * payload and the colour table cross the link.  The code stream is split at its clear codes: the width of a GIF code depends only on the
