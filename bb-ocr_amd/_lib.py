@@ -136,6 +136,16 @@ class bbocr_conv_route(C.Structure):
         return d
 
 
+PP_ROUTE_IDS = ("GAUSS_X4", "GAUSS_BYTE", "HIST_X4", "HIST_BYTE", "APPLY_CELL_2", "APPLY_CELL_8", "APPLY_CELL_32", "APPLY_VEC", "APPLY_BYTE",
+                "BOX0_X4", "BOX_BYTE", "UNSHARP_FUSED", "UNSHARP_PASSES_VEC", "UNSHARP_PASSES_BYTE", "RESIZE_TILED32", "RESIZE_TILED16",
+                "RESIZE_PIXEL")                                                  # include/bbocr.h BBOCR_PP_*, in order
+# which of them each bbocr_host_pp_<key>_route may return
+PP_ROUTES_OF = {"gauss": ("GAUSS_X4", "GAUSS_BYTE"), "clahe_hist": ("HIST_X4", "HIST_BYTE"),
+                "clahe_apply": ("APPLY_CELL_2", "APPLY_CELL_8", "APPLY_CELL_32", "APPLY_VEC", "APPLY_BYTE"), "box": ("BOX0_X4", "BOX_BYTE"),
+                "unsharp": ("UNSHARP_FUSED", "UNSHARP_PASSES_VEC", "UNSHARP_PASSES_BYTE"),
+                "resize": ("RESIZE_TILED32", "RESIZE_TILED16", "RESIZE_PIXEL")}
+
+
 class bbocr_page(C.Structure):
     _fields_ = [("dev_rgb", C.c_void_p), ("dev_gray", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("rgb_pitch", C.c_longlong),
                 ("gray_pitch", C.c_longlong)]
@@ -233,6 +243,14 @@ PROTOTYPES = {
     "bbocr_preproc_defaults": (None, [C.POINTER(bbocr_preproc_params), C.c_int]),
     "bbocr_preprocess_chain": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(bbocr_preproc_params), _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bbocr_op_preprocess_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double]),
+    "bbocr_host_pp_resize_route": (C.c_int, [C.c_int] * 4),
+    "bbocr_host_pp_resize_dword_rows": (C.c_int, [C.c_int] * 2),
+    "bbocr_host_pp_gauss_route": (C.c_int, [C.c_int] * 4),
+    "bbocr_host_pp_clahe_hist_route": (C.c_int, [C.c_int] * 3),
+    "bbocr_host_pp_clahe_apply_route": (C.c_int, [C.c_int] * 4),
+    "bbocr_host_pp_box_route": (C.c_int, [C.c_int] * 5),
+    "bbocr_host_pp_unsharp_route": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]),
+    "bbocr_host_pp_unsharp_box_radius": (C.c_int, [C.c_double]),
     "bbocr_auto_crop": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "bbocr_op_autocrop_stage": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_longlong, C.c_int, _vp]),

@@ -105,6 +105,46 @@ int bbocr_op_preprocess_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src,
     });
 }
 
+// Which kernel a stage of bbocr_op_preprocess_stage takes for a plane of this size at pointers with these low two bits: the launchers' own
+// decision functions (preproc.hip), so no device and no context.  The stage's scratch planes are the library's allocations (aligned).
+static bool pp_route_args(int H, int W, int a, int b) { return H > 0 && W > 0 && a >= 0 && a <= 3 && b >= 0 && b <= 3; }
+int bbocr_host_pp_resize_route(int H, int W, int dh, int dw) {
+    if (H <= 0 || W <= 0 || dh <= 0 || dw <= 0) return BBOCR_ERR_ARG;
+    return (int)pp_resize_route(H, W, dh, dw);
+}
+int bbocr_host_pp_resize_dword_rows(int dw, int dst_bits) {
+    if (dw <= 0 || dst_bits < 0 || dst_bits > 3) return BBOCR_ERR_ARG;
+    return pp_resize_dword_rows(dw, (unsigned)dst_bits) ? 1 : 0;
+}
+int bbocr_host_pp_gauss_route(int H, int W, int src_bits, int dst_bits) {
+    if (!pp_route_args(H, W, src_bits, dst_bits)) return BBOCR_ERR_ARG;
+    return (int)pp_gauss_route(H, W, (unsigned)src_bits, (unsigned)dst_bits);
+}
+int bbocr_host_pp_clahe_hist_route(int H, int W, int src_bits) {
+    int th = 0, tw = 0;
+    if (!pp_route_args(H, W, src_bits, 0) || !pp_clahe_tiles(H, W, &th, &tw)) return BBOCR_ERR_ARG;
+    return (int)pp_clahe_hist_route(H, W, (unsigned)src_bits);
+}
+int bbocr_host_pp_clahe_apply_route(int H, int W, int src_bits, int dst_bits) {
+    int th = 0, tw = 0;
+    if (!pp_route_args(H, W, src_bits, dst_bits) || !pp_clahe_tiles(H, W, &th, &tw)) return BBOCR_ERR_ARG;
+    return (int)pp_clahe_apply_route(H, W, th, (unsigned)src_bits, (unsigned)dst_bits);
+}
+int bbocr_host_pp_box_route(int H, int W, int r, int src_bits, int dst_bits) {
+    if (!pp_route_args(H, W, src_bits, dst_bits) || r < 0) return BBOCR_ERR_ARG;
+    return (int)pp_box_route(H, W, r, (unsigned)src_bits, (unsigned)dst_bits);
+}
+int bbocr_host_pp_unsharp_route(int H, int W, double radius, int src_bits, int dst_bits) {
+    if (!pp_route_args(H, W, src_bits, dst_bits) || !(radius > 0)) return BBOCR_ERR_ARG;
+    return (int)pp_unsharp_route(H, W, pp_unsharp_box_r((float)radius), (unsigned)src_bits, 0u, (unsigned)dst_bits);
+}
+int bbocr_host_pp_unsharp_box_radius(double radius) { return radius > 0 ? pp_unsharp_box_r((float)radius) : BBOCR_ERR_ARG; }
+static_assert(BBOCR_PP_ROUTE_COUNT == (int)PP_ROUTE_COUNT && BBOCR_PP_GAUSS_BYTE == (int)PP_GAUSS_BYTE && BBOCR_PP_HIST_BYTE == (int)PP_HIST_BYTE &&
+                  BBOCR_PP_APPLY_CELL_2 == (int)PP_APPLY_CELL_2 && BBOCR_PP_APPLY_BYTE == (int)PP_APPLY_BYTE && BBOCR_PP_BOX0_X4 == (int)PP_BOX0_X4 &&
+                  BBOCR_PP_UNSHARP_FUSED == (int)PP_UNSHARP_FUSED && BBOCR_PP_UNSHARP_PASSES_BYTE == (int)PP_UNSHARP_PASSES_BYTE &&
+                  BBOCR_PP_RESIZE_TILED32 == (int)PP_RESIZE_TILED32 && BBOCR_PP_RESIZE_PIXEL == (int)PP_RESIZE_PIXEL,
+              "BBOCR_PP_* mirrors PpRoute");
+
 int bbocr_host_cpu_share(void) { return host_cpu_share(); }
 
 int bbocr_host_component_polys(const int* comps, const int* rowext, int n, int w, int h, double ratio, int* polys_out) {

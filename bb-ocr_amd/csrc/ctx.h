@@ -483,6 +483,8 @@ bbocr_result* export_result(int B, const std::vector<BoxJob>& jobs, const std::v
 void pp_resize(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, int dh, int dw, bool src_bgr = false);   // enqueues; the caller waits
 void pp_gauss(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, double sigma);
 const uint8_t* pp_fold_lut(bbocr_ctx* c, size_t n, double contrast, double brightness);
+bool pp_clahe_tiles(int H, int W, int* th, int* tw);
+int pp_unsharp_box_r(float radius);
 void pp_clahe(bbocr_ctx* c, const uint8_t* src, int H, int W, const uint8_t* d_lut, uint8_t* dst, double clip_limit);
 void pp_unsharp(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, uint8_t* tmp1, uint8_t* tmp2, float radius, int percent, int threshold);
 void preprocess_chain_impl(bbocr_ctx* c, const uint8_t* bgr, int H, int W, const bbocr_preproc_params& q, uint8_t* out, int dh, int dw);

@@ -287,7 +287,25 @@ hipError_t launch_ctc_beam_wide(const float* probs, size_t rows, int C, int cs, 
                                 int* cand, int* out_text, int* out_len, hipStream_t s);
 
 // ------------------------------------------------------------------ OCR pre-processing chain (preproc.hip), SURVEY 8 row f2
+// Which kernel a launcher of the chain takes (include/bbocr.h BBOCR_PP_*, same order): decided by the pp_*_route functions below from the
+// plane's size and the low two bits of the pointers alone; the launchers switch on the same functions.
+enum PpRoute : int {
+    PP_GAUSS_X4 = 0, PP_GAUSS_BYTE,
+    PP_HIST_X4, PP_HIST_BYTE,
+    PP_APPLY_CELL_2, PP_APPLY_CELL_8, PP_APPLY_CELL_32, PP_APPLY_VEC, PP_APPLY_BYTE,
+    PP_BOX0_X4, PP_BOX_BYTE,
+    PP_UNSHARP_FUSED, PP_UNSHARP_PASSES_VEC, PP_UNSHARP_PASSES_BYTE,
+    PP_RESIZE_TILED32, PP_RESIZE_TILED16, PP_RESIZE_PIXEL,
+    PP_ROUTE_COUNT
+};
 int pp_resize_tile_rows(int H, int W, int dh, int dw);
+PpRoute pp_resize_route(int H, int W, int dh, int dw);
+bool pp_resize_dword_rows(int dw, unsigned dst_bits);
+PpRoute pp_gauss_route(int H, int W, unsigned src_bits, unsigned dst_bits);
+PpRoute pp_clahe_hist_route(int H, int W, unsigned src_bits);
+PpRoute pp_clahe_apply_route(int H, int W, int th, unsigned src_bits, unsigned dst_bits);
+PpRoute pp_box_route(int H, int W, int r, unsigned src_bits, unsigned dst_bits);
+PpRoute pp_unsharp_route(int H, int W, int r, unsigned src_bits, unsigned tmp_bits, unsigned dst_bits);
 hipError_t launch_pp_resize_cubic(const uint8_t* src, int H, int W, uint8_t* dst, int dh, int dw, const int* x0, const double* wx, const long long* nx,
                                   const int* y0, const double* wy, const long long* ny, unsigned long long KX, unsigned long long KY, hipStream_t s, int src_bgr = 0);
 hipError_t launch_pp_gauss3(const uint8_t* src, int H, int W, uint8_t* dst, int k0, int k1, int k2, unsigned long long* sum, hipStream_t s);
@@ -299,10 +317,10 @@ hipError_t launch_pp_box_pass(const uint8_t* src, uint8_t* dst, int H, int W, in
 hipError_t launch_pp_fold_lut(const unsigned long long* sum, unsigned long long n, float contrast, float brightness, uint8_t* lut, hipStream_t s);
 hipError_t launch_pp_clahe_luts(const unsigned int* hist, int tiles, int clip, float lut_scale, uint8_t* tile_luts, hipStream_t s);
 hipError_t launch_pp_lut(const uint8_t* src, uint8_t* dst, const uint8_t* lut, size_t total, hipStream_t s);
-bool pp_unsharp_fused_ok(int H, int W, int r, const uint8_t* a, const uint8_t* b, const uint8_t* c);
 hipError_t launch_pp_unsharp_fused(const uint8_t* in, uint8_t* tmp, uint8_t* dst, int H, int W, unsigned int ww, unsigned int fw, int percent,
                                    int threshold, hipStream_t s);
-hipError_t launch_pp_unsharp(const uint8_t* in, const uint8_t* blur, uint8_t* dst, size_t total, int percent, int threshold, hipStream_t s);
+hipError_t launch_pp_unsharp(const uint8_t* in, const uint8_t* blur, uint8_t* dst, size_t total, int percent, int threshold, PpRoute route,
+                             hipStream_t s);
 
 // ------------------------------------------------------------------ text-region auto-crop (autocrop.hip), enhanced_extractor.py::_auto_crop_text_region
 constexpr int AC_BOX = 35, AC_BOX_R = 17, AC_MEAN_C = 10;     // adaptiveThreshold MEAN: block 35, C 10

@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256) pp_resize_cubic_tiled_kernel(const uint8_
                                                                      int dw, const int* __restrict__ x0, const double* __restrict__ wx,
                                                                      const long long* __restrict__ nx, const int* __restrict__ y0,
                                                                      const double* __restrict__ wy, const long long* __restrict__ ny,
-                                                                     unsigned long long KX, unsigned long long KY) {
+                                                                     unsigned long long KX, unsigned long long KY, int dword_rows) {
     __shared__ uint8_t win[PP_RS_SH][PP_RS_SW];
     __shared__ double hor[PP_RS_SH][PP_RS_TW];
     constexpr int NIT = TH / 4;
@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(256) pp_resize_cubic_tiled_kernel(const uint8_
         res[ly][lx] = (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
     }
     __syncthreads();
-    if (nxo == PP_RS_TW && (dw & 3) == 0 && ((size_t)dst & 3) == 0) {   // whole dwords, 16 lanes per output row
+    if (nxo == PP_RS_TW && dword_rows) {   // a full tile of a plane whose rows start on dwords (pp_resize_dword_rows): 16 lanes per output row
         const int q = threadIdx.x & 15;
         for (int ly = threadIdx.x >> 4; ly < nyo; ly += 16) *(unsigned int*)(dst + (size_t)(oy + ly) * dw + ox + q * 4) = *(const unsigned int*)&res[ly][q * 4];
     } else {
@@ -462,9 +462,7 @@ __device__ __forceinline__ unsigned int pp_unsharp_dw(unsigned int av, unsigned 
     }
     return ov;
 }
-// HROWS: `blur_of` is the mask's INPUT and the three row passes are applied to each of the R + 6 rows as it is loaded (three dwords per
-// row, the neighbours' from the L1) -- the whole UnsharpMask in one launch, no intermediate plane.
-template <int R, bool HROWS>
+template <int R>
 __global__ void __launch_bounds__(256) pp_box0_v3_unsharp_kernel(const uint8_t* __restrict__ blur_of, const uint8_t* __restrict__ in,
                                                                   uint8_t* __restrict__ dst, int H, int W, unsigned int ww, unsigned int fw,
                                                                   int percent, int threshold) {
@@ -477,8 +475,7 @@ __global__ void __launch_bounds__(256) pp_box0_v3_unsharp_kernel(const uint8_t* 
     for (int k = 0; k < R + 6; ++k) {
         int y = y0 - 3 + k;
         y = y < 0 ? 0 : (y >= H ? H - 1 : y);
-        if constexpr (HROWS) a[k] = pp_box0_h3_dw(blur_of + (size_t)y * W, x, W, ww, fw);
-        else a[k] = *(const unsigned int*)(blur_of + (size_t)y * W + x);
+        a[k] = *(const unsigned int*)(blur_of + (size_t)y * W + x);
     }
     const bool top = y0 == 0, bottom = y0 + R + 2 > H - 1;       // block-uniform
     // level 1 at rows y0-2+k
@@ -515,35 +512,27 @@ __global__ void __launch_bounds__(256) pp_box0_v3_unsharp_kernel(const uint8_t* 
     }
 }
 
-// ---- PIL UnsharpMask combine: diff = in - blur; |diff| > threshold ? clip8(in + diff * percent / 100) : in
+// ---- PIL UnsharpMask combine: diff = in - blur; |diff| > threshold ? clip8(in + diff * percent / 100) : in.  vec: `in`, `blur` and `dst`
+// are all 4-byte aligned and the plane goes as dwords with a byte tail; otherwise every pixel goes byte-wise
 __global__ void __launch_bounds__(256) pp_unsharp_kernel(const uint8_t* __restrict__ in, const uint8_t* __restrict__ blur, uint8_t* __restrict__ dst,
-                                                          size_t total, int percent, int threshold) {
-    const size_t t4 = total >> 2;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < t4; i += (size_t)gridDim.x * 256) {
-        const unsigned int av = ((const unsigned int*)in)[i], bv = ((const unsigned int*)blur)[i];
-        unsigned int ov = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int a = (av >> (8 * k)) & 255, diff = a - (int)((bv >> (8 * k)) & 255);
-            int o = a;
-            if (abs(diff) > threshold) {
-                o = a + diff * percent / 100;                    // C integer division: truncates towards zero
-                o = o < 0 ? 0 : (o > 255 ? 255 : o);
-            }
-            ov |= (unsigned)o << (8 * k);
-        }
-        ((unsigned int*)dst)[i] = ov;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (total & 3)) {          // tail pixels
-        const size_t i = (t4 << 2) + threadIdx.x;
+                                                          size_t total, int percent, int threshold, int vec) {
+    auto pixel = [&](size_t i) {
         const int a = in[i], diff = a - (int)blur[i];
         int o = a;
         if (abs(diff) > threshold) {
-            o = a + diff * percent / 100;
+            o = a + diff * percent / 100;                        // C integer division: truncates towards zero
             o = o < 0 ? 0 : (o > 255 ? 255 : o);
         }
         dst[i] = (uint8_t)o;
+    };
+    if (!vec) {
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) pixel(i);
+        return;
     }
+    const size_t t4 = total >> 2;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < t4; i += (size_t)gridDim.x * 256)
+        ((unsigned int*)dst)[i] = pp_unsharp_dw(((const unsigned int*)in)[i], ((const unsigned int*)blur)[i], percent, threshold);
+    if (blockIdx.x == 0 && threadIdx.x < (total & 3)) pixel((t4 << 2) + threadIdx.x);   // tail pixels
 }
 
 // ---- the two PIL enhancers folded into one LUT on the device (libImaging/Blend.c with a constant first image; same float steps as
@@ -660,6 +649,8 @@ static inline int pp_grid(size_t total) {
     return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
 }
 
+// ---- which kernel a launcher takes: one pure host function per decision, of the plane's size and of the low two bits of the pointers
+// only.  The launchers below switch on these, and the C ABI reports them (bbocr_host_pp_*_route), so report and dispatch cannot drift.
 // which tile height the LDS-tiled kernel takes for this geometry (0: none fits, the per-pixel kernel runs)
 int pp_resize_tile_rows(int H, int W, int dh, int dw) {
     const long long sw = ((long long)PP_RS_TW * W + dw - 1) / dw + 5;
@@ -668,21 +659,60 @@ int pp_resize_tile_rows(int H, int W, int dh, int dw) {
     if (sw <= PP_RS_SW && sh16 <= PP_RS_SH && (dh + 15) / 16 <= 65535) return 16;
     return 0;
 }
+PpRoute pp_resize_route(int H, int W, int dh, int dw) {
+    const int th = pp_resize_tile_rows(H, W, dh, dw);
+    return th == 32 ? PP_RESIZE_TILED32 : (th == 16 ? PP_RESIZE_TILED16 : PP_RESIZE_PIXEL);
+}
+// whether the full tiles of the LDS-tiled resize leave as whole dwords: every destination row must start on one
+bool pp_resize_dword_rows(int dw, unsigned dst_bits) { return (dw & 3) == 0 && (dst_bits & 3) == 0; }
+PpRoute pp_gauss_route(int H, int W, unsigned src_bits, unsigned dst_bits) {
+    (void)H;
+    return (W & 3) == 0 && W >= 8 && ((src_bits | dst_bits) & 3) == 0 ? PP_GAUSS_X4 : PP_GAUSS_BYTE;
+}
+PpRoute pp_clahe_hist_route(int H, int W, unsigned src_bits) {
+    (void)H;
+    return (W & 3) == 0 && (src_bits & 3) == 0 ? PP_HIST_X4 : PP_HIST_BYTE;
+}
+// th: rows of a CLAHE tile (pp_clahe_tiles)
+PpRoute pp_clahe_apply_route(int H, int W, int th, unsigned src_bits, unsigned dst_bits) {
+    const bool vec = (W & 3) == 0 && ((src_bits | dst_bits) & 3) == 0;
+    if (!vec) return PP_APPLY_BYTE;
+    if ((size_t)H * W < (size_t)1 << 14) return PP_APPLY_VEC;    // small planes: too few pixels per cell to pay for staging the tables
+    return th >= 512 ? PP_APPLY_CELL_32 : (th >= 64 ? PP_APPLY_CELL_8 : PP_APPLY_CELL_2);
+}
+PpRoute pp_box_route(int H, int W, int r, unsigned src_bits, unsigned dst_bits) {
+    (void)H;
+    return r == 0 && (W & 3) == 0 && ((src_bits | dst_bits) & 3) == 0 ? PP_BOX0_X4 : PP_BOX_BYTE;
+}
+// UnsharpMask of `src` into `dst` through scratch planes (bits of both OR-ed into tmp_bits).  FUSED: box radius 0 on a W % 4 == 0 plane, three
+// row passes, then three column passes + combine (two launches for seven).  PASSES_*: six box passes (each by pp_box_route), then the
+// combine, which runs flat over the plane and so asks for aligned pointers only, not for W % 4 == 0.
+PpRoute pp_unsharp_route(int H, int W, int r, unsigned src_bits, unsigned tmp_bits, unsigned dst_bits) {
+    const bool aligned = ((src_bits | tmp_bits | dst_bits) & 3) == 0;
+    if (r == 0 && (W & 3) == 0 && W >= 4 && H >= 1 && aligned && (H + 15) / 16 <= 65535) return PP_UNSHARP_FUSED;
+    return aligned ? PP_UNSHARP_PASSES_VEC : PP_UNSHARP_PASSES_BYTE;
+}
+static inline unsigned pp_bits(const void* p) { return (unsigned)((size_t)p & 3); }
+
 // src_bgr != 0: src is the interleaved 3-channel page (only where pp_resize_tile_rows() != 0)
 hipError_t launch_pp_resize_cubic(const uint8_t* src, int H, int W, uint8_t* dst, int dh, int dw, const int* x0, const double* wx, const long long* nx,
                                   const int* y0, const double* wy, const long long* ny, unsigned long long KX, unsigned long long KY, hipStream_t s,
                                   int src_bgr) {
-    // window of a 64 x 16 output tile: at most ceil(tile * src / dst) + 4 source columns / rows
-    const int th = pp_resize_tile_rows(H, W, dh, dw);
+    // window of a 64 x 32 or 64 x 16 output tile: at most ceil(tile * src / dst) + 4 source columns / rows (pp_resize_tile_rows)
+    const PpRoute route = pp_resize_route(H, W, dh, dw);
+    const int th = route == PP_RESIZE_TILED32 ? 32 : (route == PP_RESIZE_TILED16 ? 16 : 0);   // 0: the per-pixel kernel, no tiles
     const dim3 grid((dw + PP_RS_TW - 1) / PP_RS_TW, th ? (dh + th - 1) / th : 1);
-#define PP_RS_LAUNCH(TH_, BGR_) hipLaunchKernelGGL((pp_resize_cubic_tiled_kernel<TH_, BGR_>), grid, dim3(256), 0, s, src, H, W, dst, dh, dw, x0, wx, nx, y0, wy, ny, KX, KY)
-    if (th == 32) {
+    const int dword_rows = pp_resize_dword_rows(dw, pp_bits(dst)) ? 1 : 0;
+#define PP_RS_LAUNCH(TH_, BGR_) hipLaunchKernelGGL((pp_resize_cubic_tiled_kernel<TH_, BGR_>), grid, dim3(256), 0, s, src, H, W, dst, dh, dw, x0, wx, nx, y0, wy, ny, KX, KY, dword_rows)
+    switch (route) {
+    case PP_RESIZE_TILED32:
         if (src_bgr) PP_RS_LAUNCH(32, true); else PP_RS_LAUNCH(32, false);
         return hipGetLastError();
-    }
-    if (th == 16) {
+    case PP_RESIZE_TILED16:
         if (src_bgr) PP_RS_LAUNCH(16, true); else PP_RS_LAUNCH(16, false);
         return hipGetLastError();
+    default:
+        break;
     }
 #undef PP_RS_LAUNCH
     if (src_bgr) return hipErrorInvalidValue;
@@ -690,7 +720,7 @@ hipError_t launch_pp_resize_cubic(const uint8_t* src, int H, int W, uint8_t* dst
     return hipGetLastError();
 }
 hipError_t launch_pp_gauss3(const uint8_t* src, int H, int W, uint8_t* dst, int k0, int k1, int k2, unsigned long long* sum, hipStream_t s) {
-    if ((W & 3) == 0 && W >= 8 && (((size_t)src | (size_t)dst) & 3) == 0) {
+    if (pp_gauss_route(H, W, pp_bits(src), pp_bits(dst)) == PP_GAUSS_X4) {
         const int g4 = pp_grid((size_t)H * (W >> 2)) > 4096 ? 4096 : pp_grid((size_t)H * (W >> 2));
         hipLaunchKernelGGL(pp_gauss3_x4_kernel, dim3(g4), dim3(256), 0, s, src, H, W, dst, k0, k1, k2, sum);
         return hipGetLastError();
@@ -701,7 +731,7 @@ hipError_t launch_pp_gauss3(const uint8_t* src, int H, int W, uint8_t* dst, int 
 }
 hipError_t launch_pp_clahe_hist(const uint8_t* src, int H, int W, const uint8_t* lut, int tw, int th, int tx, int ty, unsigned int* hist,
                                 hipStream_t s) {
-    if ((W & 3) == 0 && ((size_t)src & 3) == 0) {
+    if (pp_clahe_hist_route(H, W, pp_bits(src)) == PP_HIST_X4) {
         hipLaunchKernelGGL(pp_clahe_hist_x4_kernel, dim3(tx * ty, 32), dim3(256), 0, s, src, H, W, lut, tw, th, tx, ty, hist);
         return hipGetLastError();
     }
@@ -710,45 +740,51 @@ hipError_t launch_pp_clahe_hist(const uint8_t* src, int H, int W, const uint8_t*
 }
 hipError_t launch_pp_clahe_apply(const uint8_t* src, int H, int W, const uint8_t* lut, const uint8_t* tile_luts, int tw, int th, int tx, int ty,
                                  uint8_t* dst, hipStream_t s) {
-    const int vec = (W & 3) == 0 && (((size_t)src | (size_t)dst) & 3) == 0;
-    if (vec && (size_t)H * W >= (size_t)1 << 14) {            // small planes: too few pixels per cell to pay for staging the tables
-        const int chunks = th >= 512 ? 32 : (th >= 64 ? 8 : 2);
+    const PpRoute route = pp_clahe_apply_route(H, W, th, pp_bits(src), pp_bits(dst));
+    int chunks = 0;
+    switch (route) {
+    case PP_APPLY_CELL_32: chunks = 32; break;
+    case PP_APPLY_CELL_8: chunks = 8; break;
+    case PP_APPLY_CELL_2: chunks = 2; break;
+    default: break;
+    }
+    if (chunks) {
         hipLaunchKernelGGL(pp_clahe_apply_cell_kernel, dim3((tx + 1) * (ty + 1), chunks), dim3(256), 0, s, src, H, W, lut, tile_luts, tw, th, tx, ty,
                            dst);
         return hipGetLastError();
     }
+    const int vec = route == PP_APPLY_VEC;
     hipLaunchKernelGGL(pp_clahe_apply_kernel, dim3(pp_grid(vec ? (size_t)H * (W >> 2) : (size_t)H * W)), dim3(256), 0, s, src, H, W, lut, tile_luts, tw,
                        th, tx, ty, dst, vec);
     return hipGetLastError();
 }
 hipError_t launch_pp_box_pass(const uint8_t* src, uint8_t* dst, int H, int W, int vertical, int r, unsigned int ww, unsigned int fw, hipStream_t s) {
-    if (r == 0 && (W & 3) == 0 && (((size_t)src | (size_t)dst) & 3) == 0) {
+    if (pp_box_route(H, W, r, pp_bits(src), pp_bits(dst)) == PP_BOX0_X4) {
         hipLaunchKernelGGL(pp_box0_x4_kernel, dim3(pp_grid((size_t)H * (W >> 2))), dim3(256), 0, s, src, dst, H, W, vertical, ww, fw);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(pp_box_pass_kernel, dim3(pp_grid((size_t)H * W)), dim3(256), 0, s, src, dst, H, W, vertical, r, ww, fw);
     return hipGetLastError();
 }
-// UnsharpMask with box radius 0 on a W % 4 == 0 plane: three row passes, then three column passes + combine (two launches for seven)
-bool pp_unsharp_fused_ok(int H, int W, int r, const uint8_t* a, const uint8_t* b, const uint8_t* c) {
-    return r == 0 && (W & 3) == 0 && W >= 4 && H >= 1 && ((((size_t)a | (size_t)b | (size_t)c)) & 3) == 0 && (H + 15) / 16 <= 65535;
-}
+// PP_UNSHARP_FUSED only (pp_unsharp_route): `tmp` receives the plane after the three row passes
 hipError_t launch_pp_unsharp_fused(const uint8_t* in, uint8_t* tmp, uint8_t* dst, int H, int W, unsigned int ww, unsigned int fw, int percent,
                                    int threshold, hipStream_t s) {
-    if (!tmp) {                                                  // one launch: row passes applied on the fly
-        hipLaunchKernelGGL((pp_box0_v3_unsharp_kernel<16, true>), dim3(((W >> 2) + 255) / 256, (H + 15) / 16), dim3(256), 0, s, in, in, dst, H, W, ww, fw,
-                           percent, threshold);
-        return hipGetLastError();
-    }
+    if (pp_unsharp_route(H, W, 0, pp_bits(in), pp_bits(tmp), pp_bits(dst)) != PP_UNSHARP_FUSED) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pp_box0_h3_kernel, dim3(pp_grid((size_t)H * (W >> 2))), dim3(256), 0, s, in, tmp, H, W, ww, fw);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((pp_box0_v3_unsharp_kernel<16, false>), dim3(((W >> 2) + 255) / 256, (H + 15) / 16), dim3(256), 0, s, tmp, in, dst, H, W, ww, fw,
+    hipLaunchKernelGGL((pp_box0_v3_unsharp_kernel<16>), dim3(((W >> 2) + 255) / 256, (H + 15) / 16), dim3(256), 0, s, tmp, in, dst, H, W, ww, fw,
                        percent, threshold);
     return hipGetLastError();
 }
-hipError_t launch_pp_unsharp(const uint8_t* in, const uint8_t* blur, uint8_t* dst, size_t total, int percent, int threshold, hipStream_t s) {
-    hipLaunchKernelGGL(pp_unsharp_kernel, dim3(pp_grid((total >> 2) + 1)), dim3(256), 0, s, in, blur, dst, total, percent, threshold);
+// the combine behind the six box passes.  route: what pp_unsharp_route gave for these planes (`blur` is one of its scratch planes) --
+// PP_UNSHARP_PASSES_VEC: all three pointers are 4-byte aligned, dwords with a byte tail; PP_UNSHARP_PASSES_BYTE: byte-wise
+hipError_t launch_pp_unsharp(const uint8_t* in, const uint8_t* blur, uint8_t* dst, size_t total, int percent, int threshold, PpRoute route,
+                             hipStream_t s) {
+    if (route != PP_UNSHARP_PASSES_VEC && route != PP_UNSHARP_PASSES_BYTE) return hipErrorInvalidValue;
+    const int vec = route == PP_UNSHARP_PASSES_VEC;
+    if (vec && ((pp_bits(in) | pp_bits(blur) | pp_bits(dst)) & 3) != 0) return hipErrorInvalidValue;   // a route of other planes
+    hipLaunchKernelGGL(pp_unsharp_kernel, dim3(pp_grid(vec ? (total >> 2) + 1 : total)), dim3(256), 0, s, in, blur, dst, total, percent, threshold, vec);
     return hipGetLastError();
 }
 hipError_t launch_pp_fold_lut(const unsigned long long* sum, unsigned long long n, float contrast, float brightness, uint8_t* lut, hipStream_t s) {

@@ -52,6 +52,7 @@ static float pil_box_radius(float radius, int passes) {   // libImaging/BoxBlur.
     a = a / (6 * (sigma2 - (l + 1) * (l + 1)));
     return l + a;
 }
+int pp_unsharp_box_r(float radius) { return (int)pil_box_radius(radius, 3); }   // whole box radius of UnsharpMask(radius): 0 for radius 1
 
 // Small device tables of the chain, at fixed offsets of pp_tab (every step of a chain is enqueued without a host round trip, so
 // no two steps may share an offset): pixel sum | folded enhancer LUT | 64 tile histograms | 64 tile LUTs
@@ -111,16 +112,24 @@ const uint8_t* pp_fold_lut(bbocr_ctx* c, size_t n, double contrast, double brigh
                               c->stream));
     return t + PP_LUT;
 }
-// CLAHE of lut[src] (lut: device table from pp_fold_lut).  Histograms, clip / redistribute / cumulative LUTs and the interpolated
-// lookup are three launches on the stream, nothing comes back to the host.  Enqueues.
-void pp_clahe(bbocr_ctx* c, const uint8_t* src, int H, int W, const uint8_t* d_lut, uint8_t* dst, double clip_limit) {
+// Tile size of CLAHE's 8 x 8 grid on an H x W plane; false: the plane is smaller than the reflected padding needs (pp_clahe refuses it).
+bool pp_clahe_tiles(int H, int W, int* th, int* tw) {
     const int tx = 8, ty = 8;
     // clahe.cpp pads BOTH axes by tiles - (size % tiles) as soon as ONE of them is not a multiple of the grid -- a whole extra
     // 8 rows / columns on the axis that did divide (upstream quirk, restated as is)
     const bool pad = (H % ty) || (W % tx);
     const int EH = pad ? H + (ty - H % ty) : H, EW = pad ? W + (tx - W % tx) : W;
-    if (EH - H >= H || EW - W >= W) fail(BBOCR_ERR_ARG, "image smaller than the CLAHE tile grid");
-    const int th = EH / ty, tw = EW / tx;
+    if (EH - H >= H || EW - W >= W) return false;
+    *th = EH / ty;
+    *tw = EW / tx;
+    return true;
+}
+// CLAHE of lut[src] (lut: device table from pp_fold_lut). Histograms, clip / redistribute / cumulative LUTs and the interpolated
+// lookup are three launches on the stream, nothing comes back to the host.  Enqueues.
+void pp_clahe(bbocr_ctx* c, const uint8_t* src, int H, int W, const uint8_t* d_lut, uint8_t* dst, double clip_limit) {
+    const int tx = 8, ty = 8;
+    int th = 0, tw = 0;
+    if (!pp_clahe_tiles(H, W, &th, &tw)) fail(BBOCR_ERR_ARG, "image smaller than the CLAHE tile grid");
     unsigned char* t = pp_tab(c);
     unsigned int* d_hist = (unsigned int*)(t + PP_HIST);
     uint8_t* d_tl = t + PP_TLUT;
@@ -137,11 +146,13 @@ void pp_clahe(bbocr_ctx* c, const uint8_t* src, int H, int W, const uint8_t* d_l
 void pp_unsharp(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, uint8_t* tmp1, uint8_t* tmp2, float radius, int percent,
                        int threshold) {
     const float fr = pil_box_radius(radius, 3);
-    const int r = (int)fr;
+    const int r = pp_unsharp_box_r(radius);
     const unsigned int ww = (unsigned int)((float)(1 << 24) / (fr * 2.f + 1.f));
     const unsigned int fw = ((1u << 24) - (unsigned int)(r * 2 + 1) * ww) / 2;
-    if (pp_unsharp_fused_ok(H, W, r, src, tmp1, dst)) {       // the chain's own case (radius 1 -> box radius 0): 2 launches instead of 7
-        // (tmp = nullptr: the row passes applied on the fly inside the column kernel, ONE launch -- measured equal: 130 us against 67 + 63)
+    auto bits = [](const void* p) { return (unsigned)((size_t)p & 3); };
+    const PpRoute route = pp_unsharp_route(H, W, r, bits(src), bits(tmp1) | bits(tmp2), bits(dst));
+    if (route == PP_UNSHARP_FUSED) {
+        // the chain's own case (radius 1 -> box radius 0): 2 launches instead of 7
         HIPCHK(launch_pp_unsharp_fused(src, tmp1, dst, H, W, ww, fw, percent, threshold, c->stream));
         return;
     }
@@ -153,7 +164,7 @@ void pp_unsharp(bbocr_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, ui
         cur = bufs[w];
         w ^= 1;
     }
-    HIPCHK(launch_pp_unsharp(src, cur, dst, (size_t)H * W, percent, threshold, c->stream));
+    HIPCHK(launch_pp_unsharp(src, cur, dst, (size_t)H * W, percent, threshold, route, c->stream));   // dwords or bytes: as the route says
 }
 
 void preprocess_chain_impl(bbocr_ctx* c, const uint8_t* bgr, int H, int W, const bbocr_preproc_params& q, uint8_t* out, int dh, int dw) {

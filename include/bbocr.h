@@ -512,6 +512,45 @@ int bbocr_preprocess_chain(bbocr_ctx* ctx, const uint8_t* dev_bgr, int H, int W,
  * (radius `param`, 30 %, threshold 3), 6 = cv2 BGR2GRAY of an interleaved [H,W,3] plane (the gray plane reformat_input derives from
  * arrays), 7 = PIL UnsharpMask (radius 1, `param` %, threshold 3).  Stages 1-7 keep the size (dh = H, dw = W). */
 int bbocr_op_preprocess_stage(bbocr_ctx* ctx, int stage, const uint8_t* dev_src, int H, int W, uint8_t* dev_dst, int dh, int dw, double param);
+/* Which kernel a launch of the chain takes.  Every launcher picks between a dword kernel and a byte-wise one (or between tile sizes) from
+ * the plane's size and from the low two bits of its source and destination pointers; each choice is one host function, which the launcher
+ * itself switches on and which the bbocr_host_pp_*_route calls below report. */
+enum {
+    BBOCR_PP_GAUSS_X4 = 0,          /* pp_gauss3_x4_kernel: W % 4 == 0, W >= 8, both pointers 4-byte aligned */
+    BBOCR_PP_GAUSS_BYTE,            /* pp_gauss3_kernel */
+    BBOCR_PP_HIST_X4,               /* pp_clahe_hist_x4_kernel: W % 4 == 0, source aligned */
+    BBOCR_PP_HIST_BYTE,             /* pp_clahe_hist_kernel */
+    BBOCR_PP_APPLY_CELL_2,          /* pp_clahe_apply_cell_kernel (W % 4 == 0, aligned, H * W >= 1 << 14), 2 row chunks per cell */
+    BBOCR_PP_APPLY_CELL_8,          /* the same, 8 chunks: tile height >= 64 */
+    BBOCR_PP_APPLY_CELL_32,         /* the same, 32 chunks: tile height >= 512 */
+    BBOCR_PP_APPLY_VEC,             /* pp_clahe_apply_kernel with dword loads / stores: a smaller W % 4 == 0, aligned plane */
+    BBOCR_PP_APPLY_BYTE,            /* pp_clahe_apply_kernel byte-wise */
+    BBOCR_PP_BOX0_X4,               /* pp_box0_x4_kernel: one box pass of radius 0, W % 4 == 0, aligned */
+    BBOCR_PP_BOX_BYTE,              /* pp_box_pass_kernel */
+    BBOCR_PP_UNSHARP_FUSED,         /* pp_box0_h3_kernel + pp_box0_v3_unsharp_kernel: box radius 0, W % 4 == 0, every plane aligned */
+    BBOCR_PP_UNSHARP_PASSES_VEC,    /* six box passes (each BOX0_X4 or BOX_BYTE), then pp_unsharp_kernel over dwords with a byte tail: aligned */
+    BBOCR_PP_UNSHARP_PASSES_BYTE,   /* six box passes, then pp_unsharp_kernel byte-wise: a misaligned source or destination */
+    BBOCR_PP_RESIZE_TILED32,        /* pp_resize_cubic_tiled_kernel, 64 x 32 output tiles */
+    BBOCR_PP_RESIZE_TILED16,        /* the same, 64 x 16 tiles */
+    BBOCR_PP_RESIZE_PIXEL,          /* pp_resize_cubic_kernel: the source window of a tile does not fit */
+    BBOCR_PP_ROUTE_COUNT
+};
+/* pure host, no context, usable without a GPU: the BBOCR_PP_* route bbocr_op_preprocess_stage takes for an H x W plane whose source and
+ * destination pointers have the low two bits src_bits / dst_bits (0..3); the stage's own scratch planes are aligned.  resize: stage 0;
+ * gauss: stage 1, and stage 2's pixel sum (destination: a scratch plane, dst_bits 0); clahe_hist / clahe_apply: the two plane passes of
+ * stage 4, BBOCR_ERR_ARG for a plane smaller than the tile grid's padding, which the stage refuses; unsharp: stages 5 and 7 (radius 1);
+ * box: one of the six box passes behind BBOCR_PP_UNSHARP_PASSES_* (r = bbocr_host_pp_unsharp_box_radius(radius); the first pass reads the
+ * stage's source, all six write scratch planes).  Any other bad argument: BBOCR_ERR_ARG. */
+int bbocr_host_pp_resize_route(int H, int W, int dh, int dw);
+/* 1: the tiled resize kernels store their full 64-column tiles as whole dwords (dw % 4 == 0, destination aligned), 0: byte-wise.  The
+ * launcher passes this very value to the kernel */
+int bbocr_host_pp_resize_dword_rows(int dw, int dst_bits);
+int bbocr_host_pp_gauss_route(int H, int W, int src_bits, int dst_bits);
+int bbocr_host_pp_clahe_hist_route(int H, int W, int src_bits);
+int bbocr_host_pp_clahe_apply_route(int H, int W, int src_bits, int dst_bits);
+int bbocr_host_pp_box_route(int H, int W, int r, int src_bits, int dst_bits);
+int bbocr_host_pp_unsharp_route(int H, int W, double radius, int src_bits, int dst_bits);
+int bbocr_host_pp_unsharp_box_radius(double radius);
 
 /* ---- text-region auto-crop (enhanced_extractor.py::_auto_crop_text_region, the extractor's `crop_for_ocr`) of one u8 page on the
  * device: gray [H,W] (channels 1) or BGR [H,W,3] (channels 3), rows `pitch` bytes apart (a crop of a larger plane is passed as a
