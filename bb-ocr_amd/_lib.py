@@ -234,6 +234,16 @@ PROTOTYPES = {
     "bbocr_op_ctc_beam_wide": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bbocr_host_ctc_route": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "bbocr_host_ctc_wordbeam": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16),
+                                          C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_host_wordbeam_route": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "bbocr_set_dictionary": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "bbocr_dictionary_stats": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_op_word_segments": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_op_dict_lookup": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_int),
+                                       C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bbocr_op_ctc_wordbeam": (C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]),
     "bbocr_op_resize_u8": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int]),
     "bbocr_op_ycc_to_rgb": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, _vp]),
     "bbocr_upload_pages": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, C.c_size_t, _vp]),

@@ -98,7 +98,7 @@ void slot_destroy(bbocr_ctx* c) {
                       &c->ccl_counters, &c->crop_desc, &c->crop_desc2, &c->crop_scratch, &c->crop_hscratch, &c->crop_wscratch, &c->crop_luts, &c->crop_hist,
                       &c->ctc_idx, &c->ctc_pmax, &c->ctc_out_idx, &c->ctc_out, &c->seq_v, &c->seq_xp, &c->seq_h, &c->seq_lin, &c->seq_logits,
                       &c->seq_tables, &c->pp_gray, &c->pp_a, &c->pp_b, &c->pp_c, &c->pp_tab, &c->ctc_probs, &c->ctc_beam_idx, &c->ctc_beam_len, &c->ctc_cand, &c->ctc_cand_n, &c->ac_work, &c->th_coef, &c->je_scan, &c->je_out, &c->pe_out,
-                      &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp, &c->ctc_mask};
+                      &c->pg_rgb, &c->pg_tab, &c->seq_q8, &c->seq_rowp, &c->ctc_mask, &c->wd_buf, &c->wb_segs, &c->wb_meta, &c->wb_text};
     for (DevBuf* b : bufs) b->release();
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->seq_stream) (void)hipStreamDestroy(c->seq_stream);

@@ -25,6 +25,7 @@
 #include "hostpool.h"
 #include "common.h"
 #include "kernels.h"
+#include "word_dict.h"
 
 
 using clk = std::chrono::steady_clock;
@@ -180,6 +181,9 @@ struct WeightView {
     struct Q8Layer { int8_t* w = nullptr; float* scale = nullptr; float* bias = nullptr; };
     Q8Layer q_ih[2], q_hh[2], q_lin[2], q_pred;      // q_ih: 256 -> 2048 (b_ih); q_hh: packed by pack_q8_whh, scale [2], bias b_hh [2][1024]
     void* zero_page = nullptr;   // 256 zero bytes (padding source of the LDS-DMA conv variant)
+    // ---- the dictionary of decoder='wordbeamsearch' (bbocr_set_dictionary): the root owns both copies (wd_buf, wd_table below)
+    WordDictDev wd_dev;          // the uploaded table; slots == null: none on the device (no dictionary, or more than 128 classes)
+    const WdTable* wd_host = nullptr;   // the host's copy; null: no dictionary
 };
 
 // One bbocr_ctx = the ROOT (what bbocr_create returns: configuration, weights, the compute stream, the call-slot pool) and, at the
@@ -214,6 +218,10 @@ struct bbocr_ctx : WeightView {
     unsigned long long pp_cubic_K[2] = {0, 0};
     unsigned int ignore_mask[4] = {0, 0, 0, 0};   // recogniser class mask of the running call (bbocr_params::ignore_mask)
     int beam_width = 0;                           // > 0: decoder='beamsearch' for the running call (bbocr_params::decoder / beam_width)
+    bool word_beam = false;                       // ... 'wordbeamsearch' over the root's dictionary, at that width
+    DevBuf wd_buf;                                // root only: the uploaded dictionary, slots then byte pool (WeightView::wd_dev points into it)
+    std::unique_ptr<WdTable> wd_table;            // root only: the host's table (WeightView::wd_host)
+    DevBuf wb_segs, wb_meta, wb_text;             // word search on the device: segment table + lengths, per-sequence {first segment, count} + the counter, the segments' texts
     std::vector<unsigned int> class_mask;         // more than 128 classes: the calling thread's bbocr_set_class_mask words, padded to ceil(C / 32)
     DevBuf ctc_mask;                              // ... on the device (uploaded by the sequence stage that reads them)
     int ctc_host_seqs = 0;                        // sequences of this slot's latest call that a CTC_BEAM_DEVICE_WIDE pass left to the host search (bbocr_last_ctc_host_sequences)
@@ -466,7 +474,13 @@ void rec_seq_tiles(const bbocr_ctx* c, RecRun& run);    // rec_quant: run.tiles 
 // where the text of a CTC pass comes from (ctc_route).  CTC_GREEDY_FUSED: greedy over more than 128 classes with Prediction inside the CTC
 // kernel (pred_ctc.hip) -- the pass has no logits.  CTC_BEAM_DEVICE_WIDE: the device search over more than 128 classes (ctc_beam_wide.hip),
 // taken only by a context created with bbocr_config_v2::beam_wide
-enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2, CTC_GREEDY_FUSED = 3, CTC_BEAM_DEVICE_WIDE = 4 };
+// CTC_WORD_HOST / CTC_WORD_DEVICE: decoder='wordbeamsearch' (wordbeam_route below; ctc_wordbeam.cpp / ctc_wordbeam.hip).
+enum { CTC_GREEDY = 0, CTC_BEAM_HOST = 1, CTC_BEAM_DEVICE = 2, CTC_GREEDY_FUSED = 3, CTC_BEAM_DEVICE_WIDE = 4, CTC_WORD_HOST = 5, CTC_WORD_DEVICE = 6 };
+int wordbeam_route(int beam_width, int C, const int* seqs, int nseq);
+// the device half of a word search over sequences already on the device at seqs_dev (ctc_wordbeam.cpp): buffers sized, kernels queued on s;
+// the text lands in c->ctc_beam_idx (row-indexed) / c->ctc_beam_len.  idx_dev null: the rows' arg-max is computed from the probabilities
+void wordbeam_device(bbocr_ctx* c, const float* probs_dev, const int* idx_dev, size_t rows, int C, int cs, const int* seqs, const int* seqs_dev, int nseq,
+                     int beam_width, hipStream_t s);
 // seqs: {first row, T} per sequence (host); fused_ok: the caller holds Prediction's input and pred_ctc_kernel's weights (a 16-bit recognition pass);
 // beam_wide: bbocr_config_v2::beam_wide of the context
 int ctc_route(int beam_width, int C, const int* seqs, int nseq, bool fused_ok = false, bool beam_wide = false);

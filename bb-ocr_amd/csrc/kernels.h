@@ -275,6 +275,25 @@ size_t ctc_beam_lds_bytes(int beam_width, int C, int max_T);
 bool ctc_beam_on_device(int beam_width, int C, int max_T);
 hipError_t launch_ctc_beam(const float* probs, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int max_T, int beam_width, int* out_text,
                            int* out_len, hipStream_t s);
+// decoder='wordbeamsearch' (ctc_wordbeam.cpp states it; word_dict.h: the dictionary).  Host: one sequence / a {first row, T} table; dict null
+// or empty: every word group decodes as ctc_beam_search_host decodes its rows
+struct WdTable;
+void ctc_wordbeam_search_batch(const float* probs, const int* seqs, int nseq, int C, int cs, int beam_width, int space, const WdTable* dict,
+                               std::vector<std::vector<int>>& texts, HostPool* pool = nullptr);
+// ... and on the device (ctc_wordbeam.hip), C <= 128: the table as uploaded (WdSlot slots, byte symbols), word groups from the rows' arg-max
+// (segs {first row, T} x seg_cap, seq_seg {first segment, count} per sequence, *counter their total), one wave per group, then the join into
+// out_text (row-indexed) / out_len.  seg_text (row-indexed like out_text) and seg_len (seg_cap) are the stage in between.  seg_cap: at least
+// the sum of (T + 1) / 2 over the sequences.  Ask ctc_wordbeam_on_device first (width, classes, LDS block of the longest SEQUENCE).
+struct WordDictDev { const void* slots = nullptr; const unsigned char* pool = nullptr; unsigned int nslots = 0, pool_n = 0; int probe = 0; };
+size_t ctc_wordbeam_lds_bytes(int beam_width, int C, int max_T);
+bool ctc_wordbeam_on_device(int beam_width, int C, int max_T);
+hipError_t launch_row_argmax(const float* probs, size_t rows, int C, int cs, int* idx, hipStream_t s);
+hipError_t launch_word_segments(const int* idx, size_t rows, const int* seqs_dev, int nseq, int space, int* segs, int seg_cap, int* seq_seg, int* counter,
+                                hipStream_t s);
+hipError_t launch_ctc_wordbeam(const float* probs, size_t rows, int C, int cs, const int* seqs_dev, int nseq, int max_T, int beam_width, int space,
+                               const WordDictDev& d, const int* segs, int seg_cap, const int* seq_seg, const int* counter, int* seg_len, int* seg_text,
+                               int* out_text, int* out_len, hipStream_t s);
+hipError_t launch_dict_lookup(const WordDictDev& d, const unsigned char* qsym, const int* qoff, int nq, int qtotal, int* found, hipStream_t s);
 // the device search for 128 < C <= BBOCR_REC_CLASSES_MAX (ctc_beam_wide.hip; bbocr_config_v2::beam_wide): ctc_beam_cand_kernel lists every row's
 // candidates (cand_n int32 [rows]: the count; cand [rows][kBeamWideCand] {class, p bits}: the first kBeamWideCand of them, ascending), then
 // ctc_beam_wide_kernel searches one sequence per wave from that list and the two values it gathers from the full row.  Outputs as

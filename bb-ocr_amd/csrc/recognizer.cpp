@@ -359,7 +359,8 @@ void ctc_size(bbocr_ctx* c, size_t rows, int nseq, int cs, int route) {
     c->ctc_pmax.ensure(rows * 4);
     c->ctc_out_idx.ensure(rows * 4);
     c->ctc_out.ensure((size_t)nseq * sizeof(CtcOut));
-    if (route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE) c->ctc_probs.ensure(rows * cs * sizeof(float));
+    if (route == CTC_BEAM_HOST || route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE || route == CTC_WORD_HOST || route == CTC_WORD_DEVICE)
+        c->ctc_probs.ensure(rows * cs * sizeof(float));          // (the word search's own device buffers: wordbeam_device)
     if (route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE) {
         c->ctc_beam_idx.ensure(rows * 4);
         c->ctc_beam_len.ensure((size_t)nseq * 4);
@@ -398,10 +399,12 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     const std::vector<int>&tiles = run.tiles, &seqs = run.seqs;
     const int ntiles = (int)(tiles.size() / 4), nseq = (int)(seqs.size() / 2);
     const int C = rec_classes(c), cs = rec_cs(c);
-    const int route = ctc_route(c->beam_width, C, seqs.data(), nseq, rec_fused_ok(c), rec_beam_wide(c));
+    const int route = c->word_beam ? wordbeam_route(c->beam_width, C, seqs.data(), nseq)
+                                   : ctc_route(c->beam_width, C, seqs.data(), nseq, rec_fused_ok(c), rec_beam_wide(c));
     c->ctc_last_route = route;
-    const bool dev_beam = route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE;       // text and lengths come back, not probabilities
-    const bool fused = route == CTC_GREEDY_FUSED, beam = route == CTC_BEAM_HOST || dev_beam;
+    const bool dev_beam = route == CTC_BEAM_DEVICE || route == CTC_BEAM_DEVICE_WIDE || route == CTC_WORD_DEVICE;   // text and lengths come back, not probabilities
+    const bool host_beam = route == CTC_BEAM_HOST || route == CTC_WORD_HOST;               // the probabilities cross to the host's search
+    const bool fused = route == CTC_GREEDY_FUSED, beam = host_beam || dev_beam;
     if (!fused) c->seq_logits.ensure(rows_pad * cs * 4);
     c->seq_tables.ensure((tiles.size() + seqs.size()) * 4);
     int* tiles_dev = (int*)c->seq_tables.p;
@@ -416,7 +419,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     const CtcOut* oo = (const CtcOut*)((const char*)c->ctc_pin.p + oo_off);
     const int* bidx = (const int*)((const char*)c->ctc_pin.p + bi_off);
     const int* blen = (const int*)((const char*)c->ctc_pin.p + bl_off);
-    std::vector<float> probs(route == CTC_BEAM_HOST ? rows * cs : 0);      // only the host route moves the probabilities off the card
+    std::vector<float> probs(host_beam ? rows * cs : 0);      // only a host route moves the probabilities off the card
     std::vector<std::vector<int>> beam_texts;
     if (!c->seq_t1) { HIPCHK(hipEventCreate(&c->seq_t1)); HIPCHK(hipEventCreate(&c->seq_t2)); }
     {
@@ -451,7 +454,9 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
         if (dev_beam) {
             int max_T = 0;
             for (int i = 0; i < nseq; ++i) max_T = std::max(max_T, seqs[2 * i + 1]);
-            if (route == CTC_BEAM_DEVICE_WIDE)
+            if (route == CTC_WORD_DEVICE)          // word groups from the row kernel's arg-max, one search per group, the join: all behind the row kernel
+                wordbeam_device(c, (const float*)c->ctc_probs.p, (const int*)c->ctc_idx.p, rows, C, cs, seqs.data(), seqs_dev, nseq, c->beam_width, ss);
+            else if (route == CTC_BEAM_DEVICE_WIDE)
                 HIPCHK(launch_ctc_beam_wide((const float*)c->ctc_probs.p, rows, C, cs, seqs_dev, nseq, max_T, c->beam_width, (int*)c->ctc_cand_n.p,
                                             (int*)c->ctc_cand.p, (int*)c->ctc_beam_idx.p, (int*)c->ctc_beam_len.p, ss));
             else
@@ -459,7 +464,7 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
                                        (int*)c->ctc_beam_len.p, ss));
             HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bi_off, c->ctc_beam_idx.p, rows * 4, hipMemcpyDeviceToHost, ss));
             HIPCHK(hipMemcpyAsync((char*)c->ctc_pin.p + bl_off, c->ctc_beam_len.p, (size_t)nseq * 4, hipMemcpyDeviceToHost, ss));
-        } else if (route == CTC_BEAM_HOST) {
+        } else if (host_beam) {
             HIPCHK(hipMemcpyAsync(probs.data(), c->ctc_probs.p, probs.size() * sizeof(float), hipMemcpyDeviceToHost, ss));
         }
         HIPCHK(hipEventRecord(c->seq_t2, ss));
@@ -471,13 +476,15 @@ static void rec_finish(bbocr_ctx* c, RecRun& run, std::vector<std::vector<int>>&
     c->times[5] += ctc_ms;                           // CTC kernels + read-back (device span) ...
     t0 = clk::now();                                 // ... + the host decode below
     if (route == CTC_BEAM_HOST) ctc_beam_search_batch(probs.data(), seqs.data(), nseq, C, cs, c->beam_width, beam_texts, &host_pool(c));
+    if (route == CTC_WORD_HOST)
+        ctc_wordbeam_search_batch(probs.data(), seqs.data(), nseq, C, cs, c->beam_width, c->wd_host->space, c->wd_host, beam_texts, &host_pool(c));
     if (route == CTC_BEAM_DEVICE_WIDE) {   // the probabilities are still resident: only the overflowed sequences' rows cross the link
         hipStream_t ss = (c->seq_stream && c->feat_ev) ? c->seq_stream : c->stream;
         c->ctc_host_seqs += ctc_beam_wide_fallback(c, ss, (const float*)c->ctc_probs.p, seqs.data(), nseq, C, cs, c->beam_width, blen, beam_texts);
     }
     for (int i = 0; i < nseq; ++i) {       // the confidence stays the greedy path's for every route
         const int k = run.seq_k[i];
-        if (route == CTC_BEAM_HOST || (route == CTC_BEAM_DEVICE_WIDE && blen[i] < 0)) confs[k] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), texts[k]);
+        if (host_beam || (route == CTC_BEAM_DEVICE_WIDE && blen[i] < 0)) confs[k] = ctc_decode(oo[i], beam_texts[i].data(), (int)beam_texts[i].size(), texts[k]);
         else if (dev_beam) confs[k] = ctc_decode(oo[i], bidx + seqs[2 * i], std::clamp(blen[i], 0, seqs[2 * i + 1]), texts[k]);
         else confs[k] = ctc_decode(oo[i], oidx + seqs[2 * i], oo[i].len, texts[k]);
     }
@@ -591,9 +598,11 @@ static void rec_check_params(bbocr_ctx* c, const bbocr_params& p) {
         c->class_mask.assign((size_t)(rec_classes(c) + 31) / 32, 0u);
         for (int i = 0; i < n && i < (int)c->class_mask.size(); ++i) c->class_mask[i] = w[i];
     }
-    if (p.decoder != BBOCR_DECODER_GREEDY && p.decoder != BBOCR_DECODER_BEAMSEARCH) fail(BBOCR_ERR_ARG, "unknown decoder");
-    if (p.decoder == BBOCR_DECODER_BEAMSEARCH && p.beam_width <= 0) fail(BBOCR_ERR_ARG, "beam_width must be positive");
-    c->beam_width = p.decoder == BBOCR_DECODER_BEAMSEARCH ? p.beam_width : 0;
+    if (p.decoder != BBOCR_DECODER_GREEDY && p.decoder != BBOCR_DECODER_BEAMSEARCH && p.decoder != BBOCR_DECODER_WORDBEAMSEARCH) fail(BBOCR_ERR_ARG, "unknown decoder");
+    if (p.decoder != BBOCR_DECODER_GREEDY && p.beam_width <= 0) fail(BBOCR_ERR_ARG, "beam_width must be positive");
+    if (p.decoder == BBOCR_DECODER_WORDBEAMSEARCH && !c->wd_host) fail(BBOCR_ERR_ARG, "decoder wordbeamsearch needs a dictionary (bbocr_set_dictionary)");
+    c->beam_width = p.decoder != BBOCR_DECODER_GREEDY ? p.beam_width : 0;
+    c->word_beam = p.decoder == BBOCR_DECODER_WORDBEAMSEARCH;
 }
 
 // Reader.recognize's per-box branch: horizontal boxes first, then free boxes, page by page

@@ -550,6 +550,60 @@ def resolve_recog_network(lang_list, recog_network="standard", model_storage_dir
             "lang_list": list(lang_list)}
 
 
+def load_dictionary(source, character):
+    """The word list of ``decoder='wordbeamsearch'`` as the library takes it, without a device.  ``source``: a path, a list of paths (every
+    item an ``os.PathLike`` or the name of an existing file) or an iterable of words; ``None``: the ``os.pathsep``-separated paths of
+    ``BBOCR_DICTIONARY`` (unset: no dictionary, ``None`` is returned).  Files hold one word per line and are read as ``utf-8-sig`` with
+    ``splitlines()``, upstream's way.  Words are mapped to class indices through ``character`` (the model's list, class 0 the blank); empty
+    lines, duplicates and words with a character the model lacks (or the space, which separates words, or more than 1024 characters) are
+    dropped and counted.  A model without ``' '`` has no word separator: ``ValueError``.
+
+    -> ``{"words", "symbols" (uint16), "word_off" (int32, [words + 1]), "space", "dropped_foreign", "dropped_empty",
+    "dropped_duplicates", "unmatchable_repeats"}``; ``unmatchable_repeats`` counts kept words with a doubled letter, which a decoded text
+    equals only through a labelling that holds a blank symbol between the pair (the collapse removes adjacent repeats from the labelling)."""
+    if source is None:
+        env = os.environ.get("BBOCR_DICTIONARY", "")
+        source = [p for p in env.split(os.pathsep) if p]
+        if not source:
+            return None
+        paths = source
+    elif isinstance(source, (str, os.PathLike)):
+        paths = [source]
+    else:
+        source = list(source)
+        is_paths = bool(source) and all(isinstance(x, os.PathLike) or (isinstance(x, str) and os.path.isfile(x)) for x in source)
+        paths = source if is_paths else None
+    if paths is not None:
+        lines = []
+        for path in paths:
+            with open(path, "r", encoding="utf-8-sig") as fh:
+                lines += fh.read().splitlines()
+    else:
+        lines = [str(w) for w in source]
+    if " " not in character[1:]:
+        raise ValueError("decoder='wordbeamsearch' needs a model with a ' ' class: it separates the word groups")
+    cls = {ch: i for i, ch in enumerate(character) if i and len(ch) == 1}
+    space = cls[" "]
+    out = {"words": [], "space": space, "dropped_foreign": 0, "dropped_empty": 0, "dropped_duplicates": 0, "unmatchable_repeats": 0}
+    seen, symbols, word_off = set(), [], [0]
+    for w in lines:
+        if not w:
+            out["dropped_empty"] += 1
+        elif w in seen:
+            out["dropped_duplicates"] += 1
+        elif len(w) > 1024 or any(ch == " " or ch not in cls for ch in w):
+            out["dropped_foreign"] += 1
+        else:
+            seen.add(w)
+            out["words"].append(w)
+            symbols += [cls[ch] for ch in w]
+            word_off.append(len(symbols))
+            out["unmatchable_repeats"] += any(a == b for a, b in zip(w, w[1:]))
+    out["symbols"] = np.array(symbols, dtype=np.uint16)
+    out["word_off"] = np.array(word_off, dtype=np.int32)
+    return out
+
+
 def text_table(character):
     """``bbocr_result.text_idx`` -> text for any character list: a uint32 array of code points when every class is ONE code point (a numpy
     take and one utf-32 decode serve a whole result), else the list itself (a class of several code points: joined box by box)."""
@@ -680,7 +734,8 @@ class Reader:
                  detect_network="craft", recog_network="standard", download_enabled=True, detector=True, recognizer=True,
                  verbose=True, quantize=True, cudnn_benchmark=False, weights=None, device_index=None, det_sub_batch=0,
                  rec_max_cols=0, precision=None, call_slots=0, host_threads=None, device_decode=None, rec_quant=None, character=None,
-                 lang_char=None, beam_wide=None, png_decode=None, tiff_decode=None, gif_decode=None, bmp_decode=None, **_ignored):
+                 lang_char=None, beam_wide=None, png_decode=None, tiff_decode=None, gif_decode=None, bmp_decode=None, dictionary=None,
+                 **_ignored):
         import torch
 
         net = resolve_recog_network(lang_list, recog_network, model_storage_directory, user_network_directory, character, lang_char)
@@ -747,6 +802,10 @@ class Reader:
         self.lang_char = net["lang_char"]
         self._wide = len(self.character) > 128                                  # the class mask travels through bbocr_set_class_mask
         self._text_table = None if self.character is CHARACTER else text_table(self.character)   # None: the English latin-1 fast path
+        # the word list of decoder='wordbeamsearch' (None: the files of BBOCR_DICTIONARY; neither: no dictionary, and the decoder stays
+        # NotImplementedError as ever)
+        self._dictionary = None
+        self.set_dictionary(dictionary)
         if isinstance(weights, str) and weights == "empty":
             # multi-GPU receiver: the packed plans are laid out without values and filled by import_weights_blob (dist.broadcast_packed)
             for which, wanted in ((0, detector), (1, recognizer)):
@@ -888,6 +947,8 @@ class Reader:
             p.rotation_info[i] = int(a)
         if decoder == "beamsearch":          # BBOCR_DECODER_BEAMSEARCH
             p.decoder, p.beam_width = 1, int(kw.get("beamWidth", 5))
+        if decoder == "wordbeamsearch":      # BBOCR_DECODER_WORDBEAMSEARCH, over set_dictionary's words
+            p.decoder, p.beam_width = 2, int(kw.get("beamWidth", 5))
         return p
 
     def _to_dev(self, arr):
@@ -967,10 +1028,32 @@ class Reader:
             return [[item[1] for item in page] for page in out]
         return out
 
+    def set_dictionary(self, dictionary):
+        """Set or replace the word list of ``decoder='wordbeamsearch'`` (``load_dictionary``'s sources; ``None``: the files of
+        ``BBOCR_DICTIONARY``).  No source, or one without a usable word, clears it: the decoder is ``NotImplementedError`` again."""
+        d = load_dictionary(dictionary, self.character)
+        if d is None and self._dictionary is None:
+            return
+        if d is not None and len(d["words"]):
+            self._check(self._lib.bbocr_set_dictionary(self._h, d["symbols"].ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                       d["word_off"].ctypes.data_as(C.POINTER(C.c_int)), len(d["words"]), d["space"]))
+        else:
+            self._check(self._lib.bbocr_set_dictionary(self._h, None, None, 0, 0))
+        self._dictionary = d if d is not None and len(d["words"]) else None
+
+    def dictionary_stats(self):
+        """``{"words", "dropped_foreign", "unmatchable_repeats", "slots", "longest_probe"}`` of the dictionary in use (zeros without one):
+        the words kept, the lines dropped for a character the model lacks, the kept words with a doubled letter -- matched only through
+        a labelling with a blank symbol between the pair, as the collapse removes adjacent repeats from the labelling -- and the device table's size and longest probe run."""
+        w, sl, pr, un = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._check(self._lib.bbocr_dictionary_stats(self._h, C.byref(w), C.byref(sl), C.byref(pr), C.byref(un)))
+        return {"words": w.value, "dropped_foreign": self._dictionary["dropped_foreign"] if self._dictionary else 0,
+                "unmatchable_repeats": un.value, "slots": sl.value, "longest_probe": pr.value}
+
     def last_ctc_route(self):
         """Where the text of this thread's last recognise / readtext call came from (bbocr_last_ctc_route): 0 greedy, 1 beam search on the host,
         2 beam search on the device, 3 greedy with Prediction inside the CTC kernel (more than 128 classes, 16-bit modes), 4 beam search on the
-        device over more than 128 classes (beam_wide), -1 no pass yet"""
+        device over more than 128 classes (beam_wide), 5 word beam search on the host, 6 word beam search on the device, -1 no pass yet"""
         route = C.c_int(-1)
         self._check(self._lib.bbocr_last_ctc_route(self._h, C.byref(route)))
         return int(route.value)
@@ -1811,6 +1894,56 @@ class Reader:
                                                 probs_dev.shape[1], int(beam_width), off, idx))
         return [idx[off[i]:off[i + 1]] for i in range(n)]
 
+    def ctc_wordbeam_device(self, probs_dev, seqs, beam_width, C=97):
+        """The device word beam search alone (bbocr_op_ctc_wordbeam) over this Reader's dictionary: arguments and result as
+        ctc_beam_device's; the text equals bbocr_host_ctc_wordbeam's on the same rows."""
+        import ctypes as ct
+
+        torch = self._torch
+        if (not isinstance(probs_dev, torch.Tensor) or not probs_dev.is_cuda or probs_dev.device.index != self.device_index
+                or probs_dev.dtype != torch.float32 or probs_dev.ndim != 2 or not probs_dev.is_contiguous()):
+            raise ValueError(f"probabilities: expected a contiguous float32 [rows,cs] tensor on {self.device}")
+        flat = [int(v) for s in seqs for v in s]
+        n = len(flat) // 2
+        tab = (ct.c_int * max(len(flat), 1))(*flat)
+        off = (ct.c_int * (n + 1))()
+        idx = (ct.c_int * max(1, sum(max(t, 0) for t in flat[1::2])))()
+        self._check(self._lib.bbocr_op_ctc_wordbeam(self._h, ct.c_void_p(probs_dev.data_ptr()), probs_dev.shape[0], tab, n, int(C),
+                                                    probs_dev.shape[1], int(beam_width), off, idx))
+        return [idx[off[i]:off[i + 1]] for i in range(n)]
+
+    def word_segments_device(self, idx_dev, seqs, space):
+        """The word-group kernel alone (bbocr_op_word_segments): int32 [rows] device tensor of arg-max classes, seqs = [(first row, T)] ->
+        per sequence the list of its groups ``(first row, T)``."""
+        torch = self._torch
+        if (not isinstance(idx_dev, torch.Tensor) or not idx_dev.is_cuda or idx_dev.device.index != self.device_index
+                or idx_dev.dtype != torch.int32 or idx_dev.ndim != 1 or not idx_dev.is_contiguous()):
+            raise ValueError(f"arg-max rows: expected a contiguous int32 [rows] tensor on {self.device}")
+        flat = [int(v) for s in seqs for v in s]
+        n = len(flat) // 2
+        tab = (C.c_int * max(len(flat), 1))(*flat)
+        off = (C.c_int * (n + 1))()
+        segs = (C.c_int * max(2, 2 * sum((max(t, 0) + 1) // 2 for t in flat[1::2])))()
+        self._check(self._lib.bbocr_op_word_segments(self._h, C.c_void_p(idx_dev.data_ptr()), idx_dev.shape[0], tab, n, int(space), off, segs))
+        return [[(segs[2 * k], segs[2 * k + 1]) for k in range(off[i], off[i + 1])] for i in range(n)]
+
+    def dict_lookup_device(self, queries, words=None, n_slots=0):
+        """The dictionary lookup alone (bbocr_op_dict_lookup): queries / words = lists of class-index strings -> ([0 / 1 per query], the
+        table's longest probe run).  words None: this Reader's dictionary as uploaded; else a table built for the call with n_slots slots
+        (0: the default size)."""
+        def flat(strings):
+            off = np.concatenate([[0], np.cumsum([len(w) for w in strings])]).astype(np.int32)
+            sym = np.array([v for w in strings for v in w] or [0], dtype=np.uint16)
+            return sym, off
+
+        qs, qo = flat(queries)
+        ws, wo = flat(words or [])
+        found, probe = (C.c_int * max(1, len(queries)))(), C.c_int(0)
+        u16, i32 = C.POINTER(C.c_uint16), C.POINTER(C.c_int)
+        self._check(self._lib.bbocr_op_dict_lookup(self._h, ws.ctypes.data_as(u16), wo.ctypes.data_as(i32), len(words or []), int(n_slots),
+                                                   qs.ctypes.data_as(u16), qo.ctypes.data_as(i32), len(queries), found, C.byref(probe)))
+        return list(found)[:len(queries)], probe.value
+
     def ctc_beam_wide_device(self, probs_dev, seqs, beam_width, C):
         """The device beam search over more than 128 classes alone (bbocr_op_ctc_beam_wide), on a Reader of such a model: arguments as
         ctc_beam_device's, 128 < C <= _lib.REC_CLASSES_MAX -> (texts, n_host): one list of class indices per sequence, and the number of
@@ -1852,9 +1985,8 @@ class Reader:
         self._check(self._lib.bbocr_recognize(self._h, C.c_void_p(gray_dev.data_ptr()), B, H, W, C.byref(bl), C.byref(p), C.byref(res)))
         return self._collect(res, kw.get("detail", 1))
 
-    @staticmethod
-    def _unsupported(decoder, allowlist, blocklist, rotation_info, paragraph, output_format):
-        if decoder not in ("greedy", "beamsearch"):
+    def _unsupported(self, decoder, allowlist, blocklist, rotation_info, paragraph, output_format):
+        if decoder not in ("greedy", "beamsearch") and not (decoder == "wordbeamsearch" and self._dictionary is not None):
             raise NotImplementedError("decoder='wordbeamsearch' needs easyocr's dictionary files, which are not available offline; "
                                       "'greedy' (the reference's call) and 'beamsearch' are implemented")
         if output_format not in ("standard", "dict", "json"):

@@ -118,7 +118,7 @@ typedef struct bbocr_tensor_desc {
 } bbocr_tensor_desc;
 
 /* keyword arguments of easyocr.Reader.readtext that affect this path (same names, same defaults) */
-enum { BBOCR_DECODER_GREEDY = 0, BBOCR_DECODER_BEAMSEARCH = 1 };
+enum { BBOCR_DECODER_GREEDY = 0, BBOCR_DECODER_BEAMSEARCH = 1, BBOCR_DECODER_WORDBEAMSEARCH = 2 };
 /* Widest beam the device search takes.  The kernel keeps one sequence's whole search in the LDS of one workgroup (64 KB): the step's entry
  * table, beam_width * (1 + C) floats, plus the live labellings as bytes, 2 * beam_width * T (double-buffered), plus under 3 KB of row and
  * beam state.  At width 32 and C = 128 that is 32 * 129 * 4 = 16,512 B of entries and 64 B per time step: T up to 708, above the 639 steps
@@ -127,6 +127,12 @@ enum { BBOCR_DECODER_GREEDY = 0, BBOCR_DECODER_BEAMSEARCH = 1 };
  * labellings as 16-bit symbols, 4 * beam_width * T bytes: at width 32 that is 19,856 B of tables and state and 128 B per time step, T up
  * to 356; at width 5, T up to 3,076.  A longer sequence sends its pass to the host search. */
 #define BBOCR_BEAM_DEVICE_MAX 32
+/* decoder == BBOCR_DECODER_WORDBEAMSEARCH (easyocr's decode_wordbeamsearch for a model without separator characters, over the words of
+ * bbocr_set_dictionary; BBOCR_ERR_ARG on a context without a dictionary): the final candidates of a word group that are tested against the
+ * dictionary -- upstream's wordsearch(classes, ignore_idx, 20, dict_list).  beam_width is used as for BEAMSEARCH.  csrc/ctc_wordbeam.cpp
+ * states the decoder; widths up to BBOCR_BEAM_DEVICE_MAX at up to 128 classes run on the device, everything else on the host, with the
+ * same text. */
+#define BBOCR_WORD_CANDIDATES 20
 
 typedef struct bbocr_params {
     double text_threshold; /* 0.7 */
@@ -303,7 +309,19 @@ int bbocr_set_class_mask(bbocr_ctx* ctx, const uint32_t* words, int n_words);
  * kernel (more than 128 classes, 16-bit precisions: no logits stored), 4 beam search on the device over more than 128 classes
  * (bbocr_config_v2::beam_wide; sequences whose rows overflow the candidate list are searched on the host within the same pass); -1: no such pass (no call, a call without boxes, or the thread's
  * last call was on another context: like bbocr_stage_times this is the record of the calling thread's LAST call) */
+/* 5: word beam search (BBOCR_DECODER_WORDBEAMSEARCH) on the host, 6: word beam search on the device */
 int bbocr_last_ctc_route(bbocr_ctx* ctx, int* route);
+/* The word list of BBOCR_DECODER_WORDBEAMSEARCH, as class-index strings: word i = symbols[word_off[i] .. word_off[i + 1]) (word_off[0] = 0),
+ * space_class the class of ' ' (it separates word groups and joins the words).  Every word is checked first -- symbols in 1 .. C - 1, none
+ * the space class, length 1 .. 1024 -- and a bad table is BBOCR_ERR_ARG with nothing changed.  Duplicates are kept once.  The table is built
+ * (an open-addressing set, csrc/word_dict.h), uploaded once (contexts of at most 128 classes) and kept on the host for the host route.
+ * n_words == 0 clears it.  Waits for the context's call slots, as bbocr_load_weights does. */
+int bbocr_set_dictionary(bbocr_ctx* ctx, const uint16_t* symbols, const int* word_off, int n_words, int space_class);
+/* the context's dictionary (any pointer may be null): words kept, slots of the table, its longest probe run, and the words with two adjacent
+ * equal symbols (the collapse of a labelling removes adjacent repeats: "book" is matched only through a labelling that holds a blank symbol
+ * between the two letters).  All 0
+ * without a dictionary */
+int bbocr_dictionary_stats(bbocr_ctx* ctx, int* words, int* slots, int* longest_probe, int* unmatchable);
 /* the sequences of the calling thread's last recognise / readtext call on this context that route 4 left to the host search (a row of more
  * than 128 candidate classes), summed over the call's sequence passes; 0 on every other route.  On trained models it stays 0 or near it: a
  * count that does not says that the candidate list is too short for the model's rows */
@@ -330,6 +348,15 @@ int bbocr_host_group_boxes(const int* polys, int n, const bbocr_params* p, bbocr
  * (C <= cs classes, class 0 = blank): text_off [n+1], text_idx (<= n*T).  The definition of bbocr_params::decoder == BEAMSEARCH, the path of
  * beams wider than BBOCR_BEAM_DEVICE_MAX, and the yardstick of bbocr_op_ctc_beam */
 int bbocr_host_ctc_beam(const float* probs, int n, int T, int C, int cs, int beam_width, int* text_off, int* text_idx);
+/* CTCLabelConverter.decode_wordbeamsearch for a model without separator characters on host probabilities fp32 [n,T,cs], as
+ * csrc/ctc_wordbeam.cpp states it, over the words symbols / word_off / n_words (as bbocr_set_dictionary takes them; n_words == 0: no word,
+ * every group decodes as BEAMSEARCH decodes its rows): text_off [n+1], text_idx (<= n*T).  Needs no context and no device.  The definition of
+ * bbocr_params::decoder == WORDBEAMSEARCH and the yardstick of bbocr_op_ctc_wordbeam */
+int bbocr_host_ctc_wordbeam(const float* probs, int n, int T, int C, int cs, int beam_width, int space_class, const uint16_t* symbols,
+                            const int* word_off, int n_words, int* text_off, int* text_idx);
+/* the rule by which a WORDBEAMSEARCH pass picks its route (values 5 / 6 of bbocr_last_ctc_route): the host for more than 128 classes, a width
+ * above BBOCR_BEAM_DEVICE_MAX, or a longest SEQUENCE (which bounds every word group) whose LDS block would not fit */
+int bbocr_host_wordbeam_route(int beam_width, int C, const int* seqs, int nseq);
 /* the crop plan of explicit boxes of ONE H x W gray page, as bbocr_op_crops and a recognition pass make it (utils.get_image_list's clamp /
  * four_point_transform geometry and resize target, AlignCollate's content width): hori [n_hori][4] = x_min, x_max, y_min, y_max, free_q
  * [n_free][4][2].  Box k (the horizontal boxes, then the free ones): taken[k] = 0 for a box the pass skips (empty after clamping, a quad
@@ -446,6 +473,20 @@ int bbocr_op_pred_ctc(bbocr_ctx* ctx, const uint16_t* dev_x, size_t rows, const 
  * (see BBOCR_BEAM_DEVICE_MAX) */
 int bbocr_op_ctc_beam(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width,
                       int* text_off, int* text_idx);
+/* the stages of decoder == WORDBEAMSEARCH on the device alone (csrc/ctc_wordbeam.hip).  All arguments are checked before anything is queued;
+ * BBOCR_ERR_ARG leaves every output untouched.
+ * bbocr_op_word_segments: dev_idx int32 [rows] (arg-max rows), seqs {first row, T} -> the word groups of sequence i as {first row, T} pairs
+ * segs[2 * seg_off[i] .. 2 * seg_off[i + 1]) (host arrays: seg_off [nseq + 1], segs with room for sum((T + 1) / 2) pairs).
+ * bbocr_op_dict_lookup: n_q class-index strings (q_symbols / q_off) -> found[q] = 0 / 1 through a DEVICE table: the context's dictionary when
+ * n_words == 0, else a table built for this call from symbols / word_off / n_words (symbols 1 .. 127) with n_slots slots (0: the default,
+ * else a power of two above n_words -- a small one forces long probe runs); *longest_probe (may be null) reports the table's.
+ * bbocr_op_ctc_wordbeam: as bbocr_op_ctc_beam, with the context's dictionary (BBOCR_ERR_ARG without one); the text equals
+ * bbocr_host_ctc_wordbeam's on the same rows, exactly. */
+int bbocr_op_word_segments(bbocr_ctx* ctx, const int* dev_idx, size_t rows, const int* seqs, int nseq, int space_class, int* seg_off, int* segs);
+int bbocr_op_dict_lookup(bbocr_ctx* ctx, const uint16_t* symbols, const int* word_off, int n_words, int n_slots, const uint16_t* q_symbols,
+                         const int* q_off, int n_q, int* found, int* longest_probe);
+int bbocr_op_ctc_wordbeam(bbocr_ctx* ctx, const float* dev_probs, size_t rows, const int* seqs, int nseq, int C, int cs, int beam_width, int* text_off,
+                          int* text_idx);
 /* the device beam search over more than 128 classes alone (the kernels behind decoder == BEAMSEARCH on a context with beam_wide): arguments
  * and outputs as bbocr_op_ctc_beam's, for 128 < C <= BBOCR_REC_CLASSES_MAX on a context created with rec_classes > 128 (beam_wide need not be
  * set).  *n_host (may be NULL): the sequences that had a row of more than 128 candidates and were searched on the host.  The text equals
